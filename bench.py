@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- GraFPrint contrastive training step on N MI355X GPUs of one node (one process per GPU).
 
-    python bench.py [--gpus 1] [--steps 20] [--warmup 5]
+    python bench.py [--gpus 1] [--steps 20] [--warmup 5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,10 +12,19 @@ are randomly initialised (the architecture and shapes are config/grafp.yaml's). 
 
 The headline workload is BASELINE.json's metric: the contrastive step at GLOBAL batch 1024 (1024 / N pairs per GPU,
 global negatives; N = 8 is BASELINE config 3 and the batch fits one GPU, so N = 1 runs the same global batch:
-`scaling: strong`).  Beside it the line carries BASELINE config 2 (256 pairs on one GPU: `config2_batch256`, also as
-one HIP graph and in f32), the weak-scaling variant at N > 1 (256 pairs per GPU), the per-kernel table (HIP events,
-collected in a SEPARATE pass so the headline loop runs without event records), `roofline` for the kernel family with
-the largest measured time, a step-level bytes / time figure, and the retrieval / fingerprinting / augmentation legs.
+`scaling: strong`).  A plain run measures that and nothing else: set-up, W warm-up steps, K timed steps (at N > 1 also
+the same step replayed from HIP graphs, the headline being the faster of the two), the outputs of the last timed step
+if --dump-outputs is given, the line.
+
+With --full the line also carries BASELINE config 2 (256 pairs on one GPU: `config2_batch256`, also as one HIP graph
+and in f32), the weak-scaling variant at N > 1 (256 pairs per GPU), the per-kernel table (HIP events, collected in a
+SEPARATE pass so the headline loop runs without event records), `roofline` for the kernel family with the largest
+measured time, a step-level bytes / time figure, the retrieval / fingerprinting / augmentation legs and the CPU
+baselines.
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64, < 64 MB in all): the
+loss it returned and the state it left (parameters, their gradients, the BatchNorm running statistics; the first two
+as a fixed, seeded sample).  The inputs and initial weights are seeded, so two builds can be compared file by file.
 """
 import argparse
 import contextlib
@@ -53,8 +62,13 @@ def host_threads():
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps of the headline (>= 1)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also every secondary leg: per-kernel pass and roofline, other batch sizes and precisions, "
+                         "retrieval / fingerprinting / augmentation, CPU baselines, collectives (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy")
     ap.add_argument("--global-batch", type=int, default=1024,
                     help="positive pairs per step over all GPUs (BASELINE metric: batch 1024; N = 8 is config 3)")
     ap.add_argument("--batch-per-gpu", type=int, default=None,
@@ -70,7 +84,10 @@ def parse():
     ap.add_argument("--cpu-baseline-seconds", type=float, default=25.0)
     ap.add_argument("--backend", default=None, help="test hook: process-group backend (default nccl = RCCL)")
     ap.add_argument("--local-device", type=int, default=None, help="test hook: device index of every rank (ranks share a GPU)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def kernel_sources_sha16():
@@ -368,6 +385,39 @@ def retrieval_probe(device, cpu_check=True):
     return res
 
 
+# elements per sampled array of --dump-outputs: 16 MB of f32 each
+DUMP_SAMPLE = 1 << 22
+
+
+def flat_sample(tensors, seed):
+    """The tensors flattened and concatenated (f32, on the host): all of it up to DUMP_SAMPLE elements, beyond that the
+    elements at DUMP_SAMPLE fixed positions drawn from `seed` (sorted; the same positions for the same total size)."""
+    flat = torch.cat([t.detach().float().reshape(-1) for t in tensors])
+    if flat.numel() > DUMP_SAMPLE:
+        pos = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(seed)).sort().values
+        flat = flat[pos.to(flat.device)]
+    return flat.cpu().numpy()
+
+
+def step_outputs(model, loss):
+    """What one step hands its caller: the loss it returns (the global mean at N > 1) and the state it leaves behind --
+    parameters after the update, the gradients of that update, the floating-point buffers (BatchNorm running statistics)
+    -- as name -> numpy array, for --dump-outputs."""
+    import numpy as np
+    params = list(model.parameters())
+    return {"loss": np.asarray([float(loss.item())], dtype=np.float64),
+            "params_sample": flat_sample(params, 0),
+            "grads_sample": flat_sample([p.grad if p.grad is not None else torch.zeros_like(p) for p in params], 0),
+            "buffers_sample": flat_sample([b for b in model.buffers() if b.is_floating_point()], 1)}
+
+
+def write_outputs(out_dir, outputs):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def timed_steps(fn, steps, barrier):
     barrier()
     t0 = time.perf_counter()
@@ -401,6 +451,49 @@ def launch_ranks(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     return subprocess.run(cmd, env=env).returncode
+
+
+def kernel_figures(kernels, ms_k, B, args):
+    """--full: `roofline` (the kernel family with the largest measured time), `step_roofline` and `kernels`, from the
+    per-kernel pass."""
+    # the kernel FAMILY with the largest measured time is the roofline's subject, whichever it is
+    dom_name = max(kernels, key=lambda n: kernels[n]["total_ms"]) if kernels else None
+    dom = kernels.get(dom_name, {})
+    roof = {"kernel": dom_name, "bound": dom.get("bound"), "achieved": dom.get("achieved"), "peak": dom.get("peak"),
+            "unit": dom.get("unit"), "frac": dom.get("frac"), "traffic": None, "avg_launch_us": dom.get("avg_us"),
+            "launches": dom.get("calls"),
+            "share_of_step": round(dom.get("total_ms", 0.0) / max(1, args.kernel_steps) / ms_k, 4),
+            "algorithmic_bytes_per_launch": (round(dom["bytes"] / dom["calls"]) if dom.get("bytes") else None),
+            "note": "the hand-written kernel family with the largest total time in the per-kernel pass; achieved = "
+                    "algorithmic bytes (operands read once, results written once; flops for the exact-f32 k-NN) of "
+                    "its launches / their HIP-event time on the launch stream"}
+    if dom_name == "conv1x1_gemm":
+        roof["mfma_frac"] = dom.get("mfma_frac")
+        roof["tflops"] = dom.get("tflops")
+        roof["two_ceiling_frac"] = dom.get("two_ceiling_frac")
+        roof["note"] += "; the family mixes HBM-bound (stages 0-1) and matrix-bound (stages 2-3) shapes: both fractions are given, and two_ceiling_frac = sum over launches of max(bytes / 8 TB/s, flops / 2.5 PFLOP/s) / measured time"
+    # HBM traffic of the dominant kernel comes from separate rocprofv3 --pmc passes over this same command
+    # (FETCH_SIZE and WRITE_SIZE cannot share a pass); their committed summary is read back here.
+    pmc_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", f"pmc_{dom_name}.json")
+    if os.path.exists(pmc_path):
+        with open(pmc_path) as f:
+            pmc = json.load(f)
+        if pmc.get("kernel_sources_sha16") != kernel_sources_sha16():
+            roof["traffic_note"] = ("profiles/pmc_%s.json was collected on other kernel sources (stamp %s): not "
+                                    "reported" % (dom_name, pmc.get("kernel_sources_sha16")))
+        elif pmc.get("batch_per_gpu") == B and pmc.get("dtype") == args.dtype:
+            # gfx950: FETCH_SIZE tallies the 128-B requests of 16 B/lane streams at 64 B -> doubled
+            roof["traffic"] = int((2 * pmc["fetch_kb_per_launch"] + pmc["write_kb_per_launch"]) * 1024)
+            roof["traffic_unit"] = "bytes/launch"
+            roof["traffic_source"] = pmc.get("source")
+    step_bytes = sum(v.get("bytes", 0.0) for v in kernels.values()) / max(1, args.kernel_steps)
+    return {"roofline": roof,
+            "step_roofline": {"bytes_per_step": round(step_bytes), "ms_per_step": round(ms_k, 3),
+                              "achieved": round(step_bytes / (ms_k * 1e-3) / 1e9, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                              "frac": round(step_bytes / (ms_k * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
+                              "note": "sum of the algorithmic bytes of every timed hand-written kernel / wall time of a "
+                                      "step of the per-kernel pass (event records add ~2 % to that step)"},
+            "kernels": {k: {kk: vv for kk, vv in v.items() if kk != "bytes"} for k, v in kernels.items()}}
 
 
 def main():
@@ -454,14 +547,18 @@ def main():
     if world > 1:
         loss = loss.clone()
         dist.all_reduce(loss)
-    # ---- separate pass: HIP events around every hand-written kernel (every rank runs it: the collectives stay aligned)
-    with ops.time_kernels(*KERNEL_NAMES) as timed:
-        t_k, _ = timed_steps(lambda: trainer.step(x_i, x_j), args.kernel_steps, barrier)
-        kernels = summarise_kernels(timed, 2 if args.dtype == "bf16" else 4)
-    ms_k = 1e3 * max_over_ranks(t_k) / max(1, args.kernel_steps)
+    # what the last timed step computed (taken now: every later leg moves the weights again)
+    outputs = step_outputs(model, loss) if args.dump_outputs and rank == 0 else None
+    kernels, ms_k = {}, None
+    if args.full:
+        # ---- separate pass: HIP events around every hand-written kernel (every rank runs it: the collectives stay aligned)
+        with ops.time_kernels(*KERNEL_NAMES) as timed:
+            t_k, _ = timed_steps(lambda: trainer.step(x_i, x_j), args.kernel_steps, barrier)
+            kernels = summarise_kernels(timed, 2 if args.dtype == "bf16" else 4)
+        ms_k = 1e3 * max_over_ranks(t_k) / max(1, args.kernel_steps)
 
     weak = None
-    if world > 1 and B != 256 and args.batch_per_gpu is None:
+    if args.full and world > 1 and B != 256 and args.batch_per_gpu is None:
         # the weak-scaling variant beside the headline: 256 pairs per GPU (BASELINE config 2 on every GPU)
         cfg_w = dict(cfg, bsz_train=256 * world)
         trainer.sync.close()                                   # its gradient hooks must not fire in the next trainer's steps
@@ -478,7 +575,7 @@ def main():
         del tw, xw_i, xw_j
 
     sharded = None
-    if world > 1 and not args.no_retrieval:
+    if args.full and world > 1 and not args.no_retrieval:
         # BASELINE config 5 shape: the fingerprint database sharded across the GPUs (1.25 M x 128 rows per GPU, built
         # on the device; every rank plants its share of the queries in its own shard), one batched search =
         # local exact top-20 + all-gather of the (nq, 20) lists + merge.  Every rank runs the same collectives.
@@ -508,7 +605,7 @@ def main():
 
     # ---- what RCCL itself costs at this world size: the two collectives of a step, timed alone (HIP events, 20 calls) ----
     collectives = None
-    if world > 1:
+    if args.full and world > 1:
         def timed_coll(fn, reps=20):
             fn()
             barrier()
@@ -534,8 +631,10 @@ def main():
 
     # ---- the same data-parallel step replayed from HIP graphs (forward | loss + backward + pack | Adam, the two
     #      collectives eager between them): every rank takes the same path, so the collectives stay aligned ----
-    # (last of the legs: whatever happens here, everything above is already measured)
+    # (last of the legs: whatever happens here, everything above is already measured; part of a plain run too, since
+    #  the headline is the faster of the two forms of the step)
     hip_graph = None
+    graph_outputs = None
     if world > 1 and not args.no_graph:
         try:
             err = None
@@ -548,8 +647,12 @@ def main():
             dist.all_reduce(ok, op=dist.ReduceOp.MIN)
             if float(ok.item()) < 1.0:
                 raise err if err is not None else RuntimeError("step_graph failed on another rank")
-            dt, _ = timed_steps(lambda: trainer.step_graph(x_i, x_j), args.steps, barrier)
+            dt, g_loss = timed_steps(lambda: trainer.step_graph(x_i, x_j), args.steps, barrier)
             dt = max_over_ranks(dt)
+            if args.dump_outputs:
+                g_loss = g_loss.clone()
+                dist.all_reduce(g_loss)
+                graph_outputs = step_outputs(model, g_loss) if rank == 0 else None
             hip_graph = {"value": round(B * world * args.steps / dt, 2), "unit": "clips/s",
                          "ms_per_step": round(1e3 * dt / args.steps, 3), "steps": args.steps,
                          "backward_graphs": len(trainer._graph[1][1]), "gradient_buckets": len(trainer.sync.bounds),
@@ -563,37 +666,6 @@ def main():
 
     if rank == 0:
         clips = B * world * args.steps
-        # the kernel FAMILY with the largest measured time is the roofline's subject, whichever it is
-        dom_name = max(kernels, key=lambda n: kernels[n]["total_ms"]) if kernels else None
-        dom = kernels.get(dom_name, {})
-        roof = {"kernel": dom_name, "bound": dom.get("bound"), "achieved": dom.get("achieved"), "peak": dom.get("peak"),
-                "unit": dom.get("unit"), "frac": dom.get("frac"), "traffic": None, "avg_launch_us": dom.get("avg_us"),
-                "launches": dom.get("calls"),
-                "share_of_step": round(dom.get("total_ms", 0.0) / max(1, args.kernel_steps) / ms_k, 4),
-                "algorithmic_bytes_per_launch": (round(dom["bytes"] / dom["calls"]) if dom.get("bytes") else None),
-                "note": "the hand-written kernel family with the largest total time in the per-kernel pass; achieved = "
-                        "algorithmic bytes (operands read once, results written once; flops for the exact-f32 k-NN) of "
-                        "its launches / their HIP-event time on the launch stream"}
-        if dom_name == "conv1x1_gemm":
-            roof["mfma_frac"] = dom.get("mfma_frac")
-            roof["tflops"] = dom.get("tflops")
-            roof["two_ceiling_frac"] = dom.get("two_ceiling_frac")
-            roof["note"] += "; the family mixes HBM-bound (stages 0-1) and matrix-bound (stages 2-3) shapes: both fractions are given, and two_ceiling_frac = sum over launches of max(bytes / 8 TB/s, flops / 2.5 PFLOP/s) / measured time"
-        # HBM traffic of the dominant kernel comes from separate rocprofv3 --pmc passes over this same command
-        # (FETCH_SIZE and WRITE_SIZE cannot share a pass); their committed summary is read back here.
-        pmc_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", f"pmc_{dom_name}.json")
-        if os.path.exists(pmc_path):
-            with open(pmc_path) as f:
-                pmc = json.load(f)
-            if pmc.get("kernel_sources_sha16") != kernel_sources_sha16():
-                roof["traffic_note"] = ("profiles/pmc_%s.json was collected on other kernel sources (stamp %s): not "
-                                        "reported" % (dom_name, pmc.get("kernel_sources_sha16")))
-            elif pmc.get("batch_per_gpu") == B and pmc.get("dtype") == args.dtype:
-                # gfx950: FETCH_SIZE tallies the 128-B requests of 16 B/lane streams at 64 B -> doubled
-                roof["traffic"] = int((2 * pmc["fetch_kb_per_launch"] + pmc["write_kb_per_launch"]) * 1024)
-                roof["traffic_unit"] = "bytes/launch"
-                roof["traffic_source"] = pmc.get("source")
-        step_bytes = sum(v.get("bytes", 0.0) for v in kernels.values()) / max(1, args.kernel_steps)
         line = {
             "metric": "clips/sec contrastive step @ batch 1024", "value": round(clips / elapsed, 2), "unit": "clips/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -608,14 +680,9 @@ def main():
             "parity": "bf16 mode: every stored activation and the embedding <= 1e-3 relative L2 vs the oracle's "
                       "bf16-storage restatement with inputs held equal, hit rates within 0.5 pt of f32 "
                       "(tests/test_gpu_bf16.py); f32 mode: <= 1e-4 vs the oracle (tests/test_gpu_model.py)",
-            "roofline": roof,
-            "step_roofline": {"bytes_per_step": round(step_bytes), "ms_per_step": round(ms_k, 3),
-                              "achieved": round(step_bytes / (ms_k * 1e-3) / 1e9, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                              "frac": round(step_bytes / (ms_k * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
-                              "note": "sum of the algorithmic bytes of every timed hand-written kernel / wall time of a "
-                                      "step of the per-kernel pass (event records add ~2 % to that step)"},
-            "kernels": {k: {kk: vv for kk, vv in v.items() if kk != "bytes"} for k, v in kernels.items()},
         }
+        if args.full:
+            line.update(kernel_figures(kernels, ms_k, B, args))
         line["step_impl"] = "eager (Trainer.step)"
         if hip_graph is not None:
             line["hip_graph"] = hip_graph
@@ -631,11 +698,15 @@ def main():
                                      "Adam, the all-gather and the bucket all-reduces eager between them, each all-reduce "
                                      "under the backward graphs that follow it); the eager step of the same run is under "
                                      "`eager`, the per-kernel figures come from the eager pass")
+                if graph_outputs is not None:
+                    outputs = graph_outputs
+        if outputs is not None:
+            write_outputs(args.dump_outputs, outputs)
         if collectives is not None:
             line["collectives"] = collectives
         if weak is not None:
             line["weak_scaling_256_per_gpu"] = weak
-        if world == 1 and not args.no_config2:
+        if args.full and world == 1 and not args.no_config2:
             # BASELINE config 3's PER-GPU shape on this one GPU (128 pairs, no collectives): the compute part of one
             # rank of the 8-GPU run, eager and as one HIP graph.  8-GPU scaling >= 6x over the N = 1 line needs this
             # + the z all-gather + the 73.5 MB gradient all-reduce <= ms_per_step / 6.
@@ -745,7 +816,7 @@ def main():
                                                "every activation in f32 with bf16 product operands was measured "
                                                "(tools/mixed_mode_probe.py, profiles/r04_mixed_mode_probe.txt): 0.104 against 0.107 "
                                                "-- the drift is the operand rounding of the products (DESIGN 10.4)"}
-        if world == 1 and not args.no_config2:
+        if args.full and world == 1 and not args.no_config2:
             # BASELINE config 2: 256 pairs on one GPU -- eager, replayed from ONE HIP graph, and in f32
             B2 = 256
             cfg2 = dict(cfg, bsz_train=B2)
@@ -790,7 +861,7 @@ def main():
                                                      "ms_per_step": round(1e3 * dt / n32, 3), "steps": n32,
                                                      "global_batch": B}
                 del t32
-        if world == 1 and not args.no_retrieval:
+        if args.full and world == 1 and not args.no_retrieval:
             # BASELINE config 3/4, generation side: fingerprinting throughput of the forward pass alone (eval mode,
             # log-mel already computed), as generate.py / test_fp.py drive it, 1024 one-second segments per call
             model.eval()
@@ -837,7 +908,7 @@ def main():
             line["fingerprinting"] = fp
             model.train()
             line["retrieval"] = retrieval_probe(device, cpu_check=not args.no_cpu_baseline)
-        if world == 1 and not args.no_augment:
+        if args.full and world == 1 and not args.no_augment:
             # the second view augmented on the device (impulse response + background noise for every
             # clip: ir_prob = noise_prob = 1 as in config/grafp.yaml), synthetic banks: 8 one-second decaying-noise
             # responses, 16 ten-second noise recordings; at 256 clips
@@ -875,27 +946,28 @@ def main():
                 "note": f"{Ba} one-second clips, one-second responses (useful flops 2*sum_t min(t+1, L)), x/noise/out "
                         "once for the mix; step = the 256-pair eager step with both transforms on every clip of view j"}
             del taug
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg, args.cpu_baseline_seconds)
         if sharded is not None:
             line["retrieval_sharded"] = sharded
-        # LAST key of the line (the driver keeps only the final ~2 000 characters of stdout): every kernel family as
-        # [average launch in us, fraction of its roofline] and the handful of step figures the verdict's gates name
-        def pick(obj, *path):
-            for k in path:
-                obj = obj.get(k) if isinstance(obj, dict) else None
-            return obj
-        line["kernels_digest"] = {
-            "kernels_avg_us_frac": {k: [v.get("avg_us"), v.get("frac")] for k, v in kernels.items()},
-            "ms_1024": line["ms_per_step"], "bytes_per_step_gb": round(step_bytes / 1e9, 1),
-            "ms_256": pick(line, "config2_batch256", "ms_per_step"),
-            "ms_256_graph": pick(line, "config2_batch256", "hip_graph", "ms_per_step"),
-            "ms_128": pick(line, "config3_per_gpu_128", "ms_per_step"),
-            "ms_128_graph": pick(line, "config3_per_gpu_128", "hip_graph_ms_per_step"),
-            "ms_128_dp_graphs_rccl1": pick(line, "config3_per_gpu_128", "dp_graphs_rccl_one_rank_ms_per_step"),
-            "retrieval_frac_nq1_nq41_nq4096": [pick(line, "retrieval", "roofline", n, "frac") for n in ("nq1", "nq41", "nq4096")],
-            "retrieval_ms_nq4096": pick(line, "retrieval", "ms_per_batch_nq4096"),
-        }
+        if args.full:
+            # LAST key of the line (a reader may keep only the final ~2 000 characters of stdout): every kernel family as
+            # [average launch in us, fraction of its roofline] and the handful of step figures the verdict's gates name
+            def pick(obj, *path):
+                for k in path:
+                    obj = obj.get(k) if isinstance(obj, dict) else None
+                return obj
+            line["kernels_digest"] = {
+                "kernels_avg_us_frac": {k: [v.get("avg_us"), v.get("frac")] for k, v in kernels.items()},
+                "ms_1024": line["ms_per_step"], "bytes_per_step_gb": round(line["step_roofline"]["bytes_per_step"] / 1e9, 1),
+                "ms_256": pick(line, "config2_batch256", "ms_per_step"),
+                "ms_256_graph": pick(line, "config2_batch256", "hip_graph", "ms_per_step"),
+                "ms_128": pick(line, "config3_per_gpu_128", "ms_per_step"),
+                "ms_128_graph": pick(line, "config3_per_gpu_128", "hip_graph_ms_per_step"),
+                "ms_128_dp_graphs_rccl1": pick(line, "config3_per_gpu_128", "dp_graphs_rccl_one_rank_ms_per_step"),
+                "retrieval_frac_nq1_nq41_nq4096": [pick(line, "retrieval", "roofline", n, "frac") for n in ("nq1", "nq41", "nq4096")],
+                "retrieval_ms_nq4096": pick(line, "retrieval", "ms_per_batch_nq4096"),
+            }
         sys.stdout.flush()
         os.write(line_fd, (json.dumps(line) + "\n").encode())
     if world > 1:

@@ -159,7 +159,9 @@ def main():
     if len(sys.argv) > 3 and sys.argv[3] in ("graph", "graph_rccl1", "graph_rccl1_single", "graph_rccl1_timeline"):
         return graph_mode(out, B, rccl_one_rank=sys.argv[3] != "graph", overlap=sys.argv[3] != "graph_rccl1_single",
                           timeline=sys.argv[3] == "graph_rccl1_timeline")
-    rank, world, device = gdist.init_from_env(backend="gloo", local_device=0)
+    # GRAFP_TEST_RANK_PER_DEVICE=1: rank r on cuda:LOCAL_RANK (a box with a device per rank); otherwise every rank on cuda:0
+    own = os.environ.get("GRAFP_TEST_RANK_PER_DEVICE") == "1"
+    rank, world, device = gdist.init_from_env(backend="gloo", local_device=None if own else 0)
     cfg = load_config()
     cfg["bsz_train"] = B
     torch.manual_seed(1234)

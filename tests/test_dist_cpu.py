@@ -37,6 +37,8 @@ def _oracle_local_loss(z_i, z_j, tau, zi_all, zj_all, row_begin):
 
 
 def _worker(rank, world, port, out):
+    # a CPU test: on a machine that has GPUs too, the ranks still take init_from_env's CPU path and never open a device
+    torch.cuda.is_available = lambda: False
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
     from grafp_amd import dist as gdist

@@ -23,11 +23,13 @@ def _shared_device_env(rank, world):
     return {"ROC_GLOBAL_CU_MASK": shared_device_cu_mask(rank, world, cus)} if world > 1 else {}
 
 
-def _launch(world, out, B, extra=()):
+def _launch(world, out, B, extra=(), own_devices=False):
+    """own_devices: rank r runs on cuda:r (the production layout) instead of every rank sharing cuda:0."""
     procs = []
     for r in range(world):
+        placement = {"GRAFP_TEST_RANK_PER_DEVICE": "1"} if own_devices else _shared_device_env(r, world)
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT="29653", HSA_ENABLE_IPC_MODE_LEGACY="0", **_shared_device_env(r, world))
+                   MASTER_PORT="29653", HSA_ENABLE_IPC_MODE_LEGACY="0", **placement)
         procs.append(subprocess.Popen([sys.executable, os.path.join(HERE, "_dist_gpu_worker.py"), out, str(B), *extra],
                                       env=env,
                                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
@@ -78,12 +80,12 @@ def test_two_ranks_match_one_process(tmp_path):
     assert (wid[:, 0].cpu().reshape(4, 3) == starts[:, None]).all()          # planted runs found, across the boundary
 
 
-def _compare_with_one_process(out, B, world, got):
+def _compare_with_one_process(out, B, world, got, own_devices=False):
     """The ranks' embeddings, loss shares, reduced gradients and gradient norm against ONE process that pushes the `world`
     shards through the model one after the other (tests/_dist_gpu_worker.py reference_mode).  That side runs in a process
     of its own under a CU mask of the ranks' width: the f32 mode's library GEMMs choose their splits by the number of
-    CUs they see."""
-    env = dict(os.environ, **_shared_device_env(0, world))
+    CUs they see (ranks on devices of their own: the whole device, no mask)."""
+    env = dict(os.environ, **({} if own_devices else _shared_device_env(0, world)))
     p = subprocess.run([sys.executable, os.path.join(HERE, "_dist_gpu_worker.py"), out, str(B), "reference", str(world)],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-3000:]
@@ -108,15 +110,15 @@ def _compare_with_one_process(out, B, world, got):
         assert abs(got[r]["grad_norm"] - want_norm) <= 2e-4 * want_norm
 
 
-def _ranks_against_one_process(tmp_path, world, B, tag):
-    """`world` ranks on cuda:0 over gloo, B // world pairs each, against ONE process pushing the shards through the model
-    one after the other (per-replica BatchNorm statistics, as under the reference's DataParallel, train.py:165-168) with
-    the loss over the concatenated batch (train.py:69-71)."""
+def _ranks_against_one_process(tmp_path, world, B, tag, own_devices=False):
+    """`world` ranks over gloo -- all on cuda:0, or with `own_devices` rank r on cuda:r --, B // world pairs each, against
+    ONE process pushing the shards through the model one after the other (per-replica BatchNorm statistics, as under the
+    reference's DataParallel, train.py:165-168) with the loss over the concatenated batch (train.py:69-71)."""
     out = str(tmp_path / tag)
-    _launch(world, out, B)
+    _launch(world, out, B, own_devices=own_devices)
     got = [torch.load(f"{out}.{r}.pt", weights_only=False) for r in range(world)]
     device = torch.device("cuda:0")
-    _compare_with_one_process(out, B, world, got)
+    _compare_with_one_process(out, B, world, got, own_devices=own_devices)
     return got, device
 
 
@@ -127,13 +129,16 @@ def test_two_ranks_at_128_pairs_per_rank(tmp_path):
 
 
 def test_eight_ranks_at_128_pairs_per_rank(tmp_path):
-    """BASELINE config 3 exactly -- global batch 1024 on EIGHT ranks of 128 pairs -- with all eight processes on cuda:0
-    over gloo (288 GB holds eight replicas; RCCL needs eight devices, everything around the collectives is the production
-    code): the rank-major all-gather of 8 x (2, 128, 128) embeddings, row_begin = rank * 128 against 2046 global
-    negatives per row, the SUM of eight flat gradient buffers in arrival-order buckets, and 8-way shard_range + merge +
-    halo rerank on the retrieval side (/root/reference/train.py:69-71,165-168; eval.py:269-290)."""
+    """BASELINE config 3 exactly -- global batch 1024 on EIGHT ranks of 128 pairs -- one rank per device over gloo
+    (everything around the collectives is the production code): the rank-major all-gather of 8 x (2, 128, 128)
+    embeddings, row_begin = rank * 128 against 2046 global negatives per row, the SUM of eight flat gradient buffers in
+    arrival-order buckets, and 8-way shard_range + merge + halo rerank on the retrieval side (the reference's
+    train.py:69-71,165-168; eval.py:269-290).  Eight processes do not share one device here: the test needs eight."""
+    n_dev = torch.cuda.device_count()
+    if n_dev < 8:
+        pytest.skip(f"needs 8 GPUs (one rank per device), found {n_dev}")
     from grafp_amd import ops
-    got, device = _ranks_against_one_process(tmp_path, 8, 1024, "w8")
+    got, device = _ranks_against_one_process(tmp_path, 8, 1024, "w8", own_devices=True)
     gen = torch.Generator().manual_seed(3)
     db = torch.nn.functional.normalize(torch.randn(5000, 128, generator=gen), dim=1)
     q = torch.nn.functional.normalize(db[::97][:20] + 0.05 * torch.randn(20, 128, generator=gen), dim=1)
@@ -215,7 +220,7 @@ def test_bench_two_ranks_one_gpu(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2",
-                        "--warmup", "1", "--global-batch", "32", "--kernel-steps", "1",
+                        "--warmup", "1", "--full", "--global-batch", "32", "--kernel-steps", "1",
                         "--no-cpu-baseline", "--backend", "gloo", "--local-device", "0"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1200)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])

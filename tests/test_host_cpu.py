@@ -216,22 +216,13 @@ def test_augmentation_banks_and_cpu_branch(tmp_path):
 
 
 _IMPORT_REFERENCE_SCRIPTS = r'''
-import importlib.util, os, sys, types
+import importlib.util, os, sys
 sys.dont_write_bytecode = True
-REF, ROOT = "/root/reference", sys.argv[1]
+REF, ROOT = sys.argv[2], sys.argv[1]
 sys.path.insert(0, ROOT)
-
-def stub(name, **attrs):
-    m = types.ModuleType(name); m.__dict__.update(attrs); sys.modules[name] = m; return m
-# third-party packages of the reference's requirements.txt that this image lacks: inert stand-ins (decode / logging only)
-ta = stub("torchaudio", set_audio_backend=lambda *a, **k: None, load=None)
-stub("torchaudio.transforms"); ta.transforms = sys.modules["torchaudio.transforms"]
-import torch.utils
-stub("torch.utils.tensorboard", SummaryWriter=type("SummaryWriter", (), {"__init__": lambda self, *a, **k: None}))
-stub("soundfile"); stub("prettytable", PrettyTable=type("PrettyTable", (), {})); stub("librosa")
 assert "faiss" not in sys.modules
 
-sys.path.insert(0, REF)                        # a checkout of the reference: its scripts, util.py, modules/data.py
+sys.path.insert(0, REF)                        # the stand-in checkout: its scripts, util.py, modules/data.py
 import grafp_amd.dropin as dropin
 names = dropin.install()
 assert "faiss" in names and "util" not in names and "modules" not in names, names
@@ -271,21 +262,45 @@ print("reference scripts import through the alias route")
 '''
 
 
+def _reference_standin(root):
+    """A stand-in checkout of the reference under `root`, built from tests/golden/reference_imports.json (the project
+    imports of its train.py, test_fp.py, generate.py and eval.py, in source order; tests/golden/make_reference_imports.py):
+    each script holds exactly those import statements, and the two host-side files the scripts keep their own --
+    util.py and modules/data.py -- define the names imported from them."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "reference_imports.json")) as f:
+        imports = json.load(f)
+    own = {"util": os.path.join(root, "util.py"), "modules.data": os.path.join(root, "modules", "data.py")}
+    defined = {m: set() for m in own}
+    os.makedirs(os.path.join(root, "modules"))
+    open(os.path.join(root, "modules", "__init__.py"), "w").close()
+    for fname, stmts in imports.items():
+        lines = []
+        for module, names in stmts:
+            lines.append(f"import {module}" if names is None else f"from {module} import {', '.join(names)}")
+            if module in own:
+                defined[module].update(n for n in names if n != "*")
+        with open(os.path.join(root, fname), "w") as f:
+            f.write("\n".join(lines) + "\n")
+    for module, path in own.items():
+        with open(path, "w") as f:
+            f.write("".join(f"def {n}(*args, **kwargs):\n    raise NotImplementedError\n\n\n" for n in sorted(defined[module])))
+
+
 def test_reference_scripts_import_through_the_alias_route(tmp_path):
     """with grafp_amd.dropin.install() -- which now also registers a `faiss` stand-in -- the reference's
     train.py, test_fp.py, generate.py (and its own eval.py) IMPORT unchanged from a checkout of the reference, and the
     names they bind are this package's: GraphEncoder, SimCLR, ntxent_loss, GPUTransformNeuralfp, eval_faiss, get_index,
-    create_fp_db, create_dummy_db, faiss.IndexFlatL2.  util.py and modules/data.py stay the reference's own host-side
-    files.  torchaudio / tensorboard / soundfile / prettytable / librosa (absent from this image) are inert stubs of the
-    TEST.  Container-only: nothing of the reference travels to the GPU box."""
+    create_fp_db, create_dummy_db, faiss.IndexFlatL2.  util.py and modules/data.py stay the checkout's own host-side
+    files.  The checkout is a stand-in with the scripts' recorded import statements (_reference_standin)."""
     import subprocess
     import sys
-    if not os.path.isdir("/root/reference"):
-        pytest.skip("the reference checkout is only mounted in the build container")
+    ref = str(tmp_path / "reference")
+    _reference_standin(ref)
     script = tmp_path / "import_ref.py"
     script.write_text(_IMPORT_REFERENCE_SCRIPTS)
-    res = subprocess.run([sys.executable, str(script), ROOT], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
-                         timeout=600, cwd=str(tmp_path))
+    res = subprocess.run([sys.executable, str(script), ROOT, ref], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                         text=True, timeout=600, cwd=str(tmp_path))
     assert res.returncode == 0 and "import through the alias route" in res.stdout, res.stdout[-3000:]
 
 
