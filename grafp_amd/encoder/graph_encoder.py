@@ -5,6 +5,8 @@ forward keeps nodes as (B,C,N), builds every block's graph with the HIP k-NN ker
 convolutions as plain GEMMs (see _dense.py).  12 Grapher+FFN blocks, k-NN graph rebuilt in each; N
 halves at each of the 3 Downsample modules (1024 -> 512 -> 256 -> 128 nodes).
 """
+import contextlib
+
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -93,6 +95,7 @@ class GraphEncoder(nn.Module):
         self.num_blocks = sum(self.blocks)
         self.conv = "mr"                      # the reference ignores its `conv` argument (:123)
         self._lowp = None                     # cached low-precision copies of the 1x1 conv weights (ops.lowp_weights)
+        self._lowp_hold = None                # inside one_weight_preparation(): False, then True once prepared
         n_nodes = cfg["n_mels"] * cfg["n_frames"] // cfg["peak_stride"]
 
         self.stem = nn.Sequential(nn.Conv2d(in_channels, self.channels[0], kernel_size=1, bias=False),
@@ -121,6 +124,21 @@ class GraphEncoder(nn.Module):
                     m.bias.data.zero_()
                     m.bias.requires_grad = True
 
+    @contextlib.contextmanager
+    def one_weight_preparation(self):
+        """Every forward pass inside the block uses the low-precision weights the FIRST one prepared: the later ones
+        neither rewrite the shared buffers nor advance their generation, so the backward passes of all of them stay
+        valid (SimCLR's sequential views: two encoder forwards of one model forward, nothing can change the weights
+        between them).  Outside the block every forward under autocast prepares them anew."""
+        if self._lowp_hold is not None:                    # nested: the outer block decides
+            yield
+            return
+        self._lowp_hold = False
+        try:
+            yield
+        finally:
+            self._lowp_hold = None
+
     def forward(self, x, views=1):
         """x (B, C_in, N) node features -> (B, 1024).  Internally every activation is a (C, B, N) matrix.
         views > 1: the batch holds that many equally sized views stacked along B; BatchNorm keeps separate batch
@@ -132,7 +150,10 @@ class GraphEncoder(nn.Module):
                 # (self.proj is not in the list: the readout runs in f32 on the pooled means)
                 self._lowp = ops.lowp_weights([m for m in self.modules() if isinstance(m, nn.Conv2d)
                                                and m.kernel_size == (1, 1) and m is not self.proj])
-            self._lowp.refresh(torch.get_autocast_dtype("cuda"))
+            if not self._lowp_hold:
+                self._lowp.refresh(torch.get_autocast_dtype("cuda"))
+                if self._lowp_hold is not None:
+                    self._lowp_hold = True
         elif self._lowp is not None:
             self._lowp.clear()
         with deferred_counters():

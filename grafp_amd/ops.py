@@ -996,7 +996,6 @@ def flush_wgrad_reduce():
     ends and by whoever reads a gradient before that (dist.GradSync packs a bucket while backward is still running)."""
     global _WGRAD_PENDING
     q = _WGRAD_PENDING
-    _WGRAD_DEFERRED_IDS.clear()
     if not q:
         return
     _WGRAD_PENDING = []
@@ -1013,7 +1012,9 @@ def flush_wgrad_reduce():
 def defer_wgrad_reduce():
     """Inside the block (a backward pass) the bf16 weight gradients only run their split-K kernels; the partial sums of
     all layers are reduced together when the block ends (or at flush_wgrad_reduce()): ~60 launches fewer per step, the
-    same bits.  The returned gradient tensors must not be READ inside the block without a flush."""
+    same bits.  The returned gradient tensors must not be READ inside the block without a flush.  Which weights produced
+    a gradient in the block (_WGRAD_DEFERRED_IDS) is remembered until the OUTERMOST block ends, across flushes and across
+    several backward passes inside it (see _may_defer)."""
     global _WGRAD_PENDING
     if _WGRAD_PENDING is not None:                # nested: the outer block flushes
         yield
@@ -1068,30 +1069,37 @@ def _wgrad_bf16(g, x, cout, cin, groups, M, views=1, pro_tab=None, pro_act=ACT_N
 conv1x1_wgrad = _wgrad_bf16
 
 
-_WGRAD_DEFERRED_IDS = set()  # weights whose gradient is queued unreduced in the running defer_wgrad_reduce() block
+# weights that produced a gradient in the running defer_wgrad_reduce() block -- deferred or not (the name is older than that
+# rule), in any backward pass inside it; only the end of the outermost block clears it (a flush does not: the weights'
+# .grad may still be about to be summed)
+_WGRAD_DEFERRED_IDS = set()
 
 
 def _may_defer(w):
     """A weight gradient may leave backward() with its split-K partial sums still unreduced (defer_wgrad_reduce) only if
-    nothing can READ it before the flush: the weight is a leaf whose .grad is None (AccumulateGrad then takes the tensor
-    over as it is -- with an existing .grad it would ADD the unreduced memory into it: gradient accumulation without
-    zero()), it carries no tensor hook (a hook receives the gradient inside backward), every post-accumulate hook on it is
-    GradSync's (which flushes before it packs a bucket; anybody else's would read unreduced memory), and it is the FIRST
-    use of this weight in the pass (a weight shared by two layers gets its two gradients summed by autograd in front of
-    AccumulateGrad: the second one -- and with it the first, flushed -- must be reduced by then).  Everything else reduces
-    immediately: slower, never wrong."""
-    if w is None or w.grad is not None or getattr(w, "_backward_hooks", None) or torch.is_grad_enabled():
+    nothing can READ it before the flush: it is the FIRST gradient of this weight in the running block (a weight shared by
+    two layers gets its two gradients summed by autograd in front of AccumulateGrad, and a second backward pass inside
+    the block ADDS into the .grad the first one left: every later use flushes what is queued -- the first use among it --
+    and reduces at once; the set of weights seen survives flushes, so an order A B A B cannot defer B twice), the weight
+    is a leaf whose .grad is None (AccumulateGrad then takes the tensor over as it is -- with an existing .grad it would
+    ADD the unreduced memory into it: gradient accumulation without zero()), it carries no tensor hook (a hook receives
+    the gradient inside backward) and every post-accumulate hook on it is GradSync's (which flushes before it packs a
+    bucket; anybody else's would read unreduced memory).  Everything else reduces immediately: slower, never wrong.
+    Only a deferred gradient may be produced in place (_GRAD_TARGET_OF), so a weight seen before never gets a target."""
+    if w is None:
+        return False
+    if _WGRAD_PENDING is not None:
+        if id(w) in _WGRAD_DEFERRED_IDS:
+            flush_wgrad_reduce()                        # the earlier uses' partial sums: reduced before anyone adds to them
+            return False
+        _WGRAD_DEFERRED_IDS.add(id(w))
+    if w.grad is not None or getattr(w, "_backward_hooks", None) or torch.is_grad_enabled():
         return False                                    # (create_graph = True keeps grad mode on inside backward)
     hooks = getattr(w, "_post_accumulate_grad_hooks", None)
     if hooks:
         from .dist import GradSync
         if not all(isinstance(getattr(h, "__self__", None), GradSync) for h in hooks.values()):
             return False
-    if id(w) in _WGRAD_DEFERRED_IDS:
-        flush_wgrad_reduce()                            # the first use's partial sums: reduced before autograd adds the two
-        return False
-    if _WGRAD_PENDING is not None:
-        _WGRAD_DEFERRED_IDS.add(id(w))
     return True
 
 

@@ -5,6 +5,7 @@ format -- a checkpoint written by /root/reference/train.py:212-220 loads, and on
 with `step()` replaced for what /root/reference/train.py:174 uses: no weight decay, no amsgrad, no maximize.  Anything else
 raises -- there is no second implementation behind it.
 """
+import contextlib
 import ctypes
 
 import torch
@@ -32,10 +33,17 @@ class Adam(torch.optim.Adam):
         if not ps:
             return None                                          # a group of frozen parameters: nothing to update
         cached = self._tables[gi] if self._tables is not None and gi < len(self._tables) else None
-        if cached is not None and cached["n"] == len(ps) and cached["p"][0] == ps[0].data_ptr() and all(
-                self.state[p].get("step") is not None and self.state[p]["step"].data_ptr() == cached["steps"].data_ptr() + 4 * i
-                for i, p in ((0, ps[0]), (len(ps) - 1, ps[-1]))):
-            return cached
+        if cached is not None and cached["n"] == len(ps):
+            # every pointer in the table is checked: a parameter's .data or a moment in the state replaced between steps
+            # (load_state_dict, a user's assignment) would otherwise be updated at its OLD address
+            state = self.state
+            sts = [state[p] for p in ps]
+            if (cached["pp"] == [p.data_ptr() for p in ps]
+                    and cached["mp"] == [st["exp_avg"].data_ptr() for st in sts]
+                    and cached["vp"] == [st["exp_avg_sq"].data_ptr() for st in sts]
+                    and all(sts[i].get("step") is not None
+                            and sts[i]["step"].data_ptr() == cached["steps"].data_ptr() + 4 * i for i in (0, len(ps) - 1))):
+                return cached
         dev = ps[0].device
         for p in ps:
             if p.dtype != torch.float32 or not p.is_cuda or not p.is_contiguous():
@@ -54,10 +62,11 @@ class Adam(torch.optim.Adam):
             st["step"] = steps[i]
         n = len(ps)
         vp = ctypes.c_void_p
-        tab = {"n": n, "ps": ps, "steps": steps,
-               "p": (vp * n)(*[p.data_ptr() for p in ps]),
-               "m": (vp * n)(*[self.state[p]["exp_avg"].data_ptr() for p in ps]),
-               "v": (vp * n)(*[self.state[p]["exp_avg_sq"].data_ptr() for p in ps]),
+        pp = [p.data_ptr() for p in ps]
+        mp = [self.state[p]["exp_avg"].data_ptr() for p in ps]
+        vq = [self.state[p]["exp_avg_sq"].data_ptr() for p in ps]
+        tab = {"n": n, "ps": ps, "steps": steps, "pp": pp, "mp": mp, "vp": vq,
+               "p": (vp * n)(*pp), "m": (vp * n)(*mp), "v": (vp * n)(*vq),
                "s": (vp * n)(*[steps.data_ptr() + 4 * i for i in range(n)]),
                "numel": (ctypes.c_int64 * n)(*[p.numel() for p in ps]),
                "g": (vp * n)(), "sub": {}}
@@ -74,7 +83,6 @@ class Adam(torch.optim.Adam):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        stream = ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
         vp = ctypes.c_void_p
         for gi, group in enumerate(self.param_groups):
             if group.get("weight_decay") or group.get("amsgrad") or group.get("maximize"):
@@ -111,9 +119,33 @@ class Adam(torch.optim.Adam):
                     raise RuntimeError("grafp_amd.optim.Adam: contiguous f32 gradients only")
                 g_arr[i] = g.data_ptr()
             lr = group["lr"]
-            lr_dev = vp(lr.data_ptr()) if torch.is_tensor(lr) and lr.is_cuda else None
+            dev = tab["steps"].device
+            lr_dev = None
+            if torch.is_tensor(lr):
+                if lr.numel() != 1:
+                    raise ValueError(f"grafp_amd.optim.Adam: a tensor learning rate holds ONE value, not {lr.numel()}")
+                if lr.is_cuda:
+                    if lr.device != dev:
+                        raise RuntimeError(f"grafp_amd.optim.Adam: the learning rate lives on {lr.device}, the "
+                                           f"parameters on {dev}")
+                    if lr.dtype != torch.float32:    # the kernel reads 4 bytes of f32 (a captured step: read at replay)
+                        lr = lr.to(torch.float32)
+                    lr_dev = vp(lr.data_ptr())
             beta1, beta2 = group["betas"]
-            check(lib.grafp_adam_multi_f32(sub["p"], g_arr, sub["m"], sub["v"], sub["s"], sub["numel"], n, lr_dev,
-                                           0.0 if lr_dev is not None else float(lr), float(beta1), float(beta2),
-                                           float(group["eps"]), stream), "adam_multi")
+            # the parameters' device and its current stream, whichever device is current
+            with torch.cuda.device(dev) if dev.index != torch.cuda.current_device() else contextlib.nullcontext():
+                stream = vp(torch._C._cuda_getCurrentRawStream(dev.index))
+                check(lib.grafp_adam_multi_f32(sub["p"], g_arr, sub["m"], sub["v"], sub["s"], sub["numel"], n, lr_dev,
+                                               0.0 if lr_dev is not None else float(lr), float(beta1), float(beta2),
+                                               float(group["eps"]), stream), "adam_multi")
         return loss
+
+    # -- pickling (copy.deepcopy, torch.save of the optimizer object) ---------------------------------------------------
+    def __getstate__(self):
+        state = super().__getstate__()
+        state.pop("_tables", None)               # ctypes pointer arrays: rebuilt on the next step
+        return state
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self._tables = None

@@ -5,7 +5,10 @@ running statistics advanced twice).  Here both views travel as ONE stacked batch
 extractor, k-NN graph, max-relative) is indifferent to it, every GEMM sees twice the columns (one weight-gradient
 GEMM per layer instead of two, no gradient-accumulation adds), and the fused BatchNorm kernel keeps the per-view
 statistics and the two running-stat updates (`groups=2`) -- same numbers, half the launches.  Set
-`fuse_views = False` for the literal sequential order."""
+`fuse_views = False` for the literal sequential order (under autocast the two encoder passes share ONE preparation of
+the low-precision weights, see GraphEncoder.one_weight_preparation)."""
+import contextlib
+
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -37,6 +40,8 @@ class SimCLR(nn.Module):
             B = x_i.shape[0]
             h, z = self.embed(torch.cat((x_i, x_j), dim=0), views=2)
             return h[:B], h[B:], z[:B], z[B:]
-        h_i, z_i = self.embed(x_i)
-        h_j, z_j = self.embed(x_j)
+        hold = getattr(self.encoder, "one_weight_preparation", None)
+        with hold() if hold is not None else contextlib.nullcontext():
+            h_i, z_i = self.embed(x_i)
+            h_j, z_j = self.embed(x_j)
         return h_i, h_j, z_i, z_j

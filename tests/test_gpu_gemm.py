@@ -430,6 +430,174 @@ def test_deferred_reduction_only_when_nothing_can_read_the_gradient_first():
     assert not ops._WGRAD_DEFERRED_IDS
 
 
+# weights used more than once per block: (R, K, groups, M, views) -- plain, grouped, ragged column range (from SHAPES)
+_SHARED_SHAPES = [(128, 64, 1, 8192, 1), (128, 128, 4, 4096, 2), (64, 64, 1, 128 * 2 * 37, 2)]
+
+
+class _FlushInBackward(torch.autograd.Function):
+    """Identity whose backward flushes the queued weight-gradient reductions: a reader in the middle of backward, as
+    dist.GradSync packing a complete bucket."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        from grafp_amd import ops
+        ops.flush_wgrad_reduce()
+        return g
+
+
+def _shared_case(R, K, groups, M, views, order, seed):
+    """Leaf weights (one per letter of `order`), one bf16 operand per use, one upstream gradient per use and pass."""
+    gen = torch.Generator().manual_seed(seed)
+    names = sorted(set(order) - {"|"})
+    w0 = {c: (0.2 * torch.randn(R, K // groups, generator=gen)).to(DEV) for c in names}
+    uses = [c for c in order if c != "|"]
+    xs = [_rand((K, M), seed + 10 + i, 1.0, 0.2) for i in range(len(uses))]
+    ups = [[_rand((R, M), seed + 100 * (p + 1) + i).float() for i in range(len(uses))] for p in range(2)]
+    return w0, xs, ups
+
+
+def _shared_loss(ws, order, xs, ups, groups, views, only=None):
+    """sum over the uses of <up, conv_bn_act(x, W)>; '|' puts a _FlushInBackward on the partial sum so far (its backward
+    runs after that of every later use and before that of every earlier one).  only: that use alone."""
+    from grafp_amd import ops
+    R = next(iter(ws.values())).shape[0]
+    gamma, beta = torch.ones(R, device=DEV), torch.zeros(R, device=DEV)
+    loss, i = None, 0
+    for c in order:
+        if c == "|":
+            loss = loss if loss is None else _FlushInBackward.apply(loss)
+            continue
+        if only is None or only == i:
+            rm, rv = torch.zeros(R, device=DEV), torch.ones(R, device=DEV)
+            z = ops.conv_bn_act(xs[i], ws[c], gamma, beta, rm, rv, True, act=ops.ACT_RELU, conv_groups=groups,
+                                views=views)
+            t = (z.float() * ups[i]).sum()
+            loss = t if loss is None else loss + t
+        i += 1
+    return loss
+
+
+def _shared_grads(w0, order, xs, ups, groups, views, defer, passes=1, flat=False):
+    """.grad of every weight after `passes` backward passes, inside one defer_wgrad_reduce() block or without one;
+    flat: under dist.GradSync(force_flat=True) (no process group: nothing is all-reduced), so the first gradient of each
+    weight may be produced in its slice of the flat buffer.  -> ({name: grad}, {name: flat slice} or None)"""
+    import contextlib
+    from grafp_amd import dist as gdist, ops
+    ws = {c: w.clone().requires_grad_(True) for c, w in w0.items()}
+    sync = gdist.GradSync(list(ws.values()), force_flat=True) if flat else None
+    try:
+        if sync is not None:
+            assert not sync._reduce and ops._GRAD_TARGET_OF is not None
+            sync.zero()
+        with ops.defer_wgrad_reduce() if defer else contextlib.nullcontext():
+            for p in range(passes):
+                _shared_loss(ws, order, xs, ups[p], groups, views).backward()
+        assert ops._WGRAD_PENDING is None and not ops._WGRAD_DEFERRED_IDS
+        slices = None
+        if sync is not None:
+            sync.finish()
+            slices = {c: sync._view[id(w)].clone() for c, w in ws.items()}
+            assert all(w.grad.data_ptr() == sync._view[id(w)].data_ptr() for w in ws.values())
+    finally:
+        if sync is not None:
+            sync.close()
+    assert ops._GRAD_TARGET_OF is None
+    return {c: w.grad.clone() for c, w in ws.items()}, slices
+
+
+def _count_deferred(monkeypatch):
+    """Counts the weight gradients whose reduction was queued: every flush records the queue length it reduces."""
+    from grafp_amd import ops
+    real, counted = ops.flush_wgrad_reduce, []
+
+    def counting_flush():
+        counted.append(len(ops._WGRAD_PENDING or []))
+        real()
+    monkeypatch.setattr(ops, "flush_wgrad_reduce", counting_flush)
+    return counted
+
+
+def _single_use_f64(w0, order, xs, ups_pass, groups, views):
+    """Per weight: the float64 sum of its gradients, each use differentiated ALONE (no deferral block)."""
+    want = {c: torch.zeros(w.shape, dtype=torch.float64, device=DEV) for c, w in w0.items()}
+    uses = [c for c in order if c != "|"]
+    for i, c in enumerate(uses):
+        ws = {k: w.clone().requires_grad_(True) for k, w in w0.items()}
+        _shared_loss(ws, order, xs, ups_pass, groups, views, only=i).backward()
+        want[c] += ws[c].grad.double()
+    return want
+
+
+def _assert_close_f64(got, want, what):
+    scale = float(want.abs().max())
+    err = float((got.double() - want).abs().max())
+    assert scale > 0 and err <= 1e-6 * scale, (what, err, scale)
+
+
+@pytest.mark.parametrize("flat", [False, True])
+@pytest.mark.parametrize("order", ["ABAB", "ABBA", "AAA", "ABCCBA"])
+@pytest.mark.parametrize("R,K,groups,M,views", _SHARED_SHAPES)
+def test_deferred_weight_gradients_of_shared_weights(R, K, groups, M, views, order, flat, monkeypatch):
+    """Weights used more than once in one backward pass inside ops.defer_wgrad_reduce(): only the FIRST gradient of each
+    weight may stay unreduced; a later one flushes and reduces at once, also after a flush in between (A B A B: the flush
+    of A's second use must not forget B, or B's second gradient is queued too and autograd adds unreduced memory --
+    under the flat buffer the same slice twice).  Every .grad equals the run without a deferral block bit for bit and
+    the float64 sum of the per-use gradients; each weight's first gradient is still deferred; flat: every slice of the
+    flat buffer holds the gradient after finish()."""
+    w0, xs, ups = _shared_case(R, K, groups, M, views, order, 70)
+    want, _ = _shared_grads(w0, order, xs, ups, groups, views, defer=False)
+    want64 = _single_use_f64(w0, order, xs, ups[0], groups, views)
+    counted = _count_deferred(monkeypatch)
+    got, slices = _shared_grads(w0, order, xs, ups, groups, views, defer=True, flat=flat)
+    for c in w0:
+        assert torch.isfinite(got[c]).all(), c
+        assert torch.equal(got[c], want[c]), c
+        _assert_close_f64(got[c], want64[c], c)
+        if flat:
+            assert torch.equal(slices[c], want[c]), c
+    assert sum(counted) == len(w0), counted              # one deferred reduction per weight: its first gradient
+
+
+@pytest.mark.parametrize("order", ["A", "ABAB"])
+@pytest.mark.parametrize("R,K,groups,M,views", _SHARED_SHAPES)
+def test_deferred_weight_gradients_of_two_backward_passes_in_one_block(R, K, groups, M, views, order, monkeypatch):
+    """Gradient accumulation inside ONE defer_wgrad_reduce() block: the second pass finds .grad set by the first, whose
+    reduction is still queued -- it must flush before AccumulateGrad adds to it (otherwise the sum is made of unreduced
+    memory and the flush at the end of the block overwrites it with the first pass's gradient: the second is lost).
+    .grad equals the two passes without the block bit for bit and the float64 sum of the two single-pass gradients."""
+    w0, xs, ups = _shared_case(R, K, groups, M, views, order, 80)
+    want, _ = _shared_grads(w0, order, xs, ups, groups, views, defer=False, passes=2)
+    one = [_shared_grads(w0, order, xs, [ups[p]], groups, views, defer=False)[0] for p in range(2)]
+    counted = _count_deferred(monkeypatch)
+    got, _ = _shared_grads(w0, order, xs, ups, groups, views, defer=True, passes=2)
+    for c in w0:
+        assert torch.isfinite(got[c]).all(), c
+        assert torch.equal(got[c], want[c]), c
+        _assert_close_f64(got[c], one[0][c].double() + one[1][c].double(), c)
+    assert sum(counted) == len(w0), counted              # the first pass's first gradients; nothing of the second pass
+
+
+@pytest.mark.parametrize("order", ["A|A", "AB|BA"])
+@pytest.mark.parametrize("R,K,groups,M,views", _SHARED_SHAPES)
+def test_deferred_weight_gradients_with_a_flush_between_two_uses(R, K, groups, M, views, order, monkeypatch):
+    """A flush in the middle of backward (what GradSync does when a bucket is complete) between two uses of the same
+    weight: the second use must still be reduced at once -- the flush does not make the weight new again."""
+    w0, xs, ups = _shared_case(R, K, groups, M, views, order, 90)
+    want, _ = _shared_grads(w0, order, xs, ups, groups, views, defer=False)
+    want64 = _single_use_f64(w0, order, xs, ups[0], groups, views)
+    counted = _count_deferred(monkeypatch)
+    got, _ = _shared_grads(w0, order, xs, ups, groups, views, defer=True)
+    for c in w0:
+        assert torch.isfinite(got[c]).all(), c
+        assert torch.equal(got[c], want[c]), c
+        _assert_close_f64(got[c], want64[c], c)
+    assert sum(counted) == len(w0) and len(counted) >= 2, counted
+
+
 @pytest.mark.parametrize("R,K,M", [(64, 64, 8192), (256, 64, 16384), (64, 256, 131072), (1024, 256, 4096), (512, 2048, 1024),
                                    (128, 96, 128 * 37), (2048, 512, 2560)])
 def test_split_bf16_product_of_the_f32_mode(R, K, M):

@@ -1344,3 +1344,114 @@ def test_adam_multi_tensor_vs_torch(dev):
         Adam(mine, lr=1e-3, weight_decay=0.1)
     with pytest.raises(RuntimeError):
         Adam([torch.nn.Parameter(torch.zeros(4))], lr=1e-3).step()          # a CPU parameter: no fallback
+
+
+def _adam_pair(dev, lr, seed, sizes=(3, 64, 4095, 4097, 1000, 257, 8192 + 5)):
+    from grafp_amd.optim import Adam
+    g = torch.Generator().manual_seed(seed)
+    init = [torch.randn(n, generator=g) for n in sizes]
+    mine = [torch.nn.Parameter(t.clone().to(dev)) for t in init]
+    ref = [torch.nn.Parameter(t.clone().to(dev)) for t in init]
+    return mine, ref, Adam(mine, lr=lr), g
+
+
+def _adam_grads(g, mine, ref, step):
+    for i, (p, q) in enumerate(zip(mine, ref)):
+        gr = (torch.randn(p.numel(), generator=g) * (10.0 ** ((i + step) % 4 - 2))).to(p.device)
+        p.grad, q.grad = gr.clone().view_as(p), gr.clone().view_as(q)
+
+
+def _adam_close(a, b, mine, ref, what):
+    """The bars of test_adam_multi_tensor_vs_torch: parameters and both moments to 2e-6 of the tensor's scale."""
+    for i, (p, q) in enumerate(zip(mine, ref)):
+        scale = float(q.detach().abs().max()) + 1e-12
+        assert float((p.detach() - q.detach()).abs().max()) <= 2e-6 * scale + 1e-9, (what, i)
+        sa, sb = a.state[p], b.state[q]
+        assert float(sa["step"]) == float(sb["step"]), (what, i)
+        for k in ("exp_avg", "exp_avg_sq"):
+            sk = float(sb[k].abs().max()) + 1e-30
+            assert float((sa[k] - sb[k]).abs().max()) <= 2e-6 * sk, (what, i, k)
+
+
+def test_adam_learning_rate_tensor_dtype_and_size(dev):
+    """A float64 device learning rate gives the update of the same float value (the kernel reads an f32: the tensor is
+    converted, not reinterpreted); a learning-rate tensor of more than one element is refused."""
+    mine, ref, a, g = _adam_pair(dev, torch.tensor(3e-3, dtype=torch.float64, device=dev), 21)
+    b = torch.optim.Adam(ref, lr=3e-3, foreach=False, fused=False)
+    for step in range(3):
+        _adam_grads(g, mine, ref, step)
+        a.step()
+        b.step()
+        _adam_close(a, b, mine, ref, ("f64 lr", step))
+    with pytest.raises(ValueError):                           # (torch's constructor already refuses it)
+        _adam_pair(dev, torch.tensor([1e-3, 2e-3], device=dev), 22)
+    mine2, _, a2, _ = _adam_pair(dev, 1e-3, 22)
+    a2.param_groups[0]["lr"] = torch.tensor([1e-3, 2e-3], device=dev)      # ... but not a group edited afterwards
+    for p in mine2:
+        p.grad = torch.ones_like(p)
+    before = [p.detach().clone() for p in mine2]
+    with pytest.raises(ValueError, match="ONE value"):
+        a2.step()
+    assert all(torch.equal(p.detach(), q) for p, q in zip(mine2, before))
+
+
+def test_adam_follows_replaced_parameter_and_moment_storage(dev):
+    """Between steps a MIDDLE parameter's .data and another parameter's state['exp_avg'] are replaced by new tensors (the
+    old ones are kept alive and must not be written to): the following steps update the new storage and match torch."""
+    mine, ref, a, g = _adam_pair(dev, 1e-3, 23)
+    b = torch.optim.Adam(ref, lr=1e-3, foreach=False, fused=False)
+    _adam_grads(g, mine, ref, 0)
+    a.step()
+    b.step()
+    old_p = mine[3].data
+    mine[3].data = old_p.clone()
+    old_m = a.state[mine[4]]["exp_avg"]
+    a.state[mine[4]]["exp_avg"] = old_m.clone()
+    keep_p, keep_m = old_p.clone(), old_m.clone()
+    for step in (1, 2):
+        _adam_grads(g, mine, ref, step)
+        a.step()
+        b.step()
+        _adam_close(a, b, mine, ref, ("replaced", step))
+    assert torch.equal(old_p, keep_p) and torch.equal(old_m, keep_m)
+
+
+def test_adam_deepcopy_and_save_after_a_step(dev):
+    """copy.deepcopy(opt) after a step works and the copy then steps exactly as the original; torch.save of the optimizer
+    object and of its state_dict both succeed."""
+    import copy
+    import io
+    mine, ref, a, g = _adam_pair(dev, torch.tensor(1e-3, device=dev), 24)
+    _adam_grads(g, mine, ref, 0)
+    a.step()
+    c = copy.deepcopy(a)
+    mine_c = c.param_groups[0]["params"]
+    assert all(p.data_ptr() != q.data_ptr() for p, q in zip(mine, mine_c))
+    for step in (1, 2):
+        _adam_grads(g, mine, ref, step)
+        for p, q in zip(mine, mine_c):
+            q.grad = p.grad.clone()
+        a.step()
+        c.step()
+        for p, q in zip(mine, mine_c):
+            assert torch.equal(p.detach(), q.detach()), step
+            for k in ("exp_avg", "exp_avg_sq", "step"):
+                assert torch.equal(a.state[p][k], c.state[q][k]), (step, k)
+    torch.save(a, io.BytesIO())
+    torch.save(a.state_dict(), io.BytesIO())
+
+
+def test_adam_parameters_on_another_device_than_the_current_one():
+    """Parameters on device 1 while device 0 is current: the update runs on THEIR device's stream and matches torch."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two visible GPUs")
+    d1 = torch.device("cuda:1")
+    with torch.cuda.device(0):
+        mine, ref, a, g = _adam_pair(d1, 1e-3, 25)
+        b = torch.optim.Adam(ref, lr=1e-3, foreach=False, fused=False)
+        for step in range(3):
+            _adam_grads(g, mine, ref, step)
+            a.step()
+            b.step()
+            torch.cuda.synchronize(d1)
+            _adam_close(a, b, mine, ref, ("device 1", step))

@@ -36,26 +36,36 @@ def _rel_l2(got, want):
     return (np.linalg.norm(got - want, axis=-1) / np.linalg.norm(want, axis=-1)).max()
 
 
-def test_simclr_forward_vs_oracle_with_equal_edges(dev):
+def _simclr_forward_vs_oracle_with_equal_edges(dev, fuse_views):
     """f32 parity bar: with the k-NN edges held equal (replayed in the oracle), every embedding agrees to
-    1e-4 relative L2 (BASELINE bar: 1e-3), train and eval mode."""
+    1e-4 relative L2 (BASELINE bar: 1e-3), train and eval mode; stacked views and the sequential order."""
     from oracle import model as om
     cfg, model = _filled_model(dev)
+    model.fuse_views = fuse_views
     xi, xj = simclr_inputs()
     for train in (True, False):
         model.train(train)
         sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
         with RecordedGraphs() as rg, torch.no_grad():
             h_i, h_j, z_i, z_j = model(xi.to(dev), xj.to(dev))
-        assert len(rg.graphs) == 12                 # one graph per block over the two stacked views
+        assert len(rg.graphs) == (12 if fuse_views else 24)   # one graph per block over the two stacked views
         with torch.no_grad():
-            o = om.simclr_forward(sd, xi, xj, train, idx_fn=rg.replay_fn())
+            o = om.simclr_forward(sd, xi, xj, train, idx_fn=rg.replay_fn(views=2 if fuse_views else 1))
         for got, want in zip((h_i, h_j, z_i, z_j), o):
             assert _rel_l2(got, want) <= 1e-4
         assert rg.flips <= 200                      # near-ties only: <= 0.2% of the ~98k node decisions
         if train:
             np.testing.assert_allclose(model.encoder.stem[1].running_mean.cpu().numpy(),
                                        sd["encoder.stem.1.running_mean"].numpy(), rtol=1e-5, atol=1e-6)
+
+
+def test_simclr_forward_vs_oracle_with_equal_edges(dev):
+    _simclr_forward_vs_oracle_with_equal_edges(dev, True)
+
+
+def test_simclr_forward_vs_oracle_with_equal_edges_sequential_views(dev):
+    """SimCLR.fuse_views = False: the two views one after the other, every weight used twice per pass."""
+    _simclr_forward_vs_oracle_with_equal_edges(dev, False)
 
 
 def test_simclr_forward_matches_reference_golden(dev):
@@ -88,12 +98,14 @@ def test_simclr_forward_matches_reference_golden(dev):
     assert float(cos.min()) > 0.97, cos
 
 
-def test_train_step_vs_oracle_with_equal_edges(dev):
+def _train_step_vs_oracle_with_equal_edges(dev, fuse_views):
     """One full step (fwd + NT-Xent + bwd) against the oracle's autograd with edges held equal: loss 1e-5,
-    every parameter gradient within 3e-2 relative L2 (median 8e-3)."""
+    every parameter gradient within 3e-2 relative L2 (median 8e-3).  Both the stacked views and the literal sequential
+    order (SimCLR.fuse_views = False: every weight used twice per pass, 24 graphs already in view-major order)."""
     from grafp_amd.simclr.ntxent import ntxent_loss
     from oracle import model as om
     cfg, model = _filled_model(dev)
+    model.fuse_views = fuse_views
     model.train()
     xi, xj = simclr_inputs()
     sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
@@ -102,9 +114,10 @@ def test_train_step_vs_oracle_with_equal_edges(dev):
             v.requires_grad_(True)
     with RecordedGraphs() as rg:
         _, _, z_i, z_j = model(xi.to(dev), xj.to(dev))
+    assert len(rg.graphs) == (12 if fuse_views else 24)
     loss = ntxent_loss(z_i, z_j, cfg)
     loss.backward()
-    _, _, oz_i, oz_j = om.simclr_forward(sd, xi, xj, True, idx_fn=rg.replay_fn())
+    _, _, oz_i, oz_j = om.simclr_forward(sd, xi, xj, True, idx_fn=rg.replay_fn(views=2 if fuse_views else 1))
     oloss = om.ntxent(oz_i, oz_j, cfg["tau"])
     oloss.backward()
     np.testing.assert_allclose(loss.item(), oloss.item(), rtol=1e-4)
@@ -122,6 +135,15 @@ def test_train_step_vs_oracle_with_equal_edges(dev):
     rows.sort(reverse=True)
     assert rows[0][0] <= 3e-2, rows[:5]          # earliest layers accumulate every downstream mask flip
     assert np.median([r[0] for r in rows]) <= 8e-3
+
+
+def test_train_step_vs_oracle_with_equal_edges(dev):
+    _train_step_vs_oracle_with_equal_edges(dev, True)
+
+
+def test_train_step_vs_oracle_with_equal_edges_sequential_views(dev):
+    """SimCLR.fuse_views = False: the two views one after the other, every weight used twice per pass."""
+    _train_step_vs_oracle_with_equal_edges(dev, False)
 
 
 def test_train_step_matches_reference_golden(dev):
@@ -309,6 +331,15 @@ def test_db_writers(dev, tmp_path):
 
 
 def test_trainer_step_graph_equals_eager(dev):
+    _step_graph_equals_eager(dev, True)
+
+
+def test_trainer_step_graph_equals_eager_sequential_views(dev):
+    """SimCLR.fuse_views = False: the same bars for the step that runs the two views one after the other."""
+    _step_graph_equals_eager(dev, False)
+
+
+def _step_graph_equals_eager(dev, fuse_views):
     """Trainer.step_graph (whole step replayed from one HIP graph): from the SAME weights and optimizer state, a
     replayed step returns the loss an eager forward pass computes on the new batch and leaves the parameters where
     an eager step leaves them."""
@@ -319,6 +350,7 @@ def test_trainer_step_graph_equals_eager(dev):
     cfg["bsz_train"] = 16
     torch.manual_seed(7)
     model = build_model(cfg, device=dev)
+    model.fuse_views = fuse_views
     tr = Trainer(cfg, model, dev, amp_dtype=None)
     tr.step_graph(*synthetic_batch(16, 50, dev))                  # 3 eager warm-up steps, capture, first replay
 
@@ -354,6 +386,83 @@ def test_trainer_step_graph_equals_eager(dev):
         assert abs(loss_g - want_loss) <= 1e-5 * max(1.0, abs(want_loss))
         d_e, d_g = p_e - p_0, p_g - p_0
         assert float(d_e.norm()) > 0 and float((d_g - d_e).norm() / d_e.norm()) < 0.05     # atomics: not bit-equal
+
+
+def _bf16_step(dev, fuse_views, dp_graphs, pairs=16, seed=5):
+    """One eager bf16 Trainer.step from seeded weights and batch -> (loss, {name: grad}, {name: parameter after Adam})."""
+    from grafp_amd.train import Trainer, build_model, synthetic_batch
+    from grafp_amd.util import load_config
+    cfg = load_config()
+    cfg["bsz_train"] = pairs
+    torch.manual_seed(seed)
+    model = build_model(cfg, device=dev)
+    model.fuse_views = fuse_views
+    tr = Trainer(cfg, model, dev, amp_dtype=torch.bfloat16, lr=2e-4, data_parallel_graphs=dp_graphs)
+    try:
+        loss = tr.step(*synthetic_batch(pairs, 200, dev))
+        grads = {n: p.grad.detach().clone() for n, p in model.named_parameters() if p.grad is not None}
+        params = {n: p.detach().clone() for n, p in model.named_parameters()}
+    finally:
+        tr.sync.close()
+    return loss.clone(), grads, params
+
+
+def _deferred_count(monkeypatch):
+    """Counts the weight gradients whose reduction was queued (every flush records the queue length it reduces)."""
+    from grafp_amd import ops
+    real, counted = ops.flush_wgrad_reduce, []
+
+    def counting_flush():
+        counted.append(len(ops._WGRAD_PENDING or []))
+        real()
+    monkeypatch.setattr(ops, "flush_wgrad_reduce", counting_flush)
+    return counted
+
+
+# weight gradients the fused bf16 step defers (the 1x1 convolutions whose weight is a leaf; counted on the MI355X before
+# the bookkeeping of shared weights changed -- a fix for them must not cost the fused path a single deferral)
+_FUSED_DEFERRED = 60
+
+
+@pytest.mark.parametrize("dp_graphs", [False, True], ids=["grad_sync", "flat_buffer"])
+def test_bf16_sequential_views_step_with_deferred_reductions(dev, monkeypatch, dp_graphs):
+    """bf16 Trainer.step with SimCLR.fuse_views = False: every encoder weight is used twice per pass (its two gradients
+    summed by autograd), the low-precision weight copies are prepared once per model forward.  Against the same step with
+    ops.defer_wgrad_reduce a null context: every gradient and every parameter after Adam bit-equal and finite; against
+    the fused step on the same weights and batch: every gradient within a relative-L2 bar (a deferral bug is O(1) or
+    NaN; measured on the MI355X at 16 pairs: every weight gradient within 3.4e-2, median 1.1e-2, bars below at 2x).  flat_buffer: data_parallel_graphs=True on one process -- the flat gradient buffer and in-place targets.
+    The fused step itself still defers _FUSED_DEFERRED weight gradients."""
+    import contextlib
+    from grafp_amd import ops
+    counted = _deferred_count(monkeypatch)
+    loss_f, grads_f, _ = _bf16_step(dev, True, dp_graphs)
+    print("fused bf16 step: deferred weight gradients", sum(counted))
+    assert sum(counted) == _FUSED_DEFERRED, counted
+    del counted[:]
+    loss_s, grads_s, params_s = _bf16_step(dev, False, dp_graphs)
+    assert sum(counted) > 0, counted                      # the first gradient of each weight is still deferred
+    monkeypatch.setattr(ops, "defer_wgrad_reduce", contextlib.nullcontext)
+    loss_n, grads_n, params_n = _bf16_step(dev, False, dp_graphs)
+    assert torch.isfinite(loss_s) and torch.equal(loss_s, loss_n)
+    assert set(grads_s) == set(grads_n) == set(grads_f) and len(grads_s) > 200
+    for n in grads_n:
+        assert torch.isfinite(grads_s[n]).all(), n
+        assert torch.equal(grads_s[n], grads_n[n]), n
+    for n in params_n:
+        assert torch.equal(params_s[n], params_n[n]), n
+    # sequential against fused: the same step up to rounding (conv biases in front of a train-mode BatchNorm have a zero
+    # gradient: tensors below 1e-4 of the largest norm are compared on that absolute scale, as in the f32 oracle test)
+    gnorm = max(float(g.norm()) for g in grads_f.values())
+    rows = sorted(((float((grads_s[n] - grads_f[n]).norm()) / max(float(grads_f[n].norm()), 1e-4 * gnorm), n)
+                   for n in grads_f), reverse=True)
+    print("bf16 sequential vs fused: loss", float(loss_s), float(loss_f), "relative L2 per gradient, largest", rows[:5])
+    # bars: twice what the MI355X measured (the step is bit-reproducible): loss 8e-8 relative (one f32 rounding step);
+    # every .weight (1x1 convolutions, BatchNorm scales) <= 3.4e-2; median 1.1e-2; any tensor 1.40 -- the largest are
+    # the BatchNorm shifts of the first blocks, sums over all columns of a bf16 gradient that cancel to a small norm
+    assert abs(float(loss_s) - float(loss_f)) <= 1.6e-7 * abs(float(loss_f))
+    assert max(r for r, n in rows if n.endswith(".weight")) <= 7e-2, [r for r in rows if r[1].endswith(".weight")][:5]
+    assert rows[len(rows) // 2][0] <= 2.3e-2, rows[len(rows) // 2]
+    assert rows[0][0] <= 2.8, rows[:5]
 
 
 def test_step_graph_follows_the_scheduler_and_restores_on_failure(dev, monkeypatch):

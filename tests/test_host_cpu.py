@@ -324,3 +324,54 @@ def test_optimizer_refuses_what_the_path_does_not_use():
     w.grad = torch.ones(4)
     with pytest.raises(RuntimeError):                   # a CPU parameter: there is no CPU fallback behind step()
         opt.step()
+
+
+@pytest.mark.parametrize("order", ["ABAB", "ABBA", "AAA", "ABCCBA"])
+def test_deferral_bookkeeping_first_use_of_each_weight_only(order, monkeypatch):
+    """ops._may_defer inside defer_wgrad_reduce(): exactly the FIRST gradient of each weight in the block may stay
+    unreduced; every later one flushes the queue first and is reduced at once -- also after a flush (A B A B: the flush
+    of A's second use must not forget that B was used), so autograd never adds into unreduced memory.  CPU leaf
+    tensors under no_grad: the queue stays empty, so a flush launches nothing; flushes are counted."""
+    from grafp_amd import ops
+    flushes = []
+    real = ops.flush_wgrad_reduce                            # counted, and still run: the queue is empty, no launch
+    monkeypatch.setattr(ops, "flush_wgrad_reduce", lambda: (flushes.append(1), real()))
+    ws = {c: torch.zeros(4, requires_grad=True) for c in "ABC"}
+    with torch.no_grad(), ops.defer_wgrad_reduce():
+        seen = set()
+        for c in order:
+            before = len(flushes)
+            got = ops._may_defer(ws[c])
+            if c in seen:
+                assert got is False and len(flushes) == before + 1, (order, c)
+            else:
+                assert got is True and len(flushes) == before, (order, c)
+            seen.add(c)
+    assert not ops._WGRAD_DEFERRED_IDS and ops._WGRAD_PENDING is None
+
+
+def test_deferral_bookkeeping_survives_nesting_and_existing_grad(monkeypatch):
+    """A weight whose .grad was set after its first deferral (a second backward pass inside the block: AccumulateGrad
+    would ADD into the unreduced tensor) flushes before it is reduced; nested blocks keep what the outer one saw, and
+    only leaving the outermost block forgets it."""
+    from grafp_amd import ops
+    flushes = []
+    real = ops.flush_wgrad_reduce                            # counted, and still run: the queue is empty, no launch
+    monkeypatch.setattr(ops, "flush_wgrad_reduce", lambda: (flushes.append(1), real()))
+    a, b = torch.zeros(4, requires_grad=True), torch.zeros(4, requires_grad=True)
+    with torch.no_grad():
+        with ops.defer_wgrad_reduce():
+            assert ops._may_defer(a) is True and not flushes
+            a.grad = torch.zeros(4)                          # what the first backward pass left behind
+            assert ops._may_defer(a) is False and len(flushes) == 1
+            with ops.defer_wgrad_reduce():                   # nested: the same bookkeeping
+                assert ops._may_defer(b) is True
+                assert ops._may_defer(a) is False and len(flushes) == 2
+            assert ops._WGRAD_PENDING is not None and ops._WGRAD_DEFERRED_IDS
+            assert ops._may_defer(b) is False and len(flushes) == 3
+        assert not ops._WGRAD_DEFERRED_IDS and ops._WGRAD_PENDING is None
+        a.grad = None
+        with ops.defer_wgrad_reduce():                       # a new block: first uses again
+            assert ops._may_defer(a) is True and ops._may_defer(b) is True
+        assert ops._may_defer(a) is True                     # outside any block nothing is tracked
+        assert not ops._WGRAD_DEFERRED_IDS
