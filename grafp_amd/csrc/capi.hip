@@ -38,3 +38,38 @@ extern "C" int grafp_debug_occupy(int blocks, int threads, int64_t clocks, grafp
     GRAFP_CHECK_LAUNCH("occupy_kernel");
     return GRAFP_OK;
 }
+
+// Device-resident training corpus (corpus.hip): argument checks here, kernels and launch plans there.
+namespace grafp {
+int resample_launch(const float *in, const int64_t *in_start, const int64_t *in_len, const int64_t *out_start,
+                    int n_tracks, int64_t max_in_len, int orig, int nw, int width, int K, const float *taps, float *out,
+                    hipStream_t stream);
+int draw_pairs_launch(const float *bank, const int64_t *track_start, const int64_t *track_len, const float *norm,
+                      int n_tracks, const int32_t *row_track, const float *uniforms, int B, int A, int clip,
+                      int offset_mod, float silence, float *x_i, float *x_j, int32_t *silent_rows, hipStream_t stream);
+}  // namespace grafp
+
+extern "C" int grafp_resample_f32(const float *in, const int64_t *in_start, const int64_t *in_len,
+                                  const int64_t *out_start, int n_tracks, int64_t max_in_len, int orig, int new_rate,
+                                  int width, int K, const float *taps, float *out, grafp_stream_t stream) {
+    GRAFP_REQUIRE(in && in_start && in_len && out_start && out, "resample: null pointer");
+    GRAFP_REQUIRE(n_tracks > 0 && n_tracks <= 65535 && max_in_len >= 0, "resample: bad sizes n_tracks=%d max_in_len=%lld",
+                  n_tracks, (long long)max_in_len);
+    GRAFP_REQUIRE(orig > 0 && new_rate > 0 && width >= 0 && K == 2 * width + orig,
+                  "resample: bad filter orig=%d new=%d width=%d K=%d", orig, new_rate, width, K);
+    return grafp::resample_launch(in, in_start, in_len, out_start, n_tracks, max_in_len, orig, new_rate, width, K, taps,
+                                  out, (hipStream_t)stream);
+}
+
+extern "C" int grafp_draw_pairs_f32(const float *bank, const int64_t *track_start, const int64_t *track_len,
+                                    const float *norm, int n_tracks, const int32_t *row_track, const float *uniforms,
+                                    int B, int A, int clip, int offset_mod, float silence, float *x_i, float *x_j,
+                                    int32_t *silent_rows, grafp_stream_t stream) {
+    GRAFP_REQUIRE(bank && track_start && track_len && norm && row_track && uniforms && x_i && x_j,
+                  "draw_pairs: null pointer");
+    GRAFP_REQUIRE(n_tracks > 0 && B > 0 && A > 0 && clip > 0 && offset_mod > clip,
+                  "draw_pairs: bad sizes n_tracks=%d B=%d A=%d clip=%d offset_mod=%d", n_tracks, B, A, clip, offset_mod);
+    GRAFP_REQUIRE(x_i != x_j, "draw_pairs: the two views must not alias");
+    return grafp::draw_pairs_launch(bank, track_start, track_len, norm, n_tracks, row_track, uniforms, B, A, clip,
+                                    offset_mod, silence, x_i, x_j, silent_rows, (hipStream_t)stream);
+}

@@ -7,7 +7,8 @@ the recordings (a list of files, a directory, or an array/tensor bank), which ar
 no padding to the longest file) resident in HBM; every step draws, per clip and on the device, whether each transform applies (ir_prob / noise_prob), which
 recording, the noise offset and the SNR (uniform in tr_snr / val_snr dB).  With both unset the transforms are
 identities, as in the reference.  Decoding is limited to what the image can do without torchaudio: `.npy` arrays and
-PCM `.wav` files (stdlib `wave`) already at cfg['fs'].
+PCM `.wav` files (stdlib `wave`) already at cfg['fs'] -- or, with cfg['resample_banks'] = True, PCM `.wav` files at
+any rate, resampled to cfg['fs'] on the device (ops.resample).
 """
 import glob
 import os
@@ -40,11 +41,30 @@ def _read_audio(path, fs):
     return a.reshape(-1, ch).mean(axis=1) if ch > 1 else a
 
 
-def load_bank(src, fs, max_len=None):
+def _read_any_rate(paths, fs):
+    """resample=True of load_bank: every file decoded at its own rate (grafp_amd.data.read_audio: PCM 8/16/24/32-bit,
+    any channel count) and brought to fs by the device resampler (ops.resample, one launch per foreign rate)."""
+    from ..data import read_audio
+    rows = [read_audio(p, fs) for p in paths]
+    out = [a for a, _ in rows]
+    for rate in sorted({r for a, r in rows if r != fs and a.size > 0}):
+        ids = [i for i, (a, r) in enumerate(rows) if r == rate and a.size > 0]
+        lens = np.array([rows[i][0].size for i in ids], dtype=np.int64)
+        starts = np.concatenate([[0], np.cumsum(lens[:-1])]).astype(np.int64)
+        flat = torch.from_numpy(np.concatenate([rows[i][0] for i in ids])).to(torch.device("cuda", torch.cuda.current_device()))
+        y, ys, yl = ops.resample(flat, torch.from_numpy(starts), torch.from_numpy(lens), rate, fs)
+        y, ys, yl = y.cpu().numpy(), ys.cpu().numpy(), yl.cpu().numpy()
+        for k, i in enumerate(ids):
+            out[i] = y[ys[k]:ys[k] + yl[k]].copy()
+    return out
+
+
+def load_bank(src, fs, max_len=None, resample=False):
     """Recordings -> ragged bank on the CPU: (flat f32 buffer, starts (n) int64, lengths (n) int32); recording r is
     flat[starts[r] : starts[r] + lengths[r]] (no padding to the longest file).
     src: directory (searched recursively for .wav/.npy), list of files, 2-D array/tensor (rows = recordings), or a
-    list of 1-D arrays.  max_len truncates every recording."""
+    list of 1-D arrays.  max_len truncates every recording (after resampling).  resample=False (default): a file at a
+    rate other than fs is refused (ValueError); resample=True: it is resampled to fs on the current HIP device."""
     if isinstance(src, torch.Tensor):
         src = src.detach().cpu().numpy()
     if isinstance(src, np.ndarray):
@@ -56,7 +76,12 @@ def load_bank(src, fs, max_len=None):
                              glob.glob(os.path.join(src, "**", "*.npy"), recursive=True))
             else:
                 src = [src]
-        rows = [(_read_audio(r, fs) if isinstance(r, str) else np.asarray(r, dtype=np.float32).reshape(-1)) for r in src]
+        if resample:
+            paths = [r for r in src if isinstance(r, str)]
+            decoded = iter(_read_any_rate(paths, fs))
+            rows = [(next(decoded) if isinstance(r, str) else np.asarray(r, dtype=np.float32).reshape(-1)) for r in src]
+        else:
+            rows = [(_read_audio(r, fs) if isinstance(r, str) else np.asarray(r, dtype=np.float32).reshape(-1)) for r in src]
     rows = [r[:max_len] if max_len else r for r in rows if r.size > 0]
     if not rows:
         raise ValueError("no recordings found for the augmentation bank")
@@ -76,14 +101,14 @@ class GPUTransformNeuralfp(nn.Module):
         has_ir = ir_dir is not None and not (isinstance(ir_dir, (list, tuple, str)) and len(ir_dir) == 0)
         has_noise = noise_dir is not None and not (isinstance(noise_dir, (list, tuple, str)) and len(noise_dir) == 0)
         if has_ir:
-            bank, starts, lens = load_bank(ir_dir, cfg["fs"])
+            bank, starts, lens = load_bank(ir_dir, cfg["fs"], resample=cfg.get("resample_banks", False))
             self.register_buffer("ir_bank", bank, persistent=False)
             self.register_buffer("ir_start", starts, persistent=False)
             self.register_buffer("ir_len", lens, persistent=False)
         else:
             self.ir_bank = self.ir_start = self.ir_len = None
         if has_noise:
-            bank, starts, lens = load_bank(noise_dir, cfg["fs"])
+            bank, starts, lens = load_bank(noise_dir, cfg["fs"], resample=cfg.get("resample_banks", False))
             self.register_buffer("noise_bank", bank, persistent=False)
             self.register_buffer("noise_start", starts, persistent=False)
             self.register_buffer("noise_len", lens, persistent=False)

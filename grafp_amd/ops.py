@@ -233,6 +233,111 @@ def mix_snr(x, noise_bank, noise_len, noise_index, noise_offset, snr_db, noise_s
     return out[0] if squeeze else out
 
 
+def resample_filter(orig_fs, new_fs, lowpass_filter_width=6, rolloff=0.99):
+    """The polyphase filter of torchaudio.transforms.Resample(orig_fs, new_fs) with its defaults (sinc_interp_hann):
+    -> (orig, new, width, taps) with orig / new the rates over their gcd and taps (new, K = 2*width + orig) float32,
+    evaluated in float64 and rounded once (what Resample(dtype=None) caches).  Host-side; no device needed."""
+    g = math.gcd(int(orig_fs), int(new_fs))
+    orig, new = int(orig_fs) // g, int(new_fs) // g
+    base = min(orig, new) * rolloff
+    width = math.ceil(lowpass_filter_width * orig / base)
+    k = np.arange(-width, width + orig, dtype=np.float64)[None, :] / orig
+    t = (-np.arange(new, dtype=np.float64)[:, None] / new + k) * base
+    t = np.clip(t, -lowpass_filter_width, lowpass_filter_width)
+    window = np.cos(t * math.pi / lowpass_filter_width / 2) ** 2
+    t = t * math.pi
+    scale = base / orig
+    with np.errstate(invalid="ignore", divide="ignore"):
+        sinc = np.where(t == 0, 1.0, np.sin(t) / t)
+    return orig, new, width, (sinc * window * scale).astype(np.float32)
+
+
+def resampled_length(n, orig_fs, new_fs):
+    """Samples of a length-n track after resample(): ceil(new * n / orig) in integers (rates over their gcd)."""
+    g = math.gcd(int(orig_fs), int(new_fs))
+    orig, new = int(orig_fs) // g, int(new_fs) // g
+    return (new * int(n) + orig - 1) // orig
+
+
+_RESAMPLE_TAPS = {}
+
+
+def _resample_taps(orig_fs, new_fs, device):
+    """The filter in the kernel's layout [ceil(new/P)][K rounded up to 4][P] (P = GRAFP_RESAMPLE_PHASES), zero padded."""
+    key = (int(orig_fs), int(new_fs), str(device))
+    if key not in _RESAMPLE_TAPS:
+        orig, new, width, taps = resample_filter(orig_fs, new_fs)
+        P, K = 10, taps.shape[1]
+        n_pb, K4 = -(-new // P), -(-K // 4) * 4
+        packed = np.zeros((n_pb * P, K4), dtype=np.float32)
+        packed[:new, :K] = taps
+        packed = packed.reshape(n_pb, P, K4).transpose(0, 2, 1)
+        _RESAMPLE_TAPS[key] = (orig, new, width, K, torch.from_numpy(np.ascontiguousarray(packed)).reshape(-1).to(device))
+    return _RESAMPLE_TAPS[key]
+
+
+def resample(bank, starts, lengths, orig_fs, new_fs, out=None, out_starts=None):
+    """torchaudio.transforms.Resample(orig_fs, new_fs) (default filter) of every track of a ragged bank in ONE launch
+    (grafp_resample_f32).  bank: flat f32 device buffer; starts / lengths: per-track int64 (device or host).
+    -> (out_bank, out_starts, out_lengths), the resampled tracks packed back to back -- or, with `out` and `out_starts`,
+    written into `out` at those offsets (the caller sized it).  orig_fs == new_fs: a bit-exact copy."""
+    _require_gpu(bank)
+    dev = bank.device
+    bank = _f32c(bank)
+    lens_h = torch.as_tensor(lengths).detach().to("cpu", torch.int64)
+    n = lens_h.numel()
+    if n == 0:
+        raise ValueError("resample: no tracks")
+    out_lens_h = torch.tensor([resampled_length(int(v), orig_fs, new_fs) for v in lens_h.tolist()], dtype=torch.int64)
+    if out_starts is None:
+        out_starts_h = torch.cumsum(out_lens_h, 0) - out_lens_h
+        total = int(out_lens_h.sum())
+    else:
+        out_starts_h = torch.as_tensor(out_starts).detach().to("cpu", torch.int64)
+        total = int((out_starts_h + out_lens_h).max())
+    out_bank = torch.empty(max(total, 1), dtype=torch.float32, device=dev) if out is None else out
+    if out is not None and (out.numel() < total or out.dtype != torch.float32 or not out.is_contiguous()
+                            or out.device != dev):
+        raise ValueError("resample: `out` must be a contiguous f32 device buffer covering every output track")
+    orig, new, width, K, taps = _resample_taps(orig_fs, new_fs, dev)
+    in_starts = torch.as_tensor(starts).detach().to(device=dev, dtype=torch.int64).contiguous()
+    in_lens, out_starts = lens_h.to(dev), out_starts_h.to(dev)
+    for lo in range(0, n, 65535):                 # grid.y holds one track per row
+        hi = min(n, lo + 65535)
+        check(lib.grafp_resample_f32(_p(bank), _p(in_starts[lo:hi]), _p(in_lens[lo:hi]), _p(out_starts[lo:hi]), hi - lo,
+                                     int(lens_h[lo:hi].max()), orig, new, width, K, _p(taps), _p(out_bank), _stream()),
+              "resample")
+    return out_bank[:total], out_starts, out_lens_h.to(dev)
+
+
+def draw_pairs(bank, track_start, track_len, norm, row_track, uniforms, clip, offset_mod, silence, silent_rows=None):
+    """The training crops of NeuralfpDataset.__getitem__ (modules/data.py:70-89) for a whole batch in one launch
+    (grafp_draw_pairs_f32): row b tries tracks row_track[b], row_track[b] + 1, ... (mod n) with the uniforms
+    uniforms[b, a, 0:3] until both crops are louder than `silence`, and writes them divided by the track's norm.
+    -> (x_i, x_j), each (B, clip) f32.  silent_rows: optional int32 device counter of rows whose attempts were all
+    silent (the last attempt is written)."""
+    _require_gpu(bank, uniforms)
+    dev = bank.device
+    B, A = int(uniforms.shape[0]), int(uniforms.shape[1])
+    if uniforms.dim() != 3 or uniforms.shape[2] != 3:
+        raise ValueError("draw_pairs: uniforms must be (B, attempts, 3)")
+    if row_track.numel() != B:
+        raise ValueError("draw_pairs: one start track per row")
+    u = _f32c(uniforms)
+    starts = track_start.detach().to(device=dev, dtype=torch.int64).contiguous()
+    lens = track_len.detach().to(device=dev, dtype=torch.int64).contiguous()
+    nv = _f32c(norm.to(dev))
+    rows = _i32c(row_track, dev)
+    x_i = torch.empty((B, clip), dtype=torch.float32, device=dev)
+    x_j = torch.empty((B, clip), dtype=torch.float32, device=dev)
+    if silent_rows is not None and (silent_rows.dtype != torch.int32 or not silent_rows.is_cuda):
+        raise ValueError("draw_pairs: silent_rows must be an int32 device tensor")
+    check(lib.grafp_draw_pairs_f32(_p(_f32c(bank)), _p(starts), _p(lens), _p(nv), lens.numel(), _p(rows), _p(u), B, A,
+                                   int(clip), int(offset_mod), float(silence), _p(x_i), _p(x_j), _p(silent_rows),
+                                   _stream()), "draw_pairs")
+    return x_i, x_j
+
+
 # ------------------------------------------------------------------------------------------------
 # K2  peak extractor
 # ------------------------------------------------------------------------------------------------

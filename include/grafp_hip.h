@@ -512,6 +512,34 @@ int grafp_mix_snr_f32(const float *x, int64_t x_stride, int B, int T, const floa
                       const float *snr_db, float *out, int64_t out_stride, void *ws, size_t ws_bytes,
                       grafp_stream_t stream);
 
+/* ---- device-resident training corpus (grafp_amd/data.py; replaces the per-item CPU work of
+ *      modules/data.py:45-89, NeuralfpDataset.__getitem__) ------------------------------------------------------
+ * Tracks are a ragged bank: track r is bank[start[r], start[r] + len[r]) (int64 starts and lengths).
+ *
+ * grafp_resample_f32 -- torchaudio.transforms.Resample(orig, new) with its defaults (sinc_interp_hann,
+ *   lowpass_filter_width 6, rolloff 0.99) for n_tracks tracks of one rate pair.  orig / new are the rates divided by
+ *   their gcd, width = ceil(6 * orig / (min(orig, new) * 0.99)), K = 2 * width + orig.  Output track r has
+ *   ceil(new * in_len[r] / orig) samples at out[out_start[r] ...]: sample j*new + p = sum_{k<K} tap[p][k] *
+ *   x[j*orig + k - width] (zeros outside the track), one fmaf chain in increasing k.  taps: f32, laid out
+ *   [ceil(new / GRAFP_RESAMPLE_PHASES)][K rounded up to a multiple of 4][GRAFP_RESAMPLE_PHASES], zero padded.
+ *   max_in_len >= every in_len (sizes the grid).  orig == new: a bit-exact copy (taps may be NULL).  The input window of
+ *   64 output blocks, (63 * orig + K) samples, must fit the LDS (160 KiB): orig <= ~600 after the gcd.
+ * grafp_draw_pairs_f32 -- the training crops of NeuralfpDataset.__getitem__ (modules/data.py:70-89) for B rows.
+ *   Attempt a < A of row b uses track (row_track[b] + a) mod n_tracks and the uniforms u = uniforms[b][a][0..2]:
+ *   r = min(floor(u0 * (len - offset_mod)), len - offset_mod - 1), ri / rj the same over offset_mod - clip (f64
+ *   products); x_i = y[r+ri : r+ri+clip], x_j = y[r+rj : r+rj+clip].  The attempt is rejected when max|x_i| or
+ *   max|x_j| < silence; the first accepted one is written divided by norm[track] (IEEE division).  If all A are silent
+ *   the last is written and *silent_rows (may be NULL) is incremented.  Tracks used must hold >= offset_mod + 1 samples;
+ *   offset_mod <= 40896.  x_i, x_j: (B, clip) row-major. */
+#define GRAFP_RESAMPLE_PHASES 10
+int grafp_resample_f32(const float *in, const int64_t *in_start, const int64_t *in_len, const int64_t *out_start,
+                       int n_tracks, int64_t max_in_len, int orig, int new_rate, int width, int K, const float *taps,
+                       float *out, grafp_stream_t stream);
+int grafp_draw_pairs_f32(const float *bank, const int64_t *track_start, const int64_t *track_len, const float *norm,
+                         int n_tracks, const int32_t *row_track, const float *uniforms, int B, int A, int clip,
+                         int offset_mod, float silence, float *x_i, float *x_j, int32_t *silent_rows,
+                         grafp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
