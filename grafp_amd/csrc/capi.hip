@@ -73,3 +73,28 @@ extern "C" int grafp_draw_pairs_f32(const float *bank, const int64_t *track_star
     return grafp::draw_pairs_launch(bank, track_start, track_len, norm, n_tracks, row_track, uniforms, B, A, clip,
                                     offset_mod, silence, x_i, x_j, silent_rows, (hipStream_t)stream);
 }
+
+// Track-aware sequence identification (identify.hip): argument checks here, the kernel and its LDS plan there.
+namespace grafp {
+int identify_launch(const float *rows, int64_t n, const int64_t *first, int T, const float *q_rows,
+                    const int64_t *ids, int k, const int64_t *item_row, const int *item_len, int n_items, int max_len,
+                    int top, int min_overlap, int32_t *out_track, int32_t *out_offset, float *out_score,
+                    int32_t *out_votes, hipStream_t stream);
+}  // namespace grafp
+
+extern "C" int grafp_identify_f32(const float *index_rows, int64_t n, const int64_t *track_first_row, int n_tracks,
+                                  const float *q_rows, int64_t n_qrows, const int64_t *topk_ids, int k,
+                                  const int64_t *item_row, const int *item_len, int n_items, int max_len, int top,
+                                  int min_overlap, int32_t *out_track, int32_t *out_offset, float *out_score,
+                                  int32_t *out_votes, grafp_stream_t stream) {
+    GRAFP_REQUIRE(index_rows && track_first_row && q_rows && topk_ids && item_row && item_len && out_track &&
+                  out_offset && out_score && out_votes, "identify: null pointer");
+    GRAFP_REQUIRE(n >= 1 && n < 0x7fffff00ll && n_tracks >= 1 && n_qrows >= 1 && n_items >= 0,
+                  "identify: bad sizes n=%lld n_tracks=%d n_qrows=%lld n_items=%d", (long long)n, n_tracks,
+                  (long long)n_qrows, n_items);
+    GRAFP_REQUIRE(top >= 1 && top <= 64, "identify: top=%d not in [1, 64]", top);
+    GRAFP_REQUIRE((((uintptr_t)index_rows | (uintptr_t)q_rows) & 15) == 0, "identify: rows must be 16-byte aligned");
+    return grafp::identify_launch(index_rows, n, track_first_row, n_tracks, q_rows, topk_ids, k, item_row, item_len,
+                                  n_items, max_len, top, min_overlap, out_track, out_offset, out_score, out_votes,
+                                  (hipStream_t)stream);
+}

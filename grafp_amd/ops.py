@@ -1517,6 +1517,68 @@ def seq_rerank(index_rows, q_rows, topk_ids, item_row, item_len, top=10, shard=N
     return out_i, out_s
 
 
+IDENTIFY_MAX_LEN, IDENTIFY_MAX_K, IDENTIFY_MAX_KEYS = 256, 32, 8192      # identify.hip's limits
+
+
+def check_track_table(first, n):
+    """Refuses a track table that is not (T + 1) int64 row starts with first[0] = 0, first[T] = n, non-decreasing."""
+    f = torch.as_tensor(first).detach().to("cpu", torch.int64).reshape(-1)
+    if f.numel() < 2 or int(f[0]) != 0 or int(f[-1]) != int(n) or bool((f[1:] < f[:-1]).any()):
+        raise ValueError(f"identify: the track table must run from 0 to n = {int(n)} and never decrease "
+                         f"(got {f.numel()} entries{', ' + str(int(f[0])) + ' .. ' + str(int(f[-1])) if f.numel() else ''})")
+
+
+def identify(index_rows, track_first_row, q_rows, topk_ids, item_row, item_len, top=5, min_overlap=None, max_len=None):
+    """Track-aware sequence identification (grafp_identify_f32, one workgroup per item): for every item, the `top`
+    library tracks it most likely is, with the alignment inside each.
+    index_rows (n,128) f32 resident library, track_first_row (T+1) int64 (track t = rows [first[t], first[t+1])),
+    q_rows (n_q,128) f32, topk_ids (n_q,k) int64 (-1: no hit), item_row (n_items) int64 first query row of each item,
+    item_len (n_items) int32 segments per item.  min_overlap: segments of the query that must lie inside the track
+    (None: the whole item, unless the track is shorter).
+    Returns (track int32, offset int32 in segments from the track's first row, score f32, votes int32), each
+    (n_items, top), best first, padded with -1 / INT_MIN / -inf / 0.
+    max_len: the longest item, an upper bound is fine; the caller then vouches for the ranges (the item rows inside
+    q_rows, the track table well formed) and the call stays asynchronous and capturable.  Without it the op checks them
+    on the host."""
+    n_items, k, top = int(item_row.shape[0]), int(topk_ids.shape[1]), int(top)
+    # argument checks first (host values only): they hold on any device
+    if not 1 <= top <= 64:
+        raise ValueError(f"identify: top={top} not in [1, 64]")
+    if not 1 <= k <= IDENTIFY_MAX_K:
+        raise ValueError(f"identify: k={k} hits per segment exceeds {IDENTIFY_MAX_K}")
+    if min_overlap is not None and int(min_overlap) < 1:
+        raise ValueError("identify: min_overlap must be at least 1 segment")
+    if max_len is None and n_items:
+        max_len = max(1, int(item_len.max().item()))
+        check_track_table(track_first_row, index_rows.shape[0])
+        if int((item_row.to(torch.int64) + item_len.to(torch.int64)).max().item()) > q_rows.shape[0] or \
+                int(item_row.min().item()) < 0:
+            raise ValueError("identify: an item reaches outside q_rows")
+    if max_len is not None and (int(max_len) > IDENTIFY_MAX_LEN or int(max_len) * k > IDENTIFY_MAX_KEYS):
+        raise ValueError(f"identify: items of {int(max_len)} segments with k={k} exceed {IDENTIFY_MAX_LEN} segments "
+                         f"or {IDENTIFY_MAX_KEYS} hits per item")
+    _require_gpu(index_rows, q_rows, topk_ids, item_row, item_len)
+    index_rows, q_rows = _f32c(index_rows), _f32c(q_rows)
+    dev = index_rows.device
+    first = torch.as_tensor(track_first_row).detach().to(device=dev, dtype=torch.int64).contiguous()
+    topk_ids = topk_ids.to(torch.int64).contiguous()
+    item_row = item_row.to(torch.int64).contiguous()
+    item_len = item_len.to(torch.int32).contiguous()
+    outs = (torch.empty((n_items, top), dtype=torch.int32, device=dev),
+            torch.empty((n_items, top), dtype=torch.int32, device=dev),
+            torch.empty((n_items, top), dtype=torch.float32, device=dev),
+            torch.empty((n_items, top), dtype=torch.int32, device=dev))
+    if n_items == 0:
+        return outs
+    max_len = int(max_len)
+    with _timed("identify", (n_items, max_len, k)):
+        check(lib.grafp_identify_f32(_p(index_rows), index_rows.shape[0], _p(first), first.numel() - 1, _p(q_rows),
+                                     q_rows.shape[0], _p(topk_ids), k, _p(item_row), _p(item_len), n_items, max_len,
+                                     top, 0 if min_overlap is None else int(min_overlap), *(_p(o) for o in outs),
+                                     _stream()), "identify")
+    return outs
+
+
 class FlatL2Index:
     """Drop-in for the subset of faiss.IndexFlatL2 that eval.py uses: d, ntotal, add(x), search(q, k).
     The database lives in HBM; `add` also computes the per-row squared norms once."""

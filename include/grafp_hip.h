@@ -540,6 +540,25 @@ int grafp_draw_pairs_f32(const float *bank, const int64_t *track_start, const in
                          int offset_mod, float silence, float *x_i, float *x_j, int32_t *silent_rows,
                          grafp_stream_t stream);
 
+/* ---- track-aware sequence identification (grafp_amd/library.py; identify.hip) -----------------------------------
+ * grafp_identify_f32 -- which track, and where in it, each of n_items query items is.  index_rows: the (n, 128) f32
+ *   library rows of n_tracks tracks laid end to end, track t owning rows [track_first_row[t], track_first_row[t+1])
+ *   (n_tracks + 1 int64 entries, first 0, last n, non-decreasing: a track may have no rows).  Item i is the query rows
+ *   [item_row[i], item_row[i] + ql) of q_rows (n_qrows, 128) with ql = min(item_len[i], max_len), and topk_ids
+ *   (n_qrows, k) int64 their library ids (-1 or any id outside [0, n): no hit).
+ *   A hit (s, r) names the track t holding r and the alignment a = r - s; a candidate is a unique (t, a), its votes the
+ *   hits that map to it.  Its overlap is the o segments s < ql with a + s inside t; it is eligible iff
+ *   o >= min(min_overlap, L_t) (L_t: rows of t; min_overlap <= 0 means the item's ql) and then scores
+ *   (sum over the overlap of <q[s], row[a + s]>) / o in the arithmetic order of grafp_seq_rerank_f32 (no row outside t
+ *   is read).  Per track the best candidate is kept (highest score, then smaller a); the `top` tracks go out by score
+ *   descending, then track ascending: out_track (int32), out_offset = a - first[t] (int32, segments), out_score (f32),
+ *   out_votes (int32), each (n_items, top), padded with -1 / INT_MIN / -inf / 0.
+ *   Limits: max_len <= 256, k <= 32, max_len * k <= 8192, 1 <= top <= 64; rows 16-byte aligned. */
+int grafp_identify_f32(const float *index_rows, int64_t n, const int64_t *track_first_row, int n_tracks,
+                       const float *q_rows, int64_t n_qrows, const int64_t *topk_ids, int k, const int64_t *item_row,
+                       const int *item_len, int n_items, int max_len, int top, int min_overlap, int32_t *out_track,
+                       int32_t *out_offset, float *out_score, int32_t *out_votes, grafp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
