@@ -98,3 +98,30 @@ extern "C" int grafp_identify_f32(const float *index_rows, int64_t n, const int6
                                   n_items, max_len, top, min_overlap, out_track, out_offset, out_score, out_votes,
                                   (hipStream_t)stream);
 }
+
+// Shared audio inside a track-indexed library (selfmatch.hip): argument checks here, the kernels and the plan there.
+namespace grafp {
+size_t self_match_workspace(const int64_t *src_rows, int n_src, int k, int min_votes);
+int self_match_launch(const float *rows, int64_t n, const int64_t *first, int T, const int64_t *ids, int k,
+                      const int *tracks, int n_src, int top, int min_votes, int min_overlap, void *ws,
+                      size_t ws_bytes, int32_t *out_track, int32_t *out_delta, int32_t *out_start, int32_t *out_len,
+                      float *out_score, int32_t *out_votes, hipStream_t stream);
+}  // namespace grafp
+
+extern "C" size_t grafp_self_match_workspace(const int64_t *src_rows, int n_src, int k, int min_votes) {
+    return grafp::self_match_workspace(src_rows, n_src, k, min_votes);
+}
+
+extern "C" int grafp_self_match_f32(const float *index_rows, int64_t n, const int64_t *track_first_row, int n_tracks,
+                                    const int64_t *topk_ids, int k, const int *src_tracks, int n_src, int top,
+                                    int min_votes, int min_overlap, void *ws, size_t ws_bytes, int32_t *out_track, int32_t *out_delta, int32_t *out_start, int32_t *out_len,
+                                    float *out_score, int32_t *out_votes, grafp_stream_t stream) {
+    GRAFP_REQUIRE(index_rows && track_first_row && topk_ids && src_tracks && out_track && out_delta && out_start &&
+                  out_len && out_score && out_votes, "self_match: null pointer");
+    GRAFP_REQUIRE(n >= 1 && n < 0x7fffff00ll && n_tracks >= 1 && n_src >= 0,
+                  "self_match: bad sizes n=%lld n_tracks=%d n_src=%d", (long long)n, n_tracks, n_src);
+    GRAFP_REQUIRE(((uintptr_t)index_rows & 15) == 0, "self_match: rows must be 16-byte aligned");
+    return grafp::self_match_launch(index_rows, n, track_first_row, n_tracks, topk_ids, k, src_tracks, n_src, top,
+                                    min_votes, min_overlap, ws, ws_bytes, out_track, out_delta, out_start, out_len,
+                                    out_score, out_votes, (hipStream_t)stream);
+}

@@ -2,9 +2,11 @@
 
   python -m grafp_amd.identify build --config CFG --ckp MODEL.pth --source DIR|JSON|FILES... --out LIBDIR [--precision]
   python -m grafp_amd.identify query --ckp MODEL.pth --library LIBDIR FILES... [--top 5] [--window S --hop S]
+  python -m grafp_amd.identify dedup --ckp MODEL.pth --library LIBDIR [--min-overlap 3] [--coverage 0.9] [--json OUT]
 
 `build` fingerprints every track of the source (anything DeviceAudioCorpus accepts) into LIBDIR; `query` prints one JSON
-object per query file -- or, with --window, one per timeline span of each file."""
+object per query file -- or, with --window, one per timeline span of each file; `dedup` prints one JSON object per pair
+of tracks that share audio, then one per group of duplicates (--json also writes both to a file)."""
 import argparse
 import json
 import sys
@@ -43,6 +45,17 @@ def main(argv=None):
     q.add_argument("--window", type=float, default=None, help="seconds per window: report a timeline per file")
     q.add_argument("--hop", type=float, default=1.0)
     q.add_argument("--force", action="store_true", help="use a library made with another model")
+    d = sub.add_parser("dedup", help="find tracks of a library that share audio")
+    d.add_argument("--config", default=DEFAULT_CONFIG, help="model configuration (the library keeps its own "
+                                                            "segmentation settings)")
+    d.add_argument("--ckp", required=True)
+    d.add_argument("--library", required=True)
+    d.add_argument("--min-overlap", type=float, default=3.0, help="seconds of shared audio a pair needs")
+    d.add_argument("--coverage", type=float, default=0.9, help="share of the shorter track that makes a duplicate")
+    d.add_argument("--min-score", type=float, default=None, help="duplicate score bar (default: the library's)")
+    d.add_argument("--k-probe", type=int, default=32)
+    d.add_argument("--json", default=None, help="also write {pairs, groups} to this file")
+    d.add_argument("--force", action="store_true", help="use a library made with another model")
     args = ap.parse_args(argv)
 
     from .data import DeviceAudioCorpus
@@ -58,6 +71,20 @@ def main(argv=None):
         print(json.dumps({"library": args.out, "tracks": lib.n_tracks, "rows": lib.n_rows}))
         return 0
     lib = FingerprintLibrary.load(args.library, model, device, force=args.force)
+    if args.cmd == "dedup":
+        from .library import DUPLICATE_MIN_SCORE
+        pairs = lib.self_matches(k_probe=args.k_probe, min_overlap_s=args.min_overlap)
+        bar = DUPLICATE_MIN_SCORE if args.min_score is None else args.min_score
+        groups = [{"tracks": g, "names": [lib.names[t] for t in g]}
+                  for g in lib.duplicate_groups(pairs, min_coverage=args.coverage, min_score=bar)]
+        for p in pairs:
+            print(json.dumps({"pair": p}))
+        for g in groups:
+            print(json.dumps({"group": g}))
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump({"pairs": pairs, "groups": groups}, f, indent=1)
+        return 0
     if args.window is None:
         for path, matches in zip(args.files, lib.identify(list(args.files), top=args.top, k_probe=args.k_probe)):
             print(json.dumps({"query": path, "matches": matches}))

@@ -18,6 +18,11 @@ from . import ops
 
 SETTINGS = ("fs", "n_fft", "win_len", "hop_len", "n_mels", "n_frames", "overlap")
 FORMAT = 1
+# duplicate_groups' default score bar: a match at least this strong is shared audio.  Chosen from
+# tests/test_gpu_selfmatch.py's trained-model case (the briefly trained model of tests/_retrieval_case.py, bf16 library,
+# measured on MI355X): an exact copy scores 1.000, the pieces of a medley at 20 dB SNR 0.985 and 0.956, the strongest of
+# the 77 unrelated pairs that pass the 3 s / 4-vote filters 0.832.  0.9 sits between the two, 0.07 above the unrelated.
+DUPLICATE_MIN_SCORE = 0.9
 
 
 def model_digest(model):
@@ -370,3 +375,93 @@ class FingerprintLibrary:
             s["score"] = float(np.mean(s.pop("_scores")))
             s.pop("_delta")
         return spans
+
+    # ---- the catalog itself ------------------------------------------------------------------------------------
+    def self_matches(self, k_probe=32, min_overlap_s=3.0, min_votes=4, min_score=None, top=8, tracks=None,
+                     batch_rows=1 << 18):
+        """Tracks that share audio: re-releases, compilations, edits, quotes.  The library's own rows (or only those of
+        `tracks`) are searched against self.index in batches of about batch_rows rows, and each batch of source tracks
+        goes through one ops.self_match launch.  -> list of {track_a, name_a, track_b, name_b, offset, a_start_s,
+        b_start_s, overlap_s, coverage, score, votes}: track_a's audio from a_start_s reappears in track_b from
+        b_start_s for overlap_s seconds; offset = delta in segments (row i of a sits on row i + offset of b), coverage =
+        overlapping rows / rows of the shorter track, score = mean cosine over the span.  Ordered by track_a, then
+        score descending, then track_b; both directions are reported (a -> b from a's rows, b -> a from b's).
+        k_probe: hits per row.  At the default overlap of 0.9 a segment's nearest neighbours include its own track's
+        next rows (a hop is a tenth of a segment), and those hits are dropped, so k_probe defaults to 32 (the most
+        the kernel takes) rather than identify's 20.  min_overlap_s: the least span, in seconds of segment hops;
+        min_votes: the least rows whose hits agree on the alignment; min_score: drop weaker matches (None: keep all).
+        Memory: the kernel reads hits by library row, so the hits of the searched rows live in one (n_rows, k_probe)
+        int64 tensor whatever `tracks` is (256 MB at 1 M rows and k_probe = 32); each batch also takes its own exactly
+        sized workspace (ops.self_match_workspace_bytes: about 124 KB per 303-row source at k_probe = 32, min_votes 4)."""
+        T, n = self.n_tracks, self.n_rows
+        src = list(range(T)) if tracks is None else sorted({int(t) for t in tracks})
+        if src and not 0 <= min(src) <= max(src) < T:
+            raise ValueError(f"tracks must lie in [0, {T})")
+        if n == 0 or T < 2 or not src:
+            return []
+        seg_s = self.segment_s
+        min_overlap = max(1, int(math.ceil(float(min_overlap_s) / seg_s - 1e-9)))
+        k = min(int(k_probe), n)
+        rows, dev = self.rows(), self.device
+        first_d = torch.from_numpy(self.first).to(dev)
+        ids = torch.full((n, k), -1, dtype=torch.int64, device=dev)
+        lens = np.diff(self.first)
+        batches, cur, cur_rows = [], [], 0
+        for t in src:
+            cur.append(t)
+            cur_rows += int(lens[t])
+            if cur_rows >= batch_rows:
+                batches.append(cur)
+                cur, cur_rows = [], 0
+        if cur:
+            batches.append(cur)
+        out = []
+        for batch in batches:
+            g = np.concatenate([np.arange(self.first[t], self.first[t + 1]) for t in batch]).astype(np.int64)
+            if g.size:
+                g_d = torch.from_numpy(g).to(dev)
+                _, hit = self.index.search(rows[g_d], k)
+                ids[g_d] = hit
+            res = ops.self_match(rows, first_d, ids, tracks=torch.tensor(batch, dtype=torch.int64), top=int(top),
+                                 min_votes=int(min_votes), min_overlap=min_overlap)
+            b_, d_, lo_, m_, sc_, v_ = (x.cpu().numpy() for x in res)
+            for s, a in enumerate(batch):
+                for j in range(b_.shape[1]):
+                    b = int(b_[s, j])
+                    if b == -2:                                  # the op sizes the workspace exactly: never
+                        raise RuntimeError(f"self_match: track {a} did not fit the workspace")
+                    if b < 0:
+                        break
+                    sc = float(sc_[s, j])
+                    if min_score is not None and sc < min_score:
+                        continue
+                    d, lo, m = int(d_[s, j]), int(lo_[s, j]), int(m_[s, j])
+                    out.append({"track_a": a, "name_a": self.names[a], "track_b": b, "name_b": self.names[b],
+                                "offset": d, "a_start_s": lo * seg_s, "b_start_s": (lo + d) * seg_s,
+                                "overlap_s": m * seg_s, "coverage": m / max(1, min(int(lens[a]), int(lens[b]))),
+                                "score": sc, "votes": int(v_[s, j])})
+        return out
+
+    @staticmethod
+    def duplicate_groups(matches, min_coverage=0.9, min_score=DUPLICATE_MIN_SCORE):
+        """Connected components of the tracks whose matches (from self_matches) cover at least min_coverage of the
+        shorter track with at least min_score: duplicates, and chains of them.  -> list of sorted track lists (two or
+        more tracks each), ordered by their first track.  Union-find on the host."""
+        parent = {}
+
+        def find(x):
+            parent.setdefault(x, x)
+            while parent[x] != x:
+                parent[x] = parent[parent[x]]
+                x = parent[x]
+            return x
+
+        for m in matches:
+            if m["coverage"] >= min_coverage and (min_score is None or m["score"] >= min_score):
+                ra, rb = find(int(m["track_a"])), find(int(m["track_b"]))
+                if ra != rb:
+                    parent[max(ra, rb)] = min(ra, rb)
+        groups = {}
+        for x in parent:
+            groups.setdefault(find(x), []).append(x)
+        return sorted((sorted(g) for g in groups.values() if len(g) > 1), key=lambda g: g[0])

@@ -1579,6 +1579,66 @@ def identify(index_rows, track_first_row, q_rows, topk_ids, item_row, item_len, 
     return outs
 
 
+SELF_MATCH_MAX_K, SELF_MATCH_MAX_TOP = 32, 64                             # selfmatch.hip's limits
+
+
+def self_match_workspace_bytes(src_rows, k, min_votes):
+    """Exact workspace of one ops.self_match launch (grafp_self_match_workspace): src_rows the rows of each source track
+    (host), k hits per row."""
+    r = np.ascontiguousarray(np.asarray(src_rows, np.int64).reshape(-1))
+    return int(lib.grafp_self_match_workspace(_vp(r.ctypes.data) if r.size else None, int(r.size), int(k),
+                                              int(min_votes)))
+
+
+def self_match(index_rows, track_first_row, topk_ids, tracks=None, top=8, min_votes=4, min_overlap=1):
+    """Shared audio inside a track-indexed library (grafp_self_match_f32, one workgroup per source track): for every
+    source track a, the `top` other tracks b its rows reappear in, each at its best alignment.
+    index_rows (n,128) f32 resident library, track_first_row (T+1) int64 (track t = rows [first[t], first[t+1])),
+    topk_ids (n,k) int64 every library row's hits from searching the library against itself (-1: no hit), tracks the
+    source tracks (default all).  A hit of row first[a] + i on row first[b] + j (b != a) votes for (b, delta = j - i);
+    a candidate's span runs from its first to its last voting i (m rows) and it needs min_votes votes and m >=
+    min_overlap rows.  It scores the mean dot product over its whole span (the arithmetic order of ops.identify).
+    Returns (track, delta, start, length, score, votes), each (n_src, top) -- int32 but score f32 --, best first,
+    padded with -1 / INT_MIN / -1 / 0 / -inf / 0.  The table, the sources and the limits are checked on the host."""
+    k, top = int(topk_ids.shape[1]), int(top)
+    if not 1 <= top <= SELF_MATCH_MAX_TOP:
+        raise ValueError(f"self_match: top={top} not in [1, {SELF_MATCH_MAX_TOP}]")
+    if not 1 <= k <= SELF_MATCH_MAX_K:
+        raise ValueError(f"self_match: k={k} hits per row exceeds {SELF_MATCH_MAX_K}")
+    if int(min_votes) < 1 or int(min_overlap) < 1:
+        raise ValueError("self_match: min_votes and min_overlap must be at least 1")
+    n = int(index_rows.shape[0])
+    if n < 1 or int(topk_ids.shape[0]) != n:
+        raise ValueError(f"self_match: topk_ids has {int(topk_ids.shape[0])} rows for a library of {n}")
+    check_track_table(track_first_row, n)
+    first_h = torch.as_tensor(track_first_row).detach().to("cpu", torch.int64).reshape(-1)
+    T = first_h.numel() - 1
+    src = torch.arange(T, dtype=torch.int64) if tracks is None else \
+        torch.as_tensor(tracks).detach().to("cpu", torch.int64).reshape(-1)
+    if src.numel() and (int(src.min()) < 0 or int(src.max()) >= T):
+        raise ValueError(f"self_match: source tracks must lie in [0, {T})")
+    lens = (first_h[1:] - first_h[:-1])[src]
+    if lens.numel() and int(lens.max()) * k > 2 ** 31 - 1:
+        raise ValueError(f"self_match: a track of {int(lens.max())} rows has more than 2^31 - 1 hits at k={k} "
+                         "(votes are int32)")
+    _require_gpu(index_rows, topk_ids)
+    index_rows = _f32c(index_rows)
+    dev = index_rows.device
+    first = first_h.to(dev)
+    topk_ids = topk_ids.to(torch.int64).contiguous()
+    n_src = src.numel()
+    src_d = src.to(device=dev, dtype=torch.int32)
+    outs = tuple(torch.empty((n_src, top), dtype=torch.float32 if j == 4 else torch.int32, device=dev)
+                 for j in range(6))
+    if n_src == 0:
+        return outs
+    ws = torch.empty(self_match_workspace_bytes(lens.numpy(), k, min_votes), dtype=torch.uint8, device=dev)
+    with _timed("self_match", (n_src, int(lens.sum()), k)):
+        check(lib.grafp_self_match_f32(_p(index_rows), n, _p(first), T, _p(topk_ids), k, _p(src_d), n_src, top, int(min_votes), int(min_overlap), _p(ws), ws.numel(),
+                                       *(_p(o) for o in outs), _stream()), "self_match")
+    return outs
+
+
 class FlatL2Index:
     """Drop-in for the subset of faiss.IndexFlatL2 that eval.py uses: d, ntotal, add(x), search(q, k).
     The database lives in HBM; `add` also computes the per-row squared norms once."""

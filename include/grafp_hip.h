@@ -559,6 +559,29 @@ int grafp_identify_f32(const float *index_rows, int64_t n, const int64_t *track_
                        const int *item_len, int n_items, int max_len, int top, int min_overlap, int32_t *out_track,
                        int32_t *out_offset, float *out_score, int32_t *out_votes, grafp_stream_t stream);
 
+/* ---- shared audio inside a track-indexed library (grafp_amd/library.py; selfmatch.hip) ---------------------------
+ * grafp_self_match_f32 -- for each of n_src source tracks src_tracks[s] (int32, in [0, n_tracks)), the other tracks
+ *   its audio reappears in.  index_rows, track_first_row: as for grafp_identify_f32; topk_ids (n, k) int64: every
+ *   library row's top-k hits from searching the library against itself (-1 or any id outside [0, n): no hit).
+ *   Row first[a] + i of source a with hit r in track b != a votes for the candidate (b, delta = (r - first[b]) - i);
+ *   hits inside a are dropped, duplicate ids vote twice.  A candidate's span is [i_lo, i_hi], its smallest and largest
+ *   voting i, m = i_hi - i_lo + 1; it is eligible iff votes >= min_votes and m >= min_overlap, and scores
+ *   (sum_{i = i_lo..i_hi} <row[first[a] + i], row[first[b] + i + delta]>) / m in the arithmetic order of
+ *   grafp_identify_f32.  Per partner b the best eligible candidate is kept (highest score, then smaller delta); the
+ *   `top` partners go out by score descending, then b ascending: out_track (b), out_delta, out_start (i_lo), out_len
+ *   (m), out_votes (int32) and out_score (f32), each (n_src, top), padded with -1 / INT_MIN / -1 / 0 / 0 / -inf.
+ *   ws: grafp_self_match_workspace(src_rows, n_src, k, min_votes) bytes, src_rows (HOST, n_src int64) the rows of each
+ *   source track in the order of src_tracks: the exact size the launch lays out.  A smaller ws (but at least its
+ *   header) is not refused: every source whose region would end past ws_bytes gets out_track -2 in its first slot and
+ *   nothing else is written for it; nothing is written outside ws.
+ *   Limits: k <= 32, 1 <= top <= 64, min_votes >= 1, min_overlap >= 1, L * k <= INT_MAX hits per source (the int32
+ *   votes); tracks of any length otherwise (the hits of a long track are sorted in the workspace); rows 16-byte aligned. */
+int grafp_self_match_f32(const float *index_rows, int64_t n, const int64_t *track_first_row, int n_tracks,
+                         const int64_t *topk_ids, int k, const int *src_tracks, int n_src, int top, int min_votes, int min_overlap, void *ws, size_t ws_bytes, int32_t *out_track,
+                         int32_t *out_delta, int32_t *out_start, int32_t *out_len, float *out_score, int32_t *out_votes,
+                         grafp_stream_t stream);
+size_t grafp_self_match_workspace(const int64_t *src_rows, int n_src, int k, int min_votes);
+
 #ifdef __cplusplus
 }
 #endif
