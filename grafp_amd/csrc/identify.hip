@@ -11,9 +11,8 @@
 //     score = (sum_s <q[s], row[a + s]>) / o.  No row outside track t is ever read for a candidate of t;
 //   * the best candidate per track (highest score, then the smaller a) is kept, and the `top` tracks are written by
 //     score descending, then track ascending.
-// Arithmetic order (that of seq_rerank_kernel, so a run wholly inside one track scores bit-equal to seq_rerank's score of
-// the same start row): lane l of 32 owns dims 4l..4l+3 and runs ONE fmaf chain over (s ascending, e = 0..3); the 32
-// lane sums are combined by the butterfly 16, 8, 4, 2, 1; score = sum / o (IEEE division).
+// Arithmetic order of a score: span_sum of seqmatch.h, then score = sum / o (IEEE division) -- shared with
+// seq_rerank_kernel, so a run wholly inside one track scores bit-equal to seq_rerank's score of the same start row.
 //
 // One workgroup of 256 threads per item.  All per-item state lives in dynamic LDS sized by the launch's largest item,
 // Pmax = next power of two >= max(64, max_len * k) slots of 16 bytes:
@@ -41,64 +40,18 @@
 #include <math.h>
 
 #include "common.h"
+#include "seqmatch.h"
 
 namespace grafp {
 
-constexpr int ID_D = 128;
 constexpr int ID_THREADS = 256;
 constexpr int ID_MAX_LEN = 256;
 constexpr int ID_MAX_K = 32;
 constexpr int ID_MAX_KEYS = 8192;
 constexpr int ID_SHIFT = ID_MAX_LEN - 1;                 // a + ID_SHIFT >= 0 for every hit
 constexpr size_t ID_LDS = 160 * 1024 - 256;      // dynamic LDS budget (the static s_ncand sits next to it)
-constexpr unsigned long long ID_NONE = ~0ull;
-
-// ascending bitonic sort of P (power of two) 64-bit keys -- with idx: of (key, idx) pairs, ordered by key then idx
-template <bool kIdx>
-__device__ __forceinline__ void id_sort(unsigned long long *keys, unsigned short *idx, int P, int tid) {
-    for (int k2 = 2; k2 <= P; k2 <<= 1) {
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            for (int e = tid; e < P; e += ID_THREADS) {
-                const int partner = e ^ j;
-                if (partner > e) {
-                    const unsigned long long a = keys[e], b = keys[partner];
-                    const bool asc = (e & k2) == 0;
-                    bool gt = a > b;
-                    if (kIdx) gt = gt || (a == b && idx[e] > idx[partner]);
-                    if (gt == asc) {
-                        keys[e] = b;
-                        keys[partner] = a;
-                        if (kIdx) {
-                            const unsigned short t = idx[e];
-                            idx[e] = idx[partner];
-                            idx[partner] = t;
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
-__device__ __forceinline__ unsigned int id_ord(float f) {
-    const unsigned int u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float id_unord(unsigned int o) {
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
-
-// the track t in [lo, T) with first[t] <= r < first[t+1] (first[lo] <= r < first[T] = n)
-__device__ __forceinline__ int id_track_of(const int64_t *__restrict__ first, int lo, int T, int64_t r) {
-    int hi = T;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (first[mid] <= r) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
+// row pairs in flight in the score loop (seqmatch.h, span_sum): query rows in LDS / in global memory
+constexpr int ID_UNROLL_QLDS = 4, ID_UNROLL_QGLOBAL = 1;
 
 template <bool kQLds>
 __global__ __launch_bounds__(ID_THREADS) void identify_kernel(
@@ -123,13 +76,13 @@ __global__ __launch_bounds__(ID_THREADS) void identify_kernel(
     while (P < total) P <<= 1;                             // <= Pmax (host: max_len * k <= ID_MAX_KEYS)
     if (tid == 0) s_ncand = 0;
     if (kQLds) {
-        const float4 *src = reinterpret_cast<const float4 *>(q_rows + r0 * ID_D);
+        const float4 *src = reinterpret_cast<const float4 *>(q_rows + r0 * SEQ_D);
         float4 *dst = reinterpret_cast<float4 *>(sq);
-        for (int i = tid; i < ql * (ID_D / 4); i += ID_THREADS) dst[i] = src[i];
+        for (int i = tid; i < ql * (SEQ_D / 4); i += ID_THREADS) dst[i] = src[i];
     }
     // 1. hit keys; ids outside [0, n) are no hits
     for (int e = tid; e < P; e += ID_THREADS) {
-        unsigned long long key = ID_NONE;
+        unsigned long long key = SEQ_NONE;
         if (e < total) {
             const int s = e / k;
             const int64_t r = ids[(r0 + s) * k + (e - s * k)];
@@ -138,13 +91,13 @@ __global__ __launch_bounds__(ID_THREADS) void identify_kernel(
         keys[e] = key;
     }
     __syncthreads();
-    id_sort<false>(keys, nullptr, P, tid);
+    block_sort<ID_THREADS, false>(keys, nullptr, P, tid);
 
     // 2. one walker per alignment run (P / 256 <= 32 slots per thread: one mask bit each)
     unsigned int head = 0;
     for (int e = tid, it = 0; e < P; e += ID_THREADS, ++it) {
         const unsigned long long key = keys[e];
-        if (key != ID_NONE && (e == 0 || (keys[e - 1] >> 32) != (key >> 32))) head |= 1u << it;
+        if (key != SEQ_NONE && (e == 0 || (keys[e - 1] >> 32) != (key >> 32))) head |= 1u << it;
     }
     __syncthreads();
     for (int e = tid, it = 0; e < P; e += ID_THREADS, ++it) {
@@ -163,12 +116,12 @@ __global__ __launch_bounds__(ID_THREADS) void identify_kernel(
                     aux[start] = (unsigned int)t;
                     votes[start] = (unsigned short)nv;
                 }
-                t = id_track_of(first, end < 0 ? 0 : (t + 1 < T ? t + 1 : T - 1), T, r);   // (clamp: bad tables)
+                t = track_of(first, end < 0 ? 0 : (t + 1 < T ? t + 1 : T - 1), T, r);   // (clamp: bad tables)
                 end = first[t + 1];
                 start = f;
                 nv = 0;
             }
-            if (f != start) keys[f] = ID_NONE;
+            if (f != start) keys[f] = SEQ_NONE;
             ++nv;
         }
         keys[start] = hi << 32;
@@ -177,7 +130,7 @@ __global__ __launch_bounds__(ID_THREADS) void identify_kernel(
     }
     __syncthreads();
     for (int e = tid; e < P; e += ID_THREADS)
-        if (keys[e] != ID_NONE) idx[atomicAdd(&s_ncand, 1)] = (unsigned short)e;
+        if (keys[e] != SEQ_NONE) idx[atomicAdd(&s_ncand, 1)] = (unsigned short)e;
     __syncthreads();
     const int ncand = s_ncand;
 
@@ -185,7 +138,7 @@ __global__ __launch_bounds__(ID_THREADS) void identify_kernel(
     const int hw = tid >> 5, l = tid & 31;
     const int need_q = min_overlap > 0 ? min_overlap : ql;
     const float4 *rw4 = reinterpret_cast<const float4 *>(rows);
-    const float4 *q4 = kQLds ? reinterpret_cast<const float4 *>(sq) : reinterpret_cast<const float4 *>(q_rows + r0 * ID_D);
+    const float4 *q4 = kQLds ? reinterpret_cast<const float4 *>(sq) : reinterpret_cast<const float4 *>(q_rows + r0 * SEQ_D);
     for (int c = hw; c < ncand; c += ID_THREADS / 32) {
         const int e = idx[c];
         const int64_t a = (int64_t)(keys[e] >> 32) - ID_SHIFT;
@@ -198,23 +151,12 @@ __global__ __launch_bounds__(ID_THREADS) void identify_kernel(
         const int hi = (int)(f1 - a < ql ? f1 - a : ql);
         const int o = hi - lo;
         const bool ok = o >= 1 && o >= (need_q < L ? need_q : L);
-        float acc = 0.0f;
-        if (ok) {
-            for (int s = lo; s < hi; ++s) {
-                const float4 r = rw4[(a + s) * (ID_D / 4) + l];
-                const float4 qv = q4[s * (ID_D / 4) + l];
-                acc = __builtin_fmaf(qv.x, r.x, acc);
-                acc = __builtin_fmaf(qv.y, r.y, acc);
-                acc = __builtin_fmaf(qv.z, r.z, acc);
-                acc = __builtin_fmaf(qv.w, r.w, acc);
-            }
-        }
-#pragma unroll
-        for (int s = 16; s > 0; s >>= 1) acc += __shfl_xor(acc, s);      // stays inside the 32-lane half
+        const float acc = span_sum<kQLds ? ID_UNROLL_QLDS : ID_UNROLL_QGLOBAL>(
+            q4 + lo * (SEQ_D / 4) + l, rw4 + (a + lo) * (SEQ_D / 4) + l, ok ? o : 0);   // (not ok: no row is read)
         const float score = acc / (float)o;
         // every lane of the half-wave has read keys[e] and aux[e] before the shuffles above
         if (l == 0) {
-            keys[e] = ok ? (((unsigned long long)t << 32) | ~id_ord(score)) : ID_NONE;
+            keys[e] = ok ? (((unsigned long long)t << 32) | ~f32_ord(score)) : SEQ_NONE;
             aux[e] = (unsigned int)(a + ID_SHIFT);
         }
     }
@@ -223,30 +165,30 @@ __global__ __launch_bounds__(ID_THREADS) void identify_kernel(
     // 4. best candidate per track
     for (int e = tid; e < P; e += ID_THREADS) idx[e] = (unsigned short)e;
     __syncthreads();
-    id_sort<true>(keys, idx, P, tid);
+    block_sort<ID_THREADS, true>(keys, idx, P, tid);
     head = 0;
     for (int e = tid, it = 0; e < P; e += ID_THREADS, ++it) {
         const unsigned long long key = keys[e];
-        if (key != ID_NONE && (e == 0 || (keys[e - 1] >> 32) != (key >> 32))) head |= 1u << it;
+        if (key != SEQ_NONE && (e == 0 || (keys[e - 1] >> 32) != (key >> 32))) head |= 1u << it;
     }
     __syncthreads();
     for (int e = tid, it = 0; e < P; e += ID_THREADS, ++it) {
         const unsigned long long key = keys[e];
-        keys[e] = ((head >> it) & 1u) ? ((key << 32) | (key >> 32)) : ID_NONE;
+        keys[e] = ((head >> it) & 1u) ? ((key << 32) | (key >> 32)) : SEQ_NONE;
     }
     __syncthreads();
 
     // 5. the `top` tracks: score descending, track ascending
-    id_sort<true>(keys, idx, P, tid);
+    block_sort<ID_THREADS, true>(keys, idx, P, tid);
     if (tid < top) {
         const unsigned long long key = keys[tid];          // top <= 64 <= P
         const size_t o = (size_t)item * top + tid;
-        if (key != ID_NONE) {
+        if (key != SEQ_NONE) {
             const int t = (int)(key & 0xffffffffull);
             const int slot = idx[tid];
             out_track[o] = t;
             out_offset[o] = (int32_t)((int64_t)aux[slot] - ID_SHIFT - first[t]);
-            out_score[o] = id_unord(~(unsigned int)(key >> 32));
+            out_score[o] = ord_f32(~(unsigned int)(key >> 32));
             out_votes[o] = (int32_t)votes[slot];
         } else {
             out_track[o] = -1;
@@ -267,7 +209,7 @@ int identify_launch(const float *rows, int64_t n, const int64_t *first, int T, c
     if (n_items == 0) return GRAFP_OK;
     int Pmax = 64;
     while (Pmax < max_len * k) Pmax <<= 1;
-    const size_t slots = (size_t)16 * Pmax, qbytes = (size_t)max_len * ID_D * sizeof(float);
+    const size_t slots = (size_t)16 * Pmax, qbytes = (size_t)max_len * SEQ_D * sizeof(float);
     const bool q_lds = slots + qbytes <= ID_LDS;
     const size_t lds = q_lds ? slots + qbytes : slots;
     const void *fn = q_lds ? (const void *)identify_kernel<true> : (const void *)identify_kernel<false>;

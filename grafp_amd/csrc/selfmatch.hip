@@ -11,9 +11,8 @@
 //     (sum_{i = i_lo .. i_hi} <row[first[a] + i], row[first[b] + i + delta]>) / m;
 //   * per partner b the eligible candidate with the highest score is kept (ties: the smaller delta), and the `top`
 //     partners are written by score descending, then b ascending.
-// Arithmetic order (that of identify_kernel, so a span identify would also score gets the same bits): lane l of 32 owns
-// dims 4l..4l+3 and runs ONE fmaf chain over (i ascending, e = 0..3); the 32 lane sums are combined by the butterfly
-// 16, 8, 4, 2, 1; score = sum / m (IEEE division).
+// Arithmetic order of a score: span_sum of seqmatch.h, then score = sum / m (IEEE division) -- shared with
+// identify_kernel, so a span identify would also score gets the same bits.
 //
 // One workgroup of 512 threads per source track.  Its hit keys (a_g + L) << 32 | i, with a_g = r - i the global row
 // where the source's row 0 would sit, number N0 = L * k; they are sorted ascending by a bitonic network over
@@ -44,17 +43,17 @@
 #include <math.h>
 
 #include "common.h"
+#include "seqmatch.h"
 
 namespace grafp {
 
-constexpr int SM_D = 128;
 constexpr int SM_THREADS = 512;
 constexpr int SM_MAX_K = 32;
 constexpr int SM_MAX_TOP = 64;
 constexpr int64_t SM_PIECE = 16384;                         // keys per LDS piece
 constexpr size_t SM_LDS = (size_t)SM_PIECE * 8;            // 128 KiB of dynamic LDS
 constexpr int SM_PLAN_THREADS = 1024;
-constexpr unsigned long long SM_NONE = ~0ull;
+constexpr int SM_UNROLL = 4;                                // row pairs in flight in the score loop (span_sum)
 
 __host__ __device__ inline int64_t sm_pow2(int64_t x) {
     int64_t p = 64;
@@ -75,37 +74,10 @@ __host__ __device__ inline int64_t sm_units(int64_t L, int k, int min_votes) {
 // bytes of the workspace header (n_src + 1 int64 region starts), rounded up to 256
 __host__ __device__ inline int64_t sm_head_bytes(int n_src) { return ((int64_t)(n_src + 1) * 8 + 255) / 256 * 256; }
 
-__device__ __forceinline__ unsigned int sm_ord(float f) {
-    const unsigned int u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// the track t in [lo, T) with first[t] <= r < first[t+1] (first[lo] <= r < first[T] = n)
-__device__ __forceinline__ int sm_track_of(const int64_t *__restrict__ first, int lo, int T, int64_t r) {
-    int hi = T;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (first[mid] <= r) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// one bitonic stage (merge size k2, partner distance j) over keys[0, cnt) whose slot 0 is global slot g0
+// one bitonic stage over keys[0, cnt) whose slot 0 is global slot g0
 __device__ __forceinline__ void sm_stage(unsigned long long *keys, int64_t cnt, int64_t g0, int64_t k2, int64_t j,
                                          int tid) {
-    for (int64_t e = tid; e < cnt; e += SM_THREADS) {
-        const int64_t p = e ^ j;
-        if (p > e) {
-            const unsigned long long x = keys[e], y = keys[p];
-            const bool asc = ((g0 + e) & k2) == 0;
-            if ((x > y) == asc) {
-                keys[e] = y;
-                keys[p] = x;
-            }
-        }
-    }
-    __syncthreads();
+    bitonic_stage<SM_THREADS, false, int64_t>(keys, nullptr, cnt, g0, k2, j, tid);
 }
 
 // ascending sort of P (a power of two >= 64) keys: in place in LDS (in_lds, P <= SM_PIECE), or in global memory with
@@ -113,8 +85,7 @@ __device__ __forceinline__ void sm_stage(unsigned long long *keys, int64_t cnt, 
 __device__ __forceinline__ void sm_sort(unsigned long long *keys, int64_t P, unsigned long long *lds, bool in_lds,
                                         int tid) {
     if (in_lds) {
-        for (int64_t k2 = 2; k2 <= P; k2 <<= 1)
-            for (int64_t j = k2 >> 1; j > 0; j >>= 1) sm_stage(keys, P, 0, k2, j, tid);
+        block_sort<SM_THREADS, false>(keys, nullptr, P, tid);
         return;
     }
     const int64_t pc = P < SM_PIECE ? P : SM_PIECE;
@@ -139,17 +110,30 @@ __device__ __forceinline__ void sm_sort(unsigned long long *keys, int64_t P, uns
 __device__ __forceinline__ unsigned int sm_best(const unsigned long long *k4, int64_t P, int64_t e,
                                                 const unsigned int *rec) {
     const unsigned long long b = k4[e] >> 32;
-    unsigned int best = (unsigned int)k4[e], bo = sm_ord(__uint_as_float(rec[6 * (int64_t)best + 5]));
+    unsigned int best = (unsigned int)k4[e], bo = f32_ord(__uint_as_float(rec[6 * (int64_t)best + 5]));
     for (int64_t f = e + 1; f < P; ++f) {
         const unsigned long long key = k4[f];
         if ((key >> 32) != b) break;
-        const unsigned int c = (unsigned int)key, o = sm_ord(__uint_as_float(rec[6 * (int64_t)c + 5]));
+        const unsigned int c = (unsigned int)key, o = f32_ord(__uint_as_float(rec[6 * (int64_t)c + 5]));
         if (o > bo || (o == bo && rec[6 * (int64_t)c + 1] < rec[6 * (int64_t)best + 1])) {
             best = c;
             bo = o;
         }
     }
     return best;
+}
+
+// an empty result slot (track -1; -2 marks a source whose region does not fit the workspace)
+__device__ __forceinline__ void sm_pad(size_t o, int32_t track, int32_t *__restrict__ out_track,
+                                       int32_t *__restrict__ out_delta, int32_t *__restrict__ out_start,
+                                       int32_t *__restrict__ out_len, float *__restrict__ out_score,
+                                       int32_t *__restrict__ out_votes) {
+    out_track[o] = track;
+    out_delta[o] = INT_MIN;
+    out_start[o] = -1;
+    out_len[o] = 0;
+    out_score[o] = -INFINITY;
+    out_votes[o] = 0;
 }
 
 // exclusive scan of the per-source region sizes into the workspace header (one workgroup)
@@ -195,12 +179,7 @@ __global__ __launch_bounds__(SM_THREADS) void self_match_kernel(
     if (L64 <= 0 || N0 > INT_MAX || head_units + o1 > cap_units) {
         if (tid < top) {
             const size_t o = (size_t)src * top + tid;
-            out_track[o] = (L64 > 0 && tid == 0) ? -2 : -1;
-            out_delta[o] = INT_MIN;
-            out_start[o] = -1;
-            out_len[o] = 0;
-            out_score[o] = -INFINITY;
-            out_votes[o] = 0;
+            sm_pad(o, (L64 > 0 && tid == 0) ? -2 : -1, out_track, out_delta, out_start, out_len, out_score, out_votes);
         }
         return;
     }
@@ -214,7 +193,7 @@ __global__ __launch_bounds__(SM_THREADS) void self_match_kernel(
 
     // 1. hit keys; ids outside [0, n) and inside the source track are no hits
     for (int64_t e = tid; e < P1; e += SM_THREADS) {
-        unsigned long long key = SM_NONE;
+        unsigned long long key = SEQ_NONE;
         if (e < N0) {
             const int i = (int)e / k;                     // e < N0 <= INT_MAX
             const int64_t r = ids[(fa + i) * k + ((int)e - i * k)];
@@ -230,15 +209,15 @@ __global__ __launch_bounds__(SM_THREADS) void self_match_kernel(
     // 2. one walker per alignment run; eligible candidates become records
     for (int64_t e = tid; e < P1; e += SM_THREADS) {
         const unsigned long long key = K1[e];
-        if (key == SM_NONE || (e > 0 && (K1[e - 1] >> 32) == (key >> 32))) continue;
+        if (key == SEQ_NONE || (e > 0 && (K1[e - 1] >> 32) == (key >> 32))) continue;
         const unsigned long long hi = key >> 32;
         const int64_t ag = (int64_t)hi - L64;
         int t = 0, nv = 0;
         int64_t end = -1;
         unsigned int ilo = 0, ihi = 0;
         for (int64_t f = e;; ++f) {
-            const unsigned long long kf = f < P1 ? K1[f] : SM_NONE;
-            const bool more = kf != SM_NONE && (kf >> 32) == hi;
+            const unsigned long long kf = f < P1 ? K1[f] : SEQ_NONE;
+            const bool more = kf != SEQ_NONE && (kf >> 32) == hi;
             const int64_t r = ag + (int64_t)(unsigned int)kf;
             if (!more || r >= end) {                          // the run ends, or crosses into a later track
                 if (nv >= min_votes && (int)(ihi - ilo) + 1 >= min_overlap) {
@@ -254,7 +233,7 @@ __global__ __launch_bounds__(SM_THREADS) void self_match_kernel(
                     }
                 }
                 if (!more) break;
-                t = sm_track_of(first, end < 0 ? 0 : (t + 1 < T ? t + 1 : T - 1), T, r);
+                t = track_of(first, end < 0 ? 0 : (t + 1 < T ? t + 1 : T - 1), T, r);
                 end = first[t + 1];
                 nv = 0;
                 ilo = (unsigned int)kf;
@@ -268,12 +247,7 @@ __global__ __launch_bounds__(SM_THREADS) void self_match_kernel(
     if (nc == 0) {
         if (tid < top) {
             const size_t o = (size_t)src * top + tid;
-            out_track[o] = -1;
-            out_delta[o] = INT_MIN;
-            out_start[o] = -1;
-            out_len[o] = 0;
-            out_score[o] = -INFINITY;
-            out_votes[o] = 0;
+            sm_pad(o, -1, out_track, out_delta, out_start, out_len, out_score, out_votes);
         }
         return;
     }
@@ -285,19 +259,9 @@ __global__ __launch_bounds__(SM_THREADS) void self_match_kernel(
         const unsigned int *rc = rec + 6 * (int64_t)c;
         const int64_t ag = (int64_t)rc[1] - L64;
         const int ilo = (int)rc[2], m = (int)rc[3];
-        const float4 *x = rw4 + (fa + ilo) * (SM_D / 4) + l;
-        const float4 *y = rw4 + (ag + ilo) * (SM_D / 4) + l;
-        float acc = 0.0f;
-#pragma unroll 4
-        for (int i = 0; i < m; ++i) {
-            const float4 q = x[(int64_t)i * (SM_D / 4)], r = y[(int64_t)i * (SM_D / 4)];
-            acc = __builtin_fmaf(q.x, r.x, acc);
-            acc = __builtin_fmaf(q.y, r.y, acc);
-            acc = __builtin_fmaf(q.z, r.z, acc);
-            acc = __builtin_fmaf(q.w, r.w, acc);
-        }
-#pragma unroll
-        for (int s = 16; s > 0; s >>= 1) acc += __shfl_xor(acc, s);      // stays inside the 32-lane half
+        const float4 *x = rw4 + (fa + ilo) * (SEQ_D / 4) + l;
+        const float4 *y = rw4 + (ag + ilo) * (SEQ_D / 4) + l;
+        const float acc = span_sum<SM_UNROLL>(x, y, m);
         if (l == 0) rec[6 * (int64_t)c + 5] = __float_as_uint(acc / (float)m);
     }
     __syncthreads();
@@ -307,16 +271,16 @@ __global__ __launch_bounds__(SM_THREADS) void self_match_kernel(
     const bool l2 = 2 * P2 <= SM_PIECE;
     unsigned long long *K4 = l2 ? sm_lds : k4g, *K5 = l2 ? sm_lds + P2 : k5g;
     for (int64_t e = tid; e < P2; e += SM_THREADS)
-        K4[e] = e < nc ? (((unsigned long long)rec[6 * e] << 32) | (unsigned int)e) : SM_NONE;
+        K4[e] = e < nc ? (((unsigned long long)rec[6 * e] << 32) | (unsigned int)e) : SEQ_NONE;
     __syncthreads();
     if (l2) sm_sort(sm_lds, P2, sm_lds, true, tid);
     else sm_sort(k4g, P2, sm_lds, false, tid);
     for (int64_t e = tid; e < P2; e += SM_THREADS) {
         const unsigned long long key = K4[e];
-        unsigned long long out = SM_NONE;
-        if (key != SM_NONE && (e == 0 || (K4[e - 1] >> 32) != (key >> 32))) {
+        unsigned long long out = SEQ_NONE;
+        if (key != SEQ_NONE && (e == 0 || (K4[e - 1] >> 32) != (key >> 32))) {
             const unsigned int best = sm_best(K4, P2, e, rec);
-            out = ((unsigned long long)~sm_ord(__uint_as_float(rec[6 * (int64_t)best + 5])) << 32) | (unsigned int)e;
+            out = ((unsigned long long)~f32_ord(__uint_as_float(rec[6 * (int64_t)best + 5])) << 32) | (unsigned int)e;
         }
         K5[e] = out;
     }
@@ -328,7 +292,7 @@ __global__ __launch_bounds__(SM_THREADS) void self_match_kernel(
     if (tid < top) {
         const size_t o = (size_t)src * top + tid;
         const unsigned long long key = K5[tid];              // top <= 64 <= P2
-        if (key != SM_NONE) {
+        if (key != SEQ_NONE) {
             const unsigned int c = sm_best(K4, P2, (int64_t)(unsigned int)key, rec);
             const unsigned int *rc = rec + 6 * (int64_t)c;
             const int b = (int)rc[0];
@@ -339,12 +303,7 @@ __global__ __launch_bounds__(SM_THREADS) void self_match_kernel(
             out_score[o] = __uint_as_float(rc[5]);
             out_votes[o] = (int32_t)rc[4];
         } else {
-            out_track[o] = -1;
-            out_delta[o] = INT_MIN;
-            out_start[o] = -1;
-            out_len[o] = 0;
-            out_score[o] = -INFINITY;
-            out_votes[o] = 0;
+            sm_pad(o, -1, out_track, out_delta, out_start, out_len, out_score, out_votes);
         }
     }
 }

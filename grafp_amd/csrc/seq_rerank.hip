@@ -11,48 +11,18 @@
 // One workgroup per item: the item's query rows and candidate keys live in LDS; candidates are de-duplicated with a
 // block-wide bitonic sort of 64-bit keys, scored one per half-wave with coalesced 512-byte row reads out of the
 // resident database, and ranked with a second sort of (~score, id) keys.
-// Arithmetic order (restated in oracle/csrc/seq_rerank.c): lane l of 32 owns dims 4l..4l+3 and runs ONE fmaf chain
-// over (t ascending, e = 0..3); the 32 lane sums are combined by the butterfly s = 16, 8, 4, 2, 1 (x[l] + x[l ^ s]);
-// score = sum / rows (IEEE division).
+// Arithmetic order of a score: span_sum of seqmatch.h, then score = sum / rows (IEEE division); restated in
+// oracle/csrc/seq_rerank.c.
 #include <math.h>
 
 #include "common.h"
+#include "seqmatch.h"
 
 namespace grafp {
 
-constexpr int RR_D = 128;
 constexpr int RR_MAX_LEN = 64;       // query segments per item
 constexpr int RR_MAX_CAND = 2048;    // ql * k
-constexpr unsigned long long RR_NONE = ~0ull;
-
-// ascending bitonic sort of P (power of two) 64-bit keys in LDS by the whole workgroup
-__device__ __forceinline__ void block_sort_u64(unsigned long long *keys, int P, int tid, int nthreads) {
-    for (int k2 = 2; k2 <= P; k2 <<= 1) {
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            for (int e = tid; e < P; e += nthreads) {
-                const int partner = e ^ j;
-                if (partner > e) {
-                    const unsigned long long a = keys[e], b = keys[partner];
-                    const bool asc = (e & k2) == 0;
-                    if ((a > b) == asc) {
-                        keys[e] = b;
-                        keys[partner] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
-// monotone map f32 -> u32 (larger float = larger integer), and back
-__device__ __forceinline__ unsigned int f32_ord(float f) {
-    const unsigned int u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord_f32(unsigned int o) {
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
+constexpr int RR_UNROLL = 4;         // row pairs in flight in the score loop (seqmatch.h, span_sum)
 
 // Sharded use: `recon` holds global rows [row_base, row_base + n_rows) of an n-row index; only candidates whose start id
 // lies in [id_lo, id_hi) are scored here (the shard that owns the start row, which also holds a halo of the next
@@ -65,7 +35,7 @@ __global__ __launch_bounds__(256) void seq_rerank_kernel(const float *__restrict
                                                          const int *__restrict__ item_len, int max_len, int top,
                                                          int64_t *__restrict__ out_ids,
                                                          float *__restrict__ out_scores) {
-    __shared__ __attribute__((aligned(16))) float sq[RR_MAX_LEN * RR_D];
+    __shared__ __attribute__((aligned(16))) float sq[RR_MAX_LEN * SEQ_D];
     __shared__ unsigned long long keys[RR_MAX_CAND];
     __shared__ int cand[RR_MAX_CAND];
     __shared__ int s_ncand;
@@ -78,12 +48,12 @@ __global__ __launch_bounds__(256) void seq_rerank_kernel(const float *__restrict
     if (tid == 0) s_ncand = 0;
     // query rows -> LDS (coalesced), candidate start ids -> keys
     {
-        const float4 *src = reinterpret_cast<const float4 *>(q_rows + r0 * RR_D);
+        const float4 *src = reinterpret_cast<const float4 *>(q_rows + r0 * SEQ_D);
         float4 *dst = reinterpret_cast<float4 *>(sq);
-        for (int i = tid; i < ql * (RR_D / 4); i += 256) dst[i] = src[i];
+        for (int i = tid; i < ql * (SEQ_D / 4); i += 256) dst[i] = src[i];
     }
     for (int e = tid; e < P; e += 256) {
-        unsigned long long key = RR_NONE;
+        unsigned long long key = SEQ_NONE;
         if (e < total) {
             const int t = e / k;
             const int64_t id = ids[(r0 + t) * k + (e - t * k)];
@@ -93,18 +63,18 @@ __global__ __launch_bounds__(256) void seq_rerank_kernel(const float *__restrict
         keys[e] = key;
     }
     __syncthreads();
-    block_sort_u64(keys, P, tid, 256);
+    block_sort<256, false>(keys, nullptr, P, tid);
     // unique (eval.py:277); the order of the compacted list is irrelevant, ranking re-sorts with the id in the key
     for (int e = tid; e < P; e += 256) {
         const unsigned long long key = keys[e];
-        if (key != RR_NONE && (e == 0 || keys[e - 1] != key)) cand[atomicAdd(&s_ncand, 1)] = (int)key;
+        if (key != SEQ_NONE && (e == 0 || keys[e - 1] != key)) cand[atomicAdd(&s_ncand, 1)] = (int)key;
     }
     __syncthreads();
     const int ncand = s_ncand;
     int P2 = 64;
     while (P2 < ncand) P2 <<= 1;
     __syncthreads();                                           // keys are rewritten below
-    for (int e = tid; e < P2; e += 256) keys[e] = RR_NONE;
+    for (int e = tid; e < P2; e += 256) keys[e] = SEQ_NONE;
     __syncthreads();
     // scores: one candidate per half-wave at a time
     const int hw = tid >> 5, l = tid & 31;
@@ -116,25 +86,15 @@ __global__ __launch_bounds__(256) void seq_rerank_kernel(const float *__restrict
         int m = left < ql ? (int)left : ql;
         const int64_t have = row_base + n_rows - (int64_t)cid;        // rows of this sequence present locally
         if (have < m) m = have > 0 ? (int)have : 0;                   // (never with a halo of max_len - 1 rows)
-        float acc = 0.0f;
-        for (int t = 0; t < m; ++t) {
-            const float4 r = rc4[((int64_t)cid - row_base + t) * (RR_D / 4) + l];
-            const float4 qv = sq4[t * (RR_D / 4) + l];
-            acc = __builtin_fmaf(qv.x, r.x, acc);
-            acc = __builtin_fmaf(qv.y, r.y, acc);
-            acc = __builtin_fmaf(qv.z, r.z, acc);
-            acc = __builtin_fmaf(qv.w, r.w, acc);
-        }
-#pragma unroll
-        for (int s = 16; s > 0; s >>= 1) acc += __shfl_xor(acc, s);      // stays inside the 32-lane half
+        const float acc = span_sum<RR_UNROLL>(sq4 + l, rc4 + ((int64_t)cid - row_base) * (SEQ_D / 4) + l, m);
         const float score = acc / (float)m;
         if (l == 0) keys[c] = ((unsigned long long)(~f32_ord(score)) << 32) | (unsigned int)cid;
     }
     __syncthreads();
-    block_sort_u64(keys, P2, tid, 256);
+    block_sort<256, false>(keys, nullptr, P2, tid);
     if (tid < top) {
-        const unsigned long long key = tid < P2 ? keys[tid] : RR_NONE;
-        const bool have = key != RR_NONE;
+        const unsigned long long key = tid < P2 ? keys[tid] : SEQ_NONE;
+        const bool have = key != SEQ_NONE;
         out_ids[(size_t)item * top + tid] = have ? (int64_t)(key & 0xffffffffull) : (int64_t)-1;
         out_scores[(size_t)item * top + tid] = have ? ord_f32(~(unsigned int)(key >> 32)) : -INFINITY;
     }

@@ -1477,6 +1477,13 @@ def merge_topk(part_d, part_i):
     return out_d, out_i
 
 
+def _check_items_inside(op, item_row, item_len, n_qrows):
+    """Refuses items that do not lie inside the n_qrows query rows (two host synchronisations)."""
+    if int((item_row.to(torch.int64) + item_len.to(torch.int64)).max().item()) > n_qrows or \
+            int(item_row.min().item()) < 0:
+        raise ValueError(f"{op}: an item reaches outside q_rows")
+
+
 def seq_rerank(index_rows, q_rows, topk_ids, item_row, item_len, top=10, shard=None, max_len=None):
     """Sequence-level rerank of batched segment-search results (eval.py:272-290, one workgroup per item).
     index_rows (n,128) f32 resident database, q_rows (n_q,128) f32, topk_ids (n_q,k) int64, item_row (n_items) int64
@@ -1500,8 +1507,7 @@ def seq_rerank(index_rows, q_rows, topk_ids, item_row, item_len, top=10, shard=N
         # convenience path with three host synchronisations (length bound + range check); callers that know the longest
         # sequence pass it (eval.py, dist.py, bench.py do) and stay asynchronous / graph-capturable like the other ops
         max_len = int(item_len.max().item())
-        if int((item_row + item_len.to(torch.int64)).max().item()) > q_rows.shape[0] or int(item_row.min().item()) < 0:
-            raise ValueError("seq_rerank: an item reaches outside q_rows")
+        _check_items_inside("seq_rerank", item_row, item_len, q_rows.shape[0])
     max_len = int(max_len)
     with _timed("seq_rerank", (n_items, max_len, topk_ids.shape[1])):
         if shard is None:
@@ -1521,11 +1527,13 @@ IDENTIFY_MAX_LEN, IDENTIFY_MAX_K, IDENTIFY_MAX_KEYS = 256, 32, 8192      # ident
 
 
 def check_track_table(first, n):
-    """Refuses a track table that is not (T + 1) int64 row starts with first[0] = 0, first[T] = n, non-decreasing."""
+    """Refuses a track table that is not (T + 1) int64 row starts with first[0] = 0, first[T] = n, non-decreasing;
+    returns it as a host int64 tensor."""
     f = torch.as_tensor(first).detach().to("cpu", torch.int64).reshape(-1)
     if f.numel() < 2 or int(f[0]) != 0 or int(f[-1]) != int(n) or bool((f[1:] < f[:-1]).any()):
         raise ValueError(f"identify: the track table must run from 0 to n = {int(n)} and never decrease "
                          f"(got {f.numel()} entries{', ' + str(int(f[0])) + ' .. ' + str(int(f[-1])) if f.numel() else ''})")
+    return f
 
 
 def identify(index_rows, track_first_row, q_rows, topk_ids, item_row, item_len, top=5, min_overlap=None, max_len=None):
@@ -1551,9 +1559,7 @@ def identify(index_rows, track_first_row, q_rows, topk_ids, item_row, item_len, 
     if max_len is None and n_items:
         max_len = max(1, int(item_len.max().item()))
         check_track_table(track_first_row, index_rows.shape[0])
-        if int((item_row.to(torch.int64) + item_len.to(torch.int64)).max().item()) > q_rows.shape[0] or \
-                int(item_row.min().item()) < 0:
-            raise ValueError("identify: an item reaches outside q_rows")
+        _check_items_inside("identify", item_row, item_len, q_rows.shape[0])
     if max_len is not None and (int(max_len) > IDENTIFY_MAX_LEN or int(max_len) * k > IDENTIFY_MAX_KEYS):
         raise ValueError(f"identify: items of {int(max_len)} segments with k={k} exceed {IDENTIFY_MAX_LEN} segments "
                          f"or {IDENTIFY_MAX_KEYS} hits per item")
@@ -1610,8 +1616,7 @@ def self_match(index_rows, track_first_row, topk_ids, tracks=None, top=8, min_vo
     n = int(index_rows.shape[0])
     if n < 1 or int(topk_ids.shape[0]) != n:
         raise ValueError(f"self_match: topk_ids has {int(topk_ids.shape[0])} rows for a library of {n}")
-    check_track_table(track_first_row, n)
-    first_h = torch.as_tensor(track_first_row).detach().to("cpu", torch.int64).reshape(-1)
+    first_h = check_track_table(track_first_row, n)
     T = first_h.numel() - 1
     src = torch.arange(T, dtype=torch.int64) if tracks is None else \
         torch.as_tensor(tracks).detach().to("cpu", torch.int64).reshape(-1)

@@ -1,5 +1,6 @@
 """Shared helpers for the test-suite (inputs by name, state dicts from the committed manifest)."""
 import os
+import subprocess
 
 import numpy as np
 import torch
@@ -12,6 +13,26 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 
 def golden(name):
     return np.load(os.path.join(GOLD, name), allow_pickle=False)
+
+
+def shipped_asm(name):
+    """Device assembly of grafp_amd/csrc/<name>.hip, compiled by the shipped object's own command (make -n), which must
+    carry the no-packed-f32 switch (Makefile NOPK)."""
+    csrc = os.path.join(ROOT, "grafp_amd", "csrc")
+    res = subprocess.run(["make", "-n", "-B", "-C", csrc, f"_obj/{name}.o"], stdout=subprocess.PIPE,
+                         stderr=subprocess.STDOUT, text=True)
+    cmd = next(ln for ln in res.stdout.splitlines() if "hipcc" in ln and f"{name}.hip" in ln).split()
+    assert "-packed-fp32-ops" in cmd
+    asm_path = os.path.join(csrc, "_obj", f"{name}_check.s")
+    cmd = cmd[:cmd.index("-c")] + ["--cuda-device-only", "-S", f"{name}.hip", "-o", asm_path]
+    try:
+        r = subprocess.run(cmd, cwd=csrc, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        assert r.returncode == 0, r.stdout[-2000:]
+        with open(asm_path) as f:
+            return f.read()
+    finally:
+        if os.path.exists(asm_path):
+            os.remove(asm_path)
 
 
 def manifest_shapes():

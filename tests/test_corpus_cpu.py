@@ -4,14 +4,13 @@ import json
 import math
 import os
 import re
-import subprocess
 import wave
 
 import numpy as np
 import pytest
 import torch
 
-from _common import ROOT
+from _common import shipped_asm
 from grafp_amd import data, ops
 
 RATES = (44100, 48000, 22050, 32000, 8000, 11025)
@@ -141,21 +140,7 @@ def test_epoch_plan_disjoint_drop_last_and_shared_across_ranks():
 def test_corpus_kernels_have_no_packed_high_register_select():
     """The shipped object's own command (make -n), compiled to device assembly: no packed-f32 instruction at all in
     corpus.hip, so none whose low lane reads the high register of a pair."""
-    csrc = os.path.join(ROOT, "grafp_amd", "csrc")
-    res = subprocess.run(["make", "-n", "-B", "-C", csrc, "_obj/corpus.o"], stdout=subprocess.PIPE,
-                         stderr=subprocess.STDOUT, text=True)
-    cmd = next(ln for ln in res.stdout.splitlines() if "hipcc" in ln and "corpus.hip" in ln).split()
-    assert "-packed-fp32-ops" in cmd
-    i = cmd.index("-c")
-    asm_path = os.path.join(csrc, "_obj", "corpus_check.s")
-    cmd = cmd[:i] + ["--cuda-device-only", "-S", "corpus.hip", "-o", asm_path]
-    try:
-        r = subprocess.run(cmd, cwd=csrc, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout[-2000:]
-        asm = open(asm_path).read()
-    finally:
-        if os.path.exists(asm_path):
-            os.remove(asm_path)
+    asm = shipped_asm("corpus")
     kernels = re.findall(r"^(_ZN5grafp\w+):", asm, flags=re.M)
     assert any("resample_kernel" in k for k in kernels) and any("draw_pairs_kernel" in k for k in kernels)
     assert not re.search(r"^\s*v_pk_\w+_f32", asm, flags=re.M)

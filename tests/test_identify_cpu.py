@@ -5,13 +5,12 @@ import ctypes
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from _common import ROOT
+from _common import shipped_asm
 from _identify_ref import identify_item, identify_ref, score_run
 from grafp_amd import library, ops
 from grafp_amd.util import load_config
@@ -242,21 +241,7 @@ def test_abi_entry_refuses_out_of_range_launches_without_a_gpu():
 def test_identify_kernel_has_no_packed_f32_instructions():
     """The shipped object's own command (make -n), compiled to device assembly: no packed-f32 instruction in
     identify.hip."""
-    csrc = os.path.join(ROOT, "grafp_amd", "csrc")
-    res = subprocess.run(["make", "-n", "-B", "-C", csrc, "_obj/identify.o"], stdout=subprocess.PIPE,
-                         stderr=subprocess.STDOUT, text=True)
-    cmd = next(ln for ln in res.stdout.splitlines() if "hipcc" in ln and "identify.hip" in ln).split()
-    assert "-packed-fp32-ops" in cmd
-    i = cmd.index("-c")
-    asm_path = os.path.join(csrc, "_obj", "identify_check.s")
-    cmd = cmd[:i] + ["--cuda-device-only", "-S", "identify.hip", "-o", asm_path]
-    try:
-        r = subprocess.run(cmd, cwd=csrc, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout[-2000:]
-        asm = open(asm_path).read()
-    finally:
-        if os.path.exists(asm_path):
-            os.remove(asm_path)
+    asm = shipped_asm("identify")
     kernels = re.findall(r"^(_ZN5grafp\w+):", asm, flags=re.M)
     assert sum("identify_kernel" in k for k in kernels) == 2
     assert not re.search(r"^\s*v_pk_\w+_f32", asm, flags=re.M)

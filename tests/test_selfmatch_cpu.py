@@ -2,15 +2,13 @@
 FingerprintLibrary.self_matches / duplicate_groups): the numpy restatement on hand-built cases, the refusal paths, the
 C ABI entry, the shipped assembly and the command line.  No GPU call is made."""
 import ctypes
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from _common import ROOT
+from _common import shipped_asm
 from _identify_ref import identify_item, score_run
 from _selfmatch_ref import self_match_ref, self_match_track
 from grafp_amd import library, ops
@@ -207,21 +205,7 @@ def test_workspace_is_exactly_what_the_launch_lays_out():
 def test_selfmatch_kernel_has_no_packed_f32_instructions():
     """The shipped object's own command (make -n), compiled to device assembly: no packed-f32 instruction in
     selfmatch.hip."""
-    csrc = os.path.join(ROOT, "grafp_amd", "csrc")
-    res = subprocess.run(["make", "-n", "-B", "-C", csrc, "_obj/selfmatch.o"], stdout=subprocess.PIPE,
-                         stderr=subprocess.STDOUT, text=True)
-    cmd = next(ln for ln in res.stdout.splitlines() if "hipcc" in ln and "selfmatch.hip" in ln).split()
-    assert "-packed-fp32-ops" in cmd
-    i = cmd.index("-c")
-    asm_path = os.path.join(csrc, "_obj", "selfmatch_check.s")
-    cmd = cmd[:i] + ["--cuda-device-only", "-S", "selfmatch.hip", "-o", asm_path]
-    try:
-        r = subprocess.run(cmd, cwd=csrc, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout[-2000:]
-        asm = open(asm_path).read()
-    finally:
-        if os.path.exists(asm_path):
-            os.remove(asm_path)
+    asm = shipped_asm("selfmatch")
     kernels = re.findall(r"^(_ZN5grafp\w+):", asm, flags=re.M)
     assert sum("self_match_kernel" in k for k in kernels) == 1
     assert not re.search(r"^\s*v_pk_\w+_f32", asm, flags=re.M)
