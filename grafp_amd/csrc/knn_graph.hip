@@ -4,32 +4,24 @@
 // (/root/reference/encoder/gcn_lib/torch_edge.py:270-284, 70-103, 7-18): the reference materialises
 // the (B,N,N) distance matrix (1.07 GB at B=256, N=1024) and runs torch.topk over it; here a
 // workgroup owns 128 query nodes of one clip, streams the clip's candidates through LDS in
-// 32-channel x 128-node tiles, forms the Gram tile with exact-f32 MFMA (v_mfma_f32_32x32x2_f32:
-// bitwise a c-ordered fmaf chain, which is the order oracle/csrc/knn_graph.c fixes) and keeps a
-// per-lane top-k in registers.  Only (B,N,k) indices are written.
+// 32-channel x 128-node tiles, forms the Gram tile with exact-f32 MFMA (v_mfma_f32_32x32x2_f32) and keeps a
+// per-lane top-k in registers.  Only (B,N,k) indices are written.  The arithmetic order (that of
+// oracle/csrc/knn_graph.c) is stated once, in knngraph.h.
 //
 // Roofline: 2*N^2*C flops per clip against 4*C*N + 8*k*N bytes (63-468 flop/B) -> bound by the f32
 // matrix rate (157.3 TFLOP/s), not HBM.  See DESIGN.md "knn_topk_kernel".
-#include <math.h>
-
 #include <type_traits>
 
-#include "common.h"
+#include "knngraph.h"
 
 namespace grafp {
 
-constexpr int TQ = 128;  // query nodes per workgroup (32 per wave)
-constexpr int TR = 128;  // candidate nodes per pass
 constexpr int KC = 32;   // channels per LDS chunk
 
 // ---- pass 1: channel-L2 normalisation (torch_edge.py:281) and squared norms -------------------
 // One thread per node; lanes run over consecutive nodes so every load/store is coalesced.  The input may be
 // any (b, c) strided view with N contiguous -- (B,C,N) or the GEMM-friendly (C,B,N) -- in f32 or bf16; xn/sq are
-// always written as contiguous (B,C,N)/(B,N) f32 for pass 2.  Loads are issued 8 channels ahead of the
-// dependent fmaf chain (the chain order is still c ascending).
-__device__ __forceinline__ float ld_as_f32(const float *p) { return *p; }
-__device__ __forceinline__ float ld_as_f32(const unsigned short *p) { return __uint_as_float(((unsigned)*p) << 16); }
-
+// always written as contiguous (B,C,N)/(B,N) f32 for pass 2.
 template <typename T>
 __global__ __launch_bounds__(256) void knn_normalize_kernel(const T *__restrict__ x, int64_t sb, int64_t sc,
                                                             float *__restrict__ xn, float *__restrict__ sq, int C,
@@ -39,101 +31,23 @@ __global__ __launch_bounds__(256) void knn_normalize_kernel(const T *__restrict_
     if (n >= N) return;
     const T *xb = x + (size_t)b * sb + n;
     float *ob = xn + (size_t)b * C * N + n;
-    float den = 1.0f;
-    if (normalize) {
-        float ss = 0.0f;
-        int c = 0;
-        for (; c + 8 <= C; c += 8) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = ld_as_f32(xb + (size_t)(c + u) * sc);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) ss = __builtin_fmaf(v[u], v[u], ss);
-        }
-        for (; c < C; ++c) {
-            const float v = ld_as_f32(xb + (size_t)c * sc);
-            ss = __builtin_fmaf(v, v, ss);
-        }
-        // sqrtf, not __fsqrt_rn: only the former is correctly rounded here (with
-        // -fhip-fp32-correctly-rounded-divide-sqrt); the intrinsic is 1 ulp off for ~15 % of arguments
-        den = fmaxf(sqrtf(ss), 1e-12f);
-    }
-    float q = 0.0f;
-    int c = 0;
-    for (; c + 8 <= C; c += 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = ld_as_f32(xb + (size_t)(c + u) * sc);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            if (normalize) v[u] = __fdiv_rn(v[u], den);
-            ob[(size_t)(c + u) * N] = v[u];
-            q = __builtin_fmaf(v[u], v[u], q);
-        }
-    }
-    for (; c < C; ++c) {
-        float v = ld_as_f32(xb + (size_t)c * sc);
-        if (normalize) v = __fdiv_rn(v, den);
-        ob[(size_t)c * N] = v;
-        q = __builtin_fmaf(v, v, q);
-    }
-    sq[(size_t)b * N + n] = q;
+    const float den = normalize ? knn_node_den(xb, sc, C) : 1.0f;
+    sq[(size_t)b * N + n] =
+        knn_node_quotients(xb, sc, C, normalize, den, [&](int c, float v) { ob[(size_t)c * N] = v; });
 }
 
 // ---- pass 2: Gram tiles + top-k ----------------------------------------------------------------
-template <int K>
-struct TopK {
-    float d[K];
-    int i[K];
-    __device__ __forceinline__ void init() {
-#pragma unroll
-        for (int t = 0; t < K; ++t) {
-            d[t] = INFINITY;
-            i[t] = 0x7fffffff;
-        }
-    }
-    // Sorted insert as a carry chain of plain selects (branch-free).  `take` compares the ORIGINAL new
-    // value with each OLD slot: in a sorted list that predicate is monotone (false...false,true...true),
-    // so the first true slot receives the new element and every later slot receives its predecessor.
-    // Candidates arrive in ascending index order within a lane, so strict '<' keeps the lower index on
-    // ties, and a displaced (older) element always moves down regardless of ties.
-    __device__ __forceinline__ void push_ascending(float v, int vi) {
-        const float v0 = v;
-#pragma unroll
-        for (int t = 0; t < K; ++t) {
-            const bool take = v0 < d[t];
-            const float od = d[t];
-            const int oi = i[t];
-            d[t] = take ? v : od;
-            i[t] = take ? vi : oi;
-            v = take ? od : v;
-            vi = take ? oi : vi;
-        }
-    }
-    // arbitrary order: full (distance, index) lexicographic comparison
-    __device__ __forceinline__ void push_lex(float v, int vi) {
-#pragma unroll
-        for (int t = 0; t < K; ++t) {
-            const bool lt = v < d[t] || (v == d[t] && vi < i[t]);
-            const float lo = lt ? v : d[t], hi = lt ? d[t] : v;
-            const int ilo = lt ? vi : i[t], ihi = lt ? i[t] : vi;
-            d[t] = lo; i[t] = ilo;
-            v = hi; vi = ihi;
-        }
-    }
-};
-
 // One KC x 128 tile of xn (channels c0.., nodes n0..), 4 float4 per thread, zero-filled outside (C, N):
 // fetched to registers first (so the loads fly under the MFMAs of the previous chunk), written to LDS later.
 struct TileRegs {
-    float4 v[(KC * TR / 4) / 256];
+    float4 v[(KC * KNN_TR / 4) / 256];
 };
 __device__ __forceinline__ void fetch_tile(TileRegs &t, const float *__restrict__ xb, int C, int N, int c0, int n0,
                                            int tid, bool vec_ok) {
 #pragma unroll
-    for (int it = 0; it < (KC * TR / 4) / 256; ++it) {
+    for (int it = 0; it < (KC * KNN_TR / 4) / 256; ++it) {
         const int i = tid + it * 256;
-        const int row = i / (TR / 4), c4 = i % (TR / 4);
+        const int row = i / (KNN_TR / 4), c4 = i % (KNN_TR / 4);
         const int c = c0 + row, n = n0 + c4 * 4;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (c < C) {
@@ -152,14 +66,14 @@ __device__ __forceinline__ void fetch_tile(TileRegs &t, const float *__restrict_
 }
 __device__ __forceinline__ void store_tile(float *dst, const TileRegs &t, int tid) {
 #pragma unroll
-    for (int it = 0; it < (KC * TR / 4) / 256; ++it) {
+    for (int it = 0; it < (KC * KNN_TR / 4) / 256; ++it) {
         const int i = tid + it * 256;
-        *reinterpret_cast<float4 *>(dst + (i / (TR / 4)) * TR + (i % (TR / 4)) * 4) = t.v[it];
+        *reinterpret_cast<float4 *>(dst + (i / (KNN_TR / 4)) * KNN_TR + (i % (KNN_TR / 4)) * 4) = t.v[it];
     }
 }
 
-// dynamic LDS: sA[2][KC][TR] | sB[2][KC][TQ] | sSq[3][TR]   (66 KB: two workgroups per CU)
-constexpr int KNN_LDS_FLOATS = 2 * KC * TR + 2 * KC * TQ + 3 * TR;
+// dynamic LDS: sA[2][KC][KNN_TR] | sB[2][KC][KNN_TQ] | sSq[3][KNN_TR]   (66 KB: two workgroups per CU)
+constexpr int KNN_LDS_FLOATS = 2 * KC * KNN_TR + 2 * KC * KNN_TQ + 3 * KNN_TR;
 
 // PIPE (C a multiple of 2*KC = 64, i.e. every stage of the encoder): chunks are processed in unrolled PAIRS and the
 // top-k insertion of candidate block i-1 (64 distances per lane, ~30 % of the work at C = 64) is spread over the
@@ -170,12 +84,10 @@ __global__ __launch_bounds__(256, 2) void knn_topk_kernel(const float *__restric
                                                           I *__restrict__ idx, int C, int N, int tiles_per_clip,
                                                           int nblocks) {
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
-    float *sA = smem_f, *sB = smem_f + 2 * KC * TR, *sSq = smem_f + 2 * KC * TR + 2 * KC * TQ;
+    float *sA = smem_f, *sB = smem_f + 2 * KC * KNN_TR, *sSq = smem_f + 2 * KC * KNN_TR + 2 * KC * KNN_TQ;
 
-    const int bid = xcd_remap(blockIdx.x, nblocks);
-    const int b = bid / tiles_per_clip;
-    const int q0 = (bid % tiles_per_clip) * TQ;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
+    const KnnCoords w = knn_coords(nblocks, tiles_per_clip);
+    const int b = w.b, q0 = w.q0, tid = w.tid, wave = w.wave, half = w.half, l31 = w.l31;
     const float *xb = xn + (size_t)b * C * N;
     const float *sqb = sq + (size_t)b * N;
     const bool vec_ok = (N & 3) == 0;
@@ -186,7 +98,7 @@ __global__ __launch_bounds__(256, 2) void knn_topk_kernel(const float *__restric
     best.init();
 
     const int nch = (C + KC - 1) / KC;
-    const int nblk = (N + TR - 1) / TR;
+    const int nblk = (N + KNN_TR - 1) / KNN_TR;
     const int T = nblk * nch;
 
     f32x16 acc[4], prev[4];
@@ -204,19 +116,19 @@ __global__ __launch_bounds__(256, 2) void knn_topk_kernel(const float *__restric
     };
     auto stage_next = [&](TileRegs &ra, TileRegs &rb, int t1) {   // write chunk t1 (already in registers) to LDS
         const int blk1 = t1 / nch, ch1 = t1 - blk1 * nch;
-        int off = (t1 & 1) * KC * TR;
+        int off = (t1 & 1) * KC * KNN_TR;
         asm volatile("" : "+v"(off));
         store_tile(sA + off, ra, tid);
         store_tile(sB + off, rb, tid);
-        if (ch1 == 0 && tid < TR) {
-            const int n = blk1 * TR + tid;
-            sSq[(blk1 % 3) * TR + tid] = (n < N) ? sqb[n] : INFINITY;
+        if (ch1 == 0 && tid < KNN_TR) {
+            const int n = blk1 * KNN_TR + tid;
+            sSq[(blk1 % 3) * KNN_TR + tid] = (n < N) ? sqb[n] : INFINITY;
         }
     };
     auto fetch_next = [&](TileRegs &ra, TileRegs &rb, int t1) {
         const int blk1 = t1 / nch, ch1 = t1 - blk1 * nch;
         // opaque offsets: otherwise unrolled copies keep their own pre-computed addresses live (spills)
-        int c_off = ch1 * KC, n_off = blk1 * TR;
+        int c_off = ch1 * KC, n_off = blk1 * KNN_TR;
         asm volatile("" : "+v"(c_off), "+v"(n_off));
         fetch_tile(ra, xb, C, N, c_off, n_off, tid, vec_ok);
         fetch_tile(rb, xb, C, N, c_off, q0, tid, vec_ok);
@@ -232,18 +144,18 @@ __global__ __launch_bounds__(256, 2) void knn_topk_kernel(const float *__restric
         typedef void __attribute__((address_space(3))) *lptr_t;
         auto dma_chunk = [&](int t1) {
             const int blk1 = t1 / nch, ch1 = t1 - blk1 * nch;
-            int off = (t1 & 1) * KC * TR;
+            int off = (t1 & 1) * KC * KNN_TR;
             asm volatile("" : "+v"(off));
             const float *src = xb + (size_t)(ch1 * KC + half) * N + l31 * 4;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int row = wave * 8 + 2 * i;
-                __builtin_amdgcn_global_load_lds((gptr_t)(src + (size_t)row * N + blk1 * TR), (lptr_t)(sA + off + row * TR),
-                                                 16, 0, 0);
-                __builtin_amdgcn_global_load_lds((gptr_t)(src + (size_t)row * N + q0), (lptr_t)(sB + off + row * TR), 16, 0,
-                                                 0);
+                __builtin_amdgcn_global_load_lds((gptr_t)(src + (size_t)row * N + blk1 * KNN_TR),
+                                                 (lptr_t)(sA + off + row * KNN_TR), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((gptr_t)(src + (size_t)row * N + q0),
+                                                 (lptr_t)(sB + off + row * KNN_TR), 16, 0, 0);
             }
-            if (ch1 == 0 && tid < TR) sSq[(blk1 % 3) * TR + tid] = sqb[blk1 * TR + tid];
+            if (ch1 == 0 && tid < KNN_TR) sSq[(blk1 % 3) * KNN_TR + tid] = sqb[blk1 * KNN_TR + tid];
         };
         // One unrolled pair of chunks starting at flat chunk index t0.  INS / HAS are compile-time so that every
         // MFMA step is straight-line code: HAS = this block exists (issue MFMAs + next DMA), INS = spread the 64
@@ -253,16 +165,16 @@ __global__ __launch_bounds__(256, 2) void knn_topk_kernel(const float *__restric
             for (int c2 = 0; c2 < 2; ++c2) {
                 const int t = t0 + c2;
                 if (HAS.value && (t + 1 < T)) dma_chunk(t + 1);
-                int buf_off = (t & 1) * KC * TR;
+                int buf_off = (t & 1) * KC * KNN_TR;
                 asm volatile("" : "+v"(buf_off));
                 const float *a = sA + buf_off, *bq_ = sB + buf_off;
 #pragma unroll
                 for (int kk = 0; kk < KC; kk += 2) {
                     if (HAS.value) {
-                        const float bq = bq_[(kk + half) * TQ + wave * 32 + l31];
+                        const float bq = bq_[(kk + half) * KNN_TQ + wave * 32 + l31];
 #pragma unroll
                         for (int tt = 0; tt < 4; ++tt)
-                            acc[tt] = mfma32x32x2(a[(kk + half) * TR + tt * 32 + l31], bq, acc[tt]);
+                            acc[tt] = mfma32x32x2(a[(kk + half) * KNN_TR + tt * 32 + l31], bq, acc[tt]);
                     }
                     if (INS.value) {
                         const int step = c2 * 16 + (kk >> 1);          // 0..31
@@ -278,7 +190,7 @@ __global__ __launch_bounds__(256, 2) void knn_topk_kernel(const float *__restric
         dma_chunk(0);
         __syncthreads();
         for (int blk = 0; blk < nblk; ++blk) {
-            const int sq_prev = ((blk + 2) % 3) * TR, idx_prev = (blk - 1) * TR;
+            const int sq_prev = ((blk + 2) % 3) * KNN_TR, idx_prev = (blk - 1) * KNN_TR;
             if (blk > 0) chunk_pair(true_type{}, true_type{}, blk * nch, sq_prev, idx_prev);
             else chunk_pair(false_type{}, true_type{}, blk * nch, 0, 0);
             for (int cp = 1; cp < nch / 2; ++cp) chunk_pair(false_type{}, true_type{}, blk * nch + cp * 2, 0, 0);
@@ -292,7 +204,7 @@ __global__ __launch_bounds__(256, 2) void knn_topk_kernel(const float *__restric
         // drain: the last block's distances (no MFMAs left to hide behind)
 #pragma unroll
         for (int e = 0; e < 64; ++e) {
-            insert(prev, e, ((nblk + 2) % 3) * TR, (nblk - 1) * TR);
+            insert(prev, e, ((nblk + 2) % 3) * KNN_TR, (nblk - 1) * KNN_TR);
             if ((e & 3) == 3) __builtin_amdgcn_sched_barrier(0);
         }
     } else {
@@ -304,18 +216,19 @@ __global__ __launch_bounds__(256, 2) void knn_topk_kernel(const float *__restric
             const int blk = t / nch, ch = t - blk * nch;
             const bool more = t + 1 < T;
             if (more) fetch_next(ra, rb, t + 1);
-            const float *a = sA + (t & 1) * KC * TR, *bq_ = sB + (t & 1) * KC * TQ;
+            const float *a = sA + (t & 1) * KC * KNN_TR, *bq_ = sB + (t & 1) * KC * KNN_TQ;
 #pragma unroll 4
             for (int kk = 0; kk < KC; kk += 2) {
-                const float bq = bq_[(kk + half) * TQ + wave * 32 + l31];
+                const float bq = bq_[(kk + half) * KNN_TQ + wave * 32 + l31];
 #pragma unroll
-                for (int tt = 0; tt < 4; ++tt) acc[tt] = mfma32x32x2(a[(kk + half) * TR + tt * 32 + l31], bq, acc[tt]);
+                for (int tt = 0; tt < 4; ++tt)
+                    acc[tt] = mfma32x32x2(a[(kk + half) * KNN_TR + tt * 32 + l31], bq, acc[tt]);
             }
             if (more) stage_next(ra, rb, t + 1);
             if (ch == nch - 1) {      // block complete: lane holds G[cand][query = myq] for 64 candidates, ascending
 #pragma unroll
                 for (int e = 0; e < 64; ++e) {
-                    insert(acc, e, (blk % 3) * TR, blk * TR);
+                    insert(acc, e, (blk % 3) * KNN_TR, blk * KNN_TR);
                     if ((e & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // keep the 64 distances from being hoisted
                 }
 #pragma unroll
@@ -326,7 +239,8 @@ __global__ __launch_bounds__(256, 2) void knn_topk_kernel(const float *__restric
             __syncthreads();
         }
     }
-    // the two half-waves saw disjoint candidate subsets of the same query: merge them
+    // TopK::merge_halves, written out: as a call it moves the register allocation of the PIPE block loop (K >= 2: up to
+    // 180 bytes more scratch per lane), although the inlined code is the same
     float od[K];
     int oi[K];
 #pragma unroll
@@ -336,16 +250,12 @@ __global__ __launch_bounds__(256, 2) void knn_topk_kernel(const float *__restric
     }
 #pragma unroll
     for (int t = 0; t < K; ++t) best.push_lex(od[t], oi[t]);
-    if (half == 0 && myq < N) {
-        I *o = idx + ((size_t)b * N + myq) * K;
-#pragma unroll
-        for (int t = 0; t < K; ++t) o[t] = (I)best.i[t];
-    }
+    if (half == 0 && myq < N) best.store(idx + ((size_t)b * N + myq) * K);
 }
 
 template <int K, typename I>
 static void launch_topk(const float *xn, const float *sq, I *idx, int B, int C, int N, hipStream_t s) {
-    const int tiles = (N + TQ - 1) / TQ;
+    const int tiles = (N + KNN_TQ - 1) / KNN_TQ;
     const int nblocks = B * tiles;
     const size_t lds = (size_t)KNN_LDS_FLOATS * sizeof(float);
 #define KNN_LAUNCH(PIPE)                                                                                             \
@@ -353,18 +263,24 @@ static void launch_topk(const float *xn, const float *sq, I *idx, int B, int C, 
                               (int)lds);                                                                             \
     hipLaunchKernelGGL((knn_topk_kernel<K, I, PIPE>), dim3(nblocks), dim3(256), lds, s, xn, sq, idx, C, N, tiles,    \
                        nblocks)
-    if (K <= 4 && C % (2 * KC) == 0 && N % TR == 0 && (((uintptr_t)xn) & 15) == 0) { KNN_LAUNCH(true); }
+    if (K <= 4 && C % (2 * KC) == 0 && N % KNN_TR == 0 && (((uintptr_t)xn) & 15) == 0) { KNN_LAUNCH(true); }
     else { KNN_LAUNCH(false); }
 #undef KNN_LAUNCH
+}
+
+// the workspace of grafp_knn_graph_f32: xn (B,C,N) | sq (B,N)
+static size_t knn_graph_layout(void *ws, int B, int C, int N, float *&xn, float *&sq) {
+    WsCarve w{(char *)ws, 0};
+    xn = w.take<float>((size_t)B * C * N * sizeof(float));
+    sq = w.take<float>((size_t)B * N * sizeof(float));
+    return w.off;
 }
 
 }  // namespace grafp
 
 extern "C" size_t grafp_knn_graph_workspace(int B, int C, int N) {
-    if (B <= 0 || C <= 0 || N <= 0) return 0;
-    const size_t xn = ((size_t)B * C * N * sizeof(float) + 255) & ~(size_t)255;
-    const size_t sq = ((size_t)B * N * sizeof(float) + 255) & ~(size_t)255;
-    return xn + sq;
+    float *xn, *sq;
+    return (B <= 0 || C <= 0 || N <= 0) ? 0 : grafp::knn_graph_layout(nullptr, B, C, N, xn, sq);
 }
 
 template <typename I>
@@ -432,13 +348,12 @@ extern "C" int grafp_knn_graph_f32(const float *x, int B, int C, int N, int k, i
                                    size_t ws_bytes, grafp_stream_t stream) {
     using namespace grafp;
     if (!knn_args_ok(x, idx, B, C, N, k)) return GRAFP_ERR_ARG;
-    const size_t need = grafp_knn_graph_workspace(B, C, N);
+    float *xn, *sq;
+    const size_t need = knn_graph_layout(ws, B, C, N, xn, sq);
     if (!ws || ws_bytes < need) {
         set_error("knn_graph: workspace %zu bytes < required %zu", ws_bytes, need);
         return GRAFP_ERR_WORKSPACE;
     }
-    float *xn = (float *)ws;
-    float *sq = (float *)((char *)ws + (((size_t)B * C * N * sizeof(float) + 255) & ~(size_t)255));
     const int rc = grafp_knn_normalize_f32(x, B, C, N, normalize, xn, sq, stream);
     if (rc != GRAFP_OK) return rc;
     return grafp_knn_topk_f32(xn, sq, B, C, N, k, idx, stream);

@@ -1,7 +1,7 @@
 // knn_pre.hip -- dynamic k-NN graph through a bf16 pre-filter with exact f32 rescoring (K3-K5), gfx950.
 //
 // Same contract and the SAME indices as knn_graph.hip (the reference's DenseDilatedKnnGraph,
-// /root/reference/encoder/gcn_lib/torch_edge.py:7-18,70-103,270-284; arithmetic order of oracle/csrc/knn_graph.c),
+// /root/reference/encoder/gcn_lib/torch_edge.py:7-18,70-103,270-284; arithmetic order: knngraph.h),
 // for the shapes the encoder produces (C % 64 == 0, N % 128 == 0, k <= 4).  knn_graph.hip evaluates all N^2 distances
 // with the exact-f32 MFMA (157 TFLOP/s) and pays ~15 VALU instructions per pair for the sorted insert, which do not
 // overlap with the f32 MFMA.  Here:
@@ -12,30 +12,25 @@
 //   pass 2  the same tiles again; a candidate is kept iff its LOWER bound does not exceed that bound -- one
 //           compare per pair against a per-lane constant -- and its index goes to a lane-private list in LDS
 //           (4-8 survivors per query on the encoder's features).
-//   rescore the exact distance (c-ordered fmaf chain over the f32 rows, (sq_i + (-2 g)) + sq_j) of the survivors and
-//           the top-k by (distance, index): bit-identical to the all-f32 kernel.  A lane whose list overflows falls
-//           back to exact distances for ALL its candidates.
+//   rescore the exact distance (kp_exact) of the survivors and the top-k by (distance, index): bit-identical to the
+//           all-f32 kernel.  A lane whose list overflows falls back to exact distances for ALL its candidates.
 // Bounds: with x^ = round_bf16(x), |<q^,x^> - <q,x>| <= (2u + u^2)|q||x| <= 0.0039139 (sq_q + sq_j), u = 2^-8, so
 //   d in [ (sq_q + sq_j)(1 - S) - 2<q^,x^>, (sq_q + sq_j)(1 + S) - 2<q^,x^> ],  S = 0.008 (spare 1.7e-4 for the MFMA's
 //   f32 accumulation and the rounding of the tests); sq_j is replaced by the clip's max / min squared norm (both 1
 //   to rounding for normalised features), which makes the tests per-lane constants.
 // Data: knn_normalize_rows_kernel writes node-major rows -- xnf (B,N,C) f32 for the rescoring, xnh (B,N,C) bf16 for the
 // MFMA fragments (8 consecutive channels = 16 contiguous bytes) -- and sq (B,N).
-#include <math.h>
-
-#include "common.h"
+#include "knngraph.h"
 
 namespace grafp {
 
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int KP_TQ = 128;        // query nodes per workgroup (32 per wave)
-constexpr int KP_TR = 128;        // candidate nodes per block
 constexpr int KP_KC = 64;         // channels per LDS chunk: 128 bytes per node row
 constexpr int KP_CAP = 24;        // survivors a lane can hold (per half-lane: half of the candidates)
 constexpr float KP_SLACK = 0.008f;
-constexpr int KP_TILE_BYTES = KP_TR * KP_KC * 2;                        // 16 KB
+constexpr int KP_TILE_BYTES = KNN_TR * KP_KC * 2;                        // 16 KB
 constexpr int KP_LDS_BYTES = 4 * KP_TILE_BYTES + 256 * KP_CAP * 2 + 64;  // A[2] | B[2] | lists | reductions
 
 __device__ __forceinline__ unsigned short kp_bf16_rne(float f) {
@@ -43,12 +38,11 @@ __device__ __forceinline__ unsigned short kp_bf16_rne(float f) {
     u += 0x7fffu + ((u >> 16) & 1u);
     return (unsigned short)(u >> 16);
 }
-__device__ __forceinline__ float kp_ld(const float *p) { return *p; }
-__device__ __forceinline__ float kp_ld(const unsigned short *p) { return __uint_as_float(((unsigned)*p) << 16); }
 
 // ---- pass 0: channel-L2 normalisation (torch_edge.py:281), squared norms, node-major f32 + bf16 rows -----------------
 // One thread per node for the arithmetic (the oracle's c-ascending chains); 32-channel slabs go through an LDS
-// transpose so that the node-major rows are written in 128-byte (f32) / 64-byte (bf16) pieces.
+// transpose so that the node-major rows are written in 128-byte (f32) / 64-byte (bf16) pieces: the quotient pass
+// walks 32 channels per step here, in the order of knn_node_quotients.
 template <typename T>
 __global__ __launch_bounds__(256) void knn_normalize_rows_kernel(const T *__restrict__ x, int64_t sb, int64_t sc,
                                                                  float *__restrict__ xnf,
@@ -58,30 +52,12 @@ __global__ __launch_bounds__(256) void knn_normalize_rows_kernel(const T *__rest
     const int tid = threadIdx.x, b = blockIdx.y, n0 = blockIdx.x * 256, n = n0 + tid;
     const bool valid = n < N;
     const T *xb = x + (size_t)b * sb + (valid ? n : 0);
-    float den = 1.0f;
-    if (normalize && valid) {
-        float ss = 0.0f;
-        int c = 0;
-        for (; c + 8 <= C; c += 8) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = kp_ld(xb + (size_t)(c + u) * sc);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) ss = __builtin_fmaf(v[u], v[u], ss);
-        }
-        for (; c < C; ++c) {
-            const float v = kp_ld(xb + (size_t)c * sc);
-            ss = __builtin_fmaf(v, v, ss);
-        }
-        // sqrtf, not __fsqrt_rn: only the former is correctly rounded here (with
-        // -fhip-fp32-correctly-rounded-divide-sqrt); the intrinsic is 1 ulp off for ~15 % of arguments
-        den = fmaxf(sqrtf(ss), 1e-12f);
-    }
+    const float den = (normalize && valid) ? knn_node_den(xb, sc, C) : 1.0f;
     float q = 0.0f;
     for (int c0 = 0; c0 < C; c0 += 32) {
         float v[32];
 #pragma unroll
-        for (int u = 0; u < 32; ++u) v[u] = (valid && c0 + u < C) ? kp_ld(xb + (size_t)(c0 + u) * sc) : 0.0f;
+        for (int u = 0; u < 32; ++u) v[u] = (valid && c0 + u < C) ? ld_as_f32(xb + (size_t)(c0 + u) * sc) : 0.0f;
 #pragma unroll
         for (int u = 0; u < 32; ++u) {
             if (normalize) v[u] = __fdiv_rn(v[u], den);
@@ -118,31 +94,7 @@ __global__ __launch_bounds__(256) void knn_normalize_rows_kernel(const T *__rest
     if (valid) sq[(size_t)b * N + n] = q;
 }
 
-// (distance, index) lists of K, lexicographic insert (arbitrary arrival order)
-template <int K>
-struct KpTop {
-    float d[K];
-    int i[K];
-    __device__ __forceinline__ void init() {
-#pragma unroll
-        for (int t = 0; t < K; ++t) {
-            d[t] = INFINITY;
-            i[t] = 0x7fffffff;
-        }
-    }
-    __device__ __forceinline__ void push_lex(float v, int vi) {
-#pragma unroll
-        for (int t = 0; t < K; ++t) {
-            const bool lt = v < d[t] || (v == d[t] && vi < i[t]);
-            const float lo = lt ? v : d[t], hi = lt ? d[t] : v;
-            const int ilo = lt ? vi : i[t], ihi = lt ? i[t] : vi;
-            d[t] = lo; i[t] = ilo;
-            v = hi; vi = ihi;
-        }
-    }
-};
-
-// exact squared distance of nodes (q, j): c-ascending fmaf chain over the f32 rows, then (sq_q + (-2 g)) + sq_j
+// exact squared distance of nodes (q, j) from the f32 rows: the Gram chain and distance expression of knngraph.h
 __device__ __forceinline__ float kp_exact(const float *__restrict__ xf, int C, int q, int j, float sq_q, float sq_j) {
     const f32x4 *qr = reinterpret_cast<const f32x4 *>(xf + (size_t)q * C);
     const f32x4 *jr = reinterpret_cast<const f32x4 *>(xf + (size_t)j * C);
@@ -172,10 +124,8 @@ __global__ __launch_bounds__(256, 2) void knn_pre_kernel(const float *__restrict
     unsigned short *lists = reinterpret_cast<unsigned short *>(smem_b + 4 * KP_TILE_BYTES);
     float *sred = reinterpret_cast<float *>(smem_b + 4 * KP_TILE_BYTES + 256 * KP_CAP * 2);
 
-    const int bid = xcd_remap(blockIdx.x, nblocks);
-    const int b = bid / tiles_per_clip;
-    const int q0 = (bid % tiles_per_clip) * KP_TQ;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
+    const KnnCoords w = knn_coords(nblocks, tiles_per_clip);
+    const int b = w.b, q0 = w.q0, tid = w.tid, wave = w.wave, lane = w.lane, half = w.half, l31 = w.l31;
     const unsigned short *xh = xnh + (size_t)b * N * C;
     const float *xf = xnf + (size_t)b * N * C;
     const float *sqb = sq + (size_t)b * N;
@@ -204,7 +154,7 @@ __global__ __launch_bounds__(256, 2) void knn_pre_kernel(const float *__restrict
     const float sq_min = fminf(fminf(sred[0], sred[1]), fminf(sred[2], sred[3]));
     const float sq_max = fmaxf(fmaxf(sred[4], sred[5]), fmaxf(sred[6], sred[7]));
 
-    const int nch = C / KP_KC, nblk = N / KP_TR, T = nblk * nch;
+    const int nch = C / KP_KC, nblk = N / KNN_TR, T = nblk * nch;
 
     // LDS-DMA of chunk t1 (candidate block t1 / nch, channel chunk t1 % nch) into buffer u & 1.  One wave instruction
     // moves 8 node rows x 128 bytes to a lane-linear destination; the 16-byte slot a lane fetches is XOR-swizzled with
@@ -220,7 +170,7 @@ __global__ __launch_bounds__(256, 2) void knn_pre_kernel(const float *__restrict
             const int rowbase = (wave * 4 + i) * 8;
             const int row = rowbase + (lane >> 3);
             const int c = (lane & 7) ^ ((row >> 1) & 7);
-            const unsigned short *ga = xh + ((size_t)(blk1 * KP_TR + row) * C + ch1 * KP_KC + c * 8);
+            const unsigned short *ga = xh + ((size_t)(blk1 * KNN_TR + row) * C + ch1 * KP_KC + c * 8);
             const unsigned short *gb = xh + ((size_t)(q0 + row) * C + ch1 * KP_KC + c * 8);
             __builtin_amdgcn_global_load_lds((gptr_t)ga, (lptr_t)(sA + off + rowbase * 128), 16, 0, 0);
             __builtin_amdgcn_global_load_lds((gptr_t)gb, (lptr_t)(sB + off + rowbase * 128), 16, 0, 0);
@@ -275,7 +225,7 @@ __global__ __launch_bounds__(256, 2) void knn_pre_kernel(const float *__restrict
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
                             if (acc[tt][r] >= a_q) {
-                                if (cnt < KP_CAP) mylist[cnt] = (unsigned short)(blk * KP_TR + tt * 32 + mfma_row(r, half));
+                                if (cnt < KP_CAP) mylist[cnt] = (unsigned short)(blk * KNN_TR + tt * 32 + mfma_row(r, half));
                                 else overflow = true;
                                 ++cnt;
                             }
@@ -316,7 +266,7 @@ __global__ __launch_bounds__(256, 2) void knn_pre_kernel(const float *__restrict
     }
 
     // exact rescoring of the survivors (or of every candidate of this half-lane when its list overflowed)
-    KpTop<K> best;
+    TopK<K> best;
     best.init();
     const unsigned long long ovm = __ballot(overflow);          // either half-lane of the query overflowed
     const bool ov = (((ovm >> l31) | (ovm >> (l31 + 32))) & 1ull) != 0;
@@ -330,27 +280,14 @@ __global__ __launch_bounds__(256, 2) void knn_pre_kernel(const float *__restrict
         for (int j = half * (N / 2); j < (half + 1) * (N / 2); ++j)
             best.push_lex(kp_exact(xf, C, myq, j, sq_q, sqb[j]), j);
     }
-    // the two half-lanes hold disjoint candidate subsets of the same query: merge them
-    float od[K];
-    int oi[K];
-#pragma unroll
-    for (int t2 = 0; t2 < K; ++t2) {
-        od[t2] = __shfl_xor(best.d[t2], 32);
-        oi[t2] = __shfl_xor(best.i[t2], 32);
-    }
-#pragma unroll
-    for (int t2 = 0; t2 < K; ++t2) best.push_lex(od[t2], oi[t2]);
-    if (half == 0) {
-        I *o = idx + ((size_t)b * N + myq) * K;
-#pragma unroll
-        for (int t2 = 0; t2 < K; ++t2) o[t2] = (I)best.i[t2];
-    }
+    best.merge_halves();
+    if (half == 0) best.store(idx + ((size_t)b * N + myq) * K);
 }
 
 template <int K, typename I>
 static void launch_pre(const float *xnf, const unsigned short *xnh, const float *sq, I *idx, int B, int C, int N,
                        hipStream_t s) {
-    const int tiles = N / KP_TQ;
+    const int tiles = N / KNN_TQ;
     const int nblocks = B * tiles;
     (void)hipFuncSetAttribute((const void *)knn_pre_kernel<K, I>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)KP_LDS_BYTES);
@@ -371,19 +308,26 @@ static int pre_dispatch(const float *xnf, const unsigned short *xnh, const float
     return GRAFP_OK;
 }
 
+// the workspace of grafp_knn_graph_pre: xnf (B,N,C) f32 | xnh (B,N,C) bf16 | sq (B,N)
+static size_t pre_layout(void *ws, int B, int C, int N, float *&xnf, unsigned short *&xnh, float *&sq) {
+    WsCarve w{(char *)ws, 0};
+    xnf = w.take<float>((size_t)B * C * N * sizeof(float));
+    xnh = w.take<unsigned short>((size_t)B * C * N * sizeof(unsigned short));
+    sq = w.take<float>((size_t)B * N * sizeof(float));
+    return w.off;
+}
+
 }  // namespace grafp
 
 extern "C" int grafp_knn_pre_supported(int C, int N, int k) {
-    return (C > 0 && N > 0 && C % grafp::KP_KC == 0 && N % grafp::KP_TR == 0 && N <= 65536 && k >= 1 && k <= 4 &&
+    return (C > 0 && N > 0 && C % grafp::KP_KC == 0 && N % grafp::KNN_TR == 0 && N <= 65536 && k >= 1 && k <= 4 &&
             k <= N) ? 1 : 0;
 }
 
 extern "C" size_t grafp_knn_pre_workspace(int B, int C, int N) {
-    if (B <= 0 || C <= 0 || N <= 0) return 0;
-    const size_t f = ((size_t)B * C * N * sizeof(float) + 255) & ~(size_t)255;
-    const size_t h = ((size_t)B * C * N * sizeof(unsigned short) + 255) & ~(size_t)255;
-    const size_t sq = ((size_t)B * N * sizeof(float) + 255) & ~(size_t)255;
-    return f + h + sq;
+    float *xnf, *sq;
+    unsigned short *xnh;
+    return (B <= 0 || C <= 0 || N <= 0) ? 0 : grafp::pre_layout(nullptr, B, C, N, xnf, xnh, sq);
 }
 
 extern "C" int grafp_knn_graph_pre(const void *x, int dtype, int64_t stride_b, int64_t stride_c, int B, int C, int N,
@@ -394,18 +338,14 @@ extern "C" int grafp_knn_graph_pre(const void *x, int dtype, int64_t stride_b, i
     GRAFP_REQUIRE(B > 0 && grafp_knn_pre_supported(C, N, k), "knn_graph_pre: unsupported shape C=%d N=%d k=%d "
                   "(C %% 64 == 0, N %% 128 == 0, k <= 4; use grafp_knn_graph_f32 otherwise)", C, N, k);
     GRAFP_REQUIRE(dtype == GRAFP_F32 || dtype == GRAFP_BF16, "knn_graph_pre: dtype %d not in {f32, bf16}", dtype);
-    const size_t need = grafp_knn_pre_workspace(B, C, N);
+    float *xnf, *sq;
+    unsigned short *xnh;
+    const size_t need = pre_layout(ws, B, C, N, xnf, xnh, sq);
     if (!ws || ws_bytes < need) {
         set_error("knn_graph_pre: workspace %zu bytes < required %zu", ws_bytes, need);
         return GRAFP_ERR_WORKSPACE;
     }
     hipStream_t s = (hipStream_t)stream;
-    char *w = (char *)ws;
-    float *xnf = (float *)w;
-    w += ((size_t)B * C * N * sizeof(float) + 255) & ~(size_t)255;
-    unsigned short *xnh = (unsigned short *)w;
-    w += ((size_t)B * C * N * sizeof(unsigned short) + 255) & ~(size_t)255;
-    float *sq = (float *)w;
     const dim3 grid((N + 255) / 256, B);
     if (dtype == GRAFP_F32)
         hipLaunchKernelGGL(knn_normalize_rows_kernel<float>, grid, dim3(256), 0, s, (const float *)x, stride_b, stride_c,

@@ -14,8 +14,7 @@
 //   * a query is CERTIFIED when consecutive entries of its (k+1)-list are more than 2 m (+ the key truncation) apart:
 //     then the oracle's f32 distances have the same strict order and no candidate outside the list can enter it.  The
 //     few uncertified queries (near-ties, duplicates: 1-3 % on encoder features) are flagged and knn_exact_clip_kernel
-//     recomputes them, clip by clip, with the oracle's exact arithmetic (c-ordered fmaf chains, (sq_i + (-2 g)) + sq_j, ties to the
-//     lowest index).
+//     recomputes them, clip by clip, with the oracle's exact arithmetic (stated in knngraph.h).
 // Error budget for unit-norm rows (|x| = |y| = 1 up to rounding; the entry requires normalize = 1), C channels:
 //   representation            3.01 * 2^-18                       = 1.15e-5
 //   MFMA accumulation         3 C additions, each <= 2^-23 of a partial sum <= 1.004 (truncation assumed)
@@ -23,26 +22,19 @@
 //   oracle's own rounding     |d_oracle - d| <= 2 C 2^-24 + 5e-7
 //   m(C) = 2 e_g(C) + 2^-23 C + 1e-6         (C = 64: 7.7e-5, C = 512: 4.5e-4; typical errors are 10-30 x smaller)
 // The constant 2^-10 keeps every d~ positive (m < 2^-10 is checked), so the keys order as unsigned integers.
-#include <math.h>
-
-#include "common.h"
 #include "dma_ring.h"
+#include "knngraph.h"
 #include "tuning.h"
 
 namespace grafp {
 
-constexpr int KS_TQ = 128;                  // query nodes per workgroup (32 per wave)
-constexpr int KS_TR = 128;                  // candidate nodes per block
-constexpr int KS_KC = 32;                   // channels per chunk
-constexpr int KS_PLANE = KS_KC * KS_TR * 2; // one bf16 tile: 32 channel rows x 256 B
+constexpr int KS_KC = 32;                    // channels per chunk
+constexpr int KS_PLANE = KS_KC * KNN_TR * 2; // one bf16 tile: 32 channel rows x 256 B
 constexpr int KS_STAGE = 4 * KS_PLANE;      // candidates hi | candidates lo | queries hi | queries lo
-constexpr int KS_LDS = 2 * KS_STAGE + 3 * KS_TR * 4;
+constexpr int KS_LDS = 2 * KS_STAGE + 3 * KNN_TR * 4;
 constexpr float KS_SHIFT = 9.765625e-4f;    // 2^-10
 
-__device__ __forceinline__ float ks_ld(const float *p) { return *p; }
-__device__ __forceinline__ float ks_ld(const unsigned short *p) { return __uint_as_float(((unsigned)*p) << 16); }
-
-// pass 1: channel-L2 normalisation exactly as knn_normalize_kernel (same chains, same bits) -- but the normalised f32
+// pass 1: channel-L2 normalisation exactly as knn_normalize_kernel (the chains of knngraph.h) -- but the normalised f32
 // values are not written: only their two bf16 halves, the squared norms and the denominators (pass 3 re-derives any f32
 // value it needs as x / den, the same IEEE division)
 template <typename T>
@@ -60,44 +52,13 @@ __global__ __launch_bounds__(256) void knn_normalize_split_kernel(const T *__res
     if (n >= N) return;
     const T *xb = x + (size_t)b * sb + n;
     const size_t o = (size_t)b * C * N + n;
-    float ss = 0.0f;
-    int c = 0;
-    for (; c + 8 <= C; c += 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = ks_ld(xb + (size_t)(c + u) * sc);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) ss = __builtin_fmaf(v[u], v[u], ss);
-    }
-    for (; c < C; ++c) {
-        const float v = ks_ld(xb + (size_t)c * sc);
-        ss = __builtin_fmaf(v, v, ss);
-    }
-    const float den = fmaxf(sqrtf(ss), 1e-12f);       // sqrtf: correctly rounded (see knn_graph.hip)
-    float q = 0.0f;
-    for (c = 0; c + 8 <= C; c += 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = ks_ld(xb + (size_t)(c + u) * sc);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            v[u] = __fdiv_rn(v[u], den);
-            q = __builtin_fmaf(v[u], v[u], q);
-            const unsigned h = gm_pack_bf16(v[u], 0.0f) & 0xffffu;
-            const float r = v[u] - __uint_as_float(h << 16);          // exact
-            xh[o + (size_t)(c + u) * N] = (unsigned short)h;
-            xl[o + (size_t)(c + u) * N] = (unsigned short)(gm_pack_bf16(r, 0.0f) & 0xffffu);
-        }
-    }
-    for (; c < C; ++c) {
-        const float v = __fdiv_rn(ks_ld(xb + (size_t)c * sc), den);
-        q = __builtin_fmaf(v, v, q);
+    const float den = knn_node_den(xb, sc, C);
+    sq[(size_t)b * N + n] = knn_node_quotients(xb, sc, C, 1, den, [&](int c, float v) {
         const unsigned h = gm_pack_bf16(v, 0.0f) & 0xffffu;
-        const float r = v - __uint_as_float(h << 16);
+        const float r = v - __uint_as_float(h << 16);                 // exact
         xh[o + (size_t)c * N] = (unsigned short)h;
         xl[o + (size_t)c * N] = (unsigned short)(gm_pack_bf16(r, 0.0f) & 0xffffu);
-    }
-    sq[(size_t)b * N + n] = q;
+    });
     den_out[(size_t)b * N + n] = den;
 }
 
@@ -134,7 +95,64 @@ struct KeyList {
         for (int t = K - 1; t > 0; --t) k[t] = med3(k[t - 1], k[t], v);
         k[0] = v < k[0] ? v : k[0];
     }
+    // the two half-waves saw disjoint candidate subsets of the same query: each takes the other's list
+    __device__ __forceinline__ void merge_halves() {
+        unsigned ok[K], onext = (unsigned)__shfl_xor((int)next, 32);
+#pragma unroll
+        for (int t = 0; t < K; ++t) ok[t] = (unsigned)__shfl_xor((int)k[t], 32);
+#pragma unroll
+        for (int t = 0; t < K; ++t) push(ok[t]);
+        next = onext < next ? onext : next;
+    }
 };
+
+// ---- a lane's fragment offset inside a plane of the scans' LDS tiles, for node tile `tile` (32 nodes) at k-step 0 ----
+// lane i = lane & 15 of group (lane >> 4) & 1: row 16 ks + 8 half + (i >> 2) (+ 4), nodes tile*32 + 16 grp + 4 (i & 3).
+// The scans keep foff[tt] for the four candidate tiles and qoff for tile `wave` of the query planes (the wave's 32
+// queries); called per tile at the kernel's own site: a helper that fills all five renumbers the loop's registers.
+__device__ __forceinline__ int ks_frag_offset(int tile, int lane, int half) {
+    const int i = lane & 15, grp = (lane >> 4) & 1;
+    const int bytecol = (tile * 32 + 16 * grp + 4 * (i & 3)) * 2;
+    const int seg = (bytecol >> 6) ^ (i >> 2);
+    return (8 * half + (i >> 2)) * 256 + seg * 64 + (bytecol & 63);
+}
+// 8 consecutive channels of a node out of a tile whose rows are channels: two transposed reads, 4 rows apart
+__device__ __forceinline__ gm_bf16x8 ks_frag(const unsigned char *pl, int off) {
+    const gm_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((gm_s16x4 __attribute__((address_space(3))) *)(pl + off));
+    const gm_s16x4 hi =
+        __builtin_amdgcn_ds_read_tr16_b64_v4i16((gm_s16x4 __attribute__((address_space(3))) *)(pl + off + 4 * 256));
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// The tail of both scans, by the lane that owns query `row` after merge_halves: store the k listed indices and the tier.
+// CERTIFIED: consecutive entries of the (k+1)-list further apart than `band` = 2 m in the keys' scale (+ the truncation of
+// the lower key): the oracle's distances have the same strict order and nothing outside the first k can enter.
+// LIGHT: not certified, but the (k+2)-th smallest key is beyond the band of the k-th: the exact top k are among the
+// k + 1 listed candidates (every unlisted one is strictly worse than the first k listed) -- pass 3a recomputes
+// those k + 1 distances exactly.  HEAVY (>= 3 candidates inside the band of the k-th: clusters, duplicates):
+// pass 3b rescans the whole clip for the query.  `veto` (the raw form's out-of-range clip) makes every query HEAVY.
+template <int K, typename I>
+__device__ __forceinline__ void ks_classify_store(const KeyList<K + 1> &best, unsigned key_mask, float band, bool veto,
+                                                  size_t row, I *__restrict__ idx, int *__restrict__ unc_count,
+                                                  unsigned char *__restrict__ unc_flag, int *__restrict__ extra) {
+    const unsigned imask = ~key_mask;
+    I *o = idx + row * K;
+    const float trunc = __uint_as_float(0x3f800000u + imask) - 1.0f;       // relative size of the dropped mantissa bits
+    bool certified = !veto;
+#pragma unroll
+    for (int t = 0; t < K; ++t) {
+        const float lo = __uint_as_float(best.k[t] & key_mask), hi = __uint_as_float(best.k[t + 1] & key_mask);
+        certified = certified && (hi - lo * (1.0f + trunc) > band);
+        o[t] = (I)(best.k[t] & imask);
+    }
+    const bool light = !veto && __uint_as_float(best.next & key_mask) -
+                                        __uint_as_float(best.k[K - 1] & key_mask) * (1.0f + trunc) > band;
+    unc_flag[row] = certified ? 0 : (light ? 1 : 2);
+    if (!certified) {
+        atomicAdd(unc_count, 1);                                           // diagnostics: all uncertified queries
+        if (light) extra[row] = (int)(best.k[K] & imask);          // the (k+1)-th listed candidate (pass 3a reads it)
+    }
+}
 
 // pass 2.  Workgroup = 128 queries of one clip x all candidates, 4 waves x 32 queries; a lane owns ONE query (MFMA column
 // j = lane & 31) and, per candidate block, the 64 candidates of its rows (mfma_row).  Per chunk of 32 channels the four
@@ -154,16 +172,14 @@ __global__ __launch_bounds__(256, 2) void knn_topk_split_kernel(const unsigned s
     float *const sSq = reinterpret_cast<float *>(smem + 2 * KS_STAGE);
     const unsigned lds0 = (unsigned)(uintptr_t)(gm_lptr)smem;
 
-    const int bid = xcd_remap(blockIdx.x, nblocks);
-    const int b = bid / tiles_per_clip;
-    const int q0 = (bid % tiles_per_clip) * KS_TQ;
-    const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const KnnCoords w = knn_coords(nblocks, tiles_per_clip);
+    const int b = w.b, q0 = w.q0, lane = w.lane, half = w.half, l31 = w.l31;
+    const int wave = __builtin_amdgcn_readfirstlane(w.wave);
     const float *sqb = sq + (size_t)b * N;
     const int myq = q0 + wave * 32 + l31;
     const float dq = sqb[myq] + KS_SHIFT;
 
-    const int nch = C / KS_KC, nblk = N / KS_TR, T = nblk * nch;
+    const int nch = C / KS_KC, nblk = N / KNN_TR, T = nblk * nch;
 
     // ---- DMA: wave w moves plane w of every chunk (0 candidates hi, 1 candidates lo, 2 queries hi, 3 queries lo) ----
     // instruction i covers channel rows 4i .. 4i+3 (256 B each); LDS slot s' = lane & 15 of row lane >> 4 holds source
@@ -174,41 +190,20 @@ __global__ __launch_bounds__(256, 2) void knn_topk_split_kernel(const unsigned s
     const unsigned short *src0 = plane + (size_t)rowl * N + scol + (wave >= 2 ? q0 : 0);
     auto dma_chunk = [&](int t) {
         const int blk = t / nch, ch = t - blk * nch;
-        const unsigned short *s = src0 + (size_t)(ch * KS_KC) * N + (wave >= 2 ? 0 : blk * KS_TR);
+        const unsigned short *s = src0 + (size_t)(ch * KS_KC) * N + (wave >= 2 ? 0 : blk * KNN_TR);
         const unsigned st = lds0 + (t & 1) * KS_STAGE + wave * KS_PLANE;
 #pragma unroll
         for (int i = 0; i < 8; ++i) gm_dma16(s + (size_t)(4 * i) * N, st + i * 1024);
         // the block's 128 squared norms: also by DMA (an ordinary load here would make hipcc drain vmcnt(0) -- the DMAs
         // above included -- in front of its LDS write)
         if (ch == 0 && wave < 2)
-            gm_dma4(sqb + blk * KS_TR + wave * 64 + lane, lds0 + 2 * KS_STAGE + ((blk % 3) * KS_TR + wave * 64) * 4);
+            gm_dma4(sqb + blk * KNN_TR + wave * 64 + lane, lds0 + 2 * KS_STAGE + ((blk % 3) * KNN_TR + wave * 64) * 4);
     };
 
-    // ---- fragment offsets inside a plane: node tile tt (32 nodes), k-step ks (16 channels) ----
-    // lane i = lane & 15 of group (lane >> 4) & 1: row 16 ks + 8 half + (i >> 2) (+ 4), nodes tt*32 + 16 grp + 4 (i & 3)
     int foff[4];
-    {
-        const int i = lane & 15, grp = (lane >> 4) & 1;
 #pragma unroll
-        for (int tt = 0; tt < 4; ++tt) {
-            const int bytecol = (tt * 32 + 16 * grp + 4 * (i & 3)) * 2;
-            const int seg = (bytecol >> 6) ^ (i >> 2);
-            foff[tt] = (8 * half + (i >> 2)) * 256 + seg * 64 + (bytecol & 63);
-        }
-    }
-    int qoff;                                                  // this wave's 32 queries: node tile `wave` of the query planes
-    {
-        const int i = lane & 15, grp = (lane >> 4) & 1;
-        const int bytecol = (wave * 32 + 16 * grp + 4 * (i & 3)) * 2;
-        const int seg = (bytecol >> 6) ^ (i >> 2);
-        qoff = (8 * half + (i >> 2)) * 256 + seg * 64 + (bytecol & 63);
-    }
-    auto frag = [&](const unsigned char *pl, int off) -> gm_bf16x8 {
-        const gm_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((gm_s16x4 __attribute__((address_space(3))) *)(pl + off));
-        const gm_s16x4 hi =
-            __builtin_amdgcn_ds_read_tr16_b64_v4i16((gm_s16x4 __attribute__((address_space(3))) *)(pl + off + 4 * 256));
-        return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    };
+    for (int tt = 0; tt < 4; ++tt) foff[tt] = ks_frag_offset(tt, lane, half);
+    const int qoff = ks_frag_offset(wave, lane, half);
 
     f32x16 acc[4], prev[4];
 #pragma unroll
@@ -230,20 +225,20 @@ __global__ __launch_bounds__(256, 2) void knn_topk_split_kernel(const unsigned s
     gm_wait_vm<0>();
     __syncthreads();
     for (int blk = 0; blk < nblk; ++blk) {
-        const int sq_prev = ((blk + 2) % 3) * KS_TR;
-        const unsigned bits_prev = (unsigned)((blk - 1) * KS_TR) | (unsigned)(4 * half);
+        const int sq_prev = ((blk + 2) % 3) * KNN_TR;
+        const unsigned bits_prev = (unsigned)((blk - 1) * KNN_TR) | (unsigned)(4 * half);
         for (int ch = 0; ch < nch; ++ch) {
             const int t = blk * nch + ch;
             if (t + 1 < T) dma_chunk(t + 1);
             const unsigned char *st = smem + (t & 1) * KS_STAGE;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const gm_bf16x8 qh = frag(st + 2 * KS_PLANE, qoff + ks * 16 * 256);
-                const gm_bf16x8 ql = frag(st + 3 * KS_PLANE, qoff + ks * 16 * 256);
+                const gm_bf16x8 qh = ks_frag(st + 2 * KS_PLANE, qoff + ks * 16 * 256);
+                const gm_bf16x8 ql = ks_frag(st + 3 * KS_PLANE, qoff + ks * 16 * 256);
 #pragma unroll
                 for (int tt = 0; tt < 4; ++tt) {
-                    const gm_bf16x8 ah = frag(st, foff[tt] + ks * 16 * 256);
-                    const gm_bf16x8 al = frag(st + KS_PLANE, foff[tt] + ks * 16 * 256);
+                    const gm_bf16x8 ah = ks_frag(st, foff[tt] + ks * 16 * 256);
+                    const gm_bf16x8 al = ks_frag(st + KS_PLANE, foff[tt] + ks * 16 * 256);
                     acc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, qh, acc[tt], 0, 0, 0);
                     acc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, ql, acc[tt], 0, 0, 0);
                     acc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, qh, acc[tt], 0, 0, 0);
@@ -266,43 +261,20 @@ __global__ __launch_bounds__(256, 2) void knn_topk_split_kernel(const unsigned s
         }
     }
     {
-        const unsigned bits_last = (unsigned)((nblk - 1) * KS_TR) | (unsigned)(4 * half);
+        const unsigned bits_last = (unsigned)((nblk - 1) * KNN_TR) | (unsigned)(4 * half);
 #pragma unroll
-        for (int e = 0; e < 64; ++e) insert(prev, e, ((nblk + 2) % 3) * KS_TR, bits_last);
+        for (int e = 0; e < 64; ++e) insert(prev, e, ((nblk + 2) % 3) * KNN_TR, bits_last);
     }
-    // the two half-waves saw disjoint candidate subsets of the same query
+    // KeyList::merge_halves, written out: as a call it changes the block loop above (a third of the inserts build their
+    // key with v_and + v_or instead of one v_and_or_b32), although the inlined code is the same
     unsigned ok[K + 1], onext = (unsigned)__shfl_xor((int)best.next, 32);
 #pragma unroll
     for (int t = 0; t <= K; ++t) ok[t] = (unsigned)__shfl_xor((int)best.k[t], 32);
 #pragma unroll
     for (int t = 0; t <= K; ++t) best.push(ok[t]);
     best.next = onext < best.next ? onext : best.next;
-    if (half == 0) {
-        const unsigned imask = ~key_mask;
-        const size_t row = (size_t)b * N + myq;
-        I *o = idx + row * K;
-        // CERTIFIED: consecutive entries of the (k+1)-list further apart than 2 m (+ the truncation of the lower key):
-        // the oracle's distances have the same strict order and nothing outside the first k can enter.
-        // LIGHT: not certified, but the (k+2)-th smallest key is beyond 2 m of the k-th: the exact top k are among the
-        // k + 1 listed candidates (every unlisted one is strictly worse than the first k listed) -- pass 3a recomputes
-        // those k + 1 distances exactly.  HEAVY (>= 3 candidates inside the band of the k-th: clusters, duplicates):
-        // pass 3b rescans the whole clip for the query.
-        const float trunc = __uint_as_float(0x3f800000u + imask) - 1.0f;       // relative size of the dropped mantissa bits
-        bool certified = true;
-#pragma unroll
-        for (int t = 0; t < K; ++t) {
-            const float lo = __uint_as_float(best.k[t] & key_mask), hi = __uint_as_float(best.k[t + 1] & key_mask);
-            certified = certified && (hi - lo * (1.0f + trunc) > margin2);
-            o[t] = (I)(best.k[t] & imask);
-        }
-        const bool light = __uint_as_float(best.next & key_mask) -
-                               __uint_as_float(best.k[K - 1] & key_mask) * (1.0f + trunc) > margin2;
-        unc_flag[row] = certified ? 0 : (light ? 1 : 2);
-        if (!certified) {
-            atomicAdd(unc_count, 1);                                           // diagnostics: all uncertified queries
-            if (light) extra[row] = (int)(best.k[K] & imask);          // the (k+1)-th listed candidate (pass 3a reads it)
-        }
-    }
+    if (half == 0)
+        ks_classify_store<K>(best, key_mask, margin2, false, (size_t)b * N + myq, idx, unc_count, unc_flag, extra);
 }
 
 // ---- bf16 inputs: the RAW form (round 3b) -------------------------------------------------------------------------
@@ -321,10 +293,11 @@ __global__ __launch_bounds__(256, 2) void knn_topk_split_kernel(const unsigned s
 constexpr int KR_NS = 4;                    // ring stages of [candidates | queries] (16 KB each)
 constexpr int KR_STAGE = 2 * KS_PLANE;
 constexpr int KR_NT = 8;                    // per-block candidate tables (cj = -2 r_j, sq_j) in flight
-constexpr int KR_LDS = KR_NS * KR_STAGE + KR_NT * KS_TR * 8;
+constexpr int KR_LDS = KR_NS * KR_STAGE + KR_NT * KNN_TR * 8;
 constexpr float KR_TINY = 1.8189894e-12f;   // 2^-39: |cj| below it <=> den_j > 2^40
 
-// pass 1 (RAW): den, sq exactly as knn_normalize_kernel (same chains, same bits) + the candidate table; VE nodes per thread
+// pass 1 (RAW): den, sq by the norm chains of knngraph.h (same order, same bits) + the candidate table; VE nodes per thread
+// from packed loads -- a loop of its own shape, not knn_node_den / knn_node_quotients
 template <int VE>
 __global__ __launch_bounds__(256) void knn_norms_kernel(const unsigned short *__restrict__ x, int64_t sb, int64_t sc,
                                                         float *__restrict__ den_out, float *__restrict__ sq,
@@ -411,17 +384,15 @@ __global__ __launch_bounds__(256, 2) void knn_topk_raw_kernel(const unsigned sho
     const float2 *const sCS = reinterpret_cast<const float2 *>(smem + KR_NS * KR_STAGE);
     const unsigned lds0 = (unsigned)(uintptr_t)(gm_lptr)smem;
 
-    const int bid = xcd_remap(blockIdx.x, nblocks);
-    const int b = bid / tiles_per_clip;
-    const int q0 = (bid % tiles_per_clip) * KS_TQ;
-    const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const KnnCoords w = knn_coords(nblocks, tiles_per_clip);
+    const int b = w.b, q0 = w.q0, lane = w.lane, half = w.half, l31 = w.l31;
+    const int wave = __builtin_amdgcn_readfirstlane(w.wave);
     const int myq = q0 + wave * 32 + l31;
     const float iq = den[(size_t)b * N + myq];
     const float dqi = (sq[(size_t)b * N + myq] + KS_SHIFT) * iq;
     const float2 *csb = cs + (size_t)b * N;
 
-    const int nch = C / KS_KC, nblk = N / KS_TR, T = nblk * nch;
+    const int nch = C / KS_KC, nblk = N / KNN_TR, T = nblk * nch;
 
     // ---- DMA: waves 0, 1 move the candidate tile of every chunk (channel rows 0-15 / 16-31), waves 2, 3 the query tile;
     // instruction i covers 4 channel rows (256 B each); LDS slot s' = lane & 15 of row lane >> 4 holds source segment
@@ -432,38 +403,19 @@ __global__ __launch_bounds__(256, 2) void knn_topk_raw_kernel(const unsigned sho
     const unsigned short *src0 = x + (size_t)b * sb + (size_t)(hw * 16 + rowl) * sc + scol + (pl ? q0 : 0);
     auto dma_chunk = [&](int t) {
         const int blk = t / nch, ch = t - blk * nch;
-        const unsigned short *s = src0 + (size_t)(ch * KS_KC) * sc + (pl ? 0 : blk * KS_TR);
+        const unsigned short *s = src0 + (size_t)(ch * KS_KC) * sc + (pl ? 0 : blk * KNN_TR);
         const unsigned st = lds0 + (t % KR_NS) * KR_STAGE + pl * KS_PLANE + hw * 4096;
 #pragma unroll
         for (int i = 0; i < 4; ++i) gm_dma16(s + (size_t)(4 * i) * sc, st + i * 1024);
         // the block's candidate table: 128 x (cj, sq_j) = 1 KiB, by DMA as well (see knn_topk_split_kernel)
         if (ch == 0 && wave == 0)
-            gm_dma16(csb + blk * KS_TR + lane * 2, lds0 + KR_NS * KR_STAGE + (blk % KR_NT) * (KS_TR * 8));
+            gm_dma16(csb + blk * KNN_TR + lane * 2, lds0 + KR_NS * KR_STAGE + (blk % KR_NT) * (KNN_TR * 8));
     };
 
     int foff[4];
-    {
-        const int i = lane & 15, grp = (lane >> 4) & 1;
 #pragma unroll
-        for (int tt = 0; tt < 4; ++tt) {
-            const int bytecol = (tt * 32 + 16 * grp + 4 * (i & 3)) * 2;
-            const int seg = (bytecol >> 6) ^ (i >> 2);
-            foff[tt] = (8 * half + (i >> 2)) * 256 + seg * 64 + (bytecol & 63);
-        }
-    }
-    int qoff;
-    {
-        const int i = lane & 15, grp = (lane >> 4) & 1;
-        const int bytecol = (wave * 32 + 16 * grp + 4 * (i & 3)) * 2;
-        const int seg = (bytecol >> 6) ^ (i >> 2);
-        qoff = (8 * half + (i >> 2)) * 256 + seg * 64 + (bytecol & 63);
-    }
-    auto frag = [&](const unsigned char *p, int off) -> gm_bf16x8 {
-        const gm_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((gm_s16x4 __attribute__((address_space(3))) *)(p + off));
-        const gm_s16x4 hi =
-            __builtin_amdgcn_ds_read_tr16_b64_v4i16((gm_s16x4 __attribute__((address_space(3))) *)(p + off + 4 * 256));
-        return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    };
+    for (int tt = 0; tt < 4; ++tt) foff[tt] = ks_frag_offset(tt, lane, half);
+    const int qoff = ks_frag_offset(wave, lane, half);
 
     f32x16 acc[4];
     KeyList<K + 1> best;
@@ -509,8 +461,8 @@ __global__ __launch_bounds__(256, 2) void knn_topk_raw_kernel(const unsigned sho
     // mfma_valu_bench), so the shadow bought nothing, and the 128 v_mov per block of "prev = acc; acc = 0" were a fifth of
     // the kernel's VALU instructions at 64 channels.)
     for (int blk = 0; blk < nblk; ++blk) {
-        const int tb = (blk % KR_NT) * KS_TR;
-        const unsigned bits = (unsigned)(blk * KS_TR);                  // wave-uniform: (bits | loc_c) stays in SGPRs
+        const int tb = (blk % KR_NT) * KNN_TR;
+        const unsigned bits = (unsigned)(blk * KNN_TR);                  // wave-uniform: (bits | loc_c) stays in SGPRs
         auto chunk = [&](int ch, auto first_c) __attribute__((always_inline)) {
             constexpr bool FIRST = decltype(first_c)::value;
             const int t = blk * nch + ch;
@@ -525,10 +477,10 @@ __global__ __launch_bounds__(256, 2) void knn_topk_raw_kernel(const unsigned sho
             const unsigned char *st = smem + (t % KR_NS) * KR_STAGE;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const gm_bf16x8 qf = frag(st + KS_PLANE, qoff + ks * 16 * 256);
+                const gm_bf16x8 qf = ks_frag(st + KS_PLANE, qoff + ks * 16 * 256);
 #pragma unroll
                 for (int tt = 0; tt < 4; ++tt) {
-                    const gm_bf16x8 af = frag(st, foff[tt] + ks * 16 * 256);
+                    const gm_bf16x8 af = ks_frag(st, foff[tt] + ks * 16 * 256);
                     if (FIRST && ks == 0) {
                         const f32x16 zero = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
                         acc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, qf, zero, 0, 0, 0);
@@ -554,33 +506,9 @@ __global__ __launch_bounds__(256, 2) void knn_topk_raw_kernel(const unsigned sho
 #pragma unroll
     for (int t = 0; t <= K; ++t) best.k[t] |= (unsigned)(4 * half);
     best.next |= (unsigned)(4 * half);
-    unsigned ok[K + 1], onext = (unsigned)__shfl_xor((int)best.next, 32);
-#pragma unroll
-    for (int t = 0; t <= K; ++t) ok[t] = (unsigned)__shfl_xor((int)best.k[t], 32);
-#pragma unroll
-    for (int t = 0; t <= K; ++t) best.push(ok[t]);
-    best.next = onext < best.next ? onext : best.next;
-    if (half == 0) {
-        const unsigned imask = ~key_mask;
-        const size_t row = (size_t)b * N + myq;
-        I *o = idx + row * K;
-        const float trunc = __uint_as_float(0x3f800000u + imask) - 1.0f;
-        const float band = margin2 * iq;                                       // the keys are den_q times the distances
-        bool certified = !clip_bad;
-#pragma unroll
-        for (int t = 0; t < K; ++t) {
-            const float lo = __uint_as_float(best.k[t] & key_mask), hi = __uint_as_float(best.k[t + 1] & key_mask);
-            certified = certified && (hi - lo * (1.0f + trunc) > band);
-            o[t] = (I)(best.k[t] & imask);
-        }
-        const bool light = !clip_bad && __uint_as_float(best.next & key_mask) -
-                                                __uint_as_float(best.k[K - 1] & key_mask) * (1.0f + trunc) > band;
-        unc_flag[row] = certified ? 0 : (light ? 1 : 2);
-        if (!certified) {
-            atomicAdd(unc_count, 1);
-            if (light) extra[row] = (int)(best.k[K] & imask);          // the (k+1)-th listed candidate (pass 3a reads it)
-        }
-    }
+    best.merge_halves();
+    if (half == 0)                                                 // the keys are den_q times the distances: so is the band
+        ks_classify_store<K>(best, key_mask, margin2 * iq, clip_bad, (size_t)b * N + myq, idx, unc_count, unc_flag, extra);
 }
 
 // pass 3a (LIGHT queries: exact distances to the k + 1 listed candidates only) lives at the head of knn_exact_clip_kernel.
@@ -654,7 +582,7 @@ __global__ __launch_bounds__(256) void knn_exact_clip_kernel(const T *__restrict
 #pragma unroll
             for (int v = 0; v < K + 2; ++v) {
                 const float dv = denb[col[v]];
-                for (int c = lane; c < C; c += 64) sL[v * C + c] = __fdiv_rn(ks_ld(xb + (size_t)c * sc + col[v]), dv);
+                for (int c = lane; c < C; c += 64) sL[v * C + c] = __fdiv_rn(ld_as_f32(xb + (size_t)c * sc + col[v]), dv);
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -699,15 +627,14 @@ __global__ __launch_bounds__(256) void knn_exact_clip_kernel(const T *__restrict
         __syncthreads();
         for (int i = tid; i < ng * C; i += 256) {
             const int qi = i / C, c = i - qi * C, q = s_list[g0 + qi];
-            sQ[qi * C + c] = __fdiv_rn(ks_ld(xb + (size_t)c * sc + q), denb[q]);
+            sQ[qi * C + c] = __fdiv_rn(ld_as_f32(xb + (size_t)c * sc + q), denb[q]);
         }
-        float sqq[QG], bd[QG][K];
-        int bi[QG][K];
+        float sqq[QG];
+        TopK<K> best[QG];
 #pragma unroll
         for (int qi = 0; qi < QG; ++qi) {
             sqq[qi] = qi < ng ? sqb[s_list[g0 + qi]] : 0.0f;
-#pragma unroll
-            for (int t = 0; t < K; ++t) { bd[qi][t] = INFINITY; bi[qi][t] = 0x7fffffff; }
+            best[qi].init();
         }
         for (int j0 = 0; j0 < N; j0 += W) {                    // candidate column ranges, ascending
             float g[KX_NU][QG], dj[KX_NU];
@@ -749,7 +676,7 @@ __global__ __launch_bounds__(256) void knn_exact_clip_kernel(const T *__restrict
 #pragma unroll
                         for (int u = 0; u < KX_NU; ++u)
                             v[k2][u] = (tid + 256 * u < W)
-                                           ? __fdiv_rn(ks_ld(buf + (size_t)(cc0 + k2) * W + tid + 256 * u), dj[u]) : 0.0f;
+                                           ? __fdiv_rn(ld_as_f32(buf + (size_t)(cc0 + k2) * W + tid + 256 * u), dj[u]) : 0.0f;
 #pragma unroll
                     for (int k2 = 0; k2 < NC; ++k2) {
                         const int c = ck * chc + cc0 + k2;
@@ -776,21 +703,7 @@ __global__ __launch_bounds__(256) void knn_exact_clip_kernel(const T *__restrict
                     const float sqj = sqb[j];
 #pragma unroll
                     for (int qi = 0; qi < QG; ++qi) {
-                        if (qi < ng) {
-                            float v = __builtin_fmaf(-2.0f, g[u][qi], sqq[qi]) + sqj;      // (sq_i + (-2 g)) + sq_j
-                            int vi = j;
-                            const float v0 = v;
-#pragma unroll
-                            for (int t = 0; t < K; ++t) {                              // TopK::push_ascending
-                                const bool take = v0 < bd[qi][t];
-                                const float od = bd[qi][t];
-                                const int oi = bi[qi][t];
-                                bd[qi][t] = take ? v : od;
-                                bi[qi][t] = take ? vi : oi;
-                                v = take ? od : v;
-                                vi = take ? oi : vi;
-                            }
-                        }
+                        if (qi < ng) best[qi].push_ascending(__builtin_fmaf(-2.0f, g[u][qi], sqq[qi]) + sqj, j);
                     }
                 }
             }
@@ -801,7 +714,8 @@ __global__ __launch_bounds__(256) void knn_exact_clip_kernel(const T *__restrict
                 I *o = idx + ((size_t)b * N + s_list[g0 + qi]) * K;
 #pragma unroll
                 for (int t = 0; t < K; ++t) {
-                    const unsigned long long mine = bi[qi][0] == 0x7fffffff ? ~0ull : ks_key64(bd[qi][0], bi[qi][0]);
+                    TopK<K> &mb = best[qi];
+                    const unsigned long long mine = mb.i[0] == 0x7fffffff ? ~0ull : ks_key64(mb.d[0], mb.i[0]);
                     unsigned long long m = mine;
 #pragma unroll
                     for (int s2 = 1; s2 < 64; s2 <<= 1) {
@@ -817,9 +731,9 @@ __global__ __launch_bounds__(256) void knn_exact_clip_kernel(const T *__restrict
                     if (tid == 0) o[t] = (I)(unsigned)(m & 0xffffffffull);
                     if (mine == m) {                                           // the winner pops its head
 #pragma unroll
-                        for (int u = 0; u + 1 < K; ++u) { bd[qi][u] = bd[qi][u + 1]; bi[qi][u] = bi[qi][u + 1]; }
-                        bd[qi][K - 1] = INFINITY;
-                        bi[qi][K - 1] = 0x7fffffff;
+                        for (int u = 0; u + 1 < K; ++u) { mb.d[u] = mb.d[u + 1]; mb.i[u] = mb.i[u + 1]; }
+                        mb.d[K - 1] = INFINITY;
+                        mb.i[K - 1] = 0x7fffffff;
                     }
                 }
             }
@@ -841,20 +755,46 @@ static float ks_margin(int C) {
 }
 static float ks_margin_raw(int C) { return 2.0f * (1.7881393e-7f * (float)C + 3.6e-7f) + 2e-6f; }
 static bool ks_supported(int C, int N, int k) {
-    return C > 0 && C % KS_KC == 0 && N >= KS_TR && N % KS_TR == 0 && N <= 4096 && k >= 1 && k <= 4 && k <= N &&
+    return C > 0 && C % KS_KC == 0 && N >= KNN_TR && N % KNN_TR == 0 && N <= 4096 && k >= 1 && k <= 4 && k <= N &&
            ks_margin(C) < 0.9f * KS_SHIFT && kx_front_bytes(k, C) + (size_t)N * 4 <= 160 * 1024;   // (exact pass's LDS)
 }
-static size_t ks_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
-struct KsArgs {
+// the workspace: sq, den | planes (f32 inputs) or the candidate table (bf16 inputs) | counters | flags | extra
+struct KsWs {
+    float *sq, *den;
+    unsigned short *xh, *xl;
+    float2 *cs;
+    int *count, *extra;
+    unsigned char *flag;
+};
+static size_t ks_layout(void *ws, int dtype, int B, int C, int N, KsWs &p) {
+    const size_t nodes = (size_t)B * N, e = nodes * C;
+    WsCarve w{(char *)ws, 0};
+    p.sq = w.take<float>(nodes * 4);
+    p.den = w.take<float>(nodes * 4);
+    p.xh = p.xl = nullptr;
+    p.cs = nullptr;
+    if (dtype == GRAFP_BF16) {
+        p.cs = w.take<float2>(nodes * 8);
+    } else {
+        p.xh = w.take<unsigned short>(e * 2);
+        p.xl = w.take<unsigned short>(e * 2);
+    }
+    p.count = w.take<int>(256);
+    p.flag = w.take<unsigned char>(nodes);
+    p.extra = w.take<int>(nodes * 4);
+    return w.off;
+}
+static size_t ks_workspace(int dtype, int B, int C, int N) {
+    KsWs p;
+    return (B <= 0 || C <= 0 || N <= 0) ? 0 : ks_layout(nullptr, dtype, B, C, N, p);
+}
+
+struct KsArgs : KsWs {
     const void *x;
     bool f32, raw;
-    const float2 *cs;
     int64_t sb, sc;
-    const unsigned short *xh, *xl;
-    const float *sq, *den;
-    int *count, *extra, *n_unc;
-    unsigned char *flag;
+    int *n_unc;
     void *idx;
     int B, C, N;
     float margin2;
@@ -872,7 +812,7 @@ template <int K, typename I, typename T> static void ks_launch_exact(const KsArg
                        a.sq, a.flag, (I *)a.idx, a.C, a.N, chc, a.count, a.n_unc, a.extra, GRAFP_TUNE_INT("GRAFP_KX_STOP", 0));
 }
 template <int K, typename I> static void ks_launch(const KsArgs &a, hipStream_t s) {
-    const int tiles = a.N / KS_TQ, nblocks = a.B * tiles;
+    const int tiles = a.N / KNN_TQ, nblocks = a.B * tiles;
     if (a.raw) {
         (void)hipFuncSetAttribute((const void *)knn_topk_raw_kernel<K, I>, hipFuncAttributeMaxDynamicSharedMemorySize, KR_LDS);
         hipLaunchKernelGGL((knn_topk_raw_kernel<K, I>), dim3(nblocks), dim3(256), KR_LDS, s, (const unsigned short *)a.x,
@@ -912,16 +852,10 @@ extern "C" int grafp_knn_split_preferred_for(int dtype, int C, int N, int k) {
     return grafp::ks_supported(C, N, k) && C <= GRAFP_TUNE_INT("GRAFP_KNN_RAW_MAXC", 256) ? 1 : 0;
 }
 
-static size_t ks_workspace(int dtype, int B, int C, int N) {
-    using namespace grafp;
-    if (B <= 0 || C <= 0 || N <= 0) return 0;
-    const size_t e = (size_t)B * C * N;
-    // sq, den | planes (f32 inputs) or the candidate table (bf16 inputs) | counters | flags | extra
-    const size_t mid = dtype == GRAFP_BF16 ? ks_align((size_t)B * N * 8) : 2 * ks_align(e * 2);
-    return 2 * ks_align((size_t)B * N * 4) + mid + 256 + ks_align((size_t)B * N) + ks_align((size_t)B * N * 4);
+extern "C" size_t grafp_knn_split_workspace(int B, int C, int N) { return grafp::ks_workspace(GRAFP_F32, B, C, N); }
+extern "C" size_t grafp_knn_split_workspace_for(int dtype, int B, int C, int N) {
+    return grafp::ks_workspace(dtype, B, C, N);
 }
-extern "C" size_t grafp_knn_split_workspace(int B, int C, int N) { return ks_workspace(GRAFP_F32, B, C, N); }
-extern "C" size_t grafp_knn_split_workspace_for(int dtype, int B, int C, int N) { return ks_workspace(dtype, B, C, N); }
 
 extern "C" int grafp_knn_graph_split(const void *x, int dtype, int64_t stride_b, int64_t stride_c, int B, int C, int N,
                                      int k, void *idx, int idx_is_i32, void *ws, size_t ws_bytes, int32_t *n_uncertified,
@@ -932,28 +866,14 @@ extern "C" int grafp_knn_graph_split(const void *x, int dtype, int64_t stride_b,
                   "knn_graph_split: unsupported shape B=%d C=%d N=%d k=%d (C %% 32, N %% 128, N <= 4096, k <= 4)", B, C, N, k);
     GRAFP_REQUIRE(dtype == GRAFP_F32 || dtype == GRAFP_BF16, "knn_graph_split: dtype %d not in {f32, bf16}", dtype);
     GRAFP_REQUIRE((int64_t)B * N < (1ll << 31), "knn_graph_split: too many nodes");
-    const size_t need = ks_workspace(dtype, B, C, N);
+    KsArgs a;
+    const size_t need = ks_layout(ws, dtype, B, C, N, a);
     if (!ws || ws_bytes < need) {
         set_error("knn_graph_split: workspace %zu bytes < required %zu", ws_bytes, need);
         return GRAFP_ERR_WORKSPACE;
     }
     hipStream_t s = (hipStream_t)stream;
     const bool raw = dtype == GRAFP_BF16;
-    const size_t e = (size_t)B * C * N;
-    char *p = (char *)ws;
-    float *sq = (float *)p;                       p += ks_align((size_t)B * N * 4);
-    float *den = (float *)p;                      p += ks_align((size_t)B * N * 4);
-    unsigned short *xh = nullptr, *xl = nullptr;
-    float2 *cs = nullptr;
-    if (raw) {
-        cs = (float2 *)p;                         p += ks_align((size_t)B * N * 8);
-    } else {
-        xh = (unsigned short *)p;                 p += ks_align(e * 2);
-        xl = (unsigned short *)p;                 p += ks_align(e * 2);
-    }
-    int *count = (int *)p;                        p += 256;
-    unsigned char *flag = (unsigned char *)p;     p += ks_align((size_t)B * N);
-    int *extra = (int *)p;                        p += ks_align((size_t)B * N * 4);
     GRAFP_REQUIRE((((uintptr_t)ws | (uintptr_t)x) & 15) == 0 && (stride_b * (dtype == GRAFP_F32 ? 4 : 2)) % 16 == 0 &&
                       (stride_c * (dtype == GRAFP_F32 ? 4 : 2)) % 16 == 0,
                   "knn_graph_split: input rows and workspace must be 16-byte aligned");
@@ -965,24 +885,23 @@ extern "C" int grafp_knn_graph_split(const void *x, int dtype, int64_t stride_b,
         const int64_t threads = nodes / ve;
         const dim3 gn((unsigned)((threads + 255) / 256));
         if (ve == 8)
-            hipLaunchKernelGGL(knn_norms_kernel<8>, gn, dim3(256), 0, s, (const unsigned short *)x, stride_b, stride_c, den,
-                               sq, cs, B, C, N, count);
+            hipLaunchKernelGGL(knn_norms_kernel<8>, gn, dim3(256), 0, s, (const unsigned short *)x, stride_b, stride_c, a.den,
+                               a.sq, a.cs, B, C, N, a.count);
         else if (ve == 4)
-            hipLaunchKernelGGL(knn_norms_kernel<4>, gn, dim3(256), 0, s, (const unsigned short *)x, stride_b, stride_c, den,
-                               sq, cs, B, C, N, count);
+            hipLaunchKernelGGL(knn_norms_kernel<4>, gn, dim3(256), 0, s, (const unsigned short *)x, stride_b, stride_c, a.den,
+                               a.sq, a.cs, B, C, N, a.count);
         else
-            hipLaunchKernelGGL(knn_norms_kernel<2>, gn, dim3(256), 0, s, (const unsigned short *)x, stride_b, stride_c, den,
-                               sq, cs, B, C, N, count);
+            hipLaunchKernelGGL(knn_norms_kernel<2>, gn, dim3(256), 0, s, (const unsigned short *)x, stride_b, stride_c, a.den,
+                               a.sq, a.cs, B, C, N, a.count);
         GRAFP_CHECK_LAUNCH("knn_norms_kernel");
     } else {
         const dim3 gn((N + 255) / 256, B);
         hipLaunchKernelGGL(knn_normalize_split_kernel<float>, gn, dim3(256), 0, s, (const float *)x, stride_b, stride_c,
-                           den, sq, xh, xl, C, N, count);
+                           a.den, a.sq, a.xh, a.xl, C, N, a.count);
         GRAFP_CHECK_LAUNCH("knn_normalize_split_kernel");
     }
-    KsArgs a;
-    a.x = x; a.f32 = dtype == GRAFP_F32; a.raw = raw; a.cs = cs; a.sb = stride_b; a.sc = stride_c; a.xh = xh; a.xl = xl; a.sq = sq; a.den = den;
-    a.count = count; a.n_unc = (int *)n_uncertified; a.flag = flag; a.extra = extra; a.idx = idx; a.B = B; a.C = C; a.N = N;
+    a.x = x; a.f32 = dtype == GRAFP_F32; a.raw = raw; a.sb = stride_b; a.sc = stride_c;
+    a.n_unc = (int *)n_uncertified; a.idx = idx; a.B = B; a.C = C; a.N = N;
     a.margin2 = 2.0f * (raw ? ks_margin_raw(C) : ks_margin(C));
     a.key_mask = ~((1u << ks_index_bits(N)) - 1u);
     if (idx_is_i32) ks_launch_k<int32_t>(k, a, s);

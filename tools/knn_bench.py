@@ -1,5 +1,6 @@
 """k-NN graph build per encoder stage: the exact-f32 MFMA kernel (knn_graph.hip) against the split-bf16 certified path
-(knn_split.hip), random unit features and -- with --model -- the encoder's own features.
+(knn_split.hip) and, on the random features, the bf16 pre-filter (knn_pre.hip, ops.knn_graph(..., prefilter=True)) for
+the stages grafp_knn_pre_supported accepts; random unit features and -- with --model -- the encoder's own features.
 
     python tools/knn_bench.py [--clips 2048] [--model]
 """
@@ -11,6 +12,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from grafp_amd import ops  # noqa: E402
+from grafp_amd._lib import lib  # noqa: E402
 
 
 def timeit(fn, reps=5):
@@ -34,7 +36,7 @@ def main():
                          "f32: (B, C, N) f32 (split hi/lo planes)")
     args = ap.parse_args()
     dev = "cuda:0"
-    depth, tot = (2, 2, 6, 2), [0.0, 0.0]
+    depth, tot = (2, 2, 6, 2), [0.0, 0.0, 0.0]
     feats = {}
     if args.model:
         from grafp_amd.train import build_model, synthetic_batch
@@ -65,11 +67,17 @@ def main():
         t_split = timeit(lambda: ops.knn_graph_split(x, 3, layout=lay, index_dtype=torch.int32))
         a = ops.knn_graph(x, 3, layout=lay, index_dtype=torch.int32, prefilter=False)
         b, unc = ops.knn_graph_split(x, 3, layout=lay, index_dtype=torch.int32, return_uncertified=True)
+        pre = "not supported"
+        if lib.grafp_knn_pre_supported(C, N, 3):
+            t_pre = timeit(lambda: ops.knn_graph(x, 3, layout=lay, index_dtype=torch.int32, prefilter=True))
+            p = ops.knn_graph(x, 3, layout=lay, index_dtype=torch.int32, prefilter=True)
+            tot[2] += t_pre * depth[stage]
+            pre = f"{t_pre:8.1f} us, equal {bool(torch.equal(a, p))}"
         fl = 2.0 * N * N * C * args.clips
         tot[0] += t_f32 * depth[stage]
         tot[1] += t_split * depth[stage]
         line = (f"s{stage} C={C:4d} N={N:5d} clips={args.clips}: exact-f32 {t_f32:8.1f} us ({fl / t_f32 / 1e6:6.1f} TF/s) | split "
-                f"{t_split:8.1f} us ({fl / t_split / 1e6:6.1f} TF/s equiv) | equal {bool(torch.equal(a, b))} | uncertified "
+                f"{t_split:8.1f} us ({fl / t_split / 1e6:6.1f} TF/s equiv) | equal {bool(torch.equal(a, b))} | pre-filter {pre} | uncertified "
                 f"{int(unc)} of {args.clips * N} ({100.0 * int(unc) / (args.clips * N):.2f} %)")
         if C in feats:
             xf, layout = feats[C]
@@ -81,7 +89,8 @@ def main():
             line += (f" || encoder features ({a.shape[0]} clips): {tm_f32:7.1f} vs {tm_split:7.1f} us, equal "
                      f"{bool(torch.equal(a, b))}, uncertified {100.0 * int(unc) / nq:.2f} %")
         print(line, flush=True)
-    print(f"per step (blocks per stage 2, 2, 6, 2): exact-f32 {tot[0] / 1e3:.2f} ms, split {tot[1] / 1e3:.2f} ms")
+    print(f"per step (blocks per stage 2, 2, 6, 2): exact-f32 {tot[0] / 1e3:.2f} ms, split {tot[1] / 1e3:.2f} ms, "
+          f"pre-filter (supported stages) {tot[2] / 1e3:.2f} ms")
 
 
 if __name__ == "__main__":
