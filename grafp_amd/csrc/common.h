@@ -88,6 +88,21 @@ template <typename V> __device__ __forceinline__ V ld_once_nt(const V *p) {
 }  // namespace grafp
 #define GRAFP_LD_ONCE(bit, p) (((GRAFP_NT_LOADS) & (bit)) ? grafp::ld_once_nt(p) : *(p))
 
+namespace grafp {
+// ---- host: a workspace is a row of 256-byte aligned arrays.  Each entry writes its layout ONCE, as a function over a
+// WsCarve: with a null base it only adds up the size (every pointer null), with the caller's buffer it hands out the arrays.
+static inline size_t ws_align256(size_t v) { return (v + 255) & ~(size_t)255; }
+struct WsCarve {
+    char *base;
+    size_t off;
+    template <typename T> T *take(size_t bytes) {
+        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+        off += ws_align256(bytes);
+        return p;
+    }
+};
+}  // namespace grafp
+
 #define GRAFP_REQUIRE(cond, ...)              \
     do {                                      \
         if (!(cond)) {                        \

@@ -380,13 +380,20 @@ extern "C" int grafp_pq_assign_f32(const float *x, int64_t n, int D, int G, cons
     return GRAFP_OK;
 }
 
-static size_t km_align(size_t v) { return (v + 255) & ~(size_t)255; }
+// the workspace of grafp_kmeans_f32: asg (n, G) | partial (nchunks, G, k, D / G) | pcnt (nchunks, G, k)
+static size_t kmeans_layout(void *ws, int64_t n, int D, int G, int k, int32_t *&asg, float *&partial, int32_t *&pcnt) {
+    const size_t nchunks = (size_t)((n + grafp::KM_CHUNK - 1) / grafp::KM_CHUNK);
+    grafp::WsCarve w{(char *)ws, 0};
+    asg = w.take<int32_t>((size_t)n * G * sizeof(int32_t));
+    partial = w.take<float>(nchunks * G * k * (D / G) * sizeof(float));
+    pcnt = w.take<int32_t>(nchunks * G * k * sizeof(int32_t));
+    return w.off;
+}
 
 extern "C" size_t grafp_kmeans_workspace(int64_t n, int D, int G, int k) {
-    if (n <= 0 || D <= 0 || G <= 0 || D % G || k <= 0) return 0;
-    const size_t nchunks = (size_t)((n + grafp::KM_CHUNK - 1) / grafp::KM_CHUNK);
-    return km_align((size_t)n * G * sizeof(int32_t)) + km_align(nchunks * G * k * (D / G) * sizeof(float)) +
-           km_align(nchunks * G * k * sizeof(int32_t));
+    int32_t *asg, *pcnt;
+    float *partial;
+    return (n <= 0 || D <= 0 || G <= 0 || D % G || k <= 0) ? 0 : kmeans_layout(nullptr, n, D, G, k, asg, partial, pcnt);
 }
 
 extern "C" int grafp_kmeans_f32(const float *x, int64_t n, int D, int G, const float *base, const int32_t *base_idx,
@@ -397,17 +404,16 @@ extern "C" int grafp_kmeans_f32(const float *x, int64_t n, int D, int G, const f
     GRAFP_REQUIRE((base == nullptr) == (base_idx == nullptr), "kmeans: base and base_idx go together");
     GRAFP_REQUIRE(n >= 1 && D > 0 && G > 0 && D % G == 0 && k >= 1 && niter >= 0 && G <= 65535,
                   "kmeans: bad shape n=%lld D=%d G=%d k=%d niter=%d", (long long)n, D, G, k, niter);
-    const size_t need = grafp_kmeans_workspace(n, D, G, k);
+    int32_t *asg, *pcnt;
+    float *partial;
+    const size_t need = kmeans_layout(nullptr, n, D, G, k, asg, partial, pcnt);
     if (!ws || ws_bytes < need) {
         set_error("kmeans: workspace %zu bytes < required %zu", ws_bytes, need);
         return GRAFP_ERR_WORKSPACE;
     }
     const int d = D / G;
     const int nchunks = (int)((n + KM_CHUNK - 1) / KM_CHUNK);
-    char *w = (char *)ws;
-    int32_t *asg = (int32_t *)w;            w += km_align((size_t)n * G * sizeof(int32_t));
-    float *partial = (float *)w;            w += km_align((size_t)nchunks * G * k * d * sizeof(float));
-    int32_t *pcnt = (int32_t *)w;
+    kmeans_layout(ws, n, D, G, k, asg, partial, pcnt);
     hipStream_t s = (hipStream_t)stream;
     const int64_t ne = (int64_t)G * k * d;
     hipLaunchKernelGGL(kmeans_init_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, s, x, D, G, base, base_idx,

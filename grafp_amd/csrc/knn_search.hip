@@ -17,8 +17,18 @@
 //      rescanned exactly by that workgroup with the same arithmetic -- slow, never wrong.
 // A workgroup is 4 waves arranged as QW query-waves x RW row-waves (1x4 for <= 32 queries, 2x2 for <= 64,
 // else 4x1); the query operand (32 queries x 128 dims) lives in 64 VGPRs per lane for the whole kernel.
-// Ordering everywhere is (distance, id) lexicographic => lowest id wins ties.  search_merge_kernel
-// (grafp_merge_topk) merges per-GPU shard results.
+// search_merge_kernel (grafp_merge_topk) merges per-GPU shard results.
+//
+// THE CONTRACT (stated here once; the kernels below point back to it).  Both entries return the bits of
+// oracle/csrc/flat_search.c:
+//   (1) ip = the c-ordered fmaf chain over the 128 dimensions, from 0 (v_mfma_f32_32x32x2_f32 is that chain; the one
+//       scalar form of it is exact_l2 below);
+//   (2) distance = (qq + dd) - 2 ip in that order, clamped at 0; qq and dd are the same chain over x * x;
+//   (3) results ascend by (distance, id) lexicographically: the lowest id wins a tie;
+//   (4) a query with fewer than k rows is padded with id -1 and distance +inf;
+//   (5) the bf16 pre-filter may only DROP rows that cannot be among the k best -- the SLACK inequality
+//       |d~ - d| <= SB_SLACK (qq + dd), derived in front of the second half of this file -- and every distance it
+//       returns is (1)-(2) again.
 //
 // Roofline: one pass streams n*(512+4) bytes; 2*128 flops per (row, query).  HBM-bound up to ~50
 // queries per pass, f32-matrix-bound (157.3 TFLOP/s) beyond.  See DESIGN.md "search_scan_kernel".
@@ -49,16 +59,60 @@ constexpr int SR_NSUB = 16;      // pre-filter path: the slots are SR_NSUB sub-l
                                  // in L2 (a small batch spent 40 us of a 90 us scan there)
 constexpr int SR_SUBCAP = SR_CAP / SR_NSUB;
 
-// (database slice, query group) of this workgroup.  The grid is (slices, query groups); workgroups go to the 8 XCDs
+// Where a thread of one of the four scan kernels stands: its wave's place in the QW x RW arrangement, and the workgroup's
+// (database slice, query group) with the slice's rows [row_begin, row_end) of a launch over rows [row0, end).
+// The grid is (slices, query groups); workgroups go to the 8 XCDs
 // round-robin in dispatch order (x fastest), so without a remap the query groups that stream the SAME slice sit on
 // different XCDs and every one of them pulls the slice through its own L2: at nq = 4096 the 256 MB bf16 copy was read 32
 // times from the memory side (5 TB/s, the bound of that launch).  With the remap an XCD owns whole slices: all query
 // groups of a slice run side by side on one L2 and the database crosses the fabric about once.
-__device__ __forceinline__ void search_block(int &split, int &qgroup) {
-    const int total = (int)(gridDim.x * gridDim.y);
-    const int v = xcd_remap((int)(blockIdx.x + gridDim.x * blockIdx.y), total);
-    split = v / (int)gridDim.y;
-    qgroup = v - split * (int)gridDim.y;
+struct ScanCoords {
+    int wave, lane, half, l31, qw, rw, split, qgroup;
+    int64_t row_begin, row_end;
+};
+template <int QW>
+__device__ __forceinline__ ScanCoords scan_coords(int64_t row0, int64_t rows_per_split, int64_t end) {
+    ScanCoords c;
+    c.wave = threadIdx.x >> 6;
+    c.lane = threadIdx.x & 63;
+    c.half = c.lane >> 5;
+    c.l31 = c.lane & 31;
+    c.qw = c.wave % QW;
+    c.rw = c.wave / QW;
+    const int v = xcd_remap((int)(blockIdx.x + gridDim.x * blockIdx.y), (int)(gridDim.x * gridDim.y));
+    c.split = v / (int)gridDim.y;
+    c.qgroup = v - c.split * (int)gridDim.y;
+    c.row_begin = row0 + (int64_t)c.split * rows_per_split;
+    c.row_end = (c.row_begin + rows_per_split < end) ? c.row_begin + rows_per_split : end;
+    return c;
+}
+
+// The oracle's distance of one database row, items (1) and (2) of the contract: the whole 512-byte row is requested
+// before the dependent fmaf chain starts (every lane reads a different row); sq is the query in LDS.
+__device__ __forceinline__ float exact_l2(const float *__restrict__ db, const float *__restrict__ dd, int64_t row,
+                                          const float *sq, float myqq) {
+    f32x4 xr[SR_D / 4];
+    const f32x4 *rp = reinterpret_cast<const f32x4 *>(db) + row * (SR_D / 4);
+#pragma unroll
+    for (int c4 = 0; c4 < SR_D / 4; ++c4) xr[c4] = rp[c4];
+    const float ddr = dd[row];
+    float ip = 0.0f;
+#pragma unroll
+    for (int c4 = 0; c4 < SR_D / 4; ++c4) {
+        ip = __builtin_fmaf(xr[c4][0], sq[4 * c4 + 0], ip);
+        ip = __builtin_fmaf(xr[c4][1], sq[4 * c4 + 1], ip);
+        ip = __builtin_fmaf(xr[c4][2], sq[4 * c4 + 2], ip);
+        ip = __builtin_fmaf(xr[c4][3], sq[4 * c4 + 3], ip);
+    }
+    const float d = (myqq + ddr) - 2.0f * ip;
+    return d < 0.0f ? 0.0f : d;
+}
+
+// thr[qi] = the k-th smallest of the wave's 64 lane values (+inf when fewer than k lanes hold a finite one)
+__device__ __forceinline__ void store_kth_smallest(float d, int lane, int k, float *out) {
+    int i = lane;
+    wave_sort64(d, i, lane);
+    if (lane == k - 1) *out = d;
 }
 
 // ---- squared row norms (the `index.add` step); thread j chains over row j out of an LDS tile ------
@@ -172,8 +226,8 @@ __global__ __launch_bounds__(256) void search_init_kernel(const float *__restric
                                                           int *__restrict__ gmin, int *__restrict__ cnt) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < (int64_t)nq * SR_GROUPS) gmin[i] = 0x7f800000;  // +inf
-    if (i < (int64_t)nq * SR_NSUB) cnt[i] = 0;          // (the f32 path only uses the first nq)
     if (i < nq) {
+        cnt[i] = 0;                                       // one list, one counter per query on this path
         const float *row = q + i * SR_D;
         float s = 0.0f;
         for (int c = 0; c < SR_D; ++c) s = __builtin_fmaf(row[c], row[c], s);   // same chain as row_sqnorm_kernel
@@ -194,30 +248,26 @@ __global__ __launch_bounds__(256, 2) void search_bound_kernel(const float *__res
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *tile = reinterpret_cast<float *>(smem);  // [TROWS][SR_LS]
     float *sDD = tile + TROWS * SR_LS;              // [TROWS]
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
-    const int qw = wave % QW, rw = wave / QW;
-    int split, qgroup;
-    search_block(split, qgroup);
-    const int qi = (qgroup * QW + qw) * 32 + l31;
+    const ScanCoords c = scan_coords<QW>(0, rows_per_split, n_sample);
+    const int qi = (c.qgroup * QW + c.qw) * 32 + c.l31;
     const bool qvalid = qi < nq;
-    const int64_t row_begin = (int64_t)split * rows_per_split;
-    const int64_t row_end = (row_begin + rows_per_split < n_sample) ? row_begin + rows_per_split : n_sample;
     float bq[64];
-    load_queries(q, qi, qvalid, half, bq);
+    load_queries(q, qi, qvalid, c.half, bq);
     const float myqq = qvalid ? qq[qi] : 0.0f;
     float best = INFINITY;
-    stream_tiles<QW>(db, dd, row_begin, row_end, tile, sDD, bq, [&](int, const f32x16 &acc) {
+    stream_tiles<QW>(db, dd, c.row_begin, c.row_end, tile, sDD, bq, [&](int, const f32x16 &acc) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            // (qq + dd) - 2*ip in one rounding (2*ip is exact); rows past the end carry NaN and are ignored by fminf
-            const float x = __builtin_fmaf(-2.0f, acc[r], myqq + sDD[rw * 32 + mfma_row(r, half)]);
+            // contract (2): (qq + dd) - 2*ip in one rounding (2*ip is exact); rows past the end carry NaN and are
+            // ignored by fminf
+            const float x = __builtin_fmaf(-2.0f, acc[r], myqq + sDD[c.rw * 32 + mfma_row(r, c.half)]);
             best = fminf(best, x);
         }
     });
     best = best < 0.0f ? 0.0f : best;     // the clamp commutes with the minimum
     if (qvalid && best < INFINITY) {
         // the lanes serving one query differ in (split, row-wave, half): consecutive ids cover all 64 groups
-        const int g = (((split * RW + rw) * 2) + half) & (SR_GROUPS - 1);
+        const int g = (((c.split * RW + c.rw) * 2) + c.half) & (SR_GROUPS - 1);
         atomicMin(&gmin[(size_t)qi * SR_GROUPS + g], __float_as_int(best));
     }
 }
@@ -228,10 +278,8 @@ __global__ __launch_bounds__(256) void search_thr_kernel(const int *__restrict__
     const int lane = threadIdx.x & 63;
     const int qi = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (qi >= nq) return;
-    float d = __int_as_float(gmin[(size_t)qi * SR_GROUPS + lane]);
-    int i = lane;
-    wave_sort64(d, i, lane);
-    if (lane == k - 1) thr[qi] = d;      // +inf when fewer than k groups saw a row: every row is a candidate
+    // +inf when fewer than k groups saw a row: every row is a candidate
+    store_kth_smallest(__int_as_float(gmin[(size_t)qi * SR_GROUPS + lane]), lane, k, thr + qi);
 }
 
 // ---- launch 3: the pass over the database -------------------------------------------------------------------------
@@ -248,38 +296,33 @@ __global__ __launch_bounds__(256, 2) void search_scan_kernel(const float *__rest
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *tile = reinterpret_cast<float *>(smem);
     float *sDD = tile + TROWS * SR_LS;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
-    const int qw = wave % QW, rw = wave / QW;
-    int split, qgroup;
-    search_block(split, qgroup);
-    const int qi = (qgroup * QW + qw) * 32 + l31;
+    const ScanCoords c = scan_coords<QW>(0, rows_per_split, n);
+    const int qi = (c.qgroup * QW + c.qw) * 32 + c.l31;
     const bool qvalid = qi < nq;
-    const int64_t row_begin = (int64_t)split * rows_per_split;
-    const int64_t row_end = (row_begin + rows_per_split < n) ? row_begin + rows_per_split : n;
     float bq[64];
-    load_queries(q, qi, qvalid, half, bq);
+    load_queries(q, qi, qvalid, c.half, bq);
     const float myqq = qvalid ? qq[qi] : 0.0f;
     const float thr_q = qvalid ? thr[qi] : -1.0f;      // -1: nothing passes (distances are clamped at 0)
-    stream_tiles<QW>(db, dd, row_begin, row_end, tile, sDD, bq, [&](int t, const f32x16 &acc) {
-        // dis = max(0, x), x = (qq + dd) - 2*ip in one rounding (2*ip is exact).  thr >= 0, so dis <= thr <=> x <= thr:
-        // the common case is one add, one fma and one compare per element, the lane masks OR-ed in scalar registers.
-        // Rows past the end carry NaN norms and fail the compare.
+    stream_tiles<QW>(db, dd, c.row_begin, c.row_end, tile, sDD, bq, [&](int t, const f32x16 &acc) {
+        // contract (2): dis = max(0, x), x = (qq + dd) - 2*ip in one rounding (2*ip is exact).  thr >= 0, so
+        // dis <= thr <=> x <= thr: the common case is one add, one fma and one compare per element, the lane masks
+        // OR-ed in scalar registers.  Rows past the end carry NaN norms and fail the compare.
         float x[16];
         unsigned long long any = 0;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            x[r] = __builtin_fmaf(-2.0f, acc[r], myqq + sDD[rw * 32 + mfma_row(r, half)]);
+            x[r] = __builtin_fmaf(-2.0f, acc[r], myqq + sDD[c.rw * 32 + mfma_row(r, c.half)]);
             any |= __ballot(x[r] <= thr_q);
         }
         if (any != 0) {
-            const int64_t slab0 = row_begin + (int64_t)t * TROWS + rw * 32;
+            const int64_t slab0 = c.row_begin + (int64_t)t * TROWS + c.rw * 32;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 if (x[r] <= thr_q) {
                     const int pos = atomicAdd(&cnt[qi], 1);
                     if (pos < SR_CAP) {                 // beyond: cnt > SR_CAP tells the select kernel to rescan
                         cand_d[(size_t)qi * SR_CAP + pos] = x[r] < 0.0f ? 0.0f : x[r];
-                        cand_i[(size_t)qi * SR_CAP + pos] = (int)(slab0 + mfma_row(r, half));
+                        cand_i[(size_t)qi * SR_CAP + pos] = (int)(slab0 + mfma_row(r, c.half));
                     }
                 }
             }
@@ -315,62 +358,23 @@ __global__ __launch_bounds__(256) void search_select_kernel(const float *__restr
             top.push(valid, d, i, k, lane);
         }
     } else {
-        // the list overflowed: exact rescan of the whole database for this query, one row per thread, same
-        // c-ordered fmaf chain and distance expression as the MFMA path
+        // the list overflowed: exact rescan of the whole database for this query, one row per thread
         if (tid < SR_D) sq[tid] = q[(size_t)qi * SR_D + tid];
         __syncthreads();
         const float myqq = qq[qi];
-        const float4 *db4 = reinterpret_cast<const float4 *>(db);
         for (int64_t r0 = 0; r0 < n; r0 += 256) {
             const int64_t row = r0 + tid;
             const bool valid = row < n;
-            float d = INFINITY;
-            if (valid) {
-                float ip = 0.0f;
-                for (int c4 = 0; c4 < SR_D / 4; ++c4) {
-                    const float4 x = db4[row * 32 + c4];
-                    ip = __builtin_fmaf(x.x, sq[4 * c4 + 0], ip);
-                    ip = __builtin_fmaf(x.y, sq[4 * c4 + 1], ip);
-                    ip = __builtin_fmaf(x.z, sq[4 * c4 + 2], ip);
-                    ip = __builtin_fmaf(x.w, sq[4 * c4 + 3], ip);
-                }
-                d = (myqq + dd[row]) - 2.0f * ip;
-                d = d < 0.0f ? 0.0f : d;
-            }
-            top.push(valid, d, (int)row, k, lane);
+            top.push(valid, valid ? exact_l2(db, dd, row, sq, myqq) : INFINITY, (int)row, k, lane);
         }
     }
     if (top.pc > 0) top.fold(k, lane);
-    // merge the four wave lists as a tree: (0,1) and (2,3) in parallel, then the two winners
-    if ((wave & 1) && lane < 32) {
-        wtop_d[wave][lane] = top.td;
-        wtop_i[wave][lane] = top.ti;
-    }
-    __syncthreads();
-    float td = top.td;
-    int ti = top.ti;
-    if (!(wave & 1)) {
-        if (lane >= 32) {
-            td = wtop_d[wave + 1][lane - 32];
-            ti = wtop_i[wave + 1][lane - 32];
-        }
-        wave_sort64(td, ti, lane);
-        if (wave == 2 && lane < 32) {
-            wtop_d[2][lane] = td;
-            wtop_i[2][lane] = ti;
-        }
-    }
-    __syncthreads();
-    if (wave == 0) {
-        if (lane >= 32) {
-            td = wtop_d[2][lane - 32];
-            ti = wtop_i[2][lane - 32];
-        }
-        wave_sort64(td, ti, lane);
-        if (lane < k) {
-            out_d[(size_t)qi * k + lane] = td;
-            out_i[(size_t)qi * k + lane] = ti == SR_EMPTY ? (int64_t)-1 : id_base + (int64_t)ti;
-        }
+    float td;
+    int ti;
+    block_merge_tops(top, wtop_d, wtop_i, wave, lane, td, ti);
+    if (wave == 0 && lane < k) {
+        out_d[(size_t)qi * k + lane] = td;
+        out_i[(size_t)qi * k + lane] = ti == SR_EMPTY ? (int64_t)-1 : id_base + (int64_t)ti;
     }
 }
 
@@ -436,11 +440,8 @@ __global__ __launch_bounds__(256) void search_thr_pre_kernel(const float *__rest
     }
     if (lane == 0) qq[qi] = s;
     if (lane < SR_NSUB) cnt[qi * SR_NSUB + lane] = 0;
-    float d = m > -INFINITY ? __builtin_fmaf(-2.0f, m, s * (1.0f + SB_SLACK)) : INFINITY;
-    d = d < 0.0f ? 0.0f : d;
-    int i = lane;
-    wave_sort64(d, i, lane);
-    if (lane == k - 1) thr[qi] = d;      // +inf when fewer than k groups saw a row: every row is a candidate
+    const float d = m > -INFINITY ? __builtin_fmaf(-2.0f, m, s * (1.0f + SB_SLACK)) : INFINITY;
+    store_kth_smallest(d < 0.0f ? 0.0f : d, lane, k, thr + qi);     // +inf: as in search_thr_kernel
 }
 
 constexpr int SB_WGS_NQS2 = 2;      // workgroups per CU of the two-query-set form (three: 168 registers, 16-21 dwords spilled, same time)
@@ -652,28 +653,23 @@ __global__ __launch_bounds__(256, NQS >= 2 ? SB_WGS_NQS2 : 3) void search_bound_
     constexpr int RW = 4 / QW;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     unsigned char *ring = reinterpret_cast<unsigned char *>(smem);
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
-    const int qw = wave % QW, rw = wave / QW;
-    int split, qgroup;
-    search_block(split, qgroup);
-    const int64_t row_begin = (int64_t)split * rows_per_split;
-    const int64_t row_end = (row_begin + rows_per_split < n_sample) ? row_begin + rows_per_split : n_sample;
+    const ScanCoords c = scan_coords<QW>(0, rows_per_split, n_sample);
     const float kplus = 1.0f + SB_SLACK;
     bf16x8 bq[NQS][8];
     int qi[NQS];
     float bestm[NQS];
 #pragma unroll
     for (int j = 0; j < NQS; ++j) {
-        qi[j] = ((qgroup * QW + qw) * NQS + j) * 32 + l31;
+        qi[j] = ((c.qgroup * QW + c.qw) * NQS + j) * 32 + c.l31;
         bestm[j] = INFINITY;
     }
     // d~ + SLACK (qq + dd) = qq kplus - 2 (<q^,x^> - dd kplus / 2), and the bracket is -(kplus / 2) acc for the stream's
     // acc = dd - (2 / kplus) <q^,x^> (query operand scaled by -2 / kplus): the lane keeps the MINIMUM of acc, three at a
     // time, no arithmetic per element; rows past the end carry NaN and are ignored by fminf
     const float nhk = -0.5f * kplus;
-    stream_tiles_bf16<QW, NQS, ABL>(dbh, dd, row_begin, row_end, ring, bq, [&]() {
+    stream_tiles_bf16<QW, NQS, ABL>(dbh, dd, c.row_begin, c.row_end, ring, bq, [&]() {
 #pragma unroll
-        for (int j = 0; j < NQS; ++j) load_queries_bf16(q, qi[j], qi[j] < nq, half, bq[j], -2.0f / kplus);
+        for (int j = 0; j < NQS; ++j) load_queries_bf16(q, qi[j], qi[j] < nq, c.half, bq[j], -2.0f / kplus);
     }, [&](int, int, int j, const f32x16 &acc, const float *) {
 #pragma unroll
         for (int r = 0; r < 16; r += 2) bestm[j] = fminf(fminf(bestm[j], acc[r]), acc[r + 1]);
@@ -684,7 +680,7 @@ __global__ __launch_bounds__(256, NQS >= 2 ? SB_WGS_NQS2 : 3) void search_bound_
 #pragma unroll
     for (int j = 0; j < NQS; ++j)
         if (qi[j] < nq)
-            gmax[(size_t)qi[j] * ngroups + ((split * RW + rw) * 2 + half)] = bestm[j] < INFINITY ? nhk * bestm[j] : -INFINITY;
+            gmax[(size_t)qi[j] * ngroups + ((c.split * RW + c.rw) * 2 + c.half)] = bestm[j] < INFINITY ? nhk * bestm[j] : -INFINITY;
 }
 
 // Hits are rare (a few hundred per query over the whole database) but a returning global atomic costs microseconds,
@@ -709,26 +705,21 @@ __global__ __launch_bounds__(256, NQS >= 2 ? SB_WGS_NQS2 : 3) void search_scan_b
     //  41 queries took 0.086 instead of 0.076 ms, 128 queries 0.103 instead of 0.085)
     typedef typename std::conditional<(QW * NQS * 32 > 256), unsigned short, unsigned char>::type hb_q_t;
     __shared__ hb_q_t hb_q[4][HB_CAP];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
-    const int qw = wave % QW;
-    int split, qgroup;
-    search_block(split, qgroup);
-    const int qbase = qgroup * QW * NQS * 32;        // the workgroup's queries: qbase + [0, 32 QW NQS)
-    const int64_t row_begin = row0 + (int64_t)split * rows_per_split;      // the launch covers rows [row0, n)
-    const int64_t row_end = (row_begin + rows_per_split < n) ? row_begin + rows_per_split : n;
+    const ScanCoords c = scan_coords<QW>(row0, rows_per_split, n);          // the launch covers rows [row0, n)
+    const int qbase = c.qgroup * QW * NQS * 32;      // the workgroup's queries: qbase + [0, 32 QW NQS)
     // keep iff d~ - SLACK (qq + dd) <= bound  <=>  <q^,x^> >= A_q + H_row
     const float kminus = 1.0f - SB_SLACK;
     bf16x8 bq[NQS][8];
     float a_q[NQS];
-    const int sub = split & (SR_NSUB - 1);
-    int *my_row = hb_row[wave];
-    float *my_e = hb_e[wave];
-    float *my_d = hb_d[wave];
-    hb_q_t *my_q = hb_q[wave];
+    const int sub = c.split & (SR_NSUB - 1);
+    int *my_row = hb_row[c.wave];
+    float *my_e = hb_e[c.wave];
+    float *my_d = hb_d[c.wave];
+    hb_q_t *my_q = hb_q[c.wave];
     int fill = 0;                                             // wave-uniform
     auto drain = [&]() {                                      // this wave's queue -> sub-list `sub` of the queries' lists
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        for (int e = lane; e < fill; e += 64) {
+        for (int e = c.lane; e < fill; e += 64) {
             const int qg = qbase + my_q[e];
             const int pos = atomicAdd(&cnt[qg * SR_NSUB + sub], 1);
             if (pos < SR_SUBCAP) {                            // beyond: the select kernel sees the count and rescans
@@ -761,11 +752,11 @@ __global__ __launch_bounds__(256, NQS >= 2 ? SB_WGS_NQS2 : 3) void search_scan_b
     // accumulators three at a time (NaN past the end of the slice drops out of fminf), ONE compare and one branch per
     // block -- no arithmetic per element, no per-element lane masks (whose 16 dependent scalar ORs behind 16 VALU
     // compares cost as much as the MFMA chain itself).
-    stream_tiles_bf16<QW, NQS>(dbh, dd, row_begin, row_end, ring, bq, [&]() {
+    stream_tiles_bf16<QW, NQS>(dbh, dd, c.row_begin, c.row_end, ring, bq, [&]() {
 #pragma unroll
         for (int j = 0; j < NQS; ++j) {
-            const int qi = qbase + (qw * NQS + j) * 32 + l31;
-            load_queries_bf16(q, qi, qi < nq, half, bq[j], -2.0f / kminus);
+            const int qi = qbase + (c.qw * NQS + j) * 32 + c.l31;
+            load_queries_bf16(q, qi, qi < nq, c.half, bq[j], -2.0f / kminus);
             a_q[j] = qi < nq ? thr[qi] / kminus - qq[qi] : -INFINITY;
         }
     }, [&](int t, int rb, int j, const f32x16 &e, const float *nb) {
@@ -780,8 +771,8 @@ __global__ __launch_bounds__(256, NQS >= 2 ? SB_WGS_NQS2 : 3) void search_scan_b
             unsigned bits = 0;
 #pragma unroll
             for (int r = 0; r < 16; ++r) bits |= e[r] <= a_q[j] ? 1u << r : 0u;       // (NaN compares false)
-            const int slab0 = (int)(row_begin + (int64_t)t * SB_TR + rb * 32) + 4 * half;
-            const int ql = (qw * NQS + j) * 32 + l31;                 // < 32 QW NQS <= 384
+            const int slab0 = (int)(c.row_begin + (int64_t)t * SB_TR + rb * 32) + 4 * c.half;
+            const int ql = (c.qw * NQS + j) * 32 + c.l31;                 // < 32 QW NQS <= 384
             const bool single = (bits & (bits - 1)) == 0;
             const int r0 = bits ? __builtin_ctz(bits) : 0;            // row mfma_row(r, half) of the block
             const int off0 = (r0 & 3) + 8 * (r0 >> 2);
@@ -800,14 +791,15 @@ __global__ __launch_bounds__(256, NQS >= 2 ? SB_WGS_NQS2 : 3) void search_scan_b
 }
 
 // Per query: the k best of its candidates by (exact distance, id).
-// The scan left (row, E) pairs, E = <q^,x^> - dd[row] (1 - SLACK) / 2 -- the very value its test compared.  With
-// t = qq + dd[row] the true distance lies in [lo, hi],
-//   lo = t (1 - SLACK) - 2 <q^,x^> = qq (1 - SLACK) - 2 E             (no dd[row]: phase B needs no gather for it),
-//   hi = t (1 + SLACK) - 2 <q^,x^> = qq (1 + SLACK) - 2 E + 2 SLACK dd[row]
+// The scan left (row, E, dd[row]) records, E = <q^,x^> - dd[row] (1 - SLACK) / 2 -- the very value its test compared.
+// With t = qq + dd[row] the true distance lies in [lo, hi] (contract (5)),
+//   lo = t (1 - SLACK) - 2 <q^,x^> = qq (1 - SLACK) - 2 E             (no dd[row] at all),
+//   hi = t (1 + SLACK) - 2 <q^,x^> = qq (1 + SLACK) - 2 E + 2 SLACK dd[row]          (from the record: no gather)
 // (the roundings of these forms are a few 2^-24 (qq + dd), against the 1.7e-4 (qq + dd) SB_SLACK keeps in reserve),
 // so phase A takes the k-th smallest hi (at least k rows are truly that close: a bound ~10x tighter than the scan's)
 // and phase B evaluates the exact f32 distance -- the oracle's fmaf chain over the 512-byte row -- only for the rows
 // whose lo does not exceed it: a few dozen random row reads per query instead of several hundred.
+// Each phase has two methods, picked from the size it sees (c <= SF_CAP, nneed <= SF_NEED): see the two comments below.
 // TIGHTEN: only phase A, over the candidates the first part of a two-part scan left: thr[qi] = min(thr[qi], the k-th
 // smallest upper bound) -- the bound the second part then scans with (at least k rows of the first part are that close).
 template <bool TIGHTEN>
@@ -858,42 +850,40 @@ __global__ __launch_bounds__(256, 4) void search_select_exact_kernel(const float
     };
     float thr2 = thr[qi];
     const float kminus = 1.0f - SB_SLACK, kplus = 1.0f + SB_SLACK;
-    const float qhi = myqq * kplus, dspan = kplus - kminus;     // (the difference of two floats this close is exact)
+    const float qhi = myqq * kplus, qlo = myqq * kminus, dspan = kplus - kminus;     // (kplus - kminus is exact)
+    // ---- the pieces both selection methods are built from (one copy each) ----
+    auto cand = [&](int e, int &row, float &ev, float &ddv) {    // flat index -> the scan's record (row, E, norm);
+        const size_t sl = (size_t)qi * SR_CAP + slot_of(e < c ? e : c - 1);    // past the end: the last candidate,
+        row = cand_i[sl];                                        // loaded instead of branched around
+        const float2 ed = cand_e[sl];
+        ev = ed.x;
+        ddv = ed.y;                                              // the row's norm rides with the candidate: no gather
+    };
+    auto hi_of = [&](float ev, float ddv) {
+        const float hi = __builtin_fmaf(dspan, ddv, __builtin_fmaf(-2.0f, ev, qhi));
+        return hi < 0.0f ? 0.0f : hi;
+    };
+    auto keep = [&](bool valid, float ev, int row) {             // compaction: the rows with lo <= bound (no dd[row] needed)
+        if (valid && __builtin_fmaf(-2.0f, ev, qlo) <= thr2) need_rows[atomicAdd(&s_nneed, 1)] = row;
+    };
     WaveTop top;
     float td;
     int ti;
-    auto exact = [&](int64_t row) {                        // the oracle's chain over the 512-byte row
-        // the whole row is requested before the dependent fmaf chain starts (every lane reads a different row)
-        f32x4 xr[SR_D / 4];
-        const f32x4 *rp = reinterpret_cast<const f32x4 *>(db) + row * (SR_D / 4);
-#pragma unroll
-        for (int c4 = 0; c4 < SR_D / 4; ++c4) xr[c4] = rp[c4];
-        const float ddr = dd[row];
-        float ip = 0.0f;
-#pragma unroll
-        for (int c4 = 0; c4 < SR_D / 4; ++c4) {
-            ip = __builtin_fmaf(xr[c4][0], sq[4 * c4 + 0], ip);
-            ip = __builtin_fmaf(xr[c4][1], sq[4 * c4 + 1], ip);
-            ip = __builtin_fmaf(xr[c4][2], sq[4 * c4 + 2], ip);
-            ip = __builtin_fmaf(xr[c4][3], sq[4 * c4 + 3], ip);
-        }
-        const float d = (myqq + ddr) - 2.0f * ip;
-        return d < 0.0f ? 0.0f : d;
-    };
-    // ---- the usual case: a few hundred candidates.  No sorting networks at all (a 64-lane bitonic sort is ~1 700 cycles,
-    // and the fold + three-sort merge of the general path below ran twice per query: 16 of the kernel's 29 us at 41
-    // queries, tools' stop-point timing, round 4):
-    //   phase A  the candidates (row, E, hi) stay in registers (up to eight per thread); the bound is read from a 256-bin histogram of hi between its
-    //            minimum and maximum -- the upper edge (plus one bin against the rounding of the bin index) of the bin
-    //            the k-th smallest falls into: >= the k-th smallest hi, so still a valid bound, a bin or two looser;
-    //   phase B  the rows with lo <= bound are compacted, their exact distances computed one per thread, and every
-    //            thread finds the RANK of its row by counting the (distance, id) pairs before it -- ranks < k are the
-    //            answer, written in place.  O(need^2 / 256) compares per thread: 40 at the usual hundred rows.
+    // Phase A, the k-th smallest upper bound (or a bound on it), by one of two methods chosen from the list's size; each
+    // ends with the compaction of the rows phase B has to look at.
+    //   c <= SF_CAP (the usual case: a few hundred candidates): no sorting networks at all (a 64-lane bitonic sort is
+    //   ~1 700 cycles, and the fold + three-sort merge of the other method ran twice per query: 16 of the kernel's 29 us
+    //   at 41 queries, tools' stop-point timing, round 4).  The candidates (row, E, hi) stay in registers (up to eight
+    //   per thread); the bound is read from a 256-bin histogram of hi between its minimum and maximum -- the upper edge
+    //   (plus one bin against the rounding of the bin index) of the bin the k-th smallest falls into: >= the k-th
+    //   smallest hi, so still a valid bound, a bin or two looser.
+    //   Otherwise: WaveTop + merge, the exact k-th smallest hi.
     constexpr int SF_CAP = 2048, SF_NEED = 512, SF_PER = SF_CAP / 256;
     __shared__ int f_row[SF_NEED];
     __shared__ float f_hi[SF_NEED];
     __shared__ int f_hist[256];
     __shared__ float f_red[2][4];
+    if (tid == 0) s_nneed = 0;                             // (both methods pass a barrier before they compact)
     if (listed && c <= SF_CAP) {
         int row[SF_PER];
         float ev[SF_PER], ddv[SF_PER], hi[SF_PER];
@@ -902,20 +892,12 @@ __global__ __launch_bounds__(256, 4) void search_select_exact_kernel(const float
             row[u] = 0;                                    // end of the list (u * 256 >= c: uniform) load nothing
             ev[u] = 0.0f;
             ddv[u] = 0.0f;
-            if (u * 256 < c) {
-                const int e = u * 256 + tid;
-                const size_t sl = (size_t)qi * SR_CAP + slot_of(e < c ? e : c - 1);
-                row[u] = cand_i[sl];
-                const float2 ed = cand_e[sl];
-                ev[u] = ed.x;
-                ddv[u] = ed.y;                             // the row's norm rides with the candidate: no gather here
-            }
+            if (u * 256 < c) cand(u * 256 + tid, row[u], ev[u], ddv[u]);
         }
         float mn = INFINITY, mx = -INFINITY;
 #pragma unroll
         for (int u = 0; u < SF_PER; ++u) {
-            hi[u] = __builtin_fmaf(dspan, ddv[u], __builtin_fmaf(-2.0f, ev[u], qhi));
-            hi[u] = hi[u] < 0.0f ? 0.0f : hi[u];
+            hi[u] = hi_of(ev[u], ddv[u]);
             if (u * 256 + tid < c) {
                 mn = fminf(mn, hi[u]);
                 mx = fmaxf(mx, hi[u]);
@@ -967,129 +949,91 @@ __global__ __launch_bounds__(256, 4) void search_select_exact_kernel(const float
         }
         __syncthreads();
         thr2 = fminf(thr2, s_thr2);
-        if (TIGHTEN) {
-            if (tid == 0) thr[qi] = thr2;
-            return;
+        if (!TIGHTEN) {
+#pragma unroll
+            for (int u = 0; u < SF_PER; ++u) keep(u * 256 + tid < c, ev[u], row[u]);
         }
-        const float qlo = myqq * kminus;
-        if (tid == 0) s_nneed = 0;
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < SF_PER; ++u)
-            if (u * 256 + tid < c && __builtin_fmaf(-2.0f, ev[u], qlo) <= thr2)          // lo: no dd[row] needed
-                need_rows[atomicAdd(&s_nneed, 1)] = row[u];
-        __syncthreads();
-        const int nneed = s_nneed;
-        if (nneed <= SF_NEED) {                            // (uniform) else: the general path below, from the lists
-            float dmine[SF_NEED / 256];
-            int rmine[SF_NEED / 256];
-#pragma unroll
-            for (int v = 0; v < SF_NEED / 256; ++v) {
-                const int i = v * 256 + tid;
-                rmine[v] = i < nneed ? need_rows[i] : 0;
-                dmine[v] = (v * 256 < nneed) ? (i < nneed ? exact(rmine[v]) : INFINITY) : INFINITY;
-                if (i < nneed) {
-                    f_hi[i] = dmine[v];
-                    f_row[i] = rmine[v];
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int v = 0; v < SF_NEED / 256; ++v) {
-                const int i = v * 256 + tid;
-                if (v * 256 < nneed) {                     // uniform
-                    int rank = 0;
-                    for (int j = 0; j < nneed; ++j) rank += lex_lt(f_hi[j], f_row[j], dmine[v], rmine[v]) ? 1 : 0;
-                    if (i < nneed && rank < k) {
-                        out_d[(size_t)qi * k + rank] = dmine[v];
-                        out_i[(size_t)qi * k + rank] = id_base + (int64_t)rmine[v];
-                    }
-                }
-            }
-            if (tid >= nneed && tid < k) {                 // fewer rows than k (k <= 32 < 256)
-                out_d[(size_t)qi * k + tid] = INFINITY;
-                out_i[(size_t)qi * k + tid] = -1;
-            }
-            return;
-        }
-        thr2 = thr[qi];                                    // the general path recomputes its own bound
-        __syncthreads();
-    }
-    if (listed) {                                          // phase A: k-th smallest upper bound
+    } else if (listed) {
         top.init(pend_d[wave], pend_i[wave], INFINITY);
-        // four candidates per thread and round, every load of a kind in flight at once (indices clamped to the last
-        // candidate instead of branching around the loads): a list of 600 costs two dependent round trips, not six
+        // four candidates per thread and round, every load of a kind in flight at once: a list of 3 000 costs three
+        // dependent round trips, not twelve
         for (int e0 = 0; e0 < c; e0 += 4 * 256) {
             int row[4];
             float ev[4], ddv[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int e = e0 + u * 256 + tid;
-                const size_t sl = (size_t)qi * SR_CAP + slot_of(e < c ? e : c - 1);
-                row[u] = cand_i[sl];
-                ev[u] = cand_e[sl].x;
-            }
+            for (int u = 0; u < 4; ++u) cand(e0 + u * 256 + tid, row[u], ev[u], ddv[u]);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) ddv[u] = dd[row[u]];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (e0 + u * 256 < c) {                    // uniform: push is a wave-level call
-                    float hi = __builtin_fmaf(dspan, ddv[u], __builtin_fmaf(-2.0f, ev[u], qhi));
-                    hi = hi < 0.0f ? 0.0f : hi;
-                    top.push(e0 + u * 256 + tid < c, hi, row[u], k, lane);
-                }
-            }
+            for (int u = 0; u < 4; ++u)
+                if (e0 + u * 256 < c)                      // uniform: push is a wave-level call
+                    top.push(e0 + u * 256 + tid < c, hi_of(ev[u], ddv[u]), row[u], k, lane);
         }
         if (top.pc > 0) top.fold(k, lane);
         block_merge_tops(top, wtop_d, wtop_i, wave, lane, td, ti);
         if (wave == 0 && lane == k - 1) s_thr2 = td;      // +inf when fewer than k candidates exist
         __syncthreads();
         thr2 = fminf(thr2, s_thr2);
+        if (!TIGHTEN) {
+            for (int e0 = 0; e0 < c; e0 += 4 * 256) {
+                int row[4];
+                float ev[4], ddv[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) cand(e0 + u * 256 + tid, row[u], ev[u], ddv[u]);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) keep(e0 + u * 256 + tid < c, ev[u], row[u]);
+            }
+        }
     }
     if (TIGHTEN) {
         if (tid == 0 && listed) thr[qi] = thr2;
         return;
     }
-    __syncthreads();                                       // sq visible; the merge buffers are free again
-    // phase B: exact distances of the rows that can still be among the k best
-    top.init(pend_d[wave], pend_i[wave], thr2);
-    if (listed) {
-        // the rows still in question (lo <= the bound of phase A: a few dozen of the several hundred) are compacted
-        // into an LDS list first, then fetched one per thread side by side -- picked out of the candidate rounds where
-        // they stand, every round paid a full row-fetch latency for its two or three scattered lanes
-        const float qlo = myqq * kminus;
-        if (tid == 0) s_nneed = 0;
-        __syncthreads();
-        for (int e0 = 0; e0 < c; e0 += 4 * 256) {
-            int row[4];
-            float ev[4];
+    __syncthreads();                                       // need_rows and its count stand; the merge buffers are free again
+    const int nneed = listed ? s_nneed : 0;
+    // Phase B, the exact distances (contract (1)-(2)) of the rows still in question -- compacted first and fetched one
+    // per thread side by side: picked out of the candidate rounds where they stand, every round paid a full row-fetch
+    // latency for its two or three scattered lanes -- and the k best of them, again by one of two methods.
+    //   nneed <= SF_NEED (the usual hundred rows): every thread finds the RANK of its row by counting the (distance, id)
+    //   pairs before it -- ranks < k are the answer, written in place.  O(need^2 / 256) compares per thread: 40 at the
+    //   usual hundred rows.
+    //   Otherwise, and for a query whose lists overflowed (every row of the database): WaveTop + merge.
+    if (listed && nneed <= SF_NEED) {                      // (uniform)
+        float dmine[SF_NEED / 256];
+        int rmine[SF_NEED / 256];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int e = e0 + u * 256 + tid;
-                const size_t sl = (size_t)qi * SR_CAP + slot_of(e < c ? e : c - 1);
-                row[u] = cand_i[sl];
-                ev[u] = cand_e[sl].x;
+        for (int v = 0; v < SF_NEED / 256; ++v) {
+            const int i = v * 256 + tid;
+            rmine[v] = i < nneed ? need_rows[i] : 0;
+            dmine[v] = (v * 256 < nneed) ? (i < nneed ? exact_l2(db, dd, rmine[v], sq, myqq) : INFINITY) : INFINITY;
+            if (i < nneed) {
+                f_hi[i] = dmine[v];
+                f_row[i] = rmine[v];
             }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (e0 + u * 256 + tid < c && __builtin_fmaf(-2.0f, ev[u], qlo) <= thr2)    // lo: no dd[row] needed
-                    need_rows[atomicAdd(&s_nneed, 1)] = row[u];
         }
         __syncthreads();
-        const int nneed = s_nneed;
-        for (int i0 = 0; i0 < nneed; i0 += 256) {
-            const bool need = i0 + tid < nneed;
-            const int row = need ? need_rows[i0 + tid] : 0;
-            const float d = need ? exact(row) : INFINITY;
-            top.push(need, d, row, k, lane);
+#pragma unroll
+        for (int v = 0; v < SF_NEED / 256; ++v) {
+            const int i = v * 256 + tid;
+            if (v * 256 < nneed) {                         // uniform
+                int rank = 0;
+                for (int j = 0; j < nneed; ++j) rank += lex_lt(f_hi[j], f_row[j], dmine[v], rmine[v]) ? 1 : 0;
+                if (i < nneed && rank < k) {
+                    out_d[(size_t)qi * k + rank] = dmine[v];
+                    out_i[(size_t)qi * k + rank] = id_base + (int64_t)rmine[v];
+                }
+            }
         }
-    } else {
-        for (int64_t e0 = 0; e0 < n; e0 += 256) {
-            const int64_t row = e0 + tid;
-            const bool need = row < n;
-            const float d = need ? exact(row) : INFINITY;
-            top.push(need, d, (int)row, k, lane);
+        if (tid >= nneed && tid < k) {                     // fewer rows than k (k <= 32 < 256): contract (4)
+            out_d[(size_t)qi * k + tid] = INFINITY;
+            out_i[(size_t)qi * k + tid] = -1;
         }
+        return;
+    }
+    top.init(pend_d[wave], pend_i[wave], thr2);
+    const int64_t nrows = listed ? nneed : n;
+    for (int64_t i0 = 0; i0 < nrows; i0 += 256) {
+        const bool need = i0 + tid < nrows;
+        const int64_t row = listed ? (need ? need_rows[i0 + tid] : 0) : i0 + tid;
+        top.push(need, need ? exact_l2(db, dd, row, sq, myqq) : INFINITY, (int)row, k, lane);
     }
     if (top.pc > 0) top.fold(k, lane);
     block_merge_tops(top, wtop_d, wtop_i, wave, lane, td, ti);
@@ -1204,28 +1148,65 @@ static void split_rows(int64_t rows, int trows, int64_t want, int *splits, int64
     *splits = (int)((tiles + tps - 1) / tps);
 }
 
+static int query_groups(int nq, int qw, int nqs) { return (nq + 32 * qw * nqs - 1) / (32 * qw * nqs); }
+
+// The pre-pass sample of both paths: the first max(64k, n/16) rows, in `bwant` slices but never fewer than 32 (split,
+// row-wave) pairs per query, so that all 64 groups (pair x half) the threshold kernels select from see rows.
+static void sample_plan(int64_t n, int rw, int trows, int64_t bwant, int64_t *b_rows, int *b_splits, int64_t *b_rps) {
+    *b_rows = n / 16 > 65536 ? n / 16 : 65536;
+    if (*b_rows > n) *b_rows = n;
+    const int64_t bneed = (32 + rw - 1) / rw;
+    split_rows(*b_rows, trows, bwant < bneed ? bneed : bwant, b_splits, b_rps);
+}
+
 static SearchPlan make_plan(int64_t n, int nq) {
     SearchPlan p;
     p.qw = nq <= 32 ? 1 : (nq <= 64 ? 2 : 4);
     p.rw = 4 / p.qw;
     p.trows = 32 * p.rw;
-    p.qgroups = (nq + 32 * p.qw - 1) / (32 * p.qw);
+    p.qgroups = query_groups(nq, p.qw, 1);
     // two workgroups per CU (256 CUs), three for the 4x1 shape (registers and LDS allow it), when the query
     // groups allow it
-    int64_t want = (p.qw == 4 ? 768 : 512) / p.qgroups;
-    split_rows(n, p.trows, want < 1 ? 1 : want, &p.splits, &p.rows_per_split);
-    // pre-pass: the first max(64k, n/16) rows; >= 32 (split, row-wave) pairs per query so that all 64 groups
-    // (pair x half) see rows, and enough workgroups to fill the chip for a handful of tiles each
-    p.b_rows = n / 16 > 65536 ? n / 16 : 65536;
-    if (p.b_rows > n) p.b_rows = n;
-    int64_t bwant = 1024 / p.qgroups;
-    const int64_t need = (32 + p.rw - 1) / p.rw;
-    if (bwant < need) bwant = need;
-    split_rows(p.b_rows, p.trows, bwant, &p.b_splits, &p.b_rows_per_split);
+    split_rows(n, p.trows, (p.qw == 4 ? 768 : 512) / p.qgroups, &p.splits, &p.rows_per_split);
+    // pre-pass: enough workgroups to fill the chip for a handful of tiles each
+    sample_plan(n, p.rw, p.trows, 1024 / p.qgroups, &p.b_rows, &p.b_splits, &p.b_rows_per_split);
     return p;
 }
 
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+// the workspace of grafp_knn_search_l2_f32: qq (nq) | thr (nq) | cnt (nq) | gmin (nq, 64) | cand_d, cand_i (nq, SR_CAP)
+struct SearchWs {
+    float *qq, *thr;
+    int *cnt, *gmin;
+    float *cand_d;
+    int *cand_i;
+};
+static size_t search_layout(void *ws, int nq, SearchWs &a) {
+    WsCarve w{(char *)ws, 0};
+    a.qq = w.take<float>((size_t)nq * sizeof(float));
+    a.thr = w.take<float>((size_t)nq * sizeof(float));
+    a.cnt = w.take<int>((size_t)nq * sizeof(int));
+    a.gmin = w.take<int>((size_t)nq * SR_GROUPS * sizeof(int));
+    a.cand_d = w.take<float>((size_t)nq * SR_CAP * sizeof(float));
+    a.cand_i = w.take<int>((size_t)nq * SR_CAP * sizeof(int));
+    return w.off;
+}
+
+// the argument check of the two search entries (db_bf16: null for the all-f32 one); `who` names the entry in the message
+static int search_check(const char *who, bool nonnull, const void *db, const void *db_bf16, const void *q, int64_t n,
+                        int nq, int d, int k) {
+    GRAFP_REQUIRE(nonnull, "%s: null pointer", who);
+    GRAFP_REQUIRE(d == SR_D, "%s: d=%d unsupported (fingerprints are 128-d)", who, d);
+    GRAFP_REQUIRE(n >= 1 && n < 0x7fffffffll && nq >= 1, "%s: bad n=%lld nq=%d", who, (long long)n, nq);
+    GRAFP_REQUIRE(k >= 1 && k <= GRAFP_SEARCH_MAX_K, "%s: k=%d not in [1, %d]", who, k, GRAFP_SEARCH_MAX_K);
+    GRAFP_REQUIRE((((uintptr_t)db | (uintptr_t)db_bf16) & 15) == 0 && ((uintptr_t)q & 3) == 0,
+                  "%s: %s must be 16-byte aligned", who, db_bf16 ? "db / db_bf16" : "db");
+    return GRAFP_OK;
+}
+static int search_ws_check(const char *who, const void *ws, size_t ws_bytes, size_t need) {
+    if (ws && ws_bytes >= need) return GRAFP_OK;
+    set_error("%s: workspace %zu bytes < required %zu", who, ws_bytes, need);
+    return GRAFP_ERR_WORKSPACE;
+}
 
 }  // namespace grafp
 
@@ -1245,57 +1226,44 @@ extern "C" int grafp_row_sqnorm_f32(const float *m, int64_t n, int d, float *out
 
 extern "C" size_t grafp_knn_search_workspace(int64_t n, int nq, int d, int k) {
     using namespace grafp;
-    if (n <= 0 || nq <= 0 || d != SR_D || k < 1) return 0;
-    return align256((size_t)nq * sizeof(float)) * 2 + align256((size_t)nq * SR_NSUB * sizeof(int)) +
-           align256((size_t)nq * SR_GROUPS * sizeof(int)) + align256((size_t)nq * SR_CAP * sizeof(float)) +
-           align256((size_t)nq * SR_CAP * sizeof(int));
+    SearchWs a;
+    return (n <= 0 || nq <= 0 || d != SR_D || k < 1) ? 0 : search_layout(nullptr, nq, a);
 }
 
 extern "C" int grafp_knn_search_l2_f32(const float *db, const float *db_sqnorm, int64_t n, const float *q, int nq,
                                        int d, int k, int64_t id_base, float *out_dist, int64_t *out_ids, void *ws,
                                        size_t ws_bytes, grafp_stream_t stream) {
     using namespace grafp;
-    GRAFP_REQUIRE(db && db_sqnorm && q && out_dist && out_ids, "knn_search: null pointer");
-    GRAFP_REQUIRE(d == SR_D, "knn_search: d=%d unsupported (fingerprints are 128-d)", d);
-    GRAFP_REQUIRE(n >= 1 && n < 0x7fffffffll && nq >= 1, "knn_search: bad n=%lld nq=%d", (long long)n, nq);
-    GRAFP_REQUIRE(k >= 1 && k <= GRAFP_SEARCH_MAX_K, "knn_search: k=%d not in [1, %d]", k, GRAFP_SEARCH_MAX_K);
-    GRAFP_REQUIRE(((uintptr_t)db & 15) == 0 && ((uintptr_t)q & 3) == 0, "knn_search: db must be 16-byte aligned");
-    const size_t need = grafp_knn_search_workspace(n, nq, d, k);
-    if (!ws || ws_bytes < need) {
-        set_error("knn_search: workspace %zu bytes < required %zu", ws_bytes, need);
-        return GRAFP_ERR_WORKSPACE;
-    }
+    SearchWs a;
+    int rc = search_check("knn_search", db && db_sqnorm && q && out_dist && out_ids, db, nullptr, q, n, nq, d, k);
+    if (rc == GRAFP_OK) rc = search_ws_check("knn_search", ws, ws_bytes, search_layout(nullptr, nq, a));
+    if (rc != GRAFP_OK) return rc;
+    search_layout(ws, nq, a);
     hipStream_t s = (hipStream_t)stream;
     const SearchPlan p = make_plan(n, nq);
-    char *w = (char *)ws;
-    float *qq = (float *)w;                 w += align256((size_t)nq * sizeof(float));
-    float *thr = (float *)w;                w += align256((size_t)nq * sizeof(float));
-    int *cnt = (int *)w;                    w += align256((size_t)nq * SR_NSUB * sizeof(int));
-    int *gmin = (int *)w;                   w += align256((size_t)nq * SR_GROUPS * sizeof(int));
-    float *cand_d = (float *)w;             w += align256((size_t)nq * SR_CAP * sizeof(float));
-    int *cand_i = (int *)w;
     const int64_t ng = (int64_t)nq * SR_GROUPS;
-    hipLaunchKernelGGL(search_init_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, s, q, nq, qq, gmin, cnt);
+    hipLaunchKernelGGL(search_init_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, s, q, nq, a.qq, a.gmin,
+                       a.cnt);
     const size_t lds = ((size_t)p.trows * SR_LS + p.trows) * sizeof(float);
     const dim3 grid_b(p.b_splits, p.qgroups), grid(p.splits, p.qgroups);
 #define SR_LAUNCH(QW)                                                                                               \
     (void)hipFuncSetAttribute((const void *)search_bound_kernel<QW>, hipFuncAttributeMaxDynamicSharedMemorySize,    \
                               (int)lds);                                                                            \
-    hipLaunchKernelGGL(search_bound_kernel<QW>, grid_b, dim3(256), lds, s, db, db_sqnorm, p.b_rows, q, qq, nq,      \
-                       p.b_rows_per_split, gmin);                                                                   \
-    hipLaunchKernelGGL(search_thr_kernel, dim3((nq + 3) / 4), dim3(256), 0, s, (const int *)gmin, nq, k, thr);      \
+    hipLaunchKernelGGL(search_bound_kernel<QW>, grid_b, dim3(256), lds, s, db, db_sqnorm, p.b_rows, q, a.qq, nq,    \
+                       p.b_rows_per_split, a.gmin);                                                                 \
+    hipLaunchKernelGGL(search_thr_kernel, dim3((nq + 3) / 4), dim3(256), 0, s, (const int *)a.gmin, nq, k, a.thr);  \
     (void)hipFuncSetAttribute((const void *)search_scan_kernel<QW>, hipFuncAttributeMaxDynamicSharedMemorySize,     \
                               (int)lds);                                                                            \
-    hipLaunchKernelGGL(search_scan_kernel<QW>, grid, dim3(256), lds, s, db, db_sqnorm, n, q, qq, nq,                \
-                       p.rows_per_split, (const float *)thr, cnt, cand_d, cand_i)
+    hipLaunchKernelGGL(search_scan_kernel<QW>, grid, dim3(256), lds, s, db, db_sqnorm, n, q, a.qq, nq,              \
+                       p.rows_per_split, (const float *)a.thr, a.cnt, a.cand_d, a.cand_i)
     if (p.qw == 1) { SR_LAUNCH(1); }
     else if (p.qw == 2) { SR_LAUNCH(2); }
     else { SR_LAUNCH(4); }
 #undef SR_LAUNCH
     GRAFP_CHECK_LAUNCH("search_bound_kernel / search_scan_kernel");
-    hipLaunchKernelGGL(search_select_kernel, dim3(nq), dim3(256), 0, s, db, db_sqnorm, n, q, (const float *)qq, nq, k,
-                       id_base, (const float *)thr, (const int *)cnt, (const float *)cand_d, (const int *)cand_i,
-                       out_dist, out_ids);
+    hipLaunchKernelGGL(search_select_kernel, dim3(nq), dim3(256), 0, s, db, db_sqnorm, n, q, (const float *)a.qq, nq, k,
+                       id_base, (const float *)a.thr, (const int *)a.cnt, (const float *)a.cand_d,
+                       (const int *)a.cand_i, out_dist, out_ids);
     GRAFP_CHECK_LAUNCH("search_select_kernel");
     return GRAFP_OK;
 }
@@ -1312,10 +1280,14 @@ extern "C" int grafp_f32_to_bf16(const float *src, int64_t n_elems, void *dst, g
 }
 
 namespace grafp {
-// launch plan of the bf16 pre-filter path (shared by the workspace size and the entry)
+// launch plan of the bf16 pre-filter path: everything the entry launches with (and the workspace size depends on)
 struct PrePlan {
-    int qw, rw, nqs, qgroups, b_splits, ngroups;
+    int qw, rw, nqs, qgroups;
+    int b_splits, ngroups;        // pre-pass over the first b_rows rows: grid (b_splits, qgroups), ngroups group maxima
     int64_t b_rows, b_rps;
+    int64_t n_first;              // two-part scan: rows [0, n_first) with the pre-pass bound, grid (a_splits, qgroups) ...
+    int a_splits, splits;         // ... rows [n_first, n) with the tightened one, grid (splits, qgroups); else n_first = 0
+    int64_t a_rps, rps;
 };
 static PrePlan pre_plan(int64_t n, int nq) {
     PrePlan p;
@@ -1338,53 +1310,14 @@ static PrePlan pre_plan(int64_t n, int nq) {
     }
     p.nqs = p.qw == 4 ? GRAFP_TUNE_INT("GRAFP_SEARCH_NQS", nqs_auto) : 1;
     if (p.nqs < 1 || p.nqs > 3) p.nqs = 1;
-    p.qgroups = (nq + 32 * p.qw * p.nqs - 1) / (32 * p.qw * p.nqs);
-    p.b_rows = n / 16 > 65536 ? n / 16 : 65536;
-    if (p.b_rows > n) p.b_rows = n;
+    p.qgroups = query_groups(nq, p.qw, p.nqs);
     // pre-pass workgroups: ONE per CU, four or more ring stages each (round 4; 1024 one-tile workgroups paid their prologue
     // -- the query operand, the ring fill -- for a single tile: 41 queries 0.092 -> 0.079 ms, 1 query 0.080 -> 0.070, no
     // batch size slower); never fewer than the 64 (split, row-wave, half) groups the threshold kernel selects from
-    int64_t bwant = GRAFP_TUNE_INT("GRAFP_SEARCH_BWANT", 256) / p.qgroups;
-    const int64_t bneed = (32 + p.rw - 1) / p.rw;
-    if (bwant < bneed) bwant = bneed;
-    split_rows(p.b_rows, SB_TR, bwant, &p.b_splits, &p.b_rps);
+    sample_plan(n, p.rw, SB_TR, GRAFP_TUNE_INT("GRAFP_SEARCH_BWANT", 256) / p.qgroups, &p.b_rows, &p.b_splits, &p.b_rps);
     p.ngroups = p.b_splits * p.rw * 2;
-    return p;
-}
-}  // namespace grafp
-
-extern "C" size_t grafp_knn_search_pre_workspace(int64_t n, int nq, int d, int k) {
-    using namespace grafp;
-    if (n <= 0 || nq <= 0 || d != SR_D || k < 1) return 0;
-    const PrePlan p = pre_plan(n, nq);
-    return align256((size_t)nq * sizeof(float)) * 2 + align256((size_t)nq * SR_NSUB * sizeof(int)) +
-           align256((size_t)nq * p.ngroups * sizeof(float)) + align256((size_t)nq * SR_CAP * sizeof(int)) +
-           align256((size_t)nq * SR_CAP * sizeof(float2));
-}
-
-extern "C" int grafp_knn_search_l2_pre(const float *db, const void *db_bf16, const float *db_sqnorm, int64_t n,
-                                       const float *q, int nq, int d, int k, int64_t id_base, float *out_dist,
-                                       int64_t *out_ids, void *ws, size_t ws_bytes, grafp_stream_t stream) {
-    using namespace grafp;
-    GRAFP_REQUIRE(db && db_bf16 && db_sqnorm && q && out_dist && out_ids, "knn_search_pre: null pointer");
-    GRAFP_REQUIRE(d == SR_D, "knn_search_pre: d=%d unsupported (fingerprints are 128-d)", d);
-    GRAFP_REQUIRE(n >= 1 && n < 0x7fffffffll && nq >= 1, "knn_search_pre: bad n=%lld nq=%d", (long long)n, nq);
-    GRAFP_REQUIRE(k >= 1 && k <= GRAFP_SEARCH_MAX_K, "knn_search_pre: k=%d not in [1, %d]", k, GRAFP_SEARCH_MAX_K);
-    GRAFP_REQUIRE((((uintptr_t)db | (uintptr_t)db_bf16) & 15) == 0 && ((uintptr_t)q & 3) == 0,
-                  "knn_search_pre: db / db_bf16 must be 16-byte aligned");
-    const size_t need = grafp_knn_search_pre_workspace(n, nq, d, k);
-    if (!ws || ws_bytes < need) {
-        set_error("knn_search_pre: workspace %zu bytes < required %zu", ws_bytes, need);
-        return GRAFP_ERR_WORKSPACE;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const PrePlan pl = pre_plan(n, nq);
-    const int qw = pl.qw, nqs = pl.nqs, qgroups = pl.qgroups, b_splits = pl.b_splits;
-    const int64_t b_rows = pl.b_rows, b_rps = pl.b_rps;
-    int splits;
-    int64_t rps;
-    int64_t want = GRAFP_TUNE_INT("GRAFP_SEARCH_WANT", nqs >= 2 ? 256 * SB_WGS_NQS2 : 768) / qgroups;
-    if (want < 1) want = 1;
+    // scan workgroups: as many per CU as the kernel's __launch_bounds__ let run side by side
+    const int64_t want = GRAFP_TUNE_INT("GRAFP_SEARCH_WANT", p.nqs >= 2 ? 256 * SB_WGS_NQS2 : 768) / p.qgroups;
     // Large batches scan in two parts.  The pre-pass bound (k-th smallest of 64 group minima over n/16 rows) lets a few
     // hundred rows per query through; the first n/4 rows are scanned with it, the k-th smallest UPPER bound among their
     // candidates (at least k rows are truly that close -- the select kernel's own phase A, run early: 35 us at 4096
@@ -1394,47 +1327,84 @@ extern "C" int grafp_knn_search_l2_pre(const float *db, const void *db_bf16, con
     // n/6, n/8 gives 1.40, 1.40, 1.42 ms.  Below ~700 queries the two extra launches cost what the bound saves (256
     // queries: 0.171 -> 0.183 ms): one part.
     const int first_div = GRAFP_TUNE_INT("GRAFP_SEARCH_FIRST_DIV", 4);
-    int64_t n_first = 0;
+    p.n_first = 0;
     if (nq >= GRAFP_TUNE_INT("GRAFP_SEARCH_TWO_PART_NQ", 768) && first_div > 1 && n / first_div >= 65536)
-        n_first = (n / first_div) / SB_TR * SB_TR;
-    int a_splits = 1;
-    int64_t a_rps = SB_TR;
-    if (n_first > 0) split_rows(n_first, SB_TR, want, &a_splits, &a_rps);
-    split_rows(n - n_first, SB_TR, want, &splits, &rps);
-    char *w = (char *)ws;
-    float *qq = (float *)w;                 w += align256((size_t)nq * sizeof(float));
-    float *thr = (float *)w;                w += align256((size_t)nq * sizeof(float));
-    int *cnt = (int *)w;                    w += align256((size_t)nq * SR_NSUB * sizeof(int));
-    float *gmax = (float *)w;               w += align256((size_t)nq * pl.ngroups * sizeof(float));
-    int *cand_i = (int *)w;                 w += align256((size_t)nq * SR_CAP * sizeof(int));
-    float2 *cand_e = (float2 *)w;
+        p.n_first = (n / first_div) / SB_TR * SB_TR;
+    p.a_splits = 1;
+    p.a_rps = SB_TR;
+    if (p.n_first > 0) split_rows(p.n_first, SB_TR, want, &p.a_splits, &p.a_rps);
+    split_rows(n - p.n_first, SB_TR, want, &p.splits, &p.rps);
+    return p;
+}
+
+// the workspace of grafp_knn_search_l2_pre: qq (nq) | thr (nq) | cnt (nq, SR_NSUB) | gmax (nq, ngroups) | cand_i,
+// cand_e (nq, SR_CAP)
+struct PreWs {
+    float *qq, *thr;
+    int *cnt;
+    float *gmax;
+    int *cand_i;
+    float2 *cand_e;
+};
+static size_t pre_layout(void *ws, int nq, const PrePlan &p, PreWs &a) {
+    WsCarve w{(char *)ws, 0};
+    a.qq = w.take<float>((size_t)nq * sizeof(float));
+    a.thr = w.take<float>((size_t)nq * sizeof(float));
+    a.cnt = w.take<int>((size_t)nq * SR_NSUB * sizeof(int));
+    a.gmax = w.take<float>((size_t)nq * p.ngroups * sizeof(float));
+    a.cand_i = w.take<int>((size_t)nq * SR_CAP * sizeof(int));
+    a.cand_e = w.take<float2>((size_t)nq * SR_CAP * sizeof(float2));
+    return w.off;
+}
+}  // namespace grafp
+
+extern "C" size_t grafp_knn_search_pre_workspace(int64_t n, int nq, int d, int k) {
+    using namespace grafp;
+    PreWs a;
+    return (n <= 0 || nq <= 0 || d != SR_D || k < 1) ? 0 : pre_layout(nullptr, nq, pre_plan(n, nq), a);
+}
+
+extern "C" int grafp_knn_search_l2_pre(const float *db, const void *db_bf16, const float *db_sqnorm, int64_t n,
+                                       const float *q, int nq, int d, int k, int64_t id_base, float *out_dist,
+                                       int64_t *out_ids, void *ws, size_t ws_bytes, grafp_stream_t stream) {
+    using namespace grafp;
+    int rc = search_check("knn_search_pre", db && db_bf16 && db_sqnorm && q && out_dist && out_ids, db, db_bf16, q, n, nq,
+                          d, k);
+    if (rc != GRAFP_OK) return rc;
+    const PrePlan p = pre_plan(n, nq);
+    PreWs a;
+    rc = search_ws_check("knn_search_pre", ws, ws_bytes, pre_layout(nullptr, nq, p, a));
+    if (rc != GRAFP_OK) return rc;
+    pre_layout(ws, nq, p, a);
+    hipStream_t s = (hipStream_t)stream;
     const size_t lds = (size_t)SB_NS * SB_STAGE;
-    const dim3 grid_b(b_splits, qgroups), grid_a(a_splits, qgroups), grid(splits, qgroups);
+    const dim3 grid_b(p.b_splits, p.qgroups), grid_a(p.a_splits, p.qgroups), grid(p.splits, p.qgroups);
     const unsigned short *dbh = (const unsigned short *)db_bf16;
 #define SB_LAUNCH(QW, NQS)                                                                                          \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(search_bound_bf16_kernel<QW, NQS>), grid_b, dim3(256), lds, s, dbh,          \
-                       db_sqnorm, b_rows, q, nq, b_rps, gmax, pl.ngroups);                                          \
-    hipLaunchKernelGGL(search_thr_pre_kernel, dim3((nq + 3) / 4), dim3(256), 0, s, q, nq, (const float *)gmax,      \
-                       pl.ngroups, k, qq, thr, cnt);                                                                \
-    if (n_first > 0) {                                                                                              \
+                       db_sqnorm, p.b_rows, q, nq, p.b_rps, a.gmax, p.ngroups);                                     \
+    hipLaunchKernelGGL(search_thr_pre_kernel, dim3((nq + 3) / 4), dim3(256), 0, s, q, nq, (const float *)a.gmax,    \
+                       p.ngroups, k, a.qq, a.thr, a.cnt);                                                           \
+    if (p.n_first > 0) {                                                                                            \
         hipLaunchKernelGGL(HIP_KERNEL_NAME(search_scan_bf16_kernel<QW, NQS>), grid_a, dim3(256), lds, s, dbh,       \
-                           db_sqnorm, (int64_t)0, n_first, q, (const float *)qq, nq, a_rps, (const float *)thr,     \
-                           cnt, cand_i, cand_e);                                                                    \
+                           db_sqnorm, (int64_t)0, p.n_first, q, (const float *)a.qq, nq, p.a_rps,                   \
+                           (const float *)a.thr, a.cnt, a.cand_i, a.cand_e);                                        \
         hipLaunchKernelGGL(search_select_exact_kernel<true>, dim3(nq), dim3(256), 0, s, db, db_sqnorm, n, q,        \
-                           (const float *)qq, nq, k, id_base, thr, (const int *)cnt, (const int *)cand_i,           \
-                           (const float2 *)cand_e, out_dist, out_ids);                                               \
+                           (const float *)a.qq, nq, k, id_base, a.thr, (const int *)a.cnt, (const int *)a.cand_i,   \
+                           (const float2 *)a.cand_e, out_dist, out_ids);                                            \
     }                                                                                                               \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(search_scan_bf16_kernel<QW, NQS>), grid, dim3(256), lds, s, dbh, db_sqnorm,  \
-                       n_first, n, q, (const float *)qq, nq, rps, (const float *)thr, cnt, cand_i, cand_e)
-    if (qw == 2) { SB_LAUNCH(2, 1); }
-    else if (nqs == 1) { SB_LAUNCH(4, 1); }
-    else if (nqs == 3) { SB_LAUNCH(4, 3); }
+                       p.n_first, n, q, (const float *)a.qq, nq, p.rps, (const float *)a.thr, a.cnt, a.cand_i,      \
+                       a.cand_e)
+    if (p.qw == 2) { SB_LAUNCH(2, 1); }
+    else if (p.nqs == 1) { SB_LAUNCH(4, 1); }
+    else if (p.nqs == 3) { SB_LAUNCH(4, 3); }
     else { SB_LAUNCH(4, 2); }
 #undef SB_LAUNCH
     GRAFP_CHECK_LAUNCH("search_bound_bf16_kernel / search_scan_bf16_kernel");
     hipLaunchKernelGGL(search_select_exact_kernel<false>, dim3(nq), dim3(256), 0, s, db, db_sqnorm, n, q,
-                       (const float *)qq, nq, k, id_base, thr, (const int *)cnt, (const int *)cand_i,
-                       (const float2 *)cand_e, out_dist, out_ids);
+                       (const float *)a.qq, nq, k, id_base, a.thr, (const int *)a.cnt, (const int *)a.cand_i,
+                       (const float2 *)a.cand_e, out_dist, out_ids);
     GRAFP_CHECK_LAUNCH("search_select_exact_kernel");
     return GRAFP_OK;
 }
@@ -1445,11 +1415,10 @@ extern "C" int grafp_measure_search_loop(const void *db_bf16, const float *db_sq
                                          const float *qq, int nq, int abl, int nqs, int *gmin, grafp_stream_t stream) {
     (void)qq;
     using namespace grafp;
-    const int qgroups = (nq + 128 * nqs - 1) / (128 * nqs);
+    const int qgroups = query_groups(nq, 4, nqs);
     int splits;
     int64_t rps;
-    int64_t want = 768 / qgroups;
-    split_rows(n, SB_TR, want < 1 ? 1 : want, &splits, &rps);
+    split_rows(n, SB_TR, 768 / qgroups, &splits, &rps);
     const size_t lds = (size_t)SB_NS * SB_STAGE;
     const dim3 grid(splits, qgroups);
     const unsigned short *dbh = (const unsigned short *)db_bf16;

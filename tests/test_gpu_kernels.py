@@ -502,6 +502,38 @@ def test_search_candidate_overflow_rescan(dev):
     assert (i[0].cpu().numpy() == np.arange(1000, 1020)).all()
 
 
+def test_search_many_ties_listed(dev):
+    """Thousands of exact ties that do NOT overflow a candidate sub-list: the WaveTop + merge halves of
+    search_select_exact_kernel (knn_search.hip), which the contiguous copies of the overflow test never reach (those
+    fill one sub-list and take the full rescan).
+
+    For 12 000 rows and nq <= 64, pre_plan scans with 188 slices of one 64-row tile (SB_TR) each, and slice s appends to
+    sub-list s & 15 (SR_NSUB = 16 sub-lists of SR_SUBCAP = 256 slots), i.e. at most 12 slices per sub-list.
+      * copy A in rows 0, 4, 8, ...: 16 per tile, <= 12 * 16 = 192 <= 256 per sub-list (listed), 3 000 > SF_CAP = 2048 in
+        all: phase A runs on WaveTop, and since all 3 000 tie under its bound, nneed = 3 000 > SF_NEED = 512: phase B too;
+      * copy B in rows 1, 13, 25, ...: 5 or 6 per tile, <= 72 per sub-list, 1 000 <= SF_CAP in all: phase A reads its bound
+        from the histogram, but all 1 000 tie under it, nneed = 1 000 > SF_NEED: phase B runs on WaveTop;
+      * the all-f32 path lists 3 000 <= SR_CAP = 4096 candidates and sorts them.
+    Rows 0 (mod 4) and 1 (mod 12) are disjoint; the planted query's row 7919 is in neither set."""
+    from grafp_amd import ops
+    from oracle import native
+    db, q, rows = _planted(12000, 3, "ties")
+    a, b = db[0].copy(), db[1].copy()
+    db = db.copy()
+    db[0::4] = a                                                      # 3000 rows
+    db[1::12] = b                                                     # 1000 rows
+    assert rows[1] == 7919 and rows[1] % 4 != 0 and rows[1] % 12 != 1
+    qs = np.stack([a, b, q[1]]).astype(np.float32)
+    dbt = t(db).to(dev)
+    d, i = _search(ops, dbt, t(qs).to(dev), 20)                       # asserts pre-filter path == f32 path
+    wd, wi = native.flat_search_l2(db, qs, 20)
+    d, i = d.cpu().numpy(), i.cpu().numpy()
+    assert np.array_equal(i, wi) and np.array_equal(d, wd)
+    assert (i[0] == np.arange(0, 80, 4)).all()
+    assert (i[1] == 1 + 12 * np.arange(20)).all()
+    assert i[2, 0] == rows[1]
+
+
 @pytest.mark.parametrize("n,nq", [(1, 1), (31, 2), (33, 33), (64, 64), (65, 65), (127, 65), (4097, 40), (8191, 129),
                                   (70001, 7)])
 def test_search_ragged_sizes(dev, n, nq):
