@@ -16,90 +16,14 @@
 #include <type_traits>
 
 #define GRAFP_STORE_FAMILY 1        // (common.h: GRAFP_ST_NT experiment builds)
-#include "common.h"
-#include "tuning.h"
+#include "elemio.h"
 
 namespace grafp {
 
 constexpr int BN_THREADS = 256;
 
-template <typename T> struct BnIO;
-template <> struct BnIO<float> {
-    static constexpr int W = 4;
-    __device__ static void load(const float *p, float (&v)[4]) {
-        const float4 t = *reinterpret_cast<const float4 *>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    }
-    // outputs are streamed with the non-temporal hint: a plain-store copy of a 67-268 MB tensor runs at 3.7-4.9 TB/s
-    // on MI355X, the same copy with `nt` stores at 6.2-6.7 TB/s (tools/microbench/copy_bench.hip)
-    __device__ static void store(float *p, const float (&v)[4], bool plain = false) {
-        typedef float f4 __attribute__((ext_vector_type(4)));
-        const f4 t = {v[0], v[1], v[2], v[3]};
-        if (plain) store16_hint(p, __builtin_bit_cast(st_u32x4, t), true);      // (wave-uniform: see bn_plain_stores)
-        else GRAFP_ST_NT(t, reinterpret_cast<f4 *>(p));
-    }
-    using Raw = float4;
-    __device__ static void unpack(const float4 &t, float (&v)[4]) { v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-    __device__ static float ld1(const float *p) { return *p; }
-    __device__ static void st1(float *p, float v) { *p = v; }
-};
-__device__ __forceinline__ unsigned short f2bf(float v) {
-    unsigned u = __float_as_uint(v);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-template <> struct BnIO<unsigned short> {
-    static constexpr int W = 8;
-    __device__ static void load(const unsigned short *p, float (&v)[8]) {
-        const uint4 t = *reinterpret_cast<const uint4 *>(p);
-        const unsigned w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[2 * i] = __uint_as_float(w[i] << 16);
-            v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-        }
-    }
-    __device__ static void store(unsigned short *p, const float (&v)[8], bool plain = false) {
-        // v_cvt_pk_bf16_f32 (round to nearest even, the conversion the GEMM epilogues use): one instruction per PAIR instead
-        // of the six of the integer form per value -- a seventh of this file's backward kernel's vector instructions
-        typedef float f2 __attribute__((ext_vector_type(2)));
-        typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-        unsigned w[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const f2 pr = {v[2 * i], v[2 * i + 1]};
-            w[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(pr, b2));
-        }
-        typedef unsigned u4 __attribute__((ext_vector_type(4)));
-        const u4 t = {w[0], w[1], w[2], w[3]};
-        if (plain) store16_hint(p, __builtin_bit_cast(st_u32x4, t), true);
-        else GRAFP_ST_NT(t, reinterpret_cast<u4 *>(p));
-    }
-    using Raw = uint4;
-    __device__ static void unpack(const uint4 &t, float (&v)[8]) {
-        const unsigned w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[2 * i] = __uint_as_float(w[i] << 16);
-            v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-        }
-    }
-    __device__ static float ld1(const unsigned short *p) { return __uint_as_float(((unsigned)*p) << 16); }
-    __device__ static void st1(unsigned short *p, float v) { *p = f2bf(v); }
-};
-
 // dY of the BatchNorm backward is read twice by the two launches that follow it (data gradient and weight gradient of
-// the convolution in front).  A tensor that fits the 256 MB Infinity Cache with room for the other operand is written
-// with PLAIN stores (it stays cached for its two readers); larger ones keep the streaming hint, which wins there by
-// sparing the producers' working set.  Same-box A/B of the whole step (tools/step_lib_ab.py, profiles/r06_c_*, r06_d_*):
-// plain stores in this file -1.15 % at 128 pairs, -1.05 % at 256, +0.45 % at 512, +1.2 % at 1024; the threshold between
-// them from tools/step_env_graph_ab.py (profiles/r06_e_bn_plain_threshold.txt: tensors up to 70 / 140 / 280 MB / all
-// plain: 128 pairs -0.8 / -0.7 / -0.8 / -0.8 %, 256 pairs -0.8 / -1.2 / -0.6 / -0.7 %, 512 pairs +0.2 / -0.1 / +0.8 /
-// +1.1 %): 140 MB.  A pure function of the tensor size.
-static int bn_plain_stores(size_t bytes) {
-    return bytes <= ((size_t)GRAFP_TUNE_INT("GRAFP_BN_BWD_PLAIN_MAX_MB", 140) << 20) ? 1 : 0;
-}
+// the convolution in front): its store hint is plain_stores("GRAFP_BN_BWD_PLAIN_MAX_MB") of elemio.h.
 
 template <int THREADS = 256>
 __device__ __forceinline__ float2 block_sum2(float a, float b, float2 *scratch, int tid) {
@@ -137,24 +61,24 @@ __global__ __launch_bounds__(BN_THREADS) void bn_stats_kernel(const T *__restric
     const int S = gridDim.x, g = s / Sg, sl = s - g * Sg;
     const T *row = x + (size_t)c * M;
     const float pb = pre_bias ? pre_bias[c] : 0.0f;
-    const float shift = BnIO<T>::ld1(row + (int64_t)g * Mg) + pb;
+    const float shift = ElemIO<T>::ld1(row + (int64_t)g * Mg) + pb;
     const int64_t gend = (int64_t)(g + 1) * Mg;
     const int64_t lo = (int64_t)g * Mg + (int64_t)sl * chunk, hi = (lo + chunk < gend) ? lo + chunk : gend;
     float a = 0.0f, q = 0.0f;
-    constexpr int W = VEC ? BnIO<T>::W : 1;
+    constexpr int W = VEC ? ElemIO<T>::W : 1;
     for (int64_t m = lo + (int64_t)tid * W; m < hi; m += (int64_t)BN_THREADS * W) {
         if (VEC && m + W <= hi) {
-            float v[BnIO<T>::W];
-            BnIO<T>::load(row + m, v);
+            float v[ElemIO<T>::W];
+            ElemIO<T>::load(row + m, v);
 #pragma unroll
-            for (int i = 0; i < BnIO<T>::W; ++i) {
+            for (int i = 0; i < ElemIO<T>::W; ++i) {
                 const float d = (v[i] + pb) - shift;
                 a += d;
                 q = __builtin_fmaf(d, d, q);
             }
         } else {
             for (int i = 0; i < W && m + i < hi; ++i) {
-                const float d = (BnIO<T>::ld1(row + m + i) + pb) - shift;
+                const float d = (ElemIO<T>::ld1(row + m + i) + pb) - shift;
                 a += d;
                 q = __builtin_fmaf(d, d, q);
             }
@@ -193,7 +117,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_kernel(const T *__restric
             a += part[((size_t)c * S + i) * 2 + 0];
             q += part[((size_t)c * S + i) * 2 + 1];
         }
-        const float shift = BnIO<T>::ld1(row + (int64_t)grp * Mg) + pb;
+        const float shift = ElemIO<T>::ld1(row + (int64_t)grp * Mg) + pb;
         const float dm = a / (float)Mg;
         const float var = fmaxf(q / (float)Mg - dm * dm, 0.0f);
         mean = shift + dm;
@@ -211,7 +135,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_kernel(const T *__restric
                     a2 += part[((size_t)c * S + i) * 2 + 0];
                     q2 += part[((size_t)c * S + i) * 2 + 1];
                 }
-                const float sh2 = BnIO<T>::ld1(row + (int64_t)g2 * Mg) + pb;
+                const float sh2 = ElemIO<T>::ld1(row + (int64_t)g2 * Mg) + pb;
                 const float dm2 = a2 / (float)Mg;
                 const float var2 = fmaxf(q2 / (float)Mg - dm2 * dm2, 0.0f);
                 const float unbiased = Mg > 1 ? var2 * ((float)Mg / (float)(Mg - 1)) : var2;
@@ -235,7 +159,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_kernel(const T *__restric
     T *orow = out + (size_t)c * M;
     const int64_t gend = (int64_t)(grp + 1) * Mg;
     const int64_t lo = (int64_t)grp * Mg + (int64_t)sl * chunk, hi = (lo + chunk < gend) ? lo + chunk : gend;
-    constexpr int W = VEC ? BnIO<T>::W : 1;
+    constexpr int W = VEC ? ElemIO<T>::W : 1;
     int64_t m = lo + (int64_t)tid * W;
     if (VEC) {
         // four vectors in flight per thread (one load -> use -> store per iteration left the kernel latency-bound at
@@ -243,42 +167,42 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_kernel(const T *__restric
         constexpr int U = 4;
         const int64_t step = (int64_t)BN_THREADS * W;
         for (; m + (U - 1) * step + W <= hi; m += U * step) {
-            typename BnIO<T>::Raw rx[U], rr[U];
+            typename ElemIO<T>::Raw rx[U], rr[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                rx[u] = *reinterpret_cast<const typename BnIO<T>::Raw *>(row + m + u * step);
-                if (rrow) rr[u] = *reinterpret_cast<const typename BnIO<T>::Raw *>(rrow + m + u * step);
+                rx[u] = *reinterpret_cast<const typename ElemIO<T>::Raw *>(row + m + u * step);
+                if (rrow) rr[u] = *reinterpret_cast<const typename ElemIO<T>::Raw *>(rrow + m + u * step);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                float v[BnIO<T>::W], r[BnIO<T>::W];
-                BnIO<T>::unpack(rx[u], v);
-                if (rrow) BnIO<T>::unpack(rr[u], r);
+                float v[ElemIO<T>::W], r[ElemIO<T>::W];
+                ElemIO<T>::unpack(rx[u], v);
+                if (rrow) ElemIO<T>::unpack(rr[u], r);
 #pragma unroll
-                for (int i = 0; i < BnIO<T>::W; ++i) {
+                for (int i = 0; i < ElemIO<T>::W; ++i) {
                     v[i] = act_fwd(__builtin_fmaf(v[i], g, off), act, slope);
                     if (rrow) v[i] += r[i];
                 }
-                BnIO<T>::store(orow + m + u * step, v);
+                ElemIO<T>::store(orow + m + u * step, v, false);
             }
         }
     }
     for (; m < hi; m += (int64_t)BN_THREADS * W) {
         if (VEC && m + W <= hi) {
-            float v[BnIO<T>::W], r[BnIO<T>::W];
-            BnIO<T>::load(row + m, v);
-            if (rrow) BnIO<T>::load(rrow + m, r);
+            float v[ElemIO<T>::W], r[ElemIO<T>::W];
+            ElemIO<T>::load(row + m, v);
+            if (rrow) ElemIO<T>::load(rrow + m, r);
 #pragma unroll
-            for (int i = 0; i < BnIO<T>::W; ++i) {
+            for (int i = 0; i < ElemIO<T>::W; ++i) {
                 v[i] = act_fwd(__builtin_fmaf(v[i], g, off), act, slope);
                 if (rrow) v[i] += r[i];
             }
-            BnIO<T>::store(orow + m, v);
+            ElemIO<T>::store(orow + m, v, false);
         } else {
             for (int i = 0; i < W && m + i < hi; ++i) {
-                float z = act_fwd(__builtin_fmaf(BnIO<T>::ld1(row + m + i), g, off), act, slope);
-                if (rrow) z += BnIO<T>::ld1(rrow + m + i);
-                BnIO<T>::st1(orow + m + i, z);
+                float z = act_fwd(__builtin_fmaf(ElemIO<T>::ld1(row + m + i), g, off), act, slope);
+                if (rrow) z += ElemIO<T>::ld1(rrow + m + i);
+                ElemIO<T>::st1(orow + m + i, z);
             }
         }
     }
@@ -303,14 +227,14 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_reduce_kernel(const T *__re
     const int64_t gend = (int64_t)(grp + 1) * Mg;
     const int64_t lo = (int64_t)grp * Mg + (int64_t)sl * chunk, hi = (lo + chunk < gend) ? lo + chunk : gend;
     float sd = 0.0f, sdx = 0.0f;
-    constexpr int W = VEC ? BnIO<T>::W : 1;
+    constexpr int W = VEC ? ElemIO<T>::W : 1;
     for (int64_t m = lo + (int64_t)tid * W; m < hi; m += (int64_t)BN_THREADS * W) {
         if (VEC && m + W <= hi) {
-            float v[BnIO<T>::W], d[BnIO<T>::W];
-            BnIO<T>::load(row + m, v);
-            BnIO<T>::load(grow + m, d);
+            float v[ElemIO<T>::W], d[ElemIO<T>::W];
+            ElemIO<T>::load(row + m, v);
+            ElemIO<T>::load(grow + m, d);
 #pragma unroll
-            for (int i = 0; i < BnIO<T>::W; ++i) {
+            for (int i = 0; i < ElemIO<T>::W; ++i) {
                 const float xh = ((v[i] + pb) - mean) * invstd;
                 const float dy = d[i] * act_grad(__builtin_fmaf(xh, ga, be), act, slope);
                 sd += dy;
@@ -318,8 +242,8 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_reduce_kernel(const T *__re
             }
         } else {
             for (int i = 0; i < W && m + i < hi; ++i) {
-                const float xh = ((BnIO<T>::ld1(row + m + i) + pb) - mean) * invstd;
-                const float dy = BnIO<T>::ld1(grow + m + i) * act_grad(__builtin_fmaf(xh, ga, be), act, slope);
+                const float xh = ((ElemIO<T>::ld1(row + m + i) + pb) - mean) * invstd;
+                const float dy = ElemIO<T>::ld1(grow + m + i) * act_grad(__builtin_fmaf(xh, ga, be), act, slope);
                 sd += dy;
                 sdx = __builtin_fmaf(dy, xh, sdx);
             }
@@ -373,24 +297,24 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_dx_kernel(const T *__restri
     const float m1 = training ? sd / (float)Mg : 0.0f, m2 = training ? sdx / (float)Mg : 0.0f;
     const int64_t gend = (int64_t)(grp + 1) * Mg;
     const int64_t lo = (int64_t)grp * Mg + (int64_t)sl * chunk, hi = (lo + chunk < gend) ? lo + chunk : gend;
-    constexpr int W = VEC ? BnIO<T>::W : 1;
+    constexpr int W = VEC ? ElemIO<T>::W : 1;
     for (int64_t m = lo + (int64_t)tid * W; m < hi; m += (int64_t)BN_THREADS * W) {
         if (VEC && m + W <= hi) {
-            float v[BnIO<T>::W], d[BnIO<T>::W];
-            BnIO<T>::load(row + m, v);
-            BnIO<T>::load(grow + m, d);
+            float v[ElemIO<T>::W], d[ElemIO<T>::W];
+            ElemIO<T>::load(row + m, v);
+            ElemIO<T>::load(grow + m, d);
 #pragma unroll
-            for (int i = 0; i < BnIO<T>::W; ++i) {
+            for (int i = 0; i < ElemIO<T>::W; ++i) {
                 const float xh = ((v[i] + pb) - mean) * invstd;
                 const float dy = d[i] * act_grad(__builtin_fmaf(xh, ga, be), act, slope);
                 v[i] = k * ((dy - m1) - xh * m2);
             }
-            BnIO<T>::store(orow + m, v);
+            ElemIO<T>::store(orow + m, v, false);
         } else {
             for (int i = 0; i < W && m + i < hi; ++i) {
-                const float xh = ((BnIO<T>::ld1(row + m + i) + pb) - mean) * invstd;
-                const float dy = BnIO<T>::ld1(grow + m + i) * act_grad(__builtin_fmaf(xh, ga, be), act, slope);
-                BnIO<T>::st1(orow + m + i, k * ((dy - m1) - xh * m2));
+                const float xh = ((ElemIO<T>::ld1(row + m + i) + pb) - mean) * invstd;
+                const float dy = ElemIO<T>::ld1(grow + m + i) * act_grad(__builtin_fmaf(xh, ga, be), act, slope);
+                ElemIO<T>::st1(orow + m + i, k * ((dy - m1) - xh * m2));
             }
         }
     }
@@ -490,7 +414,7 @@ __global__ __launch_bounds__(BN1_THREADS) void bn_fwd1_kernel(const T *__restric
                                                              int *__restrict__ sync, T *__restrict__ out,
                                                              float *__restrict__ save_mean,
                                                              float *__restrict__ save_invstd, int spin_limit) {
-    constexpr int W = BnIO<T>::W, ITEMS = BN1_ITEMS_FWD, CHUNK = BN1_THREADS * ITEMS * W;
+    constexpr int W = ElemIO<T>::W, ITEMS = BN1_ITEMS_FWD, CHUNK = BN1_THREADS * ITEMS * W;
     __shared__ float2 scratch[BN1_THREADS / 64];
     __shared__ float2 sp[BN1_MAX_S];
     __shared__ int n_missing;
@@ -498,23 +422,23 @@ __global__ __launch_bounds__(BN1_THREADS) void bn_fwd1_kernel(const T *__restric
     const int S = gridDim.x, grp = s / Sg, sl = s - grp * Sg;
     const T *row = x + (size_t)c * M;
     const float pb = pre_bias ? pre_bias[c] : 0.0f;
-    const float shift = BnIO<T>::ld1(row + (int64_t)grp * Mg) + pb;
+    const float shift = ElemIO<T>::ld1(row + (int64_t)grp * Mg) + pb;
     const int64_t gend = (int64_t)(grp + 1) * Mg;
     const int64_t lo = (int64_t)grp * Mg + (int64_t)sl * CHUNK;
     const int64_t hi = (lo + CHUNK < gend) ? lo + CHUNK : gend;
-    typename BnIO<T>::Raw raw[ITEMS];
+    typename ElemIO<T>::Raw raw[ITEMS];
     float a = 0.0f, q = 0.0f;
 #pragma unroll
     for (int it = 0; it < ITEMS; ++it) {
         const int64_t m = lo + ((int64_t)it * BN1_THREADS + tid) * W;
-        if (m < hi) raw[it] = *reinterpret_cast<const typename BnIO<T>::Raw *>(row + m);
+        if (m < hi) raw[it] = *reinterpret_cast<const typename ElemIO<T>::Raw *>(row + m);
     }
 #pragma unroll
     for (int it = 0; it < ITEMS; ++it) {
         const int64_t m = lo + ((int64_t)it * BN1_THREADS + tid) * W;
         if (m < hi) {
             float v[W];
-            BnIO<T>::unpack(raw[it], v);
+            ElemIO<T>::unpack(raw[it], v);
 #pragma unroll
             for (int i = 0; i < W; ++i) {
                 const float d = (v[i] + pb) - shift;
@@ -526,12 +450,12 @@ __global__ __launch_bounds__(BN1_THREADS) void bn_fwd1_kernel(const T *__restric
     // the shortcut rows do not depend on the statistics: fetch them now, so their latency passes during the rendezvous
     // (RES is a template parameter: the 32 extra registers only exist in the instantiation that needs them)
     const T *rrow = RES ? residual + (size_t)c * M : nullptr;
-    typename BnIO<T>::Raw rres[RES ? ITEMS : 1];
+    typename ElemIO<T>::Raw rres[RES ? ITEMS : 1];
     if (RES) {
 #pragma unroll
         for (int it = 0; it < ITEMS; ++it) {
             const int64_t m = lo + ((int64_t)it * BN1_THREADS + tid) * W;
-            if (m < hi) rres[it] = *reinterpret_cast<const typename BnIO<T>::Raw *>(rrow + m);
+            if (m < hi) rres[it] = *reinterpret_cast<const typename ElemIO<T>::Raw *>(rrow + m);
         }
     }
     const float2 r = block_sum2<BN1_THREADS>(a, q, scratch, tid);
@@ -543,7 +467,7 @@ __global__ __launch_bounds__(BN1_THREADS) void bn_fwd1_kernel(const T *__restric
         for (int i = w_lo; i < w_hi; ++i) {
             if (__float_as_uint(sp[i].x) != BN1_EMPTY) continue;            // LDS value: workgroup-uniform branch
             const int g2 = i / Sg;
-            const float sh2 = BnIO<T>::ld1(row + (int64_t)g2 * Mg) + pb;
+            const float sh2 = ElemIO<T>::ld1(row + (int64_t)g2 * Mg) + pb;
             const int64_t lo2 = (int64_t)g2 * Mg + (int64_t)(i - g2 * Sg) * CHUNK;
             const int64_t hi2 = (lo2 + CHUNK < (int64_t)(g2 + 1) * Mg) ? lo2 + CHUNK : (int64_t)(g2 + 1) * Mg;
             float a2 = 0.0f, q2 = 0.0f;
@@ -552,7 +476,7 @@ __global__ __launch_bounds__(BN1_THREADS) void bn_fwd1_kernel(const T *__restric
                 const int64_t m = lo2 + ((int64_t)it * BN1_THREADS + tid) * W;
                 if (m < hi2) {
                     float v[W];
-                    BnIO<T>::load(row + m, v);
+                    ElemIO<T>::load(row + m, v);
 #pragma unroll
                     for (int e = 0; e < W; ++e) {
                         const float d = (v[e] + pb) - sh2;
@@ -591,7 +515,7 @@ __global__ __launch_bounds__(BN1_THREADS) void bn_fwd1_kernel(const T *__restric
                 a2 += sp[i].x;
                 q2 += sp[i].y;
             }
-            const float sh2 = BnIO<T>::ld1(row + (int64_t)g2 * Mg) + pb;
+            const float sh2 = ElemIO<T>::ld1(row + (int64_t)g2 * Mg) + pb;
             const float dm2 = a2 / (float)Mg;
             const float var2 = fmaxf(q2 / (float)Mg - dm2 * dm2, 0.0f);
             const float unbiased = Mg > 1 ? var2 * ((float)Mg / (float)(Mg - 1)) : var2;
@@ -609,14 +533,14 @@ __global__ __launch_bounds__(BN1_THREADS) void bn_fwd1_kernel(const T *__restric
         const int64_t m = lo + ((int64_t)it * BN1_THREADS + tid) * W;
         if (m < hi) {
             float v[W], rr[W];
-            BnIO<T>::unpack(raw[it], v);
-            if (RES) BnIO<T>::unpack(rres[it], rr);
+            ElemIO<T>::unpack(raw[it], v);
+            if (RES) ElemIO<T>::unpack(rres[it], rr);
 #pragma unroll
             for (int i = 0; i < W; ++i) {
                 v[i] = act_fwd(__builtin_fmaf(v[i], g, off), act, slope);
                 if (RES) v[i] += rr[i];
             }
-            BnIO<T>::store(orow + m, v);
+            ElemIO<T>::store(orow + m, v, false);
         }
     }
     if (tid == 0) bn1_rearm(checkout, S, counter, slots_row);
@@ -635,7 +559,7 @@ __global__ __launch_bounds__(THREADS) void bn_bwd1_kernel(const T *__restrict__ 
                                                              float *__restrict__ dgamma, float *__restrict__ dbeta,
                                                              float *__restrict__ dpre_bias, int spin_limit,
                                                              int plain_stores) {
-    constexpr int W = BnIO<T>::W, CHUNK = THREADS * ITEMS * W;
+    constexpr int W = ElemIO<T>::W, CHUNK = THREADS * ITEMS * W;
     __shared__ float2 scratch[THREADS / 64];
     __shared__ float2 sp[BN1_MAX_S];
     __shared__ int n_missing;
@@ -655,13 +579,13 @@ __global__ __launch_bounds__(THREADS) void bn_bwd1_kernel(const T *__restrict__ 
     const int64_t gend = (int64_t)(grp + 1) * Mg;
     const int64_t lo = (int64_t)grp * Mg + (int64_t)sl * CHUNK;
     const int64_t hi = (lo + CHUNK < gend) ? lo + CHUNK : gend;
-    typename BnIO<T>::Raw rx[ITEMS], rd[ITEMS];
+    typename ElemIO<T>::Raw rx[ITEMS], rd[ITEMS];
 #pragma unroll
     for (int it = 0; it < ITEMS; ++it) {
         const int64_t m = lo + ((int64_t)it * THREADS + tid) * W;
         if (m < hi) {
-            rx[it] = GRAFP_LD_ONCE(1, reinterpret_cast<const typename BnIO<T>::Raw *>(row + m));
-            rd[it] = GRAFP_LD_ONCE(4, reinterpret_cast<const typename BnIO<T>::Raw *>(grow + m));
+            rx[it] = GRAFP_LD_ONCE(1, reinterpret_cast<const typename ElemIO<T>::Raw *>(row + m));
+            rd[it] = GRAFP_LD_ONCE(4, reinterpret_cast<const typename ElemIO<T>::Raw *>(grow + m));
         }
     }
     float sd = 0.0f, sdx = 0.0f;
@@ -670,8 +594,8 @@ __global__ __launch_bounds__(THREADS) void bn_bwd1_kernel(const T *__restrict__ 
         const int64_t m = lo + ((int64_t)it * THREADS + tid) * W;
         if (m < hi) {
             float v[W], d[W];
-            BnIO<T>::unpack(rx[it], v);
-            BnIO<T>::unpack(rd[it], d);
+            ElemIO<T>::unpack(rx[it], v);
+            ElemIO<T>::unpack(rd[it], d);
 #pragma unroll
             for (int i = 0; i < W; ++i) {
                 const float xh = __builtin_fmaf(v[i], invstd, xh0);
@@ -698,8 +622,8 @@ __global__ __launch_bounds__(THREADS) void bn_bwd1_kernel(const T *__restrict__ 
                 const int64_t m = lo2 + ((int64_t)it * THREADS + tid) * W;
                 if (m < hi2) {
                     float v[W], d[W];
-                    BnIO<T>::load(row + m, v);
-                    BnIO<T>::load(grow + m, d);
+                    ElemIO<T>::load(row + m, v);
+                    ElemIO<T>::load(grow + m, d);
 #pragma unroll
                     for (int e = 0; e < W; ++e) {
                         const float xh = __builtin_fmaf(v[e], invstd2, (pb - mean2) * invstd2);
@@ -744,15 +668,15 @@ __global__ __launch_bounds__(THREADS) void bn_bwd1_kernel(const T *__restrict__ 
         const int64_t m = lo + ((int64_t)it * THREADS + tid) * W;
         if (m < hi) {
             float v[W], d[W];
-            BnIO<T>::unpack(rx[it], v);
-            BnIO<T>::unpack(rd[it], d);
+            ElemIO<T>::unpack(rx[it], v);
+            ElemIO<T>::unpack(rd[it], d);
 #pragma unroll
             for (int i = 0; i < W; ++i) {
                 const float xh = __builtin_fmaf(v[i], invstd, xh0);
                 const float dy = __builtin_fmaf(v[i], zg, zoff) > 0.0f ? d[i] : d[i] * neg;
                 v[i] = __builtin_fmaf(xh, km2, __builtin_fmaf(dy, k, km1));
             }
-            BnIO<T>::store(orow + m, v, plain_stores != 0);
+            ElemIO<T>::store(orow + m, v, plain_stores != 0);
         }
     }
     if (tid == 0) bn1_rearm(checkout, S, counter, slots_row);
@@ -785,10 +709,10 @@ static BnPlan bn_plan(int C, int64_t Mg, int G, int W) {
     return p;
 }
 
-template <typename T>
-static bool bn_vec_ok(const void *a, const void *b, const void *c, const void *d, int64_t Mg) {
+// W = ElemIO<T>::W: whole 16-byte pieces at 16-byte aligned addresses
+static bool bn_vec_ok(int W, const void *a, const void *b, const void *c, const void *d, int64_t Mg) {
     const uintptr_t m = (uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d;
-    return (Mg % BnIO<T>::W) == 0 && (m & 15) == 0;
+    return (Mg % W) == 0 && (m & 15) == 0;
 }
 
 }  // namespace grafp
@@ -830,40 +754,38 @@ extern "C" int grafp_bn_fwd_1pass(const void *x, int dtype, int C, int64_t M, in
     }
     hipStream_t s = (hipStream_t)stream;
     float *part = (float *)ws;
+    const int W = dtype == GRAFP_F32 ? 4 : 8;
+    const bool vec = bn_vec_ok(W, x, out, residual, nullptr, Mg);
     if (sync && training) {
-        const bool f32 = dtype == GRAFP_F32;
-        const bool ok = f32 ? bn_vec_ok<float>(x, out, residual, nullptr, Mg) : bn_vec_ok<unsigned short>(x, out, residual, nullptr, Mg);
-        const int Sg = ok ? bn1_plan(Mg, G, f32 ? 4 : 8, BN1_ITEMS_FWD) : 0;
+        const int Sg = vec ? bn1_plan(Mg, G, W, BN1_ITEMS_FWD) : 0;
         if (Sg > 0) {
-            const dim3 grid(Sg * G, C);
-#define BN_FWD1(T, RES)                                                                                                \
-    hipLaunchKernelGGL((bn_fwd1_kernel<T, RES>), grid, dim3(BN1_THREADS), 0, s, (const T *)x, M, Mg, Sg, G, pre_bias,  \
-                       gamma, beta, (const T *)residual, act, slope, eps, momentum, running_mean, running_var,         \
-                       (int *)sync, (T *)out, save_mean, save_invstd, spin)
-            if (f32) { if (residual) BN_FWD1(float, true); else BN_FWD1(float, false); }
-            else { if (residual) BN_FWD1(unsigned short, true); else BN_FWD1(unsigned short, false); }
-#undef BN_FWD1
+            for_elem(dtype, [&](auto te) {
+                using T = typename decltype(te)::type;
+                for_bool(residual != nullptr, [&](auto res) {
+                    hipLaunchKernelGGL((bn_fwd1_kernel<T, decltype(res)::value>), dim3(Sg * G, C), dim3(BN1_THREADS), 0, s,
+                                       (const T *)x, M, Mg, Sg, G, pre_bias, gamma, beta, (const T *)residual, act, slope,
+                                       eps, momentum, running_mean, running_var, (int *)sync, (T *)out, save_mean,
+                                       save_invstd, spin);
+                });
+            });
             GRAFP_CHECK_LAUNCH("bn_fwd1_kernel");
             return GRAFP_OK;
         }
     }
-#define BN_FWD(T, VEC)                                                                                                 \
-    do {                                                                                                               \
-        const BnPlan p = bn_plan(C, Mg, G, VEC ? BnIO<T>::W : 1);                                                      \
-        const dim3 grid(p.Sg * G, C);                                                                                  \
-        if (training)                                                                                                  \
-            hipLaunchKernelGGL((bn_stats_kernel<T, VEC>), grid, dim3(BN_THREADS), 0, s, (const T *)x, M, Mg, p.chunk,   \
-                               p.Sg, pre_bias, part);                                                                  \
-        hipLaunchKernelGGL((bn_apply_kernel<T, VEC>), grid, dim3(BN_THREADS), 0, s, (const T *)x, M, Mg, p.chunk,      \
-                           p.Sg, G, pre_bias, gamma, beta, (const T *)residual, act, slope, eps, momentum, training,            \
-                           running_mean, running_var, part, (T *)out, save_mean, save_invstd);                         \
-    } while (0)
-    if (dtype == GRAFP_F32) {
-        if (bn_vec_ok<float>(x, out, residual, nullptr, Mg)) BN_FWD(float, true); else BN_FWD(float, false);
-    } else {
-        if (bn_vec_ok<unsigned short>(x, out, residual, nullptr, Mg)) BN_FWD(unsigned short, true); else BN_FWD(unsigned short, false);
-    }
-#undef BN_FWD
+    const BnPlan p = bn_plan(C, Mg, G, vec ? W : 1);
+    const dim3 grid(p.Sg * G, C);
+    for_elem(dtype, [&](auto te) {
+        using T = typename decltype(te)::type;
+        for_bool(vec, [&](auto v) {
+            constexpr bool VEC = decltype(v)::value;
+            if (training)
+                hipLaunchKernelGGL((bn_stats_kernel<T, VEC>), grid, dim3(BN_THREADS), 0, s, (const T *)x, M, Mg, p.chunk,
+                                   p.Sg, pre_bias, part);
+            hipLaunchKernelGGL((bn_apply_kernel<T, VEC>), grid, dim3(BN_THREADS), 0, s, (const T *)x, M, Mg, p.chunk, p.Sg,
+                               G, pre_bias, gamma, beta, (const T *)residual, act, slope, eps, momentum, training,
+                               running_mean, running_var, part, (T *)out, save_mean, save_invstd);
+        });
+    });
     GRAFP_CHECK_LAUNCH("bn_stats_kernel / bn_apply_kernel");
     return GRAFP_OK;
 }
@@ -896,15 +818,28 @@ extern "C" int grafp_bn_bwd_1pass(const void *x, const void *dz, int dtype, int 
     }
     hipStream_t s = (hipStream_t)stream;
     float *part = (float *)ws;
+    const bool f32 = dtype == GRAFP_F32;
+    const int W = f32 ? 4 : 8;
+    const bool ok = bn_vec_ok(W, x, dz, dx, nullptr, Mg);
     if (sync && training) {
-        const bool f32 = dtype == GRAFP_F32;
-        const bool ok = f32 ? bn_vec_ok<float>(x, dz, dx, nullptr, Mg) : bn_vec_ok<unsigned short>(x, dz, dx, nullptr, Mg);
+        // one launch of the single-pass kernel <T, ITEMS, THREADS> over sg chunks per view
+        auto launch1 = [&](auto te, auto items_c, auto threads_c, int sg, int plain) {
+            using T = typename decltype(te)::type;
+            constexpr int THREADS = decltype(threads_c)::value;
+            hipLaunchKernelGGL((bn_bwd1_kernel<T, decltype(items_c)::value, THREADS>), dim3(sg * G, C), dim3(THREADS), 0, s,
+                               (const T *)x, (const T *)dz, M, Mg, sg, G, pre_bias, gamma, beta, save_mean, save_invstd, act,
+                               slope, (int *)sync, (T *)dx, dgamma, dbeta, dpre_bias, spin, plain);
+        };
+        using Items1 = std::integral_constant<int, BN1_ITEMS_BWD>;
+        using Items2 = std::integral_constant<int, 2 * BN1_ITEMS_BWD>;
+        using T256 = std::integral_constant<int, BN1_THREADS>;
+        using T512 = std::integral_constant<int, 512>;
         // from 16 chunks per row the rendezvous runs over fewer, larger chunks: 8 vectors per thread and operand instead
         // of 4 (tools/bn_bench.py, threshold swept 0 ... 128: 16 is best at 256, 512 and 2048 clip-views; with the
         // operands fenced across the wait -- bn_opaque -- this variant needs 122 VGPRs, 4 workgroups per CU)
         int items = BN1_ITEMS_BWD;
-        int Sg = ok ? bn1_plan(Mg, G, f32 ? 4 : 8, items) : 0;
-        const int plain = bn_plain_stores((size_t)C * (size_t)M * (f32 ? 4 : 2));
+        int Sg = ok ? bn1_plan(Mg, G, W, items) : 0;
+        const int plain = plain_stores((size_t)C * (size_t)M * (f32 ? 4 : 2), "GRAFP_BN_BWD_PLAIN_MAX_MB", 140);
         const int items8_from = GRAFP_TUNE_INT("GRAFP_BN_BWD_ITEMS8_FROM", 16);
         if (ok && !f32 && (Sg == 0 || Sg * G > items8_from)) {
             items = 2 * BN1_ITEMS_BWD;
@@ -918,51 +853,32 @@ extern "C" int grafp_bn_bwd_1pass(const void *x, const void *dz, int dtype, int 
         if (ok && !f32 && t512_from > 0 && items == 2 * BN1_ITEMS_BWD && Sg >= t512_from) {
             const int Sg2 = bn1_plan(Mg, G, 8, items, 512);
             if (Sg2 > 0) {
-                const dim3 grid2(Sg2 * G, C);
-                hipLaunchKernelGGL((bn_bwd1_kernel<unsigned short, 2 * BN1_ITEMS_BWD, 512>), grid2, dim3(512), 0, s,
-                                   (const unsigned short *)x, (const unsigned short *)dz, M, Mg, Sg2, G, pre_bias, gamma,
-                                   beta, save_mean, save_invstd, act, slope, (int *)sync, (unsigned short *)dx,
-                                   dgamma, dbeta, dpre_bias, spin, plain);
+                launch1(TypeTag<unsigned short>{}, Items2{}, T512{}, Sg2, plain);
                 GRAFP_CHECK_LAUNCH("bn_bwd1_kernel");
                 return GRAFP_OK;
             }
         }
         if (Sg > 0) {
-            const dim3 grid(Sg * G, C);
-            if (f32)
-                hipLaunchKernelGGL((bn_bwd1_kernel<float, BN1_ITEMS_BWD>), grid, dim3(BN1_THREADS), 0, s, (const float *)x,
-                                   (const float *)dz, M, Mg, Sg, G, pre_bias, gamma, beta, save_mean, save_invstd, act,
-                                   slope, (int *)sync, (float *)dx, dgamma, dbeta, dpre_bias, spin, plain);
-            else if (items == BN1_ITEMS_BWD)
-                hipLaunchKernelGGL((bn_bwd1_kernel<unsigned short, BN1_ITEMS_BWD>), grid, dim3(BN1_THREADS), 0, s,
-                                   (const unsigned short *)x, (const unsigned short *)dz, M, Mg, Sg, G, pre_bias, gamma,
-                                   beta, save_mean, save_invstd, act, slope, (int *)sync, (unsigned short *)dx,
-                                   dgamma, dbeta, dpre_bias, spin, plain);
-            else
-                hipLaunchKernelGGL((bn_bwd1_kernel<unsigned short, 2 * BN1_ITEMS_BWD>), grid, dim3(BN1_THREADS), 0, s,
-                                   (const unsigned short *)x, (const unsigned short *)dz, M, Mg, Sg, G, pre_bias, gamma,
-                                   beta, save_mean, save_invstd, act, slope, (int *)sync, (unsigned short *)dx,
-                                   dgamma, dbeta, dpre_bias, spin, plain);
+            if (f32) launch1(TypeTag<float>{}, Items1{}, T256{}, Sg, plain);
+            else if (items == BN1_ITEMS_BWD) launch1(TypeTag<unsigned short>{}, Items1{}, T256{}, Sg, plain);
+            else launch1(TypeTag<unsigned short>{}, Items2{}, T256{}, Sg, plain);
             GRAFP_CHECK_LAUNCH("bn_bwd1_kernel");
             return GRAFP_OK;
         }
     }
-#define BN_BWD(T, VEC)                                                                                                 \
-    do {                                                                                                               \
-        const BnPlan p = bn_plan(C, Mg, G, VEC ? BnIO<T>::W : 1);                                                      \
-        const dim3 grid(p.Sg * G, C);                                                                                  \
-        hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, VEC>), grid, dim3(BN_THREADS), 0, s, (const T *)x, (const T *)dz,  \
-                           M, Mg, p.chunk, p.Sg, G, pre_bias, gamma, beta, save_mean, save_invstd, act, slope, part);  \
-        hipLaunchKernelGGL((bn_bwd_dx_kernel<T, VEC>), grid, dim3(BN_THREADS), 0, s, (const T *)x, (const T *)dz, M,   \
-                           Mg, p.chunk, p.Sg, G, pre_bias, gamma, beta, save_mean, save_invstd, act, slope, training, part,    \
-                           (T *)dx, dgamma, dbeta, dpre_bias);                                                         \
-    } while (0)
-    if (dtype == GRAFP_F32) {
-        if (bn_vec_ok<float>(x, dz, dx, nullptr, Mg)) BN_BWD(float, true); else BN_BWD(float, false);
-    } else {
-        if (bn_vec_ok<unsigned short>(x, dz, dx, nullptr, Mg)) BN_BWD(unsigned short, true); else BN_BWD(unsigned short, false);
-    }
-#undef BN_BWD
+    const BnPlan p = bn_plan(C, Mg, G, ok ? W : 1);
+    const dim3 grid(p.Sg * G, C);
+    for_elem(dtype, [&](auto te) {
+        using T = typename decltype(te)::type;
+        for_bool(ok, [&](auto v) {
+            constexpr bool VEC = decltype(v)::value;
+            hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, VEC>), grid, dim3(BN_THREADS), 0, s, (const T *)x, (const T *)dz, M,
+                               Mg, p.chunk, p.Sg, G, pre_bias, gamma, beta, save_mean, save_invstd, act, slope, part);
+            hipLaunchKernelGGL((bn_bwd_dx_kernel<T, VEC>), grid, dim3(BN_THREADS), 0, s, (const T *)x, (const T *)dz, M, Mg,
+                               p.chunk, p.Sg, G, pre_bias, gamma, beta, save_mean, save_invstd, act, slope, training, part,
+                               (T *)dx, dgamma, dbeta, dpre_bias);
+        });
+    });
     GRAFP_CHECK_LAUNCH("bn_bwd_reduce_kernel / bn_bwd_dx_kernel");
     return GRAFP_OK;
 }

@@ -2,7 +2,7 @@
 #pragma once
 #include <type_traits>
 
-#include "common.h"
+#include "elemio.h"
 
 namespace grafp {
 
@@ -10,14 +10,8 @@ typedef short gm_bf16x8 __attribute__((ext_vector_type(8)));
 typedef short gm_s16x4 __attribute__((ext_vector_type(4)));
 typedef float gm_f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned gm_u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 gm_bf16x2 __attribute__((ext_vector_type(2)));
 typedef const void __attribute__((address_space(1))) *gm_gptr;
 typedef void __attribute__((address_space(3))) *gm_lptr;
-
-__device__ __forceinline__ unsigned gm_pack_bf16(float a, float b) {
-    const gm_f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, gm_bf16x2));   // v_cvt_pk_bf16_f32 (RNE)
-}
 
 // One LDS-DMA instruction: 64 lanes x 16 bytes from per-lane global addresses to LDS [lds_base + lane * 16).  Issued
 // through inline asm ON PURPOSE: hipcc's wait-count pass treats every ds_read after a builtin LDS-DMA as a possible

@@ -25,9 +25,8 @@
 // (k & 3) on the DMA source side and on the read side (conflict-free: a 32-lane pass reads 4 rows x 64 B).
 // The W tile rows are 64 B; their 16-byte slots are swizzled by (r >> 2) & 3 the same way (ds_read_b128).
 #define GRAFP_STORE_FAMILY 2        // (common.h: GRAFP_ST_NT experiment builds)
-#include "common.h"
 #include "dma_ring.h"
-#include "tuning.h"
+#include "elemio.h"
 
 namespace grafp {
 
@@ -379,12 +378,12 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::NW == 4 ? 2 : 1) void conv1x1_ge
                     gm_u32x4 w = __builtin_bit_cast(gm_u32x4, xa[mi]);
 #pragma unroll
                     for (int d = 0; d < 4; ++d) {
-                        float lo = __uint_as_float(w[d] << 16), hi = __uint_as_float(w[d] & 0xffff0000u);
+                        float lo = bf16_lo(w[d]), hi = bf16_hi(w[d]);
                         lo = __builtin_fmaf(lo, t4[d].x, t4[d].y);
                         hi = __builtin_fmaf(hi, t4[d].z, t4[d].w);
                         if (pro_act == 1) { lo = fmaxf(lo, 0.f); hi = fmaxf(hi, 0.f); }
                         else if (pro_act == 2) { lo = lo > 0.f ? lo : lo * pro_slope; hi = hi > 0.f ? hi : hi * pro_slope; }
-                        w[d] = gm_pack_bf16(lo, hi);
+                        w[d] = pack_bf16(lo, hi);
                     }
                     xa[mi] = __builtin_bit_cast(gm_bf16x8, w);
                 }
@@ -422,8 +421,8 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::NW == 4 ? 2 : 1) void conv1x1_ge
                 } else if (rt_valid[ri]) {
                     if (STATS && tile == 0) {
                         // shift = the row's first rounded output of this wave (lane l31 of the lower half holds it)
-                        const unsigned pk = gm_pack_bf16(acc[0][ri][0], 0.f);
-                        sShift[ri] = __shfl(__uint_as_float(pk << 16), l31);
+                        const unsigned pk = pack_bf16(acc[0][ri][0], 0.f);
+                        sShift[ri] = __shfl(bf16_lo(pk), l31);
                     }
                     // the shift as a REAL register pair, made once per row tile.  Left to itself hipcc keeps the RT shifts in
                     // adjacent registers and splats by operand selection (v_pk_add_f32 d, a, v[72:73] op_sel:[0,1] neg_lo
@@ -438,26 +437,26 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::NW == 4 ? 2 : 1) void conv1x1_ge
                     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
                         for (int rg = 0; rg < 4; ++rg) {
-                            unsigned p0 = gm_pack_bf16(acc[mi][ri][4 * rg + 0], acc[mi][ri][4 * rg + 1]);
-                            unsigned p1 = gm_pack_bf16(acc[mi][ri][4 * rg + 2], acc[mi][ri][4 * rg + 3]);
+                            unsigned p0 = pack_bf16(acc[mi][ri][4 * rg + 0], acc[mi][ri][4 * rg + 1]);
+                            unsigned p1 = pack_bf16(acc[mi][ri][4 * rg + 2], acc[mi][ri][4 * rg + 3]);
                             if (EPI) {
-                                float v[4] = {__uint_as_float(p0 << 16), __uint_as_float(p0 & 0xffff0000u),
-                                              __uint_as_float(p1 << 16), __uint_as_float(p1 & 0xffff0000u)};
+                                float v[4] = {bf16_lo(p0), bf16_hi(p0),
+                                              bf16_lo(p1), bf16_hi(p1)};
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) {
                                     v[e] = __builtin_fmaf(v[e], esc[ri].x, esc[ri].y);
                                     if (epi_act == 1) v[e] = fmaxf(v[e], 0.f);
                                     else if (epi_act == 2) v[e] = v[e] > 0.f ? v[e] : v[e] * epi_slope;
                                 }
-                                p0 = gm_pack_bf16(v[0], v[1]);
-                                p1 = gm_pack_bf16(v[2], v[3]);
+                                p0 = pack_bf16(v[0], v[1]);
+                                p1 = pack_bf16(v[2], v[3]);
                             }
                             if (STATS) {
                                 // two elements per VALU instruction (v_pk_add_f32 / v_pk_fma_f32): the statistics
                                 // are VALU work the MFMAs wait for -- 4 instructions per output element cost as
                                 // much as the products themselves at K = 128
-                                const gm_f32x2 da = gm_f32x2{__uint_as_float(p0 << 16), __uint_as_float(p0 & 0xffff0000u)} - sh;
-                                const gm_f32x2 db = gm_f32x2{__uint_as_float(p1 << 16), __uint_as_float(p1 & 0xffff0000u)} - sh;
+                                const gm_f32x2 da = gm_f32x2{bf16_lo(p0), bf16_hi(p0)} - sh;
+                                const gm_f32x2 db = gm_f32x2{bf16_lo(p1), bf16_hi(p1)} - sh;
                                 sS[ri] += da;
                                 sQ[ri] = __builtin_elementwise_fma(da, da, sQ[ri]);
                                 sS[ri] += db;
@@ -718,17 +717,18 @@ __global__ __launch_bounds__(256) void bn_affine_bf16_kernel(const unsigned shor
         unsigned o[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            float a = __builtin_fmaf(__uint_as_float(w[e] << 16), ss.x, ss.y);
-            float b = __builtin_fmaf(__uint_as_float(w[e] & 0xffff0000u), ss.x, ss.y);
+            float a = __builtin_fmaf(bf16_lo(w[e]), ss.x, ss.y);
+            float b = __builtin_fmaf(bf16_hi(w[e]), ss.x, ss.y);
             if (act == 1) { a = fmaxf(a, 0.f); b = fmaxf(b, 0.f); }
             else if (act == 2) { a = a > 0.f ? a : a * slope; b = b > 0.f ? b : b * slope; }
-            if (rrow) { a += __uint_as_float(q[e] << 16); b += __uint_as_float(q[e] & 0xffff0000u); }
-            o[e] = gm_pack_bf16(a, b);
+            if (rrow) { a += bf16_lo(q[e]); b += bf16_hi(q[e]); }
+            o[e] = pack_bf16(a, b);
         }
-        typedef unsigned u4 __attribute__((ext_vector_type(4)));
-        const u4 t = {o[0], o[1], o[2], o[3]};
-        if (plain) store16_hint(dst, __builtin_bit_cast(st_u32x4, t), true);      // (wave-uniform: bn_affine_launch)
-        else GRAFP_ST_NT(t, reinterpret_cast<u4 *>(dst));
+        // the two arms of ElemIO::store, spelled here: the pairs are narrowed inside the loop's own control flow, and routed
+        // through the shared function hipcc 7.2 lays this kernel's scalar branches out differently
+        const st_u32x4 t = {o[0], o[1], o[2], o[3]};
+        if (plain) store16_hint(dst, t, true);      // (wave-uniform: bn_affine_launch)
+        else GRAFP_ST_NT(t, reinterpret_cast<st_u32x4 *>(dst));
     };
     while (full) {
 #pragma unroll
@@ -932,17 +932,18 @@ __global__ __launch_bounds__(256) void split_planes_kernel(const float *__restri
                                                            unsigned short *__restrict__ hi, unsigned short *__restrict__ lo) {
     const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8;
     if (i >= n) return;
-    const float4 a = *reinterpret_cast<const float4 *>(x + i), b = *reinterpret_cast<const float4 *>(x + i + 4);
-    const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    unsigned h[4], l[4];
+    float v[8], r[8];
+    ElemIO<float>::load(x + i, reinterpret_cast<float (&)[4]>(v[0]));
+    ElemIO<float>::load(x + i + 4, reinterpret_cast<float (&)[4]>(v[4]));
+    unsigned h[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        h[e] = gm_pack_bf16(v[2 * e], v[2 * e + 1]);
-        const float r0 = v[2 * e] - __uint_as_float(h[e] << 16), r1 = v[2 * e + 1] - __uint_as_float(h[e] & 0xffff0000u);
-        l[e] = gm_pack_bf16(r0, r1);
+        h[e] = pack_bf16(v[2 * e], v[2 * e + 1]);
+        r[2 * e] = v[2 * e] - bf16_lo(h[e]);
+        r[2 * e + 1] = v[2 * e + 1] - bf16_hi(h[e]);
     }
     *reinterpret_cast<uint4 *>(hi + i) = make_uint4(h[0], h[1], h[2], h[3]);
-    *reinterpret_cast<uint4 *>(lo + i) = make_uint4(l[0], l[1], l[2], l[3]);
+    ElemIO<unsigned short>::store(lo + i, r, true);
 }
 }  // namespace grafp
 
@@ -1023,13 +1024,13 @@ static int bn_affine_launch(const void *y, int C, int64_t M, int views, const fl
     chunk = (chunk + 7) / 8 * 8;
     chunks_view = (int)((Mg + chunk - 1) / chunk);
     const dim3 grid(chunks_view * views, C);
-    // store hint by the bytes written, as for the BatchNorm backward (bn.hip: bn_plain_stores): the normalised activation
+    // store hint by the bytes written (plain_stores, elemio.h), as for the BatchNorm backward: the normalised activation
     // is the operand of the next launches (graph build, max-relative, product).  Until round 6 these were streaming
     // stores like the products' (where they ARE worth 10-15 %); the whole-step A/B (tools/step_env_graph_ab.py,
     // profiles/r06_e_affine_plain_threshold*.txt; tensors up to 70 / 140 / 280 MB / all plain) says otherwise for this
     // kernel at every size: 128 pairs -1.4 / -1.8 / -1.8 %, 256 pairs -1.4 / -1.2 / -1.7 %, 512 pairs 0 / -0.8 / -1.0
     // / -0.9 %, 1024 pairs -0.1 (280 MB) ... -0.3 % (all) -- plain everywhere (the knob stays for measurement builds)
-    const int plain = (size_t)C * (size_t)M * 2 <= ((size_t)GRAFP_TUNE_INT("GRAFP_AFFINE_PLAIN_MAX_MB", 1 << 20) << 20) ? 1 : 0;
+    const int plain = plain_stores((size_t)C * (size_t)M * 2, "GRAFP_AFFINE_PLAIN_MAX_MB", 1 << 20);
     if (st)
         hipLaunchKernelGGL(bn_affine_bf16_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned short *)y,
                            M, Mg, views, chunks_view, chunk, (const float2 *)nullptr, *st,

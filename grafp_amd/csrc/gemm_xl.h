@@ -249,8 +249,8 @@ __global__ __launch_bounds__(GemmXL::THREADS, 1) void conv1x1_gemm_xl_kernel(
                 sh2 = gm_f32x2{sShift[ri], sShift[ri]};
                 asm volatile("" : "+v"(sh2));                  // a real register pair (see conv1x1_gemm_kernel)
             }
-            const gm_f32x2 da = gm_f32x2{__uint_as_float(p0 << 16), __uint_as_float(p0 & 0xffff0000u)} - sh2;
-            const gm_f32x2 db = gm_f32x2{__uint_as_float(p1 << 16), __uint_as_float(p1 & 0xffff0000u)} - sh2;
+            const gm_f32x2 da = gm_f32x2{bf16_lo(p0), bf16_hi(p0)} - sh2;
+            const gm_f32x2 db = gm_f32x2{bf16_lo(p1), bf16_hi(p1)} - sh2;
             sS[ri] += da;
             sQ[ri] = __builtin_elementwise_fma(da, da, sQ[ri]);
             sS[ri] += db;
@@ -402,7 +402,7 @@ __global__ __launch_bounds__(GemmXL::THREADS, 1) void conv1x1_gemm_xl_kernel(
                 xl_acc_pack4<ri * MT + mi, rg>(pk[ri][G][0], pk[ri][G][1]);
             });
             if (STATS && tile == 0)      // shift = the row's first rounded output of this wave (lane l31 of the lower half)
-                sShift[ri] = __shfl(__uint_as_float(pk[ri][0][0] << 16), l31);
+                sShift[ri] = __shfl(bf16_lo(pk[ri][0][0]), l31);
         });
         pend_mcol = col0 + (int64_t)tile * TN + wm * 128;
     };

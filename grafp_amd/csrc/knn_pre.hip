@@ -33,12 +33,6 @@ constexpr float KP_SLACK = 0.008f;
 constexpr int KP_TILE_BYTES = KNN_TR * KP_KC * 2;                        // 16 KB
 constexpr int KP_LDS_BYTES = 4 * KP_TILE_BYTES + 256 * KP_CAP * 2 + 64;  // A[2] | B[2] | lists | reductions
 
-__device__ __forceinline__ unsigned short kp_bf16_rne(float f) {
-    unsigned int u = __float_as_uint(f);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-
 // ---- pass 0: channel-L2 normalisation (torch_edge.py:281), squared norms, node-major f32 + bf16 rows -----------------
 // One thread per node for the arithmetic (the oracle's c-ascending chains); 32-channel slabs go through an LDS
 // transpose so that the node-major rows are written in 128-byte (f32) / 64-byte (bf16) pieces: the quotient pass
@@ -84,8 +78,8 @@ __global__ __launch_bounds__(256) void knn_normalize_rows_kernel(const T *__rest
                 u32x4 w;
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    w[e] = (unsigned)kp_bf16_rne(tile[node][p * 8 + 2 * e]) |
-                           ((unsigned)kp_bf16_rne(tile[node][p * 8 + 2 * e + 1]) << 16);
+                    w[e] = (unsigned)f32_to_bf16(tile[node][p * 8 + 2 * e]) |
+                           ((unsigned)f32_to_bf16(tile[node][p * 8 + 2 * e + 1]) << 16);
                 *reinterpret_cast<u32x4 *>(oh + (size_t)node * C + p * 8) = w;
             }
         }

@@ -43,8 +43,8 @@
 
 #include <type_traits>
 
-#include "common.h"
 #include "dma_ring.h"
+#include "elemio.h"
 #include "topk.h"
 #include "tuning.h"
 
@@ -446,16 +446,10 @@ __global__ __launch_bounds__(256) void search_thr_pre_kernel(const float *__rest
 
 constexpr int SB_WGS_NQS2 = 2;      // workgroups per CU of the two-query-set form (three: 168 registers, 16-21 dwords spilled, same time)
 
-__device__ __forceinline__ unsigned short f32_to_bf16_rne(float f) {
-    unsigned int u = __float_as_uint(f);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-
 __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float *__restrict__ src, int64_t n,
                                                           unsigned short *__restrict__ dst) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-        dst[i] = f32_to_bf16_rne(src[i]);
+        dst[i] = f32_to_bf16(src[i]);
 }
 
 // query operand of the bf16 MFMA: lane (l31, half) holds dims 16 s + 8 half + 0..7 of query l31, s = 0..7
@@ -475,7 +469,7 @@ __device__ __forceinline__ void load_queries_bf16(const float *__restrict__ q, i
     for (int s = 0; s < 8; ++s)
 #pragma unroll
         for (int e = 0; e < 8; ++e)
-            bq[s][e] = qvalid ? (short)f32_to_bf16_rne(raw[2 * s + (e >> 2)][e & 3] * scale) : (short)0;
+            bq[s][e] = qvalid ? (short)f32_to_bf16(raw[2 * s + (e >> 2)][e & 3] * scale) : (short)0;
 }
 
 // Tiles of SB_TR bf16 rows through a ring of SB_NS LDS stages, filled by LDS-DMA (no registers, no LDS-write phase):

@@ -23,6 +23,7 @@
 //   m(C) = 2 e_g(C) + 2^-23 C + 1e-6         (C = 64: 7.7e-5, C = 512: 4.5e-4; typical errors are 10-30 x smaller)
 // The constant 2^-10 keeps every d~ positive (m < 2^-10 is checked), so the keys order as unsigned integers.
 #include "dma_ring.h"
+#include "elemio.h"
 #include "knngraph.h"
 #include "tuning.h"
 
@@ -54,10 +55,10 @@ __global__ __launch_bounds__(256) void knn_normalize_split_kernel(const T *__res
     const size_t o = (size_t)b * C * N + n;
     const float den = knn_node_den(xb, sc, C);
     sq[(size_t)b * N + n] = knn_node_quotients(xb, sc, C, 1, den, [&](int c, float v) {
-        const unsigned h = gm_pack_bf16(v, 0.0f) & 0xffffu;
-        const float r = v - __uint_as_float(h << 16);                 // exact
+        const unsigned h = pack_bf16(v, 0.0f) & 0xffffu;
+        const float r = v - bf16_lo(h);                 // exact
         xh[o + (size_t)c * N] = (unsigned short)h;
-        xl[o + (size_t)c * N] = (unsigned short)(gm_pack_bf16(r, 0.0f) & 0xffffu);
+        xl[o + (size_t)c * N] = (unsigned short)(pack_bf16(r, 0.0f) & 0xffffu);
     });
     den_out[(size_t)b * N + n] = den;
 }
@@ -332,7 +333,7 @@ __global__ __launch_bounds__(256) void knn_norms_kernel(const unsigned short *__
         for (int j = 0; j < 8; ++j)
 #pragma unroll
             for (int e = 0; e < VE / 2; ++e) {
-                const float lo = __uint_as_float(w[j][e] << 16), hi = __uint_as_float(w[j][e] & 0xffff0000u);
+                const float lo = bf16_lo(w[j][e]), hi = bf16_hi(w[j][e]);
                 ss[2 * e] = __builtin_fmaf(lo, lo, ss[2 * e]);
                 ss[2 * e + 1] = __builtin_fmaf(hi, hi, ss[2 * e + 1]);
             }
@@ -350,8 +351,8 @@ __global__ __launch_bounds__(256) void knn_norms_kernel(const unsigned short *__
         for (int j = 0; j < 8; ++j)
 #pragma unroll
             for (int e = 0; e < VE / 2; ++e) {
-                const float lo = __fdiv_rn(__uint_as_float(w[j][e] << 16), den[2 * e]);
-                const float hi = __fdiv_rn(__uint_as_float(w[j][e] & 0xffff0000u), den[2 * e + 1]);
+                const float lo = __fdiv_rn(bf16_lo(w[j][e]), den[2 * e]);
+                const float hi = __fdiv_rn(bf16_hi(w[j][e]), den[2 * e + 1]);
                 q[2 * e] = __builtin_fmaf(lo, lo, q[2 * e]);
                 q[2 * e + 1] = __builtin_fmaf(hi, hi, q[2 * e + 1]);
             }

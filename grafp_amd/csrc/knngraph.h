@@ -14,16 +14,12 @@
 #pragma once
 #include <math.h>
 
-#include "common.h"
+#include "elemio.h"
 
 namespace grafp {
 
 constexpr int KNN_TQ = 128;  // query nodes per workgroup (32 per wave)
 constexpr int KNN_TR = 128;  // candidate nodes per block
-
-// widening load: f32, or bf16 as its f32 value
-__device__ __forceinline__ float ld_as_f32(const float *p) { return *p; }
-__device__ __forceinline__ float ld_as_f32(const unsigned short *p) { return __uint_as_float(((unsigned)*p) << 16); }
 
 // Where a thread of a 256-thread scan workgroup stands: clip b, first query q0 of the workgroup's tile (XCD-remapped),
 // and the lane's place in its wave.  A lane's query is q0 + wave * 32 + l31; its half-wave sees the candidate rows

@@ -13,8 +13,7 @@
 #include <math.h>
 
 #define GRAFP_STORE_FAMILY 3        // (common.h: GRAFP_ST_NT experiment builds)
-#include "common.h"
-#include "tuning.h"
+#include "elemio.h"
 
 namespace grafp {
 
@@ -24,58 +23,10 @@ __device__ __forceinline__ int clampi(int64_t v, int n) {
     return v < 0 ? 0 : (v >= n ? n - 1 : (int)v);
 }
 
-// f32 / bf16 element access (bf16 carried as unsigned short; round-to-nearest-even on store)
-__device__ __forceinline__ float mr_ld(const float *p) { return *p; }
-__device__ __forceinline__ float mr_ld(const unsigned short *p) { return __uint_as_float(((unsigned)*p) << 16); }
-__device__ __forceinline__ void mr_st(float *p, float v) { *p = v; }
-__device__ __forceinline__ void mr_st(unsigned short *p, float v) {
-    unsigned u = __float_as_uint(v);
-    if ((u & 0x7fffffffu) > 0x7f800000u) { *p = (unsigned short)((u >> 16) | 0x40); return; }   // NaN stays NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    *p = (unsigned short)(u >> 16);
-}
-
-// 4-wide access (16 B of f32 / 8 B of bf16); callers guarantee 4-element alignment of the address
-__device__ __forceinline__ void mr_ld4(const float *p, float (&v)[4]) {
-    const float4 t = *reinterpret_cast<const float4 *>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-}
-__device__ __forceinline__ void mr_ld4(const unsigned short *p, float (&v)[4]) {
-    const uint2 t = *reinterpret_cast<const uint2 *>(p);
-    v[0] = __uint_as_float(t.x << 16); v[1] = __uint_as_float(t.x & 0xffff0000u);
-    v[2] = __uint_as_float(t.y << 16); v[3] = __uint_as_float(t.y & 0xffff0000u);
-}
-// a 4-element piece as it is loaded (what waits in registers while further slabs are in flight)
-template <typename T> struct MrRaw;
-template <> struct MrRaw<float> { typedef float4 type; static constexpr int NPAR = 2; };
-template <> struct MrRaw<unsigned short> { typedef uint2 type; static constexpr int NPAR = 4; };
-__device__ __forceinline__ void mr_unpack4(const float4 &t, float (&v)[4]) { v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-__device__ __forceinline__ void mr_unpack4(const uint2 &t, float (&v)[4]) {
-    v[0] = __uint_as_float(t.x << 16); v[1] = __uint_as_float(t.x & 0xffff0000u);
-    v[2] = __uint_as_float(t.y << 16); v[3] = __uint_as_float(t.y & 0xffff0000u);
-}
-__device__ __forceinline__ unsigned mr_pack(float lo, float hi) {
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    const f2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, b2));      // v_cvt_pk_bf16_f32: RNE, NaN stays NaN
-}
-// (outputs are streamed with the non-temporal hint: +35-65 % on a plain copy of tensors this size, tools/microbench/copy_bench.hip)
-// ... and with PLAIN stores when the result fits the Infinity Cache beside its reader's other operand (`plain`, wave-uniform:
-// mr_plain_stores below; same-box A/B of the whole step, profiles/r06_c_*, r06_d_*: -0.5 % at 128 and 256 pairs, +0.5 % at
-// 512 and 1024)
-__device__ __forceinline__ void mr_st4(float *p, const float (&v)[4], bool plain = false) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    const f4 t = {v[0], v[1], v[2], v[3]};
-    if (plain) store16_hint(p, __builtin_bit_cast(st_u32x4, t), true);
-    else GRAFP_ST_NT(t, reinterpret_cast<f4 *>(p));
-}
-__device__ __forceinline__ void mr_st4(unsigned short *p, const float (&v)[4], bool plain = false) {
-    typedef unsigned u2 __attribute__((ext_vector_type(2)));
-    const u2 t = {mr_pack(v[0], v[1]), mr_pack(v[2], v[3])};
-    if (plain) store8_hint(p, __builtin_bit_cast(st_u32x2, t), true);
-    else GRAFP_ST_NT(t, reinterpret_cast<u2 *>(p));
-}
+// What is specific to max-relative in the element access of elemio.h: how many slabs of raw pieces a thread keeps in flight
+// (the same bytes for both element types).  Outputs are streamed, or stored plain when the result fits the Infinity Cache
+// beside its reader's other operand (plain_stores, "GRAFP_MR_PLAIN_MAX_MB").
+template <typename T> constexpr int MR_NPAR = sizeof(T) == 4 ? 2 : 4;
 
 // The backward scatter accumulates in 64-bit FIXED POINT with integer LDS atomics (ds_add_f32 runs at 0.33 lane-ops per
 // clock per CU on gfx950, ds_add_u64 at 10: tools/microbench/lds_atomic_bench.hip; and the sum no longer depends on the
@@ -143,7 +94,7 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_fwd_kernel(const T *__restr
         MR_WALK(V, tid, N, c, n);
         while (c < cc) {
             float v[4];
-            if (V == 4) mr_ld4(xb + (size_t)c * x_sc + n, v); else v[0] = mr_ld(xb + (size_t)c * x_sc + n);
+            if (V == 4) ElemIO<T>::load(xb + (size_t)c * x_sc + n, v); else v[0] = ld_as_f32(xb + (size_t)c * x_sc + n);
 #pragma unroll
             for (int e = 0; e < V; ++e) rows[c * N + n + e] = v[e];
             MR_NEXT(V, N, c, n);
@@ -166,11 +117,11 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_fwd_kernel(const T *__restr
 #pragma unroll
             for (int e = 0; e < V; ++e) m[e] = fmaxf(m[e], row[sidx[k * N + n + e]] - xi[e]);
         if (V == 4) {
-            mr_st4(ob + (size_t)(2 * c) * o_sc + n, xi);
-            mr_st4(ob + (size_t)(2 * c + 1) * o_sc + n, m);
+            ElemIO<T>::store(ob + (size_t)(2 * c) * o_sc + n, xi, false);
+            ElemIO<T>::store(ob + (size_t)(2 * c + 1) * o_sc + n, m, false);
         } else {
-            mr_st(ob + (size_t)(2 * c) * o_sc + n, xi[0]);
-            mr_st(ob + (size_t)(2 * c + 1) * o_sc + n, m[0]);
+            ElemIO<T>::st1(ob + (size_t)(2 * c) * o_sc + n, xi[0]);
+            ElemIO<T>::st1(ob + (size_t)(2 * c + 1) * o_sc + n, m[0]);
         }
         MR_NEXT(V, N, c, n);
     }
@@ -212,8 +163,8 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_fwd_p_kernel(const T *__res
     // in flight / HBM latency (~3.5 us under load) is what the kernel ran at (3.5 TB/s).  The pieces wait in registers
     // as they were loaded (bf16: 8 bytes per piece instead of four floats), so the same 32 registers hold FOUR slabs of
     // bf16 -- all a workgroup has with the usual 16 slabs per clip -- or two of f32.
-    typedef typename MrRaw<T>::type Raw;
-    constexpr int NPAR = MrRaw<T>::NPAR;
+    typedef typename ElemIO<T>::Raw4 Raw;
+    constexpr int NPAR = MR_NPAR<T>;
     Raw pv[NPAR][MRP_ITEMS];
     auto fetch = [&](int par, int slab) {
         const int c0 = slab * CC, cc = min(CC, C - c0);
@@ -235,7 +186,7 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_fwd_p_kernel(const T *__res
                 __syncthreads();                   // previous slab fully consumed (and sidx staged, first time round)
                 float xi[MRP_ITEMS][4];
 #pragma unroll
-                for (int it = 0; it < MRP_ITEMS; ++it) mr_unpack4(pv[par][it], xi[it]);
+                for (int it = 0; it < MRP_ITEMS; ++it) ElemIO<T>::unpack(pv[par][it], xi[it]);
 #pragma unroll
                 for (int it = 0; it < MRP_ITEMS; ++it)
                     if (pc[it] < cc)                   // one 16-byte LDS write per piece (N % 4 == 0: aligned)
@@ -265,8 +216,8 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_fwd_p_kernel(const T *__res
                         }
                         if (WK) arg[((size_t)b * C + c0 + pc[it]) * (N / 4) + pn[it] / 4] = (unsigned char)bk;
                         T *o = ob + (size_t)(2 * (c0 + pc[it])) * o_sc + pn[it];
-                        mr_st4(o, xi[it], plain != 0);
-                        mr_st4(o + o_sc, m, plain != 0);
+                        ElemIO<T>::store(o, xi[it], plain != 0);
+                        ElemIO<T>::store(o + o_sc, m, plain != 0);
                     }
                 }
                 slab += G;
@@ -307,13 +258,13 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_bwd_kernel(const T *__restr
             if (c < cc) {
                 float v[4], ge[4];
                 if (V == 4) {
-                    mr_ld4(xb + (size_t)c * x_sc + n, v);
-                    mr_ld4(gb + (size_t)(2 * c) * g_sc + n, ge);
-                    mr_ld4(gb + (size_t)(2 * c + 1) * g_sc + n, godd[it]);
+                    ElemIO<T>::load(xb + (size_t)c * x_sc + n, v);
+                    ElemIO<T>::load(gb + (size_t)(2 * c) * g_sc + n, ge);
+                    ElemIO<T>::load(gb + (size_t)(2 * c + 1) * g_sc + n, godd[it]);
                 } else {
-                    v[0] = mr_ld(xb + (size_t)c * x_sc + n);
-                    ge[0] = mr_ld(gb + (size_t)(2 * c) * g_sc + n);
-                    godd[it][0] = mr_ld(gb + (size_t)(2 * c + 1) * g_sc + n);
+                    v[0] = ld_as_f32(xb + (size_t)c * x_sc + n);
+                    ge[0] = ld_as_f32(gb + (size_t)(2 * c) * g_sc + n);
+                    godd[it][0] = ld_as_f32(gb + (size_t)(2 * c + 1) * g_sc + n);
                 }
 #pragma unroll
                 for (int e = 0; e < V; ++e) {
@@ -366,9 +317,9 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_bwd_kernel(const T *__restr
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 v[e] = poisoned ? NAN : base[c * N + n + e] + mr_fix_decode((unsigned long long)acc[c * N + n + e]) * inv_scale;
-            mr_st4(db + (size_t)c * x_sc + n, v);
+            ElemIO<T>::store(db + (size_t)c * x_sc + n, v, false);
         } else {
-            mr_st(db + (size_t)c * x_sc + n,
+            ElemIO<T>::st1(db + (size_t)c * x_sc + n,
                   poisoned ? NAN : base[c * N + n] + mr_fix_decode((unsigned long long)acc[c * N + n]) * inv_scale);
         }
         MR_NEXT(V, N, c, n);
@@ -413,9 +364,9 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_bwd_p_kernel(const T *__res
         for (int it = 0; it < MRB_ITEMS; ++it)
             if (pc[it] < cc) {
                 const int c = c0 + pc[it];
-                mr_ld4(xb + (size_t)c * x_sc + pn[it], pv[it]);
-                mr_ld4(gb + (size_t)(2 * c) * g_sc + pn[it], pe[it]);
-                mr_ld4(gb + (size_t)(2 * c + 1) * g_sc + pn[it], po[it]);
+                ElemIO<T>::load(xb + (size_t)c * x_sc + pn[it], pv[it]);
+                ElemIO<T>::load(gb + (size_t)(2 * c) * g_sc + pn[it], pe[it]);
+                ElemIO<T>::load(gb + (size_t)(2 * c + 1) * g_sc + pn[it], po[it]);
             }
     };
     int slab = blockIdx.x;
@@ -480,7 +431,7 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_bwd_p_kernel(const T *__res
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     v[e] = poisoned ? NAN : base[it][e] + mr_fix_decode((unsigned long long)acc[pc[it] * N + pn[it] + e]) * inv_scale;
-                mr_st4(db + (size_t)(c0 + pc[it]) * x_sc + pn[it], v);
+                ElemIO<T>::store(db + (size_t)(c0 + pc[it]) * x_sc + pn[it], v, false);
             }
     }
 }
@@ -529,8 +480,8 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_bwd_a_kernel(const unsigned
     const int64_t ge_step = 2 * cstep * g_sc, dx_step = cstep * d_sc, ar_step = cstep * (N / 4);
     // g_even, g_odd of the slabs in flight, as loaded (bf16: four slabs in the registers two took unpacked; see
     // mrconv_fwd_p_kernel -- the kernel runs at bytes in flight / latency)
-    typedef typename MrRaw<T>::type Raw;
-    constexpr int NPAR = MrRaw<T>::NPAR;
+    typedef typename ElemIO<T>::Raw4 Raw;
+    constexpr int NPAR = MR_NPAR<T>;
     Raw pe[NPAR][MRB_ITEMS], po[NPAR][MRB_ITEMS];
     unsigned pa[NPAR][MRB_ITEMS];
     auto fetch = [&](int par, int slab) {                          // slabs are fetched in order, each G after the last
@@ -568,8 +519,8 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_bwd_a_kernel(const unsigned
                         *reinterpret_cast<uint4 *>(acc + off[it]) = make_uint4(0, 0, 0, 0);
                         *reinterpret_cast<uint4 *>(acc + off[it] + 2) = make_uint4(0, 0, 0, 0);
                         float ge[4];
-                        mr_unpack4(pe[par][it], ge);
-                        mr_unpack4(po[par][it], godd[it]);
+                        ElemIO<T>::unpack(pe[par][it], ge);
+                        ElemIO<T>::unpack(po[par][it], godd[it]);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             base[it][e] = ge[e] - godd[it][e];               // identity branch minus the centre terms
@@ -615,7 +566,7 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_bwd_a_kernel(const unsigned
                                                          ((unsigned long long)a23.w << 32) | a23.z};
 #pragma unroll
                         for (int e = 0; e < 4; ++e) v[e] = poisoned ? NAN : base[it][e] + mr_fix_decode(a[e]) * inv_scale;
-                        mr_st4(dx_p[it], v, plain != 0);
+                        ElemIO<T>::store(dx_p[it], v, plain != 0);
                     }
                     dx_p[it] += dx_step;
                 }
@@ -625,9 +576,18 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_bwd_a_kernel(const unsigned
     }
 }
 
-// the store hint of the training-path kernels: a pure function of the bytes they write (see mr_st4)
-static int mr_plain_stores(size_t bytes) {
-    return bytes <= ((size_t)GRAFP_TUNE_INT("GRAFP_MR_PLAIN_MAX_MB", 140) << 20) ? 1 : 0;    // profiles/r06_e_mr_plain_threshold.txt
+// the persistent kernels' launch plan: whole channel rows per slab (ccp of them), nslab slabs per clip shared among per_clip
+// workgroups -- 4 per clip, more while the grid has fewer than 1024 workgroups
+struct MrPersistPlan {
+    int ccp, nslab, per_clip;
+};
+static MrPersistPlan mr_persist_plan(int slab, int C, int N, int B) {
+    MrPersistPlan p;
+    p.ccp = slab / N < C ? slab / N : C;
+    p.nslab = (C + p.ccp - 1) / p.ccp;
+    p.per_clip = p.nslab < 4 ? p.nslab : 4;
+    while ((int64_t)p.per_clip * B < 1024 && p.per_clip < p.nslab) ++p.per_clip;
+    return p;
 }
 
 static int pick_cc(int C, int N, int target_elems) {
@@ -666,41 +626,35 @@ static int mrconv_fwd_impl(const void *x, int dtype, int64_t x_sb, int64_t x_sc,
                     ((uintptr_t)x % (4 * es) == 0) && ((uintptr_t)out % (4 * es) == 0);
     if (v4 && N <= MRP_SLAB) {
         // persistent variant: whole channel rows per slab, a few slabs per workgroup
-        const int ccp = MRP_SLAB / N < C ? MRP_SLAB / N : C;
-        const int nslab = (C + ccp - 1) / ccp;
-        int per_clip = nslab < 4 ? nslab : 4;                       // workgroups per clip
-        while ((int64_t)per_clip * B < 1024 && per_clip < nslab) ++per_clip;
+        const MrPersistPlan pp = mr_persist_plan(MRP_SLAB, C, N, B);
         const size_t ldsp = ((size_t)MRP_SLAB + (size_t)K * N) * 4;
         if (ldsp <= 160 * 1024) {
-            const dim3 gridp(per_clip, B);
-            const int plain = mr_plain_stores((size_t)2 * B * C * N * es);
-#define MR_FWDP_W(T, I, WK)                                                                                            \
-    (void)hipFuncSetAttribute((const void *)mrconv_fwd_p_kernel<T, I, WK>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              (int)ldsp);                                                                              \
-    hipLaunchKernelGGL((mrconv_fwd_p_kernel<T, I, WK>), gridp, dim3(MR_THREADS), ldsp, (hipStream_t)stream,            \
-                       (const T *)x, x_sb, x_sc, (const I *)idx, (T *)out, o_sb, o_sc, C, N, K, ccp, arg, plain)
-#define MR_FWDP(T, I)                                                                                                  \
-    if (arg) { MR_FWDP_W(T, I, true); } else { MR_FWDP_W(T, I, false); }
-            if (dtype == GRAFP_F32) { if (idx32) { MR_FWDP(float, int32_t); } else { MR_FWDP(float, int64_t); } }
-            else { if (idx32) { MR_FWDP(unsigned short, int32_t); } else { MR_FWDP(unsigned short, int64_t); } }
-#undef MR_FWDP
-#undef MR_FWDP_W
+            const int plain = plain_stores((size_t)2 * B * C * N * es, "GRAFP_MR_PLAIN_MAX_MB", 140);
+            for_elem_idx(dtype, idx32, [&](auto te, auto ti) {
+                using T = typename decltype(te)::type;
+                using I = typename decltype(ti)::type;
+                for_bool(arg != nullptr, [&](auto wk) {
+                    const auto kern = mrconv_fwd_p_kernel<T, I, decltype(wk)::value>;
+                    (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
+                    hipLaunchKernelGGL(kern, dim3(pp.per_clip, B), dim3(MR_THREADS), ldsp, (hipStream_t)stream,
+                                       (const T *)x, x_sb, x_sc, (const I *)idx, (T *)out, o_sb, o_sc, C, N, K, pp.ccp, arg, plain);
+                });
+            });
             GRAFP_CHECK_LAUNCH("mrconv_fwd_p_kernel");
             return GRAFP_OK;
         }
     }
     GRAFP_REQUIRE(!arg, "mrconv_fwd_arg: shape / alignment outside grafp_mrconv_arg_supported");
-#define MR_FWD_I(T, V, I)                                                                                              \
-    (void)hipFuncSetAttribute((const void *)mrconv_fwd_kernel<T, V, I>, hipFuncAttributeMaxDynamicSharedMemorySize,    \
-                              (int)lds);                                                                               \
-    hipLaunchKernelGGL((mrconv_fwd_kernel<T, V, I>), grid, dim3(MR_THREADS), lds, (hipStream_t)stream, (const T *)x,   \
-                       x_sb, x_sc, (const I *)idx, (T *)out, o_sb, o_sc, C, N, K, CC)
-#define MR_FWD(T, V)                                                                                                   \
-    if (idx32) { MR_FWD_I(T, V, int32_t); } else { MR_FWD_I(T, V, int64_t); }
-    if (dtype == GRAFP_F32) { if (v4) { MR_FWD(float, 4); } else { MR_FWD(float, 1); } }
-    else { if (v4) { MR_FWD(unsigned short, 4); } else { MR_FWD(unsigned short, 1); } }
-#undef MR_FWD
-#undef MR_FWD_I
+    for_elem_idx(dtype, idx32, [&](auto te, auto ti) {
+        using T = typename decltype(te)::type;
+        using I = typename decltype(ti)::type;
+        for_bool(v4, [&](auto vec) {
+            const auto kern = mrconv_fwd_kernel<T, decltype(vec)::value ? 4 : 1, I>;
+            (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(kern, grid, dim3(MR_THREADS), lds, (hipStream_t)stream, (const T *)x, x_sb, x_sc,
+                               (const I *)idx, (T *)out, o_sb, o_sc, C, N, K, CC);
+        });
+    });
     GRAFP_CHECK_LAUNCH("mrconv_fwd_kernel");
     return GRAFP_OK;
 }
@@ -716,21 +670,17 @@ static int mrconv_bwd_impl(const void *x, int dtype, int64_t x_sb, int64_t x_sc,
     const bool v4 = (N % 4 == 0) && (x_sb % 4 == 0) && (x_sc % 4 == 0) && (g_sb % 4 == 0) && (g_sc % 4 == 0) &&
                     ((uintptr_t)x % (4 * es) == 0) && ((uintptr_t)grad_out % (4 * es) == 0) && ((uintptr_t)dx % (4 * es) == 0);
     if (v4 && N <= MRB_SLAB) {
-        const int ccp = MRB_SLAB / N < C ? MRB_SLAB / N : C;
-        const int nslab = (C + ccp - 1) / ccp;
-        int per_clip = nslab < 4 ? nslab : 4;
-        while ((int64_t)per_clip * B < 1024 && per_clip < nslab) ++per_clip;
+        const MrPersistPlan pp = mr_persist_plan(MRB_SLAB, C, N, B);
         const size_t ldsp = ((size_t)3 * MRB_SLAB + (size_t)K * N) * 4;      // i64 accumulator + f32 rows + edges
         if (ldsp <= 160 * 1024) {
-            const dim3 gridp(per_clip, B);
-#define MR_BWDP(T, I)                                                                                                  \
-    (void)hipFuncSetAttribute((const void *)mrconv_bwd_p_kernel<T, I>, hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                              (int)ldsp);                                                                              \
-    hipLaunchKernelGGL((mrconv_bwd_p_kernel<T, I>), gridp, dim3(MR_THREADS), ldsp, (hipStream_t)stream, (const T *)x,  \
-                       x_sb, x_sc, (const I *)idx, (const T *)grad_out, g_sb, g_sc, (T *)dx, C, N, K, ccp)
-            if (dtype == GRAFP_F32) { if (idx32) { MR_BWDP(float, int32_t); } else { MR_BWDP(float, int64_t); } }
-            else { if (idx32) { MR_BWDP(unsigned short, int32_t); } else { MR_BWDP(unsigned short, int64_t); } }
-#undef MR_BWDP
+            for_elem_idx(dtype, idx32, [&](auto te, auto ti) {
+                using T = typename decltype(te)::type;
+                using I = typename decltype(ti)::type;
+                const auto kern = mrconv_bwd_p_kernel<T, I>;
+                (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
+                hipLaunchKernelGGL(kern, dim3(pp.per_clip, B), dim3(MR_THREADS), ldsp, (hipStream_t)stream, (const T *)x,
+                                   x_sb, x_sc, (const I *)idx, (const T *)grad_out, g_sb, g_sc, (T *)dx, C, N, K, pp.ccp);
+            });
             GRAFP_CHECK_LAUNCH("mrconv_bwd_p_kernel");
             return GRAFP_OK;
         }
@@ -749,20 +699,18 @@ static int mrconv_bwd_impl(const void *x, int dtype, int64_t x_sb, int64_t x_sc,
     const size_t lds = lds_of(CC);
     GRAFP_REQUIRE(lds <= 160 * 1024, "mrconv_bwd: N=%d K=%d needs %zu B of LDS (> 160 KiB)", N, K, lds);
     const dim3 grid((C + CC - 1) / CC, B);
-#define MR_BWD_II(T, V, I, IT)                                                                                         \
-    (void)hipFuncSetAttribute((const void *)mrconv_bwd_kernel<T, V, I, IT>,                                            \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                   \
-    hipLaunchKernelGGL((mrconv_bwd_kernel<T, V, I, IT>), grid, dim3(MR_THREADS), lds, (hipStream_t)stream,             \
-                       (const T *)x, x_sb, x_sc, (const I *)idx, (const T *)grad_out, g_sb, g_sc, (T *)dx, C, N, K, CC)
-#define MR_BWD_I(T, V, I)                                                                                              \
-    if (items == 2) { MR_BWD_II(T, V, I, 2); } else { MR_BWD_II(T, V, I, 8); }
-#define MR_BWD(T, V)                                                                                                   \
-    if (idx32) { MR_BWD_I(T, V, int32_t); } else { MR_BWD_I(T, V, int64_t); }
-    if (dtype == GRAFP_F32) { if (v4) { MR_BWD(float, 4); } else { MR_BWD(float, 1); } }
-    else { if (v4) { MR_BWD(unsigned short, 4); } else { MR_BWD(unsigned short, 1); } }
-#undef MR_BWD
-#undef MR_BWD_I
-#undef MR_BWD_II
+    for_elem_idx(dtype, idx32, [&](auto te, auto ti) {
+        using T = typename decltype(te)::type;
+        using I = typename decltype(ti)::type;
+        for_bool(v4, [&](auto vec) {
+            for_bool(items == 2, [&](auto two) {
+                const auto kern = mrconv_bwd_kernel<T, decltype(vec)::value ? 4 : 1, I, decltype(two)::value ? 2 : 8>;
+                (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                hipLaunchKernelGGL(kern, grid, dim3(MR_THREADS), lds, (hipStream_t)stream, (const T *)x, x_sb, x_sc,
+                                   (const I *)idx, (const T *)grad_out, g_sb, g_sc, (T *)dx, C, N, K, CC);
+            });
+        });
+    });
     GRAFP_CHECK_LAUNCH("mrconv_bwd_kernel");
     return GRAFP_OK;
 }
@@ -809,21 +757,17 @@ extern "C" int grafp_mrconv_bwd_arg(const uint8_t *arg, int dtype, const void *i
     GRAFP_REQUIRE(mrconv_arg_shape_ok(dtype, d_sb, d_sc, g_sb, g_sc, N, K) && (uintptr_t)grad_out % (4 * es) == 0 &&
                       (uintptr_t)dx % (4 * es) == 0,
                   "mrconv_bwd_arg: shape / alignment outside grafp_mrconv_arg_supported (N=%d K=%d)", N, K);
-    const int ccp = MRB_SLAB / N < C ? MRB_SLAB / N : C;
-    const int nslab = (C + ccp - 1) / ccp;
-    int per_clip = nslab < 4 ? nslab : 4;
-    while ((int64_t)per_clip * B < 1024 && per_clip < nslab) ++per_clip;
+    const MrPersistPlan pp = mr_persist_plan(MRB_SLAB, C, N, B);
     const size_t ldsp = (size_t)8 * MRB_SLAB + (size_t)4 * K * N;             // i64 accumulator + edges [K][N]
-    const dim3 gridp(per_clip, B);
-    const int plain = mr_plain_stores((size_t)B * C * N * es);
-#define MR_BWDA(T, I)                                                                                                  \
-    (void)hipFuncSetAttribute((const void *)mrconv_bwd_a_kernel<T, I>, hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                              (int)ldsp);                                                                              \
-    hipLaunchKernelGGL((mrconv_bwd_a_kernel<T, I>), gridp, dim3(MR_THREADS), ldsp, (hipStream_t)stream, arg,           \
-                       (const I *)idx, (const T *)grad_out, g_sb, g_sc, (T *)dx, d_sb, d_sc, C, N, K, ccp, plain)
-    if (dtype == GRAFP_F32) { if (idx_is_i32) { MR_BWDA(float, int32_t); } else { MR_BWDA(float, int64_t); } }
-    else { if (idx_is_i32) { MR_BWDA(unsigned short, int32_t); } else { MR_BWDA(unsigned short, int64_t); } }
-#undef MR_BWDA
+    const int plain = plain_stores((size_t)B * C * N * es, "GRAFP_MR_PLAIN_MAX_MB", 140);
+    for_elem_idx(dtype, idx_is_i32, [&](auto te, auto ti) {
+        using T = typename decltype(te)::type;
+        using I = typename decltype(ti)::type;
+        const auto kern = mrconv_bwd_a_kernel<T, I>;
+        (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
+        hipLaunchKernelGGL(kern, dim3(pp.per_clip, B), dim3(MR_THREADS), ldsp, (hipStream_t)stream, arg, (const I *)idx,
+                           (const T *)grad_out, g_sb, g_sc, (T *)dx, d_sb, d_sc, C, N, K, pp.ccp, plain);
+    });
     GRAFP_CHECK_LAUNCH("mrconv_bwd_a_kernel");
     return GRAFP_OK;
 }

@@ -5,18 +5,9 @@
 // gathered taps  out[t*C + c][b][j] = x[c][b][2j + t - 1]  (zero outside [0, N)).  torch builds that operand with
 // pad + three strided slices + cat (and their backward with zero-filled slice gradients): ~0.4 GB of traffic per
 // Downsample at B = 512.  These two kernels read x once / write the gradient once.
-#include "common.h"
+#include "elemio.h"
 
 namespace grafp {
-
-__device__ __forceinline__ float tp_ld(const float *p) { return *p; }
-__device__ __forceinline__ float tp_ld(const unsigned short *p) { return __uint_as_float(((unsigned)*p) << 16); }
-__device__ __forceinline__ void tp_st(float *p, float v) { *p = v; }
-__device__ __forceinline__ void tp_st(unsigned short *p, float v) {
-    unsigned int u = __float_as_uint(v);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    *p = (unsigned short)(u >> 16);
-}
 
 // rows = C * B contiguous rows of N (x) / n_out (each tap plane); plane stride of out = rows * n_out
 template <typename T>
@@ -44,12 +35,12 @@ __global__ __launch_bounds__(256) void taps_bwd_kernel(const T *__restrict__ g, 
         const T *g0 = g + r * n_out;
         float v;
         if ((n & 1) == 0) {
-            v = tp_ld(g0 + total + (n >> 1));                       // tap 1 of output n/2
+            v = ld_as_f32(g0 + total + (n >> 1));                       // tap 1 of output n/2
         } else {
-            v = tp_ld(g0 + 2 * total + ((n - 1) >> 1));             // tap 2 of output (n-1)/2
-            if (((n + 1) >> 1) < n_out) v += tp_ld(g0 + ((n + 1) >> 1));   // tap 0 of output (n+1)/2
+            v = ld_as_f32(g0 + 2 * total + ((n - 1) >> 1));             // tap 2 of output (n-1)/2
+            if (((n + 1) >> 1) < n_out) v += ld_as_f32(g0 + ((n + 1) >> 1));   // tap 0 of output (n+1)/2
         }
-        tp_st(dx + i, v);
+        ElemIO<T>::st1(dx + i, v);
     }
 }
 
@@ -57,25 +48,11 @@ __global__ __launch_bounds__(256) void taps_bwd_kernel(const T *__restrict__ g, 
 // consecutive inputs / gradient elements of one row (= 4 outputs per tap plane), moves them with 8/16-byte accesses and
 // needs no division per element.  The scalar kernels above issued one 2-byte access and two 64-bit divisions per element
 // (bwd: 118 us where the bytes take ~35).
-template <typename T> struct TpV;
-template <> struct TpV<float> {
-    __device__ static void ld4(const float *p, float (&v)[4]) { const float4 t = *reinterpret_cast<const float4 *>(p); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-    __device__ static void st4(float *p, const float (&v)[4]) { *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]); }
-};
-template <> struct TpV<unsigned short> {
-    __device__ static void ld4(const unsigned short *p, float (&v)[4]) {
-        const uint2 t = *reinterpret_cast<const uint2 *>(p);
-        v[0] = __uint_as_float(t.x << 16); v[1] = __uint_as_float(t.x & 0xffff0000u);
-        v[2] = __uint_as_float(t.y << 16); v[3] = __uint_as_float(t.y & 0xffff0000u);
-    }
-    __device__ static void st4(unsigned short *p, const float (&v)[4]) {
-        unsigned short h[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) tp_st(&h[i], v[i]);
-        *reinterpret_cast<uint2 *>(p) = make_uint2((unsigned)h[0] | ((unsigned)h[1] << 16), (unsigned)h[2] | ((unsigned)h[3] << 16));
-    }
-};
-
+// Their 4-element stores are plain (the GEMM that follows reads them) and written in C++, not through ElemIO::store's inline
+// asm: the compiler then merges the two halves of a bf16 gradient piece into one 16-byte store.
+template <typename T> __device__ __forceinline__ void tp_st4(T *p, const float (&v)[4]) {
+    *reinterpret_cast<typename ElemIO<T>::Raw4 *>(p) = ElemIO<T>::pack(v);
+}
 template <typename T>
 __global__ __launch_bounds__(256) void taps_fwd8_kernel(const T *__restrict__ x, int64_t rows, int N, int n_out,
                                                         T *__restrict__ out) {
@@ -86,14 +63,14 @@ __global__ __launch_bounds__(256) void taps_fwd8_kernel(const T *__restrict__ x,
         const int p = (int)(i - r * per_row), n0 = p << 3, j0 = p << 2;
         const T *xr = x + r * N + n0;
         float a[4], b[4];
-        TpV<T>::ld4(xr, a);
-        TpV<T>::ld4(xr + 4, b);
-        const float prev = n0 > 0 ? tp_ld(xr - 1) : 0.0f;
+        ElemIO<T>::load(xr, a);
+        ElemIO<T>::load(xr + 4, b);
+        const float prev = n0 > 0 ? ld_as_f32(xr - 1) : 0.0f;
         const float t0[4] = {prev, a[1], a[3], b[1]}, t1[4] = {a[0], a[2], b[0], b[2]}, t2[4] = {a[1], a[3], b[1], b[3]};
         T *o = out + r * n_out + j0;
-        TpV<T>::st4(o, t0);
-        TpV<T>::st4(o + total, t1);
-        TpV<T>::st4(o + 2 * total, t2);
+        tp_st4(o, t0);
+        tp_st4(o + total, t1);
+        tp_st4(o + 2 * total, t2);
     }
 }
 
@@ -107,16 +84,16 @@ __global__ __launch_bounds__(256) void taps_bwd8_kernel(const T *__restrict__ g,
         const int p = (int)(i - r * per_row), n0 = p << 3, j0 = p << 2;
         const T *g0 = g + r * n_out + j0;
         float a0[4], a1[4], a2[4];
-        TpV<T>::ld4(g0, a0);                          // tap 0 of outputs j0 .. j0+3
-        TpV<T>::ld4(g0 + total, a1);                  // tap 1
-        TpV<T>::ld4(g0 + 2 * total, a2);              // tap 2
-        const float next0 = j0 + 4 < n_out ? tp_ld(g0 + 4) : 0.0f;      // tap 0 of output j0+4
+        ElemIO<T>::load(g0, a0);                          // tap 0 of outputs j0 .. j0+3
+        ElemIO<T>::load(g0 + total, a1);                  // tap 1
+        ElemIO<T>::load(g0 + 2 * total, a2);              // tap 2
+        const float next0 = j0 + 4 < n_out ? ld_as_f32(g0 + 4) : 0.0f;      // tap 0 of output j0+4
         // even n = 2j: tap 1 of output j;  odd n = 2j+1: tap 2 of output j + tap 0 of output j+1
         const float lo[4] = {a1[0], a2[0] + a0[1], a1[1], a2[1] + a0[2]};
         const float hi[4] = {a1[2], a2[2] + a0[3], a1[3], a2[3] + next0};
         T *d = dx + r * N + n0;
-        TpV<T>::st4(d, lo);
-        TpV<T>::st4(d + 4, hi);
+        tp_st4(d, lo);
+        tp_st4(d + 4, hi);
     }
 }
 
@@ -128,32 +105,27 @@ static int taps_launch(const void *a, void *b, int dtype, int64_t rows, int N, b
     GRAFP_REQUIRE(rows > 0 && N > 0, "stride2_taps: bad shape rows=%lld N=%d", (long long)rows, N);
     GRAFP_REQUIRE(dtype == GRAFP_F32 || dtype == GRAFP_BF16, "stride2_taps: dtype %d not in {f32, bf16}", dtype);
     const int n_out = (N - 1) / 2 + 1;
-    hipStream_t s8 = (hipStream_t)stream;
+    hipStream_t s = (hipStream_t)stream;
     const size_t es = dtype == GRAFP_F32 ? 4 : 2;
     if (N % 8 == 0 && ((uintptr_t)a % (4 * es)) == 0 && ((uintptr_t)b % (4 * es)) == 0) {
         const int64_t pieces = rows * (N / 8), nb8 = (pieces + 255) / 256;
         const dim3 grid8((unsigned)(nb8 < 65536 ? nb8 : 65536));
-        if (dtype == GRAFP_F32) {
-            if (fwd) hipLaunchKernelGGL(taps_fwd8_kernel<float>, grid8, dim3(256), 0, s8, (const float *)a, rows, N, n_out, (float *)b);
-            else hipLaunchKernelGGL(taps_bwd8_kernel<float>, grid8, dim3(256), 0, s8, (const float *)a, rows, N, n_out, (float *)b);
-        } else {
-            if (fwd) hipLaunchKernelGGL(taps_fwd8_kernel<unsigned short>, grid8, dim3(256), 0, s8, (const unsigned short *)a, rows, N, n_out, (unsigned short *)b);
-            else hipLaunchKernelGGL(taps_bwd8_kernel<unsigned short>, grid8, dim3(256), 0, s8, (const unsigned short *)a, rows, N, n_out, (unsigned short *)b);
-        }
+        for_elem(dtype, [&](auto te) {
+            using T = typename decltype(te)::type;
+            hipLaunchKernelGGL(fwd ? taps_fwd8_kernel<T> : taps_bwd8_kernel<T>, grid8, dim3(256), 0, s, (const T *)a, rows, N,
+                               n_out, (T *)b);
+        });
         GRAFP_CHECK_LAUNCH("taps8 kernel");
         return GRAFP_OK;
     }
     const int64_t work = rows * (fwd ? n_out : N);
     const int64_t nb = (work + 255) / 256;
     const dim3 grid((unsigned)(nb < 65536 ? nb : 65536));
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == GRAFP_F32) {
-        if (fwd) hipLaunchKernelGGL(taps_fwd_kernel<float>, grid, dim3(256), 0, s, (const float *)a, rows, N, n_out, (float *)b);
-        else hipLaunchKernelGGL(taps_bwd_kernel<float>, grid, dim3(256), 0, s, (const float *)a, rows, N, n_out, (float *)b);
-    } else {
-        if (fwd) hipLaunchKernelGGL(taps_fwd_kernel<unsigned short>, grid, dim3(256), 0, s, (const unsigned short *)a, rows, N, n_out, (unsigned short *)b);
-        else hipLaunchKernelGGL(taps_bwd_kernel<unsigned short>, grid, dim3(256), 0, s, (const unsigned short *)a, rows, N, n_out, (unsigned short *)b);
-    }
+    for_elem(dtype, [&](auto te) {
+        using T = typename decltype(te)::type;
+        hipLaunchKernelGGL(fwd ? taps_fwd_kernel<T> : taps_bwd_kernel<T>, grid, dim3(256), 0, s, (const T *)a, rows, N, n_out,
+                           (T *)b);
+    });
     GRAFP_CHECK_LAUNCH("taps kernel");
     return GRAFP_OK;
 }

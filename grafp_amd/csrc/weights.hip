@@ -8,8 +8,7 @@
 // kernel per layer (63 launches of ~5 us per step, which is 2-3 % of a 128-pair step); here one workgroup per 32 x 32
 // tile of any layer reads the f32 tile once and writes both copies (the transposed one through LDS).
 // The table is built once by the host (grafp_amd/ops.py: lowp_weights); the identity blocks are written once, too.
-#include "common.h"
-#include "dma_ring.h"
+#include "elemio.h"
 
 namespace grafp {
 
@@ -33,7 +32,7 @@ __global__ __launch_bounds__(256) void weights_prepare_kernel(const WeightEntry 
     for (int i = 0; i < 4; ++i) {
         const int r = r0 + ty + 8 * i;
         const size_t at = ((size_t)g * e.Rg + r) * e.Kg + k0 + tx;
-        const unsigned short b = (unsigned short)(gm_pack_bf16(e.src[at], 0.0f) & 0xffffu);     // round to nearest even
+        const unsigned short b = (unsigned short)(pack_bf16(e.src[at], 0.0f) & 0xffffu);     // round to nearest even
         e.dst[at] = b;
         tile[ty + 8 * i][tx] = b;
     }

@@ -14,9 +14,8 @@
 //     bytes of a G / X row (8 consecutive m), read with ds_read_b128 from rows padded to 272 B (conflict-free);
 //   * partial tiles go to a (S, Cout, Cin/g) f32 scratch, summed by wgrad_reduce_kernel (deterministic, no atomics).
 // HBM-bound: (Cout + Cin) * M * 2 bytes per launch (+ re-reads of the smaller operand across output tiles).
-#include "common.h"
 #include "dma_ring.h"
-#include "tuning.h"
+#include "elemio.h"
 
 namespace grafp {
 
@@ -390,12 +389,12 @@ __global__ __launch_bounds__(CFG::THREADS) void wgrad_dma_kernel(
                     gm_u32x4 w = __builtin_bit_cast(gm_u32x4, bv[b]);
 #pragma unroll
                     for (int d = 0; d < 4; ++d) {
-                        float lo = __uint_as_float(w[d] << 16), hi = __uint_as_float(w[d] & 0xffff0000u);
+                        float lo = bf16_lo(w[d]), hi = bf16_hi(w[d]);
                         lo = __builtin_fmaf(lo, ssb[b].x, ssb[b].y);
                         hi = __builtin_fmaf(hi, ssb[b].x, ssb[b].y);
                         if (pro_act == 1) { lo = fmaxf(lo, 0.f); hi = fmaxf(hi, 0.f); }
                         else if (pro_act == 2) { lo = lo > 0.f ? lo : lo * pro_slope; hi = hi > 0.f ? hi : hi * pro_slope; }
-                        w[d] = gm_pack_bf16(lo, hi);
+                        w[d] = pack_bf16(lo, hi);
                     }
                     bv[b] = __builtin_bit_cast(gm_bf16x8, w);
                 }
