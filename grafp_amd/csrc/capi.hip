@@ -99,6 +99,35 @@ extern "C" int grafp_identify_f32(const float *index_rows, int64_t n, const int6
                                   (hipStream_t)stream);
 }
 
+// Identification against a library held as IVF-PQ codes (identify_pq.hip): argument checks here, the kernels there.
+namespace grafp {
+int identify_pq_launch(const int32_t *list_id, const unsigned char *codes, int64_t n, const float *centroids, int nlist,
+                       const float *codebooks, int M, const int64_t *first, int T, const float *q_rows,
+                       const int64_t *ids, int k, const int64_t *item_row, const int *item_len, int n_items,
+                       int max_len, int top, int min_overlap, int32_t *out_track, int32_t *out_offset, float *out_score,
+                       int32_t *out_votes, hipStream_t stream);
+}  // namespace grafp
+
+extern "C" int grafp_identify_pq_f32(const int32_t *list_id, const uint8_t *codes, int64_t n, const float *centroids,
+                                     int nlist, const float *codebooks, int M, const int64_t *track_first_row,
+                                     int n_tracks, const float *q_rows, int64_t n_qrows, const int64_t *topk_ids, int k,
+                                     const int64_t *item_row, const int *item_len, int n_items, int max_len, int top,
+                                     int min_overlap, int32_t *out_track, int32_t *out_offset, float *out_score,
+                                     int32_t *out_votes, grafp_stream_t stream) {
+    GRAFP_REQUIRE(list_id && codes && centroids && codebooks && track_first_row && q_rows && topk_ids && item_row &&
+                  item_len && out_track && out_offset && out_score && out_votes, "identify_pq: null pointer");
+    GRAFP_REQUIRE(n >= 1 && n < 0x7fffff00ll && nlist >= 1 && n_tracks >= 1 && n_qrows >= 1 && n_items >= 0,
+                  "identify_pq: bad sizes n=%lld nlist=%d n_tracks=%d n_qrows=%lld n_items=%d", (long long)n, nlist,
+                  n_tracks, (long long)n_qrows, n_items);
+    GRAFP_REQUIRE(top >= 1 && top <= 64, "identify_pq: top=%d not in [1, 64]", top);
+    GRAFP_REQUIRE((((uintptr_t)centroids | (uintptr_t)codebooks | (uintptr_t)q_rows) & 15) == 0 &&
+                  (((uintptr_t)codes | (uintptr_t)list_id) & 3) == 0,
+                  "identify_pq: centroids, codebooks and query rows must be 16-byte aligned, codes and list ids 4-byte");
+    return grafp::identify_pq_launch(list_id, codes, n, centroids, nlist, codebooks, M, track_first_row, n_tracks, q_rows,
+                                     topk_ids, k, item_row, item_len, n_items, max_len, top, min_overlap, out_track,
+                                     out_offset, out_score, out_votes, (hipStream_t)stream);
+}
+
 // Shared audio inside a track-indexed library (selfmatch.hip): argument checks here, the kernels and the plan there.
 namespace grafp {
 size_t self_match_workspace(const int64_t *src_rows, int n_src, int k, int min_votes);

@@ -1,0 +1,188 @@
+// identify_core.h -- the one body of the track-aware identification kernels: identify.hip (library rows held as f32) and
+// identify_pq.hip (library rows held as IVF-PQ codes, decoded while they are scored).  What the kernels compute, the LDS
+// layout and the five phases are stated at the top of identify.hip; the arithmetic order of a score at the top of
+// seqmatch.h.  The two kernels differ in ONE thing: where y[t] of the span sum (phase 3) comes from.  That is the Span
+// parameter of identify_item:
+//     float span(const float4 *x, int64_t row, int l, int m)
+// x: lane l's float4 of the first query row of the span, row: the library row that pairs with it, m: pairs (the same in
+// every lane of the half-wave; <= 0: no row is read, the butterfly still runs).  It returns the un-divided span score in
+// span_sum's order.  Rows [row, row + m) lie inside [0, n).
+// Compiles with and without the packed-f32 instructions; both users are built without (Makefile NOPK).
+#pragma once
+#include <limits.h>
+#include <math.h>
+
+#include "common.h"
+#include "seqmatch.h"
+
+namespace grafp {
+
+constexpr int ID_THREADS = 256;
+constexpr int ID_MAX_LEN = 256;
+constexpr int ID_MAX_K = 32;
+constexpr int ID_MAX_KEYS = 8192;
+constexpr int ID_SHIFT = ID_MAX_LEN - 1;                 // a + ID_SHIFT >= 0 for every hit
+constexpr size_t ID_LDS = 160 * 1024 - 256;      // dynamic LDS budget (the static s_ncand sits next to it)
+
+// The launch plan of one identify kernel: slots per item, dynamic LDS bytes, and whether the query rows sit in LDS.
+struct IdentifyPlan {
+    int Pmax;
+    size_t lds;
+    bool q_lds;
+};
+inline IdentifyPlan identify_plan(int max_len, int k) {
+    IdentifyPlan p;
+    p.Pmax = 64;
+    while (p.Pmax < max_len * k) p.Pmax <<= 1;
+    const size_t slots = (size_t)16 * p.Pmax, qbytes = (size_t)max_len * SEQ_D * sizeof(float);
+    p.q_lds = slots + qbytes <= ID_LDS;
+    p.lds = p.q_lds ? slots + qbytes : slots;
+    return p;
+}
+
+// One item by one workgroup of ID_THREADS threads (blockIdx.x = the item).
+template <bool kQLds, typename Span>
+__device__ __forceinline__ void identify_item(
+    const Span &span, int64_t n, const int64_t *__restrict__ first, int T, const float *__restrict__ q_rows,
+    const int64_t *__restrict__ ids, int k, const int64_t *__restrict__ item_row, const int *__restrict__ item_len,
+    int max_len, int Pmax, int top, int min_overlap, int32_t *__restrict__ out_track, int32_t *__restrict__ out_offset,
+    float *__restrict__ out_score, int32_t *__restrict__ out_votes) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char id_smem[];
+    __shared__ int s_ncand;
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(id_smem);
+    unsigned int *aux = reinterpret_cast<unsigned int *>(id_smem + (size_t)8 * Pmax);
+    unsigned short *votes = reinterpret_cast<unsigned short *>(id_smem + (size_t)12 * Pmax);
+    unsigned short *idx = reinterpret_cast<unsigned short *>(id_smem + (size_t)14 * Pmax);
+    float *sq = reinterpret_cast<float *>(id_smem + (size_t)16 * Pmax);
+
+    const int item = blockIdx.x, tid = threadIdx.x;
+    const int64_t r0 = item_row[item];
+    int ql = item_len[item] < max_len ? item_len[item] : max_len;
+    if (ql < 0) ql = 0;
+    const int total = ql * k;
+    int P = 64;
+    while (P < total) P <<= 1;                             // <= Pmax (host: max_len * k <= ID_MAX_KEYS)
+    if (tid == 0) s_ncand = 0;
+    if (kQLds) {
+        const float4 *src = reinterpret_cast<const float4 *>(q_rows + r0 * SEQ_D);
+        float4 *dst = reinterpret_cast<float4 *>(sq);
+        for (int i = tid; i < ql * (SEQ_D / 4); i += ID_THREADS) dst[i] = src[i];
+    }
+    // 1. hit keys; ids outside [0, n) are no hits
+    for (int e = tid; e < P; e += ID_THREADS) {
+        unsigned long long key = SEQ_NONE;
+        if (e < total) {
+            const int s = e / k;
+            const int64_t r = ids[(r0 + s) * k + (e - s * k)];
+            if (r >= 0 && r < n) key = ((unsigned long long)(r - s + ID_SHIFT) << 32) | (unsigned int)s;
+        }
+        keys[e] = key;
+    }
+    __syncthreads();
+    block_sort<ID_THREADS, false>(keys, nullptr, P, tid);
+
+    // 2. one walker per alignment run (P / 256 <= 32 slots per thread: one mask bit each)
+    unsigned int head = 0;
+    for (int e = tid, it = 0; e < P; e += ID_THREADS, ++it) {
+        const unsigned long long key = keys[e];
+        if (key != SEQ_NONE && (e == 0 || (keys[e - 1] >> 32) != (key >> 32))) head |= 1u << it;
+    }
+    __syncthreads();
+    for (int e = tid, it = 0; e < P; e += ID_THREADS, ++it) {
+        if (!((head >> it) & 1u)) continue;
+        const unsigned long long hi = keys[e] >> 32;
+        const int64_t a = (int64_t)hi - ID_SHIFT;
+        int start = e, nv = 0, t = 0;
+        int64_t end = -1;
+        for (int f = e; f < P; ++f) {
+            const unsigned long long key = keys[f];
+            if ((key >> 32) != hi) break;                   // the next run, or the empty tail
+            const int64_t r = a + (int64_t)(unsigned int)key;
+            if (r >= end) {                                 // first hit, or the run crossed into a later track
+                if (nv) {
+                    keys[start] = hi << 32;
+                    aux[start] = (unsigned int)t;
+                    votes[start] = (unsigned short)nv;
+                }
+                t = track_of(first, end < 0 ? 0 : (t + 1 < T ? t + 1 : T - 1), T, r);   // (clamp: bad tables)
+                end = first[t + 1];
+                start = f;
+                nv = 0;
+            }
+            if (f != start) keys[f] = SEQ_NONE;
+            ++nv;
+        }
+        keys[start] = hi << 32;
+        aux[start] = (unsigned int)t;
+        votes[start] = (unsigned short)nv;
+    }
+    __syncthreads();
+    for (int e = tid; e < P; e += ID_THREADS)
+        if (keys[e] != SEQ_NONE) idx[atomicAdd(&s_ncand, 1)] = (unsigned short)e;
+    __syncthreads();
+    const int ncand = s_ncand;
+
+    // 3. scores: one candidate per half-wave at a time
+    const int hw = tid >> 5, l = tid & 31;
+    const int need_q = min_overlap > 0 ? min_overlap : ql;
+    const float4 *q4 = kQLds ? reinterpret_cast<const float4 *>(sq) : reinterpret_cast<const float4 *>(q_rows + r0 * SEQ_D);
+    for (int c = hw; c < ncand; c += ID_THREADS / 32) {
+        const int e = idx[c];
+        const int64_t a = (int64_t)(keys[e] >> 32) - ID_SHIFT;
+        const int t = (int)aux[e];
+        int64_t f0 = first[t], f1 = first[t + 1];
+        f0 = f0 < 0 ? 0 : f0;                               // (a valid table needs neither clamp)
+        f1 = f1 > n ? n : f1;
+        const int64_t L = f1 - f0;
+        const int lo = (int)(f0 - a > 0 ? f0 - a : 0);
+        const int hi = (int)(f1 - a < ql ? f1 - a : ql);
+        const int o = hi - lo;
+        const bool ok = o >= 1 && o >= (need_q < L ? need_q : L);
+        const float acc = span(q4 + lo * (SEQ_D / 4) + l, a + lo, l, ok ? o : 0);   // (not ok: no row is read)
+        const float score = acc / (float)o;
+        // every lane of the half-wave has read keys[e] and aux[e] before the shuffles above
+        if (l == 0) {
+            keys[e] = ok ? (((unsigned long long)t << 32) | ~f32_ord(score)) : SEQ_NONE;
+            aux[e] = (unsigned int)(a + ID_SHIFT);
+        }
+    }
+    __syncthreads();
+
+    // 4. best candidate per track
+    for (int e = tid; e < P; e += ID_THREADS) idx[e] = (unsigned short)e;
+    __syncthreads();
+    block_sort<ID_THREADS, true>(keys, idx, P, tid);
+    head = 0;
+    for (int e = tid, it = 0; e < P; e += ID_THREADS, ++it) {
+        const unsigned long long key = keys[e];
+        if (key != SEQ_NONE && (e == 0 || (keys[e - 1] >> 32) != (key >> 32))) head |= 1u << it;
+    }
+    __syncthreads();
+    for (int e = tid, it = 0; e < P; e += ID_THREADS, ++it) {
+        const unsigned long long key = keys[e];
+        keys[e] = ((head >> it) & 1u) ? ((key << 32) | (key >> 32)) : SEQ_NONE;
+    }
+    __syncthreads();
+
+    // 5. the `top` tracks: score descending, track ascending
+    block_sort<ID_THREADS, true>(keys, idx, P, tid);
+    if (tid < top) {
+        const unsigned long long key = keys[tid];          // top <= 64 <= P
+        const size_t o = (size_t)item * top + tid;
+        if (key != SEQ_NONE) {
+            const int t = (int)(key & 0xffffffffull);
+            const int slot = idx[tid];
+            out_track[o] = t;
+            out_offset[o] = (int32_t)((int64_t)aux[slot] - ID_SHIFT - first[t]);
+            out_score[o] = ord_f32(~(unsigned int)(key >> 32));
+            out_votes[o] = (int32_t)votes[slot];
+        } else {
+            out_track[o] = -1;
+            out_offset[o] = INT_MIN;
+            out_score[o] = -INFINITY;
+            out_votes[o] = 0;
+        }
+    }
+}
+
+}  // namespace grafp

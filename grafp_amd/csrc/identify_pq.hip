@@ -1,0 +1,144 @@
+// identify_pq.hip -- track-aware sequence identification against a library held as IVF-PQ codes (grafp_amd/library.py's
+// compact form, ops.identify_pq), gfx950.
+//
+// The same operation as identify.hip, on rows that exist only as codes.  Library row r is
+//   dec[r][j] = centroids[list_id[r]][j] + codebooks[m][codes[r][m]][c],  m = j / dsub, c = j % dsub, dsub = 128 / M
+// (one f32 add per element, never an fma: the f32 form of oracle/ivfpq.py::reconstruct), and every output is bit for bit
+// what identify_kernel writes when it is handed the (n, 128) f32 array dec.  Candidates, eligibility, the per-track best,
+// the ranking, the ties, the LDS layout and phases 1, 2, 4 and 5 are identify_core.h's identify_item, shared with
+// identify.hip; only the span rows of phase 3 differ (PqSpan below).
+//
+// Per row a lane of the half-wave (it owns dims 4l..4l+3) reads its float4 of the row's coarse centroid, the code
+// byte(s) of the sub-spaces that hold its dims and the codewords those bytes name:
+//   M = 16  (dsub 8): 1 byte  (sub-space l / 2), one float4 of the 8-float codeword
+//   M = 32  (dsub 4): 1 byte  (sub-space l),     the whole float4 codeword
+//   M = 64  (dsub 2): 2 bytes (2l, 2l + 1; the half-wave reads the row's 64 code bytes as one coalesced access), two float2
+//   M = 128 (dsub 1): 4 bytes (4l .. 4l + 3; 128 bytes per half-wave), four floats
+// The codebooks (M * 256 * dsub floats = 128 KiB for any M) and the centroids are read from global memory: every
+// workgroup gathers from the same 128 KiB, so they stay in L2.  The chain of a row is list id / code byte -> centroid /
+// codeword address -> add -> fmaf, one dependent load longer than span_sum's; the loop is unrolled by kUnroll rows so
+// that the list ids and code bytes of the next rows are issued ahead of the fmaf chain of this one.
+// Built WITHOUT packed-f32 instructions (Makefile NOPK), as identify.hip.
+#include "identify_core.h"
+
+namespace grafp {
+
+// rows decoded ahead of the fmaf chain: query rows in LDS / in global memory
+constexpr int IDPQ_UNROLL_QLDS = 4, IDPQ_UNROLL_QGLOBAL = 2;
+
+template <int kM, int kUnroll>
+struct PqSpan {
+    const int32_t *__restrict__ list_id;        // (n)
+    const unsigned char *__restrict__ codes;    // (n, kM), library row order
+    const float *__restrict__ centroids;        // (nlist, 128)
+    const float *__restrict__ codebooks;        // (kM, 256, 128 / kM)
+    int nlist;
+
+    // lane l's four floats of the codewords of row `cr`
+    __device__ __forceinline__ float4 codeword(const unsigned char *cr, int l) const {
+        constexpr int dsub = SEQ_D / kM;
+        if (kM == 16) {
+            const int m = l >> 1;
+            return *reinterpret_cast<const float4 *>(codebooks + ((size_t)m * 256 + cr[m]) * dsub + (l & 1) * 4);
+        } else if (kM == 32) {
+            return *reinterpret_cast<const float4 *>(codebooks + ((size_t)l * 256 + cr[l]) * dsub);
+        } else if (kM == 64) {
+            const unsigned int cc = reinterpret_cast<const unsigned short *>(cr)[l];
+            const float2 w0 = *reinterpret_cast<const float2 *>(codebooks + ((size_t)(2 * l) * 256 + (cc & 255u)) * dsub);
+            const float2 w1 = *reinterpret_cast<const float2 *>(codebooks + ((size_t)(2 * l + 1) * 256 + (cc >> 8)) * dsub);
+            return make_float4(w0.x, w0.y, w1.x, w1.y);
+        } else {
+            const unsigned int cc = reinterpret_cast<const unsigned int *>(cr)[l];
+            return make_float4(codebooks[(size_t)(4 * l) * 256 + (cc & 255u)],
+                               codebooks[(size_t)(4 * l + 1) * 256 + ((cc >> 8) & 255u)],
+                               codebooks[(size_t)(4 * l + 2) * 256 + ((cc >> 16) & 255u)],
+                               codebooks[(size_t)(4 * l + 3) * 256 + (cc >> 24)]);
+        }
+    }
+
+    __device__ __forceinline__ float operator()(const float4 *x, int64_t row, int l, int m) const {
+        const float4 *c4 = reinterpret_cast<const float4 *>(centroids);
+        float acc = 0.0f;
+#pragma unroll kUnroll
+        for (int t = 0; t < m; ++t) {
+            const int64_t r = row + t;
+            int lid = list_id[r];
+            lid = lid < 0 ? 0 : (lid < nlist ? lid : nlist - 1);       // (valid list ids need no clamp)
+            const float4 q = x[(int64_t)t * (SEQ_D / 4)];
+            const float4 c = c4[(size_t)lid * (SEQ_D / 4) + l];
+            const float4 w = codeword(codes + r * kM, l);
+            acc = __builtin_fmaf(q.x, c.x + w.x, acc);
+            acc = __builtin_fmaf(q.y, c.y + w.y, acc);
+            acc = __builtin_fmaf(q.z, c.z + w.z, acc);
+            acc = __builtin_fmaf(q.w, c.w + w.w, acc);
+        }
+#pragma unroll
+        for (int s = 16; s > 0; s >>= 1) acc += __shfl_xor(acc, s);      // stays inside the 32-lane half
+        return acc;
+    }
+};
+
+template <int kM, bool kQLds>
+__global__ __launch_bounds__(ID_THREADS) void identify_pq_kernel(
+    const int32_t *__restrict__ list_id, const unsigned char *__restrict__ codes, int64_t n,
+    const float *__restrict__ centroids, int nlist, const float *__restrict__ codebooks,
+    const int64_t *__restrict__ first, int T, const float *__restrict__ q_rows, const int64_t *__restrict__ ids, int k,
+    const int64_t *__restrict__ item_row, const int *__restrict__ item_len, int max_len, int Pmax, int top,
+    int min_overlap, int32_t *__restrict__ out_track, int32_t *__restrict__ out_offset, float *__restrict__ out_score,
+    int32_t *__restrict__ out_votes) {
+    const PqSpan<kM, kQLds ? IDPQ_UNROLL_QLDS : IDPQ_UNROLL_QGLOBAL> span{list_id, codes, centroids, codebooks, nlist};
+    identify_item<kQLds>(span, n, first, T, q_rows, ids, k, item_row, item_len, max_len, Pmax, top, min_overlap,
+                         out_track, out_offset, out_score, out_votes);
+}
+
+template <int kM, bool kQLds>
+static int identify_pq_launch_as(const IdentifyPlan &plan, const int32_t *list_id, const unsigned char *codes, int64_t n,
+                                 const float *centroids, int nlist, const float *codebooks, const int64_t *first, int T,
+                                 const float *q_rows, const int64_t *ids, int k, const int64_t *item_row,
+                                 const int *item_len, int n_items, int max_len, int top, int min_overlap,
+                                 int32_t *out_track, int32_t *out_offset, float *out_score, int32_t *out_votes,
+                                 hipStream_t stream) {
+    if (hipFuncSetAttribute((const void *)identify_pq_kernel<kM, kQLds>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)plan.lds) != hipSuccess) {
+        set_error("identify_pq: cannot reserve %zu bytes of LDS", plan.lds);
+        return GRAFP_ERR_LAUNCH;
+    }
+    hipLaunchKernelGGL((identify_pq_kernel<kM, kQLds>), dim3(n_items), dim3(ID_THREADS), plan.lds, stream, list_id,
+                       codes, n, centroids, nlist, codebooks, first, T, q_rows, ids, k, item_row, item_len, max_len,
+                       plan.Pmax, top, min_overlap, out_track, out_offset, out_score, out_votes);
+    GRAFP_CHECK_LAUNCH("identify_pq_kernel");
+    return GRAFP_OK;
+}
+
+int identify_pq_launch(const int32_t *list_id, const unsigned char *codes, int64_t n, const float *centroids, int nlist,
+                       const float *codebooks, int M, const int64_t *first, int T, const float *q_rows,
+                       const int64_t *ids, int k, const int64_t *item_row, const int *item_len, int n_items,
+                       int max_len, int top, int min_overlap, int32_t *out_track, int32_t *out_offset, float *out_score,
+                       int32_t *out_votes, hipStream_t stream) {
+    GRAFP_REQUIRE(M == 16 || M == 32 || M == 64 || M == 128, "identify_pq: M=%d not one of 16, 32, 64, 128", M);
+    GRAFP_REQUIRE(max_len >= 1 && max_len <= ID_MAX_LEN && k >= 1 && k <= ID_MAX_K && max_len * k <= ID_MAX_KEYS,
+                  "identify_pq: max_len=%d k=%d exceed %d segments, %d hits per segment or %d keys per item", max_len,
+                  k, ID_MAX_LEN, ID_MAX_K, ID_MAX_KEYS);
+    if (n_items == 0) return GRAFP_OK;
+    const IdentifyPlan plan = identify_plan(max_len, k);
+#define GRAFP_IDPQ_CASE(m)                                                                                             \
+    case m:                                                                                                            \
+        return plan.q_lds ? identify_pq_launch_as<m, true>(plan, list_id, codes, n, centroids, nlist, codebooks, first, \
+                                                           T, q_rows, ids, k, item_row, item_len, n_items, max_len,    \
+                                                           top, min_overlap, out_track, out_offset, out_score,         \
+                                                           out_votes, stream)                                          \
+                          : identify_pq_launch_as<m, false>(plan, list_id, codes, n, centroids, nlist, codebooks,      \
+                                                            first, T, q_rows, ids, k, item_row, item_len, n_items,     \
+                                                            max_len, top, min_overlap, out_track, out_offset,          \
+                                                            out_score, out_votes, stream)
+    switch (M) {
+        GRAFP_IDPQ_CASE(16);
+        GRAFP_IDPQ_CASE(32);
+        GRAFP_IDPQ_CASE(64);
+        default:
+            GRAFP_IDPQ_CASE(128);
+    }
+#undef GRAFP_IDPQ_CASE
+}
+
+}  // namespace grafp

@@ -10,6 +10,8 @@ probed lists with the top-k fused in) are hand-written kernels of csrc/ivfpq.hip
 
 Same surface as ops.FlatL2Index / the subset of faiss eval.py uses: d, ntotal, nprobe, train(x), add(x), search(q, k),
 plus rows() (the raw vectors, which the sequence rerank reads: the reference keeps them in a memmap, eval.py:214-232).
+With keep_raw=False the index holds codes only: rows() refuses, reconstruct() decodes, and codes_by_row() / quantiser() /
+from_codes() hand the codes to grafp_amd/library.py's compact library and back without re-encoding.
 Exact search remains the faster and more accurate index on this GPU; this one exists so that the
 published protocol can be followed to the letter.
 """
@@ -44,6 +46,22 @@ def pq_assign(x, G, cent, base=None, base_idx=None, as_codes=False):
     return out
 
 
+def _cat(parts):
+    return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+
+def decode(list_id, codes, centroids, codebooks, ids=None):
+    """Rows from codes, in f32: centroids[list_id[r]][j] + codebooks[m][codes[r][m]][j % dsub], m = j // dsub -- one add
+    per element, the rows csrc/identify_pq.hip scores (the f32 form of oracle/ivfpq.py::reconstruct).  ids: only these
+    rows."""
+    if ids is not None:
+        ids = torch.as_tensor(ids, device=codes.device).long()
+        list_id, codes = list_id[ids], codes[ids]
+    M = codebooks.shape[0]
+    words = codebooks[torch.arange(M, device=codes.device)[None, :], codes.long()]            # (n, M, dsub)
+    return centroids[list_id.long()] + words.reshape(codes.shape[0], -1)
+
+
 def kmeans_init_rows(n, k, seed):
     """k distinct training rows (seeded permutation; repeated when there are fewer rows than centroids)."""
     gen = torch.Generator().manual_seed(int(seed))
@@ -69,7 +87,8 @@ def kmeans(x, G, k, niter=25, seed=1234, base=None, base_idx=None):
 
 
 class IVFPQIndex:
-    def __init__(self, d=128, nlist=64, M=64, nbits=8, device=None, seed=1234, niter=25, max_points_per_centroid=256):
+    def __init__(self, d=128, nlist=64, M=64, nbits=8, device=None, seed=1234, niter=25, max_points_per_centroid=256,
+                 keep_raw=True):
         if nbits != 8:
             raise NotImplementedError("IVFPQIndex: 8-bit codes (the reference's setting)")
         if d % M:
@@ -80,6 +99,7 @@ class IVFPQIndex:
         self.device = torch.device(device if device is not None else "cuda")
         self.seed, self.niter, self.max_ppc = seed, niter, max_points_per_centroid
         self.nprobe = 1                                   # faiss default; eval.get_index sets 20
+        self.keep_raw = bool(keep_raw)                    # False: codes only (rows() refuses, reconstruct() decodes)
         self.is_trained = False
         self.centroids = self.codebooks = None            # (nlist, d), (M, 256, dsub)
         self._raw, self._codes, self._assign = [], [], []
@@ -118,7 +138,8 @@ class IVFPQIndex:
         for lo in range(0, x.shape[0], chunk):
             xb = x[lo:lo + chunk].to(self.device, torch.float32)
             a, codes = self.encode(xb)
-            self._raw.append(xb)
+            if self.keep_raw:
+                self._raw.append(xb)
             self._assign.append(a)
             self._codes.append(codes)
         self.ntotal += x.shape[0]
@@ -126,19 +147,72 @@ class IVFPQIndex:
 
     def _materialise(self):
         if self._sorted is None:
-            raw = torch.cat(self._raw) if len(self._raw) != 1 else self._raw[0]
-            a, codes = torch.cat(self._assign), torch.cat(self._codes)
+            raw = _cat(self._raw) if self.keep_raw else None
+            a, codes = _cat(self._assign), _cat(self._codes)
             order = torch.argsort(a, stable=True)                                     # insertion order inside a list
             counts = torch.bincount(a, minlength=self.nlist)
             start = torch.zeros(self.nlist + 1, dtype=torch.int64, device=self.device)
             start[1:] = torch.cumsum(counts, 0)
-            self._raw, self._assign, self._codes = [raw], [a], [codes]
+            self._raw, self._assign, self._codes = [raw] if self.keep_raw else [], [a], [codes]
             self._sorted = (codes[order].contiguous(), order.contiguous(), start.contiguous(), counts)
         return self._sorted
 
     def rows(self):
+        if not self.keep_raw:
+            raise RuntimeError("IVFPQIndex.rows: this index was made with keep_raw=False and holds codes only; "
+                               "reconstruct() gives the decoded rows")
         self._materialise()
         return self._raw[0]
+
+    # ---- the codes themselves (grafp_amd/library.py's compact form) --------------------------------------------------
+    def codes_by_row(self):
+        """(list id (n) int32, codes (n, M) uint8) in insertion order."""
+        if not self.ntotal:
+            return (torch.zeros(0, dtype=torch.int32, device=self.device),
+                    torch.zeros((0, self.M), dtype=torch.uint8, device=self.device))
+        self._assign, self._codes = [_cat(self._assign)], [_cat(self._codes)]
+        return self._assign[0].to(torch.int32), self._codes[0]
+
+    def reconstruct(self, ids=None):
+        """Decoded f32 rows (all, in insertion order, or those of `ids`): see decode()."""
+        a, codes = self.codes_by_row()
+        return decode(a, codes, self.centroids, self.codebooks, ids)
+
+    def quantiser(self):
+        if not self.is_trained:
+            raise RuntimeError("IVFPQIndex.quantiser before train")
+        return {"centroids": self.centroids, "codebooks": self.codebooks}
+
+    @classmethod
+    def from_codes(cls, quantiser, list_id, codes, device=None, nprobe=1):
+        """A trained keep_raw=False index over rows that are already encoded with `quantiser` (list_id (n), codes
+        (n, M) uint8, insertion order): nothing is re-encoded, and a codes tensor already on the device is shared."""
+        cent, books = torch.as_tensor(quantiser["centroids"]), torch.as_tensor(quantiser["codebooks"])
+        codes, list_id = torch.as_tensor(codes), torch.as_tensor(list_id).reshape(-1)
+        M = int(books.shape[0])
+        if cent.dim() != 2 or tuple(books.shape) != (M, 256, cent.shape[1] // max(M, 1)) or cent.shape[1] % M:
+            raise ValueError(f"from_codes: centroids {tuple(cent.shape)} and codebooks {tuple(books.shape)} do not "
+                             "make a quantiser")
+        if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.shape[1] != M or list_id.shape[0] != codes.shape[0]:
+            raise ValueError(f"from_codes: codes must be (n, {M}) uint8 with n list ids, not {tuple(codes.shape)} "
+                             f"{codes.dtype} and {list_id.shape[0]} list ids")
+        index = cls(d=int(cent.shape[1]), nlist=int(cent.shape[0]), M=M, device=device, keep_raw=False)
+        index.centroids = cent.to(index.device, torch.float32).contiguous()
+        index.codebooks = books.to(index.device, torch.float32).contiguous()
+        index.is_trained = True
+        index.nprobe = int(nprobe)
+        if codes.shape[0]:
+            index._assign = [list_id.to(index.device, torch.int64)]
+            index._codes = [codes.to(index.device).contiguous()]
+            index.ntotal = int(codes.shape[0])
+        return index
+
+    def held_tensors(self):
+        """Every device tensor the index holds once it is searchable (its share of FingerprintLibrary.nbytes)."""
+        held = [self.centroids, self.codebooks] if self.is_trained else []
+        if self.ntotal:
+            held += list(self._materialise()) + self._assign + self._codes + (self._raw if self.keep_raw else [])
+        return held
 
     # ---- search: nprobe nearest lists (grafp_ivfpq_probe_f32), then ONE launch that scans their codes with the running
     # top-k fused in (grafp_ivfpq_search_f32): no (query x probed codes) scratch, no host round trip ------------------------

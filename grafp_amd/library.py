@@ -5,7 +5,14 @@ results), the track table (track t owns rows [first[t], first[t+1])), the track 
 rows were cut with.  identify() takes recordings nobody has labelled and says which tracks they are and where in each
 they start: log-mel and segments on the device, one batched embed, one batched search, then one ops.identify launch
 (csrc/identify.hip) for all queries.  Unlike eval.py's row-level rerank (ops.seq_rerank), a candidate never reads
-across a track boundary and the result is the best tracks, not the best rows."""
+across a track boundary and the result is the best tracks, not the best rows.
+
+A library has two forms.  The flat form above keeps every row as f32 (plus the index's bf16 copy and norms: 772 bytes
+per row).  The compact form keeps IVF-PQ codes only -- per row M code bytes in row order, the list id, and the
+grafp_amd.ivfpq.IVFPQIndex over them (the codes again in list order, the ids): 2 M + 20 bytes per row, 148 at M = 64 --
+and identifies with ops.identify_pq (csrc/identify_pq.hip), which scores the decoded rows without ever storing them.
+build(index="ivfpq"), compress() and load() make one; identify, identify_windows and timeline work on either form;
+rows() and self_matches() need the flat one."""
 import hashlib
 import json
 import math
@@ -17,7 +24,8 @@ import torch
 from . import ops
 
 SETTINGS = ("fs", "n_fft", "win_len", "hop_len", "n_mels", "n_frames", "overlap")
-FORMAT = 1
+FORMAT = 1                   # the files of a flat library
+FORMAT_COMPACT = 2           # the files of a compact library
 # duplicate_groups' default score bar: a match at least this strong is shared audio.  Chosen from
 # tests/test_gpu_selfmatch.py's trained-model case (the briefly trained model of tests/_retrieval_case.py, bf16 library,
 # measured on MI355X): an exact copy scores 1.000, the pieces of a medley at 20 dB SNR 0.985 and 0.956, the strongest of
@@ -96,10 +104,33 @@ class FingerprintLibrary:
         self.settings = {k: settings[k] for k in SETTINGS}
         self.precision = precision
         self._chunks, self._rows, self._index = [], None, None
+        self._pq = None                   # compact form: {"centroids", "codebooks", "nprobe"}
+        self._code_chunks, self._codes, self._encoder = [], None, None      # chunks of (list_id int32, codes uint8)
         self.first = np.zeros(1, np.int64)
         self.names = []
         if rows is not None:
             self._append(rows, first, names)
+
+    @classmethod
+    def from_codes(cls, model, settings, quantiser, list_id, codes, first, names=None, precision="bf16", device=None,
+                   nprobe=20):
+        """A compact library over rows that are already encoded: quantiser {"centroids" (nlist, 128), "codebooks"
+        (M, 256, 128 // M)}, list_id (n) and codes (n, M) uint8 in row order, the track table as for the constructor.
+        Works on device="cpu" (files and tables only), like the flat form."""
+        lib = cls(model, settings, None, None, precision=precision, device=device)
+        lib._set_quantiser(quantiser, nprobe)
+        lib._append_codes(list_id, codes, first, names)
+        return lib
+
+    def _set_quantiser(self, quantiser, nprobe):
+        cent = torch.as_tensor(quantiser["centroids"]).to(self.device, torch.float32).contiguous()
+        books = torch.as_tensor(quantiser["codebooks"]).to(self.device, torch.float32).contiguous()
+        M = int(books.shape[0]) if books.dim() == 3 else 0
+        if M not in ops.IDENTIFY_PQ_M or cent.dim() != 2 or cent.shape[1] != 128 or cent.shape[0] < 1 or \
+                tuple(books.shape) != (M, 256, 128 // M):
+            raise ValueError(f"a compact library needs centroids (nlist, 128) and codebooks (M, 256, 128 // M) with M "
+                             f"one of {ops.IDENTIFY_PQ_M}, not {tuple(cent.shape)} and {tuple(books.shape)}")
+        self._pq = {"centroids": cent, "codebooks": books, "nprobe": int(nprobe)}
 
     # ---- sizes -----------------------------------------------------------------------------------------------
     @property
@@ -118,8 +149,62 @@ class FingerprintLibrary:
     def n_rows(self):
         return int(self.first[-1])
 
+    @property
+    def is_compact(self):
+        return self._pq is not None
+
+    def quantiser(self):
+        """{"centroids", "codebooks"} of a compact library (device tensors)."""
+        self._need_compact("quantiser()")
+        return {"centroids": self._pq["centroids"], "codebooks": self._pq["codebooks"]}
+
+    def codes(self):
+        """(list_id (n_rows) int32, codes (n_rows, M) uint8) of a compact library, in row order."""
+        self._need_compact("codes()")
+        if self._codes is None:
+            M = int(self._pq["codebooks"].shape[0])
+            parts = self._code_chunks or [(torch.zeros(0, dtype=torch.int32, device=self.device),
+                                           torch.zeros((0, M), dtype=torch.uint8, device=self.device))]
+            self._codes = (parts[0] if len(parts) == 1 else
+                           (torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])))
+            self._code_chunks = [self._codes] if self._code_chunks else []
+        return self._codes
+
+    def _need_compact(self, what):
+        if not self.is_compact:
+            raise ValueError(f"FingerprintLibrary.{what}: this is a flat library (f32 rows); compress() makes a "
+                             "compact one")
+
+    def _need_flat(self, what):
+        if self.is_compact:
+            raise NotImplementedError(f"FingerprintLibrary.{what} needs the flat form of a library (f32 rows): this one "
+                                      "is compact and holds IVF-PQ codes only")
+
+    @property
+    def nbytes(self):
+        """Device bytes the library holds: its rows (flat) or its row-order codes, list ids and quantiser (compact),
+        plus its index, which is made here if the device has one (on a CPU device only the library's own tensors count).
+        Flat: 772 bytes per row.  Compact: 2 M + 20 per row, plus the quantiser and the index's two nlist-sized tables."""
+        if self.is_compact:
+            held = list(self.codes()) + [self._pq["centroids"], self._pq["codebooks"]]
+        else:
+            held = [self.rows()]
+        if self.device.type == "cuda" and self.n_rows:
+            index = self.index
+            if self.is_compact:
+                held += index.held_tensors()
+            else:
+                index._materialise()
+                held += [index._db, index._sq, index._bf16]
+        seen = {}
+        for t in held:
+            if t is not None:
+                seen[t.untyped_storage().data_ptr()] = t.untyped_storage().nbytes()
+        return int(sum(seen.values()))
+
     def rows(self):
-        """The resident (n_rows, 128) f32 fingerprints."""
+        """The resident (n_rows, 128) f32 fingerprints (flat form only)."""
+        self._need_flat("rows()")
         if self._rows is None:
             self._rows = (self._chunks[0] if len(self._chunks) == 1 else
                           torch.cat(self._chunks) if self._chunks else torch.zeros((0, 128), device=self.device))
@@ -128,25 +213,65 @@ class FingerprintLibrary:
 
     @property
     def index(self):
-        """The ops.FlatL2Index over rows() (made on first use; it shares the rows tensor)."""
+        """The index over the rows, made on first use: the ops.FlatL2Index over rows() (it shares the rows tensor), or,
+        for a compact library, the ivfpq.IVFPQIndex over codes() (from_codes: nothing is re-encoded, the row-order codes
+        are shared)."""
         if self._index is None:
-            self._index = ops.FlatL2Index(d=128, device=self.device)
-            self._index.add(self.rows())
+            if self.is_compact:
+                from .ivfpq import IVFPQIndex
+                list_id, codes = self.codes()
+                self._index = IVFPQIndex.from_codes(self.quantiser(), list_id, codes, self.device, self._pq["nprobe"])
+            else:
+                self._index = ops.FlatL2Index(d=128, device=self.device)
+                self._index.add(self.rows())
         return self._index
 
-    def _append(self, rows, first, names):
+    def _append_table(self, first, n_new, names):
         first = np.asarray(first, np.int64).reshape(-1)
-        rows = torch.as_tensor(rows).to(self.device, torch.float32).reshape(-1, 128)
-        ops.check_track_table(first, rows.shape[0])
+        ops.check_track_table(first, n_new)
         T = len(first) - 1
         names = [str(v) for v in names] if names is not None else [f"track{self.n_tracks + i}" for i in range(T)]
         if len(names) != T:
             raise ValueError(f"{len(names)} names for {T} tracks")
+        return first, names
+
+    def _append(self, rows, first, names):
+        self._need_flat("_append()")
+        rows = torch.as_tensor(rows).to(self.device, torch.float32).reshape(-1, 128)
+        first, names = self._append_table(first, rows.shape[0], names)
         if rows.shape[0]:
             self._chunks.append(rows.contiguous())
             self._rows, self._index = None, None
         self.first = np.concatenate([self.first, self.first[-1] + first[1:]])
         self.names += names
+
+    def _append_codes(self, list_id, codes, first, names):
+        self._need_compact("_append_codes()")
+        M, nlist = int(self._pq["codebooks"].shape[0]), int(self._pq["centroids"].shape[0])
+        codes, list_id = torch.as_tensor(codes), torch.as_tensor(list_id).reshape(-1)
+        if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.shape[1] != M:
+            raise ValueError(f"codes must be (n, {M}) uint8, not {tuple(codes.shape)} {codes.dtype}")
+        if list_id.shape[0] != codes.shape[0] or list_id.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"{list_id.shape[0]} list ids ({list_id.dtype}) for {codes.shape[0]} rows of codes")
+        if list_id.numel() and not 0 <= int(list_id.min()) <= int(list_id.max()) < nlist:
+            raise ValueError(f"a list id lies outside [0, {nlist})")
+        first, names = self._append_table(first, codes.shape[0], names)
+        if codes.shape[0]:
+            self._code_chunks.append((list_id.to(self.device, torch.int32).contiguous(),
+                                      codes.to(self.device).contiguous()))
+            self._codes, self._index = None, None
+        self.first = np.concatenate([self.first, self.first[-1] + first[1:]])
+        self.names += names
+
+    def _encode(self, rows):
+        """f32 rows on the device -> (list_id int32, codes uint8) with the library's quantiser (csrc/ivfpq.hip)."""
+        if self._encoder is None:
+            from .ivfpq import IVFPQIndex
+            M = int(self._pq["codebooks"].shape[0])
+            self._encoder = IVFPQIndex.from_codes(self.quantiser(), torch.zeros(0, dtype=torch.int32),
+                                                  torch.zeros((0, M), dtype=torch.uint8), self.device)
+        a, codes = self._encoder.encode(rows)
+        return a.to(torch.int32), codes
 
     # ---- fingerprinting --------------------------------------------------------------------------------------
     def _autocast(self):
@@ -174,54 +299,140 @@ class FingerprintLibrary:
         spec = ops.logmel(x, c["fs"], c["n_fft"], c["win_len"], c["hop_len"], c["n_mels"])
         return ops.unfold_segments(spec, c["n_frames"], self.step)
 
-    def _fingerprint_tracks(self, waves, max_segments):
+    def _fingerprint_batches(self, waves, max_segments, counts):
         """Segments of consecutive tracks packed into model calls as fpdb._embed_stream packs them in eval mode (a call
-        once at least max_segments segments are pending) -> (rows, per-track row counts)."""
-        out, counts, pend, n_pend = [], [], [], 0
-
-        def flush():
-            nonlocal pend, n_pend
-            if n_pend:
-                out.append(self._embed(torch.cat(pend, dim=0)))
-            pend, n_pend = [], 0
-
+        once at least max_segments segments are pending): yields the rows of one call after the other and appends every
+        track's row count to `counts`."""
+        pend, n_pend = [], 0
         for w in waves:
             segs = self.segments(w)
             counts.append(segs.shape[0])
             pend.append(segs)
             n_pend += segs.shape[0]
             if n_pend >= max_segments:
-                flush()
-        flush()
+                yield self._embed(torch.cat(pend, dim=0))
+                pend, n_pend = [], 0
+        if n_pend:
+            yield self._embed(torch.cat(pend, dim=0))
+
+    def _fingerprint_tracks(self, waves, max_segments):
+        """-> (rows, per-track row counts) of _fingerprint_batches."""
+        counts = []
+        out = list(self._fingerprint_batches(waves, max_segments, counts))
         rows = torch.cat(out, dim=0) if out else torch.zeros((0, 128), device=self.device)
         return rows, counts
 
+    def _fingerprint_codes(self, waves, max_segments, train=None):
+        """Fingerprint and encode one model call after the other; the f32 rows of a call are dropped once encoded.
+        train = (nlist, pq_m, nprobe, train_rows, seed) for a library that has no quantiser yet: the rows of the first
+        calls are held until train_rows of them are there (or the input ends), the quantiser is trained on them, they are
+        encoded, and from then on every call is encoded as it comes -- never more f32 rows alive than train_rows plus one
+        call's (max_segments, rounded up to whole tracks).  -> (list_id, codes, per-track row counts)."""
+        counts, held, n_held, out = [], [], 0, []
+        for rows in self._fingerprint_batches(waves, max_segments, counts):
+            if not self.is_compact:
+                held.append(rows)
+                n_held += rows.shape[0]
+                if n_held < train[3]:
+                    continue
+                rows, held = torch.cat(held), []
+                self._train_quantiser(rows, *train[:3], rows.shape[0], train[4])
+            if rows.shape[0]:
+                out.append(self._encode(rows))
+        if not self.is_compact:                              # the input ended before train_rows rows were there
+            if n_held == 0:
+                raise ValueError("an IVF-PQ library cannot be trained on tracks that give no fingerprint rows")
+            rows = torch.cat(held)
+            self._train_quantiser(rows, *train[:3], rows.shape[0], train[4])
+            out.append(self._encode(rows))
+        if not out:
+            return self.codes()[0][:0], self.codes()[1][:0], counts
+        return torch.cat([p[0] for p in out]), torch.cat([p[1] for p in out]), counts
+
+    def _train_quantiser(self, rows, nlist, pq_m, nprobe, train_rows, seed):
+        """Both k-means of ivfpq.IVFPQIndex.train on `rows` (at most train_rows of them, a seeded sample in row order)."""
+        from .ivfpq import IVFPQIndex
+        if int(pq_m) not in ops.IDENTIFY_PQ_M:
+            raise ValueError(f"pq_m={pq_m} not one of {ops.IDENTIFY_PQ_M}")
+        if rows.shape[0] > int(train_rows):
+            gen = torch.Generator().manual_seed(int(seed) + 1)
+            sel = torch.sort(torch.randperm(rows.shape[0], generator=gen)[:int(train_rows)]).values
+            rows = rows[sel.to(rows.device)]
+        trainer = IVFPQIndex(d=128, nlist=int(nlist), M=int(pq_m), device=self.device, seed=int(seed), keep_raw=False)
+        trainer.train(rows)
+        self._set_quantiser(trainer.quantiser(), nprobe)
+
     @classmethod
-    def build(cls, model, tracks, cfg, names=None, precision="bf16", max_segments=4096):
+    def build(cls, model, tracks, cfg, names=None, precision="bf16", max_segments=4096, index="flat", nlist=64, pq_m=64,
+              nprobe=20, train_rows=65536, quantiser=None, seed=1234):
         """Fingerprint whole tracks (a DeviceAudioCorpus, its .tracks(), or 1-D tensors / arrays at cfg['fs']) into a
-        new library.  Tracks shorter than one segment get no rows: they stay in the table and never match."""
+        new library.  Tracks shorter than one segment get no rows: they stay in the table and never match.
+        index="ivfpq": a compact library.  Its quantiser (nlist lists, pq_m sub-quantisers) is trained on the rows of
+        the first model calls, as soon as they hold train_rows rows (on all rows if there are fewer); every later
+        model call is encoded and its f32 rows dropped, so the f32 rows of the catalogue never exist at once.
+        quantiser={"centroids", "codebooks"}: nothing is trained."""
+        if index not in ("flat", "ivfpq"):
+            raise ValueError(f"index must be 'flat' or 'ivfpq', not {index!r}")
         lib = cls(model, cfg, None, None, precision=precision)
-        lib.add(tracks, names=names, max_segments=max_segments)
+        if index == "flat":
+            return lib.add(tracks, names=names, max_segments=max_segments)
+        if quantiser is not None:
+            lib._set_quantiser(quantiser, nprobe)
+            return lib.add(tracks, names=names, max_segments=max_segments)
+        waves, own = _as_waveforms(tracks)
+        a, codes, counts = lib._fingerprint_codes(waves, int(max_segments), (nlist, pq_m, nprobe, train_rows, seed))
+        lib._append_codes(a, codes, np.concatenate([[0], np.cumsum(counts)]).astype(np.int64),
+                          names if names is not None else own)
         return lib
 
     def add(self, tracks, names=None, max_segments=4096):
-        """Append tracks (as for build) to the library."""
+        """Append tracks (as for build) to the library; a compact library encodes them with its own quantiser."""
         waves, own = _as_waveforms(tracks)
         names = names if names is not None else own
+        if self.is_compact:
+            a, codes, counts = self._fingerprint_codes(waves, int(max_segments))
+            self._append_codes(a, codes, np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), names)
+            return self
         rows, counts = self._fingerprint_tracks(waves, int(max_segments))
         self._append(rows, np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), names)
         return self
 
+    def compress(self, nlist=64, pq_m=64, nprobe=20, train_rows=65536, seed=1234, chunk=1 << 16):
+        """A new compact library with this flat library's tracks: an IVF-PQ quantiser trained on a seeded sample of
+        train_rows of its own rows (all if there are fewer), every row encoded with it.  This library is left as it is."""
+        self._need_flat("compress()")
+        if self.n_rows == 0:
+            raise ValueError("compress: the library has no rows to train a quantiser on")
+        out = FingerprintLibrary(self.model, self.settings, None, None, precision=self.precision, device=self.device)
+        rows = self.rows()
+        out._train_quantiser(rows, nlist, pq_m, nprobe, train_rows, seed)
+        parts = [out._encode(rows[lo:lo + chunk]) for lo in range(0, rows.shape[0], chunk)]
+        out._append_codes(torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]), self.first, self.names)
+        return out
+
     # ---- files -----------------------------------------------------------------------------------------------
     def save(self, out_dir):
         """library.mm + library_shape.npy (the reference's memmap format: eval.load_memmap_data reads them),
-        library_tracks.npy (the track table, int64) and library.json (names, settings, precision, model digest)."""
+        library_tracks.npy (the track table, int64) and library.json (names, settings, precision, model digest).
+        A compact library writes library_codes.npy ((n, M) uint8, row order), library_lists.npy ((n) int32),
+        library_pq.npz (centroids, codebooks), library_tracks.npy and library.json ("format": 2 and "index": {"type":
+        "ivfpq", "nlist", "M", "nprobe"}) -- and no library.mm."""
         from .fpdb import _write_memmap
         os.makedirs(out_dir, exist_ok=True)
-        _write_memmap(os.path.join(out_dir, "library"), self.rows().cpu().numpy().reshape(-1, 128))
-        np.save(os.path.join(out_dir, "library_tracks.npy"), self.first.astype(np.int64))
         meta = {"format": FORMAT, "names": self.names, "settings": self.settings, "precision": self.precision,
                 "model_digest": model_digest(self.model), "n_rows": self.n_rows, "n_tracks": self.n_tracks}
+        if self.is_compact:
+            list_id, codes = self.codes()
+            cent, books = self._pq["centroids"].cpu().numpy(), self._pq["codebooks"].cpu().numpy()
+            np.save(os.path.join(out_dir, "library_codes.npy"), codes.cpu().numpy())
+            np.save(os.path.join(out_dir, "library_lists.npy"), list_id.cpu().numpy().astype(np.int32))
+            np.savez(os.path.join(out_dir, "library_pq.npz"), centroids=cent, codebooks=books)
+            meta["format"] = FORMAT_COMPACT
+            meta["index"] = {"type": "ivfpq", "nlist": int(cent.shape[0]), "M": int(books.shape[0]),
+                             "nprobe": self._pq["nprobe"]}
+        else:
+            _write_memmap(os.path.join(out_dir, "library"), self.rows().cpu().numpy().reshape(-1, 128))
+        np.save(os.path.join(out_dir, "library_tracks.npy"), self.first.astype(np.int64))
         with open(os.path.join(out_dir, "library.json"), "w") as f:
             json.dump(meta, f, indent=1)
 
@@ -231,12 +442,25 @@ class FingerprintLibrary:
         made with, unless force=True."""
         with open(os.path.join(lib_dir, "library.json")) as f:
             meta = json.load(f)
-        if meta.get("format") != FORMAT:
-            raise ValueError(f"{lib_dir}: library format {meta.get('format')} is not {FORMAT}")
+        if meta.get("format") not in (FORMAT, FORMAT_COMPACT):
+            raise ValueError(f"{lib_dir}: library format {meta.get('format')} is neither {FORMAT} nor {FORMAT_COMPACT}")
         if not force and model_digest(model) != meta["model_digest"]:
             raise ValueError(f"{lib_dir}: the library was fingerprinted with another model (state_dict digest "
                              f"{meta['model_digest'][:12]}...); pass force=True to use it anyway")
         first = np.load(os.path.join(lib_dir, "library_tracks.npy")).astype(np.int64)
+        if meta["format"] == FORMAT_COMPACT:
+            if meta.get("index", {}).get("type") != "ivfpq":
+                raise ValueError(f"{lib_dir}: a format {FORMAT_COMPACT} library with index {meta.get('index')!r}")
+            codes = np.load(os.path.join(lib_dir, "library_codes.npy"))
+            lists = np.load(os.path.join(lib_dir, "library_lists.npy"))
+            if codes.shape[0] != int(first[-1]):
+                raise ValueError(f"{lib_dir}: {codes.shape[0]} rows but the track table covers {int(first[-1])}")
+            with np.load(os.path.join(lib_dir, "library_pq.npz")) as pq:
+                quantiser = {"centroids": torch.from_numpy(pq["centroids"]), "codebooks": torch.from_numpy(pq["codebooks"])}
+            if device is not None:
+                model = model.to(device)
+            return cls.from_codes(model, meta["settings"], quantiser, torch.from_numpy(lists), torch.from_numpy(codes),
+                                  first, meta["names"], meta["precision"], device, meta["index"]["nprobe"])
         shape = tuple(int(v) for v in np.load(os.path.join(lib_dir, "library_shape.npy")))
         if shape[0] != int(first[-1]):
             raise ValueError(f"{lib_dir}: {shape[0]} rows but the track table covers {int(first[-1])}")
@@ -306,10 +530,13 @@ class FingerprintLibrary:
         k = min(int(k_probe), self.n_rows)
         _, ids = self.index.search(q, k)
         dev = self.device
-        tr, off, sc, vo = ops.identify(self.rows(), torch.from_numpy(self.first).to(dev), q, ids,
-                                       torch.from_numpy(np.asarray(item_row, np.int64)).to(dev),
-                                       torch.from_numpy(np.asarray(item_len, np.int32)).to(dev), top=top,
-                                       min_overlap=min_overlap, max_len=max_len)
+        tail = (torch.from_numpy(self.first).to(dev), q, ids, torch.from_numpy(np.asarray(item_row, np.int64)).to(dev),
+                torch.from_numpy(np.asarray(item_len, np.int32)).to(dev))
+        if self.is_compact:
+            tr, off, sc, vo = ops.identify_pq(*self.codes(), self._pq["centroids"], self._pq["codebooks"], *tail,
+                                              top=top, min_overlap=min_overlap, max_len=max_len)
+        else:
+            tr, off, sc, vo = ops.identify(self.rows(), *tail, top=top, min_overlap=min_overlap, max_len=max_len)
         tr, off, sc, vo = (t.cpu().numpy() for t in (tr, off, sc, vo))
         step, hop, fs = self.step, self.settings["hop_len"], self.settings["fs"]
         out = []
@@ -393,6 +620,7 @@ class FingerprintLibrary:
         Memory: the kernel reads hits by library row, so the hits of the searched rows live in one (n_rows, k_probe)
         int64 tensor whatever `tracks` is (256 MB at 1 M rows and k_probe = 32); each batch also takes its own exactly
         sized workspace (ops.self_match_workspace_bytes: about 124 KB per 303-row source at k_probe = 32, min_votes 4)."""
+        self._need_flat("self_matches()")
         T, n = self.n_tracks, self.n_rows
         src = list(range(T)) if tracks is None else sorted({int(t) for t in tracks})
         if src and not 0 <= min(src) <= max(src) < T:

@@ -1585,7 +1585,71 @@ def identify(index_rows, track_first_row, q_rows, topk_ids, item_row, item_len, 
     return outs
 
 
-SELF_MATCH_MAX_K, SELF_MATCH_MAX_TOP = 32, 64                             # selfmatch.hip's limits
+IDENTIFY_PQ_M = (16, 32, 64, 128)                                        # identify_pq.hip's sub-quantiser counts
+
+
+def identify_pq(list_id, codes, centroids, codebooks, track_first_row, q_rows, topk_ids, item_row, item_len, top=5,
+                min_overlap=None, max_len=None):
+    """ops.identify against a library held as IVF-PQ codes (grafp_identify_pq_f32): library row r is
+    centroids[list_id[r]] + the codewords codes[r] names (one f32 add per element), and every output is bit for bit
+    what ops.identify returns on those decoded rows.
+    list_id (n) int32 in [0, nlist), codes (n, M) uint8 in library row order, centroids (nlist, 128) f32, codebooks
+    (M, 256, 128 // M) f32, M one of 16, 32, 64, 128; the other arguments, the results and the meaning of max_len as
+    for ops.identify (without max_len the list ids are range-checked on the host too)."""
+    n_items, k, top = int(item_row.shape[0]), int(topk_ids.shape[1]), int(top)
+    # argument checks first (host values only): they hold on any device
+    if codes.dim() != 2 or codes.dtype != torch.uint8:
+        raise ValueError(f"identify_pq: codes must be (n, M) uint8, not {tuple(codes.shape)} {codes.dtype}")
+    n, M = int(codes.shape[0]), int(codes.shape[1])
+    if M not in IDENTIFY_PQ_M:
+        raise ValueError(f"identify_pq: M={M} sub-quantisers, not one of {IDENTIFY_PQ_M}")
+    if list_id.dtype != torch.int32 or tuple(list_id.shape) != (n,):
+        raise ValueError(f"identify_pq: list_id must be ({n},) int32, not {tuple(list_id.shape)} {list_id.dtype}")
+    if centroids.dim() != 2 or centroids.shape[0] < 1 or centroids.shape[1] != 128:
+        raise ValueError(f"identify_pq: centroids must be (nlist, 128), not {tuple(centroids.shape)}")
+    if tuple(codebooks.shape) != (M, 256, 128 // M):
+        raise ValueError(f"identify_pq: codebooks must be {(M, 256, 128 // M)} for M={M}, not {tuple(codebooks.shape)}")
+    nlist = int(centroids.shape[0])
+    if not 1 <= top <= 64:
+        raise ValueError(f"identify_pq: top={top} not in [1, 64]")
+    if not 1 <= k <= IDENTIFY_MAX_K:
+        raise ValueError(f"identify_pq: k={k} hits per segment exceeds {IDENTIFY_MAX_K}")
+    if min_overlap is not None and int(min_overlap) < 1:
+        raise ValueError("identify_pq: min_overlap must be at least 1 segment")
+    if max_len is None and n_items:
+        max_len = max(1, int(item_len.max().item()))
+        check_track_table(track_first_row, n)
+        _check_items_inside("identify_pq", item_row, item_len, q_rows.shape[0])
+        if n and not 0 <= int(list_id.min().item()) <= int(list_id.max().item()) < nlist:
+            raise ValueError(f"identify_pq: a list id lies outside [0, {nlist})")
+    if max_len is not None and (int(max_len) > IDENTIFY_MAX_LEN or int(max_len) * k > IDENTIFY_MAX_KEYS):
+        raise ValueError(f"identify_pq: items of {int(max_len)} segments with k={k} exceed {IDENTIFY_MAX_LEN} segments "
+                         f"or {IDENTIFY_MAX_KEYS} hits per item")
+    _require_gpu(list_id, codes, centroids, codebooks, q_rows, topk_ids, item_row, item_len)
+    list_id, codes = list_id.detach().contiguous(), codes.detach().contiguous()
+    centroids, codebooks, q_rows = _f32c(centroids), _f32c(codebooks), _f32c(q_rows)
+    dev = codes.device
+    first = torch.as_tensor(track_first_row).detach().to(device=dev, dtype=torch.int64).contiguous()
+    topk_ids = topk_ids.to(torch.int64).contiguous()
+    item_row = item_row.to(torch.int64).contiguous()
+    item_len = item_len.to(torch.int32).contiguous()
+    outs = (torch.empty((n_items, top), dtype=torch.int32, device=dev),
+            torch.empty((n_items, top), dtype=torch.int32, device=dev),
+            torch.empty((n_items, top), dtype=torch.float32, device=dev),
+            torch.empty((n_items, top), dtype=torch.int32, device=dev))
+    if n_items == 0:
+        return outs
+    max_len = int(max_len)
+    with _timed("identify_pq", (n_items, max_len, k, M)):
+        check(lib.grafp_identify_pq_f32(_p(list_id), _p(codes), n, _p(centroids), nlist, _p(codebooks), M, _p(first),
+                                        first.numel() - 1, _p(q_rows), q_rows.shape[0], _p(topk_ids), k, _p(item_row),
+                                        _p(item_len), n_items, max_len, top,
+                                        0 if min_overlap is None else int(min_overlap), *(_p(o) for o in outs),
+                                        _stream()), "identify_pq")
+    return outs
+
+
+SELF_MATCH_MAX_K, SELF_MATCH_MAX_TOP = 32, 64                            # selfmatch.hip's limits
 
 
 def self_match_workspace_bytes(src_rows, k, min_votes):

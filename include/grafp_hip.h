@@ -559,6 +559,20 @@ int grafp_identify_f32(const float *index_rows, int64_t n, const int64_t *track_
                        const int *item_len, int n_items, int max_len, int top, int min_overlap, int32_t *out_track,
                        int32_t *out_offset, float *out_score, int32_t *out_votes, grafp_stream_t stream);
 
+/* ---- identification against a library held as IVF-PQ codes (grafp_amd/library.py; identify_pq.hip) ---------------
+ * grafp_identify_pq_f32 -- grafp_identify_f32 on a library whose rows exist only as codes.  Library row r is
+ *   dec[r][j] = centroids[list_id[r]][j] + codebooks[m][codes[r][m]][c], m = j / dsub, c = j % dsub, dsub = 128 / M
+ *   (one f32 add per element), and all four outputs are bit for bit what grafp_identify_f32 writes for index_rows = dec.
+ *   list_id (n) int32 in [0, nlist), codes (n, M) uint8 in library row order, centroids (nlist, 128) f32, codebooks
+ *   (M, 256, dsub) f32; every other argument as for grafp_identify_f32.
+ *   Limits: those of grafp_identify_f32, M one of 16, 32, 64, 128; centroids, codebooks and q_rows 16-byte aligned,
+ *   codes and list_id 4-byte aligned. */
+int grafp_identify_pq_f32(const int32_t *list_id, const uint8_t *codes, int64_t n, const float *centroids, int nlist,
+                          const float *codebooks, int M, const int64_t *track_first_row, int n_tracks,
+                          const float *q_rows, int64_t n_qrows, const int64_t *topk_ids, int k, const int64_t *item_row,
+                          const int *item_len, int n_items, int max_len, int top, int min_overlap, int32_t *out_track,
+                          int32_t *out_offset, float *out_score, int32_t *out_votes, grafp_stream_t stream);
+
 /* ---- shared audio inside a track-indexed library (grafp_amd/library.py; selfmatch.hip) ---------------------------
  * grafp_self_match_f32 -- for each of n_src source tracks src_tracks[s] (int32, in [0, n_tracks)), the other tracks
  *   its audio reappears in.  index_rows, track_first_row: as for grafp_identify_f32; topk_ids (n, k) int64: every

@@ -1,0 +1,276 @@
+"""CPU tests of identification against IVF-PQ codes (csrc/identify_pq.hip, ops.identify_pq, the compact form of
+grafp_amd/library.py): the decode restatement, the refusal paths of the op and of the C entry, the shipped assembly, the
+host bookkeeping and the files of a compact library, the command line.  No GPU call is made."""
+import ctypes
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from _common import shipped_asm
+from _identify_pq_ref import decode
+from grafp_amd import library, ops
+from grafp_amd.ivfpq import IVFPQIndex, decode as torch_decode
+from grafp_amd.util import load_config
+
+
+def _quantiser(M, nlist, seed):
+    """Dyadic centroids and codewords: multiples of 2^-8 in [-1/32, 1/32)."""
+    rng = np.random.RandomState(seed)
+    cent = (rng.randint(-8, 8, size=(nlist, 128)) / 256.0).astype(np.float32)
+    books = (rng.randint(-8, 8, size=(M, 256, 128 // M)) / 256.0).astype(np.float32)
+    return cent, books
+
+
+@pytest.mark.parametrize("M", [16, 64])
+def test_decode_is_the_oracle_reconstruction_in_f32(M):
+    from oracle import ivfpq as oracle_ivfpq
+    cent, books = _quantiser(M, 5, M)
+    rng = np.random.RandomState(M + 1)
+    a = rng.randint(0, 5, size=37)
+    codes = rng.randint(0, 256, size=(37, M)).astype(np.uint8)
+    got = decode(a, codes, cent, books)
+    want = oracle_ivfpq.reconstruct(a, codes, cent, books)
+    assert got.dtype == np.float32 and got.shape == (37, 128)
+    assert np.array_equal(got, want.astype(np.float32)) and np.array_equal(got.astype(np.float64), want)   # dyadic: exact
+    # by hand: dim j of row 3 = its centroid's dim j + dim j % dsub of the codeword codes[3][j // dsub] of sub-space j // dsub
+    dsub = 128 // M
+    for j in (0, 1, dsub - 1, dsub, 77, 127):
+        assert got[3, j] == cent[a[3], j] + books[j // dsub, codes[3, j // dsub], j % dsub]
+
+
+def test_decode_in_torch_is_the_restatement():
+    for M in (16, 32, 64, 128):
+        cent, books = _quantiser(M, 3, 40 + M)
+        rng = np.random.RandomState(M)
+        a = rng.randint(0, 3, size=11).astype(np.int32)
+        codes = rng.randint(0, 256, size=(11, M)).astype(np.uint8)
+        t = lambda x: torch.from_numpy(x)
+        got = torch_decode(t(a), t(codes), t(cent), t(books))
+        assert np.array_equal(got.numpy(), decode(a, codes, cent, books))
+        some = torch_decode(t(a), t(codes), t(cent), t(books), ids=[4, 0])
+        assert np.array_equal(some.numpy(), decode(a, codes, cent, books)[[4, 0]])
+
+
+def _op_args(M=64, n=8, nq=300, k=4, nlist=3):
+    return dict(list_id=torch.zeros(n, dtype=torch.int32), codes=torch.zeros((n, M), dtype=torch.uint8),
+                centroids=torch.zeros(nlist, 128), codebooks=torch.zeros(M, 256, 128 // M),
+                track_first_row=torch.tensor([0, n]), q_rows=torch.zeros(nq, 128),
+                topk_ids=torch.zeros(nq, k, dtype=torch.int64), item_row=torch.zeros(1, dtype=torch.int64),
+                item_len=torch.tensor([2], dtype=torch.int32))
+
+
+def test_identify_pq_op_refusals_without_a_gpu():
+    def call(match, exc=ValueError, **kw):
+        args = _op_args(**{k: kw.pop(k) for k in list(kw) if k in ("M", "n", "nq", "k", "nlist")})
+        extra = {k: kw.pop(k) for k in list(kw) if k in ("top", "min_overlap", "max_len")}
+        args.update(kw)
+        with pytest.raises(exc, match=match):
+            ops.identify_pq(**args, **extra)
+
+    call("M=48", codes=torch.zeros((8, 48), dtype=torch.uint8), codebooks=torch.zeros(48, 256, 2))
+    call("M=8", codes=torch.zeros((8, 8), dtype=torch.uint8), codebooks=torch.zeros(8, 256, 16))
+    call("uint8", codes=torch.zeros((8, 64), dtype=torch.int32))
+    call("uint8", codes=torch.zeros(8 * 64, dtype=torch.uint8))
+    call("list_id", list_id=torch.zeros(8, dtype=torch.int64))
+    call("list_id", list_id=torch.zeros(7, dtype=torch.int32))
+    call("codebooks", codebooks=torch.zeros(64, 256, 4))
+    call("codebooks", codebooks=torch.zeros(32, 256, 4))
+    call("centroids", centroids=torch.zeros(3, 64))
+    call("256 segments", item_len=torch.tensor([257], dtype=torch.int32))
+    call("k=33", k=33)
+    call("hits per item", k=32, max_len=257)
+    call("top", top=65)
+    call("min_overlap", min_overlap=0)
+    call("never decrease", track_first_row=torch.tensor([0, 5, 3, 8]))
+    call("outside q_rows", item_row=torch.tensor([299]))
+    call(r"list id lies outside \[0, 3\)", list_id=torch.tensor([0, 1, 2, 3, 0, 0, 0, 0], dtype=torch.int32))
+    call(r"list id lies outside \[0, 3\)", list_id=torch.tensor([0, 1, 2, -1, 0, 0, 0, 0], dtype=torch.int32))
+    for M in (16, 32, 64, 128):                           # every argument check passes: only the device is missing
+        call("no CPU", exc=RuntimeError, M=M)
+    # with max_len the caller vouches for the ranges: no range check runs, the device check is reached
+    call("no CPU", exc=RuntimeError, list_id=torch.full((8,), 9, dtype=torch.int32), max_len=2)
+
+
+# ---- the C ABI entry and the shipped object ---------------------------------------------------------------------
+def test_abi_entry_follows_the_conventions():
+    from test_abi import _ctype_of, _declared
+    from grafp_amd import _lib
+    d = _declared()
+    ret, args = d["grafp_identify_pq_f32"]
+    assert ret == "int" and args[-1].startswith("grafp_stream_t")
+    res, argtypes = _lib.SIGNATURES["grafp_identify_pq_f32"]
+    assert res is ctypes.c_int and [_ctype_of(a) for a in args] == list(argtypes)
+    assert hasattr(ctypes.CDLL(_lib.LIB_PATH), "grafp_identify_pq_f32")
+
+
+def test_abi_entry_refuses_out_of_range_launches_without_a_gpu():
+    from grafp_amd._lib import lib
+    # never dereferenced: every call below fails an argument check before anything is launched (no call here may pass
+    # them -- this file also runs on machines with a GPU)
+    fake = [ctypes.c_void_p(256 * (i + 1)) for i in range(13)]
+
+    def call(max_len, k, top=5, n=100, M=64, nlist=8, null=None, ptrs=None):
+        p = list(ptrs or fake)
+        if null is not None:
+            p[null] = None
+        return lib.grafp_identify_pq_f32(p[0], p[1], n, p[2], nlist, p[3], M, p[4], 2, p[5], 1000, p[6], k, p[7], p[8],
+                                         4, max_len, top, 0, p[9], p[10], p[11], p[12], None)
+    assert call(257, 4) == -1 and b"exceed" in lib.grafp_last_error()
+    assert call(8, 33) == -1 and b"exceed" in lib.grafp_last_error()
+    assert call(205, 40) == -1 and b"exceed" in lib.grafp_last_error()
+    assert call(8, 4, top=65) == -1 and b"top" in lib.grafp_last_error()
+    for M in (0, 8, 48, 256):
+        assert call(8, 4, M=M) == -1 and b"M=" in lib.grafp_last_error()
+    assert call(8, 4, n=0) == -1 and b"bad sizes" in lib.grafp_last_error()
+    assert call(8, 4, n=0x7fffff00) == -1 and b"bad sizes" in lib.grafp_last_error()
+    assert call(8, 4, nlist=0) == -1 and b"bad sizes" in lib.grafp_last_error()
+    for i in range(13):
+        assert call(8, 4, null=i) == -1 and b"null pointer" in lib.grafp_last_error(), i
+    odd = list(fake)
+    odd[1] = ctypes.c_void_p(257)                          # codes: the kernel reads them 2 and 4 bytes at a time
+    assert call(8, 4, ptrs=odd) == -1 and b"aligned" in lib.grafp_last_error()
+    odd = list(fake)
+    odd[3] = ctypes.c_void_p(264)                          # codebooks: float4 gathers
+    assert call(8, 4, ptrs=odd) == -1 and b"aligned" in lib.grafp_last_error()
+
+
+def test_identify_pq_kernels_have_no_packed_f32_instructions():
+    """The shipped object's own command (make -n), compiled to device assembly: eight kernels (M = 16, 32, 64, 128, query
+    rows in LDS or not), no packed-f32 instruction, and the score is an fma chain."""
+    asm = shipped_asm("identify_pq")
+    kernels = re.findall(r"^(_ZN5grafp\w+):", asm, flags=re.M)
+    assert sum("identify_pq_kernel" in k for k in kernels) == 8
+    assert not re.search(r"^\s*v_pk_\w+_f32", asm, flags=re.M)
+    assert "v_fmac_f32" in asm or "v_fma_f32" in asm
+
+
+# ---- a compact library on the CPU: tables and files --------------------------------------------------------------
+def _tiny_model():
+    from grafp_amd.train import build_model
+    torch.manual_seed(0)
+    return build_model(load_config())
+
+
+def _compact(model, M=64, nlist=4, seed=5):
+    cent, books = _quantiser(M, nlist, seed)
+    rng = np.random.RandomState(seed + 1)
+    a = rng.randint(0, nlist, size=9).astype(np.int32)
+    codes = rng.randint(0, 256, size=(9, M)).astype(np.uint8)
+    q = {"centroids": torch.from_numpy(cent), "codebooks": torch.from_numpy(books)}
+    lib = library.FingerprintLibrary.from_codes(model, load_config(), q, torch.from_numpy(a), torch.from_numpy(codes),
+                                                [0, 4, 4, 9], ["a", "b", "c"], precision="f32", device="cpu", nprobe=3)
+    return lib, a, codes, cent, books
+
+
+def test_compact_library_tables_save_load_and_refusals(tmp_path):
+    model = _tiny_model()
+    lib, a, codes, cent, books = _compact(model)
+    assert lib.is_compact and lib.n_tracks == 3 and lib.n_rows == 9 and lib.step == 3
+    rng = np.random.RandomState(9)
+    a2, c2 = rng.randint(0, 4, size=2).astype(np.int32), rng.randint(0, 256, size=(2, 64)).astype(np.uint8)
+    lib._append_codes(torch.from_numpy(a2), torch.from_numpy(c2), [0, 2], ["d"])
+    assert lib.first.tolist() == [0, 4, 4, 9, 11] and lib.names == ["a", "b", "c", "d"]
+    got_a, got_c = lib.codes()
+    assert got_a.dtype == torch.int32 and got_c.dtype == torch.uint8
+    assert np.array_equal(got_a.numpy(), np.concatenate([a, a2])) and np.array_equal(got_c.numpy(), np.concatenate([codes, c2]))
+    assert torch.equal(lib.quantiser()["centroids"], torch.from_numpy(cent))
+    assert lib.nbytes == 11 * (64 + 4) + cent.nbytes + books.nbytes      # no index on a CPU device: the library's own
+    # refusals that name the flat form
+    with pytest.raises(NotImplementedError, match="flat form"):
+        lib.rows()
+    with pytest.raises(NotImplementedError, match="flat form"):
+        lib.self_matches()
+    with pytest.raises(NotImplementedError, match="flat form"):
+        lib.compress()
+    # files
+    lib.save(str(tmp_path))
+    assert sorted(os.listdir(tmp_path)) == ["library.json", "library_codes.npy", "library_lists.npy", "library_pq.npz",
+                                            "library_tracks.npy"]
+    meta = json.load(open(tmp_path / "library.json"))
+    assert meta["format"] == 2 and meta["index"] == {"type": "ivfpq", "nlist": 4, "M": 64, "nprobe": 3}
+    assert meta["names"] == lib.names and meta["n_rows"] == 11 and meta["precision"] == "f32"
+    assert np.load(tmp_path / "library_codes.npy").dtype == np.uint8
+    assert np.load(tmp_path / "library_lists.npy").dtype == np.int32
+    back = library.FingerprintLibrary.load(str(tmp_path), model)
+    assert back.is_compact and back.first.tolist() == lib.first.tolist() and back.names == lib.names
+    assert all(torch.equal(x, y) for x, y in zip(back.codes(), lib.codes()))
+    assert all(torch.equal(back.quantiser()[k], lib.quantiser()[k]) for k in ("centroids", "codebooks"))
+    assert back.settings == lib.settings and back.precision == "f32" and back._pq["nprobe"] == 3
+    other = _tiny_model()
+    with torch.no_grad():
+        next(other.parameters()).add_(1.0)
+    with pytest.raises(ValueError, match="another model"):
+        library.FingerprintLibrary.load(str(tmp_path), other)
+    assert library.FingerprintLibrary.load(str(tmp_path), other, force=True).n_rows == 11
+
+
+def test_compact_library_refuses_bad_codes():
+    model = _tiny_model()
+    cent, books = _quantiser(64, 4, 1)
+    q = {"centroids": torch.from_numpy(cent), "codebooks": torch.from_numpy(books)}
+    mk = lambda quant, a, c, first=(0, 4): library.FingerprintLibrary.from_codes(
+        model, load_config(), quant, a, c, list(first), device="cpu")
+    a, c = torch.zeros(4, dtype=torch.int32), torch.zeros((4, 64), dtype=torch.uint8)
+    assert mk(q, a, c).n_rows == 4
+    with pytest.raises(ValueError, match="uint8"):
+        mk(q, a, c.to(torch.int32))
+    with pytest.raises(ValueError, match="uint8"):
+        mk(q, a, c[:, :32])
+    with pytest.raises(ValueError, match="list ids"):
+        mk(q, a[:3], c)
+    with pytest.raises(ValueError, match="outside"):
+        mk(q, torch.tensor([0, 1, 4, 0], dtype=torch.int32), c)
+    with pytest.raises(ValueError, match="track table"):
+        mk(q, a, c, first=(0, 3))
+    with pytest.raises(ValueError, match="compact library needs"):
+        mk({"centroids": q["centroids"], "codebooks": torch.zeros(48, 256, 2)}, a, c)
+    with pytest.raises(ValueError, match="compact library needs"):
+        mk({"centroids": torch.zeros(4, 64), "codebooks": q["codebooks"]}, a, c)
+    flat = library.FingerprintLibrary(model, load_config(), torch.zeros(4, 128), [0, 4], device="cpu")
+    assert not flat.is_compact and flat.nbytes == 4 * 512
+    with pytest.raises(ValueError, match="flat library"):
+        flat.codes()
+
+
+def test_a_flat_library_is_written_as_before_and_still_loads(tmp_path):
+    """format 1 and the same four files; a directory whose library.json says 1 loads as a flat library."""
+    model = _tiny_model()
+    rows = torch.from_numpy((np.random.RandomState(2).randint(-32, 32, size=(6, 128)) / 256.0).astype(np.float32))
+    flat = library.FingerprintLibrary(model, load_config(), rows, [0, 2, 6], ["x", "y"], precision="f32", device="cpu")
+    flat.save(str(tmp_path))
+    assert sorted(os.listdir(tmp_path)) == ["library.json", "library.mm", "library_shape.npy", "library_tracks.npy"]
+    meta = json.load(open(tmp_path / "library.json"))
+    assert meta["format"] == 1 and "index" not in meta
+    back = library.FingerprintLibrary.load(str(tmp_path), model)
+    assert not back.is_compact and torch.equal(back.rows(), rows) and back.names == ["x", "y"]
+    meta["format"] = 3
+    json.dump(meta, open(tmp_path / "library.json", "w"))
+    with pytest.raises(ValueError, match="format 3"):
+        library.FingerprintLibrary.load(str(tmp_path), model)
+
+
+def test_index_surface_for_codes_only():
+    import inspect
+    sig = inspect.signature(IVFPQIndex.__init__)
+    assert sig.parameters["keep_raw"].default is True
+    for name in ("codes_by_row", "reconstruct", "quantiser", "from_codes"):
+        assert hasattr(IVFPQIndex, name)
+
+
+def test_command_line_parses_the_index_options(capsys):
+    from grafp_amd import identify
+    with pytest.raises(SystemExit) as e:
+        identify.main(["build", "--help"])
+    assert e.value.code == 0
+    out = capsys.readouterr().out
+    for opt in ("--index", "--nlist", "--pq-m", "--nprobe", "--train-rows"):
+        assert opt in out, opt
+    base = ["build", "--ckp", "m.pth", "--source", "dir", "--out", "lib"]
+    for bad in (["--index", "hnsw"], ["--index", "ivfpq", "--pq-m", "48"]):
+        with pytest.raises(SystemExit) as e:
+            identify.main(base + bad)                                  # refused by the parser, before any device is used
+        assert e.value.code == 2

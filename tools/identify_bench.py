@@ -6,6 +6,11 @@ one batched search at k = --k (default 20), then:
   search      ops.FlatL2Index.search of every query row (bf16 pre-filter, exact)
   identify    ops.identify of all items in one launch (top 5)
   seq_rerank  ops.seq_rerank of the same items and hits (top 10), the row-level rerank of eval.py, as the comparison
+With --index ivfpq the library is held as IVF-PQ codes (ivfpq.IVFPQIndex, keep_raw=False: --nlist, --pq-m, --nprobe) and
+the two stages of a query against a compact library are reported separately:
+  ivfpq_search   IVFPQIndex.search of every query row
+  identify_pq    ops.identify_pq of all items on the codes, next to ops.identify of the same items and hits on the
+                 decoded rows (index.reconstruct()), and their ratio
 Kernel times from events (median of --reps); `rocprofv3 --kernel-trace --stats -- python tools/identify_bench.py` gives
 the per-kernel figures.
 """
@@ -34,6 +39,37 @@ def _events(fn, reps):
     return float(np.median(times))
 
 
+def _ivfpq(args, dev, rows, first, q, item_row, item_len, true_track, true_off):
+    from grafp_amd import ops
+    from grafp_amd.ivfpq import IVFPQIndex
+    ql = args.qlen
+    index = IVFPQIndex(nlist=args.nlist, M=args.pq_m, device=dev, keep_raw=False)
+    index.train(rows)
+    index.add(rows)
+    index.nprobe = args.nprobe
+    list_id, codes = index.codes_by_row()
+    quant = index.quantiser()
+    cent, books = quant["centroids"], quant["codebooks"]
+    t_search = _events(lambda: index.search(q, args.k), max(1, args.reps // 4))
+    _, ids = index.search(q, args.k)
+    run_pq = lambda: ops.identify_pq(list_id, codes, cent, books, first, q, ids, item_row, item_len, top=5, max_len=ql)
+    t_pq = _events(run_pq, args.reps)
+    dec = index.reconstruct()
+    run_dec = lambda: ops.identify(dec, first, q, ids, item_row, item_len, top=5, max_len=ql)
+    t_dec = _events(run_dec, args.reps)
+    got, want = run_pq(), run_dec()
+    same = all(torch.equal(g.view(torch.int32), w.view(torch.int32)) for g, w in zip(got, want))
+    tr, off = got[0], got[1]
+    hit = (tr[:, 0].long() == torch.from_numpy(true_track).to(dev)) & \
+          (off[:, 0].long() == torch.from_numpy(true_off).to(dev))
+    return {"index": "ivfpq", "rows": int(rows.shape[0]), "tracks": int(first.numel() - 1), "queries": args.queries,
+            "qlen": ql, "k": args.k, "nlist": args.nlist, "M": args.pq_m, "nprobe": args.nprobe,
+            "ivfpq_search_ms": round(t_search * 1e3, 3), "identify_pq_ms": round(t_pq * 1e3, 3),
+            "identify_decoded_ms": round(t_dec * 1e3, 3), "identify_pq_over_identify": round(t_pq / t_dec, 3),
+            "bit_equal_to_identify_on_decoded_rows": bool(same),
+            "identify_top1_correct": round(float(hit.float().mean()), 4)}
+
+
 def main(argv=None):
     from grafp_amd import library, ops
     from grafp_amd.util import load_config
@@ -44,6 +80,10 @@ def main(argv=None):
     ap.add_argument("--qlen", type=int, default=31)
     ap.add_argument("--k", type=int, default=20)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--index", choices=("flat", "ivfpq"), default="flat")
+    ap.add_argument("--nlist", type=int, default=64)
+    ap.add_argument("--pq-m", type=int, default=64)
+    ap.add_argument("--nprobe", type=int, default=20)
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     cfg = load_config()
@@ -63,6 +103,9 @@ def main(argv=None):
     item_row = torch.arange(nq, device=dev, dtype=torch.int64) * ql
     item_len = torch.full((nq,), ql, device=dev, dtype=torch.int32)
 
+    if args.index == "ivfpq":
+        print(json.dumps(_ivfpq(args, dev, rows, first, q, item_row, item_len, t, a - t * per)))
+        return
     index = ops.FlatL2Index(device=dev)
     index.add(rows)
     t_search = _events(lambda: index.search(q, args.k), max(1, args.reps // 4))
