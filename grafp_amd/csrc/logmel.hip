@@ -15,6 +15,14 @@ namespace grafp {
 constexpr int LM_THREADS = 256;
 constexpr int LM_FPB = 8;  // frames per block
 
+// 10 log10(max(p, 1e-10)) (AmplitudeToDB, top_db=None).  The clamp's own value is written, not computed: the device
+// log10f(1e-10f) is one ulp short of -10, which made silent frames -99.99999 where bands without a bin (folded by the
+// compiler) and the reference give -100.
+__device__ __forceinline__ float lm_db(float p) {
+    const float db = 10.0f * log10f(fmaxf(p, 1e-10f));
+    return p > 1e-10f ? db : -100.0f;
+}
+
 template <int NFFT>
 __global__ __launch_bounds__(LM_THREADS) void logmel_kernel(const float *__restrict__ wav, int64_t wav_stride, int T,
                                                             int hop, int n_mels, int n_frames,
@@ -82,7 +90,7 @@ __global__ __launch_bounds__(LM_THREADS) void logmel_kernel(const float *__restr
                 float acc = 0.0f;
                 const int lo = band_lo[m], hi = band_hi[m];
                 for (int k = lo; k <= hi; ++k) acc = __builtin_fmaf(pw[fs][k], fb[(size_t)k * n_mels + m], acc);
-                out[((size_t)b * n_mels + m) * n_frames + f] = 10.0f * log10f(fmaxf(acc, 1e-10f));
+                out[((size_t)b * n_mels + m) * n_frames + f] = lm_db(acc);
             }
         }
         __syncthreads();
@@ -234,8 +242,8 @@ __global__ __launch_bounds__(256, 2) void logmel1024_kernel(const float *__restr
                 acc1 = __builtin_fmaf(pw.y, wgt, acc1);
             }
             float *o = out + ((size_t)b * n_mels + m) * n_frames + f0;
-            o[0] = 10.0f * log10f(fmaxf(acc0, 1e-10f));
-            if (has1) o[1] = 10.0f * log10f(fmaxf(acc1, 1e-10f));
+            o[0] = lm_db(acc0);
+            if (has1) o[1] = lm_db(acc1);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();          // the band sums are done with the buffer before the next pair overwrites it

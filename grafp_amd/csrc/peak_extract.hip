@@ -28,6 +28,9 @@ __device__ __forceinline__ float block_reduce(float v, bool is_max, float *scrat
     return r;
 }
 
+// ReLU that lets NaN through, as torch's does: fmaxf(NaN, 0) is 0, which turned the 0/0 of a constant clip into zeros.
+__device__ __forceinline__ float relu_keep_nan(float v) { return v <= 0.0f ? 0.0f : v; }
+
 // Build img[3][HP][WP] (zero padded) in LDS from one clip.  Returns nothing; ends with a barrier.
 // WP = row pitch of the padded image in floats (>= W + 2 * pw).
 __device__ __forceinline__ void build_image(float *img, float *scratch, const float *__restrict__ spec, int H, int W,
@@ -82,7 +85,7 @@ __global__ __launch_bounds__(PK_THREADS) void peak_fwd_kernel(const float *__res
                 const float *wr = wf + (ci * KH + ky) * KW;
                 for (int kx = 0; kx < KW; ++kx) acc = __builtin_fmaf(wr[kx], row[kx], acc);
             }
-        ob[i] = fmaxf(acc, 0.0f);
+        ob[i] = relu_keep_nan(acc);
     }
 }
 
@@ -210,7 +213,7 @@ __global__ __launch_bounds__(PK_THREADS) void peak_fwd8_kernel(const float *__re
         for (int f = 0; f < F; ++f) {
             f32x4 o;
 #pragma unroll
-            for (int px = 0; px < 4; ++px) o[px] = fmaxf(acc[f][px], 0.0f);
+            for (int px = 0; px < 4; ++px) o[px] = relu_keep_nan(acc[f][px]);
             *reinterpret_cast<f32x4 *>(ob + (size_t)f * Ho * W + y * W + x0) = o;
         }
     }

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import _frontend_ref as fr
 from _common import golden, hash_ints, hash_normalish, hash_uniform, knn_margin_mask
 
 pytestmark = pytest.mark.gpu
@@ -365,6 +366,107 @@ def test_whole_track_segments_vs_oracle(dev):
     np.testing.assert_allclose(b.cpu().numpy(), om.logmel(t(x[:, 16000:32000]), CFG).numpy(), atol=2e-3)
 
 
+def _empty_bands(n_fft, n_mels):
+    from oracle import model as om
+    return ~(om.mel_filterbank(n_fft // 2 + 1, n_mels, fr.FS) > 0).any(dim=0)
+
+
+@pytest.mark.parametrize("case", fr.LOGMEL_CASES, ids=fr.LOGMEL_IDS)
+def test_logmel_vs_float64(dev, case):
+    """Both log-mel kernels against the float64 reference (_frontend_ref.logmel_power64) at their edge shapes: frame counts
+    odd and even, 16 / 33 / 40 bands (filters wider than the staged 48 bins, the lane-to-band mappings below 64 bands),
+    a zero-padded window, hop != n_fft / 2, every n_fft of the radix-2 kernel, bands without a bin, and signal edges.
+    With Pg = 10^(got / 10), Pc = max(P64, 1e-10) and M the loudest band of the frame:
+      (1) where Pc >= 1e-4 M:  |got - 10 log10 Pc| <= 2e-3 dB, the project's bar (the f32 torch path is within 3e-5 dB
+          there, so the reference leaves the bar to the kernel); it must cover every entry on noise (99.8 % at 256 / 128
+          bands, whose one-bin bands cannot all be loud: _frontend_ref.min_loud_share) and at least 5 % on the tone;
+      (2) everywhere:  |Pg - Pc| <= 4.7e-4 Pc + c M.  A quiet band next to a loud one sits on the f32 transform's noise
+          floor: its dB value is not determined, its power relative to the frame is.  c = 16 c_ref = 1.36e-5, where
+          c_ref = 8.5e-7 bounds max |P32 - Pc| / M of the f32 torch path (oracle.model.logmel) against the same float64
+          reference on these very inputs -- measured by test_frontend_cpu.py::test_logmel_f32_oracle_vs_float64 on an
+          x86-64 host (8.3e-7 at most), which asserts it.  The factor 16 is four bits for the register kernel's 31-step
+          twiddle recurrence and the radix-2 ordering against pocketfft.
+    Bands without a bin and the all-zero input give exactly -100.0; the 3e-7 noise straddles the clamp (only (2))."""
+    from grafp_amd import ops
+    name, (n_fft, win_len, hop, n_mels), B, T, signal = case
+    x, p64 = fr.logmel_case_ref(case)
+    xt = t(x).to(dev)
+    if name.endswith("-1d"):
+        got = ops.logmel(xt[0], fr.FS, n_fft, win_len, hop, n_mels)
+        assert got.shape == (n_mels, 1 + T // hop)
+        got = got.unsqueeze(0)
+    else:
+        got = ops.logmel(xt, fr.FS, n_fft, win_len, hop, n_mels)
+    got = got.cpu()
+    assert got.shape == (B, n_mels, 1 + T // hop) and got.dtype == torch.float32 and got.is_contiguous()
+    assert bool(torch.isfinite(got).all())
+    e = fr.logmel_errors(got, p64)
+    empty = _empty_bands(n_fft, n_mels)
+    share = float(e["loud"][:, ~empty].double().mean())
+    loud_db = float(e["db_err"][e["loud"]].max())
+    need_c = float(e["floor_excess"].max())
+    print(f"\n[frontend] logmel {name}: loud share={share:.4f} loud entries {loud_db:.2e} dB; "
+          f"all entries need c={need_c:.2e} (c={fr.C_FLOOR:.2e})")
+    assert bool(empty.any()) == (name == "g256-128bands-empty")
+    assert bool((got[:, empty] == -100.0).all())
+    if signal == "zeros":
+        assert bool((got == -100.0).all())
+    if signal == "quiet":
+        clamped = p64 < fr.POWER_FLOOR
+        assert bool(clamped.any()) and bool((~clamped).any())
+    else:
+        assert share >= fr.min_loud_share(case)
+        assert loud_db <= fr.DB_BAR
+    assert need_c <= fr.C_FLOOR
+
+
+@pytest.mark.parametrize("cfg", [(1024, 1024, 512, 64), (512, 512, 256, 64)], ids=["register", "radix2"])
+def test_logmel_row_stride(dev, cfg):
+    """The C entry on rows that are wider than the signal (wav_stride = T + 37, the tails NaN): the same bits as the
+    wrapper gives on the contiguous copy, and no NaN -- nothing past T is read into a frame."""
+    from grafp_amd import ops
+    n_fft, win_len, hop, n_mels = cfg
+    B, T = 3, 4000
+    x = t(0.1 * hash_normalish(f"frontend:logmel.stride.{n_fft}", (B, T))).to(dev)
+    buf = torch.full((B, T + 37), float("nan"), device=dev)
+    buf[:, :T] = x
+    plan = ops._mel_plan(x.device, fr.FS, n_fft, win_len, n_mels)
+    out = torch.full((B, n_mels, 1 + T // hop), float("nan"), device=dev)
+    ops.check(ops.lib.grafp_logmel_f32(ops._p(buf), T + 37, B, T, n_fft, hop, n_mels, ops._p(plan.window),
+                                       ops._p(plan.twiddle), ops._p(plan.fb), ops._p(plan.band_lo), ops._p(plan.band_hi),
+                                       ops._p(out), ops._stream()), "logmel")
+    want = ops.logmel(x, fr.FS, n_fft, win_len, hop, n_mels)
+    assert not bool(torch.isnan(out).any())
+    assert torch.equal(out, want)
+
+
+def test_logmel_argument_checks(dev):
+    from grafp_amd import ops
+    with pytest.raises(RuntimeError, match="reflect padding needs T=512 > n_fft/2=512"):
+        ops.logmel(torch.zeros(1, 512, device=dev))
+    with pytest.raises(RuntimeError, match="n_fft=768 not in"):
+        ops.logmel(torch.zeros(1, 4000, device=dev), n_fft=768, win_len=768, hop=384)
+    with pytest.raises(RuntimeError, match="bad B=1 hop=512 n_mels=257"):
+        ops.logmel(torch.zeros(1, 4000, device=dev), n_mels=257)
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("n_mels,n_frames,size,step", fr.UNFOLD_CASES)
+def test_unfold_segments_exact(dev, n_mels, n_frames, size, step):
+    """unfold_segments is a copy: equal to the strided view, bit for bit -- one segment, none (a track shorter than a
+    segment), a step beyond the size, size 1, and 557 segments (1.14 M elements: more than the 4096 x 256 one sweep of
+    the grid covers, so the grid-stride loop runs)."""
+    from grafp_amd import ops
+    spec = t(hash_normalish(f"frontend:unfold.{n_mels}.{n_frames}", (n_mels, n_frames)))
+    want = fr.unfold64(spec, size, step)
+    got = ops.unfold_segments(spec.to(dev), size, step)
+    n_seg = (n_frames - size) // step + 1 if n_frames >= size else 0
+    assert got.shape == want.shape == (n_seg, n_mels, size) and got.is_contiguous() and got.dtype == torch.float32
+    if (n_mels, n_frames) == (64, 1700):
+        assert got.numel() > 4096 * 256
+    assert torch.equal(got.cpu(), want)
+
+
 # =============================================================== peak extractor
 def test_peak_extract_forward_backward(dev):
     """Tolerance 1e-4 relative / 1e-5 absolute (147-term f32 dot products in a different order)."""
@@ -421,6 +523,78 @@ def test_peak_extract_backward_many_clips_bit_reproducible(dev, B, F, K, W):
     np.testing.assert_allclose(grads[0][1].cpu().numpy()[keep], bias.grad.numpy()[keep], rtol=1e-3,
                                atol=2e-5 * float(bias.grad.abs().max()))
     assert torch.equal(grads[0][0], grads[1][0]) and torch.equal(grads[0][1], grads[1][1])
+
+
+def _peak_on_gpu(dev, c, stride_h, backward=0):
+    """ops.peak_extract on a case of _frontend_ref.peak_case -> (out, [(dweight, dbias)] * backward), on the CPU."""
+    from grafp_amd import ops
+    spec, g = c["spec"].to(dev), c["g"].to(dev)
+    grads, out = [], None
+    for _ in range(max(backward, 1)):
+        w = c["w"].to(dev).requires_grad_(True)
+        b = c["b"].to(dev).requires_grad_(True)
+        out = ops.peak_extract(spec, w, b, stride_h)
+        if backward:
+            out.backward(g)
+            grads.append((w.grad.cpu(), b.grad.cpu()))
+    return out.detach().cpu(), grads
+
+
+@pytest.mark.parametrize("shape", fr.PEAK_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_peak_extract_vs_float64(dev, shape):
+    """The register-blocked kernels (8 filters, 7x7, 32 frames) at H odd, tiny, above 64 (the backward kernel's second
+    staging branch) and strides 1 / 2 / 3, the generic kernels at other filter counts, widths and non-square / 1x1 taps, and
+    more clips than workgroups, against _frontend_ref.peak_extract64.  The upstream gradient is zero wherever the float64
+    pre-activation is within 1e-4 of zero (at most 1e-3 of the positions: asserted), so the gradients do not depend on
+    which way a borderline ReLU fell and every filter is compared.
+      forward    |out - relu(z)| <= 1e-5 + 1e-4 |relu(z)|      (the project's bar, now against float64)
+      mask       (out > 0) == (z > 0) wherever |z| >= 1e-4
+      gradients  max|d - d64| <= 2e-5 max|d64| for dweight and dbias (1e-4 over the 600 clips; the f32 torch path measures
+                 7e-7 and 7e-6: test_frontend_cpu.py)
+      two backward calls give the same bits."""
+    c = fr.peak_case(shape)
+    share = float(c["ambiguous"].double().mean())
+    assert share <= 1e-3, share
+    out, grads = _peak_on_gpu(dev, c, shape[6], backward=2)
+    assert out.shape == c["out64"].shape and out.dtype == torch.float32
+    fwd = fr.forward_excess(out, c["out64"])
+    keep = ~c["ambiguous"]
+    ew, eb = fr.rel_max(grads[0][0], c["dw64"]), fr.rel_max(grads[0][1], c["db64"])
+    print(f"\n[frontend] peak {shape}: ambiguous share={share:.1e} forward excess={fwd:.1e} dW={ew:.1e} dbias={eb:.1e} "
+          f"(of max; bar {fr.peak_grad_bar(shape):.0e})")
+    assert fwd <= 0.0
+    assert torch.equal((out > 0)[keep], (c["z"] > 0)[keep])
+    assert grads[0][0].shape == c["dw64"].shape and grads[0][1].shape == c["db64"].shape
+    assert ew <= fr.peak_grad_bar(shape) and eb <= fr.peak_grad_bar(shape)
+    assert torch.equal(grads[0][0], grads[1][0]) and torch.equal(grads[0][1], grads[1][1])
+
+
+@pytest.mark.parametrize("shape", [(3, 64, 32, 8, 7, 7, 2), (3, 33, 20, 5, 5, 3, 2)], ids=["fast", "generic"])
+def test_peak_extract_constant_clip(dev, shape):
+    """A silent segment (every value -100) between two ordinary clips: its min-max scaling is 0 / 0, so every output of
+    that clip is NaN as in the reference, and the neighbours are untouched."""
+    from grafp_amd import ops
+    spec, w, b = fr.peak_inputs(shape)
+    spec = spec.clone()
+    spec[1] = -100.0
+    want, _z = fr.peak_extract64(spec, w, b, shape[6])
+    assert bool(torch.isnan(want[1]).all()) and not bool(torch.isnan(want[[0, 2]]).any())
+    out = ops.peak_extract(spec.to(dev), w.to(dev), b.to(dev), shape[6]).cpu()
+    assert fr.forward_excess(out[[0, 2]], want[[0, 2]]) <= 0.0
+    assert bool(torch.isnan(out[1]).all())
+
+
+def test_peak_extract_argument_checks(dev):
+    from grafp_amd import ops
+    spec = torch.zeros(2, 64, 32, device=dev)
+    with pytest.raises(RuntimeError, match="peak_extract_fwd: bad shape B=2 H=64 W=32 F=8 K=4x7"):
+        ops.peak_extract(spec, torch.zeros(8, 3, 4, 7, device=dev), torch.zeros(8, device=dev), 2)
+    with pytest.raises(ValueError, match="expects 3 input planes"):
+        ops.peak_extract(spec, torch.zeros(8, 2, 7, 7, device=dev), torch.zeros(8, device=dev), 2)
+    with pytest.raises(RuntimeError, match=r"peak_extract_fwd: needs \d+ B of LDS"):
+        ops.peak_extract(torch.zeros(1, 512, 32, device=dev), torch.zeros(8, 3, 7, 7, device=dev),
+                         torch.zeros(8, device=dev), 2)
+    torch.cuda.synchronize()
 
 
 def test_peak_extract_reference_golden(dev):
