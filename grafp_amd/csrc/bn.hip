@@ -44,11 +44,27 @@ __device__ __forceinline__ float2 block_sum2(float a, float b, float2 *scratch, 
 }
 
 __device__ __forceinline__ float act_fwd(float u, int act, float slope) {
-    return act == 0 ? u : (u > 0.0f ? u : (act == 1 ? 0.0f : u * slope));
+    return act == 0 ? u : (act == 1 ? relu_keep_nan(u) : (u > 0.0f ? u : u * slope));
 }
 __device__ __forceinline__ float act_grad(float u, int act, float slope) {
     return act == 0 ? 1.0f : (u > 0.0f ? 1.0f : (act == 1 ? 0.0f : slope));
 }
+
+// The forward folds the normalisation into ONE fma per element, z = act(fma(x, g, off)) with g = gamma invstd and
+// off = beta + (pb - mean) g.  off is rounded at the magnitude of (mean - pb) g, so a row whose mean lies hundreds of
+// standard deviations from zero -- a constant non-zero row: invstd = 1/sqrt(eps) -- would lose that much of a result of
+// magnitude beta (measured on a row constant at 3.0: 9.4e-5 against float64).  Such rows subtract first,
+// fma((x + pb) - mean, g, beta) (x + pb rounds as the statistics' shift did, so the difference is exact where it
+// cancels).  The choice is uniform over a row and view; rows of ordinary statistics keep the folded form and its bits.
+constexpr float BN_FOLD_MAX = 64.0f;      // folded form up to |(mean - pb) g| = 64: 2 ulp(64) = 1.5e-5 absolute at most
+struct BnNorm {
+    float g, off, pb, mean, be;
+    __device__ __forceinline__ bool centred() const { return fabsf((mean - pb) * g) > BN_FOLD_MAX; }
+    template <bool CENTRED>
+    __device__ __forceinline__ float pre(float x) const {
+        return CENTRED ? __builtin_fmaf((x + pb) - mean, g, be) : __builtin_fmaf(x, g, off);
+    }
+};
 
 // ---- forward pass 1: partial shifted sums --------------------------------------------------------
 template <typename T, bool VEC>
@@ -119,7 +135,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_kernel(const T *__restric
         }
         const float shift = ElemIO<T>::ld1(row + (int64_t)grp * Mg) + pb;
         const float dm = a / (float)Mg;
-        const float var = fmaxf(q / (float)Mg - dm * dm, 0.0f);
+        const float var = relu_keep_nan(q / (float)Mg - dm * dm);
         mean = shift + dm;
         invstd = 1.0f / sqrtf(var + eps);
         if (sl == 0 && tid == 0) {
@@ -137,7 +153,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_kernel(const T *__restric
                 }
                 const float sh2 = ElemIO<T>::ld1(row + (int64_t)g2 * Mg) + pb;
                 const float dm2 = a2 / (float)Mg;
-                const float var2 = fmaxf(q2 / (float)Mg - dm2 * dm2, 0.0f);
+                const float var2 = relu_keep_nan(q2 / (float)Mg - dm2 * dm2);
                 const float unbiased = Mg > 1 ? var2 * ((float)Mg / (float)(Mg - 1)) : var2;
                 rm = (1.0f - momentum) * rm + momentum * (sh2 + dm2);
                 rv = (1.0f - momentum) * rv + momentum * unbiased;
@@ -154,58 +170,64 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_kernel(const T *__restric
         }
     }
     const float g = gamma[c] * invstd;
-    const float off = beta[c] + (pb - mean) * g;      // z = act(x*g + off) + r
+    const float off = beta[c] + (pb - mean) * g;      // z = act(x*g + off) + r (BnNorm)
+    const BnNorm nrm = {g, off, pb, mean, beta[c]};
     const T *rrow = residual ? residual + (size_t)c * M : nullptr;
     T *orow = out + (size_t)c * M;
     const int64_t gend = (int64_t)(grp + 1) * Mg;
     const int64_t lo = (int64_t)grp * Mg + (int64_t)sl * chunk, hi = (lo + chunk < gend) ? lo + chunk : gend;
     constexpr int W = VEC ? ElemIO<T>::W : 1;
     int64_t m = lo + (int64_t)tid * W;
-    if (VEC) {
-        // four vectors in flight per thread (one load -> use -> store per iteration left the kernel latency-bound at
-        // ~4.7 TB/s; this is the eval-mode / fingerprinting path)
-        constexpr int U = 4;
-        const int64_t step = (int64_t)BN_THREADS * W;
-        for (; m + (U - 1) * step + W <= hi; m += U * step) {
-            typename ElemIO<T>::Raw rx[U], rr[U];
+    auto apply = [&](auto cen_c) {
+        constexpr bool CEN = decltype(cen_c)::value;
+        if (VEC) {
+            // four vectors in flight per thread (one load -> use -> store per iteration left the kernel latency-bound at
+            // ~4.7 TB/s; this is the eval-mode / fingerprinting path)
+            constexpr int U = 4;
+            const int64_t step = (int64_t)BN_THREADS * W;
+            for (; m + (U - 1) * step + W <= hi; m += U * step) {
+                typename ElemIO<T>::Raw rx[U], rr[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                rx[u] = *reinterpret_cast<const typename ElemIO<T>::Raw *>(row + m + u * step);
-                if (rrow) rr[u] = *reinterpret_cast<const typename ElemIO<T>::Raw *>(rrow + m + u * step);
+                for (int u = 0; u < U; ++u) {
+                    rx[u] = *reinterpret_cast<const typename ElemIO<T>::Raw *>(row + m + u * step);
+                    if (rrow) rr[u] = *reinterpret_cast<const typename ElemIO<T>::Raw *>(rrow + m + u * step);
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    float v[ElemIO<T>::W], r[ElemIO<T>::W];
+                    ElemIO<T>::unpack(rx[u], v);
+                    if (rrow) ElemIO<T>::unpack(rr[u], r);
+#pragma unroll
+                    for (int i = 0; i < ElemIO<T>::W; ++i) {
+                        v[i] = act_fwd(nrm.template pre<CEN>(v[i]), act, slope);
+                        if (rrow) v[i] += r[i];
+                    }
+                    ElemIO<T>::store(orow + m + u * step, v, false);
+                }
             }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
+        }
+        for (; m < hi; m += (int64_t)BN_THREADS * W) {
+            if (VEC && m + W <= hi) {
                 float v[ElemIO<T>::W], r[ElemIO<T>::W];
-                ElemIO<T>::unpack(rx[u], v);
-                if (rrow) ElemIO<T>::unpack(rr[u], r);
+                ElemIO<T>::load(row + m, v);
+                if (rrow) ElemIO<T>::load(rrow + m, r);
 #pragma unroll
                 for (int i = 0; i < ElemIO<T>::W; ++i) {
-                    v[i] = act_fwd(__builtin_fmaf(v[i], g, off), act, slope);
+                    v[i] = act_fwd(nrm.template pre<CEN>(v[i]), act, slope);
                     if (rrow) v[i] += r[i];
                 }
-                ElemIO<T>::store(orow + m + u * step, v, false);
+                ElemIO<T>::store(orow + m, v, false);
+            } else {
+                for (int i = 0; i < W && m + i < hi; ++i) {
+                    float z = act_fwd(nrm.template pre<CEN>(ElemIO<T>::ld1(row + m + i)), act, slope);
+                    if (rrow) z += ElemIO<T>::ld1(rrow + m + i);
+                    ElemIO<T>::st1(orow + m + i, z);
+                }
             }
         }
-    }
-    for (; m < hi; m += (int64_t)BN_THREADS * W) {
-        if (VEC && m + W <= hi) {
-            float v[ElemIO<T>::W], r[ElemIO<T>::W];
-            ElemIO<T>::load(row + m, v);
-            if (rrow) ElemIO<T>::load(rrow + m, r);
-#pragma unroll
-            for (int i = 0; i < ElemIO<T>::W; ++i) {
-                v[i] = act_fwd(__builtin_fmaf(v[i], g, off), act, slope);
-                if (rrow) v[i] += r[i];
-            }
-            ElemIO<T>::store(orow + m, v, false);
-        } else {
-            for (int i = 0; i < W && m + i < hi; ++i) {
-                float z = act_fwd(__builtin_fmaf(ElemIO<T>::ld1(row + m + i), g, off), act, slope);
-                if (rrow) z += ElemIO<T>::ld1(rrow + m + i);
-                ElemIO<T>::st1(orow + m + i, z);
-            }
-        }
-    }
+    };
+    if (nrm.centred()) apply(std::true_type{});
+    else apply(std::false_type{});
 }
 
 // ---- backward pass 1: partial sums of dy and dy * xhat ----------------------------------------------
@@ -307,14 +329,14 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_dx_kernel(const T *__restri
             for (int i = 0; i < ElemIO<T>::W; ++i) {
                 const float xh = ((v[i] + pb) - mean) * invstd;
                 const float dy = d[i] * act_grad(__builtin_fmaf(xh, ga, be), act, slope);
-                v[i] = k * ((dy - m1) - xh * m2);
+                v[i] = training ? k * ((dy - m1) - xh * m2) : k * dy;      // (eval: no xh * 0, which is NaN for a non-finite x)
             }
             ElemIO<T>::store(orow + m, v, false);
         } else {
             for (int i = 0; i < W && m + i < hi; ++i) {
                 const float xh = ((ElemIO<T>::ld1(row + m + i) + pb) - mean) * invstd;
                 const float dy = ElemIO<T>::ld1(grow + m + i) * act_grad(__builtin_fmaf(xh, ga, be), act, slope);
-                ElemIO<T>::st1(orow + m + i, k * ((dy - m1) - xh * m2));
+                ElemIO<T>::st1(orow + m + i, training ? k * ((dy - m1) - xh * m2) : k * dy);
             }
         }
     }
@@ -500,7 +522,7 @@ __global__ __launch_bounds__(BN1_THREADS) void bn_fwd1_kernel(const T *__restric
         q += sp[i].y;
     }
     const float dm = a / (float)Mg;
-    const float var = fmaxf(q / (float)Mg - dm * dm, 0.0f);
+    const float var = relu_keep_nan(q / (float)Mg - dm * dm);
     const float mean = shift + dm;
     const float invstd = 1.0f / sqrtf(var + eps);
     if (sl == 0 && tid == 0) {
@@ -517,7 +539,7 @@ __global__ __launch_bounds__(BN1_THREADS) void bn_fwd1_kernel(const T *__restric
             }
             const float sh2 = ElemIO<T>::ld1(row + (int64_t)g2 * Mg) + pb;
             const float dm2 = a2 / (float)Mg;
-            const float var2 = fmaxf(q2 / (float)Mg - dm2 * dm2, 0.0f);
+            const float var2 = relu_keep_nan(q2 / (float)Mg - dm2 * dm2);
             const float unbiased = Mg > 1 ? var2 * ((float)Mg / (float)(Mg - 1)) : var2;
             rm = (1.0f - momentum) * rm + momentum * (sh2 + dm2);
             rv = (1.0f - momentum) * rv + momentum * unbiased;
@@ -527,22 +549,28 @@ __global__ __launch_bounds__(BN1_THREADS) void bn_fwd1_kernel(const T *__restric
     }
     const float g = gamma[c] * invstd;
     const float off = beta[c] + (pb - mean) * g;
+    const BnNorm nrm = {g, off, pb, mean, beta[c]};
     T *orow = out + (size_t)c * M;
+    auto apply = [&](auto cen_c) {
+        constexpr bool CEN = decltype(cen_c)::value;
 #pragma unroll
-    for (int it = 0; it < ITEMS; ++it) {
-        const int64_t m = lo + ((int64_t)it * BN1_THREADS + tid) * W;
-        if (m < hi) {
-            float v[W], rr[W];
-            ElemIO<T>::unpack(raw[it], v);
-            if (RES) ElemIO<T>::unpack(rres[it], rr);
+        for (int it = 0; it < ITEMS; ++it) {
+            const int64_t m = lo + ((int64_t)it * BN1_THREADS + tid) * W;
+            if (m < hi) {
+                float v[W], rr[W];
+                ElemIO<T>::unpack(raw[it], v);
+                if (RES) ElemIO<T>::unpack(rres[it], rr);
 #pragma unroll
-            for (int i = 0; i < W; ++i) {
-                v[i] = act_fwd(__builtin_fmaf(v[i], g, off), act, slope);
-                if (RES) v[i] += rr[i];
+                for (int i = 0; i < W; ++i) {
+                    v[i] = act_fwd(nrm.template pre<CEN>(v[i]), act, slope);
+                    if (RES) v[i] += rr[i];
+                }
+                ElemIO<T>::store(orow + m, v, false);
             }
-            ElemIO<T>::store(orow + m, v, false);
         }
-    }
+    };
+    if (nrm.centred()) apply(std::true_type{});
+    else apply(std::false_type{});
     if (tid == 0) bn1_rearm(checkout, S, counter, slots_row);
 }
 
@@ -709,6 +737,60 @@ static BnPlan bn_plan(int C, int64_t Mg, int G, int W) {
     return p;
 }
 
+// The launch a call takes: ONE function for grafp_bn_fwd_1pass, grafp_bn_bwd_1pass and grafp_bn_plan, so the query cannot
+// drift from the launches.  vec = bn_vec_ok of the call's pointers; have_sync = a rendezvous buffer was passed.
+enum { BN_PATH_1PASS = 0, BN_PATH_2PASS_VEC = 1, BN_PATH_2PASS_SCALAR = 2 };
+struct BnLaunch {
+    int path;
+    int items;          // single pass: 16-byte vectors a thread holds per operand; two-pass: 0 (threads stride over the chunk)
+    int threads;
+    int Sg;             // chunks per view
+    int64_t chunk;      // elements per chunk (the last chunk of a view may be shorter)
+};
+static BnLaunch bn_choose(int dtype, int C, int64_t Mg, int G, bool training, bool backward, bool vec, bool have_sync) {
+    const bool f32 = dtype == GRAFP_F32;
+    const int W = f32 ? 4 : 8;
+    BnLaunch L;
+    if (have_sync && training && !backward) {
+        const int Sg = vec ? bn1_plan(Mg, G, W, BN1_ITEMS_FWD) : 0;
+        if (Sg > 0) {
+            L = {BN_PATH_1PASS, BN1_ITEMS_FWD, BN1_THREADS, Sg, (int64_t)BN1_THREADS * BN1_ITEMS_FWD * W};
+            return L;
+        }
+    }
+    if (have_sync && training && backward) {
+        // from 16 chunks per row the rendezvous runs over fewer, larger chunks: 8 vectors per thread and operand instead
+        // of 4 (tools/bn_bench.py, threshold swept 0 ... 128: 16 is best at 256, 512 and 2048 clip-views; with the
+        // operands fenced across the wait -- bn_opaque -- this variant needs 122 VGPRs, 4 workgroups per CU)
+        int items = BN1_ITEMS_BWD;
+        int Sg = vec ? bn1_plan(Mg, G, W, items) : 0;
+        const int items8_from = GRAFP_TUNE_INT("GRAFP_BN_BWD_ITEMS8_FROM", 16);
+        if (vec && !f32 && (Sg == 0 || Sg * G > items8_from)) {
+            items = 2 * BN1_ITEMS_BWD;
+            Sg = bn1_plan(Mg, G, 8, items);
+        }
+        // ... and from 32 chunks per view on 512-thread workgroups: half the chunks again with the same registers per
+        // thread and the same waves per CU (two workgroups instead of four).  tools/bn_bench.py at 2048 clip-views: 64
+        // chunks per view (stage 0) 783 -> 703 us, 32 (stage 1) 681 -> 650; from 16 chunks (stage 2) it loses 1 %, and
+        // 1024-thread workgroups -- ONE per CU, whose phases overlap nobody's -- lose 10-20 % everywhere.
+        const int t512_from = GRAFP_TUNE_INT("GRAFP_BN_BWD_T512_FROM", 32);
+        if (vec && !f32 && t512_from > 0 && items == 2 * BN1_ITEMS_BWD && Sg >= t512_from) {
+            const int Sg2 = bn1_plan(Mg, G, 8, items, 512);
+            if (Sg2 > 0) {
+                L = {BN_PATH_1PASS, items, 512, Sg2, (int64_t)512 * items * W};
+                return L;
+            }
+        }
+        if (Sg > 0) {
+            L = {BN_PATH_1PASS, items, BN1_THREADS, Sg, (int64_t)BN1_THREADS * items * W};
+            return L;
+        }
+    }
+    const BnPlan p = bn_plan(C, Mg, G, vec ? W : 1);
+    L = {vec ? BN_PATH_2PASS_VEC : BN_PATH_2PASS_SCALAR, 0, BN_THREADS, p.Sg, p.chunk};
+    return L;
+}
+
 // W = ElemIO<T>::W: whole 16-byte pieces at 16-byte aligned addresses
 static bool bn_vec_ok(int W, const void *a, const void *b, const void *c, const void *d, int64_t Mg) {
     const uintptr_t m = (uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d;
@@ -756,23 +838,21 @@ extern "C" int grafp_bn_fwd_1pass(const void *x, int dtype, int C, int64_t M, in
     float *part = (float *)ws;
     const int W = dtype == GRAFP_F32 ? 4 : 8;
     const bool vec = bn_vec_ok(W, x, out, residual, nullptr, Mg);
-    if (sync && training) {
-        const int Sg = vec ? bn1_plan(Mg, G, W, BN1_ITEMS_FWD) : 0;
-        if (Sg > 0) {
-            for_elem(dtype, [&](auto te) {
-                using T = typename decltype(te)::type;
-                for_bool(residual != nullptr, [&](auto res) {
-                    hipLaunchKernelGGL((bn_fwd1_kernel<T, decltype(res)::value>), dim3(Sg * G, C), dim3(BN1_THREADS), 0, s,
-                                       (const T *)x, M, Mg, Sg, G, pre_bias, gamma, beta, (const T *)residual, act, slope,
-                                       eps, momentum, running_mean, running_var, (int *)sync, (T *)out, save_mean,
-                                       save_invstd, spin);
-                });
+    const BnLaunch p = bn_choose(dtype, C, Mg, G, training != 0, false, vec, sync != nullptr);
+    if (p.path == BN_PATH_1PASS) {
+        const int Sg = p.Sg;
+        for_elem(dtype, [&](auto te) {
+            using T = typename decltype(te)::type;
+            for_bool(residual != nullptr, [&](auto res) {
+                hipLaunchKernelGGL((bn_fwd1_kernel<T, decltype(res)::value>), dim3(Sg * G, C), dim3(BN1_THREADS), 0, s,
+                                   (const T *)x, M, Mg, Sg, G, pre_bias, gamma, beta, (const T *)residual, act, slope,
+                                   eps, momentum, running_mean, running_var, (int *)sync, (T *)out, save_mean,
+                                   save_invstd, spin);
             });
-            GRAFP_CHECK_LAUNCH("bn_fwd1_kernel");
-            return GRAFP_OK;
-        }
+        });
+        GRAFP_CHECK_LAUNCH("bn_fwd1_kernel");
+        return GRAFP_OK;
     }
-    const BnPlan p = bn_plan(C, Mg, G, vec ? W : 1);
     const dim3 grid(p.Sg * G, C);
     for_elem(dtype, [&](auto te) {
         using T = typename decltype(te)::type;
@@ -821,7 +901,8 @@ extern "C" int grafp_bn_bwd_1pass(const void *x, const void *dz, int dtype, int 
     const bool f32 = dtype == GRAFP_F32;
     const int W = f32 ? 4 : 8;
     const bool ok = bn_vec_ok(W, x, dz, dx, nullptr, Mg);
-    if (sync && training) {
+    const BnLaunch p = bn_choose(dtype, C, Mg, G, training != 0, true, ok, sync != nullptr);
+    if (p.path == BN_PATH_1PASS) {
         // one launch of the single-pass kernel <T, ITEMS, THREADS> over sg chunks per view
         auto launch1 = [&](auto te, auto items_c, auto threads_c, int sg, int plain) {
             using T = typename decltype(te)::type;
@@ -834,39 +915,14 @@ extern "C" int grafp_bn_bwd_1pass(const void *x, const void *dz, int dtype, int 
         using Items2 = std::integral_constant<int, 2 * BN1_ITEMS_BWD>;
         using T256 = std::integral_constant<int, BN1_THREADS>;
         using T512 = std::integral_constant<int, 512>;
-        // from 16 chunks per row the rendezvous runs over fewer, larger chunks: 8 vectors per thread and operand instead
-        // of 4 (tools/bn_bench.py, threshold swept 0 ... 128: 16 is best at 256, 512 and 2048 clip-views; with the
-        // operands fenced across the wait -- bn_opaque -- this variant needs 122 VGPRs, 4 workgroups per CU)
-        int items = BN1_ITEMS_BWD;
-        int Sg = ok ? bn1_plan(Mg, G, W, items) : 0;
         const int plain = plain_stores((size_t)C * (size_t)M * (f32 ? 4 : 2), "GRAFP_BN_BWD_PLAIN_MAX_MB", 140);
-        const int items8_from = GRAFP_TUNE_INT("GRAFP_BN_BWD_ITEMS8_FROM", 16);
-        if (ok && !f32 && (Sg == 0 || Sg * G > items8_from)) {
-            items = 2 * BN1_ITEMS_BWD;
-            Sg = bn1_plan(Mg, G, 8, items);
-        }
-        // ... and from 32 chunks per view on 512-thread workgroups: half the chunks again with the same registers per
-        // thread and the same waves per CU (two workgroups instead of four).  tools/bn_bench.py at 2048 clip-views: 64
-        // chunks per view (stage 0) 783 -> 703 us, 32 (stage 1) 681 -> 650; from 16 chunks (stage 2) it loses 1 %, and
-        // 1024-thread workgroups -- ONE per CU, whose phases overlap nobody's -- lose 10-20 % everywhere.
-        const int t512_from = GRAFP_TUNE_INT("GRAFP_BN_BWD_T512_FROM", 32);
-        if (ok && !f32 && t512_from > 0 && items == 2 * BN1_ITEMS_BWD && Sg >= t512_from) {
-            const int Sg2 = bn1_plan(Mg, G, 8, items, 512);
-            if (Sg2 > 0) {
-                launch1(TypeTag<unsigned short>{}, Items2{}, T512{}, Sg2, plain);
-                GRAFP_CHECK_LAUNCH("bn_bwd1_kernel");
-                return GRAFP_OK;
-            }
-        }
-        if (Sg > 0) {
-            if (f32) launch1(TypeTag<float>{}, Items1{}, T256{}, Sg, plain);
-            else if (items == BN1_ITEMS_BWD) launch1(TypeTag<unsigned short>{}, Items1{}, T256{}, Sg, plain);
-            else launch1(TypeTag<unsigned short>{}, Items2{}, T256{}, Sg, plain);
-            GRAFP_CHECK_LAUNCH("bn_bwd1_kernel");
-            return GRAFP_OK;
-        }
+        if (f32) launch1(TypeTag<float>{}, Items1{}, T256{}, p.Sg, plain);
+        else if (p.threads == 512) launch1(TypeTag<unsigned short>{}, Items2{}, T512{}, p.Sg, plain);
+        else if (p.items == BN1_ITEMS_BWD) launch1(TypeTag<unsigned short>{}, Items1{}, T256{}, p.Sg, plain);
+        else launch1(TypeTag<unsigned short>{}, Items2{}, T256{}, p.Sg, plain);
+        GRAFP_CHECK_LAUNCH("bn_bwd1_kernel");
+        return GRAFP_OK;
     }
-    const BnPlan p = bn_plan(C, Mg, G, ok ? W : 1);
     const dim3 grid(p.Sg * G, C);
     for_elem(dtype, [&](auto te) {
         using T = typename decltype(te)::type;
@@ -889,4 +945,24 @@ extern "C" int grafp_bn_bwd(const void *x, const void *dz, int dtype, int C, int
                             float *dpre_bias, void *ws, size_t ws_bytes, grafp_stream_t stream) {
     return grafp_bn_bwd_1pass(x, dz, dtype, C, M, groups, pre_bias, gamma, beta, save_mean, save_invstd, act, slope,
                               training, dx, dgamma, dbeta, dpre_bias, ws, ws_bytes, nullptr, -1, stream);
+}
+
+extern "C" int grafp_bn_plan(int dtype, int C, int64_t M, int groups, int training, int backward, int aligned,
+                             int have_sync, int *info) {
+    using namespace grafp;
+    GRAFP_REQUIRE(info, "bn_plan: null pointer");
+    GRAFP_REQUIRE(C > 0 && M > 0 && C <= 65535, "bn_plan: bad shape C=%d M=%lld", C, (long long)M);
+    GRAFP_REQUIRE(groups >= 1 && groups <= 8 && M % groups == 0, "bn_plan: groups=%d must be in [1,8] and divide M=%lld", groups, (long long)M);
+    GRAFP_REQUIRE(dtype == GRAFP_F32 || dtype == GRAFP_BF16, "bn_plan: dtype %d not in {f32, bf16}", dtype);
+    const int64_t Mg = M / groups;
+    const int W = dtype == GRAFP_F32 ? 4 : 8;
+    const BnLaunch p = bn_choose(dtype, C, Mg, groups, training != 0, backward != 0, aligned != 0 && Mg % W == 0,
+                                 have_sync != 0);
+    info[0] = p.path;
+    info[1] = p.items;
+    info[2] = p.threads;
+    info[3] = p.Sg;
+    info[4] = p.chunk > 0x7fffffff ? 0x7fffffff : (int)p.chunk;
+    for (int i = 5; i < 8; ++i) info[i] = 0;
+    return GRAFP_OK;
 }

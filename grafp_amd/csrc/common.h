@@ -30,6 +30,10 @@ __device__ __forceinline__ f32x16 mfma32x32x2(float a, float b, f32x16 c) {
 }
 __device__ __forceinline__ int mfma_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
 
+// ReLU (and the clamp of a variance at zero) that lets NaN through, as torch's does: fmaxf(NaN, 0) is 0, which turns a
+// poisoned row into zeros and a NaN variance into a finite one.
+__device__ __forceinline__ float relu_keep_nan(float v) { return v <= 0.0f ? 0.0f : v; }
+
 }  // namespace grafp
 
 // Streaming (non-temporal) store of a result row piece: the consumer is a later launch and the producers' working set

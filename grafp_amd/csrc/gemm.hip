@@ -381,7 +381,7 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::NW == 4 ? 2 : 1) void conv1x1_ge
                         float lo = bf16_lo(w[d]), hi = bf16_hi(w[d]);
                         lo = __builtin_fmaf(lo, t4[d].x, t4[d].y);
                         hi = __builtin_fmaf(hi, t4[d].z, t4[d].w);
-                        if (pro_act == 1) { lo = fmaxf(lo, 0.f); hi = fmaxf(hi, 0.f); }
+                        if (pro_act == 1) { lo = relu_keep_nan(lo); hi = relu_keep_nan(hi); }
                         else if (pro_act == 2) { lo = lo > 0.f ? lo : lo * pro_slope; hi = hi > 0.f ? hi : hi * pro_slope; }
                         w[d] = pack_bf16(lo, hi);
                     }
@@ -445,7 +445,7 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::NW == 4 ? 2 : 1) void conv1x1_ge
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) {
                                     v[e] = __builtin_fmaf(v[e], esc[ri].x, esc[ri].y);
-                                    if (epi_act == 1) v[e] = fmaxf(v[e], 0.f);
+                                    if (epi_act == 1) v[e] = relu_keep_nan(v[e]);
                                     else if (epi_act == 2) v[e] = v[e] > 0.f ? v[e] : v[e] * epi_slope;
                                 }
                                 p0 = pack_bf16(v[0], v[1]);
@@ -719,7 +719,7 @@ __global__ __launch_bounds__(256) void bn_affine_bf16_kernel(const unsigned shor
         for (int e = 0; e < 4; ++e) {
             float a = __builtin_fmaf(bf16_lo(w[e]), ss.x, ss.y);
             float b = __builtin_fmaf(bf16_hi(w[e]), ss.x, ss.y);
-            if (act == 1) { a = fmaxf(a, 0.f); b = fmaxf(b, 0.f); }
+            if (act == 1) { a = relu_keep_nan(a); b = relu_keep_nan(b); }
             else if (act == 2) { a = a > 0.f ? a : a * slope; b = b > 0.f ? b : b * slope; }
             if (rrow) { a += bf16_lo(q[e]); b += bf16_hi(q[e]); }
             o[e] = pack_bf16(a, b);

@@ -28,9 +28,7 @@ __device__ __forceinline__ float block_reduce(float v, bool is_max, float *scrat
     return r;
 }
 
-// ReLU that lets NaN through, as torch's does: fmaxf(NaN, 0) is 0, which turned the 0/0 of a constant clip into zeros.
-__device__ __forceinline__ float relu_keep_nan(float v) { return v <= 0.0f ? 0.0f : v; }
-
+// (relu_keep_nan of common.h: fmaxf(NaN, 0) is 0, which turned the 0/0 of a constant clip into zeros)
 // Build img[3][HP][WP] (zero padded) in LDS from one clip.  Returns nothing; ends with a barrier.
 // WP = row pitch of the padded image in floats (>= W + 2 * pw).
 __device__ __forceinline__ void build_image(float *img, float *scratch, const float *__restrict__ spec, int H, int W,

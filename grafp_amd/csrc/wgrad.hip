@@ -392,7 +392,7 @@ __global__ __launch_bounds__(CFG::THREADS) void wgrad_dma_kernel(
                         float lo = bf16_lo(w[d]), hi = bf16_hi(w[d]);
                         lo = __builtin_fmaf(lo, ssb[b].x, ssb[b].y);
                         hi = __builtin_fmaf(hi, ssb[b].x, ssb[b].y);
-                        if (pro_act == 1) { lo = fmaxf(lo, 0.f); hi = fmaxf(hi, 0.f); }
+                        if (pro_act == 1) { lo = relu_keep_nan(lo); hi = relu_keep_nan(hi); }
                         else if (pro_act == 2) { lo = lo > 0.f ? lo : lo * pro_slope; hi = hi > 0.f ? hi : hi * pro_slope; }
                         w[d] = pack_bf16(lo, hi);
                     }

@@ -221,6 +221,14 @@ int grafp_bn_bwd_1pass(const void *x, const void *dz, int dtype, int C, int64_t 
                        int act, float slope, int training, void *dx, float *dgamma, float *dbeta,
                        float *dpre_bias /* (C) or NULL */, void *ws, size_t ws_bytes, int32_t *sync, int spin_limit,
                        grafp_stream_t stream);
+/* The launch grafp_bn_fwd_1pass (backward == 0) or grafp_bn_bwd_1pass (backward != 0) takes for this call (a pure function
+ * of the arguments, as grafp_conv1x1_gemm_plan; both launches choose through the same host function): aligned != 0 = every
+ * activation pointer of the call (x, out, residual / x, dz, dx) is 16-byte aligned; have_sync != 0 = `sync` is not NULL.
+ * info (host, 8 ints) = {path: 0 single-pass, 1 two-pass on 16-byte vectors, 2 two-pass scalar; 16-byte vectors a thread
+ * holds per operand (0: two-pass, threads stride over their chunk); threads per workgroup; chunks per view; elements per
+ * chunk; 0; 0; 0}. */
+int grafp_bn_plan(int dtype, int C, int64_t M, int groups, int training, int backward, int aligned, int have_sync,
+                  int *info);
 
 /* ---- IVF-PQ parity index: asymmetric-distance scan ----------------------------------------------------------------
  * The index of the published protocol, faiss.IndexIVFPQ(IndexFlatL2(d), d, 64, 64, 8) with nprobe = 20
