@@ -11,6 +11,12 @@
 // of the row) in f32, which removes the E[x^2] - E[x]^2 cancellation for rows with |mean| >> std.
 // A conv bias in front of a train-mode BatchNorm cancels in the output; it only shifts the running mean, and its
 // gradient is exactly zero -- so it is folded in here instead of costing an elementwise launch + a reduction.
+// Six kernels (two-pass: stats, apply, bwd_reduce, bwd_dx, on vectors or element by element; single pass: fwd1, bwd1) in
+// 24 instantiations.  What they have in common is written once, in front of them: the chunk a workgroup or slot covers
+// (BnChunk), the two walks over a chunk (bn_walk, bn1_walk), the shifted sums (bn_shifted_sums), the statistics of a view
+// and the running-statistics advance from partial pairs in global memory or LDS (bn_view_stats, bn_advance_running), the
+// forward element (BnNorm, bn_act_res), the two backward elements (BnGrad, BnGradFolded) and, for the single pass, the
+// rendezvous (bn1_rendezvous).  A kernel states only its own per-element body.
 #include <math.h>
 
 #include <type_traits>
@@ -64,7 +70,174 @@ struct BnNorm {
     __device__ __forceinline__ float pre(float x) const {
         return CENTRED ? __builtin_fmaf((x + pb) - mean, g, be) : __builtin_fmaf(x, g, off);
     }
+    __device__ __forceinline__ static BnNorm make(float ga, float be, float pb, float mean, float invstd) {
+        const float g = ga * invstd;
+        return {g, be + (pb - mean) * g, pb, mean, be};      // z = act(x*g + off) + r
+    }
 };
+// the N elements of a piece: normalise, activate, add the shortcut
+template <bool CENTRED, int N>
+__device__ __forceinline__ void bn_act_res(const BnNorm &nrm, int act, float slope, bool res, float (&v)[N], const float (&r)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        v[i] = act_fwd(nrm.template pre<CENTRED>(v[i]), act, slope);
+        if (res) v[i] += r[i];
+    }
+}
+
+// ---- what the six kernels share: the arithmetic of each formula below is written here only --------------------------------
+// (two loops are still spelled in their kernels, around the shared arithmetic: the unrolled-by-4 loop of bn_apply_kernel
+//  next to its bn_walk, and the last walk of bn_fwd1_kernel, which repeats bn1_walk's position for the reason given there)
+// Chunk `i` of a row (a workgroup's own: i = blockIdx.x; a row-mate's: its slot): view grp, chunk sl of that view,
+// columns [lo, hi) of the row.  Sg chunks of `chunk` elements per view of Mg columns; the last one may be shorter.
+struct BnChunk {
+    int grp, sl;
+    int64_t lo, hi;
+    __device__ __forceinline__ BnChunk(int i, int Sg, int64_t chunk, int64_t Mg) {
+        grp = i / Sg;
+        sl = i - grp * Sg;
+        const int64_t gend = (int64_t)(grp + 1) * Mg;
+        lo = (int64_t)grp * Mg + (int64_t)sl * chunk;
+        hi = (lo + chunk < gend) ? lo + chunk : gend;
+    }
+};
+
+// N = 1 or ElemIO<T>::W elements, as the walks hand them out
+template <typename T, int N> __device__ __forceinline__ void bn_load(const T *p, float (&v)[N]) {
+    if constexpr (N == 1) v[0] = ElemIO<T>::ld1(p);
+    else ElemIO<T>::load(p, v);
+}
+template <typename T, int N> __device__ __forceinline__ void bn_store(T *p, const float (&v)[N]) {
+    if constexpr (N == 1) ElemIO<T>::st1(p, v[0]);
+    else ElemIO<T>::store(p, v, false);
+}
+
+// The strided walk of the two-pass kernels: the workgroup's threads cover [.., hi) W elements at a time from the thread's
+// first position m.  body(m, n) gets a whole vector (n = W) while one fits, else the remaining elements one by one (n = 1).
+template <int W, typename Body> __device__ __forceinline__ void bn_walk(int64_t m, int64_t hi, Body body) {
+    for (; m < hi; m += (int64_t)BN_THREADS * W) {
+        if (W > 1 && m + W <= hi) {
+            body(m, std::integral_constant<int, W>{});
+        } else {
+            for (int i = 0; i < W && m + i < hi; ++i) body(m + i, std::integral_constant<int, 1>{});
+        }
+    }
+}
+// The register-resident walk of the single-pass kernels: item `it` of a thread is the vector at m; body(it, m).
+template <int ITEMS, int THREADS, int W, typename Body>
+__device__ __forceinline__ void bn1_walk(int64_t lo, int64_t hi, Body body) {
+    const int tid = threadIdx.x;        // read HERE: as a parameter its range is unknown when this function is first optimised
+#pragma unroll
+    for (int it = 0; it < ITEMS; ++it) {
+        const int64_t m = lo + ((int64_t)it * THREADS + tid) * W;
+        if (m < hi) body(it, m);
+    }
+}
+
+// Forward statistics are shifted sums: a = sum d, q = sum d^2 with d = (x + pb) - shift, shift = the view's first element.
+template <typename T> __device__ __forceinline__ float bn_shift(const T *row, int g, int64_t Mg, float pb) {
+    return ElemIO<T>::ld1(row + (int64_t)g * Mg) + pb;
+}
+template <int N>
+__device__ __forceinline__ void bn_shifted_sums(const float (&v)[N], float pb, float shift, float &a, float &q) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const float d = (v[i] + pb) - shift;
+        a += d;
+        q = __builtin_fmaf(d, d, q);
+    }
+}
+
+// Partial pairs, one per chunk of a row: in global memory (two-pass: `part`) or in LDS (single pass: `sp`).  A reader is
+// anything that returns pair i of the row as a float2.
+struct BnPart {
+    const float *part;
+    size_t row0;            // c * S
+    __device__ __forceinline__ float2 operator()(int i) const {
+        return make_float2(part[(row0 + i) * 2 + 0], part[(row0 + i) * 2 + 1]);
+    }
+};
+__device__ __forceinline__ void bn_put_pair(float *part, size_t i, float2 r) {
+    part[i * 2 + 0] = r.x;
+    part[i * 2 + 1] = r.y;
+}
+template <typename Pairs> __device__ __forceinline__ float2 bn_sum_pairs(Pairs pair, int i0, int i1) {
+    float a = 0.0f, b = 0.0f;
+    for (int i = i0; i < i1; ++i) {         // index order: the same sum in every workgroup that forms it
+        const float2 p = pair(i);
+        a += p.x;
+        b += p.y;
+    }
+    return make_float2(a, b);
+}
+// (mean, biased variance) of view g from its Sg pairs of shifted sums
+template <typename Pairs>
+__device__ __forceinline__ float2 bn_view_mean_var(Pairs pair, int g, int Sg, int64_t Mg, float shift) {
+    const float2 t = bn_sum_pairs(pair, g * Sg, (g + 1) * Sg);
+    const float dm = t.x / (float)Mg;
+    const float var = relu_keep_nan(t.y / (float)Mg - dm * dm);
+    return make_float2(shift + dm, var);
+}
+template <typename Pairs>
+__device__ __forceinline__ void bn_view_stats(Pairs pair, int g, int Sg, int64_t Mg, float shift, float eps, float &mean,
+                                              float &invstd) {
+    const float2 mv = bn_view_mean_var(pair, g, Sg, Mg, shift);
+    mean = mv.x;
+    invstd = 1.0f / sqrtf(mv.y + eps);
+}
+// running statistics advance once per view, in order -- exactly what G sequential forward calls do
+template <typename T, typename Pairs>
+__device__ __forceinline__ void bn_advance_running(Pairs pair, int G, int Sg, int64_t Mg, const T *row, float pb,
+                                                   float momentum, float *running_mean, float *running_var) {
+    float rm = *running_mean, rv = *running_var;
+    for (int g = 0; g < G; ++g) {
+        const float2 mv = bn_view_mean_var(pair, g, Sg, Mg, bn_shift(row, g, Mg, pb));
+        const float unbiased = Mg > 1 ? mv.y * ((float)Mg / (float)(Mg - 1)) : mv.y;
+        rm = (1.0f - momentum) * rm + momentum * mv.x;
+        rv = (1.0f - momentum) * rv + momentum * unbiased;
+    }
+    *running_mean = rm;
+    *running_var = rv;
+}
+
+// One element of the backward: (x, dz) -> (dy, xhat), dy = dz * act'(pre-activation).  Two forms, built once per
+// (row, view) from the same seven values.  Their bits differ, and they stay two:
+// BnGrad, the two-pass kernels': subtract the mean first, as the statistics did.
+struct BnGrad {
+    float pb, mean, invstd, ga, be;
+    int act;
+    float slope;
+    __device__ __forceinline__ float2 operator()(float x, float dz) const {
+        const float xh = ((x + pb) - mean) * invstd;
+        return make_float2(dz * act_grad(__builtin_fmaf(xh, ga, be), act, slope), xh);
+    }
+};
+// BnGradFolded, the single-pass kernel's.  That kernel is partly bound by its vector instructions (27 per element against
+// ~50 lane-operations per element that 5 TB/s leave a CU), so the per-element arithmetic is folded into the fewest fused
+// operations:
+//   xhat = fma(x, invstd, (pb - mean) invstd);  pre-activation = fma(x, gamma invstd, beta + (pb - mean) gamma invstd)
+//   -- the very expression the forward pass thresholds, so the ReLU decision is the forward one by construction;
+//   masked gradient = pre > 0 ? dz : dz * neg   (neg: 1 without activation, 0 for ReLU, the slope for LeakyReLU)
+struct BnGradFolded {
+    float invstd, xh0, zg, zoff, neg;
+    __device__ __forceinline__ BnGradFolded(float pb, float mean, float invstd_, float ga, float be, int act, float slope)
+        : invstd(invstd_), xh0((pb - mean) * invstd_), zg(ga * invstd_), zoff(be + (pb - mean) * zg),
+          neg(act == 0 ? 1.0f : (act == 1 ? 0.0f : slope)) {}
+    __device__ __forceinline__ float2 operator()(float x, float dz) const {
+        const float xh = __builtin_fmaf(x, invstd, xh0);
+        return make_float2(__builtin_fmaf(x, zg, zoff) > 0.0f ? dz : dz * neg, xh);
+    }
+};
+// the partial sums of the backward over N elements, in either form: sd = sum dy, sdx = sum dy * xhat
+template <typename Grad, int N>
+__device__ __forceinline__ void bn_grad_sums(const Grad &gr, const float (&x)[N], const float (&dz)[N], float &sd, float &sdx) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const float2 e = gr(x[i], dz[i]);
+        sd += e.x;
+        sdx = __builtin_fmaf(e.x, e.y, sdx);
+    }
+}
 
 // ---- forward pass 1: partial shifted sums --------------------------------------------------------
 template <typename T, bool VEC>
@@ -73,38 +246,20 @@ __global__ __launch_bounds__(BN_THREADS) void bn_stats_kernel(const T *__restric
                                                               const float *__restrict__ pre_bias,
                                                               float *__restrict__ part) {
     __shared__ float2 scratch[BN_THREADS / 64];
-    const int c = blockIdx.y, s = blockIdx.x, tid = threadIdx.x;
-    const int S = gridDim.x, g = s / Sg, sl = s - g * Sg;
+    const int c = blockIdx.y, s = blockIdx.x, tid = threadIdx.x, S = gridDim.x;
+    const BnChunk ck(s, Sg, chunk, Mg);
     const T *row = x + (size_t)c * M;
     const float pb = pre_bias ? pre_bias[c] : 0.0f;
-    const float shift = ElemIO<T>::ld1(row + (int64_t)g * Mg) + pb;
-    const int64_t gend = (int64_t)(g + 1) * Mg;
-    const int64_t lo = (int64_t)g * Mg + (int64_t)sl * chunk, hi = (lo + chunk < gend) ? lo + chunk : gend;
+    const float shift = bn_shift(row, ck.grp, Mg, pb);
     float a = 0.0f, q = 0.0f;
     constexpr int W = VEC ? ElemIO<T>::W : 1;
-    for (int64_t m = lo + (int64_t)tid * W; m < hi; m += (int64_t)BN_THREADS * W) {
-        if (VEC && m + W <= hi) {
-            float v[ElemIO<T>::W];
-            ElemIO<T>::load(row + m, v);
-#pragma unroll
-            for (int i = 0; i < ElemIO<T>::W; ++i) {
-                const float d = (v[i] + pb) - shift;
-                a += d;
-                q = __builtin_fmaf(d, d, q);
-            }
-        } else {
-            for (int i = 0; i < W && m + i < hi; ++i) {
-                const float d = (ElemIO<T>::ld1(row + m + i) + pb) - shift;
-                a += d;
-                q = __builtin_fmaf(d, d, q);
-            }
-        }
-    }
+    bn_walk<W>(ck.lo + (int64_t)tid * W, ck.hi, [&](int64_t m, auto n) {
+        float v[decltype(n)::value];
+        bn_load(row + m, v);
+        bn_shifted_sums(v, pb, shift, a, q);
+    });
     const float2 r = block_sum2(a, q, scratch, tid);
-    if (tid == 0) {
-        part[((size_t)c * S + s) * 2 + 0] = r.x;
-        part[((size_t)c * S + s) * 2 + 1] = r.y;
-    }
+    if (tid == 0) bn_put_pair(part, (size_t)c * S + s, r);
 }
 
 // ---- forward pass 2: finalise statistics (train) or take running ones (eval), then apply -----------
@@ -121,63 +276,30 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_kernel(const T *__restric
                                                               const float *__restrict__ part, T *__restrict__ out,
                                                               float *__restrict__ save_mean,
                                                               float *__restrict__ save_invstd) {
-    const int c = blockIdx.y, s = blockIdx.x, tid = threadIdx.x;
-    const int S = gridDim.x, grp = s / Sg, sl = s - grp * Sg;
+    const int c = blockIdx.y, s = blockIdx.x, tid = threadIdx.x, S = gridDim.x;
+    const BnChunk ck(s, Sg, chunk, Mg);
     const T *row = x + (size_t)c * M;
     const float pb = pre_bias ? pre_bias[c] : 0.0f;
     float mean, invstd;
     if (training) {
-        // statistics of group `grp` (a view's columns); same summation order in every block of the group
-        float a = 0.0f, q = 0.0f;
-        for (int i = grp * Sg; i < (grp + 1) * Sg; ++i) {
-            a += part[((size_t)c * S + i) * 2 + 0];
-            q += part[((size_t)c * S + i) * 2 + 1];
-        }
-        const float shift = ElemIO<T>::ld1(row + (int64_t)grp * Mg) + pb;
-        const float dm = a / (float)Mg;
-        const float var = relu_keep_nan(q / (float)Mg - dm * dm);
-        mean = shift + dm;
-        invstd = 1.0f / sqrtf(var + eps);
-        if (sl == 0 && tid == 0) {
-            save_mean[c * G + grp] = mean;
-            save_invstd[c * G + grp] = invstd;
-        }
-        if (s == 0 && tid == 0 && running_mean) {
-            // running statistics advance once per group, in order -- exactly what G sequential forward calls do
-            float rm = running_mean[c], rv = running_var[c];
-            for (int g2 = 0; g2 < G; ++g2) {
-                float a2 = 0.0f, q2 = 0.0f;
-                for (int i = g2 * Sg; i < (g2 + 1) * Sg; ++i) {
-                    a2 += part[((size_t)c * S + i) * 2 + 0];
-                    q2 += part[((size_t)c * S + i) * 2 + 1];
-                }
-                const float sh2 = ElemIO<T>::ld1(row + (int64_t)g2 * Mg) + pb;
-                const float dm2 = a2 / (float)Mg;
-                const float var2 = relu_keep_nan(q2 / (float)Mg - dm2 * dm2);
-                const float unbiased = Mg > 1 ? var2 * ((float)Mg / (float)(Mg - 1)) : var2;
-                rm = (1.0f - momentum) * rm + momentum * (sh2 + dm2);
-                rv = (1.0f - momentum) * rv + momentum * unbiased;
-            }
-            running_mean[c] = rm;
-            running_var[c] = rv;
-        }
+        const BnPart pair = {part, (size_t)c * S};
+        bn_view_stats(pair, ck.grp, Sg, Mg, bn_shift(row, ck.grp, Mg, pb), eps, mean, invstd);
+        if (s == 0 && tid == 0 && running_mean)
+            bn_advance_running(pair, G, Sg, Mg, row, pb, momentum, running_mean + c, running_var + c);
     } else {
         mean = running_mean[c];
         invstd = 1.0f / sqrtf(running_var[c] + eps);
-        if (sl == 0 && tid == 0) {
-            save_mean[c * G + grp] = mean;
-            save_invstd[c * G + grp] = invstd;
-        }
     }
-    const float g = gamma[c] * invstd;
-    const float off = beta[c] + (pb - mean) * g;      // z = act(x*g + off) + r (BnNorm)
-    const BnNorm nrm = {g, off, pb, mean, beta[c]};
+    if (ck.sl == 0 && tid == 0) {
+        save_mean[c * G + ck.grp] = mean;
+        save_invstd[c * G + ck.grp] = invstd;
+    }
+    const BnNorm nrm = BnNorm::make(gamma[c], beta[c], pb, mean, invstd);
     const T *rrow = residual ? residual + (size_t)c * M : nullptr;
     T *orow = out + (size_t)c * M;
-    const int64_t gend = (int64_t)(grp + 1) * Mg;
-    const int64_t lo = (int64_t)grp * Mg + (int64_t)sl * chunk, hi = (lo + chunk < gend) ? lo + chunk : gend;
     constexpr int W = VEC ? ElemIO<T>::W : 1;
-    int64_t m = lo + (int64_t)tid * W;
+    int64_t m = ck.lo + (int64_t)tid * W;
+    const int64_t hi = ck.hi;
     auto apply = [&](auto cen_c) {
         constexpr bool CEN = decltype(cen_c)::value;
         if (VEC) {
@@ -197,34 +319,18 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_kernel(const T *__restric
                     float v[ElemIO<T>::W], r[ElemIO<T>::W];
                     ElemIO<T>::unpack(rx[u], v);
                     if (rrow) ElemIO<T>::unpack(rr[u], r);
-#pragma unroll
-                    for (int i = 0; i < ElemIO<T>::W; ++i) {
-                        v[i] = act_fwd(nrm.template pre<CEN>(v[i]), act, slope);
-                        if (rrow) v[i] += r[i];
-                    }
-                    ElemIO<T>::store(orow + m + u * step, v, false);
+                    bn_act_res<CEN>(nrm, act, slope, rrow != nullptr, v, r);
+                    bn_store(orow + m + u * step, v);
                 }
             }
         }
-        for (; m < hi; m += (int64_t)BN_THREADS * W) {
-            if (VEC && m + W <= hi) {
-                float v[ElemIO<T>::W], r[ElemIO<T>::W];
-                ElemIO<T>::load(row + m, v);
-                if (rrow) ElemIO<T>::load(rrow + m, r);
-#pragma unroll
-                for (int i = 0; i < ElemIO<T>::W; ++i) {
-                    v[i] = act_fwd(nrm.template pre<CEN>(v[i]), act, slope);
-                    if (rrow) v[i] += r[i];
-                }
-                ElemIO<T>::store(orow + m, v, false);
-            } else {
-                for (int i = 0; i < W && m + i < hi; ++i) {
-                    float z = act_fwd(nrm.template pre<CEN>(ElemIO<T>::ld1(row + m + i)), act, slope);
-                    if (rrow) z += ElemIO<T>::ld1(rrow + m + i);
-                    ElemIO<T>::st1(orow + m + i, z);
-                }
-            }
-        }
+        bn_walk<W>(m, hi, [&](int64_t p, auto n) {      // from where the unrolled loop stopped
+            float v[decltype(n)::value], r[decltype(n)::value];
+            bn_load(row + p, v);
+            if (rrow) bn_load(rrow + p, r);
+            bn_act_res<CEN>(nrm, act, slope, rrow != nullptr, v, r);
+            bn_store(orow + p, v);
+        });
     };
     if (nrm.centred()) apply(std::true_type{});
     else apply(std::false_type{});
@@ -241,41 +347,21 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_reduce_kernel(const T *__re
                                                                    const float *__restrict__ save_invstd, int act,
                                                                    float slope, float *__restrict__ part) {
     __shared__ float2 scratch[BN_THREADS / 64];
-    const int c = blockIdx.y, s = blockIdx.x, tid = threadIdx.x;
-    const int S = gridDim.x, grp = s / Sg, sl = s - grp * Sg;
+    const int c = blockIdx.y, s = blockIdx.x, tid = threadIdx.x, S = gridDim.x;
+    const BnChunk ck(s, Sg, chunk, Mg);
     const T *row = x + (size_t)c * M, *grow = dz + (size_t)c * M;
     const float pb = pre_bias ? pre_bias[c] : 0.0f;
-    const float mean = save_mean[c * G + grp], invstd = save_invstd[c * G + grp], ga = gamma[c], be = beta[c];
-    const int64_t gend = (int64_t)(grp + 1) * Mg;
-    const int64_t lo = (int64_t)grp * Mg + (int64_t)sl * chunk, hi = (lo + chunk < gend) ? lo + chunk : gend;
+    const BnGrad gr = {pb, save_mean[c * G + ck.grp], save_invstd[c * G + ck.grp], gamma[c], beta[c], act, slope};
     float sd = 0.0f, sdx = 0.0f;
     constexpr int W = VEC ? ElemIO<T>::W : 1;
-    for (int64_t m = lo + (int64_t)tid * W; m < hi; m += (int64_t)BN_THREADS * W) {
-        if (VEC && m + W <= hi) {
-            float v[ElemIO<T>::W], d[ElemIO<T>::W];
-            ElemIO<T>::load(row + m, v);
-            ElemIO<T>::load(grow + m, d);
-#pragma unroll
-            for (int i = 0; i < ElemIO<T>::W; ++i) {
-                const float xh = ((v[i] + pb) - mean) * invstd;
-                const float dy = d[i] * act_grad(__builtin_fmaf(xh, ga, be), act, slope);
-                sd += dy;
-                sdx = __builtin_fmaf(dy, xh, sdx);
-            }
-        } else {
-            for (int i = 0; i < W && m + i < hi; ++i) {
-                const float xh = ((ElemIO<T>::ld1(row + m + i) + pb) - mean) * invstd;
-                const float dy = ElemIO<T>::ld1(grow + m + i) * act_grad(__builtin_fmaf(xh, ga, be), act, slope);
-                sd += dy;
-                sdx = __builtin_fmaf(dy, xh, sdx);
-            }
-        }
-    }
+    bn_walk<W>(ck.lo + (int64_t)tid * W, ck.hi, [&](int64_t m, auto n) {
+        float v[decltype(n)::value], d[decltype(n)::value];
+        bn_load(row + m, v);
+        bn_load(grow + m, d);
+        bn_grad_sums(gr, v, d, sd, sdx);
+    });
     const float2 r = block_sum2(sd, sdx, scratch, tid);
-    if (tid == 0) {
-        part[((size_t)c * S + s) * 2 + 0] = r.x;
-        part[((size_t)c * S + s) * 2 + 1] = r.y;
-    }
+    if (tid == 0) bn_put_pair(part, (size_t)c * S + s, r);
 }
 
 // ---- backward pass 2: dgamma, dbeta, dx ---------------------------------------------------------------
@@ -291,55 +377,38 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_dx_kernel(const T *__restri
                                                                const float *__restrict__ part, T *__restrict__ dx,
                                                                float *__restrict__ dgamma, float *__restrict__ dbeta,
                                                                float *__restrict__ dpre_bias) {
-    const int c = blockIdx.y, s = blockIdx.x, tid = threadIdx.x;
-    const int S = gridDim.x, grp = s / Sg, sl = s - grp * Sg;
+    const int c = blockIdx.y, s = blockIdx.x, tid = threadIdx.x, S = gridDim.x;
+    const BnChunk ck(s, Sg, chunk, Mg);
     const T *row = x + (size_t)c * M, *grow = dz + (size_t)c * M;
     T *orow = dx + (size_t)c * M;
     const float pb = pre_bias ? pre_bias[c] : 0.0f;
-    const float mean = save_mean[c * G + grp], invstd = save_invstd[c * G + grp], ga = gamma[c], be = beta[c];
-    float sd = 0.0f, sdx = 0.0f;
-    for (int i = grp * Sg; i < (grp + 1) * Sg; ++i) {
-        sd += part[((size_t)c * S + i) * 2 + 0];
-        sdx += part[((size_t)c * S + i) * 2 + 1];
-    }
+    const BnGrad gr = {pb, save_mean[c * G + ck.grp], save_invstd[c * G + ck.grp], gamma[c], beta[c], act, slope};
+    const BnPart pair = {part, (size_t)c * S};
+    const float2 sg = bn_sum_pairs(pair, ck.grp * Sg, (ck.grp + 1) * Sg);
     if (s == 0 && tid == 0) {          // parameter gradients sum over all groups (fixed order)
-        float td = 0.0f, tdx = 0.0f;
-        for (int i = 0; i < S; ++i) {
-            td += part[((size_t)c * S + i) * 2 + 0];
-            tdx += part[((size_t)c * S + i) * 2 + 1];
-        }
-        dgamma[c] = tdx;
-        dbeta[c] = td;
+        const float2 t = bn_sum_pairs(pair, 0, S);
+        dgamma[c] = t.y;
+        dbeta[c] = t.x;
         // gradient of a bias added BEFORE the normalisation: cancels exactly under batch statistics; with running
         // statistics (eval) dx = ga*invstd*dy, so it is ga*invstd*sum(dy)
-        if (dpre_bias) dpre_bias[c] = training ? 0.0f : ga * invstd * td;
+        if (dpre_bias) dpre_bias[c] = training ? 0.0f : gr.ga * gr.invstd * t.x;
     }
     // train: dx = ga*invstd * (dy - mean_g(dy) - xhat * mean_g(dy*xhat)) within the group; eval: dx = ga*invstd*dy
-    const float k = ga * invstd;
-    const float m1 = training ? sd / (float)Mg : 0.0f, m2 = training ? sdx / (float)Mg : 0.0f;
-    const int64_t gend = (int64_t)(grp + 1) * Mg;
-    const int64_t lo = (int64_t)grp * Mg + (int64_t)sl * chunk, hi = (lo + chunk < gend) ? lo + chunk : gend;
+    const float k = gr.ga * gr.invstd;
+    const float m1 = training ? sg.x / (float)Mg : 0.0f, m2 = training ? sg.y / (float)Mg : 0.0f;
     constexpr int W = VEC ? ElemIO<T>::W : 1;
-    for (int64_t m = lo + (int64_t)tid * W; m < hi; m += (int64_t)BN_THREADS * W) {
-        if (VEC && m + W <= hi) {
-            float v[ElemIO<T>::W], d[ElemIO<T>::W];
-            ElemIO<T>::load(row + m, v);
-            ElemIO<T>::load(grow + m, d);
+    bn_walk<W>(ck.lo + (int64_t)tid * W, ck.hi, [&](int64_t m, auto n) {
+        constexpr int N = decltype(n)::value;
+        float v[N], d[N];
+        bn_load(row + m, v);
+        bn_load(grow + m, d);
 #pragma unroll
-            for (int i = 0; i < ElemIO<T>::W; ++i) {
-                const float xh = ((v[i] + pb) - mean) * invstd;
-                const float dy = d[i] * act_grad(__builtin_fmaf(xh, ga, be), act, slope);
-                v[i] = training ? k * ((dy - m1) - xh * m2) : k * dy;      // (eval: no xh * 0, which is NaN for a non-finite x)
-            }
-            ElemIO<T>::store(orow + m, v, false);
-        } else {
-            for (int i = 0; i < W && m + i < hi; ++i) {
-                const float xh = ((ElemIO<T>::ld1(row + m + i) + pb) - mean) * invstd;
-                const float dy = ElemIO<T>::ld1(grow + m + i) * act_grad(__builtin_fmaf(xh, ga, be), act, slope);
-                ElemIO<T>::st1(orow + m + i, training ? k * ((dy - m1) - xh * m2) : k * dy);
-            }
+        for (int i = 0; i < N; ++i) {
+            const float2 e = gr(v[i], d[i]);
+            v[i] = training ? k * ((e.x - m1) - e.y * m2) : k * e.x;      // (eval: no xh * 0, which is NaN for a non-finite x)
         }
-    }
+        bn_store(orow + m, v);
+    });
 }
 
 // ---- single-pass variants: the chunk stays in registers across a row-wide rendezvous --------------------------
@@ -369,10 +438,10 @@ constexpr unsigned BN1_EMPTY = 0xffffffffu;            // "not published yet" (a
 // No read-modify-write sits on the critical path: a slot is ONE 8-byte write-through store, the wait is wave 0 polling
 // the row's S slots with L2-bypassing loads (the successful poll already holds the data).  Returns with sp[0..S) set.
 // The wait is BOUNDED and never traps: after `spin_limit` polls the slots that are still empty are left marked in sp
-// (BN1_EMPTY in .x) and the caller recomputes exactly those partials from global memory itself (same thread mapping,
-// same summation order => the same bits), so a workgroup never depends on row-mates that are not resident -- other
-// kernels holding CUs (RCCL all-reduces overlapping backward, several ranks on one device, CU masks) cost time, not
-// correctness.  Returns the number of slots the caller has to fill in (workgroup-uniform).
+// (BN1_EMPTY in .x) and the caller (bn1_rendezvous) recomputes exactly those partials from global memory itself (same
+// thread mapping, same summation order => the same bits), so a workgroup never depends on row-mates that are not resident
+// -- other kernels holding CUs (RCCL all-reduces overlapping backward, several ranks on one device, CU masks) cost time,
+// not correctness.  Returns the number of slots the caller has to fill in (workgroup-uniform).
 __device__ __forceinline__ int bn1_publish_and_wait(float a, float b, unsigned long long *slots_row, int s, int w_lo,
                                                     int w_hi, float2 *sp, int *n_missing, int spin_limit, int tid) {
     if (tid == 0) {
@@ -424,6 +493,35 @@ __device__ __forceinline__ void bn1_rearm(int old, int S, int *counter, unsigned
 __device__ __forceinline__ void bn_opaque(float4 &v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
 __device__ __forceinline__ void bn_opaque(uint4 &v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
 
+// What the two single-pass kernels share between their first phase and the reduction of `sp`: where the row's slots and
+// counter live in `sync`, which slots this workgroup waits for, publish-and-wait, and the recompute of the slots that
+// stayed empty -- partial(i) returns THIS THREAD's share of the pair of chunk i, straight from the row (same thread mapping
+// and summation order as the first phase of the workgroup that owns the chunk => the same bits).  Returns with sp[w_lo, w_hi)
+// valid for every thread; the caller checks out BEFORE it reduces sp and re-arms as its last statement.
+struct Bn1Row {
+    unsigned long long *slots;
+    int *counter;
+};
+template <int THREADS, typename Partial>
+__device__ __forceinline__ Bn1Row bn1_rendezvous(float2 r, int *sync, int c, int s, int grp, int Sg, float2 *sp,
+                                                 int *n_missing, float2 *scratch, int spin_limit, int tid, Partial partial) {
+    const int S = gridDim.x;
+    const Bn1Row rw = {reinterpret_cast<unsigned long long *>(sync + (size_t)gridDim.y * BN1_SYNC_STRIDE) + (size_t)c * S,
+                       sync + (size_t)c * BN1_SYNC_STRIDE};
+    const int w_lo = s == 0 ? 0 : grp * Sg, w_hi = s == 0 ? S : (grp + 1) * Sg;     // chunk 0 also writes the per-row results
+    if (bn1_publish_and_wait(r.x, r.y, rw.slots, s, w_lo, w_hi, sp, n_missing, spin_limit, tid) > 0) {
+        // row-mates that did not show up in time
+        for (int i = w_lo; i < w_hi; ++i) {
+            if (__float_as_uint(sp[i].x) != BN1_EMPTY) continue;            // LDS value: workgroup-uniform branch
+            const float2 p = partial(i);
+            const float2 r2 = block_sum2<THREADS>(p.x, p.y, scratch, tid);
+            if (tid == 0) sp[i] = r2;
+        }
+        __syncthreads();
+    }
+    return rw;
+}
+
 template <typename T, bool RES>
 __global__ __launch_bounds__(BN1_THREADS) void bn_fwd1_kernel(const T *__restrict__ x, int64_t M, int64_t Mg, int Sg,
                                                              int G, const float *__restrict__ pre_bias,
@@ -437,141 +535,73 @@ __global__ __launch_bounds__(BN1_THREADS) void bn_fwd1_kernel(const T *__restric
                                                              float *__restrict__ save_mean,
                                                              float *__restrict__ save_invstd, int spin_limit) {
     constexpr int W = ElemIO<T>::W, ITEMS = BN1_ITEMS_FWD, CHUNK = BN1_THREADS * ITEMS * W;
+    using Raw = typename ElemIO<T>::Raw;
     __shared__ float2 scratch[BN1_THREADS / 64];
     __shared__ float2 sp[BN1_MAX_S];
     __shared__ int n_missing;
-    const int c = blockIdx.y, s = blockIdx.x, tid = threadIdx.x;
-    const int S = gridDim.x, grp = s / Sg, sl = s - grp * Sg;
+    const int c = blockIdx.y, s = blockIdx.x, tid = threadIdx.x, S = gridDim.x;
+    const BnChunk ck(s, Sg, CHUNK, Mg);
     const T *row = x + (size_t)c * M;
     const float pb = pre_bias ? pre_bias[c] : 0.0f;
-    const float shift = ElemIO<T>::ld1(row + (int64_t)grp * Mg) + pb;
-    const int64_t gend = (int64_t)(grp + 1) * Mg;
-    const int64_t lo = (int64_t)grp * Mg + (int64_t)sl * CHUNK;
-    const int64_t hi = (lo + CHUNK < gend) ? lo + CHUNK : gend;
-    typename ElemIO<T>::Raw raw[ITEMS];
+    const float shift = bn_shift(row, ck.grp, Mg, pb);
+    Raw raw[ITEMS];
     float a = 0.0f, q = 0.0f;
-#pragma unroll
-    for (int it = 0; it < ITEMS; ++it) {
-        const int64_t m = lo + ((int64_t)it * BN1_THREADS + tid) * W;
-        if (m < hi) raw[it] = *reinterpret_cast<const typename ElemIO<T>::Raw *>(row + m);
-    }
-#pragma unroll
-    for (int it = 0; it < ITEMS; ++it) {
-        const int64_t m = lo + ((int64_t)it * BN1_THREADS + tid) * W;
-        if (m < hi) {
-            float v[W];
-            ElemIO<T>::unpack(raw[it], v);
-#pragma unroll
-            for (int i = 0; i < W; ++i) {
-                const float d = (v[i] + pb) - shift;
-                a += d;
-                q = __builtin_fmaf(d, d, q);
-            }
-        }
-    }
+    bn1_walk<ITEMS, BN1_THREADS, W>(ck.lo, ck.hi, [&](int it, int64_t m) { raw[it] = *reinterpret_cast<const Raw *>(row + m); });
+    bn1_walk<ITEMS, BN1_THREADS, W>(ck.lo, ck.hi, [&](int it, int64_t) {
+        float v[W];
+        ElemIO<T>::unpack(raw[it], v);
+        bn_shifted_sums(v, pb, shift, a, q);
+    });
     // the shortcut rows do not depend on the statistics: fetch them now, so their latency passes during the rendezvous
     // (RES is a template parameter: the 32 extra registers only exist in the instantiation that needs them)
     const T *rrow = RES ? residual + (size_t)c * M : nullptr;
-    typename ElemIO<T>::Raw rres[RES ? ITEMS : 1];
-    if (RES) {
-#pragma unroll
-        for (int it = 0; it < ITEMS; ++it) {
-            const int64_t m = lo + ((int64_t)it * BN1_THREADS + tid) * W;
-            if (m < hi) rres[it] = *reinterpret_cast<const typename ElemIO<T>::Raw *>(rrow + m);
-        }
-    }
+    Raw rres[RES ? ITEMS : 1];
+    if (RES) bn1_walk<ITEMS, BN1_THREADS, W>(ck.lo, ck.hi, [&](int it, int64_t m) { rres[it] = *reinterpret_cast<const Raw *>(rrow + m); });
     const float2 r = block_sum2<BN1_THREADS>(a, q, scratch, tid);
-    unsigned long long *slots_row = reinterpret_cast<unsigned long long *>(sync + (size_t)gridDim.y * BN1_SYNC_STRIDE) + (size_t)c * S;
-    int *counter = sync + (size_t)c * BN1_SYNC_STRIDE;
-    const int w_lo = s == 0 ? 0 : grp * Sg, w_hi = s == 0 ? S : (grp + 1) * Sg;     // chunk 0 also writes the running stats
-    if (bn1_publish_and_wait(r.x, r.y, slots_row, s, w_lo, w_hi, sp, &n_missing, spin_limit, tid) > 0) {
-        // row-mates that did not show up in time: their partial sums straight from the row (identical order and bits)
-        for (int i = w_lo; i < w_hi; ++i) {
-            if (__float_as_uint(sp[i].x) != BN1_EMPTY) continue;            // LDS value: workgroup-uniform branch
-            const int g2 = i / Sg;
-            const float sh2 = ElemIO<T>::ld1(row + (int64_t)g2 * Mg) + pb;
-            const int64_t lo2 = (int64_t)g2 * Mg + (int64_t)(i - g2 * Sg) * CHUNK;
-            const int64_t hi2 = (lo2 + CHUNK < (int64_t)(g2 + 1) * Mg) ? lo2 + CHUNK : (int64_t)(g2 + 1) * Mg;
-            float a2 = 0.0f, q2 = 0.0f;
-#pragma unroll
-            for (int it = 0; it < ITEMS; ++it) {
-                const int64_t m = lo2 + ((int64_t)it * BN1_THREADS + tid) * W;
-                if (m < hi2) {
-                    float v[W];
-                    ElemIO<T>::load(row + m, v);
-#pragma unroll
-                    for (int e = 0; e < W; ++e) {
-                        const float d = (v[e] + pb) - sh2;
-                        a2 += d;
-                        q2 = __builtin_fmaf(d, d, q2);
-                    }
-                }
-            }
-            const float2 r2 = block_sum2<BN1_THREADS>(a2, q2, scratch, tid);
-            if (tid == 0) sp[i] = r2;
-        }
-        __syncthreads();
-    }
+    const Bn1Row rw = bn1_rendezvous<BN1_THREADS>(r, sync, c, s, ck.grp, Sg, sp, &n_missing, scratch, spin_limit, tid, [&](int i) {
+        const BnChunk c2(i, Sg, CHUNK, Mg);
+        const float sh2 = bn_shift(row, c2.grp, Mg, pb);
+        float a2 = 0.0f, q2 = 0.0f;
+        bn1_walk<ITEMS, BN1_THREADS, W>(c2.lo, c2.hi, [&](int, int64_t m) {
+            float v[W];
+            ElemIO<T>::load(row + m, v);
+            bn_shifted_sums(v, pb, sh2, a2, q2);
+        });
+        return make_float2(a2, q2);
+    });
 #pragma unroll
     for (int it = 0; it < ITEMS; ++it) bn_opaque(raw[it]);
     int checkout = 0;
-    if (tid == 0) checkout = bn1_checkout(counter);
-    a = 0.0f, q = 0.0f;
-    for (int i = grp * Sg; i < (grp + 1) * Sg; ++i) {
-        a += sp[i].x;
-        q += sp[i].y;
+    if (tid == 0) checkout = bn1_checkout(rw.counter);
+    const auto pair = [&](int i) { return sp[i]; };
+    float mean, invstd;
+    bn_view_stats(pair, ck.grp, Sg, Mg, shift, eps, mean, invstd);
+    if (ck.sl == 0 && tid == 0) {
+        save_mean[c * G + ck.grp] = mean;
+        save_invstd[c * G + ck.grp] = invstd;
     }
-    const float dm = a / (float)Mg;
-    const float var = relu_keep_nan(q / (float)Mg - dm * dm);
-    const float mean = shift + dm;
-    const float invstd = 1.0f / sqrtf(var + eps);
-    if (sl == 0 && tid == 0) {
-        save_mean[c * G + grp] = mean;
-        save_invstd[c * G + grp] = invstd;
-    }
-    if (s == 0 && tid == 0 && running_mean) {
-        float rm = running_mean[c], rv = running_var[c];
-        for (int g2 = 0; g2 < G; ++g2) {
-            float a2 = 0.0f, q2 = 0.0f;
-            for (int i = g2 * Sg; i < (g2 + 1) * Sg; ++i) {
-                a2 += sp[i].x;
-                q2 += sp[i].y;
-            }
-            const float sh2 = ElemIO<T>::ld1(row + (int64_t)g2 * Mg) + pb;
-            const float dm2 = a2 / (float)Mg;
-            const float var2 = relu_keep_nan(q2 / (float)Mg - dm2 * dm2);
-            const float unbiased = Mg > 1 ? var2 * ((float)Mg / (float)(Mg - 1)) : var2;
-            rm = (1.0f - momentum) * rm + momentum * (sh2 + dm2);
-            rv = (1.0f - momentum) * rv + momentum * unbiased;
-        }
-        running_mean[c] = rm;
-        running_var[c] = rv;
-    }
-    const float g = gamma[c] * invstd;
-    const float off = beta[c] + (pb - mean) * g;
-    const BnNorm nrm = {g, off, pb, mean, beta[c]};
+    if (s == 0 && tid == 0 && running_mean)
+        bn_advance_running(pair, G, Sg, Mg, row, pb, momentum, running_mean + c, running_var + c);
+    const BnNorm nrm = BnNorm::make(gamma[c], beta[c], pb, mean, invstd);
     T *orow = out + (size_t)c * M;
+    // (this walk keeps its own spelling: through bn1_walk the positions m are the first phase's own expressions and stay
+    //  live across the rendezvous, 14 VGPRs; written here they are formed again)
     auto apply = [&](auto cen_c) {
-        constexpr bool CEN = decltype(cen_c)::value;
 #pragma unroll
         for (int it = 0; it < ITEMS; ++it) {
-            const int64_t m = lo + ((int64_t)it * BN1_THREADS + tid) * W;
-            if (m < hi) {
+            const int64_t m = ck.lo + ((int64_t)it * BN1_THREADS + tid) * W;
+            if (m < ck.hi) {
                 float v[W], rr[W];
                 ElemIO<T>::unpack(raw[it], v);
                 if (RES) ElemIO<T>::unpack(rres[it], rr);
-#pragma unroll
-                for (int i = 0; i < W; ++i) {
-                    v[i] = act_fwd(nrm.template pre<CEN>(v[i]), act, slope);
-                    if (RES) v[i] += rr[i];
-                }
+                bn_act_res<decltype(cen_c)::value>(nrm, act, slope, RES, v, rr);
                 ElemIO<T>::store(orow + m, v, false);
             }
         }
     };
     if (nrm.centred()) apply(std::true_type{});
     else apply(std::false_type{});
-    if (tid == 0) bn1_rearm(checkout, S, counter, slots_row);
+    if (tid == 0) bn1_rearm(checkout, S, rw.counter, rw.slots);
 }
 
 template <typename T, int ITEMS, int THREADS = BN1_THREADS>
@@ -588,126 +618,72 @@ __global__ __launch_bounds__(THREADS) void bn_bwd1_kernel(const T *__restrict__ 
                                                              float *__restrict__ dpre_bias, int spin_limit,
                                                              int plain_stores) {
     constexpr int W = ElemIO<T>::W, CHUNK = THREADS * ITEMS * W;
+    using Raw = typename ElemIO<T>::Raw;
     __shared__ float2 scratch[THREADS / 64];
     __shared__ float2 sp[BN1_MAX_S];
     __shared__ int n_missing;
-    const int c = blockIdx.y, s = blockIdx.x, tid = threadIdx.x;
-    const int S = gridDim.x, grp = s / Sg, sl = s - grp * Sg;
+    const int c = blockIdx.y, s = blockIdx.x, tid = threadIdx.x, S = gridDim.x;
+    const BnChunk ck(s, Sg, CHUNK, Mg);
     const T *row = x + (size_t)c * M, *grow = dz + (size_t)c * M;
     T *orow = dx + (size_t)c * M;
     const float pb = pre_bias ? pre_bias[c] : 0.0f;
-    const float mean = save_mean[c * G + grp], invstd = save_invstd[c * G + grp], ga = gamma[c], be = beta[c];
-    // The kernel is partly bound by its vector instructions (27 per element against ~50 lane-operations per element that
-    // 5 TB/s leave a CU), so the per-element arithmetic is folded into the fewest fused operations:
-    //   xhat = fma(x, invstd, (pb - mean) invstd);  pre-activation = fma(x, gamma invstd, beta + (pb - mean) gamma invstd)
-    //   -- the very expression the forward pass thresholds, so the ReLU decision is the forward one by construction;
-    //   masked gradient = pre > 0 ? dz : dz * neg   (neg: 1 without activation, 0 for ReLU, the slope for LeakyReLU)
-    const float xh0 = (pb - mean) * invstd, zg = ga * invstd, zoff = be + (pb - mean) * zg;
-    const float neg = act == 0 ? 1.0f : (act == 1 ? 0.0f : slope);
-    const int64_t gend = (int64_t)(grp + 1) * Mg;
-    const int64_t lo = (int64_t)grp * Mg + (int64_t)sl * CHUNK;
-    const int64_t hi = (lo + CHUNK < gend) ? lo + CHUNK : gend;
-    typename ElemIO<T>::Raw rx[ITEMS], rd[ITEMS];
-#pragma unroll
-    for (int it = 0; it < ITEMS; ++it) {
-        const int64_t m = lo + ((int64_t)it * THREADS + tid) * W;
-        if (m < hi) {
-            rx[it] = GRAFP_LD_ONCE(1, reinterpret_cast<const typename ElemIO<T>::Raw *>(row + m));
-            rd[it] = GRAFP_LD_ONCE(4, reinterpret_cast<const typename ElemIO<T>::Raw *>(grow + m));
-        }
-    }
+    const float ga = gamma[c], be = beta[c];
+    const BnGradFolded gr(pb, save_mean[c * G + ck.grp], save_invstd[c * G + ck.grp], ga, be, act, slope);
+    Raw rx[ITEMS], rd[ITEMS];
+    bn1_walk<ITEMS, THREADS, W>(ck.lo, ck.hi, [&](int it, int64_t m) {
+        rx[it] = GRAFP_LD_ONCE(1, reinterpret_cast<const Raw *>(row + m));
+        rd[it] = GRAFP_LD_ONCE(4, reinterpret_cast<const Raw *>(grow + m));
+    });
     float sd = 0.0f, sdx = 0.0f;
-#pragma unroll
-    for (int it = 0; it < ITEMS; ++it) {
-        const int64_t m = lo + ((int64_t)it * THREADS + tid) * W;
-        if (m < hi) {
-            float v[W], d[W];
-            ElemIO<T>::unpack(rx[it], v);
-            ElemIO<T>::unpack(rd[it], d);
-#pragma unroll
-            for (int i = 0; i < W; ++i) {
-                const float xh = __builtin_fmaf(v[i], invstd, xh0);
-                const float dy = __builtin_fmaf(v[i], zg, zoff) > 0.0f ? d[i] : d[i] * neg;
-                sd += dy;
-                sdx = __builtin_fmaf(dy, xh, sdx);
-            }
-        }
-    }
+    bn1_walk<ITEMS, THREADS, W>(ck.lo, ck.hi, [&](int it, int64_t) {
+        float v[W], d[W];
+        ElemIO<T>::unpack(rx[it], v);
+        ElemIO<T>::unpack(rd[it], d);
+        bn_grad_sums(gr, v, d, sd, sdx);
+    });
     const float2 r = block_sum2<THREADS>(sd, sdx, scratch, tid);
-    unsigned long long *slots_row = reinterpret_cast<unsigned long long *>(sync + (size_t)gridDim.y * BN1_SYNC_STRIDE) + (size_t)c * S;
-    int *counter = sync + (size_t)c * BN1_SYNC_STRIDE;
-    const int w_lo = s == 0 ? 0 : grp * Sg, w_hi = s == 0 ? S : (grp + 1) * Sg;     // chunk 0 also writes dgamma / dbeta
-    if (bn1_publish_and_wait(r.x, r.y, slots_row, s, w_lo, w_hi, sp, &n_missing, spin_limit, tid) > 0) {
-        for (int i = w_lo; i < w_hi; ++i) {
-            if (__float_as_uint(sp[i].x) != BN1_EMPTY) continue;
-            const int g2 = i / Sg;
-            const float mean2 = save_mean[c * G + g2], invstd2 = save_invstd[c * G + g2];
-            const int64_t lo2 = (int64_t)g2 * Mg + (int64_t)(i - g2 * Sg) * CHUNK;
-            const int64_t hi2 = (lo2 + CHUNK < (int64_t)(g2 + 1) * Mg) ? lo2 + CHUNK : (int64_t)(g2 + 1) * Mg;
-            float sd2 = 0.0f, sdx2 = 0.0f;
-#pragma unroll
-            for (int it = 0; it < ITEMS; ++it) {
-                const int64_t m = lo2 + ((int64_t)it * THREADS + tid) * W;
-                if (m < hi2) {
-                    float v[W], d[W];
-                    ElemIO<T>::load(row + m, v);
-                    ElemIO<T>::load(grow + m, d);
-#pragma unroll
-                    for (int e = 0; e < W; ++e) {
-                        const float xh = __builtin_fmaf(v[e], invstd2, (pb - mean2) * invstd2);
-                        const float dy = __builtin_fmaf(v[e], ga * invstd2, be + (pb - mean2) * (ga * invstd2)) > 0.0f ? d[e] : d[e] * neg;
-                        sd2 += dy;
-                        sdx2 = __builtin_fmaf(dy, xh, sdx2);
-                    }
-                }
-            }
-            const float2 r2 = block_sum2<THREADS>(sd2, sdx2, scratch, tid);
-            if (tid == 0) sp[i] = r2;
-        }
-        __syncthreads();
-    }
+    const Bn1Row rw = bn1_rendezvous<THREADS>(r, sync, c, s, ck.grp, Sg, sp, &n_missing, scratch, spin_limit, tid, [&](int i) {
+        const BnChunk c2(i, Sg, CHUNK, Mg);
+        const BnGradFolded gr2(pb, save_mean[c * G + c2.grp], save_invstd[c * G + c2.grp], ga, be, act, slope);
+        float sd2 = 0.0f, sdx2 = 0.0f;
+        bn1_walk<ITEMS, THREADS, W>(c2.lo, c2.hi, [&](int, int64_t m) {
+            float v[W], d[W];
+            ElemIO<T>::load(row + m, v);
+            ElemIO<T>::load(grow + m, d);
+            bn_grad_sums(gr2, v, d, sd2, sdx2);
+        });
+        return make_float2(sd2, sdx2);
+    });
 #pragma unroll
     for (int it = 0; it < ITEMS; ++it) {
         bn_opaque(rx[it]);
         bn_opaque(rd[it]);
     }
     int checkout = 0;
-    if (tid == 0) checkout = bn1_checkout(counter);
-    sd = 0.0f, sdx = 0.0f;
-    for (int i = grp * Sg; i < (grp + 1) * Sg; ++i) {
-        sd += sp[i].x;
-        sdx += sp[i].y;
-    }
+    if (tid == 0) checkout = bn1_checkout(rw.counter);
+    const auto pair = [&](int i) { return sp[i]; };
+    const float2 sg = bn_sum_pairs(pair, ck.grp * Sg, (ck.grp + 1) * Sg);
     if (s == 0 && tid == 0) {
-        float td = 0.0f, tdx = 0.0f;
-        for (int i = 0; i < S; ++i) {
-            td += sp[i].x;
-            tdx += sp[i].y;
-        }
-        dgamma[c] = tdx;
-        dbeta[c] = td;
+        const float2 t = bn_sum_pairs(pair, 0, S);
+        dgamma[c] = t.y;
+        dbeta[c] = t.x;
         if (dpre_bias) dpre_bias[c] = 0.0f;          // training mode only: cancels in the normalisation
     }
-    const float k = ga * invstd;
-    const float m1 = sd / (float)Mg, m2 = sdx / (float)Mg;
+    const float k = ga * gr.invstd;
+    const float m1 = sg.x / (float)Mg, m2 = sg.y / (float)Mg;
     const float km1 = -(k * m1), km2 = -(k * m2);               // dx = k dy - k m1 - k m2 xh: two fmaf per element
+    bn1_walk<ITEMS, THREADS, W>(ck.lo, ck.hi, [&](int it, int64_t m) {
+        float v[W], d[W];
+        ElemIO<T>::unpack(rx[it], v);
+        ElemIO<T>::unpack(rd[it], d);
 #pragma unroll
-    for (int it = 0; it < ITEMS; ++it) {
-        const int64_t m = lo + ((int64_t)it * THREADS + tid) * W;
-        if (m < hi) {
-            float v[W], d[W];
-            ElemIO<T>::unpack(rx[it], v);
-            ElemIO<T>::unpack(rd[it], d);
-#pragma unroll
-            for (int i = 0; i < W; ++i) {
-                const float xh = __builtin_fmaf(v[i], invstd, xh0);
-                const float dy = __builtin_fmaf(v[i], zg, zoff) > 0.0f ? d[i] : d[i] * neg;
-                v[i] = __builtin_fmaf(xh, km2, __builtin_fmaf(dy, k, km1));
-            }
-            ElemIO<T>::store(orow + m, v, plain_stores != 0);
+        for (int i = 0; i < W; ++i) {
+            const float2 e = gr(v[i], d[i]);
+            v[i] = __builtin_fmaf(e.y, km2, __builtin_fmaf(e.x, k, km1));
         }
-    }
-    if (tid == 0) bn1_rearm(checkout, S, counter, slots_row);
+        ElemIO<T>::store(orow + m, v, plain_stores != 0);
+    });
+    if (tid == 0) bn1_rearm(checkout, S, rw.counter, rw.slots);
 }
 
 // single-pass plan: Sg chunks per group, or 0 when the shape does not qualify
@@ -747,9 +723,10 @@ struct BnLaunch {
     int Sg;             // chunks per view
     int64_t chunk;      // elements per chunk (the last chunk of a view may be shorter)
 };
+static int bn_vec_width(int dtype) { return dtype == GRAFP_F32 ? 4 : 8; }      // ElemIO<T>::W of the dtype's T
 static BnLaunch bn_choose(int dtype, int C, int64_t Mg, int G, bool training, bool backward, bool vec, bool have_sync) {
     const bool f32 = dtype == GRAFP_F32;
-    const int W = f32 ? 4 : 8;
+    const int W = bn_vec_width(dtype);
     BnLaunch L;
     if (have_sync && training && !backward) {
         const int Sg = vec ? bn1_plan(Mg, G, W, BN1_ITEMS_FWD) : 0;
@@ -803,6 +780,16 @@ static bool bn_vec_ok(int W, const void *a, const void *b, const void *c, const 
 // per-call argument of the *_1pass entry points (negative = this default; 0 = never wait)
 static inline int bn_spin(int spin_limit) { return spin_limit < 0 ? (1 << 12) : spin_limit; }
 
+// what grafp_bn_fwd_1pass, grafp_bn_bwd_1pass and grafp_bn_plan ask of their arguments; op names the entry in the message
+static int bn_check_args(const char *op, bool pointers, int dtype, int C, int64_t M, int groups, int act) {
+    GRAFP_REQUIRE(pointers, "%s: null pointer", op);
+    GRAFP_REQUIRE(C > 0 && M > 0 && C <= 65535, "%s: bad shape C=%d M=%lld", op, C, (long long)M);
+    GRAFP_REQUIRE(groups >= 1 && groups <= 8 && M % groups == 0, "%s: groups=%d must be in [1,8] and divide M=%lld", op, groups, (long long)M);
+    GRAFP_REQUIRE(dtype == GRAFP_F32 || dtype == GRAFP_BF16, "%s: dtype %d not in {f32, bf16}", op, dtype);
+    GRAFP_REQUIRE(act >= 0 && act <= 2, "%s: act %d not in {0 none, 1 relu, 2 leaky}", op, act);
+    return GRAFP_OK;
+}
+
 extern "C" size_t grafp_bn_workspace(int C, int64_t M) {
     if (C <= 0 || M <= 0) return 0;
     const size_t two_pass = (size_t)4096 + (size_t)C * 8;          // >= C * G * Sg partial pairs for any G <= 8
@@ -815,6 +802,14 @@ extern "C" size_t grafp_bn_sync_bytes(int C, int64_t M) {
     return (size_t)C * grafp::BN1_SYNC_STRIDE * sizeof(int) + (size_t)C * ((size_t)(M / grafp::BN1_MIN_CHUNK) + 8) * 8;
 }
 
+static int bn_check_ws(const char *op, const void *ws, size_t ws_bytes, int C, int64_t M) {
+    if (!ws || ws_bytes < grafp_bn_workspace(C, M)) {
+        grafp::set_error("%s: workspace %zu bytes < required %zu", op, ws_bytes, grafp_bn_workspace(C, M));
+        return GRAFP_ERR_WORKSPACE;
+    }
+    return GRAFP_OK;
+}
+
 extern "C" int grafp_bn_fwd_1pass(const void *x, int dtype, int C, int64_t M, int groups, const float *pre_bias,
                                   const float *gamma, const float *beta, const void *residual, int act, float slope,
                                   float eps, float momentum, int training, float *running_mean, float *running_var,
@@ -822,22 +817,14 @@ extern "C" int grafp_bn_fwd_1pass(const void *x, int dtype, int C, int64_t M, in
                                   int32_t *sync, int spin_limit, grafp_stream_t stream) {
     using namespace grafp;
     const int spin = bn_spin(spin_limit);
-    GRAFP_REQUIRE(x && gamma && beta && out && save_mean && save_invstd, "bn_fwd: null pointer");
-    GRAFP_REQUIRE(C > 0 && M > 0 && C <= 65535, "bn_fwd: bad shape C=%d M=%lld", C, (long long)M);
-    GRAFP_REQUIRE(groups >= 1 && groups <= 8 && M % groups == 0, "bn_fwd: groups=%d must be in [1,8] and divide M=%lld", groups, (long long)M);
+    if (int e = bn_check_args("bn_fwd", x && gamma && beta && out && save_mean && save_invstd, dtype, C, M, groups, act)) return e;
+    GRAFP_REQUIRE(training || (running_mean && running_var), "bn_fwd: eval mode needs running statistics");
+    if (int e = bn_check_ws("bn_fwd", ws, ws_bytes, C, M)) return e;
     const int G = groups;
     const int64_t Mg = M / G;
-    GRAFP_REQUIRE(dtype == GRAFP_F32 || dtype == GRAFP_BF16, "bn_fwd: dtype %d not in {f32, bf16}", dtype);
-    GRAFP_REQUIRE(act >= 0 && act <= 2, "bn_fwd: act %d not in {0 none, 1 relu, 2 leaky}", act);
-    GRAFP_REQUIRE(training || (running_mean && running_var), "bn_fwd: eval mode needs running statistics");
-    if (!ws || ws_bytes < grafp_bn_workspace(C, M)) {
-        set_error("bn_fwd: workspace %zu bytes < required %zu", ws_bytes, grafp_bn_workspace(C, M));
-        return GRAFP_ERR_WORKSPACE;
-    }
     hipStream_t s = (hipStream_t)stream;
     float *part = (float *)ws;
-    const int W = dtype == GRAFP_F32 ? 4 : 8;
-    const bool vec = bn_vec_ok(W, x, out, residual, nullptr, Mg);
+    const bool vec = bn_vec_ok(bn_vec_width(dtype), x, out, residual, nullptr, Mg);
     const BnLaunch p = bn_choose(dtype, C, Mg, G, training != 0, false, vec, sync != nullptr);
     if (p.path == BN_PATH_1PASS) {
         const int Sg = p.Sg;
@@ -885,22 +872,16 @@ extern "C" int grafp_bn_bwd_1pass(const void *x, const void *dz, int dtype, int 
                                   int32_t *sync, int spin_limit, grafp_stream_t stream) {
     using namespace grafp;
     const int spin = bn_spin(spin_limit);
-    GRAFP_REQUIRE(x && dz && gamma && beta && save_mean && save_invstd && dx && dgamma && dbeta, "bn_bwd: null pointer");
-    GRAFP_REQUIRE(C > 0 && M > 0 && C <= 65535, "bn_bwd: bad shape C=%d M=%lld", C, (long long)M);
-    GRAFP_REQUIRE(groups >= 1 && groups <= 8 && M % groups == 0, "bn_bwd: groups=%d must be in [1,8] and divide M=%lld", groups, (long long)M);
+    if (int e = bn_check_args("bn_bwd", x && dz && gamma && beta && save_mean && save_invstd && dx && dgamma && dbeta, dtype, C, M,
+                              groups, act))
+        return e;
+    if (int e = bn_check_ws("bn_bwd", ws, ws_bytes, C, M)) return e;
     const int G = groups;
     const int64_t Mg = M / G;
-    GRAFP_REQUIRE(dtype == GRAFP_F32 || dtype == GRAFP_BF16, "bn_bwd: dtype %d not in {f32, bf16}", dtype);
-    GRAFP_REQUIRE(act >= 0 && act <= 2, "bn_bwd: act %d not in {0 none, 1 relu, 2 leaky}", act);
-    if (!ws || ws_bytes < grafp_bn_workspace(C, M)) {
-        set_error("bn_bwd: workspace %zu bytes < required %zu", ws_bytes, grafp_bn_workspace(C, M));
-        return GRAFP_ERR_WORKSPACE;
-    }
     hipStream_t s = (hipStream_t)stream;
     float *part = (float *)ws;
     const bool f32 = dtype == GRAFP_F32;
-    const int W = f32 ? 4 : 8;
-    const bool ok = bn_vec_ok(W, x, dz, dx, nullptr, Mg);
+    const bool ok = bn_vec_ok(bn_vec_width(dtype), x, dz, dx, nullptr, Mg);
     const BnLaunch p = bn_choose(dtype, C, Mg, G, training != 0, true, ok, sync != nullptr);
     if (p.path == BN_PATH_1PASS) {
         // one launch of the single-pass kernel <T, ITEMS, THREADS> over sg chunks per view
@@ -950,14 +931,10 @@ extern "C" int grafp_bn_bwd(const void *x, const void *dz, int dtype, int C, int
 extern "C" int grafp_bn_plan(int dtype, int C, int64_t M, int groups, int training, int backward, int aligned,
                              int have_sync, int *info) {
     using namespace grafp;
-    GRAFP_REQUIRE(info, "bn_plan: null pointer");
-    GRAFP_REQUIRE(C > 0 && M > 0 && C <= 65535, "bn_plan: bad shape C=%d M=%lld", C, (long long)M);
-    GRAFP_REQUIRE(groups >= 1 && groups <= 8 && M % groups == 0, "bn_plan: groups=%d must be in [1,8] and divide M=%lld", groups, (long long)M);
-    GRAFP_REQUIRE(dtype == GRAFP_F32 || dtype == GRAFP_BF16, "bn_plan: dtype %d not in {f32, bf16}", dtype);
+    if (int e = bn_check_args("bn_plan", info != nullptr, dtype, C, M, groups, 0)) return e;
     const int64_t Mg = M / groups;
-    const int W = dtype == GRAFP_F32 ? 4 : 8;
-    const BnLaunch p = bn_choose(dtype, C, Mg, groups, training != 0, backward != 0, aligned != 0 && Mg % W == 0,
-                                 have_sync != 0);
+    const BnLaunch p = bn_choose(dtype, C, Mg, groups, training != 0, backward != 0,
+                                 aligned != 0 && Mg % bn_vec_width(dtype) == 0, have_sync != 0);
     info[0] = p.path;
     info[1] = p.items;
     info[2] = p.threads;

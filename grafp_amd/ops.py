@@ -593,20 +593,9 @@ class _BnAct(torch.autograd.Function):
         x, g32, b32, pb, mean, invstd = ctx.saved_tensors
         C, M, act, slope, training, has_pb, has_res, groups = ctx.cfg
         dz = dz.detach().to(x.dtype).contiguous()
-        dx = torch.empty_like(x)
-        # separate tensors (not views of one buffer): autograd adopts a fresh whole tensor as .grad without a copy
-        dgamma = torch.empty((C,), dtype=torch.float32, device=x.device)
-        dbeta = torch.empty((C,), dtype=torch.float32, device=x.device)
-        # d(pre_bias), written by the kernel: zero under batch statistics, ga*invstd*sum(dy) in eval mode
-        dpb = torch.empty((C,), dtype=torch.float32, device=x.device) if has_pb else None
-        nbytes = lib.grafp_bn_workspace(C, M)
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
-        with _timed("bn_bwd", (C, M, x.element_size())):
-            check(lib.grafp_bn_bwd_1pass(_p(x), _p(dz), _DT[x.dtype], C, M, groups, _p(pb) if has_pb else None, _p(g32),
-                                         _p(b32), _p(mean), _p(invstd), act, slope, int(training), _p(dx), _p(dgamma),
-                                         _p(dbeta), _p(dpb) if has_pb else None, _p(ws), nbytes,
-                                         _p(_bn_sync(x.device, C, M)), switches.bn_spin_limit, _stream()), "bn_bwd")
-        return dx, dgamma, dbeta, dpb, (dz if has_res else None), None, None, None, None, None, None, None, None
+        dx, dgamma, dbeta, dpb = _bn_bwd(x.view(C, M), dz.view(C, M), C, M, groups, pb if has_pb else None, g32, b32, mean,
+                                         invstd, act, slope, training)
+        return dx.view(x.shape), dgamma, dbeta, dpb, (dz if has_res else None), None, None, None, None, None, None, None, None
 
 
 def bn_act(x, gamma, beta, running_mean, running_var, training, momentum=0.1, eps=1e-5, pre_bias=None, residual=None,
@@ -1080,8 +1069,10 @@ def _group_transpose(wl, groups):
 def _bn_bwd(y, dz, C, M, views, pb, g32, b32, mean, invstd, act, slope, training):
     """BatchNorm + activation backward on (C, M) rows (grafp_bn_bwd_1pass): -> dy, dgamma, dbeta, dpre_bias."""
     dy = torch.empty_like(y)
+    # separate tensors (not views of one buffer): autograd adopts a fresh whole tensor as .grad without a copy
     dgamma = torch.empty((C,), dtype=torch.float32, device=y.device)
     dbeta = torch.empty((C,), dtype=torch.float32, device=y.device)
+    # d(pre_bias), written by the kernel: zero under batch statistics, ga*invstd*sum(dy) in eval mode
     dpb = torch.empty((C,), dtype=torch.float32, device=y.device) if pb is not None else None
     nbytes = lib.grafp_bn_workspace(C, M)
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=y.device)

@@ -153,6 +153,35 @@ def test_bn_vs_float64_on_every_path(dev, monkeypatch, name):
         assert q <= 1.0, (key, q, d, "row", int(where[0]))
 
 
+# ---- the recompute fallback of the single-pass rendezvous ----------------------------------------------------------------
+_ONE_PASS = [c.name for c in br.CASES if br.PATH_1PASS in (c.fwd[0], c.bwd[0])]
+
+
+def _bits(a):
+    # float64 widened exactly from f32 / bf16: equal bits here are equal bits there (-0.0 and NaN payloads included)
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+
+
+@pytest.mark.parametrize("name", _ONE_PASS)
+def test_bn_single_pass_recompute_gives_the_same_bits(dev, monkeypatch, name):
+    """Every case of the table with a single-pass launch (f32 and bf16; 4 / 256, 8 / 256 and 8 / 512; ragged last chunks;
+    one, two and three views), once as is and once with a spin limit of 0, where a workgroup does not wait but recomputes
+    from the row whatever partial sums are not yet published: all results are the same bits, and the rendezvous buffer is
+    all ones again afterwards."""
+    from grafp_amd import ops
+    case = br.CASE_BY_NAME[name]
+    inputs = br.case_inputs(case)
+    want, plans = _run(case, inputs, dev, monkeypatch)
+    assert (plans[0][:4], plans[1][:4]) == (case.fwd, case.bwd), plans
+    monkeypatch.setattr(ops.switches, "bn_spin_limit", 0)
+    got, _ = _run(case, inputs, dev, monkeypatch)
+    for key in ("out", "dx", "dgamma", "dbeta", "rm", "rv"):
+        assert np.array_equal(_bits(got[key]), _bits(want[key])), key
+    assert ops._BN_SYNC
+    for buf in ops._BN_SYNC.values():
+        assert bool((buf == -1).all()), "rendezvous buffer not re-armed"
+
+
 # ---- non-finite inputs ------------------------------------------------------------------------------------------------
 _POISON_MODES = {"single-pass": (True, False), "two-pass": (True, True), "eval": (False, False)}
 
