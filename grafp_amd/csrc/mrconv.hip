@@ -48,16 +48,44 @@ __device__ __forceinline__ float mr_fix_decode(unsigned long long a) {
     const int hi = (int)(unsigned)(a >> 32) - (lo >> 31);
     return (float)__builtin_fma((double)hi, 1048576.0, (double)lo);             // the sum exactly, rounded once
 }
-// scale of a slab from the largest |addend| bits (integer maximum of the sign-stripped patterns: NaN / inf sort last)
-__device__ __forceinline__ void mr_fix_scale(unsigned mbits, bool &poisoned, float &scale, float &inv_scale) {
-    poisoned = mbits >= 0x7f800000u;
-    const float m = __uint_as_float(mbits);
+// The fixed-point scale of a slab, in the two halves around the barrier every backward kernel has anyway: each thread brings
+// the largest sign-stripped bit pattern of its g_odd (an integer maximum: NaN / inf sort last), mr_scale_publish leaves the
+// four waves' maxima in s_max, and after the barrier mr_scale_read gives every thread the same scale.
+struct MrScale {
+    float scale, inv_scale;
+    bool poisoned;                                  // a non-finite gradient in the slab: its whole output is NaN
+    __device__ __forceinline__ unsigned long long encode(float g) const { return mr_fix_encode(g, scale); }
+    // the output element: identity branch minus the centre term, plus what was scattered to it
+    __device__ __forceinline__ float out(float base, unsigned long long acc) const {
+        return poisoned ? NAN : base + mr_fix_decode(acc) * inv_scale;
+    }
+};
+__device__ __forceinline__ void mr_scale_publish(unsigned m, unsigned *s_max, int tid) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
+    if ((tid & 63) == 0) s_max[tid >> 6] = m;
+}
+__device__ __forceinline__ MrScale mr_scale_read(const unsigned *s_max) {
+    const unsigned mbits = max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3]));
+    MrScale s;
+    s.poisoned = mbits >= 0x7f800000u;
     int ex = 0;
-    (void)frexpf(m, &ex);                                     // m < 2^ex
+    (void)frexpf(__uint_as_float(mbits), &ex);                // m < 2^ex
     int sh = mbits ? 39 - ex : 0;
     sh = sh > 100 ? 100 : sh;
-    scale = ldexpf(1.0f, sh);
-    inv_scale = ldexpf(1.0f, -sh);
+    s.scale = ldexpf(1.0f, sh);
+    s.inv_scale = ldexpf(1.0f, -sh);
+    return s;
+}
+
+// The routing rule of the backward pass, written once: a node's g_odd goes to the FIRST maximum of x[j] - x[n] over its K
+// edges.  Edge 0 wins unconditionally -- a NaN difference there stays the winner, as the first NaN does in torch.max --
+// and a later edge only on v > best (never a NaN).  The forward record and both recomputing backward kernels call this,
+// so they cannot route differently.  True when edge k is the winner so far.
+__device__ __forceinline__ bool mr_first_max(int k, float v, float &best) {
+    const bool wins = k == 0 || v > best;
+    if (wins) best = v;
+    return wins;
 }
 
 // Activations are addressed as base + b*sb + c*sc + n (N contiguous): (B,C,N) has sb = C*N, sc = N; the
@@ -77,6 +105,18 @@ template <typename I>
 __device__ __forceinline__ void stage_idx(int *sidx, const I *__restrict__ idxb, int N, int K, int tid) {
     for (int n = tid; n < N; n += MR_THREADS)
         for (int k = 0; k < K; ++k) sidx[k * N + n] = clampi((int64_t)idxb[(size_t)n * K + k], N);
+}
+
+// A thread's ITEMS 4-element pieces inside a slab of the persistent kernels: (channel offset, node) of piece it.
+template <int ITEMS>
+__device__ __forceinline__ void mr_pieces(int tid, int N, int (&pc)[ITEMS], int (&pn)[ITEMS]) {
+    MR_WALK(4, tid, N, c, n);
+#pragma unroll
+    for (int it = 0; it < ITEMS; ++it) {
+        pc[it] = c;
+        pn[it] = n;
+        MR_NEXT(4, N, c, n);
+    }
 }
 
 template <typename T, int V, typename I>
@@ -148,17 +188,8 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_fwd_p_kernel(const T *__res
     const int nslab = (C + CC - 1) / CC;
     const T *xb = x + (size_t)b * x_sb;
     T *ob = out + (size_t)b * o_sb;
-    // this thread's pieces inside a slab: (channel offset, node) of piece it
     int pc[MRP_ITEMS], pn[MRP_ITEMS];
-    {
-        MR_WALK(4, tid, N, c, n);
-#pragma unroll
-        for (int it = 0; it < MRP_ITEMS; ++it) {
-            pc[it] = c;
-            pn[it] = n;
-            MR_NEXT(4, N, c, n);
-        }
-    }
+    mr_pieces(tid, N, pc, pn);
     // SEVERAL slabs in flight per workgroup: with one, 5 workgroups x 8 KB per CU = 10 MB on the whole chip, and bytes
     // in flight / HBM latency (~3.5 us under load) is what the kernel ran at (3.5 TB/s).  The pieces wait in registers
     // as they were loaded (bf16: 8 bytes per piece instead of four floats), so the same 32 registers hold FOUR slabs of
@@ -208,10 +239,8 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_fwd_p_kernel(const T *__res
 #pragma unroll
                             for (int e = 0; e < 4; ++e) {
                                 m[e] = fmaxf(m[e], v[e]);
-                                if (WK && (k == 0 || v[e] > best[e])) {  // mrconv_bwd's routing rule, comparison for comparison
-                                    best[e] = v[e];
+                                if (WK && mr_first_max(k, v[e], best[e]))
                                     bk = (bk & ~(3u << (2 * e))) | ((unsigned)k << (2 * e));
-                                }
                             }
                         }
                         if (WK) arg[((size_t)b * C + c0 + pc[it]) * (N / 4) + pn[it] / 4] = (unsigned char)bk;
@@ -240,7 +269,7 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_bwd_kernel(const T *__restr
     __shared__ unsigned s_max[MR_THREADS / 64];
     const int b = blockIdx.y, c0 = blockIdx.x * CC, tid = threadIdx.x;
     const int cc = min(CC, C - c0);
-    // 64-bit fixed-point scatter accumulator + integer LDS atomics (see mrconv_bwd_p_kernel): deterministic, and
+    // 64-bit fixed-point scatter accumulator + integer LDS atomics (see mr_fix_encode): deterministic, and
     // ds_add_u64 is 30x the rate of ds_add_f32 on gfx950
     const size_t slab_al = ((size_t)CC * N + 1) & ~(size_t)1;
     long long *acc = reinterpret_cast<long long *>(smem);
@@ -277,16 +306,11 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_bwd_kernel(const T *__restr
             MR_NEXT(V, N, c, n);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
-    if ((tid & 63) == 0) s_max[tid >> 6] = m;
+    mr_scale_publish(m, s_max, tid);
     stage_idx<I>(sidx, idx + (size_t)b * N * K, N, K, tid);
     __syncthreads();
-    m = max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3]));
-    bool poisoned;
-    float scale, inv_scale;
-    mr_fix_scale(m, poisoned, scale, inv_scale);
-    if (!poisoned) {   // route g_odd[c][m] to the arg-max neighbour of m (first maximum)
+    const MrScale fx = mr_scale_read(s_max);
+    if (!fx.poisoned) {   // route g_odd[c][m] to the arg-max neighbour of m (first maximum)
         MR_WALK(V, tid, N, c, n);
 #pragma unroll
         for (int it = 0; it < BWD_ITEMS; ++it) {
@@ -295,14 +319,13 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_bwd_kernel(const T *__restr
 #pragma unroll
                 for (int e = 0; e < V; ++e) {
                     const float xi = row[n + e];
-                    float best = -INFINITY;
-                    int bj = sidx[n + e];
+                    float best = 0.0f;
+                    int bj = 0;
                     for (int k = 0; k < K; ++k) {
                         const int j = sidx[k * N + n + e];
-                        const float v = row[j] - xi;
-                        if (v > best) { best = v; bj = j; }
+                        if (mr_first_max(k, row[j] - xi, best)) bj = j;
                     }
-                    atomicAdd(reinterpret_cast<unsigned long long *>(&acc[c * N + bj]), mr_fix_encode(godd[it][e], scale));
+                    atomicAdd(reinterpret_cast<unsigned long long *>(&acc[c * N + bj]), fx.encode(godd[it][e]));
                 }
             }
             MR_NEXT(V, N, c, n);
@@ -316,11 +339,10 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_bwd_kernel(const T *__restr
             float v[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                v[e] = poisoned ? NAN : base[c * N + n + e] + mr_fix_decode((unsigned long long)acc[c * N + n + e]) * inv_scale;
+                v[e] = fx.out(base[c * N + n + e], (unsigned long long)acc[c * N + n + e]);
             ElemIO<T>::store(db + (size_t)c * x_sc + n, v, false);
         } else {
-            ElemIO<T>::st1(db + (size_t)c * x_sc + n,
-                  poisoned ? NAN : base[c * N + n] + mr_fix_decode((unsigned long long)acc[c * N + n]) * inv_scale);
+            ElemIO<T>::st1(db + (size_t)c * x_sc + n, fx.out(base[c * N + n], (unsigned long long)acc[c * N + n]));
         }
         MR_NEXT(V, N, c, n);
     }
@@ -348,15 +370,7 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_bwd_p_kernel(const T *__res
     const T *gb = gout + (size_t)b * g_sb;
     T *db = dx + (size_t)b * x_sb;
     int pc[MRB_ITEMS], pn[MRB_ITEMS];
-    {
-        MR_WALK(4, tid, N, c, n);
-#pragma unroll
-        for (int it = 0; it < MRB_ITEMS; ++it) {
-            pc[it] = c;
-            pn[it] = n;
-            MR_NEXT(4, N, c, n);
-        }
-    }
+    mr_pieces(tid, N, pc, pn);
     float pv[MRB_ITEMS][4], pe[MRB_ITEMS][4], po[MRB_ITEMS][4];     // x, g_even, g_odd of the slab in flight
     auto fetch = [&](int slab) {
         const int c0 = slab * CC, cc = min(CC, C - c0);
@@ -390,15 +404,10 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_bwd_p_kernel(const T *__res
                     m = max(m, __float_as_uint(po[it][e]) & 0x7fffffffu);
                 }
             }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
-        if ((tid & 63) == 0) s_max[tid >> 6] = m;
+        mr_scale_publish(m, s_max, tid);
         __syncthreads();
         if (slab + gridDim.x < nslab) fetch(slab + gridDim.x);
-        m = max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3]));
-        bool poisoned;                                          // a non-finite gradient: the slab's output is NaN
-        float scale, inv_scale;
-        mr_fix_scale(m, poisoned, scale, inv_scale);
+        const MrScale fx = mr_scale_read(s_max);
         // route g_odd[c][m] to the arg-max neighbour of m (first maximum)
 #pragma unroll
         for (int it = 0; it < MRB_ITEMS; ++it) {
@@ -410,16 +419,13 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_bwd_p_kernel(const T *__res
                     const int4 j4 = *reinterpret_cast<const int4 *>(sidx + k * N + pn[it]);
                     const int jj[4] = {j4.x, j4.y, j4.z, j4.w};
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float v = row[jj[e]] - xi[it][e];
-                        if (k == 0 || v > best[e]) { best[e] = v; bj[e] = jj[e]; }
-                    }
+                    for (int e = 0; e < 4; ++e)
+                        if (mr_first_max(k, row[jj[e]] - xi[it][e], best[e])) bj[e] = jj[e];
                 }
-                if (!poisoned) {
+                if (!fx.poisoned) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
-                        atomicAdd(reinterpret_cast<unsigned long long *>(&acc[pc[it] * N + bj[e]]),
-                                  mr_fix_encode(godd[it][e], scale));
+                        atomicAdd(reinterpret_cast<unsigned long long *>(&acc[pc[it] * N + bj[e]]), fx.encode(godd[it][e]));
                 }
             }
         }
@@ -430,7 +436,7 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_bwd_p_kernel(const T *__res
                 float v[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    v[e] = poisoned ? NAN : base[it][e] + mr_fix_decode((unsigned long long)acc[pc[it] * N + pn[it] + e]) * inv_scale;
+                    v[e] = fx.out(base[it][e], (unsigned long long)acc[pc[it] * N + pn[it] + e]);
                 ElemIO<T>::store(db + (size_t)(c0 + pc[it]) * x_sc + pn[it], v, false);
             }
     }
@@ -455,16 +461,9 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_bwd_a_kernel(const unsigned
     const int nslab = (C + CC - 1) / CC;
     // this thread's pieces inside a slab: element offset pc * N + pn, node pn
     int off[MRB_ITEMS], pn[MRB_ITEMS], pc[MRB_ITEMS];
-    {
-        MR_WALK(4, tid, N, c, n);
+    mr_pieces(tid, N, pc, pn);
 #pragma unroll
-        for (int it = 0; it < MRB_ITEMS; ++it) {
-            pc[it] = c;
-            pn[it] = n;
-            off[it] = c * N + n;
-            MR_NEXT(4, N, c, n);
-        }
-    }
+    for (int it = 0; it < MRB_ITEMS; ++it) off[it] = pc[it] * N + pn[it];
     // running pointers of the pieces: slab s -> s + gridDim.x moves them by a constant
     const T *ge_p[MRB_ITEMS];
     T *dx_p[MRB_ITEMS];
@@ -527,16 +526,11 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_bwd_a_kernel(const unsigned
                             m = max(m, __float_as_uint(godd[it][e]) & 0x7fffffffu);
                         }
                     }
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
-                if ((tid & 63) == 0) s_max[tid >> 6] = m;
+                mr_scale_publish(m, s_max, tid);
                 __syncthreads();
                 if (slab + NPAR * G < nslab) fetch(par, slab + NPAR * G);
-                m = max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3]));
-                bool poisoned;
-                float scale, inv_scale;
-                mr_fix_scale(m, poisoned, scale, inv_scale);
-                if (!poisoned) {
+                const MrScale fx = mr_scale_read(s_max);
+                if (!fx.poisoned) {
 #pragma unroll
                     for (int it = 0; it < MRB_ITEMS; ++it)
                         if (pc[it] < cc) {
@@ -550,7 +544,7 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_bwd_a_kernel(const unsigned
                                 for (int e = 0; e < 4; ++e) bj[e] = ((ak[it] >> (2 * e)) & 3u) == (unsigned)k ? jj[e] : bj[e];
                             }
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) atomicAdd(arow + bj[e], mr_fix_encode(godd[it][e], scale));
+                            for (int e = 0; e < 4; ++e) atomicAdd(arow + bj[e], fx.encode(godd[it][e]));
                         }
                 }
                 __syncthreads();
@@ -565,7 +559,7 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_bwd_a_kernel(const unsigned
                                                          ((unsigned long long)a23.y << 32) | a23.x,
                                                          ((unsigned long long)a23.w << 32) | a23.z};
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = poisoned ? NAN : base[it][e] + mr_fix_decode(a[e]) * inv_scale;
+                        for (int e = 0; e < 4; ++e) v[e] = fx.out(base[it][e], a[e]);
                         ElemIO<T>::store(dx_p[it], v, plain != 0);
                     }
                     dx_p[it] += dx_step;
@@ -576,200 +570,205 @@ __global__ __launch_bounds__(MR_THREADS) void mrconv_bwd_a_kernel(const unsigned
     }
 }
 
-// the persistent kernels' launch plan: whole channel rows per slab (ccp of them), nslab slabs per clip shared among per_clip
-// workgroups -- 4 per clip, more while the grid has fewer than 1024 workgroups
-struct MrPersistPlan {
-    int ccp, nslab, per_clip;
+// ---- host: the launch choice, made once: a pure function of (strides, shape, alignment, direction, record wanted) that the
+// forward and backward launchers, the two record entries, grafp_mrconv_arg_supported and grafp_mrconv_plan all ask ----------
+enum { MR_PATH_PERSISTENT = 0, MR_PATH_VEC4 = 1, MR_PATH_SCALAR = 2, MR_PATH_RECORD = 3 };
+struct MrLaunch {
+    int path;          // persistent 4-wide | generic 4-wide | generic scalar | persistent with the arg-max record (fwd<WK> / bwd_a)
+    int items;         // pieces (elements, scalar) a thread holds per slab; 0 = the generic forward, whose threads stride
+    int cc;            // channel rows per slab
+    int nslab, per_clip;   // slabs per clip; workgroups per clip (grid.x): one per slab for the generic kernels
+    size_t lds;        // dynamic LDS bytes
 };
-static MrPersistPlan mr_persist_plan(int slab, int C, int N, int B) {
-    MrPersistPlan p;
-    p.ccp = slab / N < C ? slab / N : C;
-    p.nslab = (C + p.ccp - 1) / p.ccp;
-    p.per_clip = p.nslab < 4 ? p.nslab : 4;
-    while ((int64_t)p.per_clip * B < 1024 && p.per_clip < p.nslab) ++p.per_clip;
-    return p;
+constexpr size_t MR_LDS_LIMIT = 160 * 1024;                   // of a gfx950 workgroup
+constexpr int MR_FWD_ELEMS = 4096;   // generic forward; measured: 28 KB of LDS per workgroup (5 per CU) beats the 76 KB slab by 35 %
+static_assert(MRB_SLAB <= MRP_SLAB, "a row that fits the backward slab fits the forward one");
+
+static inline int mr_clamp_cc(int cc, int C) { return cc < 1 ? 1 : (cc > C ? C : cc); }
+
+// x_s*: strides of x (forward) and of dx; o_s*: strides of out (forward) or grad_out (backward).  aligned: every activation
+// pointer of the call is 4-element aligned.  with_arg: the caller wants the arg-max record; where the shape cannot have one
+// the answer is the launch of the plain call, which fwd_arg / bwd_arg refuse.  Shape and dtype are checked (mr_check_args).
+static int mr_choose(int64_t x_sb, int64_t x_sc, int64_t o_sb, int64_t o_sc, int N, int K, int C, int B,
+                     bool aligned, bool backward, bool with_arg, MrLaunch *L) {
+    const bool v4 = aligned && N % 4 == 0 && x_sb % 4 == 0 && x_sc % 4 == 0 && o_sb % 4 == 0 && o_sc % 4 == 0;
+    const size_t edges = (size_t)K * N;
+    // dynamic LDS of each kernel, in 4-byte words: fwd_p rows | edges; bwd_p i64 accumulator + rows | edges; bwd_a i64
+    // accumulator | edges; generic: rows (+ i64 accumulator + identity term, slab rounded to even) | edges
+    const size_t lds_fwd_p = (MRP_SLAB + edges) * 4, lds_bwd_p = (3 * (size_t)MRB_SLAB + edges) * 4,
+                 lds_bwd_a = (2 * (size_t)MRB_SLAB + edges) * 4;
+    auto lds_generic = [&](int cc) {
+        const size_t slab = (size_t)cc * N;
+        return (backward ? 4 * ((slab + 1) & ~(size_t)1) + edges : slab + edges) * 4;
+    };
+    // the record: 2 bits per edge number, written by the persistent forward and read by bwd_a -- both must be able to run
+    const bool record = with_arg && v4 && K <= 4 && N <= MRB_SLAB && lds_fwd_p <= MR_LDS_LIMIT && lds_bwd_a <= MR_LDS_LIMIT;
+    const int slab = backward ? MRB_SLAB : MRP_SLAB;
+    const size_t lds_p = !backward ? lds_fwd_p : (record ? lds_bwd_a : lds_bwd_p);
+    if (record || (v4 && N <= slab && lds_p <= MR_LDS_LIMIT)) {
+        // whole channel rows per slab, shared among 4 workgroups per clip, more while the grid has fewer than 1024 workgroups
+        *L = {record ? MR_PATH_RECORD : MR_PATH_PERSISTENT, backward ? MRB_ITEMS : MRP_ITEMS, std::min(slab / N, C), 0, 0, lds_p};
+        L->nslab = (C + L->cc - 1) / L->cc;
+        L->per_clip = L->nslab < 4 ? L->nslab : 4;
+        while ((int64_t)L->per_clip * B < 1024 && L->per_clip < L->nslab) ++L->per_clip;
+        return GRAFP_OK;
+    }
+    // generic: one slab of whole channel rows per workgroup; backward, it covers exactly items * 256 * V elements (the
+    // odd-channel gradients wait in registers)
+    int items = 0, cc = mr_clamp_cc(MR_FWD_ELEMS / N, C);
+    if (backward) {
+        const int per_item = MR_THREADS * (v4 ? 4 : 1);
+        items = N <= 2 * per_item ? 2 : 8;
+        cc = mr_clamp_cc(items * per_item / N, C);
+        GRAFP_REQUIRE((size_t)cc * N <= (size_t)items * per_item, "mrconv_bwd: N=%d exceeds the %d nodes a workgroup covers", N,
+                      items * per_item);
+        while (cc > 1 && lds_generic(cc) > MR_LDS_LIMIT) --cc;
+    }
+    GRAFP_REQUIRE(lds_generic(cc) <= MR_LDS_LIMIT, "mrconv_%s: N=%d K=%d needs %zu B of LDS (> 160 KiB)",
+                  backward ? "bwd" : "fwd", N, K, lds_generic(cc));
+    *L = {v4 ? MR_PATH_VEC4 : MR_PATH_SCALAR, items, cc, (C + cc - 1) / cc, (C + cc - 1) / cc, lds_generic(cc)};
+    return GRAFP_OK;
 }
 
-static int pick_cc(int C, int N, int target_elems) {
-    int cc = target_elems / N;
-    if (cc < 1) cc = 1;
-    if (cc > C) cc = C;
-    return cc;
+// what every entry asks of its arguments; op names the entry in the message
+static int mr_check_args(const char *op, bool pointers, int dtype, int B, int C, int N, int K) {
+    GRAFP_REQUIRE(pointers, "%s: null pointer", op);
+    GRAFP_REQUIRE(B > 0 && C > 0 && N > 0 && K > 0, "%s: bad shape B=%d C=%d N=%d K=%d", op, B, C, N, K);
+    GRAFP_REQUIRE(dtype == GRAFP_F32 || dtype == GRAFP_BF16, "%s: dtype %d not in {f32, bf16}", op, dtype);
+    return GRAFP_OK;
+}
+
+static bool mr_aligned(int dtype, const void *a, const void *b, const void *c = nullptr) {
+    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) % (dtype == GRAFP_F32 ? 16 : 8)) == 0;
+}
+
+// one launch: per_clip x B workgroups of MR_THREADS with L.lds bytes of dynamic LDS (above the 64 KiB a kernel gets unasked)
+template <typename Kern, typename... Args>
+static int mr_launch(const char *name, Kern kern, const MrLaunch &L, int B, grafp_stream_t stream, Args... args) {
+    (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds);
+    hipLaunchKernelGGL(kern, dim3(L.per_clip, B), dim3(MR_THREADS), L.lds, (hipStream_t)stream, args...);
+    GRAFP_CHECK_LAUNCH(name);
+    return GRAFP_OK;
 }
 
 }  // namespace grafp
 
-// the shapes whose forward can record the arg-max and whose backward can run from it (pointer alignment aside)
-static bool mrconv_arg_shape_ok(int dtype, int64_t x_sb, int64_t x_sc, int64_t o_sb, int64_t o_sc, int N, int K) {
-    using namespace grafp;
-    return (dtype == GRAFP_F32 || dtype == GRAFP_BF16) && N > 0 && K >= 1 && K <= 4 && N % 4 == 0 && x_sb % 4 == 0 &&
-           x_sc % 4 == 0 && o_sb % 4 == 0 && o_sc % 4 == 0 && N <= MRB_SLAB && N <= MRP_SLAB &&
-           ((size_t)MRP_SLAB + (size_t)K * N) * 4 <= 160 * 1024;
-}
-
-static int mrconv_fwd_impl(const void *x, int dtype, int64_t x_sb, int64_t x_sc, const void *idx, int idx32, int B,
-                           int C, int N, int K, void *out, int64_t o_sb, int64_t o_sc, grafp_stream_t stream,
+// arg != nullptr: the forward of grafp_mrconv_fwd_arg (op names the entry)
+static int mrconv_fwd_impl(const char *op, const void *x, int dtype, int64_t x_sb, int64_t x_sc, const void *idx, int idx32,
+                           int B, int C, int N, int K, void *out, int64_t o_sb, int64_t o_sc, grafp_stream_t stream,
                            unsigned char *arg = nullptr) {
     using namespace grafp;
-    GRAFP_REQUIRE(x && idx && out, "mrconv_fwd: null pointer");
-    GRAFP_REQUIRE(B > 0 && C > 0 && N > 0 && K > 0, "mrconv_fwd: bad shape B=%d C=%d N=%d K=%d", B, C, N, K);
-    GRAFP_REQUIRE(dtype == GRAFP_F32 || dtype == GRAFP_BF16, "mrconv_fwd: dtype %d not in {f32, bf16}", dtype);
-#ifndef MR_FWD_ELEMS
-#define MR_FWD_ELEMS 4096    // measured: 28 KB of LDS per workgroup (5 per CU) beats the 76 KB slab by 35 %
-#endif
-    const int CC = pick_cc(C, N, MR_FWD_ELEMS);
-    const size_t lds = ((size_t)CC * N + (size_t)K * N) * 4;
-    GRAFP_REQUIRE(lds <= 160 * 1024, "mrconv_fwd: N=%d K=%d needs %zu B of LDS (> 160 KiB)", N, K, lds);
-    const dim3 grid((C + CC - 1) / CC, B);
-    const size_t es = dtype == GRAFP_F32 ? 4 : 2;
-    const bool v4 = (N % 4 == 0) && (x_sb % 4 == 0) && (x_sc % 4 == 0) && (o_sb % 4 == 0) && (o_sc % 4 == 0) &&
-                    ((uintptr_t)x % (4 * es) == 0) && ((uintptr_t)out % (4 * es) == 0);
-    if (v4 && N <= MRP_SLAB) {
-        // persistent variant: whole channel rows per slab, a few slabs per workgroup
-        const MrPersistPlan pp = mr_persist_plan(MRP_SLAB, C, N, B);
-        const size_t ldsp = ((size_t)MRP_SLAB + (size_t)K * N) * 4;
-        if (ldsp <= 160 * 1024) {
-            const int plain = plain_stores((size_t)2 * B * C * N * es, "GRAFP_MR_PLAIN_MAX_MB", 140);
-            for_elem_idx(dtype, idx32, [&](auto te, auto ti) {
-                using T = typename decltype(te)::type;
-                using I = typename decltype(ti)::type;
-                for_bool(arg != nullptr, [&](auto wk) {
-                    const auto kern = mrconv_fwd_p_kernel<T, I, decltype(wk)::value>;
-                    (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
-                    hipLaunchKernelGGL(kern, dim3(pp.per_clip, B), dim3(MR_THREADS), ldsp, (hipStream_t)stream,
-                                       (const T *)x, x_sb, x_sc, (const I *)idx, (T *)out, o_sb, o_sc, C, N, K, pp.ccp, arg, plain);
-                });
-            });
-            GRAFP_CHECK_LAUNCH("mrconv_fwd_p_kernel");
-            return GRAFP_OK;
-        }
-    }
-    GRAFP_REQUIRE(!arg, "mrconv_fwd_arg: shape / alignment outside grafp_mrconv_arg_supported");
+    if (int e = mr_check_args(op, x && idx && out, dtype, B, C, N, K)) return e;
+    MrLaunch L;
+    if (int e = mr_choose(x_sb, x_sc, o_sb, o_sc, N, K, C, B, mr_aligned(dtype, x, out), false, arg != nullptr, &L)) return e;
+    GRAFP_REQUIRE(!arg || L.path == MR_PATH_RECORD,
+                  "mrconv_fwd_arg: shape / alignment outside grafp_mrconv_arg_supported (N=%d K=%d)", N, K);
+    int rc = GRAFP_OK;
     for_elem_idx(dtype, idx32, [&](auto te, auto ti) {
         using T = typename decltype(te)::type;
         using I = typename decltype(ti)::type;
-        for_bool(v4, [&](auto vec) {
-            const auto kern = mrconv_fwd_kernel<T, decltype(vec)::value ? 4 : 1, I>;
-            (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(kern, grid, dim3(MR_THREADS), lds, (hipStream_t)stream, (const T *)x, x_sb, x_sc,
-                               (const I *)idx, (T *)out, o_sb, o_sc, C, N, K, CC);
-        });
+        if (L.path == MR_PATH_PERSISTENT || L.path == MR_PATH_RECORD) {
+            const int plain = plain_stores((size_t)2 * B * C * N * sizeof(T), "GRAFP_MR_PLAIN_MAX_MB", 140);
+            for_bool(arg != nullptr, [&](auto wk) {
+                rc = mr_launch("mrconv_fwd_p_kernel", mrconv_fwd_p_kernel<T, I, decltype(wk)::value>, L, B, stream, (const T *)x,
+                               x_sb, x_sc, (const I *)idx, (T *)out, o_sb, o_sc, C, N, K, L.cc, arg, plain);
+            });
+        } else {
+            for_bool(L.path == MR_PATH_VEC4, [&](auto vec) {
+                rc = mr_launch("mrconv_fwd_kernel", mrconv_fwd_kernel<T, decltype(vec)::value ? 4 : 1, I>, L, B, stream,
+                               (const T *)x, x_sb, x_sc, (const I *)idx, (T *)out, o_sb, o_sc, C, N, K, L.cc);
+            });
+        }
     });
-    GRAFP_CHECK_LAUNCH("mrconv_fwd_kernel");
-    return GRAFP_OK;
+    return rc;
 }
 
-static int mrconv_bwd_impl(const void *x, int dtype, int64_t x_sb, int64_t x_sc, const void *idx, int idx32,
-                           const void *grad_out, int64_t g_sb, int64_t g_sc, int B, int C, int N, int K, void *dx,
-                           grafp_stream_t stream) {
+// arg != nullptr: the backward of grafp_mrconv_bwd_arg, which reads the record and not x
+static int mrconv_bwd_impl(const char *op, const void *x, const unsigned char *arg, int dtype, int64_t x_sb, int64_t x_sc,
+                           const void *idx, int idx32, const void *grad_out, int64_t g_sb, int64_t g_sc, int B, int C, int N,
+                           int K, void *dx, grafp_stream_t stream) {
     using namespace grafp;
-    GRAFP_REQUIRE(x && idx && grad_out && dx, "mrconv_bwd: null pointer");
-    GRAFP_REQUIRE(B > 0 && C > 0 && N > 0 && K > 0, "mrconv_bwd: bad shape B=%d C=%d N=%d K=%d", B, C, N, K);
-    GRAFP_REQUIRE(dtype == GRAFP_F32 || dtype == GRAFP_BF16, "mrconv_bwd: dtype %d not in {f32, bf16}", dtype);
-    const size_t es = dtype == GRAFP_F32 ? 4 : 2;
-    const bool v4 = (N % 4 == 0) && (x_sb % 4 == 0) && (x_sc % 4 == 0) && (g_sb % 4 == 0) && (g_sc % 4 == 0) &&
-                    ((uintptr_t)x % (4 * es) == 0) && ((uintptr_t)grad_out % (4 * es) == 0) && ((uintptr_t)dx % (4 * es) == 0);
-    if (v4 && N <= MRB_SLAB) {
-        const MrPersistPlan pp = mr_persist_plan(MRB_SLAB, C, N, B);
-        const size_t ldsp = ((size_t)3 * MRB_SLAB + (size_t)K * N) * 4;      // i64 accumulator + f32 rows + edges
-        if (ldsp <= 160 * 1024) {
-            for_elem_idx(dtype, idx32, [&](auto te, auto ti) {
-                using T = typename decltype(te)::type;
-                using I = typename decltype(ti)::type;
-                const auto kern = mrconv_bwd_p_kernel<T, I>;
-                (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
-                hipLaunchKernelGGL(kern, dim3(pp.per_clip, B), dim3(MR_THREADS), ldsp, (hipStream_t)stream, (const T *)x,
-                                   x_sb, x_sc, (const I *)idx, (const T *)grad_out, g_sb, g_sc, (T *)dx, C, N, K, pp.ccp);
-            });
-            GRAFP_CHECK_LAUNCH("mrconv_bwd_p_kernel");
-            return GRAFP_OK;
-        }
-    }
-    // a workgroup covers exactly ITEMS * 256 * V elements (whole channel rows)
-    const int per_item = MR_THREADS * (v4 ? 4 : 1);
-    const int items = N <= 2 * per_item ? 2 : 8;
-    int CC = (items * per_item) / N;
-    if (CC < 1) CC = 1;
-    if (CC > C) CC = C;
-    GRAFP_REQUIRE((size_t)CC * N <= (size_t)items * per_item,
-                  "mrconv_bwd: N=%d exceeds the %d nodes a workgroup covers", N, items * per_item);
-    // i64 accumulator + f32 rows + f32 identity term per slab element, + the clip's edges
-    auto lds_of = [&](int cc_) { return ((size_t)4 * (((size_t)cc_ * N + 1) & ~(size_t)1) + (size_t)K * N) * 4; };
-    while (CC > 1 && lds_of(CC) > 160 * 1024) --CC;
-    const size_t lds = lds_of(CC);
-    GRAFP_REQUIRE(lds <= 160 * 1024, "mrconv_bwd: N=%d K=%d needs %zu B of LDS (> 160 KiB)", N, K, lds);
-    const dim3 grid((C + CC - 1) / CC, B);
+    if (int e = mr_check_args(op, (x || arg) && idx && grad_out && dx, dtype, B, C, N, K)) return e;
+    MrLaunch L;
+    if (int e = mr_choose(x_sb, x_sc, g_sb, g_sc, N, K, C, B, mr_aligned(dtype, x, grad_out, dx), true, arg != nullptr, &L)) return e;
+    GRAFP_REQUIRE(!arg || L.path == MR_PATH_RECORD,
+                  "mrconv_bwd_arg: shape / alignment outside grafp_mrconv_arg_supported (N=%d K=%d)", N, K);
+    int rc = GRAFP_OK;
     for_elem_idx(dtype, idx32, [&](auto te, auto ti) {
         using T = typename decltype(te)::type;
         using I = typename decltype(ti)::type;
-        for_bool(v4, [&](auto vec) {
-            for_bool(items == 2, [&](auto two) {
-                const auto kern = mrconv_bwd_kernel<T, decltype(vec)::value ? 4 : 1, I, decltype(two)::value ? 2 : 8>;
-                (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                hipLaunchKernelGGL(kern, grid, dim3(MR_THREADS), lds, (hipStream_t)stream, (const T *)x, x_sb, x_sc,
-                                   (const I *)idx, (const T *)grad_out, g_sb, g_sc, (T *)dx, C, N, K, CC);
+        if (L.path == MR_PATH_RECORD) {
+            const int plain = plain_stores((size_t)B * C * N * sizeof(T), "GRAFP_MR_PLAIN_MAX_MB", 140);
+            rc = mr_launch("mrconv_bwd_a_kernel", mrconv_bwd_a_kernel<T, I>, L, B, stream, arg, (const I *)idx,
+                           (const T *)grad_out, g_sb, g_sc, (T *)dx, x_sb, x_sc, C, N, K, L.cc, plain);
+        } else if (L.path == MR_PATH_PERSISTENT) {
+            rc = mr_launch("mrconv_bwd_p_kernel", mrconv_bwd_p_kernel<T, I>, L, B, stream, (const T *)x, x_sb, x_sc,
+                           (const I *)idx, (const T *)grad_out, g_sb, g_sc, (T *)dx, C, N, K, L.cc);
+        } else {
+            for_bool(L.path == MR_PATH_VEC4, [&](auto vec) {
+                for_bool(L.items == 2, [&](auto two) {
+                    rc = mr_launch("mrconv_bwd_kernel",
+                                   mrconv_bwd_kernel<T, decltype(vec)::value ? 4 : 1, I, decltype(two)::value ? 2 : 8>, L, B,
+                                   stream, (const T *)x, x_sb, x_sc, (const I *)idx, (const T *)grad_out, g_sb, g_sc, (T *)dx,
+                                   C, N, K, L.cc);
+                });
             });
-        });
+        }
     });
-    GRAFP_CHECK_LAUNCH("mrconv_bwd_kernel");
-    return GRAFP_OK;
+    return rc;
 }
 
 extern "C" int grafp_mrconv_fwd_strided(const void *x, int dtype, int64_t x_sb, int64_t x_sc, const int64_t *idx, int B,
                                         int C, int N, int K, void *out, int64_t o_sb, int64_t o_sc,
                                         grafp_stream_t stream) {
-    return mrconv_fwd_impl(x, dtype, x_sb, x_sc, idx, 0, B, C, N, K, out, o_sb, o_sc, stream);
+    return mrconv_fwd_impl("mrconv_fwd", x, dtype, x_sb, x_sc, idx, 0, B, C, N, K, out, o_sb, o_sc, stream);
 }
 extern "C" int grafp_mrconv_fwd_strided_i32(const void *x, int dtype, int64_t x_sb, int64_t x_sc, const int32_t *idx,
                                             int B, int C, int N, int K, void *out, int64_t o_sb, int64_t o_sc,
                                             grafp_stream_t stream) {
-    return mrconv_fwd_impl(x, dtype, x_sb, x_sc, idx, 1, B, C, N, K, out, o_sb, o_sc, stream);
+    return mrconv_fwd_impl("mrconv_fwd", x, dtype, x_sb, x_sc, idx, 1, B, C, N, K, out, o_sb, o_sc, stream);
 }
 extern "C" int grafp_mrconv_bwd_strided(const void *x, int dtype, int64_t x_sb, int64_t x_sc, const int64_t *idx,
                                         const void *grad_out, int64_t g_sb, int64_t g_sc, int B, int C, int N, int K,
                                         void *dx, grafp_stream_t stream) {
-    return mrconv_bwd_impl(x, dtype, x_sb, x_sc, idx, 0, grad_out, g_sb, g_sc, B, C, N, K, dx, stream);
+    return mrconv_bwd_impl("mrconv_bwd", x, nullptr, dtype, x_sb, x_sc, idx, 0, grad_out, g_sb, g_sc, B, C, N, K, dx, stream);
 }
 extern "C" int grafp_mrconv_bwd_strided_i32(const void *x, int dtype, int64_t x_sb, int64_t x_sc, const int32_t *idx,
                                             const void *grad_out, int64_t g_sb, int64_t g_sc, int B, int C, int N,
                                             int K, void *dx, grafp_stream_t stream) {
-    return mrconv_bwd_impl(x, dtype, x_sb, x_sc, idx, 1, grad_out, g_sb, g_sc, B, C, N, K, dx, stream);
+    return mrconv_bwd_impl("mrconv_bwd", x, nullptr, dtype, x_sb, x_sc, idx, 1, grad_out, g_sb, g_sc, B, C, N, K, dx, stream);
 }
 
+extern "C" int grafp_mrconv_plan(int dtype, int64_t x_sb, int64_t x_sc, int64_t o_sb, int64_t o_sc, int B, int C, int N,
+                                 int K, int aligned, int backward, int with_arg, int *info) {
+    using namespace grafp;
+    if (int e = mr_check_args("mrconv_plan", info != nullptr, dtype, B, C, N, K)) return e;
+    MrLaunch L;
+    if (int e = mr_choose(x_sb, x_sc, o_sb, o_sc, N, K, C, B, aligned != 0, backward != 0, with_arg != 0, &L)) return e;
+    const int out[8] = {L.path, L.items, L.cc, L.nslab, L.per_clip, (int)L.lds, 0, 0};
+    for (int i = 0; i < 8; ++i) info[i] = out[i];
+    return GRAFP_OK;
+}
+
+// the shapes whose forward can record the arg-max and whose backward can run from it (pointer alignment aside)
 extern "C" int grafp_mrconv_arg_supported(int dtype, int64_t x_sb, int64_t x_sc, int64_t o_sb, int64_t o_sc, int N, int K) {
-    return mrconv_arg_shape_ok(dtype, x_sb, x_sc, o_sb, o_sc, N, K) ? 1 : 0;
+    using namespace grafp;
+    MrLaunch L;
+    return (dtype == GRAFP_F32 || dtype == GRAFP_BF16) && N > 0 && K >= 1 &&
+           mr_choose(x_sb, x_sc, o_sb, o_sc, N, K, 1, 1, true, false, true, &L) == GRAFP_OK && L.path == MR_PATH_RECORD;
 }
 extern "C" int grafp_mrconv_fwd_arg(const void *x, int dtype, int64_t x_sb, int64_t x_sc, const void *idx, int idx_is_i32,
                                     int B, int C, int N, int K, void *out, int64_t o_sb, int64_t o_sc, uint8_t *arg,
                                     grafp_stream_t stream) {
     GRAFP_REQUIRE(arg, "mrconv_fwd_arg: null pointer");
-    GRAFP_REQUIRE(mrconv_arg_shape_ok(dtype, x_sb, x_sc, o_sb, o_sc, N, K),
-                  "mrconv_fwd_arg: shape outside grafp_mrconv_arg_supported (N=%d K=%d)", N, K);
-    return mrconv_fwd_impl(x, dtype, x_sb, x_sc, idx, idx_is_i32, B, C, N, K, out, o_sb, o_sc, stream, arg);
+    return mrconv_fwd_impl("mrconv_fwd_arg", x, dtype, x_sb, x_sc, idx, idx_is_i32, B, C, N, K, out, o_sb, o_sc, stream, arg);
 }
 extern "C" int grafp_mrconv_bwd_arg(const uint8_t *arg, int dtype, const void *idx, int idx_is_i32, const void *grad_out,
                                     int64_t g_sb, int64_t g_sc, int B, int C, int N, int K, void *dx, int64_t d_sb,
                                     int64_t d_sc, grafp_stream_t stream) {
-    using namespace grafp;
-    GRAFP_REQUIRE(arg && idx && grad_out && dx, "mrconv_bwd_arg: null pointer");
-    GRAFP_REQUIRE(B > 0 && C > 0, "mrconv_bwd_arg: bad shape B=%d C=%d", B, C);
-    const size_t es = dtype == GRAFP_F32 ? 4 : 2;
-    GRAFP_REQUIRE(mrconv_arg_shape_ok(dtype, d_sb, d_sc, g_sb, g_sc, N, K) && (uintptr_t)grad_out % (4 * es) == 0 &&
-                      (uintptr_t)dx % (4 * es) == 0,
-                  "mrconv_bwd_arg: shape / alignment outside grafp_mrconv_arg_supported (N=%d K=%d)", N, K);
-    const MrPersistPlan pp = mr_persist_plan(MRB_SLAB, C, N, B);
-    const size_t ldsp = (size_t)8 * MRB_SLAB + (size_t)4 * K * N;             // i64 accumulator + edges [K][N]
-    const int plain = plain_stores((size_t)B * C * N * es, "GRAFP_MR_PLAIN_MAX_MB", 140);
-    for_elem_idx(dtype, idx_is_i32, [&](auto te, auto ti) {
-        using T = typename decltype(te)::type;
-        using I = typename decltype(ti)::type;
-        const auto kern = mrconv_bwd_a_kernel<T, I>;
-        (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
-        hipLaunchKernelGGL(kern, dim3(pp.per_clip, B), dim3(MR_THREADS), ldsp, (hipStream_t)stream, arg, (const I *)idx,
-                           (const T *)grad_out, g_sb, g_sc, (T *)dx, d_sb, d_sc, C, N, K, pp.ccp, plain);
-    });
-    GRAFP_CHECK_LAUNCH("mrconv_bwd_a_kernel");
-    return GRAFP_OK;
+    GRAFP_REQUIRE(arg, "mrconv_bwd_arg: null pointer");
+    return mrconv_bwd_impl("mrconv_bwd_arg", nullptr, arg, dtype, d_sb, d_sc, idx, idx_is_i32, grad_out, g_sb, g_sc, B, C, N, K, dx,
+                           stream);
 }
 
 extern "C" int grafp_mrconv_fwd_f32(const float *x, const int64_t *idx, int B, int C, int N, int K, float *out,

@@ -493,8 +493,13 @@ class _MaxRelative(torch.autograd.Function):
         out = torch.empty((B, 2 * C, N) if layout == "bcn" else (2 * C, B, N), dtype=x.dtype, device=x.device)
         o_sb, o_sc = (2 * C * N, N) if layout == "bcn" else (N, B * N)
         ctx.layout, ctx.dims = layout, (B, C, N, tuple(x.shape), x.dtype)
-        ctx.from_arg = bool(switches.mrconv_arg and ctx.needs_input_grad[0]
-                            and lib.grafp_mrconv_arg_supported(_DT[x.dtype], sb, sc, o_sb, o_sc, N, K))
+        ctx.from_arg = False
+        if switches.mrconv_arg and ctx.needs_input_grad[0]:
+            # the launch this very call would take with a record: shape, strides and the alignment of x and out decide
+            info = (ctypes.c_int * 8)()
+            aligned = x.data_ptr() % (4 * x.element_size()) == 0 and out.data_ptr() % (4 * x.element_size()) == 0
+            check(lib.grafp_mrconv_plan(_DT[x.dtype], sb, sc, o_sb, o_sc, B, C, N, K, int(aligned), 0, 1, info), "mrconv_plan")
+            ctx.from_arg = info[0] == 3
         if ctx.from_arg:
             # training: record which neighbour won (2 bits per element) -- backward then needs neither x nor the gather
             arg = torch.empty((B, C, N // 4), dtype=torch.uint8, device=x.device)

@@ -177,6 +177,17 @@ int grafp_mrconv_fwd_arg(const void *x, int dtype, int64_t x_sb, int64_t x_sc, c
 int grafp_mrconv_bwd_arg(const uint8_t *arg, int dtype, const void *idx, int idx_is_i32, const void *grad_out,
                          int64_t g_sb, int64_t g_sc, int B, int C, int N, int K, void *dx, int64_t d_sb, int64_t d_sc,
                          grafp_stream_t stream);
+/* The launch a max-relative call takes (a pure host function of the arguments, as grafp_bn_plan; every entry above chooses
+ * through the same host function).  backward == 0: x_s* are x's strides and o_s* out's; backward != 0: x_s* are x's and dx's
+ * strides and o_s* grad_out's.  aligned != 0 = every activation pointer of the call (x, out / x, grad_out, dx; from the
+ * record: grad_out, dx) is aligned to 4 elements.  with_arg != 0 = the caller wants the arg-max record
+ * (grafp_mrconv_fwd_arg / _bwd_arg): path 3 says the call can have it, any other path is the launch of the plain call.
+ * info (host, 8 ints) = {path: 0 persistent 4-wide, 1 generic 4-wide, 2 generic scalar, 3 persistent with the record;
+ * 4-element pieces (path 2: elements) a thread holds per slab, 0 = the generic forward's threads stride over the slab;
+ * channel rows per slab; slabs per clip; workgroups per clip; dynamic LDS bytes; 0; 0}.  GRAFP_ERR_ARG with a message where
+ * no kernel takes the shape (backward: N > 2048 unaligned; LDS over 160 KiB). */
+int grafp_mrconv_plan(int dtype, int64_t x_sb, int64_t x_sc, int64_t o_sb, int64_t o_sc, int B, int C, int N, int K,
+                      int aligned, int backward, int with_arg, int *info);
 
 /* ---- K8/K9 glue: fused [conv bias] + BatchNorm + activation + residual on the (C, M = B*N) layout ----
  * Replaces the `+ bias` -> BatchNorm2d -> ReLU/LeakyReLU -> `+ shortcut` chains around every 1x1 convolution
