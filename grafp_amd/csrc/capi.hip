@@ -154,3 +154,58 @@ extern "C" int grafp_self_match_f32(const float *index_rows, int64_t n, const in
                                     min_votes, min_overlap, ws, ws_bytes, out_track, out_delta, out_start, out_len,
                                     out_score, out_votes, (hipStream_t)stream);
 }
+
+// What recordings held outside a library share with it (crossmatch.hip): argument checks here, the kernels there.
+namespace grafp {
+int cross_match_launch(const float *rows, int64_t n, const int64_t *first, int T, const float *q_rows,
+                       const int64_t *src_first, int n_src, const int64_t *ids, int k, int top, int min_votes,
+                       int min_overlap, void *ws, size_t ws_bytes, int32_t *out_track, int32_t *out_delta,
+                       int32_t *out_start, int32_t *out_len, float *out_score, int32_t *out_votes, hipStream_t stream);
+int cross_match_pq_launch(const int32_t *list_id, const unsigned char *codes, int64_t n, const float *centroids,
+                          int nlist, const float *codebooks, int M, const int64_t *first, int T, const float *q_rows,
+                          const int64_t *src_first, int n_src, const int64_t *ids, int k, int top, int min_votes,
+                          int min_overlap, void *ws, size_t ws_bytes, int32_t *out_track, int32_t *out_delta,
+                          int32_t *out_start, int32_t *out_len, float *out_score, int32_t *out_votes,
+                          hipStream_t stream);
+}  // namespace grafp
+
+extern "C" int grafp_cross_match_f32(const float *index_rows, int64_t n, const int64_t *track_first_row, int n_tracks,
+                                     const float *q_rows, int64_t n_qrows, const int64_t *src_first_row, int n_src,
+                                     const int64_t *topk_ids, int k, int top, int min_votes, int min_overlap, void *ws,
+                                     size_t ws_bytes, int32_t *out_track, int32_t *out_delta, int32_t *out_start,
+                                     int32_t *out_len, float *out_score, int32_t *out_votes, grafp_stream_t stream) {
+    GRAFP_REQUIRE(index_rows && track_first_row && q_rows && src_first_row && topk_ids && out_track && out_delta &&
+                  out_start && out_len && out_score && out_votes, "cross_match: null pointer");
+    // n + the longest source < 2^32 (the width of a hit key's alignment half) follows from the two row bounds
+    GRAFP_REQUIRE(n >= 1 && n < 0x7fffff00ll && n_tracks >= 1 && n_qrows >= 0 && n_qrows < 0x7fffff00ll && n_src >= 0,
+                  "cross_match: bad sizes n=%lld n_tracks=%d n_qrows=%lld n_src=%d", (long long)n, n_tracks,
+                  (long long)n_qrows, n_src);
+    GRAFP_REQUIRE((((uintptr_t)index_rows | (uintptr_t)q_rows) & 15) == 0, "cross_match: rows must be 16-byte aligned");
+    return grafp::cross_match_launch(index_rows, n, track_first_row, n_tracks, q_rows, src_first_row, n_src, topk_ids,
+                                     k, top, min_votes, min_overlap, ws, ws_bytes, out_track, out_delta, out_start,
+                                     out_len, out_score, out_votes, (hipStream_t)stream);
+}
+
+extern "C" int grafp_cross_match_pq_f32(const int32_t *list_id, const uint8_t *codes, int64_t n, const float *centroids,
+                                        int nlist, const float *codebooks, int M, const int64_t *track_first_row,
+                                        int n_tracks, const float *q_rows, int64_t n_qrows,
+                                        const int64_t *src_first_row, int n_src, const int64_t *topk_ids, int k,
+                                        int top, int min_votes, int min_overlap, void *ws, size_t ws_bytes,
+                                        int32_t *out_track, int32_t *out_delta, int32_t *out_start, int32_t *out_len,
+                                        float *out_score, int32_t *out_votes, grafp_stream_t stream) {
+    GRAFP_REQUIRE(list_id && codes && centroids && codebooks && track_first_row && q_rows && src_first_row &&
+                  topk_ids && out_track && out_delta && out_start && out_len && out_score && out_votes,
+                  "cross_match_pq: null pointer");
+    GRAFP_REQUIRE(n >= 1 && n < 0x7fffff00ll && nlist >= 1 && n_tracks >= 1 && n_qrows >= 0 &&
+                  n_qrows < 0x7fffff00ll && n_src >= 0,
+                  "cross_match_pq: bad sizes n=%lld nlist=%d n_tracks=%d n_qrows=%lld n_src=%d", (long long)n, nlist,
+                  n_tracks, (long long)n_qrows, n_src);
+    GRAFP_REQUIRE((((uintptr_t)centroids | (uintptr_t)codebooks | (uintptr_t)q_rows) & 15) == 0 &&
+                  (((uintptr_t)codes | (uintptr_t)list_id) & 3) == 0,
+                  "cross_match_pq: centroids, codebooks and query rows must be 16-byte aligned, codes and list ids "
+                  "4-byte");
+    return grafp::cross_match_pq_launch(list_id, codes, n, centroids, nlist, codebooks, M, track_first_row, n_tracks,
+                                        q_rows, src_first_row, n_src, topk_ids, k, top, min_votes, min_overlap, ws,
+                                        ws_bytes, out_track, out_delta, out_start, out_len, out_score, out_votes,
+                                        (hipStream_t)stream);
+}

@@ -35,24 +35,16 @@
 //      smaller a); it becomes ~ord(score) << 32 | t, every other entry empty;
 //   5. bitonic sort of those; the first `top` entries are the result.
 // The five phases are identify_item of identify_core.h, shared with identify_pq.hip (the same operation on a library held
-// as IVF-PQ codes); this file supplies the span rows of phase 3 (RowSpan: the resident f32 rows) and the launch.
+// as IVF-PQ codes); this file supplies the span rows of phase 3 (RowSpan of span_rows.h: the resident f32 rows) and the launch.
 // Built WITHOUT packed-f32 instructions (Makefile NOPK, as corpus.hip): its sums are plain fmaf chains, and the packed
 // operand-select form is the hazard of DESIGN.md section 12.7b.
 #include "identify_core.h"
+#include "span_rows.h"
 
 namespace grafp {
 
 // row pairs in flight in the score loop (seqmatch.h, span_sum): query rows in LDS / in global memory
 constexpr int ID_UNROLL_QLDS = 4, ID_UNROLL_QGLOBAL = 1;
-
-// the span rows of identify_core.h's phase 3: the library's resident f32 rows
-template <int kUnroll>
-struct RowSpan {
-    const float4 *rw4;
-    __device__ __forceinline__ float operator()(const float4 *x, int64_t row, int l, int m) const {
-        return span_sum<kUnroll>(x, rw4 + row * (SEQ_D / 4) + l, m);
-    }
-};
 
 template <bool kQLds>
 __global__ __launch_bounds__(ID_THREADS) void identify_kernel(

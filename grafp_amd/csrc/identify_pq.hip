@@ -6,7 +6,7 @@
 // (one f32 add per element, never an fma: the f32 form of oracle/ivfpq.py::reconstruct), and every output is bit for bit
 // what identify_kernel writes when it is handed the (n, 128) f32 array dec.  Candidates, eligibility, the per-track best,
 // the ranking, the ties, the LDS layout and phases 1, 2, 4 and 5 are identify_core.h's identify_item, shared with
-// identify.hip; only the span rows of phase 3 differ (PqSpan below).
+// identify.hip; only the span rows of phase 3 differ (PqSpan of span_rows.h).
 //
 // Per row a lane of the half-wave (it owns dims 4l..4l+3) reads its float4 of the row's coarse centroid, the code
 // byte(s) of the sub-spaces that hold its dims and the codewords those bytes name:
@@ -20,63 +20,12 @@
 // that the list ids and code bytes of the next rows are issued ahead of the fmaf chain of this one.
 // Built WITHOUT packed-f32 instructions (Makefile NOPK), as identify.hip.
 #include "identify_core.h"
+#include "span_rows.h"
 
 namespace grafp {
 
 // rows decoded ahead of the fmaf chain: query rows in LDS / in global memory
 constexpr int IDPQ_UNROLL_QLDS = 4, IDPQ_UNROLL_QGLOBAL = 2;
-
-template <int kM, int kUnroll>
-struct PqSpan {
-    const int32_t *__restrict__ list_id;        // (n)
-    const unsigned char *__restrict__ codes;    // (n, kM), library row order
-    const float *__restrict__ centroids;        // (nlist, 128)
-    const float *__restrict__ codebooks;        // (kM, 256, 128 / kM)
-    int nlist;
-
-    // lane l's four floats of the codewords of row `cr`
-    __device__ __forceinline__ float4 codeword(const unsigned char *cr, int l) const {
-        constexpr int dsub = SEQ_D / kM;
-        if (kM == 16) {
-            const int m = l >> 1;
-            return *reinterpret_cast<const float4 *>(codebooks + ((size_t)m * 256 + cr[m]) * dsub + (l & 1) * 4);
-        } else if (kM == 32) {
-            return *reinterpret_cast<const float4 *>(codebooks + ((size_t)l * 256 + cr[l]) * dsub);
-        } else if (kM == 64) {
-            const unsigned int cc = reinterpret_cast<const unsigned short *>(cr)[l];
-            const float2 w0 = *reinterpret_cast<const float2 *>(codebooks + ((size_t)(2 * l) * 256 + (cc & 255u)) * dsub);
-            const float2 w1 = *reinterpret_cast<const float2 *>(codebooks + ((size_t)(2 * l + 1) * 256 + (cc >> 8)) * dsub);
-            return make_float4(w0.x, w0.y, w1.x, w1.y);
-        } else {
-            const unsigned int cc = reinterpret_cast<const unsigned int *>(cr)[l];
-            return make_float4(codebooks[(size_t)(4 * l) * 256 + (cc & 255u)],
-                               codebooks[(size_t)(4 * l + 1) * 256 + ((cc >> 8) & 255u)],
-                               codebooks[(size_t)(4 * l + 2) * 256 + ((cc >> 16) & 255u)],
-                               codebooks[(size_t)(4 * l + 3) * 256 + (cc >> 24)]);
-        }
-    }
-
-    __device__ __forceinline__ float operator()(const float4 *x, int64_t row, int l, int m) const {
-        const float4 *c4 = reinterpret_cast<const float4 *>(centroids);
-        float acc = 0.0f;
-#pragma unroll kUnroll
-        for (int t = 0; t < m; ++t) {
-            const int64_t r = row + t;
-            int lid = list_id[r];
-            lid = lid < 0 ? 0 : (lid < nlist ? lid : nlist - 1);       // (valid list ids need no clamp)
-            const float4 q = x[(int64_t)t * (SEQ_D / 4)];
-            const float4 c = c4[(size_t)lid * (SEQ_D / 4) + l];
-            const float4 w = codeword(codes + r * kM, l);
-            acc = __builtin_fmaf(q.x, c.x + w.x, acc);
-            acc = __builtin_fmaf(q.y, c.y + w.y, acc);
-            acc = __builtin_fmaf(q.z, c.z + w.z, acc);
-            acc = __builtin_fmaf(q.w, c.w + w.w, acc);
-        }
-#pragma unroll
-        for (int s = 16; s > 0; s >>= 1) acc += __shfl_xor(acc, s);      // stays inside the 32-lane half
-        return acc;
-    }
-};
 
 template <int kM, bool kQLds>
 __global__ __launch_bounds__(ID_THREADS) void identify_pq_kernel(

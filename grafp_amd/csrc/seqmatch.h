@@ -1,5 +1,6 @@
-// seqmatch.h -- what the sequence-matching kernels share: seq_rerank.hip (row-level rerank), identify.hip (track-aware
-// identification), selfmatch.hip (shared audio inside a library).  Device helpers only, no state; compiles with and
+// seqmatch.h -- what the sequence-matching kernels share: seq_rerank.hip (row-level rerank), identify.hip and
+// identify_pq.hip (track-aware identification), selfmatch.hip and crossmatch.hip (shared audio inside a library, and of
+// recordings against one).  Device helpers only, no state; compiles with and
 // without the packed-f32 instructions (Makefile NOPK).
 //
 // THE arithmetic order of a span score (restated for the CPU in oracle/csrc/seq_rerank.c and tests/_identify_ref.py):

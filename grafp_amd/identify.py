@@ -4,12 +4,16 @@
                                        [--index flat|ivfpq --nlist 64 --pq-m 64 --nprobe 20 --train-rows 65536]
   python -m grafp_amd.identify query --ckp MODEL.pth --library LIBDIR FILES... [--top 5] [--window S --hop S]
   python -m grafp_amd.identify dedup --ckp MODEL.pth --library LIBDIR [--min-overlap 3] [--coverage 0.9] [--json OUT]
+  python -m grafp_amd.identify match --ckp MODEL.pth --library LIBDIR FILES... [--min-overlap 3] [--min-votes 4]
+                                       [--min-score S] [--top 8] [--k-probe 20] [--json OUT]
 
 `build` fingerprints every track of the source (anything DeviceAudioCorpus accepts) into LIBDIR -- with --index ivfpq as
 a compact library of IVF-PQ codes (about 150 bytes per row instead of 772; `query` works on either form, `dedup` needs
 the flat one); `query` prints one JSON
 object per query file -- or, with --window, one per timeline span of each file; `dedup` prints one JSON object per pair
-of tracks that share audio, then one per group of duplicates (--json also writes both to a file)."""
+of tracks that share audio, then one per group of duplicates (--json also writes both to a file); `match` takes whole
+recordings that are not in the library and prints one JSON object per (recording, library track) that share audio, with
+the span and the coverage (either form of a library; --json also writes them to a file)."""
 import argparse
 import json
 import sys
@@ -65,6 +69,19 @@ def main(argv=None):
     d.add_argument("--k-probe", type=int, default=32)
     d.add_argument("--json", default=None, help="also write {pairs, groups} to this file")
     d.add_argument("--force", action="store_true", help="use a library made with another model")
+    m = sub.add_parser("match", help="find what whole recordings share with a library")
+    m.add_argument("--config", default=DEFAULT_CONFIG, help="model configuration (the library keeps its own "
+                                                            "segmentation settings)")
+    m.add_argument("--ckp", required=True)
+    m.add_argument("--library", required=True)
+    m.add_argument("files", nargs="+")
+    m.add_argument("--min-overlap", type=float, default=3.0, help="seconds of shared audio a match needs")
+    m.add_argument("--min-votes", type=int, default=4, help="rows whose hits must agree on the alignment")
+    m.add_argument("--min-score", type=float, default=None, help="drop weaker matches (default: keep all)")
+    m.add_argument("--top", type=int, default=8, help="library tracks reported per recording")
+    m.add_argument("--k-probe", type=int, default=20)
+    m.add_argument("--json", default=None, help="also write the matches to this file")
+    m.add_argument("--force", action="store_true", help="use a library made with another model")
     args = ap.parse_args(argv)
 
     from .data import DeviceAudioCorpus
@@ -99,6 +116,16 @@ def main(argv=None):
         if args.json:
             with open(args.json, "w") as f:
                 json.dump({"pairs": pairs, "groups": groups}, f, indent=1)
+        return 0
+    if args.cmd == "match":
+        res = lib.match(list(args.files), k_probe=args.k_probe, min_overlap_s=args.min_overlap,
+                        min_votes=args.min_votes, min_score=args.min_score, top=args.top)
+        found = [{"recording": path, **hit} for path, hits in zip(args.files, res) for hit in hits]
+        for hit in found:
+            print(json.dumps(hit))
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump({"matches": found}, f, indent=1)
         return 0
     if args.window is None:
         for path, matches in zip(args.files, lib.identify(list(args.files), top=args.top, k_probe=args.k_probe)):

@@ -11,8 +11,13 @@ A library has two forms.  The flat form above keeps every row as f32 (plus the i
 per row).  The compact form keeps IVF-PQ codes only -- per row M code bytes in row order, the list id, and the
 grafp_amd.ivfpq.IVFPQIndex over them (the codes again in list order, the ids): 2 M + 20 bytes per row, 148 at M = 64 --
 and identifies with ops.identify_pq (csrc/identify_pq.hip), which scores the decoded rows without ever storing them.
-build(index="ivfpq"), compress() and load() make one; identify, identify_windows and timeline work on either form;
-rows() and self_matches() need the flat one."""
+build(index="ivfpq"), compress() and load() make one; identify, identify_windows, timeline and match work on either
+form; rows() and self_matches() need the flat one.
+
+match() takes whole recordings of any length that are NOT in the library and says which tracks they share audio with,
+where and how much (spans, coverage, votes: what self_matches says about the library's own tracks) -- the question an
+ingest gate asks before add().  It runs on ops.cross_match (f32 rows) or ops.cross_match_pq (codes), the kernels of
+csrc/crossmatch.hip."""
 import hashlib
 import json
 import math
@@ -668,6 +673,82 @@ class FingerprintLibrary:
                                 "offset": d, "a_start_s": lo * seg_s, "b_start_s": (lo + d) * seg_s,
                                 "overlap_s": m * seg_s, "coverage": m / max(1, min(int(lens[a]), int(lens[b]))),
                                 "score": sc, "votes": int(v_[s, j])})
+        return out
+
+    # ---- recordings against the catalog -------------------------------------------------------------------------
+    def match(self, recordings, fs=None, k_probe=20, min_overlap_s=3.0, min_votes=4, min_score=None, top=8,
+              max_segments=4096, batch_rows=1 << 18):
+        """What whole recordings share with the library: is an upload already in the catalogue, in whole or in part,
+        which tracks does a mix or medley contain, and where.  recordings: as identify's queries (one waveform, a list
+        of ragged waveforms, or file paths, at `fs`; other rates are resampled on the device), of any length.  They are
+        segmented, embedded in model calls of at least max_segments segments, searched with self.index (k_probe hits per
+        row) and matched in launches of about batch_rows rows by ops.cross_match (flat) or ops.cross_match_pq (compact);
+        nothing is added to the library.
+        -> per recording, a list of {track, name, score, votes, offset, recording_start_s, track_start_s, overlap_s,
+        coverage, recording_coverage, track_coverage}, best first (a single recording: its list alone, as identify).  The
+        recording's audio from recording_start_s reappears in `track` from track_start_s for overlap_s seconds; offset =
+        delta in segments (row i of the recording sits on row i + offset of the track); coverage = overlapping rows /
+        rows of the shorter of the two, recording_coverage and track_coverage the same over the rows of each; score =
+        mean cosine over the span; votes = rows whose hits agree on the alignment.  At most `top` tracks per recording,
+        each at its best alignment.  min_overlap_s, min_votes and min_score as for self_matches.  A recording shorter
+        than one segment, or an empty library, gives [].
+        k_probe = 20 is identify's default; it has not been measured for this use (self_matches uses 32 because it
+        drops a row's hits on its own track; nothing is dropped here).
+        One recording is one workgroup, as a track is in self_matches: an hour-long recording is not split into pieces,
+        its hits are sorted through the launch's workspace (ops.self_match_workspace_bytes of the batch's row counts)."""
+        single = isinstance(recordings, (str, np.ndarray, torch.Tensor)) and (
+            isinstance(recordings, str) or torch.as_tensor(recordings).dim() == 1)
+        waves = self._load_queries(recordings, fs)
+        if self.n_rows == 0:
+            res = [[] for _ in waves]
+        else:
+            rows, counts = self._fingerprint_tracks(waves, int(max_segments))
+            res = self._match_rows(rows, counts, int(k_probe), float(min_overlap_s), int(min_votes), min_score,
+                                   int(top), int(batch_rows))
+        return res[0] if single and len(res) == 1 else res
+
+    def _match_rows(self, q, counts, k_probe, min_overlap_s, min_votes, min_score, top, batch_rows):
+        """match() from the recordings' rows on: q (n_q, 128) f32 on the device, counts the rows of each recording."""
+        seg_s, dev = self.segment_s, self.device
+        min_overlap = max(1, int(math.ceil(min_overlap_s / seg_s - 1e-9)))
+        k = min(k_probe, self.n_rows)
+        lens = np.diff(self.first)
+        first_d = torch.from_numpy(self.first).to(dev)
+        starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        out = [[] for _ in counts]
+        s0 = 0
+        while s0 < len(counts):
+            s1 = s0 + 1
+            while s1 < len(counts) and starts[s1] - starts[s0] < batch_rows:
+                s1 += 1
+            qb = q[int(starts[s0]):int(starts[s1])]
+            if qb.shape[0]:
+                _, ids = self.index.search(qb, k)
+                src = torch.from_numpy(starts[s0:s1 + 1] - starts[s0])
+                kw = dict(top=top, min_votes=min_votes, min_overlap=min_overlap)
+                if self.is_compact:
+                    res = ops.cross_match_pq(*self.codes(), self._pq["centroids"], self._pq["codebooks"], first_d, qb,
+                                             src, ids, **kw)
+                else:
+                    res = ops.cross_match(self.rows(), first_d, qb, src, ids, **kw)
+                b_, d_, lo_, m_, sc_, v_ = (x.cpu().numpy() for x in res)
+                for s in range(s0, s1):
+                    for j in range(b_.shape[1]):
+                        b = int(b_[s - s0, j])
+                        if b == -2:                              # the op sizes the workspace exactly: never
+                            raise RuntimeError(f"cross_match: recording {s} did not fit the workspace")
+                        if b < 0:
+                            break
+                        sc = float(sc_[s - s0, j])
+                        if min_score is not None and sc < min_score:
+                            continue
+                        d, lo, m = int(d_[s - s0, j]), int(lo_[s - s0, j]), int(m_[s - s0, j])
+                        lr, lt = max(1, int(counts[s])), max(1, int(lens[b]))
+                        out[s].append({"track": b, "name": self.names[b], "score": sc, "votes": int(v_[s - s0, j]),
+                                       "offset": d, "recording_start_s": lo * seg_s, "track_start_s": (lo + d) * seg_s,
+                                       "overlap_s": m * seg_s, "coverage": m / min(lr, lt),
+                                       "recording_coverage": m / lr, "track_coverage": m / lt})
+            s0 = s1
         return out
 
     @staticmethod

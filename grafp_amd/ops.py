@@ -1704,6 +1704,116 @@ def self_match(index_rows, track_first_row, topk_ids, tracks=None, top=8, min_vo
     return outs
 
 
+def _cross_match_args(name, n, track_first_row, q_rows, src_first_row, topk_ids, top, min_votes, min_overlap):
+    """The host checks ops.cross_match and ops.cross_match_pq share -> (track table, source table, rows per source),
+    host int64 tensors."""
+    k = int(topk_ids.shape[1])
+    if not 1 <= top <= SELF_MATCH_MAX_TOP:
+        raise ValueError(f"{name}: top={top} not in [1, {SELF_MATCH_MAX_TOP}]")
+    if not 1 <= k <= SELF_MATCH_MAX_K:
+        raise ValueError(f"{name}: k={k} hits per row exceeds {SELF_MATCH_MAX_K}")
+    if int(min_votes) < 1 or int(min_overlap) < 1:
+        raise ValueError(f"{name}: min_votes and min_overlap must be at least 1")
+    if n < 1:
+        raise ValueError(f"{name}: a library of {n} rows")
+    if q_rows.dim() != 2 or q_rows.shape[1] != 128:
+        raise ValueError(f"{name}: q_rows must be (n_q, 128), not {tuple(q_rows.shape)}")
+    n_q = int(q_rows.shape[0])
+    if topk_ids.dim() != 2 or int(topk_ids.shape[0]) != n_q:
+        raise ValueError(f"{name}: topk_ids has {int(topk_ids.shape[0])} rows for {n_q} source rows")
+    first_h = check_track_table(track_first_row, n)
+    src_h = torch.as_tensor(src_first_row).detach().to("cpu", torch.int64).reshape(-1)
+    if src_h.numel() < 1 or int(src_h[0]) != 0 or int(src_h[-1]) != n_q or bool((src_h[1:] < src_h[:-1]).any()):
+        raise ValueError(f"{name}: the source table must run from 0 to n_q = {n_q} and never decrease")
+    lens = src_h[1:] - src_h[:-1]
+    if lens.numel() and int(lens.max()) * k > 2 ** 31 - 1:
+        raise ValueError(f"{name}: a source of {int(lens.max())} rows has more than 2^31 - 1 hits at k={k} "
+                         "(votes are int32)")
+    if n + (int(lens.max()) if lens.numel() else 0) >= 2 ** 32 or max(n, n_q) >= 0x7fffff00:
+        raise ValueError(f"{name}: n={n} library rows and n_q={n_q} source rows exceed the 32-bit alignment of a hit key")
+    return first_h, src_h, lens
+
+
+def _cross_match_outs(n_src, top, dev):
+    """The six (n_src, top) results, holding the padding (what sources without rows get)."""
+    pad = (-1, -2 ** 31, -1, 0, float("-inf"), 0)
+    return tuple(torch.full((n_src, top), pad[j], dtype=torch.float32 if j == 4 else torch.int32, device=dev)
+                 for j in range(6))
+
+
+def cross_match(index_rows, track_first_row, q_rows, src_first_row, topk_ids, top=8, min_votes=4, min_overlap=1):
+    """What recordings held outside a track-indexed library share with it (grafp_cross_match_f32, one workgroup per
+    source): ops.self_match with the sources taken from q_rows instead of the library.
+    index_rows (n,128) f32 resident library, track_first_row (T+1) int64, q_rows (n_q,128) f32 the rows of S sources
+    laid end to end, src_first_row (S+1) int64 (source s = rows [src_first[s], src_first[s+1]); first 0, last n_q),
+    topk_ids (n_q,k) int64 every source row's hits from searching the library (-1 or outside [0, n): no hit).
+    Row i of a source with hit first[b] + j votes for (b, delta = j - i); nothing is dropped.  Spans, eligibility, the
+    score, the per-partner best and the order are ops.self_match's, and so are the six (S, top) results and their
+    padding.  The tables and the limits are checked on the host."""
+    top, k = int(top), int(topk_ids.shape[1])
+    n = int(index_rows.shape[0])
+    first_h, src_h, lens = _cross_match_args("cross_match", n, track_first_row, q_rows, src_first_row, topk_ids, top,
+                                             min_votes, min_overlap)
+    _require_gpu(index_rows, q_rows, topk_ids)
+    index_rows, q_rows = _f32c(index_rows), _f32c(q_rows)
+    dev = index_rows.device
+    n_src = lens.numel()
+    outs = _cross_match_outs(n_src, top, dev)
+    if n_src == 0 or q_rows.shape[0] == 0:
+        return outs
+    first, src = first_h.to(dev), src_h.to(dev)
+    topk_ids = topk_ids.to(torch.int64).contiguous()
+    ws = torch.empty(self_match_workspace_bytes(lens.numpy(), k, min_votes), dtype=torch.uint8, device=dev)
+    with _timed("cross_match", (n_src, int(lens.sum()), k)):
+        check(lib.grafp_cross_match_f32(_p(index_rows), n, _p(first), first.numel() - 1, _p(q_rows), q_rows.shape[0],
+                                        _p(src), n_src, _p(topk_ids), k, top, int(min_votes), int(min_overlap), _p(ws),
+                                        ws.numel(), *(_p(o) for o in outs), _stream()), "cross_match")
+    return outs
+
+
+def cross_match_pq(list_id, codes, centroids, codebooks, track_first_row, q_rows, src_first_row, topk_ids, top=8,
+                   min_votes=4, min_overlap=1):
+    """ops.cross_match against a library held as IVF-PQ codes (grafp_cross_match_pq_f32): library row r is
+    centroids[list_id[r]] + the codewords codes[r] names (one f32 add per element), and every output is bit for bit
+    what ops.cross_match returns on those decoded rows.  list_id, codes, centroids, codebooks as for ops.identify_pq
+    (the list ids are range-checked on the host); the other arguments and the results as for ops.cross_match."""
+    top, k = int(top), int(topk_ids.shape[1])
+    if codes.dim() != 2 or codes.dtype != torch.uint8:
+        raise ValueError(f"cross_match_pq: codes must be (n, M) uint8, not {tuple(codes.shape)} {codes.dtype}")
+    n, M = int(codes.shape[0]), int(codes.shape[1])
+    if M not in IDENTIFY_PQ_M:
+        raise ValueError(f"cross_match_pq: M={M} sub-quantisers, not one of {IDENTIFY_PQ_M}")
+    if list_id.dtype != torch.int32 or tuple(list_id.shape) != (n,):
+        raise ValueError(f"cross_match_pq: list_id must be ({n},) int32, not {tuple(list_id.shape)} {list_id.dtype}")
+    if centroids.dim() != 2 or centroids.shape[0] < 1 or centroids.shape[1] != 128:
+        raise ValueError(f"cross_match_pq: centroids must be (nlist, 128), not {tuple(centroids.shape)}")
+    if tuple(codebooks.shape) != (M, 256, 128 // M):
+        raise ValueError(f"cross_match_pq: codebooks must be {(M, 256, 128 // M)} for M={M}, not "
+                         f"{tuple(codebooks.shape)}")
+    nlist = int(centroids.shape[0])
+    first_h, src_h, lens = _cross_match_args("cross_match_pq", n, track_first_row, q_rows, src_first_row, topk_ids,
+                                             top, min_votes, min_overlap)
+    if not 0 <= int(list_id.min().item()) <= int(list_id.max().item()) < nlist:
+        raise ValueError(f"cross_match_pq: a list id lies outside [0, {nlist})")
+    _require_gpu(list_id, codes, centroids, codebooks, q_rows, topk_ids)
+    list_id, codes = list_id.detach().contiguous(), codes.detach().contiguous()
+    centroids, codebooks, q_rows = _f32c(centroids), _f32c(codebooks), _f32c(q_rows)
+    dev = codes.device
+    n_src = lens.numel()
+    outs = _cross_match_outs(n_src, top, dev)
+    if n_src == 0 or q_rows.shape[0] == 0:
+        return outs
+    first, src = first_h.to(dev), src_h.to(dev)
+    topk_ids = topk_ids.to(torch.int64).contiguous()
+    ws = torch.empty(self_match_workspace_bytes(lens.numpy(), k, min_votes), dtype=torch.uint8, device=dev)
+    with _timed("cross_match_pq", (n_src, int(lens.sum()), k, M)):
+        check(lib.grafp_cross_match_pq_f32(_p(list_id), _p(codes), n, _p(centroids), nlist, _p(codebooks), M, _p(first),
+                                           first.numel() - 1, _p(q_rows), q_rows.shape[0], _p(src), n_src,
+                                           _p(topk_ids), k, top, int(min_votes), int(min_overlap), _p(ws), ws.numel(),
+                                           *(_p(o) for o in outs), _stream()), "cross_match_pq")
+    return outs
+
+
 class FlatL2Index:
     """Drop-in for the subset of faiss.IndexFlatL2 that eval.py uses: d, ntotal, add(x), search(q, k).
     The database lives in HBM; `add` also computes the per-row squared norms once."""

@@ -615,6 +615,34 @@ int grafp_self_match_f32(const float *index_rows, int64_t n, const int64_t *trac
                          grafp_stream_t stream);
 size_t grafp_self_match_workspace(const int64_t *src_rows, int n_src, int k, int min_votes);
 
+/* ---- what recordings held outside a library share with it (grafp_amd/library.py; crossmatch.hip) -----------------
+ * grafp_cross_match_f32 -- grafp_self_match_f32 with the sources taken from outside the library: source s is the rows
+ *   [src_first_row[s], src_first_row[s+1]) of q_rows (n_qrows, 128) f32 (n_src + 1 int64 entries on the device, first
+ *   0, last n_qrows, non-decreasing: a source may have no rows), and topk_ids (n_qrows, k) int64 the library hits of
+ *   every source row (-1 or any id outside [0, n): no hit).  index_rows, track_first_row: as for grafp_identify_f32.
+ *   Row i of a source with hit r in track b votes for the candidate (b, delta = (r - first[b]) - i); nothing is
+ *   dropped, duplicate ids vote twice.  Spans, eligibility, the score
+ *   (sum_{i = i_lo..i_hi} <q_rows[src_first_row[s] + i], row[first[b] + i + delta]>) / m, the per-partner best, the
+ *   order, the six outputs (n_src, top) and their padding are those of grafp_self_match_f32.
+ *   ws: grafp_self_match_workspace(src_rows, n_src, k, min_votes) bytes, src_rows (HOST) the rows of each source; a
+ *   smaller ws (but at least its header) marks the sources that do not fit -2, as there.
+ *   Limits: k <= 32, 1 <= top <= 64, min_votes >= 1, min_overlap >= 1, L * k <= INT_MAX hits per source, n and
+ *   n_qrows below 2^31 - 256 (so n + L < 2^32); rows 16-byte aligned.
+ * grafp_cross_match_pq_f32 -- the same against a library held as IVF-PQ codes: library row r is the dec[r] of
+ *   grafp_identify_pq_f32 (one f32 add per element), and all six outputs are bit for bit what grafp_cross_match_f32
+ *   writes for index_rows = dec.  list_id, codes, centroids, codebooks, M and their alignment as there. */
+int grafp_cross_match_f32(const float *index_rows, int64_t n, const int64_t *track_first_row, int n_tracks,
+                          const float *q_rows, int64_t n_qrows, const int64_t *src_first_row, int n_src,
+                          const int64_t *topk_ids, int k, int top, int min_votes, int min_overlap, void *ws,
+                          size_t ws_bytes, int32_t *out_track, int32_t *out_delta, int32_t *out_start, int32_t *out_len,
+                          float *out_score, int32_t *out_votes, grafp_stream_t stream);
+int grafp_cross_match_pq_f32(const int32_t *list_id, const uint8_t *codes, int64_t n, const float *centroids, int nlist,
+                             const float *codebooks, int M, const int64_t *track_first_row, int n_tracks,
+                             const float *q_rows, int64_t n_qrows, const int64_t *src_first_row, int n_src,
+                             const int64_t *topk_ids, int k, int top, int min_votes, int min_overlap, void *ws,
+                             size_t ws_bytes, int32_t *out_track, int32_t *out_delta, int32_t *out_start,
+                             int32_t *out_len, float *out_score, int32_t *out_votes, grafp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,5 @@
-"""Measurements of shared-audio detection inside a library (ops.self_match, csrc/selfmatch.hip); prints one JSON line.
+"""Measurements of shared-audio detection inside a library (ops.self_match, csrc/selfmatch.hip) and, with --cross, of
+whole recordings against it (ops.cross_match / cross_match_pq, csrc/crossmatch.hip); prints one JSON line.
 
 A library of --tracks tracks x --track-s seconds (default 3 300 x 30 s: 303 segments each, about 1 M rows of random unit
 fingerprints) with --copies planted copies (default 100): a noisy sub-range of one track written into another at a known
@@ -8,6 +9,13 @@ offset.  Then:
   recall      planted pairs found in both directions with the exact offset
 Times from events (median of --reps); `rocprofv3 --kernel-trace --stats -- python tools/selfmatch_bench.py` gives the
 per-kernel figures.  Target: self_match <= 0.25 x search.
+--cross: the sources are copies of the library's tracks held outside the library, their hits the same search result.
+  cross_match              ops.cross_match with every source's hits on its own track blanked: the work ops.self_match
+                           does (it drops them), and the six outputs must equal self_match's bit for bit
+  cross_match_all_hits     nothing blanked: every source also finds the track it copies (a 303-row span to score)
+  cross_match_pq[_all_hits]  the same two launches through ops.cross_match_pq against the library encoded at M = 64
+                           (a quantiser trained on the first 65 536 rows; the codes decide the rows that are scored, not
+                           the work)
 """
 import argparse
 import json
@@ -34,6 +42,31 @@ def _events(fn, reps):
     return float(np.median(times))
 
 
+def _cross(ops, rows, first, ids, per, reps):
+    """The cross mode (see the top): sources = copies of the library's tracks, src_first = the track table."""
+    from grafp_amd.ivfpq import IVFPQIndex
+    n = rows.shape[0]
+    q = rows.clone()
+    own = torch.arange(n, device=rows.device) // per                       # the track of every row
+    blanked = torch.where(torch.div(ids, per, rounding_mode="floor") == own[:, None], -1, ids)
+    kw = dict(top=8, min_votes=4)
+    same = all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in
+               zip(ops.cross_match(rows, first, q, first, blanked, **kw), ops.self_match(rows, first, ids, **kw)))
+    res = {"cross_match_equals_self_match": bool(same),
+           "cross_match_ms": _events(lambda: ops.cross_match(rows, first, q, first, blanked, **kw), reps) * 1e3,
+           "cross_match_all_hits_ms": _events(lambda: ops.cross_match(rows, first, q, first, ids, **kw), reps) * 1e3}
+    pq = IVFPQIndex(d=128, nlist=64, M=64, device=rows.device, niter=8, keep_raw=False)
+    pq.train(rows[:65536])
+    parts = [pq.encode(rows[lo:lo + 65536]) for lo in range(0, n, 65536)]
+    lid, codes = torch.cat([p[0] for p in parts]).to(torch.int32), torch.cat([p[1] for p in parts])
+    args = (lid, codes, pq.centroids, pq.codebooks, first, q, first)
+    res["cross_match_pq_ms"] = _events(lambda: ops.cross_match_pq(*args, blanked, **kw), reps) * 1e3
+    res["cross_match_pq_all_hits_ms"] = _events(lambda: ops.cross_match_pq(*args, ids, **kw), reps) * 1e3
+    b_, d_ = (x.cpu().numpy() for x in ops.cross_match_pq(*args, ids, **kw)[:2])
+    res["pq_sources_that_find_their_track_at_delta_0"] = int(((b_[:, 0] == np.arange(len(b_))) & (d_[:, 0] == 0)).sum())
+    return {k: round(v, 3) if isinstance(v, float) else v for k, v in res.items()}
+
+
 def main(argv=None):
     from grafp_amd import library, ops
     from grafp_amd.util import load_config
@@ -43,6 +76,7 @@ def main(argv=None):
     ap.add_argument("--copies", type=int, default=100)
     ap.add_argument("--k", type=int, default=32)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--cross", action="store_true", help="also time ops.cross_match and ops.cross_match_pq (M = 64)")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     cfg = load_config()
@@ -83,6 +117,8 @@ def main(argv=None):
            "self_match_over_search": round(t_sm / t_search, 4),
            "recall_exact_offset": round(hit / (2 * len(planted)), 4),
            "stray_pairs": len(stray), "max_stray_score": round(max(stray), 4) if stray else None}
+    if args.cross:
+        out.update(_cross(ops, rows, first, ids, per, args.reps))
     print(json.dumps(out))
 
 
