@@ -19,10 +19,69 @@
 
 namespace grafp {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int WG_KC = 128;               // contraction columns per LDS chunk
 constexpr int WG_LS = WG_KC * 2 + 16;    // LDS row stride in bytes (272: ds_read_b128 rows land on distinct bank quads)
+
+// ---- what the kernels of this file share -------------------------------------------------------------
+// Logical block -> (K-split, output tile): one XCD (= one L2) owns a contiguous range of logical blocks, and the output
+// tiles of one K-split are consecutive logical blocks, so tiles that re-read the same G rows / X rows of a split hit
+// that L2.  TO x TC is the output tile of a workgroup.
+struct WgTile {
+    int split, o0, c0;
+};
+template <int TO, int TC> __device__ __forceinline__ WgTile wg_tile_of(int nblocks, int tiles_o, int tiles_c) {
+    const int ntiles = tiles_o * tiles_c;
+    const int logical = xcd_remap(blockIdx.x, nblocks);
+    WgTile w;
+    w.split = logical / ntiles;
+    const int tile = logical - w.split * ntiles;
+    w.o0 = (tile / tiles_c) * TO;
+    w.c0 = (tile % tiles_c) * TC;
+    return w;
+}
+// The register-staged kernels: a split is cols_per_split columns of the whole M (the last one may be short and ragged).
+template <typename E> struct WgSplit {
+    int split, grp, o0, c0;
+    int64_t m_begin, m_end;
+    const E *Gg, *Xg;
+};
+template <int TW, typename E>
+__device__ __forceinline__ WgSplit<E> wg_split(const E *G, const E *X, int64_t M, int cout_g, int cin_g, int tiles_o,
+                                               int tiles_c, int64_t cols_per_split) {
+    const WgTile t = wg_tile_of<TW, TW>(gridDim.x, tiles_o, tiles_c);
+    WgSplit<E> w;
+    w.split = t.split, w.grp = blockIdx.z, w.o0 = t.o0, w.c0 = t.c0;
+    w.Gg = G + (size_t)w.grp * cout_g * M;
+    w.Xg = X + (size_t)w.grp * cin_g * M;
+    w.m_begin = (int64_t)w.split * cols_per_split;
+    w.m_end = (w.m_begin + cols_per_split < M) ? w.m_begin + cols_per_split : M;
+    return w;
+}
+template <int RT, int CT> __device__ __forceinline__ void wg_zero(f32x16 (&acc)[RT][CT]) {
+#pragma unroll
+    for (int a = 0; a < RT; ++a)
+#pragma unroll
+        for (int b = 0; b < CT; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
+}
+// A wave's RT x CT accumulator tiles -> part[split][grp][o][c]; (ob, cb) = the first row and column of the wave's tiles,
+// pp = the (split, grp) plane.  Rows and columns beyond the matrix are not stored.
+template <int RT, int CT>
+__device__ __forceinline__ void wg_store_partial(float *__restrict__ pp, const f32x16 (&acc)[RT][CT], int ob, int cb,
+                                                 int cout_g, int cin_g, int half, int l31) {
+#pragma unroll
+    for (int a = 0; a < RT; ++a)
+#pragma unroll
+        for (int b = 0; b < CT; ++b) {
+            const int c = cb + b * 32 + l31;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int o = ob + a * 32 + mfma_row(r, half);
+                if (o < cout_g && c < cin_g) pp[(size_t)o * cin_g + c] = acc[a][b][r];
+            }
+        }
+}
 
 // TW = output tile edge per workgroup (64: one 32x32 MFMA tile per wave; 128: 2x2 tiles per wave, which halves
 // the re-reads of the smaller operand for the large outputs).
@@ -37,25 +96,14 @@ __global__ __launch_bounds__(256) void wgrad_partial_kernel(const unsigned short
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char *sG = smem, *sX = smem + TW * WG_LS;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
-    // one XCD (= one L2) owns a contiguous range of logical blocks, and the output tiles of one K-slice are
-    // consecutive logical blocks: tiles that re-read the same G rows / X rows of a slice hit that L2
-    const int ntiles = tiles_o * tiles_c;
-    const int logical = xcd_remap(blockIdx.x, gridDim.x);
-    const int split = logical / ntiles, tile = logical - split * ntiles, grp = blockIdx.z;
-    const int o0 = (tile / tiles_c) * TW, c0 = (tile % tiles_c) * TW;
-    const unsigned short *Gg = G + (size_t)grp * cout_g * M;
-    const unsigned short *Xg = X + (size_t)grp * cin_g * M;
-    const int64_t m_begin = (int64_t)split * cols_per_split;
-    const int64_t m_end = (m_begin + cols_per_split < M) ? m_begin + cols_per_split : M;
+    const WgSplit<unsigned short> w = wg_split<TW>(G, X, M, cout_g, cin_g, tiles_o, tiles_c, cols_per_split);
+    const int split = w.split, grp = w.grp, o0 = w.o0, c0 = w.c0;
+    const unsigned short *Gg = w.Gg, *Xg = w.Xg;
+    const int64_t m_begin = w.m_begin, m_end = w.m_end;
     const int wo = wave >> 1, wc = wave & 1;
 
     f32x16 acc[NT][NT];
-#pragma unroll
-    for (int a = 0; a < NT; ++a)
-#pragma unroll
-        for (int b = 0; b < NT; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
+    wg_zero(acc);
 
     const bool vec_ok = (M & 7) == 0;
     // chunk m0 of both operands -> registers: thread -> (row = i*16 + tid/16, 16-byte column tid%16)
@@ -97,18 +145,18 @@ __global__ __launch_bounds__(256) void wgrad_partial_kernel(const unsigned short
         const unsigned char *xa = sX + (wc * Q + l31) * WG_LS + half * 16;
 #pragma unroll
         for (int kk = 0; kk < WG_KC / 16; ++kk) {
-            bf16x8 av[NT], bv[NT];
+            gm_bf16x8 av[NT], bv[NT];
 #pragma unroll
-            for (int a = 0; a < NT; ++a) av[a] = *reinterpret_cast<const bf16x8 *>(ga + a * 32 * WG_LS + kk * 32);
+            for (int a = 0; a < NT; ++a) av[a] = *reinterpret_cast<const gm_bf16x8 *>(ga + a * 32 * WG_LS + kk * 32);
 #pragma unroll
-            for (int b = 0; b < NT; ++b) bv[b] = *reinterpret_cast<const bf16x8 *>(xa + b * 32 * WG_LS + kk * 32);
+            for (int b = 0; b < NT; ++b) bv[b] = *reinterpret_cast<const gm_bf16x8 *>(xa + b * 32 * WG_LS + kk * 32);
 #pragma unroll
             for (int a = 0; a < NT; ++a)
 #pragma unroll
                 for (int b = 0; b < NT; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[a], bv[b], acc[a][b], 0, 0, 0);
         }
     }
-    // partial tile -> part[split][grp][o][c]
+    // partial tile -> part[split][grp][o][c]; written out here: through wg_store_partial the 64-tile takes 100 VGPRs, not 96
     float *pp = part + ((size_t)split * gridDim.z + grp) * cout_g * cin_g;
 #pragma unroll
     for (int a = 0; a < NT; ++a)
@@ -129,13 +177,12 @@ __global__ __launch_bounds__(256) void wgrad_partial_kernel(const unsigned short
 //                                             Gl Xl^T term and the 16-bit representation are ~2^-16 relative)
 // -- 3 matrix instructions at the bf16 rate (16x the f32 MFMA rate) instead of the library's f32 GEMM, which runs
 // this tall-K shape at 42 ms per step.  64 x 64 tiles only (four LDS planes of 64 rows).
-typedef float wg_f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 wg_bf16x2 __attribute__((ext_vector_type(2)));
 // two values -> (packed hi pair, packed lo pair): v_cvt_pk_bf16_f32 (round to nearest even), exact residual, again
 __device__ __forceinline__ void wg_split2(float a, float b, unsigned &hi, unsigned &lo) {
-    const wg_f32x2 v = {a, b};
+    const gm_f32x2 v = {a, b};
     const wg_bf16x2 h = __builtin_convertvector(v, wg_bf16x2);
-    const wg_bf16x2 l = __builtin_convertvector(v - __builtin_convertvector(h, wg_f32x2), wg_bf16x2);
+    const wg_bf16x2 l = __builtin_convertvector(v - __builtin_convertvector(h, gm_f32x2), wg_bf16x2);
     hi = __builtin_bit_cast(unsigned, h);
     lo = __builtin_bit_cast(unsigned, l);
 }
@@ -153,18 +200,13 @@ __global__ __launch_bounds__(256) void wgrad3_partial_kernel(const float *__rest
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char *sGh = smem, *sGl = smem + PL, *sXh = smem + 2 * PL, *sXl = smem + 3 * PL;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
-    const int ntiles = tiles_o * tiles_c;
-    const int logical = xcd_remap(blockIdx.x, gridDim.x);
-    const int split = logical / ntiles, tile = logical - split * ntiles, grp = blockIdx.z;
-    const int o0 = (tile / tiles_c) * TW, c0 = (tile % tiles_c) * TW;
-    const float *Gg = G + (size_t)grp * cout_g * M;
-    const float *Xg = X + (size_t)grp * cin_g * M;
-    const int64_t m_begin = (int64_t)split * cols_per_split;
-    const int64_t m_end = (m_begin + cols_per_split < M) ? m_begin + cols_per_split : M;
+    const WgSplit<float> w = wg_split<TW>(G, X, M, cout_g, cin_g, tiles_o, tiles_c, cols_per_split);
+    const int split = w.split, grp = w.grp, o0 = w.o0, c0 = w.c0;
+    const float *Gg = w.Gg, *Xg = w.Xg;
+    const int64_t m_begin = w.m_begin, m_end = w.m_end;
     const int wo = wave >> 1, wc = wave & 1;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    f32x16 acc[1][1];
+    wg_zero(acc);
     const bool vec_ok = (M & 3) == 0;
     float4 pg[TW / 16][2], px[TW / 16][2];
     auto ld8 = [&](const float *rowp, int64_t m, float4 (&d)[2]) {
@@ -209,22 +251,17 @@ __global__ __launch_bounds__(256) void wgrad3_partial_kernel(const float *__rest
         const int ga = (wo * 32 + l31) * WG_LS + half * 16, xa = (wc * 32 + l31) * WG_LS + half * 16;
 #pragma unroll
         for (int kk = 0; kk < WG_KC / 16; ++kk) {
-            const bf16x8 gh = *reinterpret_cast<const bf16x8 *>(sGh + ga + kk * 32);
-            const bf16x8 gl = *reinterpret_cast<const bf16x8 *>(sGl + ga + kk * 32);
-            const bf16x8 xh = *reinterpret_cast<const bf16x8 *>(sXh + xa + kk * 32);
-            const bf16x8 xl = *reinterpret_cast<const bf16x8 *>(sXl + xa + kk * 32);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gl, xh, acc, 0, 0, 0);     // small terms first
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gh, xl, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gh, xh, acc, 0, 0, 0);
+            const gm_bf16x8 gh = *reinterpret_cast<const gm_bf16x8 *>(sGh + ga + kk * 32);
+            const gm_bf16x8 gl = *reinterpret_cast<const gm_bf16x8 *>(sGl + ga + kk * 32);
+            const gm_bf16x8 xh = *reinterpret_cast<const gm_bf16x8 *>(sXh + xa + kk * 32);
+            const gm_bf16x8 xl = *reinterpret_cast<const gm_bf16x8 *>(sXl + xa + kk * 32);
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gl, xh, acc[0][0], 0, 0, 0);     // small terms first
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gh, xl, acc[0][0], 0, 0, 0);
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gh, xh, acc[0][0], 0, 0, 0);
         }
     }
-    float *pp = part + ((size_t)split * gridDim.z + grp) * cout_g * cin_g;
-    const int c = c0 + wc * 32 + l31;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int o = o0 + wo * 32 + mfma_row(r, half);
-        if (o < cout_g && c < cin_g) pp[(size_t)o * cin_g + c] = acc[r];
-    }
+    wg_store_partial<1, 1>(part + ((size_t)split * gridDim.z + grp) * cout_g * cin_g, acc, o0 + wo * 32, c0 + wc * 32,
+                           cout_g, cin_g, half, l31);
 }
 
 // ---- the LDS-DMA form (every shape of the encoder: rows per group % 32 == 0, M per view % 64 == 0) ---------------------
@@ -272,6 +309,80 @@ typedef WgCfg<2, 4, 4, 2, 4, 32> WgL32;                            // 256 x 256,
 typedef WgCfg<2, 2, 2, 2, 3> WgSG;                                 // wgrad_gr_kernel: 128 x 128, 80 KB, 2 workgroups per CU
 typedef WgCfg<2, 4, 4, 2, 3> WgLG;                                 // wgrad_gr_kernel: 256 x 256, 160 KB, 1 workgroup per CU
 
+// where a workgroup of the two LDS-DMA kernels works: a slice is cols_per_slice columns of ONE view (whole chunks of KC
+// columns), T its chunks; Gg / Xg point at the slice's first column of the group's first row
+struct WgSlice {
+    int slice, grp, view, o0, c0, T;
+    const unsigned short *Gg, *Xg;
+};
+template <typename CFG>
+__device__ __forceinline__ WgSlice wg_slice(const unsigned short *G, const unsigned short *X, int64_t M, int cout_g, int cin_g,
+                                            int tiles_o, int tiles_c, int slices_view, int64_t cols_per_slice, int views,
+                                            int nblocks) {
+    const WgTile t = wg_tile_of<CFG::TO, CFG::TC>(nblocks, tiles_o, tiles_c);
+    WgSlice w;
+    w.slice = t.split, w.grp = blockIdx.z, w.o0 = t.o0, w.c0 = t.c0;
+    w.view = w.slice / slices_view;
+    const int sl = w.slice - w.view * slices_view;
+    const int64_t Mv = M / views;
+    const int64_t m_begin = (int64_t)w.view * Mv + (int64_t)sl * cols_per_slice;
+    int64_t m_len = Mv - (int64_t)sl * cols_per_slice;
+    if (m_len > cols_per_slice) m_len = cols_per_slice;
+    w.T = (int)(m_len / CFG::KC);
+    w.Gg = G + (size_t)w.grp * cout_g * M + m_begin;
+    w.Xg = X + (size_t)w.grp * cin_g * M + m_begin;
+    return w;
+}
+// DMA sources of one operand: instruction q covers tile rows RPD q .. RPD q + RPD - 1; lane -> row RPD q + lane / SLOTS, and
+// its LDS slot lane % SLOTS receives the source slot (lane % SLOTS) ^ swz(row).  Rows beyond the matrix re-read its last
+// row (their outputs are not stored).  r0 = the tile's first row, rows = rows per group, ND instructions per wave.
+template <typename CFG, int ND>
+__device__ __forceinline__ void wg_row_src(const unsigned short *base, int r0, int rows, int64_t M, int wave, int lane,
+                                           const unsigned short *(&src)[ND]) {
+#pragma unroll
+    for (int j = 0; j < ND; ++j) {
+        const int row = CFG::RPD * (ND * wave + j) + lane / CFG::SLOTS;
+        int r = r0 + row;
+        if (r > rows - 1) r = rows - 1;
+        src[j] = base + (size_t)r * M + (((lane & (CFG::SLOTS - 1)) ^ CFG::swz(row)) << 3);
+    }
+}
+// fragment read offsets of one operand: base + row * ROWB + ((2 ks + half) ^ swz(row)) * 16; the XOR is applied per k-step
+template <typename CFG, int NT>
+__device__ __forceinline__ void wg_frag_rows(int row0, int base, int l31, int (&off)[NT], int (&sw)[NT]) {
+#pragma unroll
+    for (int a = 0; a < NT; ++a) {
+        const int row = row0 + a * 32 + l31;
+        off[a] = base + row * CFG::ROWB;
+        sw[a] = CFG::swz(row);
+    }
+}
+// one chunk: KC / 16 k-steps of swizzled ds_read_b128 fragments (G from gs, X from xs) and RT x CT MFMAs; xform(bv) is
+// applied to the X fragments of a k-step before they are multiplied (PRO)
+template <typename CFG, typename XF>
+__device__ __forceinline__ void wg_chunk_product(const unsigned char *gs, const unsigned char *xs, const int (&goff)[CFG::RT],
+                                                 const int (&gx)[CFG::RT], const int (&xoff)[CFG::CT],
+                                                 const int (&xx)[CFG::CT], int half, f32x16 (&acc)[CFG::RT][CFG::CT],
+                                                 XF &&xform) {
+    constexpr int RT = CFG::RT, CT = CFG::CT;
+#pragma unroll
+    for (int ks = 0; ks < CFG::KC / 16; ++ks) {
+        gm_bf16x8 av[RT], bv[CT];
+#pragma unroll
+        for (int a = 0; a < RT; ++a)
+            av[a] = *reinterpret_cast<const gm_bf16x8 *>(gs + goff[a] + (((2 * ks + half) ^ gx[a]) << 4));
+#pragma unroll
+        for (int b = 0; b < CT; ++b)
+            bv[b] = *reinterpret_cast<const gm_bf16x8 *>(xs + xoff[b] + (((2 * ks + half) ^ xx[b]) << 4));
+        xform(bv);
+#pragma unroll
+        for (int a = 0; a < RT; ++a)
+#pragma unroll
+            for (int b = 0; b < CT; ++b)
+                acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[a], bv[b], acc[a][b], 0, 0, 0);
+    }
+}
+
 template <typename CFG, bool PRO>
 __global__ __launch_bounds__(CFG::THREADS) void wgrad_dma_kernel(
     const unsigned short *__restrict__ G, const unsigned short *__restrict__ X, int64_t M, int cout_g, int cin_g,
@@ -286,18 +397,8 @@ __global__ __launch_bounds__(CFG::THREADS) void wgrad_dma_kernel(
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wo = wave / CFG::WM, wc = wave % CFG::WM;
     const unsigned lds0 = (unsigned)(uintptr_t)(gm_lptr)smem;
-    const int ntiles = tiles_o * tiles_c;
-    const int logical = xcd_remap(blockIdx.x, nblocks);
-    const int slice = logical / ntiles, tile = logical - slice * ntiles, grp = blockIdx.z;
-    const int view = slice / slices_view, sl = slice - view * slices_view;
-    const int o0 = (tile / tiles_c) * CFG::TO, c0 = (tile % tiles_c) * CFG::TC;
-    const int64_t Mv = M / views;
-    const int64_t m_begin = (int64_t)view * Mv + (int64_t)sl * cols_per_slice;
-    int64_t m_len = Mv - (int64_t)sl * cols_per_slice;
-    if (m_len > cols_per_slice) m_len = cols_per_slice;
-    const int T = (int)(m_len / KC);
-    const unsigned short *Gg = G + (size_t)grp * cout_g * M + m_begin;
-    const unsigned short *Xg = X + (size_t)grp * cin_g * M + m_begin;
+    const WgSlice w = wg_slice<CFG>(G, X, M, cout_g, cin_g, tiles_o, tiles_c, slices_view, cols_per_slice, views, nblocks);
+    const int slice = w.slice, grp = w.grp, view = w.view, o0 = w.o0, c0 = w.c0, T = w.T;
 
     if (PRO) {
         const float2 *src = pro_tab + ((size_t)grp * cin_g) * views;
@@ -306,24 +407,9 @@ __global__ __launch_bounds__(CFG::THREADS) void wgrad_dma_kernel(
             reinterpret_cast<float2 *>(s_tab)[r] = src[(size_t)c * views + view];
         }
     }
-    // DMA: instruction q covers tile rows RPD q .. RPD q + RPD - 1; lane -> row RPD q + lane / SLOTS, and its LDS slot
-    // lane % SLOTS receives the source slot (lane % SLOTS) ^ swz(row).  Rows beyond the matrix re-read its last row
-    // (their outputs are not stored).
     const unsigned short *g_src[CFG::G_DMA], *x_src[CFG::X_DMA];
-#pragma unroll
-    for (int j = 0; j < CFG::G_DMA; ++j) {
-        const int row = CFG::RPD * (CFG::G_DMA * wave + j) + lane / CFG::SLOTS;
-        int o = o0 + row;
-        if (o > cout_g - 1) o = cout_g - 1;
-        g_src[j] = Gg + (size_t)o * M + (((lane & (CFG::SLOTS - 1)) ^ CFG::swz(row)) << 3);
-    }
-#pragma unroll
-    for (int j = 0; j < CFG::X_DMA; ++j) {
-        const int row = CFG::RPD * (CFG::X_DMA * wave + j) + lane / CFG::SLOTS;
-        int c = c0 + row;
-        if (c > cin_g - 1) c = cin_g - 1;
-        x_src[j] = Xg + (size_t)c * M + (((lane & (CFG::SLOTS - 1)) ^ CFG::swz(row)) << 3);
-    }
+    wg_row_src<CFG>(w.Gg, o0, cout_g, M, wave, lane, g_src);
+    wg_row_src<CFG>(w.Xg, c0, cin_g, M, wave, lane, x_src);
     auto issue = [&](int t) {
         const unsigned st = lds0 + (t % NS) * CFG::STAGE;
 #pragma unroll
@@ -332,27 +418,11 @@ __global__ __launch_bounds__(CFG::THREADS) void wgrad_dma_kernel(
         for (int j = 0; j < CFG::X_DMA; ++j)
             gm_dma16(x_src[j] + (size_t)t * KC, st + CFG::G_BYTES + (CFG::X_DMA * wave + j) * 1024);
     };
-    // fragment read offsets: row * ROWB + ((2 ks + half) ^ swz(row)) * 16; the XOR is applied per k-step below
     int goff[RT], gx[RT], xoff[CT], xx[CT];
-#pragma unroll
-    for (int a = 0; a < RT; ++a) {
-        const int row = wo * 32 * RT + a * 32 + l31;
-        goff[a] = row * CFG::ROWB;
-        gx[a] = CFG::swz(row);
-    }
-#pragma unroll
-    for (int b = 0; b < CT; ++b) {
-        const int row = wc * 32 * CT + b * 32 + l31;
-        xoff[b] = CFG::G_BYTES + row * CFG::ROWB;
-        xx[b] = CFG::swz(row);
-    }
+    wg_frag_rows<CFG>(wo * 32 * RT, 0, l31, goff, gx);
+    wg_frag_rows<CFG>(wc * 32 * CT, CFG::G_BYTES, l31, xoff, xx);
     f32x16 acc[RT][CT];
-#pragma unroll
-    for (int a = 0; a < RT; ++a)
-#pragma unroll
-        for (int b = 0; b < CT; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
+    wg_zero(acc);
 
     float2 ssb[CT];
 #pragma unroll
@@ -372,53 +442,32 @@ __global__ __launch_bounds__(CFG::THREADS) void wgrad_dma_kernel(
         __builtin_amdgcn_s_barrier();
         if (t + D < T) issue(t + D);
         unsigned char *const st = smem + (t % NS) * CFG::STAGE;
-#pragma unroll
-        for (int ks = 0; ks < KC / 16; ++ks) {
-            gm_bf16x8 av[RT], bv[CT];
-#pragma unroll
-            for (int a = 0; a < RT; ++a)
-                av[a] = *reinterpret_cast<const gm_bf16x8 *>(st + goff[a] + (((2 * ks + half) ^ gx[a]) << 4));
-#pragma unroll
-            for (int b = 0; b < CT; ++b)
-                bv[b] = *reinterpret_cast<const gm_bf16x8 *>(st + xoff[b] + (((2 * ks + half) ^ xx[b]) << 4));
+        wg_chunk_product<CFG>(st, st, goff, gx, xoff, xx, half, acc, [&](gm_bf16x8 (&bv)[CT]) {
             if (PRO) {
+                const int act = pro_act;        // locals: read through the closure inside the ?: arms below, hipcc
+                const float slope = pro_slope;  // builds branches instead of selects
                 // the fragment is 8 columns of ONE operand row: its (scale, shift) sits in two registers of the lane
                 // (in registers, not as a pass over the staged tile: see conv1x1_gemm_kernel)
 #pragma unroll
                 for (int b = 0; b < CT; ++b) {
-                    gm_u32x4 w = __builtin_bit_cast(gm_u32x4, bv[b]);
+                    gm_u32x4 v = __builtin_bit_cast(gm_u32x4, bv[b]);
 #pragma unroll
                     for (int d = 0; d < 4; ++d) {
-                        float lo = bf16_lo(w[d]), hi = bf16_hi(w[d]);
+                        float lo = bf16_lo(v[d]), hi = bf16_hi(v[d]);
                         lo = __builtin_fmaf(lo, ssb[b].x, ssb[b].y);
                         hi = __builtin_fmaf(hi, ssb[b].x, ssb[b].y);
-                        if (pro_act == 1) { lo = relu_keep_nan(lo); hi = relu_keep_nan(hi); }
-                        else if (pro_act == 2) { lo = lo > 0.f ? lo : lo * pro_slope; hi = hi > 0.f ? hi : hi * pro_slope; }
-                        w[d] = pack_bf16(lo, hi);
+                        if (act == 1) { lo = relu_keep_nan(lo); hi = relu_keep_nan(hi); }
+                        else if (act == 2) { lo = lo > 0.f ? lo : lo * slope; hi = hi > 0.f ? hi : hi * slope; }
+                        v[d] = pack_bf16(lo, hi);
                     }
-                    bv[b] = __builtin_bit_cast(gm_bf16x8, w);
+                    bv[b] = __builtin_bit_cast(gm_bf16x8, v);
                 }
             }
-#pragma unroll
-            for (int a = 0; a < RT; ++a)
-#pragma unroll
-                for (int b = 0; b < CT; ++b)
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[a], bv[b], acc[a][b], 0, 0, 0);
-        }
+        });
     }
     // partial tile -> part[slice][grp][o][c]
-    float *pp = part + ((size_t)slice * gridDim.z + grp) * cout_g * cin_g;
-#pragma unroll
-    for (int a = 0; a < RT; ++a)
-#pragma unroll
-        for (int b = 0; b < CT; ++b) {
-            const int c = c0 + wc * 32 * CT + b * 32 + l31;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int o = o0 + wo * 32 * RT + a * 32 + mfma_row(r, half);
-                if (o < cout_g && c < cin_g) pp[(size_t)o * cin_g + c] = acc[a][b][r];
-            }
-        }
+    wg_store_partial<RT, CT>(part + ((size_t)slice * gridDim.z + grp) * cout_g * cin_g, acc, o0 + wo * 32 * RT,
+                             c0 + wc * 32 * CT, cout_g, cin_g, half, l31);
 }
 
 // ---- G through registers: twice the bytes in flight for the wide tiles -------------------------------------------------
@@ -473,34 +522,12 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::NW == 4 ? 2 : 1) __attribute__((
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wo = wave / CFG::WM, wc = wave % CFG::WM;
     const unsigned lds0 = (unsigned)(uintptr_t)(gm_lptr)smem;
-    const int ntiles = tiles_o * tiles_c;
-    const int logical = xcd_remap(blockIdx.x, nblocks);
-    const int slice = logical / ntiles, tile = logical - slice * ntiles, grp = blockIdx.z;
-    const int view = slice / slices_view, sl = slice - view * slices_view;
-    const int o0 = (tile / tiles_c) * CFG::TO, c0 = (tile % tiles_c) * CFG::TC;
-    const int64_t Mv = M / views;
-    const int64_t m_begin = (int64_t)view * Mv + (int64_t)sl * cols_per_slice;
-    int64_t m_len = Mv - (int64_t)sl * cols_per_slice;
-    if (m_len > cols_per_slice) m_len = cols_per_slice;
-    const int T = (int)(m_len / KC);
-    const unsigned short *Gg = G + (size_t)grp * cout_g * M + m_begin;
-    const unsigned short *Xg = X + (size_t)grp * cin_g * M + m_begin;
+    const WgSlice w = wg_slice<CFG>(G, X, M, cout_g, cin_g, tiles_o, tiles_c, slices_view, cols_per_slice, views, nblocks);
+    const int slice = w.slice, grp = w.grp, o0 = w.o0, c0 = w.c0, T = w.T;
 
     const unsigned short *g_src[GD], *x_src[XD];
-#pragma unroll
-    for (int j = 0; j < GD; ++j) {
-        const int row = CFG::RPD * (GD * wave + j) + lane / CFG::SLOTS;
-        int o = o0 + row;
-        if (o > cout_g - 1) o = cout_g - 1;
-        g_src[j] = Gg + (size_t)o * M + (((lane & (CFG::SLOTS - 1)) ^ CFG::swz(row)) << 3);
-    }
-#pragma unroll
-    for (int j = 0; j < XD; ++j) {
-        const int row = CFG::RPD * (XD * wave + j) + lane / CFG::SLOTS;
-        int c = c0 + row;
-        if (c > cin_g - 1) c = cin_g - 1;
-        x_src[j] = Xg + (size_t)c * M + (((lane & (CFG::SLOTS - 1)) ^ CFG::swz(row)) << 3);
-    }
+    wg_row_src<CFG>(w.Gg, o0, cout_g, M, wave, lane, g_src);
+    wg_row_src<CFG>(w.Xg, c0, cin_g, M, wave, lane, x_src);
     auto issue = [&](auto PAR, int t) {                             // chunk t: X by DMA, G into register set PAR
         const unsigned st = lds0 + (t % NSX) * CFG::X_BYTES;
 #pragma unroll
@@ -515,25 +542,10 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::NW == 4 ? 2 : 1) __attribute__((
         else wg_stash4<0, decltype(PAR)::value>(addr);
     };
     int goff[RT], gx[RT], xoff[CT], xx[CT];
-#pragma unroll
-    for (int a = 0; a < RT; ++a) {
-        const int row = wo * 32 * RT + a * 32 + l31;
-        goff[a] = G0 + row * CFG::ROWB;
-        gx[a] = CFG::swz(row);
-    }
-#pragma unroll
-    for (int b = 0; b < CT; ++b) {
-        const int row = wc * 32 * CT + b * 32 + l31;
-        xoff[b] = row * CFG::ROWB;
-        xx[b] = CFG::swz(row);
-    }
+    wg_frag_rows<CFG>(wo * 32 * RT, G0, l31, goff, gx);
+    wg_frag_rows<CFG>(wc * 32 * CT, 0, l31, xoff, xx);
     f32x16 acc[RT][CT];
-#pragma unroll
-    for (int a = 0; a < RT; ++a)
-#pragma unroll
-        for (int b = 0; b < CT; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
+    wg_zero(acc);
 
     using P0 = std::integral_constant<int, 0>;
     using P1 = std::integral_constant<int, 1>;
@@ -547,21 +559,7 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::NW == 4 ? 2 : 1) __attribute__((
         if (t + 2 < T) issue(PAR, t + 2);                           // X -> stage (t + 2) % 3, G -> the set chunk t left
         const unsigned char *const xs = smem + (t % NSX) * CFG::X_BYTES;
         const unsigned char *const gs = smem + (t & 1) * CFG::G_BYTES;
-#pragma unroll
-        for (int ks = 0; ks < KC / 16; ++ks) {
-            gm_bf16x8 av[RT], bv[CT];
-#pragma unroll
-            for (int a = 0; a < RT; ++a)
-                av[a] = *reinterpret_cast<const gm_bf16x8 *>(gs + goff[a] + (((2 * ks + half) ^ gx[a]) << 4));
-#pragma unroll
-            for (int b = 0; b < CT; ++b)
-                bv[b] = *reinterpret_cast<const gm_bf16x8 *>(xs + xoff[b] + (((2 * ks + half) ^ xx[b]) << 4));
-#pragma unroll
-            for (int a = 0; a < RT; ++a)
-#pragma unroll
-                for (int b = 0; b < CT; ++b)
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[a], bv[b], acc[a][b], 0, 0, 0);
-        }
+        wg_chunk_product<CFG>(gs, xs, goff, gx, xoff, xx, half, acc, [](gm_bf16x8 (&)[CT]) {});
         // chunk t + 1's G (requested one iteration ago) -> the G stage chunk t - 1 used; its X DMA is older, so done too
         if (t + 1 < T) stash(NXT{}, t + 1, t + 2 < T);
     };
@@ -569,35 +567,66 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::NW == 4 ? 2 : 1) __attribute__((
         body(P0{}, t);
         if (t + 1 < T) body(P1{}, t + 1);
     }
-    float *pp = part + ((size_t)slice * gridDim.z + grp) * cout_g * cin_g;
-#pragma unroll
-    for (int a = 0; a < RT; ++a)
-#pragma unroll
-        for (int b = 0; b < CT; ++b) {
-            const int c = c0 + wc * 32 * CT + b * 32 + l31;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int o = o0 + wo * 32 * RT + a * 32 + mfma_row(r, half);
-                if (o < cout_g && c < cin_g) pp[(size_t)o * cin_g + c] = acc[a][b][r];
-            }
-        }
+    wg_store_partial<RT, CT>(part + ((size_t)slice * gridDim.z + grp) * cout_g * cin_g, acc, o0 + wo * 32 * RT,
+                             c0 + wc * 32 * CT, cout_g, cin_g, half, l31);
 }
 
+// The tile configurations; the values are the `tile` numbers of the C ABI (include/grafp_hip.h).
+enum WgTileId : int {
+    WG_AUTO = -1,     // the measured rule of wgrad_dma_plan
+    WG_T = 0, WG_S = 1, WG_L = 2, WG_S32 = 3, WG_M32 = 4, WG_L32 = 5,     // wgrad_dma_kernel<WgT ... WgL32>
+    WG_SG = 6, WG_LG = 7,                                                   // wgrad_gr_kernel: G through registers
+    WG_T128 = 8,
+    WG_REG = 9,       // the register-staged split-K kernel (wgrad_partial_kernel): no LDS-DMA plan
+    WG_S128 = 10,
+    WG_NTILES = 11
+};
+// number -> its WgCfg and its kernel: f(WgKind<CFG, GR>{}); the one place that maps one to the other
+template <typename CFG_, bool GR_ = false> struct WgKind {
+    typedef CFG_ CFG;
+    static constexpr bool GR = GR_;             // wgrad_gr_kernel instead of wgrad_dma_kernel
+};
+template <typename F> static void wg_visit(int cfg, F &&f) {
+    switch (cfg) {
+    case WG_T: return f(WgKind<WgT>{});
+    case WG_S: return f(WgKind<WgS>{});
+    case WG_L: return f(WgKind<WgL>{});
+    case WG_S32: return f(WgKind<WgS32>{});
+    case WG_M32: return f(WgKind<WgM32>{});
+    case WG_SG: return f(WgKind<WgSG, true>{});
+    case WG_LG: return f(WgKind<WgLG, true>{});
+    case WG_T128: return f(WgKind<WgT128>{});
+    case WG_S128: return f(WgKind<WgS128>{});
+    default: return f(WgKind<WgL32>{});         // WG_L32
+    }
+}
+// what a type cannot say: the workgroups to aim for, and whether the configuration has the normalise-on-load form (PRO).
+// ONE round of resident workgroups (512 for the tiles with two workgroups per CU: -11 % over all layers at 256 clip-views,
+// -5 % at 512 against two rounds; one workgroup per CU for the 256 x 256 tiles -- a second round doubles their partial
+// sums (128 slices x 1 MB written and read back against 1.3 GB of operands) and was 5-30 % slower on every shape (LG at
+// 2048 clip-views: 16.4 -> 15.0 ms per step)
+struct WgTileInfo {
+    int64_t target;
+    bool pro;
+};
+static const WgTileInfo wg_tile_info[WG_NTILES] = {
+    /* T */ {512, true},   /* S */ {512, true},    /* L */ {512, true},    /* S32 */ {1024, true}, /* M32 */ {512, true},
+    /* L32 */ {256, true}, /* SG */ {512, false},  /* LG */ {256, false},  /* T128 */ {512, true}, /* REG */ {0, false},
+    /* S128 */ {256, true}};
+
 struct WgDmaPlan {
-    int cfg;                      // 0 = T (64 x 64), 1 = S (128 x 128), 2 = L (256 x 256), 3 = S32, 4 = M32 (256 x 128), 5 = L32,
-                                  // 6 = SG, 7 = LG (G through registers), 8 = T128 (64 x 64, 256-byte row pieces), 10 = S128
+    int cfg;                      // a WgTileId other than WG_AUTO and WG_REG
     int to, tc, tiles_o, tiles_c, slices_view, nslices;
     int64_t cols;
 };
-// tile: -1 = the measured heuristic below; 0 ... 8, 10 = that configuration (T, S, L, S32, M32, L32, SG, LG, T128; S128); 9 = the
-// register-staged split-K kernel of round 1 (wgrad_partial_kernel).  A per-call argument of the *_tile entry points
-// (tests force every configuration on small cases); GRAFP_WGRAD_TILE only in measurement builds (tuning.h).
+// tile: WG_AUTO = the measured heuristic below, otherwise that configuration.  A per-call argument of the *_tile entry
+// points (tests force every configuration on small cases); GRAFP_WGRAD_TILE only in measurement builds (tuning.h).
 static int wg_tile(int tile) {
     if (tile < 0) tile = GRAFP_TUNE_INT("GRAFP_WGRAD_TILE", -1);
-    return (tile >= 0 && tile <= 10) ? tile : -1;
+    return (tile >= 0 && tile < WG_NTILES) ? tile : WG_AUTO;
 }
 static bool wgrad_dma_ok(int cout_g, int cin_g, int64_t M, int views, int tile) {
-    return wg_tile(tile) != 9 && cout_g % 32 == 0 && cin_g % 32 == 0 && views >= 1 && M % views == 0 &&
+    return wg_tile(tile) != WG_REG && cout_g % 32 == 0 && cin_g % 32 == 0 && views >= 1 && M % views == 0 &&
            (M / views) % 64 == 0;
 }
 static WgDmaPlan wgrad_dma_plan(int cout_g, int cin_g, int groups, int64_t M, int views, bool pro, int tile) {
@@ -618,19 +647,19 @@ static WgDmaPlan wgrad_dma_plan(int cout_g, int cin_g, int groups, int64_t M, in
     const double opbytes = (double)(cout_g + cin_g) * groups * (double)M * 2.0;
     const bool big = opbytes > 500e6;
     const int lo = cout_g < cin_g ? cout_g : cin_g, hi = cout_g < cin_g ? cin_g : cout_g;
-    p.cfg = 0;
-    if (lo >= 128 && (outs >= (1 << 19) || (big && groups == 1))) p.cfg = 1;
-    if (big && groups == 1 && cout_g >= 64 && cin_g >= 2 * cout_g) p.cfg = 1;
-    if (pro && cin_g >= 256 && cout_g >= 128) p.cfg = 1;
+    p.cfg = WG_T;
+    if (lo >= 128 && (outs >= (1 << 19) || (big && groups == 1))) p.cfg = WG_S;
+    if (big && groups == 1 && cout_g >= 64 && cin_g >= 2 * cout_g) p.cfg = WG_S;
+    if (pro && cin_g >= 256 && cout_g >= 128) p.cfg = WG_S;
     const bool no_wide = GRAFP_TUNE_INT("GRAFP_WGRAD_NO_WIDE", 0) != 0;        // A/B: the three DMA tiles only
     if (!pro && !no_wide) {
         const bool wide = (lo >= 256 && hi >= 1024 && opbytes >= 200e6) || (lo >= 128 && hi >= 256 && opbytes >= 400e6) ||
                           (lo >= 512 && opbytes >= 250e6);
         if (groups == 1) {
-            if (wide) p.cfg = 7;                                   // LG, one workgroup per CU (see targets below)
-            else if (opbytes >= 750e6 && hi >= 128) p.cfg = 6;     // SG
+            if (wide) p.cfg = WG_LG;                               // one workgroup per CU (see wg_tile_info)
+            else if (opbytes >= 750e6 && hi >= 128) p.cfg = WG_SG;
         } else if (cout_g >= 256 && opbytes >= 400e6) {
-            p.cfg = opbytes >= 750e6 ? 6 : 5;
+            p.cfg = opbytes >= 750e6 ? WG_SG : WG_L32;
         }
     }
     // 256-byte row pieces (T128) for the small outputs of stages 0-1 from 2^19 columns on (tools/gemm_bench.py --wgrad with
@@ -638,48 +667,46 @@ static WgDmaPlan wgrad_dma_plan(int cout_g, int cin_g, int groups, int64_t M, in
     // convolution of stage 0 -8 ... -15 %, that of stage 1 -30 % at 2048 clip-views but +24 % at 1024; equal at 256)
     const bool p256 = GRAFP_TUNE_INT("GRAFP_WGRAD_NO_P256", 0) == 0;          // A/B: without the 256-byte-piece tiles
     if (p256 && M >= (1 << 19)) {
-        if (groups == 1 && (lo <= 64 || outs <= 128 * 128)) p.cfg = 8;
-        if (groups > 1 && (cout_g <= 32 || (cout_g <= 64 && opbytes >= 750e6))) p.cfg = 8;
+        if (groups == 1 && (lo <= 64 || outs <= 128 * 128)) p.cfg = WG_T128;
+        if (groups > 1 && (cout_g <= 32 || (cout_g <= 64 && opbytes >= 750e6))) p.cfg = WG_T128;
     }
     // ... and the 128 x 128 tile on 256-byte pieces (S128, one workgroup per CU) for the next size class, 128 x 256 ...
     // 256 x 256 outputs from 250 MB of operands: -9 ... -28 % at 1024 / 2048 clip-views (stage 1 fc2 / FFN, stage 2 fc1);
     // the grouped convolution of stage 2 only at 2048 clip-views (-20 %; +15 % at 1024).  Larger outputs lose 10-30 %.
     if (p256 && !pro) {
-        if (groups == 1 && outs > 128 * 128 && outs <= 256 * 256 && opbytes >= 250e6) p.cfg = 10;
-        if (groups > 1 && cout_g == 128 && cin_g == 128 && opbytes >= 750e6) p.cfg = 10;
+        if (groups == 1 && outs > 128 * 128 && outs <= 256 * 256 && opbytes >= 250e6) p.cfg = WG_S128;
+        if (groups > 1 && cout_g == 128 && cin_g == 128 && opbytes >= 750e6) p.cfg = WG_S128;
     }
     // ... and at SMALL batches (operands under 200 MB: 128 pairs per GPU, BASELINE config 3's per-rank shape) for the 2^17 ...
     // 2^19-output layers with >= 256 rows on both sides (stage 2 fc2 / FFN, stage 3 fc1), which the first rule leaves on
     // the 64 x 64 tile: tools/wgrad_sweep.sh at 256 clip-views (profiles/r05_wgrad_sweep_256.txt): 65 -> 55 us (FFN),
     // 39 -> 35 (stage 3 fc1), 37 -> 34.5 (stage 2 fc2); the 2^19+ outputs stay where they are (128 x 128: best there).
-    if (p256 && !pro && groups == 1 && lo >= 256 && outs >= (1 << 17) && outs < (1 << 19) && opbytes < 200e6) p.cfg = 10;
+    if (p256 && !pro && groups == 1 && lo >= 256 && outs >= (1 << 17) && outs < (1 << 19) && opbytes < 200e6) p.cfg = WG_S128;
     const int forced = wg_tile(tile);
-    if (forced >= 0 && forced != 9 && !(pro && (forced == 6 || forced == 7))) p.cfg = forced;
-    if (p.cfg == 8 && (M / views) % 128 != 0) p.cfg = 0;          // T128 / S128 need whole 128-column chunks
-    if (p.cfg == 10 && (M / views) % 128 != 0) p.cfg = 1;
-    static const int tile_o[11] = {64, 128, 256, 128, 256, 256, 128, 256, 64, 0, 128}, tile_c[11] = {64, 128, 256, 128, 128, 256, 128, 256, 64, 0, 128};
-    p.to = tile_o[p.cfg];
-    p.tc = tile_c[p.cfg];
+    if (forced != WG_AUTO && forced != WG_REG && !(pro && !wg_tile_info[forced].pro)) p.cfg = forced;
+    const int64_t Mv = M / views;
+    if (p.cfg == WG_T128 && Mv % WgT128::KC != 0) p.cfg = WG_T;   // T128 / S128 need whole 128-column chunks
+    if (p.cfg == WG_S128 && Mv % WgS128::KC != 0) p.cfg = WG_S;
+    // slices are cut in units of 64 columns (what wgrad_dma_ok asks of M / views), or of a chunk where a chunk is longer
+    int64_t unit = 64;
+    wg_visit(p.cfg, [&](auto k) {
+        typedef typename decltype(k)::CFG CFG;
+        p.to = CFG::TO;
+        p.tc = CFG::TC;
+        if (CFG::KC > unit) unit = CFG::KC;
+    });
     p.tiles_o = (cout_g + p.to - 1) / p.to;
     p.tiles_c = (cin_g + p.tc - 1) / p.tc;
     const int64_t tiles = (int64_t)p.tiles_o * p.tiles_c * groups;
-    const int64_t Mv = M / views;
-    // two rounds of resident workgroups (L: one per CU, T/S: two), at least 8 chunks per slice
-    // workgroups to aim for: ONE round of resident workgroups (512 for the tiles with two workgroups per CU: -11 % over
-    // all layers at 256 clip-views, -5 % at 512 against two rounds; one workgroup per CU
-    // for the 256 x 256 tiles -- a second round doubles their partial sums (128 slices x 1 MB written and read back
-    // against 1.3 GB of operands) and was 5-30 % slower on every shape (LG at 2048 clip-views: 16.4 -> 15.0 ms per step)
-    static const int64_t targets[11] = {512, 512, 512, 1024, 512, 256, 512, 256, 512, 0, 256};
-    int64_t target = targets[p.cfg];
-    if ((p.cfg <= 1 || p.cfg == 8) && opbytes >= 750e6) target = 1024;        // the small tiles at 1024 pairs per GPU: two rounds (+2 %)
+    int64_t target = wg_tile_info[p.cfg].target;
+    if ((p.cfg == WG_T || p.cfg == WG_S || p.cfg == WG_T128) && opbytes >= 750e6) target = 1024;   // the small tiles at 1024 pairs per GPU: two rounds (+2 %)
     if (GRAFP_TUNE_INT("GRAFP_WGRAD_TARGET", 0) > 0) target = GRAFP_TUNE_INT("GRAFP_WGRAD_TARGET", 0);
     int64_t sv = (target + tiles * views - 1) / (tiles * views);
-    const int64_t max_sv = (Mv / 64 + 7) / 8;
+    const int64_t max_sv = (Mv / 64 + 7) / 8;                      // at least 8 x 64 columns per slice
     if (sv > max_sv) sv = max_sv;
     if (sv < 1) sv = 1;
     int64_t cols = (Mv + sv - 1) / sv;
-    const int64_t kc = p.cfg == 8 || p.cfg == 10 ? 128 : 64;
-    cols = (cols + kc - 1) / kc * kc;
+    cols = (cols + unit - 1) / unit * unit;
     p.cols = cols;
     p.slices_view = (int)((Mv + cols - 1) / cols);
     p.nslices = p.slices_view * views;
@@ -711,21 +738,16 @@ struct WgradPlan {
     int tw, tiles_o, tiles_c, S;
     int64_t cols;
 };
-static WgradPlan wgrad_plan(int cout_g, int cin_g, int groups, int64_t M) {
+// split-K of the register-staged kernels: `target` workgroups over tw x tw output tiles, at most 256 splits of whole
+// chunks, at least 4 chunks each
+static WgradPlan wg_split_k(int tw, int cout_g, int cin_g, int groups, int64_t M, int64_t target) {
     WgradPlan p;
-    // measured crossover.  (Two chunks in flight per workgroup -- a second register set -- costs the 128-tile its
-    // second workgroup per CU (320 registers) and was 30-40 % slower on the stage 2-3 shapes, 3-8 % on the 64-tile.)
-    // (A 256 x 128 tile with 64-column chunks -- 85 flop per operand byte instead of 64 -- was
-    // tried and is 5-30 % slower on every FFN shape: the halved chunk doubles the barriers per MFMA.)
-    p.tw = (cout_g >= 128 && cin_g >= 128 && (int64_t)cout_g * cin_g >= 65536) ? 128 : 64;
-    p.tiles_o = (cout_g + p.tw - 1) / p.tw;
-    p.tiles_c = (cin_g + p.tw - 1) / p.tw;
+    p.tw = tw;
+    p.tiles_o = (cout_g + tw - 1) / tw;
+    p.tiles_c = (cin_g + tw - 1) / tw;
     const int64_t tiles = (int64_t)p.tiles_o * p.tiles_c * groups;
-    // measured on MI355X: ~1024 workgroups for the 64-tiles (small outputs: parallelism must come from split-K),
-    // ~512 for the 128-tiles (large outputs: more splits only add partial-sum traffic)
-    const int64_t target = p.tw == 64 ? 1024 : 512;
     int64_t S = (target + tiles - 1) / tiles;
-    const int64_t max_s = (M + 4 * WG_KC - 1) / (4 * WG_KC);  // >= 4 chunks per slice
+    const int64_t max_s = (M + 4 * WG_KC - 1) / (4 * WG_KC);
     if (S > max_s) S = max_s;
     if (S > 256) S = 256;
     if (S < 1) S = 1;
@@ -734,6 +756,46 @@ static WgradPlan wgrad_plan(int cout_g, int cin_g, int groups, int64_t M) {
     p.cols = cols;
     p.S = (int)((M + cols - 1) / cols);
     return p;
+}
+static WgradPlan wgrad_plan(int cout_g, int cin_g, int groups, int64_t M) {
+    // measured crossover.  (Two chunks in flight per workgroup -- a second register set -- costs the 128-tile its
+    // second workgroup per CU (320 registers) and was 30-40 % slower on the stage 2-3 shapes, 3-8 % on the 64-tile.)
+    // (A 256 x 128 tile with 64-column chunks -- 85 flop per operand byte instead of 64 -- was
+    // tried and is 5-30 % slower on every FFN shape: the halved chunk doubles the barriers per MFMA.)
+    const int tw = (cout_g >= 128 && cin_g >= 128 && (int64_t)cout_g * cin_g >= 65536) ? 128 : 64;
+    // measured on MI355X: ~1024 workgroups for the 64-tiles (small outputs: parallelism must come from split-K),
+    // ~512 for the 128-tiles (large outputs: more splits only add partial-sum traffic)
+    return wg_split_k(tw, cout_g, cin_g, groups, M, tw == 64 ? 1024 : 512);
+}
+// the f32 kernel: 64 x 64 tiles only
+static WgradPlan wgrad3_plan(int cout_g, int cin_g, int groups, int64_t M) {
+    return wg_split_k(64, cout_g, cin_g, groups, M, 1024);
+}
+
+// the argument and workspace checks of the bf16 and f32 entry points
+static int wgrad_check(const char *who, const void *grad_out, const void *x, int Cout, int Cin, int groups, int64_t M,
+                       const void *ws, size_t ws_bytes, size_t need) {
+    GRAFP_REQUIRE(Cout > 0 && Cin > 0 && groups > 0 && M > 0 && Cout % groups == 0 && Cin % groups == 0,
+                  "%s: bad shape Cout=%d Cin=%d groups=%d M=%lld", who, Cout, Cin, groups, (long long)M);
+    GRAFP_REQUIRE((((uintptr_t)grad_out | (uintptr_t)x) & 15) == 0, "%s: operands must be 16-byte aligned", who);
+    if (!ws || ws_bytes < need) {
+        set_error("%s: workspace %zu bytes < required %zu", who, ws_bytes, need);
+        return GRAFP_ERR_WORKSPACE;
+    }
+    return GRAFP_OK;
+}
+// a launch with `lds` bytes of dynamic LDS: beyond the 48 KB every kernel may have, the function attribute has to allow it
+template <typename... P, typename... A>
+static void wg_launch(void (*kernel)(P...), dim3 grid, int threads, size_t lds, hipStream_t s, A... args) {
+    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, s, static_cast<P>(args)...);
+}
+// dweight[i] = the sum of the S partial planes of n outputs in ws
+static int wgrad_reduce(const void *ws, int S, int64_t n, float *dweight, hipStream_t s) {
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, s, (const float *)ws, S, n,
+                       dweight);
+    GRAFP_CHECK_LAUNCH("wgrad_reduce_kernel");
+    return GRAFP_OK;
 }
 
 }  // namespace grafp
@@ -783,97 +845,48 @@ static int wgrad_tile_impl(const void *grad_out, const void *x, int Cout, int Ci
                            size_t ws_bytes, int *n_slices, grafp_stream_t stream) {
     using namespace grafp;
     GRAFP_REQUIRE(grad_out && x && (dweight || n_slices), "conv1x1_wgrad: null pointer");
-    GRAFP_REQUIRE(Cout > 0 && Cin > 0 && groups > 0 && M > 0 && Cout % groups == 0 && Cin % groups == 0,
-                  "conv1x1_wgrad: bad shape Cout=%d Cin=%d groups=%d M=%lld", Cout, Cin, groups, (long long)M);
-    GRAFP_REQUIRE((((uintptr_t)grad_out | (uintptr_t)x) & 15) == 0, "conv1x1_wgrad: operands must be 16-byte aligned");
     GRAFP_REQUIRE(pro_act >= 0 && pro_act <= 2, "conv1x1_wgrad: bad activation %d", pro_act);
-    const size_t need = grafp_conv1x1_wgrad_tile_workspace(Cout, Cin, groups, M, views, tile);
-    if (!ws || ws_bytes < need) {
-        set_error("conv1x1_wgrad: workspace %zu bytes < required %zu", ws_bytes, need);
-        return GRAFP_ERR_WORKSPACE;
-    }
+    const int err = wgrad_check("conv1x1_wgrad", grad_out, x, Cout, Cin, groups, M, ws, ws_bytes,
+                                grafp_conv1x1_wgrad_tile_workspace(Cout, Cin, groups, M, views, tile));
+    if (err != GRAFP_OK) return err;
     const int cout_g = Cout / groups, cin_g = Cin / groups;
+    const unsigned short *G = (const unsigned short *)grad_out, *X = (const unsigned short *)x;
     hipStream_t s = (hipStream_t)stream;
-    const int64_t n = (int64_t)Cout * cin_g;
+    int S;
     if (wgrad_dma_ok(cout_g, cin_g, M, views, tile)) {
         const WgDmaPlan p = wgrad_dma_plan(cout_g, cin_g, groups, M, views, pro_tab != nullptr, tile);
         const int nblocks = p.nslices * p.tiles_o * p.tiles_c;
         const dim3 grid(nblocks, 1, groups);
-#define WG_LAUNCH(CFG, PRO)                                                                                              \
-    do {                                                                                                                 \
-        const size_t lds = (size_t)CFG::NS * CFG::STAGE + ((PRO) ? (size_t)CFG::TC * 8 : 0);                             \
-        (void)hipFuncSetAttribute((const void *)wgrad_dma_kernel<CFG, PRO>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                  (int)lds);                                                                             \
-        hipLaunchKernelGGL((wgrad_dma_kernel<CFG, PRO>), grid, dim3(CFG::THREADS), lds, s,                               \
-                           (const unsigned short *)grad_out, (const unsigned short *)x, M, cout_g, cin_g, p.tiles_o,     \
-                           p.tiles_c, p.slices_view, p.cols, views, (const float2 *)pro_tab, pro_act, pro_slope,         \
-                           (float *)ws, nblocks);                                                                        \
-    } while (0)
-#define WG_LAUNCH_GR(CFG)                                                                                                \
-    do {                                                                                                                 \
-        const size_t lds = (size_t)3 * CFG::X_BYTES + 2 * CFG::G_BYTES;                                                  \
-        (void)hipFuncSetAttribute((const void *)wgrad_gr_kernel<CFG>, hipFuncAttributeMaxDynamicSharedMemorySize,        \
-                                  (int)lds);                                                                             \
-        hipLaunchKernelGGL((wgrad_gr_kernel<CFG>), grid, dim3(CFG::THREADS), lds, s, (const unsigned short *)grad_out,   \
-                           (const unsigned short *)x, M, cout_g, cin_g, p.tiles_o, p.tiles_c, p.slices_view, p.cols,     \
-                           views, (float *)ws, nblocks);                                                                 \
-    } while (0)
-        if (pro_tab) {
-            switch (p.cfg) {
-            case 0: WG_LAUNCH(WgT, true); break;
-            case 8: WG_LAUNCH(WgT128, true); break;
-            case 10: WG_LAUNCH(WgS128, true); break;
-            case 1: WG_LAUNCH(WgS, true); break;
-            case 2: WG_LAUNCH(WgL, true); break;
-            case 3: WG_LAUNCH(WgS32, true); break;
-            case 4: WG_LAUNCH(WgM32, true); break;
-            default: WG_LAUNCH(WgL32, true); break;
-            }
-        } else {
-            switch (p.cfg) {
-            case 6: WG_LAUNCH_GR(WgSG); break;
-            case 7: WG_LAUNCH_GR(WgLG); break;
-            case 0: WG_LAUNCH(WgT, false); break;
-            case 8: WG_LAUNCH(WgT128, false); break;
-            case 10: WG_LAUNCH(WgS128, false); break;
-            case 1: WG_LAUNCH(WgS, false); break;
-            case 2: WG_LAUNCH(WgL, false); break;
-            case 3: WG_LAUNCH(WgS32, false); break;
-            case 4: WG_LAUNCH(WgM32, false); break;
-            default: WG_LAUNCH(WgL32, false); break;
-            }
-        }
-#undef WG_LAUNCH
-#undef WG_LAUNCH_GR
+        wg_visit(p.cfg, [&](auto k) {
+            typedef typename decltype(k)::CFG CFG;
+            const size_t ring = (size_t)CFG::NS * CFG::STAGE;
+            if constexpr (decltype(k)::GR)                      // never with a pro_tab: wg_tile_info[].pro
+                wg_launch(wgrad_gr_kernel<CFG>, grid, CFG::THREADS, (size_t)3 * CFG::X_BYTES + 2 * CFG::G_BYTES, s, G, X, M,
+                          cout_g, cin_g, p.tiles_o, p.tiles_c, p.slices_view, p.cols, views, (float *)ws, nblocks);
+            else if (pro_tab)
+                wg_launch(wgrad_dma_kernel<CFG, true>, grid, CFG::THREADS, ring + (size_t)CFG::TC * 8, s, G, X, M, cout_g,
+                          cin_g, p.tiles_o, p.tiles_c, p.slices_view, p.cols, views, (const float2 *)pro_tab, pro_act,
+                          pro_slope, (float *)ws, nblocks);
+            else
+                wg_launch(wgrad_dma_kernel<CFG, false>, grid, CFG::THREADS, ring, s, G, X, M, cout_g, cin_g, p.tiles_o,
+                          p.tiles_c, p.slices_view, p.cols, views, (const float2 *)pro_tab, pro_act, pro_slope, (float *)ws,
+                          nblocks);
+        });
         GRAFP_CHECK_LAUNCH("wgrad_dma_kernel");
-        if (n_slices) *n_slices = p.nslices;
-        if (!dweight) return GRAFP_OK;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, s, (const float *)ws,
-                           p.nslices, n, dweight);
-        GRAFP_CHECK_LAUNCH("wgrad_reduce_kernel");
-        return GRAFP_OK;
-    }
-    GRAFP_REQUIRE(!pro_tab, "conv1x1_wgrad: the normalise-on-load form needs rows per group %% 32 == 0 and columns per "
-                            "view %% 64 == 0");
-    const WgradPlan p = wgrad_plan(cout_g, cin_g, groups, M);
-    GRAFP_REQUIRE((int64_t)p.S * p.tiles_o * p.tiles_c < (1ll << 31), "conv1x1_wgrad: output too large");
-    const dim3 grid(p.S * p.tiles_o * p.tiles_c, 1, groups);
-    const size_t lds = (size_t)2 * p.tw * WG_LS;
-    if (p.tw == 64) {
-        hipLaunchKernelGGL(wgrad_partial_kernel<64>, grid, dim3(256), lds, s, (const unsigned short *)grad_out,
-                           (const unsigned short *)x, M, cout_g, cin_g, p.tiles_o, p.tiles_c, p.cols, (float *)ws);
+        S = p.nslices;
     } else {
-        (void)hipFuncSetAttribute((const void *)wgrad_partial_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(wgrad_partial_kernel<128>, grid, dim3(256), lds, s, (const unsigned short *)grad_out,
-                           (const unsigned short *)x, M, cout_g, cin_g, p.tiles_o, p.tiles_c, p.cols, (float *)ws);
+        GRAFP_REQUIRE(!pro_tab, "conv1x1_wgrad: the normalise-on-load form needs rows per group %% 32 == 0 and columns "
+                                "per view %% 64 == 0");
+        const WgradPlan p = wgrad_plan(cout_g, cin_g, groups, M);
+        GRAFP_REQUIRE((int64_t)p.S * p.tiles_o * p.tiles_c < (1ll << 31), "conv1x1_wgrad: output too large");
+        const dim3 grid(p.S * p.tiles_o * p.tiles_c, 1, groups);
+        wg_launch(p.tw == 64 ? wgrad_partial_kernel<64> : wgrad_partial_kernel<128>, grid, 256, (size_t)2 * p.tw * WG_LS, s,
+                  G, X, M, cout_g, cin_g, p.tiles_o, p.tiles_c, p.cols, (float *)ws);
+        GRAFP_CHECK_LAUNCH("wgrad_partial_kernel");
+        S = p.S;
     }
-    GRAFP_CHECK_LAUNCH("wgrad_partial_kernel");
-    if (n_slices) *n_slices = p.S;
-    if (!dweight) return GRAFP_OK;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, s, (const float *)ws, p.S, n,
-                       dweight);
-    GRAFP_CHECK_LAUNCH("wgrad_reduce_kernel");
-    return GRAFP_OK;
+    if (n_slices) *n_slices = S;
+    return dweight ? wgrad_reduce(ws, S, (int64_t)Cout * cin_g, dweight, s) : GRAFP_OK;
 }
 
 extern "C" int grafp_conv1x1_wgrad_tile_bf16(const void *grad_out, const void *x, int Cout, int Cin, int groups,
@@ -1002,28 +1015,9 @@ extern "C" int grafp_conv1x1_wgrad_bf16(const void *grad_out, const void *x, int
                                          stream);
 }
 
-static grafp::WgradPlan wgrad3_plan(int cout_g, int cin_g, int groups, int64_t M) {
-    using namespace grafp;
-    WgradPlan p;
-    p.tw = 64;
-    p.tiles_o = (cout_g + 63) / 64;
-    p.tiles_c = (cin_g + 63) / 64;
-    const int64_t tiles = (int64_t)p.tiles_o * p.tiles_c * groups;
-    int64_t S = (1024 + tiles - 1) / tiles;
-    const int64_t max_s = (M + 4 * WG_KC - 1) / (4 * WG_KC);
-    if (S > max_s) S = max_s;
-    if (S > 256) S = 256;
-    if (S < 1) S = 1;
-    int64_t cols = (M + S - 1) / S;
-    cols = (cols + WG_KC - 1) / WG_KC * WG_KC;
-    p.cols = cols;
-    p.S = (int)((M + cols - 1) / cols);
-    return p;
-}
-
 extern "C" size_t grafp_conv1x1_wgrad_f32_workspace(int Cout, int Cin, int groups, int64_t M) {
     if (Cout <= 0 || Cin <= 0 || groups <= 0 || M <= 0 || Cout % groups || Cin % groups) return 0;
-    const grafp::WgradPlan p = wgrad3_plan(Cout / groups, Cin / groups, groups, M);
+    const grafp::WgradPlan p = grafp::wgrad3_plan(Cout / groups, Cin / groups, groups, M);
     return (size_t)p.S * Cout * (Cin / groups) * sizeof(float);
 }
 
@@ -1031,27 +1025,16 @@ extern "C" int grafp_conv1x1_wgrad_f32(const float *grad_out, const float *x, in
                                        float *dweight, void *ws, size_t ws_bytes, grafp_stream_t stream) {
     using namespace grafp;
     GRAFP_REQUIRE(grad_out && x && dweight, "conv1x1_wgrad_f32: null pointer");
-    GRAFP_REQUIRE(Cout > 0 && Cin > 0 && groups > 0 && M > 0 && Cout % groups == 0 && Cin % groups == 0,
-                  "conv1x1_wgrad_f32: bad shape Cout=%d Cin=%d groups=%d M=%lld", Cout, Cin, groups, (long long)M);
-    GRAFP_REQUIRE((((uintptr_t)grad_out | (uintptr_t)x) & 15) == 0, "conv1x1_wgrad_f32: operands must be 16-byte aligned");
-    const size_t need = grafp_conv1x1_wgrad_f32_workspace(Cout, Cin, groups, M);
-    if (!ws || ws_bytes < need) {
-        set_error("conv1x1_wgrad_f32: workspace %zu bytes < required %zu", ws_bytes, need);
-        return GRAFP_ERR_WORKSPACE;
-    }
+    const int err = wgrad_check("conv1x1_wgrad_f32", grad_out, x, Cout, Cin, groups, M, ws, ws_bytes,
+                                grafp_conv1x1_wgrad_f32_workspace(Cout, Cin, groups, M));
+    if (err != GRAFP_OK) return err;
     const int cout_g = Cout / groups, cin_g = Cin / groups;
     const WgradPlan p = wgrad3_plan(cout_g, cin_g, groups, M);
     GRAFP_REQUIRE((int64_t)p.S * p.tiles_o * p.tiles_c < (1ll << 31), "conv1x1_wgrad_f32: output too large");
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(p.S * p.tiles_o * p.tiles_c, 1, groups);
-    const size_t lds = (size_t)4 * 64 * WG_LS;
-    (void)hipFuncSetAttribute((const void *)wgrad3_partial_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(wgrad3_partial_kernel, grid, dim3(256), lds, s, grad_out, x, M, cout_g, cin_g, p.tiles_o, p.tiles_c,
-                       p.cols, (float *)ws);
+    wg_launch(wgrad3_partial_kernel, grid, 256, (size_t)4 * 64 * WG_LS, s, grad_out, x, M, cout_g, cin_g, p.tiles_o,
+              p.tiles_c, p.cols, (float *)ws);
     GRAFP_CHECK_LAUNCH("wgrad3_partial_kernel");
-    const int64_t n = (int64_t)Cout * cin_g;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, s, (const float *)ws, p.S, n,
-                       dweight);
-    GRAFP_CHECK_LAUNCH("wgrad_reduce_kernel");
-    return GRAFP_OK;
+    return wgrad_reduce(ws, p.S, (int64_t)Cout * cin_g, dweight, s);
 }

@@ -395,7 +395,10 @@ int grafp_conv1x1_wgrad_pro_bf16(const void *grad_out, const void *x, int Cout, 
 /* The same with the tile configuration as an explicit per-call argument (tile = -1: the measured rule, what the
  * entries above use; 0 ... 7: T 64x64, S 128x128, L 256x256, S32, M32 256x128, L32 (64-byte row pieces), SG, LG (G
  * operand through registers); 8, 10: T128, S128 = T and S on 256-byte row pieces, for operand rows that lie megabytes
- * apart; 9: the register-staged split-K kernel).  The rule picks the wide configurations only at
+ * apart; 9: the register-staged split-K kernel; the numbers are enum WgTileId of csrc/wgrad.hip, any other value = -1).
+ * A forced tile is taken where it can run: SG and LG have no pro_tab form (with one, the rule's choice runs), T128 and
+ * S128 need M / views % 128 == 0 (otherwise T and S run), and shapes outside the LDS-DMA form (rows per group % 32, M /
+ * views % 64) take the register-staged kernel whatever `tile` says.  The rule picks the wide configurations only at
  * sizes a test cannot afford for every shape, so the tests force each one on small cases through this entry. */
 size_t grafp_conv1x1_wgrad_tile_workspace(int Cout, int Cin, int groups, int64_t M, int views, int tile);
 int grafp_conv1x1_wgrad_tile_bf16(const void *grad_out, const void *x, int Cout, int Cin, int groups, int64_t M,

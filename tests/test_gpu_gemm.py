@@ -284,6 +284,73 @@ def test_wgrad_every_tile_configuration(tile, cout, cin, groups, M, views):
     assert torch.equal(dw, again)
 
 
+# ragged rows; groups and views; one chunk per slice (T128 and S128 fall back to T and S)
+WG_PRO_SHAPES = [(96, 160, 1, 1280, 1), (512, 1024, 4, 1024, 2), (256, 512, 1, 64, 1)]
+_WG_PRO_CASES = {}
+
+
+def _wg_pro_case(shape):
+    """(g, x, ReLU pro_tab, float64 product of the bf16-rounded transformed operand) of a shape, made once."""
+    if shape not in _WG_PRO_CASES:
+        cout, cin, groups, M, views = shape
+        g, x = _rand((cout, M), 21), _rand((cin, M), 22, 1.5, 0.5)
+        gen = torch.Generator().manual_seed(23)
+        tab = torch.stack((torch.rand((cin, views), generator=gen) + 0.5, torch.randn((cin, views), generator=gen)), -1).to(DEV)
+        t = tab.reshape(cin, views, 1, 2)
+        xe = torch.relu(torch.addcmul(t[..., 1], x.float().reshape(cin, views, -1), t[..., 0])).reshape(cin, M)
+        gd, xd = g.double(), xe.to(torch.bfloat16).double()
+        og, cg = cout // groups, cin // groups
+        want = torch.cat([gd[i * og:(i + 1) * og] @ xd[i * cg:(i + 1) * cg].t() for i in range(groups)], dim=0)
+        _WG_PRO_CASES[shape] = (g, x, tab, want)
+    return _WG_PRO_CASES[shape]
+
+
+# T, S, L, S32, M32, L32, T128, S128: every configuration that has the normalise-on-load form
+@pytest.mark.parametrize("tile", [0, 1, 2, 3, 4, 5, 8, 10])
+@pytest.mark.parametrize("shape", WG_PRO_SHAPES)
+def test_wgrad_every_dma_tile_with_normalise_on_load(tile, shape):
+    """The rule picks three tiles with a pro_tab; the other five are reachable through `tile` only.  Reference and bar
+    of test_wgrad_dma."""
+    from grafp_amd import ops
+    cout, cin, groups, M, views = shape
+    g, x, tab, want = _wg_pro_case(shape)
+    dw = ops.conv1x1_wgrad(g, x, cout, cin, groups, M, views, tab, ops.ACT_RELU, tile=tile)
+    assert dw.shape == (cout, cin // groups) and dw.dtype == torch.float32
+    assert float((dw.double() - want).abs().max()) <= 4e-3 * float(want.abs().max())
+    assert torch.equal(dw, ops.conv1x1_wgrad(g, x, cout, cin, groups, M, views, tab, ops.ACT_RELU, tile=tile))
+
+
+@pytest.mark.parametrize("tile", [6, 7])
+@pytest.mark.parametrize("shape", WG_PRO_SHAPES)
+def test_wgrad_forced_register_staged_g_is_ignored_with_normalise_on_load(tile, shape):
+    """SG and LG have no normalise-on-load form: with a pro_tab the rule's own choice runs, bit for bit."""
+    from grafp_amd import ops
+    cout, cin, groups, M, views = shape
+    g, x, tab, _ = _wg_pro_case(shape)
+    dw = ops.conv1x1_wgrad(g, x, cout, cin, groups, M, views, tab, ops.ACT_RELU, tile=tile)
+    assert torch.equal(dw, ops.conv1x1_wgrad(g, x, cout, cin, groups, M, views, tab, ops.ACT_RELU, tile=-1))
+
+
+@pytest.mark.parametrize("cout,cin,groups,M,views", [(64, 64, 1, 8192, 2), (1024, 256, 1, 2048, 2), (40, 24, 1, 777, 1)])
+def test_wgrad_partials_report_the_slices_of_the_plan_query(cout, cin, groups, M, views):
+    """n_slices of grafp_conv1x1_wgrad_partials_bf16 = info[3] of grafp_conv1x1_wgrad_plan, on LDS-DMA shapes and on one
+    the register-staged kernel takes (info[0] == -1)."""
+    import ctypes
+    from grafp_amd import ops
+    from grafp_amd._lib import lib
+    info = (ctypes.c_int * 8)()
+    assert lib.grafp_conv1x1_wgrad_plan(cout, cin, groups, M, views, info) == 0
+    assert (info[0] == -1) == (cout == 40)
+    g, x = _rand((cout, M), 31), _rand((cin, M), 32, 1.5, 0.5)
+    nbytes = lib.grafp_conv1x1_wgrad_tile_workspace(cout, cin, groups, M, views, -1)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=DEV)
+    S = ctypes.c_int(0)
+    ops.check(lib.grafp_conv1x1_wgrad_partials_bf16(ops._p(g), ops._p(x), cout, cin, groups, M, views, None, 0, 0.0, -1,
+                                                    ops._p(ws), nbytes, ctypes.byref(S), ops._stream()), "conv1x1_wgrad_partials")
+    torch.cuda.synchronize()
+    assert S.value == info[3] and S.value * cout * (cin // groups) * 4 <= nbytes
+
+
 def test_gemm_cat_equals_product_plus_shortcut():
     """conv1x1_gemm_cat(W | I, dY, dZ) = W dY + dZ with ONE rounding (the data gradient of a residual block's first
     layer with the shortcut's gradient as extra operand rows), for an S-tile and an L-tile shape."""

@@ -25,11 +25,9 @@ rep('''    for (int t = 0; t < T; ++t) {
         if (t + D < T) issue(t + D);
         TICK(2);
         unsigned char *const st = smem + (t % NS) * CFG::STAGE;''')
-rep('''                    acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[a], bv[b], acc[a][b], 0, 0, 0);
-        }
+rep('''        });
     }
-    // partial tile -> part[slice][grp][o][c]''', '''                    acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[a], bv[b], acc[a][b], 0, 0, 0);
-        }
+    // partial tile -> part[slice][grp][o][c]''', '''        });
         { float sink = acc[0][0][0]; asm volatile("" :: "v"(sink)); }
         TICK(3);
     }
