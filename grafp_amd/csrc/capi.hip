@@ -99,6 +99,34 @@ extern "C" int grafp_identify_f32(const float *index_rows, int64_t n, const int6
                                   (hipStream_t)stream);
 }
 
+// Identification against a library that keeps every row_stride-th row of each track (identify_thin.hip): argument checks
+// here and there (the stride and the 2^32 bound of the alignment key sit next to the kernel).
+namespace grafp {
+int identify_thin_launch(const float *rows, int64_t n, const int64_t *first, int T, int row_stride,
+                         const float *q_rows, const int64_t *ids, int k, const int64_t *item_row, const int *item_len,
+                         int n_items, int max_len, int top, int min_overlap, int32_t *out_track, int32_t *out_offset,
+                         float *out_score, int32_t *out_votes, hipStream_t stream);
+}  // namespace grafp
+
+extern "C" int grafp_identify_thin_f32(const float *index_rows, int64_t n, const int64_t *track_first_row,
+                                       int n_tracks, int row_stride, const float *q_rows, int64_t n_qrows,
+                                       const int64_t *topk_ids, int k, const int64_t *item_row, const int *item_len,
+                                       int n_items, int max_len, int top, int min_overlap, int32_t *out_track,
+                                       int32_t *out_offset, float *out_score, int32_t *out_votes,
+                                       grafp_stream_t stream) {
+    GRAFP_REQUIRE(index_rows && track_first_row && q_rows && topk_ids && item_row && item_len && out_track &&
+                  out_offset && out_score && out_votes, "identify_thin: null pointer");
+    GRAFP_REQUIRE(n >= 1 && n < 0x7fffff00ll && n_tracks >= 1 && n_qrows >= 1 && n_items >= 0,
+                  "identify_thin: bad sizes n=%lld n_tracks=%d n_qrows=%lld n_items=%d", (long long)n, n_tracks,
+                  (long long)n_qrows, n_items);
+    GRAFP_REQUIRE(top >= 1 && top <= 64, "identify_thin: top=%d not in [1, 64]", top);
+    GRAFP_REQUIRE((((uintptr_t)index_rows | (uintptr_t)q_rows) & 15) == 0,
+                  "identify_thin: rows must be 16-byte aligned");
+    return grafp::identify_thin_launch(index_rows, n, track_first_row, n_tracks, row_stride, q_rows, topk_ids, k,
+                                       item_row, item_len, n_items, max_len, top, min_overlap, out_track, out_offset,
+                                       out_score, out_votes, (hipStream_t)stream);
+}
+
 // Identification against a library held as IVF-PQ codes (identify_pq.hip): argument checks here, the kernels there.
 namespace grafp {
 int identify_pq_launch(const int32_t *list_id, const unsigned char *codes, int64_t n, const float *centroids, int nlist,

@@ -35,7 +35,8 @@
 //      smaller a); it becomes ~ord(score) << 32 | t, every other entry empty;
 //   5. bitonic sort of those; the first `top` entries are the result.
 // The five phases are identify_item of identify_core.h, shared with identify_pq.hip (the same operation on a library held
-// as IVF-PQ codes); this file supplies the span rows of phase 3 (RowSpan of span_rows.h: the resident f32 rows) and the launch.
+// as IVF-PQ codes) and identify_thin.hip (a library that keeps every D-th row of a track); this file supplies the row grid
+// (DenseGrid: one row per segment), the span rows of phase 3 (RowSpan of span_rows.h: the resident f32 rows) and the launch.
 // Built WITHOUT packed-f32 instructions (Makefile NOPK, as corpus.hip): its sums are plain fmaf chains, and the packed
 // operand-select form is the hazard of DESIGN.md section 12.7b.
 #include "identify_core.h"
@@ -53,7 +54,7 @@ __global__ __launch_bounds__(ID_THREADS) void identify_kernel(
     const int *__restrict__ item_len, int max_len, int Pmax, int top, int min_overlap, int32_t *__restrict__ out_track,
     int32_t *__restrict__ out_offset, float *__restrict__ out_score, int32_t *__restrict__ out_votes) {
     const RowSpan<kQLds ? ID_UNROLL_QLDS : ID_UNROLL_QGLOBAL> span{reinterpret_cast<const float4 *>(rows)};
-    identify_item<kQLds>(span, n, first, T, q_rows, ids, k, item_row, item_len, max_len, Pmax, top, min_overlap,
+    identify_item<kQLds>(DenseGrid{}, span, n, first, T, q_rows, ids, k, item_row, item_len, max_len, Pmax, top, min_overlap,
                          out_track, out_offset, out_score, out_votes);
 }
 

@@ -1,13 +1,23 @@
-// identify_core.h -- the one body of the track-aware identification kernels: identify.hip (library rows held as f32) and
-// identify_pq.hip (library rows held as IVF-PQ codes, decoded while they are scored).  What the kernels compute, the LDS
-// layout and the five phases are stated at the top of identify.hip; the arithmetic order of a score at the top of
-// seqmatch.h.  The two kernels differ in ONE thing: where y[t] of the span sum (phase 3) comes from.  That is the Span
-// parameter of identify_item:
+// identify_core.h -- the one body of the track-aware identification kernels: identify.hip (library rows held as f32),
+// identify_pq.hip (library rows held as IVF-PQ codes, decoded while they are scored) and identify_thin.hip (f32 rows,
+// every D-th row of each track kept).  What the kernels compute, the LDS layout and the five phases are stated at the
+// top of identify.hip; the arithmetic order of a score at the top of seqmatch.h.  The dense kernels differ in ONE thing:
+// where y[t] of the span sum (phase 3) comes from.  That is the Span parameter of identify_item:
 //     float span(const float4 *x, int64_t row, int l, int m)
 // x: lane l's float4 of the first query row of the span, row: the library row that pairs with it, m: pairs (the same in
 // every lane of the half-wave; <= 0: no row is read, the butterfly still runs).  It returns the un-divided span score in
 // span_sum's order.  Rows [row, row + m) lie inside [0, n).
-// Compiles with and without the packed-f32 instructions; both users are built without (Makefile NOPK).
+// The library rows sit on a ROW GRID, the Grid parameter of identify_item: which fine position (dense segment, counted
+// over the whole library) a row holds, and so which query rows of an alignment pair with which library rows.
+//     int64_t fine(int64_t r)    the fine position of library row r (and of a track's first row)
+//     int64_t row(int64_t p)     the library row at fine position p = a + s of a pair (p >= 0, on the grid)
+//     int need(int need_q)       the pairs a candidate needs, from the query rows the caller asks for
+//     void pairs(a, f0, f1, ql, lo, o)   the pairs of alignment a with the track of rows [f0, f1): query rows
+//                                lo, lo + step, ... (o of them; o < 1: none), library rows row(a + lo), + 1, ...
+//   DenseGrid   one row per fine position (identify.hip, identify_pq.hip): a = r - s, pairs are consecutive rows
+//   ThinGrid    every D-th position of each track is kept (identify_thin.hip): a = r * D - s, the query steps D rows
+//               per pair and the library one (the Span functor carries the query step)
+// Compiles with and without the packed-f32 instructions; every user is built without (Makefile NOPK).
 #pragma once
 #include <limits.h>
 #include <math.h>
@@ -22,6 +32,7 @@ constexpr int ID_MAX_LEN = 256;
 constexpr int ID_MAX_K = 32;
 constexpr int ID_MAX_KEYS = 8192;
 constexpr int ID_SHIFT = ID_MAX_LEN - 1;                 // a + ID_SHIFT >= 0 for every hit
+constexpr int ID_MAX_STRIDE = 32;                        // ThinGrid: the largest row stride
 constexpr size_t ID_LDS = 160 * 1024 - 256;      // dynamic LDS budget (the static s_ncand sits next to it)
 
 // The launch plan of one identify kernel: slots per item, dynamic LDS bytes, and whether the query rows sit in LDS.
@@ -40,13 +51,45 @@ inline IdentifyPlan identify_plan(int max_len, int k) {
     return p;
 }
 
+struct DenseGrid {
+    __device__ __forceinline__ int64_t fine(int64_t r) const { return r; }
+    __device__ __forceinline__ int64_t row(int64_t p) const { return p; }
+    __device__ __forceinline__ int need(int need_q) const { return need_q; }
+    __device__ __forceinline__ void pairs(int64_t a, int64_t f0, int64_t f1, int ql, int &lo, int &o) const {
+        lo = (int)(f0 - a > 0 ? f0 - a : 0);
+        const int hi = (int)(f1 - a < ql ? f1 - a : ql);
+        o = hi - lo;
+    }
+};
+
+// Every D-th fine position of each track, D in [1, ID_MAX_STRIDE]; the host keeps n * D + ID_SHIFT below 2^32, so
+// fine(r) - s + ID_SHIFT fits the upper half of a key.  Query row s pairs with a row of the track iff (a + s) mod D == 0
+// (mathematical mod: a may be negative) and f0 <= (a + s) / D < f1; everything is compared in 64 bits before it is
+// narrowed, so that a table the caller vouched for wrongly yields no pairs instead of a query row outside the item.
+struct ThinGrid {
+    int D;
+    __device__ __forceinline__ int64_t fine(int64_t r) const { return r * D; }
+    __device__ __forceinline__ int64_t row(int64_t p) const { return p / D; }
+    __device__ __forceinline__ int need(int need_q) const { return need_q / D > 1 ? need_q / D : 1; }
+    __device__ __forceinline__ void pairs(int64_t a, int64_t f0, int64_t f1, int ql, int &lo, int &o) const {
+        const int64_t s0 = ((-a) % D + D) % D;             // the first s >= 0 on the grid
+        const int64_t sf = f0 * D - a;                     // the s of the track's first row (on the grid too)
+        const int64_t lo64 = sf > s0 ? sf : s0;
+        const int64_t end = (f1 - 1) * D - a + 1;          // one past the s of the track's last row
+        const int64_t hi64 = end < ql ? end : ql;
+        const bool any = hi64 > lo64;                      // then 0 <= lo64 < hi64 <= ql
+        lo = any ? (int)lo64 : 0;
+        o = any ? (int)((hi64 - lo64 + D - 1) / D) : 0;
+    }
+};
+
 // One item by one workgroup of ID_THREADS threads (blockIdx.x = the item).
-template <bool kQLds, typename Span>
+template <bool kQLds, typename Grid, typename Span>
 __device__ __forceinline__ void identify_item(
-    const Span &span, int64_t n, const int64_t *__restrict__ first, int T, const float *__restrict__ q_rows,
-    const int64_t *__restrict__ ids, int k, const int64_t *__restrict__ item_row, const int *__restrict__ item_len,
-    int max_len, int Pmax, int top, int min_overlap, int32_t *__restrict__ out_track, int32_t *__restrict__ out_offset,
-    float *__restrict__ out_score, int32_t *__restrict__ out_votes) {
+    const Grid &grid, const Span &span, int64_t n, const int64_t *__restrict__ first, int T,
+    const float *__restrict__ q_rows, const int64_t *__restrict__ ids, int k, const int64_t *__restrict__ item_row,
+    const int *__restrict__ item_len, int max_len, int Pmax, int top, int min_overlap, int32_t *__restrict__ out_track,
+    int32_t *__restrict__ out_offset, float *__restrict__ out_score, int32_t *__restrict__ out_votes) {
     extern __shared__ __attribute__((aligned(16))) unsigned char id_smem[];
     __shared__ int s_ncand;
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(id_smem);
@@ -74,7 +117,7 @@ __device__ __forceinline__ void identify_item(
         if (e < total) {
             const int s = e / k;
             const int64_t r = ids[(r0 + s) * k + (e - s * k)];
-            if (r >= 0 && r < n) key = ((unsigned long long)(r - s + ID_SHIFT) << 32) | (unsigned int)s;
+            if (r >= 0 && r < n) key = ((unsigned long long)(grid.fine(r) - s + ID_SHIFT) << 32) | (unsigned int)s;
         }
         keys[e] = key;
     }
@@ -97,7 +140,7 @@ __device__ __forceinline__ void identify_item(
         for (int f = e; f < P; ++f) {
             const unsigned long long key = keys[f];
             if ((key >> 32) != hi) break;                   // the next run, or the empty tail
-            const int64_t r = a + (int64_t)(unsigned int)key;
+            const int64_t r = grid.row(a + (int64_t)(unsigned int)key);
             if (r >= end) {                                 // first hit, or the run crossed into a later track
                 if (nv) {
                     keys[start] = hi << 32;
@@ -124,7 +167,7 @@ __device__ __forceinline__ void identify_item(
 
     // 3. scores: one candidate per half-wave at a time
     const int hw = tid >> 5, l = tid & 31;
-    const int need_q = min_overlap > 0 ? min_overlap : ql;
+    const int need = grid.need(min_overlap > 0 ? min_overlap : ql);
     const float4 *q4 = kQLds ? reinterpret_cast<const float4 *>(sq) : reinterpret_cast<const float4 *>(q_rows + r0 * SEQ_D);
     for (int c = hw; c < ncand; c += ID_THREADS / 32) {
         const int e = idx[c];
@@ -134,11 +177,10 @@ __device__ __forceinline__ void identify_item(
         f0 = f0 < 0 ? 0 : f0;                               // (a valid table needs neither clamp)
         f1 = f1 > n ? n : f1;
         const int64_t L = f1 - f0;
-        const int lo = (int)(f0 - a > 0 ? f0 - a : 0);
-        const int hi = (int)(f1 - a < ql ? f1 - a : ql);
-        const int o = hi - lo;
-        const bool ok = o >= 1 && o >= (need_q < L ? need_q : L);
-        const float acc = span(q4 + lo * (SEQ_D / 4) + l, a + lo, l, ok ? o : 0);   // (not ok: no row is read)
+        int lo, o;
+        grid.pairs(a, f0, f1, ql, lo, o);
+        const bool ok = o >= 1 && o >= (need < L ? need : L);
+        const float acc = span(q4 + lo * (SEQ_D / 4) + l, grid.row(a + lo), l, ok ? o : 0);   // (not ok: nothing read)
         const float score = acc / (float)o;
         // every lane of the half-wave has read keys[e] and aux[e] before the shuffles above
         if (l == 0) {
@@ -173,7 +215,7 @@ __device__ __forceinline__ void identify_item(
             const int t = (int)(key & 0xffffffffull);
             const int slot = idx[tid];
             out_track[o] = t;
-            out_offset[o] = (int32_t)((int64_t)aux[slot] - ID_SHIFT - first[t]);
+            out_offset[o] = (int32_t)((int64_t)aux[slot] - ID_SHIFT - grid.fine(first[t]));
             out_score[o] = ord_f32(~(unsigned int)(key >> 32));
             out_votes[o] = (int32_t)votes[slot];
         } else {

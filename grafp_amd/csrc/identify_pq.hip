@@ -36,7 +36,7 @@ __global__ __launch_bounds__(ID_THREADS) void identify_pq_kernel(
     int min_overlap, int32_t *__restrict__ out_track, int32_t *__restrict__ out_offset, float *__restrict__ out_score,
     int32_t *__restrict__ out_votes) {
     const PqSpan<kM, kQLds ? IDPQ_UNROLL_QLDS : IDPQ_UNROLL_QGLOBAL> span{list_id, codes, centroids, codebooks, nlist};
-    identify_item<kQLds>(span, n, first, T, q_rows, ids, k, item_row, item_len, max_len, Pmax, top, min_overlap,
+    identify_item<kQLds>(DenseGrid{}, span, n, first, T, q_rows, ids, k, item_row, item_len, max_len, Pmax, top, min_overlap,
                          out_track, out_offset, out_score, out_votes);
 }
 

@@ -76,12 +76,13 @@ __device__ __forceinline__ void block_sort(unsigned long long *keys, unsigned sh
 // row reads, so the count decides how many are in flight per wave (and the registers they take).  Every kernel uses
 // the count its own loop had before the loops were merged here: 4 in seq_rerank_kernel, identify_kernel<true> and
 // self_match_kernel, 1 in identify_kernel<false> (both rows of a pair come from global memory there).
+// x_step: float4s between the x rows of two consecutive pairs (a query against a thinned library steps D rows).
 template <int kUnroll>
-__device__ __forceinline__ float span_sum(const float4 *x, const float4 *y, int m) {
+__device__ __forceinline__ float span_sum(const float4 *x, const float4 *y, int m, int x_step = SEQ_D / 4) {
     float acc = 0.0f;
 #pragma unroll kUnroll
     for (int t = 0; t < m; ++t) {
-        const float4 q = x[(int64_t)t * (SEQ_D / 4)], r = y[(int64_t)t * (SEQ_D / 4)];
+        const float4 q = x[(int64_t)t * x_step], r = y[(int64_t)t * (SEQ_D / 4)];
         acc = __builtin_fmaf(q.x, r.x, acc);
         acc = __builtin_fmaf(q.y, r.y, acc);
         acc = __builtin_fmaf(q.z, r.z, acc);

@@ -5,6 +5,7 @@
 // same in every lane of the half-wave; <= 0: no row is read, the butterfly still runs).  Returns the un-divided span
 // score in span_sum's order (seqmatch.h).
 //   RowSpan<kUnroll>      the library's resident (n, 128) f32 rows     identify.hip, selfmatch.hip, crossmatch.hip
+//   StridedRowSpan<kUnroll>   the same rows, the x rows of consecutive pairs x_step float4s apart    identify_thin.hip
 //   PqSpan<kM, kUnroll>   rows decoded from IVF-PQ codes while scored  identify_pq.hip, crossmatch.hip
 // Library row r of the compact form is
 //   dec[r][j] = centroids[list_id[r]][j] + codebooks[m][codes[r][m]][c],  m = j / dsub, c = j % dsub, dsub = 128 / M
@@ -22,6 +23,15 @@ struct RowSpan {
     const float4 *rw4;
     __device__ __forceinline__ float operator()(const float4 *x, int64_t row, int l, int m) const {
         return span_sum<kUnroll>(x, rw4 + row * (SEQ_D / 4) + l, m);
+    }
+};
+
+template <int kUnroll>
+struct StridedRowSpan {
+    const float4 *rw4;
+    int x_step;                                  // float4s between the x rows of two consecutive pairs
+    __device__ __forceinline__ float operator()(const float4 *x, int64_t row, int l, int m) const {
+        return span_sum<kUnroll>(x, rw4 + row * (SEQ_D / 4) + l, m, x_step);
     }
 };
 

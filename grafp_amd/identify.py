@@ -2,6 +2,7 @@
 
   python -m grafp_amd.identify build --config CFG --ckp MODEL.pth --source DIR|JSON|FILES... --out LIBDIR [--precision]
                                        [--index flat|ivfpq --nlist 64 --pq-m 64 --nprobe 20 --train-rows 65536]
+                                       [--row-stride D]
   python -m grafp_amd.identify query --ckp MODEL.pth --library LIBDIR FILES... [--top 5] [--window S --hop S]
   python -m grafp_amd.identify dedup --ckp MODEL.pth --library LIBDIR [--min-overlap 3] [--coverage 0.9] [--json OUT]
   python -m grafp_amd.identify match --ckp MODEL.pth --library LIBDIR FILES... [--min-overlap 3] [--min-votes 4]
@@ -13,7 +14,9 @@ the flat one); `query` prints one JSON
 object per query file -- or, with --window, one per timeline span of each file; `dedup` prints one JSON object per pair
 of tracks that share audio, then one per group of duplicates (--json also writes both to a file); `match` takes whole
 recordings that are not in the library and prints one JSON object per (recording, library track) that share audio, with
-the span and the coverage (either form of a library; --json also writes them to a file)."""
+the span and the coverage (either form of a library; --json also writes them to a file).  build --row-stride D keeps
+every D-th fingerprint row of each track (a flat library of 772 / D bytes per original row; `query` works on it
+unchanged, `dedup` and `match` need every row)."""
 import argparse
 import json
 import sys
@@ -47,6 +50,8 @@ def main(argv=None):
     b.add_argument("--pq-m", type=int, default=64, choices=(16, 32, 64, 128), help="ivfpq: code bytes per row")
     b.add_argument("--nprobe", type=int, default=20, help="ivfpq: lists a query row probes")
     b.add_argument("--train-rows", type=int, default=65536, help="ivfpq: rows the quantiser is trained on")
+    b.add_argument("--row-stride", type=int, default=1,
+                   help="flat: keep every D-th fingerprint row of each track (1..32); queries stay dense")
     q = sub.add_parser("query", help="identify recordings against a library")
     q.add_argument("--config", default=DEFAULT_CONFIG, help="model configuration (the library keeps its own "
                                                             "segmentation settings)")
@@ -94,12 +99,16 @@ def main(argv=None):
         corpus = DeviceAudioCorpus(cfg, source, device)
         lib = FingerprintLibrary.build(model, corpus, cfg, precision=args.precision, max_segments=args.max_segments,
                                        index=args.index, nlist=args.nlist, pq_m=args.pq_m, nprobe=args.nprobe,
-                                       train_rows=args.train_rows)
+                                       train_rows=args.train_rows, row_stride=args.row_stride)
         lib.save(args.out)
-        print(json.dumps({"library": args.out, "index": args.index, "tracks": lib.n_tracks, "rows": lib.n_rows,
-                          "bytes": lib.nbytes}))
+        stride = {"row_stride": lib.row_stride} if lib.row_stride != 1 else {}
+        print(json.dumps({"library": args.out, "index": args.index, **stride, "tracks": lib.n_tracks,
+                          "rows": lib.n_rows, "bytes": lib.nbytes}))
         return 0
     lib = FingerprintLibrary.load(args.library, model, device, force=args.force)
+    if args.cmd in ("dedup", "match") and lib.row_stride != 1:
+        sys.exit(f"{args.library}: {args.cmd} needs every row of a track: this library keeps every {lib.row_stride}th "
+                 f"(row_stride={lib.row_stride})")
     if args.cmd == "dedup":
         from .library import DUPLICATE_MIN_SCORE
         if lib.is_compact:

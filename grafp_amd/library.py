@@ -14,6 +14,13 @@ and identifies with ops.identify_pq (csrc/identify_pq.hip), which scores the dec
 build(index="ivfpq"), compress() and load() make one; identify, identify_windows, timeline and match work on either
 form; rows() and self_matches() need the flat one.
 
+A flat library may keep only every D-th row of each track (build(row_stride=D), thin(D)): the catalogue is stored at
+a coarse hop and the query stays dense, so some of its rows land exactly on kept rows whatever the true alignment is
+and the offset is still resolved to one segment hop.  772 / D bytes per original row with exact f32 scores, a search
+over D times fewer rows and a build that runs the model on D times fewer segments; identify, identify_windows and
+timeline work on it through ops.identify_thin (csrc/identify_thin.hip).  compress(), self_matches() and match() need
+every row (row_stride 1).
+
 match() takes whole recordings of any length that are NOT in the library and says which tracks they share audio with,
 where and how much (spans, coverage, votes: what self_matches says about the library's own tracks) -- the question an
 ingest gate asks before add().  It runs on ops.cross_match (f32 rows) or ops.cross_match_pq (codes), the kernels of
@@ -31,6 +38,7 @@ from . import ops
 SETTINGS = ("fs", "n_fft", "win_len", "hop_len", "n_mels", "n_frames", "overlap")
 FORMAT = 1                   # the files of a flat library
 FORMAT_COMPACT = 2           # the files of a compact library
+FORMAT_THIN = 3              # the files of a flat library that keeps every row_stride-th row ("row_stride" in library.json)
 # duplicate_groups' default score bar: a match at least this strong is shared audio.  Chosen from
 # tests/test_gpu_selfmatch.py's trained-model case (the briefly trained model of tests/_retrieval_case.py, bf16 library,
 # measured on MI355X): an exact copy scores 1.000, the pieces of a medley at 20 dB SNR 0.985 and 0.956, the strongest of
@@ -101,9 +109,12 @@ def _as_waveforms(tracks):
 class FingerprintLibrary:
     """Fingerprints of whole tracks, resident on one device, with the table that says which rows are which track."""
 
-    def __init__(self, model, settings, rows, first, names=None, precision="bf16", device=None):
+    def __init__(self, model, settings, rows, first, names=None, precision="bf16", device=None, row_stride=1):
         if precision not in ("bf16", "f32"):
             raise ValueError(f"precision must be 'bf16' or 'f32', not {precision!r}")
+        if not 1 <= int(row_stride) <= ops.IDENTIFY_MAX_STRIDE:
+            raise ValueError(f"row_stride={row_stride} not in [1, {ops.IDENTIFY_MAX_STRIDE}]")
+        self._row_stride = int(row_stride)
         self.model = model
         self.device = torch.device(device) if device is not None else next(model.parameters()).device
         self.settings = {k: settings[k] for k in SETTINGS}
@@ -157,6 +168,16 @@ class FingerprintLibrary:
     @property
     def is_compact(self):
         return self._pq is not None
+
+    @property
+    def row_stride(self):
+        """D: row j of a track is the track's segment j * D (a dense library: 1).  Offsets stay in segments."""
+        return self._row_stride
+
+    def _need_dense(self, what):
+        if self._row_stride != 1:
+            raise NotImplementedError(f"FingerprintLibrary.{what} needs every row of a track: this library keeps every "
+                                      f"{self._row_stride}th (row_stride={self._row_stride})")
 
     def quantiser(self):
         """{"centroids", "codebooks"} of a compact library (device tensors)."""
@@ -310,7 +331,7 @@ class FingerprintLibrary:
         track's row count to `counts`."""
         pend, n_pend = [], 0
         for w in waves:
-            segs = self.segments(w)
+            segs = self.segments(w)[::self._row_stride]              # (a thinned library embeds the kept segments only)
             counts.append(segs.shape[0])
             pend.append(segs)
             n_pend += segs.shape[0]
@@ -369,16 +390,21 @@ class FingerprintLibrary:
 
     @classmethod
     def build(cls, model, tracks, cfg, names=None, precision="bf16", max_segments=4096, index="flat", nlist=64, pq_m=64,
-              nprobe=20, train_rows=65536, quantiser=None, seed=1234):
+              nprobe=20, train_rows=65536, quantiser=None, seed=1234, row_stride=1):
         """Fingerprint whole tracks (a DeviceAudioCorpus, its .tracks(), or 1-D tensors / arrays at cfg['fs']) into a
         new library.  Tracks shorter than one segment get no rows: they stay in the table and never match.
         index="ivfpq": a compact library.  Its quantiser (nlist lists, pq_m sub-quantisers) is trained on the rows of
         the first model calls, as soon as they hold train_rows rows (on all rows if there are fewer); every later
         model call is encoded and its f32 rows dropped, so the f32 rows of the catalogue never exist at once.
-        quantiser={"centroids", "codebooks"}: nothing is trained."""
+        quantiser={"centroids", "codebooks"}: nothing is trained.
+        row_stride=D (flat only): every D-th segment of each track is fingerprinted and kept, selected before the model
+        call -- 1 / D of the model work and of the rows; a track of S segments gets ceil(S / D) rows."""
         if index not in ("flat", "ivfpq"):
             raise ValueError(f"index must be 'flat' or 'ivfpq', not {index!r}")
-        lib = cls(model, cfg, None, None, precision=precision)
+        if index == "ivfpq" and int(row_stride) != 1:
+            raise NotImplementedError(f"build(index='ivfpq') needs every row of a track: row_stride={row_stride} codes "
+                                      "are not implemented")
+        lib = cls(model, cfg, None, None, precision=precision, row_stride=row_stride)
         if index == "flat":
             return lib.add(tracks, names=names, max_segments=max_segments)
         if quantiser is not None:
@@ -391,7 +417,8 @@ class FingerprintLibrary:
         return lib
 
     def add(self, tracks, names=None, max_segments=4096):
-        """Append tracks (as for build) to the library; a compact library encodes them with its own quantiser."""
+        """Append tracks (as for build) to the library; a compact library encodes them with its own quantiser, a
+        thinned one keeps every row_stride-th segment of each."""
         waves, own = _as_waveforms(tracks)
         names = names if names is not None else own
         if self.is_compact:
@@ -406,6 +433,7 @@ class FingerprintLibrary:
         """A new compact library with this flat library's tracks: an IVF-PQ quantiser trained on a seeded sample of
         train_rows of its own rows (all if there are fewer), every row encoded with it.  This library is left as it is."""
         self._need_flat("compress()")
+        self._need_dense("compress()")
         if self.n_rows == 0:
             raise ValueError("compress: the library has no rows to train a quantiser on")
         out = FingerprintLibrary(self.model, self.settings, None, None, precision=self.precision, device=self.device)
@@ -415,13 +443,29 @@ class FingerprintLibrary:
         out._append_codes(torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]), self.first, self.names)
         return out
 
+    def thin(self, row_stride):
+        """A new flat library that keeps rows first[t] + 0, D, 2D, ... of every track of this dense one (D =
+        row_stride): what build(row_stride=D) fingerprints.  This library is left as it is."""
+        self._need_flat("thin()")
+        self._need_dense("thin()")
+        D = int(row_stride)
+        if not 1 <= D <= ops.IDENTIFY_MAX_STRIDE:
+            raise ValueError(f"row_stride={row_stride} not in [1, {ops.IDENTIFY_MAX_STRIDE}]")
+        keep = [np.arange(self.first[t], self.first[t + 1], D) for t in range(self.n_tracks)]
+        keep = np.concatenate(keep).astype(np.int64) if keep else np.zeros(0, np.int64)
+        first = np.concatenate([[0], np.cumsum(-(-np.diff(self.first) // D))]).astype(np.int64)
+        rows = self.rows()[torch.from_numpy(keep).to(self.device)]
+        return FingerprintLibrary(self.model, self.settings, rows, first, list(self.names), precision=self.precision,
+                                  device=self.device, row_stride=D)
+
     # ---- files -----------------------------------------------------------------------------------------------
     def save(self, out_dir):
         """library.mm + library_shape.npy (the reference's memmap format: eval.load_memmap_data reads them),
         library_tracks.npy (the track table, int64) and library.json (names, settings, precision, model digest).
         A compact library writes library_codes.npy ((n, M) uint8, row order), library_lists.npy ((n) int32),
         library_pq.npz (centroids, codebooks), library_tracks.npy and library.json ("format": 2 and "index": {"type":
-        "ivfpq", "nlist", "M", "nprobe"}) -- and no library.mm."""
+        "ivfpq", "nlist", "M", "nprobe"}) -- and no library.mm.  A thinned library writes the flat library's four files
+        with "format": 3 and "row_stride": D in library.json."""
         from .fpdb import _write_memmap
         os.makedirs(out_dir, exist_ok=True)
         meta = {"format": FORMAT, "names": self.names, "settings": self.settings, "precision": self.precision,
@@ -436,6 +480,8 @@ class FingerprintLibrary:
             meta["index"] = {"type": "ivfpq", "nlist": int(cent.shape[0]), "M": int(books.shape[0]),
                              "nprobe": self._pq["nprobe"]}
         else:
+            if self._row_stride != 1:
+                meta["format"], meta["row_stride"] = FORMAT_THIN, self._row_stride
             _write_memmap(os.path.join(out_dir, "library"), self.rows().cpu().numpy().reshape(-1, 128))
         np.save(os.path.join(out_dir, "library_tracks.npy"), self.first.astype(np.int64))
         with open(os.path.join(out_dir, "library.json"), "w") as f:
@@ -447,8 +493,13 @@ class FingerprintLibrary:
         made with, unless force=True."""
         with open(os.path.join(lib_dir, "library.json")) as f:
             meta = json.load(f)
-        if meta.get("format") not in (FORMAT, FORMAT_COMPACT):
-            raise ValueError(f"{lib_dir}: library format {meta.get('format')} is neither {FORMAT} nor {FORMAT_COMPACT}")
+        if meta.get("format") not in (FORMAT, FORMAT_COMPACT, FORMAT_THIN):
+            raise ValueError(f"{lib_dir}: library format {meta.get('format')} is none of {FORMAT}, {FORMAT_COMPACT} and "
+                             f"{FORMAT_THIN}")
+        stride = meta.get("row_stride", 1 if meta["format"] != FORMAT_THIN else None)
+        if meta["format"] == FORMAT_THIN and not (isinstance(stride, int) and 1 <= stride <= ops.IDENTIFY_MAX_STRIDE):
+            raise ValueError(f"{lib_dir}: library format {FORMAT_THIN} needs a row_stride in [1, "
+                             f"{ops.IDENTIFY_MAX_STRIDE}], not {stride!r}")
         if not force and model_digest(model) != meta["model_digest"]:
             raise ValueError(f"{lib_dir}: the library was fingerprinted with another model (state_dict digest "
                              f"{meta['model_digest'][:12]}...); pass force=True to use it anyway")
@@ -473,7 +524,9 @@ class FingerprintLibrary:
             np.zeros((0, 128), np.float32)
         if device is not None:
             model = model.to(device)
-        return cls(model, meta["settings"], torch.from_numpy(rows), first, meta["names"], meta["precision"], device)
+        stride = stride if meta["format"] == FORMAT_THIN else 1
+        return cls(model, meta["settings"], torch.from_numpy(rows), first, meta["names"], meta["precision"], device,
+                   row_stride=stride)
 
     @classmethod
     def from_memmap(cls, db_dir, fname, track_rows, model, cfg, names=None, precision="f32"):
@@ -522,7 +575,8 @@ class FingerprintLibrary:
         return waves
 
     def _search_and_identify(self, segs, item_row, item_len, top, k_probe, min_overlap):
-        """One batched embed + search of all segments, one ops.identify launch for all items -> per-item lists."""
+        """One batched embed + search of all segments, one ops.identify launch for all items -> per-item lists.  (The
+        queries' segments are all embedded, whatever the library's row_stride: the query side stays dense.)"""
         n_items = len(item_row)
         if n_items == 0 or segs.shape[0] == 0 or self.n_rows == 0 or int(np.max(item_len, initial=0)) == 0:
             return [[] for _ in range(n_items)]
@@ -540,6 +594,9 @@ class FingerprintLibrary:
         if self.is_compact:
             tr, off, sc, vo = ops.identify_pq(*self.codes(), self._pq["centroids"], self._pq["codebooks"], *tail,
                                               top=top, min_overlap=min_overlap, max_len=max_len)
+        elif self._row_stride != 1:
+            tr, off, sc, vo = ops.identify_thin(self.rows(), *tail, self._row_stride, top=top, min_overlap=min_overlap,
+                                                max_len=max_len)
         else:
             tr, off, sc, vo = ops.identify(self.rows(), *tail, top=top, min_overlap=min_overlap, max_len=max_len)
         tr, off, sc, vo = (t.cpu().numpy() for t in (tr, off, sc, vo))
@@ -626,6 +683,7 @@ class FingerprintLibrary:
         int64 tensor whatever `tracks` is (256 MB at 1 M rows and k_probe = 32); each batch also takes its own exactly
         sized workspace (ops.self_match_workspace_bytes: about 124 KB per 303-row source at k_probe = 32, min_votes 4)."""
         self._need_flat("self_matches()")
+        self._need_dense("self_matches()")
         T, n = self.n_tracks, self.n_rows
         src = list(range(T)) if tracks is None else sorted({int(t) for t in tracks})
         if src and not 0 <= min(src) <= max(src) < T:
@@ -696,6 +754,7 @@ class FingerprintLibrary:
         drops a row's hits on its own track; nothing is dropped here).
         One recording is one workgroup, as a track is in self_matches: an hour-long recording is not split into pieces,
         its hits are sorted through the launch's workspace (ops.self_match_workspace_bytes of the batch's row counts)."""
+        self._need_dense("match()")
         single = isinstance(recordings, (str, np.ndarray, torch.Tensor)) and (
             isinstance(recordings, str) or torch.as_tensor(recordings).dim() == 1)
         waves = self._load_queries(recordings, fs)

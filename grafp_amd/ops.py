@@ -1581,7 +1581,63 @@ def identify(index_rows, track_first_row, q_rows, topk_ids, item_row, item_len, 
     return outs
 
 
-IDENTIFY_PQ_M = (16, 32, 64, 128)                                        # identify_pq.hip's sub-quantiser counts
+IDENTIFY_MAX_STRIDE = 32                                                 # identify_thin.hip's largest row stride
+
+
+def identify_thin(index_rows, track_first_row, q_rows, topk_ids, item_row, item_len, row_stride, top=5,
+                  min_overlap=None, max_len=None):
+    """ops.identify against a library that keeps every row_stride-th row of each track (grafp_identify_thin_f32):
+    row j of track t is that track's dense segment j * D (D = row_stride in [1, 32]), a track of S dense segments has
+    ceil(S / D) rows, and track_first_row counts kept rows.  The query rows stay dense.
+    A hit (s, r) names the track t holding r and the fine alignment a = r * D - s; the pairs of (t, a) are the query
+    rows s with (a + s) mod D == 0 whose row (a + s) / D lies inside t, o of them; the candidate is eligible iff
+    o >= 1 and o >= min(max(1, need // D), rows of t) with need = min_overlap (None: the item's length), and scores the
+    mean dot product over its pairs in ops.identify's arithmetic order.  offset = a - first[t] * D: dense segments from
+    the track's start, as ops.identify reports it.  Everything else (arguments, ranking, padding, max_len) as for
+    ops.identify, which this equals bit for bit at row_stride = 1."""
+    n_items, k, top, D = int(item_row.shape[0]), int(topk_ids.shape[1]), int(top), int(row_stride)
+    # argument checks first (host values only): they hold on any device
+    if not 1 <= D <= IDENTIFY_MAX_STRIDE:
+        raise ValueError(f"identify_thin: row_stride={D} not in [1, {IDENTIFY_MAX_STRIDE}]")
+    if int(index_rows.shape[0]) * D + IDENTIFY_MAX_LEN - 1 >= 1 << 32:
+        raise ValueError(f"identify_thin: {int(index_rows.shape[0])} rows at row_stride={D} reach past the 2^32 fine "
+                         "positions an alignment key holds")
+    if not 1 <= top <= 64:
+        raise ValueError(f"identify_thin: top={top} not in [1, 64]")
+    if not 1 <= k <= IDENTIFY_MAX_K:
+        raise ValueError(f"identify_thin: k={k} hits per segment exceeds {IDENTIFY_MAX_K}")
+    if min_overlap is not None and int(min_overlap) < 1:
+        raise ValueError("identify_thin: min_overlap must be at least 1 segment")
+    if max_len is None and n_items:
+        max_len = max(1, int(item_len.max().item()))
+        check_track_table(track_first_row, index_rows.shape[0])
+        _check_items_inside("identify_thin", item_row, item_len, q_rows.shape[0])
+    if max_len is not None and (int(max_len) > IDENTIFY_MAX_LEN or int(max_len) * k > IDENTIFY_MAX_KEYS):
+        raise ValueError(f"identify_thin: items of {int(max_len)} segments with k={k} exceed {IDENTIFY_MAX_LEN} "
+                         f"segments or {IDENTIFY_MAX_KEYS} hits per item")
+    _require_gpu(index_rows, q_rows, topk_ids, item_row, item_len)
+    index_rows, q_rows = _f32c(index_rows), _f32c(q_rows)
+    dev = index_rows.device
+    first = torch.as_tensor(track_first_row).detach().to(device=dev, dtype=torch.int64).contiguous()
+    topk_ids = topk_ids.to(torch.int64).contiguous()
+    item_row = item_row.to(torch.int64).contiguous()
+    item_len = item_len.to(torch.int32).contiguous()
+    outs = (torch.empty((n_items, top), dtype=torch.int32, device=dev),
+            torch.empty((n_items, top), dtype=torch.int32, device=dev),
+            torch.empty((n_items, top), dtype=torch.float32, device=dev),
+            torch.empty((n_items, top), dtype=torch.int32, device=dev))
+    if n_items == 0:
+        return outs
+    max_len = int(max_len)
+    with _timed("identify_thin", (n_items, max_len, k, D)):
+        check(lib.grafp_identify_thin_f32(_p(index_rows), index_rows.shape[0], _p(first), first.numel() - 1, D,
+                                          _p(q_rows), q_rows.shape[0], _p(topk_ids), k, _p(item_row), _p(item_len),
+                                          n_items, max_len, top, 0 if min_overlap is None else int(min_overlap),
+                                          *(_p(o) for o in outs), _stream()), "identify_thin")
+    return outs
+
+
+IDENTIFY_PQ_M = (16, 32, 64, 128)                                       # identify_pq.hip's sub-quantiser counts
 
 
 def identify_pq(list_id, codes, centroids, codebooks, track_first_row, q_rows, topk_ids, item_row, item_len, top=5,

@@ -581,6 +581,25 @@ int grafp_identify_f32(const float *index_rows, int64_t n, const int64_t *track_
                        const int *item_len, int n_items, int max_len, int top, int min_overlap, int32_t *out_track,
                        int32_t *out_offset, float *out_score, int32_t *out_votes, grafp_stream_t stream);
 
+/* ---- identification against a library that keeps every D-th row (grafp_amd/library.py; identify_thin.hip) ---------
+ * grafp_identify_thin_f32 -- grafp_identify_f32 against a library that keeps every row_stride-th fingerprint row of
+ *   each track, D = row_stride in [1, 32]: row j of track t is that track's dense segment j * D, a track of S dense
+ *   segments has ceil(S / D) rows, track_first_row counts kept rows, and the fine position of library row r is r * D.
+ *   The query rows stay dense.
+ *   A hit (s, r) names the track t holding r and the fine alignment a = r * D - s; a candidate is a unique (t, a), its
+ *   votes the hits that map to it.  Its pairs are the s < ql with (a + s) mod D == 0 (mathematical mod) and
+ *   (a + s) / D inside t, o of them; it is eligible iff o >= 1 and o >= min(max(1, need / D), rows of t), need =
+ *   min_overlap (<= 0: ql), and scores (sum over the pairs, s ascending, <q[s], row[(a + s) / D]>) / o in the arithmetic
+ *   order of grafp_identify_f32.  No row outside t is read.  The per-track best, the order, the four outputs and their
+ *   padding as there; out_offset = a - track_first_row[t] * D, in dense segments from the track's start.  With
+ *   row_stride 1 every output is bit for bit grafp_identify_f32's.
+ *   Limits: those of grafp_identify_f32, and n * row_stride + 255 < 2^32. */
+int grafp_identify_thin_f32(const float *index_rows, int64_t n, const int64_t *track_first_row, int n_tracks,
+                            int row_stride, const float *q_rows, int64_t n_qrows, const int64_t *topk_ids, int k,
+                            const int64_t *item_row, const int *item_len, int n_items, int max_len, int top,
+                            int min_overlap, int32_t *out_track, int32_t *out_offset, float *out_score,
+                            int32_t *out_votes, grafp_stream_t stream);
+
 /* ---- identification against a library held as IVF-PQ codes (grafp_amd/library.py; identify_pq.hip) ---------------
  * grafp_identify_pq_f32 -- grafp_identify_f32 on a library whose rows exist only as codes.  Library row r is
  *   dec[r][j] = centroids[list_id[r]][j] + codebooks[m][codes[r][m]][c], m = j / dsub, c = j % dsub, dsub = 128 / M

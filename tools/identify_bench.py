@@ -11,6 +11,11 @@ the two stages of a query against a compact library are reported separately:
   ivfpq_search   IVFPQIndex.search of every query row
   identify_pq    ops.identify_pq of all items on the codes, next to ops.identify of the same items and hits on the
                  decoded rows (index.reconstruct()), and their ratio
+With --row-stride D the flat library keeps every D-th row of each track (FingerprintLibrary.thin) and the same dense
+items are identified against it:
+  search         ops.FlatL2Index.search of every query row over the kept rows
+  identify_thin  ops.identify_thin of all items in one launch (top 5), next to ops.identify of the same items on the
+                 dense library, and the library's bytes per original row
 Kernel times from events (median of --reps); `rocprofv3 --kernel-trace --stats -- python tools/identify_bench.py` gives
 the per-kernel figures.
 """
@@ -70,6 +75,30 @@ def _ivfpq(args, dev, rows, first, q, item_row, item_len, true_track, true_off):
             "identify_top1_correct": round(float(hit.float().mean()), 4)}
 
 
+def _thin(args, dev, cfg, rows, first, q, item_row, item_len, true_track, true_off):
+    from grafp_amd import library, ops
+    ql, D = args.qlen, args.row_stride
+    dense = library.FingerprintLibrary(None, cfg, rows, first.cpu().numpy(), precision="f32", device=dev)
+    thin = dense.thin(D)
+    trows, tfirst = thin.rows(), torch.from_numpy(thin.first).to(dev)
+    t_search = _events(lambda: thin.index.search(q, args.k), max(1, args.reps // 4))
+    _, ids = thin.index.search(q, args.k)
+    run = lambda: ops.identify_thin(trows, tfirst, q, ids, item_row, item_len, D, top=5, max_len=ql)
+    t_thin = _events(run, args.reps)
+    tr, off, _, vo = run()
+    hit = (tr[:, 0].long() == torch.from_numpy(true_track).to(dev)) & \
+          (off[:, 0].long() == torch.from_numpy(true_off).to(dev))
+    nbytes = thin.nbytes
+    _, dids = dense.index.search(q, args.k)
+    t_dense = _events(lambda: ops.identify(rows, first, q, dids, item_row, item_len, top=5, max_len=ql), args.reps)
+    return {"row_stride": D, "rows": int(rows.shape[0]), "kept_rows": thin.n_rows, "tracks": thin.n_tracks,
+            "queries": args.queries, "qlen": ql, "k": args.k, "search_ms": round(t_search * 1e3, 3),
+            "identify_thin_ms": round(t_thin * 1e3, 3), "identify_dense_ms": round(t_dense * 1e3, 3),
+            "bytes_per_original_row": round(nbytes / rows.shape[0], 1),
+            "identify_top1_correct": round(float(hit.float().mean()), 4),
+            "mean_votes_top1": round(float(vo[:, 0].float().mean()), 2)}
+
+
 def main(argv=None):
     from grafp_amd import library, ops
     from grafp_amd.util import load_config
@@ -84,6 +113,7 @@ def main(argv=None):
     ap.add_argument("--nlist", type=int, default=64)
     ap.add_argument("--pq-m", type=int, default=64)
     ap.add_argument("--nprobe", type=int, default=20)
+    ap.add_argument("--row-stride", type=int, default=None, help="flat: keep every D-th row of each track")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     cfg = load_config()
@@ -105,6 +135,9 @@ def main(argv=None):
 
     if args.index == "ivfpq":
         print(json.dumps(_ivfpq(args, dev, rows, first, q, item_row, item_len, t, a - t * per)))
+        return
+    if args.row_stride is not None:
+        print(json.dumps(_thin(args, dev, cfg, rows, first, q, item_row, item_len, t, a - t * per)))
         return
     index = ops.FlatL2Index(device=dev)
     index.add(rows)
