@@ -29,6 +29,8 @@ SIGNATURES = {
     "grafp_last_error": (_c.c_char_p, []),
     "grafp_logmel_f32": (_I, [_P, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "grafp_unfold_segments_f32": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    "grafp_stream_logmel_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "grafp_stream_segments_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "grafp_peak_extract_fwd_f32": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "grafp_peak_extract_bwd_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "grafp_peak_extract_bwd_workspace": (_Z, [_I, _I, _I, _I]),

@@ -237,3 +237,50 @@ extern "C" int grafp_cross_match_pq_f32(const int32_t *list_id, const uint8_t *c
                                         ws_bytes, out_track, out_delta, out_start, out_len, out_score, out_votes,
                                         (hipStream_t)stream);
 }
+
+// The front end of live multi-channel monitoring (stream_frontend.hip): argument checks here, the kernels there.  The
+// per-channel tables are device data: the caller (ops.stream_logmel) checks them on the host before it uploads them.
+namespace grafp {
+int stream_logmel_launch(const float *bank, const int64_t *buf_start, const int32_t *buf_len, const int64_t *buf_base,
+                         const int64_t *frame_lo, const int64_t *frame_hi, const int32_t *group_first, int n_channels,
+                         int n_groups, int hop, int n_mels, int ring_len, const float *window, const float *twiddle,
+                         const float *fb, const int32_t *band_lo, const int32_t *band_hi, float *ring,
+                         hipStream_t stream);
+int stream_segments_launch(const float *ring, const int64_t *seg_lo, const int32_t *seg_first, int n_channels,
+                           int n_segments, int n_mels, int ring_len, int size, int step, float *seg,
+                           hipStream_t stream);
+}  // namespace grafp
+
+extern "C" int grafp_stream_logmel_f32(const float *bank, const int64_t *buf_start, const int32_t *buf_len,
+                                       const int64_t *buf_base, const int64_t *frame_lo, const int64_t *frame_hi,
+                                       const int32_t *group_first, int n_channels, int n_groups, int n_fft, int hop,
+                                       int n_mels, int ring_len, const float *window, const float *twiddle,
+                                       const float *fb, const int32_t *band_lo, const int32_t *band_hi, float *ring,
+                                       grafp_stream_t stream) {
+    GRAFP_REQUIRE(bank && buf_start && buf_len && buf_base && frame_lo && frame_hi && group_first && window && twiddle &&
+                  fb && band_lo && band_hi && ring, "stream_logmel: null pointer");
+    GRAFP_REQUIRE(n_fft == 1024 && n_mels >= 1 && n_mels <= 64,
+                  "stream_logmel: only n_fft=1024 and n_mels<=64 are supported (got %d and %d)", n_fft, n_mels);
+    GRAFP_REQUIRE(n_channels >= 1 && n_groups >= 0 && hop >= 1, "stream_logmel: bad n_channels=%d n_groups=%d hop=%d",
+                  n_channels, n_groups, hop);
+    GRAFP_REQUIRE(ring_len >= 2 && (ring_len & (ring_len - 1)) == 0,
+                  "stream_logmel: ring_len=%d is no power of two >= 2", ring_len);
+    if (n_groups == 0) return GRAFP_OK;
+    return grafp::stream_logmel_launch(bank, buf_start, buf_len, buf_base, frame_lo, frame_hi, group_first, n_channels,
+                                       n_groups, hop, n_mels, ring_len, window, twiddle, fb, band_lo, band_hi, ring,
+                                       (hipStream_t)stream);
+}
+
+extern "C" int grafp_stream_segments_f32(const float *ring, const int64_t *seg_lo, const int32_t *seg_first,
+                                         int n_channels, int n_segments, int n_mels, int ring_len, int size, int step,
+                                         float *seg, grafp_stream_t stream) {
+    GRAFP_REQUIRE(ring && seg_lo && seg_first && seg, "stream_segments: null pointer");
+    GRAFP_REQUIRE(n_channels >= 1 && n_segments >= 0 && n_mels >= 1 && size >= 1 && step >= 1,
+                  "stream_segments: bad n_channels=%d n_segments=%d n_mels=%d size=%d step=%d", n_channels, n_segments,
+                  n_mels, size, step);
+    GRAFP_REQUIRE(ring_len >= size && (ring_len & (ring_len - 1)) == 0,
+                  "stream_segments: ring_len=%d is no power of two >= size=%d", ring_len, size);
+    if (n_segments == 0) return GRAFP_OK;
+    return grafp::stream_segments_launch(ring, seg_lo, seg_first, n_channels, n_segments, n_mels, ring_len, size, step,
+                                         seg, (hipStream_t)stream);
+}

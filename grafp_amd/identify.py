@@ -7,6 +7,7 @@
   python -m grafp_amd.identify dedup --ckp MODEL.pth --library LIBDIR [--min-overlap 3] [--coverage 0.9] [--json OUT]
   python -m grafp_amd.identify match --ckp MODEL.pth --library LIBDIR FILES... [--min-overlap 3] [--min-votes 4]
                                        [--min-score S] [--top 8] [--k-probe 20] [--json OUT]
+  python -m grafp_amd.identify monitor --ckp MODEL.pth LIBDIR FILES... [--chunk-s 1.0] [--window 3 --hop 1] [--top 5]
 
 `build` fingerprints every track of the source (anything DeviceAudioCorpus accepts) into LIBDIR -- with --index ivfpq as
 a compact library of IVF-PQ codes (about 150 bytes per row instead of 772; `query` works on either form, `dedup` needs
@@ -16,7 +17,10 @@ of tracks that share audio, then one per group of duplicates (--json also writes
 recordings that are not in the library and prints one JSON object per (recording, library track) that share audio, with
 the span and the coverage (either form of a library; --json also writes them to a file).  build --row-stride D keeps
 every D-th fingerprint row of each track (a flat library of 772 / D bytes per original row; `query` works on it
-unchanged, `dedup` and `match` need every row)."""
+unchanged, `dedup` and `match` need every row).  `monitor` treats every file as one live channel: it feeds them to a
+StreamMonitor (grafp_amd/monitor.py) chunk by chunk, all channels per push, prints one JSON object per window as it
+becomes due ({"channel", "file", start_s, end_s, segment_start_s, matches}) and, when the files end, one per timeline
+span of each channel ({"channel", "file", "span": ...})."""
 import argparse
 import json
 import sys
@@ -87,6 +91,19 @@ def main(argv=None):
     m.add_argument("--k-probe", type=int, default=20)
     m.add_argument("--json", default=None, help="also write the matches to this file")
     m.add_argument("--force", action="store_true", help="use a library made with another model")
+    mo = sub.add_parser("monitor", help="follow files as live channels, chunk by chunk")
+    mo.add_argument("--config", default=DEFAULT_CONFIG, help="model configuration (the library keeps its own "
+                                                             "segmentation settings)")
+    mo.add_argument("--ckp", required=True)
+    mo.add_argument("library", metavar="LIBDIR")
+    mo.add_argument("files", nargs="+")
+    mo.add_argument("--chunk-s", type=float, default=1.0, help="seconds of audio every channel gets per push")
+    mo.add_argument("--window", type=float, default=3.0)
+    mo.add_argument("--hop", type=float, default=1.0)
+    mo.add_argument("--top", type=int, default=5)
+    mo.add_argument("--k-probe", type=int, default=20)
+    mo.add_argument("--min-score", type=float, default=None, help="timeline: drop windows whose best match is weaker")
+    mo.add_argument("--force", action="store_true", help="use a library made with another model")
     args = ap.parse_args(argv)
 
     from .data import DeviceAudioCorpus
@@ -125,6 +142,26 @@ def main(argv=None):
         if args.json:
             with open(args.json, "w") as f:
                 json.dump({"pairs": pairs, "groups": groups}, f, indent=1)
+        return 0
+    if args.cmd == "monitor":
+        from .monitor import StreamMonitor
+        waves = lib._load_queries(list(args.files), None)
+        chunk = max(1, int(args.chunk_s * lib.settings["fs"]))
+        mon = StreamMonitor(lib, len(waves), window_s=args.window, hop_s=args.hop, top=args.top, k_probe=args.k_probe,
+                            max_chunk_s=args.chunk_s)
+
+        def report(per_channel):
+            for ch, windows in enumerate(per_channel):
+                for w in windows:
+                    print(json.dumps({"file": args.files[ch], **w}), flush=True)
+
+        for lo in range(0, max(w.numel() for w in waves), chunk):
+            report(mon.push([w[lo:lo + chunk] for w in waves]))
+            report(mon.end([ch for ch, w in enumerate(waves) if lo < w.numel() <= lo + chunk]))
+        report(mon.end(range(len(waves))))                      # (empty files)
+        for ch, path in enumerate(args.files):
+            for span in mon.timeline(ch, args.min_score):
+                print(json.dumps({"channel": ch, "file": path, "span": span}))
         return 0
     if args.cmd == "match":
         res = lib.match(list(args.files), k_probe=args.k_probe, min_overlap_s=args.min_overlap,

@@ -574,20 +574,30 @@ class FingerprintLibrary:
                 waves[i] = out[starts[j]:starts[j] + out_lens[j]]
         return waves
 
-    def _search_and_identify(self, segs, item_row, item_len, top, k_probe, min_overlap):
-        """One batched embed + search of all segments, one ops.identify launch for all items -> per-item lists.  (The
-        queries' segments are all embedded, whatever the library's row_stride: the query side stays dense.)"""
-        n_items = len(item_row)
-        if n_items == 0 or segs.shape[0] == 0 or self.n_rows == 0 or int(np.max(item_len, initial=0)) == 0:
-            return [[] for _ in range(n_items)]
-        max_len = int(np.max(item_len))
+    def _check_item_len(self, max_len, k_probe):
         if max_len > ops.IDENTIFY_MAX_LEN or max_len * k_probe > ops.IDENTIFY_MAX_KEYS:
             raise ValueError(f"a query of {max_len} segments ({max_len * self.segment_s:.1f} s) with k_probe={k_probe} "
                              f"exceeds {ops.IDENTIFY_MAX_LEN} segments / {ops.IDENTIFY_MAX_KEYS} hits per item: use "
                              "identify_windows for long recordings")
+
+    def _embed_and_search(self, segs, k_probe):
+        """One batched embed of the segments and one search of their rows -> (q (n, 128) f32, ids (n, k) int64)."""
         q = self._embed(segs)
+        return q, self._search_rows(q, k_probe)
+
+    def _search_rows(self, q, k_probe):
         k = min(int(k_probe), self.n_rows)
-        _, ids = self.index.search(q, k)
+        return self.index.search(q, k)[1]
+
+    def _identify_items(self, q, ids, item_row, item_len, top, min_overlap, max_len=None):
+        """One identify launch (the kernel of the library's form) for all items over the rows q and their hits ids ->
+        per-item lists of matches.  max_len: an upper bound of the items' lengths (None: the longest).  (StreamMonitor
+        calls it with rows it kept from earlier pushes.)"""
+        n_items = len(item_row)
+        longest = int(np.max(item_len, initial=0))
+        if n_items == 0 or longest == 0:
+            return [[] for _ in range(n_items)]
+        max_len = longest if max_len is None else max(int(max_len), longest)
         dev = self.device
         tail = (torch.from_numpy(self.first).to(dev), q, ids, torch.from_numpy(np.asarray(item_row, np.int64)).to(dev),
                 torch.from_numpy(np.asarray(item_len, np.int32)).to(dev))
@@ -613,6 +623,16 @@ class FingerprintLibrary:
                             "votes": int(vo[i, j])})
             out.append(res)
         return out
+
+    def _search_and_identify(self, segs, item_row, item_len, top, k_probe, min_overlap):
+        """One batched embed + search of all segments, one ops.identify launch for all items -> per-item lists.  (The
+        queries' segments are all embedded, whatever the library's row_stride: the query side stays dense.)"""
+        n_items = len(item_row)
+        if n_items == 0 or segs.shape[0] == 0 or self.n_rows == 0 or int(np.max(item_len, initial=0)) == 0:
+            return [[] for _ in range(n_items)]
+        self._check_item_len(int(np.max(item_len)), k_probe)
+        q, ids = self._embed_and_search(segs, k_probe)
+        return self._identify_items(q, ids, item_row, item_len, top, min_overlap)
 
     def identify(self, queries, fs=None, top=5, k_probe=20, min_overlap=None):
         """queries: one waveform, a list of ragged waveforms, or file paths; at `fs` (default settings['fs']; other rates

@@ -179,6 +179,139 @@ def unfold_segments(spec, size, step):
 
 
 # ------------------------------------------------------------------------------------------------
+# K1 for live streams (csrc/stream_frontend.hip; grafp_amd/monitor.py holds the per-channel state)
+# ------------------------------------------------------------------------------------------------
+STREAM_PAIRS_PER_GROUP = 8          # frame pairs of one channel a workgroup of stream_logmel does (LM1K_PAIRS)
+
+
+def _host_i64(v, n, what):
+    a = np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v).astype(np.int64).reshape(-1)
+    if a.shape[0] != n:
+        raise ValueError(f"{what}: {a.shape[0]} entries for {n} channels")
+    return a
+
+
+def _check_ring(name, ring, n_mels=None):
+    if ring.dim() != 3 or ring.dtype != torch.float32 or not ring.is_contiguous():
+        raise ValueError(f"{name}: the ring must be a contiguous f32 (channels, n_mels, R) tensor")
+    R = int(ring.shape[2])
+    if R < 2 or R & (R - 1) or (n_mels is not None and int(ring.shape[1]) != int(n_mels)):
+        raise ValueError(f"{name}: a ring of shape {tuple(ring.shape)} needs R a power of two"
+                         + (f" and n_mels = {n_mels}" if n_mels is not None else ""))
+    return int(ring.shape[0]), int(ring.shape[1]), R
+
+
+def stream_logmel_plan(n_channels, ring_len, bank_len, starts, lengths, base, seen, ended, frame_lo, frame_hi, n_fft,
+                       hop):
+    """The host checks and the workgroup table of stream_logmel (pure: no device needed).  Refuses (ValueError) what
+    would not give the offline kernel's bits or would read outside a buffer.  -> None if no channel has a frame due, else
+    (starts, lengths, base, frame_lo, frame_hi as int64 arrays, group_first (C + 1) int64 prefix sums of the workgroups
+    per channel)."""
+    C, R = int(n_channels), int(ring_len)
+    hop, half = int(hop), int(n_fft) // 2
+    st, ln, bs, sn, lo, hi = (_host_i64(v, C, "stream_logmel") for v in (starts, lengths, base, seen, frame_lo,
+                                                                           frame_hi))
+    en = np.asarray(ended).astype(bool).reshape(-1)
+    if en.shape[0] != C:
+        raise ValueError(f"stream_logmel: {en.shape[0]} `ended` flags for {C} channels")
+    act = hi > lo
+    if not act.any():
+        return None
+    if (lo[act] < 0).any() or (lo[act] & 1).any() or (hi[act] - lo[act] > R).any():
+        raise ValueError("stream_logmel: a frame range must start at an even frame >= 0 and hold at most R frames")
+    if (st[act] < 0).any() or (ln[act] < 1).any() or (st[act] + ln[act] > int(bank_len)).any() or \
+            (ln[act] >= 2 ** 31 - 2 * half - hop).any() or (bs[act] < 0).any() or (bs[act] + ln[act] != sn[act]).any():
+        raise ValueError("stream_logmel: a channel's buffer must lie inside the bank and end at the samples seen so far")
+    # every position read lies in [base, seen): the first frame's left edge (the reflection at the stream's start is of
+    # positions >= 0, so base must be 0 there), the last frame's right edge unless the stream has ended
+    first_pos = lo * hop - half
+    if (bs[act] > np.maximum(first_pos[act], 0)).any() or ((first_pos[act] < 0) & (sn[act] <= half)).any():
+        raise ValueError("stream_logmel: the buffer starts behind the first sample a frame reads")
+    opn, end = act & ~en, act & en
+    if (((hi[opn] - lo[opn]) & 1) != 0).any() or ((hi[opn] - 1) * hop + half - 1 >= sn[opn]).any():
+        raise ValueError("stream_logmel: an open stream emits whole frame pairs whose samples have all arrived")
+    if (hi[end] > 1 + sn[end] // hop).any() or (sn[end] <= half).any() or \
+            (bs[end] > np.maximum(sn[end] - half - 1, 0)).any():
+        raise ValueError("stream_logmel: an ended stream has 1 + seen // hop frames, needs seen > n_fft / 2 and its "
+                         "buffer must hold the samples the end reflection reads")
+    pairs = -(-(hi - lo) // 2)
+    groups = np.where(act, -(-pairs // STREAM_PAIRS_PER_GROUP), 0)
+    return st, ln, bs, lo, hi, np.concatenate([[0], np.cumsum(groups)]).astype(np.int64)
+
+
+def stream_logmel(bank, starts, lengths, base, seen, ended, frame_lo, frame_hi, ring, fs=16000, n_fft=1024,
+                  win_len=1024, hop=512, n_mels=64):
+    """The new log-mel frames of many live channels in ONE launch (grafp_stream_logmel_f32).
+    bank: flat f32 device buffer; channel c's samples are bank[starts[c] : starts[c] + lengths[c]] -- what the caller
+    carried over from earlier chunks, then the new chunk -- and the first of them is sample base[c] of the stream, of
+    which seen[c] = base[c] + lengths[c] samples have arrived; ended[c]: no more will.  Frames [frame_lo[c], frame_hi[c])
+    are written to ring[c, :, f & (R - 1)] (ring: (C, n_mels, R) f32, R a power of two); an empty range does nothing
+    for that channel.  The per-channel tables are HOST integers (sequences or arrays).
+    The frames are bit-equal to ops.logmel(whole stream)[:, f].  That needs what stream_logmel_plan checks on the host:
+    frame_lo even (two frames share one transform), every sample a frame reads inside the buffer, an even number of
+    frames while the stream is open, and, once it has ended, no frame beyond 1 + seen // hop.  Only n_fft == 1024 and
+    n_mels <= 64 (the model's configuration); anything else is a ValueError.
+    -> the number of workgroups launched (0: nothing was due, nothing launched)."""
+    _require_gpu(bank, ring)
+    if int(n_fft) != 1024 or not 1 <= int(n_mels) <= 64:
+        raise ValueError(f"stream_logmel: only n_fft == 1024 and n_mels <= 64 are supported, not n_fft={n_fft}, "
+                         f"n_mels={n_mels}")
+    C, _, R = _check_ring("stream_logmel", ring, n_mels)
+    if bank.dim() != 1 or bank.dtype != torch.float32 or not bank.is_contiguous() or bank.device != ring.device:
+        raise ValueError("stream_logmel: the bank must be a flat contiguous f32 buffer on the ring's device")
+    plan_ = stream_logmel_plan(C, R, bank.numel(), starts, lengths, base, seen, ended, frame_lo, frame_hi, n_fft, hop)
+    if plan_ is None:
+        return 0
+    st, ln, bs, lo, hi, first = plan_
+    n_groups = int(first[-1])
+    plan = _mel_plan(ring.device, fs, n_fft, win_len, n_mels)
+    # one upload: the four int64 tables, then the two int32 ones (viewed in the same buffer)
+    tab = np.concatenate([st, bs, lo, hi, np.zeros(C + 1, np.int64)])
+    i32 = tab[4 * C:].view(np.int32)
+    i32[:C] = ln
+    i32[C:2 * C + 1] = first
+    d = torch.from_numpy(tab).to(ring.device)
+    d32 = d[4 * C:].view(torch.int32)
+    with _timed("stream_logmel", (C, n_groups)):
+        check(lib.grafp_stream_logmel_f32(_p(bank), _p(d[0:C]), _p(d32[0:C]), _p(d[C:2 * C]), _p(d[2 * C:3 * C]),
+                                          _p(d[3 * C:4 * C]), _p(d32[C:2 * C + 1]), C, n_groups, int(n_fft), int(hop),
+                                          int(n_mels), R, _p(plan.window), _p(plan.twiddle), _p(plan.fb),
+                                          _p(plan.band_lo), _p(plan.band_hi), _p(ring), _stream()), "stream_logmel")
+    return n_groups
+
+
+def stream_segments(ring, seg_lo, seg_hi, size, step):
+    """The new segments of many live channels in ONE launch (grafp_stream_segments_f32).  ring (C, n_mels, R) as
+    stream_logmel fills it; segments [seg_lo[c], seg_hi[c]) of channel c (host integers) are frames
+    [s * step, s * step + size) read through the ring.  -> (sum(seg_hi - seg_lo), n_mels, size) f32, channel by channel,
+    segments ascending: the values ops.unfold_segments gives on the whole spectrogram.  The caller vouches that the ring
+    still holds those frames (R >= size + the frames written since segment seg_lo[c] started)."""
+    _require_gpu(ring)
+    C, n_mels, R = _check_ring("stream_segments", ring)
+    size, step = int(size), int(step)
+    if not (1 <= size <= R and step >= 1):
+        raise ValueError(f"stream_segments: size={size} must lie in [1, R={R}] and step={step} be positive")
+    lo, hi = _host_i64(seg_lo, C, "stream_segments"), _host_i64(seg_hi, C, "stream_segments")
+    cnt = np.maximum(hi - lo, 0)
+    if ((lo < 0) & (cnt > 0)).any() or ((cnt - 1) * step + size > R).any():
+        raise ValueError("stream_segments: a segment range must be non-negative and fit the ring")
+    first = np.concatenate([[0], np.cumsum(cnt)])
+    n = int(first[-1])
+    seg = torch.empty((n, n_mels, size), dtype=torch.float32, device=ring.device)
+    if n == 0:
+        return seg
+    if n >= 2 ** 31:
+        raise ValueError("stream_segments: too many segments for one launch")
+    tab = np.concatenate([lo, np.zeros((C + 2) // 2, np.int64)])
+    tab[C:].view(np.int32)[:C + 1] = first
+    d = torch.from_numpy(tab).to(ring.device)
+    with _timed("stream_segments", (C, n)):
+        check(lib.grafp_stream_segments_f32(_p(ring), _p(d[0:C]), _p(d[C:].view(torch.int32)), C, n, n_mels, R, size,
+                                            step, _p(seg), _stream()), "stream_segments")
+    return seg
+
+
+# ------------------------------------------------------------------------------------------------
 # device-side augmentation (SURVEY.md 8f-3; modules/transformations.py:25-48)
 # ------------------------------------------------------------------------------------------------
 def _i32c(t, device):

@@ -67,6 +67,38 @@ int grafp_logmel_f32(const float *wav, int64_t wav_stride, int B, int T, int n_f
 int grafp_unfold_segments_f32(const float *spec, int n_mels, int n_frames, int size, int step, float *seg,
                               grafp_stream_t stream);
 
+/* ---- K1 for live streams: the front end of grafp_amd/monitor.py ------------------------------
+ * Many channels, each an open-ended stream that arrives chunk by chunk.  The caller keeps, per channel, a buffer with
+ * the samples [buf_base, buf_base + buf_len) of the stream (what earlier frames left to be read again, then the new
+ * chunk) and a spectrogram ring (n_mels, ring_len), ring_len a power of two.  ONE launch computes the frames
+ * [frame_lo, frame_hi) of every channel -- frame f into ring column f & (ring_len - 1) -- with the arithmetic of
+ * grafp_logmel_f32 at n_fft = 1024 (the same frame-pair body, csrc/logmel_core.h): the frames are bit-equal to those of
+ * grafp_logmel_f32 on the whole stream, PROVIDED frame_lo is even (two frames share one transform) and every position a
+ * frame reads is in the buffer: for an open stream max(f hop + 511, 512 - f hop) < buf_base + buf_len and
+ * buf_base <= max(0, frame_lo hop - 512); a stream that has ended may also emit its last frames, which reflect at
+ * buf_len (torch.stft center=True) and need buf_base <= end - 513.  The kernel clamps every read into the buffer.
+ *   bank         flat f32 buffer; channel c's buffer is bank[buf_start[c] .. + buf_len[c])
+ *   buf_start    (C) int64      buf_len (C) int32      buf_base (C) int64 absolute position of the buffer's first sample
+ *   frame_lo/hi  (C) int64      frame_hi - frame_lo <= ring_len; equal: nothing for that channel
+ *   group_first  (C + 1) int32  prefix sums of ceil(ceil((frame_hi - frame_lo) / 2) / 8): a workgroup does up to 8 frame
+ *                               pairs of one channel and finds the channel here; n_groups = group_first[C]
+ *   window, twiddle, fb, band_lo, band_hi: as for grafp_logmel_f32;  ring (C, n_mels, ring_len) f32
+ * Only n_fft = 1024 and n_mels <= 64. */
+int grafp_stream_logmel_f32(const float *bank, const int64_t *buf_start, const int32_t *buf_len,
+                            const int64_t *buf_base, const int64_t *frame_lo, const int64_t *frame_hi,
+                            const int32_t *group_first, int n_channels, int n_groups, int n_fft, int hop, int n_mels,
+                            int ring_len, const float *window, const float *twiddle, const float *fb,
+                            const int32_t *band_lo, const int32_t *band_hi, float *ring, grafp_stream_t stream);
+
+/* The new segments of every channel in ONE launch: segment s of channel c is frames [s step, s step + size) read through
+ * the channel's ring; the segments seg_lo[c] ... of channel 0, then of channel 1, ... are written packed into
+ * seg (n_segments, n_mels, size) -- the values grafp_unfold_segments_f32 gives on the whole spectrogram.
+ *   seg_lo (C) int64 first new segment per channel;  seg_first (C + 1) int32 prefix sums of the new segments per channel,
+ *   n_segments = seg_first[C].  The caller vouches that the ring still holds those frames. */
+int grafp_stream_segments_f32(const float *ring, const int64_t *seg_lo, const int32_t *seg_first, int n_channels,
+                              int n_segments, int n_mels, int ring_len, int size, int step, float *seg,
+                              grafp_stream_t stream);
+
 /* ---- K2: peak extractor ----------------------------------------------------------------------
  * Replaces GPUPeakExtractorv2.forward, peak_extractor.py:56-82: per-clip min-max normalisation,
  * [T-ramp, F-ramp, spec] stack, Conv2d(3 -> F, (KH,KW), stride (sh,1), pad (KH/2,KW/2)) + ReLU, flatten.

@@ -1,0 +1,159 @@
+"""Time of one StreamMonitor.push for C live channels of random audio in 1 s chunks, split into front end, embed,
+search and identify -- and, in the same process, of the per-channel path the library offered before (keep every
+channel's last window_s seconds as a waveform, run FingerprintLibrary.segments on each tail, then one embed + search +
+identify of every channel's newest window).
+
+    python tools/stream_bench.py [--channels 64 512] [--pushes 10] [--warm 4] [--tracks 64] [--track-s 30]
+
+The monitor embeds only the segments that are new (about 10.4 per channel and second at the default settings); the
+per-channel path embeds the 21 segments of the newest window again every second.  One JSON line per channel count, then
+a table."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from grafp_amd.library import FingerprintLibrary, n_segments  # noqa: E402
+from grafp_amd.monitor import StreamMonitor  # noqa: E402
+from grafp_amd.train import build_model  # noqa: E402
+from grafp_amd.util import load_config  # noqa: E402
+
+
+class Phases:
+    """Wall time of the wrapped callables, each bracketed by a device synchronisation."""
+
+    def __init__(self):
+        self.ms, self.enabled = {}, False
+
+    def wrap(self, name, fn):
+        def timed(*a, **kw):
+            if not self.enabled:
+                return fn(*a, **kw)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn(*a, **kw)
+            torch.cuda.synchronize()
+            self.ms[name] = self.ms.get(name, 0.0) + (time.perf_counter() - t0) * 1e3
+            return out
+        return timed
+
+    def take(self):
+        out, self.ms = self.ms, {}
+        return out
+
+
+def _median(rows, key):
+    return statistics.median(r.get(key, 0.0) for r in rows)
+
+
+def bench_monitor(lib, audio, chunk, warm, phases):
+    C, total = audio.shape
+    plain, split, launches, windows = [], [], [], 0
+    for instrumented in (False, True):
+        phases.enabled = instrumented
+        mon = StreamMonitor(lib, C, max_chunk_s=chunk / lib.settings["fs"])
+        mon.front.push = phases.wrap("front_end", mon.front.push)
+        for s in range(total // chunk):
+            chunks = list(audio[:, s * chunk:(s + 1) * chunk])
+            before = mon.front.launches
+            phases.take()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = mon.push(chunks)
+            torch.cuda.synchronize()
+            ms = (time.perf_counter() - t0) * 1e3
+            if s < warm:
+                continue
+            if instrumented:
+                split.append(dict(phases.take(), total=ms))
+            else:
+                plain.append(ms)
+                launches.append(mon.front.launches - before)
+                windows += sum(len(w) for w in out)
+    res = {"push_ms": statistics.median(plain), "front_end_launches": max(launches),
+           "windows_per_push": windows / len(plain)}
+    for key in ("front_end", "embed", "search", "identify"):
+        res[key + "_ms"] = _median(split, key)
+    res["other_ms"] = max(0.0, _median(split, "total") - sum(res[k + "_ms"] for k in ("front_end", "embed", "search",
+                                                                                        "identify")))
+    return res
+
+
+def bench_per_channel(lib, audio, chunk, warm, phases, window_s=3.0, top=5, k_probe=20):
+    C, total = audio.shape
+    keep = int(window_s * lib.settings["fs"])
+    per_window = n_segments(keep, lib.settings)
+    plain, split = [], []
+    for instrumented in (False, True):
+        phases.enabled = instrumented
+        tails = [audio[c, :0] for c in range(C)]
+        for s in range(total // chunk):
+            phases.take()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            t1 = time.perf_counter()
+            segs = []
+            for c in range(C):
+                tails[c] = torch.cat([tails[c], audio[c, s * chunk:(s + 1) * chunk]])[-keep:]
+                segs.append(lib.segments(tails[c])[-per_window:])
+            if instrumented:
+                torch.cuda.synchronize()
+                phases.ms["front_end"] = (time.perf_counter() - t1) * 1e3
+            lens = np.array([x.shape[0] for x in segs], np.int32)
+            rows = np.concatenate([[0], np.cumsum(lens[:-1])]).astype(np.int64)
+            lib._search_and_identify(torch.cat(segs), rows, lens, top, k_probe, None)
+            torch.cuda.synchronize()
+            ms = (time.perf_counter() - t0) * 1e3
+            if s >= warm:
+                (split if instrumented else plain).append(dict(phases.take(), total=ms) if instrumented else ms)
+    res = {"push_ms": statistics.median(plain), "front_end_launches": 2 * C}
+    for key in ("front_end", "embed", "search", "identify"):
+        res[key + "_ms"] = _median(split, key)
+    res["other_ms"] = max(0.0, _median(split, "total") - sum(res[k + "_ms"] for k in ("front_end", "embed", "search",
+                                                                                        "identify")))
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--channels", type=int, nargs="+", default=[64, 512])
+    ap.add_argument("--pushes", type=int, default=10, help="timed pushes per path")
+    ap.add_argument("--warm", type=int, default=4, help="untimed pushes first (3 s fill the first window)")
+    ap.add_argument("--tracks", type=int, default=64)
+    ap.add_argument("--track-s", type=float, default=30.0)
+    ap.add_argument("--chunk-s", type=float, default=1.0)
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    cfg = load_config()
+    torch.manual_seed(0)
+    model = build_model(cfg, device=dev).eval()
+    g = torch.Generator(device=dev).manual_seed(1)
+    tracks = 0.1 * torch.randn((args.tracks, int(args.track_s * cfg["fs"])), generator=g, device=dev)
+    lib = FingerprintLibrary.build(model, list(tracks), cfg)
+    phases = Phases()
+    lib._embed = phases.wrap("embed", lib._embed)
+    lib._search_rows = phases.wrap("search", lib._search_rows)
+    lib._identify_items = phases.wrap("identify", lib._identify_items)
+    chunk = int(args.chunk_s * cfg["fs"])
+    rows = []
+    for C in args.channels:
+        audio = 0.1 * torch.randn((C, (args.warm + args.pushes) * chunk), generator=g, device=dev)
+        for path, fn in (("monitor", bench_monitor), ("per_channel", bench_per_channel)):
+            res = dict(fn(lib, audio, chunk, args.warm, phases), channels=C, path=path, library_rows=lib.n_rows)
+            rows.append(res)
+            print(json.dumps(res), flush=True)
+    print(f"{'C':>5} {'path':<12} {'push ms':>9} {'front end':>10} {'embed':>8} {'search':>8} {'identify':>9} {'other':>7} "
+          f"{'front-end launches':>19}")
+    for r in rows:
+        print(f"{r['channels']:>5} {r['path']:<12} {r['push_ms']:>9.2f} {r['front_end_ms']:>10.2f} {r['embed_ms']:>8.2f} "
+              f"{r['search_ms']:>8.2f} {r['identify_ms']:>9.2f} {r['other_ms']:>7.2f} {r['front_end_launches']:>19d}")
+
+
+if __name__ == "__main__":
+    main()
