@@ -49,9 +49,6 @@ __device__ __forceinline__ float2 block_sum2(float a, float b, float2 *scratch, 
     return r;
 }
 
-__device__ __forceinline__ float act_fwd(float u, int act, float slope) {
-    return act == 0 ? u : (act == 1 ? relu_keep_nan(u) : (u > 0.0f ? u : u * slope));
-}
 __device__ __forceinline__ float act_grad(float u, int act, float slope) {
     return act == 0 ? 1.0f : (u > 0.0f ? 1.0f : (act == 1 ? 0.0f : slope));
 }

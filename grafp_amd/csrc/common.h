@@ -33,6 +33,17 @@ __device__ __forceinline__ int mfma_row(int reg, int half) { return (reg & 3) + 
 // ReLU (and the clamp of a variance at zero) that lets NaN through, as torch's does: fmaxf(NaN, 0) is 0, which turns a
 // poisoned row into zeros and a NaN variance into a finite one.
 __device__ __forceinline__ float relu_keep_nan(float v) { return v <= 0.0f ? 0.0f : v; }
+// the activation codes of the ABI: 0 none, 1 ReLU, 2 leaky ReLU with `slope`
+__device__ __forceinline__ float act_fwd(float u, int act, float slope) {
+    return act == 0 ? u : (act == 1 ? relu_keep_nan(u) : (u > 0.0f ? u : u * slope));
+}
+// ... of the two halves of a packed bf16 pair at once, for the kernels that transform an MFMA operand or a 16-byte vector
+// in registers: one test of `act` around both elements is what lets hipcc 7.2 use v_pk_mul_f32 / v_pk_fma_f32 there
+// (element by element through act_fwd the normalise-on-load chunk loops grow by 100 ... 780 instructions)
+__device__ __forceinline__ void act_fwd_pair(float &a, float &b, int act, float slope) {
+    if (act == 1) { a = relu_keep_nan(a); b = relu_keep_nan(b); }
+    else if (act == 2) { a = a > 0.f ? a : a * slope; b = b > 0.f ? b : b * slope; }
+}
 
 }  // namespace grafp
 

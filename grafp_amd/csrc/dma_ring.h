@@ -47,4 +47,12 @@ __device__ __forceinline__ void gm_wait_allowed(int allowed) {
     }
 }
 
+// host: a launch with `lds` bytes of dynamic LDS: beyond the 48 KB every kernel may have, the function attribute has to
+// allow it
+template <typename... P, typename... A>
+static void gm_launch(void (*kernel)(P...), dim3 grid, int threads, size_t lds, hipStream_t s, A... args) {
+    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, s, static_cast<P>(args)...);
+}
+
 }  // namespace grafp

@@ -10,8 +10,8 @@
 // passes over the activations:
 //   * STATS: per output row the shifted sums  sum(y - s), sum((y - s)^2)  of the bf16-ROUNDED outputs, accumulated in
 //     registers over all tiles of a workgroup, merged over its wave columns in LDS and written as ONE (count, mean, M2)
-//     partial per (row, workgroup): the BatchNorm that
-//     follows needs no statistics pass (grafp_bn_finalize + grafp_bn_affine, or the next GEMM's PRO);
+//     partial per (row, workgroup): the BatchNorm that follows needs no statistics pass (grafp_bn_finalize +
+//     grafp_bn_affine, or the next GEMM's PRO);
 //   * PRO: x -> act(x * scale[k] + shift[k]) per operand row while the tile sits in LDS: the normalised hidden
 //     activation of the FFN (4C rows, the largest tensor of a block) and of the max-relative conv are never written.
 // Structure: 4 waves, 128 x 128 output tile, 64 (r) x 64 (m) per wave as 2 x 2 v_mfma_f32_32x32x16_bf16 tiles with
@@ -27,6 +27,8 @@
 #define GRAFP_STORE_FAMILY 2        // (common.h: GRAFP_ST_NT experiment builds)
 #include "dma_ring.h"
 #include "elemio.h"
+#include <cstdarg>
+#include <cstdio>
 
 namespace grafp {
 
@@ -57,6 +59,12 @@ template <int WR_, int WM_, int RT_, int OR_ = 32> struct GemmCfg {
     static constexpr int RPI = 64 / SLOTS;                // X tile rows per DMA instruction
     static constexpr int OUT_BYTES = OR_ * 128;           // per-wave output staging: OR rows (r) x 64 m bf16
     static constexpr int PRO_PIECES = TN / (16 * NW);     // PRO: 16-byte X pieces per thread and chunk
+    // workgroups per CU (by launch bounds: the four-wave tile runs two, 140-156 VGPRs) and ring depth: the stages that
+    // fit a workgroup's share of the 160 KB beside the staging slabs -- 4 everywhere (four stages on L = all 160 KB, -2.7 %
+    // against three) but 3 on N128; 3 stages everywhere beside a PRO table
+    static constexpr int PER_CU = NW == 4 ? 2 : 1;
+    static constexpr int NS = (160 * 1024 / PER_CU - NW * OUT_BYTES) / STAGE, NS_PRO = 3;
+    static constexpr bool HAS_PRO = true, HAS_EPI = true, HAS_OUTF32 = true;
     static_assert(SLOTS <= 64 && 64 % SLOTS == 0 && A_BYTES == NA * 1024 && B_BYTES == NB * 1024, "1-KiB DMA pieces");
     static_assert(OR_ == 32 || OR_ == 16, "staging slab");
 };
@@ -68,11 +76,42 @@ typedef GemmCfg<1, 8, 4, 32> GemmN128;
 // (Measured and dropped, round 3: M = 2 x 2 waves, RT 4 -> 256 x 128 with THREE 24 KB stages + 2 KB staging slabs = 80 KB,
 //  i.e. two workgroups per CU that run out of phase by themselves, one's MFMA chain under the other's epilogue and store
 //  drain: 10-15 % SLOWER than L on every stage 2-3 shape, 37.6 vs 34.0 ms over a step's products at 2048 clip-views.)
-enum { GM_CFG_S = 0, GM_CFG_L = 1, GM_CFG_N32 = 2, GM_CFG_N64 = 3, GM_CFG_N128 = 4, GM_CFG_XL = 5 };   // XL: gemm_xl.h
+// XL: the 256 x 256 tile on FOUR waves (conv1x1_gemm_xl_kernel, gemm_xl.h): same stage layout and swizzles as GemmL
+struct GemmXL {
+    static constexpr int NW = 4, THREADS = 256, TR = 256, TN = 256, RT = 4, MT = 4, NS = 4, NS_PRO = 0, PER_CU = 1;
+    static constexpr int NA = 16, NB = 16, PW = NA / NW, PX = NB / NW;   // 1-KiB LDS-DMA pieces per chunk: W, X; ... per wave
+    static constexpr int A_BYTES = TR * GM_KC * 2, B_BYTES = GM_KC * TN * 2, STAGE = A_BYTES + B_BYTES;
+    static constexpr int ROWB = TN * 2, SLOTS = TN / 8, RPI = 64 / SLOTS;
+    static constexpr int OUT_BYTES = 32 * 256;                   // per wave: 32 rows (r) x 128 m bf16
+    static constexpr int STORES_PER_RT = 8;                      // 16-byte store instructions per wave and 32-row tile
+    static constexpr size_t LDS = (size_t)NS * STAGE + NW * OUT_BYTES;
+    // no normalise-on-load, affine-epilogue or f32-output form: those launches take GemmL on the same grid (gemm_dispatch)
+    static constexpr bool HAS_PRO = false, HAS_EPI = false, HAS_OUTF32 = false;
+};
+enum { GM_CFG_S = 0, GM_CFG_L = 1, GM_CFG_N32 = 2, GM_CFG_N64 = 3, GM_CFG_N128 = 4, GM_CFG_XL = 5, GM_NCFG = 6 };
+// number -> its tile type: f(GemmS{}) ... f(GemmXL{}); the one place that maps one to the other
+template <typename F> static void gm_visit(int cfg, F &&f) {
+    switch (cfg) {
+    case GM_CFG_L: return f(GemmL{});
+    case GM_CFG_N32: return f(GemmN32{});
+    case GM_CFG_N64: return f(GemmN64{});
+    case GM_CFG_N128: return f(GemmN128{});
+    case GM_CFG_XL: return f(GemmXL{});
+    default: return f(GemmS{});                 // GM_CFG_S
+    }
+}
+// what the host needs of a tile configuration, read off its type: tile, workgroups per CU, ring depth (beside a PRO table),
+// the forms that exist
+struct GemmTile { int tr, tn, per_cu, ns, ns_pro; bool pro, epi, outf32; };
+template <typename T> constexpr GemmTile gm_tile_of() {
+    return {T::TR, T::TN, T::PER_CU, T::NS, T::NS_PRO, T::HAS_PRO, T::HAS_EPI, T::HAS_OUTF32};
+}
+static const GemmTile gm_tiles[GM_NCFG] = {gm_tile_of<GemmS>(),   gm_tile_of<GemmL>(),    gm_tile_of<GemmN32>(),
+                                           gm_tile_of<GemmN64>(), gm_tile_of<GemmN128>(), gm_tile_of<GemmXL>()};
 
 struct GemmPlan {
     int cfg;                                     // tile configuration (GM_CFG_*)
-    int tr, tn, wm, ns, row_tiles, col_tiles_view, ranges_view, tiles_range, nblocks, P;
+    int tr, tn, wm, row_tiles, col_tiles_view, ranges_view, tiles_range, nblocks, P;
     int wgs;                                     // resident-workgroup target the column ranges were cut for
 };
 // R rows per conv group, M columns, `views` column segments with separate statistics (a range never straddles two)
@@ -119,15 +158,11 @@ static GemmPlan gemm_plan(int Rg, int K, int groups, int64_t M, int views) {
     // the four-wave tile (gemm_xl.h) takes whole 256-row tiles and hides a tile's epilogue in the next tile's first four
     // chunks: rows per group a multiple of 256, at least 128 operand rows
     if (p.cfg == GM_CFG_XL && (Rg % 256 != 0 || K < 4 * GM_KC)) p.cfg = GM_CFG_L;
-    static const int trs[6] = {GemmS::TR, GemmL::TR, GemmN32::TR, GemmN64::TR, GemmN128::TR, 256};
-    static const int tns[6] = {GemmS::TN, GemmL::TN, GemmN32::TN, GemmN64::TN, GemmN128::TN, 256};
-    p.tr = trs[p.cfg];
-    p.tn = tns[p.cfg];
+    const GemmTile &tile = gm_tiles[p.cfg];
+    p.tr = tile.tr;
+    p.tn = tile.tn;
     p.wm = p.tn / 64;
-    // ring depth: S keeps 2 workgroups per CU (80 KB each: 4 stages); the others are alone on their CU and take what
-    // the 160 KB hold beside the staging slabs; 3 stages everywhere beside a PRO table (gemm_dispatch)
-    p.ns = p.cfg == GM_CFG_N128 ? 3 : 4;
-    const int per_cu = p.cfg == GM_CFG_S ? 2 : 1;
+    const int per_cu = tile.per_cu;
     p.row_tiles = (Rg + p.tr - 1) / p.tr;
     p.col_tiles_view = (int)(Mg / p.tn);
     const int nch = K / GM_KC;
@@ -161,6 +196,124 @@ __device__ __forceinline__ void gm_chan(float &n, float &mean, float &m2, float 
     }
 }
 
+// ---- pieces shared by conv1x1_gemm_kernel and conv1x1_gemm_xl_kernel (gemm_xl.h) ----
+// What a workgroup owns: row tile rt and column range rloc of view `view`: ntile tiles, the first at column col0 of the row.
+struct GemmRange {
+    int rt, view, rloc, ntile;
+    int64_t col0;
+};
+// tiles in column range `range` of a view (the last one may be short): the writers of the partials and their reader agree
+__host__ __device__ __forceinline__ int gm_range_tiles(int range, int tiles_range, int col_tiles_view) {
+    return (tiles_range < col_tiles_view - range * tiles_range) ? tiles_range : col_tiles_view - range * tiles_range;
+}
+__device__ __forceinline__ GemmRange gm_range(int nblocks, int row_tiles, int ranges_view, int tiles_range,
+                                              int col_tiles_view, int64_t M, int views, int TN) {
+    GemmRange g;
+    const int logical = xcd_remap(blockIdx.x, nblocks);
+    const int range = logical / row_tiles;
+    g.rt = logical % row_tiles;
+    g.view = range / ranges_view;
+    g.rloc = range - g.view * ranges_view;
+    g.ntile = gm_range_tiles(g.rloc, tiles_range, col_tiles_view);
+    g.col0 = (int64_t)g.view * (M / views) + (int64_t)(g.rloc * tiles_range) * TN;
+    return g;
+}
+
+// LDS-DMA sources.  The LDS side of a piece is lane-linear (stage + piece KiB + lane * 16): the swizzles are applied on the
+// SOURCE side here and again by the fragment reads below.  W piece: 16 rows of 64 B, `row` = the lane's (first row of the
+// piece, a multiple of 16, + lane >> 2): 16-byte slot lane & 3 of the LDS row holds source slot (lane & 3) ^ ((row >> 2) & 3).
+__device__ __forceinline__ const unsigned short *gm_w_src(const unsigned short *A, int lda, int row, int lane) {
+    return A + (size_t)row * lda + ((lane & 3) ^ ((lane >> 4) & 3)) * 8;
+}
+// X piece `piece`: RPI k-rows of ROWB bytes; 16-byte slot s' = lane % SLOTS of its row holds source segment
+// (s' >> 2) ^ (row & 3) (low two bits of the 64-byte segment index), piece s' & 3 of the segment.
+template <typename CFG>
+__device__ __forceinline__ const unsigned short *gm_x_src(const unsigned short *X, int64_t M, int64_t col0, int piece,
+                                                          int lane) {
+    const int row = CFG::RPI * piece + lane / CFG::SLOTS;
+    const int sl = lane % CFG::SLOTS;
+    const int seg = (sl >> 2) ^ (row & 3);
+    return X + (size_t)row * M + col0 + (seg * 4 + (sl & 3)) * 8;
+}
+// Fragment read offsets of a lane inside a stage.
+// X fragment (A operand, i = m): lane i = lane & 15 of group (lane >> 4): row 8*(lane>>5) + i/4 (+ 16 ks + 4 t2), columns
+// wcol (first column of the wave) + mi*32 + 16*((lane>>4)&1) + 4*(i&3)
+template <int ROWB, int A_BYTES> __device__ __forceinline__ int gm_x_frag_off(int wcol, int mi, int lane) {
+    const int i = lane & 15;
+    const int bytecol = (wcol + mi * 32 + 16 * ((lane >> 4) & 1) + 4 * (i & 3)) * 2;
+    const int seg = (bytecol >> 6) ^ (i >> 2);
+    return A_BYTES + (8 * (lane >> 5) + (i >> 2)) * ROWB + seg * 64 + (bytecol & 63);
+}
+// W fragment (B operand, j = r) of tile row `row`: 16-byte slot (2 ks + half) ^ ((row >> 2) & 3)
+__device__ __forceinline__ int gm_w_frag_off(int row, int ks, int half) {
+    return row * 64 + (((2 * ks + half) ^ ((row >> 2) & 3)) << 4);
+}
+// the X fragment at stage byte offset `off`: two 8-byte transpose reads (k 0-3 and k 4-7 of the lane's half)
+template <int ROWB> __device__ __forceinline__ gm_bf16x8 gm_x_frag(const unsigned char *st, int off) {
+    typedef gm_s16x4 __attribute__((address_space(3))) *lds_s16x4;
+    const gm_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(st + off));
+    const gm_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(st + off + 4 * ROWB));
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+// STATS: one group of four rounded outputs (p0, p1: two packed bf16 pairs) into a row tile's shifted sums.  Two elements
+// per VALU instruction (v_pk_add_f32 / v_pk_fma_f32): the statistics are VALU work the MFMAs wait for -- 4 instructions
+// per output element cost as much as the products themselves at K = 128.  `sh`: a REAL register pair made at the call
+// site (see conv1x1_gemm_kernel; tools/check_kernel_regs.py); the call sites keep their own register pins.
+__device__ __forceinline__ void gm_stats_add(unsigned p0, unsigned p1, const gm_f32x2 &sh, gm_f32x2 &sS, gm_f32x2 &sQ) {
+    const gm_f32x2 da = gm_f32x2{bf16_lo(p0), bf16_hi(p0)} - sh;
+    const gm_f32x2 db = gm_f32x2{bf16_lo(p1), bf16_hi(p1)} - sh;
+    sS += da;
+    sQ = __builtin_elementwise_fma(da, da, sQ);
+    sS += db;
+    sQ = __builtin_elementwise_fma(db, db, sQ);
+}
+// The partial of (row, view, range): three floats (S, Q, shift) of a shifted sum with S = 0, i.e. (0, M2, mean); row =
+// grp * Rg + r.  gm_stats_tail writes through this, gm_row_stats reads through it.
+template <typename T> __device__ __forceinline__ T *gm_part(T *part, size_t row, int views, int view, int P, int range) {
+    return part + (((size_t)row * views + view) * P + range) * 3;
+}
+// End of a STATS kernel.  Per row: this wave's (sum, sum of squares, shift) over its COLS-column share of every tile of the
+// range -> (count, mean, M2); the WM wave columns of the workgroup are merged through LDS (Chan, fixed order) so that the
+// consumer finds ONE partial per (row, range) -- its combine runs in every workgroup of the normalise pass.
+// wrow: the wave's first tile row; prow: grp * Rg + the tile's first row; rt_valid: the eight-wave tile can own 32-row
+// tiles beyond R; s_st: [WM][TR][2] floats (mean, M2) -- the ring, idle by now.
+template <int WM, int TR, int RT, int COLS>
+__device__ __forceinline__ void gm_stats_tail(float *s_st, const gm_f32x2 (&sS)[RT], const gm_f32x2 (&sQ)[RT],
+                                              const float (&sShift)[RT], const bool (&rt_valid)[RT], int ntile, int wm,
+                                              int wrow, int lane, float *__restrict__ part, size_t prow, int views,
+                                              int view, int P, int rloc) {
+    const int half = lane >> 5, l31 = lane & 31;
+    const float np = (float)COLS * (float)ntile;
+    __syncthreads();
+#pragma unroll
+    for (int ri = 0; ri < RT; ++ri) {
+        const float s1 = sS[ri].x + sS[ri].y, q1 = sQ[ri].x + sQ[ri].y;
+        const float s = s1 + __shfl_xor(s1, 32), q = q1 + __shfl_xor(q1, 32);
+        if (half == 0) {
+            const int row = wrow + ri * 32 + l31;
+            const float dm = s / np;
+            s_st[(wm * TR + row) * 2 + 0] = sShift[ri] + dm;
+            s_st[(wm * TR + row) * 2 + 1] = fmaxf(q - s * dm, 0.0f);
+        }
+    }
+    __syncthreads();
+    if (wm == 0 && half == 0) {
+#pragma unroll
+        for (int ri = 0; ri < RT; ++ri) {
+            const int row = wrow + ri * 32 + l31;
+            float n = 0.0f, mean = 0.0f, m2 = 0.0f;
+#pragma unroll
+            for (int w = 0; w < WM; ++w) gm_chan(n, mean, m2, np, s_st[(w * TR + row) * 2], s_st[(w * TR + row) * 2 + 1]);
+            if (rt_valid[ri]) {
+                float *pp = gm_part(part, prow + row, views, view, P, rloc);
+                pp[0] = 0.0f;
+                pp[1] = m2;
+                pp[2] = mean;
+            }
+        }
+    }
+}
+
 // CAT: the operand is the row-wise concatenation [X (K1 rows); X2 (K - K1 rows)] of two tensors (never materialised):
 // the data gradient of the first layer of a residual block takes the shortcut's gradient as extra operand rows
 // against an identity block of the weight, dX = [W^T | I] [dY; dZ] -- the sum is rounded once and the separate
@@ -188,16 +341,10 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::NW == 4 ? 2 : 1) void conv1x1_ge
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);          // scalar: everything derived stays in SGPRs
     const int wr = wave / CFG::WM, wm = wave % CFG::WM;
     const unsigned lds0 = (unsigned)(uintptr_t)(gm_lptr)smem;
-    const int logical = xcd_remap(blockIdx.x, nblocks);
-    const int rt = logical % row_tiles, range = logical / row_tiles;
-    const int view = range / ranges_view, rloc = range - view * ranges_view;
-    const int grp = blockIdx.z;
-    const int tile0 = rloc * tiles_range;
-    const int ntile = (tiles_range < col_tiles_view - tile0) ? tiles_range : col_tiles_view - tile0;
-    const int nch = K / GM_KC;
-    const int T = ntile * nch;
-    const int r0 = rt * CFG::TR;
-    const int64_t col0 = (int64_t)view * (M / views) + (int64_t)tile0 * TN;
+    const GemmRange own = gm_range(nblocks, row_tiles, ranges_view, tiles_range, col_tiles_view, M, views, TN);
+    const int view = own.view, rloc = own.rloc, ntile = own.ntile, grp = blockIdx.z;
+    const int nch = K / GM_KC, T = ntile * nch, r0 = own.rt * CFG::TR;
+    const int64_t col0 = own.col0;
     A += (size_t)grp * Rg * lda;
     X += (size_t)grp * K * M;
     Y += (size_t)grp * Rg * M;
@@ -208,10 +355,8 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::NW == 4 ? 2 : 1) void conv1x1_ge
     }
 
     // ---- the chunk's NI LDS-DMA instructions (1 KiB each: 64 lanes x 16 bytes; W rows first, then X rows) are dealt to
-    //      the waves round robin: this wave issues q = wave + j * NW.  LDS side lane-linear: stage + q KiB + lane * 16.
-    // W piece q < NA: rows 16q .. 16q+15 (64 B each); slot' = lane & 3 holds source slot slot' ^ ((row >> 2) & 3)
-    // X piece q - NA: RPI k-rows (ROWB bytes each); 16-byte slot s' = lane % SLOTS of its row holds source segment
-    //          (s' >> 2) ^ (row & 3) (low two bits of the 64-byte segment index), piece s' & 3
+    //      the waves round robin: this wave issues q = wave + j * NW: W piece q < NA (rows 16q .. 16q+15), X piece q - NA
+    //      (gm_w_src, gm_x_src)
     const unsigned short *src[PER], *src2[PER];
     bool is_w[PER];
     int my_dma = 0;
@@ -224,13 +369,9 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::NW == 4 ? 2 : 1) void conv1x1_ge
         if (is_w[j]) {
             int row = r0 + 16 * q + (lane >> 2);
             if (row > Rg - 1) row = Rg - 1;                  // rows beyond R: duplicates, never stored
-            const int slot = (lane & 3) ^ ((lane >> 4) & 3);
-            src[j] = A + (size_t)row * lda + slot * 8;
+            src[j] = gm_w_src(A, lda, row, lane);
         } else {
-            const int row = CFG::RPI * (q - CFG::NA) + lane / CFG::SLOTS;
-            const int sl = lane % CFG::SLOTS;
-            const int seg = (sl >> 2) ^ (row & 3);
-            src[j] = X + (size_t)row * M + col0 + (seg * 4 + (sl & 3)) * 8;
+            src[j] = gm_x_src<CFG>(X, M, col0, q - CFG::NA, lane);
             if (CAT) src2[j] = X2 + (src[j] - X);
         }
     }
@@ -259,26 +400,14 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::NW == 4 ? 2 : 1) void conv1x1_ge
         }
     };
 
-    // ---- fragment read offsets of this lane inside a stage ----
-    // X fragment (A operand, i = m): lane i = lane & 15 of group (lane >> 4): row 8*(lane>>5) + i/4 (+ 16 ks + 4 t2),
-    // columns wm*64 + mi*32 + 16*((lane>>4)&1) + 4*(i&3)
-    int xoff[2];
+    // ---- fragment read offsets of this lane inside a stage: the wave's columns wm*64 .., its rows wr*32*RT + ri*32 + l31
+    int xoff[2], woff[RT][2];
 #pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
-        const int i = lane & 15;
-        const int bytecol = (wm * 64 + mi * 32 + 16 * ((lane >> 4) & 1) + 4 * (i & 3)) * 2;
-        const int seg = (bytecol >> 6) ^ (i >> 2);
-        xoff[mi] = CFG::A_BYTES + (8 * half + (i >> 2)) * ROWB + seg * 64 + (bytecol & 63);
-    }
-    // W fragment (B operand, j = r): row wr*32*RT + ri*32 + l31, 16-byte slot (2 ks + half) ^ ((row >> 2) & 3)
-    int woff[RT][2];
+    for (int mi = 0; mi < 2; ++mi) xoff[mi] = gm_x_frag_off<ROWB, CFG::A_BYTES>(wm * 64, mi, lane);
 #pragma unroll
     for (int ri = 0; ri < RT; ++ri)
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const int row = wr * 32 * RT + ri * 32 + l31;
-            woff[ri][ks] = row * 64 + (((2 * ks + half) ^ ((row >> 2) & 3)) << 4);
-        }
+        for (int ks = 0; ks < 2; ++ks) woff[ri][ks] = gm_w_frag_off(wr * 32 * RT + ri * 32 + l31, ks, half);
 
     f32x16 acc[2][RT];
 #pragma unroll
@@ -355,13 +484,7 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::NW == 4 ? 2 : 1) void conv1x1_ge
         for (int ks = 0; ks < 2; ++ks) {
             gm_bf16x8 xa[2], wb[RT];
 #pragma unroll
-            for (int mi = 0; mi < 2; ++mi) {
-                const gm_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (gm_s16x4 __attribute__((address_space(3))) *)(st + xoff[mi] + ks * 16 * ROWB));
-                const gm_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (gm_s16x4 __attribute__((address_space(3))) *)(st + xoff[mi] + ks * 16 * ROWB + 4 * ROWB));
-                xa[mi] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-            }
+            for (int mi = 0; mi < 2; ++mi) xa[mi] = gm_x_frag<ROWB>(st, xoff[mi] + ks * 16 * ROWB);
             if (PRO) {
                 // normalise + activate the fragment IN REGISTERS: its 8 elements are 8 consecutive operand rows
                 // (16 ks + 8 half + 0..7) of the lane's column, so the 8 (scale, shift) pairs are the same for a whole
@@ -381,8 +504,7 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::NW == 4 ? 2 : 1) void conv1x1_ge
                         float lo = bf16_lo(w[d]), hi = bf16_hi(w[d]);
                         lo = __builtin_fmaf(lo, t4[d].x, t4[d].y);
                         hi = __builtin_fmaf(hi, t4[d].z, t4[d].w);
-                        if (pro_act == 1) { lo = relu_keep_nan(lo); hi = relu_keep_nan(hi); }
-                        else if (pro_act == 2) { lo = lo > 0.f ? lo : lo * pro_slope; hi = hi > 0.f ? hi : hi * pro_slope; }
+                        act_fwd_pair(lo, hi, pro_act, pro_slope);
                         w[d] = pack_bf16(lo, hi);
                     }
                     xa[mi] = __builtin_bit_cast(gm_bf16x8, w);
@@ -445,23 +567,15 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::NW == 4 ? 2 : 1) void conv1x1_ge
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) {
                                     v[e] = __builtin_fmaf(v[e], esc[ri].x, esc[ri].y);
+                                    // act_fwd_pair (common.h), spelled out: through it the EPI kernels take 2 ... 7 more
+                                    // VGPRs (L: 230 -> 237)
                                     if (epi_act == 1) v[e] = relu_keep_nan(v[e]);
                                     else if (epi_act == 2) v[e] = v[e] > 0.f ? v[e] : v[e] * epi_slope;
                                 }
                                 p0 = pack_bf16(v[0], v[1]);
                                 p1 = pack_bf16(v[2], v[3]);
                             }
-                            if (STATS) {
-                                // two elements per VALU instruction (v_pk_add_f32 / v_pk_fma_f32): the statistics
-                                // are VALU work the MFMAs wait for -- 4 instructions per output element cost as
-                                // much as the products themselves at K = 128
-                                const gm_f32x2 da = gm_f32x2{bf16_lo(p0), bf16_hi(p0)} - sh;
-                                const gm_f32x2 db = gm_f32x2{bf16_lo(p1), bf16_hi(p1)} - sh;
-                                sS[ri] += da;
-                                sQ[ri] = __builtin_elementwise_fma(da, da, sQ[ri]);
-                                sS[ri] += db;
-                                sQ[ri] = __builtin_elementwise_fma(db, db, sQ[ri]);
-                            }
+                            if (STATS) gm_stats_add(p0, p1, sh, sS[ri], sQ[ri]);
                             pk0[mi][rg] = p0;
                             pk1[mi][rg] = p1;
 #pragma unroll
@@ -508,66 +622,35 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::NW == 4 ? 2 : 1) void conv1x1_ge
         for (int j = D; j > 0; --j) st_hist[j] = st_hist[j - 1];
         st_hist[0] = stored_now;
     }
-    if (STATS) {
-        // per row: this wave's (sum, sum of squares, shift) over its 64-column share of every tile of the range ->
-        // (count, mean, M2); the WM wave columns of the workgroup are merged through LDS (Chan, fixed order) so that the
-        // consumer finds ONE partial per (row, range) -- its combine runs in every workgroup of the normalise pass
-        float *s_st = reinterpret_cast<float *>(smem);                  // [WM][TR][2] (mean, M2): the ring is idle now
-        const float np = 64.0f * (float)ntile;
-        __syncthreads();
-#pragma unroll
-        for (int ri = 0; ri < RT; ++ri) {
-            const float s1 = sS[ri].x + sS[ri].y, q1 = sQ[ri].x + sQ[ri].y;
-            const float s = s1 + __shfl_xor(s1, 32), q = q1 + __shfl_xor(q1, 32);
-            if (half == 0) {
-                const int row = wr * 32 * RT + ri * 32 + l31;
-                const float dm = s / np;
-                s_st[(wm * CFG::TR + row) * 2 + 0] = sShift[ri] + dm;
-                s_st[(wm * CFG::TR + row) * 2 + 1] = fmaxf(q - s * dm, 0.0f);
-            }
-        }
-        __syncthreads();
-        if (wm == 0 && half == 0) {
-#pragma unroll
-            for (int ri = 0; ri < RT; ++ri) {
-                const int row = wr * 32 * RT + ri * 32 + l31;
-                float n = 0.0f, mean = 0.0f, m2 = 0.0f;
-#pragma unroll
-                for (int w = 0; w < CFG::WM; ++w)
-                    gm_chan(n, mean, m2, np, s_st[(w * CFG::TR + row) * 2], s_st[(w * CFG::TR + row) * 2 + 1]);
-                const int r = r0 + row;
-                if (rt_valid[ri]) {
-                    float *pp = part + ((((size_t)grp * Rg + r) * views + view) * P + rloc) * 3;
-                    pp[0] = 0.0f;                                       // (S, Q, shift) with S = 0: mean = shift, M2 = Q
-                    pp[1] = m2;
-                    pp[2] = mean;
-                }
-            }
-        }
-    }
+    if (STATS)       // the ring is idle now: its first bytes take the merge
+        gm_stats_tail<CFG::WM, CFG::TR, RT, 64>(reinterpret_cast<float *>(smem), sS, sQ, sShift, rt_valid, ntile, wm,
+                                                wr * 32 * RT, lane, part, (size_t)grp * Rg + r0, views, view, P, rloc);
 }
 
 }  // namespace grafp
 #include "gemm_xl.h"
 namespace grafp {
 
-// Statistics of row c, view v from the P partials of the GEMM (n_p columns each): Chan's combination of
-// (count, mean, M2) in a fixed order (lane-strided partials, then a 6-step butterfly: deterministic) -> mean, invstd
-// saved for backward; (scale, shift) for the affine kernel / the next GEMM's PRO: z = act(y * scale + shift); running
-// statistics advance once per view, in order.  One workgroup per row, one wave per view.  f32 is enough here: the
-// partials are already centred on a sample of their own row, and the combination never subtracts large numbers.
-// (count, mean, M2) of row c, view v from its P partials: every lane of the calling WAVE returns the same values
-__device__ __forceinline__ void gm_row_stats(const float *__restrict__ part, int c, int v, int views, int P, int wm,
-                                             int tiles_range, int col_tiles_view, int lane, float &n, float &mean,
-                                             float &m2) {
+// BatchNorm from the GEMM's partials.  gm_row_stats: (count, mean, M2) of row c, view v from its P partials (one per column
+// range), Chan's combination in a fixed order (lane-strided partials, then a 6-step butterfly: deterministic); every lane
+// of the calling WAVE returns the same values.  f32 is enough here: the partials are already centred on a sample of
+// their own row, and the combination never subtracts large numbers.  From those gm_bn_point makes mean and invstd (saved
+// for backward) and (scale, shift) for the affine kernel / the next GEMM's PRO: z = act(y * scale + shift);
+// gm_running_update advances the running statistics once per view, in order.
+struct BnStatsArgs {            // what a training-mode finalizer takes (bn_finalize_kernel, bn_affine_bf16_kernel<true>)
+    const float *part, *pre_bias, *gamma, *beta;
+    float *running_mean, *running_var, *save_mean, *save_invstd;
+    float2 *tab;
+    int P, wm, tiles_range, col_tiles_view;
+    float eps, momentum;
+};
+__device__ __forceinline__ void gm_row_stats(const BnStatsArgs &st, int c, int v, int views, int lane, float &n,
+                                             float &mean, float &m2) {
     n = 0.0f, mean = 0.0f, m2 = 0.0f;
-    for (int p = lane; p < P; p += 64) {
-        const float *pp = part + (((size_t)c * views + v) * P + p) * 3;
-        const int range = p;                 // one partial per column range (the workgroup merged its wave columns)
-        const int tiles = (tiles_range < col_tiles_view - range * tiles_range) ? tiles_range
-                                                                               : col_tiles_view - range * tiles_range;
-        const float np = (float)wm * 64.0f * tiles, S = pp[0], Q = pp[1], sh = pp[2];
-        const float dm = S / np;
+    for (int p = lane; p < st.P; p += 64) {
+        const float *pp = gm_part(st.part, c, views, v, st.P, p);
+        const float np = (float)st.wm * 64.0f * gm_range_tiles(p, st.tiles_range, st.col_tiles_view);
+        const float S = pp[0], Q = pp[1], sh = pp[2], dm = S / np;
         gm_chan(n, mean, m2, np, sh + dm, fmaxf(Q - S * dm, 0.0f));
     }
 #pragma unroll
@@ -582,39 +665,51 @@ __device__ __forceinline__ void gm_row_stats(const float *__restrict__ part, int
         }
     }
 }
+// (scale, shift) of a row whose statistics are mean (conv bias pb included or not: `mean` is what is subtracted) and invstd
+__device__ __forceinline__ float2 gm_bn_tab(float mean, float invstd, float pb, float gamma, float beta) {
+    const float g = gamma * invstd;
+    return make_float2(g, beta + (pb - mean) * g);
+}
+struct BnPoint {
+    float meanf, invstd, unbiased;              // mean of y + conv bias; 1 / sqrt(var + eps); variance for the running one
+    float2 tab;
+};
+__device__ __forceinline__ BnPoint gm_bn_point(float n, float mean, float m2, float pb, float gamma, float beta, float eps,
+                                               int64_t Mg) {
+    BnPoint b;
+    const float var = fmaxf(m2 / n, 0.0f);
+    b.meanf = mean + pb;                                            // statistics of y + conv bias
+    b.invstd = 1.0f / sqrtf(var + eps);
+    b.tab = gm_bn_tab(b.meanf, b.invstd, pb, gamma, beta);
+    b.unbiased = Mg > 1 ? m2 / (n - 1.0f) : var;
+    return b;
+}
+// s_stat[u] = (meanf, unbiased variance) of view u
+__device__ __forceinline__ void gm_running_update(const BnStatsArgs &st, int c, const float2 *s_stat, int views) {
+    float rm = st.running_mean[c], rv = st.running_var[c];
+    for (int u = 0; u < views; ++u) {
+        rm = (1.0f - st.momentum) * rm + st.momentum * s_stat[u].x;
+        rv = (1.0f - st.momentum) * rv + st.momentum * s_stat[u].y;
+    }
+    st.running_mean[c] = rm;
+    st.running_var[c] = rv;
+}
 
-__global__ __launch_bounds__(512) void bn_finalize_kernel(const float *__restrict__ part, int C, int views, int P,
-                                                          int wm, int tiles_range, int col_tiles_view, int64_t Mg,
-                                                          const float *__restrict__ pre_bias,
-                                                          const float *__restrict__ gamma, const float *__restrict__ beta,
-                                                          float eps, float momentum, float *__restrict__ running_mean,
-                                                          float *__restrict__ running_var, float *__restrict__ save_mean,
-                                                          float *__restrict__ save_invstd, float2 *__restrict__ tab) {
+// one workgroup per row, one wave per view
+__global__ __launch_bounds__(512) void bn_finalize_kernel(BnStatsArgs st, int views, int64_t Mg) {
     __shared__ float2 s_stat[8];                 // (mean + bias, unbiased variance) per view
     const int c = blockIdx.x, lane = threadIdx.x & 63, v = threadIdx.x >> 6;
-    const float pb = pre_bias ? pre_bias[c] : 0.0f;
     float n, mean, m2;
-    gm_row_stats(part, c, v, views, P, wm, tiles_range, col_tiles_view, lane, n, mean, m2);
+    gm_row_stats(st, c, v, views, lane, n, mean, m2);
     if (lane == 0) {
-        const float var = fmaxf(m2 / n, 0.0f);
-        const float meanf = mean + pb;                              // statistics of y + conv bias
-        const float invstd = 1.0f / sqrtf(var + eps);
-        save_mean[c * views + v] = meanf;
-        save_invstd[c * views + v] = invstd;
-        const float g = gamma[c] * invstd;
-        tab[(size_t)c * views + v] = make_float2(g, beta[c] + (pb - meanf) * g);
-        s_stat[v] = make_float2(meanf, Mg > 1 ? m2 / (n - 1.0f) : var);
+        const BnPoint b = gm_bn_point(n, mean, m2, st.pre_bias ? st.pre_bias[c] : 0.0f, st.gamma[c], st.beta[c], st.eps, Mg);
+        st.save_mean[c * views + v] = b.meanf;
+        st.save_invstd[c * views + v] = b.invstd;
+        st.tab[(size_t)c * views + v] = b.tab;
+        s_stat[v] = make_float2(b.meanf, b.unbiased);
     }
     __syncthreads();
-    if (threadIdx.x == 0 && running_mean) {
-        float rm = running_mean[c], rv = running_var[c];
-        for (int u = 0; u < views; ++u) {
-            rm = (1.0f - momentum) * rm + momentum * s_stat[u].x;
-            rv = (1.0f - momentum) * rv + momentum * s_stat[u].y;
-        }
-        running_mean[c] = rm;
-        running_var[c] = rv;
-    }
+    if (threadIdx.x == 0 && st.running_mean) gm_running_update(st, c, s_stat, views);
 }
 
 // eval mode: (scale, shift) from the running statistics
@@ -628,21 +723,13 @@ __global__ __launch_bounds__(64) void bn_eval_tab_kernel(int C, int views, const
     if (c >= C) return;
     const float pb = pre_bias ? pre_bias[c] : 0.0f;
     const float mean = running_mean[c], invstd = 1.0f / sqrtf(running_var[c] + eps);
-    const float g = gamma[c] * invstd;
+    const float2 t = gm_bn_tab(mean, invstd, pb, gamma[c], beta[c]);
     for (int v = 0; v < views; ++v) {
         save_mean[c * views + v] = mean;
         save_invstd[c * views + v] = invstd;
-        tab[(size_t)c * views + v] = make_float2(g, beta[c] + (pb - mean) * g);
+        tab[(size_t)c * views + v] = t;
     }
 }
-
-struct BnStatsArgs {            // what bn_finalize_kernel takes, for the affine kernel that finalises by itself
-    const float *part, *pre_bias, *gamma, *beta;
-    float *running_mean, *running_var, *save_mean, *save_invstd;
-    float2 *tab;
-    int P, wm, tiles_range, col_tiles_view;
-    float eps, momentum;
-};
 
 // z = act(y * scale + shift) [+ residual] over rows of bf16 (C, M); 4 x 16-byte vectors in flight per thread.
 // STATS: no table comes in -- every workgroup combines the GEMM's partial sums of its (row, view) itself (one wave, a
@@ -680,35 +767,23 @@ __global__ __launch_bounds__(256) void bn_affine_bf16_kernel(const unsigned shor
         const bool row_leader = s == 0;                       // view 0, chunk 0: also owns the running statistics
         const int vv = row_leader ? wave : v;                 // the leader's waves take one view each
         if (row_leader ? wave < views : wave == 0) {
-            const float pb = st.pre_bias ? st.pre_bias[c] : 0.0f;
             float n, mean, m2;
-            gm_row_stats(st.part, c, vv, views, st.P, st.wm, st.tiles_range, st.col_tiles_view, lane, n, mean, m2);
+            gm_row_stats(st, c, vv, views, lane, n, mean, m2);
             if (lane == 0) {
-                const float var = fmaxf(m2 / n, 0.0f);
-                const float meanf = mean + pb;
-                const float invstd = 1.0f / sqrtf(var + st.eps);
-                const float g = st.gamma[c] * invstd;
-                const float2 t = make_float2(g, st.beta[c] + (pb - meanf) * g);
-                if (vv == v) s_ss = t;
-                if (row_leader) s_stat[vv] = make_float2(meanf, Mg > 1 ? m2 / (n - 1.0f) : var);
+                const BnPoint b =
+                    gm_bn_point(n, mean, m2, st.pre_bias ? st.pre_bias[c] : 0.0f, st.gamma[c], st.beta[c], st.eps, Mg);
+                if (vv == v) s_ss = b.tab;
+                if (row_leader) s_stat[vv] = make_float2(b.meanf, b.unbiased);
                 if (sl == 0 && vv == v) {
-                    st.save_mean[c * views + v] = meanf;
-                    st.save_invstd[c * views + v] = invstd;
-                    st.tab[(size_t)c * views + v] = t;
+                    st.save_mean[c * views + v] = b.meanf;
+                    st.save_invstd[c * views + v] = b.invstd;
+                    st.tab[(size_t)c * views + v] = b.tab;
                 }
             }
         }
         __syncthreads();
         ss = s_ss;
-        if (row_leader && tid == 0 && st.running_mean) {
-            float rm = st.running_mean[c], rv = st.running_var[c];
-            for (int u = 0; u < views; ++u) {
-                rm = (1.0f - st.momentum) * rm + st.momentum * s_stat[u].x;
-                rv = (1.0f - st.momentum) * rv + st.momentum * s_stat[u].y;
-            }
-            st.running_mean[c] = rm;
-            st.running_var[c] = rv;
-        }
+        if (row_leader && tid == 0 && st.running_mean) gm_running_update(st, c, s_stat, views);
     } else {
         ss = tab[(size_t)c * views + v];
     }
@@ -719,6 +794,8 @@ __global__ __launch_bounds__(256) void bn_affine_bf16_kernel(const unsigned shor
         for (int e = 0; e < 4; ++e) {
             float a = __builtin_fmaf(bf16_lo(w[e]), ss.x, ss.y);
             float b = __builtin_fmaf(bf16_hi(w[e]), ss.x, ss.y);
+            // act_fwd_pair (common.h), spelled out: through it hipcc 7.2 lays this kernel's loops out differently (as for
+            // the store below)
             if (act == 1) { a = relu_keep_nan(a); b = relu_keep_nan(b); }
             else if (act == 2) { a = a > 0.f ? a : a * slope; b = b > 0.f ? b : b * slope; }
             if (rrow) { a += bf16_lo(q[e]); b += bf16_hi(q[e]); }
@@ -742,6 +819,14 @@ __global__ __launch_bounds__(256) void bn_affine_bf16_kernel(const unsigned shor
         const uint4 ar = rrow ? *reinterpret_cast<const uint4 *>(rrow + m) : make_uint4(0, 0, 0, 0);
         one(ax, ar, orow + m);
     }
+}
+
+// the partials' geometry from the plan of the launch that wrote them + the caller's arrays
+static BnStatsArgs bn_stats_args(const GemmPlan &p, const float *part, const float *pre_bias, const float *gamma,
+                                 const float *beta, float eps, float momentum, float *running_mean, float *running_var,
+                                 float *save_mean, float *save_invstd, float *tab) {
+    return {part, pre_bias, gamma, beta, running_mean, running_var, save_mean, save_invstd, (float2 *)tab,
+            p.P,  p.wm,     p.tiles_range, p.col_tiles_view, eps, momentum};
 }
 
 static bool gemm_shape_ok(int R, int K, int groups, int64_t M, int views) {
@@ -775,92 +860,97 @@ extern "C" int grafp_conv1x1_gemm_plan(int R, int K, int groups, int64_t M, int 
 
 namespace grafp {
 struct GemmArgs {
+    const unsigned short *w = nullptr, *x = nullptr, *x2 = nullptr;      // x2: CAT, operand rows K1 .. K - 1
+    unsigned short *y = nullptr;
     bool out_f32 = false;                        // y: R x M floats (split-bf16 product of the f32 mode; concatenated operands)
-    const unsigned short *w, *x, *x2;
-    unsigned short *y;
-    int lda, K1;
-    int64_t M;
-    int Rg, Kg, groups, views;
-    const float2 *pro_tab;
-    int pro_act;
-    float pro_slope;
-    float *part;
-    const float2 *epi_tab = nullptr;
-    int epi_act = 0;
-    float epi_slope = 0.0f;
+    int lda = 0, K1 = 0, Rg = 0, Kg = 0, groups = 1, views = 1;
+    int64_t M = 0;
+    const float2 *pro_tab = nullptr, *epi_tab = nullptr;
+    int pro_act = 0, epi_act = 0;
+    float pro_slope = 0.0f, epi_slope = 0.0f;
+    float *part = nullptr;
 };
+// the part every entry point fills the same way; the forms (x2 / K1, pro_*, part, epi_*, out_f32) are the entry's own
+static GemmArgs gemm_args(const void *w, const void *x, void *y, int R, int K, int groups, int64_t M, int views) {
+    GemmArgs a;
+    a.w = (const unsigned short *)w; a.x = (const unsigned short *)x; a.y = (unsigned short *)y;
+    a.lda = a.Kg = K / groups; a.Rg = R / groups; a.groups = groups; a.M = M; a.views = views;
+    return a;
+}
+// The checks of every entry point, in their order, under the entry's name `who`: pointers, shape (`shape`: the entry's own
+// description of it, printf-style), alignment of the OR of the operand addresses, activation code.
+#define GM_ALIGNED "operands must be 16-byte aligned"
+__attribute__((format(printf, 7, 8)))
+static int gemm_check(const char *who, bool ptrs, uintptr_t addr, const char *aligned, int act, bool shape_ok,
+                      const char *shape, ...) {
+    GRAFP_REQUIRE(ptrs, "%s: null pointer", who);
+    if (!shape_ok) {
+        char text[256];
+        va_list ap;
+        va_start(ap, shape);
+        vsnprintf(text, sizeof text, shape, ap);
+        va_end(ap);
+        GRAFP_REQUIRE(false, "%s: unsupported shape %s", who, text);
+    }
+    GRAFP_REQUIRE((addr & 15) == 0, "%s: %s", who, aligned);
+    GRAFP_REQUIRE(act >= 0 && act <= 2, "%s: bad activation %d", who, act);
+    return GRAFP_OK;
+}
+
 template <typename CFG, int NS, bool PRO, bool STATS, bool CAT, bool EPI = false, bool OUTF32 = false>
 static void gemm_launch(const GemmPlan &p, const GemmArgs &a, hipStream_t s) {
     const size_t lds = (size_t)NS * CFG::STAGE + CFG::NW * CFG::OUT_BYTES + (PRO ? (size_t)a.Kg * 8 : 0);
-    (void)hipFuncSetAttribute((const void *)conv1x1_gemm_kernel<CFG, NS, PRO, STATS, CAT, EPI, OUTF32>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((conv1x1_gemm_kernel<CFG, NS, PRO, STATS, CAT, EPI, OUTF32>), dim3(p.nblocks, 1, a.groups),
-                       dim3(CFG::THREADS), lds, s, a.w, a.lda, a.x, a.y, a.M, a.Rg, a.Kg, p.row_tiles, p.ranges_view,
-                       p.tiles_range, p.col_tiles_view, a.views, a.pro_tab, a.pro_act, a.pro_slope, a.part, p.P, p.nblocks,
-                       a.x2, a.K1, a.epi_tab, a.epi_act, a.epi_slope);
+    gm_launch(conv1x1_gemm_kernel<CFG, NS, PRO, STATS, CAT, EPI, OUTF32>, dim3(p.nblocks, 1, a.groups), CFG::THREADS, lds, s,
+              a.w, a.lda, a.x, a.y, a.M, a.Rg, a.Kg, p.row_tiles, p.ranges_view, p.tiles_range, p.col_tiles_view, a.views,
+              a.pro_tab, a.pro_act, a.pro_slope, a.part, p.P, p.nblocks, a.x2, a.K1, a.epi_tab, a.epi_act, a.epi_slope);
 }
 template <bool STATS, bool CAT, bool EPI, int ABL = 0>
 static void gemm_launch_xl(const GemmPlan &p, const GemmArgs &a, hipStream_t s) {
-    (void)hipFuncSetAttribute((const void *)conv1x1_gemm_xl_kernel<STATS, CAT, EPI, ABL>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)GemmXL::LDS);
-    hipLaunchKernelGGL((conv1x1_gemm_xl_kernel<STATS, CAT, EPI, ABL>), dim3(p.nblocks, 1, a.groups), dim3(GemmXL::THREADS),
-                       GemmXL::LDS, s, a.w, a.lda, a.x, a.y, a.M, a.Rg, a.Kg, p.row_tiles, p.ranges_view, p.tiles_range,
-                       p.col_tiles_view, a.views, a.part, p.P, p.nblocks, a.x2, a.K1, a.epi_tab, a.epi_act, a.epi_slope);
+    gm_launch(conv1x1_gemm_xl_kernel<STATS, CAT, EPI, ABL>, dim3(p.nblocks, 1, a.groups), GemmXL::THREADS, GemmXL::LDS, s,
+              a.w, a.lda, a.x, a.y, a.M, a.Rg, a.Kg, p.row_tiles, p.ranges_view, p.tiles_range, p.col_tiles_view, a.views,
+              a.part, p.P, p.nblocks, a.x2, a.K1, a.epi_tab, a.epi_act, a.epi_slope);
 }
-// plain / statistics / concatenated-operand forms of one tile configuration
-template <typename CFG, int NS> static void gemm_launch_cfg(const GemmPlan &p, const GemmArgs &a, hipStream_t s) {
-    if (a.out_f32) gemm_launch<CFG, NS, false, false, true, false, true>(p, a, s);
+#ifdef GRAFP_MEASURE
+// tools/gemm_bench.py --abl: the ablated statistics forms of the four-wave tile, GRAFP_XL_ABL = one of the list
+template <int... ABL>
+static bool gemm_launch_xl_abl(std::integer_sequence<int, ABL...>, int abl, const GemmPlan &p, const GemmArgs &a,
+                               hipStream_t s) {
+    return ((abl == ABL && (gemm_launch_xl<true, false, false, ABL>(p, a, s), true)) || ...);
+}
+#endif
+// the variant of one tile configuration that the arguments ask for: normalise-on-load (with or without statistics), f32
+// output, affine epilogue, concatenated operand, statistics, plain
+template <typename CFG> static void gemm_launch_variant(CFG, const GemmPlan &p, const GemmArgs &a, hipStream_t s) {
+    constexpr int NS = CFG::NS, NP = CFG::NS_PRO;
+    if (a.pro_tab && a.part) gemm_launch<CFG, NP, true, true, false>(p, a, s);
+    else if (a.pro_tab) gemm_launch<CFG, NP, true, false, false>(p, a, s);
+    else if (a.out_f32) gemm_launch<CFG, NS, false, false, true, false, true>(p, a, s);
     else if (a.epi_tab) gemm_launch<CFG, NS, false, false, false, true>(p, a, s);
     else if (a.x2) gemm_launch<CFG, NS, false, false, true>(p, a, s);
     else if (a.part) gemm_launch<CFG, NS, false, true, false>(p, a, s);
     else gemm_launch<CFG, NS, false, false, false>(p, a, s);
 }
-static void gemm_dispatch(const GemmPlan &p, const GemmArgs &a, hipStream_t s) {
-    if (a.pro_tab) {                                  // normalise-on-load: three stages beside the table
-#define GM_PRO(CFG)                                                        \
-    do {                                                                   \
-        if (a.part) gemm_launch<CFG, 3, true, true, false>(p, a, s);       \
-        else gemm_launch<CFG, 3, true, false, false>(p, a, s);             \
-    } while (0)
-        switch (p.cfg) {
-        case GM_CFG_XL:                                  // (no normalise-on-load form of the four-wave tile: same tile grid)
-        case GM_CFG_L: GM_PRO(GemmL); break;
-        case GM_CFG_N32: GM_PRO(GemmN32); break;
-        case GM_CFG_N64: GM_PRO(GemmN64); break;
-        case GM_CFG_N128: GM_PRO(GemmN128); break;
-        default: GM_PRO(GemmS); break;
-        }
-#undef GM_PRO
-        return;
-    }
-    switch (p.cfg) {
-    case GM_CFG_XL:
+static void gemm_launch_variant(GemmXL, const GemmPlan &p, const GemmArgs &a, hipStream_t s) {
 #ifdef GRAFP_MEASURE
-        switch (a.part && !a.x2 && !a.epi_tab ? GRAFP_TUNE_INT("GRAFP_XL_ABL", 0) : 0) {      // tools/gemm_bench.py --abl
-        case 1: gemm_launch_xl<true, false, false, 1>(p, a, s); return;
-        case 2: gemm_launch_xl<true, false, false, 2>(p, a, s); return;
-        case 3: gemm_launch_xl<true, false, false, 3>(p, a, s); return;
-        case 5: gemm_launch_xl<true, false, false, 5>(p, a, s); return;
-        case 7: gemm_launch_xl<true, false, false, 7>(p, a, s); return;
-        case 8: gemm_launch_xl<true, false, false, 8>(p, a, s); return;
-        case 10: gemm_launch_xl<true, false, false, 10>(p, a, s); return;
-        case 11: gemm_launch_xl<true, false, false, 11>(p, a, s); return;
-        case 13: gemm_launch_xl<true, false, false, 13>(p, a, s); return;
-        case 14: gemm_launch_xl<true, false, false, 14>(p, a, s); return;
-        default: break;
-        }
+    if (a.part && !a.x2 && gemm_launch_xl_abl(std::integer_sequence<int, 1, 2, 3, 5, 7, 8, 10, 11, 13, 14>{},
+                                              GRAFP_TUNE_INT("GRAFP_XL_ABL", 0), p, a, s))
+        return;
 #endif
-        if (a.epi_tab || a.out_f32) gemm_launch_cfg<GemmL, 4>(p, a, s);   // affine epilogue, f32 output: the eight-wave tile (same grid)
-        else if (a.x2) gemm_launch_xl<false, true, false>(p, a, s);
-        else if (a.part) gemm_launch_xl<true, false, false>(p, a, s);
-        else gemm_launch_xl<false, false, false>(p, a, s);
-        break;
-    case GM_CFG_L: gemm_launch_cfg<GemmL, 4>(p, a, s); break;       // four stages = all 160 KB (-2.7 % against three)
-    case GM_CFG_N32: gemm_launch_cfg<GemmN32, 4>(p, a, s); break;
-    case GM_CFG_N64: gemm_launch_cfg<GemmN64, 4>(p, a, s); break;
-    case GM_CFG_N128: gemm_launch_cfg<GemmN128, 3>(p, a, s); break;
-    default: gemm_launch_cfg<GemmS, 4>(p, a, s); break;
-    }
+    if (a.x2) gemm_launch_xl<false, true, false>(p, a, s);
+    else if (a.part) gemm_launch_xl<true, false, false>(p, a, s);
+    else gemm_launch_xl<false, false, false>(p, a, s);
+}
+// plan, launch, launch check (`what` names the kernel in the error text)
+static int gemm_run(const GemmArgs &a, const char *what, grafp_stream_t stream) {
+    const GemmPlan p = gemm_plan(a.Rg, a.Kg, a.groups, a.M, a.views);
+    const GemmTile &t = gm_tiles[p.cfg];
+    GRAFP_REQUIRE(!a.pro_tab || p.cfg != GM_CFG_N128 || a.Kg <= 1024, "conv1x1_gemm: normalise-on-load with <= 128 output rows takes at most 1024 operand rows");
+    // a form the plan's tile does not have (the four-wave tile: normalise-on-load, affine epilogue, f32 output) runs on
+    // the eight-wave L tile: the same 256 x 256 tile grid
+    const bool missing = (a.pro_tab && !t.pro) || (a.epi_tab && !t.epi) || (a.out_f32 && !t.outf32);
+    gm_visit(missing ? GM_CFG_L : p.cfg, [&](auto tile) { gemm_launch_variant(tile, p, a, (hipStream_t)stream); });
+    GRAFP_CHECK_LAUNCH(what);
+    return GRAFP_OK;
 }
 }  // namespace grafp
 
@@ -868,61 +958,40 @@ extern "C" int grafp_conv1x1_gemm_bf16(const void *w, const void *x, int R, int 
                                        const float *pro_tab, int pro_act, float pro_slope, void *y, float *stats_part,
                                        grafp_stream_t stream) {
     using namespace grafp;
-    GRAFP_REQUIRE(w && x && y, "conv1x1_gemm: null pointer");
-    GRAFP_REQUIRE(gemm_shape_ok(R, K, groups, M, views),
-                  "conv1x1_gemm: unsupported shape R=%d K=%d groups=%d M=%lld views=%d (rows per group %% 32, K per "
-                  "group %% 32, columns per view %% 128)", R, K, groups, (long long)M, views);
-    GRAFP_REQUIRE((((uintptr_t)w | (uintptr_t)x | (uintptr_t)y) & 15) == 0, "conv1x1_gemm: operands must be 16-byte aligned");
-    GRAFP_REQUIRE(pro_act >= 0 && pro_act <= 2, "conv1x1_gemm: bad activation %d", pro_act);
-    const int Rg = R / groups, Kg = K / groups;
-    const GemmPlan p = gemm_plan(Rg, Kg, groups, M, views);
-    GRAFP_REQUIRE(!pro_tab || p.cfg != GM_CFG_N128 || Kg <= 1024, "conv1x1_gemm: normalise-on-load with <= 128 output rows takes at most 1024 operand rows");
-    GemmArgs a;
-    a.w = (const unsigned short *)w; a.x = (const unsigned short *)x; a.x2 = nullptr; a.y = (unsigned short *)y;
-    a.lda = Kg; a.K1 = 0; a.M = M; a.Rg = Rg; a.Kg = Kg; a.groups = groups; a.views = views;
+    if (int rc = gemm_check("conv1x1_gemm", w && x && y, (uintptr_t)w | (uintptr_t)x | (uintptr_t)y, GM_ALIGNED, pro_act,
+                            gemm_shape_ok(R, K, groups, M, views),
+                            "R=%d K=%d groups=%d M=%lld views=%d (rows per group %% 32, K per group %% 32, columns per "
+                            "view %% 128)", R, K, groups, (long long)M, views))
+        return rc;
+    GemmArgs a = gemm_args(w, x, y, R, K, groups, M, views);
     a.pro_tab = (const float2 *)pro_tab; a.pro_act = pro_act; a.pro_slope = pro_slope; a.part = stats_part;
-    gemm_dispatch(p, a, (hipStream_t)stream);
-    GRAFP_CHECK_LAUNCH("conv1x1_gemm_kernel");
-    return GRAFP_OK;
+    return gemm_run(a, "conv1x1_gemm_kernel", stream);
 }
 
 extern "C" int grafp_conv1x1_gemm_affine_bf16(const void *w, const void *x, int R, int K, int groups, int64_t M, int views,
                                               const float *tab, int act, float slope, void *z, grafp_stream_t stream) {
     using namespace grafp;
-    GRAFP_REQUIRE(w && x && z && tab, "conv1x1_gemm_affine: null pointer");
-    GRAFP_REQUIRE(gemm_shape_ok(R, K, groups, M, views), "conv1x1_gemm_affine: unsupported shape R=%d K=%d groups=%d M=%lld "
-                  "views=%d", R, K, groups, (long long)M, views);
-    GRAFP_REQUIRE((((uintptr_t)w | (uintptr_t)x | (uintptr_t)z) & 15) == 0, "conv1x1_gemm_affine: operands must be 16-byte aligned");
-    GRAFP_REQUIRE(act >= 0 && act <= 2, "conv1x1_gemm_affine: bad activation %d", act);
-    const int Rg = R / groups, Kg = K / groups;
-    const GemmPlan p = gemm_plan(Rg, Kg, groups, M, views);
-    GemmArgs a;
-    a.w = (const unsigned short *)w; a.x = (const unsigned short *)x; a.x2 = nullptr; a.y = (unsigned short *)z;
-    a.lda = Kg; a.K1 = 0; a.M = M; a.Rg = Rg; a.Kg = Kg; a.groups = groups; a.views = views;
-    a.pro_tab = nullptr; a.pro_act = 0; a.pro_slope = 0.0f; a.part = nullptr;
+    if (int rc = gemm_check("conv1x1_gemm_affine", w && x && z && tab, (uintptr_t)w | (uintptr_t)x | (uintptr_t)z,
+                            GM_ALIGNED, act, gemm_shape_ok(R, K, groups, M, views), "R=%d K=%d groups=%d M=%lld views=%d",
+                            R, K, groups, (long long)M, views))
+        return rc;
+    GemmArgs a = gemm_args(w, x, z, R, K, groups, M, views);
     a.epi_tab = (const float2 *)tab; a.epi_act = act; a.epi_slope = slope;
-    gemm_dispatch(p, a, (hipStream_t)stream);
-    GRAFP_CHECK_LAUNCH("conv1x1_gemm_kernel (affine epilogue)");
-    return GRAFP_OK;
+    return gemm_run(a, "conv1x1_gemm_kernel (affine epilogue)", stream);
 }
 
 extern "C" int grafp_conv1x1_gemm_cat_bf16(const void *w, const void *x1, int K1, const void *x2, int K2, int R, int64_t M,
                                            void *y, grafp_stream_t stream) {
     using namespace grafp;
-    GRAFP_REQUIRE(w && x1 && x2 && y, "conv1x1_gemm_cat: null pointer");
     const int K = K1 + K2;
-    GRAFP_REQUIRE(K1 > 0 && K2 > 0 && K1 % GM_KC == 0 && gemm_shape_ok(R, K, 1, M, 1),
-                  "conv1x1_gemm_cat: unsupported shape R=%d K1=%d K2=%d M=%lld", R, K1, K2, (long long)M);
-    GRAFP_REQUIRE((((uintptr_t)w | (uintptr_t)x1 | (uintptr_t)x2 | (uintptr_t)y) & 15) == 0,
-                  "conv1x1_gemm_cat: operands must be 16-byte aligned");
-    const GemmPlan p = gemm_plan(R, K, 1, M, 1);
-    GemmArgs a;
-    a.w = (const unsigned short *)w; a.x = (const unsigned short *)x1; a.x2 = (const unsigned short *)x2;
-    a.y = (unsigned short *)y; a.lda = K; a.K1 = K1; a.M = M; a.Rg = R; a.Kg = K; a.groups = 1; a.views = 1;
-    a.pro_tab = nullptr; a.pro_act = 0; a.pro_slope = 0.0f; a.part = nullptr;
-    gemm_dispatch(p, a, (hipStream_t)stream);
-    GRAFP_CHECK_LAUNCH("conv1x1_gemm_kernel (cat)");
-    return GRAFP_OK;
+    if (int rc = gemm_check("conv1x1_gemm_cat", w && x1 && x2 && y,
+                            (uintptr_t)w | (uintptr_t)x1 | (uintptr_t)x2 | (uintptr_t)y, GM_ALIGNED, 0,
+                            K1 > 0 && K2 > 0 && K1 % GM_KC == 0 && gemm_shape_ok(R, K, 1, M, 1), "R=%d K1=%d K2=%d M=%lld", R,
+                            K1, K2, (long long)M))
+        return rc;
+    GemmArgs a = gemm_args(w, x1, y, R, K, 1, M, 1);
+    a.x2 = (const unsigned short *)x2; a.K1 = K1;
+    return gemm_run(a, "conv1x1_gemm_kernel (cat)", stream);
 }
 
 // ---- the f32 mode's products on the bf16 matrix cores (round 4) ----
@@ -960,21 +1029,14 @@ extern "C" int grafp_split_bf16_planes(const float *x, int64_t n, void *hi, void
 extern "C" int grafp_conv1x1_gemm_split_f32(const void *w3, const void *x_planes, int R, int K, int64_t M, float *y,
                                             grafp_stream_t stream) {
     using namespace grafp;
-    GRAFP_REQUIRE(w3 && x_planes && y, "conv1x1_gemm_split: null pointer");
-    GRAFP_REQUIRE(K > 0 && K % GM_KC == 0 && gemm_shape_ok(R, 3 * K, 1, M, 1),
-                  "conv1x1_gemm_split: unsupported shape R=%d K=%d M=%lld", R, K, (long long)M);
-    GRAFP_REQUIRE((((uintptr_t)w3 | (uintptr_t)x_planes | (uintptr_t)y) & 15) == 0, "conv1x1_gemm_split: 16-byte alignment");
-    GemmPlan p = gemm_plan(R, 3 * K, 1, M, 1);
-    GemmArgs a;
+    if (int rc = gemm_check("conv1x1_gemm_split", w3 && x_planes && y, (uintptr_t)w3 | (uintptr_t)x_planes | (uintptr_t)y,
+                            "16-byte alignment", 0, K > 0 && K % GM_KC == 0 && gemm_shape_ok(R, 3 * K, 1, M, 1),
+                            "R=%d K=%d M=%lld", R, K, (long long)M))
+        return rc;
+    GemmArgs a = gemm_args(w3, x_planes, y, R, 3 * K, 1, M, 1);          // operand rows [Xh; Xl] ...
+    a.x2 = (const unsigned short *)x_planes; a.K1 = 2 * K;               // ... then Xh again
     a.out_f32 = true;
-    a.w = (const unsigned short *)w3;
-    a.x = (const unsigned short *)x_planes;                              // rows [Xh; Xl]
-    a.x2 = (const unsigned short *)x_planes;                             // ... then Xh again
-    a.y = (unsigned short *)y; a.lda = 3 * K; a.K1 = 2 * K; a.M = M; a.Rg = R; a.Kg = 3 * K; a.groups = 1; a.views = 1;
-    a.pro_tab = nullptr; a.pro_act = 0; a.pro_slope = 0.0f; a.part = nullptr;
-    gemm_dispatch(p, a, (hipStream_t)stream);
-    GRAFP_CHECK_LAUNCH("conv1x1_gemm_kernel (split f32)");
-    return GRAFP_OK;
+    return gemm_run(a, "conv1x1_gemm_kernel (split f32)", stream);
 }
 
 extern "C" int grafp_bn_finalize(const float *stats_part, int C, int K, int groups, int64_t M, int views,
@@ -995,9 +1057,10 @@ extern "C" int grafp_bn_finalize(const float *stats_part, int C, int K, int grou
     GRAFP_REQUIRE(gemm_shape_ok(C, K, groups, M, views), "bn_finalize: shape does not match a conv1x1_gemm launch");
     const GemmPlan p = gemm_plan(C / groups, K / groups, groups, M, views);
     GRAFP_REQUIRE(views <= 8, "bn_finalize: at most 8 views");
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(64 * views), 0, s, stats_part, C, views, p.P, p.wm, p.tiles_range,
-                       p.col_tiles_view, M / views, pre_bias, gamma, beta, eps, momentum, running_mean, running_var,
-                       save_mean, save_invstd, (float2 *)tab);
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(64 * views), 0, s,
+                       bn_stats_args(p, stats_part, pre_bias, gamma, beta, eps, momentum, running_mean, running_var, save_mean,
+                                     save_invstd, tab),
+                       views, M / views);
     GRAFP_CHECK_LAUNCH("bn_finalize_kernel");
     return GRAFP_OK;
 }
@@ -1058,10 +1121,7 @@ extern "C" int grafp_bn_finalize_affine_bf16(const void *y, const float *stats_p
     GRAFP_REQUIRE(views >= 1 && views <= 4, "bn_finalize_affine: 1..4 views (one wave each in the row's first workgroup)");
     GRAFP_REQUIRE(gemm_shape_ok(C, K, groups, M, views), "bn_finalize_affine: shape does not match a conv1x1_gemm launch");
     const GemmPlan p = gemm_plan(C / groups, K / groups, groups, M, views);
-    BnStatsArgs st;
-    st.part = stats_part; st.pre_bias = pre_bias; st.gamma = gamma; st.beta = beta;
-    st.running_mean = running_mean; st.running_var = running_var; st.save_mean = save_mean; st.save_invstd = save_invstd;
-    st.tab = (float2 *)tab; st.P = p.P; st.wm = p.wm; st.tiles_range = p.tiles_range; st.col_tiles_view = p.col_tiles_view;
-    st.eps = eps; st.momentum = momentum;
+    const BnStatsArgs st = bn_stats_args(p, stats_part, pre_bias, gamma, beta, eps, momentum, running_mean, running_var,
+                                         save_mean, save_invstd, tab);
     return bn_affine_launch(y, C, M, views, nullptr, &st, residual, act, slope, out, stream);
 }

@@ -78,16 +78,7 @@ template <int T, int G> __device__ __forceinline__ void xl_acc_pack4(unsigned &p
     asm volatile("; a0-a255 released" ::"a"(h[0]), "a"(h[1]), "a"(h[2]), "a"(h[3]), "a"(h[4]), "a"(h[5]), "a"(h[6]),       \
                  "a"(h[7]), "a"(h[8]), "a"(h[9]), "a"(h[10]), "a"(h[11]), "a"(h[12]), "a"(h[13]), "a"(h[14]), "a"(h[15]))
 
-struct GemmXL {
-    static constexpr int NW = 4, THREADS = 256, TR = 256, TN = 256, RT = 4, MT = 4, NS = 4;
-    static constexpr int NA = 16, NB = 16;                       // 1-KiB LDS-DMA pieces per chunk: W, X
-    static constexpr int PW = NA / NW, PX = NB / NW;             // ... per wave
-    static constexpr int A_BYTES = TR * GM_KC * 2, B_BYTES = GM_KC * TN * 2, STAGE = A_BYTES + B_BYTES;
-    static constexpr int ROWB = TN * 2, SLOTS = TN / 8, RPI = 64 / SLOTS;
-    static constexpr int OUT_BYTES = 32 * 256;                   // per wave: 32 rows (r) x 128 m bf16
-    static constexpr int STORES_PER_RT = 8;                      // 16-byte store instructions per wave and 32-row tile
-    static constexpr size_t LDS = (size_t)NS * STAGE + NW * OUT_BYTES;
-};
+// (struct GemmXL, the tile's geometry: gemm.hip, beside the other tile configurations)
 
 // ABL (measurement builds only, results are garbage): 1 = no W pieces, 2 = no stores, 4 = no X pieces, 8 = no MFMAs
 template <bool STATS, bool CAT, bool EPI, int ABL = 0>
@@ -108,36 +99,21 @@ __global__ __launch_bounds__(GemmXL::THREADS, 1) void conv1x1_gemm_xl_kernel(
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 1, wm = wave & 1;
     const unsigned lds0 = (unsigned)(uintptr_t)(gm_lptr)smem;
-    const int logical = xcd_remap(blockIdx.x, nblocks);
-    const int rt = logical % row_tiles, range = logical / row_tiles;
-    const int view = range / ranges_view, rloc = range - view * ranges_view;
-    const int grp = blockIdx.z;
-    const int tile0 = rloc * tiles_range;
-    const int ntile = (tiles_range < col_tiles_view - tile0) ? tiles_range : col_tiles_view - tile0;
-    const int nch = K / GM_KC;
-    const int T = ntile * nch;
-    const int r0 = rt * C::TR;
-    const int64_t col0 = (int64_t)view * (M / views) + (int64_t)tile0 * TN;
+    const GemmRange own = gm_range(nblocks, row_tiles, ranges_view, tiles_range, col_tiles_view, M, views, TN);
+    const int view = own.view, rloc = own.rloc, ntile = own.ntile, grp = blockIdx.z;
+    const int nch = K / GM_KC, T = ntile * nch, r0 = own.rt * C::TR;
+    const int64_t col0 = own.col0;
     A += (size_t)grp * Rg * lda;
     X += (size_t)grp * K * M;
     Y += (size_t)grp * Rg * M;
 
     // ---- LDS-DMA sources: W pieces q = wave + 4 j (rows 16 q .. 16 q + 15, 64 B each), X pieces p = wave + 4 j
-    //      (k-rows 2 p, 2 p + 1, 512 B each); swizzles as in conv1x1_gemm_kernel ----
-    //      (Rg is a multiple of 256: no row of a W piece lies beyond the matrix; piece j of a wave = piece 0 + a fixed step)
-    const unsigned short *srcw, *srcx, *srcx2 = nullptr;
-    {
-        const int row = r0 + 16 * wave + (lane >> 2);
-        const int slot = (lane & 3) ^ ((lane >> 4) & 3);
-        srcw = A + (size_t)row * lda + slot * 8;
-    }
-    {
-        const int row = C::RPI * wave + lane / C::SLOTS;
-        const int sl = lane % C::SLOTS;
-        const int seg = (sl >> 2) ^ (row & 3);                 // (row + RPI * NW * j) & 3 == row & 3: RPI * NW = 8
-        srcx = X + (size_t)row * M + col0 + (seg * 4 + (sl & 3)) * 8;
-        if (CAT) srcx2 = X2 + (srcx - X);
-    }
+    //      (k-rows 2 p, 2 p + 1, 512 B each); gm_w_src, gm_x_src ----
+    //      No row clamp: Rg is a multiple of 256 (gemm_plan), no row of a W piece lies beyond the matrix.  Piece j of a wave =
+    //      piece 0 + a fixed step: 64 rows (W) and 8 rows (X) further on, which leaves the swizzles ((row >> 2) & 3, row & 3).
+    const unsigned short *const srcw = gm_w_src(A, lda, r0 + 16 * wave + (lane >> 2), lane);
+    const unsigned short *srcx = gm_x_src<C>(X, M, col0, wave, lane), *srcx2 = nullptr;
+    if (CAT) srcx2 = X2 + (srcx - X);
     const int64_t w_step = (int64_t)16 * C::NW * lda, x_step = (int64_t)C::RPI * C::NW * M;   // elements per piece index
     const int nch1 = CAT ? K1 / GM_KC : nch;
     int is_ch = 0;                                           // chunk-in-tile of the chunk being issued
@@ -170,6 +146,8 @@ __global__ __launch_bounds__(GemmXL::THREADS, 1) void conv1x1_gemm_xl_kernel(
     int xoff[MT];
 #pragma unroll
     for (int mi = 0; mi < MT; ++mi) {
+        // gm_x_frag_off<ROWB, C::A_BYTES>(wm * 128, mi, lane), written out: through the function hipcc 7.2 assigns other
+        // registers and a slice-store gap of the chunk loop gains `s_waitcnt lgkmcnt(4); s_nop 0` (next address in the store's data)
         const int i = lane & 15;
         const int bytecol = (wm * 128 + mi * 32 + 16 * ((lane >> 4) & 1) + 4 * (i & 3)) * 2;
         const int seg = (bytecol >> 6) ^ (i >> 2);
@@ -177,10 +155,7 @@ __global__ __launch_bounds__(GemmXL::THREADS, 1) void conv1x1_gemm_xl_kernel(
     }
     int woff[2];                                             // row tile ri: + ri * 2048 ((row >> 2) & 3 is the same)
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-        const int row = wr * 128 + l31;
-        woff[ks] = row * 64 + (((2 * ks + half) ^ ((row >> 2) & 3)) << 4);
-    }
+    for (int ks = 0; ks < 2; ++ks) woff[ks] = gm_w_frag_off(wr * 128 + l31, ks, half);
 
     gm_f32x2 sS[RT], sQ[RT];
     float sShift[RT];
@@ -198,12 +173,7 @@ __global__ __launch_bounds__(GemmXL::THREADS, 1) void conv1x1_gemm_xl_kernel(
     gm_bf16x8 xa0[MT], xa1[MT], wb[RT];
     auto x_read = [&](auto set_c, auto mi_c, const unsigned char *st) __attribute__((always_inline)) {   // fragment mi of X set SET
         constexpr int SET = decltype(set_c)::value, mi = decltype(mi_c)::value;
-        const gm_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (gm_s16x4 __attribute__((address_space(3))) *)(st + xoff[mi] + SET * 16 * ROWB));
-        const gm_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (gm_s16x4 __attribute__((address_space(3))) *)(st + xoff[mi] + SET * 16 * ROWB + 4 * ROWB));
-        if constexpr (SET == 0) xa0[mi] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        else xa1[mi] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+        (SET == 0 ? xa0[mi] : xa1[mi]) = gm_x_frag<ROWB>(st, xoff[mi] + SET * 16 * ROWB);
     };
     auto w_read = [&](auto ks_c, auto ri_c, const unsigned char *st) __attribute__((always_inline)) {
         constexpr int KS = decltype(ks_c)::value, ri = decltype(ri_c)::value;
@@ -249,12 +219,7 @@ __global__ __launch_bounds__(GemmXL::THREADS, 1) void conv1x1_gemm_xl_kernel(
                 sh2 = gm_f32x2{sShift[ri], sShift[ri]};
                 asm volatile("" : "+v"(sh2));                  // a real register pair (see conv1x1_gemm_kernel)
             }
-            const gm_f32x2 da = gm_f32x2{bf16_lo(p0), bf16_hi(p0)} - sh2;
-            const gm_f32x2 db = gm_f32x2{bf16_lo(p1), bf16_hi(p1)} - sh2;
-            sS[ri] += da;
-            sQ[ri] = __builtin_elementwise_fma(da, da, sQ[ri]);
-            sS[ri] += db;
-            sQ[ri] = __builtin_elementwise_fma(db, db, sQ[ri]);
+            gm_stats_add(p0, p1, sh2, sS[ri], sQ[ri]);
             // pinned HERE, in this MFMA gap: the sums are only needed at the end of the kernel, and hipcc sinks the whole
             // chain of a tile's 64 groups into one block behind phase A (512 live floats, parked in AGPRs -- seen in the .s)
             asm volatile("" : "+v"(sS[ri]), "+v"(sQ[ri]));
@@ -437,38 +402,10 @@ __global__ __launch_bounds__(GemmXL::THREADS, 1) void conv1x1_gemm_xl_kernel(
         });
     });
     gm_wait_vm<0>();
-    if (STATS) {
-        float *s_st = reinterpret_cast<float *>(smem);                  // [2][TR][2] (mean, M2): the ring is idle now
-        const float np = 128.0f * (float)ntile;
-        __syncthreads();
-#pragma unroll
-        for (int ri = 0; ri < RT; ++ri) {
-            const float s1 = sS[ri].x + sS[ri].y, q1 = sQ[ri].x + sQ[ri].y;
-            const float s = s1 + __shfl_xor(s1, 32), q = q1 + __shfl_xor(q1, 32);
-            if (half == 0) {
-                const int row = wr * 128 + ri * 32 + l31;
-                const float dm = s / np;
-                s_st[(wm * C::TR + row) * 2 + 0] = sShift[ri] + dm;
-                s_st[(wm * C::TR + row) * 2 + 1] = fmaxf(q - s * dm, 0.0f);
-            }
-        }
-        __syncthreads();
-        if (wm == 0 && half == 0) {
-#pragma unroll
-            for (int ri = 0; ri < RT; ++ri) {
-                const int row = wr * 128 + ri * 32 + l31;
-                float n = 0.0f, mean = 0.0f, m2 = 0.0f;
-#pragma unroll
-                for (int w = 0; w < 2; ++w)
-                    gm_chan(n, mean, m2, np, s_st[(w * C::TR + row) * 2], s_st[(w * C::TR + row) * 2 + 1]);
-                {
-                    float *pp = part + ((((size_t)grp * Rg + r0 + row) * views + view) * P + rloc) * 3;
-                    pp[0] = 0.0f;                                       // (S, Q, shift) with S = 0: mean = shift, M2 = Q
-                    pp[1] = m2;
-                    pp[2] = mean;
-                }
-            }
-        }
+    if (STATS) {     // the ring is idle now: its first bytes take the merge of the two wave columns; every row tile exists
+        const bool all_rows[RT] = {true, true, true, true};
+        gm_stats_tail<2, C::TR, RT, 128>(reinterpret_cast<float *>(smem), sS, sQ, sShift, all_rows, ntile, wm, wr * 128, lane,
+                                         part, (size_t)grp * Rg + r0, views, view, P, rloc);
     }
     XL_RELEASE_AGPRS(agpr_hold);
 }

@@ -456,8 +456,7 @@ __global__ __launch_bounds__(CFG::THREADS) void wgrad_dma_kernel(
                         float lo = bf16_lo(v[d]), hi = bf16_hi(v[d]);
                         lo = __builtin_fmaf(lo, ssb[b].x, ssb[b].y);
                         hi = __builtin_fmaf(hi, ssb[b].x, ssb[b].y);
-                        if (act == 1) { lo = relu_keep_nan(lo); hi = relu_keep_nan(hi); }
-                        else if (act == 2) { lo = lo > 0.f ? lo : lo * slope; hi = hi > 0.f ? hi : hi * slope; }
+                        act_fwd_pair(lo, hi, act, slope);
                         v[d] = pack_bf16(lo, hi);
                     }
                     bv[b] = __builtin_bit_cast(gm_bf16x8, v);
@@ -784,12 +783,6 @@ static int wgrad_check(const char *who, const void *grad_out, const void *x, int
     }
     return GRAFP_OK;
 }
-// a launch with `lds` bytes of dynamic LDS: beyond the 48 KB every kernel may have, the function attribute has to allow it
-template <typename... P, typename... A>
-static void wg_launch(void (*kernel)(P...), dim3 grid, int threads, size_t lds, hipStream_t s, A... args) {
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, s, static_cast<P>(args)...);
-}
 // dweight[i] = the sum of the S partial planes of n outputs in ws
 static int wgrad_reduce(const void *ws, int S, int64_t n, float *dweight, hipStream_t s) {
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, s, (const float *)ws, S, n,
@@ -861,14 +854,14 @@ static int wgrad_tile_impl(const void *grad_out, const void *x, int Cout, int Ci
             typedef typename decltype(k)::CFG CFG;
             const size_t ring = (size_t)CFG::NS * CFG::STAGE;
             if constexpr (decltype(k)::GR)                      // never with a pro_tab: wg_tile_info[].pro
-                wg_launch(wgrad_gr_kernel<CFG>, grid, CFG::THREADS, (size_t)3 * CFG::X_BYTES + 2 * CFG::G_BYTES, s, G, X, M,
+                gm_launch(wgrad_gr_kernel<CFG>, grid, CFG::THREADS, (size_t)3 * CFG::X_BYTES + 2 * CFG::G_BYTES, s, G, X, M,
                           cout_g, cin_g, p.tiles_o, p.tiles_c, p.slices_view, p.cols, views, (float *)ws, nblocks);
             else if (pro_tab)
-                wg_launch(wgrad_dma_kernel<CFG, true>, grid, CFG::THREADS, ring + (size_t)CFG::TC * 8, s, G, X, M, cout_g,
+                gm_launch(wgrad_dma_kernel<CFG, true>, grid, CFG::THREADS, ring + (size_t)CFG::TC * 8, s, G, X, M, cout_g,
                           cin_g, p.tiles_o, p.tiles_c, p.slices_view, p.cols, views, (const float2 *)pro_tab, pro_act,
                           pro_slope, (float *)ws, nblocks);
             else
-                wg_launch(wgrad_dma_kernel<CFG, false>, grid, CFG::THREADS, ring, s, G, X, M, cout_g, cin_g, p.tiles_o,
+                gm_launch(wgrad_dma_kernel<CFG, false>, grid, CFG::THREADS, ring, s, G, X, M, cout_g, cin_g, p.tiles_o,
                           p.tiles_c, p.slices_view, p.cols, views, (const float2 *)pro_tab, pro_act, pro_slope, (float *)ws,
                           nblocks);
         });
@@ -880,7 +873,7 @@ static int wgrad_tile_impl(const void *grad_out, const void *x, int Cout, int Ci
         const WgradPlan p = wgrad_plan(cout_g, cin_g, groups, M);
         GRAFP_REQUIRE((int64_t)p.S * p.tiles_o * p.tiles_c < (1ll << 31), "conv1x1_wgrad: output too large");
         const dim3 grid(p.S * p.tiles_o * p.tiles_c, 1, groups);
-        wg_launch(p.tw == 64 ? wgrad_partial_kernel<64> : wgrad_partial_kernel<128>, grid, 256, (size_t)2 * p.tw * WG_LS, s,
+        gm_launch(p.tw == 64 ? wgrad_partial_kernel<64> : wgrad_partial_kernel<128>, grid, 256, (size_t)2 * p.tw * WG_LS, s,
                   G, X, M, cout_g, cin_g, p.tiles_o, p.tiles_c, p.cols, (float *)ws);
         GRAFP_CHECK_LAUNCH("wgrad_partial_kernel");
         S = p.S;
@@ -1033,7 +1026,7 @@ extern "C" int grafp_conv1x1_wgrad_f32(const float *grad_out, const float *x, in
     GRAFP_REQUIRE((int64_t)p.S * p.tiles_o * p.tiles_c < (1ll << 31), "conv1x1_wgrad_f32: output too large");
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(p.S * p.tiles_o * p.tiles_c, 1, groups);
-    wg_launch(wgrad3_partial_kernel, grid, 256, (size_t)4 * 64 * WG_LS, s, grad_out, x, M, cout_g, cin_g, p.tiles_o,
+    gm_launch(wgrad3_partial_kernel, grid, 256, (size_t)4 * 64 * WG_LS, s, grad_out, x, M, cout_g, cin_g, p.tiles_o,
               p.tiles_c, p.cols, (float *)ws);
     GRAFP_CHECK_LAUNCH("wgrad3_partial_kernel");
     return wgrad_reduce(ws, p.S, (int64_t)Cout * cin_g, dweight, s);

@@ -149,6 +149,70 @@ def test_gemm_statistics_with_large_mean():
     np.testing.assert_allclose(invstd[:, 0].cpu().numpy(), (1 / yv.std(dim=1, unbiased=False)).cpu().numpy(), rtol=1e-4)
 
 
+def _plan_info(R, K, groups, M, views):
+    import ctypes
+    from grafp_amd._lib import lib
+    info = (ctypes.c_int * 8)()
+    assert lib.grafp_conv1x1_gemm_plan(R, K, groups, M, views, info) == 0
+    return list(info)
+
+
+# ((R, K, groups, M, views), tile configuration): per configuration the smallest shape the plan rule sends there -- S, L,
+# XL, N32, N64, N128 -- and an N64 shape whose last column range is short (131 tiles in ranges of 4)
+PART_SHAPES = [((64, 64, 1, 256, 2), 0), ((512, 64, 1, 512, 1), 1), ((256, 512, 1, 512, 2), 5), ((32, 32, 1, 65536, 1), 2),
+               ((64, 64, 1, 65536, 1), 3), ((128, 512, 1, 131072, 1), 4), ((64, 64, 1, 2 * 512 * 131, 2), 3)]
+
+
+@pytest.mark.parametrize("shape,cfg", PART_SHAPES)
+def test_gemm_partials_against_float64(shape, cfg):
+    """The layout of the statistics partials, which the end of a STATS kernel writes and the finalizers read: part[r][v][p]
+    = (0, M2, mean) of row r over the columns of range p of view v (info[2] tiles of info[6] columns, the last range of a
+    view what is left), against float64 on the rounded y.  mean: the bar of test_gemm_product_and_stats; M2: rtol 4e-5,
+    twice that test's bar on invstd (invstd ~ var^-1/2)."""
+    from grafp_amd import ops
+    R, K, groups, M, views = shape
+    info = _plan_info(*shape)
+    assert info[0] == cfg == _plan_cfg(*shape)
+    w, x = _rand((R, K // groups), 1, 0.2), _rand((K, M), 2, 1.0, 0.3)
+    y, part = ops.conv1x1_gemm(w, x, groups, views, stats=True)
+    Mg, cols, P = M // views, info[2] * info[6], info[3]
+    assert part.shape == (R, views, P, 3) and P == -(-Mg // cols)
+    yv = y.float().double().reshape(R, views, Mg)
+    full = Mg // cols
+    segs = [yv[:, :, :full * cols].reshape(R, views, full, cols)] + ([yv[:, :, full * cols:, None].transpose(2, 3)] if P > full else [])
+    mean = torch.cat([s.mean(dim=3) for s in segs], dim=2)
+    m2 = torch.cat([((s - s.mean(dim=3, keepdim=True)) ** 2).sum(dim=3) for s in segs], dim=2)
+    got = part.double()
+    print(f"{shape}: cfg {cfg}, {P} ranges of {cols} columns (last {Mg - (P - 1) * cols}); worst deviation: mean "
+          f"{float((got[..., 2] - mean).abs().max()):.3e} abs, M2 {float(((got[..., 1] - m2).abs() / m2).max()):.3e} rel")
+    assert bool((part[..., 0] == 0).all())
+    np.testing.assert_allclose(got[..., 2].cpu().numpy(), mean.cpu().numpy(), rtol=1e-5, atol=1e-5)
+    np.testing.assert_allclose(got[..., 1].cpu().numpy(), m2.cpu().numpy(), rtol=4e-5)
+
+
+def test_bn_finalize_in_eval_mode():
+    """bn_finalize(training=False): mean, invstd and the (scale, shift) table from the RUNNING statistics (the conv bias
+    goes into the shift only), the same for every view, against the float64 formula within the bars of
+    test_gemm_product_and_stats; the running statistics stay as they are."""
+    from grafp_amd import ops
+    R, K, groups, M, views, eps = 64, 64, 1, 256, 2, 1e-5
+    g = torch.Generator().manual_seed(7)
+    gamma, beta = torch.linspace(0.5, 1.5, R, device=DEV), torch.linspace(-0.2, 0.2, R, device=DEV)
+    bias = torch.linspace(-1.0, 1.0, R, device=DEV)
+    rm, rv = torch.randn(R, generator=g).to(DEV), (torch.rand(R, generator=g) + 0.1).to(DEV)
+    rm0, rv0 = rm.clone(), rv.clone()
+    mean, invstd, tab = ops.bn_finalize(None, R, K, groups, M, views, gamma, beta, bias, rm, rv, False, 0.1, eps)
+    assert torch.equal(rm, rm0) and torch.equal(rv, rv0)
+    want_invstd = 1.0 / torch.sqrt(rv0.double() + eps)
+    scale = gamma.double() * want_invstd
+    shift = beta.double() + (bias.double() - rm0.double()) * scale
+    for v in range(views):
+        np.testing.assert_allclose(mean[:, v].cpu().numpy(), rm0.double().cpu().numpy(), rtol=1e-5, atol=1e-5)
+        np.testing.assert_allclose(invstd[:, v].cpu().numpy(), want_invstd.cpu().numpy(), rtol=2e-5)
+        np.testing.assert_allclose(tab[:, v, 0].cpu().numpy(), scale.cpu().numpy(), rtol=2e-5)
+        np.testing.assert_allclose(tab[:, v, 1].cpu().numpy(), shift.cpu().numpy(), rtol=1e-4, atol=1e-4)
+
+
 @pytest.mark.parametrize("R,K,groups,M,views,act", [(64, 128, 1, 4096, 2, 1), (128, 256, 1, 2048, 2, 1),
                                                     (64, 128, 1, 131072, 2, 1), (128, 512, 1, 131072, 1, 2),
                                                     (512, 2048, 1, 1024, 2, 1), (64, 64, 1, 2048, 1, 2),

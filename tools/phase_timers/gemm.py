@@ -33,11 +33,11 @@ rep('''        // shift the issue history by one iteration
         // shift the issue history by one iteration
 #pragma unroll
         for (int j = D - 1; j > 0; --j) dma_hist[j] = dma_hist[j - 1];''')
-rep('''    if (STATS) {
-        // per row: this wave's (sum, sum of squares, shift) over its 64-column share of every tile of the range ->''', '''    if (blockIdx.x == 37 && blockIdx.y == 0 && blockIdx.z == 0 && (threadIdx.x & 63) == 0 && T >= 8)
+rep('''    if (STATS)       // the ring is idle now: its first bytes take the merge
+        gm_stats_tail<CFG::WM, CFG::TR, RT, 64>(''', '''    if (blockIdx.x == 37 && blockIdx.y == 0 && blockIdx.z == 0 && (threadIdx.x & 63) == 0 && T >= 8)
         printf("gemm TR %d TN %d NW %d w%d T %d nch %d tiles %d STATS %d: per chunk: vmwait %llu barrier %llu issue %llu mfma %llu | epilogue per tile %llu\\n", CFG::TR, TN, CFG::NW, (int)(threadIdx.x >> 6), T, nch, tile, (int)STATS, TT[0] / T, TT[1] / T, TT[2] / T, TT[3] / T, TT[4] / (tile > 0 ? tile : 1));
-    if (STATS) {
-        // per row: this wave's (sum, sum of squares, shift) over its 64-column share of every tile of the range ->''')
+    if (STATS)       // the ring is idle now: its first bytes take the merge
+        gm_stats_tail<CFG::WM, CFG::TR, RT, 64>(''')
 open("/tmp/gemm_tm.hip", "w").write(s)
 csrc = os.path.join(root, "grafp_amd/csrc")
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-I" + os.path.join(root, "include"), "-I" + csrc, "-Wno-inline-asm", "-c", "/tmp/gemm_tm.hip", "-o", "/tmp/gemm_tm.o"])
