@@ -101,6 +101,7 @@ SIGNATURES = {
     "grafp_conv1x1_wgrad_f32": (_I, [_P, _P, _I, _I, _I, _L, _P, _P, _Z, _P]),
     "grafp_ntxent_workspace": (_Z, [_I]),
     "grafp_ntxent_num_partials": (_I, [_I]),
+    "grafp_ntxent_plan": (_I, [_I, _I, _P]),
     "grafp_ntxent_fwd_bwd_f32": (_I, [_P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _Z, _P]),
     "grafp_row_sqnorm_f32": (_I, [_P, _L, _I, _P, _P]),
     "grafp_knn_search_workspace": (_Z, [_L, _I, _I, _I]),

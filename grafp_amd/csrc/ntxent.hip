@@ -275,22 +275,55 @@ __global__ __launch_bounds__(256) void ntxent_dz_combine_kernel(const float *__r
 
 }  // namespace grafp
 
-// candidate splits of pass 1: NT_C-row chunks dealt to up to 8 workgroups per row block, >= 2 chunks each
-static int nt_splits(int M) {
-    const int chunks = (M + grafp::NT_C - 1) / grafp::NT_C;
-    int sp = chunks / 2;
-    if (sp > 8) sp = 8;
-    return sp < 1 ? 1 : sp;
+// The launch plan of one call, written once: the launch code, grafp_ntxent_workspace and grafp_ntxent_plan read it.
+//   pass 1: the NT_C-row candidate chunks are dealt to up to 8 workgroups per 32-row block, >= 2 chunks each; every split
+//           takes ceil(chunks / splits) chunks, so trailing splits may be empty (they write (-inf, 0, -inf) triples)
+//   pass 2: candidate splits so that ~256 workgroups run, never more than pass 1's
+// Workspace (floats): lse[M] | pos[M] | pass-1 triples [splits][M][3] | pass-2 partial gradients [splits2][2][n_local][D]
+struct NtPlan {
+    int chunks, splits, cols_per_split, splits2, cols_per_split2;
+    dim3 grid1, grid2;
+    size_t dzpart_off;  // floats from the start of the workspace
+};
+static NtPlan nt_plan(int B_all, int n_local) {
+    using namespace grafp;
+    NtPlan p;
+    const int M = 2 * B_all, qblocks = (n_local + NT_Q - 1) / NT_Q;
+    p.chunks = (M + NT_C - 1) / NT_C;
+    p.splits = p.chunks / 2;
+    if (p.splits > 8) p.splits = 8;
+    if (p.splits < 1) p.splits = 1;
+    p.cols_per_split = ((p.chunks + p.splits - 1) / p.splits) * NT_C;
+    p.splits2 = 256 / (2 * qblocks);
+    if (p.splits2 > p.splits) p.splits2 = p.splits;
+    if (p.splits2 < 1) p.splits2 = 1;
+    p.cols_per_split2 = ((p.chunks + p.splits2 - 1) / p.splits2) * NT_C;
+    p.grid1 = dim3((M + NT_Q - 1) / NT_Q, p.splits);
+    p.grid2 = dim3(qblocks, 2, p.splits2);
+    p.dzpart_off = (size_t)2 * M + (size_t)p.splits * M * 3;
+    return p;
 }
 extern "C" size_t grafp_ntxent_workspace(int B_all) {
     if (B_all <= 0) return 0;
-    const size_t M = (size_t)2 * B_all;
-    // lse[2B] + pos[2B] + partial triples of pass 1 + partial gradients of pass 2 (n_local <= B_all rows, D <= 128)
-    return (2 * M + (size_t)nt_splits((int)M) * M * 3 + (size_t)nt_splits((int)M) * M * 128) * sizeof(float);
+    // the partial gradients of pass 2 at their largest: pass 1's split count, n_local = B_all rows, D = 128
+    const NtPlan p = nt_plan(B_all, B_all);
+    return (p.dzpart_off + (size_t)p.splits * 2 * B_all * 128) * sizeof(float);
 }
 
 extern "C" int grafp_ntxent_num_partials(int n_local) {
     return n_local > 0 ? 2 * ((n_local + grafp::NT_Q - 1) / grafp::NT_Q) : 0;
+}
+
+extern "C" int grafp_ntxent_plan(int B_all, int n_local, int *info) {
+    using namespace grafp;
+    GRAFP_REQUIRE(info, "ntxent_plan: null pointer");
+    for (int i = 0; i < 8; ++i) info[i] = 0;
+    GRAFP_REQUIRE(B_all >= 1 && n_local >= 1 && n_local <= B_all, "ntxent_plan: need 1 <= n_local <= B_all (B_all=%d n_local=%d)",
+                  B_all, n_local);
+    const NtPlan p = nt_plan(B_all, n_local);
+    info[0] = p.chunks; info[1] = p.splits; info[2] = p.cols_per_split; info[3] = p.splits2; info[4] = p.cols_per_split2;
+    info[5] = grafp_ntxent_num_partials(n_local);
+    return GRAFP_OK;
 }
 
 extern "C" int grafp_ntxent_fwd_bwd_f32(const float *zi_all, const float *zj_all, int B_all, int D, int row_begin,
@@ -312,19 +345,13 @@ extern "C" int grafp_ntxent_fwd_bwd_f32(const float *zi_all, const float *zj_all
     const int M = 2 * B_all, LS = D + 1;
     float *lse = (float *)ws, *pos = lse + M, *part = pos + M;
     const float inv_tau = 1.0f / tau;
-    const int splits = nt_splits(M);
-    const int chunks = (M + NT_C - 1) / NT_C;
-    const int cols_per_split = ((chunks + splits - 1) / splits) * NT_C;
+    const NtPlan pl = nt_plan(B_all, n_local);
+    const int splits = pl.splits, cols_per_split = pl.cols_per_split;
+    const int splits2 = pl.splits2, cols_per_split2 = pl.cols_per_split2;
     const size_t lds1 = ((size_t)(NT_Q + NT_C) * LS + 3 * 4 * 32) * sizeof(float);
     const size_t lds2 = ((size_t)(NT_Q + NT_C) * LS + NT_C) * sizeof(float);
-    const dim3 grid1((M + NT_Q - 1) / NT_Q, splits);
-    // pass 2: candidate splits so that ~256 workgroups run (never more than pass 1's, >= 2 chunks each)
-    int splits2 = 256 / (2 * ((n_local + NT_Q - 1) / NT_Q));
-    if (splits2 > splits) splits2 = splits;
-    if (splits2 < 1) splits2 = 1;
-    const int cols_per_split2 = ((chunks + splits2 - 1) / splits2) * NT_C;
-    float *dzpart = part + (size_t)splits * M * 3;
-    const dim3 grid((n_local + NT_Q - 1) / NT_Q, 2, splits2);
+    const dim3 grid1 = pl.grid1, grid = pl.grid2;
+    float *dzpart = lse + pl.dzpart_off;
 #define NT_LAUNCH(NDB)                                                                                              \
     (void)hipFuncSetAttribute((const void *)ntxent_lse_kernel<NDB>, hipFuncAttributeMaxDynamicSharedMemorySize,     \
                               (int)lds1);                                                                           \

@@ -1514,6 +1514,24 @@ class _NTXent(torch.autograd.Function):
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, z_i, z_j, tau, zi_all, zj_all, row_begin):
         _require_gpu(z_i, z_j)
+        # the kernels read zi_all and zj_all with z_i's width and zi_all's row count: a mismatch would be an out-of-bounds
+        # read, so it is refused here, before any launch
+        if z_i.dim() != 2 or z_i.shape != z_j.shape:
+            raise ValueError(f"ntxent: z_i and z_j must be 2-D of one shape, got {tuple(z_i.shape)} and {tuple(z_j.shape)}")
+        if z_j.device != z_i.device:
+            raise ValueError(f"ntxent: z_j is on {z_j.device}, z_i (shape {tuple(z_i.shape)}) on {z_i.device}")
+        if (zi_all is None) != (zj_all is None):
+            raise ValueError(f"ntxent: zi_all and zj_all come together, got only {'zi_all' if zj_all is None else 'zj_all'} "
+                             f"(shape {tuple((zi_all if zj_all is None else zj_all).shape)})")
+        if zi_all is not None:
+            if zi_all.shape != zj_all.shape:
+                raise ValueError(f"ntxent: zi_all and zj_all differ in shape: {tuple(zi_all.shape)} and {tuple(zj_all.shape)}")
+            if zi_all.dim() != 2 or zi_all.shape[1] != z_i.shape[1]:
+                raise ValueError(f"ntxent: zi_all / zj_all of shape {tuple(zi_all.shape)} do not have the width of z_i "
+                                 f"{tuple(z_i.shape)}")
+            if zi_all.device != z_i.device or zj_all.device != z_i.device:
+                raise ValueError(f"ntxent: zi_all (shape {tuple(zi_all.shape)}) on {zi_all.device} and zj_all on "
+                                 f"{zj_all.device}, z_i on {z_i.device}")
         n_local, D = z_i.shape
         if zi_all is None:
             zi_all, zj_all, row_begin = z_i, z_j, 0

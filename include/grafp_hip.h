@@ -485,6 +485,13 @@ int grafp_conv1x1_wgrad_f32(const float *grad_out, const float *x, int Cout, int
  *                  order: deterministic) */
 size_t grafp_ntxent_workspace(int B_all);
 int grafp_ntxent_num_partials(int n_local);
+/* The launch plan of a call (as grafp_conv1x1_wgrad_plan: a pure host function of the sizes; 1 <= n_local <= B_all):
+ * info (host, 8 ints) = {chunks of 128 candidate rows, first-pass splits, candidate rows per first-pass split,
+ *  second-pass splits, candidate rows per second-pass split, loss partials (= grafp_ntxent_num_partials), 0, 0}.
+ * Every split takes ceil(chunks / splits) chunks, so trailing splits can be empty.  Workspace layout (floats):
+ * lse[2 B_all] | pos[2 B_all] | first-pass triples [splits][2 B_all][3] | second-pass partial gradients
+ * [second-pass splits][2][n_local][D]. */
+int grafp_ntxent_plan(int B_all, int n_local, int *info);
 int grafp_ntxent_fwd_bwd_f32(const float *zi_all, const float *zj_all, int B_all, int D, int row_begin,
                              int n_local, float tau, float *loss_partial, float *dzi, float *dzj, void *ws,
                              size_t ws_bytes, grafp_stream_t stream);
