@@ -616,9 +616,8 @@ __global__ __launch_bounds__(256) void knn_exact_clip_kernel(const T *__restrict
         }
     }
     if (n == 0 || stop == 2) return;                           // (stop == 2: measurement builds, after the light queries)
-    const int W = N < 256 * KX_NU ? N : 256 * KX_NU;          // columns per range (N % 128 == 0)
+    const int Wmax = N < 256 * KX_NU ? N : 256 * KX_NU;       // columns per full range (N % 128 == 0)
     constexpr int VE = 16 / (int)sizeof(T);                    // elements per 16-byte vector
-    const int vrow = W / VE, nvec = chc * vrow;                // vectors per row / per chunk
     // a clip's heavy queries in groups of QG, each group one pass over the clip's features; most clips hold one to four
     // of them, and the pass is VALU work of (one division + QG fma) per candidate and channel: the narrow group for those
     auto passes = [&](auto qg) {
@@ -637,7 +636,11 @@ __global__ __launch_bounds__(256) void knn_exact_clip_kernel(const T *__restrict
             sqq[qi] = qi < ng ? sqb[s_list[g0 + qi]] : 0.0f;
             best[qi].init();
         }
-        for (int j0 = 0; j0 < N; j0 += W) {                    // candidate column ranges, ascending
+        for (int j0 = 0; j0 < N; j0 += Wmax) {                 // candidate column ranges, ascending
+            // the last range ends with the clip: N % 512 columns when that is not 0 (a multiple of 128, so a chunk is still
+            // a whole number of 64-vector wave instructions); behind it lie the next clip's nodes, or the end of x
+            const int W = N - j0 < Wmax ? N - j0 : Wmax;
+            const int vrow = W / VE, nvec = chc * vrow;        // vectors per row / per chunk
             float g[KX_NU][QG], dj[KX_NU];
 #pragma unroll
             for (int u = 0; u < KX_NU; ++u) {

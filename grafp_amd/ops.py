@@ -556,10 +556,12 @@ def knn_graph(x, k, normalize=True, layout="bcn", index_dtype=torch.int64, prefi
     x, B, C, N, sb, sc = _act_view(x.detach(), layout)
     idx = torch.empty((B, N, k), dtype=index_dtype, device=x.device)
     if (prefilter is None and switches.knn_split and normalize and index_dtype in (torch.int32, torch.int64)
-            and lib.grafp_knn_split_preferred_for(_DT[x.dtype], C, N, k)):
+            and lib.grafp_knn_split_preferred_for(_DT[x.dtype], C, N, k) and x.data_ptr() % 16 == 0):
         # split-bf16 Gram matrix + certified order, exact recomputation of the near-ties (knn_split.hip): the same
         # indices bit for bit, ~2x faster than the exact-f32 MFMA kernel below where the library prefers it (f32
-        # inputs: C <= 128; bf16 inputs, whose raw features are exact bf16 operands: every stage)
+        # inputs: C <= 128; bf16 inputs, whose raw features are exact bf16 operands: every stage).  Its 16-byte loads
+        # need an aligned first element (the rows are: N % 128 == 0); a view at another storage offset takes the
+        # exact-f32 kernel, whose normalisation pass reads element by element
         knn_graph_split(x, k, layout="raw", index_dtype=index_dtype, _view=(x, B, C, N, sb, sc), _out=idx)
         return idx
     if prefilter is None:
