@@ -121,6 +121,9 @@ SIGNATURES = {
     "grafp_identify_thin_f32": (_I, [_P, _L, _P, _I, _I, _P, _L, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "grafp_identify_pq_f32": (_I, [_P, _P, _L, _P, _I, _P, _I, _P, _I, _P, _L, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P,
                                    _P, _P]),
+    "grafp_identify_tempo_f32": (_I, [_P, _L, _P, _I, _P, _L, _P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P,
+                                      _P, _P]),
+    "grafp_identify_tempo_workspace": (_Z, [_I, _I, _I]),
     "grafp_self_match_workspace": (_Z, [_P, _I, _I, _I]),
     "grafp_self_match_f32": (_I, [_P, _L, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P, _P, _P]),
     "grafp_cross_match_f32": (_I, [_P, _L, _P, _I, _P, _L, _P, _I, _P, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P, _P,

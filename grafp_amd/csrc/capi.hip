@@ -127,6 +127,40 @@ extern "C" int grafp_identify_thin_f32(const float *index_rows, int64_t n, const
                                        out_score, out_votes, (hipStream_t)stream);
 }
 
+// Identification of recordings that play faster or slower than the catalogue (identify_tempo.hip): the checks shared
+// with grafp_identify_f32 here, the ratio checks, the 2^32 bound of the alignment key and the two launches there.
+namespace grafp {
+int identify_tempo_launch(const float *rows, int64_t n, const int64_t *first, int T, const float *q_rows,
+                          const int64_t *ids, int k, const int64_t *item_row, const int *item_len, int n_items,
+                          int max_len, int top, int min_overlap, const int32_t *ratio_num, int n_ratios, void *ws,
+                          int32_t *out_track, int32_t *out_offset, float *out_score, int32_t *out_votes,
+                          int32_t *out_ratio, hipStream_t stream);
+size_t identify_tempo_workspace(int n_items, int n_ratios, int top);
+}  // namespace grafp
+
+extern "C" size_t grafp_identify_tempo_workspace(int n_items, int n_ratios, int top) {
+    return grafp::identify_tempo_workspace(n_items, n_ratios, top);
+}
+
+extern "C" int grafp_identify_tempo_f32(const float *index_rows, int64_t n, const int64_t *track_first_row,
+                                        int n_tracks, const float *q_rows, int64_t n_qrows, const int64_t *topk_ids,
+                                        int k, const int64_t *item_row, const int *item_len, int n_items, int max_len,
+                                        int top, int min_overlap, const int32_t *ratio_num, int n_ratios, void *ws,
+                                        int32_t *out_track, int32_t *out_offset, float *out_score, int32_t *out_votes,
+                                        int32_t *out_ratio, grafp_stream_t stream) {
+    GRAFP_REQUIRE(index_rows && track_first_row && q_rows && topk_ids && item_row && item_len && ratio_num &&
+                  out_track && out_offset && out_score && out_votes && out_ratio, "identify_tempo: null pointer");
+    GRAFP_REQUIRE(n >= 1 && n < 0x7fffff00ll && n_tracks >= 1 && n_qrows >= 1 && n_items >= 0,
+                  "identify_tempo: bad sizes n=%lld n_tracks=%d n_qrows=%lld n_items=%d", (long long)n, n_tracks,
+                  (long long)n_qrows, n_items);
+    GRAFP_REQUIRE(top >= 1 && top <= 64, "identify_tempo: top=%d not in [1, 64]", top);
+    GRAFP_REQUIRE((((uintptr_t)index_rows | (uintptr_t)q_rows) & 15) == 0,
+                  "identify_tempo: rows must be 16-byte aligned");
+    return grafp::identify_tempo_launch(index_rows, n, track_first_row, n_tracks, q_rows, topk_ids, k, item_row,
+                                        item_len, n_items, max_len, top, min_overlap, ratio_num, n_ratios, ws, out_track,
+                                        out_offset, out_score, out_votes, out_ratio, (hipStream_t)stream);
+}
+
 // Identification against a library held as IVF-PQ codes (identify_pq.hip): argument checks here, the kernels there.
 namespace grafp {
 int identify_pq_launch(const int32_t *list_id, const unsigned char *codes, int64_t n, const float *centroids, int nlist,

@@ -35,7 +35,8 @@
 //      smaller a); it becomes ~ord(score) << 32 | t, every other entry empty;
 //   5. bitonic sort of those; the first `top` entries are the result.
 // The five phases are identify_item of identify_core.h, shared with identify_pq.hip (the same operation on a library held
-// as IVF-PQ codes) and identify_thin.hip (a library that keeps every D-th row of a track); this file supplies the row grid
+// as IVF-PQ codes), identify_thin.hip (a library that keeps every D-th row of a track) and identify_tempo.hip (recordings
+// that play faster or slower than the catalogue: one run of the phases per speed ratio); this file supplies the row grid
 // (DenseGrid: one row per segment), the span rows of phase 3 (RowSpan of span_rows.h: the resident f32 rows) and the launch.
 // Built WITHOUT packed-f32 instructions (Makefile NOPK, as corpus.hip): its sums are plain fmaf chains, and the packed
 // operand-select form is the hazard of DESIGN.md section 12.7b.

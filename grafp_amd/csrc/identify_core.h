@@ -17,6 +17,13 @@
 //   DenseGrid   one row per fine position (identify.hip, identify_pq.hip): a = r - s, pairs are consecutive rows
 //   ThinGrid    every D-th position of each track is kept (identify_thin.hip): a = r * D - s, the query steps D rows
 //               per pair and the library one (the Span functor carries the query step)
+// A grid also says where the query rows sit, for a recording that does not run at the catalogue's speed:
+//     int at(int s)              rows after query row 0 at which query row s sits (s on the two grids above)
+//     int shift()                the key shift: fine(r) - at(s) + shift() >= 0 for every hit
+//     int64_t cap(int64_t L)     the pairs a track of L rows can always hold (caps need in the eligibility rule)
+//     float score(span, q4, a, lo, l, m)   the span call of phase 3: m pairs from query row lo on
+//   TempoGrid   one row per fine position, query row s sits w(s) = (s * num + 128) >> 8 rows after row 0
+//               (identify_tempo.hip): a = r - w(s), the library rows of the pairs are gathered (TempoRowSpan)
 // Compiles with and without the packed-f32 instructions; every user is built without (Makefile NOPK).
 #pragma once
 #include <limits.h>
@@ -32,6 +39,9 @@ constexpr int ID_MAX_LEN = 256;
 constexpr int ID_MAX_K = 32;
 constexpr int ID_MAX_KEYS = 8192;
 constexpr int ID_SHIFT = ID_MAX_LEN - 1;                 // a + ID_SHIFT >= 0 for every hit
+constexpr int ID_TEMPO_DEN = 256;                        // TempoGrid: a ratio is num / 256
+constexpr int ID_TEMPO_MIN = 128, ID_TEMPO_MAX = 512;    // the range of num
+constexpr int ID_TEMPO_SHIFT = 511;                      // w(255) = 510 at num = 512
 constexpr int ID_MAX_STRIDE = 32;                        // ThinGrid: the largest row stride
 constexpr size_t ID_LDS = 160 * 1024 - 256;      // dynamic LDS budget (the static s_ncand sits next to it)
 
@@ -60,6 +70,13 @@ struct DenseGrid {
         const int hi = (int)(f1 - a < ql ? f1 - a : ql);
         o = hi - lo;
     }
+    __device__ __forceinline__ int at(int s) const { return s; }
+    __device__ __forceinline__ int shift() const { return ID_SHIFT; }
+    __device__ __forceinline__ int64_t cap(int64_t L) const { return L; }
+    template <typename Span>
+    __device__ __forceinline__ float score(const Span &span, const float4 *q4, int64_t a, int lo, int l, int m) const {
+        return span(q4 + lo * (SEQ_D / 4) + l, row(a + lo), l, m);
+    }
 };
 
 // Every D-th fine position of each track, D in [1, ID_MAX_STRIDE]; the host keeps n * D + ID_SHIFT below 2^32, so
@@ -81,9 +98,47 @@ struct ThinGrid {
         lo = any ? (int)lo64 : 0;
         o = any ? (int)((hi64 - lo64 + D - 1) / D) : 0;
     }
+    __device__ __forceinline__ int at(int s) const { return s; }
+    __device__ __forceinline__ int shift() const { return ID_SHIFT; }
+    __device__ __forceinline__ int64_t cap(int64_t L) const { return L; }
+    template <typename Span>
+    __device__ __forceinline__ float score(const Span &span, const float4 *q4, int64_t a, int lo, int l, int m) const {
+        return span(q4 + lo * (SEQ_D / 4) + l, row(a + lo), l, m);
+    }
 };
 
-// One item by one workgroup of ID_THREADS threads (blockIdx.x = the item).
+// One row per fine position; the recording runs at num / 256 of the catalogue's speed, so query row s sits
+// w(s) = (s * num + 128) >> 8 rows after query row 0 (num in [ID_TEMPO_MIN, ID_TEMPO_MAX]; w(s) <= 510 for s <= 255).
+// w never decreases, so the pairs of an alignment are a contiguous range of s: w(s) >= x iff s * num + 128 >= 256 * x.
+// The host keeps n + ID_TEMPO_SHIFT below 2^32.  Its Span gathers: span(x, a, lo, num, l, m) reads row a + w(lo + t).
+struct TempoGrid {
+    int num;
+    __device__ __forceinline__ int64_t fine(int64_t r) const { return r; }
+    __device__ __forceinline__ int64_t row(int64_t p) const { return p; }
+    __device__ __forceinline__ int need(int need_q) const { return need_q; }
+    __device__ __forceinline__ int at(int s) const { return (s * num + ID_TEMPO_DEN / 2) >> 8; }
+    __device__ __forceinline__ int shift() const { return ID_TEMPO_SHIFT; }
+    __device__ __forceinline__ int64_t cap(int64_t L) const {
+        const int64_t c = L * ID_TEMPO_DEN / num;
+        return c > 1 ? c : 1;
+    }
+    // the first s in [0, ql] with w(s) >= x (ql: none)
+    __device__ __forceinline__ int first_at(int64_t x, int ql) const {
+        if (x <= 0) return 0;
+        const int64_t s = (x * ID_TEMPO_DEN - ID_TEMPO_DEN / 2 + num - 1) / num;
+        return s < ql ? (int)s : ql;
+    }
+    __device__ __forceinline__ void pairs(int64_t a, int64_t f0, int64_t f1, int ql, int &lo, int &o) const {
+        lo = first_at(f0 - a, ql);
+        o = first_at(f1 - a, ql) - lo;
+    }
+    template <typename Span>
+    __device__ __forceinline__ float score(const Span &span, const float4 *q4, int64_t a, int lo, int l, int m) const {
+        return span(q4 + lo * (SEQ_D / 4) + l, a, lo, num, l, m);
+    }
+};
+
+// One item by one workgroup of ID_THREADS threads (blockIdx.x = the item); the four outputs are (gridDim.x, top).
 template <bool kQLds, typename Grid, typename Span>
 __device__ __forceinline__ void identify_item(
     const Grid &grid, const Span &span, int64_t n, const int64_t *__restrict__ first, int T,
@@ -117,7 +172,7 @@ __device__ __forceinline__ void identify_item(
         if (e < total) {
             const int s = e / k;
             const int64_t r = ids[(r0 + s) * k + (e - s * k)];
-            if (r >= 0 && r < n) key = ((unsigned long long)(grid.fine(r) - s + ID_SHIFT) << 32) | (unsigned int)s;
+            if (r >= 0 && r < n) key = ((unsigned long long)(grid.fine(r) - grid.at(s) + grid.shift()) << 32) | (unsigned int)s;
         }
         keys[e] = key;
     }
@@ -134,13 +189,13 @@ __device__ __forceinline__ void identify_item(
     for (int e = tid, it = 0; e < P; e += ID_THREADS, ++it) {
         if (!((head >> it) & 1u)) continue;
         const unsigned long long hi = keys[e] >> 32;
-        const int64_t a = (int64_t)hi - ID_SHIFT;
+        const int64_t a = (int64_t)hi - grid.shift();
         int start = e, nv = 0, t = 0;
         int64_t end = -1;
         for (int f = e; f < P; ++f) {
             const unsigned long long key = keys[f];
             if ((key >> 32) != hi) break;                   // the next run, or the empty tail
-            const int64_t r = grid.row(a + (int64_t)(unsigned int)key);
+            const int64_t r = grid.row(a + grid.at((int)(unsigned int)key));
             if (r >= end) {                                 // first hit, or the run crossed into a later track
                 if (nv) {
                     keys[start] = hi << 32;
@@ -171,7 +226,7 @@ __device__ __forceinline__ void identify_item(
     const float4 *q4 = kQLds ? reinterpret_cast<const float4 *>(sq) : reinterpret_cast<const float4 *>(q_rows + r0 * SEQ_D);
     for (int c = hw; c < ncand; c += ID_THREADS / 32) {
         const int e = idx[c];
-        const int64_t a = (int64_t)(keys[e] >> 32) - ID_SHIFT;
+        const int64_t a = (int64_t)(keys[e] >> 32) - grid.shift();
         const int t = (int)aux[e];
         int64_t f0 = first[t], f1 = first[t + 1];
         f0 = f0 < 0 ? 0 : f0;                               // (a valid table needs neither clamp)
@@ -179,13 +234,14 @@ __device__ __forceinline__ void identify_item(
         const int64_t L = f1 - f0;
         int lo, o;
         grid.pairs(a, f0, f1, ql, lo, o);
-        const bool ok = o >= 1 && o >= (need < L ? need : L);
-        const float acc = span(q4 + lo * (SEQ_D / 4) + l, grid.row(a + lo), l, ok ? o : 0);   // (not ok: nothing read)
+        const int64_t cap = grid.cap(L);
+        const bool ok = o >= 1 && o >= (need < cap ? need : cap);
+        const float acc = grid.score(span, q4, a, lo, l, ok ? o : 0);                         // (not ok: nothing read)
         const float score = acc / (float)o;
         // every lane of the half-wave has read keys[e] and aux[e] before the shuffles above
         if (l == 0) {
             keys[e] = ok ? (((unsigned long long)t << 32) | ~f32_ord(score)) : SEQ_NONE;
-            aux[e] = (unsigned int)(a + ID_SHIFT);
+            aux[e] = (unsigned int)(a + grid.shift());
         }
     }
     __syncthreads();
@@ -215,7 +271,7 @@ __device__ __forceinline__ void identify_item(
             const int t = (int)(key & 0xffffffffull);
             const int slot = idx[tid];
             out_track[o] = t;
-            out_offset[o] = (int32_t)((int64_t)aux[slot] - ID_SHIFT - grid.fine(first[t]));
+            out_offset[o] = (int32_t)((int64_t)aux[slot] - grid.shift() - grid.fine(first[t]));
             out_score[o] = ord_f32(~(unsigned int)(key >> 32));
             out_votes[o] = (int32_t)votes[slot];
         } else {

@@ -6,6 +6,7 @@
 // score in span_sum's order (seqmatch.h).
 //   RowSpan<kUnroll>      the library's resident (n, 128) f32 rows     identify.hip, selfmatch.hip, crossmatch.hip
 //   StridedRowSpan<kUnroll>   the same rows, the x rows of consecutive pairs x_step float4s apart    identify_thin.hip
+//   TempoRowSpan<kUnroll>     the same rows, gathered along a sloped alignment (its own call, see there)  identify_tempo.hip
 //   PqSpan<kM, kUnroll>   rows decoded from IVF-PQ codes while scored  identify_pq.hip, crossmatch.hip
 // Library row r of the compact form is
 //   dec[r][j] = centroids[list_id[r]][j] + codebooks[m][codes[r][m]][c],  m = j / dsub, c = j % dsub, dsub = 128 / M
@@ -32,6 +33,29 @@ struct StridedRowSpan {
     int x_step;                                  // float4s between the x rows of two consecutive pairs
     __device__ __forceinline__ float operator()(const float4 *x, int64_t row, int l, int m) const {
         return span_sum<kUnroll>(x, rw4 + row * (SEQ_D / 4) + l, m, x_step);
+    }
+};
+
+// The pairs of a recording that runs at num / 256 of the catalogue's speed (TempoGrid of identify_core.h): pair t is
+// query row lo + t with library row a + w(lo + t), w(s) = (s * num + 128) >> 8, so the library rows are gathered (one
+// row may be read twice, rows may be skipped).  span_sum's order; at num = 256 the rows and so the bits are RowSpan's.
+template <int kUnroll>
+struct TempoRowSpan {
+    const float4 *rw4;
+    __device__ __forceinline__ float operator()(const float4 *x, int64_t a, int lo, int num, int l, int m) const {
+        float acc = 0.0f;
+#pragma unroll kUnroll
+        for (int t = 0; t < m; ++t) {
+            const int64_t row = a + (((lo + t) * num + 128) >> 8);
+            const float4 q = x[(int64_t)t * (SEQ_D / 4)], r = rw4[row * (SEQ_D / 4) + l];
+            acc = __builtin_fmaf(q.x, r.x, acc);
+            acc = __builtin_fmaf(q.y, r.y, acc);
+            acc = __builtin_fmaf(q.z, r.z, acc);
+            acc = __builtin_fmaf(q.w, r.w, acc);
+        }
+#pragma unroll
+        for (int s = 16; s > 0; s >>= 1) acc += __shfl_xor(acc, s);      // stays inside the 32-lane half
+        return acc;
     }
 };
 

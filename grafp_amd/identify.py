@@ -4,6 +4,7 @@
                                        [--index flat|ivfpq --nlist 64 --pq-m 64 --nprobe 20 --train-rows 65536]
                                        [--row-stride D]
   python -m grafp_amd.identify query --ckp MODEL.pth --library LIBDIR FILES... [--top 5] [--window S --hop S]
+                                       [--tempo X [--tempo-step G]]
   python -m grafp_amd.identify dedup --ckp MODEL.pth --library LIBDIR [--min-overlap 3] [--coverage 0.9] [--json OUT]
   python -m grafp_amd.identify match --ckp MODEL.pth --library LIBDIR FILES... [--min-overlap 3] [--min-votes 4]
                                        [--min-score S] [--top 8] [--k-probe 20] [--json OUT]
@@ -17,7 +18,9 @@ of tracks that share audio, then one per group of duplicates (--json also writes
 recordings that are not in the library and prints one JSON object per (recording, library track) that share audio, with
 the span and the coverage (either form of a library; --json also writes them to a file).  build --row-stride D keeps
 every D-th fingerprint row of each track (a flat library of 772 / D bytes per original row; `query` works on it
-unchanged, `dedup` and `match` need every row).  `monitor` treats every file as one live channel: it feeds them to a
+unchanged, `dedup` and `match` need every row).  query --tempo X also searches recordings that play up to X (0.06: six
+per cent) faster or slower than the catalogue (a flat library that keeps every row; every match and timeline span then
+carries "tempo" next to its score; --tempo-step G spaces the ratios searched G / 256 apart).  `monitor` treats every file as one live channel: it feeds them to a
 StreamMonitor (grafp_amd/monitor.py) chunk by chunk, all channels per push, prints one JSON object per window as it
 becomes due ({"channel", "file", start_s, end_s, segment_start_s, matches}) and, when the files end, one per timeline
 span of each channel ({"channel", "file", "span": ...})."""
@@ -66,6 +69,9 @@ def main(argv=None):
     q.add_argument("--k-probe", type=int, default=20)
     q.add_argument("--window", type=float, default=None, help="seconds per window: report a timeline per file")
     q.add_argument("--hop", type=float, default=1.0)
+    q.add_argument("--tempo", type=float, default=None,
+                   help="also search recordings that play up to this fraction faster or slower (0.06: 0.94 to 1.06)")
+    q.add_argument("--tempo-step", type=int, default=None, help="spacing of the ratios searched, in 1/256")
     q.add_argument("--force", action="store_true", help="use a library made with another model")
     d = sub.add_parser("dedup", help="find tracks of a library that share audio")
     d.add_argument("--config", default=DEFAULT_CONFIG, help="model configuration (the library keeps its own "
@@ -174,12 +180,13 @@ def main(argv=None):
                 json.dump({"matches": found}, f, indent=1)
         return 0
     if args.window is None:
-        for path, matches in zip(args.files, lib.identify(list(args.files), top=args.top, k_probe=args.k_probe)):
+        for path, matches in zip(args.files, lib.identify(list(args.files), top=args.top, k_probe=args.k_probe,
+                                                            tempo=args.tempo, tempo_step=args.tempo_step)):
             print(json.dumps({"query": path, "matches": matches}))
     else:
         for path in args.files:
             windows = lib.identify_windows(path, window_s=args.window, hop_s=args.hop, top=args.top,
-                                           k_probe=args.k_probe)
+                                           k_probe=args.k_probe, tempo=args.tempo, tempo_step=args.tempo_step)
             for span in lib.timeline(windows):
                 print(json.dumps({"query": path, **span}))
     return 0

@@ -21,6 +21,12 @@ over D times fewer rows and a build that runs the model on D times fewer segment
 timeline work on it through ops.identify_thin (csrc/identify_thin.hip).  compress(), self_matches() and match() need
 every row (row_stride 1).
 
+identify(tempo=...) and identify_windows(tempo=...) also find recordings that play a few per cent faster or slower
+than the catalogue: the same embed and search, then one ops.identify_tempo launch (csrc/identify_tempo.hip) that scores
+every candidate along the sloped alignment of each speed ratio of tempo_ratios(); timeline() follows such windows along
+their slope.  A flat library that keeps every row only; speed, not pitch; match(), self_matches() and StreamMonitor know
+no tempo.
+
 match() takes whole recordings of any length that are NOT in the library and says which tracks they share audio with,
 where and how much (spans, coverage, votes: what self_matches says about the library's own tracks) -- the question an
 ingest gate asks before add().  It runs on ops.cross_match (f32 rows) or ops.cross_match_pq (codes), the kernels of
@@ -92,6 +98,39 @@ def window_items(n_seg_total, n_samples, settings, window_s=3.0, hop_s=1.0):
         rows.append(j0)
         lens.append(max(0, min(per_window, n_seg_total - j0)))
     return np.array(starts, np.float64), np.array(rows, np.int64), np.array(lens, np.int32)
+
+
+def tempo_ratios(tempo, max_len, step=None):
+    """The ratio grid of a tempo search over items of up to max_len segments, as ops.identify_tempo takes it: ascending
+    int32 `num`, each standing for num / 256 track seconds per recording second.
+    tempo: a float x in (0, 0.5] meaning the ratios [1 - x, 1 + x], or a pair (lo, hi) of ratios.  step: the grid's
+    spacing in units of 1/256; by default g = max(1, 256 // max_len), with which the nearest grid ratio is at most half
+    a row off at the item's end.  The result is 256 + i * g for the integers i that land inside
+    [ceil(256 * lo), floor(256 * hi)] clipped to [128, 512]."""
+    if isinstance(tempo, (tuple, list, np.ndarray)):
+        if len(tempo) != 2:
+            raise ValueError(f"tempo must be one number or a pair (lo, hi) of ratios, got {tempo!r}")
+        lo, hi = float(tempo[0]), float(tempo[1])
+    else:
+        x = float(tempo)
+        if not 0.0 < x <= 0.5:
+            raise ValueError(f"tempo={x} must lie in (0, 0.5]: the ratios searched are [1 - tempo, 1 + tempo]")
+        lo, hi = 1.0 - x, 1.0 + x
+    if not lo <= hi:
+        raise ValueError(f"tempo=({lo}, {hi}): the lower ratio is above the upper one")
+    g = max(1, ops.IDENTIFY_TEMPO_DEN // max(1, int(max_len))) if step is None else int(step)
+    if g < 1:
+        raise ValueError(f"tempo: step={g} must be at least 1 (in units of 1/256)")
+    a = max(ops.IDENTIFY_TEMPO_MIN, int(math.ceil(ops.IDENTIFY_TEMPO_DEN * lo - 1e-9)))
+    b = min(ops.IDENTIFY_TEMPO_MAX, int(math.floor(ops.IDENTIFY_TEMPO_DEN * hi + 1e-9)))
+    i0, i1 = -((ops.IDENTIFY_TEMPO_DEN - a) // g), (b - ops.IDENTIFY_TEMPO_DEN) // g
+    nums = ops.IDENTIFY_TEMPO_DEN + g * np.arange(i0, i1 + 1, dtype=np.int64)
+    if nums.size == 0:
+        raise ValueError(f"tempo: no ratio 256 + i * {g} lies in [{a}, {b}] / 256; give a smaller step")
+    if nums.size > ops.IDENTIFY_TEMPO_MAX_RATIOS:
+        raise ValueError(f"tempo: {nums.size} ratios from {a} to {b} at step={g} exceed the "
+                         f"{ops.IDENTIFY_TEMPO_MAX_RATIOS} of one launch; give a larger step or a narrower range")
+    return nums.astype(np.int32)
 
 
 def _as_waveforms(tracks):
@@ -589,10 +628,11 @@ class FingerprintLibrary:
         k = min(int(k_probe), self.n_rows)
         return self.index.search(q, k)[1]
 
-    def _identify_items(self, q, ids, item_row, item_len, top, min_overlap, max_len=None):
+    def _identify_items(self, q, ids, item_row, item_len, top, min_overlap, max_len=None, tempo=None, tempo_step=None):
         """One identify launch (the kernel of the library's form) for all items over the rows q and their hits ids ->
         per-item lists of matches.  max_len: an upper bound of the items' lengths (None: the longest).  (StreamMonitor
-        calls it with rows it kept from earlier pushes.)"""
+        calls it with rows it kept from earlier pushes.)  tempo: tempo_ratios' argument; the launch is then
+        ops.identify_tempo over the ratio grid of the longest item, and every match names its ratio."""
         n_items = len(item_row)
         longest = int(np.max(item_len, initial=0))
         if n_items == 0 or longest == 0:
@@ -601,7 +641,13 @@ class FingerprintLibrary:
         dev = self.device
         tail = (torch.from_numpy(self.first).to(dev), q, ids, torch.from_numpy(np.asarray(item_row, np.int64)).to(dev),
                 torch.from_numpy(np.asarray(item_len, np.int32)).to(dev))
-        if self.is_compact:
+        ra = None
+        if tempo is not None:
+            nums = tempo_ratios(tempo, longest, tempo_step)
+            tr, off, sc, vo, ra = ops.identify_tempo(self.rows(), *tail, nums, top=top, min_overlap=min_overlap,
+                                                     max_len=max_len)
+            ra = ra.cpu().numpy()
+        elif self.is_compact:
             tr, off, sc, vo = ops.identify_pq(*self.codes(), self._pq["centroids"], self._pq["codebooks"], *tail,
                                               top=top, min_overlap=min_overlap, max_len=max_len)
         elif self._row_stride != 1:
@@ -621,24 +667,42 @@ class FingerprintLibrary:
                 res.append({"track": t, "name": self.names[t], "offset": int(off[i, j]),
                             "offset_s": int(off[i, j]) * step * hop / fs, "score": float(sc[i, j]),
                             "votes": int(vo[i, j])})
+                if ra is not None:
+                    res[-1]["tempo"] = int(ra[i, j]) / ops.IDENTIFY_TEMPO_DEN
+                    res[-1]["tempo_num"] = int(ra[i, j])
             out.append(res)
         return out
 
-    def _search_and_identify(self, segs, item_row, item_len, top, k_probe, min_overlap):
+    def _need_tempo_form(self, what, tempo):
+        if tempo is not None:
+            self._need_flat(f"{what}(tempo=...)")
+            self._need_dense(f"{what}(tempo=...)")
+
+    def _search_and_identify(self, segs, item_row, item_len, top, k_probe, min_overlap, tempo=None, tempo_step=None):
         """One batched embed + search of all segments, one ops.identify launch for all items -> per-item lists.  (The
         queries' segments are all embedded, whatever the library's row_stride: the query side stays dense.)"""
         n_items = len(item_row)
+        if tempo is not None:
+            tempo_ratios(tempo, max(1, int(np.max(item_len, initial=0))), tempo_step)      # refuse a bad range early
         if n_items == 0 or segs.shape[0] == 0 or self.n_rows == 0 or int(np.max(item_len, initial=0)) == 0:
             return [[] for _ in range(n_items)]
         self._check_item_len(int(np.max(item_len)), k_probe)
         q, ids = self._embed_and_search(segs, k_probe)
-        return self._identify_items(q, ids, item_row, item_len, top, min_overlap)
+        return self._identify_items(q, ids, item_row, item_len, top, min_overlap, tempo=tempo, tempo_step=tempo_step)
 
-    def identify(self, queries, fs=None, top=5, k_probe=20, min_overlap=None):
+    def identify(self, queries, fs=None, top=5, k_probe=20, min_overlap=None, tempo=None, tempo_step=None):
         """queries: one waveform, a list of ragged waveforms, or file paths; at `fs` (default settings['fs']; other rates
         are resampled on the device).  -> per query, a list of matches {track, name, offset, offset_s, score, votes},
         best first.  offset_s = offset * step * hop_len / fs is where the query's first segment sits in the track.  A
-        query shorter than one segment gives an empty list."""
+        query shorter than one segment gives an empty list.
+        tempo: None, or the speeds to search for a recording that plays faster or slower than the catalogue -- a float
+        x in (0, 0.5] for the ratios [1 - x, 1 + x] (track seconds per recording second), or a pair (lo, hi);
+        tempo_step: the ratio grid's spacing in 1/256 (tempo_ratios; default: from the longest query).  The segments
+        are embedded and searched as without it and one ops.identify_tempo launch scores every candidate along the
+        sloped alignment of every ratio; each match then also carries "tempo" (the ratio) and "tempo_num" (ratio *
+        256), and offset / offset_s keep their meaning.  Needs a flat library that keeps every row.  Speed only: pitch
+        is not searched, and match(), self_matches(), StreamMonitor, the IVF-PQ and the thinned forms know no tempo."""
+        self._need_tempo_form("identify", tempo)
         single = isinstance(queries, (str, np.ndarray, torch.Tensor)) and (
             isinstance(queries, str) or torch.as_tensor(queries).dim() == 1)
         waves = self._load_queries(queries, fs)
@@ -646,18 +710,20 @@ class FingerprintLibrary:
         lens = np.array([s.shape[0] for s in segs], np.int32)
         rows = np.concatenate([[0], np.cumsum(lens[:-1])]).astype(np.int64) if len(lens) else np.zeros(0, np.int64)
         allsegs = torch.cat(segs, dim=0) if segs else torch.empty((0,), device=self.device)
-        res = self._search_and_identify(allsegs, rows, lens, int(top), int(k_probe), min_overlap)
+        res = self._search_and_identify(allsegs, rows, lens, int(top), int(k_probe), min_overlap, tempo, tempo_step)
         return res[0] if single and len(res) == 1 else res
 
-    def identify_windows(self, recording, window_s=3.0, hop_s=1.0, fs=None, top=5, k_probe=20, min_overlap=None):
+    def identify_windows(self, recording, window_s=3.0, hop_s=1.0, fs=None, top=5, k_probe=20, min_overlap=None,
+                         tempo=None, tempo_step=None):
         """A long recording cut into items of window_s seconds every hop_s seconds.  The recording is segmented,
         fingerprinted and searched once; all windows are identified in one launch.  -> per window
         {start_s, end_s, segment_start_s, matches}; segment_start_s is where the window's first segment starts in the
-        recording (the time its matches' offset_s refers to)."""
+        recording (the time its matches' offset_s refers to).  tempo, tempo_step: as for identify()."""
+        self._need_tempo_form("identify_windows", tempo)
         wave = self._load_queries([recording], fs)[0]
         segs = self.segments(wave)
         starts, rows, lens = window_items(segs.shape[0], wave.numel(), self.settings, window_s, hop_s)
-        res = self._search_and_identify(segs, rows, lens, int(top), int(k_probe), min_overlap)
+        res = self._search_and_identify(segs, rows, lens, int(top), int(k_probe), min_overlap, tempo, tempo_step)
         seg_s = self.segment_s
         return [{"start_s": float(s), "end_s": float(s) + window_s, "segment_start_s": int(r) * seg_s, "matches": m}
                 for s, r, m in zip(starts, rows, res)]
@@ -665,15 +731,35 @@ class FingerprintLibrary:
     def timeline(self, windows, min_score=None):
         """What played when: consecutive windows whose best match is the same track at a consistent position (the
         track offset minus the window's segment start agrees within one segment hop) merge into one span.
-        -> list of {start_s, end_s, track, name, track_offset_s (the track position at start_s), score (mean)}."""
+        -> list of {start_s, end_s, track, name, track_offset_s (the track position at start_s), score (mean)}.
+        A window whose match carries a "tempo" rho (identify_windows(tempo=...)) is followed along its slope: the span
+        keeps its last merged window (u = segment_start_s, o = offset_s, rho), and the next window (u', o') of the same
+        track merges iff |o' - (o + rho * (u' - u))| is within one segment hop and it starts no later than the span's
+        end; the reference point then advances.  Such a span also reports "tempo", the mean of its windows' rho."""
         spans, seg_s = [], self.segment_s
         for w in windows:
             if not w["matches"] or (min_score is not None and w["matches"][0]["score"] < min_score):
                 continue
             m = w["matches"][0]
+            if "tempo" in m:
+                u, o, rho = w["segment_start_s"], m["offset_s"], m["tempo"]
+                last = spans[-1] if spans else None
+                if (last is not None and last["track"] == m["track"] and "_ref" in last
+                        and abs(o - (last["_ref"][1] + last["_ref"][2] * (u - last["_ref"][0]))) <= seg_s + 1e-9
+                        and w["start_s"] <= last["end_s"]):
+                    last["end_s"] = w["end_s"]
+                    last["_scores"].append(m["score"])
+                    last["_tempos"].append(rho)
+                else:
+                    spans.append({"start_s": w["start_s"], "end_s": w["end_s"], "track": m["track"], "name": m["name"],
+                                  "track_offset_s": o + rho * (w["start_s"] - u), "_scores": [m["score"]],
+                                  "_tempos": [rho]})
+                spans[-1]["_ref"] = (u, o, rho)
+                continue
             delta = m["offset_s"] - w["segment_start_s"]              # track time = recording time + delta
             last = spans[-1] if spans else None
-            if (last is not None and last["track"] == m["track"] and abs(delta - last["_delta"]) <= seg_s + 1e-9
+            if (last is not None and last["track"] == m["track"] and "_delta" in last
+                    and abs(delta - last["_delta"]) <= seg_s + 1e-9
                     and w["start_s"] <= last["end_s"]):
                 last["end_s"] = w["end_s"]
                 last["_scores"].append(m["score"])
@@ -682,7 +768,9 @@ class FingerprintLibrary:
                               "track_offset_s": w["start_s"] + delta, "_delta": delta, "_scores": [m["score"]]})
         for s in spans:
             s["score"] = float(np.mean(s.pop("_scores")))
-            s.pop("_delta")
+            s.pop("_delta", None)
+            if s.pop("_ref", None) is not None:
+                s["tempo"] = float(np.mean(s.pop("_tempos")))
         return spans
 
     # ---- the catalog itself ------------------------------------------------------------------------------------

@@ -1790,7 +1790,76 @@ def identify_thin(index_rows, track_first_row, q_rows, topk_ids, item_row, item_
     return outs
 
 
-IDENTIFY_PQ_M = (16, 32, 64, 128)                                       # identify_pq.hip's sub-quantiser counts
+IDENTIFY_TEMPO_MAX_RATIOS = 64                                           # identify_tempo.hip's ratios per call
+IDENTIFY_TEMPO_MIN, IDENTIFY_TEMPO_MAX, IDENTIFY_TEMPO_DEN = 128, 512, 256   # a ratio is num / 256
+
+
+def identify_tempo(index_rows, track_first_row, q_rows, topk_ids, item_row, item_len, ratio_num, top=5,
+                   min_overlap=None, max_len=None):
+    """ops.identify for recordings that play faster or slower than the catalogue (grafp_identify_tempo_f32: one
+    workgroup per item and ratio, then one per item that merges the ratios' lists).  ratio_num: 1 to 64 strictly
+    ascending integers in [128, 512] (host values), each standing for num / 256 track seconds per recording second.
+    At ratio num query row s sits w(s) = (s * num + 128) >> 8 library rows after query row 0.  A hit (s, r) names the
+    track t holding r and the alignment a = r - w(s); the pairs of (t, a, num) are the query rows s with a + w(s) inside
+    t, o of them; the candidate is eligible iff o >= 1 and o >= min(need, max(1, rows of t * 256 // num)) with need =
+    min_overlap (None: the item's length), and scores the mean dot product over its pairs in ops.identify's arithmetic
+    order.  Per track the best candidate: highest score, then the ratio nearer to 1 (smaller |num - 256|, then smaller
+    num), then the smaller a.
+    Returns (track, offset, score, votes, ratio int32 = num), each (n_items, top), padded with -1 / INT_MIN / -inf / 0 /
+    0; offset = a - first[t] is where the item's first row sits in the track.  Everything else (arguments, ranking,
+    max_len) as for ops.identify, whose four outputs this equals bit for bit at ratio_num = [256]."""
+    n_items, k, top = int(item_row.shape[0]), int(topk_ids.shape[1]), int(top)
+    # argument checks first (host values only): they hold on any device
+    if not 1 <= top <= 64:
+        raise ValueError(f"identify_tempo: top={top} not in [1, 64]")
+    if not 1 <= k <= IDENTIFY_MAX_K:
+        raise ValueError(f"identify_tempo: k={k} hits per segment exceeds {IDENTIFY_MAX_K}")
+    if min_overlap is not None and int(min_overlap) < 1:
+        raise ValueError("identify_tempo: min_overlap must be at least 1 segment")
+    if max_len is None and n_items:
+        max_len = max(1, int(item_len.max().item()))
+        check_track_table(track_first_row, index_rows.shape[0])
+        _check_items_inside("identify_tempo", item_row, item_len, q_rows.shape[0])
+    if max_len is not None and (int(max_len) > IDENTIFY_MAX_LEN or int(max_len) * k > IDENTIFY_MAX_KEYS):
+        raise ValueError(f"identify_tempo: items of {int(max_len)} segments with k={k} exceed {IDENTIFY_MAX_LEN} "
+                         f"segments or {IDENTIFY_MAX_KEYS} hits per item")
+    ratios = [int(v) for v in torch.as_tensor(ratio_num).reshape(-1).tolist()]
+    if not 1 <= len(ratios) <= IDENTIFY_TEMPO_MAX_RATIOS:
+        raise ValueError(f"identify_tempo: {len(ratios)} ratios, not 1 to {IDENTIFY_TEMPO_MAX_RATIOS}")
+    if any(b <= a for a, b in zip(ratios, ratios[1:])):
+        raise ValueError("identify_tempo: ratio_num must be strictly ascending")
+    if not all(IDENTIFY_TEMPO_MIN <= v <= IDENTIFY_TEMPO_MAX for v in ratios):
+        raise ValueError(f"identify_tempo: every ratio must lie in [{IDENTIFY_TEMPO_MIN}, {IDENTIFY_TEMPO_MAX}] "
+                         f"(got {min(ratios)} .. {max(ratios)})")
+    if int(index_rows.shape[0]) + 2 * IDENTIFY_MAX_LEN - 1 >= 1 << 32:
+        raise ValueError(f"identify_tempo: {int(index_rows.shape[0])} rows reach past the 2^32 alignments a key holds")
+    _require_gpu(index_rows, q_rows, topk_ids, item_row, item_len)
+    index_rows, q_rows = _f32c(index_rows), _f32c(q_rows)
+    dev = index_rows.device
+    first = torch.as_tensor(track_first_row).detach().to(device=dev, dtype=torch.int64).contiguous()
+    topk_ids = topk_ids.to(torch.int64).contiguous()
+    item_row = item_row.to(torch.int64).contiguous()
+    item_len = item_len.to(torch.int32).contiguous()
+    outs = (torch.empty((n_items, top), dtype=torch.int32, device=dev),
+            torch.empty((n_items, top), dtype=torch.int32, device=dev),
+            torch.empty((n_items, top), dtype=torch.float32, device=dev),
+            torch.empty((n_items, top), dtype=torch.int32, device=dev),
+            torch.empty((n_items, top), dtype=torch.int32, device=dev))
+    if n_items == 0:
+        return outs
+    max_len = int(max_len)
+    nums = (ctypes.c_int32 * len(ratios))(*ratios)                       # read by the entry before it returns
+    ws = torch.empty(lib.grafp_identify_tempo_workspace(n_items, len(ratios), top), dtype=torch.uint8, device=dev)
+    with _timed("identify_tempo", (n_items, max_len, k, len(ratios))):
+        check(lib.grafp_identify_tempo_f32(_p(index_rows), index_rows.shape[0], _p(first), first.numel() - 1,
+                                           _p(q_rows), q_rows.shape[0], _p(topk_ids), k, _p(item_row), _p(item_len),
+                                           n_items, max_len, top, 0 if min_overlap is None else int(min_overlap),
+                                           ctypes.cast(nums, ctypes.c_void_p), len(ratios), _p(ws),
+                                           *(_p(o) for o in outs), _stream()), "identify_tempo")
+    return outs
+
+
+IDENTIFY_PQ_M = (16, 32, 64, 128)                                      # identify_pq.hip's sub-quantiser counts
 
 
 def identify_pq(list_id, codes, centroids, codebooks, track_first_row, q_rows, topk_ids, item_row, item_len, top=5,

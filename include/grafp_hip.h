@@ -639,6 +639,36 @@ int grafp_identify_thin_f32(const float *index_rows, int64_t n, const int64_t *t
                             int min_overlap, int32_t *out_track, int32_t *out_offset, float *out_score,
                             int32_t *out_votes, grafp_stream_t stream);
 
+/* ---- identification of recordings that play fast or slow (grafp_amd/library.py; identify_tempo.hip) ---------------
+ * grafp_identify_tempo_f32 -- grafp_identify_f32 for recordings that do not run at the catalogue's speed.  A ratio is
+ *   an integer num in [128, 512] standing for num / 256 track seconds per recording second (> 256: the recording plays
+ *   the track fast); ratio_num (HOST, n_ratios int32, 1 <= n_ratios <= 64) is strictly ascending.  At ratio num query
+ *   row s sits w(s) = (s * num + 128) >> 8 library rows after query row 0 (integer arithmetic; w(s) <= 510 for
+ *   s <= 255; two ratios 1/256 apart differ by at most one row over the 256 rows an item may have).
+ *   For every ratio j: a hit (s, r), 0 <= r < n, names the track t holding r and the alignment a = r - w_j(s); a
+ *   candidate is a unique (t, a, j), its votes the hits that map to it.  Its pairs are the s < ql with a + w_j(s)
+ *   inside t, o of them, a contiguous range of s (below 256 two consecutive s may share a library row, above it rows
+ *   are skipped).  It is eligible iff o >= 1 and o >= min(need, max(1, (L_t * 256) / num)), need = min_overlap
+ *   (<= 0: ql), L_t the rows of t, integer division: the cap is the number of pairs a track of L_t rows can always hold
+ *   at that ratio, and at num = 256 the rule is grafp_identify_f32's.  It scores
+ *   (sum over the pairs, s ascending, <q[s], row[a + w_j(s)]>) / o in the arithmetic order of grafp_identify_f32; no row
+ *   outside t is read.  Per track the best candidate is kept: highest score, then the ratio nearer to 1 (smaller
+ *   |num - 256|, then smaller num), then the smaller a.  The `top` tracks go out by score descending, then track
+ *   ascending: out_track, out_offset = a - first[t], out_score, out_votes as for grafp_identify_f32, and out_ratio
+ *   (int32) = num, each (n_items, top), padded with -1 / INT_MIN / -inf / 0 / 0.  With ratio_num = {256} the first four
+ *   outputs are bit for bit grafp_identify_f32's.
+ *   ws: grafp_identify_tempo_workspace(n_items, n_ratios, top) bytes on the device, 16-byte aligned (16 bytes per
+ *   ratio, item and rank: every ratio's own `top` list, merged per item by a second launch; 0 for arguments out of
+ *   range).  Both launches go out on `stream` with no host synchronisation.
+ *   Limits: those of grafp_identify_f32, and n + 511 < 2^32 (the alignment field of a key is a + 511). */
+int grafp_identify_tempo_f32(const float *index_rows, int64_t n, const int64_t *track_first_row, int n_tracks,
+                             const float *q_rows, int64_t n_qrows, const int64_t *topk_ids, int k,
+                             const int64_t *item_row, const int *item_len, int n_items, int max_len, int top,
+                             int min_overlap, const int32_t *ratio_num, int n_ratios, void *ws, int32_t *out_track,
+                             int32_t *out_offset, float *out_score, int32_t *out_votes, int32_t *out_ratio,
+                             grafp_stream_t stream);
+size_t grafp_identify_tempo_workspace(int n_items, int n_ratios, int top);
+
 /* ---- identification against a library held as IVF-PQ codes (grafp_amd/library.py; identify_pq.hip) ---------------
  * grafp_identify_pq_f32 -- grafp_identify_f32 on a library whose rows exist only as codes.  Library row r is
  *   dec[r][j] = centroids[list_id[r]][j] + codebooks[m][codes[r][m]][c], m = j / dsub, c = j % dsub, dsub = 128 / M

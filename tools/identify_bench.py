@@ -16,6 +16,12 @@ items are identified against it:
   search         ops.FlatL2Index.search of every query row over the kept rows
   identify_thin  ops.identify_thin of all items in one launch (top 5), next to ops.identify of the same items on the
                  dense library, and the library's bytes per original row
+With --tempo-ratios R1,R2,... the items are the library's own rows along the slope of ratio --tempo-num / 256 (default
+266: 4 % fast) and their hits are made, not searched: the planted row, its four neighbours and random rows (the search is
+the same with and without a tempo, and at 4 096 items of 94 rows it would take the run).  For every R:
+  identify_tempo  ops.identify_tempo of all items over the R ratios 256 - 2 * (R // 2) ... in steps of 2 (plus 266 if it
+                  is not among them), next to ops.identify of the same items and hits, calls alternating, and the top-1
+                  hit rate of both
 Kernel times from events (median of --reps); `rocprofv3 --kernel-trace --stats -- python tools/identify_bench.py` gives
 the per-kernel figures.
 """
@@ -99,6 +105,58 @@ def _thin(args, dev, cfg, rows, first, q, item_row, item_len, true_track, true_o
             "mean_votes_top1": round(float(vo[:, 0].float().mean()), 2)}
 
 
+def _tempo(args, dev, rows, first, per):
+    from grafp_amd import ops
+    T, ql, nq, k, num = args.tracks, args.qlen, args.queries, args.k, args.tempo_num
+    n = rows.shape[0]
+    rng = np.random.RandomState(2)
+    at = (np.arange(ql) * num + 128) >> 8
+    t = rng.randint(0, T, size=nq)
+    p0 = rng.randint(0, per - int(at[-1]), size=nq)
+    src = ((t * per + p0)[:, None] + at[None]).reshape(-1)
+    q = rows[torch.from_numpy(src).to(dev)].contiguous()
+    ids = rng.randint(0, n, size=(nq * ql, k)).astype(np.int64)
+    for c, d in enumerate((0, 1, -1, 2, -2)):
+        ids[:, c] = np.clip(src + d, 0, n - 1)
+    ids = torch.from_numpy(ids).to(dev)
+    item_row = torch.arange(nq, device=dev, dtype=torch.int64) * ql
+    item_len = torch.full((nq,), ql, device=dev, dtype=torch.int32)
+    want_t, want_o = torch.from_numpy(t).to(dev), torch.from_numpy(p0).to(dev)
+    dense = lambda: ops.identify(rows, first, q, ids, item_row, item_len, top=5, max_len=ql)
+    out = {"rows": int(n), "tracks": T, "queries": nq, "qlen": ql, "k": k, "planted_num": num, "by_ratios": []}
+    for R in args.tempo_ratios:
+        nums = sorted(set([256 + 2 * (i - R // 2) for i in range(R)] + ([num] if R > 1 else [])))
+        sloped = lambda: ops.identify_tempo(rows, first, q, ids, item_row, item_len, nums, top=5, max_len=ql)
+        for _ in range(3):
+            dense(), sloped()
+        torch.cuda.synchronize()
+        td, ts = [], []
+        a, b, c = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+        for _ in range(args.reps):                          # alternating, one synchronise per pair
+            a.record()
+            dense()
+            b.record()
+            sloped()
+            c.record()
+            torch.cuda.synchronize()
+            td.append(a.elapsed_time(b))
+            ts.append(b.elapsed_time(c))
+        tr, off, sc, _, ra = sloped()
+        dt, do, ds, _ = dense()
+        hit = (tr[:, 0].long() == want_t) & (off[:, 0].long() == want_o)
+        dhit = dt[:, 0].long() == want_t
+        out["by_ratios"].append({"R": len(nums), "identify_tempo_ms": round(float(np.median(ts)), 4),
+                                 "identify_ms": round(float(np.median(td)), 4),
+                                 "tempo_over_dense": round(float(np.median(ts) / np.median(td)), 3),
+                                 "tempo_ms_min_max": [round(min(ts), 4), round(max(ts), 4)],
+                                 "dense_ms_min_max": [round(min(td), 4), round(max(td), 4)],
+                                 "tempo_top1_track_and_offset": round(float(hit.float().mean()), 4),
+                                 "tempo_top1_score": round(float(sc[:, 0].mean()), 4),
+                                 "dense_top1_track": round(float(dhit.float().mean()), 4),
+                                 "dense_top1_score": round(float(ds[:, 0].mean()), 4)})
+    return out
+
+
 def main(argv=None):
     from grafp_amd import library, ops
     from grafp_amd.util import load_config
@@ -114,6 +172,9 @@ def main(argv=None):
     ap.add_argument("--pq-m", type=int, default=64)
     ap.add_argument("--nprobe", type=int, default=20)
     ap.add_argument("--row-stride", type=int, default=None, help="flat: keep every D-th row of each track")
+    ap.add_argument("--tempo-ratios", type=lambda v: [int(x) for x in v.split(",")], default=None,
+                    help="ratio counts to time ops.identify_tempo at, e.g. 1,15,31")
+    ap.add_argument("--tempo-num", type=int, default=266, help="tempo: the ratio the items are planted at (num / 256)")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     cfg = load_config()
@@ -124,6 +185,9 @@ def main(argv=None):
     rows = torch.randn((n, 128), generator=g, device=dev)
     rows /= rows.norm(dim=1, keepdim=True)
     first = torch.arange(T + 1, device=dev, dtype=torch.int64) * per
+    if args.tempo_ratios is not None:
+        print(json.dumps(_tempo(args, dev, rows, first, per)))
+        return
     rng = np.random.RandomState(1)
     t = rng.randint(0, T, size=nq)
     a = t * per + rng.randint(0, per - ql + 1, size=nq)
