@@ -324,11 +324,15 @@ __device__ __forceinline__ void gm_stats_tail(float *s_st, const gm_f32x2 (&sS)[
 // OUTF32 (round 4): the accumulators leave as f32 (Y points to R x M floats): the product of the f32 "parity" mode, whose
 // operands arrive as bf16 hi / lo planes and whose weight is [Wh | Wh | Wl] against the operand rows [Xh; Xl; Xh] (CAT) --
 // three exact bf16 products per term, summed in the f32 accumulators: ~2^-16 relative, 2-3 x the library's f32 GEMM rate.
-template <typename CFG, int NS, bool PRO, bool STATS, bool CAT = false, bool EPI = false, bool OUTF32 = false>
+// PACT: the activation code of PRO, a template argument (gemm_launch_variant picks the instantiation).  With the code in
+// a register every bf16 pair of the transform sat behind scalar branches (272-297 instructions per chunk against 13-48
+// plain), and the PRO + STATS kernels of the 128- and 256-row tiles needed 256 VGPRs and spilled DMA source pointers: the
+// reload in the issue path is followed by s_waitcnt vmcnt(0), which drains the ring the counted waits keep full.
+template <typename CFG, int NS, bool PRO, bool STATS, bool CAT = false, bool EPI = false, bool OUTF32 = false, int PACT = 0>
 __global__ __launch_bounds__(CFG::THREADS, CFG::NW == 4 ? 2 : 1) void conv1x1_gemm_kernel(
     const unsigned short *__restrict__ A, int lda, const unsigned short *__restrict__ X, unsigned short *__restrict__ Y,
     int64_t M, int Rg, int K, int row_tiles, int ranges_view, int tiles_range, int col_tiles_view, int views,
-    const float2 *__restrict__ pro_tab, int pro_act, float pro_slope, float *__restrict__ part, int P, int nblocks,
+    const float2 *__restrict__ pro_tab, float pro_slope, float *__restrict__ part, int P, int nblocks,
     const unsigned short *__restrict__ X2 = nullptr, int K1 = 0, const float2 *__restrict__ epi_tab = nullptr,
     int epi_act = 0, float epi_slope = 0.0f) {
     constexpr int D = NS - 1;                               // chunks in flight
@@ -339,6 +343,10 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::NW == 4 ? 2 : 1) void conv1x1_ge
 
     const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);          // scalar: everything derived stays in SGPRs
+    // PRO: without the bound hipcc 7.2 keeps "this wave's piece j exists" (below) as one flag per piece in VGPRs, and in
+    // the PRO + STATS form of N128 spills three of them: reloaded in issue(), each with s_waitcnt vmcnt(0) behind it.  (The
+    // other forms keep the loops they were measured with.)
+    if (PRO) __builtin_assume(wave >= 0 && wave < CFG::NW);
     const int wr = wave / CFG::WM, wm = wave % CFG::WM;
     const unsigned lds0 = (unsigned)(uintptr_t)(gm_lptr)smem;
     const GemmRange own = gm_range(nblocks, row_tiles, ranges_view, tiles_range, col_tiles_view, M, views, TN);
@@ -428,6 +436,7 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::NW == 4 ? 2 : 1) void conv1x1_ge
         rt_valid[ri] = r0 + wr * 32 * RT + ri * 32 < Rg;
         stores_per_epi += rt_valid[ri] ? GM_STORES_PER_RT : 0;
     }
+    const bool any_valid = rt_valid[0];                      // (the tiles of a wave are consecutive rows)
 
     float2 esc[RT];                                          // EPI: (scale, shift) of the lane's row of each 32-row tile
 #pragma unroll
@@ -480,6 +489,10 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::NW == 4 ? 2 : 1) void conv1x1_ge
         }
         unsigned char *const st = smem + (t % NS) * CFG::STAGE;
         // ---- 2 k-steps x (2 x RT) MFMAs ----
+        // (PRO: not in a wave whose rows all lie beyond R -- the second wave row of the S tile at R = 64 -- which would
+        //  transform the fragments its neighbour transforms, for products nobody stores: s0 gfc2 was VALU-bound on that.
+        //  The wave still issues its DMA pieces and meets every barrier.)
+        if (!PRO || any_valid)
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             gm_bf16x8 xa[2], wb[RT];
@@ -504,7 +517,7 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::NW == 4 ? 2 : 1) void conv1x1_ge
                         float lo = bf16_lo(w[d]), hi = bf16_hi(w[d]);
                         lo = __builtin_fmaf(lo, t4[d].x, t4[d].y);
                         hi = __builtin_fmaf(hi, t4[d].z, t4[d].w);
-                        act_fwd_pair(lo, hi, pro_act, pro_slope);
+                        act_fwd_pair(lo, hi, PACT, pro_slope);
                         w[d] = pack_bf16(lo, hi);
                     }
                     xa[mi] = __builtin_bit_cast(gm_bf16x8, w);
@@ -897,12 +910,19 @@ static int gemm_check(const char *who, bool ptrs, uintptr_t addr, const char *al
     return GRAFP_OK;
 }
 
-template <typename CFG, int NS, bool PRO, bool STATS, bool CAT, bool EPI = false, bool OUTF32 = false>
+template <typename CFG, int NS, bool PRO, bool STATS, bool CAT, bool EPI = false, bool OUTF32 = false, int PACT = 0>
 static void gemm_launch(const GemmPlan &p, const GemmArgs &a, hipStream_t s) {
     const size_t lds = (size_t)NS * CFG::STAGE + CFG::NW * CFG::OUT_BYTES + (PRO ? (size_t)a.Kg * 8 : 0);
-    gm_launch(conv1x1_gemm_kernel<CFG, NS, PRO, STATS, CAT, EPI, OUTF32>, dim3(p.nblocks, 1, a.groups), CFG::THREADS, lds, s,
-              a.w, a.lda, a.x, a.y, a.M, a.Rg, a.Kg, p.row_tiles, p.ranges_view, p.tiles_range, p.col_tiles_view, a.views,
-              a.pro_tab, a.pro_act, a.pro_slope, a.part, p.P, p.nblocks, a.x2, a.K1, a.epi_tab, a.epi_act, a.epi_slope);
+    gm_launch(conv1x1_gemm_kernel<CFG, NS, PRO, STATS, CAT, EPI, OUTF32, PACT>, dim3(p.nblocks, 1, a.groups), CFG::THREADS,
+              lds, s, a.w, a.lda, a.x, a.y, a.M, a.Rg, a.Kg, p.row_tiles, p.ranges_view, p.tiles_range, p.col_tiles_view,
+              a.views, a.pro_tab, a.pro_slope, a.part, p.P, p.nblocks, a.x2, a.K1, a.epi_tab, a.epi_act, a.epi_slope);
+}
+// normalise-on-load: the instantiation of the activation code
+template <typename CFG, bool STATS> static void gemm_launch_pro(const GemmPlan &p, const GemmArgs &a, hipStream_t s) {
+    constexpr int NP = CFG::NS_PRO;
+    if (a.pro_act == 1) gemm_launch<CFG, NP, true, STATS, false, false, false, 1>(p, a, s);
+    else if (a.pro_act == 2) gemm_launch<CFG, NP, true, STATS, false, false, false, 2>(p, a, s);
+    else gemm_launch<CFG, NP, true, STATS, false, false, false, 0>(p, a, s);
 }
 template <bool STATS, bool CAT, bool EPI, int ABL = 0>
 static void gemm_launch_xl(const GemmPlan &p, const GemmArgs &a, hipStream_t s) {
@@ -921,9 +941,9 @@ static bool gemm_launch_xl_abl(std::integer_sequence<int, ABL...>, int abl, cons
 // the variant of one tile configuration that the arguments ask for: normalise-on-load (with or without statistics), f32
 // output, affine epilogue, concatenated operand, statistics, plain
 template <typename CFG> static void gemm_launch_variant(CFG, const GemmPlan &p, const GemmArgs &a, hipStream_t s) {
-    constexpr int NS = CFG::NS, NP = CFG::NS_PRO;
-    if (a.pro_tab && a.part) gemm_launch<CFG, NP, true, true, false>(p, a, s);
-    else if (a.pro_tab) gemm_launch<CFG, NP, true, false, false>(p, a, s);
+    constexpr int NS = CFG::NS;
+    if (a.pro_tab && a.part) gemm_launch_pro<CFG, true>(p, a, s);
+    else if (a.pro_tab) gemm_launch_pro<CFG, false>(p, a, s);
     else if (a.out_f32) gemm_launch<CFG, NS, false, false, true, false, true>(p, a, s);
     else if (a.epi_tab) gemm_launch<CFG, NS, false, false, false, true>(p, a, s);
     else if (a.x2) gemm_launch<CFG, NS, false, false, true>(p, a, s);

@@ -383,11 +383,14 @@ __device__ __forceinline__ void wg_chunk_product(const unsigned char *gs, const 
     }
 }
 
-template <typename CFG, bool PRO>
+// PACT: the activation code of PRO, a template argument (the host picks the instantiation): with the code in a register
+// the transform was 26-29 instructions per bf16 pair -- both activations computed for every element and one selected
+// (T128: 965 instructions per chunk against 44 plain) -- and the stage 0-1 weight gradients were bound by it, not by HBM
+template <typename CFG, bool PRO, int PACT = 0>
 __global__ __launch_bounds__(CFG::THREADS) void wgrad_dma_kernel(
     const unsigned short *__restrict__ G, const unsigned short *__restrict__ X, int64_t M, int cout_g, int cin_g,
     int tiles_o, int tiles_c, int slices_view, int64_t cols_per_slice, int views, const float2 *__restrict__ pro_tab,
-    int pro_act, float pro_slope, float *__restrict__ part, int nblocks) {
+    float pro_slope, float *__restrict__ part, int nblocks) {
     constexpr int NS = CFG::NS, D = NS - 1, RT = CFG::RT, CT = CFG::CT, KC = CFG::KC;
     constexpr int DMA_PER_CHUNK = CFG::G_DMA + CFG::X_DMA;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -444,8 +447,8 @@ __global__ __launch_bounds__(CFG::THREADS) void wgrad_dma_kernel(
         unsigned char *const st = smem + (t % NS) * CFG::STAGE;
         wg_chunk_product<CFG>(st, st, goff, gx, xoff, xx, half, acc, [&](gm_bf16x8 (&bv)[CT]) {
             if (PRO) {
-                const int act = pro_act;        // locals: read through the closure inside the ?: arms below, hipcc
-                const float slope = pro_slope;  // builds branches instead of selects
+                const float slope = pro_slope;  // a local: read through the closure inside the ?: arms below, hipcc
+                                                // builds branches instead of selects
                 // the fragment is 8 columns of ONE operand row: its (scale, shift) sits in two registers of the lane
                 // (in registers, not as a pass over the staged tile: see conv1x1_gemm_kernel)
 #pragma unroll
@@ -456,7 +459,7 @@ __global__ __launch_bounds__(CFG::THREADS) void wgrad_dma_kernel(
                         float lo = bf16_lo(v[d]), hi = bf16_hi(v[d]);
                         lo = __builtin_fmaf(lo, ssb[b].x, ssb[b].y);
                         hi = __builtin_fmaf(hi, ssb[b].x, ssb[b].y);
-                        act_fwd_pair(lo, hi, act, slope);
+                        act_fwd_pair(lo, hi, PACT, slope);
                         v[d] = pack_bf16(lo, hi);
                     }
                     bv[b] = __builtin_bit_cast(gm_bf16x8, v);
@@ -676,6 +679,10 @@ static WgDmaPlan wgrad_dma_plan(int cout_g, int cin_g, int groups, int64_t M, in
         if (groups == 1 && outs > 128 * 128 && outs <= 256 * 256 && opbytes >= 250e6) p.cfg = WG_S128;
         if (groups > 1 && cout_g == 128 && cin_g == 128 && opbytes >= 750e6) p.cfg = WG_S128;
     }
+    // (With the in-LDS normalisation, since its activation code is a template argument, S128 is the faster tile here too --
+    // tools/pro_bench.py 2048 tiles, plain / PRO on the forced tile: 128 x 256 S 281 / 283, S128 189 / 215; 128 x 512 S 467 /
+    // 466, S128 342 / 417; likewise L32 / L at 256 x 512 and 256 x 1024 (profiles/pro_cost_bench_2048.txt).  The rule for a
+    // pro_tab is left as it is: it moves the workspace sizes that tests/golden/wgrad_plan.json records.)
     // ... and at SMALL batches (operands under 200 MB: 128 pairs per GPU, BASELINE config 3's per-rank shape) for the 2^17 ...
     // 2^19-output layers with >= 256 rows on both sides (stage 2 fc2 / FFN, stage 3 fc1), which the first rule leaves on
     // the 64 x 64 tile: tools/wgrad_sweep.sh at 256 clip-views (profiles/r05_wgrad_sweep_256.txt): 65 -> 55 us (FFN),
@@ -856,14 +863,17 @@ static int wgrad_tile_impl(const void *grad_out, const void *x, int Cout, int Ci
             if constexpr (decltype(k)::GR)                      // never with a pro_tab: wg_tile_info[].pro
                 gm_launch(wgrad_gr_kernel<CFG>, grid, CFG::THREADS, (size_t)3 * CFG::X_BYTES + 2 * CFG::G_BYTES, s, G, X, M,
                           cout_g, cin_g, p.tiles_o, p.tiles_c, p.slices_view, p.cols, views, (float *)ws, nblocks);
-            else if (pro_tab)
-                gm_launch(wgrad_dma_kernel<CFG, true>, grid, CFG::THREADS, ring + (size_t)CFG::TC * 8, s, G, X, M, cout_g,
-                          cin_g, p.tiles_o, p.tiles_c, p.slices_view, p.cols, views, (const float2 *)pro_tab, pro_act,
-                          pro_slope, (float *)ws, nblocks);
-            else
-                gm_launch(wgrad_dma_kernel<CFG, false>, grid, CFG::THREADS, ring, s, G, X, M, cout_g, cin_g, p.tiles_o,
-                          p.tiles_c, p.slices_view, p.cols, views, (const float2 *)pro_tab, pro_act, pro_slope, (float *)ws,
+            else {
+                // plain, or the normalise-on-load instantiation of the activation code
+                auto kern = wgrad_dma_kernel<CFG, false>;
+                if (pro_tab)
+                    kern = pro_act == 1   ? wgrad_dma_kernel<CFG, true, 1>
+                           : pro_act == 2 ? wgrad_dma_kernel<CFG, true, 2>
+                                          : wgrad_dma_kernel<CFG, true, 0>;
+                gm_launch(kern, grid, CFG::THREADS, ring + (pro_tab ? (size_t)CFG::TC * 8 : 0), s, G, X, M, cout_g, cin_g,
+                          p.tiles_o, p.tiles_c, p.slices_view, p.cols, views, (const float2 *)pro_tab, pro_slope, (float *)ws,
                           nblocks);
+            }
         });
         GRAFP_CHECK_LAUNCH("wgrad_dma_kernel");
         S = p.nslices;

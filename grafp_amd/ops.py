@@ -1468,9 +1468,12 @@ class DeferredNorm:
 
 
 def defer_norm_pays(consumer_rows, consumer_operand_rows, M):
-    """Measured at 512 and 2048 clip-views: the consumer's output rows <= 128 (stages 0-1): skipped
-    pass 200-400 us against +30-115 us in the GEMM and +10-35 us in the weight gradient; beyond, the products are
-    matrix-bound and the in-LDS transform costs more than the pass."""
+    """Measured at 512 and 2048 clip-views (DESIGN.md sections 6 and 12.5): the consumer's output rows <= 128 (stages
+    0-1): skipped pass 210-415 us against 0 ... +90 us in the GEMM and +5 ... +120 us in the weight gradient.  256 rows
+    (stage 2) at 2048 clip-views (profiles/pro_cost_bench_2048.txt): the product leaves the four-wave tile for the
+    eight-wave one (+93 / +182 us), the weight gradient the register-staged tile for the S tile (+104 / +218 us), against
+    208 / 416 us of skipped pass: -11 / -18 us per layer, inside the run-to-run spread, so it stays out.  Beyond (stage
+    3), the products are matrix-bound and the in-register transform costs more than the pass."""
     return bool(switches.defer_norm) and consumer_rows <= 128
 
 

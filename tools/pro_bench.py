@@ -12,6 +12,24 @@ def timeit(fn, reps=10):
     for _ in range(reps): fn()
     e.record(); torch.cuda.synchronize()
     return s.elapsed_time(e) / reps * 1e3
+if len(sys.argv) > 2 and sys.argv[2] == "tiles":
+    # python tools/pro_bench.py 2048 tiles: the weight gradient of the stage 0-2 consumers on every tile that has the
+    # normalise-on-load form, forced -- plain / with pro_tab, us (what wgrad_dma_plan's rule for a pro_tab was read from)
+    names = {0: "T", 1: "S", 2: "L", 3: "S32", 4: "M32", 5: "L32", 8: "T128", 10: "S128"}
+    for stage, (C, N) in enumerate(((64, 1024), (128, 512), (256, 256))):
+        M = clips * N
+        for name, R, K in (("gfc2", C, 2 * C), ("ffn2", C, 4 * C)):
+            x = torch.randn(K, M, device=dev).to(torch.bfloat16)
+            gy = torch.randn(R, M, device=dev).to(torch.bfloat16)
+            tab = torch.rand(K, 2, 2, device=dev) + 0.5
+            row = [f"plain {timeit(lambda: ops._wgrad_bf16(gy, x, R, K, 1, M, may_defer=False)):6.1f}",
+                   f"pro auto {timeit(lambda: ops._wgrad_bf16(gy, x, R, K, 1, M, views=2, pro_tab=tab, pro_act=ops.ACT_RELU, may_defer=False)):6.1f}"]
+            for tile, tn in names.items():
+                tp = timeit(lambda: ops._wgrad_bf16(gy, x, R, K, 1, M, views=2, tile=tile, may_defer=False))
+                t = timeit(lambda: ops._wgrad_bf16(gy, x, R, K, 1, M, views=2, pro_tab=tab, pro_act=ops.ACT_RELU, tile=tile, may_defer=False))
+                row.append(f"{tn} {tp:5.0f}/{t:5.0f}")
+            print(f"s{stage} {name} {R}x{K}: " + " | ".join(row), flush=True)
+    sys.exit(0)
 tot = [0.0, 0.0]
 depth = (2, 2, 6, 2)
 for stage, (C, N) in enumerate(((64, 1024), (128, 512), (256, 256), (512, 128))):
