@@ -9,7 +9,8 @@ launch (ops.draw_pairs), following NeuralfpDataset.__getitem__ for training; eva
 (tracks()), which fpdb.create_fp_db / create_dummy_db take in place of DataLoader(NeuralfpDataset(train=False)).
 
 Differences from the reference, on purpose:
-  * a track shorter than offset_mod + 1 samples (offset_mod = int(fs*offset + clip)) is excluded from training draws
+  * a track shorter than offset_mod + 1 samples (offset_mod = int(fs*offset + clip); with speed augmentation on,
+    int(fs*offset) + draw_len: the views are drawn with the resampler's context) is excluded from training draws
     and counted (stats['excluded']).  The reference skips tracks up to one clip long (:61-62) and raises in
     np.random.randint for those up to offset_mod (:74); here neither happens.
   * a silent draw moves on to the next track of the corpus (order of the index), as `self[idx + 1]` does, but at most
@@ -229,6 +230,17 @@ class DeviceAudioCorpus:
         self.fs = int(cfg["fs"])
         self.clip = int(self.fs * cfg["dur"])
         self.offset_mod = int(self.fs * cfg["offset"] + self.clip)
+        # speed augmentation on (cfg['speed_prob'] > 0): both views are drawn at draw_len samples, the clip plus the context
+        # ops.speed_change needs at the largest ratio; the jitter between the views stays int(fs * offset)
+        self.draw_len = self.clip
+        speed = ops.speed_config(cfg)
+        if speed is not None:
+            self.draw_len = ops.speed_input_len(self.clip, speed[2])
+            self.offset_mod = int(self.fs * cfg["offset"]) + self.draw_len
+            if self.offset_mod > ops.DRAW_PAIRS_MAX_WINDOW:
+                raise ValueError(f"speed_range = {list(cfg['speed_range'])}: the training draw needs a window of "
+                                 f"{self.offset_mod} samples (draw_len = {self.draw_len} plus the offset jitter), more than "
+                                 f"the {ops.DRAW_PAIRS_MAX_WINDOW} draw_pairs holds on chip; lower the upper ratio, dur or offset")
         self.silence = float(cfg["silence"])
         self.norm_q = cfg.get("norm")
         npy_fs = self.fs if npy_fs is None else int(npy_fs)
@@ -351,7 +363,9 @@ class DeviceAudioCorpus:
 
     # ---- training draws -------------------------------------------------------------------------------------
     def draw_pairs(self, track_ids, generator=None, attempts=8):
-        """One batch: row b starts at corpus track track_ids[b] (which must be eligible) -> (x_i, x_j), (B, clip)."""
+        """One batch: row b starts at corpus track track_ids[b] (which must be eligible) -> (x_i, x_j), (B, draw_len):
+        draw_len is the clip, or with speed augmentation on the clip plus the resampler's context (what
+        GPUTransformNeuralfp.forward and Trainer.step then take)."""
         try:
             rows = [self._pos[int(t)] for t in torch.as_tensor(track_ids).reshape(-1).tolist()]
         except KeyError as e:
@@ -363,7 +377,7 @@ class DeviceAudioCorpus:
         B = rows.numel()
         gdev = generator.device if generator is not None else self.device
         u = torch.rand((B, attempts, 3), generator=generator, device=gdev).to(self.device)
-        return ops.draw_pairs(self.bank, self._el_start, self._el_len, self._el_norm, rows.to(self.device), u, self.clip,
+        return ops.draw_pairs(self.bank, self._el_start, self._el_len, self._el_norm, rows.to(self.device), u, self.draw_len,
                               self.offset_mod, self.silence, self._silent)
 
     def batches(self, batch, generator=None, rank=0, world=1, attempts=8):

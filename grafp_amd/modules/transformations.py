@@ -9,6 +9,11 @@ recording, the noise offset and the SNR (uniform in tr_snr / val_snr dB).  With 
 identities, as in the reference.  Decoding is limited to what the image can do without torchaudio: `.npy` arrays and
 PCM `.wav` files (stdlib `wave`) already at cfg['fs'] -- or, with cfg['resample_banks'] = True, PCM `.wav` files at
 any rate, resampled to cfg['fs'] on the device (ops.resample).
+
+Speed augmentation (optional; off unless cfg['speed_prob'] > 0): the second training view is first played at a per-clip
+random ratio from cfg['speed_range'] = [lo, hi] by resampling on the device (ops.speed_change, csrc/speed.hip), then goes
+through the two chains above.  Both training views are then `draw_len` samples long (the clip plus the context the
+resampler needs, ops.speed_input_len); validation and test transforms are unchanged.
 """
 import glob
 import os
@@ -98,6 +103,14 @@ class GPUTransformNeuralfp(nn.Module):
         self.overlap, self.arch, self.n_frames = cfg["overlap"], cfg["arch"], cfg["n_frames"]
         self.train, self.cpu, self.cfg, self.abl = train, cpu, cfg, abl   # `train` shadows nn.Module.train as in the reference
         self.seed, self._gen = cfg.get("aug_seed"), None      # optional: reproducible augmentation draws
+        # optional speed augmentation of the second training view (cfg['speed_prob'], cfg['speed_range'] = [lo, hi]): the
+        # clip is played at a random ratio by resampling, which moves its pitch too (ops.speed_change).  When on, the
+        # train branch of forward() takes both views at draw_len samples: pad samples of context on either side of x_i's
+        # clip, and enough input for x_j at the largest ratio
+        self.speed = ops.speed_config(cfg)
+        self.clip = int(cfg["fs"] * cfg["dur"]) if self.speed or "dur" in cfg else None
+        self.pad = ops.speed_pad(self.speed[2]) if self.speed else 0
+        self.draw_len = ops.speed_input_len(self.clip, self.speed[2]) if self.speed else self.clip
         has_ir = ir_dir is not None and not (isinstance(ir_dir, (list, tuple, str)) and len(ir_dir) == 0)
         has_noise = noise_dir is not None and not (isinstance(noise_dir, (list, tuple, str)) and len(noise_dir) == 0)
         if has_ir:
@@ -152,7 +165,20 @@ class GPUTransformNeuralfp(nn.Module):
     def _has_banks(self):
         return self.ir_bank is not None or self.noise_bank is not None
 
+    def speed_change(self, x):
+        """x (B, draw_len) -> (B, clip): per clip, with probability speed_prob, played at a ratio uniform in speed_range
+        (otherwise at 1: a copy of x[:, pad:pad + clip]).  The recording is played fast; room and noise, applied after
+        it, are not."""
+        prob, lo, hi = self.speed
+        B, dev = x.shape[0], x.device
+        g = self._rng(dev)
+        keep = torch.rand(B, device=dev, generator=g) < prob
+        rho = lo + (hi - lo) * torch.rand(B, device=dev, generator=g)
+        return ops.speed_change(x, torch.where(keep, rho, torch.ones_like(rho)), self.clip, x_offset=self.pad)
+
     def train_transform(self, x):
+        if self.speed:
+            x = self.speed_change(x)
         if not self._has_banks():
             return x
         return self.augment(x, self.cfg["ir_prob"], self.cfg["noise_prob"], self.cfg["tr_snr"])
@@ -176,6 +202,12 @@ class GPUTransformNeuralfp(nn.Module):
             # to the batched device transform of the train branch below (workers never touch the GPU)
             return x_i, x_j.flatten()[:int(self.sample_rate * self.cfg["dur"])]
         if self.train:                    # (:77-85) both views -> (B, n_mels, n_frames)
+            if self.speed:
+                if x_i.dim() != 2 or x_j.dim() != 2 or x_i.shape[1] != self.draw_len or x_j.shape[1] != self.draw_len:
+                    raise ValueError(f"speed augmentation is on: both views must be (B, draw_len = {self.draw_len}) "
+                                     f"samples (the clip of {self.clip} with its context), got {tuple(x_i.shape)} and "
+                                     f"{tuple(x_j.shape)}")
+                x_i = x_i[:, self.pad:self.pad + self.clip]
             return self.logmelspec(x_i), self.logmelspec(self.train_transform(x_j))
         X_i = self._segments(x_i)         # (:87-113) whole track -> (n_seg, n_mels, n_frames)
         if x_j is None:

@@ -443,6 +443,9 @@ def resample(bank, starts, lengths, orig_fs, new_fs, out=None, out_starts=None):
     return out_bank[:total], out_starts, out_lens_h.to(dev)
 
 
+DRAW_PAIRS_MAX_WINDOW = 40896      # offset_mod that draw_pairs_kernel holds in LDS (DP_MAX_WINDOW of csrc/corpus.hip)
+
+
 def draw_pairs(bank, track_start, track_len, norm, row_track, uniforms, clip, offset_mod, silence, silent_rows=None):
     """The training crops of NeuralfpDataset.__getitem__ (modules/data.py:70-89) for a whole batch in one launch
     (grafp_draw_pairs_f32): row b tries tracks row_track[b], row_track[b] + 1, ... (mod n) with the uniforms
@@ -469,6 +472,75 @@ def draw_pairs(bank, track_start, track_len, norm, row_track, uniforms, clip, of
                                    int(clip), int(offset_mod), float(silence), _p(x_i), _p(x_j), _p(silent_rows),
                                    _stream()), "draw_pairs")
     return x_i, x_j
+
+
+# ------------------------------------------------------------------------------------------------
+# speed augmentation (csrc/speed.hip): every clip resampled by its own ratio, read on the device
+# ------------------------------------------------------------------------------------------------
+def speed_pad(max_ratio):
+    """Samples of context in front of (and behind) a clip that is to be played at up to max_ratio: the filter's reach
+    6 / c with c = 0.99 * min(1, 1 / max_ratio), rounded up, plus one.  Host-side; no device needed."""
+    return math.ceil(6.0 / (0.99 * min(1.0, 1.0 / float(max_ratio)))) + 1
+
+
+def speed_input_len(out_len, max_ratio):
+    """Input samples from which speed_change(x, ratio, out_len, x_offset=speed_pad(max_ratio)) reads no zero padding at
+    any ratio <= max_ratio: pad + ceil((out_len - 1) * max_ratio) + 1 + pad."""
+    pad = speed_pad(max_ratio)
+    return pad + math.ceil((int(out_len) - 1) * float(max_ratio)) + 1 + pad
+
+
+def speed_config(cfg):
+    """The speed keys of a configuration, validated: -> (speed_prob, lo, hi), or None when speed augmentation is off
+    (speed_prob absent or 0).  speed_range = [lo, hi] with 0.5 <= lo <= hi <= 2 is required when it is on."""
+    prob, rng = cfg.get("speed_prob"), cfg.get("speed_range")
+    prob = 0.0 if prob is None else float(prob)
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError(f"speed_prob = {prob} is not a probability")
+    if rng is not None:
+        if not isinstance(rng, (list, tuple)) or len(rng) != 2:
+            raise ValueError(f"speed_range = {rng!r} must be [lo, hi]")
+        lo, hi = float(rng[0]), float(rng[1])
+        if not 0.5 <= lo <= hi <= 2.0:
+            raise ValueError(f"speed_range = {rng!r} must satisfy 0.5 <= lo <= hi <= 2")
+    if prob == 0.0:
+        return None
+    if rng is None:
+        raise ValueError("speed_prob > 0 needs speed_range = [lo, hi]")
+    return prob, lo, hi
+
+
+def speed_change(x, ratio, out_len, x_offset=0, out=None):
+    """Every clip of a batch resampled by its own ratio in one launch (grafp_speed_change_f32; the rule is stated in
+    csrc/speed.hip): x (B, T_in) or (T_in,) f32, rows may be strided; ratio (B,) f32 device tensor of input samples per
+    output sample (clamped to [0.5, 2], NaN = 1; above 1 the clip plays fast and its pitch rises; exactly 1 is a bit
+    copy) -- or one number for all clips; output m reads the input at x_offset + m * ratio, zeros outside the row.
+    -> (B, out_len) f32 (`out`: written in place, rows may be strided).  The ratios are read on the device: no host
+    synchronisation, so the launch can be captured into a HIP graph."""
+    _require_gpu(x, ratio if torch.is_tensor(ratio) else None, out)
+    squeeze = x.dim() == 1
+    x2 = x.detach().reshape(1, -1) if squeeze else x.detach()
+    if x2.dim() != 2:
+        raise ValueError("speed_change: x must be (B, T_in) or (T_in,)")
+    if x2.dtype != torch.float32 or x2.stride(1) != 1 or x2.stride(0) < x2.shape[1]:
+        x2 = _f32c(x2)
+    B, T_in = x2.shape
+    out_len = int(out_len)
+    if torch.is_tensor(ratio):
+        r = _f32c(ratio.to(x2.device)).reshape(-1)
+    else:
+        r = torch.full((B,), float(ratio), dtype=torch.float32, device=x2.device)
+    if r.numel() != B:
+        raise ValueError(f"speed_change: {r.numel()} ratios for {B} clips")
+    if out is None:
+        out = torch.empty((B, out_len), dtype=torch.float32, device=x2.device)
+    elif (out.dtype != torch.float32 or out.device != x2.device or tuple(out.shape) != (B, out_len)
+          or out.stride(1) != 1 or out.stride(0) < out_len):
+        raise ValueError("speed_change: `out` must be a (B, out_len) f32 device tensor with unit column stride")
+    with _timed("speed_change", (B, T_in, out_len)):
+        check(lib.grafp_speed_change_f32(_p(x2), x2.stride(0), B, T_in, int(x_offset), _p(r), _p(out), out.stride(0),
+                                         out_len, _stream()), "speed_change")
+    return out[0] if squeeze and out.dim() == 2 else out
 
 
 # ------------------------------------------------------------------------------------------------

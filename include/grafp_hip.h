@@ -601,6 +601,19 @@ int grafp_draw_pairs_f32(const float *bank, const int64_t *track_start, const in
                          int offset_mod, float silence, float *x_i, float *x_j, int32_t *silent_rows,
                          grafp_stream_t stream);
 
+/* ---- speed augmentation of the second training view (speed.hip) ---------------------------------------------------
+ * grafp_speed_change_f32 -- resamples each of B clips by its own ratio, read on the device (capturable).  For clip b:
+ *   rho = ratio[b] clamped to [0.5, 2], NaN -> 1 (input samples per output sample: above 1 plays fast, pitch up);
+ *   c = 0.99 * min(1, 1 / rho);  p = x_offset + m * rho (formed in f64);
+ *   out[b][m] = sum over k = ceil(p - 6/c) .. floor(p + 6/c), ascending, of xz[b][k] * h(k - p), one fmaf chain from 0,
+ *   xz = x inside [0, T_in) and 0 outside,  h(u) = c * sinc(pi t) * cos^2(pi t / 12),  t = clip(c u, -6, 6)
+ *   (the filter of grafp_resample_f32 at an arbitrary position).  rho == 1.0f exactly: out[b][m] = xz[b][x_offset + m],
+ *   bit for bit.  x: (B, T_in) with row stride x_stride >= T_in; out: (B, T_out) with row stride out_stride >= T_out;
+ *   out must not alias x; x_offset >= 0.  No atomics: bit-reproducible. */
+int grafp_speed_change_f32(const float *x, int64_t x_stride, int B, int T_in, int64_t x_offset,
+                           const float *ratio /* (B) device */, float *out, int64_t out_stride, int T_out,
+                           grafp_stream_t stream);
+
 /* ---- track-aware sequence identification (grafp_amd/library.py; identify.hip) -----------------------------------
  * grafp_identify_f32 -- which track, and where in it, each of n_items query items is.  index_rows: the (n, 128) f32
  *   library rows of n_tracks tracks laid end to end, track t owning rows [track_first_row[t], track_first_row[t+1])
