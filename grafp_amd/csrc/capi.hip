@@ -272,6 +272,44 @@ extern "C" int grafp_cross_match_pq_f32(const int32_t *list_id, const uint8_t *c
                                         (hipStream_t)stream);
 }
 
+// What recordings that play faster or slower than the catalogue share with a library (crossmatch_tempo.hip): the checks
+// shared with grafp_cross_match_f32 here; the ratio checks, the workspace floor and the three launches there.
+namespace grafp {
+int cross_match_tempo_launch(const float *rows, int64_t n, const int64_t *first, int T, const float *q_rows,
+                             int64_t n_qrows, const int64_t *src_first, int n_src, const int64_t *ids, int k, int top,
+                             int min_votes, int min_overlap, const int32_t *ratio_num, int n_ratios, void *ws,
+                             size_t ws_bytes, int32_t *out_track, int32_t *out_delta, int32_t *out_start,
+                             int32_t *out_len, float *out_score, int32_t *out_votes, int32_t *out_ratio,
+                             hipStream_t stream);
+size_t cross_match_tempo_workspace(const int64_t *src_rows, int n_src, int k, int min_votes, int n_ratios, int top);
+}  // namespace grafp
+
+extern "C" size_t grafp_cross_match_tempo_workspace(const int64_t *src_rows, int n_src, int k, int min_votes,
+                                                    int n_ratios, int top) {
+    return grafp::cross_match_tempo_workspace(src_rows, n_src, k, min_votes, n_ratios, top);
+}
+
+extern "C" int grafp_cross_match_tempo_f32(const float *index_rows, int64_t n, const int64_t *track_first_row,
+                                           int n_tracks, const float *q_rows, int64_t n_qrows,
+                                           const int64_t *src_first_row, int n_src, const int64_t *topk_ids, int k,
+                                           int top, int min_votes, int min_overlap, const int32_t *ratio_num,
+                                           int n_ratios, void *ws, size_t ws_bytes, int32_t *out_track,
+                                           int32_t *out_delta, int32_t *out_start, int32_t *out_len, float *out_score,
+                                           int32_t *out_votes, int32_t *out_ratio, grafp_stream_t stream) {
+    GRAFP_REQUIRE(index_rows && track_first_row && q_rows && src_first_row && topk_ids && ratio_num && out_track &&
+                  out_delta && out_start && out_len && out_score && out_votes && out_ratio,
+                  "cross_match_tempo: null pointer");
+    GRAFP_REQUIRE(n >= 1 && n < 0x7fffff00ll && n_tracks >= 1 && n_qrows >= 0 && n_qrows < 0x7fffff00ll && n_src >= 0,
+                  "cross_match_tempo: bad sizes n=%lld n_tracks=%d n_qrows=%lld n_src=%d", (long long)n, n_tracks,
+                  (long long)n_qrows, n_src);
+    GRAFP_REQUIRE((((uintptr_t)index_rows | (uintptr_t)q_rows) & 15) == 0,
+                  "cross_match_tempo: rows must be 16-byte aligned");
+    return grafp::cross_match_tempo_launch(index_rows, n, track_first_row, n_tracks, q_rows, n_qrows, src_first_row,
+                                           n_src, topk_ids, k, top, min_votes, min_overlap, ratio_num, n_ratios, ws,
+                                           ws_bytes, out_track, out_delta, out_start, out_len, out_score, out_votes,
+                                           out_ratio, (hipStream_t)stream);
+}
+
 // The front end of live multi-channel monitoring (stream_frontend.hip): argument checks here, the kernels there.  The
 // per-channel tables are device data: the caller (ops.stream_logmel) checks them on the host before it uploads them.
 namespace grafp {

@@ -48,7 +48,7 @@ __global__ __launch_bounds__(SM_THREADS) void cross_match_kernel(
     int32_t *__restrict__ out_len, float *__restrict__ out_score, int32_t *__restrict__ out_votes) {
     const TableSource source{q_rows, src_first};
     const RowSpan<XM_UNROLL> span{reinterpret_cast<const float4 *>(rows)};
-    match_source(source, span, n, first, T, ids, k, top, min_votes, min_overlap, ws, head_units, cap_units, out_track,
+    match_source(MatchDenseGrid{}, source, span, n, first, T, ids, k, top, min_votes, min_overlap, ws, head_units, cap_units, out_track,
                  out_delta, out_start, out_len, out_score, out_votes);
 }
 
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(SM_THREADS) void cross_match_pq_kernel(
     float *__restrict__ out_score, int32_t *__restrict__ out_votes) {
     const TableSource source{q_rows, src_first};
     const PqSpan<kM, XM_UNROLL_PQ> span{list_id, codes, centroids, codebooks, nlist};
-    match_source(source, span, n, first, T, ids, k, top, min_votes, min_overlap, ws, head_units, cap_units, out_track,
+    match_source(MatchDenseGrid{}, source, span, n, first, T, ids, k, top, min_votes, min_overlap, ws, head_units, cap_units, out_track,
                  out_delta, out_start, out_len, out_score, out_votes);
 }
 

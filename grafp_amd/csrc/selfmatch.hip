@@ -63,7 +63,7 @@ __global__ __launch_bounds__(SM_THREADS) void self_match_kernel(
     int32_t *__restrict__ out_votes) {
     const SelfSource source{rows, first, tracks};
     const RowSpan<SM_UNROLL> span{reinterpret_cast<const float4 *>(rows)};
-    match_source(source, span, n, first, T, ids, k, top, min_votes, min_overlap, ws, head_units, cap_units, out_track,
+    match_source(MatchDenseGrid{}, source, span, n, first, T, ids, k, top, min_votes, min_overlap, ws, head_units, cap_units, out_track,
                  out_delta, out_start, out_len, out_score, out_votes);
 }
 

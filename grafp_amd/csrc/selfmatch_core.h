@@ -1,8 +1,9 @@
 // selfmatch_core.h -- the one body of the shared-audio kernels: selfmatch.hip (the sources are tracks of the library,
 // ops.self_match) and crossmatch.hip (the sources are recordings held outside the library, ops.cross_match and
-// ops.cross_match_pq).  What a source's votes, spans, scores and partners are, the five phases and the workspace layout
+// ops.cross_match_pq) and crossmatch_tempo.hip (such recordings played faster or slower than the catalogue,
+// ops.cross_match_tempo).  What a source's votes, spans, scores and partners are, the five phases and the workspace layout
 // are stated at the top of selfmatch.hip; the arithmetic order of a score at the top of seqmatch.h.  The kernels differ
-// in TWO things, the parameters of match_source:
+// in THREE things, the parameters of match_source:
 //   * Source -- where source s comes from:
 //         const float *x                the array its rows are read from, (.., 128) f32
 //         int64_t row0(int s)           its first row in x AND in ids (ids holds one row of k hits per row of x)
@@ -11,10 +12,18 @@
 //     SelfSource (x = the library, row0 = first[tracks[s]], own-track hits dropped) and TableSource (x = q_rows,
 //     row0 = src_first[s], nothing dropped) below;
 //   * Span -- where the library rows of a span score come from (span_rows.h): RowSpan for f32 rows, PqSpan for rows
-//     decoded from IVF-PQ codes.
+//     decoded from IVF-PQ codes, TempoRowSpan for f32 rows gathered along a slope;
+//   * Grid -- where the rows of a source sit along the library, for a source that does not run at the catalogue's speed
+//     (the manner of identify_core.h's DenseGrid / TempoGrid):
+//         int64_t at(int64_t i)         library rows after source row 0 at which source row i sits
+//         int64_t shift(int64_t L)      the key shift of a source of L rows: r - at(i) + shift(L) >= 0 for every hit
+//         float score(span, x, a, lo, l, m)   the span call of phase 3: m pairs from source row lo on, alignment a
+//     MatchDenseGrid (at = i, shift = L, span(x, a + lo, l, m)) for the three files above and MatchTempoGrid (at = w(i) =
+//     (i * num + 128) >> 8, shift = 2 L, span(x, a, lo, num, l, m): TempoRowSpan) for crossmatch_tempo.hip.  Inside one
+//     alignment run r = a + at(i) never decreases with i on either grid, which is all phase 2's walk needs.
 // The workspace depends on a source's row count, k and min_votes only (sm_units), so plan_sources, the host's
 // self_match_workspace and the -2 mark of a source that does not fit serve every kernel.
-// Compiles with and without the packed-f32 instructions; both users are built without (Makefile NOPK).
+// Compiles with and without the packed-f32 instructions; every user is built without (Makefile NOPK).
 #pragma once
 #include <limits.h>
 #include <math.h>
@@ -69,6 +78,31 @@ struct TableSource {
     __device__ __forceinline__ int64_t len(int s) const { return src_first[s + 1] - src_first[s]; }
 };
 
+// the source runs at the catalogue's speed: row i sits i rows after row 0, a span is m consecutive library rows
+struct MatchDenseGrid {
+    __device__ __forceinline__ int64_t at(int64_t i) const { return i; }
+    __device__ __forceinline__ int64_t shift(int64_t L) const { return L; }
+    template <typename Span>
+    __device__ __forceinline__ float score(const Span &span, const float4 *x, int64_t a, int lo, int l, int m) const {
+        return span(x, a + lo, l, m);
+    }
+};
+
+// The source runs at num / 256 of the catalogue's speed: row i sits w(i) = (i * num + 128) >> 8 rows after row 0 (num in
+// [SM_TEMPO_MIN, SM_TEMPO_MAX]; i * num + 128 stays inside an int32 for the SM_TEMPO_MAX_ROWS a source may have, and
+// w(L - 1) <= 2 L - 2, hence the shift).  Its Span gathers: span(x, a, lo, num, l, m) reads row a + w(lo + t).
+constexpr int SM_TEMPO_DEN = 256, SM_TEMPO_MIN = 128, SM_TEMPO_MAX = 512;
+constexpr int64_t SM_TEMPO_MAX_ROWS = 4194303;             // (2^31 - 128) / 512
+struct MatchTempoGrid {
+    int num;
+    __device__ __forceinline__ int64_t at(int64_t i) const { return ((int)i * num + SM_TEMPO_DEN / 2) >> 8; }
+    __device__ __forceinline__ int64_t shift(int64_t L) const { return 2 * L; }
+    template <typename Span>
+    __device__ __forceinline__ float score(const Span &span, const float4 *x, int64_t a, int lo, int l, int m) const {
+        return span(x, a, lo, num, l, m);
+    }
+};
+
 // one bitonic stage over keys[0, cnt) whose slot 0 is global slot g0
 __device__ __forceinline__ void sm_stage(unsigned long long *keys, int64_t cnt, int64_t g0, int64_t k2, int64_t j,
                                          int tid) {
@@ -101,18 +135,29 @@ __device__ __forceinline__ void sm_sort(unsigned long long *keys, int64_t P, uns
     }
 }
 
+// the rank of record c among its partner's: the score, then the smaller alignment key -- ONE 64-bit value, so that the
+// choice is one compare.  (Stated as `o > bo || (o == bo && a_c < a_best)` the generated gfx950 code kept the old record
+// when the second clause held: equal scores went to whichever record the walkers of phase 2 had stored first, DESIGN.md
+// section 12.25.)
+__device__ __forceinline__ unsigned long long sm_rank(const unsigned int *rec, unsigned int c) {
+    const unsigned int *rc = rec + 6 * (int64_t)c;
+    return ((unsigned long long)f32_ord(__uint_as_float(rc[5])) << 32) | (unsigned int)~rc[1];
+}
+
 // the best record of the partner run that starts at slot e of the sorted phase 4 keys
 __device__ __forceinline__ unsigned int sm_best(const unsigned long long *k4, int64_t P, int64_t e,
                                                 const unsigned int *rec) {
     const unsigned long long b = k4[e] >> 32;
-    unsigned int best = (unsigned int)k4[e], bo = f32_ord(__uint_as_float(rec[6 * (int64_t)best + 5]));
+    unsigned int best = (unsigned int)k4[e];
+    unsigned long long br = sm_rank(rec, best);
     for (int64_t f = e + 1; f < P; ++f) {
         const unsigned long long key = k4[f];
         if ((key >> 32) != b) break;
-        const unsigned int c = (unsigned int)key, o = f32_ord(__uint_as_float(rec[6 * (int64_t)c + 5]));
-        if (o > bo || (o == bo && rec[6 * (int64_t)c + 1] < rec[6 * (int64_t)best + 1])) {
+        const unsigned int c = (unsigned int)key;
+        const unsigned long long cr = sm_rank(rec, c);
+        if (cr > br) {                                       // (two records of one partner never share an alignment)
             best = c;
-            bo = o;
+            br = cr;
         }
     }
     return best;
@@ -157,10 +202,11 @@ __device__ __forceinline__ void plan_sources(const Source &source, int n_src, in
     if (tid == SM_PLAN_THREADS - 1) off[n_src] = part[tid];
 }
 
-// One source by one workgroup of SM_THREADS threads (blockIdx.x = the source), SM_LDS bytes of dynamic LDS.
-template <typename Source, typename Span>
+// One source by one workgroup of SM_THREADS threads (blockIdx.x = the source), SM_LDS bytes of dynamic LDS.  The source's
+// region is ws + head_units + off[src]: a caller with one copy of the regions per grid passes that copy's start.
+template <typename Grid, typename Source, typename Span>
 __device__ __forceinline__ void match_source(
-    const Source &source, const Span &span, int64_t n, const int64_t *__restrict__ first, int T,
+    const Grid &grid, const Source &source, const Span &span, int64_t n, const int64_t *__restrict__ first, int T,
     const int64_t *__restrict__ ids, int k, int top, int min_votes, int min_overlap, unsigned long long *__restrict__ ws,
     int64_t head_units, int64_t cap_units, int32_t *__restrict__ out_track, int32_t *__restrict__ out_delta,
     int32_t *__restrict__ out_start, int32_t *__restrict__ out_len, float *__restrict__ out_score,
@@ -194,7 +240,7 @@ __device__ __forceinline__ void match_source(
             const int i = (int)e / k;                     // e < N0 <= INT_MAX
             const int64_t r = ids[(fa + i) * k + ((int)e - i * k)];
             if (r >= 0 && r < n && (!Source::kDropOwn || r < fa || r >= fa + L64))
-                key = ((unsigned long long)(r - i + L64) << 32) | (unsigned int)i;
+                key = ((unsigned long long)(r - grid.at(i) + grid.shift(L64)) << 32) | (unsigned int)i;
         }
         K1[e] = key;
     }
@@ -207,14 +253,14 @@ __device__ __forceinline__ void match_source(
         const unsigned long long key = K1[e];
         if (key == SEQ_NONE || (e > 0 && (K1[e - 1] >> 32) == (key >> 32))) continue;
         const unsigned long long hi = key >> 32;
-        const int64_t ag = (int64_t)hi - L64;
+        const int64_t ag = (int64_t)hi - grid.shift(L64);
         int t = 0, nv = 0;
         int64_t end = -1;
         unsigned int ilo = 0, ihi = 0;
         for (int64_t f = e;; ++f) {
             const unsigned long long kf = f < P1 ? K1[f] : SEQ_NONE;
             const bool more = kf != SEQ_NONE && (kf >> 32) == hi;
-            const int64_t r = ag + (int64_t)(unsigned int)kf;
+            const int64_t r = ag + grid.at((int64_t)(unsigned int)kf);
             if (!more || r >= end) {                          // the run ends, or crosses into a later track
                 if (nv >= min_votes && (int)(ihi - ilo) + 1 >= min_overlap) {
                     const int c = atomicAdd(&s_nc, 1);
@@ -253,9 +299,9 @@ __device__ __forceinline__ void match_source(
     const float4 *x4 = reinterpret_cast<const float4 *>(source.x);
     for (int c = hw; c < nc; c += SM_THREADS / 32) {
         const unsigned int *rc = rec + 6 * (int64_t)c;
-        const int64_t ag = (int64_t)rc[1] - L64;
+        const int64_t ag = (int64_t)rc[1] - grid.shift(L64);
         const int ilo = (int)rc[2], m = (int)rc[3];
-        const float acc = span(x4 + (fa + ilo) * (SEQ_D / 4) + l, ag + ilo, l, m);
+        const float acc = grid.score(span, x4 + (fa + ilo) * (SEQ_D / 4) + l, ag, ilo, l, m);
         if (l == 0) rec[6 * (int64_t)c + 5] = __float_as_uint(acc / (float)m);
     }
     __syncthreads();
@@ -291,7 +337,7 @@ __device__ __forceinline__ void match_source(
             const unsigned int *rc = rec + 6 * (int64_t)c;
             const int b = (int)rc[0];
             out_track[o] = b;
-            out_delta[o] = (int32_t)((int64_t)rc[1] - L64 - first[b]);
+            out_delta[o] = (int32_t)((int64_t)rc[1] - grid.shift(L64) - first[b]);
             out_start[o] = (int32_t)rc[2];
             out_len[o] = (int32_t)rc[3];
             out_score[o] = __uint_as_float(rc[5]);

@@ -8,6 +8,7 @@
   python -m grafp_amd.identify dedup --ckp MODEL.pth --library LIBDIR [--min-overlap 3] [--coverage 0.9] [--json OUT]
   python -m grafp_amd.identify match --ckp MODEL.pth --library LIBDIR FILES... [--min-overlap 3] [--min-votes 4]
                                        [--min-score S] [--top 8] [--k-probe 20] [--json OUT]
+                                       [--tempo X [--tempo-step G]]
   python -m grafp_amd.identify monitor --ckp MODEL.pth LIBDIR FILES... [--chunk-s 1.0] [--window 3 --hop 1] [--top 5]
 
 `build` fingerprints every track of the source (anything DeviceAudioCorpus accepts) into LIBDIR -- with --index ivfpq as
@@ -20,7 +21,9 @@ the span and the coverage (either form of a library; --json also writes them to 
 every D-th fingerprint row of each track (a flat library of 772 / D bytes per original row; `query` works on it
 unchanged, `dedup` and `match` need every row).  query --tempo X also searches recordings that play up to X (0.06: six
 per cent) faster or slower than the catalogue (a flat library that keeps every row; every match and timeline span then
-carries "tempo" next to its score; --tempo-step G spaces the ratios searched G / 256 apart).  `monitor` treats every file as one live channel: it feeds them to a
+carries "tempo" next to its score; --tempo-step G spaces the ratios searched G / 256 apart).  match --tempo X does the
+same for whole recordings -- a pitched DJ set, a sped-up re-upload -- on a flat library that keeps every row: every
+printed match then also carries "tempo", "tempo_num" and "track_overlap_s" (--tempo-step defaults to 1).  `monitor` treats every file as one live channel: it feeds them to a
 StreamMonitor (grafp_amd/monitor.py) chunk by chunk, all channels per push, prints one JSON object per window as it
 becomes due ({"channel", "file", start_s, end_s, segment_start_s, matches}) and, when the files end, one per timeline
 span of each channel ({"channel", "file", "span": ...})."""
@@ -96,6 +99,9 @@ def main(argv=None):
     m.add_argument("--top", type=int, default=8, help="library tracks reported per recording")
     m.add_argument("--k-probe", type=int, default=20)
     m.add_argument("--json", default=None, help="also write the matches to this file")
+    m.add_argument("--tempo", type=float, default=None,
+                   help="also match recordings that play up to this fraction faster or slower (0.06: 0.94 to 1.06)")
+    m.add_argument("--tempo-step", type=int, default=None, help="spacing of the ratios searched, in 1/256 (default 1)")
     m.add_argument("--force", action="store_true", help="use a library made with another model")
     mo = sub.add_parser("monitor", help="follow files as live channels, chunk by chunk")
     mo.add_argument("--config", default=DEFAULT_CONFIG, help="model configuration (the library keeps its own "
@@ -171,7 +177,8 @@ def main(argv=None):
         return 0
     if args.cmd == "match":
         res = lib.match(list(args.files), k_probe=args.k_probe, min_overlap_s=args.min_overlap,
-                        min_votes=args.min_votes, min_score=args.min_score, top=args.top)
+                        min_votes=args.min_votes, min_score=args.min_score, top=args.top, tempo=args.tempo,
+                        tempo_step=args.tempo_step)
         found = [{"recording": path, **hit} for path, hits in zip(args.files, res) for hit in hits]
         for hit in found:
             print(json.dumps(hit))

@@ -24,13 +24,15 @@ every row (row_stride 1).
 identify(tempo=...) and identify_windows(tempo=...) also find recordings that play a few per cent faster or slower
 than the catalogue: the same embed and search, then one ops.identify_tempo launch (csrc/identify_tempo.hip) that scores
 every candidate along the sloped alignment of each speed ratio of tempo_ratios(); timeline() follows such windows along
-their slope.  A flat library that keeps every row only; speed, not pitch; match(), self_matches() and StreamMonitor know
-no tempo.
+their slope.  match(tempo=...) does the same for whole recordings (one ops.cross_match_tempo launch per batch,
+csrc/crossmatch_tempo.hip).  A flat library that keeps every row only; speed, not pitch; self_matches() and StreamMonitor
+know no tempo.
 
 match() takes whole recordings of any length that are NOT in the library and says which tracks they share audio with,
 where and how much (spans, coverage, votes: what self_matches says about the library's own tracks) -- the question an
 ingest gate asks before add().  It runs on ops.cross_match (f32 rows) or ops.cross_match_pq (codes), the kernels of
-csrc/crossmatch.hip."""
+csrc/crossmatch.hip, and with tempo=... on ops.cross_match_tempo (csrc/crossmatch_tempo.hip): a DJ set pitched a few
+per cent or a sped-up re-upload is then one match along its sloped alignment, not fragments of diagonals."""
 import hashlib
 import json
 import math
@@ -701,7 +703,8 @@ class FingerprintLibrary:
         are embedded and searched as without it and one ops.identify_tempo launch scores every candidate along the
         sloped alignment of every ratio; each match then also carries "tempo" (the ratio) and "tempo_num" (ratio *
         256), and offset / offset_s keep their meaning.  Needs a flat library that keeps every row.  Speed only: pitch
-        is not searched, and match(), self_matches(), StreamMonitor, the IVF-PQ and the thinned forms know no tempo."""
+        is not searched; match() takes the same tempo for whole recordings; self_matches(), StreamMonitor, the IVF-PQ
+        and the thinned forms know no tempo."""
         self._need_tempo_form("identify", tempo)
         single = isinstance(queries, (str, np.ndarray, torch.Tensor)) and (
             isinstance(queries, str) or torch.as_tensor(queries).dim() == 1)
@@ -843,7 +846,7 @@ class FingerprintLibrary:
 
     # ---- recordings against the catalog -------------------------------------------------------------------------
     def match(self, recordings, fs=None, k_probe=20, min_overlap_s=3.0, min_votes=4, min_score=None, top=8,
-              max_segments=4096, batch_rows=1 << 18):
+              max_segments=4096, batch_rows=1 << 18, tempo=None, tempo_step=None):
         """What whole recordings share with the library: is an upload already in the catalogue, in whole or in part,
         which tracks does a mix or medley contain, and where.  recordings: as identify's queries (one waveform, a list
         of ragged waveforms, or file paths, at `fs`; other rates are resampled on the device), of any length.  They are
@@ -861,8 +864,21 @@ class FingerprintLibrary:
         k_probe = 20 is identify's default; it has not been measured for this use (self_matches uses 32 because it
         drops a row's hits on its own track; nothing is dropped here).
         One recording is one workgroup, as a track is in self_matches: an hour-long recording is not split into pieces,
-        its hits are sorted through the launch's workspace (ops.self_match_workspace_bytes of the batch's row counts)."""
+        its hits are sorted through the launch's workspace (ops.self_match_workspace_bytes of the batch's row counts).
+        tempo: None, or the speeds to search, as identify takes them (a float x for the ratios [1 - x, 1 + x] of track
+        seconds per recording second, or a pair (lo, hi)); tempo_step: the ratio grid's spacing in 1/256, by default 1
+        (recordings are long: at a coarser grid the nearest ratio drifts off a long span).  The launches then go to
+        ops.cross_match_tempo, R ratios at once, in batches of about batch_rows // R rows (the workspace is R times a
+        dense launch's), and row i of the recording sits on row offset + w(i) of the track, w(i) = (i * tempo_num + 128)
+        >> 8.  Each match also carries tempo (= tempo_num / 256), tempo_num and track_overlap_s = (w(i_hi) - w(i_lo) +
+        1) segment hops, the track's side of the span; track_start_s = (offset + w(i_lo)) hops, recording_coverage = m /
+        recording rows, track_coverage = (w(i_hi) - w(i_lo) + 1) / track rows, coverage the larger of the two (at 256:
+        the dense m / min).  When the true ratio lies between two grid ratios a long span drifts off its alignment by
+        up to a row per 512 rows and may end early: overlap_s is then a lower bound of the shared audio.  Needs a flat
+        library that keeps every row."""
+        self._need_tempo_form("match", tempo)
         self._need_dense("match()")
+        nums = None if tempo is None else tempo_ratios(tempo, ops.IDENTIFY_TEMPO_DEN, tempo_step)   # step 1 by default
         single = isinstance(recordings, (str, np.ndarray, torch.Tensor)) and (
             isinstance(recordings, str) or torch.as_tensor(recordings).dim() == 1)
         waves = self._load_queries(recordings, fs)
@@ -871,18 +887,39 @@ class FingerprintLibrary:
         else:
             rows, counts = self._fingerprint_tracks(waves, int(max_segments))
             res = self._match_rows(rows, counts, int(k_probe), float(min_overlap_s), int(min_votes), min_score,
-                                   int(top), int(batch_rows))
+                                   int(top), int(batch_rows), nums)
         return res[0] if single and len(res) == 1 else res
 
-    def _match_rows(self, q, counts, k_probe, min_overlap_s, min_votes, min_score, top, batch_rows):
-        """match() from the recordings' rows on: q (n_q, 128) f32 on the device, counts the rows of each recording."""
+    def _match_entry(self, b, d, lo, m, sc, v, n_rec, num=None):
+        """One match of match() from one slot of the kernel's outputs: partner b, delta d, span start lo, span rows m,
+        score, votes, for a recording of n_rec rows; num: the winning ratio of ops.cross_match_tempo (None: dense)."""
+        seg_s = self.segment_s
+        lr, lt = max(1, int(n_rec)), max(1, int(self.first[b + 1] - self.first[b]))
+        if num is None:
+            return {"track": b, "name": self.names[b], "score": sc, "votes": v,
+                    "offset": d, "recording_start_s": lo * seg_s, "track_start_s": (lo + d) * seg_s,
+                    "overlap_s": m * seg_s, "coverage": m / min(lr, lt),
+                    "recording_coverage": m / lr, "track_coverage": m / lt}
+        half = ops.IDENTIFY_TEMPO_DEN // 2
+        w_lo, w_hi = (lo * num + half) >> 8, ((lo + m - 1) * num + half) >> 8
+        mt = w_hi - w_lo + 1                                         # the track's side of the span, in rows
+        return {"track": b, "name": self.names[b], "score": sc, "votes": v,
+                "offset": d, "recording_start_s": lo * seg_s, "track_start_s": (d + w_lo) * seg_s,
+                "overlap_s": m * seg_s, "coverage": max(m / lr, mt / lt),
+                "recording_coverage": m / lr, "track_coverage": mt / lt,
+                "tempo": num / ops.IDENTIFY_TEMPO_DEN, "tempo_num": num, "track_overlap_s": mt * seg_s}
+
+    def _match_rows(self, q, counts, k_probe, min_overlap_s, min_votes, min_score, top, batch_rows, nums=None):
+        """match() from the recordings' rows on: q (n_q, 128) f32 on the device, counts the rows of each recording.
+        nums: the ratio grid of match(tempo=...) (None: the dense kernels)."""
         seg_s, dev = self.segment_s, self.device
         min_overlap = max(1, int(math.ceil(min_overlap_s / seg_s - 1e-9)))
         k = min(k_probe, self.n_rows)
-        lens = np.diff(self.first)
         first_d = torch.from_numpy(self.first).to(dev)
         starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
         out = [[] for _ in counts]
+        if nums is not None:
+            batch_rows = batch_rows // len(nums)                     # the workspace is R times a dense launch's
         s0 = 0
         while s0 < len(counts):
             s1 = s0 + 1
@@ -893,12 +930,16 @@ class FingerprintLibrary:
                 _, ids = self.index.search(qb, k)
                 src = torch.from_numpy(starts[s0:s1 + 1] - starts[s0])
                 kw = dict(top=top, min_votes=min_votes, min_overlap=min_overlap)
-                if self.is_compact:
+                ra_ = None
+                if nums is not None:
+                    res = ops.cross_match_tempo(self.rows(), first_d, qb, src, ids, nums, **kw)
+                    ra_ = res[6].cpu().numpy()
+                elif self.is_compact:
                     res = ops.cross_match_pq(*self.codes(), self._pq["centroids"], self._pq["codebooks"], first_d, qb,
                                              src, ids, **kw)
                 else:
                     res = ops.cross_match(self.rows(), first_d, qb, src, ids, **kw)
-                b_, d_, lo_, m_, sc_, v_ = (x.cpu().numpy() for x in res)
+                b_, d_, lo_, m_, sc_, v_ = (x.cpu().numpy() for x in res[:6])
                 for s in range(s0, s1):
                     for j in range(b_.shape[1]):
                         b = int(b_[s - s0, j])
@@ -910,11 +951,8 @@ class FingerprintLibrary:
                         if min_score is not None and sc < min_score:
                             continue
                         d, lo, m = int(d_[s - s0, j]), int(lo_[s - s0, j]), int(m_[s - s0, j])
-                        lr, lt = max(1, int(counts[s])), max(1, int(lens[b]))
-                        out[s].append({"track": b, "name": self.names[b], "score": sc, "votes": int(v_[s - s0, j]),
-                                       "offset": d, "recording_start_s": lo * seg_s, "track_start_s": (lo + d) * seg_s,
-                                       "overlap_s": m * seg_s, "coverage": m / min(lr, lt),
-                                       "recording_coverage": m / lr, "track_coverage": m / lt})
+                        out[s].append(self._match_entry(b, d, lo, m, sc, int(v_[s - s0, j]), counts[s],
+                                                        None if ra_ is None else int(ra_[s - s0, j])))
             s0 = s1
         return out
 

@@ -1898,14 +1898,7 @@ def identify_tempo(index_rows, track_first_row, q_rows, topk_ids, item_row, item
     if max_len is not None and (int(max_len) > IDENTIFY_MAX_LEN or int(max_len) * k > IDENTIFY_MAX_KEYS):
         raise ValueError(f"identify_tempo: items of {int(max_len)} segments with k={k} exceed {IDENTIFY_MAX_LEN} "
                          f"segments or {IDENTIFY_MAX_KEYS} hits per item")
-    ratios = [int(v) for v in torch.as_tensor(ratio_num).reshape(-1).tolist()]
-    if not 1 <= len(ratios) <= IDENTIFY_TEMPO_MAX_RATIOS:
-        raise ValueError(f"identify_tempo: {len(ratios)} ratios, not 1 to {IDENTIFY_TEMPO_MAX_RATIOS}")
-    if any(b <= a for a, b in zip(ratios, ratios[1:])):
-        raise ValueError("identify_tempo: ratio_num must be strictly ascending")
-    if not all(IDENTIFY_TEMPO_MIN <= v <= IDENTIFY_TEMPO_MAX for v in ratios):
-        raise ValueError(f"identify_tempo: every ratio must lie in [{IDENTIFY_TEMPO_MIN}, {IDENTIFY_TEMPO_MAX}] "
-                         f"(got {min(ratios)} .. {max(ratios)})")
+    ratios = _tempo_ratio_list("identify_tempo", ratio_num)
     if int(index_rows.shape[0]) + 2 * IDENTIFY_MAX_LEN - 1 >= 1 << 32:
         raise ValueError(f"identify_tempo: {int(index_rows.shape[0])} rows reach past the 2^32 alignments a key holds")
     _require_gpu(index_rows, q_rows, topk_ids, item_row, item_len)
@@ -2121,6 +2114,77 @@ def cross_match(index_rows, track_first_row, q_rows, src_first_row, topk_ids, to
         check(lib.grafp_cross_match_f32(_p(index_rows), n, _p(first), first.numel() - 1, _p(q_rows), q_rows.shape[0],
                                         _p(src), n_src, _p(topk_ids), k, top, int(min_votes), int(min_overlap), _p(ws),
                                         ws.numel(), *(_p(o) for o in outs), _stream()), "cross_match")
+    return outs
+
+
+CROSS_MATCH_TEMPO_MAX_ROWS = 4194303                                     # rows per source: i * 512 + 128 fits an int32
+
+
+def _tempo_ratio_list(name, ratio_num):
+    """The ratio checks ops.identify_tempo and ops.cross_match_tempo share -> the ratios as a list of ints."""
+    ratios = [int(v) for v in torch.as_tensor(ratio_num).reshape(-1).tolist()]
+    if not 1 <= len(ratios) <= IDENTIFY_TEMPO_MAX_RATIOS:
+        raise ValueError(f"{name}: {len(ratios)} ratios, not 1 to {IDENTIFY_TEMPO_MAX_RATIOS}")
+    if any(b <= a for a, b in zip(ratios, ratios[1:])):
+        raise ValueError(f"{name}: ratio_num must be strictly ascending")
+    if not all(IDENTIFY_TEMPO_MIN <= v <= IDENTIFY_TEMPO_MAX for v in ratios):
+        raise ValueError(f"{name}: every ratio must lie in [{IDENTIFY_TEMPO_MIN}, {IDENTIFY_TEMPO_MAX}] "
+                         f"(got {min(ratios)} .. {max(ratios)})")
+    return ratios
+
+
+def cross_match_tempo_workspace_bytes(src_rows, k, min_votes, n_ratios, top):
+    """Exact workspace of one ops.cross_match_tempo launch (grafp_cross_match_tempo_workspace): one header, one copy of
+    ops.self_match_workspace_bytes' per-source regions per ratio, six (n_ratios, n_src, top) list arrays."""
+    r = np.ascontiguousarray(np.asarray(src_rows, np.int64).reshape(-1))
+    return int(lib.grafp_cross_match_tempo_workspace(_vp(r.ctypes.data) if r.size else None, int(r.size), int(k),
+                                                     int(min_votes), int(n_ratios), int(top)))
+
+
+def cross_match_tempo(index_rows, track_first_row, q_rows, src_first_row, topk_ids, ratio_num, top=8, min_votes=4,
+                      min_overlap=1):
+    """ops.cross_match for recordings that play faster or slower than the catalogue (grafp_cross_match_tempo_f32: one
+    workgroup per source and ratio, then one per source that merges the ratios' lists).  ratio_num as for
+    ops.identify_tempo: 1 to 64 strictly ascending integers in [128, 512] (host values), each num / 256 track seconds
+    per recording second.  At ratio num row i of a source (counted from the source's row 0) sits w(i) = (i * num + 128)
+    >> 8 library rows after the source's row 0.  A hit r of row i names the track b holding r and the alignment a = r -
+    w(i); a candidate is a unique (b, a, num); votes, span [i_lo, i_hi], m and eligibility as for ops.cross_match, and the
+    score is the mean of <q[i], row[a + w(i)]> over i = i_lo .. i_hi in ops.identify's arithmetic order.  Per partner the
+    best candidate over all ratios: highest score, then the ratio nearer to 1 (smaller |num - 256|, then smaller num),
+    then the smaller a.
+    Returns (track, delta = a - first[b], start = i_lo, length = m, score, votes, ratio int32 = num), each (S, top),
+    padded with -1 / INT_MIN / -1 / 0 / -inf / 0 / 0; at ratio_num = [256] the first six are ops.cross_match's bit for
+    bit.  Limits: ops.cross_match's, sources of at most 4 194 303 rows, n + 2 * (longest source) < 2^32."""
+    top, k = int(top), int(topk_ids.shape[1])
+    n = int(index_rows.shape[0])
+    first_h, src_h, lens = _cross_match_args("cross_match_tempo", n, track_first_row, q_rows, src_first_row, topk_ids,
+                                             top, min_votes, min_overlap)
+    ratios = _tempo_ratio_list("cross_match_tempo", ratio_num)
+    if len(ratios) * top > 4096:
+        raise ValueError(f"cross_match_tempo: {len(ratios)} ratios x top={top} exceed the 4096 slots of the merge")
+    longest = int(lens.max()) if lens.numel() else 0
+    if longest > CROSS_MATCH_TEMPO_MAX_ROWS:
+        raise ValueError(f"cross_match_tempo: a source of {longest} rows exceeds {CROSS_MATCH_TEMPO_MAX_ROWS}")
+    if n + 2 * longest >= 1 << 32:
+        raise ValueError(f"cross_match_tempo: n={n} library rows and a source of {longest} reach past the 2^32 "
+                         "alignments a key holds")
+    _require_gpu(index_rows, q_rows, topk_ids)
+    index_rows, q_rows = _f32c(index_rows), _f32c(q_rows)
+    dev = index_rows.device
+    n_src = lens.numel()
+    outs = _cross_match_outs(n_src, top, dev) + (torch.zeros((n_src, top), dtype=torch.int32, device=dev),)
+    if n_src == 0 or q_rows.shape[0] == 0:
+        return outs
+    first, src = first_h.to(dev), src_h.to(dev)
+    topk_ids = topk_ids.to(torch.int64).contiguous()
+    nums = (ctypes.c_int32 * len(ratios))(*ratios)                       # read by the entry before it returns
+    ws = torch.empty(cross_match_tempo_workspace_bytes(lens.numpy(), k, min_votes, len(ratios), top), dtype=torch.uint8,
+                     device=dev)
+    with _timed("cross_match_tempo", (n_src, int(lens.sum()), k, len(ratios))):
+        check(lib.grafp_cross_match_tempo_f32(_p(index_rows), n, _p(first), first.numel() - 1, _p(q_rows),
+                                              q_rows.shape[0], _p(src), n_src, _p(topk_ids), k, top, int(min_votes),
+                                              int(min_overlap), ctypes.cast(nums, ctypes.c_void_p), len(ratios), _p(ws),
+                                              ws.numel(), *(_p(o) for o in outs), _stream()), "cross_match_tempo")
     return outs
 
 

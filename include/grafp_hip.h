@@ -747,6 +747,42 @@ int grafp_cross_match_pq_f32(const int32_t *list_id, const uint8_t *codes, int64
                              size_t ws_bytes, int32_t *out_track, int32_t *out_delta, int32_t *out_start,
                              int32_t *out_len, float *out_score, int32_t *out_votes, grafp_stream_t stream);
 
+/* ---- recordings that play fast or slow against a library (grafp_amd/library.py; crossmatch_tempo.hip) ------------
+ * grafp_cross_match_tempo_f32 -- grafp_cross_match_f32 for sources that do not run at the catalogue's speed.  Ratios as
+ *   for grafp_identify_tempo_f32: ratio_num (HOST, n_ratios int32, 1 <= n_ratios <= 64) strictly ascending integers num
+ *   in [128, 512], each num / 256 track seconds per recording second.  w(i) = (i * num + 128) >> 8 (integer
+ *   arithmetic), i a row's index inside its source, counted from the source's row 0.
+ *   For every source and ratio j: row i with a hit r in [0, n) names the track b holding r and the alignment
+ *   a = r - w_j(i), the library row on which source row 0 would sit; a candidate is a unique (b, a, j), its votes the
+ *   hits that map to it (duplicates vote twice, nothing is dropped).  Its span is [i_lo, i_hi], the smallest and largest
+ *   voting i, m = i_hi - i_lo + 1; it is eligible iff votes >= min_votes and m >= min_overlap, and scores
+ *   (sum_{i = i_lo..i_hi} <q[i], row[a + w_j(i)]>) / m in the arithmetic order of grafp_identify_f32, the library rows
+ *   gathered (below 256 a row may be read twice, above it rows are skipped); every such row lies in b.  Per partner b the
+ *   best eligible candidate over all ratios is kept: highest score, then the ratio nearer to 1 (smaller |num - 256|,
+ *   then smaller num), then the smaller a.  The `top` partners go out by score descending, then b ascending: the six
+ *   outputs of grafp_cross_match_f32 with out_delta = a - first[b], out_start = i_lo, out_len = m, and out_ratio (int32)
+ *   = num, each (n_src, top), padded with -1 / INT_MIN / -1 / 0 / -inf / 0 / 0.  With ratio_num = {256} the first six
+ *   outputs are bit for bit grafp_cross_match_f32's.
+ *   ws: grafp_cross_match_tempo_workspace(src_rows, n_src, k, min_votes, n_ratios, top) bytes, src_rows (HOST) the rows
+ *   of each source: head + n_ratios * (grafp_self_match_workspace(src_rows, n_src, k, min_votes) - head) + 24 * n_src *
+ *   n_ratios * top with head the header's bytes ((n_src + 1) * 8 rounded up to 256) -- one header, one copy of the
+ *   per-source regions per ratio, six (n_ratios, n_src, top) list arrays; 0 for an n_ratios or top out of range.  A
+ *   ws_bytes below the header and the lists is refused with GRAFP_ERR_WORKSPACE.  The regions' size depends on the
+ *   source table, which is device memory: a ws_bytes below the full size writes nothing outside ws and leaves every
+ *   output padding; there is no -2 mark.  The plan, the (n_src, n_ratios) pass and the merge go out on `stream` with no
+ *   host synchronisation.
+ *   Limits: those of grafp_cross_match_f32; n_ratios * top <= 4096; a source of more than 4 194 303 rows (i * 512 + 128
+ *   must fit an int32) is padding; n + 2 * (longest source) < 2^32 (the alignment field of a key is a + 2 L), which the
+ *   other limits imply. */
+int grafp_cross_match_tempo_f32(const float *index_rows, int64_t n, const int64_t *track_first_row, int n_tracks,
+                                const float *q_rows, int64_t n_qrows, const int64_t *src_first_row, int n_src,
+                                const int64_t *topk_ids, int k, int top, int min_votes, int min_overlap,
+                                const int32_t *ratio_num, int n_ratios, void *ws, size_t ws_bytes, int32_t *out_track,
+                                int32_t *out_delta, int32_t *out_start, int32_t *out_len, float *out_score,
+                                int32_t *out_votes, int32_t *out_ratio, grafp_stream_t stream);
+size_t grafp_cross_match_tempo_workspace(const int64_t *src_rows, int n_src, int k, int min_votes, int n_ratios,
+                                         int top);
+
 #ifdef __cplusplus
 }
 #endif

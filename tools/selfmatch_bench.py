@@ -16,6 +16,12 @@ per-kernel figures.  Target: self_match <= 0.25 x search.
   cross_match_pq[_all_hits]  the same two launches through ops.cross_match_pq against the library encoded at M = 64
                            (a quantiser trained on the first 65 536 rows; the codes decide the rows that are scored, not
                            the work)
+--cross --tempo-ratios 1,15,31: ops.cross_match_tempo (csrc/crossmatch_tempo.hip) at grids of that many ratios against
+dense ops.cross_match on the same tensors, alternating in one loop (medians of --reps).  The sources are the library's
+rows taken along the slope of the grid ratio 266 (+4 %): every track as one source (as many rows as stay inside the
+track), or with --tempo-source-rows N one source of N rows that runs on through the tracks from library row 0 (37 500:
+an hour).  Their hits are the self-search's.  Also reports the workspace bytes of every launch and how many sources
+find their track at ratio 266 over their whole length.
 """
 import argparse
 import json
@@ -67,6 +73,58 @@ def _cross(ops, rows, first, ids, per, reps):
     return {k: round(v, 3) if isinstance(v, float) else v for k, v in res.items()}
 
 
+def _tempo(ops, rows, first, ids, per, reps, counts, source_rows):
+    """The tempo mode (see the top)."""
+    n, dev, num = rows.shape[0], rows.device, 266
+    T = first.numel() - 1
+    if source_rows:
+        L = min(int(source_rows), (n - 1) * 256 // num)
+        g = (torch.arange(L, device=dev, dtype=torch.int64) * num + 128) >> 8
+        lens = np.array([L], np.int64)
+    else:
+        at = (torch.arange(per, device=dev, dtype=torch.int64) * num + 128) >> 8
+        at = at[at < per]
+        L = int(at.numel())
+        g = (first[:-1, None] + at[None, :]).reshape(-1)
+        lens = np.full(T, L, np.int64)
+    q, hits = rows[g].contiguous(), ids[g].contiguous()
+    src_first = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)])).to(dev)
+    kw = dict(top=8, min_votes=4)
+    grids = {}
+    for R in counts:
+        step = 1 if R == 1 else max(1, 30 // (R - 1))
+        grids[R] = [num] if R == 1 else [256 + step * i for i in range(-(R // 2), R - R // 2)]
+        assert num in grids[R] and len(grids[R]) == R, (R, grids[R])
+    runs = {"cross_match_dense_ms": lambda: ops.cross_match(rows, first, q, src_first, hits, **kw)}
+    for R, grid in grids.items():
+        runs[f"cross_match_tempo_R{R}_ms"] = (lambda grid=grid: ops.cross_match_tempo(rows, first, q, src_first, hits,
+                                                                                     grid, **kw))
+    times = {name: [] for name in runs}
+    for fn in runs.values():
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(reps):                                                  # the launches alternate in one loop
+        for name, fn in runs.items():
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            times[name].append(a.elapsed_time(b))
+    res = {"tempo_sources": int(len(lens)), "tempo_rows_per_source": L, "tempo_ratio": num}
+    res.update({name: round(float(np.median(v)), 3) for name, v in times.items()})
+    res["workspace_dense_bytes"] = ops.self_match_workspace_bytes(lens, ids.shape[1], 4)
+    for R in grids:
+        res[f"workspace_tempo_R{R}_bytes"] = ops.cross_match_tempo_workspace_bytes(lens, ids.shape[1], 4, R, 8)
+        b_, _, lo_, m_, sc_, _, ra_ = (x.cpu().numpy() for x in runs[f"cross_match_tempo_R{R}_ms"]())
+        whole = (ra_[:, 0] == num) & (lo_[:, 0] == 0) & (m_[:, 0] == L)
+        res[f"tempo_R{R}_sources_found_whole_at_266"] = int(whole.sum())
+        res[f"tempo_R{R}_best_rows_min"] = int(m_[:, 0].min())
+    d = [x.cpu().numpy() for x in runs["cross_match_dense_ms"]()]
+    res["dense_best_rows_max"] = int(d[3][:, 0].max())
+    return res
+
+
 def main(argv=None):
     from grafp_amd import library, ops
     from grafp_amd.util import load_config
@@ -77,6 +135,10 @@ def main(argv=None):
     ap.add_argument("--k", type=int, default=32)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--cross", action="store_true", help="also time ops.cross_match and ops.cross_match_pq (M = 64)")
+    ap.add_argument("--tempo-ratios", default=None,
+                    help="with --cross: ratio counts, e.g. 1,15,31: time ops.cross_match_tempo against ops.cross_match")
+    ap.add_argument("--tempo-source-rows", type=int, default=0,
+                    help="with --tempo-ratios: one source of this many rows instead of every track as a source")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     cfg = load_config()
@@ -119,6 +181,9 @@ def main(argv=None):
            "stray_pairs": len(stray), "max_stray_score": round(max(stray), 4) if stray else None}
     if args.cross:
         out.update(_cross(ops, rows, first, ids, per, args.reps))
+        if args.tempo_ratios:
+            out.update(_tempo(ops, rows, first, ids, per, args.reps, [int(v) for v in args.tempo_ratios.split(",")],
+                              args.tempo_source_rows))
     print(json.dumps(out))
 
 
