@@ -74,6 +74,45 @@ extern "C" int grafp_draw_pairs_f32(const float *bank, const int64_t *track_star
                                     offset_mod, silence, x_i, x_j, silent_rows, (hipStream_t)stream);
 }
 
+// The size, `top` and alignment checks that the identify entries, and those that the cross-match entries, repeat (name:
+// the operation, for the message).  nlist: null for a library of f32 rows, which align16 covers with the query rows;
+// else the library is held as IVF-PQ codes, nlist joins the sizes, align16 covers the centroids, the codebooks and the
+// query rows and align4 the codes and the list ids.
+static int check_aligned(const char *name, const int *nlist, uintptr_t align16, uintptr_t align4) {
+    if (nlist)
+        GRAFP_REQUIRE((align16 & 15) == 0 && (align4 & 3) == 0,
+                      "%s: centroids, codebooks and query rows must be 16-byte aligned, codes and list ids 4-byte", name);
+    else
+        GRAFP_REQUIRE((align16 & 15) == 0, "%s: rows must be 16-byte aligned", name);
+    return GRAFP_OK;
+}
+
+static int check_identify(const char *name, int64_t n, const int *nlist, int n_tracks, int64_t n_qrows, int n_items,
+                          int top, uintptr_t align16, uintptr_t align4) {
+    const bool sizes = n >= 1 && n < 0x7fffff00ll && n_tracks >= 1 && n_qrows >= 1 && n_items >= 0;
+    if (nlist)
+        GRAFP_REQUIRE(sizes && *nlist >= 1, "%s: bad sizes n=%lld nlist=%d n_tracks=%d n_qrows=%lld n_items=%d", name,
+                      (long long)n, *nlist, n_tracks, (long long)n_qrows, n_items);
+    else
+        GRAFP_REQUIRE(sizes, "%s: bad sizes n=%lld n_tracks=%d n_qrows=%lld n_items=%d", name, (long long)n, n_tracks,
+                      (long long)n_qrows, n_items);
+    GRAFP_REQUIRE(top >= 1 && top <= 64, "%s: top=%d not in [1, 64]", name, top);
+    return check_aligned(name, nlist, align16, align4);
+}
+
+static int check_cross_match(const char *name, int64_t n, const int *nlist, int n_tracks, int64_t n_qrows, int n_src,
+                             uintptr_t align16, uintptr_t align4) {
+    // n + the longest source < 2^32 (the width of a hit key's alignment half) follows from the two row bounds
+    const bool sizes = n >= 1 && n < 0x7fffff00ll && n_tracks >= 1 && n_qrows >= 0 && n_qrows < 0x7fffff00ll && n_src >= 0;
+    if (nlist)
+        GRAFP_REQUIRE(sizes && *nlist >= 1, "%s: bad sizes n=%lld nlist=%d n_tracks=%d n_qrows=%lld n_src=%d", name,
+                      (long long)n, *nlist, n_tracks, (long long)n_qrows, n_src);
+    else
+        GRAFP_REQUIRE(sizes, "%s: bad sizes n=%lld n_tracks=%d n_qrows=%lld n_src=%d", name, (long long)n, n_tracks,
+                      (long long)n_qrows, n_src);
+    return check_aligned(name, nlist, align16, align4);
+}
+
 // Track-aware sequence identification (identify.hip): argument checks here, the kernel and its LDS plan there.
 namespace grafp {
 int identify_launch(const float *rows, int64_t n, const int64_t *first, int T, const float *q_rows,
@@ -89,11 +128,9 @@ extern "C" int grafp_identify_f32(const float *index_rows, int64_t n, const int6
                                   int32_t *out_votes, grafp_stream_t stream) {
     GRAFP_REQUIRE(index_rows && track_first_row && q_rows && topk_ids && item_row && item_len && out_track &&
                   out_offset && out_score && out_votes, "identify: null pointer");
-    GRAFP_REQUIRE(n >= 1 && n < 0x7fffff00ll && n_tracks >= 1 && n_qrows >= 1 && n_items >= 0,
-                  "identify: bad sizes n=%lld n_tracks=%d n_qrows=%lld n_items=%d", (long long)n, n_tracks,
-                  (long long)n_qrows, n_items);
-    GRAFP_REQUIRE(top >= 1 && top <= 64, "identify: top=%d not in [1, 64]", top);
-    GRAFP_REQUIRE((((uintptr_t)index_rows | (uintptr_t)q_rows) & 15) == 0, "identify: rows must be 16-byte aligned");
+    const int st = check_identify("identify", n, nullptr, n_tracks, n_qrows, n_items, top,
+                                  (uintptr_t)index_rows | (uintptr_t)q_rows, 0);
+    if (st != GRAFP_OK) return st;
     return grafp::identify_launch(index_rows, n, track_first_row, n_tracks, q_rows, topk_ids, k, item_row, item_len,
                                   n_items, max_len, top, min_overlap, out_track, out_offset, out_score, out_votes,
                                   (hipStream_t)stream);
@@ -116,12 +153,9 @@ extern "C" int grafp_identify_thin_f32(const float *index_rows, int64_t n, const
                                        grafp_stream_t stream) {
     GRAFP_REQUIRE(index_rows && track_first_row && q_rows && topk_ids && item_row && item_len && out_track &&
                   out_offset && out_score && out_votes, "identify_thin: null pointer");
-    GRAFP_REQUIRE(n >= 1 && n < 0x7fffff00ll && n_tracks >= 1 && n_qrows >= 1 && n_items >= 0,
-                  "identify_thin: bad sizes n=%lld n_tracks=%d n_qrows=%lld n_items=%d", (long long)n, n_tracks,
-                  (long long)n_qrows, n_items);
-    GRAFP_REQUIRE(top >= 1 && top <= 64, "identify_thin: top=%d not in [1, 64]", top);
-    GRAFP_REQUIRE((((uintptr_t)index_rows | (uintptr_t)q_rows) & 15) == 0,
-                  "identify_thin: rows must be 16-byte aligned");
+    const int st = check_identify("identify_thin", n, nullptr, n_tracks, n_qrows, n_items, top,
+                                  (uintptr_t)index_rows | (uintptr_t)q_rows, 0);
+    if (st != GRAFP_OK) return st;
     return grafp::identify_thin_launch(index_rows, n, track_first_row, n_tracks, row_stride, q_rows, topk_ids, k,
                                        item_row, item_len, n_items, max_len, top, min_overlap, out_track, out_offset,
                                        out_score, out_votes, (hipStream_t)stream);
@@ -150,12 +184,9 @@ extern "C" int grafp_identify_tempo_f32(const float *index_rows, int64_t n, cons
                                         int32_t *out_ratio, grafp_stream_t stream) {
     GRAFP_REQUIRE(index_rows && track_first_row && q_rows && topk_ids && item_row && item_len && ratio_num &&
                   out_track && out_offset && out_score && out_votes && out_ratio, "identify_tempo: null pointer");
-    GRAFP_REQUIRE(n >= 1 && n < 0x7fffff00ll && n_tracks >= 1 && n_qrows >= 1 && n_items >= 0,
-                  "identify_tempo: bad sizes n=%lld n_tracks=%d n_qrows=%lld n_items=%d", (long long)n, n_tracks,
-                  (long long)n_qrows, n_items);
-    GRAFP_REQUIRE(top >= 1 && top <= 64, "identify_tempo: top=%d not in [1, 64]", top);
-    GRAFP_REQUIRE((((uintptr_t)index_rows | (uintptr_t)q_rows) & 15) == 0,
-                  "identify_tempo: rows must be 16-byte aligned");
+    const int st = check_identify("identify_tempo", n, nullptr, n_tracks, n_qrows, n_items, top,
+                                  (uintptr_t)index_rows | (uintptr_t)q_rows, 0);
+    if (st != GRAFP_OK) return st;
     return grafp::identify_tempo_launch(index_rows, n, track_first_row, n_tracks, q_rows, topk_ids, k, item_row,
                                         item_len, n_items, max_len, top, min_overlap, ratio_num, n_ratios, ws, out_track,
                                         out_offset, out_score, out_votes, out_ratio, (hipStream_t)stream);
@@ -178,13 +209,10 @@ extern "C" int grafp_identify_pq_f32(const int32_t *list_id, const uint8_t *code
                                      int32_t *out_votes, grafp_stream_t stream) {
     GRAFP_REQUIRE(list_id && codes && centroids && codebooks && track_first_row && q_rows && topk_ids && item_row &&
                   item_len && out_track && out_offset && out_score && out_votes, "identify_pq: null pointer");
-    GRAFP_REQUIRE(n >= 1 && n < 0x7fffff00ll && nlist >= 1 && n_tracks >= 1 && n_qrows >= 1 && n_items >= 0,
-                  "identify_pq: bad sizes n=%lld nlist=%d n_tracks=%d n_qrows=%lld n_items=%d", (long long)n, nlist,
-                  n_tracks, (long long)n_qrows, n_items);
-    GRAFP_REQUIRE(top >= 1 && top <= 64, "identify_pq: top=%d not in [1, 64]", top);
-    GRAFP_REQUIRE((((uintptr_t)centroids | (uintptr_t)codebooks | (uintptr_t)q_rows) & 15) == 0 &&
-                  (((uintptr_t)codes | (uintptr_t)list_id) & 3) == 0,
-                  "identify_pq: centroids, codebooks and query rows must be 16-byte aligned, codes and list ids 4-byte");
+    const int st = check_identify("identify_pq", n, &nlist, n_tracks, n_qrows, n_items, top,
+                                  (uintptr_t)centroids | (uintptr_t)codebooks | (uintptr_t)q_rows,
+                                  (uintptr_t)codes | (uintptr_t)list_id);
+    if (st != GRAFP_OK) return st;
     return grafp::identify_pq_launch(list_id, codes, n, centroids, nlist, codebooks, M, track_first_row, n_tracks, q_rows,
                                      topk_ids, k, item_row, item_len, n_items, max_len, top, min_overlap, out_track,
                                      out_offset, out_score, out_votes, (hipStream_t)stream);
@@ -238,11 +266,9 @@ extern "C" int grafp_cross_match_f32(const float *index_rows, int64_t n, const i
                                      int32_t *out_len, float *out_score, int32_t *out_votes, grafp_stream_t stream) {
     GRAFP_REQUIRE(index_rows && track_first_row && q_rows && src_first_row && topk_ids && out_track && out_delta &&
                   out_start && out_len && out_score && out_votes, "cross_match: null pointer");
-    // n + the longest source < 2^32 (the width of a hit key's alignment half) follows from the two row bounds
-    GRAFP_REQUIRE(n >= 1 && n < 0x7fffff00ll && n_tracks >= 1 && n_qrows >= 0 && n_qrows < 0x7fffff00ll && n_src >= 0,
-                  "cross_match: bad sizes n=%lld n_tracks=%d n_qrows=%lld n_src=%d", (long long)n, n_tracks,
-                  (long long)n_qrows, n_src);
-    GRAFP_REQUIRE((((uintptr_t)index_rows | (uintptr_t)q_rows) & 15) == 0, "cross_match: rows must be 16-byte aligned");
+    const int st = check_cross_match("cross_match", n, nullptr, n_tracks, n_qrows, n_src,
+                                     (uintptr_t)index_rows | (uintptr_t)q_rows, 0);
+    if (st != GRAFP_OK) return st;
     return grafp::cross_match_launch(index_rows, n, track_first_row, n_tracks, q_rows, src_first_row, n_src, topk_ids,
                                      k, top, min_votes, min_overlap, ws, ws_bytes, out_track, out_delta, out_start,
                                      out_len, out_score, out_votes, (hipStream_t)stream);
@@ -258,14 +284,10 @@ extern "C" int grafp_cross_match_pq_f32(const int32_t *list_id, const uint8_t *c
     GRAFP_REQUIRE(list_id && codes && centroids && codebooks && track_first_row && q_rows && src_first_row &&
                   topk_ids && out_track && out_delta && out_start && out_len && out_score && out_votes,
                   "cross_match_pq: null pointer");
-    GRAFP_REQUIRE(n >= 1 && n < 0x7fffff00ll && nlist >= 1 && n_tracks >= 1 && n_qrows >= 0 &&
-                  n_qrows < 0x7fffff00ll && n_src >= 0,
-                  "cross_match_pq: bad sizes n=%lld nlist=%d n_tracks=%d n_qrows=%lld n_src=%d", (long long)n, nlist,
-                  n_tracks, (long long)n_qrows, n_src);
-    GRAFP_REQUIRE((((uintptr_t)centroids | (uintptr_t)codebooks | (uintptr_t)q_rows) & 15) == 0 &&
-                  (((uintptr_t)codes | (uintptr_t)list_id) & 3) == 0,
-                  "cross_match_pq: centroids, codebooks and query rows must be 16-byte aligned, codes and list ids "
-                  "4-byte");
+    const int st = check_cross_match("cross_match_pq", n, &nlist, n_tracks, n_qrows, n_src,
+                                     (uintptr_t)centroids | (uintptr_t)codebooks | (uintptr_t)q_rows,
+                                     (uintptr_t)codes | (uintptr_t)list_id);
+    if (st != GRAFP_OK) return st;
     return grafp::cross_match_pq_launch(list_id, codes, n, centroids, nlist, codebooks, M, track_first_row, n_tracks,
                                         q_rows, src_first_row, n_src, topk_ids, k, top, min_votes, min_overlap, ws,
                                         ws_bytes, out_track, out_delta, out_start, out_len, out_score, out_votes,
@@ -299,11 +321,9 @@ extern "C" int grafp_cross_match_tempo_f32(const float *index_rows, int64_t n, c
     GRAFP_REQUIRE(index_rows && track_first_row && q_rows && src_first_row && topk_ids && ratio_num && out_track &&
                   out_delta && out_start && out_len && out_score && out_votes && out_ratio,
                   "cross_match_tempo: null pointer");
-    GRAFP_REQUIRE(n >= 1 && n < 0x7fffff00ll && n_tracks >= 1 && n_qrows >= 0 && n_qrows < 0x7fffff00ll && n_src >= 0,
-                  "cross_match_tempo: bad sizes n=%lld n_tracks=%d n_qrows=%lld n_src=%d", (long long)n, n_tracks,
-                  (long long)n_qrows, n_src);
-    GRAFP_REQUIRE((((uintptr_t)index_rows | (uintptr_t)q_rows) & 15) == 0,
-                  "cross_match_tempo: rows must be 16-byte aligned");
+    const int st = check_cross_match("cross_match_tempo", n, nullptr, n_tracks, n_qrows, n_src,
+                                     (uintptr_t)index_rows | (uintptr_t)q_rows, 0);
+    if (st != GRAFP_OK) return st;
     return grafp::cross_match_tempo_launch(index_rows, n, track_first_row, n_tracks, q_rows, n_qrows, src_first_row,
                                            n_src, topk_ids, k, top, min_votes, min_overlap, ratio_num, n_ratios, ws,
                                            ws_bytes, out_track, out_delta, out_start, out_len, out_score, out_votes,

@@ -81,8 +81,8 @@ int cross_match_launch(const float *rows, int64_t n, const int64_t *first, int T
     int st = sm_check_launch("cross_match", k, top, min_votes, min_overlap, n_src, ws, ws_bytes);
     if (st != GRAFP_OK || n_src == 0) return st;
     if ((st = cross_match_plan(src_first, n_src, k, min_votes, ws, stream)) != GRAFP_OK) return st;
-    return sm_launch("cross_match_kernel", cross_match_kernel, n_src, stream, rows, n, first, T, q_rows, src_first, ids,
-                     k, top, min_votes, min_overlap, reinterpret_cast<unsigned long long *>(ws),
+    return sm_launch("cross_match_kernel", cross_match_kernel, dim3(n_src), stream, rows, n, first, T, q_rows, src_first,
+                     ids, k, top, min_votes, min_overlap, reinterpret_cast<unsigned long long *>(ws),
                      sm_head_bytes(n_src) / 8, (int64_t)(ws_bytes / 8), out_track, out_delta, out_start, out_len,
                      out_score, out_votes);
 }
@@ -99,7 +99,7 @@ int cross_match_pq_launch(const int32_t *list_id, const unsigned char *codes, in
     if ((st = cross_match_plan(src_first, n_src, k, min_votes, ws, stream)) != GRAFP_OK) return st;
 #define GRAFP_XMPQ_CASE(m)                                                                                             \
     case m:                                                                                                            \
-        return sm_launch("cross_match_pq_kernel", cross_match_pq_kernel<m>, n_src, stream, list_id, codes, n,          \
+        return sm_launch("cross_match_pq_kernel", cross_match_pq_kernel<m>, dim3(n_src), stream, list_id, codes, n,    \
                          centroids, nlist, codebooks, first, T, q_rows, src_first, ids, k, top, min_votes,             \
                          min_overlap, reinterpret_cast<unsigned long long *>(ws), sm_head_bytes(n_src) / 8,            \
                          (int64_t)(ws_bytes / 8), out_track, out_delta, out_start, out_len, out_score, out_votes)

@@ -41,12 +41,7 @@
 namespace grafp {
 
 constexpr int XT_UNROLL = 4;                               // row pairs in flight in the score loop (cross_match_kernel's)
-constexpr int XT_MAX_RATIOS = 64;
 constexpr int XT_MERGE_THREADS = 256;
-
-struct MatchRatios {
-    int32_t num[XT_MAX_RATIOS];                            // travels in the kernel arguments
-};
 
 size_t self_match_workspace(const int64_t *src_rows, int n_src, int k, int min_votes);      // selfmatch.hip
 
@@ -72,7 +67,7 @@ __global__ __launch_bounds__(SM_PLAN_THREADS) void cross_match_tempo_plan_kernel
 }
 
 __global__ __launch_bounds__(SM_THREADS) void cross_match_tempo_kernel(
-    const float *__restrict__ rows, int64_t n, const int64_t *__restrict__ first, int T, MatchRatios ratios, int R,
+    const float *__restrict__ rows, int64_t n, const int64_t *__restrict__ first, int T, TempoRatios ratios, int R,
     const float *__restrict__ q_rows, const int64_t *__restrict__ src_first, const int64_t *__restrict__ ids, int k,
     int top, int min_votes, int min_overlap, unsigned long long *__restrict__ ws, int64_t head_units,
     int64_t cap_units) {
@@ -96,12 +91,12 @@ __global__ __launch_bounds__(SM_THREADS) void cross_match_tempo_kernel(
 }
 
 __global__ __launch_bounds__(XT_MERGE_THREADS) void cross_match_tempo_merge_kernel(
-    MatchRatios ratios, int R, int top, const unsigned long long *__restrict__ ws, int64_t head_units,
+    TempoRatios ratios, int R, int top, const unsigned long long *__restrict__ ws, int64_t head_units,
     int64_t cap_units, int32_t *__restrict__ out_track, int32_t *__restrict__ out_delta,
     int32_t *__restrict__ out_start, int32_t *__restrict__ out_len, float *__restrict__ out_score,
     int32_t *__restrict__ out_votes, int32_t *__restrict__ out_ratio) {
     extern __shared__ __attribute__((aligned(16))) unsigned char xt_smem[];       // 10 * P bytes (the launch's P)
-    __shared__ int order[XT_MAX_RATIOS];                  // order[p]: the ratio of preference rank p
+    __shared__ int order[SEQ_MAX_RATIOS];                  // order[p]: the ratio of preference rank p
     const int src = blockIdx.x, n_src = gridDim.x, tid = threadIdx.x;
     const int total = R * top;
     const int P = xt_merge_slots(R, top);
@@ -120,10 +115,10 @@ __global__ __launch_bounds__(XT_MERGE_THREADS) void cross_match_tempo_merge_kern
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(xt_smem);
     unsigned short *idx = reinterpret_cast<unsigned short *>(xt_smem + (size_t)8 * P);
     if (tid < R) {
-        const int num = ratios.num[tid], d = num < SM_TEMPO_DEN ? SM_TEMPO_DEN - num : num - SM_TEMPO_DEN;
+        const int num = ratios.num[tid], d = num < SEQ_TEMPO_DEN ? SEQ_TEMPO_DEN - num : num - SEQ_TEMPO_DEN;
         int rank = 0;
         for (int j = 0; j < R; ++j) {
-            const int nj = ratios.num[j], dj = nj < SM_TEMPO_DEN ? SM_TEMPO_DEN - nj : nj - SM_TEMPO_DEN;
+            const int nj = ratios.num[j], dj = nj < SEQ_TEMPO_DEN ? SEQ_TEMPO_DEN - nj : nj - SEQ_TEMPO_DEN;
             rank += (dj < d || (dj == d && nj < num)) ? 1 : 0;         // (the ratios are distinct)
         }
         order[rank] = tid;
@@ -181,7 +176,7 @@ __global__ __launch_bounds__(XT_MERGE_THREADS) void cross_match_tempo_merge_kern
 }
 
 size_t cross_match_tempo_workspace(const int64_t *src_rows, int n_src, int k, int min_votes, int n_ratios, int top) {
-    if (n_ratios < 1 || n_ratios > XT_MAX_RATIOS || top < 1 || top > SM_MAX_TOP) return 0;
+    if (n_ratios < 1 || n_ratios > SEQ_MAX_RATIOS || top < 1 || top > SM_MAX_TOP) return 0;
     const size_t dense = self_match_workspace(src_rows, n_src, k, min_votes);
     if (dense == 0) return 0;
     const size_t head = (size_t)sm_head_bytes(n_src);
@@ -194,19 +189,10 @@ int cross_match_tempo_launch(const float *rows, int64_t n, const int64_t *first,
                              size_t ws_bytes, int32_t *out_track, int32_t *out_delta, int32_t *out_start,
                              int32_t *out_len, float *out_score, int32_t *out_votes, int32_t *out_ratio,
                              hipStream_t stream) {
-    GRAFP_REQUIRE(n_ratios >= 1 && n_ratios <= XT_MAX_RATIOS, "cross_match_tempo: n_ratios=%d not in [1, %d]", n_ratios,
-                  XT_MAX_RATIOS);
-    MatchRatios ratios = {};
-    for (int j = 0; j < n_ratios; ++j) {
-        GRAFP_REQUIRE(ratio_num[j] >= SM_TEMPO_MIN && ratio_num[j] <= SM_TEMPO_MAX,
-                      "cross_match_tempo: ratio_num[%d]=%d not in [%d, %d]", j, (int)ratio_num[j], SM_TEMPO_MIN,
-                      SM_TEMPO_MAX);
-        GRAFP_REQUIRE(j == 0 || ratio_num[j] > ratio_num[j - 1],
-                      "cross_match_tempo: ratio_num must be strictly ascending (%d after %d)", (int)ratio_num[j],
-                      j ? (int)ratio_num[j - 1] : 0);
-        ratios.num[j] = ratio_num[j];
-    }
-    int st = sm_check_launch("cross_match_tempo", k, top, min_votes, min_overlap, n_src, ws, ws_bytes);
+    TempoRatios ratios;
+    int st = tempo_ratios("cross_match_tempo", ratio_num, n_ratios, ratios);
+    if (st != GRAFP_OK) return st;
+    st = sm_check_launch("cross_match_tempo", k, top, min_votes, min_overlap, n_src, ws, ws_bytes);
     if (st != GRAFP_OK) return st;
     GRAFP_REQUIRE(n_ratios * top <= 4096, "cross_match_tempo: %d ratios x top=%d exceed the 4096 slots of the merge",
                   n_ratios, top);
@@ -227,15 +213,9 @@ int cross_match_tempo_launch(const float *rows, int64_t n, const int64_t *first,
     hipLaunchKernelGGL(cross_match_tempo_plan_kernel, dim3(1), dim3(SM_PLAN_THREADS), 0, stream, src_first, n_src, k,
                        min_votes, reinterpret_cast<int64_t *>(ws));
     GRAFP_CHECK_LAUNCH("cross_match_tempo_plan_kernel");
-    if (hipFuncSetAttribute((const void *)cross_match_tempo_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)SM_LDS) != hipSuccess) {
-        set_error("cross_match_tempo: cannot reserve %zu bytes of LDS", SM_LDS);
-        return GRAFP_ERR_LAUNCH;
-    }
-    hipLaunchKernelGGL(cross_match_tempo_kernel, dim3(n_src, n_ratios), dim3(SM_THREADS), SM_LDS, stream, rows, n, first,
-                       T, ratios, n_ratios, q_rows, src_first, ids, k, top, min_votes, min_overlap, ws8, head_units,
-                       cap_units);
-    GRAFP_CHECK_LAUNCH("cross_match_tempo_kernel");
+    st = sm_launch("cross_match_tempo", cross_match_tempo_kernel, dim3(n_src, n_ratios), stream, rows, n, first, T, ratios,
+                   n_ratios, q_rows, src_first, ids, k, top, min_votes, min_overlap, ws8, head_units, cap_units);
+    if (st != GRAFP_OK) return st;
     hipLaunchKernelGGL(cross_match_tempo_merge_kernel, dim3(n_src), dim3(XT_MERGE_THREADS),
                        (size_t)10 * xt_merge_slots(n_ratios, top), stream, ratios, n_ratios, top, ws8, head_units,
                        cap_units, out_track, out_delta, out_start, out_len, out_score, out_votes, out_ratio);

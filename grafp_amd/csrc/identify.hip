@@ -63,29 +63,12 @@ int identify_launch(const float *rows, int64_t n, const int64_t *first, int T, c
                     const int64_t *ids, int k, const int64_t *item_row, const int *item_len, int n_items, int max_len,
                     int top, int min_overlap, int32_t *out_track, int32_t *out_offset, float *out_score,
                     int32_t *out_votes, hipStream_t stream) {
-    GRAFP_REQUIRE(max_len >= 1 && max_len <= ID_MAX_LEN && k >= 1 && k <= ID_MAX_K && max_len * k <= ID_MAX_KEYS,
-                  "identify: max_len=%d k=%d exceed %d segments, %d hits per segment or %d keys per item", max_len, k,
-                  ID_MAX_LEN, ID_MAX_K, ID_MAX_KEYS);
-    if (n_items == 0) return GRAFP_OK;
+    const int st = id_check_launch("identify", max_len, k);
+    if (st != GRAFP_OK || n_items == 0) return st;
     const IdentifyPlan plan = identify_plan(max_len, k);
-    const int Pmax = plan.Pmax;
-    const size_t lds = plan.lds;
-    const bool q_lds = plan.q_lds;
-    const void *fn = q_lds ? (const void *)identify_kernel<true> : (const void *)identify_kernel<false>;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        set_error("identify: cannot reserve %zu bytes of LDS", lds);
-        return GRAFP_ERR_LAUNCH;
-    }
-    if (q_lds)
-        hipLaunchKernelGGL(identify_kernel<true>, dim3(n_items), dim3(ID_THREADS), lds, stream, rows, n, first, T,
-                           q_rows, ids, k, item_row, item_len, max_len, Pmax, top, min_overlap, out_track, out_offset,
-                           out_score, out_votes);
-    else
-        hipLaunchKernelGGL(identify_kernel<false>, dim3(n_items), dim3(ID_THREADS), lds, stream, rows, n, first, T,
-                           q_rows, ids, k, item_row, item_len, max_len, Pmax, top, min_overlap, out_track, out_offset,
-                           out_score, out_votes);
-    GRAFP_CHECK_LAUNCH("identify_kernel");
-    return GRAFP_OK;
+    return id_launch("identify", identify_kernel<true>, identify_kernel<false>, plan, dim3(n_items), stream, rows, n,
+                     first, T, q_rows, ids, k, item_row, item_len, max_len, plan.Pmax, top, min_overlap, out_track,
+                     out_offset, out_score, out_votes);
 }
 
 }  // namespace grafp

@@ -39,9 +39,7 @@ constexpr int ID_MAX_LEN = 256;
 constexpr int ID_MAX_K = 32;
 constexpr int ID_MAX_KEYS = 8192;
 constexpr int ID_SHIFT = ID_MAX_LEN - 1;                 // a + ID_SHIFT >= 0 for every hit
-constexpr int ID_TEMPO_DEN = 256;                        // TempoGrid: a ratio is num / 256
-constexpr int ID_TEMPO_MIN = 128, ID_TEMPO_MAX = 512;    // the range of num
-constexpr int ID_TEMPO_SHIFT = 511;                      // w(255) = 510 at num = 512
+constexpr int ID_TEMPO_SHIFT = 511;                      // TempoGrid: w(255) = 510 at num = SEQ_TEMPO_MAX
 constexpr int ID_MAX_STRIDE = 32;                        // ThinGrid: the largest row stride
 constexpr size_t ID_LDS = 160 * 1024 - 256;      // dynamic LDS budget (the static s_ncand sits next to it)
 
@@ -59,6 +57,22 @@ inline IdentifyPlan identify_plan(int max_len, int k) {
     p.q_lds = slots + qbytes <= ID_LDS;
     p.lds = p.q_lds ? slots + qbytes : slots;
     return p;
+}
+
+// the limit check every identify launch shares (name: the operation, for the message)
+inline int id_check_launch(const char *name, int max_len, int k) {
+    GRAFP_REQUIRE(max_len >= 1 && max_len <= ID_MAX_LEN && k >= 1 && k <= ID_MAX_K && max_len * k <= ID_MAX_KEYS,
+                  "%s: max_len=%d k=%d exceed %d segments, %d hits per segment or %d keys per item", name, max_len, k,
+                  ID_MAX_LEN, ID_MAX_K, ID_MAX_KEYS);
+    return GRAFP_OK;
+}
+
+// reserves the plan's dynamic LDS for the kernel the plan chooses (query rows in LDS / in global memory) and launches it
+// on `grid` (blockIdx.x = the item); the caller places plan.Pmax among args where the kernel expects it
+template <typename... Params, typename... Args>
+inline int id_launch(const char *name, void (*kernel_q_lds)(Params...), void (*kernel_q_global)(Params...),
+                     const IdentifyPlan &plan, dim3 grid, hipStream_t stream, Args... args) {
+    return seq_launch(name, plan.q_lds ? kernel_q_lds : kernel_q_global, grid, ID_THREADS, plan.lds, stream, args...);
 }
 
 struct DenseGrid {
@@ -108,7 +122,7 @@ struct ThinGrid {
 };
 
 // One row per fine position; the recording runs at num / 256 of the catalogue's speed, so query row s sits
-// w(s) = (s * num + 128) >> 8 rows after query row 0 (num in [ID_TEMPO_MIN, ID_TEMPO_MAX]; w(s) <= 510 for s <= 255).
+// w(s) = (s * num + 128) >> 8 rows after query row 0 (num in [SEQ_TEMPO_MIN, SEQ_TEMPO_MAX]; w(s) <= 510 for s <= 255).
 // w never decreases, so the pairs of an alignment are a contiguous range of s: w(s) >= x iff s * num + 128 >= 256 * x.
 // The host keeps n + ID_TEMPO_SHIFT below 2^32.  Its Span gathers: span(x, a, lo, num, l, m) reads row a + w(lo + t).
 struct TempoGrid {
@@ -116,16 +130,16 @@ struct TempoGrid {
     __device__ __forceinline__ int64_t fine(int64_t r) const { return r; }
     __device__ __forceinline__ int64_t row(int64_t p) const { return p; }
     __device__ __forceinline__ int need(int need_q) const { return need_q; }
-    __device__ __forceinline__ int at(int s) const { return (s * num + ID_TEMPO_DEN / 2) >> 8; }
+    __device__ __forceinline__ int at(int s) const { return (s * num + SEQ_TEMPO_DEN / 2) >> 8; }
     __device__ __forceinline__ int shift() const { return ID_TEMPO_SHIFT; }
     __device__ __forceinline__ int64_t cap(int64_t L) const {
-        const int64_t c = L * ID_TEMPO_DEN / num;
+        const int64_t c = L * SEQ_TEMPO_DEN / num;
         return c > 1 ? c : 1;
     }
     // the first s in [0, ql] with w(s) >= x (ql: none)
     __device__ __forceinline__ int first_at(int64_t x, int ql) const {
         if (x <= 0) return 0;
-        const int64_t s = (x * ID_TEMPO_DEN - ID_TEMPO_DEN / 2 + num - 1) / num;
+        const int64_t s = (x * SEQ_TEMPO_DEN - SEQ_TEMPO_DEN / 2 + num - 1) / num;
         return s < ql ? (int)s : ql;
     }
     __device__ __forceinline__ void pairs(int64_t a, int64_t f0, int64_t f1, int ql, int &lo, int &o) const {

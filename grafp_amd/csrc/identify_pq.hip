@@ -40,46 +40,20 @@ __global__ __launch_bounds__(ID_THREADS) void identify_pq_kernel(
                          out_track, out_offset, out_score, out_votes);
 }
 
-template <int kM, bool kQLds>
-static int identify_pq_launch_as(const IdentifyPlan &plan, const int32_t *list_id, const unsigned char *codes, int64_t n,
-                                 const float *centroids, int nlist, const float *codebooks, const int64_t *first, int T,
-                                 const float *q_rows, const int64_t *ids, int k, const int64_t *item_row,
-                                 const int *item_len, int n_items, int max_len, int top, int min_overlap,
-                                 int32_t *out_track, int32_t *out_offset, float *out_score, int32_t *out_votes,
-                                 hipStream_t stream) {
-    if (hipFuncSetAttribute((const void *)identify_pq_kernel<kM, kQLds>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)plan.lds) != hipSuccess) {
-        set_error("identify_pq: cannot reserve %zu bytes of LDS", plan.lds);
-        return GRAFP_ERR_LAUNCH;
-    }
-    hipLaunchKernelGGL((identify_pq_kernel<kM, kQLds>), dim3(n_items), dim3(ID_THREADS), plan.lds, stream, list_id,
-                       codes, n, centroids, nlist, codebooks, first, T, q_rows, ids, k, item_row, item_len, max_len,
-                       plan.Pmax, top, min_overlap, out_track, out_offset, out_score, out_votes);
-    GRAFP_CHECK_LAUNCH("identify_pq_kernel");
-    return GRAFP_OK;
-}
-
 int identify_pq_launch(const int32_t *list_id, const unsigned char *codes, int64_t n, const float *centroids, int nlist,
                        const float *codebooks, int M, const int64_t *first, int T, const float *q_rows,
                        const int64_t *ids, int k, const int64_t *item_row, const int *item_len, int n_items,
                        int max_len, int top, int min_overlap, int32_t *out_track, int32_t *out_offset, float *out_score,
                        int32_t *out_votes, hipStream_t stream) {
     GRAFP_REQUIRE(M == 16 || M == 32 || M == 64 || M == 128, "identify_pq: M=%d not one of 16, 32, 64, 128", M);
-    GRAFP_REQUIRE(max_len >= 1 && max_len <= ID_MAX_LEN && k >= 1 && k <= ID_MAX_K && max_len * k <= ID_MAX_KEYS,
-                  "identify_pq: max_len=%d k=%d exceed %d segments, %d hits per segment or %d keys per item", max_len,
-                  k, ID_MAX_LEN, ID_MAX_K, ID_MAX_KEYS);
-    if (n_items == 0) return GRAFP_OK;
+    const int st = id_check_launch("identify_pq", max_len, k);
+    if (st != GRAFP_OK || n_items == 0) return st;
     const IdentifyPlan plan = identify_plan(max_len, k);
+    decltype(&identify_pq_kernel<16, true>) q_lds, q_global;
 #define GRAFP_IDPQ_CASE(m)                                                                                             \
     case m:                                                                                                            \
-        return plan.q_lds ? identify_pq_launch_as<m, true>(plan, list_id, codes, n, centroids, nlist, codebooks, first, \
-                                                           T, q_rows, ids, k, item_row, item_len, n_items, max_len,    \
-                                                           top, min_overlap, out_track, out_offset, out_score,         \
-                                                           out_votes, stream)                                          \
-                          : identify_pq_launch_as<m, false>(plan, list_id, codes, n, centroids, nlist, codebooks,      \
-                                                            first, T, q_rows, ids, k, item_row, item_len, n_items,     \
-                                                            max_len, top, min_overlap, out_track, out_offset,          \
-                                                            out_score, out_votes, stream)
+        q_lds = identify_pq_kernel<m, true>, q_global = identify_pq_kernel<m, false>;                                  \
+        break
     switch (M) {
         GRAFP_IDPQ_CASE(16);
         GRAFP_IDPQ_CASE(32);
@@ -88,6 +62,9 @@ int identify_pq_launch(const int32_t *list_id, const unsigned char *codes, int64
             GRAFP_IDPQ_CASE(128);
     }
 #undef GRAFP_IDPQ_CASE
+    return id_launch("identify_pq", q_lds, q_global, plan, dim3(n_items), stream, list_id, codes, n, centroids, nlist,
+                     codebooks, first, T, q_rows, ids, k, item_row, item_len, max_len, plan.Pmax, top, min_overlap,
+                     out_track, out_offset, out_score, out_votes);
 }
 
 }  // namespace grafp

@@ -41,11 +41,6 @@ namespace grafp {
 
 // row pairs in flight in the score loop: query rows in LDS / in global memory (identify.hip's counts)
 constexpr int IDR_UNROLL_QLDS = 4, IDR_UNROLL_QGLOBAL = 1;
-constexpr int IDR_MAX_RATIOS = 64;
-
-struct TempoRatios {
-    int32_t num[IDR_MAX_RATIOS];                         // travels in the kernel arguments
-};
 
 // slots of one item's merge: the power of two >= max(64, R * top), at most 4096 (host: R <= 64, top <= 64)
 __host__ __device__ inline int merge_slots(int R, int top) {
@@ -73,17 +68,17 @@ __global__ __launch_bounds__(ID_THREADS) void identify_tempo_merge_kernel(
     int32_t *__restrict__ out_offset, float *__restrict__ out_score, int32_t *__restrict__ out_votes,
     int32_t *__restrict__ out_ratio) {
     extern __shared__ __attribute__((aligned(16))) unsigned char idr_smem[];      // 10 * P bytes (the launch's P)
-    __shared__ int order[IDR_MAX_RATIOS];                 // order[p]: the ratio of preference rank p
+    __shared__ int order[SEQ_MAX_RATIOS];                 // order[p]: the ratio of preference rank p
     const int item = blockIdx.x, n_items = gridDim.x, tid = threadIdx.x;
     const int total = R * top;
     const int P = merge_slots(R, top);
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(idr_smem);
     unsigned short *idx = reinterpret_cast<unsigned short *>(idr_smem + (size_t)8 * P);
     if (tid < R) {
-        const int num = ratios.num[tid], d = num < ID_TEMPO_DEN ? ID_TEMPO_DEN - num : num - ID_TEMPO_DEN;
+        const int num = ratios.num[tid], d = num < SEQ_TEMPO_DEN ? SEQ_TEMPO_DEN - num : num - SEQ_TEMPO_DEN;
         int rank = 0;
         for (int j = 0; j < R; ++j) {
-            const int nj = ratios.num[j], dj = nj < ID_TEMPO_DEN ? ID_TEMPO_DEN - nj : nj - ID_TEMPO_DEN;
+            const int nj = ratios.num[j], dj = nj < SEQ_TEMPO_DEN ? SEQ_TEMPO_DEN - nj : nj - SEQ_TEMPO_DEN;
             rank += (dj < d || (dj == d && nj < num)) ? 1 : 0;         // (the ratios are distinct)
         }
         order[rank] = tid;
@@ -142,26 +137,8 @@ __global__ __launch_bounds__(ID_THREADS) void identify_tempo_merge_kernel(
 }
 
 size_t identify_tempo_workspace(int n_items, int n_ratios, int top) {
-    if (n_items < 0 || n_ratios < 1 || n_ratios > IDR_MAX_RATIOS || top < 1 || top > 64) return 0;
+    if (n_items < 0 || n_ratios < 1 || n_ratios > SEQ_MAX_RATIOS || top < 1 || top > 64) return 0;
     return (size_t)16 * n_items * n_ratios * top;
-}
-
-template <bool kQLds>
-static int identify_tempo_launch_as(const IdentifyPlan &plan, const float *rows, int64_t n, const int64_t *first, int T,
-                                    const TempoRatios &ratios, int R, const float *q_rows, const int64_t *ids, int k,
-                                    const int64_t *item_row, const int *item_len, int n_items, int max_len, int top,
-                                    int min_overlap, int32_t *ws_track, int32_t *ws_offset, float *ws_score,
-                                    int32_t *ws_votes, hipStream_t stream) {
-    if (hipFuncSetAttribute((const void *)identify_tempo_kernel<kQLds>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)plan.lds) != hipSuccess) {
-        set_error("identify_tempo: cannot reserve %zu bytes of LDS", plan.lds);
-        return GRAFP_ERR_LAUNCH;
-    }
-    hipLaunchKernelGGL(identify_tempo_kernel<kQLds>, dim3(n_items, R), dim3(ID_THREADS), plan.lds, stream, rows, n,
-                       first, T, ratios, q_rows, ids, k, item_row, item_len, max_len, plan.Pmax, top, min_overlap,
-                       ws_track, ws_offset, ws_score, ws_votes);
-    GRAFP_CHECK_LAUNCH("identify_tempo_kernel");
-    return GRAFP_OK;
 }
 
 int identify_tempo_launch(const float *rows, int64_t n, const int64_t *first, int T, const float *q_rows,
@@ -169,38 +146,23 @@ int identify_tempo_launch(const float *rows, int64_t n, const int64_t *first, in
                           int max_len, int top, int min_overlap, const int32_t *ratio_num, int n_ratios, void *ws,
                           int32_t *out_track, int32_t *out_offset, float *out_score, int32_t *out_votes,
                           int32_t *out_ratio, hipStream_t stream) {
-    GRAFP_REQUIRE(n_ratios >= 1 && n_ratios <= IDR_MAX_RATIOS, "identify_tempo: n_ratios=%d not in [1, %d]", n_ratios,
-                  IDR_MAX_RATIOS);
-    TempoRatios ratios = {};
-    for (int j = 0; j < n_ratios; ++j) {
-        GRAFP_REQUIRE(ratio_num[j] >= ID_TEMPO_MIN && ratio_num[j] <= ID_TEMPO_MAX,
-                      "identify_tempo: ratio_num[%d]=%d not in [%d, %d]", j, (int)ratio_num[j], ID_TEMPO_MIN,
-                      ID_TEMPO_MAX);
-        GRAFP_REQUIRE(j == 0 || ratio_num[j] > ratio_num[j - 1],
-                      "identify_tempo: ratio_num must be strictly ascending (%d after %d)", (int)ratio_num[j],
-                      j ? (int)ratio_num[j - 1] : 0);
-        ratios.num[j] = ratio_num[j];
-    }
+    TempoRatios ratios;
+    int st = tempo_ratios("identify_tempo", ratio_num, n_ratios, ratios);
+    if (st != GRAFP_OK) return st;
     GRAFP_REQUIRE(n + ID_TEMPO_SHIFT < (1ll << 32),
                   "identify_tempo: n=%lld rows reach past the 2^32 alignments of a key", (long long)n);
-    GRAFP_REQUIRE(max_len >= 1 && max_len <= ID_MAX_LEN && k >= 1 && k <= ID_MAX_K && max_len * k <= ID_MAX_KEYS,
-                  "identify_tempo: max_len=%d k=%d exceed %d segments, %d hits per segment or %d keys per item", max_len,
-                  k, ID_MAX_LEN, ID_MAX_K, ID_MAX_KEYS);
-    if (n_items == 0) return GRAFP_OK;
+    st = id_check_launch("identify_tempo", max_len, k);
+    if (st != GRAFP_OK || n_items == 0) return st;
     GRAFP_REQUIRE(ws && ((uintptr_t)ws & 15) == 0, "identify_tempo: the workspace is missing or not 16-byte aligned");
     const size_t lists = (size_t)n_ratios * n_items * top;
     int32_t *ws_track = reinterpret_cast<int32_t *>(ws), *ws_offset = ws_track + lists;
     float *ws_score = reinterpret_cast<float *>(ws_offset + lists);
     int32_t *ws_votes = reinterpret_cast<int32_t *>(ws_score + lists);
     const IdentifyPlan plan = identify_plan(max_len, k);
-    const int rc = plan.q_lds ? identify_tempo_launch_as<true>(plan, rows, n, first, T, ratios, n_ratios, q_rows, ids, k,
-                                                               item_row, item_len, n_items, max_len, top, min_overlap,
-                                                               ws_track, ws_offset, ws_score, ws_votes, stream)
-                              : identify_tempo_launch_as<false>(plan, rows, n, first, T, ratios, n_ratios, q_rows, ids,
-                                                                k, item_row, item_len, n_items, max_len, top,
-                                                                min_overlap, ws_track, ws_offset, ws_score, ws_votes,
-                                                                stream);
-    if (rc != GRAFP_OK) return rc;
+    st = id_launch("identify_tempo", identify_tempo_kernel<true>, identify_tempo_kernel<false>, plan,
+                   dim3(n_items, n_ratios), stream, rows, n, first, T, ratios, q_rows, ids, k, item_row, item_len,
+                   max_len, plan.Pmax, top, min_overlap, ws_track, ws_offset, ws_score, ws_votes);
+    if (st != GRAFP_OK) return st;
     hipLaunchKernelGGL(identify_tempo_merge_kernel, dim3(n_items), dim3(ID_THREADS), (size_t)10 * merge_slots(n_ratios, top),
                        stream, ratios, n_ratios, top,
                        ws_track, ws_offset, ws_score, ws_votes, out_track, out_offset, out_score, out_votes, out_ratio);

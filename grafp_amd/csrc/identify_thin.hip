@@ -41,24 +41,6 @@ __global__ __launch_bounds__(ID_THREADS) void identify_thin_kernel(
                          min_overlap, out_track, out_offset, out_score, out_votes);
 }
 
-template <bool kQLds>
-static int identify_thin_launch_as(const IdentifyPlan &plan, const float *rows, int64_t n, const int64_t *first, int T,
-                                   int D, const float *q_rows, const int64_t *ids, int k, const int64_t *item_row,
-                                   const int *item_len, int n_items, int max_len, int top, int min_overlap,
-                                   int32_t *out_track, int32_t *out_offset, float *out_score, int32_t *out_votes,
-                                   hipStream_t stream) {
-    if (hipFuncSetAttribute((const void *)identify_thin_kernel<kQLds>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)plan.lds) != hipSuccess) {
-        set_error("identify_thin: cannot reserve %zu bytes of LDS", plan.lds);
-        return GRAFP_ERR_LAUNCH;
-    }
-    hipLaunchKernelGGL(identify_thin_kernel<kQLds>, dim3(n_items), dim3(ID_THREADS), plan.lds, stream, rows, n, first,
-                       T, D, q_rows, ids, k, item_row, item_len, max_len, plan.Pmax, top, min_overlap, out_track,
-                       out_offset, out_score, out_votes);
-    GRAFP_CHECK_LAUNCH("identify_thin_kernel");
-    return GRAFP_OK;
-}
-
 int identify_thin_launch(const float *rows, int64_t n, const int64_t *first, int T, int row_stride,
                          const float *q_rows, const int64_t *ids, int k, const int64_t *item_row, const int *item_len,
                          int n_items, int max_len, int top, int min_overlap, int32_t *out_track, int32_t *out_offset,
@@ -68,17 +50,12 @@ int identify_thin_launch(const float *rows, int64_t n, const int64_t *first, int
     GRAFP_REQUIRE(n * row_stride + ID_SHIFT < (1ll << 32),
                   "identify_thin: n=%lld rows at row_stride=%d reach past the 2^32 fine positions of a key",
                   (long long)n, row_stride);
-    GRAFP_REQUIRE(max_len >= 1 && max_len <= ID_MAX_LEN && k >= 1 && k <= ID_MAX_K && max_len * k <= ID_MAX_KEYS,
-                  "identify_thin: max_len=%d k=%d exceed %d segments, %d hits per segment or %d keys per item", max_len,
-                  k, ID_MAX_LEN, ID_MAX_K, ID_MAX_KEYS);
-    if (n_items == 0) return GRAFP_OK;
+    const int st = id_check_launch("identify_thin", max_len, k);
+    if (st != GRAFP_OK || n_items == 0) return st;
     const IdentifyPlan plan = identify_plan(max_len, k);
-    return plan.q_lds ? identify_thin_launch_as<true>(plan, rows, n, first, T, row_stride, q_rows, ids, k, item_row,
-                                                      item_len, n_items, max_len, top, min_overlap, out_track,
-                                                      out_offset, out_score, out_votes, stream)
-                      : identify_thin_launch_as<false>(plan, rows, n, first, T, row_stride, q_rows, ids, k, item_row,
-                                                       item_len, n_items, max_len, top, min_overlap, out_track,
-                                                       out_offset, out_score, out_votes, stream);
+    return id_launch("identify_thin", identify_thin_kernel<true>, identify_thin_kernel<false>, plan, dim3(n_items),
+                     stream, rows, n, first, T, row_stride, q_rows, ids, k, item_row, item_len, max_len, plan.Pmax, top,
+                     min_overlap, out_track, out_offset, out_score, out_votes);
 }
 
 }  // namespace grafp

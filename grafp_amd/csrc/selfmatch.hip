@@ -83,8 +83,8 @@ int self_match_launch(const float *rows, int64_t n, const int64_t *first, int T,
     hipLaunchKernelGGL(self_match_plan_kernel, dim3(1), dim3(SM_PLAN_THREADS), 0, stream, first, tracks, n_src, k,
                        min_votes, reinterpret_cast<int64_t *>(ws));
     GRAFP_CHECK_LAUNCH("self_match_plan_kernel");
-    return sm_launch("self_match_kernel", self_match_kernel, n_src, stream, rows, n, first, T, ids, k, tracks, top,
-                     min_votes, min_overlap, reinterpret_cast<unsigned long long *>(ws), sm_head_bytes(n_src) / 8,
+    return sm_launch("self_match_kernel", self_match_kernel, dim3(n_src), stream, rows, n, first, T, ids, k, tracks,
+                     top, min_votes, min_overlap, reinterpret_cast<unsigned long long *>(ws), sm_head_bytes(n_src) / 8,
                      (int64_t)(ws_bytes / 8), out_track, out_delta, out_start, out_len, out_score, out_votes);
 }
 

@@ -89,13 +89,12 @@ struct MatchDenseGrid {
 };
 
 // The source runs at num / 256 of the catalogue's speed: row i sits w(i) = (i * num + 128) >> 8 rows after row 0 (num in
-// [SM_TEMPO_MIN, SM_TEMPO_MAX]; i * num + 128 stays inside an int32 for the SM_TEMPO_MAX_ROWS a source may have, and
-// w(L - 1) <= 2 L - 2, hence the shift).  Its Span gathers: span(x, a, lo, num, l, m) reads row a + w(lo + t).
-constexpr int SM_TEMPO_DEN = 256, SM_TEMPO_MIN = 128, SM_TEMPO_MAX = 512;
+// [SEQ_TEMPO_MIN, SEQ_TEMPO_MAX] of seqmatch.h; i * num + 128 stays inside an int32 for the SM_TEMPO_MAX_ROWS a source
+// may have, and w(L - 1) <= 2 L - 2, hence the shift).  Its Span gathers: span(x, a, lo, num, l, m) reads row a + w(lo + t).
 constexpr int64_t SM_TEMPO_MAX_ROWS = 4194303;             // (2^31 - 128) / 512
 struct MatchTempoGrid {
     int num;
-    __device__ __forceinline__ int64_t at(int64_t i) const { return ((int)i * num + SM_TEMPO_DEN / 2) >> 8; }
+    __device__ __forceinline__ int64_t at(int64_t i) const { return ((int)i * num + SEQ_TEMPO_DEN / 2) >> 8; }
     __device__ __forceinline__ int64_t shift(int64_t L) const { return 2 * L; }
     template <typename Span>
     __device__ __forceinline__ float score(const Span &span, const float4 *x, int64_t a, int lo, int l, int m) const {
@@ -364,17 +363,10 @@ inline int sm_check_launch(const char *name, int k, int top, int min_votes, int 
     return GRAFP_OK;
 }
 
-// reserves the dynamic LDS of one match kernel and launches it, one workgroup per source
+// reserves the dynamic LDS of one match kernel and launches it on `grid` (blockIdx.x = the source)
 template <typename... Params, typename... Args>
-inline int sm_launch(const char *name, void (*kernel)(Params...), int n_src, hipStream_t stream, Args... args) {
-    if (hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SM_LDS) !=
-        hipSuccess) {
-        set_error("%s: cannot reserve %zu bytes of LDS", name, SM_LDS);
-        return GRAFP_ERR_LAUNCH;
-    }
-    hipLaunchKernelGGL(kernel, dim3(n_src), dim3(SM_THREADS), SM_LDS, stream, args...);
-    GRAFP_CHECK_LAUNCH(name);
-    return GRAFP_OK;
+inline int sm_launch(const char *name, void (*kernel)(Params...), dim3 grid, hipStream_t stream, Args... args) {
+    return seq_launch(name, kernel, grid, SM_THREADS, SM_LDS, stream, args...);
 }
 
 }  // namespace grafp

@@ -1,7 +1,8 @@
 // seqmatch.h -- what the sequence-matching kernels share: seq_rerank.hip (row-level rerank), identify.hip and
 // identify_pq.hip (track-aware identification), selfmatch.hip and crossmatch.hip (shared audio inside a library, and of
-// recordings against one).  Device helpers only, no state; compiles with and
-// without the packed-f32 instructions (Makefile NOPK).
+// recordings against one).  Device helpers, and at the end what their host launches share (the speed ratios of the
+// tempo kernels, the launch with reserved LDS); no state; compiles with and without the packed-f32 instructions
+// (Makefile NOPK).
 //
 // THE arithmetic order of a span score (restated for the CPU in oracle/csrc/seq_rerank.c and tests/_identify_ref.py):
 // a span is m pairs of 128-float rows (x[t], y[t]), t = 0..m-1.  Lane l of a 32-lane half-wave owns dims 4l..4l+3 and
@@ -91,6 +92,42 @@ __device__ __forceinline__ float span_sum(const float4 *x, const float4 *y, int 
 #pragma unroll
     for (int s = 16; s > 0; s >>= 1) acc += __shfl_xor(acc, s);      // stays inside the 32-lane half
     return acc;
+}
+
+// The speed ratios of identify_tempo.hip and crossmatch_tempo.hip: an integer num in [SEQ_TEMPO_MIN, SEQ_TEMPO_MAX] stands
+// for num / SEQ_TEMPO_DEN track seconds per recording second; a call names up to SEQ_MAX_RATIOS of them, ascending.
+constexpr int SEQ_TEMPO_DEN = 256, SEQ_TEMPO_MIN = 128, SEQ_TEMPO_MAX = 512;
+constexpr int SEQ_MAX_RATIOS = 64;
+struct TempoRatios {
+    int32_t num[SEQ_MAX_RATIOS];                           // travels in the kernel arguments
+};
+
+// host: checks a call's ratios and copies them into the table (name: the operation, for the message)
+inline int tempo_ratios(const char *name, const int32_t *ratio_num, int n_ratios, TempoRatios &ratios) {
+    GRAFP_REQUIRE(n_ratios >= 1 && n_ratios <= SEQ_MAX_RATIOS, "%s: n_ratios=%d not in [1, %d]", name, n_ratios,
+                  SEQ_MAX_RATIOS);
+    ratios = {};
+    for (int j = 0; j < n_ratios; ++j) {
+        GRAFP_REQUIRE(ratio_num[j] >= SEQ_TEMPO_MIN && ratio_num[j] <= SEQ_TEMPO_MAX, "%s: ratio_num[%d]=%d not in [%d, %d]",
+                      name, j, (int)ratio_num[j], SEQ_TEMPO_MIN, SEQ_TEMPO_MAX);
+        GRAFP_REQUIRE(j == 0 || ratio_num[j] > ratio_num[j - 1], "%s: ratio_num must be strictly ascending (%d after %d)",
+                      name, (int)ratio_num[j], j ? (int)ratio_num[j - 1] : 0);
+        ratios.num[j] = ratio_num[j];
+    }
+    return GRAFP_OK;
+}
+
+// host: reserves `lds` bytes of dynamic LDS for a kernel and launches it (name: for the messages)
+template <typename... Params, typename... Args>
+inline int seq_launch(const char *name, void (*kernel)(Params...), dim3 grid, int threads, size_t lds,
+                      hipStream_t stream, Args... args) {
+    if (hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        set_error("%s: cannot reserve %zu bytes of LDS", name, lds);
+        return GRAFP_ERR_LAUNCH;
+    }
+    hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, stream, args...);
+    GRAFP_CHECK_LAUNCH(name);
+    return GRAFP_OK;
 }
 
 }  // namespace grafp

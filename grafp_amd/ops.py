@@ -1760,6 +1760,42 @@ def check_track_table(first, n):
     return f
 
 
+def _identify_args(name, n_rows, track_first_row, q_rows, topk_ids, item_row, item_len, top, min_overlap, max_len):
+    """The host checks the identify ops share, for a library of n_rows rows -> (n_items, k, top, max_len, min_overlap as
+    the int the C entry takes).  Without max_len, and with items, the longest item is read back (the max_len returned)
+    and the track table and the item ranges are checked on the host; with it nothing here touches a device.  max_len stays
+    None only when there is no item."""
+    n_items, k, top = int(item_row.shape[0]), int(topk_ids.shape[1]), int(top)
+    # argument checks first (host values only): they hold on any device
+    if not 1 <= top <= 64:
+        raise ValueError(f"{name}: top={top} not in [1, 64]")
+    if not 1 <= k <= IDENTIFY_MAX_K:
+        raise ValueError(f"{name}: k={k} hits per segment exceeds {IDENTIFY_MAX_K}")
+    if min_overlap is not None and int(min_overlap) < 1:
+        raise ValueError(f"{name}: min_overlap must be at least 1 segment")
+    if max_len is None and n_items:
+        max_len = max(1, int(item_len.max().item()))
+        check_track_table(track_first_row, n_rows)
+        _check_items_inside(name, item_row, item_len, q_rows.shape[0])
+    if max_len is not None and (int(max_len) > IDENTIFY_MAX_LEN or int(max_len) * k > IDENTIFY_MAX_KEYS):
+        raise ValueError(f"{name}: items of {int(max_len)} segments with k={k} exceed {IDENTIFY_MAX_LEN} segments "
+                         f"or {IDENTIFY_MAX_KEYS} hits per item")
+    return (n_items, k, top, None if max_len is None else int(max_len),
+            0 if min_overlap is None else int(min_overlap))
+
+
+def _identify_tensors(dev, track_first_row, topk_ids, item_row, item_len, top, n_outs=4):
+    """The track table, the hits and the items in the C entry's dtypes on dev, and the n_outs (n_items, top) results
+    (track, offset, score, votes and, for the tempo op, ratio: int32 but score f32), uninitialised."""
+    first = torch.as_tensor(track_first_row).detach().to(device=dev, dtype=torch.int64).contiguous()
+    topk_ids = topk_ids.to(torch.int64).contiguous()
+    item_row = item_row.to(torch.int64).contiguous()
+    item_len = item_len.to(torch.int32).contiguous()
+    outs = tuple(torch.empty((item_row.shape[0], top), dtype=torch.float32 if j == 2 else torch.int32, device=dev)
+                 for j in range(n_outs))
+    return first, topk_ids, item_row, item_len, outs
+
+
 def identify(index_rows, track_first_row, q_rows, topk_ids, item_row, item_len, top=5, min_overlap=None, max_len=None):
     """Track-aware sequence identification (grafp_identify_f32, one workgroup per item): for every item, the `top`
     library tracks it most likely is, with the alignment inside each.
@@ -1772,40 +1808,18 @@ def identify(index_rows, track_first_row, q_rows, topk_ids, item_row, item_len, 
     max_len: the longest item, an upper bound is fine; the caller then vouches for the ranges (the item rows inside
     q_rows, the track table well formed) and the call stays asynchronous and capturable.  Without it the op checks them
     on the host."""
-    n_items, k, top = int(item_row.shape[0]), int(topk_ids.shape[1]), int(top)
-    # argument checks first (host values only): they hold on any device
-    if not 1 <= top <= 64:
-        raise ValueError(f"identify: top={top} not in [1, 64]")
-    if not 1 <= k <= IDENTIFY_MAX_K:
-        raise ValueError(f"identify: k={k} hits per segment exceeds {IDENTIFY_MAX_K}")
-    if min_overlap is not None and int(min_overlap) < 1:
-        raise ValueError("identify: min_overlap must be at least 1 segment")
-    if max_len is None and n_items:
-        max_len = max(1, int(item_len.max().item()))
-        check_track_table(track_first_row, index_rows.shape[0])
-        _check_items_inside("identify", item_row, item_len, q_rows.shape[0])
-    if max_len is not None and (int(max_len) > IDENTIFY_MAX_LEN or int(max_len) * k > IDENTIFY_MAX_KEYS):
-        raise ValueError(f"identify: items of {int(max_len)} segments with k={k} exceed {IDENTIFY_MAX_LEN} segments "
-                         f"or {IDENTIFY_MAX_KEYS} hits per item")
+    n_items, k, top, max_len, min_overlap = _identify_args("identify", index_rows.shape[0], track_first_row, q_rows,
+                                                           topk_ids, item_row, item_len, top, min_overlap, max_len)
     _require_gpu(index_rows, q_rows, topk_ids, item_row, item_len)
     index_rows, q_rows = _f32c(index_rows), _f32c(q_rows)
-    dev = index_rows.device
-    first = torch.as_tensor(track_first_row).detach().to(device=dev, dtype=torch.int64).contiguous()
-    topk_ids = topk_ids.to(torch.int64).contiguous()
-    item_row = item_row.to(torch.int64).contiguous()
-    item_len = item_len.to(torch.int32).contiguous()
-    outs = (torch.empty((n_items, top), dtype=torch.int32, device=dev),
-            torch.empty((n_items, top), dtype=torch.int32, device=dev),
-            torch.empty((n_items, top), dtype=torch.float32, device=dev),
-            torch.empty((n_items, top), dtype=torch.int32, device=dev))
+    first, topk_ids, item_row, item_len, outs = _identify_tensors(index_rows.device, track_first_row, topk_ids,
+                                                                  item_row, item_len, top)
     if n_items == 0:
         return outs
-    max_len = int(max_len)
     with _timed("identify", (n_items, max_len, k)):
         check(lib.grafp_identify_f32(_p(index_rows), index_rows.shape[0], _p(first), first.numel() - 1, _p(q_rows),
                                      q_rows.shape[0], _p(topk_ids), k, _p(item_row), _p(item_len), n_items, max_len,
-                                     top, 0 if min_overlap is None else int(min_overlap), *(_p(o) for o in outs),
-                                     _stream()), "identify")
+                                     top, min_overlap, *(_p(o) for o in outs), _stream()), "identify")
     return outs
 
 
@@ -1823,45 +1837,26 @@ def identify_thin(index_rows, track_first_row, q_rows, topk_ids, item_row, item_
     mean dot product over its pairs in ops.identify's arithmetic order.  offset = a - first[t] * D: dense segments from
     the track's start, as ops.identify reports it.  Everything else (arguments, ranking, padding, max_len) as for
     ops.identify, which this equals bit for bit at row_stride = 1."""
-    n_items, k, top, D = int(item_row.shape[0]), int(topk_ids.shape[1]), int(top), int(row_stride)
+    D = int(row_stride)
     # argument checks first (host values only): they hold on any device
     if not 1 <= D <= IDENTIFY_MAX_STRIDE:
         raise ValueError(f"identify_thin: row_stride={D} not in [1, {IDENTIFY_MAX_STRIDE}]")
     if int(index_rows.shape[0]) * D + IDENTIFY_MAX_LEN - 1 >= 1 << 32:
         raise ValueError(f"identify_thin: {int(index_rows.shape[0])} rows at row_stride={D} reach past the 2^32 fine "
                          "positions an alignment key holds")
-    if not 1 <= top <= 64:
-        raise ValueError(f"identify_thin: top={top} not in [1, 64]")
-    if not 1 <= k <= IDENTIFY_MAX_K:
-        raise ValueError(f"identify_thin: k={k} hits per segment exceeds {IDENTIFY_MAX_K}")
-    if min_overlap is not None and int(min_overlap) < 1:
-        raise ValueError("identify_thin: min_overlap must be at least 1 segment")
-    if max_len is None and n_items:
-        max_len = max(1, int(item_len.max().item()))
-        check_track_table(track_first_row, index_rows.shape[0])
-        _check_items_inside("identify_thin", item_row, item_len, q_rows.shape[0])
-    if max_len is not None and (int(max_len) > IDENTIFY_MAX_LEN or int(max_len) * k > IDENTIFY_MAX_KEYS):
-        raise ValueError(f"identify_thin: items of {int(max_len)} segments with k={k} exceed {IDENTIFY_MAX_LEN} "
-                         f"segments or {IDENTIFY_MAX_KEYS} hits per item")
+    n_items, k, top, max_len, min_overlap = _identify_args("identify_thin", index_rows.shape[0], track_first_row, q_rows,
+                                                           topk_ids, item_row, item_len, top, min_overlap, max_len)
     _require_gpu(index_rows, q_rows, topk_ids, item_row, item_len)
     index_rows, q_rows = _f32c(index_rows), _f32c(q_rows)
-    dev = index_rows.device
-    first = torch.as_tensor(track_first_row).detach().to(device=dev, dtype=torch.int64).contiguous()
-    topk_ids = topk_ids.to(torch.int64).contiguous()
-    item_row = item_row.to(torch.int64).contiguous()
-    item_len = item_len.to(torch.int32).contiguous()
-    outs = (torch.empty((n_items, top), dtype=torch.int32, device=dev),
-            torch.empty((n_items, top), dtype=torch.int32, device=dev),
-            torch.empty((n_items, top), dtype=torch.float32, device=dev),
-            torch.empty((n_items, top), dtype=torch.int32, device=dev))
+    first, topk_ids, item_row, item_len, outs = _identify_tensors(index_rows.device, track_first_row, topk_ids,
+                                                                  item_row, item_len, top)
     if n_items == 0:
         return outs
-    max_len = int(max_len)
     with _timed("identify_thin", (n_items, max_len, k, D)):
         check(lib.grafp_identify_thin_f32(_p(index_rows), index_rows.shape[0], _p(first), first.numel() - 1, D,
                                           _p(q_rows), q_rows.shape[0], _p(topk_ids), k, _p(item_row), _p(item_len),
-                                          n_items, max_len, top, 0 if min_overlap is None else int(min_overlap),
-                                          *(_p(o) for o in outs), _stream()), "identify_thin")
+                                          n_items, max_len, top, min_overlap, *(_p(o) for o in outs), _stream()),
+              "identify_thin")
     return outs
 
 
@@ -1883,51 +1878,52 @@ def identify_tempo(index_rows, track_first_row, q_rows, topk_ids, item_row, item
     Returns (track, offset, score, votes, ratio int32 = num), each (n_items, top), padded with -1 / INT_MIN / -inf / 0 /
     0; offset = a - first[t] is where the item's first row sits in the track.  Everything else (arguments, ranking,
     max_len) as for ops.identify, whose four outputs this equals bit for bit at ratio_num = [256]."""
-    n_items, k, top = int(item_row.shape[0]), int(topk_ids.shape[1]), int(top)
-    # argument checks first (host values only): they hold on any device
-    if not 1 <= top <= 64:
-        raise ValueError(f"identify_tempo: top={top} not in [1, 64]")
-    if not 1 <= k <= IDENTIFY_MAX_K:
-        raise ValueError(f"identify_tempo: k={k} hits per segment exceeds {IDENTIFY_MAX_K}")
-    if min_overlap is not None and int(min_overlap) < 1:
-        raise ValueError("identify_tempo: min_overlap must be at least 1 segment")
-    if max_len is None and n_items:
-        max_len = max(1, int(item_len.max().item()))
-        check_track_table(track_first_row, index_rows.shape[0])
-        _check_items_inside("identify_tempo", item_row, item_len, q_rows.shape[0])
-    if max_len is not None and (int(max_len) > IDENTIFY_MAX_LEN or int(max_len) * k > IDENTIFY_MAX_KEYS):
-        raise ValueError(f"identify_tempo: items of {int(max_len)} segments with k={k} exceed {IDENTIFY_MAX_LEN} "
-                         f"segments or {IDENTIFY_MAX_KEYS} hits per item")
+    n_items, k, top, max_len, min_overlap = _identify_args("identify_tempo", index_rows.shape[0], track_first_row,
+                                                           q_rows, topk_ids, item_row, item_len, top, min_overlap, max_len)
     ratios = _tempo_ratio_list("identify_tempo", ratio_num)
     if int(index_rows.shape[0]) + 2 * IDENTIFY_MAX_LEN - 1 >= 1 << 32:
         raise ValueError(f"identify_tempo: {int(index_rows.shape[0])} rows reach past the 2^32 alignments a key holds")
     _require_gpu(index_rows, q_rows, topk_ids, item_row, item_len)
     index_rows, q_rows = _f32c(index_rows), _f32c(q_rows)
     dev = index_rows.device
-    first = torch.as_tensor(track_first_row).detach().to(device=dev, dtype=torch.int64).contiguous()
-    topk_ids = topk_ids.to(torch.int64).contiguous()
-    item_row = item_row.to(torch.int64).contiguous()
-    item_len = item_len.to(torch.int32).contiguous()
-    outs = (torch.empty((n_items, top), dtype=torch.int32, device=dev),
-            torch.empty((n_items, top), dtype=torch.int32, device=dev),
-            torch.empty((n_items, top), dtype=torch.float32, device=dev),
-            torch.empty((n_items, top), dtype=torch.int32, device=dev),
-            torch.empty((n_items, top), dtype=torch.int32, device=dev))
+    first, topk_ids, item_row, item_len, outs = _identify_tensors(dev, track_first_row, topk_ids, item_row, item_len,
+                                                                  top, n_outs=5)
     if n_items == 0:
         return outs
-    max_len = int(max_len)
     nums = (ctypes.c_int32 * len(ratios))(*ratios)                       # read by the entry before it returns
     ws = torch.empty(lib.grafp_identify_tempo_workspace(n_items, len(ratios), top), dtype=torch.uint8, device=dev)
     with _timed("identify_tempo", (n_items, max_len, k, len(ratios))):
         check(lib.grafp_identify_tempo_f32(_p(index_rows), index_rows.shape[0], _p(first), first.numel() - 1,
                                            _p(q_rows), q_rows.shape[0], _p(topk_ids), k, _p(item_row), _p(item_len),
-                                           n_items, max_len, top, 0 if min_overlap is None else int(min_overlap),
-                                           ctypes.cast(nums, ctypes.c_void_p), len(ratios), _p(ws),
-                                           *(_p(o) for o in outs), _stream()), "identify_tempo")
+                                           n_items, max_len, top, min_overlap, ctypes.cast(nums, ctypes.c_void_p),
+                                           len(ratios), _p(ws), *(_p(o) for o in outs), _stream()), "identify_tempo")
     return outs
 
 
 IDENTIFY_PQ_M = (16, 32, 64, 128)                                      # identify_pq.hip's sub-quantiser counts
+
+
+def _pq_args(name, list_id, codes, centroids, codebooks):
+    """The shape and dtype checks of a library held as IVF-PQ codes (ops.identify_pq, ops.cross_match_pq)
+    -> (n rows, M sub-quantisers, nlist)."""
+    if codes.dim() != 2 or codes.dtype != torch.uint8:
+        raise ValueError(f"{name}: codes must be (n, M) uint8, not {tuple(codes.shape)} {codes.dtype}")
+    n, M = int(codes.shape[0]), int(codes.shape[1])
+    if M not in IDENTIFY_PQ_M:
+        raise ValueError(f"{name}: M={M} sub-quantisers, not one of {IDENTIFY_PQ_M}")
+    if list_id.dtype != torch.int32 or tuple(list_id.shape) != (n,):
+        raise ValueError(f"{name}: list_id must be ({n},) int32, not {tuple(list_id.shape)} {list_id.dtype}")
+    if centroids.dim() != 2 or centroids.shape[0] < 1 or centroids.shape[1] != 128:
+        raise ValueError(f"{name}: centroids must be (nlist, 128), not {tuple(centroids.shape)}")
+    if tuple(codebooks.shape) != (M, 256, 128 // M):
+        raise ValueError(f"{name}: codebooks must be {(M, 256, 128 // M)} for M={M}, not {tuple(codebooks.shape)}")
+    return n, M, int(centroids.shape[0])
+
+
+def _check_list_ids(name, list_id, nlist):
+    """Refuses list ids outside [0, nlist) (two host synchronisations)."""
+    if not 0 <= int(list_id.min().item()) <= int(list_id.max().item()) < nlist:
+        raise ValueError(f"{name}: a list id lies outside [0, {nlist})")
 
 
 def identify_pq(list_id, codes, centroids, codebooks, track_first_row, q_rows, topk_ids, item_row, item_len, top=5,
@@ -1938,60 +1934,39 @@ def identify_pq(list_id, codes, centroids, codebooks, track_first_row, q_rows, t
     list_id (n) int32 in [0, nlist), codes (n, M) uint8 in library row order, centroids (nlist, 128) f32, codebooks
     (M, 256, 128 // M) f32, M one of 16, 32, 64, 128; the other arguments, the results and the meaning of max_len as
     for ops.identify (without max_len the list ids are range-checked on the host too)."""
-    n_items, k, top = int(item_row.shape[0]), int(topk_ids.shape[1]), int(top)
     # argument checks first (host values only): they hold on any device
-    if codes.dim() != 2 or codes.dtype != torch.uint8:
-        raise ValueError(f"identify_pq: codes must be (n, M) uint8, not {tuple(codes.shape)} {codes.dtype}")
-    n, M = int(codes.shape[0]), int(codes.shape[1])
-    if M not in IDENTIFY_PQ_M:
-        raise ValueError(f"identify_pq: M={M} sub-quantisers, not one of {IDENTIFY_PQ_M}")
-    if list_id.dtype != torch.int32 or tuple(list_id.shape) != (n,):
-        raise ValueError(f"identify_pq: list_id must be ({n},) int32, not {tuple(list_id.shape)} {list_id.dtype}")
-    if centroids.dim() != 2 or centroids.shape[0] < 1 or centroids.shape[1] != 128:
-        raise ValueError(f"identify_pq: centroids must be (nlist, 128), not {tuple(centroids.shape)}")
-    if tuple(codebooks.shape) != (M, 256, 128 // M):
-        raise ValueError(f"identify_pq: codebooks must be {(M, 256, 128 // M)} for M={M}, not {tuple(codebooks.shape)}")
-    nlist = int(centroids.shape[0])
-    if not 1 <= top <= 64:
-        raise ValueError(f"identify_pq: top={top} not in [1, 64]")
-    if not 1 <= k <= IDENTIFY_MAX_K:
-        raise ValueError(f"identify_pq: k={k} hits per segment exceeds {IDENTIFY_MAX_K}")
-    if min_overlap is not None and int(min_overlap) < 1:
-        raise ValueError("identify_pq: min_overlap must be at least 1 segment")
-    if max_len is None and n_items:
-        max_len = max(1, int(item_len.max().item()))
-        check_track_table(track_first_row, n)
-        _check_items_inside("identify_pq", item_row, item_len, q_rows.shape[0])
-        if n and not 0 <= int(list_id.min().item()) <= int(list_id.max().item()) < nlist:
-            raise ValueError(f"identify_pq: a list id lies outside [0, {nlist})")
-    if max_len is not None and (int(max_len) > IDENTIFY_MAX_LEN or int(max_len) * k > IDENTIFY_MAX_KEYS):
-        raise ValueError(f"identify_pq: items of {int(max_len)} segments with k={k} exceed {IDENTIFY_MAX_LEN} segments "
-                         f"or {IDENTIFY_MAX_KEYS} hits per item")
+    n, M, nlist = _pq_args("identify_pq", list_id, codes, centroids, codebooks)
+    on_host = max_len is None                                            # the ranges are checked here, not vouched for
+    n_items, k, top, max_len, min_overlap = _identify_args("identify_pq", n, track_first_row, q_rows, topk_ids,
+                                                           item_row, item_len, top, min_overlap, max_len)
+    if on_host and n_items and n:
+        _check_list_ids("identify_pq", list_id, nlist)
     _require_gpu(list_id, codes, centroids, codebooks, q_rows, topk_ids, item_row, item_len)
     list_id, codes = list_id.detach().contiguous(), codes.detach().contiguous()
     centroids, codebooks, q_rows = _f32c(centroids), _f32c(codebooks), _f32c(q_rows)
-    dev = codes.device
-    first = torch.as_tensor(track_first_row).detach().to(device=dev, dtype=torch.int64).contiguous()
-    topk_ids = topk_ids.to(torch.int64).contiguous()
-    item_row = item_row.to(torch.int64).contiguous()
-    item_len = item_len.to(torch.int32).contiguous()
-    outs = (torch.empty((n_items, top), dtype=torch.int32, device=dev),
-            torch.empty((n_items, top), dtype=torch.int32, device=dev),
-            torch.empty((n_items, top), dtype=torch.float32, device=dev),
-            torch.empty((n_items, top), dtype=torch.int32, device=dev))
+    first, topk_ids, item_row, item_len, outs = _identify_tensors(codes.device, track_first_row, topk_ids, item_row,
+                                                                  item_len, top)
     if n_items == 0:
         return outs
-    max_len = int(max_len)
     with _timed("identify_pq", (n_items, max_len, k, M)):
         check(lib.grafp_identify_pq_f32(_p(list_id), _p(codes), n, _p(centroids), nlist, _p(codebooks), M, _p(first),
                                         first.numel() - 1, _p(q_rows), q_rows.shape[0], _p(topk_ids), k, _p(item_row),
-                                        _p(item_len), n_items, max_len, top,
-                                        0 if min_overlap is None else int(min_overlap), *(_p(o) for o in outs),
+                                        _p(item_len), n_items, max_len, top, min_overlap, *(_p(o) for o in outs),
                                         _stream()), "identify_pq")
     return outs
 
 
 SELF_MATCH_MAX_K, SELF_MATCH_MAX_TOP = 32, 64                            # selfmatch.hip's limits
+
+
+def _check_match_limits(name, top, k, min_votes, min_overlap):
+    """The limits ops.self_match and the cross-match ops share."""
+    if not 1 <= top <= SELF_MATCH_MAX_TOP:
+        raise ValueError(f"{name}: top={top} not in [1, {SELF_MATCH_MAX_TOP}]")
+    if not 1 <= k <= SELF_MATCH_MAX_K:
+        raise ValueError(f"{name}: k={k} hits per row exceeds {SELF_MATCH_MAX_K}")
+    if int(min_votes) < 1 or int(min_overlap) < 1:
+        raise ValueError(f"{name}: min_votes and min_overlap must be at least 1")
 
 
 def self_match_workspace_bytes(src_rows, k, min_votes):
@@ -2013,12 +1988,7 @@ def self_match(index_rows, track_first_row, topk_ids, tracks=None, top=8, min_vo
     Returns (track, delta, start, length, score, votes), each (n_src, top) -- int32 but score f32 --, best first,
     padded with -1 / INT_MIN / -1 / 0 / -inf / 0.  The table, the sources and the limits are checked on the host."""
     k, top = int(topk_ids.shape[1]), int(top)
-    if not 1 <= top <= SELF_MATCH_MAX_TOP:
-        raise ValueError(f"self_match: top={top} not in [1, {SELF_MATCH_MAX_TOP}]")
-    if not 1 <= k <= SELF_MATCH_MAX_K:
-        raise ValueError(f"self_match: k={k} hits per row exceeds {SELF_MATCH_MAX_K}")
-    if int(min_votes) < 1 or int(min_overlap) < 1:
-        raise ValueError("self_match: min_votes and min_overlap must be at least 1")
+    _check_match_limits("self_match", top, k, min_votes, min_overlap)
     n = int(index_rows.shape[0])
     if n < 1 or int(topk_ids.shape[0]) != n:
         raise ValueError(f"self_match: topk_ids has {int(topk_ids.shape[0])} rows for a library of {n}")
@@ -2054,12 +2024,7 @@ def _cross_match_args(name, n, track_first_row, q_rows, src_first_row, topk_ids,
     """The host checks ops.cross_match and ops.cross_match_pq share -> (track table, source table, rows per source),
     host int64 tensors."""
     k = int(topk_ids.shape[1])
-    if not 1 <= top <= SELF_MATCH_MAX_TOP:
-        raise ValueError(f"{name}: top={top} not in [1, {SELF_MATCH_MAX_TOP}]")
-    if not 1 <= k <= SELF_MATCH_MAX_K:
-        raise ValueError(f"{name}: k={k} hits per row exceeds {SELF_MATCH_MAX_K}")
-    if int(min_votes) < 1 or int(min_overlap) < 1:
-        raise ValueError(f"{name}: min_votes and min_overlap must be at least 1")
+    _check_match_limits(name, top, k, min_votes, min_overlap)
     if n < 1:
         raise ValueError(f"{name}: a library of {n} rows")
     if q_rows.dim() != 2 or q_rows.shape[1] != 128:
@@ -2195,23 +2160,10 @@ def cross_match_pq(list_id, codes, centroids, codebooks, track_first_row, q_rows
     what ops.cross_match returns on those decoded rows.  list_id, codes, centroids, codebooks as for ops.identify_pq
     (the list ids are range-checked on the host); the other arguments and the results as for ops.cross_match."""
     top, k = int(top), int(topk_ids.shape[1])
-    if codes.dim() != 2 or codes.dtype != torch.uint8:
-        raise ValueError(f"cross_match_pq: codes must be (n, M) uint8, not {tuple(codes.shape)} {codes.dtype}")
-    n, M = int(codes.shape[0]), int(codes.shape[1])
-    if M not in IDENTIFY_PQ_M:
-        raise ValueError(f"cross_match_pq: M={M} sub-quantisers, not one of {IDENTIFY_PQ_M}")
-    if list_id.dtype != torch.int32 or tuple(list_id.shape) != (n,):
-        raise ValueError(f"cross_match_pq: list_id must be ({n},) int32, not {tuple(list_id.shape)} {list_id.dtype}")
-    if centroids.dim() != 2 or centroids.shape[0] < 1 or centroids.shape[1] != 128:
-        raise ValueError(f"cross_match_pq: centroids must be (nlist, 128), not {tuple(centroids.shape)}")
-    if tuple(codebooks.shape) != (M, 256, 128 // M):
-        raise ValueError(f"cross_match_pq: codebooks must be {(M, 256, 128 // M)} for M={M}, not "
-                         f"{tuple(codebooks.shape)}")
-    nlist = int(centroids.shape[0])
+    n, M, nlist = _pq_args("cross_match_pq", list_id, codes, centroids, codebooks)
     first_h, src_h, lens = _cross_match_args("cross_match_pq", n, track_first_row, q_rows, src_first_row, topk_ids,
                                              top, min_votes, min_overlap)
-    if not 0 <= int(list_id.min().item()) <= int(list_id.max().item()) < nlist:
-        raise ValueError(f"cross_match_pq: a list id lies outside [0, {nlist})")
+    _check_list_ids("cross_match_pq", list_id, nlist)
     _require_gpu(list_id, codes, centroids, codebooks, q_rows, topk_ids)
     list_id, codes = list_id.detach().contiguous(), codes.detach().contiguous()
     centroids, codebooks, q_rows = _f32c(centroids), _f32c(codebooks), _f32c(q_rows)

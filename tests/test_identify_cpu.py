@@ -208,6 +208,52 @@ def test_identify_op_refusals_without_a_gpu():
         ops.identify(rows, first, q, ids, one, torch.tensor([2], dtype=torch.int32))
 
 
+# what each of the four identify ops takes besides the shared arguments (n library rows)
+_IDENTIFY_OPS = {
+    "identify": lambda n: dict(index_rows=torch.zeros(n, 128)),
+    "identify_thin": lambda n: dict(index_rows=torch.zeros(n, 128), row_stride=2),
+    "identify_tempo": lambda n: dict(index_rows=torch.zeros(n, 128), ratio_num=[240, 256]),
+    "identify_pq": lambda n: dict(list_id=torch.zeros(n, dtype=torch.int32), codes=torch.zeros((n, 64), dtype=torch.uint8),
+                                  centroids=torch.zeros(3, 128), codebooks=torch.zeros(64, 256, 2)),
+}
+# (case, changed arguments, k, the fragment every op's message holds, whether the message is the op's own and so starts
+# with its name -- the track table's comes from check_track_table and the device refusal from _require_gpu)
+_SHARED_REFUSALS = [
+    ("top_0", dict(top=0), 4, "top=0 not in [1, 64]", True),
+    ("top_65", dict(top=65), 4, "top=65 not in [1, 64]", True),
+    ("k_33", dict(), 33, "k=33 hits per segment exceeds 32", True),
+    ("min_overlap_0", dict(min_overlap=0), 4, "min_overlap must be at least 1 segment", True),
+    ("item_of_257", dict(item_len=torch.tensor([257], dtype=torch.int32)), 4,
+     "items of 257 segments with k=4 exceed 256 segments or 8192 hits per item", True),
+    ("max_len_257", dict(max_len=257), 4, "items of 257 segments with k=4 exceed 256 segments or 8192 hits per item", True),
+    ("256_x_32_accepted", dict(item_len=torch.tensor([256], dtype=torch.int32)), 32, "no CPU", False),
+    ("256_x_32_accepted_max_len", dict(max_len=256), 32, "no CPU", False),
+    ("129_x_64_refused_on_k", dict(item_len=torch.tensor([129], dtype=torch.int32)), 64,
+     "k=64 hits per segment exceeds 32", True),
+    ("decreasing_table", dict(track_first_row=torch.tensor([0, 5, 3, 8])), 4, "never decrease", False),
+    ("item_outside_q_rows", dict(item_row=torch.tensor([299])), 4, "an item reaches outside q_rows", True),
+    ("valid", dict(), 4, "no CPU", False),
+]
+
+
+@pytest.mark.parametrize("case,changed,k,fragment,named", _SHARED_REFUSALS, ids=[c[0] for c in _SHARED_REFUSALS])
+@pytest.mark.parametrize("op", sorted(_IDENTIFY_OPS))
+def test_identify_ops_share_their_refusals(op, case, changed, k, fragment, named):
+    """The checks the four identify ops share refuse the same arguments with the same words, each under its own name."""
+    args = dict(_IDENTIFY_OPS[op](8), track_first_row=torch.tensor([0, 8]), q_rows=torch.zeros(300, 128),
+                topk_ids=torch.zeros(300, k, dtype=torch.int64), item_row=torch.zeros(1, dtype=torch.int64),
+                item_len=torch.tensor([2], dtype=torch.int32))
+    args.update(changed)
+    with pytest.raises(RuntimeError if fragment == "no CPU" else ValueError) as e:
+        getattr(ops, op)(**args)
+    message = str(e.value)
+    assert fragment in message
+    if named:
+        assert message.startswith(op + ": ")
+    elif case == "decreasing_table":
+        assert message.startswith("identify: the track table")
+
+
 # ---- the C ABI entry and the shipped object ---------------------------------------------------------------------
 def test_abi_entry_follows_the_conventions():
     from test_abi import _ctype_of, _declared
