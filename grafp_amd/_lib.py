@@ -134,6 +134,8 @@ SIGNATURES = {
     "grafp_cross_match_tempo_f32": (_I, [_P, _L, _P, _I, _P, _L, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _Z, _P, _P, _P,
                                          _P, _P, _P, _P, _P]),
     "grafp_cross_match_tempo_workspace": (_Z, [_P, _I, _I, _I, _I, _I]),
+    "grafp_self_match_tempo_f32": (_I, [_P, _L, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _Z, _P, _P, _P, _P, _P,
+                                        _P, _P, _P]),
 }
 
 

@@ -330,6 +330,33 @@ extern "C" int grafp_cross_match_tempo_f32(const float *index_rows, int64_t n, c
                                            out_ratio, (hipStream_t)stream);
 }
 
+// Tracks that share audio at another speed inside a library (selfmatch_tempo.hip): the checks of grafp_self_match_f32
+// here; the ratio checks, the workspace floor and the three launches there.
+namespace grafp {
+int self_match_tempo_launch(const float *rows, int64_t n, const int64_t *first, int T, const int64_t *ids, int k,
+                            const int *tracks, int n_src, int top, int min_votes, int min_overlap,
+                            const int32_t *ratio_num, int n_ratios, void *ws, size_t ws_bytes, int32_t *out_track,
+                            int32_t *out_delta, int32_t *out_start, int32_t *out_len, float *out_score,
+                            int32_t *out_votes, int32_t *out_ratio, hipStream_t stream);
+}  // namespace grafp
+
+extern "C" int grafp_self_match_tempo_f32(const float *index_rows, int64_t n, const int64_t *track_first_row,
+                                          int n_tracks, const int64_t *topk_ids, int k, const int *src_tracks, int n_src,
+                                          int top, int min_votes, int min_overlap, const int32_t *ratio_num,
+                                          int n_ratios, void *ws, size_t ws_bytes, int32_t *out_track,
+                                          int32_t *out_delta, int32_t *out_start, int32_t *out_len, float *out_score,
+                                          int32_t *out_votes, int32_t *out_ratio, grafp_stream_t stream) {
+    GRAFP_REQUIRE(index_rows && track_first_row && topk_ids && src_tracks && ratio_num && out_track && out_delta &&
+                  out_start && out_len && out_score && out_votes && out_ratio, "self_match_tempo: null pointer");
+    GRAFP_REQUIRE(n >= 1 && n < 0x7fffff00ll && n_tracks >= 1 && n_src >= 0,
+                  "self_match_tempo: bad sizes n=%lld n_tracks=%d n_src=%d", (long long)n, n_tracks, n_src);
+    GRAFP_REQUIRE(((uintptr_t)index_rows & 15) == 0, "self_match_tempo: rows must be 16-byte aligned");
+    return grafp::self_match_tempo_launch(index_rows, n, track_first_row, n_tracks, topk_ids, k, src_tracks, n_src, top,
+                                          min_votes, min_overlap, ratio_num, n_ratios, ws, ws_bytes, out_track,
+                                          out_delta, out_start, out_len, out_score, out_votes, out_ratio,
+                                          (hipStream_t)stream);
+}
+
 // The front end of live multi-channel monitoring (stream_frontend.hip): argument checks here, the kernels there.  The
 // per-channel tables are device data: the caller (ops.stream_logmel) checks them on the host before it uploads them.
 namespace grafp {

@@ -1,7 +1,8 @@
 // selfmatch_core.h -- the one body of the shared-audio kernels: selfmatch.hip (the sources are tracks of the library,
 // ops.self_match) and crossmatch.hip (the sources are recordings held outside the library, ops.cross_match and
-// ops.cross_match_pq) and crossmatch_tempo.hip (such recordings played faster or slower than the catalogue,
-// ops.cross_match_tempo).  What a source's votes, spans, scores and partners are, the five phases and the workspace layout
+// ops.cross_match_pq), crossmatch_tempo.hip (such recordings played faster or slower than the catalogue,
+// ops.cross_match_tempo) and selfmatch_tempo.hip (tracks of the library that share audio at another speed,
+// ops.self_match_tempo; match_tempo.h holds what the two tempo files share).  What a source's votes, spans, scores and partners are, the five phases and the workspace layout
 // are stated at the top of selfmatch.hip; the arithmetic order of a score at the top of seqmatch.h.  The kernels differ
 // in THREE things, the parameters of match_source:
 //   * Source -- where source s comes from:
@@ -19,7 +20,7 @@
 //         int64_t shift(int64_t L)      the key shift of a source of L rows: r - at(i) + shift(L) >= 0 for every hit
 //         float score(span, x, a, lo, l, m)   the span call of phase 3: m pairs from source row lo on, alignment a
 //     MatchDenseGrid (at = i, shift = L, span(x, a + lo, l, m)) for the three files above and MatchTempoGrid (at = w(i) =
-//     (i * num + 128) >> 8, shift = 2 L, span(x, a, lo, num, l, m): TempoRowSpan) for crossmatch_tempo.hip.  Inside one
+//     (i * num + 128) >> 8, shift = 2 L, span(x, a, lo, num, l, m): TempoRowSpan) for the two tempo files.  Inside one
 //     alignment run r = a + at(i) never decreases with i on either grid, which is all phase 2's walk needs.
 // The workspace depends on a source's row count, k and min_votes only (sm_units), so plan_sources, the host's
 // self_match_workspace and the -2 mark of a source that does not fit serve every kernel.

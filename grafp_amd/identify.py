@@ -6,6 +6,7 @@
   python -m grafp_amd.identify query --ckp MODEL.pth --library LIBDIR FILES... [--top 5] [--window S --hop S]
                                        [--tempo X [--tempo-step G]]
   python -m grafp_amd.identify dedup --ckp MODEL.pth --library LIBDIR [--min-overlap 3] [--coverage 0.9] [--json OUT]
+                                       [--tempo X [--tempo-step G]]
   python -m grafp_amd.identify match --ckp MODEL.pth --library LIBDIR FILES... [--min-overlap 3] [--min-votes 4]
                                        [--min-score S] [--top 8] [--k-probe 20] [--json OUT]
                                        [--tempo X [--tempo-step G]]
@@ -23,7 +24,9 @@ unchanged, `dedup` and `match` need every row).  query --tempo X also searches r
 per cent) faster or slower than the catalogue (a flat library that keeps every row; every match and timeline span then
 carries "tempo" next to its score; --tempo-step G spaces the ratios searched G / 256 apart).  match --tempo X does the
 same for whole recordings -- a pitched DJ set, a sped-up re-upload -- on a flat library that keeps every row: every
-printed match then also carries "tempo", "tempo_num" and "track_overlap_s" (--tempo-step defaults to 1).  `monitor` treats every file as one live channel: it feeds them to a
+printed match then also carries "tempo", "tempo_num" and "track_overlap_s" (--tempo-step defaults to 1).  dedup --tempo X
+also finds the tracks of the library that share audio at another speed -- a sped-up re-release, a varispeed remaster --:
+every printed pair then also carries "tempo", "tempo_num" and "b_overlap_s" (--tempo-step defaults to 1).  `monitor` treats every file as one live channel: it feeds them to a
 StreamMonitor (grafp_amd/monitor.py) chunk by chunk, all channels per push, prints one JSON object per window as it
 becomes due ({"channel", "file", start_s, end_s, segment_start_s, matches}) and, when the files end, one per timeline
 span of each channel ({"channel", "file", "span": ...})."""
@@ -86,6 +89,9 @@ def main(argv=None):
     d.add_argument("--min-score", type=float, default=None, help="duplicate score bar (default: the library's)")
     d.add_argument("--k-probe", type=int, default=32)
     d.add_argument("--json", default=None, help="also write {pairs, groups} to this file")
+    d.add_argument("--tempo", type=float, default=None,
+                   help="also find tracks that share audio up to this fraction faster or slower (0.06: 0.94 to 1.06)")
+    d.add_argument("--tempo-step", type=int, default=None, help="spacing of the ratios searched, in 1/256 (default 1)")
     d.add_argument("--force", action="store_true", help="use a library made with another model")
     m = sub.add_parser("match", help="find what whole recordings share with a library")
     m.add_argument("--config", default=DEFAULT_CONFIG, help="model configuration (the library keeps its own "
@@ -143,7 +149,8 @@ def main(argv=None):
         if lib.is_compact:
             sys.exit(f"{args.library}: dedup needs the flat form of a library (f32 rows): this one is compact and holds "
                      "IVF-PQ codes only")
-        pairs = lib.self_matches(k_probe=args.k_probe, min_overlap_s=args.min_overlap)
+        pairs = lib.self_matches(k_probe=args.k_probe, min_overlap_s=args.min_overlap, tempo=args.tempo,
+                                 tempo_step=args.tempo_step)
         bar = DUPLICATE_MIN_SCORE if args.min_score is None else args.min_score
         groups = [{"tracks": g, "names": [lib.names[t] for t in g]}
                   for g in lib.duplicate_groups(pairs, min_coverage=args.coverage, min_score=bar)]

@@ -25,8 +25,8 @@ identify(tempo=...) and identify_windows(tempo=...) also find recordings that pl
 than the catalogue: the same embed and search, then one ops.identify_tempo launch (csrc/identify_tempo.hip) that scores
 every candidate along the sloped alignment of each speed ratio of tempo_ratios(); timeline() follows such windows along
 their slope.  match(tempo=...) does the same for whole recordings (one ops.cross_match_tempo launch per batch,
-csrc/crossmatch_tempo.hip).  A flat library that keeps every row only; speed, not pitch; self_matches() and StreamMonitor
-know no tempo.
+csrc/crossmatch_tempo.hip) and self_matches(tempo=...) for the tracks of the library itself (ops.self_match_tempo,
+csrc/selfmatch_tempo.hip).  A flat library that keeps every row only; speed, not pitch; StreamMonitor knows no tempo.
 
 match() takes whole recordings of any length that are NOT in the library and says which tracks they share audio with,
 where and how much (spans, coverage, votes: what self_matches says about the library's own tracks) -- the question an
@@ -703,8 +703,8 @@ class FingerprintLibrary:
         are embedded and searched as without it and one ops.identify_tempo launch scores every candidate along the
         sloped alignment of every ratio; each match then also carries "tempo" (the ratio) and "tempo_num" (ratio *
         256), and offset / offset_s keep their meaning.  Needs a flat library that keeps every row.  Speed only: pitch
-        is not searched; match() takes the same tempo for whole recordings; self_matches(), StreamMonitor, the IVF-PQ
-        and the thinned forms know no tempo."""
+        is not searched; match() takes the same tempo for whole recordings and self_matches() for the tracks of the
+        library itself; StreamMonitor, the IVF-PQ and the thinned forms know no tempo."""
         self._need_tempo_form("identify", tempo)
         single = isinstance(queries, (str, np.ndarray, torch.Tensor)) and (
             isinstance(queries, str) or torch.as_tensor(queries).dim() == 1)
@@ -778,7 +778,7 @@ class FingerprintLibrary:
 
     # ---- the catalog itself ------------------------------------------------------------------------------------
     def self_matches(self, k_probe=32, min_overlap_s=3.0, min_votes=4, min_score=None, top=8, tracks=None,
-                     batch_rows=1 << 18):
+                     batch_rows=1 << 18, tempo=None, tempo_step=None):
         """Tracks that share audio: re-releases, compilations, edits, quotes.  The library's own rows (or only those of
         `tracks`) are searched against self.index in batches of about batch_rows rows, and each batch of source tracks
         goes through one ops.self_match launch.  -> list of {track_a, name_a, track_b, name_b, offset, a_start_s,
@@ -792,9 +792,22 @@ class FingerprintLibrary:
         min_votes: the least rows whose hits agree on the alignment; min_score: drop weaker matches (None: keep all).
         Memory: the kernel reads hits by library row, so the hits of the searched rows live in one (n_rows, k_probe)
         int64 tensor whatever `tracks` is (256 MB at 1 M rows and k_probe = 32); each batch also takes its own exactly
-        sized workspace (ops.self_match_workspace_bytes: about 124 KB per 303-row source at k_probe = 32, min_votes 4)."""
+        sized workspace (ops.self_match_workspace_bytes: about 124 KB per 303-row source at k_probe = 32, min_votes 4).
+        tempo: None, or the speeds to search for tracks that share audio at another speed (a sped-up re-release, a
+        varispeed remaster), as match() takes them: a float x for the ratios [1 - x, 1 + x] of track_b rows per track_a
+        row, or a pair (lo, hi); tempo_step: the ratio grid's spacing in 1/256, by default 1 for match()'s reason
+        (tracks are long: at a coarser grid the nearest ratio drifts off a long span).  The launches then go to
+        ops.self_match_tempo (csrc/selfmatch_tempo.hip), R ratios at once, in batches of about batch_rows // R rows (the
+        workspace is R times a dense launch's), and row i of track_a sits on row offset + w(i) of track_b, w(i) = (i *
+        tempo_num + 128) >> 8.  Each entry then also carries tempo (= tempo_num / 256), tempo_num and b_overlap_s =
+        (w(i_hi) - w(i_lo) + 1) segment hops, track_b's side of the span; b_start_s = (offset + w(i_lo)) hops and
+        coverage = max(m / rows of a, (w(i_hi) - w(i_lo) + 1) / rows of b), match()'s rule (at 256: m / the shorter
+        track, as without tempo).  A copy at ratio rho is reported from both sides, near rho from the original's rows
+        and near 1 / rho from the copy's.  Needs a flat library that keeps every row."""
+        self._need_tempo_form("self_matches", tempo)
         self._need_flat("self_matches()")
         self._need_dense("self_matches()")
+        nums = None if tempo is None else tempo_ratios(tempo, ops.IDENTIFY_TEMPO_DEN, tempo_step)   # step 1 by default
         T, n = self.n_tracks, self.n_rows
         src = list(range(T)) if tracks is None else sorted({int(t) for t in tracks})
         if src and not 0 <= min(src) <= max(src) < T:
@@ -808,6 +821,8 @@ class FingerprintLibrary:
         first_d = torch.from_numpy(self.first).to(dev)
         ids = torch.full((n, k), -1, dtype=torch.int64, device=dev)
         lens = np.diff(self.first)
+        if nums is not None:
+            batch_rows = batch_rows // len(nums)                     # the workspace is R times a dense launch's
         batches, cur, cur_rows = [], [], 0
         for t in src:
             cur.append(t)
@@ -824,9 +839,12 @@ class FingerprintLibrary:
                 g_d = torch.from_numpy(g).to(dev)
                 _, hit = self.index.search(rows[g_d], k)
                 ids[g_d] = hit
-            res = ops.self_match(rows, first_d, ids, tracks=torch.tensor(batch, dtype=torch.int64), top=int(top),
-                                 min_votes=int(min_votes), min_overlap=min_overlap)
-            b_, d_, lo_, m_, sc_, v_ = (x.cpu().numpy() for x in res)
+            kw = dict(tracks=torch.tensor(batch, dtype=torch.int64), top=int(top), min_votes=int(min_votes),
+                      min_overlap=min_overlap)
+            res = ops.self_match(rows, first_d, ids, **kw) if nums is None else \
+                ops.self_match_tempo(rows, first_d, ids, nums, **kw)
+            b_, d_, lo_, m_, sc_, v_ = (x.cpu().numpy() for x in res[:6])
+            ra_ = None if nums is None else res[6].cpu().numpy()
             for s, a in enumerate(batch):
                 for j in range(b_.shape[1]):
                     b = int(b_[s, j])
@@ -838,10 +856,18 @@ class FingerprintLibrary:
                     if min_score is not None and sc < min_score:
                         continue
                     d, lo, m = int(d_[s, j]), int(lo_[s, j]), int(m_[s, j])
+                    la, lb = max(1, int(lens[a])), max(1, int(lens[b]))
                     out.append({"track_a": a, "name_a": self.names[a], "track_b": b, "name_b": self.names[b],
                                 "offset": d, "a_start_s": lo * seg_s, "b_start_s": (lo + d) * seg_s,
-                                "overlap_s": m * seg_s, "coverage": m / max(1, min(int(lens[a]), int(lens[b]))),
+                                "overlap_s": m * seg_s, "coverage": m / min(la, lb),
                                 "score": sc, "votes": int(v_[s, j])})
+                    if ra_ is not None:
+                        num, half = int(ra_[s, j]), ops.IDENTIFY_TEMPO_DEN // 2
+                        w_lo, w_hi = (lo * num + half) >> 8, ((lo + m - 1) * num + half) >> 8
+                        mb = w_hi - w_lo + 1                         # track_b's side of the span, in rows
+                        out[-1].update({"b_start_s": (d + w_lo) * seg_s, "coverage": max(m / la, mb / lb),
+                                        "tempo": num / ops.IDENTIFY_TEMPO_DEN, "tempo_num": num,
+                                        "b_overlap_s": mb * seg_s})
         return out
 
     # ---- recordings against the catalog -------------------------------------------------------------------------

@@ -1977,6 +1977,27 @@ def self_match_workspace_bytes(src_rows, k, min_votes):
                                               int(min_votes)))
 
 
+def _self_match_args(name, index_rows, track_first_row, topk_ids, tracks, top, min_votes, min_overlap):
+    """The host checks ops.self_match and ops.self_match_tempo share -> (n, track table, source tracks, rows per
+    source), the last three host int64 tensors."""
+    k = int(topk_ids.shape[1])
+    _check_match_limits(name, top, k, min_votes, min_overlap)
+    n = int(index_rows.shape[0])
+    if n < 1 or int(topk_ids.shape[0]) != n:
+        raise ValueError(f"{name}: topk_ids has {int(topk_ids.shape[0])} rows for a library of {n}")
+    first_h = check_track_table(track_first_row, n)
+    T = first_h.numel() - 1
+    src = torch.arange(T, dtype=torch.int64) if tracks is None else \
+        torch.as_tensor(tracks).detach().to("cpu", torch.int64).reshape(-1)
+    if src.numel() and (int(src.min()) < 0 or int(src.max()) >= T):
+        raise ValueError(f"{name}: source tracks must lie in [0, {T})")
+    lens = (first_h[1:] - first_h[:-1])[src]
+    if lens.numel() and int(lens.max()) * k > 2 ** 31 - 1:
+        raise ValueError(f"{name}: a track of {int(lens.max())} rows has more than 2^31 - 1 hits at k={k} "
+                         "(votes are int32)")
+    return n, first_h, src, lens
+
+
 def self_match(index_rows, track_first_row, topk_ids, tracks=None, top=8, min_votes=4, min_overlap=1):
     """Shared audio inside a track-indexed library (grafp_self_match_f32, one workgroup per source track): for every
     source track a, the `top` other tracks b its rows reappear in, each at its best alignment.
@@ -1988,20 +2009,9 @@ def self_match(index_rows, track_first_row, topk_ids, tracks=None, top=8, min_vo
     Returns (track, delta, start, length, score, votes), each (n_src, top) -- int32 but score f32 --, best first,
     padded with -1 / INT_MIN / -1 / 0 / -inf / 0.  The table, the sources and the limits are checked on the host."""
     k, top = int(topk_ids.shape[1]), int(top)
-    _check_match_limits("self_match", top, k, min_votes, min_overlap)
-    n = int(index_rows.shape[0])
-    if n < 1 or int(topk_ids.shape[0]) != n:
-        raise ValueError(f"self_match: topk_ids has {int(topk_ids.shape[0])} rows for a library of {n}")
-    first_h = check_track_table(track_first_row, n)
+    n, first_h, src, lens = _self_match_args("self_match", index_rows, track_first_row, topk_ids, tracks, top, min_votes,
+                                             min_overlap)
     T = first_h.numel() - 1
-    src = torch.arange(T, dtype=torch.int64) if tracks is None else \
-        torch.as_tensor(tracks).detach().to("cpu", torch.int64).reshape(-1)
-    if src.numel() and (int(src.min()) < 0 or int(src.max()) >= T):
-        raise ValueError(f"self_match: source tracks must lie in [0, {T})")
-    lens = (first_h[1:] - first_h[:-1])[src]
-    if lens.numel() and int(lens.max()) * k > 2 ** 31 - 1:
-        raise ValueError(f"self_match: a track of {int(lens.max())} rows has more than 2^31 - 1 hits at k={k} "
-                         "(votes are int32)")
     _require_gpu(index_rows, topk_ids)
     index_rows = _f32c(index_rows)
     dev = index_rows.device
@@ -2086,7 +2096,7 @@ CROSS_MATCH_TEMPO_MAX_ROWS = 4194303                                     # rows 
 
 
 def _tempo_ratio_list(name, ratio_num):
-    """The ratio checks ops.identify_tempo and ops.cross_match_tempo share -> the ratios as a list of ints."""
+    """The ratio checks ops.identify_tempo and the two tempo match ops share -> the ratios as a list of ints."""
     ratios = [int(v) for v in torch.as_tensor(ratio_num).reshape(-1).tolist()]
     if not 1 <= len(ratios) <= IDENTIFY_TEMPO_MAX_RATIOS:
         raise ValueError(f"{name}: {len(ratios)} ratios, not 1 to {IDENTIFY_TEMPO_MAX_RATIOS}")
@@ -2095,6 +2105,21 @@ def _tempo_ratio_list(name, ratio_num):
     if not all(IDENTIFY_TEMPO_MIN <= v <= IDENTIFY_TEMPO_MAX for v in ratios):
         raise ValueError(f"{name}: every ratio must lie in [{IDENTIFY_TEMPO_MIN}, {IDENTIFY_TEMPO_MAX}] "
                          f"(got {min(ratios)} .. {max(ratios)})")
+    return ratios
+
+
+def _tempo_match_limits(name, ratio_num, top, n, lens):
+    """The limits ops.cross_match_tempo and ops.self_match_tempo add to their dense forms' (lens: the rows of each
+    source, a host tensor) -> the ratios as a list of ints."""
+    ratios = _tempo_ratio_list(name, ratio_num)
+    if len(ratios) * top > 4096:
+        raise ValueError(f"{name}: {len(ratios)} ratios x top={top} exceed the 4096 slots of the merge")
+    longest = int(lens.max()) if lens.numel() else 0
+    if longest > CROSS_MATCH_TEMPO_MAX_ROWS:
+        raise ValueError(f"{name}: a source of {longest} rows exceeds {CROSS_MATCH_TEMPO_MAX_ROWS}")
+    if n + 2 * longest >= 1 << 32:
+        raise ValueError(f"{name}: n={n} library rows and a source of {longest} reach past the 2^32 "
+                         "alignments a key holds")
     return ratios
 
 
@@ -2124,15 +2149,7 @@ def cross_match_tempo(index_rows, track_first_row, q_rows, src_first_row, topk_i
     n = int(index_rows.shape[0])
     first_h, src_h, lens = _cross_match_args("cross_match_tempo", n, track_first_row, q_rows, src_first_row, topk_ids,
                                              top, min_votes, min_overlap)
-    ratios = _tempo_ratio_list("cross_match_tempo", ratio_num)
-    if len(ratios) * top > 4096:
-        raise ValueError(f"cross_match_tempo: {len(ratios)} ratios x top={top} exceed the 4096 slots of the merge")
-    longest = int(lens.max()) if lens.numel() else 0
-    if longest > CROSS_MATCH_TEMPO_MAX_ROWS:
-        raise ValueError(f"cross_match_tempo: a source of {longest} rows exceeds {CROSS_MATCH_TEMPO_MAX_ROWS}")
-    if n + 2 * longest >= 1 << 32:
-        raise ValueError(f"cross_match_tempo: n={n} library rows and a source of {longest} reach past the 2^32 "
-                         "alignments a key holds")
+    ratios = _tempo_match_limits("cross_match_tempo", ratio_num, top, n, lens)
     _require_gpu(index_rows, q_rows, topk_ids)
     index_rows, q_rows = _f32c(index_rows), _f32c(q_rows)
     dev = index_rows.device
@@ -2150,6 +2167,45 @@ def cross_match_tempo(index_rows, track_first_row, q_rows, src_first_row, topk_i
                                               q_rows.shape[0], _p(src), n_src, _p(topk_ids), k, top, int(min_votes),
                                               int(min_overlap), ctypes.cast(nums, ctypes.c_void_p), len(ratios), _p(ws),
                                               ws.numel(), *(_p(o) for o in outs), _stream()), "cross_match_tempo")
+    return outs
+
+
+def self_match_tempo(index_rows, track_first_row, topk_ids, ratio_num, tracks=None, top=8, min_votes=4, min_overlap=1):
+    """ops.self_match for tracks that share audio at another speed (grafp_self_match_tempo_f32: one workgroup per source
+    track and ratio, then one per source that merges the ratios' lists).  index_rows, track_first_row, topk_ids and
+    tracks as for ops.self_match; ratio_num as for ops.cross_match_tempo: 1 to 64 strictly ascending integers in
+    [128, 512] (host values), each num / 256 rows of the partner per row of the source.  At ratio num row i of source
+    track a sits w(i) = (i * num + 128) >> 8 rows after the source's row 0.  A hit r of row first[a] + i outside track a
+    names the track b holding r and the alignment a_g = r - w(i); a candidate is a unique (b, a_g, num); votes, span
+    [i_lo, i_hi], m and eligibility as for ops.self_match, and the score is the mean of <row[first[a] + i],
+    row[a_g + w(i)]> over i = i_lo .. i_hi in ops.identify's arithmetic order.  Per partner the best candidate over all
+    ratios: highest score, then the ratio nearer to 1 (smaller |num - 256|, then smaller num), then the smaller a_g.
+    Returns (track, delta = a_g - first[b], start = i_lo, length = m, score, votes, ratio int32 = num), each
+    (n_src, top), padded with -1 / INT_MIN / -1 / 0 / -inf / 0 / 0.  At ratio_num = [256] the first six are
+    ops.self_match's bit for bit; for any ratios all seven are ops.cross_match_tempo's on the source tracks' own rows and
+    hits with the own-track hits set to -1.  Limits: ops.self_match's and ops.cross_match_tempo's."""
+    k, top = int(topk_ids.shape[1]), int(top)
+    n, first_h, src, lens = _self_match_args("self_match_tempo", index_rows, track_first_row, topk_ids, tracks, top,
+                                             min_votes, min_overlap)
+    ratios = _tempo_match_limits("self_match_tempo", ratio_num, top, n, lens)
+    _require_gpu(index_rows, topk_ids)
+    index_rows = _f32c(index_rows)
+    dev = index_rows.device
+    n_src = src.numel()
+    outs = _cross_match_outs(n_src, top, dev) + (torch.zeros((n_src, top), dtype=torch.int32, device=dev),)
+    if n_src == 0:
+        return outs
+    first = first_h.to(dev)
+    topk_ids = topk_ids.to(torch.int64).contiguous()
+    src_d = src.to(device=dev, dtype=torch.int32)
+    nums = (ctypes.c_int32 * len(ratios))(*ratios)                       # read by the entry before it returns
+    ws = torch.empty(cross_match_tempo_workspace_bytes(lens.numpy(), k, min_votes, len(ratios), top), dtype=torch.uint8,
+                     device=dev)
+    with _timed("self_match_tempo", (n_src, int(lens.sum()), k, len(ratios))):
+        check(lib.grafp_self_match_tempo_f32(_p(index_rows), n, _p(first), first.numel() - 1, _p(topk_ids), k, _p(src_d),
+                                             n_src, top, int(min_votes), int(min_overlap),
+                                             ctypes.cast(nums, ctypes.c_void_p), len(ratios), _p(ws), ws.numel(),
+                                             *(_p(o) for o in outs), _stream()), "self_match_tempo")
     return outs
 
 

@@ -783,6 +783,36 @@ int grafp_cross_match_tempo_f32(const float *index_rows, int64_t n, const int64_
 size_t grafp_cross_match_tempo_workspace(const int64_t *src_rows, int n_src, int k, int min_votes, int n_ratios,
                                          int top);
 
+/* ---- tracks that share audio at another speed inside a library (grafp_amd/library.py; selfmatch_tempo.hip) ---------
+ * grafp_self_match_tempo_f32 -- grafp_self_match_f32 along sloped alignments.  Ratios as for
+ *   grafp_cross_match_tempo_f32: ratio_num (HOST, n_ratios int32, 1 <= n_ratios <= 64) strictly ascending integers num
+ *   in [128, 512], each num / 256 rows of the partner per row of the source; w(i) = (i * num + 128) >> 8, i a row's
+ *   index inside its source track.
+ *   For source track a = src_tracks[s] of L rows (library rows first[a] + i) and every ratio j: a hit r of row i counts
+ *   when it lies in [0, n) and outside [first[a], first[a + 1]) (own-track hits are dropped as in grafp_self_match_f32);
+ *   it names the track b holding r and the alignment a_g = r - w_j(i).  A candidate is a unique (b, a_g, j); duplicate
+ *   ids vote twice; a run that crosses a track boundary continues as a candidate of the next track.  Span [i_lo, i_hi],
+ *   m and eligibility as there; score = (sum_{i = i_lo..i_hi} <row[first[a] + i], row[a_g + w_j(i)]>) / m in the
+ *   arithmetic order of grafp_identify_f32, the partner's rows gathered.  Per partner b the best eligible candidate over
+ *   all ratios: highest score, then the ratio nearer to 1 (smaller |num - 256|, then smaller num), then the smaller a_g.
+ *   The `top` partners go out by score descending, then b ascending: out_track = b, out_delta = a_g - first[b],
+ *   out_start = i_lo, out_len = m, out_score, out_votes, out_ratio (int32) = num, each (n_src, top), padded with
+ *   -1 / INT_MIN / -1 / 0 / -inf / 0 / 0.  With ratio_num = {256} the first six outputs are bit for bit
+ *   grafp_self_match_f32's; for any ratios all seven are grafp_cross_match_tempo_f32's on q_rows = the source tracks' own
+ *   rows laid end to end and topk_ids = those rows' hits with every hit inside the source's own track replaced by -1.
+ *   ws: grafp_cross_match_tempo_workspace(src_rows, n_src, k, min_votes, n_ratios, top) bytes, src_rows (HOST) the rows
+ *   of each source track; the layout and what a smaller ws_bytes does are those of grafp_cross_match_tempo_f32 (below
+ *   the header and the lists: GRAFP_ERR_WORKSPACE; below the full size: every output padding, nothing written outside
+ *   ws, no -2 mark).  The plan, the (n_src, n_ratios) pass and the merge go out on `stream` with no host
+ *   synchronisation.
+ *   Limits: those of grafp_self_match_f32; n_ratios * top <= 4096; a source track of more than 4 194 303 rows is
+ *   padding; n + 2 * (longest source) < 2^32, which the other limits imply. */
+int grafp_self_match_tempo_f32(const float *index_rows, int64_t n, const int64_t *track_first_row, int n_tracks,
+                               const int64_t *topk_ids, int k, const int *src_tracks, int n_src, int top, int min_votes,
+                               int min_overlap, const int32_t *ratio_num, int n_ratios, void *ws, size_t ws_bytes,
+                               int32_t *out_track, int32_t *out_delta, int32_t *out_start, int32_t *out_len,
+                               float *out_score, int32_t *out_votes, int32_t *out_ratio, grafp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

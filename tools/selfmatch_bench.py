@@ -22,6 +22,13 @@ rows taken along the slope of the grid ratio 266 (+4 %): every track as one sour
 track), or with --tempo-source-rows N one source of N rows that runs on through the tracks from library row 0 (37 500:
 an hour).  Their hits are the self-search's.  Also reports the workspace bytes of every launch and how many sources
 find their track at ratio 266 over their whole length.
+--tempo X [--tempo-step G]: ops.self_match_tempo (csrc/selfmatch_tempo.hip) over the ratio grid of
+library.tempo_ratios(X, 256, G) (0.06 at step 1: 31 ratios) next to ops.self_match on the same library and hits,
+alternating in one loop (medians of --reps).  Also reports the workspace bytes of both launches and what the sloped launch
+makes of the planted copies (which run at ratio 256): the share whose partner it lists, the share it lists at the exact
+offset and ratio 256, and the median of its span's rows over the dense launch's (a partner's best is its highest MEAN over
+all ratios, so a cleaner part of a noisy copy, cut out by a neighbouring ratio, can outscore the whole span).  Expected
+cost: about R dense passes plus the merge.
 """
 import argparse
 import json
@@ -125,6 +132,47 @@ def _tempo(ops, rows, first, ids, per, reps, counts, source_rows):
     return res
 
 
+def _self_tempo(ops, library, rows, first, ids, per, reps, tempo, step, planted):
+    """The --tempo mode (see the top)."""
+    grid = library.tempo_ratios(tempo, ops.IDENTIFY_TEMPO_DEN, 1 if step is None else step)
+    kw = dict(top=8, min_votes=4)
+    runs = {"self_match_dense_ms": lambda: ops.self_match(rows, first, ids, **kw),
+            "self_match_tempo_ms": lambda: ops.self_match_tempo(rows, first, ids, grid, **kw)}
+    times = {name: [] for name in runs}
+    for fn in runs.values():
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(reps):                                                  # the launches alternate in one loop
+        for name, fn in runs.items():
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            times[name].append(a.elapsed_time(b))
+    res = {"tempo_ratios": int(len(grid)), "tempo_grid": [int(grid[0]), int(grid[-1])]}
+    res.update({name: round(float(np.median(v)), 3) for name, v in times.items()})
+    res["self_match_tempo_over_dense"] = round(res["self_match_tempo_ms"] / res["self_match_dense_ms"], 3)
+    lens = np.full(first.numel() - 1, per, np.int64)
+    res["workspace_dense_bytes"] = ops.self_match_workspace_bytes(lens, ids.shape[1], 4)
+    res["workspace_tempo_bytes"] = ops.cross_match_tempo_workspace_bytes(lens, ids.shape[1], 4, len(grid), 8)
+    b_, d_, _, m_, _, _, ra_ = (x.cpu().numpy() for x in runs["self_match_tempo_ms"]())
+    db_, _, _, dm_, _, _ = (x.cpu().numpy() for x in runs["self_match_dense_ms"]())
+    found, exact, share = 0, 0, []
+    for src, dst, d in planted:
+        for a, b, dd in ((src, dst, d), (dst, src, -d)):
+            j = np.flatnonzero(b_[a] == b)
+            found += j.size > 0
+            exact += bool(j.size and d_[a, j[0]] == dd and ra_[a, j[0]] == 256)
+            jd = np.flatnonzero(db_[a] == b)
+            if j.size and jd.size:
+                share.append(m_[a, j[0]] / dm_[a, jd[0]])
+    res["tempo_planted_partner_found"] = round(found / max(1, 2 * len(planted)), 4)
+    res["tempo_planted_exact_offset_at_256"] = round(exact / max(1, 2 * len(planted)), 4)
+    res["tempo_planted_rows_over_dense_rows_median"] = round(float(np.median(share)), 4) if share else None
+    return res
+
+
 def main(argv=None):
     from grafp_amd import library, ops
     from grafp_amd.util import load_config
@@ -139,6 +187,9 @@ def main(argv=None):
                     help="with --cross: ratio counts, e.g. 1,15,31: time ops.cross_match_tempo against ops.cross_match")
     ap.add_argument("--tempo-source-rows", type=int, default=0,
                     help="with --tempo-ratios: one source of this many rows instead of every track as a source")
+    ap.add_argument("--tempo", type=float, default=None,
+                    help="also time ops.self_match_tempo over the ratios [1 - X, 1 + X] against ops.self_match")
+    ap.add_argument("--tempo-step", type=int, default=None, help="with --tempo: the grid's spacing in 1/256 (default 1)")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     cfg = load_config()
@@ -179,6 +230,8 @@ def main(argv=None):
            "self_match_over_search": round(t_sm / t_search, 4),
            "recall_exact_offset": round(hit / (2 * len(planted)), 4),
            "stray_pairs": len(stray), "max_stray_score": round(max(stray), 4) if stray else None}
+    if args.tempo is not None:
+        out.update(_self_tempo(ops, library, rows, first, ids, per, args.reps, args.tempo, args.tempo_step, planted))
     if args.cross:
         out.update(_cross(ops, rows, first, ids, per, args.reps))
         if args.tempo_ratios:
