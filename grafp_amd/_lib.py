@@ -118,6 +118,7 @@ SIGNATURES = {
     "grafp_resample_f32": (_I, [_P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _P, _P, _P]),
     "grafp_draw_pairs_f32": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
     "grafp_speed_change_f32": (_I, [_P, _L, _I, _I, _L, _P, _P, _L, _I, _P]),
+    "grafp_time_stretch_f32": (_I, [_P, _L, _I, _I, _L, _P, _P, _L, _I, _P, _L, _P]),
     "grafp_identify_f32": (_I, [_P, _L, _P, _I, _P, _L, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "grafp_identify_thin_f32": (_I, [_P, _L, _P, _I, _I, _P, _L, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "grafp_identify_pq_f32": (_I, [_P, _P, _L, _P, _I, _P, _I, _P, _I, _P, _L, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P,

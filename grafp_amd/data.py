@@ -9,9 +9,9 @@ launch (ops.draw_pairs), following NeuralfpDataset.__getitem__ for training; eva
 (tracks()), which fpdb.create_fp_db / create_dummy_db take in place of DataLoader(NeuralfpDataset(train=False)).
 
 Differences from the reference, on purpose:
-  * a track shorter than offset_mod + 1 samples (offset_mod = int(fs*offset + clip); with speed augmentation on,
-    int(fs*offset) + draw_len: the views are drawn with the resampler's context) is excluded from training draws
-    and counted (stats['excluded']).  The reference skips tracks up to one clip long (:61-62) and raises in
+  * a track shorter than offset_mod + 1 samples (offset_mod = int(fs*offset + clip); with speed or time-stretch
+    augmentation on, int(fs*offset) + draw_len: the views are drawn with the context those need) is excluded from
+    training draws and counted (stats['excluded']).  The reference skips tracks up to one clip long (:61-62) and raises in
     np.random.randint for those up to offset_mod (:74); here neither happens.
   * a silent draw moves on to the next track of the corpus (order of the index), as `self[idx + 1]` does, but at most
     `attempts` times; if all are silent the last draw is used and counted (silent_rows()).
@@ -232,13 +232,20 @@ class DeviceAudioCorpus:
         self.offset_mod = int(self.fs * cfg["offset"] + self.clip)
         # speed augmentation on (cfg['speed_prob'] > 0): both views are drawn at draw_len samples, the clip plus the context
         # ops.speed_change needs at the largest ratio; the jitter between the views stays int(fs * offset)
+        # time-stretch augmentation on (cfg['stretch_prob'] > 0): draw_len also holds what ops.time_stretch needs to
+        # produce the speed change's input (or the clip), as GPUTransformNeuralfp.draw_len does
         self.draw_len = self.clip
-        speed = ops.speed_config(cfg)
+        speed, stretch = ops.speed_config(cfg), ops.stretch_config(cfg)
         if speed is not None:
             self.draw_len = ops.speed_input_len(self.clip, speed[2])
+        if stretch is not None:
+            self.draw_len = ops.stretch_input_len(self.draw_len, stretch[2])
+        if speed is not None or stretch is not None:
             self.offset_mod = int(self.fs * cfg["offset"]) + self.draw_len
             if self.offset_mod > ops.DRAW_PAIRS_MAX_WINDOW:
-                raise ValueError(f"speed_range = {list(cfg['speed_range'])}: the training draw needs a window of "
+                keys = " and ".join(f"{k} = {list(cfg[k])}" for k, on in (("stretch_range", stretch), ("speed_range", speed))
+                                    if on is not None)
+                raise ValueError(f"{keys}: the training draw needs a window of "
                                  f"{self.offset_mod} samples (draw_len = {self.draw_len} plus the offset jitter), more than "
                                  f"the {ops.DRAW_PAIRS_MAX_WINDOW} draw_pairs holds on chip; lower the upper ratio, dur or offset")
         self.silence = float(cfg["silence"])
@@ -364,7 +371,7 @@ class DeviceAudioCorpus:
     # ---- training draws -------------------------------------------------------------------------------------
     def draw_pairs(self, track_ids, generator=None, attempts=8):
         """One batch: row b starts at corpus track track_ids[b] (which must be eligible) -> (x_i, x_j), (B, draw_len):
-        draw_len is the clip, or with speed augmentation on the clip plus the resampler's context (what
+        draw_len is the clip, or with speed or time-stretch augmentation on the clip plus their context (what
         GPUTransformNeuralfp.forward and Trainer.step then take)."""
         try:
             rows = [self._pos[int(t)] for t in torch.as_tensor(track_ids).reshape(-1).tolist()]

@@ -544,6 +544,91 @@ def speed_change(x, ratio, out_len, x_offset=0, out=None):
 
 
 # ------------------------------------------------------------------------------------------------
+# time-stretch augmentation (csrc/stretch.hip): every clip's tempo changed by its own ratio, pitch kept
+# ------------------------------------------------------------------------------------------------
+STRETCH_FRAME, STRETCH_HOP, STRETCH_SEARCH = 512, 256, 128      # N, HS and the reach of delta (ST_N, ST_HS, ST_D)
+
+
+def stretch_frames(out_len):
+    """Frames of the rule for out_len outputs: F = ceil(out_len / HS) + 1 (the columns of time_stretch's shifts)."""
+    return -(-int(out_len) // STRETCH_HOP) + 1
+
+
+def stretch_pad(max_ratio):
+    """Samples of context in front of a clip that is to be stretched at up to max_ratio: frame 0 starts HS * ratio
+    samples before the clip and the search reaches 128 further; ceil(HS * max_ratio) + 128 + 1.  Host-side."""
+    return math.ceil(STRETCH_HOP * float(max_ratio)) + STRETCH_SEARCH + 1
+
+
+def stretch_input_len(out_len, max_ratio):
+    """Input samples from which time_stretch(x, ratio, out_len, x_offset=stretch_pad(max_ratio)) reads no zero padding
+    at any ratio <= max_ratio.  From the rule: the last frame's last candidate ends at a_{F-1} + 127 + N and its template
+    at a_{F-2} + 127 + HS + N (the further of the two below ratio 1), with a_i = pad + floor((i - 1) HS ratio + 0.5)
+    rounded up and one sample to spare: pad + max(ceil((F-2) HS r), ceil((F-3) HS r) + HS) + 128 + N + 1."""
+    F, r = stretch_frames(out_len), float(max_ratio)
+    last = max(math.ceil((F - 2) * STRETCH_HOP * r), math.ceil((F - 3) * STRETCH_HOP * r) + STRETCH_HOP)
+    return stretch_pad(r) + last + STRETCH_SEARCH + STRETCH_FRAME + 1
+
+
+def stretch_config(cfg):
+    """The stretch keys of a configuration, validated: -> (stretch_prob, lo, hi), or None when time-stretch augmentation
+    is off (stretch_prob absent or 0).  stretch_range = [lo, hi] with 0.5 <= lo <= hi <= 2 is required when it is on."""
+    prob, rng = cfg.get("stretch_prob"), cfg.get("stretch_range")
+    prob = 0.0 if prob is None else float(prob)
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError(f"stretch_prob = {prob} is not a probability")
+    if rng is not None:
+        if not isinstance(rng, (list, tuple)) or len(rng) != 2:
+            raise ValueError(f"stretch_range = {rng!r} must be [lo, hi]")
+        lo, hi = float(rng[0]), float(rng[1])
+        if not 0.5 <= lo <= hi <= 2.0:
+            raise ValueError(f"stretch_range = {rng!r} must satisfy 0.5 <= lo <= hi <= 2")
+    if prob == 0.0:
+        return None
+    if rng is None:
+        raise ValueError("stretch_prob > 0 needs stretch_range = [lo, hi]")
+    return prob, lo, hi
+
+
+def time_stretch(x, ratio, out_len, x_offset=0, out=None, return_shifts=False):
+    """Every clip of a batch time-stretched by its own ratio in one launch, pitch kept (grafp_time_stretch_f32; WSOLA,
+    the rule is stated in csrc/stretch.hip): x (B, T_in) or (T_in,) f32, rows may be strided; ratio (B,) f32 device tensor
+    of input samples per output sample (clamped to [0.5, 2], NaN = 1; above 1 the clip plays fast; exactly 1 is a bit
+    copy) -- or one number for all clips; frame i is taken near input x_offset + (i - 1) * 256 * ratio, zeros outside the
+    row.  -> (B, out_len) f32 (`out`: written in place, rows may be strided); with return_shifts=True also the
+    (B, stretch_frames(out_len)) int32 shifts delta_i of the frames, which say where the splices are.  The ratios are
+    read on the device: no host synchronisation, so the launch can be captured into a HIP graph."""
+    _require_gpu(x, ratio if torch.is_tensor(ratio) else None, out)
+    squeeze = x.dim() == 1
+    x2 = x.detach().reshape(1, -1) if squeeze else x.detach()
+    if x2.dim() != 2:
+        raise ValueError("time_stretch: x must be (B, T_in) or (T_in,)")
+    if x2.dtype != torch.float32 or x2.stride(1) != 1 or x2.stride(0) < x2.shape[1]:
+        x2 = _f32c(x2)
+    B, T_in = x2.shape
+    out_len = int(out_len)
+    if torch.is_tensor(ratio):
+        r = _f32c(ratio.to(x2.device)).reshape(-1)
+    else:
+        r = torch.full((B,), float(ratio), dtype=torch.float32, device=x2.device)
+    if r.numel() != B:
+        raise ValueError(f"time_stretch: {r.numel()} ratios for {B} clips")
+    if out is None:
+        out = torch.empty((B, out_len), dtype=torch.float32, device=x2.device)
+    elif (out.dtype != torch.float32 or out.device != x2.device or tuple(out.shape) != (B, out_len)
+          or out.stride(1) != 1 or out.stride(0) < out_len):
+        raise ValueError("time_stretch: `out` must be a (B, out_len) f32 device tensor with unit column stride")
+    shifts = torch.empty((B, stretch_frames(out_len)), dtype=torch.int32, device=x2.device) if return_shifts else None
+    with _timed("time_stretch", (B, T_in, out_len)):
+        check(lib.grafp_time_stretch_f32(_p(x2), x2.stride(0), B, T_in, int(x_offset), _p(r), _p(out), out.stride(0),
+                                         out_len, _p(shifts), shifts.stride(0) if return_shifts else 0, _stream()),
+              "time_stretch")
+    if squeeze and out.dim() == 2:
+        out, shifts = out[0], (shifts[0] if return_shifts else None)
+    return (out, shifts) if return_shifts else out
+
+
+# ------------------------------------------------------------------------------------------------
 # K2  peak extractor
 # ------------------------------------------------------------------------------------------------
 _RAMPS = {}

@@ -36,9 +36,10 @@ class Trainer:
         self._overlap_graph_allreduce = bool(overlap_graph_allreduce)
         # ir_dir / noise_dir: recordings for the batched device-side augmentation of the second view (train.py:150-151)
         self.augment = GPUTransformNeuralfp(dict(cfg, aug_seed=aug_seed), ir_dir, noise_dir, train=True).to(device)
-        # samples per view that step() / step_graph() take: the clip, or -- with speed augmentation on (cfg['speed_prob'],
-        # cfg['speed_range']) -- the clip plus the resampler's context, as DeviceAudioCorpus then draws it.  The per-clip
-        # ratios come from the same generator as the other draws: under step_graph every replay draws fresh ones
+        # samples per view that step() / step_graph() take: the clip, or -- with speed augmentation (cfg['speed_prob'],
+        # cfg['speed_range']) or time-stretch augmentation (cfg['stretch_prob'], cfg['stretch_range']) on -- the clip plus
+        # the context those need, as DeviceAudioCorpus then draws it.  The per-clip ratios come from the same generator as
+        # the other draws: under step_graph every replay draws fresh ones
         self.draw_len = self.augment.draw_len
         # train.py:174 (same Adam, defaults); on the GPU the update of all 271 parameter tensors is one fused launch
         # with device-side step counters instead of ~35 multi-tensor launches and 271 host-side counter bumps
@@ -73,9 +74,9 @@ class Trainer:
         return torch.autocast(device_type="cuda", dtype=self.amp_dtype)
 
     def step(self, x_i, x_j):
-        """x_i, x_j: (B_local, T) waveforms already on the device (T = self.draw_len when speed augmentation is on; any
-        other length is refused).  Returns this rank's share of the loss (a 0-d device tensor; the shares sum to the
-        global mean loss)."""
+        """x_i, x_j: (B_local, T) waveforms already on the device (T = self.draw_len when speed or time-stretch
+        augmentation is on; any other length is refused).  Returns this rank's share of the loss (a 0-d device tensor; the
+        shares sum to the global mean loss)."""
         self._rebind_lr()                      # a util.load_ckp(optimizer=trainer.opt) in between swapped the lr object
         # (Module.train() walks and re-assigns ~340 modules: 1.7 ms of host time per call -- only when something IS in eval
         #  mode: the root, or one of the mode-sensitive modules under it, e.g. after model.encoder.eval() for fingerprinting)

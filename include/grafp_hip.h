@@ -614,6 +614,23 @@ int grafp_speed_change_f32(const float *x, int64_t x_stride, int B, int T_in, in
                            const float *ratio /* (B) device */, float *out, int64_t out_stride, int T_out,
                            grafp_stream_t stream);
 
+/* ---- time-stretch augmentation of the second training view (stretch.hip) ------------------------------------------
+ * grafp_time_stretch_f32 -- changes the tempo of each of B clips by its own ratio, read on the device (capturable), and
+ *   keeps the pitch: WSOLA in the time domain.  Frame N = 512, hop HS = 256, 256 candidates delta in [-128, 127], window
+ *   w[n] = sin^2(pi n / N).  For clip b:
+ *   rho = ratio[b] clamped to [0.5, 2], NaN -> 1 (input samples per output sample: above 1 plays fast);
+ *   frames i = 0 .. F - 1, F = ceil(T_out / HS) + 1;  a_i = x_offset + floor((i - 1) * HS * rho + 0.5) (formed in f64);
+ *   delta_0 = 0; for i >= 1, p_i = a_i + delta_i where delta_i maximises c(delta) = sum over n < N of
+ *   xz[p_{i-1} + HS + n] * xz[a_i + delta + n] (ties: the smaller |delta|, then the negative one);
+ *   out[b][(i - 1) HS + n] = w[n + HS] * xz[p_{i-1} + HS + n] + w[n] * xz[p_i + n], 0 <= n < HS;
+ *   xz = x inside [0, T_in) and 0 outside.  rho == 1.0f exactly: out[b][m] = xz[b][x_offset + m] bit for bit, all delta 0.
+ *   shift (may be null): (B, F) int32 with row stride shift_stride >= F, receives delta_i.
+ *   x: (B, T_in) with row stride x_stride >= T_in; out: (B, T_out) with row stride out_stride >= T_out; out must not
+ *   alias x; x_offset >= 0; T_out <= 2^30.  No atomics, no workspace: bit-reproducible. */
+int grafp_time_stretch_f32(const float *x, int64_t x_stride, int B, int T_in, int64_t x_offset,
+                           const float *ratio /* (B) device */, float *out, int64_t out_stride, int T_out,
+                           int32_t *shift /* (B, F) or null */, int64_t shift_stride, grafp_stream_t stream);
+
 /* ---- track-aware sequence identification (grafp_amd/library.py; identify.hip) -----------------------------------
  * grafp_identify_f32 -- which track, and where in it, each of n_items query items is.  index_rows: the (n, 128) f32
  *   library rows of n_tracks tracks laid end to end, track t owning rows [track_first_row[t], track_first_row[t+1])
