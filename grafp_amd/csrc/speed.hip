@@ -33,6 +33,7 @@
 // Built WITHOUT packed-f32 instructions (Makefile NOPK), as corpus.hip is: DESIGN.md section 12.7b.
 #include <math.h>
 
+#include "clipwarp.h"
 #include "common.h"
 
 namespace grafp {
@@ -45,11 +46,6 @@ constexpr int SP_STAGE = (SP_TILE - 1) * 2 + 2 * SP_WMAX + 4;
 constexpr float SP_PI = 3.14159265358979323846f;
 constexpr float SP_PI_12 = 0.26179938779914943654f;
 
-__device__ __forceinline__ float sp_ratio(float r) {
-    if (!(r == r)) return 1.0f;
-    return r < 0.5f ? 0.5f : (r > 2.0f ? 2.0f : r);
-}
-
 __global__ __launch_bounds__(SP_THREADS) void speed_change_kernel(const float *__restrict__ x, int64_t x_stride, int T_in,
                                                                   int64_t x_offset, const float *__restrict__ ratio,
                                                                   float *__restrict__ out, int64_t out_stride, int T_out,
@@ -58,17 +54,12 @@ __global__ __launch_bounds__(SP_THREADS) void speed_change_kernel(const float *_
     const int b = blockIdx.x / tiles, tile = blockIdx.x - b * tiles, tid = threadIdx.x;
     const float *xb = x + (int64_t)b * x_stride;
     float *ob = out + (int64_t)b * out_stride;
-    const float rho = sp_ratio(ratio[b]);
+    const float rho = warp_ratio(ratio[b]);
     const int m0 = tile * SP_TILE;
     const int m_end = min(T_out, m0 + SP_TILE);            // > m0: the grid covers T_out exactly
 
-    if (rho == 1.0f) {                                     // wave-uniform: the whole workgroup copies
-        for (int m = m0 + tid; m < m_end; m += SP_THREADS) {
-            const int64_t s = x_offset + m;
-            ob[m] = s < T_in ? xb[s] : 0.0f;               // x_offset >= 0
-        }
-        return;
-    }
+    if (rho == 1.0f)                                       // wave-uniform: the whole workgroup copies
+        return warp_copy<SP_THREADS>(xb, T_in, x_offset, ob, m0, m_end, tid);
 
     const float c = 0.99f * fminf(1.0f, 1.0f / rho);
     const int W = min(SP_WMAX, (int)(6.0f / c + 1e-3f));   // floor(6 / c); the nudge keeps an integer 6 / c from rounding
@@ -110,12 +101,8 @@ extern "C" int grafp_speed_change_f32(const float *x, int64_t x_stride, int B, i
                                       const float *ratio, float *out, int64_t out_stride, int T_out,
                                       grafp_stream_t stream) {
     using namespace grafp;
-    GRAFP_REQUIRE(x && ratio && out, "speed_change: null pointer");
-    GRAFP_REQUIRE(B > 0 && T_in > 0 && T_out > 0, "speed_change: bad sizes B=%d T_in=%d T_out=%d", B, T_in, T_out);
-    GRAFP_REQUIRE(x_stride >= T_in && out_stride >= T_out, "speed_change: row strides %lld / %lld below the row lengths %d / %d",
-                  (long long)x_stride, (long long)out_stride, T_in, T_out);
-    GRAFP_REQUIRE(x != out, "speed_change: out must not alias x");
-    GRAFP_REQUIRE(x_offset >= 0 && x_offset <= ((int64_t)1 << 40), "speed_change: x_offset=%lld out of range", (long long)x_offset);
+    const int st = warp_check("speed_change", x, x_stride, B, T_in, x_offset, ratio, out, out_stride, T_out, 0);
+    if (st != GRAFP_OK) return st;
     const int64_t tiles = ((int64_t)T_out + SP_TILE - 1) / SP_TILE;
     GRAFP_REQUIRE(tiles * B <= 0x7fffffff, "speed_change: %d clips of %d outputs exceed the grid", B, T_out);
     hipLaunchKernelGGL(speed_change_kernel, dim3((unsigned)(tiles * B)), dim3(SP_THREADS), 0, (hipStream_t)stream, x,

@@ -47,6 +47,7 @@
 // Built WITHOUT packed-f32 instructions (Makefile NOPK), as speed.hip is: DESIGN.md section 12.7b.
 #include <math.h>
 
+#include "clipwarp.h"
 #include "common.h"
 
 namespace grafp {
@@ -65,11 +66,6 @@ static_assert(ST_D + (ST_D - 1) + ST_HS + ST_N <= ST_R, "the next template lies 
 static_assert(4 * 63 + 3 + ST_N <= ST_R, "the last candidate's last product lies inside R");
 
 typedef float st_slot __attribute__((ext_vector_type(4)));    // one 16-byte LDS slot, read whole (ds_read_b128)
-
-__device__ __forceinline__ float st_ratio(float r) {
-    if (!(r == r)) return 1.0f;
-    return r < 0.5f ? 0.5f : (r > 2.0f ? 2.0f : r);
-}
 
 // the rule's order on candidates: larger c, then smaller |delta|, then the negative one.  (A NaN c never wins.)
 __device__ __forceinline__ bool st_better(float c, int d, float bc, int bd) {
@@ -91,13 +87,10 @@ __global__ __launch_bounds__(ST_THREADS) void time_stretch_kernel(const float *_
     const float *xb = x + (int64_t)b * x_stride;
     float *ob = out + (int64_t)b * out_stride;
     int32_t *sb = shift ? shift + (int64_t)b * shift_stride : nullptr;
-    const float rho = st_ratio(ratio[b]);
+    const float rho = warp_ratio(ratio[b]);
 
     if (rho == 1.0f) {                                     // workgroup-uniform: the whole workgroup copies
-        for (int m = tid; m < T_out; m += ST_THREADS) {
-            const int64_t s = x_offset + m;
-            ob[m] = s < T_in ? xb[s] : 0.0f;               // x_offset >= 0
-        }
+        warp_copy<ST_THREADS>(xb, T_in, x_offset, ob, 0, T_out, tid);
         if (sb)
             for (int i = tid; i < frames; i += ST_THREADS) sb[i] = 0;
         return;
@@ -197,16 +190,11 @@ extern "C" int grafp_time_stretch_f32(const float *x, int64_t x_stride, int B, i
                                       const float *ratio, float *out, int64_t out_stride, int T_out, int32_t *shift,
                                       int64_t shift_stride, grafp_stream_t stream) {
     using namespace grafp;
-    GRAFP_REQUIRE(x && ratio && out, "time_stretch: null pointer");
-    GRAFP_REQUIRE(B > 0 && T_in > 0 && T_out > 0 && T_out <= (1 << 30), "time_stretch: bad sizes B=%d T_in=%d T_out=%d", B,
-                  T_in, T_out);
-    GRAFP_REQUIRE(x_stride >= T_in && out_stride >= T_out, "time_stretch: row strides %lld / %lld below the row lengths %d / %d",
-                  (long long)x_stride, (long long)out_stride, T_in, T_out);
+    const int st = warp_check("time_stretch", x, x_stride, B, T_in, x_offset, ratio, out, out_stride, T_out, 1 << 30);
+    if (st != GRAFP_OK) return st;
     const int frames = (T_out + ST_HS - 1) / ST_HS + 1;
     GRAFP_REQUIRE(!shift || shift_stride >= frames, "time_stretch: shift row stride %lld below the %d frames",
                   (long long)shift_stride, frames);
-    GRAFP_REQUIRE(x != out, "time_stretch: out must not alias x");
-    GRAFP_REQUIRE(x_offset >= 0 && x_offset <= ((int64_t)1 << 40), "time_stretch: x_offset=%lld out of range", (long long)x_offset);
     GRAFP_REQUIRE((int64_t)B <= 0x7fffffff, "time_stretch: %d clips exceed the grid", B);      // one workgroup per clip
     hipLaunchKernelGGL(time_stretch_kernel, dim3((unsigned)B), dim3(ST_THREADS), 0, (hipStream_t)stream, x, x_stride, T_in,
                        x_offset, ratio, out, out_stride, T_out, shift, shift_stride, frames);

@@ -233,18 +233,14 @@ class DeviceAudioCorpus:
         # speed augmentation on (cfg['speed_prob'] > 0): both views are drawn at draw_len samples, the clip plus the context
         # ops.speed_change needs at the largest ratio; the jitter between the views stays int(fs * offset)
         # time-stretch augmentation on (cfg['stretch_prob'] > 0): draw_len also holds what ops.time_stretch needs to
-        # produce the speed change's input (or the clip), as GPUTransformNeuralfp.draw_len does
-        self.draw_len = self.clip
-        speed, stretch = ops.speed_config(cfg), ops.stretch_config(cfg)
-        if speed is not None:
-            self.draw_len = ops.speed_input_len(self.clip, speed[2])
-        if stretch is not None:
-            self.draw_len = ops.stretch_input_len(self.draw_len, stretch[2])
-        if speed is not None or stretch is not None:
+        # produce the speed change's input (or the clip): ops.view_plan, which GPUTransformNeuralfp.draw_len comes from too
+        plan = ops.view_plan(cfg)
+        self.draw_len = plan.draw_len
+        if plan.on:
             self.offset_mod = int(self.fs * cfg["offset"]) + self.draw_len
             if self.offset_mod > ops.DRAW_PAIRS_MAX_WINDOW:
-                keys = " and ".join(f"{k} = {list(cfg[k])}" for k, on in (("stretch_range", stretch), ("speed_range", speed))
-                                    if on is not None)
+                keys = " and ".join(f"{k} = {list(cfg[k])}" for k, on in (("stretch_range", plan.stretch),
+                                                                         ("speed_range", plan.speed)) if on is not None)
                 raise ValueError(f"{keys}: the training draw needs a window of "
                                  f"{self.offset_mod} samples (draw_len = {self.draw_len} plus the offset jitter), more than "
                                  f"the {ops.DRAW_PAIRS_MAX_WINDOW} draw_pairs holds on chip; lower the upper ratio, dur or offset")

@@ -109,22 +109,13 @@ class GPUTransformNeuralfp(nn.Module):
         self.overlap, self.arch, self.n_frames = cfg["overlap"], cfg["arch"], cfg["n_frames"]
         self.train, self.cpu, self.cfg, self.abl = train, cpu, cfg, abl   # `train` shadows nn.Module.train as in the reference
         self.seed, self._gen = cfg.get("aug_seed"), None      # optional: reproducible augmentation draws
-        # optional speed augmentation of the second training view (cfg['speed_prob'], cfg['speed_range'] = [lo, hi]): the
-        # clip is played at a random ratio by resampling, which moves its pitch too (ops.speed_change).  When on, the
-        # train branch of forward() takes both views at draw_len samples: pad samples of context on either side of x_i's
-        # clip, and enough input for x_j at the largest ratio
-        self.speed = ops.speed_config(cfg)
-        # optional time-stretch augmentation of the same view (cfg['stretch_prob'], cfg['stretch_range'] = [lo, hi]): the
-        # tempo moves, the pitch stays (ops.time_stretch).  It runs before the speed change and hands it speed_len samples,
-        # so draw_len is what the stretch needs for that many outputs at its largest ratio, and x_i's clip starts
-        # pad = stretch pad + speed pad samples into its view: at both ratios 1 the two views then hold the same samples
-        self.stretch = ops.stretch_config(cfg)
-        self.clip = int(cfg["fs"] * cfg["dur"]) if self.speed or self.stretch or "dur" in cfg else None
-        self.speed_pad = ops.speed_pad(self.speed[2]) if self.speed else 0
-        self.speed_len = ops.speed_input_len(self.clip, self.speed[2]) if self.speed else self.clip
-        self.stretch_pad = ops.stretch_pad(self.stretch[2]) if self.stretch else 0
-        self.pad = self.stretch_pad + self.speed_pad
-        self.draw_len = ops.stretch_input_len(self.speed_len, self.stretch[2]) if self.stretch else self.speed_len
+        # optional time-stretch (cfg['stretch_prob'], cfg['stretch_range'] = [lo, hi]: the tempo moves, the pitch stays) and
+        # speed augmentation (cfg['speed_prob'], cfg['speed_range']: resampling, the pitch moves too) of the second training
+        # view.  When on, the train branch of forward() takes both views at draw_len samples and x_i's clip starts pad
+        # samples into its view: at both ratios 1 the two views hold the same samples.  ops.view_plan gives speed, stretch,
+        # clip, speed_pad, speed_len, stretch_pad, pad, draw_len and `on` (which are on, in words)
+        for name, value in ops.view_plan(cfg)._asdict().items():
+            setattr(self, name, value)
         has_ir = ir_dir is not None and not (isinstance(ir_dir, (list, tuple, str)) and len(ir_dir) == 0)
         has_noise = noise_dir is not None and not (isinstance(noise_dir, (list, tuple, str)) and len(noise_dir) == 0)
         if has_ir:
@@ -179,26 +170,26 @@ class GPUTransformNeuralfp(nn.Module):
     def _has_banks(self):
         return self.ir_bank is not None or self.noise_bank is not None
 
-    def time_stretch(self, x):
-        """x (B, draw_len) -> (B, speed_len): per clip, with probability stretch_prob, its tempo changed at a ratio uniform
-        in stretch_range with the pitch kept (otherwise at 1: a copy of x[:, stretch_pad:stretch_pad + speed_len])."""
-        prob, lo, hi = self.stretch
-        B, dev = x.shape[0], x.device
+    def _draw_ratio(self, spec, B, dev):
+        """(B,) ratios for spec = (prob, lo, hi): per clip, with probability prob uniform in [lo, hi], otherwise 1."""
+        prob, lo, hi = spec
         g = self._rng(dev)
         keep = torch.rand(B, device=dev, generator=g) < prob
         rho = lo + (hi - lo) * torch.rand(B, device=dev, generator=g)
-        return ops.time_stretch(x, torch.where(keep, rho, torch.ones_like(rho)), self.speed_len, x_offset=self.stretch_pad)
+        return torch.where(keep, rho, torch.ones_like(rho))
+
+    def time_stretch(self, x):
+        """x (B, draw_len) -> (B, speed_len): per clip, with probability stretch_prob, its tempo changed at a ratio uniform
+        in stretch_range with the pitch kept (otherwise at 1: a copy of x[:, stretch_pad:stretch_pad + speed_len])."""
+        rho = self._draw_ratio(self.stretch, x.shape[0], x.device)
+        return ops.time_stretch(x, rho, self.speed_len, x_offset=self.stretch_pad)
 
     def speed_change(self, x):
         """x (B, speed_len) -> (B, clip): per clip, with probability speed_prob, played at a ratio uniform in speed_range
         (otherwise at 1: a copy of x[:, speed_pad:speed_pad + clip]; speed_len is draw_len unless time stretch is on too).
         The recording is played fast; room and noise, applied after it, are not."""
-        prob, lo, hi = self.speed
-        B, dev = x.shape[0], x.device
-        g = self._rng(dev)
-        keep = torch.rand(B, device=dev, generator=g) < prob
-        rho = lo + (hi - lo) * torch.rand(B, device=dev, generator=g)
-        return ops.speed_change(x, torch.where(keep, rho, torch.ones_like(rho)), self.clip, x_offset=self.speed_pad)
+        rho = self._draw_ratio(self.speed, x.shape[0], x.device)
+        return ops.speed_change(x, rho, self.clip, x_offset=self.speed_pad)
 
     def train_transform(self, x):
         if self.stretch:
@@ -230,8 +221,7 @@ class GPUTransformNeuralfp(nn.Module):
         if self.train:                    # (:77-85) both views -> (B, n_mels, n_frames)
             if self.speed or self.stretch:
                 if x_i.dim() != 2 or x_j.dim() != 2 or x_i.shape[1] != self.draw_len or x_j.shape[1] != self.draw_len:
-                    what = " and ".join(n for n, on in (("stretch", self.stretch), ("speed", self.speed)) if on)
-                    raise ValueError(f"{what} augmentation is on: both views must be (B, draw_len = {self.draw_len}) "
+                    raise ValueError(f"{self.on} augmentation is on: both views must be (B, draw_len = {self.draw_len}) "
                                      f"samples (the clip of {self.clip} with its context), got {tuple(x_i.shape)} and "
                                      f"{tuple(x_j.shape)}")
                 x_i = x_i[:, self.pad:self.pad + self.clip]

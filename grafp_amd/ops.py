@@ -4,6 +4,7 @@ PyTorch is used here for device memory, the current HIP stream and autograd plum
 computation below runs in libgrafp_hip.so.  There is no CPU path: tensors that are not on a HIP device
 raise immediately.
 """
+import collections
 import contextlib
 import ctypes
 import math
@@ -475,6 +476,55 @@ def draw_pairs(bank, track_start, track_len, norm, row_track, uniforms, clip, of
 
 
 # ------------------------------------------------------------------------------------------------
+# the per-clip warps of the second training view (csrc/clipwarp.h): speed change and time stretch, what they share
+# ------------------------------------------------------------------------------------------------
+def _ratio_config(cfg, key):
+    """The {key}_prob / {key}_range keys of a configuration, validated: -> (prob, lo, hi), or None when the augmentation
+    is off ({key}_prob absent or 0).  {key}_range = [lo, hi] with 0.5 <= lo <= hi <= 2 is required when it is on."""
+    prob, rng = cfg.get(f"{key}_prob"), cfg.get(f"{key}_range")
+    prob = 0.0 if prob is None else float(prob)
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError(f"{key}_prob = {prob} is not a probability")
+    if rng is not None:
+        if not isinstance(rng, (list, tuple)) or len(rng) != 2:
+            raise ValueError(f"{key}_range = {rng!r} must be [lo, hi]")
+        lo, hi = float(rng[0]), float(rng[1])
+        if not 0.5 <= lo <= hi <= 2.0:
+            raise ValueError(f"{key}_range = {rng!r} must satisfy 0.5 <= lo <= hi <= 2")
+    if prob == 0.0:
+        return None
+    if rng is None:
+        raise ValueError(f"{key}_prob > 0 needs {key}_range = [lo, hi]")
+    return prob, lo, hi
+
+
+def _warp_args(name, x, ratio, out_len, out):
+    """The arguments speed_change and time_stretch share, as the entry points take them: x as f32 rows (B, T_in) with unit
+    column stride, ratio as (B,) f32 on x's device, `out` checked or allocated.  -> (x2, r, out, squeeze, B, T_in);
+    squeeze: x was 1-D, the caller hands row 0 back."""
+    _require_gpu(x, ratio if torch.is_tensor(ratio) else None, out)
+    squeeze = x.dim() == 1
+    x2 = x.detach().reshape(1, -1) if squeeze else x.detach()
+    if x2.dim() != 2:
+        raise ValueError(f"{name}: x must be (B, T_in) or (T_in,)")
+    if x2.dtype != torch.float32 or x2.stride(1) != 1 or x2.stride(0) < x2.shape[1]:
+        x2 = _f32c(x2)
+    B, T_in = x2.shape
+    if torch.is_tensor(ratio):
+        r = _f32c(ratio.to(x2.device)).reshape(-1)
+    else:
+        r = torch.full((B,), float(ratio), dtype=torch.float32, device=x2.device)
+    if r.numel() != B:
+        raise ValueError(f"{name}: {r.numel()} ratios for {B} clips")
+    if out is None:
+        out = torch.empty((B, out_len), dtype=torch.float32, device=x2.device)
+    elif (out.dtype != torch.float32 or out.device != x2.device or tuple(out.shape) != (B, out_len)
+          or out.stride(1) != 1 or out.stride(0) < out_len):
+        raise ValueError(f"{name}: `out` must be a (B, out_len) f32 device tensor with unit column stride")
+    return x2, r, out, squeeze, B, T_in
+
+
+# ------------------------------------------------------------------------------------------------
 # speed augmentation (csrc/speed.hip): every clip resampled by its own ratio, read on the device
 # ------------------------------------------------------------------------------------------------
 def speed_pad(max_ratio):
@@ -493,21 +543,7 @@ def speed_input_len(out_len, max_ratio):
 def speed_config(cfg):
     """The speed keys of a configuration, validated: -> (speed_prob, lo, hi), or None when speed augmentation is off
     (speed_prob absent or 0).  speed_range = [lo, hi] with 0.5 <= lo <= hi <= 2 is required when it is on."""
-    prob, rng = cfg.get("speed_prob"), cfg.get("speed_range")
-    prob = 0.0 if prob is None else float(prob)
-    if not 0.0 <= prob <= 1.0:
-        raise ValueError(f"speed_prob = {prob} is not a probability")
-    if rng is not None:
-        if not isinstance(rng, (list, tuple)) or len(rng) != 2:
-            raise ValueError(f"speed_range = {rng!r} must be [lo, hi]")
-        lo, hi = float(rng[0]), float(rng[1])
-        if not 0.5 <= lo <= hi <= 2.0:
-            raise ValueError(f"speed_range = {rng!r} must satisfy 0.5 <= lo <= hi <= 2")
-    if prob == 0.0:
-        return None
-    if rng is None:
-        raise ValueError("speed_prob > 0 needs speed_range = [lo, hi]")
-    return prob, lo, hi
+    return _ratio_config(cfg, "speed")
 
 
 def speed_change(x, ratio, out_len, x_offset=0, out=None):
@@ -517,30 +553,12 @@ def speed_change(x, ratio, out_len, x_offset=0, out=None):
     copy) -- or one number for all clips; output m reads the input at x_offset + m * ratio, zeros outside the row.
     -> (B, out_len) f32 (`out`: written in place, rows may be strided).  The ratios are read on the device: no host
     synchronisation, so the launch can be captured into a HIP graph."""
-    _require_gpu(x, ratio if torch.is_tensor(ratio) else None, out)
-    squeeze = x.dim() == 1
-    x2 = x.detach().reshape(1, -1) if squeeze else x.detach()
-    if x2.dim() != 2:
-        raise ValueError("speed_change: x must be (B, T_in) or (T_in,)")
-    if x2.dtype != torch.float32 or x2.stride(1) != 1 or x2.stride(0) < x2.shape[1]:
-        x2 = _f32c(x2)
-    B, T_in = x2.shape
     out_len = int(out_len)
-    if torch.is_tensor(ratio):
-        r = _f32c(ratio.to(x2.device)).reshape(-1)
-    else:
-        r = torch.full((B,), float(ratio), dtype=torch.float32, device=x2.device)
-    if r.numel() != B:
-        raise ValueError(f"speed_change: {r.numel()} ratios for {B} clips")
-    if out is None:
-        out = torch.empty((B, out_len), dtype=torch.float32, device=x2.device)
-    elif (out.dtype != torch.float32 or out.device != x2.device or tuple(out.shape) != (B, out_len)
-          or out.stride(1) != 1 or out.stride(0) < out_len):
-        raise ValueError("speed_change: `out` must be a (B, out_len) f32 device tensor with unit column stride")
+    x2, r, out, squeeze, B, T_in = _warp_args("speed_change", x, ratio, out_len, out)
     with _timed("speed_change", (B, T_in, out_len)):
         check(lib.grafp_speed_change_f32(_p(x2), x2.stride(0), B, T_in, int(x_offset), _p(r), _p(out), out.stride(0),
                                          out_len, _stream()), "speed_change")
-    return out[0] if squeeze and out.dim() == 2 else out
+    return out[0] if squeeze else out
 
 
 # ------------------------------------------------------------------------------------------------
@@ -573,21 +591,26 @@ def stretch_input_len(out_len, max_ratio):
 def stretch_config(cfg):
     """The stretch keys of a configuration, validated: -> (stretch_prob, lo, hi), or None when time-stretch augmentation
     is off (stretch_prob absent or 0).  stretch_range = [lo, hi] with 0.5 <= lo <= hi <= 2 is required when it is on."""
-    prob, rng = cfg.get("stretch_prob"), cfg.get("stretch_range")
-    prob = 0.0 if prob is None else float(prob)
-    if not 0.0 <= prob <= 1.0:
-        raise ValueError(f"stretch_prob = {prob} is not a probability")
-    if rng is not None:
-        if not isinstance(rng, (list, tuple)) or len(rng) != 2:
-            raise ValueError(f"stretch_range = {rng!r} must be [lo, hi]")
-        lo, hi = float(rng[0]), float(rng[1])
-        if not 0.5 <= lo <= hi <= 2.0:
-            raise ValueError(f"stretch_range = {rng!r} must satisfy 0.5 <= lo <= hi <= 2")
-    if prob == 0.0:
-        return None
-    if rng is None:
-        raise ValueError("stretch_prob > 0 needs stretch_range = [lo, hi]")
-    return prob, lo, hi
+    return _ratio_config(cfg, "stretch")
+
+
+# what the training views need with the two augmentations on or off: the transform and the corpus both take it from here
+ViewPlan = collections.namedtuple("ViewPlan", "speed stretch clip speed_pad speed_len stretch_pad pad draw_len on")
+
+
+def view_plan(cfg):
+    """The geometry of the training views, from the speed and stretch keys (both pairs validated): the second view is
+    stretched, then sped up (GPUTransformNeuralfp.train_transform), so draw_len samples are drawn per view, time_stretch
+    turns them into speed_len and speed_change into clip; the first view's clip starts pad = stretch_pad + speed_pad
+    samples into its draw.  speed / stretch: (prob, lo, hi) or None; on: "stretch and speed", "stretch", "speed" or "".
+    clip (and with it speed_len and draw_len) is None when both are off and cfg has no 'dur'."""
+    speed, stretch = speed_config(cfg), stretch_config(cfg)
+    clip = int(cfg["fs"] * cfg["dur"]) if speed or stretch or "dur" in cfg else None
+    speed_len = speed_input_len(clip, speed[2]) if speed else clip
+    sp, st = speed_pad(speed[2]) if speed else 0, stretch_pad(stretch[2]) if stretch else 0
+    draw_len = stretch_input_len(speed_len, stretch[2]) if stretch else speed_len
+    on = " and ".join(n for n, c in (("stretch", stretch), ("speed", speed)) if c)
+    return ViewPlan(speed, stretch, clip, sp, speed_len, st, st + sp, draw_len, on)
 
 
 def time_stretch(x, ratio, out_len, x_offset=0, out=None, return_shifts=False):
@@ -598,32 +621,14 @@ def time_stretch(x, ratio, out_len, x_offset=0, out=None, return_shifts=False):
     row.  -> (B, out_len) f32 (`out`: written in place, rows may be strided); with return_shifts=True also the
     (B, stretch_frames(out_len)) int32 shifts delta_i of the frames, which say where the splices are.  The ratios are
     read on the device: no host synchronisation, so the launch can be captured into a HIP graph."""
-    _require_gpu(x, ratio if torch.is_tensor(ratio) else None, out)
-    squeeze = x.dim() == 1
-    x2 = x.detach().reshape(1, -1) if squeeze else x.detach()
-    if x2.dim() != 2:
-        raise ValueError("time_stretch: x must be (B, T_in) or (T_in,)")
-    if x2.dtype != torch.float32 or x2.stride(1) != 1 or x2.stride(0) < x2.shape[1]:
-        x2 = _f32c(x2)
-    B, T_in = x2.shape
     out_len = int(out_len)
-    if torch.is_tensor(ratio):
-        r = _f32c(ratio.to(x2.device)).reshape(-1)
-    else:
-        r = torch.full((B,), float(ratio), dtype=torch.float32, device=x2.device)
-    if r.numel() != B:
-        raise ValueError(f"time_stretch: {r.numel()} ratios for {B} clips")
-    if out is None:
-        out = torch.empty((B, out_len), dtype=torch.float32, device=x2.device)
-    elif (out.dtype != torch.float32 or out.device != x2.device or tuple(out.shape) != (B, out_len)
-          or out.stride(1) != 1 or out.stride(0) < out_len):
-        raise ValueError("time_stretch: `out` must be a (B, out_len) f32 device tensor with unit column stride")
+    x2, r, out, squeeze, B, T_in = _warp_args("time_stretch", x, ratio, out_len, out)
     shifts = torch.empty((B, stretch_frames(out_len)), dtype=torch.int32, device=x2.device) if return_shifts else None
     with _timed("time_stretch", (B, T_in, out_len)):
         check(lib.grafp_time_stretch_f32(_p(x2), x2.stride(0), B, T_in, int(x_offset), _p(r), _p(out), out.stride(0),
                                          out_len, _p(shifts), shifts.stride(0) if return_shifts else 0, _stream()),
               "time_stretch")
-    if squeeze and out.dim() == 2:
+    if squeeze:
         out, shifts = out[0], (shifts[0] if return_shifts else None)
     return (out, shifts) if return_shifts else out
 

@@ -11,7 +11,7 @@ WMAX = 13                                 # SP_WMAX
 
 
 def clamp_ratio(r):
-    """The kernel's sp_ratio on an f32: NaN -> 1, then [0.5, 2]."""
+    """The kernels' warp_ratio (csrc/clipwarp.h) on an f32: NaN -> 1, then [0.5, 2]."""
     r = F(r)
     if r != r:
         return F(1.0)

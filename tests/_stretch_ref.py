@@ -25,7 +25,7 @@ Stretch = namedtuple("Stretch", "out shifts corr bound lead first")
 
 
 def clamp_ratio(r):
-    """The kernel's st_ratio on an f32: NaN -> 1, then [0.5, 2]."""
+    """The kernels' warp_ratio (csrc/clipwarp.h) on an f32: NaN -> 1, then [0.5, 2]."""
     r = F32(r)
     if r != r:
         return F32(1.0)

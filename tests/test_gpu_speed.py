@@ -11,10 +11,10 @@ import torch
 
 from _corpus_ref import draw_pairs_ref
 from _speed_ref import SMALL_RATIOS, batch_refs, clamp_ratio, uniform_rows
+from _warp_views import _cfg, _noise_bank, _tracks, _views
 from grafp_amd import data, ops
 from grafp_amd.modules.transformations import GPUTransformNeuralfp
 from grafp_amd.train import Trainer, build_model, synthetic_batch
-from grafp_amd.util import load_config
 
 pytestmark = pytest.mark.gpu
 T_OUT = 700                           # not a multiple of the kernel's 1024-output tile, nor of its 256 threads
@@ -142,14 +142,6 @@ def test_captured_launch_reads_the_ratios_at_replay(dev, small):
 
 
 # ---- the second view's transform ---------------------------------------------------------------------------------
-def _cfg(**kw):
-    return dict(load_config(), **kw)
-
-
-def _noise_bank():
-    return 0.1 * torch.randn(3, 20000, generator=torch.Generator().manual_seed(31))
-
-
 def test_transform_off_is_the_module_without_the_keys(dev):
     x_i, x_j = synthetic_batch(8, 5, dev)
     outs = []
@@ -161,12 +153,6 @@ def test_transform_off_is_the_module_without_the_keys(dev):
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
     assert torch.equal(outs[0][2], outs[1][2])
     assert not torch.equal(outs[0][1], t.logmelspec(x_j))                 # the noise was mixed in: draws were made
-
-
-def _views(B, L, dev, seed=6):
-    g = torch.Generator().manual_seed(seed)
-    x = 0.1 * torch.randn(B, L, generator=g)
-    return x.to(dev), (x + 0.03 * torch.randn(B, L, generator=g)).to(dev)
 
 
 def test_transform_with_a_fixed_ratio_is_speed_change_then_logmel(dev):
@@ -215,11 +201,6 @@ def test_transform_keeps_about_speed_prob_of_the_clips(dev):
 
 
 # ---- the corpus draw -----------------------------------------------------------------------------------------------
-def _tracks(lengths, seed):
-    g = torch.Generator().manual_seed(seed)
-    return [0.2 * torch.randn(n, generator=g) for n in lengths]
-
-
 def test_corpus_draws_both_views_at_draw_len(dev):
     cfg = _cfg(speed_prob=0.7, speed_range=[0.94, 1.06])
     fs = cfg["fs"]

@@ -15,10 +15,10 @@ import torch
 
 from _stretch_ref import (LONG_RATIOS, LONG_TAIL, SMALL_RATIOS, T_SMALL, check_shifts, clamp_ratio, frames, long_case,
                           small_cases, stretch_f32, stretch_f64, tie_case)
+from _warp_views import _cfg, _noise_bank, _tracks, _views
 from grafp_amd import data, ops
 from grafp_amd.modules.transformations import GPUTransformNeuralfp
 from grafp_amd.train import Trainer, build_model, synthetic_batch
-from grafp_amd.util import load_config
 
 pytestmark = pytest.mark.gpu
 NF = frames(T_SMALL)                   # 7
@@ -181,22 +181,8 @@ def test_captured_launch_reads_the_ratios_at_replay(dev):
 
 
 # ---- the second view's transform ---------------------------------------------------------------------------------
-def _cfg(**kw):
-    return dict(load_config(), **kw)
-
-
 STRETCH = {"stretch_prob": 1.0, "stretch_range": [0.94, 1.06]}
 SPEED = {"speed_prob": 1.0, "speed_range": [0.94, 1.06]}
-
-
-def _noise_bank():
-    return 0.1 * torch.randn(3, 20000, generator=torch.Generator().manual_seed(31))
-
-
-def _views(B, L, dev, seed=6):
-    g = torch.Generator().manual_seed(seed)
-    x = 0.1 * torch.randn(B, L, generator=g)
-    return x.to(dev), (x + 0.03 * torch.randn(B, L, generator=g)).to(dev)
 
 
 def test_transform_off_is_the_module_without_the_keys(dev):
@@ -275,11 +261,6 @@ def test_transform_aug_seed_repeats_the_ratios(dev):
 
 
 # ---- the corpus draw -----------------------------------------------------------------------------------------------
-def _tracks(lengths, seed):
-    g = torch.Generator().manual_seed(seed)
-    return [0.2 * torch.randn(n, generator=g) for n in lengths]
-
-
 def test_corpus_draws_both_views_at_draw_len(dev):
     cfg = _cfg(stretch_prob=0.7, stretch_range=[0.94, 1.06])
     fs = cfg["fs"]

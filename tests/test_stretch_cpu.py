@@ -233,7 +233,10 @@ def test_entry_reports_argument_errors_without_a_gpu():
                        ((one, 10, 1, 10, 0, one, one * 2, 9, 10, None, 0, None), b"row strides"),
                        ((one, 10, 1, 10, 0, one, one * 2, 300, 300, one * 3, 2, None), b"shift row stride"),
                        ((one, 10, 1, 10, 0, one, one, 10, 10, None, 0, None), b"alias"),
-                       ((one, 10, 1, 10, -1, one, one * 2, 10, 10, None, 0, None), b"x_offset")):
+                       ((one, 10, 1, 10, -1, one, one * 2, 10, 10, None, 0, None), b"x_offset"),
+                       # two faults at once: the checks shared with speed_change (csrc/clipwarp.h) come before the shift's
+                       ((one, 300, 1, 300, 0, one, one, 300, 300, one * 3, 2, None), b"alias"),
+                       ((one, 300, 1, 300, -1, one, one * 2, 300, 300, one * 3, 2, None), b"x_offset")):
         assert lib.grafp_time_stretch_f32(*args) == -1 and what in lib.grafp_last_error(), what
 
 
