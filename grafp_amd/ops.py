@@ -319,9 +319,32 @@ def _i32c(t, device):
     return t.detach().to(device=device, dtype=torch.int32).contiguous()
 
 
-def _bank(bank, lens, device, starts=None):
+def _host_ints(t):
+    """The values of a HOST tensor as an int64 array; None for a device tensor, which is never read back (no
+    synchronisation: the augmentation ops stay graph-capturable, and their caller vouches for what lives on the device)."""
+    return None if t.is_cuda else t.detach().reshape(-1).to(torch.int64).numpy()
+
+
+def _bank(name, bank, lens, device, starts=None):
     """(flat f32 buffer, int64 starts, int32 lengths) of a recording bank.  bank: a flat 1-D buffer with `starts`, or a
-    2-D (n, Lmax) array whose row r holds recording r in its first lens[r] elements."""
+    2-D (n, Lmax) array whose row r holds recording r in its first lens[r] elements.  Refuses (ValueError) a bank
+    without its tables and, where lens / starts are host tensors, a recording that is empty or leaves the bank."""
+    if bank.dim() not in (1, 2):
+        raise ValueError(f"{name}: the bank must be a flat buffer with `starts` or a padded (n, Lmax) array")
+    if bank.dim() == 1 and starts is None:
+        raise ValueError(f"{name}: a flat bank needs the `starts` of its recordings")
+    n = int(bank.shape[0]) if bank.dim() == 2 else int(starts.numel())
+    if n == 0 or int(lens.numel()) != n:
+        raise ValueError(f"{name}: {int(lens.numel())} lengths for {n} recordings (at least one, as many of each)")
+    ln = _host_ints(lens)
+    if bank.dim() == 2:
+        st, room = None, int(bank.shape[1])
+    else:
+        st, room = _host_ints(starts), int(bank.numel())
+    if (ln is not None and (ln < 1).any()) or (st is not None and (st < 0).any()):
+        raise ValueError(f"{name}: a recording needs a length >= 1 and a start >= 0")
+    if (ln is not None or st is not None) and ((0 if st is None else st) + (1 if ln is None else ln) > room).any():
+        raise ValueError(f"{name}: a recording ends beyond the bank")
     bank = _f32c(bank)
     lens = _i32c(lens, device)
     if bank.dim() == 2:
@@ -332,15 +355,37 @@ def _bank(bank, lens, device, starts=None):
     return bank, starts, lens
 
 
+def _aug_rows(name, x):
+    """x as contiguous f32 (B, T) rows, and whether it came as one (T,) signal."""
+    if x.dim() not in (1, 2):
+        raise ValueError(f"{name}: x must be (B, T) or (T,)")
+    return _f32c(x.reshape(1, -1) if x.dim() == 1 else x), x.dim() == 1
+
+
+def _per_clip(name, what, t, B, below=None, floor=None):
+    """A per-clip argument has B entries; the values of a host tensor lie below `below` (indices: a negative one is
+    legal, it skips the clip) and at or above `floor` (offsets, which must also fit the kernel's int32)."""
+    if int(t.numel()) != B:
+        raise ValueError(f"{name}: {int(t.numel())} entries in `{what}` for {B} clips")
+    v = None if below is None and floor is None else _host_ints(t)
+    if v is not None and below is not None and (v >= below).any():
+        raise ValueError(f"{name}: `{what}` must be below the {below} recordings")
+    if v is not None and floor is not None and ((v < floor) | (v >= 2 ** 31)).any():
+        raise ValueError(f"{name}: `{what}` must be >= {floor} and fit 32 bits")
+
+
 def ir_convolve(x, ir_bank, ir_len, ir_index=None, ir_start=None):
     """ApplyImpulseResponse for a batch: x (B,T) f32; the impulse responses as a ragged bank (flat buffer + ir_start
     + ir_len) or a padded (n_ir, Lmax) array + ir_len; ir_index (B) recording per signal (< 0: copied unchanged;
-    None: recording 0) -> (B,T), the full convolution truncated to T (grafp_ir_convolve_f32)."""
+    None: recording 0) -> (B,T), the full convolution truncated to T (grafp_ir_convolve_f32).
+    Shapes and counts are checked, and so are the values of lens / starts / ir_index where they are HOST tensors
+    (ValueError); device tensors are not read back, their caller vouches that they lie inside the bank."""
     _require_gpu(x, ir_bank)
-    squeeze = x.dim() == 1
-    x2 = _f32c(x.reshape(1, -1) if squeeze else x)
-    bank, starts, lens = _bank(ir_bank, ir_len, x2.device, ir_start)
+    x2, squeeze = _aug_rows("ir_convolve", x)
+    bank, starts, lens = _bank("ir_convolve", ir_bank, ir_len, x2.device, ir_start)
     B, T = x2.shape
+    if ir_index is not None:
+        _per_clip("ir_convolve", "ir_index", ir_index, B, below=lens.numel())
     out = torch.empty_like(x2)
     idx = None if ir_index is None else _i32c(ir_index, x2.device)   # (locals: a temporary's block could be re-used)
     check(lib.grafp_ir_convolve_f32(_p(x2), T, B, T, _p(bank), _p(starts), lens.numel(), _p(lens), _p(idx), _p(out), T,
@@ -351,12 +396,15 @@ def ir_convolve(x, ir_bank, ir_len, ir_index=None, ir_start=None):
 def mix_snr(x, noise_bank, noise_len, noise_index, noise_offset, snr_db, noise_start=None):
     """AddBackgroundNoise for a batch: out = x + rms(x)/10^(snr/20) * n/(rms(n)+1e-8) with n the circular read of
     recording noise_index[b] (ragged bank: flat buffer + noise_start + noise_len, or a padded (n, Lmax) array) from
-    noise_offset[b]; noise_index < 0: copied unchanged (grafp_mix_snr_f32)."""
+    noise_offset[b] (any offset >= 0: the kernel reduces it mod the length); noise_index < 0: copied unchanged
+    (grafp_mix_snr_f32).  Checked as ir_convolve's arguments are: counts always, values where the tensor is on the host."""
     _require_gpu(x, noise_bank)
-    squeeze = x.dim() == 1
-    x2 = _f32c(x.reshape(1, -1) if squeeze else x)
-    bank, starts, lens = _bank(noise_bank, noise_len, x2.device, noise_start)
+    x2, squeeze = _aug_rows("mix_snr", x)
+    bank, starts, lens = _bank("mix_snr", noise_bank, noise_len, x2.device, noise_start)
     B, T = x2.shape
+    _per_clip("mix_snr", "noise_index", noise_index, B, below=lens.numel())
+    _per_clip("mix_snr", "noise_offset", noise_offset, B, floor=0)
+    _per_clip("mix_snr", "snr_db", snr_db, B)
     out = torch.empty_like(x2)
     nbytes = lib.grafp_mix_snr_workspace(B, T)
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=x2.device)
