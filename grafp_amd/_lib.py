@@ -137,6 +137,7 @@ SIGNATURES = {
     "grafp_cross_match_tempo_workspace": (_Z, [_P, _I, _I, _I, _I, _I]),
     "grafp_self_match_tempo_f32": (_I, [_P, _L, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _Z, _P, _P, _P, _P, _P,
                                         _P, _P, _P]),
+    "grafp_merge_track_lists_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
 }
 
 

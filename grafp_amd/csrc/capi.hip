@@ -357,6 +357,22 @@ extern "C" int grafp_self_match_tempo_f32(const float *index_rows, int64_t n, co
                                           (hipStream_t)stream);
 }
 
+// The merge of the lists that the shards of a library return for the same items (merge_lists.hip): the limits, the host
+// tables and the launch are all there.
+namespace grafp {
+int merge_track_lists_launch(const int32_t *track, const float *score, const int32_t *payload, int n_lists, int n_items,
+                             int top, int n_payload, const int32_t *track_base, const int32_t *pad, int32_t *out_track,
+                             float *out_score, int32_t *out_payload, hipStream_t stream);
+}  // namespace grafp
+
+extern "C" int grafp_merge_track_lists_f32(const int32_t *track, const float *score, const int32_t *payload, int n_lists,
+                                           int n_items, int top, int n_payload, const int32_t *track_base,
+                                           const int32_t *pad, int32_t *out_track, float *out_score,
+                                           int32_t *out_payload, grafp_stream_t stream) {
+    return grafp::merge_track_lists_launch(track, score, payload, n_lists, n_items, top, n_payload, track_base, pad,
+                                           out_track, out_score, out_payload, (hipStream_t)stream);
+}
+
 // The front end of live multi-channel monitoring (stream_frontend.hip): argument checks here, the kernels there.  The
 // per-channel tables are device data: the caller (ops.stream_logmel) checks them on the host before it uploads them.
 namespace grafp {

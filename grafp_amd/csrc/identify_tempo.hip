@@ -42,13 +42,6 @@ namespace grafp {
 // row pairs in flight in the score loop: query rows in LDS / in global memory (identify.hip's counts)
 constexpr int IDR_UNROLL_QLDS = 4, IDR_UNROLL_QGLOBAL = 1;
 
-// slots of one item's merge: the power of two >= max(64, R * top), at most 4096 (host: R <= 64, top <= 64)
-__host__ __device__ inline int merge_slots(int R, int top) {
-    int P = 64;
-    while (P < R * top) P <<= 1;
-    return P;
-}
-
 template <bool kQLds>
 __global__ __launch_bounds__(ID_THREADS) void identify_tempo_kernel(
     const float *__restrict__ rows, int64_t n, const int64_t *__restrict__ first, int T, TempoRatios ratios,

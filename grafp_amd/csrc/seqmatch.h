@@ -117,6 +117,14 @@ inline int tempo_ratios(const char *name, const int32_t *ratio_num, int n_ratios
     return GRAFP_OK;
 }
 
+// slots of one item's merge of R lists of `top` entries (identify_tempo.hip: one list per ratio; merge_lists.hip: one per
+// shard): the power of two >= max(64, R * top), at most 4096 (host: R <= 64, top <= 64), 10 bytes of LDS each
+__host__ __device__ inline int merge_slots(int R, int top) {
+    int P = 64;
+    while (P < R * top) P <<= 1;
+    return P;
+}
+
 // host: reserves `lds` bytes of dynamic LDS for a kernel and launches it (name: for the messages)
 template <typename... Params, typename... Args>
 inline int seq_launch(const char *name, void (*kernel)(Params...), dim3 grid, int threads, size_t lds,

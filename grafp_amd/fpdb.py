@@ -23,6 +23,10 @@ def _embed(model, x):
 
 def _write_memmap(path_noext, arr):
     shape = (len(arr), arr.shape[-1])
+    if shape[0] == 0:                      # (np.memmap cannot map an empty file: a library or shard without rows)
+        open(path_noext + ".mm", "wb").close()
+        np.save(path_noext + "_shape.npy", shape)
+        return
     mm = np.memmap(path_noext + ".mm", dtype="float32", mode="w+", shape=shape)
     mm[:] = arr[:]
     mm.flush()

@@ -2,7 +2,7 @@
 
   python -m grafp_amd.identify build --config CFG --ckp MODEL.pth --source DIR|JSON|FILES... --out LIBDIR [--precision]
                                        [--index flat|ivfpq --nlist 64 --pq-m 64 --nprobe 20 --train-rows 65536]
-                                       [--row-stride D]
+                                       [--row-stride D] [--shards N [--devices cuda:0,cuda:1]]
   python -m grafp_amd.identify query --ckp MODEL.pth --library LIBDIR FILES... [--top 5] [--window S --hop S]
                                        [--tempo X [--tempo-step G]]
   python -m grafp_amd.identify dedup --ckp MODEL.pth --library LIBDIR [--min-overlap 3] [--coverage 0.9] [--json OUT]
@@ -29,7 +29,10 @@ also finds the tracks of the library that share audio at another speed -- a sped
 every printed pair then also carries "tempo", "tempo_num" and "b_overlap_s" (--tempo-step defaults to 1).  `monitor` treats every file as one live channel: it feeds them to a
 StreamMonitor (grafp_amd/monitor.py) chunk by chunk, all channels per push, prints one JSON object per window as it
 becomes due ({"channel", "file", start_s, end_s, segment_start_s, matches}) and, when the files end, one per timeline
-span of each channel ({"channel", "file", "span": ...})."""
+span of each channel ({"channel", "file", "span": ...}).  build --shards N writes a sharded library
+(grafp_amd/sharded.py: N flat shards over contiguous track ranges, shard s on the s-th of --devices, all on one device
+without it); `query`, `match` and `monitor` load a directory that holds shards.json as one (--devices again says where
+the shards go) and answer as the one-card library would; `dedup` across shards is not built."""
 import argparse
 import json
 import sys
@@ -65,6 +68,8 @@ def main(argv=None):
     b.add_argument("--train-rows", type=int, default=65536, help="ivfpq: rows the quantiser is trained on")
     b.add_argument("--row-stride", type=int, default=1,
                    help="flat: keep every D-th fingerprint row of each track (1..32); queries stay dense")
+    b.add_argument("--shards", type=int, default=None, help="flat: write a library of this many shards")
+    b.add_argument("--devices", default=None, help="--shards: the shards' devices, comma-separated (cuda:0,cuda:1)")
     q = sub.add_parser("query", help="identify recordings against a library")
     q.add_argument("--config", default=DEFAULT_CONFIG, help="model configuration (the library keeps its own "
                                                             "segmentation settings)")
@@ -79,6 +84,7 @@ def main(argv=None):
                    help="also search recordings that play up to this fraction faster or slower (0.06: 0.94 to 1.06)")
     q.add_argument("--tempo-step", type=int, default=None, help="spacing of the ratios searched, in 1/256")
     q.add_argument("--force", action="store_true", help="use a library made with another model")
+    q.add_argument("--devices", default=None, help="a sharded library: its shards' devices, comma-separated")
     d = sub.add_parser("dedup", help="find tracks of a library that share audio")
     d.add_argument("--config", default=DEFAULT_CONFIG, help="model configuration (the library keeps its own "
                                                             "segmentation settings)")
@@ -109,6 +115,7 @@ def main(argv=None):
                    help="also match recordings that play up to this fraction faster or slower (0.06: 0.94 to 1.06)")
     m.add_argument("--tempo-step", type=int, default=None, help="spacing of the ratios searched, in 1/256 (default 1)")
     m.add_argument("--force", action="store_true", help="use a library made with another model")
+    m.add_argument("--devices", default=None, help="a sharded library: its shards' devices, comma-separated")
     mo = sub.add_parser("monitor", help="follow files as live channels, chunk by chunk")
     mo.add_argument("--config", default=DEFAULT_CONFIG, help="model configuration (the library keeps its own "
                                                              "segmentation settings)")
@@ -122,16 +129,30 @@ def main(argv=None):
     mo.add_argument("--k-probe", type=int, default=20)
     mo.add_argument("--min-score", type=float, default=None, help="timeline: drop windows whose best match is weaker")
     mo.add_argument("--force", action="store_true", help="use a library made with another model")
+    mo.add_argument("--devices", default=None, help="a sharded library: its shards' devices, comma-separated")
     args = ap.parse_args(argv)
 
     from .data import DeviceAudioCorpus
     from .library import FingerprintLibrary
-    device = torch.device("cuda")
+    from .sharded import ShardedFingerprintLibrary
+    devices = args.devices.split(",") if getattr(args, "devices", None) else None
+    device = torch.device(devices[0] if devices else "cuda")
     cfg = load_config(args.config)
     model = _model(cfg, args.ckp, device)
     if args.cmd == "build":
         source = args.source[0] if len(args.source) == 1 else args.source
         corpus = DeviceAudioCorpus(cfg, source, device)
+        if args.shards is not None or devices:
+            if args.index != "flat":
+                sys.exit("build --shards needs --index flat: compact shards are not built")
+            lib = ShardedFingerprintLibrary.build(model, corpus, cfg, n_shards=args.shards, devices=devices,
+                                                  precision=args.precision, max_segments=args.max_segments,
+                                                  row_stride=args.row_stride)
+            lib.save(args.out)
+            print(json.dumps({"library": args.out, "index": "flat", "shards": len(lib.shards),
+                              "row_stride": lib.row_stride, "tracks": lib.n_tracks, "rows": lib.n_rows,
+                              "rows_per_shard": [sh.n_rows for sh in lib.shards], "bytes": lib.nbytes}))
+            return 0
         lib = FingerprintLibrary.build(model, corpus, cfg, precision=args.precision, max_segments=args.max_segments,
                                        index=args.index, nlist=args.nlist, pq_m=args.pq_m, nprobe=args.nprobe,
                                        train_rows=args.train_rows, row_stride=args.row_stride)
@@ -140,7 +161,13 @@ def main(argv=None):
         print(json.dumps({"library": args.out, "index": args.index, **stride, "tracks": lib.n_tracks,
                           "rows": lib.n_rows, "bytes": lib.nbytes}))
         return 0
-    lib = FingerprintLibrary.load(args.library, model, device, force=args.force)
+    if ShardedFingerprintLibrary.is_sharded_dir(args.library):
+        if args.cmd == "dedup":
+            sys.exit(f"{args.library}: dedup across the shards of a sharded library is not built "
+                     "(ShardedFingerprintLibrary.self_matches)")
+        lib = ShardedFingerprintLibrary.load(args.library, model, devices, force=args.force)
+    else:
+        lib = FingerprintLibrary.load(args.library, model, device, force=args.force)
     if args.cmd in ("dedup", "match") and lib.row_stride != 1:
         sys.exit(f"{args.library}: {args.cmd} needs every row of a track: this library keeps every {lib.row_stride}th "
                  f"(row_stride={lib.row_stride})")

@@ -32,7 +32,12 @@ match() takes whole recordings of any length that are NOT in the library and say
 where and how much (spans, coverage, votes: what self_matches says about the library's own tracks) -- the question an
 ingest gate asks before add().  It runs on ops.cross_match (f32 rows) or ops.cross_match_pq (codes), the kernels of
 csrc/crossmatch.hip, and with tempo=... on ops.cross_match_tempo (csrc/crossmatch_tempo.hip): a DJ set pitched a few
-per cent or a sped-up re-upload is then one match along its sloped alignment, not fragments of diagonals."""
+per cent or a sped-up re-upload is then one match along its sloped alignment, not fragments of diagonals.
+
+A FingerprintLibrary lives on one device.  grafp_amd/sharded.py's ShardedFingerprintLibrary holds several flat ones over
+contiguous track ranges, one per device, and answers identify, identify_windows, timeline and match with exactly what
+the one library over the same tracks would: every shard runs the ops above unchanged (_identify_lists, _match_launch)
+and ops.merge_track_lists (csrc/merge_lists.hip) merges their lists on the device."""
 import hashlib
 import json
 import math
@@ -640,24 +645,11 @@ class FingerprintLibrary:
         if n_items == 0 or longest == 0:
             return [[] for _ in range(n_items)]
         max_len = longest if max_len is None else max(int(max_len), longest)
-        dev = self.device
-        tail = (torch.from_numpy(self.first).to(dev), q, ids, torch.from_numpy(np.asarray(item_row, np.int64)).to(dev),
-                torch.from_numpy(np.asarray(item_len, np.int32)).to(dev))
-        ra = None
-        if tempo is not None:
-            nums = tempo_ratios(tempo, longest, tempo_step)
-            tr, off, sc, vo, ra = ops.identify_tempo(self.rows(), *tail, nums, top=top, min_overlap=min_overlap,
-                                                     max_len=max_len)
-            ra = ra.cpu().numpy()
-        elif self.is_compact:
-            tr, off, sc, vo = ops.identify_pq(*self.codes(), self._pq["centroids"], self._pq["codebooks"], *tail,
-                                              top=top, min_overlap=min_overlap, max_len=max_len)
-        elif self._row_stride != 1:
-            tr, off, sc, vo = ops.identify_thin(self.rows(), *tail, self._row_stride, top=top, min_overlap=min_overlap,
-                                                max_len=max_len)
-        else:
-            tr, off, sc, vo = ops.identify(self.rows(), *tail, top=top, min_overlap=min_overlap, max_len=max_len)
-        tr, off, sc, vo = (t.cpu().numpy() for t in (tr, off, sc, vo))
+        nums = None if tempo is None else tempo_ratios(tempo, longest, tempo_step)
+        lists = self._identify_lists(q, ids, np.asarray(item_row, np.int64), np.asarray(item_len, np.int32), top,
+                                     min_overlap, max_len, nums)
+        tr, off, sc, vo = (t.cpu().numpy() for t in lists[:4])
+        ra = lists[4].cpu().numpy() if nums is not None else None
         step, hop, fs = self.step, self.settings["hop_len"], self.settings["fs"]
         out = []
         for i in range(n_items):
@@ -674,6 +666,21 @@ class FingerprintLibrary:
                     res[-1]["tempo_num"] = int(ra[i, j])
             out.append(res)
         return out
+
+    def _identify_lists(self, q, ids, item_row, item_len, top, min_overlap, max_len, nums=None):
+        """The launch of _identify_items -> the op's device tensors (track, offset, score, votes and, with the ratio
+        grid nums, ratio), nothing read back.  (ShardedFingerprintLibrary runs one per shard and merges them.)"""
+        dev = self.device
+        tail = (torch.from_numpy(self.first).to(dev), q, ids, torch.from_numpy(item_row).to(dev),
+                torch.from_numpy(item_len).to(dev))
+        kw = dict(top=top, min_overlap=min_overlap, max_len=max_len)
+        if nums is not None:
+            return ops.identify_tempo(self.rows(), *tail, nums, **kw)
+        if self.is_compact:
+            return ops.identify_pq(*self.codes(), self._pq["centroids"], self._pq["codebooks"], *tail, **kw)
+        if self._row_stride != 1:
+            return ops.identify_thin(self.rows(), *tail, self._row_stride, **kw)
+        return ops.identify(self.rows(), *tail, **kw)
 
     def _need_tempo_form(self, what, tempo):
         if tempo is not None:
@@ -938,10 +945,8 @@ class FingerprintLibrary:
     def _match_rows(self, q, counts, k_probe, min_overlap_s, min_votes, min_score, top, batch_rows, nums=None):
         """match() from the recordings' rows on: q (n_q, 128) f32 on the device, counts the rows of each recording.
         nums: the ratio grid of match(tempo=...) (None: the dense kernels)."""
-        seg_s, dev = self.segment_s, self.device
+        seg_s = self.segment_s
         min_overlap = max(1, int(math.ceil(min_overlap_s / seg_s - 1e-9)))
-        k = min(k_probe, self.n_rows)
-        first_d = torch.from_numpy(self.first).to(dev)
         starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
         out = [[] for _ in counts]
         if nums is not None:
@@ -953,18 +958,9 @@ class FingerprintLibrary:
                 s1 += 1
             qb = q[int(starts[s0]):int(starts[s1])]
             if qb.shape[0]:
-                _, ids = self.index.search(qb, k)
-                src = torch.from_numpy(starts[s0:s1 + 1] - starts[s0])
-                kw = dict(top=top, min_votes=min_votes, min_overlap=min_overlap)
-                ra_ = None
-                if nums is not None:
-                    res = ops.cross_match_tempo(self.rows(), first_d, qb, src, ids, nums, **kw)
-                    ra_ = res[6].cpu().numpy()
-                elif self.is_compact:
-                    res = ops.cross_match_pq(*self.codes(), self._pq["centroids"], self._pq["codebooks"], first_d, qb,
-                                             src, ids, **kw)
-                else:
-                    res = ops.cross_match(self.rows(), first_d, qb, src, ids, **kw)
+                res = self._match_lists(qb, torch.from_numpy(starts[s0:s1 + 1] - starts[s0]), k_probe, nums,
+                                        dict(top=top, min_votes=min_votes, min_overlap=min_overlap))
+                ra_ = res[6].cpu().numpy() if nums is not None else None
                 b_, d_, lo_, m_, sc_, v_ = (x.cpu().numpy() for x in res[:6])
                 for s in range(s0, s1):
                     for j in range(b_.shape[1]):
@@ -981,6 +977,24 @@ class FingerprintLibrary:
                                                         None if ra_ is None else int(ra_[s - s0, j])))
             s0 = s1
         return out
+
+    def _match_lists(self, qb, src, k_probe, nums, kw):
+        """The search and the launch of one batch of _match_rows: qb the batch's rows, src its source table (a host
+        tensor) -> the op's device tensors (track, delta, start, length, score, votes and, with nums, ratio), nothing
+        read back."""
+        _, ids = self.index.search(qb, min(k_probe, self.n_rows))
+        return self._match_launch(qb, src, ids, nums, kw)
+
+    def _match_launch(self, qb, src, ids, nums, kw):
+        """The launch of _match_lists over the hits ids.  (ShardedFingerprintLibrary runs one per shard and merges
+        them.)"""
+        first_d = torch.from_numpy(self.first).to(self.device)
+        if nums is not None:
+            return ops.cross_match_tempo(self.rows(), first_d, qb, src, ids, nums, **kw)
+        if self.is_compact:
+            return ops.cross_match_pq(*self.codes(), self._pq["centroids"], self._pq["codebooks"], first_d, qb, src, ids,
+                                      **kw)
+        return ops.cross_match(self.rows(), first_d, qb, src, ids, **kw)
 
     @staticmethod
     def duplicate_groups(matches, min_coverage=0.9, min_score=DUPLICATE_MIN_SCORE):

@@ -2377,6 +2377,65 @@ def cross_match_pq(list_id, codes, centroids, codebooks, track_first_row, q_rows
     return outs
 
 
+MERGE_LISTS_MAX, MERGE_LISTS_MAX_SLOTS, MERGE_LISTS_MAX_PAYLOAD = 64, 4096, 6      # merge_lists.hip's limits
+
+
+def merge_track_lists(track, score, payload, track_base, pad, top=None):
+    """One list per item from the lists that S shards of a library returned for the same items
+    (grafp_merge_track_lists_f32, one workgroup per item; grafp_amd/sharded.py).  Shard s owns the global tracks
+    [track_base[s], track_base[s + 1]) and its lists are in the form the identify and match ops write:
+    track (S, n_items, L) int32 shard-local track numbers (negative: padding), score (S, n_items, L) f32, payload
+    (P, S, n_items, L) int32 the ops' other outputs (identify: offset, votes; identify_tempo: also ratio; cross_match:
+    delta, start, length, votes; cross_match_tempo: also ratio; None: P = 0).  track_base: S host ints, non-negative and
+    ascending; pad: P host ints, the padding value of each payload.
+    The non-padding entries of an item are ranked by score descending, then global track (track_base[s] + track)
+    ascending.  Returns (track int32 (n_items, L) global, score f32 (n_items, L), payload int32 (P, n_items, L)), padded
+    with -1 / -inf / pad[p]; top (default L, at most L): only the first `top` columns of each.  An item with
+    cross_match's -2 mark in any entry gets track -2 in slot 0 and padding elsewhere.
+    Limits: 1 <= S <= 64, 1 <= L <= 64, S * L <= 4096, P <= 6.  Nothing is copied to the device and nothing is read
+    back: the call is asynchronous and capturable."""
+    if track.dim() != 3 or tuple(score.shape) != tuple(track.shape):
+        raise ValueError(f"merge_track_lists: track and score must both be (S, n_items, top), not "
+                         f"{tuple(track.shape)} and {tuple(score.shape)}")
+    S, n_items, L = (int(v) for v in track.shape)
+    P = 0 if payload is None else int(payload.shape[0])
+    if payload is not None and (payload.dim() != 4 or tuple(payload.shape[1:]) != (S, n_items, L)):
+        raise ValueError(f"merge_track_lists: payload must be (P, {S}, {n_items}, {L}), not {tuple(payload.shape)}")
+    if not 1 <= S <= MERGE_LISTS_MAX:
+        raise ValueError(f"merge_track_lists: S={S} lists per item, not 1 to {MERGE_LISTS_MAX}")
+    if not 1 <= L <= 64:
+        raise ValueError(f"merge_track_lists: lists of top={L} entries, not 1 to 64")
+    if S * L > MERGE_LISTS_MAX_SLOTS:
+        raise ValueError(f"merge_track_lists: S={S} lists x top={L} exceed the {MERGE_LISTS_MAX_SLOTS} slots of the merge")
+    if P > MERGE_LISTS_MAX_PAYLOAD:
+        raise ValueError(f"merge_track_lists: P={P} payloads, not 0 to {MERGE_LISTS_MAX_PAYLOAD}")
+    top = L if top is None else int(top)
+    if not 1 <= top <= L:
+        raise ValueError(f"merge_track_lists: top={top} not in [1, {L}], the length of the lists")
+    bases = [int(v) for v in np.asarray(track_base).reshape(-1)]
+    pads = [int(v) for v in np.asarray(pad).reshape(-1)]
+    if len(bases) != S or len(pads) != P:
+        raise ValueError(f"merge_track_lists: {len(bases)} track bases and {len(pads)} pads for S={S} and P={P}")
+    if bases[0] < 0 or any(b < a for a, b in zip(bases, bases[1:])) or bases[-1] >= 2 ** 31:
+        raise ValueError("merge_track_lists: track_base must be non-negative and ascending")
+    if any(not -2 ** 31 <= v < 2 ** 31 for v in pads):
+        raise ValueError("merge_track_lists: a pad is no int32")
+    _require_gpu(track, score, payload)
+    dev = track.device
+    track, score = track.to(torch.int32).contiguous(), _f32c(score)
+    payload = None if P == 0 else payload.to(torch.int32).contiguous()
+    out_t = torch.empty((n_items, L), dtype=torch.int32, device=dev)
+    out_s = torch.empty((n_items, L), dtype=torch.float32, device=dev)
+    out_p = torch.empty((P, n_items, L), dtype=torch.int32, device=dev)
+    if n_items:
+        c_bases, c_pads = (ctypes.c_int32 * S)(*bases), (ctypes.c_int32 * max(1, P))(*pads)   # read before the return
+        with _timed("merge_track_lists", (S, n_items, L, P)):
+            check(lib.grafp_merge_track_lists_f32(_p(track), _p(score), _p(payload), S, n_items, L, P,
+                                                  ctypes.cast(c_bases, _vp), ctypes.cast(c_pads, _vp), _p(out_t),
+                                                  _p(out_s), _p(out_p) if P else None, _stream()), "merge_track_lists")
+    return out_t[:, :top], out_s[:, :top], out_p[:, :, :top]
+
+
 class FlatL2Index:
     """Drop-in for the subset of faiss.IndexFlatL2 that eval.py uses: d, ntotal, add(x), search(q, k).
     The database lives in HBM; `add` also computes the per-row squared norms once."""

@@ -830,6 +830,27 @@ int grafp_self_match_tempo_f32(const float *index_rows, int64_t n, const int64_t
                                int32_t *out_track, int32_t *out_delta, int32_t *out_start, int32_t *out_len,
                                float *out_score, int32_t *out_votes, int32_t *out_ratio, grafp_stream_t stream);
 
+/* ---- one list from the lists of a library's shards (grafp_amd/sharded.py; merge_lists.hip) ------------------------
+ * grafp_merge_track_lists_f32 -- n_lists shards, each owning the global tracks [track_base[s], track_base[s + 1]), have
+ *   answered the same n_items items with a `top` list each, in the form the identify and cross-match entries write:
+ *   track (n_lists, n_items, top) int32, shard-local track numbers, negative = padding; score (n_lists, n_items, top)
+ *   f32; payload (n_payload, n_lists, n_items, top) int32, the producing entry's other outputs (offset and votes; delta,
+ *   start, length and votes; the ratio), carried along unread.  track_base (HOST, n_lists int32, non-negative,
+ *   ascending) and pad (HOST, n_payload int32, the padding value of each payload) are read before the call returns and
+ *   travel in the kernel arguments.
+ *   Per item the non-padding entries of its n_lists lists are ranked by score descending, then global track
+ *   (track_base[s] + track) ascending; the first `top` go out as out_track (global) and out_score (n_items, top) and
+ *   out_payload (n_payload, n_items, top), the rest of a list padded with -1 / -inf / pad[p].  The shards own disjoint
+ *   tracks, so with lists of length top the result is the one list an unsharded entry would have written.  If any entry
+ *   of an item carries track -2 (grafp_cross_match_f32's mark of a source outside its workspace), out_track of that
+ *   item's slot 0 is -2 and the rest of the item is padding.
+ *   One launch on `stream`, no host synchronisation, no float arithmetic; n_items = 0 launches nothing.
+ *   Limits: 1 <= n_lists <= 64, 1 <= top <= 64, n_lists * top <= 4096, 0 <= n_payload <= 6 (payload, pad and
+ *   out_payload may be null at 0); every global track number must fit an int32. */
+int grafp_merge_track_lists_f32(const int32_t *track, const float *score, const int32_t *payload, int n_lists,
+                                int n_items, int top, int n_payload, const int32_t *track_base, const int32_t *pad,
+                                int32_t *out_track, float *out_score, int32_t *out_payload, grafp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
