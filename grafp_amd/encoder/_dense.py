@@ -38,8 +38,9 @@ def conv1x1(conv, x):
     """1x1 Conv2d weights (any `groups`, bias NOT applied) on x (Cin,B,N) -> (Cout,B,N): one GEMM (a 4-batch GEMM
     for the grouped conv of the max-relative block)."""
     cin, B, N = x.shape
-    cout, g = conv.out_channels, conv.groups
-    return ops.conv1x1_rows(x.reshape(cin, B * N), conv.weight, g, getattr(conv, "_w_lowp", None)).reshape(cout, B, N)
+    prepared = getattr(conv, "_prepared", None)
+    lowp = None if prepared is None else prepared.lowp
+    return ops.conv1x1_rows(x.reshape(cin, B * N), conv.weight, conv.groups, lowp).reshape(conv.out_channels, B, N)
 
 
 # num_batches_tracked of every BatchNorm touched inside a `deferred_counters()` block advance with ONE multi-tensor
@@ -98,48 +99,46 @@ def _bn_training(bn, groups):
     return training, (0.0 if bn.momentum is None else bn.momentum)
 
 
+def _first_layer_rows(x, conv, groups):
+    """x (Cin, B, N) as the (Cin, B*N) rows the first layer `conv` will see; None if it does not take the fused bf16 path."""
+    x2 = ops.autocast_rows(x).reshape(x.shape[0], -1)
+    return x2 if ops.conv_bn_act_supported(x2, conv.out_channels, conv.groups, groups) else None
+
+
 def deferred_norm(x, prod_conv, prod_bn, cons_conv, cons_bn, groups=1):
     """An ops.DeferredNorm for  x -> [prod_conv, prod_bn, act] -> [cons_conv, cons_bn ...]  when the first layer's output
     feeds only the second, both take the fused bf16 path in training mode and the measured rule says it pays."""
-    if not (prod_bn.training and cons_bn.training and cons_conv.groups == 1):
-        return None
-    cin, B, N = x.shape
-    xa = x
-    if torch.is_autocast_enabled() and x.is_cuda and x.dtype == torch.float32:
-        xa = x.to(torch.get_autocast_dtype("cuda"))
-    if not ops.conv_bn_act_supported(xa.reshape(cin, B * N), prod_conv.out_channels, prod_conv.groups, groups):
-        return None
-    if not ops.conv_bn_act_shape_supported(cons_conv.in_channels, B * N, cons_conv.out_channels, 1, groups):
-        return None
-    if not ops.defer_norm_pays(cons_conv.out_channels, cons_conv.in_channels, B * N):
-        return None
-    return ops.DeferredNorm()
+    M = x.shape[1] * x.shape[2]
+    ok = (prod_bn.training and cons_bn.training and cons_conv.groups == 1
+          and _first_layer_rows(x, prod_conv, groups) is not None
+          and ops.conv_bn_act_shape_supported(cons_conv.in_channels, M, cons_conv.out_channels, 1, groups)
+          and ops.defer_norm_pays(cons_conv.out_channels, cons_conv.in_channels, M))
+    return ops.DeferredNorm() if ok else None
 
 
 def conv_bn_act(conv, bn, x, residual=None, act=ops.ACT_NONE, slope=0.0, groups=1, weight=None, use_bias=True,
-                token=None, token_role=0, defer=None, defer_role=0):
+                shortcut_in=None, shortcut_out=None, norm_out=None, norm_in=None):
     """[1x1 Conv2d -> BatchNorm2d -> activation -> + shortcut] on x (Cin, B, N) -> (Cout, B, N).  bf16 activations on
     the GPU take the fused path (ops.conv_bn_act: hand-written GEMM with the batch statistics in its epilogue, one
     normalise pass); everything else the GEMM + fused BatchNorm kernel pair.  `weight`: a 2-D (Cout, K) weight derived
-    from conv.weight (Downsample's tap matrix) instead of the conv's own; groups = views stacked along B."""
+    from conv.weight (Downsample's tap matrix) in its place, cast per call; groups = views stacked along B; the last four
+    keywords: the layer's ops.LayerLinks, built here."""
     cin, B, N = x.shape
     cout = conv.out_channels
     cg = conv.groups if weight is None else 1
-    if torch.is_autocast_enabled() and x.is_cuda and x.dtype == torch.float32:
-        x = x.to(torch.get_autocast_dtype("cuda"))
+    x = ops.autocast_rows(x)
     x2 = x.reshape(cin, B * N)
     bias = conv.bias if use_bias else None
     if ops.conv_bn_act_supported(x2, cout, cg, groups):
         training, momentum = _bn_training(bn, groups)
-        w = conv.weight if weight is None else weight
         res = None if residual is None else residual.reshape(cout, B * N)
+        w, prepared = (conv.weight, getattr(conv, "_prepared", None)) if weight is None else (weight, None)
+        linked = not (shortcut_in is None and shortcut_out is None and norm_out is None and norm_in is None)
+        links = ops.LayerLinks(shortcut_in, shortcut_out, norm_out, norm_in) if linked else None
         z = ops.conv_bn_act(x2, w, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum, bn.eps,
-                            bias, res, act, slope, cg, groups, getattr(conv, "_w_lowp", None) if weight is None else None,
-                            token, token_role, getattr(conv, "_w_t", None) if weight is None else None,
-                            getattr(conv, "_w_aug", None) if weight is None else None, defer, defer_role,
-                            getattr(conv, "_lowp_owner", None) if weight is None else None)
+                            bias, res, act, slope, cg, groups, prepared, links)
         return z.reshape(cout, B, N)
-    if defer is not None:
+    if norm_out is not None or norm_in is not None:
         raise RuntimeError("conv_bn_act: a DeferredNorm was handed to a layer outside the fused bf16 path")
     if weight is None:
         y = conv1x1(conv, x)
@@ -153,16 +152,10 @@ def shortcut_token(x, first_conv, last_conv, groups=1):
     path in training mode (otherwise None: autograd adds the two gradients of x as usual)."""
     if not (torch.is_grad_enabled() and x.requires_grad and first_conv.groups == 1):
         return None
-    cin, B, N = x.shape
-    xa = x
-    if torch.is_autocast_enabled() and x.is_cuda and x.dtype == torch.float32:
-        xa = x.to(torch.get_autocast_dtype("cuda"))
-    x2 = xa.reshape(cin, B * N)
-    if not (ops.conv_bn_act_supported(x2, first_conv.out_channels, 1, groups) and ops.shortcut_token_supported(x2)):
-        return None
-    if not ops.conv_bn_act_shape_supported(last_conv.in_channels, B * N, last_conv.out_channels, last_conv.groups, groups):
-        return None
-    return ops.ShortcutToken()
+    x2 = _first_layer_rows(x, first_conv, groups)
+    ok = (x2 is not None and ops.shortcut_token_supported(x2) and ops.conv_bn_act_shape_supported(
+        last_conv.in_channels, x2.shape[1], last_conv.out_channels, last_conv.groups, groups))
+    return ops.ShortcutToken() if ok else None
 
 
 def bn_act(bn, y, pre_bias=None, residual=None, act=ops.ACT_NONE, slope=0.0, groups=1):

@@ -79,7 +79,7 @@ class BasicConv(nn.Sequential):
                 and isinstance(mods[2], nn.ReLU)):
             d = deferred_norm(x, mods[0], mods[1], consumer[0], consumer[1], groups)
             if d is not None:
-                return conv_bn_act(mods[0], mods[1], x, act=ops.ACT_RELU, groups=groups, defer=d, defer_role=1), d
+                return conv_bn_act(mods[0], mods[1], x, act=ops.ACT_RELU, groups=groups, norm_out=d), d
         return self.forward_cbn(x, groups), None
 
     def forward_cbn(self, x, groups=1):

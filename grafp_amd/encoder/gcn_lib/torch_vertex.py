@@ -97,11 +97,10 @@ class Grapher(nn.Module):
     def forward_cbn(self, x, groups=1):
         """x (C,B,N) -> (C,B,N): 3 GEMMs, 3 fused BN kernels, the k-NN build and the max-relative gather."""
         tok = shortcut_token(x, self.fc1[0], self.fc2[0], groups)     # the shortcut's gradient rides fc1's data gradient
-        y = conv_bn_act(self.fc1[0], self.fc1[1], x, groups=groups, token=tok, token_role=1)
+        y = conv_bn_act(self.fc1[0], self.fc1[1], x, groups=groups, shortcut_in=tok)
         # stages 0-1: the grouped conv's BatchNorm + ReLU ride fc2's operand staging (no pass of their own)
         y, d = self.graph_conv.forward_cbn(y, groups, consumer=(self.fc2[0], self.fc2[1]))
-        return conv_bn_act(self.fc2[0], self.fc2[1], y, residual=x, groups=groups, token=tok, token_role=2, defer=d,
-                           defer_role=2)
+        return conv_bn_act(self.fc2[0], self.fc2[1], y, residual=x, groups=groups, shortcut_out=tok, norm_in=d)
 
     def forward(self, x):
         return from_cbn(self.forward_cbn(to_cbn(x)), x)

@@ -72,13 +72,11 @@ class FFN(nn.Module):
         if isinstance(self.act, torch.nn.ReLU):
             # stages 0-1: the hidden activation (4C rows) is never normalised by a pass of its own -- fc2 does it on load
             d = deferred_norm(x, self.fc1[0], self.fc1[1], self.fc2[0], self.fc2[1], groups)
-            h = conv_bn_act(self.fc1[0], self.fc1[1], x, act=ops.ACT_RELU, groups=groups, token=tok, token_role=1,
-                            defer=d, defer_role=1)
+            h = conv_bn_act(self.fc1[0], self.fc1[1], x, act=ops.ACT_RELU, groups=groups, shortcut_in=tok, norm_out=d)
         else:
             d = None
-            h = self.act(conv_bn_act(self.fc1[0], self.fc1[1], x, groups=groups, token=tok, token_role=1))
-        return conv_bn_act(self.fc2[0], self.fc2[1], h, residual=x, groups=groups, token=tok, token_role=2, defer=d,
-                           defer_role=2)
+            h = self.act(conv_bn_act(self.fc1[0], self.fc1[1], x, groups=groups, shortcut_in=tok))
+        return conv_bn_act(self.fc2[0], self.fc2[1], h, residual=x, groups=groups, shortcut_out=tok, norm_in=d)
 
     def forward(self, x):
         return from_cbn(self.forward_cbn(to_cbn(x)), x)

@@ -1048,6 +1048,23 @@ def split_gemm_f32(w, x):
     return y
 
 
+class PreparedWeight:
+    """What lowp_weights keeps ready of one convolution's weight (conv._prepared): `lowp` the forward operand, `t` the per-
+    group transposed copy or, for the first layer of a residual block, `aug` = [W^T | I]; `owner` that lowp_weights."""
+    __slots__ = ("lowp", "t", "aug", "owner")
+
+    def __init__(self, lowp=None, t=None, aug=None, owner=None):
+        self.lowp, self.t, self.aug, self.owner = lowp, t, aug, owner
+
+
+def _forward_operand(w, lowp, dtype):
+    """w as (R, -1) rows in `dtype`: the prepared copy `lowp` as it is when its dtype and element count fit, else a cast."""
+    R = w.shape[0]
+    if lowp is not None and lowp.dtype == dtype and lowp.numel() == w.numel():
+        return lowp.detach().reshape(R, -1)
+    return w.detach().reshape(R, -1).to(dtype)
+
+
 class _Conv1x1(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, groups, w_lowp=None):
@@ -1069,10 +1086,8 @@ class _Conv1x1(torch.autograd.Function):
         ctx.batched = False
         if groups > 1:
             dense = _block_diag_weight(w2, groups, x.dtype)
-        elif w_lowp is not None and w_lowp.dtype == x.dtype and w_lowp.numel() == w.numel():
-            dense = w_lowp.detach().reshape(w2.shape)
         else:
-            dense = w2.to(x.dtype)
+            dense = _forward_operand(w, w_lowp, x.dtype)
         ctx.split = bool(x.is_cuda and x.dtype == torch.float32 and x.numel() % 8 == 0
                          and split_gemm_supported(dense.shape[0], dense.shape[1], x.shape[1])
                          and split_gemm_supported(dense.shape[1], dense.shape[0], x.shape[1]))
@@ -1122,13 +1137,16 @@ class _Conv1x1(torch.autograd.Function):
         return dx, (None if dw is None else dw.reshape(ctx.wfull)), None, None
 
 
+def autocast_rows(x):
+    """x, lowered to the autocast dtype if it is f32 on the GPU under autocast (the rest of a block already flows in it)."""
+    lower = torch.is_autocast_enabled() and x.is_cuda and x.dtype == torch.float32
+    return x.to(torch.get_autocast_dtype("cuda")) if lower else x
+
+
 def conv1x1_rows(x, w, groups=1, w_lowp=None):
-    """y = W x over (C, M) rows (x contiguous 2-D).  Under autocast f32 inputs are lowered to the autocast dtype
-    (the rest of a block already flows in it); the weight gradient of bf16 operands is the hand-written split-K
-    kernel (grafp_conv1x1_wgrad_bf16), everything else a plain library GEMM."""
-    if torch.is_autocast_enabled() and x.is_cuda and x.dtype == torch.float32:
-        x = x.to(torch.get_autocast_dtype("cuda"))
-    return _Conv1x1.apply(x.contiguous(), w, groups, w_lowp)
+    """y = W x over (C, M) rows (x contiguous 2-D, lowered by autocast_rows).  The weight gradient of bf16 operands is
+    the hand-written split-K kernel (grafp_conv1x1_wgrad_bf16), everything else a plain library GEMM."""
+    return _Conv1x1.apply(autocast_rows(x).contiguous(), w, groups, w_lowp)
 
 
 class lowp_weights:
@@ -1136,7 +1154,7 @@ class lowp_weights:
     the per-group transposed bf16 copy (data-gradient operand) and, for the first layer of a residual block (conv.
     _shortcut_first), [W^T | I] -- ONE launch of grafp_weights_prepare for every layer whose rows and columns per
     group are multiples of 32, one multi-tensor cast for the rest (the 8-channel stem).  `refresh()` before the layers
-    run; conv._w_lowp, conv._w_t and conv._w_aug are picked up by encoder/_dense.conv_bn_act.
+    run; conv._prepared (a PreparedWeight) is picked up by encoder/_dense.conv_bn_act.
     The buffers are shared between passes and rewritten by EVERY refresh() (one launch; whether the weights changed
     cannot be seen from the host: fused optimizers and replayed graphs update parameters without touching their version
     counters -- a skip-when-unchanged variant trained on stale copies and was caught by the hit-rate test).  Each refresh
@@ -1148,20 +1166,19 @@ class lowp_weights:
         self.convs = list(convs)
         self.generation = 0             # advanced by every refresh() of THIS instance (its buffers are its own)
         self._dtype, self._dev = None, None
-        self._fast, self._slow, self._slow_bufs = [], [], []
+        self._prepared, self._slow, self._slow_bufs, self._src_ptrs = [], [], [], []
         self._table = self._tile_entry = None
-        self._keep, self._src_ptrs = [], []
 
     def _build(self, dtype, dev):
         self._dtype, self._dev = dtype, dev
-        self._fast, self._slow, self._slow_bufs, self._keep = [], [], [], []
+        self._prepared, self._slow, self._slow_bufs = [PreparedWeight(owner=self) for _ in self.convs], [], []
         rows, tiles, base = [], [], 0
-        for c in self.convs:
+        for c, p in zip(self.convs, self._prepared):
             w = c.weight
             G = c.groups
             Rg, Kg = w.shape[0] // G, w.shape[1]
             if dtype == torch.bfloat16 and Rg % 32 == 0 and Kg % 32 == 0 and w.dtype == torch.float32 and w.is_contiguous():
-                lo = torch.empty((w.shape[0], Kg), dtype=dtype, device=dev)
+                p.lowp = lo = torch.empty((w.shape[0], Kg), dtype=dtype, device=dev)
                 aug = bool(getattr(c, "_shortcut_first", False)) and G == 1
                 ld_t = Rg + Kg if aug else Rg
                 wt = torch.zeros((G * Kg, ld_t), dtype=dtype, device=dev)
@@ -1171,10 +1188,11 @@ class lowp_weights:
                 rows.append([w.data_ptr(), lo.data_ptr(), wt.data_ptr(), Rg, Kg, G, ld_t, base])
                 tiles.append(torch.full((n_t,), len(rows) - 1, dtype=torch.int32))
                 base += n_t
-                self._fast.append((c, lo, wt, aug, Rg))
+                p.t, p.aug = (None, wt) if aug else (wt, None)
             elif G == 1:
+                p.lowp = torch.empty(w.shape, dtype=dtype, device=dev)
                 self._slow.append(c)
-                self._slow_bufs.append(torch.empty(w.shape, dtype=dtype, device=dev))
+                self._slow_bufs.append(p.lowp)
         if rows:
             self._table = torch.tensor(rows, dtype=torch.int64).to(dev)
             self._tile_entry = torch.cat(tiles).to(dev)
@@ -1199,25 +1217,19 @@ class lowp_weights:
                                                 _stream()), "weights_prepare")
             if self._slow:
                 torch._foreach_copy_(self._slow_bufs, [c.weight for c in self._slow])
-        # the prepared buffers are refreshed IN PLACE: the modules' attributes only change when the buffers were rebuilt
-        # (or cleared) -- re-assigning 4 x 61 module attributes on every forward pass was 0.6 ms of host time per step
+        # the prepared buffers are refreshed IN PLACE: the modules' attribute only changes when the buffers were rebuilt
+        # (or cleared) -- re-assigning module attributes of 61 layers on every forward pass was 0.6 ms of host time per step
         if not getattr(self, "_published", False):
             self._publish()
             self._published = True
 
     def _publish(self):
-        for c in self.convs:
-            c._lowp_owner = self
-        for c, lo, wt, aug, Rg in self._fast:
-            c._w_lowp = lo.view(c.weight.shape) if c.weight.dim() == 4 else lo
-            c._w_t, c._w_aug = (None, wt) if aug else (wt, None)
-        for c, b in zip(self._slow, self._slow_bufs):
-            c._w_lowp, c._w_t, c._w_aug = b, None, None
+        for c, p in zip(self.convs, self._prepared):
+            c._prepared = p
 
     def clear(self):
         for c in self.convs:
-            c._w_lowp = c._w_t = c._w_aug = None
-            c._lowp_owner = None
+            c._prepared = None
         self._published = False
 
 
@@ -1459,8 +1471,8 @@ def defer_wgrad_reduce():
     """Inside the block (a backward pass) the bf16 weight gradients only run their split-K kernels; the partial sums of
     all layers are reduced together when the block ends (or at flush_wgrad_reduce()): ~60 launches fewer per step, the
     same bits.  The returned gradient tensors must not be READ inside the block without a flush.  Which weights produced
-    a gradient in the block (_WGRAD_DEFERRED_IDS) is remembered until the OUTERMOST block ends, across flushes and across
-    several backward passes inside it (see _may_defer)."""
+    a gradient in the block (_WGRAD_SEEN_IDS) is remembered until the OUTERMOST block ends, across flushes and across
+    several backward passes inside it (see _wgrad_plan)."""
     global _WGRAD_PENDING
     if _WGRAD_PENDING is not None:                # nested: the outer block flushes
         yield
@@ -1471,7 +1483,7 @@ def defer_wgrad_reduce():
         flush_wgrad_reduce()
     finally:
         _WGRAD_PENDING = None
-        _WGRAD_DEFERRED_IDS.clear()
+        _WGRAD_SEEN_IDS.clear()
 
 
 # Under data parallelism the parameter gradients live in ONE flat buffer (dist.GradSync) that the bucket all-reduces run on.
@@ -1515,38 +1527,42 @@ def _wgrad_bf16(g, x, cout, cin, groups, M, views=1, pro_tab=None, pro_act=ACT_N
 conv1x1_wgrad = _wgrad_bf16
 
 
-# weights that produced a gradient in the running defer_wgrad_reduce() block -- deferred or not (the name is older than that
-# rule), in any backward pass inside it; only the end of the outermost block clears it (a flush does not: the weights'
-# .grad may still be about to be summed)
-_WGRAD_DEFERRED_IDS = set()
+# weights that produced a gradient in the running defer_wgrad_reduce() block -- deferred or not, in any backward pass inside
+# it; only the end of the outermost block clears it (a flush does not: the weights' .grad may still be about to be summed)
+_WGRAD_SEEN_IDS = _WGRAD_DEFERRED_IDS = set()    # (one set: the second is the name it had before, still read by callers)
 
 
-def _may_defer(w):
-    """A weight gradient may leave backward() with its split-K partial sums still unreduced (defer_wgrad_reduce) only if
-    nothing can READ it before the flush: it is the FIRST gradient of this weight in the running block (a weight shared by
-    two layers gets its two gradients summed by autograd in front of AccumulateGrad, and a second backward pass inside
-    the block ADDS into the .grad the first one left: every later use flushes what is queued -- the first use among it --
-    and reduces at once; the set of weights seen survives flushes, so an order A B A B cannot defer B twice), the weight
-    is a leaf whose .grad is None (AccumulateGrad then takes the tensor over as it is -- with an existing .grad it would
-    ADD the unreduced memory into it: gradient accumulation without zero()), it carries no tensor hook (a hook receives
-    the gradient inside backward) and every post-accumulate hook on it is GradSync's (which flushes before it packs a
-    bucket; anybody else's would read unreduced memory).  Everything else reduces immediately: slower, never wrong.
-    Only a deferred gradient may be produced in place (_GRAD_TARGET_OF), so a weight seen before never gets a target."""
+def _wgrad_plan(w):
+    """-> (may_defer, target) for the gradient of w, a leaf parameter (None, a derived weight: autograd reads its gradient).
+    may_defer: the gradient may leave backward() with its split-K partial sums unreduced (defer_wgrad_reduce), because
+    nothing can READ it before the flush.  That holds for the FIRST gradient of a weight in the running block only: a weight
+    shared by two layers gets its gradients summed by autograd in front of AccumulateGrad, and a second backward pass ADDS
+    into the .grad the first one left, so every later use flushes what is queued and reduces at once (the set of weights
+    seen survives flushes: A B A B cannot defer B twice).  And only while .grad is None (AccumulateGrad then takes the
+    tensor over; it would ADD unreduced memory into an existing one: accumulation without zero()), with no tensor hook (it
+    receives the gradient inside backward) and no post-accumulate hook but GradSync's (which flushes before it packs a
+    bucket).  Everything else reduces immediately: slower, never wrong.  target: only a deferred gradient may be produced in
+    place, and only inside a block with a registered _GRAD_TARGET_OF: what that returns for w, otherwise None."""
+    in_block = _WGRAD_PENDING is not None
     if w is None:
-        return False
-    if _WGRAD_PENDING is not None:
-        if id(w) in _WGRAD_DEFERRED_IDS:
+        return False, None
+    if in_block:
+        if id(w) in _WGRAD_SEEN_IDS:
             flush_wgrad_reduce()                        # the earlier uses' partial sums: reduced before anyone adds to them
-            return False
-        _WGRAD_DEFERRED_IDS.add(id(w))
+            return False, None
+        _WGRAD_SEEN_IDS.add(id(w))
     if w.grad is not None or getattr(w, "_backward_hooks", None) or torch.is_grad_enabled():
-        return False                                    # (create_graph = True keeps grad mode on inside backward)
+        return False, None                              # (create_graph = True keeps grad mode on inside backward)
     hooks = getattr(w, "_post_accumulate_grad_hooks", None)
     if hooks:
         from .dist import GradSync
         if not all(isinstance(getattr(h, "__self__", None), GradSync) for h in hooks.values()):
-            return False
-    return True
+            return False, None
+    return True, (_GRAD_TARGET_OF(w) if in_block and _GRAD_TARGET_OF is not None else None)
+
+
+def _may_defer(w):
+    return _wgrad_plan(w)[0]                            # (the half of the plan that tests and tools ask for)
 
 
 class _ConvBnAct(torch.autograd.Function):
@@ -1556,29 +1572,19 @@ class _ConvBnAct(torch.autograd.Function):
     pass), data gradient by the same GEMM kernel on the transposed weight, weight gradient by the split-K kernel."""
 
     @staticmethod
-    def forward(ctx, x, w, w_lowp, conv_groups, views, gamma, beta, pre_bias, residual, running_mean, running_var,
-                training, momentum, eps, act, slope, token=None, token_role=0, w_t=None, w_aug=None, defer=None,
-                defer_role=0, lowp_owner=None):
+    def forward(ctx, x, w, gamma, beta, pre_bias, residual, running_mean, running_var, rest):
+        conv_groups, views, training, momentum, eps, act, slope, prepared, links = rest       # as conv_bn_act packs them
+        ctx.prepared, ctx.links = prepared, links
         x = x.detach()
-        # DeferredNorm: role 1 = this layer's BatchNorm + activation are applied by its only consumer while THAT stages
-        # its operand (no normalise pass, the normalised tensor is never written); role 2 = that consumer
-        pro = None
-        if defer is not None and defer_role == 2 and defer.tab is not None:
-            pro = (defer.tab, int(defer.act), float(defer.slope))
-        ctx.pro = pro
-        ctx.w_leaf = bool(w.is_leaf)                         # its gradient goes straight to AccumulateGrad (never read here)
-        ctx.w_param = w if w.is_leaf else None               # (looked at again in backward: see _may_defer)
-        ctx.token, ctx.token_role = token, token_role        # 1: first layer of the block (consumes), 2: last (provides)
-        ctx.w_t, ctx.w_aug = w_t, w_aug                      # prepared with the forward operand (lowp_weights), or None
+        defer, d_in = links.norm_out, links.norm_in          # see LayerLinks; pro: what the producer left for this layer
+        ctx.pro = pro = (d_in.tab, int(d_in.act), float(d_in.slope)) if d_in is not None and d_in.tab is not None else None
+        ctx.w_param = w if w.is_leaf else None               # (looked at again in backward: see _wgrad_plan)
         # shared prepared buffers in use: remember which preparation this forward pass saw
-        shared = lowp_owner is not None and (w_lowp is not None or w_t is not None or w_aug is not None)
-        ctx.lowp_owner, ctx.lowp_gen = (lowp_owner, lowp_owner.generation) if shared else (None, None)
+        shared = prepared.owner is not None and not (prepared.lowp is None and prepared.t is None and prepared.aug is None)
+        ctx.lowp_gen = prepared.owner.generation if shared else None
         K, M = x.shape
         R = w.shape[0]
-        if w_lowp is not None and w_lowp.dtype == torch.bfloat16 and w_lowp.numel() == w.numel():
-            wl = w_lowp.detach().reshape(R, -1)
-        else:
-            wl = w.detach().reshape(R, -1).to(torch.bfloat16)
+        wl = _forward_operand(w, prepared.lowp, torch.bfloat16)
         g32, b32 = _f32c(gamma), _f32c(beta)
         pb = None if pre_bias is None else _f32c(pre_bias)
         if pro is not None:
@@ -1590,7 +1596,7 @@ class _ConvBnAct(torch.autograd.Function):
         else:
             y, part = conv1x1_gemm(wl, x, conv_groups, views), None
         res = None if residual is None else residual.detach().to(torch.bfloat16).contiguous()
-        if defer is not None and defer_role == 1:
+        if defer is not None:
             if not training or res is not None:
                 raise RuntimeError("conv_bn_act: only a training-mode layer without a shortcut can defer its normalisation")
             mean, invstd, tab = bn_finalize(part, R, K, conv_groups, M, views, g32, b32, pb, running_mean, running_var,
@@ -1613,7 +1619,8 @@ class _ConvBnAct(torch.autograd.Function):
     def backward(ctx, dz):
         x, wl, y, mean, invstd, g32, b32, pb = ctx.saved_tensors
         R, K, M, cg, views, act, slope, training, has_pb, has_res, wfull = ctx.cfg
-        if ctx.lowp_owner is not None and ctx.lowp_gen != ctx.lowp_owner.generation:
+        prepared, tok_in, tok_out = ctx.prepared, ctx.links.shortcut_in, ctx.links.shortcut_out
+        if ctx.lowp_gen is not None and ctx.lowp_gen != prepared.owner.generation:
             raise RuntimeError("conv_bn_act backward: the shared low-precision weight buffers were re-prepared (another forward "
                                "of THIS encoder under autocast, possibly after an optimizer step) between this layer's "
                                "forward and backward pass; run backward before the next forward")
@@ -1621,36 +1628,29 @@ class _ConvBnAct(torch.autograd.Function):
         dy, dgamma, dbeta, dpb = _bn_bwd(y, dz, R, M, views, pb if has_pb else None, g32, b32, mean, invstd, act, slope,
                                          training)
         dx = None
-        tok = ctx.token
         if ctx.needs_input_grad[0]:
-            short = tok.grad if (tok is not None and ctx.token_role == 1) else None
-            w_t, w_aug = ctx.w_t, ctx.w_aug
+            short = tok_in.grad if tok_in is not None else None
             if short is not None:
                 # dX = [W^T | I] [dY; dZ_shortcut]: the block input's two gradients in one product, rounded once
-                tok.grad = None
-                if w_aug is None:
-                    w_aug = torch.cat((wl.t(), _eye_bf16(K, wl.device)), dim=1)
+                tok_in.grad = None
+                w_aug = prepared.aug if prepared.aug is not None else torch.cat((wl.t(), _eye_bf16(K, wl.device)), dim=1)
                 dx = conv1x1_gemm_cat(w_aug, dy, short)
-            elif w_t is not None and w_t.is_contiguous():
-                dx = conv1x1_gemm(w_t, dy, cg, 1)
+            elif prepared.t is not None and prepared.t.is_contiguous():
+                dx = conv1x1_gemm(prepared.t, dy, cg, 1)
             else:
                 dx = conv1x1_gemm(_group_transpose(wl, cg), dy, cg, 1)
         dw = None
         if ctx.needs_input_grad[1]:
-            md = _may_defer(ctx.w_param)
-            # (a deferred gradient is the FIRST of this weight in the pass and nothing reads it before the flush: it may be
-            #  produced in place, in the parameter's slice of the data-parallel flat buffer)
-            tgt = _GRAD_TARGET_OF(ctx.w_param) if (md and _WGRAD_PENDING is not None and _GRAD_TARGET_OF is not None) else None
+            md, tgt = _wgrad_plan(ctx.w_param)
             if ctx.pro is not None:                        # x is the producer's raw output: the same transform on load
                 dw = _wgrad_bf16(dy, x, R, K, cg, M, views, ctx.pro[0], ctx.pro[1], ctx.pro[2], may_defer=md,
                                  out=tgt).reshape(wfull)
             else:
                 dw = _wgrad_bf16(dy, x, R, K, cg, M, may_defer=md, out=tgt).reshape(wfull)
         dres = dz if has_res else None
-        if has_res and tok is not None and ctx.token_role == 2 and tok.grad is None:
-            tok.grad, dres = dz, None                      # the first layer's backward adds it (see above)
-        return (dx, dw, None, None, None, dgamma, dbeta, dpb, dres, None, None, None, None, None, None, None, None, None,
-                None, None, None, None, None)
+        if has_res and tok_out is not None and tok_out.grad is None:
+            tok_out.grad, dres = dz, None                  # the first layer's backward adds it (see above)
+        return dx, dw, dgamma, dbeta, dpb, dres, None, None, None      # x, w, gamma, beta, pre_bias, residual + 3 constants
 
 
 def conv_bn_act_supported(x, cout, conv_groups, views):
@@ -1668,13 +1668,28 @@ def conv_bn_act_shape_supported(K, M, cout, conv_groups, views):
 
 
 class DeferredNorm:
-    """Shared by a layer whose BatchNorm + activation output has exactly ONE consumer, another conv_bn_act (role 1), and
-    that consumer (role 2): the producer returns its raw convolution output and leaves (scale, shift) here, the consumer
+    """Shared by a layer whose BatchNorm + activation output has exactly ONE consumer, another conv_bn_act (norm_out),
+    and that consumer (norm_in): the producer returns its raw convolution output and leaves (scale, shift) here, the consumer
     applies them to the operand tile while it is staged (conv1x1_gemm PRO, and again in its weight gradient).  Saves the
     normalise pass (one read + one write of the widest tensors of a block) where the GEMM is HBM-bound."""
 
     def __init__(self):
         self.tab, self.act, self.slope = None, ACT_NONE, 0.0
+
+
+class LayerLinks:
+    """The cells a fused layer shares with its neighbours in a residual block, each None or:
+      shortcut_in   ShortcutToken: this layer's input IS the block's shortcut, its data gradient takes the token's gradient
+      shortcut_out  ShortcutToken: this layer adds the shortcut (`residual` is that input), its backward leaves dZ in the token
+      norm_out      DeferredNorm: this layer leaves its BatchNorm + activation to its only consumer (no normalise pass)
+      norm_in       DeferredNorm: this layer applies its producer's normalisation on load, in its product and weight gradient"""
+    __slots__ = ("shortcut_in", "shortcut_out", "norm_out", "norm_in")
+
+    def __init__(self, shortcut_in=None, shortcut_out=None, norm_out=None, norm_in=None):
+        self.shortcut_in, self.shortcut_out, self.norm_out, self.norm_in = shortcut_in, shortcut_out, norm_out, norm_in
+
+
+_UNPREPARED, _UNLINKED = PreparedWeight(), LayerLinks()      # what a layer without prepared copies / without links sees
 
 
 def defer_norm_pays(consumer_rows, consumer_operand_rows, M):
@@ -1688,29 +1703,24 @@ def defer_norm_pays(consumer_rows, consumer_operand_rows, M):
 
 
 def conv_bn_act(x, w, gamma, beta, running_mean, running_var, training, momentum=0.1, eps=1e-5, pre_bias=None,
-                residual=None, act=ACT_NONE, slope=0.0, conv_groups=1, views=1, w_lowp=None, token=None, token_role=0,
-                w_t=None, w_aug=None, defer=None, defer_role=0, lowp_owner=None):
-    """act(BatchNorm(W x + pre_bias)) + residual for bf16 (K, M) rows (see _ConvBnAct).  token / token_role: a
-    ShortcutToken shared by the first (role 1: its input IS the shortcut) and the last layer (role 2: `residual` is that
-    same input) of a residual block."""
+                residual=None, act=ACT_NONE, slope=0.0, conv_groups=1, views=1, prepared=None, links=None):
+    """act(BatchNorm(W x + pre_bias)) + residual for bf16 (K, M) rows (see _ConvBnAct).  prepared: the PreparedWeight of
+    w (lowp_weights) or None; links: the LayerLinks of a layer inside a residual block or None."""
+    prepared, links = prepared or _UNPREPARED, links or _UNLINKED
     if not training and residual is None and switches.fused_eval_affine and not torch.is_grad_enabled():
         # inference without a shortcut (fc1, the grouped conv, ffn1, Downsample): the normalisation rides the GEMM's
         # epilogue -- no y, no second pass, no autograd node
         x = x.detach().contiguous()
         K, M = x.shape
         R = w.shape[0]
-        if w_lowp is not None and w_lowp.dtype == torch.bfloat16 and w_lowp.numel() == w.numel():
-            wl = w_lowp.detach().reshape(R, -1)
-        else:
-            wl = w.detach().reshape(R, -1).to(torch.bfloat16)
+        wl = _forward_operand(w, prepared.lowp, torch.bfloat16)
         _, _, tab = bn_finalize(None, R, K, int(conv_groups), M, int(views), gamma, beta, pre_bias, running_mean,
                                 running_var, False, momentum, eps)
         return conv1x1_gemm_affine(wl, x, tab, int(conv_groups), int(views), int(act), float(slope))
-    if defer is not None and not training:
+    if not training and (links.norm_out is not None or links.norm_in is not None):
         raise RuntimeError("conv_bn_act: deferred normalisation is a training-mode construct")
-    return _ConvBnAct.apply(x.contiguous(), w, w_lowp, int(conv_groups), int(views), gamma, beta, pre_bias, residual,
-                            running_mean, running_var, bool(training), float(momentum), float(eps), int(act),
-                            float(slope), token, int(token_role), w_t, w_aug, defer, int(defer_role), lowp_owner)
+    rest = (int(conv_groups), int(views), bool(training), float(momentum), float(eps), int(act), float(slope), prepared, links)
+    return _ConvBnAct.apply(x.contiguous(), w, gamma, beta, pre_bias, residual, running_mean, running_var, rest)
 
 
 def shortcut_token_supported(x, conv_groups=1):

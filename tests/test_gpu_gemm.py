@@ -449,15 +449,15 @@ def test_weights_prepare_one_launch():
         lw.refresh(torch.bfloat16)
         for c in convs:
             want = c.weight.detach().to(torch.bfloat16)
-            assert torch.equal(c._w_lowp.reshape(want.shape), want)
+            assert torch.equal(c._prepared.lowp.reshape(want.shape), want)
             R, Kg = want.shape[0], want.shape[1]
             if Kg % 32 or (R // c.groups) % 32:
                 continue                                   # the 8-channel stem: plain cast only
             if getattr(c, "_shortcut_first", False):
                 eye = torch.eye(Kg, dtype=torch.bfloat16, device=DEV)
-                assert c._w_t is None and torch.equal(c._w_aug, torch.cat((want.reshape(R, Kg).t(), eye), dim=1))
+                assert c._prepared.t is None and torch.equal(c._prepared.aug, torch.cat((want.reshape(R, Kg).t(), eye), dim=1))
             else:
-                assert c._w_aug is None and torch.equal(c._w_t, ops._group_transpose(want.reshape(R, Kg), c.groups))
+                assert c._prepared.aug is None and torch.equal(c._prepared.t, ops._group_transpose(want.reshape(R, Kg), c.groups))
 
 
 @pytest.mark.parametrize("R,K,groups,M,views,act", [(64, 64, 1, 8192, 2, 0), (256, 64, 1, 8192, 1, 1), (128, 128, 4, 4096, 2, 1),
@@ -558,7 +558,7 @@ def test_deferred_reduction_only_when_nothing_can_read_the_gradient_first():
     zb5 = ops.conv_bn_act(x2, w5, gamma, beta, rm.clone(), rv.clone(), True, act=ops.ACT_RELU)
     (zb5.float() * up).sum().backward()
     assert torch.allclose(w4.grad, once + w5.grad, rtol=1e-6, atol=1e-6 * float(once.abs().max()))
-    assert not ops._WGRAD_DEFERRED_IDS
+    assert not ops._WGRAD_SEEN_IDS
 
 
 # weights used more than once per block: (R, K, groups, M, views) -- plain, grouped, ragged column range (from SHAPES)
@@ -627,7 +627,7 @@ def _shared_grads(w0, order, xs, ups, groups, views, defer, passes=1, flat=False
         with ops.defer_wgrad_reduce() if defer else contextlib.nullcontext():
             for p in range(passes):
                 _shared_loss(ws, order, xs, ups[p], groups, views).backward()
-        assert ops._WGRAD_PENDING is None and not ops._WGRAD_DEFERRED_IDS
+        assert ops._WGRAD_PENDING is None and not ops._WGRAD_SEEN_IDS
         slices = None
         if sync is not None:
             sync.finish()

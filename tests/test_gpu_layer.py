@@ -175,7 +175,7 @@ def _run_block(name, token, defer=False, prepared=False, counts=None):
     x = _leaf(inp["x"])
     p = {k: _leaf(inp[k]) for k in ("gamma1", "gamma2", "beta1", "beta2", "pb1", "pb2")}
     st = {k: inp[k[:2] + "0" + k[2]].clone() for k in ("rm1", "rv1", "rm2", "rv2")}
-    lowp = [(None, None, None, None)] * 2
+    prep = [None, None]
     if prepared:
         convs = [torch.nn.Conv2d(b.K, b.H, 1, bias=False).to(DEV), torch.nn.Conv2d(b.H, b.K, 1, bias=False).to(DEV)]
         with torch.no_grad():
@@ -184,8 +184,9 @@ def _run_block(name, token, defer=False, prepared=False, counts=None):
         convs[0]._shortcut_first = True
         owner = ops.lowp_weights(convs)
         owner.refresh(torch.bfloat16)
-        assert convs[0]._w_aug is not None and convs[0]._w_t is None and convs[1]._w_t is not None
-        lowp = [(cv._w_lowp, cv._w_t, cv._w_aug, owner) for cv in convs]
+        prep = [cv._prepared for cv in convs]
+        assert all(isinstance(pw, ops.PreparedWeight) and pw.lowp is not None and pw.owner is owner for pw in prep)
+        assert prep[0].aug is not None and prep[0].t is None and prep[1].t is not None
         w1, w2 = convs[0].weight, convs[1].weight
     else:
         w1, w2 = _leaf(inp["w1"]), _leaf(inp["w2"])
@@ -204,9 +205,9 @@ def _run_block(name, token, defer=False, prepared=False, counts=None):
     ops.conv1x1_gemm_cat, ops.conv1x1_gemm = cat, gemm
     try:
         h = ops.conv_bn_act(x, w1, p["gamma1"], p["beta1"], st["rm1"], st["rv1"], True, lr.MOMENTUM, lr.EPS, p["pb1"], None,
-                            ops.ACT_RELU, 0.0, 1, b.views, lowp[0][0], tok, 1, lowp[0][1], lowp[0][2], d, 1, lowp[0][3])
+                            ops.ACT_RELU, 0.0, 1, b.views, prep[0], ops.LayerLinks(shortcut_in=tok, norm_out=d))
         z = ops.conv_bn_act(h, w2, p["gamma2"], p["beta2"], st["rm2"], st["rv2"], True, lr.MOMENTUM, lr.EPS, p["pb2"], x,
-                            ops.ACT_NONE, 0.0, 1, b.views, lowp[1][0], tok, 2, lowp[1][1], lowp[1][2], d, 2, lowp[1][3])
+                            ops.ACT_NONE, 0.0, 1, b.views, prep[1], ops.LayerLinks(shortcut_out=tok, norm_in=d))
         y1, y2 = h.grad_fn.saved_tensors[2].detach(), z.grad_fn.saved_tensors[2].detach()
         z.backward(inp["dz"])
         torch.cuda.synchronize()

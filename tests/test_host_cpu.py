@@ -347,7 +347,7 @@ def test_deferral_bookkeeping_first_use_of_each_weight_only(order, monkeypatch):
             else:
                 assert got is True and len(flushes) == before, (order, c)
             seen.add(c)
-    assert not ops._WGRAD_DEFERRED_IDS and ops._WGRAD_PENDING is None
+    assert not ops._WGRAD_SEEN_IDS and ops._WGRAD_PENDING is None
 
 
 def test_deferral_bookkeeping_survives_nesting_and_existing_grad(monkeypatch):
@@ -367,11 +367,60 @@ def test_deferral_bookkeeping_survives_nesting_and_existing_grad(monkeypatch):
             with ops.defer_wgrad_reduce():                   # nested: the same bookkeeping
                 assert ops._may_defer(b) is True
                 assert ops._may_defer(a) is False and len(flushes) == 2
-            assert ops._WGRAD_PENDING is not None and ops._WGRAD_DEFERRED_IDS
+            assert ops._WGRAD_PENDING is not None and ops._WGRAD_SEEN_IDS
             assert ops._may_defer(b) is False and len(flushes) == 3
-        assert not ops._WGRAD_DEFERRED_IDS and ops._WGRAD_PENDING is None
+        assert not ops._WGRAD_SEEN_IDS and ops._WGRAD_PENDING is None
         a.grad = None
         with ops.defer_wgrad_reduce():                       # a new block: first uses again
             assert ops._may_defer(a) is True and ops._may_defer(b) is True
         assert ops._may_defer(a) is True                     # outside any block nothing is tracked
-        assert not ops._WGRAD_DEFERRED_IDS
+        assert not ops._WGRAD_SEEN_IDS
+
+
+def test_wgrad_plan_target_only_for_a_deferred_gradient_inside_a_block(monkeypatch):
+    """ops._wgrad_plan -> (may_defer, target): inside defer_wgrad_reduce() the first use of a weight may be deferred and is
+    produced in place, in what the registered _GRAD_TARGET_OF returns for it; its second use flushes once and gets
+    neither; outside any block there is no target; a weight with an existing .grad gets neither."""
+    from grafp_amd import ops
+    flushes = []
+    real = ops.flush_wgrad_reduce                            # counted, and still run: the queue is empty, no launch
+    monkeypatch.setattr(ops, "flush_wgrad_reduce", lambda: (flushes.append(1), real()))
+    a, b = torch.zeros(4, requires_grad=True), torch.zeros(4, requires_grad=True)
+    slices = {id(a): torch.zeros(4), id(b): torch.zeros(4)}
+    asked = []
+    monkeypatch.setattr(ops, "_GRAD_TARGET_OF", lambda w: (asked.append(id(w)), slices[id(w)])[1])
+    with torch.no_grad():
+        assert ops._wgrad_plan(a) == (True, None) and not asked          # outside any block: deferrable, never in place
+        with ops.defer_wgrad_reduce():
+            for w in (a, b):
+                may, tgt = ops._wgrad_plan(w)
+                assert may is True and tgt is slices[id(w)] and not flushes
+            assert ops._wgrad_plan(a) == (False, None) and len(flushes) == 1
+            assert ops._wgrad_plan(b) == (False, None) and len(flushes) == 2
+            assert asked == [id(a), id(b)]                   # a weight seen before is never asked for a target
+        assert ops._wgrad_plan(a) == (True, None) and ops._wgrad_plan(None) == (False, None)
+        b.grad = torch.zeros(4)                              # gradient accumulation without zero()
+        with ops.defer_wgrad_reduce():
+            assert ops._wgrad_plan(b) == (False, None)
+            may, tgt = ops._wgrad_plan(a)
+            assert may is True and tgt is slices[id(a)] and ops._may_defer(a) is False
+        assert ops._wgrad_plan(b) == (False, None)
+    assert not ops._WGRAD_SEEN_IDS and ops._WGRAD_PENDING is None and len(asked) == 3
+
+
+@pytest.mark.parametrize("shape", [(8, 4, 1, 1), (8, 4)])
+def test_forward_operand_uses_the_prepared_copy_only_when_it_fits(shape):
+    """ops._forward_operand(w, lowp, dtype): a prepared copy of that dtype and of w's element count is used as it is (same
+    storage, as (R, -1) rows); a copy of another dtype, of another element count, or none: a fresh cast of w."""
+    from grafp_amd import ops
+    g = torch.Generator().manual_seed(3)
+    w = torch.randn(shape, generator=g, requires_grad=True)
+    want = w.detach().reshape(8, 4).to(torch.bfloat16)
+    lowp = w.detach().to(torch.bfloat16)
+    got = ops._forward_operand(w, lowp, torch.bfloat16)
+    assert got.data_ptr() == lowp.data_ptr() and got.shape == (8, 4) and torch.equal(got, want) and not got.requires_grad
+    for other in (w.detach().to(torch.float16), torch.zeros(8, 8, dtype=torch.bfloat16), None):
+        got = ops._forward_operand(w, other, torch.bfloat16)
+        assert got.dtype == torch.bfloat16 and got.shape == (8, 4) and torch.equal(got, want) and not got.requires_grad
+        assert other is None or got.data_ptr() != other.data_ptr()
+        assert got.data_ptr() != w.data_ptr()
