@@ -116,6 +116,7 @@ SIGNATURES = {
     "grafp_mix_snr_workspace": (_Z, [_I, _I]),
     "grafp_mix_snr_f32": (_I, [_P, _L, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _L, _P, _Z, _P]),
     "grafp_resample_f32": (_I, [_P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _P, _P, _P]),
+    "grafp_resample_plan": (_I, [_I, _I, _I, _I, _P]),
     "grafp_draw_pairs_f32": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
     "grafp_speed_change_f32": (_I, [_P, _L, _I, _I, _L, _P, _P, _L, _I, _P]),
     "grafp_time_stretch_f32": (_I, [_P, _L, _I, _I, _L, _P, _P, _L, _I, _P, _L, _P]),

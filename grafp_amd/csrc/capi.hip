@@ -44,10 +44,19 @@ namespace grafp {
 int resample_launch(const float *in, const int64_t *in_start, const int64_t *in_len, const int64_t *out_start,
                     int n_tracks, int64_t max_in_len, int orig, int nw, int width, int K, const float *taps, float *out,
                     hipStream_t stream);
+int resample_plan(int orig, int nw, int K, int *info);
 int draw_pairs_launch(const float *bank, const int64_t *track_start, const int64_t *track_len, const float *norm,
                       int n_tracks, const int32_t *row_track, const float *uniforms, int B, int A, int clip,
                       int offset_mod, float silence, float *x_i, float *x_j, int32_t *silent_rows, hipStream_t stream);
 }  // namespace grafp
+
+extern "C" int grafp_resample_plan(int orig, int new_rate, int width, int K, int *info) {
+    GRAFP_REQUIRE(info, "resample_plan: null pointer");
+    for (int i = 0; i < 8; ++i) info[i] = 0;
+    GRAFP_REQUIRE(orig > 0 && new_rate > 0 && width >= 0 && K == 2 * width + orig,
+                  "resample_plan: bad filter orig=%d new=%d width=%d K=%d", orig, new_rate, width, K);
+    return grafp::resample_plan(orig, new_rate, K, info);
+}
 
 extern "C" int grafp_resample_f32(const float *in, const int64_t *in_start, const int64_t *in_len,
                                   const int64_t *out_start, int n_tracks, int64_t max_in_len, int orig, int new_rate,

@@ -159,6 +159,22 @@ __global__ __launch_bounds__(DP_THREADS) void draw_pairs_kernel(const float *__r
     }
 }
 
+// The launch plan of a rate pair, written once: resample_launch and grafp_resample_plan (capi.hip) read it.  Tiles of 64
+// output blocks per workgroup: enough wave items for the 16 waves, as long as the window fits the LDS.
+// info = {JT, n_pb, K4, W, LDS bytes, output blocks j per workgroup, input samples per workgroup tile, 0}
+int resample_plan(int orig, int nw, int K, int *info) {
+    const int K4 = (K + RS_KU - 1) / RS_KU * RS_KU;
+    const int n_pb = (nw + RS_P - 1) / RS_P;
+    int JT = (RS_WAVES + n_pb - 1) / n_pb;
+    while (JT > 1 && (int64_t)(64 * JT - 1) * orig + K4 > RS_LDS_FLOATS) --JT;
+    const int64_t W = (int64_t)(64 * JT - 1) * orig + K4;
+    GRAFP_REQUIRE(W <= RS_LDS_FLOATS, "resample: rate ratio %d/%d needs a %lld-sample window (LDS holds %d)", nw, orig,
+                  (long long)W, RS_LDS_FLOATS);
+    info[0] = JT; info[1] = n_pb; info[2] = K4; info[3] = (int)W; info[4] = (int)(W * sizeof(float));
+    info[5] = 64 * JT; info[6] = 64 * JT * orig; info[7] = 0;
+    return GRAFP_OK;
+}
+
 int resample_launch(const float *in, const int64_t *in_start, const int64_t *in_len, const int64_t *out_start,
                     int n_tracks, int64_t max_in_len, int orig, int nw, int width, int K, const float *taps, float *out,
                     hipStream_t stream) {
@@ -170,20 +186,15 @@ int resample_launch(const float *in, const int64_t *in_start, const int64_t *in_
         return GRAFP_OK;
     }
     GRAFP_REQUIRE(taps, "resample: null taps");
-    const int K4 = (K + RS_KU - 1) / RS_KU * RS_KU;
-    const int n_pb = (nw + RS_P - 1) / RS_P;
-    // tiles of 64 output blocks per workgroup: enough wave items for the 16 waves, as long as the window fits the LDS
-    int JT = (RS_WAVES + n_pb - 1) / n_pb;
-    while (JT > 1 && (int64_t)(64 * JT - 1) * orig + K4 > RS_LDS_FLOATS) --JT;
-    const int64_t W = (int64_t)(64 * JT - 1) * orig + K4;
-    GRAFP_REQUIRE(W <= RS_LDS_FLOATS, "resample: rate ratio %d/%d needs a %lld-sample window (LDS holds %d)", nw, orig,
-                  (long long)W, RS_LDS_FLOATS);
+    int plan[8];
+    if (int e = resample_plan(orig, nw, K, plan)) return e;
+    const int JT = plan[0], n_pb = plan[1], K4 = plan[2];
     const int64_t max_out = (max_in_len * nw + orig - 1) / orig;
     const int64_t n_j = (max_out + nw - 1) / nw;
     const int64_t tiles = (n_j + 64 * JT - 1) / (64 * JT);
     GRAFP_REQUIRE(tiles <= 0x7fffffff, "resample: track too long");
     if (tiles == 0) return GRAFP_OK;
-    const size_t lds = (size_t)W * sizeof(float);
+    const size_t lds = (size_t)plan[4];
     if (hipFuncSetAttribute((const void *)resample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
         set_error("resample: cannot reserve %zu bytes of LDS", lds);
         return GRAFP_ERR_LAUNCH;

@@ -590,12 +590,20 @@ int grafp_mix_snr_f32(const float *x, int64_t x_stride, int B, int T, const floa
  *   r = min(floor(u0 * (len - offset_mod)), len - offset_mod - 1), ri / rj the same over offset_mod - clip (f64
  *   products); x_i = y[r+ri : r+ri+clip], x_j = y[r+rj : r+rj+clip].  The attempt is rejected when max|x_i| or
  *   max|x_j| < silence; the first accepted one is written divided by norm[track] (IEEE division).  If all A are silent
- *   the last is written and *silent_rows (may be NULL) is incremented.  Tracks used must hold >= offset_mod + 1 samples;
+ *   the last is written and *silent_rows (may be NULL) is incremented.  The comparison with silence is a strict < in f32.
+ *   A track of fewer than offset_mod + 1 samples takes r = 0 and reads zeros past its end (DeviceAudioCorpus leaves such
+ *   tracks out of its draws); a row_track outside [0, n_tracks) counts modulo n_tracks (-1 is the last track).
  *   offset_mod <= 40896.  x_i, x_j: (B, clip) row-major. */
 #define GRAFP_RESAMPLE_PHASES 10
 int grafp_resample_f32(const float *in, const int64_t *in_start, const int64_t *in_len, const int64_t *out_start,
                        int n_tracks, int64_t max_in_len, int orig, int new_rate, int width, int K, const float *taps,
                        float *out, grafp_stream_t stream);
+/* The launch plan of a rate pair (a pure host function of the filter sizes, as grafp_bn_plan; grafp_resample_f32 takes
+ * its numbers from the same function, and refuses with the same message when the window of one tile does not fit):
+ * info (host, 8 ints) = {JT: tiles of 64 output blocks per workgroup; phase blocks of GRAFP_RESAMPLE_PHASES phases;
+ *  K rounded up to a multiple of 4; window (64*JT - 1)*orig + K4 in floats; its LDS bytes; output blocks per workgroup
+ *  (64*JT); input samples a workgroup advances by (64*JT*orig); 0}.  orig == new is a copy and uses no plan. */
+int grafp_resample_plan(int orig, int new_rate, int width, int K, int *info);
 int grafp_draw_pairs_f32(const float *bank, const int64_t *track_start, const int64_t *track_len, const float *norm,
                          int n_tracks, const int32_t *row_track, const float *uniforms, int B, int A, int clip,
                          int offset_mod, float silence, float *x_i, float *x_j, int32_t *silent_rows,
