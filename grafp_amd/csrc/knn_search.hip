@@ -1206,9 +1206,9 @@ static int search_ws_check(const char *who, const void *ws, size_t ws_bytes, siz
 
 extern "C" int grafp_row_sqnorm_f32(const float *m, int64_t n, int d, float *out, grafp_stream_t stream) {
     using namespace grafp;
-    GRAFP_REQUIRE(m && out, "row_sqnorm: null pointer");
     GRAFP_REQUIRE(n >= 0 && d > 0 && d <= 152, "row_sqnorm: bad n=%lld d=%d (d <= 152)", (long long)n, d);
-    if (n == 0) return GRAFP_OK;
+    if (n == 0) return GRAFP_OK;                           // an empty matrix has no storage: its pointers may be null
+    GRAFP_REQUIRE(m && out, "row_sqnorm: null pointer");
     const size_t lds = (size_t)256 * (d + 1) * sizeof(float);
     (void)hipFuncSetAttribute((const void *)row_sqnorm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     const int64_t nb = (n + 255) / 256;

@@ -108,6 +108,7 @@ extern "C" int grafp_seq_rerank_shard_f32(const float *index_rows, int64_t n_row
                                           const int *item_len, int n_items, int max_len, int top, int64_t *out_ids,
                                           float *out_scores, grafp_stream_t stream) {
     using namespace grafp;
+    GRAFP_REQUIRE(top >= 1 && top <= 64, "seq_rerank: top=%d not in [1, 64]", top);    // first: top = 0 has null outputs
     GRAFP_REQUIRE(index_rows && q_rows && topk_ids && item_row && item_len && out_ids && out_scores,
                   "seq_rerank: null pointer");
     GRAFP_REQUIRE(n >= 1 && n < 0x7fffffffll && n_qrows >= 1 && n_items >= 0, "seq_rerank: bad n=%lld n_qrows=%lld",
@@ -118,7 +119,6 @@ extern "C" int grafp_seq_rerank_shard_f32(const float *index_rows, int64_t n_row
     GRAFP_REQUIRE(k >= 1 && max_len >= 1 && max_len <= RR_MAX_LEN && (int64_t)max_len * k <= RR_MAX_CAND,
                   "seq_rerank: max_len=%d k=%d exceed %d segments / %d candidates per item", max_len, k, RR_MAX_LEN,
                   RR_MAX_CAND);
-    GRAFP_REQUIRE(top >= 1 && top <= 64, "seq_rerank: top=%d not in [1, 64]", top);
     GRAFP_REQUIRE((((uintptr_t)index_rows | (uintptr_t)q_rows) & 15) == 0, "seq_rerank: rows must be 16-byte aligned");
     if (n_items == 0) return GRAFP_OK;
     hipLaunchKernelGGL(seq_rerank_kernel, dim3(n_items), dim3(256), 0, (hipStream_t)stream, index_rows, n, row_base,

@@ -506,7 +506,8 @@ int grafp_stride2_taps_bwd(const void *grad_out, int dtype, int64_t rows, int N,
  * Replaces faiss.IndexFlatL2 add/search as used at eval.py:54,212-213,269-270: exact squared-L2
  * top-k, ascending, ids = row index + id_base, ties -> lowest id, id -1 / dist +inf when fewer than
  * k rows exist.  Arithmetic order fixed in oracle/csrc/flat_search.c.
- *   grafp_row_sqnorm_f32: the `index.add` step -- per-row squared norms of the resident database.
+ *   grafp_row_sqnorm_f32: the `index.add` step -- per-row squared norms of the resident database
+ *   (m (n,d), d <= 152; n = 0 does nothing and m / out may then be null).
  *   db (n,d) f32   db_sqnorm (n) f32   q (nq,d) f32   d == 128   1 <= k <= GRAFP_SEARCH_MAX_K
  *   out_dist (nq,k) f32   out_ids (nq,k) int64 */
 int grafp_row_sqnorm_f32(const float *m, int64_t n, int d, float *out, grafp_stream_t stream);
