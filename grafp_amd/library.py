@@ -34,10 +34,11 @@ ingest gate asks before add().  It runs on ops.cross_match (f32 rows) or ops.cro
 csrc/crossmatch.hip, and with tempo=... on ops.cross_match_tempo (csrc/crossmatch_tempo.hip): a DJ set pitched a few
 per cent or a sped-up re-upload is then one match along its sloped alignment, not fragments of diagonals.
 
-A FingerprintLibrary lives on one device.  grafp_amd/sharded.py's ShardedFingerprintLibrary holds several flat ones over
-contiguous track ranges, one per device, and answers identify, identify_windows, timeline and match with exactly what
-the one library over the same tracks would: every shard runs the ops above unchanged (_identify_lists, _match_launch)
-and ops.merge_track_lists (csrc/merge_lists.hip) merges their lists on the device."""
+A FingerprintLibrary lives on one device.  Its query calls (identify, identify_windows, timeline, match) are
+LibraryFront's, written over the track table and three hooks: _search_rows, _identify_lists, _match_lists.
+grafp_amd/sharded.py's ShardedFingerprintLibrary is the same front over several flat libraries of contiguous track
+ranges, one per device, and answers with exactly what the one library over the same tracks would: every shard runs the
+ops above unchanged (_identify_lists, _match_launch) and ops.merge_track_lists (csrc/merge_lists.hip) merges them on chip."""
 import hashlib
 import json
 import math
@@ -140,6 +141,65 @@ def tempo_ratios(tempo, max_len, step=None):
     return nums.astype(np.int32)
 
 
+def tempo_span(lo, m, num):
+    """The other side of a span of m rows from row lo on at ratio num / 256, where row i sits w(i) = (i * num + 128) >> 8
+    rows after the other side's reference row: -> (w(lo), w(lo + m - 1) - w(lo) + 1), its first row and its rows.  At
+    num = 256: (lo, m)."""
+    half = ops.IDENTIFY_TEMPO_DEN // 2
+    w_lo, w_hi = (lo * num + half) >> 8, ((lo + m - 1) * num + half) >> 8
+    return w_lo, w_hi - w_lo + 1
+
+
+def track_table(counts):
+    """Row counts per track, in order -> the int64 track table: track t owns rows [first[t], first[t+1])."""
+    return np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+
+
+def track_names(names, n_tracks, base=0):
+    """The names of n_tracks new tracks behind `base` existing ones: str() of the given ones, or track{base + i}."""
+    names = [str(v) for v in names] if names is not None else [f"track{base + i}" for i in range(n_tracks)]
+    if len(names) != n_tracks:
+        raise ValueError(f"{len(names)} names for {n_tracks} tracks")
+    return names
+
+
+def batch_ranges(counts, limit):
+    """The batching rule of self_matches and match over items of counts[i] rows: a batch of consecutive items closes
+    once it holds at least `limit` rows (limit <= 0: every item alone), the last takes the rest.  -> ranges (i0, i1)."""
+    out, i0, held = [], 0, 0
+    for i, n in enumerate(counts):
+        held += int(n)
+        if held >= limit or i == len(counts) - 1:
+            out.append((i0, i + 1))
+            i0, held = i + 1, 0
+    return out
+
+
+def span_slots(res, sources, has_ratio, min_score, what):
+    """The walk over the outputs of a span op (ops.self_match, ops.cross_match, their kin): res = (partner, delta, start,
+    length, score, votes[, ratio]), each (len(sources), top), read back here.  Yields (source, partner, ..., votes, ratio
+    or None) per filled slot: a negative partner ends a source, a score under min_score is skipped, the -2 mark raises."""
+    cols = [x.cpu().numpy() for x in res[:7 if has_ratio else 6]]
+    for s, src in enumerate(sources):
+        for j in range(cols[0].shape[1]):
+            b = int(cols[0][s, j])
+            if b == -2:                                              # the op sizes the workspace exactly: never
+                raise RuntimeError(f"{what} {src} did not fit the workspace")
+            if b < 0:
+                break
+            sc = float(cols[4][s, j])
+            if min_score is not None and sc < min_score:
+                continue
+            yield (src, b, int(cols[1][s, j]), int(cols[2][s, j]), int(cols[3][s, j]), sc, int(cols[5][s, j]),
+                   int(cols[6][s, j]) if has_ratio else None)
+
+
+def is_single(queries):
+    """Whether identify and match were given one query (a path or a 1-D waveform) and answer with its list alone."""
+    return isinstance(queries, str) or (isinstance(queries, (np.ndarray, torch.Tensor)) and
+                                        torch.as_tensor(queries).dim() == 1)
+
+
 def _as_waveforms(tracks):
     """A DeviceAudioCorpus (-> every track and its file names), its .tracks(), or 1-D tensors / arrays."""
     from .data import DeviceAudioCorpus
@@ -152,47 +212,38 @@ def _as_waveforms(tracks):
     return list(tracks), None
 
 
-class FingerprintLibrary:
-    """Fingerprints of whole tracks, resident on one device, with the table that says which rows are which track."""
+class LibraryFront:
+    """The query front of a fingerprint library: the sizes, the refusals, fingerprinting and identify, identify_windows,
+    timeline and match, written once over the shared state -- model, settings, precision, device (where the model runs
+    and the queries are embedded), first, names and _row_stride.  A library (FingerprintLibrary,
+    sharded.ShardedFingerprintLibrary) derives from it and implements is_compact and the three hooks _search_rows,
+    _identify_lists and _match_lists: the interface that StreamMonitor, the sharded library and the tools rely on."""
 
-    def __init__(self, model, settings, rows, first, names=None, precision="bf16", device=None, row_stride=1):
-        if precision not in ("bf16", "f32"):
-            raise ValueError(f"precision must be 'bf16' or 'f32', not {precision!r}")
-        if not 1 <= int(row_stride) <= ops.IDENTIFY_MAX_STRIDE:
-            raise ValueError(f"row_stride={row_stride} not in [1, {ops.IDENTIFY_MAX_STRIDE}]")
-        self._row_stride = int(row_stride)
-        self.model = model
-        self.device = torch.device(device) if device is not None else next(model.parameters()).device
+    def __init__(self, model, settings, precision, device, row_stride):
+        self.model, self.device, self.precision, self._row_stride = model, device, precision, int(row_stride)
         self.settings = {k: settings[k] for k in SETTINGS}
-        self.precision = precision
-        self._chunks, self._rows, self._index = [], None, None
-        self._pq = None                   # compact form: {"centroids", "codebooks", "nprobe"}
-        self._code_chunks, self._codes, self._encoder = [], None, None      # chunks of (list_id int32, codes uint8)
-        self.first = np.zeros(1, np.int64)
-        self.names = []
-        if rows is not None:
-            self._append(rows, first, names)
+        self.first, self.names = np.zeros(1, np.int64), []
 
-    @classmethod
-    def from_codes(cls, model, settings, quantiser, list_id, codes, first, names=None, precision="bf16", device=None,
-                   nprobe=20):
-        """A compact library over rows that are already encoded: quantiser {"centroids" (nlist, 128), "codebooks"
-        (M, 256, 128 // M)}, list_id (n) and codes (n, M) uint8 in row order, the track table as for the constructor.
-        Works on device="cpu" (files and tables only), like the flat form."""
-        lib = cls(model, settings, None, None, precision=precision, device=device)
-        lib._set_quantiser(quantiser, nprobe)
-        lib._append_codes(list_id, codes, first, names)
-        return lib
+    # ---- what a library implements ----------------------------------------------------------------------------
+    @property
+    def is_compact(self):
+        """Whether the library holds IVF-PQ codes and no f32 rows."""
+        raise NotImplementedError
 
-    def _set_quantiser(self, quantiser, nprobe):
-        cent = torch.as_tensor(quantiser["centroids"]).to(self.device, torch.float32).contiguous()
-        books = torch.as_tensor(quantiser["codebooks"]).to(self.device, torch.float32).contiguous()
-        M = int(books.shape[0]) if books.dim() == 3 else 0
-        if M not in ops.IDENTIFY_PQ_M or cent.dim() != 2 or cent.shape[1] != 128 or cent.shape[0] < 1 or \
-                tuple(books.shape) != (M, 256, 128 // M):
-            raise ValueError(f"a compact library needs centroids (nlist, 128) and codebooks (M, 256, 128 // M) with M "
-                             f"one of {ops.IDENTIFY_PQ_M}, not {tuple(cent.shape)} and {tuple(books.shape)}")
-        self._pq = {"centroids": cent, "codebooks": books, "nprobe": int(nprobe)}
+    def _search_rows(self, q, k_probe):
+        """q (n, 128) f32 -> ids (n, min(k_probe, n_rows)) int64, each row's nearest library rows, on the device."""
+        raise NotImplementedError
+
+    def _identify_lists(self, q, ids, item_row, item_len, top, min_overlap, max_len, nums=None):
+        """The launch of _identify_items -> the op's device tensors (track, offset, score, votes and, with the ratio
+        grid nums, ratio), nothing read back."""
+        raise NotImplementedError
+
+    def _match_lists(self, qb, src, k_probe, nums, kw):
+        """The search and the launch of one batch of _match_rows: qb the batch's rows, src its source table (a host
+        tensor) -> the op's device tensors (track, delta, start, length, score, votes and, with nums, ratio), nothing
+        read back."""
+        raise NotImplementedError
 
     # ---- sizes -----------------------------------------------------------------------------------------------
     @property
@@ -212,10 +263,6 @@ class FingerprintLibrary:
         return int(self.first[-1])
 
     @property
-    def is_compact(self):
-        return self._pq is not None
-
-    @property
     def row_stride(self):
         """D: row j of a track is the track's segment j * D (a dense library: 1).  Offsets stay in segments."""
         return self._row_stride
@@ -225,125 +272,15 @@ class FingerprintLibrary:
             raise NotImplementedError(f"FingerprintLibrary.{what} needs every row of a track: this library keeps every "
                                       f"{self._row_stride}th (row_stride={self._row_stride})")
 
-    def quantiser(self):
-        """{"centroids", "codebooks"} of a compact library (device tensors)."""
-        self._need_compact("quantiser()")
-        return {"centroids": self._pq["centroids"], "codebooks": self._pq["codebooks"]}
-
-    def codes(self):
-        """(list_id (n_rows) int32, codes (n_rows, M) uint8) of a compact library, in row order."""
-        self._need_compact("codes()")
-        if self._codes is None:
-            M = int(self._pq["codebooks"].shape[0])
-            parts = self._code_chunks or [(torch.zeros(0, dtype=torch.int32, device=self.device),
-                                           torch.zeros((0, M), dtype=torch.uint8, device=self.device))]
-            self._codes = (parts[0] if len(parts) == 1 else
-                           (torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])))
-            self._code_chunks = [self._codes] if self._code_chunks else []
-        return self._codes
-
-    def _need_compact(self, what):
-        if not self.is_compact:
-            raise ValueError(f"FingerprintLibrary.{what}: this is a flat library (f32 rows); compress() makes a "
-                             "compact one")
-
     def _need_flat(self, what):
         if self.is_compact:
             raise NotImplementedError(f"FingerprintLibrary.{what} needs the flat form of a library (f32 rows): this one "
                                       "is compact and holds IVF-PQ codes only")
 
-    @property
-    def nbytes(self):
-        """Device bytes the library holds: its rows (flat) or its row-order codes, list ids and quantiser (compact),
-        plus its index, which is made here if the device has one (on a CPU device only the library's own tensors count).
-        Flat: 772 bytes per row.  Compact: 2 M + 20 per row, plus the quantiser and the index's two nlist-sized tables."""
-        if self.is_compact:
-            held = list(self.codes()) + [self._pq["centroids"], self._pq["codebooks"]]
-        else:
-            held = [self.rows()]
-        if self.device.type == "cuda" and self.n_rows:
-            index = self.index
-            if self.is_compact:
-                held += index.held_tensors()
-            else:
-                index._materialise()
-                held += [index._db, index._sq, index._bf16]
-        seen = {}
-        for t in held:
-            if t is not None:
-                seen[t.untyped_storage().data_ptr()] = t.untyped_storage().nbytes()
-        return int(sum(seen.values()))
-
-    def rows(self):
-        """The resident (n_rows, 128) f32 fingerprints (flat form only)."""
-        self._need_flat("rows()")
-        if self._rows is None:
-            self._rows = (self._chunks[0] if len(self._chunks) == 1 else
-                          torch.cat(self._chunks) if self._chunks else torch.zeros((0, 128), device=self.device))
-            self._chunks = [self._rows] if self._chunks else []
-        return self._rows
-
-    @property
-    def index(self):
-        """The index over the rows, made on first use: the ops.FlatL2Index over rows() (it shares the rows tensor), or,
-        for a compact library, the ivfpq.IVFPQIndex over codes() (from_codes: nothing is re-encoded, the row-order codes
-        are shared)."""
-        if self._index is None:
-            if self.is_compact:
-                from .ivfpq import IVFPQIndex
-                list_id, codes = self.codes()
-                self._index = IVFPQIndex.from_codes(self.quantiser(), list_id, codes, self.device, self._pq["nprobe"])
-            else:
-                self._index = ops.FlatL2Index(d=128, device=self.device)
-                self._index.add(self.rows())
-        return self._index
-
-    def _append_table(self, first, n_new, names):
-        first = np.asarray(first, np.int64).reshape(-1)
-        ops.check_track_table(first, n_new)
-        T = len(first) - 1
-        names = [str(v) for v in names] if names is not None else [f"track{self.n_tracks + i}" for i in range(T)]
-        if len(names) != T:
-            raise ValueError(f"{len(names)} names for {T} tracks")
-        return first, names
-
-    def _append(self, rows, first, names):
-        self._need_flat("_append()")
-        rows = torch.as_tensor(rows).to(self.device, torch.float32).reshape(-1, 128)
-        first, names = self._append_table(first, rows.shape[0], names)
-        if rows.shape[0]:
-            self._chunks.append(rows.contiguous())
-            self._rows, self._index = None, None
-        self.first = np.concatenate([self.first, self.first[-1] + first[1:]])
-        self.names += names
-
-    def _append_codes(self, list_id, codes, first, names):
-        self._need_compact("_append_codes()")
-        M, nlist = int(self._pq["codebooks"].shape[0]), int(self._pq["centroids"].shape[0])
-        codes, list_id = torch.as_tensor(codes), torch.as_tensor(list_id).reshape(-1)
-        if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.shape[1] != M:
-            raise ValueError(f"codes must be (n, {M}) uint8, not {tuple(codes.shape)} {codes.dtype}")
-        if list_id.shape[0] != codes.shape[0] or list_id.dtype not in (torch.int32, torch.int64):
-            raise ValueError(f"{list_id.shape[0]} list ids ({list_id.dtype}) for {codes.shape[0]} rows of codes")
-        if list_id.numel() and not 0 <= int(list_id.min()) <= int(list_id.max()) < nlist:
-            raise ValueError(f"a list id lies outside [0, {nlist})")
-        first, names = self._append_table(first, codes.shape[0], names)
-        if codes.shape[0]:
-            self._code_chunks.append((list_id.to(self.device, torch.int32).contiguous(),
-                                      codes.to(self.device).contiguous()))
-            self._codes, self._index = None, None
-        self.first = np.concatenate([self.first, self.first[-1] + first[1:]])
-        self.names += names
-
-    def _encode(self, rows):
-        """f32 rows on the device -> (list_id int32, codes uint8) with the library's quantiser (csrc/ivfpq.hip)."""
-        if self._encoder is None:
-            from .ivfpq import IVFPQIndex
-            M = int(self._pq["codebooks"].shape[0])
-            self._encoder = IVFPQIndex.from_codes(self.quantiser(), torch.zeros(0, dtype=torch.int32),
-                                                  torch.zeros((0, M), dtype=torch.uint8), self.device)
-        a, codes = self._encoder.encode(rows)
-        return a.to(torch.int32), codes
+    def _need_tempo_form(self, what, tempo):
+        if tempo is not None:
+            self._need_flat(f"{what}(tempo=...)")
+            self._need_dense(f"{what}(tempo=...)")
 
     # ---- fingerprinting --------------------------------------------------------------------------------------
     def _autocast(self):
@@ -393,6 +330,402 @@ class FingerprintLibrary:
         out = list(self._fingerprint_batches(waves, max_segments, counts))
         rows = torch.cat(out, dim=0) if out else torch.zeros((0, 128), device=self.device)
         return rows, counts
+
+    # ---- queries ---------------------------------------------------------------------------------------------
+    def _load_queries(self, queries, fs):
+        """-> list of 1-D device waveforms at settings['fs']."""
+        from .data import read_audio
+        fs0 = int(self.settings["fs"])
+        if isinstance(queries, str):
+            queries = [queries]
+        elif isinstance(queries, (np.ndarray, torch.Tensor)):
+            queries = [queries] if queries.ndim <= 1 else list(queries)
+        waves, rates = [], []
+        for q in queries:
+            if isinstance(q, str):
+                a, r = read_audio(q, fs0 if fs is None else fs)
+            else:
+                a, r = q, (fs0 if fs is None else fs)
+            waves.append(torch.as_tensor(np.asarray(a, np.float32) if isinstance(a, np.ndarray) else a)
+                         .to(self.device, torch.float32).reshape(-1))
+            rates.append(int(r))
+        for r in sorted(set(rates)):
+            if r == fs0:
+                continue
+            ids = [i for i, v in enumerate(rates) if v == r and waves[i].numel()]
+            if not ids:
+                continue
+            lens = torch.tensor([waves[i].numel() for i in ids], dtype=torch.int64)
+            bank = torch.cat([waves[i] for i in ids])
+            out, starts, out_lens = ops.resample(bank, torch.cumsum(lens, 0) - lens, lens, r, fs0)
+            starts, out_lens = starts.cpu().tolist(), out_lens.cpu().tolist()
+            for j, i in enumerate(ids):
+                waves[i] = out[starts[j]:starts[j] + out_lens[j]]
+        return waves
+
+    def _check_item_len(self, max_len, k_probe):
+        if max_len > ops.IDENTIFY_MAX_LEN or max_len * k_probe > ops.IDENTIFY_MAX_KEYS:
+            raise ValueError(f"a query of {max_len} segments ({max_len * self.segment_s:.1f} s) with k_probe={k_probe} "
+                             f"exceeds {ops.IDENTIFY_MAX_LEN} segments / {ops.IDENTIFY_MAX_KEYS} hits per item: use "
+                             "identify_windows for long recordings")
+
+    def _embed_and_search(self, segs, k_probe):
+        """One batched embed of the segments and one search of their rows -> (q (n, 128) f32, ids (n, k) int64)."""
+        q = self._embed(segs)
+        return q, self._search_rows(q, k_probe)
+
+    def _identify_items(self, q, ids, item_row, item_len, top, min_overlap, max_len=None, tempo=None, tempo_step=None):
+        """One identify launch (the kernel of the library's form) for all items over the rows q and their hits ids ->
+        per-item lists of matches.  max_len: an upper bound of the items' lengths (None: the longest).  (StreamMonitor
+        calls it with rows it kept from earlier pushes.)  tempo: tempo_ratios' argument; the launch is then
+        ops.identify_tempo over the ratio grid of the longest item, and every match names its ratio."""
+        n_items = len(item_row)
+        longest = int(np.max(item_len, initial=0))
+        if n_items == 0 or longest == 0:
+            return [[] for _ in range(n_items)]
+        max_len = longest if max_len is None else max(int(max_len), longest)
+        nums = None if tempo is None else tempo_ratios(tempo, longest, tempo_step)
+        lists = self._identify_lists(q, ids, np.asarray(item_row, np.int64), np.asarray(item_len, np.int32), top,
+                                     min_overlap, max_len, nums)
+        tr, off, sc, vo = (t.cpu().numpy() for t in lists[:4])
+        ra = lists[4].cpu().numpy() if nums is not None else None
+        step, hop, fs = self.step, self.settings["hop_len"], self.settings["fs"]
+        out = []
+        for i in range(n_items):
+            res = []
+            for j in range(top):
+                t = int(tr[i, j])
+                if t < 0:
+                    break
+                res.append({"track": t, "name": self.names[t], "offset": int(off[i, j]),
+                            "offset_s": int(off[i, j]) * step * hop / fs, "score": float(sc[i, j]),
+                            "votes": int(vo[i, j])})
+                if ra is not None:
+                    res[-1]["tempo"] = int(ra[i, j]) / ops.IDENTIFY_TEMPO_DEN
+                    res[-1]["tempo_num"] = int(ra[i, j])
+            out.append(res)
+        return out
+
+    def _search_and_identify(self, segs, item_row, item_len, top, k_probe, min_overlap, tempo=None, tempo_step=None):
+        """One batched embed + search of all segments, one ops.identify launch for all items -> per-item lists.  (The
+        queries' segments are all embedded, whatever the library's row_stride: the query side stays dense.)"""
+        n_items = len(item_row)
+        if tempo is not None:
+            tempo_ratios(tempo, max(1, int(np.max(item_len, initial=0))), tempo_step)      # refuse a bad range early
+        if n_items == 0 or segs.shape[0] == 0 or self.n_rows == 0 or int(np.max(item_len, initial=0)) == 0:
+            return [[] for _ in range(n_items)]
+        self._check_item_len(int(np.max(item_len)), k_probe)
+        q, ids = self._embed_and_search(segs, k_probe)
+        return self._identify_items(q, ids, item_row, item_len, top, min_overlap, tempo=tempo, tempo_step=tempo_step)
+
+    def identify(self, queries, fs=None, top=5, k_probe=20, min_overlap=None, tempo=None, tempo_step=None):
+        """queries: one waveform, a list of ragged waveforms, or file paths; at `fs` (default settings['fs']; other rates
+        are resampled on the device).  -> per query, a list of matches {track, name, offset, offset_s, score, votes},
+        best first.  offset_s = offset * step * hop_len / fs is where the query's first segment sits in the track.  A
+        query shorter than one segment gives an empty list.
+        tempo: None, or the speeds to search for a recording that plays faster or slower than the catalogue -- a float
+        x in (0, 0.5] for the ratios [1 - x, 1 + x] (track seconds per recording second), or a pair (lo, hi);
+        tempo_step: the ratio grid's spacing in 1/256 (tempo_ratios; default: from the longest query).  The segments
+        are embedded and searched as without it and one ops.identify_tempo launch scores every candidate along the
+        sloped alignment of every ratio; each match then also carries "tempo" (the ratio) and "tempo_num" (ratio *
+        256), and offset / offset_s keep their meaning.  Needs a flat library that keeps every row.  Speed only: pitch
+        is not searched; match() takes the same tempo for whole recordings and self_matches() for the tracks of the
+        library itself; StreamMonitor, the IVF-PQ and the thinned forms know no tempo."""
+        self._need_tempo_form("identify", tempo)
+        single = is_single(queries)
+        waves = self._load_queries(queries, fs)
+        segs = [self.segments(w) for w in waves]
+        lens = np.array([s.shape[0] for s in segs], np.int32)
+        allsegs = torch.cat(segs, dim=0) if segs else torch.empty((0,), device=self.device)
+        res = self._search_and_identify(allsegs, track_table(lens)[:-1], lens, int(top), int(k_probe), min_overlap,
+                                        tempo, tempo_step)
+        return res[0] if single and len(res) == 1 else res
+
+    def identify_windows(self, recording, window_s=3.0, hop_s=1.0, fs=None, top=5, k_probe=20, min_overlap=None,
+                         tempo=None, tempo_step=None):
+        """A long recording cut into items of window_s seconds every hop_s seconds.  The recording is segmented,
+        fingerprinted and searched once; all windows are identified in one launch.  -> per window
+        {start_s, end_s, segment_start_s, matches}; segment_start_s is where the window's first segment starts in the
+        recording (the time its matches' offset_s refers to).  tempo, tempo_step: as for identify()."""
+        self._need_tempo_form("identify_windows", tempo)
+        wave = self._load_queries([recording], fs)[0]
+        segs = self.segments(wave)
+        starts, rows, lens = window_items(segs.shape[0], wave.numel(), self.settings, window_s, hop_s)
+        res = self._search_and_identify(segs, rows, lens, int(top), int(k_probe), min_overlap, tempo, tempo_step)
+        seg_s = self.segment_s
+        return [{"start_s": float(s), "end_s": float(s) + window_s, "segment_start_s": int(r) * seg_s, "matches": m}
+                for s, r, m in zip(starts, rows, res)]
+
+    def timeline(self, windows, min_score=None):
+        """What played when: consecutive windows whose best match is the same track at a consistent position (the
+        track offset minus the window's segment start agrees within one segment hop) merge into one span.
+        -> list of {start_s, end_s, track, name, track_offset_s (the track position at start_s), score (mean)}.
+        A window whose match carries a "tempo" rho (identify_windows(tempo=...)) is followed along its slope: the span
+        keeps its last merged window (u = segment_start_s, o = offset_s, rho), and the next window (u', o') of the same
+        track merges iff |o' - (o + rho * (u' - u))| is within one segment hop and it starts no later than the span's
+        end; the reference point then advances.  Such a span also reports "tempo", the mean of its windows' rho."""
+        spans, seg_s = [], self.segment_s
+        for w in windows:
+            if not w["matches"] or (min_score is not None and w["matches"][0]["score"] < min_score):
+                continue
+            m = w["matches"][0]
+            if "tempo" in m:
+                u, o, rho = w["segment_start_s"], m["offset_s"], m["tempo"]
+                last = spans[-1] if spans else None
+                if (last is not None and last["track"] == m["track"] and "_ref" in last
+                        and abs(o - (last["_ref"][1] + last["_ref"][2] * (u - last["_ref"][0]))) <= seg_s + 1e-9
+                        and w["start_s"] <= last["end_s"]):
+                    last["end_s"] = w["end_s"]
+                    last["_scores"].append(m["score"])
+                    last["_tempos"].append(rho)
+                else:
+                    spans.append({"start_s": w["start_s"], "end_s": w["end_s"], "track": m["track"], "name": m["name"],
+                                  "track_offset_s": o + rho * (w["start_s"] - u), "_scores": [m["score"]],
+                                  "_tempos": [rho]})
+                spans[-1]["_ref"] = (u, o, rho)
+                continue
+            delta = m["offset_s"] - w["segment_start_s"]              # track time = recording time + delta
+            last = spans[-1] if spans else None
+            if (last is not None and last["track"] == m["track"] and "_delta" in last
+                    and abs(delta - last["_delta"]) <= seg_s + 1e-9
+                    and w["start_s"] <= last["end_s"]):
+                last["end_s"] = w["end_s"]
+                last["_scores"].append(m["score"])
+            else:
+                spans.append({"start_s": w["start_s"], "end_s": w["end_s"], "track": m["track"], "name": m["name"],
+                              "track_offset_s": w["start_s"] + delta, "_delta": delta, "_scores": [m["score"]]})
+        for s in spans:
+            s["score"] = float(np.mean(s.pop("_scores")))
+            s.pop("_delta", None)
+            if s.pop("_ref", None) is not None:
+                s["tempo"] = float(np.mean(s.pop("_tempos")))
+        return spans
+
+    # ---- recordings against the catalog -------------------------------------------------------------------------
+    def match(self, recordings, fs=None, k_probe=20, min_overlap_s=3.0, min_votes=4, min_score=None, top=8,
+              max_segments=4096, batch_rows=1 << 18, tempo=None, tempo_step=None):
+        """What whole recordings share with the library: is an upload already in the catalogue, in whole or in part,
+        which tracks does a mix or medley contain, and where.  recordings: as identify's queries (one waveform, a list
+        of ragged waveforms, or file paths, at `fs`; other rates are resampled on the device), of any length.  They are
+        segmented, embedded in model calls of at least max_segments segments, searched with self.index (k_probe hits per
+        row) and matched in launches of about batch_rows rows by ops.cross_match (flat) or ops.cross_match_pq (compact);
+        nothing is added to the library.
+        -> per recording, a list of {track, name, score, votes, offset, recording_start_s, track_start_s, overlap_s,
+        coverage, recording_coverage, track_coverage}, best first (a single recording: its list alone, as identify).  The
+        recording's audio from recording_start_s reappears in `track` from track_start_s for overlap_s seconds; offset =
+        delta in segments (row i of the recording sits on row i + offset of the track); coverage = overlapping rows /
+        rows of the shorter of the two, recording_coverage and track_coverage the same over the rows of each; score =
+        mean cosine over the span; votes = rows whose hits agree on the alignment.  At most `top` tracks per recording,
+        each at its best alignment.  min_overlap_s, min_votes and min_score as for self_matches.  A recording shorter
+        than one segment, or an empty library, gives [].
+        k_probe = 20 is identify's default; it has not been measured for this use (self_matches uses 32 because it
+        drops a row's hits on its own track; nothing is dropped here).
+        One recording is one workgroup, as a track is in self_matches: an hour-long recording is not split into pieces,
+        its hits are sorted through the launch's workspace (ops.self_match_workspace_bytes of the batch's row counts).
+        tempo: None, or the speeds to search, as identify takes them (a float x for the ratios [1 - x, 1 + x] of track
+        seconds per recording second, or a pair (lo, hi)); tempo_step: the ratio grid's spacing in 1/256, by default 1
+        (recordings are long: at a coarser grid the nearest ratio drifts off a long span).  The launches then go to
+        ops.cross_match_tempo, R ratios at once, in batches of about batch_rows // R rows (the workspace is R times a
+        dense launch's), and row i of the recording sits on row offset + w(i) of the track, w(i) = (i * tempo_num + 128)
+        >> 8.  Each match also carries tempo (= tempo_num / 256), tempo_num and track_overlap_s = (w(i_hi) - w(i_lo) +
+        1) segment hops, the track's side of the span; track_start_s = (offset + w(i_lo)) hops, recording_coverage = m /
+        recording rows, track_coverage = (w(i_hi) - w(i_lo) + 1) / track rows, coverage the larger of the two (at 256:
+        the dense m / min).  When the true ratio lies between two grid ratios a long span drifts off its alignment by
+        up to a row per 512 rows and may end early: overlap_s is then a lower bound of the shared audio.  Needs a flat
+        library that keeps every row."""
+        self._need_tempo_form("match", tempo)
+        self._need_dense("match()")
+        nums = None if tempo is None else tempo_ratios(tempo, ops.IDENTIFY_TEMPO_DEN, tempo_step)   # step 1 by default
+        single = is_single(recordings)
+        waves = self._load_queries(recordings, fs)
+        if self.n_rows == 0:
+            res = [[] for _ in waves]
+        else:
+            rows, counts = self._fingerprint_tracks(waves, int(max_segments))
+            res = self._match_rows(rows, counts, int(k_probe), float(min_overlap_s), int(min_votes), min_score,
+                                   int(top), int(batch_rows), nums)
+        return res[0] if single and len(res) == 1 else res
+
+    def _match_entry(self, b, d, lo, m, sc, v, n_rec, num=None):
+        """One match of match() from one slot of the kernel's outputs: partner b, delta d, span start lo, span rows m,
+        score, votes, for a recording of n_rec rows; num: the winning ratio of ops.cross_match_tempo (None: dense)."""
+        seg_s = self.segment_s
+        lr, lt = max(1, int(n_rec)), max(1, int(self.first[b + 1] - self.first[b]))
+        w_lo, mt = (lo, m) if num is None else tempo_span(lo, m, num)     # the track's side of the span (dense: the same)
+        entry = {"track": b, "name": self.names[b], "score": sc, "votes": v,
+                 "offset": d, "recording_start_s": lo * seg_s, "track_start_s": (d + w_lo) * seg_s,
+                 "overlap_s": m * seg_s, "coverage": max(m / lr, mt / lt),
+                 "recording_coverage": m / lr, "track_coverage": mt / lt}
+        if num is not None:
+            entry.update({"tempo": num / ops.IDENTIFY_TEMPO_DEN, "tempo_num": num, "track_overlap_s": mt * seg_s})
+        return entry
+
+    def _match_rows(self, q, counts, k_probe, min_overlap_s, min_votes, min_score, top, batch_rows, nums=None):
+        """match() from the recordings' rows on: q (n_q, 128) f32 on the device, counts the rows of each recording.
+        nums: the ratio grid of match(tempo=...) (None: the dense kernels)."""
+        min_overlap = max(1, int(math.ceil(min_overlap_s / self.segment_s - 1e-9)))
+        starts = track_table(counts)
+        out = [[] for _ in counts]
+        if nums is not None:
+            batch_rows = batch_rows // len(nums)                     # the workspace is R times a dense launch's
+        for s0, s1 in batch_ranges(counts, batch_rows):
+            qb = q[int(starts[s0]):int(starts[s1])]
+            if qb.shape[0]:
+                res = self._match_lists(qb, torch.from_numpy(starts[s0:s1 + 1] - starts[s0]), k_probe, nums,
+                                        dict(top=top, min_votes=min_votes, min_overlap=min_overlap))
+                for s, b, d, lo, m, sc, v, num in span_slots(res, range(s0, s1), nums is not None, min_score,
+                                                             "cross_match: recording"):
+                    out[s].append(self._match_entry(b, d, lo, m, sc, v, counts[s], num))
+        return out
+
+
+class FingerprintLibrary(LibraryFront):
+    """Fingerprints of whole tracks, resident on one device, with the table that says which rows are which track."""
+
+    def __init__(self, model, settings, rows, first, names=None, precision="bf16", device=None, row_stride=1):
+        if precision not in ("bf16", "f32"):
+            raise ValueError(f"precision must be 'bf16' or 'f32', not {precision!r}")
+        if not 1 <= int(row_stride) <= ops.IDENTIFY_MAX_STRIDE:
+            raise ValueError(f"row_stride={row_stride} not in [1, {ops.IDENTIFY_MAX_STRIDE}]")
+        super().__init__(model, settings, precision,
+                         torch.device(device) if device is not None else next(model.parameters()).device, row_stride)
+        # the rows: chunks of (rows f32,), or in the compact form of (list_id int32, codes uint8), as they were appended
+        self._chunks, self._held, self._index = [], None, None
+        self._pq, self._encoder = None, None       # compact form: {"centroids", "codebooks", "nprobe"}
+        if rows is not None:
+            self._append(rows, first, names)
+
+    @classmethod
+    def from_codes(cls, model, settings, quantiser, list_id, codes, first, names=None, precision="bf16", device=None,
+                   nprobe=20):
+        """A compact library over rows that are already encoded: quantiser {"centroids" (nlist, 128), "codebooks"
+        (M, 256, 128 // M)}, list_id (n) and codes (n, M) uint8 in row order, the track table as for the constructor.
+        Works on device="cpu" (files and tables only), like the flat form."""
+        lib = cls(model, settings, None, None, precision=precision, device=device)
+        lib._set_quantiser(quantiser, nprobe)
+        lib._append_codes(list_id, codes, first, names)
+        return lib
+
+    def _set_quantiser(self, quantiser, nprobe):
+        cent = torch.as_tensor(quantiser["centroids"]).to(self.device, torch.float32).contiguous()
+        books = torch.as_tensor(quantiser["codebooks"]).to(self.device, torch.float32).contiguous()
+        M = int(books.shape[0]) if books.dim() == 3 else 0
+        if M not in ops.IDENTIFY_PQ_M or cent.dim() != 2 or cent.shape[1] != 128 or cent.shape[0] < 1 or \
+                tuple(books.shape) != (M, 256, 128 // M):
+            raise ValueError(f"a compact library needs centroids (nlist, 128) and codebooks (M, 256, 128 // M) with M "
+                             f"one of {ops.IDENTIFY_PQ_M}, not {tuple(cent.shape)} and {tuple(books.shape)}")
+        self._pq, self._held = {"centroids": cent, "codebooks": books, "nprobe": int(nprobe)}, None
+
+    @property
+    def is_compact(self):
+        return self._pq is not None
+
+    def quantiser(self):
+        """{"centroids", "codebooks"} of a compact library (device tensors)."""
+        self._need_compact("quantiser()")
+        return {"centroids": self._pq["centroids"], "codebooks": self._pq["codebooks"]}
+
+    def _need_compact(self, what):
+        if not self.is_compact:
+            raise ValueError(f"FingerprintLibrary.{what}: this is a flat library (f32 rows); compress() makes a "
+                             "compact one")
+
+    @property
+    def nbytes(self):
+        """Device bytes the library holds: its rows (flat) or its row-order codes, list ids and quantiser (compact),
+        plus its index, which is made here if the device has one (on a CPU device only the library's own tensors count).
+        Flat: 772 bytes per row.  Compact: 2 M + 20 per row, plus the quantiser and the index's two nlist-sized tables."""
+        held = list(self._stored()) + ([self._pq["centroids"], self._pq["codebooks"]] if self.is_compact else [])
+        if self.device.type == "cuda" and self.n_rows:
+            index = self.index
+            if self.is_compact:
+                held += index.held_tensors()
+            else:
+                index._materialise()
+                held += [index._db, index._sq, index._bf16]
+        seen = {t.untyped_storage().data_ptr(): t.untyped_storage().nbytes() for t in held if t is not None}
+        return int(sum(seen.values()))
+
+    def _stored(self):
+        """All rows as one tuple of tensors, (rows,) or (list_id, codes): the chunks concatenated on first use and kept
+        as the one chunk; a library without rows gives its form's empty tensors."""
+        if self._held is None:
+            if len(self._chunks) > 1:
+                self._chunks = [tuple(torch.cat(part) for part in zip(*self._chunks))]
+            if self._chunks:
+                self._held = self._chunks[0]
+            elif self.is_compact:
+                M = int(self._pq["codebooks"].shape[0])
+                self._held = (torch.zeros(0, dtype=torch.int32, device=self.device),
+                              torch.zeros((0, M), dtype=torch.uint8, device=self.device))
+            else:
+                self._held = (torch.zeros((0, 128), device=self.device),)
+        return self._held
+
+    def rows(self):
+        """The resident (n_rows, 128) f32 fingerprints (flat form only)."""
+        self._need_flat("rows()")
+        return self._stored()[0]
+
+    def codes(self):
+        """(list_id (n_rows) int32, codes (n_rows, M) uint8) of a compact library, in row order."""
+        self._need_compact("codes()")
+        return self._stored()
+
+    @property
+    def index(self):
+        """The index over the rows, made on first use: the ops.FlatL2Index over rows() (it shares the rows tensor), or,
+        for a compact library, the ivfpq.IVFPQIndex over codes() (from_codes: nothing is re-encoded, the row-order codes
+        are shared)."""
+        if self._index is None:
+            if self.is_compact:
+                from .ivfpq import IVFPQIndex
+                list_id, codes = self.codes()
+                self._index = IVFPQIndex.from_codes(self.quantiser(), list_id, codes, self.device, self._pq["nprobe"])
+            else:
+                self._index = ops.FlatL2Index(d=128, device=self.device)
+                self._index.add(self.rows())
+        return self._index
+
+    def _store(self, n_new, chunk, first, names):
+        """The tail of _append and _append_codes: n_new rows of new tracks with their own table `first` go behind the
+        library's.  chunk() -> their tuple of device tensors, asked for only if there are rows."""
+        first = np.asarray(first, np.int64).reshape(-1)
+        ops.check_track_table(first, n_new)
+        names = track_names(names, len(first) - 1, self.n_tracks)
+        if n_new:
+            self._chunks.append(chunk())
+            self._held, self._index = None, None
+        self.first = np.concatenate([self.first, self.first[-1] + first[1:]])
+        self.names += names
+
+    def _append(self, rows, first, names):
+        self._need_flat("_append()")
+        rows = torch.as_tensor(rows).to(self.device, torch.float32).reshape(-1, 128)
+        self._store(rows.shape[0], lambda: (rows.contiguous(),), first, names)
+
+    def _append_codes(self, list_id, codes, first, names):
+        self._need_compact("_append_codes()")
+        M, nlist = int(self._pq["codebooks"].shape[0]), int(self._pq["centroids"].shape[0])
+        codes, list_id = torch.as_tensor(codes), torch.as_tensor(list_id).reshape(-1)
+        if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.shape[1] != M:
+            raise ValueError(f"codes must be (n, {M}) uint8, not {tuple(codes.shape)} {codes.dtype}")
+        if list_id.shape[0] != codes.shape[0] or list_id.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"{list_id.shape[0]} list ids ({list_id.dtype}) for {codes.shape[0]} rows of codes")
+        if list_id.numel() and not 0 <= int(list_id.min()) <= int(list_id.max()) < nlist:
+            raise ValueError(f"a list id lies outside [0, {nlist})")
+        self._store(codes.shape[0], lambda: (list_id.to(self.device, torch.int32).contiguous(),
+                                             codes.to(self.device).contiguous()), first, names)
+
+    def _encode(self, rows):
+        """f32 rows on the device -> (list_id int32, codes uint8) with the library's quantiser (csrc/ivfpq.hip)."""
+        if self._encoder is None:
+            from .ivfpq import IVFPQIndex
+            M = int(self._pq["codebooks"].shape[0])
+            self._encoder = IVFPQIndex.from_codes(self.quantiser(), torch.zeros(0, dtype=torch.int32),
+                                                  torch.zeros((0, M), dtype=torch.uint8), self.device)
+        a, codes = self._encoder.encode(rows)
+        return a.to(torch.int32), codes
 
     def _fingerprint_codes(self, waves, max_segments, train=None):
         """Fingerprint and encode one model call after the other; the f32 rows of a call are dropped once encoded.
@@ -458,8 +791,7 @@ class FingerprintLibrary:
             return lib.add(tracks, names=names, max_segments=max_segments)
         waves, own = _as_waveforms(tracks)
         a, codes, counts = lib._fingerprint_codes(waves, int(max_segments), (nlist, pq_m, nprobe, train_rows, seed))
-        lib._append_codes(a, codes, np.concatenate([[0], np.cumsum(counts)]).astype(np.int64),
-                          names if names is not None else own)
+        lib._append_codes(a, codes, track_table(counts), names if names is not None else own)
         return lib
 
     def add(self, tracks, names=None, max_segments=4096):
@@ -469,10 +801,10 @@ class FingerprintLibrary:
         names = names if names is not None else own
         if self.is_compact:
             a, codes, counts = self._fingerprint_codes(waves, int(max_segments))
-            self._append_codes(a, codes, np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), names)
-            return self
-        rows, counts = self._fingerprint_tracks(waves, int(max_segments))
-        self._append(rows, np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), names)
+            self._append_codes(a, codes, track_table(counts), names)
+        else:
+            rows, counts = self._fingerprint_tracks(waves, int(max_segments))
+            self._append(rows, track_table(counts), names)
         return self
 
     def compress(self, nlist=64, pq_m=64, nprobe=20, train_rows=65536, seed=1234, chunk=1 << 16):
@@ -499,10 +831,9 @@ class FingerprintLibrary:
             raise ValueError(f"row_stride={row_stride} not in [1, {ops.IDENTIFY_MAX_STRIDE}]")
         keep = [np.arange(self.first[t], self.first[t + 1], D) for t in range(self.n_tracks)]
         keep = np.concatenate(keep).astype(np.int64) if keep else np.zeros(0, np.int64)
-        first = np.concatenate([[0], np.cumsum(-(-np.diff(self.first) // D))]).astype(np.int64)
         rows = self.rows()[torch.from_numpy(keep).to(self.device)]
-        return FingerprintLibrary(self.model, self.settings, rows, first, list(self.names), precision=self.precision,
-                                  device=self.device, row_stride=D)
+        return FingerprintLibrary(self.model, self.settings, rows, track_table(-(-np.diff(self.first) // D)),
+                                  list(self.names), precision=self.precision, device=self.device, row_stride=D)
 
     # ---- files -----------------------------------------------------------------------------------------------
     def save(self, out_dir):
@@ -550,26 +881,26 @@ class FingerprintLibrary:
             raise ValueError(f"{lib_dir}: the library was fingerprinted with another model (state_dict digest "
                              f"{meta['model_digest'][:12]}...); pass force=True to use it anyway")
         first = np.load(os.path.join(lib_dir, "library_tracks.npy")).astype(np.int64)
-        if meta["format"] == FORMAT_COMPACT:
+        compact = meta["format"] == FORMAT_COMPACT
+        if compact:
             if meta.get("index", {}).get("type") != "ivfpq":
                 raise ValueError(f"{lib_dir}: a format {FORMAT_COMPACT} library with index {meta.get('index')!r}")
             codes = np.load(os.path.join(lib_dir, "library_codes.npy"))
             lists = np.load(os.path.join(lib_dir, "library_lists.npy"))
-            if codes.shape[0] != int(first[-1]):
-                raise ValueError(f"{lib_dir}: {codes.shape[0]} rows but the track table covers {int(first[-1])}")
-            with np.load(os.path.join(lib_dir, "library_pq.npz")) as pq:
-                quantiser = {"centroids": torch.from_numpy(pq["centroids"]), "codebooks": torch.from_numpy(pq["codebooks"])}
-            if device is not None:
-                model = model.to(device)
-            return cls.from_codes(model, meta["settings"], quantiser, torch.from_numpy(lists), torch.from_numpy(codes),
-                                  first, meta["names"], meta["precision"], device, meta["index"]["nprobe"])
-        shape = tuple(int(v) for v in np.load(os.path.join(lib_dir, "library_shape.npy")))
+            shape = codes.shape
+        else:
+            shape = tuple(int(v) for v in np.load(os.path.join(lib_dir, "library_shape.npy")))
         if shape[0] != int(first[-1]):
             raise ValueError(f"{lib_dir}: {shape[0]} rows but the track table covers {int(first[-1])}")
-        rows = np.fromfile(os.path.join(lib_dir, "library.mm"), dtype=np.float32).reshape(shape) if shape[0] else \
-            np.zeros((0, 128), np.float32)
         if device is not None:
             model = model.to(device)
+        if compact:
+            with np.load(os.path.join(lib_dir, "library_pq.npz")) as pq:
+                quantiser = {"centroids": torch.from_numpy(pq["centroids"]), "codebooks": torch.from_numpy(pq["codebooks"])}
+            return cls.from_codes(model, meta["settings"], quantiser, torch.from_numpy(lists), torch.from_numpy(codes),
+                                  first, meta["names"], meta["precision"], device, meta["index"]["nprobe"])
+        rows = np.fromfile(os.path.join(lib_dir, "library.mm"), dtype=np.float32).reshape(shape) if shape[0] else \
+            np.zeros((0, 128), np.float32)
         stride = stride if meta["format"] == FORMAT_THIN else 1
         return cls(model, meta["settings"], torch.from_numpy(rows), first, meta["names"], meta["precision"], device,
                    row_stride=stride)
@@ -585,91 +916,15 @@ class FingerprintLibrary:
         counts = np.asarray(track_rows, np.int64).reshape(-1)
         if (counts < 0).any() or int(counts.sum()) != int(shape[0]):
             raise ValueError(f"track_rows sum to {int(counts.sum())}, the database holds {int(shape[0])} rows")
-        first = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        return cls(model, cfg, torch.from_numpy(np.ascontiguousarray(rows, np.float32)), first, names, precision)
+        return cls(model, cfg, torch.from_numpy(np.ascontiguousarray(rows, np.float32)), track_table(counts), names,
+                   precision)
 
-    # ---- queries ---------------------------------------------------------------------------------------------
-    def _load_queries(self, queries, fs):
-        """-> list of 1-D device waveforms at settings['fs']."""
-        from .data import read_audio
-        fs0 = int(self.settings["fs"])
-        if isinstance(queries, str):
-            queries = [queries]
-        elif isinstance(queries, (np.ndarray, torch.Tensor)):
-            queries = [queries] if queries.ndim <= 1 else list(queries)
-        waves, rates = [], []
-        for q in queries:
-            if isinstance(q, str):
-                a, r = read_audio(q, fs0 if fs is None else fs)
-            else:
-                a, r = q, (fs0 if fs is None else fs)
-            waves.append(torch.as_tensor(np.asarray(a, np.float32) if isinstance(a, np.ndarray) else a)
-                         .to(self.device, torch.float32).reshape(-1))
-            rates.append(int(r))
-        for r in sorted(set(rates)):
-            if r == fs0:
-                continue
-            ids = [i for i, v in enumerate(rates) if v == r and waves[i].numel()]
-            if not ids:
-                continue
-            lens = torch.tensor([waves[i].numel() for i in ids], dtype=torch.int64)
-            bank = torch.cat([waves[i] for i in ids])
-            out, starts, out_lens = ops.resample(bank, torch.cumsum(lens, 0) - lens, lens, r, fs0)
-            starts, out_lens = starts.cpu().tolist(), out_lens.cpu().tolist()
-            for j, i in enumerate(ids):
-                waves[i] = out[starts[j]:starts[j] + out_lens[j]]
-        return waves
-
-    def _check_item_len(self, max_len, k_probe):
-        if max_len > ops.IDENTIFY_MAX_LEN or max_len * k_probe > ops.IDENTIFY_MAX_KEYS:
-            raise ValueError(f"a query of {max_len} segments ({max_len * self.segment_s:.1f} s) with k_probe={k_probe} "
-                             f"exceeds {ops.IDENTIFY_MAX_LEN} segments / {ops.IDENTIFY_MAX_KEYS} hits per item: use "
-                             "identify_windows for long recordings")
-
-    def _embed_and_search(self, segs, k_probe):
-        """One batched embed of the segments and one search of their rows -> (q (n, 128) f32, ids (n, k) int64)."""
-        q = self._embed(segs)
-        return q, self._search_rows(q, k_probe)
-
+    # ---- the front's hooks -----------------------------------------------------------------------------------
     def _search_rows(self, q, k_probe):
-        k = min(int(k_probe), self.n_rows)
-        return self.index.search(q, k)[1]
-
-    def _identify_items(self, q, ids, item_row, item_len, top, min_overlap, max_len=None, tempo=None, tempo_step=None):
-        """One identify launch (the kernel of the library's form) for all items over the rows q and their hits ids ->
-        per-item lists of matches.  max_len: an upper bound of the items' lengths (None: the longest).  (StreamMonitor
-        calls it with rows it kept from earlier pushes.)  tempo: tempo_ratios' argument; the launch is then
-        ops.identify_tempo over the ratio grid of the longest item, and every match names its ratio."""
-        n_items = len(item_row)
-        longest = int(np.max(item_len, initial=0))
-        if n_items == 0 or longest == 0:
-            return [[] for _ in range(n_items)]
-        max_len = longest if max_len is None else max(int(max_len), longest)
-        nums = None if tempo is None else tempo_ratios(tempo, longest, tempo_step)
-        lists = self._identify_lists(q, ids, np.asarray(item_row, np.int64), np.asarray(item_len, np.int32), top,
-                                     min_overlap, max_len, nums)
-        tr, off, sc, vo = (t.cpu().numpy() for t in lists[:4])
-        ra = lists[4].cpu().numpy() if nums is not None else None
-        step, hop, fs = self.step, self.settings["hop_len"], self.settings["fs"]
-        out = []
-        for i in range(n_items):
-            res = []
-            for j in range(top):
-                t = int(tr[i, j])
-                if t < 0:
-                    break
-                res.append({"track": t, "name": self.names[t], "offset": int(off[i, j]),
-                            "offset_s": int(off[i, j]) * step * hop / fs, "score": float(sc[i, j]),
-                            "votes": int(vo[i, j])})
-                if ra is not None:
-                    res[-1]["tempo"] = int(ra[i, j]) / ops.IDENTIFY_TEMPO_DEN
-                    res[-1]["tempo_num"] = int(ra[i, j])
-            out.append(res)
-        return out
+        return self.index.search(q, min(int(k_probe), self.n_rows))[1]
 
     def _identify_lists(self, q, ids, item_row, item_len, top, min_overlap, max_len, nums=None):
-        """The launch of _identify_items -> the op's device tensors (track, offset, score, votes and, with the ratio
-        grid nums, ratio), nothing read back.  (ShardedFingerprintLibrary runs one per shard and merges them.)"""
+        """One launch of the op of the library's form.  (ShardedFingerprintLibrary runs and merges one per shard.)"""
         dev = self.device
         tail = (torch.from_numpy(self.first).to(dev), q, ids, torch.from_numpy(item_row).to(dev),
                 torch.from_numpy(item_len).to(dev))
@@ -682,106 +937,19 @@ class FingerprintLibrary:
             return ops.identify_thin(self.rows(), *tail, self._row_stride, **kw)
         return ops.identify(self.rows(), *tail, **kw)
 
-    def _need_tempo_form(self, what, tempo):
-        if tempo is not None:
-            self._need_flat(f"{what}(tempo=...)")
-            self._need_dense(f"{what}(tempo=...)")
+    def _match_lists(self, qb, src, k_probe, nums, kw):
+        return self._match_launch(qb, src, self._search_rows(qb, k_probe), nums, kw)
 
-    def _search_and_identify(self, segs, item_row, item_len, top, k_probe, min_overlap, tempo=None, tempo_step=None):
-        """One batched embed + search of all segments, one ops.identify launch for all items -> per-item lists.  (The
-        queries' segments are all embedded, whatever the library's row_stride: the query side stays dense.)"""
-        n_items = len(item_row)
-        if tempo is not None:
-            tempo_ratios(tempo, max(1, int(np.max(item_len, initial=0))), tempo_step)      # refuse a bad range early
-        if n_items == 0 or segs.shape[0] == 0 or self.n_rows == 0 or int(np.max(item_len, initial=0)) == 0:
-            return [[] for _ in range(n_items)]
-        self._check_item_len(int(np.max(item_len)), k_probe)
-        q, ids = self._embed_and_search(segs, k_probe)
-        return self._identify_items(q, ids, item_row, item_len, top, min_overlap, tempo=tempo, tempo_step=tempo_step)
-
-    def identify(self, queries, fs=None, top=5, k_probe=20, min_overlap=None, tempo=None, tempo_step=None):
-        """queries: one waveform, a list of ragged waveforms, or file paths; at `fs` (default settings['fs']; other rates
-        are resampled on the device).  -> per query, a list of matches {track, name, offset, offset_s, score, votes},
-        best first.  offset_s = offset * step * hop_len / fs is where the query's first segment sits in the track.  A
-        query shorter than one segment gives an empty list.
-        tempo: None, or the speeds to search for a recording that plays faster or slower than the catalogue -- a float
-        x in (0, 0.5] for the ratios [1 - x, 1 + x] (track seconds per recording second), or a pair (lo, hi);
-        tempo_step: the ratio grid's spacing in 1/256 (tempo_ratios; default: from the longest query).  The segments
-        are embedded and searched as without it and one ops.identify_tempo launch scores every candidate along the
-        sloped alignment of every ratio; each match then also carries "tempo" (the ratio) and "tempo_num" (ratio *
-        256), and offset / offset_s keep their meaning.  Needs a flat library that keeps every row.  Speed only: pitch
-        is not searched; match() takes the same tempo for whole recordings and self_matches() for the tracks of the
-        library itself; StreamMonitor, the IVF-PQ and the thinned forms know no tempo."""
-        self._need_tempo_form("identify", tempo)
-        single = isinstance(queries, (str, np.ndarray, torch.Tensor)) and (
-            isinstance(queries, str) or torch.as_tensor(queries).dim() == 1)
-        waves = self._load_queries(queries, fs)
-        segs = [self.segments(w) for w in waves]
-        lens = np.array([s.shape[0] for s in segs], np.int32)
-        rows = np.concatenate([[0], np.cumsum(lens[:-1])]).astype(np.int64) if len(lens) else np.zeros(0, np.int64)
-        allsegs = torch.cat(segs, dim=0) if segs else torch.empty((0,), device=self.device)
-        res = self._search_and_identify(allsegs, rows, lens, int(top), int(k_probe), min_overlap, tempo, tempo_step)
-        return res[0] if single and len(res) == 1 else res
-
-    def identify_windows(self, recording, window_s=3.0, hop_s=1.0, fs=None, top=5, k_probe=20, min_overlap=None,
-                         tempo=None, tempo_step=None):
-        """A long recording cut into items of window_s seconds every hop_s seconds.  The recording is segmented,
-        fingerprinted and searched once; all windows are identified in one launch.  -> per window
-        {start_s, end_s, segment_start_s, matches}; segment_start_s is where the window's first segment starts in the
-        recording (the time its matches' offset_s refers to).  tempo, tempo_step: as for identify()."""
-        self._need_tempo_form("identify_windows", tempo)
-        wave = self._load_queries([recording], fs)[0]
-        segs = self.segments(wave)
-        starts, rows, lens = window_items(segs.shape[0], wave.numel(), self.settings, window_s, hop_s)
-        res = self._search_and_identify(segs, rows, lens, int(top), int(k_probe), min_overlap, tempo, tempo_step)
-        seg_s = self.segment_s
-        return [{"start_s": float(s), "end_s": float(s) + window_s, "segment_start_s": int(r) * seg_s, "matches": m}
-                for s, r, m in zip(starts, rows, res)]
-
-    def timeline(self, windows, min_score=None):
-        """What played when: consecutive windows whose best match is the same track at a consistent position (the
-        track offset minus the window's segment start agrees within one segment hop) merge into one span.
-        -> list of {start_s, end_s, track, name, track_offset_s (the track position at start_s), score (mean)}.
-        A window whose match carries a "tempo" rho (identify_windows(tempo=...)) is followed along its slope: the span
-        keeps its last merged window (u = segment_start_s, o = offset_s, rho), and the next window (u', o') of the same
-        track merges iff |o' - (o + rho * (u' - u))| is within one segment hop and it starts no later than the span's
-        end; the reference point then advances.  Such a span also reports "tempo", the mean of its windows' rho."""
-        spans, seg_s = [], self.segment_s
-        for w in windows:
-            if not w["matches"] or (min_score is not None and w["matches"][0]["score"] < min_score):
-                continue
-            m = w["matches"][0]
-            if "tempo" in m:
-                u, o, rho = w["segment_start_s"], m["offset_s"], m["tempo"]
-                last = spans[-1] if spans else None
-                if (last is not None and last["track"] == m["track"] and "_ref" in last
-                        and abs(o - (last["_ref"][1] + last["_ref"][2] * (u - last["_ref"][0]))) <= seg_s + 1e-9
-                        and w["start_s"] <= last["end_s"]):
-                    last["end_s"] = w["end_s"]
-                    last["_scores"].append(m["score"])
-                    last["_tempos"].append(rho)
-                else:
-                    spans.append({"start_s": w["start_s"], "end_s": w["end_s"], "track": m["track"], "name": m["name"],
-                                  "track_offset_s": o + rho * (w["start_s"] - u), "_scores": [m["score"]],
-                                  "_tempos": [rho]})
-                spans[-1]["_ref"] = (u, o, rho)
-                continue
-            delta = m["offset_s"] - w["segment_start_s"]              # track time = recording time + delta
-            last = spans[-1] if spans else None
-            if (last is not None and last["track"] == m["track"] and "_delta" in last
-                    and abs(delta - last["_delta"]) <= seg_s + 1e-9
-                    and w["start_s"] <= last["end_s"]):
-                last["end_s"] = w["end_s"]
-                last["_scores"].append(m["score"])
-            else:
-                spans.append({"start_s": w["start_s"], "end_s": w["end_s"], "track": m["track"], "name": m["name"],
-                              "track_offset_s": w["start_s"] + delta, "_delta": delta, "_scores": [m["score"]]})
-        for s in spans:
-            s["score"] = float(np.mean(s.pop("_scores")))
-            s.pop("_delta", None)
-            if s.pop("_ref", None) is not None:
-                s["tempo"] = float(np.mean(s.pop("_tempos")))
-        return spans
+    def _match_launch(self, qb, src, ids, nums, kw):
+        """The launch of _match_lists over the hits ids.  (ShardedFingerprintLibrary runs one per shard and merges
+        them.)"""
+        first_d = torch.from_numpy(self.first).to(self.device)
+        if nums is not None:
+            return ops.cross_match_tempo(self.rows(), first_d, qb, src, ids, nums, **kw)
+        if self.is_compact:
+            return ops.cross_match_pq(*self.codes(), self._pq["centroids"], self._pq["codebooks"], first_d, qb, src, ids,
+                                      **kw)
+        return ops.cross_match(self.rows(), first_d, qb, src, ids, **kw)
 
     # ---- the catalog itself ------------------------------------------------------------------------------------
     def self_matches(self, k_probe=32, min_overlap_s=3.0, min_votes=4, min_score=None, top=8, tracks=None,
@@ -821,26 +989,16 @@ class FingerprintLibrary:
             raise ValueError(f"tracks must lie in [0, {T})")
         if n == 0 or T < 2 or not src:
             return []
-        seg_s = self.segment_s
-        min_overlap = max(1, int(math.ceil(float(min_overlap_s) / seg_s - 1e-9)))
+        min_overlap = max(1, int(math.ceil(float(min_overlap_s) / self.segment_s - 1e-9)))
         k = min(int(k_probe), n)
         rows, dev = self.rows(), self.device
         first_d = torch.from_numpy(self.first).to(dev)
         ids = torch.full((n, k), -1, dtype=torch.int64, device=dev)
-        lens = np.diff(self.first)
         if nums is not None:
             batch_rows = batch_rows // len(nums)                     # the workspace is R times a dense launch's
-        batches, cur, cur_rows = [], [], 0
-        for t in src:
-            cur.append(t)
-            cur_rows += int(lens[t])
-            if cur_rows >= batch_rows:
-                batches.append(cur)
-                cur, cur_rows = [], 0
-        if cur:
-            batches.append(cur)
         out = []
-        for batch in batches:
+        for i0, i1 in batch_ranges(np.diff(self.first)[src], batch_rows):
+            batch = src[i0:i1]
             g = np.concatenate([np.arange(self.first[t], self.first[t + 1]) for t in batch]).astype(np.int64)
             if g.size:
                 g_d = torch.from_numpy(g).to(dev)
@@ -850,151 +1008,22 @@ class FingerprintLibrary:
                       min_overlap=min_overlap)
             res = ops.self_match(rows, first_d, ids, **kw) if nums is None else \
                 ops.self_match_tempo(rows, first_d, ids, nums, **kw)
-            b_, d_, lo_, m_, sc_, v_ = (x.cpu().numpy() for x in res[:6])
-            ra_ = None if nums is None else res[6].cpu().numpy()
-            for s, a in enumerate(batch):
-                for j in range(b_.shape[1]):
-                    b = int(b_[s, j])
-                    if b == -2:                                  # the op sizes the workspace exactly: never
-                        raise RuntimeError(f"self_match: track {a} did not fit the workspace")
-                    if b < 0:
-                        break
-                    sc = float(sc_[s, j])
-                    if min_score is not None and sc < min_score:
-                        continue
-                    d, lo, m = int(d_[s, j]), int(lo_[s, j]), int(m_[s, j])
-                    la, lb = max(1, int(lens[a])), max(1, int(lens[b]))
-                    out.append({"track_a": a, "name_a": self.names[a], "track_b": b, "name_b": self.names[b],
-                                "offset": d, "a_start_s": lo * seg_s, "b_start_s": (lo + d) * seg_s,
-                                "overlap_s": m * seg_s, "coverage": m / min(la, lb),
-                                "score": sc, "votes": int(v_[s, j])})
-                    if ra_ is not None:
-                        num, half = int(ra_[s, j]), ops.IDENTIFY_TEMPO_DEN // 2
-                        w_lo, w_hi = (lo * num + half) >> 8, ((lo + m - 1) * num + half) >> 8
-                        mb = w_hi - w_lo + 1                         # track_b's side of the span, in rows
-                        out[-1].update({"b_start_s": (d + w_lo) * seg_s, "coverage": max(m / la, mb / lb),
-                                        "tempo": num / ops.IDENTIFY_TEMPO_DEN, "tempo_num": num,
-                                        "b_overlap_s": mb * seg_s})
+            out += [self._self_match_entry(*slot)
+                    for slot in span_slots(res, batch, nums is not None, min_score, "self_match: track")]
         return out
 
-    # ---- recordings against the catalog -------------------------------------------------------------------------
-    def match(self, recordings, fs=None, k_probe=20, min_overlap_s=3.0, min_votes=4, min_score=None, top=8,
-              max_segments=4096, batch_rows=1 << 18, tempo=None, tempo_step=None):
-        """What whole recordings share with the library: is an upload already in the catalogue, in whole or in part,
-        which tracks does a mix or medley contain, and where.  recordings: as identify's queries (one waveform, a list
-        of ragged waveforms, or file paths, at `fs`; other rates are resampled on the device), of any length.  They are
-        segmented, embedded in model calls of at least max_segments segments, searched with self.index (k_probe hits per
-        row) and matched in launches of about batch_rows rows by ops.cross_match (flat) or ops.cross_match_pq (compact);
-        nothing is added to the library.
-        -> per recording, a list of {track, name, score, votes, offset, recording_start_s, track_start_s, overlap_s,
-        coverage, recording_coverage, track_coverage}, best first (a single recording: its list alone, as identify).  The
-        recording's audio from recording_start_s reappears in `track` from track_start_s for overlap_s seconds; offset =
-        delta in segments (row i of the recording sits on row i + offset of the track); coverage = overlapping rows /
-        rows of the shorter of the two, recording_coverage and track_coverage the same over the rows of each; score =
-        mean cosine over the span; votes = rows whose hits agree on the alignment.  At most `top` tracks per recording,
-        each at its best alignment.  min_overlap_s, min_votes and min_score as for self_matches.  A recording shorter
-        than one segment, or an empty library, gives [].
-        k_probe = 20 is identify's default; it has not been measured for this use (self_matches uses 32 because it
-        drops a row's hits on its own track; nothing is dropped here).
-        One recording is one workgroup, as a track is in self_matches: an hour-long recording is not split into pieces,
-        its hits are sorted through the launch's workspace (ops.self_match_workspace_bytes of the batch's row counts).
-        tempo: None, or the speeds to search, as identify takes them (a float x for the ratios [1 - x, 1 + x] of track
-        seconds per recording second, or a pair (lo, hi)); tempo_step: the ratio grid's spacing in 1/256, by default 1
-        (recordings are long: at a coarser grid the nearest ratio drifts off a long span).  The launches then go to
-        ops.cross_match_tempo, R ratios at once, in batches of about batch_rows // R rows (the workspace is R times a
-        dense launch's), and row i of the recording sits on row offset + w(i) of the track, w(i) = (i * tempo_num + 128)
-        >> 8.  Each match also carries tempo (= tempo_num / 256), tempo_num and track_overlap_s = (w(i_hi) - w(i_lo) +
-        1) segment hops, the track's side of the span; track_start_s = (offset + w(i_lo)) hops, recording_coverage = m /
-        recording rows, track_coverage = (w(i_hi) - w(i_lo) + 1) / track rows, coverage the larger of the two (at 256:
-        the dense m / min).  When the true ratio lies between two grid ratios a long span drifts off its alignment by
-        up to a row per 512 rows and may end early: overlap_s is then a lower bound of the shared audio.  Needs a flat
-        library that keeps every row."""
-        self._need_tempo_form("match", tempo)
-        self._need_dense("match()")
-        nums = None if tempo is None else tempo_ratios(tempo, ops.IDENTIFY_TEMPO_DEN, tempo_step)   # step 1 by default
-        single = isinstance(recordings, (str, np.ndarray, torch.Tensor)) and (
-            isinstance(recordings, str) or torch.as_tensor(recordings).dim() == 1)
-        waves = self._load_queries(recordings, fs)
-        if self.n_rows == 0:
-            res = [[] for _ in waves]
-        else:
-            rows, counts = self._fingerprint_tracks(waves, int(max_segments))
-            res = self._match_rows(rows, counts, int(k_probe), float(min_overlap_s), int(min_votes), min_score,
-                                   int(top), int(batch_rows), nums)
-        return res[0] if single and len(res) == 1 else res
-
-    def _match_entry(self, b, d, lo, m, sc, v, n_rec, num=None):
-        """One match of match() from one slot of the kernel's outputs: partner b, delta d, span start lo, span rows m,
-        score, votes, for a recording of n_rec rows; num: the winning ratio of ops.cross_match_tempo (None: dense)."""
+    def _self_match_entry(self, a, b, d, lo, m, sc, v, num=None):
+        """One entry of self_matches() from one slot of the kernel's outputs, as _match_entry makes match()'s, for the
+        source track a; num: the winning ratio of ops.self_match_tempo (None: dense)."""
         seg_s = self.segment_s
-        lr, lt = max(1, int(n_rec)), max(1, int(self.first[b + 1] - self.first[b]))
-        if num is None:
-            return {"track": b, "name": self.names[b], "score": sc, "votes": v,
-                    "offset": d, "recording_start_s": lo * seg_s, "track_start_s": (lo + d) * seg_s,
-                    "overlap_s": m * seg_s, "coverage": m / min(lr, lt),
-                    "recording_coverage": m / lr, "track_coverage": m / lt}
-        half = ops.IDENTIFY_TEMPO_DEN // 2
-        w_lo, w_hi = (lo * num + half) >> 8, ((lo + m - 1) * num + half) >> 8
-        mt = w_hi - w_lo + 1                                         # the track's side of the span, in rows
-        return {"track": b, "name": self.names[b], "score": sc, "votes": v,
-                "offset": d, "recording_start_s": lo * seg_s, "track_start_s": (d + w_lo) * seg_s,
-                "overlap_s": m * seg_s, "coverage": max(m / lr, mt / lt),
-                "recording_coverage": m / lr, "track_coverage": mt / lt,
-                "tempo": num / ops.IDENTIFY_TEMPO_DEN, "tempo_num": num, "track_overlap_s": mt * seg_s}
-
-    def _match_rows(self, q, counts, k_probe, min_overlap_s, min_votes, min_score, top, batch_rows, nums=None):
-        """match() from the recordings' rows on: q (n_q, 128) f32 on the device, counts the rows of each recording.
-        nums: the ratio grid of match(tempo=...) (None: the dense kernels)."""
-        seg_s = self.segment_s
-        min_overlap = max(1, int(math.ceil(min_overlap_s / seg_s - 1e-9)))
-        starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        out = [[] for _ in counts]
-        if nums is not None:
-            batch_rows = batch_rows // len(nums)                     # the workspace is R times a dense launch's
-        s0 = 0
-        while s0 < len(counts):
-            s1 = s0 + 1
-            while s1 < len(counts) and starts[s1] - starts[s0] < batch_rows:
-                s1 += 1
-            qb = q[int(starts[s0]):int(starts[s1])]
-            if qb.shape[0]:
-                res = self._match_lists(qb, torch.from_numpy(starts[s0:s1 + 1] - starts[s0]), k_probe, nums,
-                                        dict(top=top, min_votes=min_votes, min_overlap=min_overlap))
-                ra_ = res[6].cpu().numpy() if nums is not None else None
-                b_, d_, lo_, m_, sc_, v_ = (x.cpu().numpy() for x in res[:6])
-                for s in range(s0, s1):
-                    for j in range(b_.shape[1]):
-                        b = int(b_[s - s0, j])
-                        if b == -2:                              # the op sizes the workspace exactly: never
-                            raise RuntimeError(f"cross_match: recording {s} did not fit the workspace")
-                        if b < 0:
-                            break
-                        sc = float(sc_[s - s0, j])
-                        if min_score is not None and sc < min_score:
-                            continue
-                        d, lo, m = int(d_[s - s0, j]), int(lo_[s - s0, j]), int(m_[s - s0, j])
-                        out[s].append(self._match_entry(b, d, lo, m, sc, int(v_[s - s0, j]), counts[s],
-                                                        None if ra_ is None else int(ra_[s - s0, j])))
-            s0 = s1
-        return out
-
-    def _match_lists(self, qb, src, k_probe, nums, kw):
-        """The search and the launch of one batch of _match_rows: qb the batch's rows, src its source table (a host
-        tensor) -> the op's device tensors (track, delta, start, length, score, votes and, with nums, ratio), nothing
-        read back."""
-        _, ids = self.index.search(qb, min(k_probe, self.n_rows))
-        return self._match_launch(qb, src, ids, nums, kw)
-
-    def _match_launch(self, qb, src, ids, nums, kw):
-        """The launch of _match_lists over the hits ids.  (ShardedFingerprintLibrary runs one per shard and merges
-        them.)"""
-        first_d = torch.from_numpy(self.first).to(self.device)
-        if nums is not None:
-            return ops.cross_match_tempo(self.rows(), first_d, qb, src, ids, nums, **kw)
-        if self.is_compact:
-            return ops.cross_match_pq(*self.codes(), self._pq["centroids"], self._pq["codebooks"], first_d, qb, src, ids,
-                                      **kw)
-        return ops.cross_match(self.rows(), first_d, qb, src, ids, **kw)
+        la, lb = (max(1, int(self.first[t + 1] - self.first[t])) for t in (a, b))
+        w_lo, mb = (lo, m) if num is None else tempo_span(lo, m, num)     # track_b's side of the span, in rows
+        entry = {"track_a": a, "name_a": self.names[a], "track_b": b, "name_b": self.names[b],
+                 "offset": d, "a_start_s": lo * seg_s, "b_start_s": (d + w_lo) * seg_s,
+                 "overlap_s": m * seg_s, "coverage": max(m / la, mb / lb), "score": sc, "votes": v}
+        if num is not None:
+            entry.update({"tempo": num / ops.IDENTIFY_TEMPO_DEN, "tempo_num": num, "b_overlap_s": mb * seg_s})
+        return entry
 
     @staticmethod
     def duplicate_groups(matches, min_coverage=0.9, min_score=DUPLICATE_MIN_SCORE):

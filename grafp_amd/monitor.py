@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .library import n_segments, segment_step, window_items
+from .library import n_segments, segment_step, track_table, window_items
 
 
 # ---- readiness rules: pure host functions ------------------------------------------------------------------------------
@@ -170,7 +170,7 @@ class StreamFrontEnd:
         allseg = torch.cat([s for s, _ in per_round])
         base, order = 0, [[] for _ in range(self.channels)]
         for _, n in per_round:
-            first = base + np.concatenate([[0], np.cumsum(n)])
+            first = base + track_table(n)
             for c in np.nonzero(n)[0]:
                 order[c].append(np.arange(first[c], first[c + 1]))
             base = int(first[-1])
@@ -407,7 +407,7 @@ class StreamMonitor:
         ids = lib._search_rows(rows, self.k_probe) if lib.n_rows else \
             torch.zeros((rows.shape[0], 0), dtype=torch.int64, device=rows.device)
         n_old = int(self._first[-1])
-        new_first = n_old + np.concatenate([[0], np.cumsum(counts)])
+        new_first = n_old + track_table(counts)
         order = []
         for ch in range(C):
             order.append(np.arange(self._first[ch] + self._stale[ch], self._first[ch + 1]))
@@ -418,7 +418,7 @@ class StreamMonitor:
         kept = np.diff(self._first) - self._stale + counts
         self._row0 += self._stale
         self._stale[:] = 0
-        self._first = np.concatenate([[0], np.cumsum(kept)])
+        self._first = track_table(kept)
         self._n_rows += counts
 
     def _advance(self, rows, counts, touched):

@@ -17,8 +17,9 @@ merged list is, bit for bit and key for key, what the one-card library over the 
 rows launches nothing.
 
 identify, identify_windows, timeline, match, their tempo= forms and StreamMonitor(sharded, channels) work as on the
-one-card library -- the front of each call IS FingerprintLibrary's code, borrowed below.  Not built: self_matches across
-shards, compact (IVF-PQ) shards, shards in several processes, concurrent shards on one device."""
+one-card library: both classes derive from library.LibraryFront, which holds the front of each call, and this one
+implements its three hooks -- _search_rows, _identify_lists, _match_lists -- over the shards.  Not built: self_matches
+across shards, compact (IVF-PQ) shards, shards in several processes, concurrent shards on one device."""
 import json
 import os
 
@@ -26,7 +27,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .library import FingerprintLibrary, _as_waveforms, model_digest
+from .library import FingerprintLibrary, LibraryFront, _as_waveforms, model_digest, track_names, track_table
 
 FORMAT_SHARDED = 1           # shards.json
 INT_MIN = -2 ** 31
@@ -63,8 +64,9 @@ def _cut(lib, t0, t1, device):
                   lib.row_stride)
 
 
-class ShardedFingerprintLibrary:
+class ShardedFingerprintLibrary(LibraryFront):
     """S flat FingerprintLibrary shards over contiguous track ranges, queried as one library."""
+    is_compact = False
 
     def __init__(self, shards):
         shards = list(shards)
@@ -78,16 +80,14 @@ class ShardedFingerprintLibrary:
             if sh.settings != head.settings or sh.precision != head.precision or sh.row_stride != head.row_stride or \
                     sh.model is not head.model:
                 raise ValueError("the shards of a library share one model, its settings, precision and row_stride")
+        super().__init__(head.model, head.settings, head.precision, head.device, head.row_stride)
         self.shards = shards
-        self.model, self.settings, self.precision = head.model, dict(head.settings), head.precision
-        self._row_stride = head.row_stride
-        self.device = head.device
         self._refresh()
 
     def _refresh(self):
         """The global tables from the shards': tb, rb, first and names."""
-        self.tb = np.concatenate([[0], np.cumsum([sh.n_tracks for sh in self.shards])]).astype(np.int64)
-        self.rb = np.concatenate([[0], np.cumsum([sh.n_rows for sh in self.shards])]).astype(np.int64)
+        self.tb = track_table([sh.n_tracks for sh in self.shards])
+        self.rb = track_table([sh.n_rows for sh in self.shards])
         self.first = np.concatenate([sh.first[:-1] + self.rb[s] for s, sh in enumerate(self.shards)] +
                                     [self.rb[-1:]]).astype(np.int64)
         self.names = [name for sh in self.shards for name in sh.names]
@@ -136,17 +136,13 @@ class ShardedFingerprintLibrary:
                                    row_stride=kw.get("row_stride", 1))
         devices = cls._devices(devices, n_shards, front.device)
         waves, own = _as_waveforms(tracks)
-        names = kw.get("names") if kw.get("names") is not None else own
-        names = [str(v) for v in names] if names is not None else [f"track{i}" for i in range(len(waves))]
-        if len(names) != len(waves):
-            raise ValueError(f"{len(names)} names for {len(waves)} tracks")
+        names = track_names(kw.get("names") if kw.get("names") is not None else own, len(waves))
         shards, parts, held, t0, counts = [], [], [], 0, []
 
         def close(t1):
             rows = torch.cat(parts) if parts else torch.zeros((0, 128), device=front.device)
-            first = np.concatenate([[0], np.cumsum(held)]).astype(np.int64)
-            shards.append(_shard(model, cfg, rows, first, names[t0:t1], front.precision, devices[len(shards)],
-                                 front.row_stride))
+            shards.append(_shard(model, cfg, rows, track_table(held), names[t0:t1], front.precision,
+                                 devices[len(shards)], front.row_stride))
             parts.clear()
             held.clear()
 
@@ -172,11 +168,9 @@ class ShardedFingerprintLibrary:
         """Append tracks (as for build) to the last shard: fingerprinted on the primary device, the global order stays
         contiguous.  rebalance() evens the shards out again."""
         waves, own = _as_waveforms(tracks)
-        names = names if names is not None else own
-        names = [str(v) for v in names] if names is not None else \
-            [f"track{self.n_tracks + i}" for i in range(len(waves))]
+        names = track_names(names if names is not None else own, len(waves), self.n_tracks)
         rows, counts = self._fingerprint_tracks(waves, int(max_segments))
-        self.shards[-1]._append(rows, np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), names)
+        self.shards[-1]._append(rows, track_table(counts), names)
         self._refresh()
         return self
 
@@ -243,40 +237,12 @@ class ShardedFingerprintLibrary:
             shards.append(sh if sh.device == dev else _cut(sh, 0, sh.n_tracks, dev))
         return cls(shards)
 
-    # ---- sizes -------------------------------------------------------------------------------------------------
-    step = FingerprintLibrary.step
-    segment_s = FingerprintLibrary.segment_s
-    n_tracks = FingerprintLibrary.n_tracks
-    n_rows = FingerprintLibrary.n_rows
-    row_stride = FingerprintLibrary.row_stride
-    is_compact = False
-
     @property
     def nbytes(self):
         """Device bytes over all shards (FingerprintLibrary.nbytes of each)."""
         return int(sum(sh.nbytes for sh in self.shards))
 
-    # ---- queries: FingerprintLibrary's own front (same signatures, defaults, result dicts and refusals) -----------
-    _need_flat = FingerprintLibrary._need_flat
-    _need_dense = FingerprintLibrary._need_dense
-    _need_tempo_form = FingerprintLibrary._need_tempo_form
-    _autocast = FingerprintLibrary._autocast
-    _embed = FingerprintLibrary._embed
-    segments = FingerprintLibrary.segments
-    _fingerprint_batches = FingerprintLibrary._fingerprint_batches
-    _fingerprint_tracks = FingerprintLibrary._fingerprint_tracks
-    _load_queries = FingerprintLibrary._load_queries
-    _check_item_len = FingerprintLibrary._check_item_len
-    _embed_and_search = FingerprintLibrary._embed_and_search
-    _search_and_identify = FingerprintLibrary._search_and_identify
-    _identify_items = FingerprintLibrary._identify_items
-    identify = FingerprintLibrary.identify
-    identify_windows = FingerprintLibrary.identify_windows
-    timeline = FingerprintLibrary.timeline
-    match = FingerprintLibrary.match
-    _match_rows = FingerprintLibrary._match_rows
-    _match_entry = FingerprintLibrary._match_entry
-
+    # ---- queries: LibraryFront's calls (the one-card library's signatures, defaults, result dicts and refusals) ------
     def self_matches(self, *args, **kw):
         raise NotImplementedError("ShardedFingerprintLibrary.self_matches is not built: it needs the S^2 shard pairs "
                                   "through _match_rows")
@@ -315,22 +281,21 @@ class ShardedFingerprintLibrary:
         merged = {form["track"]: tr, form["score"]: sc, **{j: pl[p] for p, j in enumerate(payload)}}
         return tuple(merged[j] for j in range(n_out))
 
-    def _identify_lists(self, q, ids, item_row, item_len, top, min_overlap, max_len, nums=None):
-        """FingerprintLibrary._identify_lists on every shard that holds rows, over the global hits minus the shard's
-        row base, merged."""
+    def _on_shards(self, q, ids, launch, form):
+        """launch(shard, q, ids) on every shard that holds rows, on its device, with the rows q and the global hits ids
+        minus the shard's row base moved there; the shards' lists merged."""
         live, outs = self._live(), []
         for s, sh in live:
             with torch.cuda.device(sh.device):
-                outs.append(sh._identify_lists(q.to(sh.device), (ids - int(self.rb[s])).to(sh.device), item_row,
-                                               item_len, top, min_overlap, max_len, nums))
-        return self._merge(outs, live, _IDENTIFY_FORM)
+                outs.append(launch(sh, q.to(sh.device), (ids - int(self.rb[s])).to(sh.device)))
+        return self._merge(outs, live, form)
+
+    def _identify_lists(self, q, ids, item_row, item_len, top, min_overlap, max_len, nums=None):
+        """FingerprintLibrary._identify_lists on every shard that holds rows."""
+        return self._on_shards(q, ids, lambda sh, q_s, ids_s: sh._identify_lists(
+            q_s, ids_s, item_row, item_len, top, min_overlap, max_len, nums), _IDENTIFY_FORM)
 
     def _match_lists(self, qb, src, k_probe, nums, kw):
-        """FingerprintLibrary._match_lists over the shards: one merged search, every shard's own cross-match launch over
-        the same batch of recordings, merged."""
-        ids = self._search_rows(qb, k_probe)
-        live, outs = self._live(), []
-        for s, sh in live:
-            with torch.cuda.device(sh.device):
-                outs.append(sh._match_launch(qb.to(sh.device), src, (ids - int(self.rb[s])).to(sh.device), nums, kw))
-        return self._merge(outs, live, _MATCH_FORM)
+        """One merged search, then FingerprintLibrary._match_launch on every shard over the same batch of recordings."""
+        return self._on_shards(qb, self._search_rows(qb, k_probe), lambda sh, q_s, ids_s: sh._match_launch(
+            q_s, src, ids_s, nums, kw), _MATCH_FORM)

@@ -383,3 +383,54 @@ def test_command_line_parses_match(capsys):
     with pytest.raises(SystemExit) as e:
         identify.main(["match", "--library", "lib", "a.wav"])              # --ckp is required
     assert e.value.code == 2
+
+
+# ---- the batching rule of match and self_matches ---------------------------------------------------------------------
+def _batches_as_self_matches_wrote_them(counts, limit):
+    """self_matches' loop before library.batch_ranges: accumulate, close once at least `limit` rows are held."""
+    batches, cur, cur_rows = [], [], 0
+    for t in range(len(counts)):
+        cur.append(t)
+        cur_rows += int(counts[t])
+        if cur_rows >= limit:
+            batches.append(cur)
+            cur, cur_rows = [], 0
+    if cur:
+        batches.append(cur)
+    return [(b[0], b[-1] + 1) for b in batches]
+
+
+def _batches_as_match_rows_wrote_them(counts, limit):
+    """_match_rows' loop before library.batch_ranges: two pointers over the running sums."""
+    starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    out, s0 = [], 0
+    while s0 < len(counts):
+        s1 = s0 + 1
+        while s1 < len(counts) and starts[s1] - starts[s0] < limit:
+            s1 += 1
+        out.append((s0, s1))
+        s0 = s1
+    return out
+
+
+def test_batch_ranges_on_small_cases():
+    assert library.batch_ranges([3, 0, 5, 2], 5) == [(0, 3), (3, 4)]
+    assert library.batch_ranges([3, 0, 5, 2], 0) == [(0, 1), (1, 2), (2, 3), (3, 4)]
+    assert library.batch_ranges([3, 0, 5, 2], -7) == [(0, 1), (1, 2), (2, 3), (3, 4)]
+    assert library.batch_ranges([3, 0, 5, 2], 10 ** 9) == [(0, 4)]
+    assert library.batch_ranges([3, 0, 5, 2], 8) == [(0, 3), (3, 4)]      # a sum that lands exactly on the limit closes
+    assert library.batch_ranges([0, 0], 1) == [(0, 2)]
+    assert library.batch_ranges([], 5) == [] and library.batch_ranges(np.zeros(0, np.int64), 0) == []
+
+
+def test_batch_ranges_is_both_loops_it_replaces():
+    rng = np.random.RandomState(5)
+    for case in range(200):
+        n = int(rng.randint(0, 13))
+        counts = rng.randint(0, 9, size=n) * (rng.rand(n) < 0.7)             # zeros included
+        sums = np.cumsum(counts)
+        limit = int(rng.choice([0, -3, 1, 10 ** 9, int(rng.randint(1, 40))] + ([int(rng.choice(sums))] if n else [])))
+        got = library.batch_ranges(counts, limit)
+        assert got == _batches_as_self_matches_wrote_them(counts, limit), (case, counts, limit)
+        assert got == _batches_as_match_rows_wrote_them(counts, limit), (case, counts, limit)
+        assert library.batch_ranges(list(counts), limit) == got

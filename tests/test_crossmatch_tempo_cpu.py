@@ -323,3 +323,42 @@ def test_match_takes_a_tempo_on_the_command_line(capsys):
     out = capsys.readouterr().out
     assert "--tempo" in out and "--tempo-step" in out
     assert "match --tempo" in identify.__doc__
+
+
+# ---- the span arithmetic and the entries built from it ---------------------------------------------------------------
+def test_tempo_span_is_the_integer_formula():
+    for lo, m in ((0, 1), (0, 7), (5, 12), (300, 1), (1234, 4321)):
+        assert library.tempo_span(lo, m, 256) == (lo, m)
+        for num in range(128, 385):
+            w_lo, w_hi = (lo * num + 128) >> 8, ((lo + m - 1) * num + 128) >> 8
+            assert library.tempo_span(lo, m, num) == (w_lo, w_hi - w_lo + 1), (lo, m, num)
+            assert (w_lo, w_hi) == (int(w(lo, num)), int(w(lo + m - 1, num)))
+
+
+def test_match_and_self_match_entries_are_the_ones_written_before():
+    """_match_entry and _self_match_entry on the library of test_identify_tempo_cpu._cpu_lib (tracks of 0, 7, 1 and 6
+    rows): the dicts are literals computed with the code as it stood before tempo_span and _self_match_entry."""
+    from test_identify_tempo_cpu import _cpu_lib
+    lib = _cpu_lib()
+    assert lib.segment_s == 0.096
+    assert lib._match_entry(3, -2, 4, 5, 0.75, 6, 9) == {
+        "track": 3, "name": "d", "score": 0.75, "votes": 6, "offset": -2, "recording_start_s": 0.384,
+        "track_start_s": 0.192, "overlap_s": 0.48, "coverage": 0.8333333333333334,
+        "recording_coverage": 0.5555555555555556, "track_coverage": 0.8333333333333334}
+    assert lib._match_entry(1, 3, 2, 6, 0.5, 7, 20, 320) == {
+        "track": 1, "name": "b", "score": 0.5, "votes": 7, "offset": 3, "recording_start_s": 0.192,
+        "track_start_s": 0.5760000000000001, "overlap_s": 0.5760000000000001, "coverage": 1.0,
+        "recording_coverage": 0.3, "track_coverage": 1.0, "tempo": 1.25, "tempo_num": 320, "track_overlap_s": 0.672}
+    assert lib._self_match_entry(1, 3, -1, 2, 4, 0.75, 5) == {
+        "track_a": 1, "name_a": "b", "track_b": 3, "name_b": "d", "offset": -1, "a_start_s": 0.192,
+        "b_start_s": 0.096, "overlap_s": 0.384, "coverage": 0.6666666666666666, "score": 0.75, "votes": 5}
+    assert lib._self_match_entry(3, 1, 2, 1, 5, 0.5, 4, 200) == {
+        "track_a": 3, "name_a": "d", "track_b": 1, "name_b": "b", "offset": 2, "a_start_s": 0.096,
+        "b_start_s": 0.28800000000000003, "overlap_s": 0.48, "coverage": 0.8333333333333334, "score": 0.5, "votes": 4,
+        "tempo": 0.78125, "tempo_num": 200, "b_overlap_s": 0.384}
+    for entry, keys in ((lib._match_entry(1, 3, 2, 6, 0.5, 7, 20, 320), "track name score votes offset "
+                         "recording_start_s track_start_s overlap_s coverage recording_coverage track_coverage tempo "
+                         "tempo_num track_overlap_s"),
+                        (lib._self_match_entry(3, 1, 2, 1, 5, 0.5, 4, 200), "track_a name_a track_b name_b offset "
+                         "a_start_s b_start_s overlap_s coverage score votes tempo tempo_num b_overlap_s")):
+        assert list(entry) == keys.split()                                     # the order the keys were written in

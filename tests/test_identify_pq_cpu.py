@@ -208,6 +208,49 @@ def test_compact_library_tables_save_load_and_refusals(tmp_path):
     assert library.FingerprintLibrary.load(str(tmp_path), other, force=True).n_rows == 11
 
 
+def test_rows_and_codes_are_the_appended_chunks_in_order_and_concatenated_once():
+    model, cfg = _tiny_model(), load_config()
+    rng = np.random.RandomState(21)
+    # flat: the empty defaults, then two appends (and one of tracks without rows, which files no chunk)
+    flat = library.FingerprintLibrary(model, cfg, None, None, device="cpu")
+    assert tuple(flat.rows().shape) == (0, 128) and flat.rows().dtype == torch.float32 and flat.rows() is flat.rows()
+    assert (flat.n_rows, flat.first.tolist(), flat.names) == (0, [0], [])
+    r1, r2 = (torch.from_numpy(rng.randn(n, 128).astype(np.float32)) for n in (5, 3))
+    flat._append(r1, [0, 2, 5], None)
+    assert flat.rows() is flat.rows() and torch.equal(flat.rows(), r1)
+    flat._append(r2.numpy().reshape(-1), [0, 0, 3], ["x", 7])                # anything that reshapes to (n, 128)
+    flat._append(torch.zeros((0, 128)), [0, 0], None)
+    got = flat.rows()
+    assert got is flat.rows() and got.dtype == torch.float32 and torch.equal(got, torch.cat([r1, r2]))
+    assert flat.n_rows == 8 and flat.first.tolist() == [0, 2, 5, 5, 8, 8] and flat.first.dtype == np.int64
+    assert flat.names == ["track0", "track1", "x", "7", "track4"] and flat.nbytes == 8 * 512
+    with pytest.raises(ValueError, match="2 names for 1 tracks"):
+        flat._append(r2, [0, 3], ["y", "z"])
+    with pytest.raises(ValueError, match="track table"):
+        flat._append(r2, [0, 2], None)
+    with pytest.raises(NotImplementedError, match="flat form"):
+        _compact(model)[0]._append(r2, [0, 3], None)
+    assert flat.rows() is got and flat.n_tracks == 5                         # a refused append leaves the library alone
+    # compact: the same through codes()
+    cent, books = _quantiser(16, 4, 3)
+    comp = library.FingerprintLibrary(model, cfg, None, None, device="cpu")
+    comp._set_quantiser({"centroids": torch.from_numpy(cent), "codebooks": torch.from_numpy(books)}, 2)
+    a0, c0 = comp.codes()
+    assert tuple(a0.shape) == (0,) and a0.dtype == torch.int32 and tuple(c0.shape) == (0, 16) and c0.dtype == torch.uint8
+    assert all(x is y for x, y in zip(comp.codes(), comp.codes()))
+    a1, a2 = (torch.from_numpy(rng.randint(0, 4, size=n)) for n in (4, 2))  # int64 list ids are stored as int32
+    c1, c2 = (torch.from_numpy(rng.randint(0, 256, size=(n, 16)).astype(np.uint8)) for n in (4, 2))
+    comp._append_codes(a1, c1, [0, 4], ["p"])
+    comp._append_codes(a2, c2, [0, 1, 2], None)
+    got_a, got_c = comp.codes()
+    assert all(x is y for x, y in zip(comp.codes(), (got_a, got_c)))
+    assert got_a.dtype == torch.int32 and torch.equal(got_a, torch.cat([a1, a2]).to(torch.int32))
+    assert got_c.dtype == torch.uint8 and torch.equal(got_c, torch.cat([c1, c2]))
+    assert comp.n_rows == 6 and comp.first.tolist() == [0, 4, 5, 6] and comp.names == ["p", "track1", "track2"]
+    with pytest.raises(ValueError, match="flat library"):
+        flat._append_codes(a1, c1, [0, 4], None)
+
+
 def test_compact_library_refuses_bad_codes():
     model = _tiny_model()
     cent, books = _quantiser(64, 4, 1)

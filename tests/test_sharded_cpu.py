@@ -150,6 +150,48 @@ def test_timeline_is_the_librarys():
     assert sh.timeline(windows) == lib.timeline(windows)
 
 
+def test_both_libraries_answer_with_the_same_front():
+    assert issubclass(ShardedFingerprintLibrary, library.LibraryFront)
+    assert issubclass(library.FingerprintLibrary, library.LibraryFront)
+    assert not issubclass(ShardedFingerprintLibrary, library.FingerprintLibrary)
+    for name in ("identify", "identify_windows", "timeline", "match", "_identify_items", "_match_rows", "_match_entry",
+                 "_load_queries", "_embed", "segments", "_search_and_identify", "_check_item_len", "_fingerprint_tracks",
+                 "_need_dense", "_need_flat", "_need_tempo_form"):
+        assert getattr(ShardedFingerprintLibrary, name) is getattr(library.FingerprintLibrary, name), name
+        assert getattr(ShardedFingerprintLibrary, name) is getattr(library.LibraryFront, name), name
+    for name in ("_search_rows", "_identify_lists", "_match_lists"):           # the hooks: each library's own
+        own = {vars(cls)[name] for cls in (library.LibraryFront, library.FingerprintLibrary, ShardedFingerprintLibrary)}
+        assert len(own) == 3, name
+    assert ShardedFingerprintLibrary.is_compact is False
+
+
+def test_a_front_without_hooks_refuses_at_the_search():
+    lib = _cpu_lib()
+    reached = []
+
+    class Bare(library.LibraryFront):
+        def segments(self, wav):
+            return torch.zeros((3, 4, 4))
+
+        def _embed(self, segs):
+            reached.append(int(segs.shape[0]))
+            return torch.zeros((segs.shape[0], 128))
+
+    bare = Bare(lib.model, lib.settings, "f32", torch.device("cpu"), 1)
+    assert (bare.n_tracks, bare.n_rows, bare.names, bare.row_stride, bare.settings) == (0, 0, [], 1, lib.settings)
+    assert bare.identify(np.zeros(16000, np.float32)) == [] and reached == []   # no rows: nothing to search
+    bare.first, bare.names = lib.first, lib.names
+    with pytest.raises(NotImplementedError):
+        bare.identify(np.zeros(16000, np.float32))
+    assert reached == [3]                                                    # embedded, then refused at _search_rows
+    q, ids = torch.zeros((3, 128)), torch.zeros((3, 2), dtype=torch.int64)
+    for call in (lambda: bare._search_rows(q, 2), lambda: bare.is_compact,
+                 lambda: bare._identify_lists(q, ids, np.zeros(1, np.int64), np.full(1, 3, np.int32), 5, None, 3),
+                 lambda: bare._match_lists(q, torch.tensor([0, 3]), 2, None, {})):
+        with pytest.raises(NotImplementedError):
+            call()
+
+
 # ---- files --------------------------------------------------------------------------------------------------------
 def test_save_and_load_round_trip(tmp_path):
     lib = _cpu_lib()
