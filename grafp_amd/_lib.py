@@ -122,6 +122,7 @@ SIGNATURES = {
     "grafp_time_stretch_f32": (_I, [_P, _L, _I, _I, _L, _P, _P, _L, _I, _P, _L, _P]),
     "grafp_identify_f32": (_I, [_P, _L, _P, _I, _P, _L, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "grafp_identify_thin_f32": (_I, [_P, _L, _P, _I, _I, _P, _L, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "grafp_identify_stride_f32": (_I, [_P, _L, _P, _I, _I, _P, _L, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "grafp_identify_pq_f32": (_I, [_P, _P, _L, _P, _I, _P, _I, _P, _I, _P, _L, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P,
                                    _P, _P]),
     "grafp_identify_tempo_f32": (_I, [_P, _L, _P, _I, _P, _L, _P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P,

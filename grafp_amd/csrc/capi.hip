@@ -170,6 +170,31 @@ extern "C" int grafp_identify_thin_f32(const float *index_rows, int64_t n, const
                                        out_score, out_votes, (hipStream_t)stream);
 }
 
+// Identification of items that hold every query_stride-th segment of the recording (identify_stride.hip): argument
+// checks here and there (the stride and the 2^32 bound of the alignment key sit next to the kernel).
+namespace grafp {
+int identify_stride_launch(const float *rows, int64_t n, const int64_t *first, int T, int query_stride,
+                           const float *q_rows, const int64_t *ids, int k, const int64_t *item_row,
+                           const int *item_len, int n_items, int max_len, int top, int min_overlap, int32_t *out_track,
+                           int32_t *out_offset, float *out_score, int32_t *out_votes, hipStream_t stream);
+}  // namespace grafp
+
+extern "C" int grafp_identify_stride_f32(const float *index_rows, int64_t n, const int64_t *track_first_row,
+                                         int n_tracks, int query_stride, const float *q_rows, int64_t n_qrows,
+                                         const int64_t *topk_ids, int k, const int64_t *item_row, const int *item_len,
+                                         int n_items, int max_len, int top, int min_overlap, int32_t *out_track,
+                                         int32_t *out_offset, float *out_score, int32_t *out_votes,
+                                         grafp_stream_t stream) {
+    GRAFP_REQUIRE(index_rows && track_first_row && q_rows && topk_ids && item_row && item_len && out_track &&
+                  out_offset && out_score && out_votes, "identify_stride: null pointer");
+    const int st = check_identify("identify_stride", n, nullptr, n_tracks, n_qrows, n_items, top,
+                                  (uintptr_t)index_rows | (uintptr_t)q_rows, 0);
+    if (st != GRAFP_OK) return st;
+    return grafp::identify_stride_launch(index_rows, n, track_first_row, n_tracks, query_stride, q_rows, topk_ids, k,
+                                         item_row, item_len, n_items, max_len, top, min_overlap, out_track, out_offset,
+                                         out_score, out_votes, (hipStream_t)stream);
+}
+
 // Identification of recordings that play faster or slower than the catalogue (identify_tempo.hip): the checks shared
 // with grafp_identify_f32 here, the ratio checks, the 2^32 bound of the alignment key and the two launches there.
 namespace grafp {

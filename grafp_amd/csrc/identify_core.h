@@ -24,6 +24,8 @@
 //     float score(span, q4, a, lo, l, m)   the span call of phase 3: m pairs from query row lo on
 //   TempoGrid   one row per fine position, query row s sits w(s) = (s * num + 128) >> 8 rows after row 0
 //               (identify_tempo.hip): a = r - w(s), the library rows of the pairs are gathered (TempoRowSpan)
+//   StrideGrid  one row per fine position, the item holds every Q-th segment of the recording: query row s sits s * Q
+//               rows after row 0 (identify_stride.hip): a = r - s * Q, the library steps Q rows per pair (StepRowSpan)
 // Compiles with and without the packed-f32 instructions; every user is built without (Makefile NOPK).
 #pragma once
 #include <limits.h>
@@ -41,6 +43,7 @@ constexpr int ID_MAX_KEYS = 8192;
 constexpr int ID_SHIFT = ID_MAX_LEN - 1;                 // a + ID_SHIFT >= 0 for every hit
 constexpr int ID_TEMPO_SHIFT = 511;                      // TempoGrid: w(255) = 510 at num = SEQ_TEMPO_MAX
 constexpr int ID_MAX_STRIDE = 32;                        // ThinGrid: the largest row stride
+constexpr int ID_MAX_QUERY_STRIDE = 32;                  // StrideGrid: the largest query stride
 constexpr size_t ID_LDS = 160 * 1024 - 256;      // dynamic LDS budget (the static s_ncand sits next to it)
 
 // The launch plan of one identify kernel: slots per item, dynamic LDS bytes, and whether the query rows sit in LDS.
@@ -149,6 +152,35 @@ struct TempoGrid {
     template <typename Span>
     __device__ __forceinline__ float score(const Span &span, const float4 *q4, int64_t a, int lo, int l, int m) const {
         return span(q4 + lo * (SEQ_D / 4) + l, a, lo, num, l, m);
+    }
+};
+
+// One row per fine position; the item's rows are every Q-th segment of the recording, Q in [1, ID_MAX_QUERY_STRIDE], so
+// query row s sits s * Q rows after query row 0 (TempoGrid's w at num = 256 * Q, exactly) and a = r - s * Q.  The pairs
+// of an alignment are a contiguous range of s: s * Q >= x iff s >= ceil(x / Q).  The host keeps n + shift() below 2^32.
+// Everything is compared in 64 bits before it is narrowed (as ThinGrid): a table the caller vouched for wrongly yields
+// no pairs instead of a query row outside the item.  Its Span steps the library Q rows per pair (StepRowSpan).
+struct StrideGrid {
+    int Q;
+    __device__ __forceinline__ int64_t fine(int64_t r) const { return r; }
+    __device__ __forceinline__ int64_t row(int64_t p) const { return p; }
+    __device__ __forceinline__ int need(int need_q) const { return need_q; }
+    __device__ __forceinline__ int at(int s) const { return s * Q; }
+    __device__ __forceinline__ int shift() const { return (ID_MAX_LEN - 1) * Q; }
+    __device__ __forceinline__ int64_t cap(int64_t L) const { return L / Q > 1 ? L / Q : 1; }
+    // the first s in [0, ql] with s * Q >= x (ql: none)
+    __device__ __forceinline__ int first_at(int64_t x, int ql) const {
+        if (x <= 0) return 0;
+        const int64_t s = (x + Q - 1) / Q;
+        return s < ql ? (int)s : ql;
+    }
+    __device__ __forceinline__ void pairs(int64_t a, int64_t f0, int64_t f1, int ql, int &lo, int &o) const {
+        lo = first_at(f0 - a, ql);
+        o = first_at(f1 - a, ql) - lo;
+    }
+    template <typename Span>
+    __device__ __forceinline__ float score(const Span &span, const float4 *q4, int64_t a, int lo, int l, int m) const {
+        return span(q4 + lo * (SEQ_D / 4) + l, a + (int64_t)lo * Q, l, m);
     }
 };
 

@@ -7,6 +7,7 @@
 //   RowSpan<kUnroll>      the library's resident (n, 128) f32 rows     identify.hip, selfmatch.hip, crossmatch.hip
 //   StridedRowSpan<kUnroll>   the same rows, the x rows of consecutive pairs x_step float4s apart    identify_thin.hip
 //   TempoRowSpan<kUnroll>     the same rows, gathered along a sloped alignment (its own call, see there)  identify_tempo.hip
+//   StepRowSpan<kUnroll>      the same rows, the library rows of consecutive pairs Q rows apart (its own loop)  identify_stride.hip
 //   PqSpan<kM, kUnroll>   rows decoded from IVF-PQ codes while scored  identify_pq.hip, crossmatch.hip
 // Library row r of the compact form is
 //   dec[r][j] = centroids[list_id[r]][j] + codebooks[m][codes[r][m]][c],  m = j / dsub, c = j % dsub, dsub = 128 / M
@@ -48,6 +49,31 @@ struct TempoRowSpan {
         for (int t = 0; t < m; ++t) {
             const int64_t row = a + (((lo + t) * num + 128) >> 8);
             const float4 q = x[(int64_t)t * (SEQ_D / 4)], r = rw4[row * (SEQ_D / 4) + l];
+            acc = __builtin_fmaf(q.x, r.x, acc);
+            acc = __builtin_fmaf(q.y, r.y, acc);
+            acc = __builtin_fmaf(q.z, r.z, acc);
+            acc = __builtin_fmaf(q.w, r.w, acc);
+        }
+#pragma unroll
+        for (int s = 16; s > 0; s >>= 1) acc += __shfl_xor(acc, s);      // stays inside the 32-lane half
+        return acc;
+    }
+};
+
+// The pairs of an item that holds every Q-th segment of the recording (StrideGrid of identify_core.h): pair t is query
+// row x + t with library row `row` + t * Q, each still one whole 512-byte row per half-wave.  span_sum's order; at Q = 1
+// the rows and so the bits are RowSpan's, at Q = 2 TempoRowSpan's at num = 512.
+template <int kUnroll>
+struct StepRowSpan {
+    const float4 *rw4;
+    int Q;                                       // library rows between two consecutive pairs
+    __device__ __forceinline__ float operator()(const float4 *x, int64_t row, int l, int m) const {
+        const float4 *y = rw4 + row * (SEQ_D / 4) + l;
+        const int64_t y_step = (int64_t)Q * (SEQ_D / 4);
+        float acc = 0.0f;
+#pragma unroll kUnroll
+        for (int t = 0; t < m; ++t) {
+            const float4 q = x[(int64_t)t * (SEQ_D / 4)], r = y[t * y_step];
             acc = __builtin_fmaf(q.x, r.x, acc);
             acc = __builtin_fmaf(q.y, r.y, acc);
             acc = __builtin_fmaf(q.z, r.z, acc);

@@ -4,13 +4,14 @@
                                        [--index flat|ivfpq --nlist 64 --pq-m 64 --nprobe 20 --train-rows 65536]
                                        [--row-stride D] [--shards N [--devices cuda:0,cuda:1]]
   python -m grafp_amd.identify query --ckp MODEL.pth --library LIBDIR FILES... [--top 5] [--window S --hop S]
-                                       [--tempo X [--tempo-step G]]
+                                       [--tempo X [--tempo-step G]] [--query-stride Q]
   python -m grafp_amd.identify dedup --ckp MODEL.pth --library LIBDIR [--min-overlap 3] [--coverage 0.9] [--json OUT]
                                        [--tempo X [--tempo-step G]]
   python -m grafp_amd.identify match --ckp MODEL.pth --library LIBDIR FILES... [--min-overlap 3] [--min-votes 4]
                                        [--min-score S] [--top 8] [--k-probe 20] [--json OUT]
                                        [--tempo X [--tempo-step G]]
   python -m grafp_amd.identify monitor --ckp MODEL.pth LIBDIR FILES... [--chunk-s 1.0] [--window 3 --hop 1] [--top 5]
+                                       [--query-stride Q]
 
 `build` fingerprints every track of the source (anything DeviceAudioCorpus accepts) into LIBDIR -- with --index ivfpq as
 a compact library of IVF-PQ codes (about 150 bytes per row instead of 772; `query` works on either form, `dedup` needs
@@ -32,7 +33,9 @@ becomes due ({"channel", "file", start_s, end_s, segment_start_s, matches}) and,
 span of each channel ({"channel", "file", "span": ...}).  build --shards N writes a sharded library
 (grafp_amd/sharded.py: N flat shards over contiguous track ranges, shard s on the s-th of --devices, all on one device
 without it); `query`, `match` and `monitor` load a directory that holds shards.json as one (--devices again says where
-the shards go) and answer as the one-card library would; `dedup` across shards is not built."""
+the shards go) and answer as the one-card library would; `dedup` across shards is not built.  query --query-stride Q and
+monitor --query-stride Q embed only every Q-th segment of the recordings (1 / Q of the model's work; a flat library that
+keeps every row, no --tempo) and align those (csrc/identify_stride.hip); what is printed keeps its form."""
 import argparse
 import json
 import sys
@@ -83,6 +86,8 @@ def main(argv=None):
     q.add_argument("--tempo", type=float, default=None,
                    help="also search recordings that play up to this fraction faster or slower (0.06: 0.94 to 1.06)")
     q.add_argument("--tempo-step", type=int, default=None, help="spacing of the ratios searched, in 1/256")
+    q.add_argument("--query-stride", type=int, default=1,
+                   help="embed every Q-th segment of a recording only (1 to 32; a flat library that keeps every row)")
     q.add_argument("--force", action="store_true", help="use a library made with another model")
     q.add_argument("--devices", default=None, help="a sharded library: its shards' devices, comma-separated")
     d = sub.add_parser("dedup", help="find tracks of a library that share audio")
@@ -128,6 +133,8 @@ def main(argv=None):
     mo.add_argument("--top", type=int, default=5)
     mo.add_argument("--k-probe", type=int, default=20)
     mo.add_argument("--min-score", type=float, default=None, help="timeline: drop windows whose best match is weaker")
+    mo.add_argument("--query-stride", type=int, default=1,
+                    help="embed every Q-th segment of a channel only (1 to 32; a flat library that keeps every row)")
     mo.add_argument("--force", action="store_true", help="use a library made with another model")
     mo.add_argument("--devices", default=None, help="a sharded library: its shards' devices, comma-separated")
     args = ap.parse_args(argv)
@@ -194,7 +201,7 @@ def main(argv=None):
         waves = lib._load_queries(list(args.files), None)
         chunk = max(1, int(args.chunk_s * lib.settings["fs"]))
         mon = StreamMonitor(lib, len(waves), window_s=args.window, hop_s=args.hop, top=args.top, k_probe=args.k_probe,
-                            max_chunk_s=args.chunk_s)
+                            max_chunk_s=args.chunk_s, query_stride=args.query_stride)
 
         def report(per_channel):
             for ch, windows in enumerate(per_channel):
@@ -222,12 +229,14 @@ def main(argv=None):
         return 0
     if args.window is None:
         for path, matches in zip(args.files, lib.identify(list(args.files), top=args.top, k_probe=args.k_probe,
-                                                            tempo=args.tempo, tempo_step=args.tempo_step)):
+                                                            tempo=args.tempo, tempo_step=args.tempo_step,
+                                                            query_stride=args.query_stride)):
             print(json.dumps({"query": path, "matches": matches}))
     else:
         for path in args.files:
             windows = lib.identify_windows(path, window_s=args.window, hop_s=args.hop, top=args.top,
-                                           k_probe=args.k_probe, tempo=args.tempo, tempo_step=args.tempo_step)
+                                           k_probe=args.k_probe, tempo=args.tempo, tempo_step=args.tempo_step,
+                                           query_stride=args.query_stride)
             for span in lib.timeline(windows):
                 print(json.dumps({"query": path, **span}))
     return 0

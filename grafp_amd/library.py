@@ -28,6 +28,12 @@ their slope.  match(tempo=...) does the same for whole recordings (one ops.cross
 csrc/crossmatch_tempo.hip) and self_matches(tempo=...) for the tracks of the library itself (ops.self_match_tempo,
 csrc/selfmatch_tempo.hip).  A flat library that keeps every row only; speed, not pitch; StreamMonitor knows no tempo.
 
+identify(query_stride=Q) and identify_windows(query_stride=Q) are the query side's counterpart of row_stride: only the
+segments 0, Q, 2 Q, ... of a recording are embedded and searched -- the encoder is nearly all of a query's cost -- and
+one ops.identify_stride launch (csrc/identify_stride.hip) aligns them on the dense rows of the library; a query may
+then hold 256 * Q segments.  A flat library that keeps every row only, no tempo; match() and self_matches() do not take
+it; StreamMonitor does.
+
 match() takes whole recordings of any length that are NOT in the library and says which tracks they share audio with,
 where and how much (spans, coverage, votes: what self_matches says about the library's own tracks) -- the question an
 ingest gate asks before add().  It runs on ops.cross_match (f32 rows) or ops.cross_match_pq (codes), the kernels of
@@ -106,6 +112,17 @@ def window_items(n_seg_total, n_samples, settings, window_s=3.0, hop_s=1.0):
         rows.append(j0)
         lens.append(max(0, min(per_window, n_seg_total - j0)))
     return np.array(starts, np.float64), np.array(rows, np.int64), np.array(lens, np.int32)
+
+
+def kept_items(item_row, item_len, Q):
+    """Items over the dense segments [item_row, item_row + item_len) of a recording, of which only the segments whose
+    index is a multiple of Q are kept (kept row c is segment c * Q) -> (kept_row, kept_len), the same items over the kept
+    rows: the first is c0 = ceil(item_row / Q), the count max(0, (item_row + item_len - 1) // Q - c0 + 1), 0 for an empty
+    item.  An item with no kept row still gets c0 as its row."""
+    j, n, Q = np.asarray(item_row, np.int64), np.asarray(item_len, np.int64), int(Q)
+    c0 = -(-j // Q)
+    cnt = np.where(n > 0, np.maximum(0, (j + n - 1) // Q - c0 + 1), 0)
+    return c0.astype(np.int64), cnt.astype(np.int32)
 
 
 def tempo_ratios(tempo, max_len, step=None):
@@ -234,9 +251,10 @@ class LibraryFront:
         """q (n, 128) f32 -> ids (n, min(k_probe, n_rows)) int64, each row's nearest library rows, on the device."""
         raise NotImplementedError
 
-    def _identify_lists(self, q, ids, item_row, item_len, top, min_overlap, max_len, nums=None):
+    def _identify_lists(self, q, ids, item_row, item_len, top, min_overlap, max_len, nums=None, q_stride=1):
         """The launch of _identify_items -> the op's device tensors (track, offset, score, votes and, with the ratio
-        grid nums, ratio), nothing read back."""
+        grid nums, ratio), nothing read back.  q_stride: the items' rows are every q_stride-th segment of the
+        recording (min_overlap and max_len then count those rows)."""
         raise NotImplementedError
 
     def _match_lists(self, qb, src, k_probe, nums, kw):
@@ -281,6 +299,20 @@ class LibraryFront:
         if tempo is not None:
             self._need_flat(f"{what}(tempo=...)")
             self._need_dense(f"{what}(tempo=...)")
+
+    def _need_stride_form(self, what, query_stride, tempo=None):
+        """The checks of a query_stride: an integer in [1, ops.IDENTIFY_MAX_QUERY_STRIDE]; above 1 it needs a flat
+        library that keeps every row, and no tempo.  -> the stride as an int."""
+        Q = int(query_stride)
+        if Q != query_stride or not 1 <= Q <= ops.IDENTIFY_MAX_QUERY_STRIDE:
+            raise ValueError(f"query_stride={query_stride} not in [1, {ops.IDENTIFY_MAX_QUERY_STRIDE}]")
+        if Q > 1:
+            if tempo is not None:
+                raise NotImplementedError(f"FingerprintLibrary.{what}(query_stride={Q}) with tempo=... is not built: "
+                                          "a strided query is identified at the catalogue's speed only")
+            self._need_flat(f"{what}(query_stride={Q})")
+            self._need_dense(f"{what}(query_stride={Q})")
+        return Q
 
     # ---- fingerprinting --------------------------------------------------------------------------------------
     def _autocast(self):
@@ -374,19 +406,24 @@ class LibraryFront:
         q = self._embed(segs)
         return q, self._search_rows(q, k_probe)
 
-    def _identify_items(self, q, ids, item_row, item_len, top, min_overlap, max_len=None, tempo=None, tempo_step=None):
+    def _identify_items(self, q, ids, item_row, item_len, top, min_overlap, max_len=None, tempo=None, tempo_step=None,
+                        q_stride=1):
         """One identify launch (the kernel of the library's form) for all items over the rows q and their hits ids ->
         per-item lists of matches.  max_len: an upper bound of the items' lengths (None: the longest).  (StreamMonitor
         calls it with rows it kept from earlier pushes.)  tempo: tempo_ratios' argument; the launch is then
-        ops.identify_tempo over the ratio grid of the longest item, and every match names its ratio."""
+        ops.identify_tempo over the ratio grid of the longest item, and every match names its ratio.  q_stride: the rows
+        q are every q_stride-th segment of the recording and the items count those rows; min_overlap stays in dense
+        segments (the op gets max(1, min_overlap // q_stride) pairs) and the offsets in dense segments."""
         n_items = len(item_row)
         longest = int(np.max(item_len, initial=0))
         if n_items == 0 or longest == 0:
             return [[] for _ in range(n_items)]
         max_len = longest if max_len is None else max(int(max_len), longest)
         nums = None if tempo is None else tempo_ratios(tempo, longest, tempo_step)
+        if q_stride != 1 and min_overlap is not None:
+            min_overlap = max(1, int(min_overlap) // q_stride)
         lists = self._identify_lists(q, ids, np.asarray(item_row, np.int64), np.asarray(item_len, np.int32), top,
-                                     min_overlap, max_len, nums)
+                                     min_overlap, max_len, nums, q_stride)
         tr, off, sc, vo = (t.cpu().numpy() for t in lists[:4])
         ra = lists[4].cpu().numpy() if nums is not None else None
         step, hop, fs = self.step, self.settings["hop_len"], self.settings["fs"]
@@ -406,9 +443,11 @@ class LibraryFront:
             out.append(res)
         return out
 
-    def _search_and_identify(self, segs, item_row, item_len, top, k_probe, min_overlap, tempo=None, tempo_step=None):
+    def _search_and_identify(self, segs, item_row, item_len, top, k_probe, min_overlap, tempo=None, tempo_step=None,
+                             q_stride=1):
         """One batched embed + search of all segments, one ops.identify launch for all items -> per-item lists.  (The
-        queries' segments are all embedded, whatever the library's row_stride: the query side stays dense.)"""
+        segments given are all embedded, whatever the library's row_stride: against a thinned library the query side
+        stays dense.  q_stride: segs are every q_stride-th segment of the recordings and the items count those.)"""
         n_items = len(item_row)
         if tempo is not None:
             tempo_ratios(tempo, max(1, int(np.max(item_len, initial=0))), tempo_step)      # refuse a bad range early
@@ -416,9 +455,11 @@ class LibraryFront:
             return [[] for _ in range(n_items)]
         self._check_item_len(int(np.max(item_len)), k_probe)
         q, ids = self._embed_and_search(segs, k_probe)
-        return self._identify_items(q, ids, item_row, item_len, top, min_overlap, tempo=tempo, tempo_step=tempo_step)
+        return self._identify_items(q, ids, item_row, item_len, top, min_overlap, tempo=tempo, tempo_step=tempo_step,
+                                    q_stride=q_stride)
 
-    def identify(self, queries, fs=None, top=5, k_probe=20, min_overlap=None, tempo=None, tempo_step=None):
+    def identify(self, queries, fs=None, top=5, k_probe=20, min_overlap=None, tempo=None, tempo_step=None,
+                 query_stride=1):
         """queries: one waveform, a list of ragged waveforms, or file paths; at `fs` (default settings['fs']; other rates
         are resampled on the device).  -> per query, a list of matches {track, name, offset, offset_s, score, votes},
         best first.  offset_s = offset * step * hop_len / fs is where the query's first segment sits in the track.  A
@@ -430,31 +471,46 @@ class LibraryFront:
         sloped alignment of every ratio; each match then also carries "tempo" (the ratio) and "tempo_num" (ratio *
         256), and offset / offset_s keep their meaning.  Needs a flat library that keeps every row.  Speed only: pitch
         is not searched; match() takes the same tempo for whole recordings and self_matches() for the tracks of the
-        library itself; StreamMonitor, the IVF-PQ and the thinned forms know no tempo."""
+        library itself; StreamMonitor, the IVF-PQ and the thinned forms know no tempo.
+        query_stride: Q in [1, 32]; above 1 only the segments 0, Q, 2 Q, ... of every query are embedded and searched
+        (1 / Q of the model's work) and one ops.identify_stride launch aligns them (csrc/identify_stride.hip).  The
+        matches keep their form and offset / offset_s their meaning; min_overlap stays in dense segments (the kernel
+        asks for max(1, min_overlap // Q) pairs); a query may then hold 256 * Q segments.  Needs a flat library that
+        keeps every row, and no tempo."""
         self._need_tempo_form("identify", tempo)
+        Q = self._need_stride_form("identify", query_stride, tempo)
         single = is_single(queries)
         waves = self._load_queries(queries, fs)
-        segs = [self.segments(w) for w in waves]
+        segs = [self.segments(w)[::Q] for w in waves]
         lens = np.array([s.shape[0] for s in segs], np.int32)
         allsegs = torch.cat(segs, dim=0) if segs else torch.empty((0,), device=self.device)
         res = self._search_and_identify(allsegs, track_table(lens)[:-1], lens, int(top), int(k_probe), min_overlap,
-                                        tempo, tempo_step)
+                                        tempo, tempo_step, Q)
         return res[0] if single and len(res) == 1 else res
 
     def identify_windows(self, recording, window_s=3.0, hop_s=1.0, fs=None, top=5, k_probe=20, min_overlap=None,
-                         tempo=None, tempo_step=None):
+                         tempo=None, tempo_step=None, query_stride=1):
         """A long recording cut into items of window_s seconds every hop_s seconds.  The recording is segmented,
         fingerprinted and searched once; all windows are identified in one launch.  -> per window
         {start_s, end_s, segment_start_s, matches}; segment_start_s is where the window's first segment starts in the
-        recording (the time its matches' offset_s refers to).  tempo, tempo_step: as for identify()."""
+        recording (the time its matches' offset_s refers to).  tempo, tempo_step: as for identify().
+        query_stride: as for identify(); the recording's segments 0, Q, 2 Q, ... are embedded once, the windows stay
+        those of window_items and each takes the kept segments inside it (kept_items), so segment_start_s is a multiple
+        of Q segment hops; a window that holds no kept segment keeps the dense segment_start_s and has no matches."""
         self._need_tempo_form("identify_windows", tempo)
+        Q = self._need_stride_form("identify_windows", query_stride, tempo)
         wave = self._load_queries([recording], fs)[0]
         segs = self.segments(wave)
         starts, rows, lens = window_items(segs.shape[0], wave.numel(), self.settings, window_s, hop_s)
-        res = self._search_and_identify(segs, rows, lens, int(top), int(k_probe), min_overlap, tempo, tempo_step)
+        first_seg = rows
+        if Q > 1:
+            segs = segs[::Q].contiguous()
+            rows, lens = kept_items(rows, lens, Q)
+            first_seg = np.where(lens > 0, rows * Q, first_seg)
+        res = self._search_and_identify(segs, rows, lens, int(top), int(k_probe), min_overlap, tempo, tempo_step, Q)
         seg_s = self.segment_s
         return [{"start_s": float(s), "end_s": float(s) + window_s, "segment_start_s": int(r) * seg_s, "matches": m}
-                for s, r, m in zip(starts, rows, res)]
+                for s, r, m in zip(starts, first_seg, res)]
 
     def timeline(self, windows, min_score=None):
         """What played when: consecutive windows whose best match is the same track at a consistent position (the
@@ -923,12 +979,14 @@ class FingerprintLibrary(LibraryFront):
     def _search_rows(self, q, k_probe):
         return self.index.search(q, min(int(k_probe), self.n_rows))[1]
 
-    def _identify_lists(self, q, ids, item_row, item_len, top, min_overlap, max_len, nums=None):
+    def _identify_lists(self, q, ids, item_row, item_len, top, min_overlap, max_len, nums=None, q_stride=1):
         """One launch of the op of the library's form.  (ShardedFingerprintLibrary runs and merges one per shard.)"""
         dev = self.device
         tail = (torch.from_numpy(self.first).to(dev), q, ids, torch.from_numpy(item_row).to(dev),
                 torch.from_numpy(item_len).to(dev))
         kw = dict(top=top, min_overlap=min_overlap, max_len=max_len)
+        if q_stride != 1:                                            # (the front refused tempo and the other forms)
+            return ops.identify_stride(self.rows(), *tail, q_stride, **kw)
         if nums is not None:
             return ops.identify_tempo(self.rows(), *tail, nums, **kw)
         if self.is_compact:

@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .library import n_segments, segment_step, track_table, window_items
+from .library import kept_items, n_segments, segment_step, track_table, window_items
 
 
 # ---- readiness rules: pure host functions ------------------------------------------------------------------------------
@@ -242,11 +242,18 @@ class StreamMonitor:
 
     Per channel the monitor keeps the fingerprint rows and hit ids from the first row of the next window that has not
     been reported, and the windows it reported (timeline()).  max_chunk_s sizes the spectrogram ring; longer chunks are
-    fed in pieces.  All work runs on the current stream."""
+    fed in pieces.  All work runs on the current stream.
+
+    query_stride = Q > 1 (a flat library that keeps every row): a channel keeps only the segments whose index in the
+    channel's stream is a multiple of Q.  push() hands only those to the model (1 / Q of its work); push_rows() still
+    takes the channel's dense rows and files the kept ones, the others are never read.  The windows are scheduled on
+    the dense segment counts as without it, each one's item is library.kept_items of it, and what is reported is
+    identify_windows(query_stride=Q) of the finished stream."""
 
     def __init__(self, library, channels, window_s=3.0, hop_s=1.0, top=5, k_probe=20, min_overlap=None,
-                 max_chunk_s=1.0):
+                 max_chunk_s=1.0, query_stride=1):
         self.library = library
+        self.query_stride = library._need_stride_form("StreamMonitor", query_stride)
         c = library.settings
         _check_settings(c)
         self.channels = int(channels)
@@ -259,18 +266,20 @@ class StreamMonitor:
         self.per_window = n_segments(int(round(self.window_s * c["fs"])), c)
         if self.per_window < 1:
             raise ValueError(f"a window of {window_s} s is shorter than one segment")
-        library._check_item_len(self.per_window, self.k_probe)
+        self.per_kept = -(-self.per_window // self.query_stride)      # the most kept rows a window holds
+        library._check_item_len(self.per_kept, self.k_probe)
         self.front = StreamFrontEnd(c, self.channels, library.device, max_chunk_s)
         C = self.channels
         self._mode = [None] * C                  # None, "audio" (push) or "rows" (push_rows)
         self._closed = np.zeros(C, bool)
-        self._n_rows = np.zeros(C, np.int64)     # fingerprint rows (segments) so far
+        self._n_rows = np.zeros(C, np.int64)     # segments so far (dense, whatever the query stride)
         self._samples = np.zeros(C, np.int64)    # rows-fed channels: the samples the caller said it has seen
         self._n_win = np.zeros(C, np.int64)      # windows reported
         self._windows = [[] for _ in range(C)]
         # the rows and hits still needed, channel by channel in ONE pair of tensors: channel c's are
         # [_first[c], _first[c + 1]), the first of them is row _row0[c] of the channel; _stale[c] of them are no longer
-        # needed and go at the next ingest (one gather per push, whatever the number of channels)
+        # needed and go at the next ingest (one gather per push, whatever the number of channels).  These count KEPT
+        # rows: kept row c of a channel is its segment c * query_stride
         self._q = self._ids = None
         self._first, self._row0, self._stale = np.zeros(C + 1, np.int64), np.zeros(C, np.int64), np.zeros(C, np.int64)
 
@@ -288,6 +297,25 @@ class StreamMonitor:
         if self._mode[ch] not in (None, mode):
             raise ValueError(f"channel {ch} is fed with {'push_rows' if mode == 'audio' else 'push'} already")
         self._mode[ch] = mode
+
+    def _kept_of(self, ch, n):
+        """Of channel ch's next n segments, behind its _n_rows[ch] earlier ones, those whose index in the channel's
+        stream is a multiple of query_stride -> their positions among the n."""
+        lo, Q = int(self._n_rows[ch]), self.query_stride
+        return np.arange(-(-lo // Q) * Q, lo + int(n), Q) - lo
+
+    def _kept(self, packed, counts):
+        """Of the new segments of all channels, packed channel by channel (counts[ch] of channel ch), the kept ones, by
+        one gather -> (kept, kept counts).  At query_stride 1: (packed, counts)."""
+        if self.query_stride == 1:
+            return packed, counts
+        base, pick, kept = track_table(counts), [], np.zeros(self.channels, np.int64)
+        for ch in np.nonzero(counts)[0]:
+            idx = self._kept_of(ch, counts[ch])
+            pick.append(base[ch] + idx)
+            kept[ch] = idx.size
+        pick = np.concatenate(pick).astype(np.int64) if pick else np.zeros(0, np.int64)
+        return packed[torch.from_numpy(pick).to(packed.device)], kept
 
     def push(self, chunks, fs=None):
         """One 1-D waveform per channel (tensor or array; empty or None: nothing for that channel), at `fs` (default
@@ -318,17 +346,20 @@ class StreamMonitor:
             for j, ch in enumerate(live):
                 waves[ch] = out[starts[j]:starts[j] + out_lens[j]]
         segs, counts = self.front.push(waves)
+        segs, kept = self._kept(segs, counts)
         rows = lib._embed(segs) if segs.shape[0] else None
-        return self._advance(rows, counts, live)
+        return self._advance(rows, counts, live, kept)
 
     def push_rows(self, rows_per_channel, samples=None):
         """The same scheduling from fingerprint rows the caller already has (its own embedder, or rows computed
         elsewhere): per channel a (n, 128) tensor of the channel's NEXT n rows, or None.  samples: per channel, the
         samples of the stream seen so far (None: the fewest samples that many segments need, samples_lower_bound --
-        windows are then reported as early as they can be told to be final).  -> per channel, the list of new windows."""
+        windows are then reported as early as they can be told to be final).  -> per channel, the list of new windows.
+        With a query_stride the rows given stay the channel's dense ones; only the kept ones are read."""
         items = self._per_channel(rows_per_channel, "push_rows")
         samples = None if samples is None else self._per_channel(samples, "push_rows")
         dev, parts, counts, live = self.library.device, [], np.zeros(self.channels, np.int64), []
+        kept = counts if self.query_stride == 1 else np.zeros(self.channels, np.int64)
         for ch, r in enumerate(items):
             if r is None:
                 continue
@@ -337,8 +368,11 @@ class StreamMonitor:
                 raise ValueError(f"push_rows: channel {ch}'s rows must be (n, 128), not {tuple(r.shape)}")
             if r.shape[0]:
                 self._claim(ch, "rows")
-                parts.append(r.to(dev, torch.float32))
                 counts[ch] = r.shape[0]
+                if self.query_stride != 1:
+                    idx = self._kept_of(ch, r.shape[0])
+                    r, kept[ch] = r[torch.from_numpy(idx).to(r.device)], idx.size
+                parts.append(r.to(dev, torch.float32))
                 live.append(ch)
         for ch in range(self.channels):
             if samples is not None and samples[ch] is not None and self._mode[ch] != "audio":
@@ -348,7 +382,7 @@ class StreamMonitor:
                     live.append(ch)
         if not live:
             return [[] for _ in range(self.channels)]
-        return self._advance(torch.cat(parts).contiguous() if parts else None, counts, live)
+        return self._advance(torch.cat(parts).contiguous() if parts else None, counts, live, kept)
 
     def end(self, channel, n_samples=None):
         """The stream on `channel` (an index or several) has ended: flushes the frames, segments and windows that were
@@ -371,9 +405,10 @@ class StreamMonitor:
                 self._samples[ch] = int(n_samples)
         audio = [ch for ch in chans if self._mode[ch] != "rows"]
         segs, counts = self.front.end(audio)
+        segs, kept = self._kept(segs, counts)
         rows = self.library._embed(segs) if segs.shape[0] else None
         self._closed[chans] = True
-        out = self._advance(rows, counts, chans)
+        out = self._advance(rows, counts, chans, kept)
         return out if many else out[chans[0]] if chans else []
 
     def reset(self, channel):
@@ -419,14 +454,14 @@ class StreamMonitor:
         self._row0 += self._stale
         self._stale[:] = 0
         self._first = track_table(kept)
-        self._n_rows += counts
 
-    def _advance(self, rows, counts, touched):
-        """File the new rows, find the windows that became due on the touched channels and identify them all in one
-        launch."""
-        lib, c = self.library, self.library.settings
+    def _advance(self, rows, counts, touched, kept):
+        """File the new rows (kept[ch] of channel ch, of its counts[ch] new segments), find the windows that became due
+        on the touched channels and identify them all in one launch."""
+        lib, c, Q = self.library, self.library.settings, self.query_stride
         if rows is not None and rows.shape[0]:
-            self._ingest(rows, counts)
+            self._ingest(rows, kept)
+        self._n_rows += counts
         seg_hop = self.front.step * int(c["hop_len"])
         due = []                                  # (channel, start_s, first row, rows)
         for ch in touched:
@@ -436,20 +471,23 @@ class StreamMonitor:
                 due.append((ch, float(starts[w]), int(jrow[w]), int(lens[w])))
                 w += 1
             self._n_win[ch] = w
-            # rows before the next unreported window's first row are not needed again
+            # rows before the next unreported window's first row are not needed again (kept rows: before ceil(nxt / Q))
             nxt = -(-int(round(w * self.hop_s * c["fs"])) // seg_hop)
+            nxt = -(-nxt // Q)
             have = self._first[ch + 1] - self._first[ch]
             self._stale[ch] = have if self._closed[ch] else min(have, max(int(self._stale[ch]),
                                                                           nxt - int(self._row0[ch])))
         out = [[] for _ in range(self.channels)]
         if not due:
             return out
-        item_row = np.array([self._first[ch] + j - self._row0[ch] for ch, _, j, _ in due], np.int64)
-        item_len = np.array([n for _, _, _, n in due], np.int32)
+        # a window's item: its kept rows (at Q = 1 the window itself); one that holds none keeps its dense first segment
+        krow, item_len = kept_items([j for _, _, j, _ in due], [n for _, _, _, n in due], Q)
+        due = [(ch, s, int(k) * Q if n else j, n) for (ch, s, j, _), k, n in zip(due, krow, item_len)]
+        item_row = np.array([self._first[ch] + k - self._row0[ch] for (ch, _, _, _), k in zip(due, krow)], np.int64)
         item_row[item_len == 0] = 0
         if lib.n_rows and self._q is not None and item_len.any():
             res = lib._identify_items(self._q, self._ids, item_row, item_len, self.top, self.min_overlap,
-                                      max_len=self.per_window)
+                                      max_len=self.per_kept, q_stride=Q)
         else:
             res = [[] for _ in due]
         seg_s = lib.segment_s

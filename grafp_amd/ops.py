@@ -2008,6 +2008,43 @@ def identify_thin(index_rows, track_first_row, q_rows, topk_ids, item_row, item_
     return outs
 
 
+IDENTIFY_MAX_QUERY_STRIDE = 32                                           # identify_stride.hip's largest query stride
+
+
+def identify_stride(index_rows, track_first_row, q_rows, topk_ids, item_row, item_len, query_stride, top=5,
+                    min_overlap=None, max_len=None):
+    """ops.identify for items whose rows are every query_stride-th segment of the recording
+    (grafp_identify_stride_f32): item row s is the recording's segment s * Q (Q = query_stride in [1, 32]), so it sits
+    s * Q library rows after item row 0.  The library is dense; item_len, max_len and min_overlap count kept rows.
+    A hit (s, r) names the track t holding r and the alignment a = r - s * Q; the pairs of (t, a) are the item rows s
+    with a + s * Q inside t, o of them; the candidate is eligible iff o >= 1 and o >= min(need, max(1, rows of t // Q))
+    with need = min_overlap (None: the item's length), and scores the mean dot product over its pairs in ops.identify's
+    arithmetic order.  offset = a - first[t]: where the item's first row sits in the track, in dense segments.
+    Everything else (arguments, ranking, padding, max_len) as for ops.identify, which this equals bit for bit at
+    query_stride = 1; at 2 it equals the first four outputs of ops.identify_tempo at ratio_num = [512]."""
+    Q = int(query_stride)
+    # argument checks first (host values only): they hold on any device
+    if not 1 <= Q <= IDENTIFY_MAX_QUERY_STRIDE:
+        raise ValueError(f"identify_stride: query_stride={Q} not in [1, {IDENTIFY_MAX_QUERY_STRIDE}]")
+    if int(index_rows.shape[0]) + (IDENTIFY_MAX_LEN - 1) * Q >= 1 << 32:
+        raise ValueError(f"identify_stride: {int(index_rows.shape[0])} rows at query_stride={Q} reach past the 2^32 "
+                         "alignments a key holds")
+    n_items, k, top, max_len, min_overlap = _identify_args("identify_stride", index_rows.shape[0], track_first_row,
+                                                           q_rows, topk_ids, item_row, item_len, top, min_overlap, max_len)
+    _require_gpu(index_rows, q_rows, topk_ids, item_row, item_len)
+    index_rows, q_rows = _f32c(index_rows), _f32c(q_rows)
+    first, topk_ids, item_row, item_len, outs = _identify_tensors(index_rows.device, track_first_row, topk_ids,
+                                                                  item_row, item_len, top)
+    if n_items == 0:
+        return outs
+    with _timed("identify_stride", (n_items, max_len, k, Q)):
+        check(lib.grafp_identify_stride_f32(_p(index_rows), index_rows.shape[0], _p(first), first.numel() - 1, Q,
+                                            _p(q_rows), q_rows.shape[0], _p(topk_ids), k, _p(item_row), _p(item_len),
+                                            n_items, max_len, top, min_overlap, *(_p(o) for o in outs), _stream()),
+              "identify_stride")
+    return outs
+
+
 IDENTIFY_TEMPO_MAX_RATIOS = 64                                           # identify_tempo.hip's ratios per call
 IDENTIFY_TEMPO_MIN, IDENTIFY_TEMPO_MAX, IDENTIFY_TEMPO_DEN = 128, 512, 256   # a ratio is num / 256
 

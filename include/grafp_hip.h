@@ -678,6 +678,26 @@ int grafp_identify_thin_f32(const float *index_rows, int64_t n, const int64_t *t
                             int min_overlap, int32_t *out_track, int32_t *out_offset, float *out_score,
                             int32_t *out_votes, grafp_stream_t stream);
 
+/* ---- identification from every Q-th segment of the recording (grafp_amd/library.py; identify_stride.hip) ----------
+ * grafp_identify_stride_f32 -- grafp_identify_f32 for items whose rows are every query_stride-th segment of the
+ *   recording, Q = query_stride in [1, 32]: item row s is the recording's segment s * Q, so it sits s * Q library rows
+ *   after item row 0.  The library is dense.
+ *   A hit (s, r), 0 <= r < n, names the track t holding r and the alignment a = r - s * Q (the library row on which item
+ *   row 0 sits); a candidate is a unique (t, a), its votes the hits that map to it.  Its pairs are the s < ql with
+ *   a + s * Q inside t, o of them, a contiguous range of s; it is eligible iff o >= 1 and
+ *   o >= min(need, max(1, L_t / Q)), need = min_overlap in pairs (<= 0: ql), L_t the rows of t, integer division, and
+ *   scores (sum over the pairs, s ascending, <q[s], row[a + s * Q]>) / o in the arithmetic order of grafp_identify_f32.
+ *   No row outside t is read.  The per-track best, the order, the four outputs and their padding as there; out_offset =
+ *   a - track_first_row[t].  This is grafp_identify_tempo_f32's rule at the one ratio 256 * Q: with query_stride 1 every
+ *   output is bit for bit grafp_identify_f32's, with 2 the first four of grafp_identify_tempo_f32 at ratio_num = {512}.
+ *   One launch, no workspace, no host synchronisation.
+ *   Limits: those of grafp_identify_f32, and n + 255 * query_stride < 2^32. */
+int grafp_identify_stride_f32(const float *index_rows, int64_t n, const int64_t *track_first_row, int n_tracks,
+                              int query_stride, const float *q_rows, int64_t n_qrows, const int64_t *topk_ids, int k,
+                              const int64_t *item_row, const int *item_len, int n_items, int max_len, int top,
+                              int min_overlap, int32_t *out_track, int32_t *out_offset, float *out_score,
+                              int32_t *out_votes, grafp_stream_t stream);
+
 /* ---- identification of recordings that play fast or slow (grafp_amd/library.py; identify_tempo.hip) ---------------
  * grafp_identify_tempo_f32 -- grafp_identify_f32 for recordings that do not run at the catalogue's speed.  A ratio is
  *   an integer num in [128, 512] standing for num / 256 track seconds per recording second (> 256: the recording plays

@@ -22,6 +22,10 @@ the same with and without a tempo, and at 4 096 items of 94 rows it would take t
   identify_tempo  ops.identify_tempo of all items over the R ratios 256 - 2 * (R // 2) ... in steps of 2 (plus 266 if it
                   is not among them), next to ops.identify of the same items and hits, calls alternating, and the top-1
                   hit rate of both
+With --query-stride Q only every Q-th row of every item is kept (rows 0, Q, 2 Q, ... of its --qlen: ceil(qlen / Q) rows):
+  search           ops.FlatL2Index.search of the kept query rows, next to the search of all of them
+  identify_stride  ops.identify_stride of the kept items in one launch (top 5), next to ops.identify of the same items
+                   with Q times the rows, and the top-1 hit rate of both
 Kernel times from events (median of --reps); `rocprofv3 --kernel-trace --stats -- python tools/identify_bench.py` gives
 the per-kernel figures.
 """
@@ -105,6 +109,32 @@ def _thin(args, dev, cfg, rows, first, q, item_row, item_len, true_track, true_o
             "mean_votes_top1": round(float(vo[:, 0].float().mean()), 2)}
 
 
+def _stride(args, dev, rows, first, q, item_row, item_len, true_track, true_off):
+    from grafp_amd import ops
+    ql, Q, nq = args.qlen, args.query_stride, args.queries
+    kl = -(-ql // Q)
+    keep = (np.arange(nq)[:, None] * ql + np.arange(kl)[None] * Q).reshape(-1)
+    qk = q[torch.from_numpy(keep).to(dev)].contiguous()
+    krow = torch.arange(nq, device=dev, dtype=torch.int64) * kl
+    klen = torch.full((nq,), kl, device=dev, dtype=torch.int32)
+    index = ops.FlatL2Index(device=dev)
+    index.add(rows)
+    t_search_dense = _events(lambda: index.search(q, args.k), max(1, args.reps // 4))
+    t_search = _events(lambda: index.search(qk, args.k), max(1, args.reps // 4))
+    _, ids = index.search(q, args.k)
+    _, kids = index.search(qk, args.k)
+    dense = lambda: ops.identify(rows, first, q, ids, item_row, item_len, top=5, max_len=ql)
+    strided = lambda: ops.identify_stride(rows, first, qk, kids, krow, klen, Q, top=5, max_len=kl)
+    t_dense, t_stride = _events(dense, args.reps), _events(strided, args.reps)
+    want_t, want_o = torch.from_numpy(true_track).to(dev), torch.from_numpy(true_off).to(dev)
+    hit = lambda out: round(float(((out[0][:, 0].long() == want_t) & (out[1][:, 0].long() == want_o)).float().mean()), 4)
+    return {"query_stride": Q, "rows": int(rows.shape[0]), "tracks": int(first.numel() - 1), "queries": nq, "qlen": ql,
+            "kept_qlen": kl, "k": args.k, "search_ms": round(t_search * 1e3, 3),
+            "search_dense_ms": round(t_search_dense * 1e3, 3), "identify_stride_ms": round(t_stride * 1e3, 3),
+            "identify_dense_ms": round(t_dense * 1e3, 3), "stride_over_dense": round(t_stride / t_dense, 3),
+            "identify_stride_top1_correct": hit(strided()), "identify_dense_top1_correct": hit(dense())}
+
+
 def _tempo(args, dev, rows, first, per):
     from grafp_amd import ops
     T, ql, nq, k, num = args.tracks, args.qlen, args.queries, args.k, args.tempo_num
@@ -172,6 +202,7 @@ def main(argv=None):
     ap.add_argument("--pq-m", type=int, default=64)
     ap.add_argument("--nprobe", type=int, default=20)
     ap.add_argument("--row-stride", type=int, default=None, help="flat: keep every D-th row of each track")
+    ap.add_argument("--query-stride", type=int, default=None, help="flat: keep every Q-th row of each item")
     ap.add_argument("--tempo-ratios", type=lambda v: [int(x) for x in v.split(",")], default=None,
                     help="ratio counts to time ops.identify_tempo at, e.g. 1,15,31")
     ap.add_argument("--tempo-num", type=int, default=266, help="tempo: the ratio the items are planted at (num / 256)")
@@ -202,6 +233,9 @@ def main(argv=None):
         return
     if args.row_stride is not None:
         print(json.dumps(_thin(args, dev, cfg, rows, first, q, item_row, item_len, t, a - t * per)))
+        return
+    if args.query_stride is not None:
+        print(json.dumps(_stride(args, dev, rows, first, q, item_row, item_len, t, a - t * per)))
         return
     index = ops.FlatL2Index(device=dev)
     index.add(rows)

@@ -4,10 +4,13 @@ channel's last window_s seconds as a waveform, run FingerprintLibrary.segments o
 identify of every channel's newest window).
 
     python tools/stream_bench.py [--channels 64 512] [--pushes 10] [--warm 4] [--tracks 64] [--track-s 30]
+                                 [--query-stride 1 2 4] [--monitor-only]
 
 The monitor embeds only the segments that are new (about 10.4 per channel and second at the default settings); the
 per-channel path embeds the 21 segments of the newest window again every second.  One JSON line per channel count, then
-a table."""
+a table.  --query-stride Q ... times the monitor once per stride (StreamMonitor(query_stride=Q)
+embeds every Q-th segment of a channel only; 1 is the baseline of the same run; DESIGN.md section 12.31);
+--monitor-only leaves the per-channel path out."""
 import argparse
 import json
 import os
@@ -52,12 +55,12 @@ def _median(rows, key):
     return statistics.median(r.get(key, 0.0) for r in rows)
 
 
-def bench_monitor(lib, audio, chunk, warm, phases):
+def bench_monitor(lib, audio, chunk, warm, phases, query_stride=1):
     C, total = audio.shape
     plain, split, launches, windows = [], [], [], 0
     for instrumented in (False, True):
         phases.enabled = instrumented
-        mon = StreamMonitor(lib, C, max_chunk_s=chunk / lib.settings["fs"])
+        mon = StreamMonitor(lib, C, max_chunk_s=chunk / lib.settings["fs"], query_stride=query_stride)
         mon.front.push = phases.wrap("front_end", mon.front.push)
         for s in range(total // chunk):
             chunks = list(audio[:, s * chunk:(s + 1) * chunk])
@@ -128,6 +131,8 @@ def main():
     ap.add_argument("--tracks", type=int, default=64)
     ap.add_argument("--track-s", type=float, default=30.0)
     ap.add_argument("--chunk-s", type=float, default=1.0)
+    ap.add_argument("--query-stride", type=int, nargs="+", default=[1], help="strides to time the monitor at")
+    ap.add_argument("--monitor-only", action="store_true", help="leave the per-channel path out")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     cfg = load_config()
@@ -144,8 +149,10 @@ def main():
     rows = []
     for C in args.channels:
         audio = 0.1 * torch.randn((C, (args.warm + args.pushes) * chunk), generator=g, device=dev)
-        for path, fn in (("monitor", bench_monitor), ("per_channel", bench_per_channel)):
-            res = dict(fn(lib, audio, chunk, args.warm, phases), channels=C, path=path, library_rows=lib.n_rows)
+        runs = [("monitor" if Q == 1 else f"monitor Q={Q}", bench_monitor, {"query_stride": Q})
+                for Q in args.query_stride]
+        for path, fn, kw in runs + ([] if args.monitor_only else [("per_channel", bench_per_channel, {})]):
+            res = dict(fn(lib, audio, chunk, args.warm, phases, **kw), channels=C, path=path, library_rows=lib.n_rows)
             rows.append(res)
             print(json.dumps(res), flush=True)
     print(f"{'C':>5} {'path':<12} {'push ms':>9} {'front end':>10} {'embed':>8} {'search':>8} {'identify':>9} {'other':>7} "
