@@ -109,6 +109,8 @@ SIGNATURES = {
     "grafp_f32_to_bf16": (_I, [_P, _L, _P, _P]),
     "grafp_knn_search_pre_workspace": (_Z, [_L, _I, _I, _I]),
     "grafp_knn_search_l2_pre": (_I, [_P, _P, _P, _L, _P, _I, _I, _I, _L, _P, _P, _P, _Z, _P]),
+    "grafp_row_sqnorm_bf16": (_I, [_P, _L, _I, _P, _P]),
+    "grafp_knn_search_l2_half": (_I, [_P, _P, _L, _P, _I, _I, _I, _L, _P, _P, _P, _Z, _P]),
     "grafp_merge_topk": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "grafp_seq_rerank_f32": (_I, [_P, _L, _P, _L, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
     "grafp_seq_rerank_shard_f32": (_I, [_P, _L, _L, _L, _L, _L, _P, _L, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
@@ -128,6 +130,9 @@ SIGNATURES = {
     "grafp_identify_tempo_f32": (_I, [_P, _L, _P, _I, _P, _L, _P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P,
                                       _P, _P]),
     "grafp_identify_tempo_workspace": (_Z, [_I, _I, _I]),
+    "grafp_identify_half_f32": (_I, [_P, _L, _P, _I, _P, _L, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "grafp_cross_match_half_f32": (_I, [_P, _L, _P, _I, _P, _L, _P, _I, _P, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P,
+                                        _P, _P]),
     "grafp_self_match_workspace": (_Z, [_P, _I, _I, _I]),
     "grafp_self_match_f32": (_I, [_P, _L, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P, _P, _P]),
     "grafp_cross_match_f32": (_I, [_P, _L, _P, _I, _P, _L, _P, _I, _P, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P, _P,

@@ -252,6 +252,30 @@ extern "C" int grafp_identify_pq_f32(const int32_t *list_id, const uint8_t *code
                                      out_offset, out_score, out_votes, (hipStream_t)stream);
 }
 
+// Identification against a library held as bf16 rows (identify_half.hip): grafp_identify_f32's checks here, the kernels
+// there.
+namespace grafp {
+int identify_half_launch(const unsigned short *rows, int64_t n, const int64_t *first, int T, const float *q_rows,
+                         const int64_t *ids, int k, const int64_t *item_row, const int *item_len, int n_items,
+                         int max_len, int top, int min_overlap, int32_t *out_track, int32_t *out_offset,
+                         float *out_score, int32_t *out_votes, hipStream_t stream);
+}  // namespace grafp
+
+extern "C" int grafp_identify_half_f32(const void *index_rows_bf16, int64_t n, const int64_t *track_first_row,
+                                       int n_tracks, const float *q_rows, int64_t n_qrows, const int64_t *topk_ids,
+                                       int k, const int64_t *item_row, const int *item_len, int n_items, int max_len,
+                                       int top, int min_overlap, int32_t *out_track, int32_t *out_offset,
+                                       float *out_score, int32_t *out_votes, grafp_stream_t stream) {
+    GRAFP_REQUIRE(index_rows_bf16 && track_first_row && q_rows && topk_ids && item_row && item_len && out_track &&
+                  out_offset && out_score && out_votes, "identify_half: null pointer");
+    const int st = check_identify("identify_half", n, nullptr, n_tracks, n_qrows, n_items, top,
+                                  (uintptr_t)index_rows_bf16 | (uintptr_t)q_rows, 0);
+    if (st != GRAFP_OK) return st;
+    return grafp::identify_half_launch((const unsigned short *)index_rows_bf16, n, track_first_row, n_tracks, q_rows,
+                                       topk_ids, k, item_row, item_len, n_items, max_len, top, min_overlap, out_track,
+                                       out_offset, out_score, out_votes, (hipStream_t)stream);
+}
+
 // Shared audio inside a track-indexed library (selfmatch.hip): argument checks here, the kernels and the plan there.
 namespace grafp {
 size_t self_match_workspace(const int64_t *src_rows, int n_src, int k, int min_votes);
@@ -326,6 +350,33 @@ extern "C" int grafp_cross_match_pq_f32(const int32_t *list_id, const uint8_t *c
                                         q_rows, src_first_row, n_src, topk_ids, k, top, min_votes, min_overlap, ws,
                                         ws_bytes, out_track, out_delta, out_start, out_len, out_score, out_votes,
                                         (hipStream_t)stream);
+}
+
+// What recordings held outside a library of bf16 rows share with it (crossmatch_half.hip): grafp_cross_match_f32's checks
+// here, the kernels there.
+namespace grafp {
+int cross_match_half_launch(const unsigned short *rows, int64_t n, const int64_t *first, int T, const float *q_rows,
+                            const int64_t *src_first, int n_src, const int64_t *ids, int k, int top, int min_votes,
+                            int min_overlap, void *ws, size_t ws_bytes, int32_t *out_track, int32_t *out_delta,
+                            int32_t *out_start, int32_t *out_len, float *out_score, int32_t *out_votes,
+                            hipStream_t stream);
+}  // namespace grafp
+
+extern "C" int grafp_cross_match_half_f32(const void *index_rows_bf16, int64_t n, const int64_t *track_first_row,
+                                          int n_tracks, const float *q_rows, int64_t n_qrows,
+                                          const int64_t *src_first_row, int n_src, const int64_t *topk_ids, int k,
+                                          int top, int min_votes, int min_overlap, void *ws, size_t ws_bytes,
+                                          int32_t *out_track, int32_t *out_delta, int32_t *out_start, int32_t *out_len,
+                                          float *out_score, int32_t *out_votes, grafp_stream_t stream) {
+    GRAFP_REQUIRE(index_rows_bf16 && track_first_row && q_rows && src_first_row && topk_ids && out_track && out_delta &&
+                  out_start && out_len && out_score && out_votes, "cross_match_half: null pointer");
+    const int st = check_cross_match("cross_match_half", n, nullptr, n_tracks, n_qrows, n_src,
+                                     (uintptr_t)index_rows_bf16 | (uintptr_t)q_rows, 0);
+    if (st != GRAFP_OK) return st;
+    return grafp::cross_match_half_launch((const unsigned short *)index_rows_bf16, n, track_first_row, n_tracks, q_rows,
+                                          src_first_row, n_src, topk_ids, k, top, min_votes, min_overlap, ws, ws_bytes,
+                                          out_track, out_delta, out_start, out_len, out_score, out_votes,
+                                          (hipStream_t)stream);
 }
 
 // What recordings that play faster or slower than the catalogue share with a library (crossmatch_tempo.hip): the checks

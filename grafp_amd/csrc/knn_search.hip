@@ -108,6 +108,30 @@ __device__ __forceinline__ float exact_l2(const float *__restrict__ db, const fl
     return d < 0.0f ? 0.0f : d;
 }
 
+// The same distance of a row held as bf16 (the half form, grafp_knn_search_l2_half): the 256-byte row is requested whole
+// and widened in registers (a bf16 is the upper half of its f32: exact), then the chain above runs on the widened values
+// in the same order -- the bits exact_l2 returns on the f32 array of those values.
+__device__ __forceinline__ float exact_l2(const unsigned short *__restrict__ db, const float *__restrict__ dd,
+                                          int64_t row, const float *sq, float myqq) {
+    typedef unsigned int u32x4_row __attribute__((ext_vector_type(4)));
+    u32x4_row xr[SR_D / 8];
+    const u32x4_row *rp = reinterpret_cast<const u32x4_row *>(db) + row * (SR_D / 8);
+#pragma unroll
+    for (int c8 = 0; c8 < SR_D / 8; ++c8) xr[c8] = rp[c8];
+    const float ddr = dd[row];
+    float ip = 0.0f;
+#pragma unroll
+    for (int c8 = 0; c8 < SR_D / 8; ++c8) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            ip = __builtin_fmaf(__uint_as_float(xr[c8][e] << 16), sq[8 * c8 + 2 * e], ip);
+            ip = __builtin_fmaf(__uint_as_float(xr[c8][e] & 0xffff0000u), sq[8 * c8 + 2 * e + 1], ip);
+        }
+    }
+    const float d = (myqq + ddr) - 2.0f * ip;
+    return d < 0.0f ? 0.0f : d;
+}
+
 // thr[qi] = the k-th smallest of the wave's 64 lane values (+inf when fewer than k lanes hold a finite one)
 __device__ __forceinline__ void store_kth_smallest(float d, int lane, int k, float *out) {
     int i = lane;
@@ -136,6 +160,31 @@ __global__ __launch_bounds__(256) void row_sqnorm_kernel(const float *__restrict
             for (int c = 0; c < d; ++c) s = __builtin_fmaf(row[c], row[c], s);
             out[r0 + tid] = s;
         }
+    }
+}
+
+// The norms of rows held as bf16 (the half form's `add`): the chain above over the widened values of a row, so the bits
+// row_sqnorm_kernel writes for the f32 array of those values, without that array ever existing.  Thread j owns row j and
+// reads its 256 bytes as sixteen 16-byte pieces (two whole 128-byte lines per thread: no byte is fetched twice).
+__global__ __launch_bounds__(256) void row_sqnorm_bf16_kernel(const unsigned short *__restrict__ m, int64_t n,
+                                                              float *__restrict__ out) {
+    typedef unsigned int u32x4_row __attribute__((ext_vector_type(4)));
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256) {
+        const u32x4_row *rp = reinterpret_cast<const u32x4_row *>(m) + r * (SR_D / 8);
+        u32x4_row xr[SR_D / 8];
+#pragma unroll
+        for (int c8 = 0; c8 < SR_D / 8; ++c8) xr[c8] = rp[c8];
+        float s = 0.0f;
+#pragma unroll
+        for (int c8 = 0; c8 < SR_D / 8; ++c8) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float lo = __uint_as_float(xr[c8][e] << 16), hi = __uint_as_float(xr[c8][e] & 0xffff0000u);
+                s = __builtin_fmaf(lo, lo, s);
+                s = __builtin_fmaf(hi, hi, s);
+            }
+        }
+        out[r] = s;
     }
 }
 
@@ -392,6 +441,11 @@ __global__ __launch_bounds__(256) void search_select_kernel(const float *__restr
 //   * bound pre-pass: group minima of d~ + SLACK (qq + dd) >= group minima of d  -> a valid bound, as before;
 //   * scan: a row is kept iff d~ - SLACK (qq + dd) <= bound, i.e. every row with d <= bound is kept.
 // Rearranged, the scan test per element is <q^,x^> >= A_q + H_row: one add and one compare.
+// The half form (grafp_knn_search_l2_half) hands the scan a database that IS bf16: x^ = x, the database operand's rounding
+// error is zero, and d is the distance to the row the library holds (dd the norm of that row).  The derivation never uses a
+// lower bound on an error: with x^ = x only the query side remains, |<q^,x> - <q,x>| <= u |q| |x| < (2u + u^2) |q| |x|, so
+// |d~ - d| <= SB_SLACK (qq + dd) holds with room to spare and both tests stay conservative.  The bound is merely looser
+// than needed (about twice): a few more candidates reach the select kernel, none is lost.
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));   // native vector: stays in registers (uint4 went to scratch)
 constexpr int SB_TR = 64;            // rows per ring stage
@@ -796,6 +850,8 @@ __global__ __launch_bounds__(256, NQS >= 2 ? SB_WGS_NQS2 : 3) void search_scan_b
 // Each phase has two methods, picked from the size it sees (c <= SF_CAP, nneed <= SF_NEED): see the two comments below.
 // TIGHTEN: only phase A, over the candidates the first part of a two-part scan left: thr[qi] = min(thr[qi], the k-th
 // smallest upper bound) -- the bound the second part then scans with (at least k rows of the first part are that close).
+// The body is written once, in search_select_exact.inc, and stands in two kernels: over the f32 database and over the
+// half form's bf16 rows (db's element type is all that differs: exact_l2 has a form for each).
 template <bool TIGHTEN>
 __global__ __launch_bounds__(256, 4) void search_select_exact_kernel(const float *__restrict__ db,
                                                                   const float *__restrict__ dd, int64_t n,
@@ -807,234 +863,25 @@ __global__ __launch_bounds__(256, 4) void search_select_exact_kernel(const float
                                                                   const float2 *__restrict__ cand_e,
                                                                   float *__restrict__ out_d,
                                                                   int64_t *__restrict__ out_i) {
-    __shared__ float pend_d[4][WT_PEND];
-    __shared__ int pend_i[4][WT_PEND];
-    __shared__ float wtop_d[4][32];
-    __shared__ int wtop_i[4][32];
-    __shared__ float sq[SR_D];
-    __shared__ float s_thr2;
-    __shared__ int need_rows[SR_CAP];                      // every listed candidate fits: no overflow case
-    __shared__ int s_nneed;
-    const int qi = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    if (tid < SR_D) sq[tid] = q[(size_t)qi * SR_D + tid];
-    __shared__ int s_off[SR_NSUB + 1];
-    const float myqq = qq[qi];
-    if (wave == 0) {                                       // sub-list fills -> offsets of a flat candidate index
-        const int cs = lane < SR_NSUB ? cnt[qi * SR_NSUB + lane] : 0;      // (one load per lane, a 16-lane prefix sum)
-        const bool over = cs > SR_SUBCAP;
-        const int v = over ? SR_SUBCAP : cs;
-        int inc = v;
-#pragma unroll
-        for (int j = 1; j < SR_NSUB; j <<= 1) {
-            const int o = __shfl_up(inc, j);
-            if (lane >= j) inc += o;
-        }
-        const bool any_over = __ballot(over) != 0;
-        if (lane < SR_NSUB) s_off[lane] = inc - v;
-        if (lane == SR_NSUB - 1) s_off[SR_NSUB] = any_over ? -1 : inc;
-    }
-    __syncthreads();
-    const int c = s_off[SR_NSUB];
-    const bool listed = c >= 0;                            // else: a sub-list overflowed -> exact rescan of every row
-    auto slot_of = [&](int e) {                            // flat candidate index -> slot in the query's list
-        int s2 = 0;
-#pragma unroll
-        for (int b2 = SR_NSUB / 2; b2 > 0; b2 >>= 1) s2 += (e >= s_off[s2 + b2]) ? b2 : 0;
-        return s2 * SR_SUBCAP + (e - s_off[s2]);
-    };
-    float thr2 = thr[qi];
-    const float kminus = 1.0f - SB_SLACK, kplus = 1.0f + SB_SLACK;
-    const float qhi = myqq * kplus, qlo = myqq * kminus, dspan = kplus - kminus;     // (kplus - kminus is exact)
-    // ---- the pieces both selection methods are built from (one copy each) ----
-    auto cand = [&](int e, int &row, float &ev, float &ddv) {    // flat index -> the scan's record (row, E, norm);
-        const size_t sl = (size_t)qi * SR_CAP + slot_of(e < c ? e : c - 1);    // past the end: the last candidate,
-        row = cand_i[sl];                                        // loaded instead of branched around
-        const float2 ed = cand_e[sl];
-        ev = ed.x;
-        ddv = ed.y;                                              // the row's norm rides with the candidate: no gather
-    };
-    auto hi_of = [&](float ev, float ddv) {
-        const float hi = __builtin_fmaf(dspan, ddv, __builtin_fmaf(-2.0f, ev, qhi));
-        return hi < 0.0f ? 0.0f : hi;
-    };
-    auto keep = [&](bool valid, float ev, int row) {             // compaction: the rows with lo <= bound (no dd[row] needed)
-        if (valid && __builtin_fmaf(-2.0f, ev, qlo) <= thr2) need_rows[atomicAdd(&s_nneed, 1)] = row;
-    };
-    WaveTop top;
-    float td;
-    int ti;
-    // Phase A, the k-th smallest upper bound (or a bound on it), by one of two methods chosen from the list's size; each
-    // ends with the compaction of the rows phase B has to look at.
-    //   c <= SF_CAP (the usual case: a few hundred candidates): no sorting networks at all (a 64-lane bitonic sort is
-    //   ~1 700 cycles, and the fold + three-sort merge of the other method ran twice per query: 16 of the kernel's 29 us
-    //   at 41 queries, tools' stop-point timing, round 4).  The candidates (row, E, hi) stay in registers (up to eight
-    //   per thread); the bound is read from a 256-bin histogram of hi between its minimum and maximum -- the upper edge
-    //   (plus one bin against the rounding of the bin index) of the bin the k-th smallest falls into: >= the k-th
-    //   smallest hi, so still a valid bound, a bin or two looser.
-    //   Otherwise: WaveTop + merge, the exact k-th smallest hi.
-    constexpr int SF_CAP = 2048, SF_NEED = 512, SF_PER = SF_CAP / 256;
-    __shared__ int f_row[SF_NEED];
-    __shared__ float f_hi[SF_NEED];
-    __shared__ int f_hist[256];
-    __shared__ float f_red[2][4];
-    if (tid == 0) s_nneed = 0;                             // (both methods pass a barrier before they compact)
-    if (listed && c <= SF_CAP) {
-        int row[SF_PER];
-        float ev[SF_PER], ddv[SF_PER], hi[SF_PER];
-#pragma unroll
-        for (int u = 0; u < SF_PER; ++u) {                 // every load of a kind in flight at once; the rounds past the
-            row[u] = 0;                                    // end of the list (u * 256 >= c: uniform) load nothing
-            ev[u] = 0.0f;
-            ddv[u] = 0.0f;
-            if (u * 256 < c) cand(u * 256 + tid, row[u], ev[u], ddv[u]);
-        }
-        float mn = INFINITY, mx = -INFINITY;
-#pragma unroll
-        for (int u = 0; u < SF_PER; ++u) {
-            hi[u] = hi_of(ev[u], ddv[u]);
-            if (u * 256 + tid < c) {
-                mn = fminf(mn, hi[u]);
-                mx = fmaxf(mx, hi[u]);
-            }
-        }
-        f_hist[tid] = 0;
-#pragma unroll
-        for (int j = 1; j < 64; j <<= 1) {
-            mn = fminf(mn, __shfl_xor(mn, j));
-            mx = fmaxf(mx, __shfl_xor(mx, j));
-        }
-        if (lane == 0) {
-            f_red[0][wave] = mn;
-            f_red[1][wave] = mx;
-        }
-        __syncthreads();
-        const float lo_h = fminf(fminf(f_red[0][0], f_red[0][1]), fminf(f_red[0][2], f_red[0][3]));
-        const float hi_h = fmaxf(fmaxf(f_red[1][0], f_red[1][1]), fmaxf(f_red[1][2], f_red[1][3]));
-        const float w = (hi_h - lo_h) * (1.0f / 256.0f);
-        const float inv = (w > 0.0f && w < INFINITY) ? 1.0f / w : 0.0f;
-#pragma unroll
-        for (int u = 0; u < SF_PER; ++u) {
-            if (u * 256 + tid < c) {
-                int b = (int)((hi[u] - lo_h) * inv);
-                b = b < 0 ? 0 : (b > 255 ? 255 : b);
-                atomicAdd(&f_hist[b], 1);
-            }
-        }
-        __syncthreads();
-        if (wave == 0) {                                   // bins 4 lane .. 4 lane + 3: inclusive scan over the lanes
-            const int h0 = f_hist[4 * lane], h1 = f_hist[4 * lane + 1], h2 = f_hist[4 * lane + 2], h3 = f_hist[4 * lane + 3];
-            const int mine = h0 + h1 + h2 + h3;
-            int cum = mine;
-#pragma unroll
-            for (int j = 1; j < 64; j <<= 1) {
-                const int o = __shfl_up(cum, j);
-                if (lane >= j) cum += o;
-            }
-            const int before = cum - mine;                 // candidates in the bins of the lanes below
-            if (c < k) {
-                if (lane == 0) s_thr2 = INFINITY;          // fewer than k candidates exist
-            } else if (before < k && cum >= k) {           // exactly one lane
-                int b = 4 * lane, run = before + h0;
-                if (run < k) { ++b; run += h1; }
-                if (run < k) { ++b; run += h2; }
-                if (run < k) { ++b; }
-                s_thr2 = fminf(hi_h, __builtin_fmaf((float)(b + 2), w, lo_h));
-            }
-        }
-        __syncthreads();
-        thr2 = fminf(thr2, s_thr2);
-        if (!TIGHTEN) {
-#pragma unroll
-            for (int u = 0; u < SF_PER; ++u) keep(u * 256 + tid < c, ev[u], row[u]);
-        }
-    } else if (listed) {
-        top.init(pend_d[wave], pend_i[wave], INFINITY);
-        // four candidates per thread and round, every load of a kind in flight at once: a list of 3 000 costs three
-        // dependent round trips, not twelve
-        for (int e0 = 0; e0 < c; e0 += 4 * 256) {
-            int row[4];
-            float ev[4], ddv[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) cand(e0 + u * 256 + tid, row[u], ev[u], ddv[u]);
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (e0 + u * 256 < c)                      // uniform: push is a wave-level call
-                    top.push(e0 + u * 256 + tid < c, hi_of(ev[u], ddv[u]), row[u], k, lane);
-        }
-        if (top.pc > 0) top.fold(k, lane);
-        block_merge_tops(top, wtop_d, wtop_i, wave, lane, td, ti);
-        if (wave == 0 && lane == k - 1) s_thr2 = td;      // +inf when fewer than k candidates exist
-        __syncthreads();
-        thr2 = fminf(thr2, s_thr2);
-        if (!TIGHTEN) {
-            for (int e0 = 0; e0 < c; e0 += 4 * 256) {
-                int row[4];
-                float ev[4], ddv[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) cand(e0 + u * 256 + tid, row[u], ev[u], ddv[u]);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) keep(e0 + u * 256 + tid < c, ev[u], row[u]);
-            }
-        }
-    }
-    if (TIGHTEN) {
-        if (tid == 0 && listed) thr[qi] = thr2;
-        return;
-    }
-    __syncthreads();                                       // need_rows and its count stand; the merge buffers are free again
-    const int nneed = listed ? s_nneed : 0;
-    // Phase B, the exact distances (contract (1)-(2)) of the rows still in question -- compacted first and fetched one
-    // per thread side by side: picked out of the candidate rounds where they stand, every round paid a full row-fetch
-    // latency for its two or three scattered lanes -- and the k best of them, again by one of two methods.
-    //   nneed <= SF_NEED (the usual hundred rows): every thread finds the RANK of its row by counting the (distance, id)
-    //   pairs before it -- ranks < k are the answer, written in place.  O(need^2 / 256) compares per thread: 40 at the
-    //   usual hundred rows.
-    //   Otherwise, and for a query whose lists overflowed (every row of the database): WaveTop + merge.
-    if (listed && nneed <= SF_NEED) {                      // (uniform)
-        float dmine[SF_NEED / 256];
-        int rmine[SF_NEED / 256];
-#pragma unroll
-        for (int v = 0; v < SF_NEED / 256; ++v) {
-            const int i = v * 256 + tid;
-            rmine[v] = i < nneed ? need_rows[i] : 0;
-            dmine[v] = (v * 256 < nneed) ? (i < nneed ? exact_l2(db, dd, rmine[v], sq, myqq) : INFINITY) : INFINITY;
-            if (i < nneed) {
-                f_hi[i] = dmine[v];
-                f_row[i] = rmine[v];
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int v = 0; v < SF_NEED / 256; ++v) {
-            const int i = v * 256 + tid;
-            if (v * 256 < nneed) {                         // uniform
-                int rank = 0;
-                for (int j = 0; j < nneed; ++j) rank += lex_lt(f_hi[j], f_row[j], dmine[v], rmine[v]) ? 1 : 0;
-                if (i < nneed && rank < k) {
-                    out_d[(size_t)qi * k + rank] = dmine[v];
-                    out_i[(size_t)qi * k + rank] = id_base + (int64_t)rmine[v];
-                }
-            }
-        }
-        if (tid >= nneed && tid < k) {                     // fewer rows than k (k <= 32 < 256): contract (4)
-            out_d[(size_t)qi * k + tid] = INFINITY;
-            out_i[(size_t)qi * k + tid] = -1;
-        }
-        return;
-    }
-    top.init(pend_d[wave], pend_i[wave], thr2);
-    const int64_t nrows = listed ? nneed : n;
-    for (int64_t i0 = 0; i0 < nrows; i0 += 256) {
-        const bool need = i0 + tid < nrows;
-        const int64_t row = listed ? (need ? need_rows[i0 + tid] : 0) : i0 + tid;
-        top.push(need, need ? exact_l2(db, dd, row, sq, myqq) : INFINITY, (int)row, k, lane);
-    }
-    if (top.pc > 0) top.fold(k, lane);
-    block_merge_tops(top, wtop_d, wtop_i, wave, lane, td, ti);
-    if (wave == 0 && lane < k) {
-        out_d[(size_t)qi * k + lane] = td;
-        out_i[(size_t)qi * k + lane] = ti == SR_EMPTY ? (int64_t)-1 : id_base + (int64_t)ti;
-    }
+#include "search_select_exact.inc"
+}
+
+// The half form's last launch (grafp_knn_search_l2_half): the same body with the bf16 rows the scan streamed as the
+// rescoring source -- they ARE the database; exact_l2 widens them in registers.  A kernel of its own, not a template
+// parameter of the one above: that one keeps its name and, instruction for instruction, its code.
+// (The TIGHTEN step reads no database row: the half entry launches search_select_exact_kernel<true> with no database.)
+__global__ __launch_bounds__(256, 4) void search_select_exact_half_kernel(const unsigned short *__restrict__ db,
+                                                                       const float *__restrict__ dd, int64_t n,
+                                                                       const float *__restrict__ q,
+                                                                       const float *__restrict__ qq, int nq, int k,
+                                                                       int64_t id_base, float *__restrict__ thr,
+                                                                       const int *__restrict__ cnt,
+                                                                       const int *__restrict__ cand_i,
+                                                                       const float2 *__restrict__ cand_e,
+                                                                       float *__restrict__ out_d,
+                                                                       int64_t *__restrict__ out_i) {
+    constexpr bool TIGHTEN = false;
+#include "search_select_exact.inc"
 }
 
 // ---- merge of P partial lists per query: one workgroup per query ------------------------------------------
@@ -1358,22 +1205,20 @@ extern "C" size_t grafp_knn_search_pre_workspace(int64_t n, int nq, int d, int k
     return (n <= 0 || nq <= 0 || d != SR_D || k < 1) ? 0 : pre_layout(nullptr, nq, pre_plan(n, nq), a);
 }
 
-extern "C" int grafp_knn_search_l2_pre(const float *db, const void *db_bf16, const float *db_sqnorm, int64_t n,
-                                       const float *q, int nq, int d, int k, int64_t id_base, float *out_dist,
-                                       int64_t *out_ids, void *ws, size_t ws_bytes, grafp_stream_t stream) {
-    using namespace grafp;
-    int rc = search_check("knn_search_pre", db && db_bf16 && db_sqnorm && q && out_dist && out_ids, db, db_bf16, q, n, nq,
-                          d, k);
-    if (rc != GRAFP_OK) return rc;
+namespace grafp {
+// The launches of the two pre-filter entries (who: the entry, for the messages; the arguments are checked by then).  dbh:
+// the bf16 rows the scans stream.  db: the f32 rows the last launch rescores from, or null for the half form, whose
+// rescoring source is dbh itself.
+static int pre_search(const char *who, const float *db, const unsigned short *dbh, const float *db_sqnorm, int64_t n,
+                      const float *q, int nq, int k, int64_t id_base, float *out_dist, int64_t *out_ids, void *ws,
+                      size_t ws_bytes, hipStream_t s) {
     const PrePlan p = pre_plan(n, nq);
     PreWs a;
-    rc = search_ws_check("knn_search_pre", ws, ws_bytes, pre_layout(nullptr, nq, p, a));
+    const int rc = search_ws_check(who, ws, ws_bytes, pre_layout(nullptr, nq, p, a));
     if (rc != GRAFP_OK) return rc;
     pre_layout(ws, nq, p, a);
-    hipStream_t s = (hipStream_t)stream;
     const size_t lds = (size_t)SB_NS * SB_STAGE;
     const dim3 grid_b(p.b_splits, p.qgroups), grid_a(p.a_splits, p.qgroups), grid(p.splits, p.qgroups);
-    const unsigned short *dbh = (const unsigned short *)db_bf16;
 #define SB_LAUNCH(QW, NQS)                                                                                          \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(search_bound_bf16_kernel<QW, NQS>), grid_b, dim3(256), lds, s, dbh,          \
                        db_sqnorm, p.b_rows, q, nq, p.b_rps, a.gmax, p.ngroups);                                     \
@@ -1396,10 +1241,55 @@ extern "C" int grafp_knn_search_l2_pre(const float *db, const void *db_bf16, con
     else { SB_LAUNCH(4, 2); }
 #undef SB_LAUNCH
     GRAFP_CHECK_LAUNCH("search_bound_bf16_kernel / search_scan_bf16_kernel");
-    hipLaunchKernelGGL(search_select_exact_kernel<false>, dim3(nq), dim3(256), 0, s, db, db_sqnorm, n, q,
-                       (const float *)a.qq, nq, k, id_base, a.thr, (const int *)a.cnt, (const int *)a.cand_i,
-                       (const float2 *)a.cand_e, out_dist, out_ids);
+    if (db)
+        hipLaunchKernelGGL(search_select_exact_kernel<false>, dim3(nq), dim3(256), 0, s, db, db_sqnorm, n, q,
+                           (const float *)a.qq, nq, k, id_base, a.thr, (const int *)a.cnt, (const int *)a.cand_i,
+                           (const float2 *)a.cand_e, out_dist, out_ids);
+    else
+        hipLaunchKernelGGL(search_select_exact_half_kernel, dim3(nq), dim3(256), 0, s, dbh, db_sqnorm, n, q,
+                           (const float *)a.qq, nq, k, id_base, a.thr, (const int *)a.cnt, (const int *)a.cand_i,
+                           (const float2 *)a.cand_e, out_dist, out_ids);
     GRAFP_CHECK_LAUNCH("search_select_exact_kernel");
+    return GRAFP_OK;
+}
+}  // namespace grafp
+
+extern "C" int grafp_knn_search_l2_pre(const float *db, const void *db_bf16, const float *db_sqnorm, int64_t n,
+                                       const float *q, int nq, int d, int k, int64_t id_base, float *out_dist,
+                                       int64_t *out_ids, void *ws, size_t ws_bytes, grafp_stream_t stream) {
+    using namespace grafp;
+    const int rc = search_check("knn_search_pre", db && db_bf16 && db_sqnorm && q && out_dist && out_ids, db, db_bf16, q,
+                                n, nq, d, k);
+    if (rc != GRAFP_OK) return rc;
+    return pre_search("knn_search_pre", db, (const unsigned short *)db_bf16, db_sqnorm, n, q, nq, k, id_base, out_dist,
+                      out_ids, ws, ws_bytes, (hipStream_t)stream);
+}
+
+// The half form: the database IS the bf16 rows (260 bytes a row with the norm).  The pipeline of grafp_knn_search_l2_pre
+// with db_bf16 as the scan operand and the rescoring source; db_sqnorm must be grafp_row_sqnorm_bf16 of those rows.  The
+// results are the bits of grafp_knn_search_l2_pre (and so of oracle/csrc/flat_search.c) on the f32 array of the rows'
+// values.  Workspace: grafp_knn_search_pre_workspace, the same plan.
+extern "C" int grafp_knn_search_l2_half(const void *db_bf16, const float *db_sqnorm, int64_t n, const float *q, int nq,
+                                        int d, int k, int64_t id_base, float *out_dist, int64_t *out_ids, void *ws,
+                                        size_t ws_bytes, grafp_stream_t stream) {
+    using namespace grafp;
+    const int rc = search_check("knn_search_half", db_bf16 && db_sqnorm && q && out_dist && out_ids, db_bf16, nullptr, q,
+                                n, nq, d, k);
+    if (rc != GRAFP_OK) return rc;
+    return pre_search("knn_search_half", nullptr, (const unsigned short *)db_bf16, db_sqnorm, n, q, nq, k, id_base,
+                      out_dist, out_ids, ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" int grafp_row_sqnorm_bf16(const void *m_bf16, int64_t n, int d, float *out, grafp_stream_t stream) {
+    using namespace grafp;
+    GRAFP_REQUIRE(n >= 0 && d == SR_D, "row_sqnorm_bf16: bad n=%lld d=%d (d == 128)", (long long)n, d);
+    if (n == 0) return GRAFP_OK;                           // an empty matrix has no storage: its pointers may be null
+    GRAFP_REQUIRE(m_bf16 && out, "row_sqnorm_bf16: null pointer");
+    GRAFP_REQUIRE(((uintptr_t)m_bf16 & 15) == 0, "row_sqnorm_bf16: rows must be 16-byte aligned");
+    const int64_t nb = (n + 255) / 256;
+    hipLaunchKernelGGL(row_sqnorm_bf16_kernel, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(256), 0,
+                       (hipStream_t)stream, (const unsigned short *)m_bf16, n, out);
+    GRAFP_CHECK_LAUNCH("row_sqnorm_bf16_kernel");
     return GRAFP_OK;
 }
 

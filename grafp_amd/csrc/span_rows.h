@@ -9,6 +9,9 @@
 //   TempoRowSpan<kUnroll>     the same rows, gathered along a sloped alignment (its own call, see there)  identify_tempo.hip
 //   StepRowSpan<kUnroll>      the same rows, the library rows of consecutive pairs Q rows apart (its own loop)  identify_stride.hip
 //   PqSpan<kM, kUnroll>   rows decoded from IVF-PQ codes while scored  identify_pq.hip, crossmatch.hip
+//   Bf16RowSpan<kUnroll>  the half form's resident (n, 128) bf16 rows, widened in registers  identify_half.hip, crossmatch_half.hip
+// Library row r of the half form is U[r] = the f32 value of its bf16 row (the bits shifted up by 16: exact), so
+// Bf16RowSpan returns the bits RowSpan returns on the (n, 128) f32 array U.
 // Library row r of the compact form is
 //   dec[r][j] = centroids[list_id[r]][j] + codebooks[m][codes[r][m]][c],  m = j / dsub, c = j % dsub, dsub = 128 / M
 // (one f32 add per element, never an fma), so PqSpan returns the bits RowSpan returns on the (n, 128) f32 array dec.
@@ -78,6 +81,30 @@ struct StepRowSpan {
             acc = __builtin_fmaf(q.y, r.y, acc);
             acc = __builtin_fmaf(q.z, r.z, acc);
             acc = __builtin_fmaf(q.w, r.w, acc);
+        }
+#pragma unroll
+        for (int s = 16; s > 0; s >>= 1) acc += __shfl_xor(acc, s);      // stays inside the 32-lane half
+        return acc;
+    }
+};
+
+// The rows of a library held as bf16 (the half form): lane l reads the 8 bytes that hold its dims 4l..4l+3 -- a half-wave
+// reads the row's 256 bytes as one access -- and widens them by shifts (a bf16 is the upper half of its f32).  span_sum's
+// order on the widened values, so the bits are RowSpan's on the f32 array of those values.
+template <int kUnroll>
+struct Bf16RowSpan {
+    const uint2 *rh2;                            // the (n, 128) bf16 rows, SEQ_D / 4 uint2 each
+    __device__ __forceinline__ float operator()(const float4 *x, int64_t row, int l, int m) const {
+        const uint2 *y = rh2 + row * (SEQ_D / 4) + l;
+        float acc = 0.0f;
+#pragma unroll kUnroll
+        for (int t = 0; t < m; ++t) {
+            const float4 q = x[(int64_t)t * (SEQ_D / 4)];
+            const uint2 w = y[(int64_t)t * (SEQ_D / 4)];
+            acc = __builtin_fmaf(q.x, __uint_as_float(w.x << 16), acc);
+            acc = __builtin_fmaf(q.y, __uint_as_float(w.x & 0xffff0000u), acc);
+            acc = __builtin_fmaf(q.z, __uint_as_float(w.y << 16), acc);
+            acc = __builtin_fmaf(q.w, __uint_as_float(w.y & 0xffff0000u), acc);
         }
 #pragma unroll
         for (int s = 16; s > 0; s >>= 1) acc += __shfl_xor(acc, s);      // stays inside the 32-lane half

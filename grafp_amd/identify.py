@@ -1,7 +1,7 @@
 """Command line of the track-indexed fingerprint library (grafp_amd/library.py).
 
   python -m grafp_amd.identify build --config CFG --ckp MODEL.pth --source DIR|JSON|FILES... --out LIBDIR [--precision]
-                                       [--index flat|ivfpq --nlist 64 --pq-m 64 --nprobe 20 --train-rows 65536]
+                                       [--index flat|ivfpq|half --nlist 64 --pq-m 64 --nprobe 20 --train-rows 65536]
                                        [--row-stride D] [--shards N [--devices cuda:0,cuda:1]]
   python -m grafp_amd.identify query --ckp MODEL.pth --library LIBDIR FILES... [--top 5] [--window S --hop S]
                                        [--tempo X [--tempo-step G]] [--query-stride Q]
@@ -15,7 +15,9 @@
 
 `build` fingerprints every track of the source (anything DeviceAudioCorpus accepts) into LIBDIR -- with --index ivfpq as
 a compact library of IVF-PQ codes (about 150 bytes per row instead of 772; `query` works on either form, `dedup` needs
-the flat one); `query` prints one JSON
+the flat one), with --index half as a half library of bf16 rows (260 bytes per row, nothing trained, the search exact
+over the rows held; `query`, `match` and `monitor` load whichever form the directory holds, `dedup`, --tempo,
+--query-stride above 1, --row-stride and --shards need the flat one); `query` prints one JSON
 object per query file -- or, with --window, one per timeline span of each file; `dedup` prints one JSON object per pair
 of tracks that share audio, then one per group of duplicates (--json also writes both to a file); `match` takes whole
 recordings that are not in the library and prints one JSON object per (recording, library track) that share audio, with
@@ -63,8 +65,8 @@ def main(argv=None):
     b.add_argument("--out", required=True)
     b.add_argument("--precision", choices=("bf16", "f32"), default="bf16")
     b.add_argument("--max-segments", type=int, default=4096)
-    b.add_argument("--index", choices=("flat", "ivfpq"), default="flat",
-                   help="flat: f32 rows; ivfpq: a compact library of IVF-PQ codes")
+    b.add_argument("--index", choices=("flat", "ivfpq", "half"), default="flat",
+                   help="flat: f32 rows; ivfpq: a compact library of IVF-PQ codes; half: bf16 rows, 260 bytes a row")
     b.add_argument("--nlist", type=int, default=64, help="ivfpq: inverted lists")
     b.add_argument("--pq-m", type=int, default=64, choices=(16, 32, 64, 128), help="ivfpq: code bytes per row")
     b.add_argument("--nprobe", type=int, default=20, help="ivfpq: lists a query row probes")
@@ -151,7 +153,8 @@ def main(argv=None):
         corpus = DeviceAudioCorpus(cfg, source, device)
         if args.shards is not None or devices:
             if args.index != "flat":
-                sys.exit("build --shards needs --index flat: compact shards are not built")
+                sys.exit("build --shards needs --index flat: compact shards are not built" if args.index == "ivfpq" else
+                         "build --shards needs --index flat: shards of the half form are not built")
             lib = ShardedFingerprintLibrary.build(model, corpus, cfg, n_shards=args.shards, devices=devices,
                                                   precision=args.precision, max_segments=args.max_segments,
                                                   row_stride=args.row_stride)
@@ -180,6 +183,9 @@ def main(argv=None):
                  f"(row_stride={lib.row_stride})")
     if args.cmd == "dedup":
         from .library import DUPLICATE_MIN_SCORE
+        if getattr(lib, "is_half", False):
+            sys.exit(f"{args.library}: dedup needs the flat form of a library (f32 rows): this one is of the half form "
+                     "and holds bf16 rows only; build it with --index flat")
         if lib.is_compact:
             sys.exit(f"{args.library}: dedup needs the flat form of a library (f32 rows): this one is compact and holds "
                      "IVF-PQ codes only")

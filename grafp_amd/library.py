@@ -7,12 +7,20 @@ they start: log-mel and segments on the device, one batched embed, one batched s
 (csrc/identify.hip) for all queries.  Unlike eval.py's row-level rerank (ops.seq_rerank), a candidate never reads
 across a track boundary and the result is the best tracks, not the best rows.
 
-A library has two forms.  The flat form above keeps every row as f32 (plus the index's bf16 copy and norms: 772 bytes
+A library has three forms.  The flat form above keeps every row as f32 (plus the index's bf16 copy and norms: 772 bytes
 per row).  The compact form keeps IVF-PQ codes only -- per row M code bytes in row order, the list id, and the
 grafp_amd.ivfpq.IVFPQIndex over them (the codes again in list order, the ids): 2 M + 20 bytes per row, 148 at M = 64 --
 and identifies with ops.identify_pq (csrc/identify_pq.hip), which scores the decoded rows without ever storing them.
 build(index="ivfpq"), compress() and load() make one; identify, identify_windows, timeline and match work on either
 form; rows() and self_matches() need the flat one.
+
+The half form keeps the rows as bf16 and their norms, nothing else: 260 bytes per row, a third of the flat form, with no
+quantiser to train.  build(index="half"), halve(), from_half() and load() make one.  With U the f32 values of its bf16 rows
+(exact), it answers identify, identify_windows, timeline, match and StreamMonitor bit for bit as the flat library over U
+does: the search (ops.HalfL2Index) is exact over the rows held, ops.identify_half (csrc/identify_half.hip) and
+ops.cross_match_half (csrc/crossmatch_half.hip) score them widened in registers.  Against the flat library over the f32
+rows it was rounded from, a score moves by at most 2^-8 max||q|| max||x|| (HALF_SCORE_BOUND).  rows(), tempo=,
+query_stride > 1, thin(), compress(), self_matches() and sharding need the flat form.
 
 A flat library may keep only every D-th row of each track (build(row_stride=D), thin(D)): the catalogue is stored at
 a coarse hop and the query stays dense, so some of its rows land exactly on kept rows whatever the true alignment is
@@ -59,6 +67,13 @@ SETTINGS = ("fs", "n_fft", "win_len", "hop_len", "n_mels", "n_frames", "overlap"
 FORMAT = 1                   # the files of a flat library
 FORMAT_COMPACT = 2           # the files of a compact library
 FORMAT_THIN = 3              # the files of a flat library that keeps every row_stride-th row ("row_stride" in library.json)
+FORMAT_HALF = 5              # the files of a half library (bf16 rows as uint16 bit patterns; 4 is refused, as it always was)
+# What the half form costs against the flat form over the f32 rows X it was rounded from.  bf16 keeps 8 significant bits,
+# so round to nearest even moves a component by at most half an ulp, 2^-8 relative; then ||x^ - x|| <= 2^-8 ||x|| and
+# (Cauchy-Schwarz) an inner product <q, x> moves by at most 2^-8 |q| |x|; a span score, a mean of such products, by at most
+# HALF_SCORE_BOUND * max|q| * max|x|.  That is the worst case (every component at a tie, the error parallel to q); on real
+# rows the errors are independent and the shift is a few 1e-5.
+HALF_SCORE_BOUND = 2.0 ** -8
 # duplicate_groups' default score bar: a match at least this strong is shared audio.  Chosen from
 # tests/test_gpu_selfmatch.py's trained-model case (the briefly trained model of tests/_retrieval_case.py, bf16 library,
 # measured on MI355X): an exact copy scores 1.000, the pieces of a medley at 20 dB SNR 0.985 and 0.956, the strongest of
@@ -247,6 +262,12 @@ class LibraryFront:
         """Whether the library holds IVF-PQ codes and no f32 rows."""
         raise NotImplementedError
 
+    @property
+    def is_half(self):
+        """Whether the library holds bf16 rows and no f32 rows (a FingerprintLibrary made by build(index="half"),
+        halve(), from_half() or load())."""
+        return False
+
     def _search_rows(self, q, k_probe):
         """q (n, 128) f32 -> ids (n, min(k_probe, n_rows)) int64, each row's nearest library rows, on the device."""
         raise NotImplementedError
@@ -290,7 +311,10 @@ class LibraryFront:
             raise NotImplementedError(f"FingerprintLibrary.{what} needs every row of a track: this library keeps every "
                                       f"{self._row_stride}th (row_stride={self._row_stride})")
 
-    def _need_flat(self, what):
+    def _need_flat(self, what, instead="build(index='flat') keeps the f32 rows that it needs"):
+        if self.is_half:
+            raise NotImplementedError(f"FingerprintLibrary.{what} is not built for the half form of a library (bf16 rows "
+                                      f"only): {instead}")
         if self.is_compact:
             raise NotImplementedError(f"FingerprintLibrary.{what} needs the flat form of a library (f32 rows): this one "
                                       "is compact and holds IVF-PQ codes only")
@@ -648,6 +672,7 @@ class FingerprintLibrary(LibraryFront):
         # the rows: chunks of (rows f32,), or in the compact form of (list_id int32, codes uint8), as they were appended
         self._chunks, self._held, self._index = [], None, None
         self._pq, self._encoder = None, None       # compact form: {"centroids", "codebooks", "nprobe"}
+        self._half = False                         # half form: the chunks are (rows bf16,)
         if rows is not None:
             self._append(rows, first, names)
 
@@ -660,6 +685,17 @@ class FingerprintLibrary(LibraryFront):
         lib = cls(model, settings, None, None, precision=precision, device=device)
         lib._set_quantiser(quantiser, nprobe)
         lib._append_codes(list_id, codes, first, names)
+        return lib
+
+    @classmethod
+    def from_half(cls, model, settings, rows_bf16, first, names=None, precision="bf16", device=None):
+        """A half library over rows that are already bf16: rows_bf16 (n, 128) torch.bfloat16, or their bit patterns as
+        uint16 (a numpy array, what save() writes); the track table as for the constructor.  With U the rows' f32 values
+        it answers every call it supports bit for bit as the flat library over U does.  Works on device="cpu" (files and
+        tables only), like from_codes."""
+        lib = cls(model, settings, None, None, precision=precision, device=device)
+        lib._half = True
+        lib._append_half(rows_bf16, first, names)
         return lib
 
     def _set_quantiser(self, quantiser, nprobe):
@@ -676,6 +712,20 @@ class FingerprintLibrary(LibraryFront):
     def is_compact(self):
         return self._pq is not None
 
+    @property
+    def is_half(self):
+        return self._half
+
+    def _need_half(self, what):
+        if not self.is_half:
+            raise ValueError(f"FingerprintLibrary.{what}: this is no half library (bf16 rows); halve() makes one of a "
+                             "flat library")
+
+    def half_rows(self):
+        """The resident (n_rows, 128) bf16 fingerprints of a half library: the tensor its index searches."""
+        self._need_half("half_rows()")
+        return self._stored()[0]
+
     def quantiser(self):
         """{"centroids", "codebooks"} of a compact library (device tensors)."""
         self._need_compact("quantiser()")
@@ -690,12 +740,15 @@ class FingerprintLibrary(LibraryFront):
     def nbytes(self):
         """Device bytes the library holds: its rows (flat) or its row-order codes, list ids and quantiser (compact),
         plus its index, which is made here if the device has one (on a CPU device only the library's own tensors count).
-        Flat: 772 bytes per row.  Compact: 2 M + 20 per row, plus the quantiser and the index's two nlist-sized tables."""
+        Flat: 772 bytes per row.  Compact: 2 M + 20 per row, plus the quantiser and the index's two nlist-sized tables.
+        Half: 260 bytes per row -- the bf16 rows, which the index shares, and its norms."""
         held = list(self._stored()) + ([self._pq["centroids"], self._pq["codebooks"]] if self.is_compact else [])
         if self.device.type == "cuda" and self.n_rows:
             index = self.index
             if self.is_compact:
                 held += index.held_tensors()
+            elif self.is_half:
+                held += list(index._materialise())
             else:
                 index._materialise()
                 held += [index._db, index._sq, index._bf16]
@@ -703,7 +756,7 @@ class FingerprintLibrary(LibraryFront):
         return int(sum(seen.values()))
 
     def _stored(self):
-        """All rows as one tuple of tensors, (rows,) or (list_id, codes): the chunks concatenated on first use and kept
+        """All rows as one tuple of tensors, (rows,) (f32, or bf16 in the half form) or (list_id, codes): the chunks concatenated on first use and kept
         as the one chunk; a library without rows gives its form's empty tensors."""
         if self._held is None:
             if len(self._chunks) > 1:
@@ -715,12 +768,13 @@ class FingerprintLibrary(LibraryFront):
                 self._held = (torch.zeros(0, dtype=torch.int32, device=self.device),
                               torch.zeros((0, M), dtype=torch.uint8, device=self.device))
             else:
-                self._held = (torch.zeros((0, 128), device=self.device),)
+                self._held = (torch.zeros((0, 128), dtype=torch.bfloat16 if self.is_half else torch.float32,
+                                          device=self.device),)
         return self._held
 
     def rows(self):
         """The resident (n_rows, 128) f32 fingerprints (flat form only)."""
-        self._need_flat("rows()")
+        self._need_flat("rows()", "half_rows() gives its bf16 rows, half_rows().float() their exact f32 values")
         return self._stored()[0]
 
     def codes(self):
@@ -732,9 +786,12 @@ class FingerprintLibrary(LibraryFront):
     def index(self):
         """The index over the rows, made on first use: the ops.FlatL2Index over rows() (it shares the rows tensor), or,
         for a compact library, the ivfpq.IVFPQIndex over codes() (from_codes: nothing is re-encoded, the row-order codes
-        are shared)."""
+        are shared), or, for a half library, the ops.HalfL2Index over half_rows() (it shares that tensor)."""
         if self._index is None:
-            if self.is_compact:
+            if self.is_half:
+                self._index = ops.HalfL2Index(d=128, device=self.device)
+                self._index.add(self.half_rows())
+            elif self.is_compact:
                 from .ivfpq import IVFPQIndex
                 list_id, codes = self.codes()
                 self._index = IVFPQIndex.from_codes(self.quantiser(), list_id, codes, self.device, self._pq["nprobe"])
@@ -759,6 +816,16 @@ class FingerprintLibrary(LibraryFront):
         self._need_flat("_append()")
         rows = torch.as_tensor(rows).to(self.device, torch.float32).reshape(-1, 128)
         self._store(rows.shape[0], lambda: (rows.contiguous(),), first, names)
+
+    def _append_half(self, rows_bf16, first, names):
+        self._need_half("_append_half()")
+        if isinstance(rows_bf16, np.ndarray) and rows_bf16.dtype == np.uint16:      # bit patterns, as save() writes them
+            rows_bf16 = torch.from_numpy(np.ascontiguousarray(rows_bf16).view(np.int16)).view(torch.bfloat16)
+        rows = torch.as_tensor(rows_bf16)
+        if rows.dtype != torch.bfloat16 or rows.dim() != 2 or rows.shape[1] != 128:
+            raise ValueError(f"the rows of a half library must be (n, 128) torch.bfloat16 (or their uint16 bit patterns "
+                             f"in a numpy array), not {tuple(rows.shape)} {rows.dtype}")
+        self._store(rows.shape[0], lambda: (rows.detach().to(self.device).contiguous(),), first, names)
 
     def _append_codes(self, list_id, codes, first, names):
         self._need_compact("_append_codes()")
@@ -832,10 +899,20 @@ class FingerprintLibrary(LibraryFront):
         the first model calls, as soon as they hold train_rows rows (on all rows if there are fewer); every later
         model call is encoded and its f32 rows dropped, so the f32 rows of the catalogue never exist at once.
         quantiser={"centroids", "codebooks"}: nothing is trained.
+        index="half": a half library, the bf16 rows and their norms only (260 bytes a row against the flat form's 772).
+        Every model call's rows are rounded to bf16 (round to nearest even) as they come and the f32 rows dropped, so the
+        f32 rows of the catalogue never exist at once; nothing is trained.  The search stays exact over the rows held.
         row_stride=D (flat only): every D-th segment of each track is fingerprinted and kept, selected before the model
         call -- 1 / D of the model work and of the rows; a track of S segments gets ceil(S / D) rows."""
-        if index not in ("flat", "ivfpq"):
-            raise ValueError(f"index must be 'flat' or 'ivfpq', not {index!r}")
+        if index not in ("flat", "ivfpq", "half"):
+            raise ValueError(f"index must be 'flat', 'ivfpq' or 'half', not {index!r}")
+        if index == "half":
+            if int(row_stride) != 1:
+                raise NotImplementedError(f"build(index='half') needs every row of a track: a thinned half library "
+                                          f"(row_stride={row_stride}) is not built; use index='flat' with row_stride")
+            lib = cls(model, cfg, None, None, precision=precision)
+            lib._half = True
+            return lib.add(tracks, names=names, max_segments=max_segments)
         if index == "ivfpq" and int(row_stride) != 1:
             raise NotImplementedError(f"build(index='ivfpq') needs every row of a track: row_stride={row_stride} codes "
                                       "are not implemented")
@@ -852,10 +929,16 @@ class FingerprintLibrary(LibraryFront):
 
     def add(self, tracks, names=None, max_segments=4096):
         """Append tracks (as for build) to the library; a compact library encodes them with its own quantiser, a
-        thinned one keeps every row_stride-th segment of each."""
+        thinned one keeps every row_stride-th segment of each, a half one rounds each model call's rows to bf16."""
         waves, own = _as_waveforms(tracks)
         names = names if names is not None else own
-        if self.is_compact:
+        if self.is_half:
+            counts = []
+            parts = [ops.rows_to_bf16(rows) for rows in self._fingerprint_batches(waves, int(max_segments), counts)
+                     if rows.shape[0]]
+            rows = torch.cat(parts) if parts else self.half_rows()[:0]
+            self._append_half(rows, track_table(counts), names)
+        elif self.is_compact:
             a, codes, counts = self._fingerprint_codes(waves, int(max_segments))
             self._append_codes(a, codes, track_table(counts), names)
         else:
@@ -876,6 +959,18 @@ class FingerprintLibrary(LibraryFront):
         parts = [out._encode(rows[lo:lo + chunk]) for lo in range(0, rows.shape[0], chunk)]
         out._append_codes(torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]), self.first, self.names)
         return out
+
+    def halve(self, chunk=1 << 18):
+        """A new half library with this flat library's tracks: every row rounded to bf16 (round to nearest even,
+        ops.rows_to_bf16, `chunk` rows at a time).  From a flat library that keeps every row; this library is left as it
+        is.  Against this library a score moves by at most HALF_SCORE_BOUND * max||q|| * max||x||."""
+        self._need_flat("halve()", "it is half already")
+        self._need_dense("halve()")
+        rows = self.rows()
+        parts = [ops.rows_to_bf16(rows[lo:lo + chunk]) for lo in range(0, rows.shape[0], chunk)]
+        return FingerprintLibrary.from_half(self.model, self.settings,
+                                            torch.cat(parts) if parts else rows.to(torch.bfloat16), self.first,
+                                            list(self.names), precision=self.precision, device=self.device)
 
     def thin(self, row_stride):
         """A new flat library that keeps rows first[t] + 0, D, 2D, ... of every track of this dense one (D =
@@ -898,12 +993,17 @@ class FingerprintLibrary(LibraryFront):
         A compact library writes library_codes.npy ((n, M) uint8, row order), library_lists.npy ((n) int32),
         library_pq.npz (centroids, codebooks), library_tracks.npy and library.json ("format": 2 and "index": {"type":
         "ivfpq", "nlist", "M", "nprobe"}) -- and no library.mm.  A thinned library writes the flat library's four files
-        with "format": 3 and "row_stride": D in library.json."""
+        with "format": 3 and "row_stride": D in library.json.  A half library writes library_half.npy ((n, 128) uint16,
+        the bf16 bit patterns), library_tracks.npy and library.json ("format": 5) -- and no library.mm."""
         from .fpdb import _write_memmap
         os.makedirs(out_dir, exist_ok=True)
         meta = {"format": FORMAT, "names": self.names, "settings": self.settings, "precision": self.precision,
                 "model_digest": model_digest(self.model), "n_rows": self.n_rows, "n_tracks": self.n_tracks}
-        if self.is_compact:
+        if self.is_half:
+            bits = self.half_rows().cpu().contiguous().view(torch.int16).numpy().view(np.uint16)
+            np.save(os.path.join(out_dir, "library_half.npy"), bits.reshape(-1, 128))
+            meta["format"] = FORMAT_HALF
+        elif self.is_compact:
             list_id, codes = self.codes()
             cent, books = self._pq["centroids"].cpu().numpy(), self._pq["codebooks"].cpu().numpy()
             np.save(os.path.join(out_dir, "library_codes.npy"), codes.cpu().numpy())
@@ -926,9 +1026,9 @@ class FingerprintLibrary(LibraryFront):
         made with, unless force=True."""
         with open(os.path.join(lib_dir, "library.json")) as f:
             meta = json.load(f)
-        if meta.get("format") not in (FORMAT, FORMAT_COMPACT, FORMAT_THIN):
-            raise ValueError(f"{lib_dir}: library format {meta.get('format')} is none of {FORMAT}, {FORMAT_COMPACT} and "
-                             f"{FORMAT_THIN}")
+        if meta.get("format") not in (FORMAT, FORMAT_COMPACT, FORMAT_THIN, FORMAT_HALF):
+            raise ValueError(f"{lib_dir}: library format {meta.get('format')} is none of {FORMAT}, {FORMAT_COMPACT}, "
+                             f"{FORMAT_THIN} and {FORMAT_HALF}")
         stride = meta.get("row_stride", 1 if meta["format"] != FORMAT_THIN else None)
         if meta["format"] == FORMAT_THIN and not (isinstance(stride, int) and 1 <= stride <= ops.IDENTIFY_MAX_STRIDE):
             raise ValueError(f"{lib_dir}: library format {FORMAT_THIN} needs a row_stride in [1, "
@@ -937,8 +1037,13 @@ class FingerprintLibrary(LibraryFront):
             raise ValueError(f"{lib_dir}: the library was fingerprinted with another model (state_dict digest "
                              f"{meta['model_digest'][:12]}...); pass force=True to use it anyway")
         first = np.load(os.path.join(lib_dir, "library_tracks.npy")).astype(np.int64)
-        compact = meta["format"] == FORMAT_COMPACT
-        if compact:
+        compact, half = meta["format"] == FORMAT_COMPACT, meta["format"] == FORMAT_HALF
+        if half:
+            bits = np.load(os.path.join(lib_dir, "library_half.npy"))
+            if bits.dtype != np.uint16 or bits.ndim != 2 or bits.shape[1] != 128:
+                raise ValueError(f"{lib_dir}: library_half.npy must be (n, 128) uint16, not {bits.shape} {bits.dtype}")
+            shape = bits.shape
+        elif compact:
             if meta.get("index", {}).get("type") != "ivfpq":
                 raise ValueError(f"{lib_dir}: a format {FORMAT_COMPACT} library with index {meta.get('index')!r}")
             codes = np.load(os.path.join(lib_dir, "library_codes.npy"))
@@ -950,6 +1055,8 @@ class FingerprintLibrary(LibraryFront):
             raise ValueError(f"{lib_dir}: {shape[0]} rows but the track table covers {int(first[-1])}")
         if device is not None:
             model = model.to(device)
+        if half:
+            return cls.from_half(model, meta["settings"], bits, first, meta["names"], meta["precision"], device)
         if compact:
             with np.load(os.path.join(lib_dir, "library_pq.npz")) as pq:
                 quantiser = {"centroids": torch.from_numpy(pq["centroids"]), "codebooks": torch.from_numpy(pq["codebooks"])}
@@ -989,6 +1096,8 @@ class FingerprintLibrary(LibraryFront):
             return ops.identify_stride(self.rows(), *tail, q_stride, **kw)
         if nums is not None:
             return ops.identify_tempo(self.rows(), *tail, nums, **kw)
+        if self.is_half:
+            return ops.identify_half(self.half_rows(), *tail, **kw)
         if self.is_compact:
             return ops.identify_pq(*self.codes(), self._pq["centroids"], self._pq["codebooks"], *tail, **kw)
         if self._row_stride != 1:
@@ -1004,6 +1113,8 @@ class FingerprintLibrary(LibraryFront):
         first_d = torch.from_numpy(self.first).to(self.device)
         if nums is not None:
             return ops.cross_match_tempo(self.rows(), first_d, qb, src, ids, nums, **kw)
+        if self.is_half:
+            return ops.cross_match_half(self.half_rows(), first_d, qb, src, ids, **kw)
         if self.is_compact:
             return ops.cross_match_pq(*self.codes(), self._pq["centroids"], self._pq["codebooks"], first_d, qb, src, ids,
                                       **kw)

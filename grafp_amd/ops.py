@@ -1836,6 +1836,48 @@ def search_l2(db, db_sqnorm, q, k, id_base=0, max_queries_per_launch=4096, db_bf
     return out_d, out_i
 
 
+def _half_rows(name, rows):
+    """Refuses anything but the half form's rows: a contiguous torch.bfloat16 tensor of shape (n, 128).  (Host values
+    only: holds on any device.)"""
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.bfloat16 or rows.dim() != 2 or rows.shape[1] != 128 \
+            or not rows.is_contiguous():
+        got = f"{rows.dtype} {tuple(rows.shape)}" if isinstance(rows, torch.Tensor) else type(rows).__name__
+        raise ValueError(f"{name}: the half form's rows must be a contiguous torch.bfloat16 tensor of shape (n, 128), "
+                         f"not {got}")
+    return rows
+
+
+def row_sqnorm_half(rows_bf16):
+    """The squared norms of bf16 rows (n, 128): bit for bit row_sqnorm(rows_bf16.float()), without the f32 rows."""
+    rows_bf16 = _half_rows("row_sqnorm_half", rows_bf16)
+    _require_gpu(rows_bf16)
+    out = torch.empty((rows_bf16.shape[0],), dtype=torch.float32, device=rows_bf16.device)
+    check(lib.grafp_row_sqnorm_bf16(_p(rows_bf16), rows_bf16.shape[0], 128, _p(out), _stream()), "row_sqnorm_bf16")
+    return out
+
+
+def search_l2_half(db_bf16, db_sqnorm, q, k, id_base=0, max_queries_per_launch=4096):
+    """search_l2 against a database held as bf16 rows only (grafp_knn_search_l2_half, 260 bytes a row): bit for bit
+    search_l2(U, row_sqnorm(U), q, k, db_bf16=db_bf16) with U = db_bf16.float().  db_sqnorm: row_sqnorm_half(db_bf16).
+    Against the f32 rows db_bf16 was rounded from, an inner product moves by at most 2^-8 |q| |x|."""
+    db_bf16 = _half_rows("search_l2_half", db_bf16)
+    _require_gpu(db_bf16, db_sqnorm, q)
+    q = _f32c(q)
+    n, d = db_bf16.shape
+    nq = q.shape[0]
+    out_d = torch.empty((nq, k), dtype=torch.float32, device=db_bf16.device)
+    out_i = torch.empty((nq, k), dtype=torch.int64, device=db_bf16.device)
+    for s in range(0, nq, max_queries_per_launch):
+        e = min(nq, s + max_queries_per_launch)
+        nbytes = lib.grafp_knn_search_pre_workspace(n, e - s, d, k)
+        ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=db_bf16.device)
+        with _timed("knn_search_half", (n, e - s, k)):
+            check(lib.grafp_knn_search_l2_half(_p(db_bf16), _p(db_sqnorm), n, _p(q[s:e]), e - s, d, k, int(id_base),
+                                               _p(out_d[s:e]), _p(out_i[s:e]), _p(ws), nbytes, _stream()),
+                  "knn_search_l2_half")
+    return out_d, out_i
+
+
 def merge_topk(part_d, part_i):
     """(P,nq,k) partial lists (id < 0 = empty) -> (nq,k) by (distance, id)."""
     _require_gpu(part_d, part_i)
@@ -1971,7 +2013,31 @@ def identify(index_rows, track_first_row, q_rows, topk_ids, item_row, item_len, 
     return outs
 
 
-IDENTIFY_MAX_STRIDE = 32                                                 # identify_thin.hip's largest row stride
+def identify_half(index_rows_bf16, track_first_row, q_rows, topk_ids, item_row, item_len, top=5, min_overlap=None,
+                  max_len=None):
+    """ops.identify against a library held as bf16 rows (grafp_identify_half_f32): index_rows_bf16 (n, 128) contiguous
+    torch.bfloat16, and every output is bit for bit what ops.identify returns on index_rows_bf16.float().  The other
+    arguments, max_len's promise and the results as for ops.identify.  Against the f32 rows the bf16 rows were rounded
+    from, a score moves by at most 2^-8 max||q|| max||x||."""
+    index_rows_bf16 = _half_rows("identify_half", index_rows_bf16)
+    n_items, k, top, max_len, min_overlap = _identify_args("identify_half", index_rows_bf16.shape[0], track_first_row,
+                                                           q_rows, topk_ids, item_row, item_len, top, min_overlap,
+                                                           max_len)
+    _require_gpu(index_rows_bf16, q_rows, topk_ids, item_row, item_len)
+    q_rows = _f32c(q_rows)
+    first, topk_ids, item_row, item_len, outs = _identify_tensors(index_rows_bf16.device, track_first_row, topk_ids,
+                                                                  item_row, item_len, top)
+    if n_items == 0:
+        return outs
+    with _timed("identify_half", (n_items, max_len, k)):
+        check(lib.grafp_identify_half_f32(_p(index_rows_bf16), index_rows_bf16.shape[0], _p(first), first.numel() - 1,
+                                          _p(q_rows), q_rows.shape[0], _p(topk_ids), k, _p(item_row), _p(item_len),
+                                          n_items, max_len, top, min_overlap, *(_p(o) for o in outs), _stream()),
+              "identify_half")
+    return outs
+
+
+IDENTIFY_MAX_STRIDE = 32                                            # identify_thin.hip's largest row stride
 
 
 def identify_thin(index_rows, track_first_row, q_rows, topk_ids, item_row, item_len, row_stride, top=5,
@@ -2277,7 +2343,35 @@ def cross_match(index_rows, track_first_row, q_rows, src_first_row, topk_ids, to
     return outs
 
 
-CROSS_MATCH_TEMPO_MAX_ROWS = 4194303                                     # rows per source: i * 512 + 128 fits an int32
+def cross_match_half(index_rows_bf16, track_first_row, q_rows, src_first_row, topk_ids, top=8, min_votes=4,
+                     min_overlap=1):
+    """ops.cross_match against a library held as bf16 rows (grafp_cross_match_half_f32): index_rows_bf16 (n, 128)
+    contiguous torch.bfloat16, and every output is bit for bit what ops.cross_match returns on index_rows_bf16.float().
+    The other arguments and the results as for ops.cross_match."""
+    index_rows_bf16 = _half_rows("cross_match_half", index_rows_bf16)
+    top, k = int(top), int(topk_ids.shape[1])
+    n = int(index_rows_bf16.shape[0])
+    first_h, src_h, lens = _cross_match_args("cross_match_half", n, track_first_row, q_rows, src_first_row, topk_ids,
+                                             top, min_votes, min_overlap)
+    _require_gpu(index_rows_bf16, q_rows, topk_ids)
+    q_rows = _f32c(q_rows)
+    dev = index_rows_bf16.device
+    n_src = lens.numel()
+    outs = _cross_match_outs(n_src, top, dev)
+    if n_src == 0 or q_rows.shape[0] == 0:
+        return outs
+    first, src = first_h.to(dev), src_h.to(dev)
+    topk_ids = topk_ids.to(torch.int64).contiguous()
+    ws = torch.empty(self_match_workspace_bytes(lens.numpy(), k, min_votes), dtype=torch.uint8, device=dev)
+    with _timed("cross_match_half", (n_src, int(lens.sum()), k)):
+        check(lib.grafp_cross_match_half_f32(_p(index_rows_bf16), n, _p(first), first.numel() - 1, _p(q_rows),
+                                             q_rows.shape[0], _p(src), n_src, _p(topk_ids), k, top, int(min_votes),
+                                             int(min_overlap), _p(ws), ws.numel(), *(_p(o) for o in outs), _stream()),
+              "cross_match_half")
+    return outs
+
+
+CROSS_MATCH_TEMPO_MAX_ROWS = 4194303                                    # rows per source: i * 512 + 128 fits an int32
 
 
 def _tempo_ratio_list(name, ratio_num):
@@ -2530,4 +2624,62 @@ class FlatL2Index:
         else:
             db, sq = self._materialise()
             D, I = search_l2(db, sq, qt.reshape(-1, self.d), k, self.id_base, db_bf16=self._bf16)
+        return (D.cpu().numpy(), I.cpu().numpy()) if as_numpy else (D, I)
+
+
+class HalfL2Index:
+    """FlatL2Index for a database held as bf16 rows only: d, ntotal, add(rows_bf16), search(q, k); 260 bytes a row with
+    the norm, and no rows() in f32.  With U = the rows' f32 values (exact) every search answers bit for bit as a
+    FlatL2Index over U does.  The index shares the rows tensor it is given and copies nothing (several add() calls are
+    concatenated once, at the first search after them)."""
+
+    def __init__(self, d=128, device=None, id_base=0):
+        if not torch.cuda.is_available():
+            raise RuntimeError("HalfL2Index needs a HIP device: there is no CPU fallback")
+        if d != 128:
+            raise ValueError(f"HalfL2Index: d={d} unsupported (fingerprints are 128-d)")
+        self.d = d
+        self.device = torch.device(device if device is not None else "cuda")
+        self.id_base = int(id_base)
+        self._chunks = []
+        self._db = None
+        self._sq = None
+        self.ntotal = 0
+
+    def add(self, rows_bf16):
+        t = _half_rows("HalfL2Index.add", rows_bf16)
+        _require_gpu(t)
+        self._chunks.append(t)
+        self.ntotal += t.shape[0]
+        self._db = None
+
+    def _materialise(self):
+        if self._db is None:
+            self._db = self._chunks[0] if len(self._chunks) == 1 else torch.cat(self._chunks, dim=0)
+            self._chunks = [self._db]
+            self._sq = row_sqnorm_half(self._db)
+        return self._db, self._sq
+
+    def half_rows(self):
+        """The resident (ntotal, 128) bf16 database tensor: the one tensor add() was given, when it was one."""
+        return self._materialise()[0]
+
+    @property
+    def nbytes(self):
+        """Device bytes of the index: 260 a row."""
+        if self.ntotal == 0:
+            return 0
+        db, sq = self._materialise()
+        return db.numel() * db.element_size() + sq.numel() * sq.element_size()
+
+    def search(self, q, k):
+        """numpy in -> numpy out (D float32 (nq,k), I int64 (nq,k)), like faiss; tensors in -> tensors out."""
+        as_numpy = isinstance(q, np.ndarray)
+        qt = torch.as_tensor(np.ascontiguousarray(q) if as_numpy else q).to(self.device, dtype=torch.float32)
+        if self.ntotal == 0:
+            D = torch.full((qt.shape[0], k), float("inf"), device=self.device)
+            I = torch.full((qt.shape[0], k), -1, dtype=torch.int64, device=self.device)
+        else:
+            db, sq = self._materialise()
+            D, I = search_l2_half(db, sq, qt.reshape(-1, self.d), k, self.id_base)
         return (D.cpu().numpy(), I.cpu().numpy()) if as_numpy else (D, I)

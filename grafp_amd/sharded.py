@@ -74,6 +74,9 @@ class ShardedFingerprintLibrary(LibraryFront):
             raise ValueError(f"{len(shards)} shards, not 1 to {ops.MERGE_LISTS_MAX}")
         head = shards[0]
         for sh in shards:
+            if sh.is_half:
+                raise NotImplementedError("a sharded library needs flat shards (f32 rows): shards of the half form "
+                                          "(bf16 rows) are not built; build the shards with index='flat'")
             if sh.is_compact:
                 raise NotImplementedError("a sharded library needs flat shards (f32 rows): compact shards under one "
                                           "shared quantiser are not built")
@@ -98,6 +101,9 @@ class ShardedFingerprintLibrary(LibraryFront):
         """The tracks of a flat library (dense or thinned) cut into n_shards shards by split_tracks' rule; shard s on
         devices[s] (default: all on the library's device); every shard gets its own copy of its rows and `lib` is left as
         it is."""
+        if lib.is_half:
+            raise NotImplementedError("ShardedFingerprintLibrary.split needs the flat form of a library: this one is of "
+                                      "the half form (bf16 rows), which is not sharded yet; split the flat library")
         if lib.is_compact:
             raise NotImplementedError("ShardedFingerprintLibrary.split needs the flat form of a library: this one is "
                                       "compact, and IVF-PQ codes under one shared quantiser are not sharded yet")

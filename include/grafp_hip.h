@@ -526,6 +526,19 @@ int grafp_knn_search_l2_pre(const float *db, const void *db_bf16, const float *d
                             int nq, int d, int k, int64_t id_base, float *out_dist, int64_t *out_ids, void *ws,
                             size_t ws_bytes, grafp_stream_t stream);
 
+/* The half form: the database IS `db_bf16` (n*128 bf16, 16-byte aligned), 260 bytes a row with its norm; no f32 rows
+ * exist.  With U the f32 array of the bf16 rows' values (exact), the results are bit for bit those of
+ * grafp_knn_search_l2_pre on db = U: the scan streams db_bf16 and the exact distances are evaluated from the same rows,
+ * widened in registers.  Against the f32 rows X that db_bf16 was rounded from (round to nearest even) an inner product
+ * moves by at most 2^-8 |q| |x|.
+ *   grafp_row_sqnorm_bf16: the `index.add` step -- db_sqnorm, the bits grafp_row_sqnorm_f32 writes for U (d == 128;
+ *   n = 0 does nothing).
+ *   ws: grafp_knn_search_pre_workspace(n, nq, d, k) bytes, the same plan. */
+int grafp_row_sqnorm_bf16(const void *m_bf16, int64_t n, int d, float *out, grafp_stream_t stream);
+int grafp_knn_search_l2_half(const void *db_bf16, const float *db_sqnorm, int64_t n, const float *q, int nq, int d,
+                             int k, int64_t id_base, float *out_dist, int64_t *out_ids, void *ws, size_t ws_bytes,
+                             grafp_stream_t stream);
+
 /* Merge P partial result lists (e.g. one per database shard/GPU after an all-gather):
  *   part_dist (P,nq,k) f32, part_ids (P,nq,k) int64 (id < 0 = empty) -> out (nq,k), by (dist,id). */
 int grafp_merge_topk(const float *part_dist, const int64_t *part_ids, int P, int nq, int k, float *out_dist,
@@ -741,6 +754,26 @@ int grafp_identify_pq_f32(const int32_t *list_id, const uint8_t *codes, int64_t 
                           const float *q_rows, int64_t n_qrows, const int64_t *topk_ids, int k, const int64_t *item_row,
                           const int *item_len, int n_items, int max_len, int top, int min_overlap, int32_t *out_track,
                           int32_t *out_offset, float *out_score, int32_t *out_votes, grafp_stream_t stream);
+
+/* ---- identification and matching against a library held as bf16 rows (grafp_amd/library.py's half form;
+ *      identify_half.hip, crossmatch_half.hip) --------------------------------------------------------------------
+ * grafp_identify_half_f32 -- grafp_identify_f32 on a library whose rows exist only as bf16: index_rows_bf16 (n, 128)
+ *   bf16, 16-byte aligned.  Library row r is U[r], the f32 value of its bf16 row (exact), and all four outputs are bit
+ *   for bit what grafp_identify_f32 writes for index_rows = U; every other argument and limit as there.
+ * grafp_cross_match_half_f32 -- grafp_cross_match_f32 on the same rows: all six outputs are bit for bit what
+ *   grafp_cross_match_f32 writes for index_rows = U; ws and every other argument and limit as there.
+ *   Against the f32 rows X the bf16 rows were rounded from (round to nearest even) a score moves by at most
+ *   2^-8 max|q| max|x|. */
+int grafp_identify_half_f32(const void *index_rows_bf16, int64_t n, const int64_t *track_first_row, int n_tracks,
+                            const float *q_rows, int64_t n_qrows, const int64_t *topk_ids, int k,
+                            const int64_t *item_row, const int *item_len, int n_items, int max_len, int top,
+                            int min_overlap, int32_t *out_track, int32_t *out_offset, float *out_score,
+                            int32_t *out_votes, grafp_stream_t stream);
+int grafp_cross_match_half_f32(const void *index_rows_bf16, int64_t n, const int64_t *track_first_row, int n_tracks,
+                               const float *q_rows, int64_t n_qrows, const int64_t *src_first_row, int n_src,
+                               const int64_t *topk_ids, int k, int top, int min_votes, int min_overlap, void *ws,
+                               size_t ws_bytes, int32_t *out_track, int32_t *out_delta, int32_t *out_start,
+                               int32_t *out_len, float *out_score, int32_t *out_votes, grafp_stream_t stream);
 
 /* ---- shared audio inside a track-indexed library (grafp_amd/library.py; selfmatch.hip) ---------------------------
  * grafp_self_match_f32 -- for each of n_src source tracks src_tracks[s] (int32, in [0, n_tracks)), the other tracks

@@ -26,6 +26,11 @@ With --query-stride Q only every Q-th row of every item is kept (rows 0, Q, 2 Q,
   search           ops.FlatL2Index.search of the kept query rows, next to the search of all of them
   identify_stride  ops.identify_stride of the kept items in one launch (top 5), next to ops.identify of the same items
                    with Q times the rows, and the top-1 hit rate of both
+With --index half the library is held as bf16 rows (B = ops.rows_to_bf16(rows)) next to the flat library over their f32
+values U, in the same process, calls alternating:
+  search_half    ops.HalfL2Index.search of every query row, next to ops.FlatL2Index.search over U
+  identify_half  ops.identify_half of all items on B, next to ops.identify of the same items and hits on U, their ratio,
+                 whether the two are bit-equal, and the bytes per row of both forms
 Kernel times from events (median of --reps); `rocprofv3 --kernel-trace --stats -- python tools/identify_bench.py` gives
 the per-kernel figures.
 """
@@ -82,6 +87,53 @@ def _ivfpq(args, dev, rows, first, q, item_row, item_len, true_track, true_off):
             "ivfpq_search_ms": round(t_search * 1e3, 3), "identify_pq_ms": round(t_pq * 1e3, 3),
             "identify_decoded_ms": round(t_dec * 1e3, 3), "identify_pq_over_identify": round(t_pq / t_dec, 3),
             "bit_equal_to_identify_on_decoded_rows": bool(same),
+            "identify_top1_correct": round(float(hit.float().mean()), 4)}
+
+
+def _half(args, dev, rows, first, q, item_row, item_len, true_track, true_off):
+    from grafp_amd import ops
+    ql = args.qlen
+    b = ops.rows_to_bf16(rows)
+    u = b.float()
+    half, flat = ops.HalfL2Index(device=dev), ops.FlatL2Index(device=dev)
+    half.add(b)
+    flat.add(u)
+    _, ids = half.search(q, args.k)
+    same_ids = torch.equal(ids, flat.search(q, args.k)[1])
+    run_h = lambda: ops.identify_half(b, first, q, ids, item_row, item_len, top=5, max_len=ql)
+    run_f = lambda: ops.identify(u, first, q, ids, item_row, item_len, top=5, max_len=ql)
+    pairs = {"search": (lambda: flat.search(q, args.k), lambda: half.search(q, args.k), max(1, args.reps // 4)),
+             "identify": (run_f, run_h, args.reps)}
+    times = {}
+    for name, (f_call, h_call, reps) in pairs.items():
+        for _ in range(2):
+            f_call(), h_call()
+        torch.cuda.synchronize()
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        tf, th = [], []
+        for _ in range(reps):                               # alternating, one synchronise per pair
+            e[0].record()
+            f_call()
+            e[1].record()
+            h_call()
+            e[2].record()
+            torch.cuda.synchronize()
+            tf.append(e[0].elapsed_time(e[1]))
+            th.append(e[1].elapsed_time(e[2]))
+        times[name] = (float(np.median(tf)), float(np.median(th)))
+    got, want = run_h(), run_f()
+    same = all(torch.equal(g.view(torch.int32), w.view(torch.int32)) for g, w in zip(got, want))
+    hit = (got[0][:, 0].long() == torch.from_numpy(true_track).to(dev)) & \
+          (got[1][:, 0].long() == torch.from_numpy(true_off).to(dev))
+    n = int(rows.shape[0])
+    db, sq = flat._materialise()
+    flat_bytes = db.numel() * 4 + sq.numel() * 4 + flat._bf16.numel() * 2
+    return {"index": "half", "rows": n, "tracks": int(first.numel() - 1), "queries": args.queries, "qlen": ql,
+            "k": args.k, "search_flat_ms": round(times["search"][0], 3), "search_half_ms": round(times["search"][1], 3),
+            "identify_flat_ms": round(times["identify"][0], 3), "identify_half_ms": round(times["identify"][1], 3),
+            "identify_half_over_identify": round(times["identify"][1] / times["identify"][0], 3),
+            "search_ids_equal": bool(same_ids), "bit_equal_to_identify_on_widened_rows": bool(same),
+            "bytes_per_row_flat": round(flat_bytes / n, 1), "bytes_per_row_half": round(half.nbytes / n, 1),
             "identify_top1_correct": round(float(hit.float().mean()), 4)}
 
 
@@ -197,7 +249,7 @@ def main(argv=None):
     ap.add_argument("--qlen", type=int, default=31)
     ap.add_argument("--k", type=int, default=20)
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--index", choices=("flat", "ivfpq"), default="flat")
+    ap.add_argument("--index", choices=("flat", "ivfpq", "half"), default="flat")
     ap.add_argument("--nlist", type=int, default=64)
     ap.add_argument("--pq-m", type=int, default=64)
     ap.add_argument("--nprobe", type=int, default=20)
@@ -230,6 +282,9 @@ def main(argv=None):
 
     if args.index == "ivfpq":
         print(json.dumps(_ivfpq(args, dev, rows, first, q, item_row, item_len, t, a - t * per)))
+        return
+    if args.index == "half":
+        print(json.dumps(_half(args, dev, rows, first, q, item_row, item_len, t, a - t * per)))
         return
     if args.row_stride is not None:
         print(json.dumps(_thin(args, dev, cfg, rows, first, q, item_row, item_len, t, a - t * per)))
