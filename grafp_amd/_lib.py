@@ -130,6 +130,9 @@ SIGNATURES = {
     "grafp_identify_tempo_f32": (_I, [_P, _L, _P, _I, _P, _L, _P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P,
                                       _P, _P]),
     "grafp_identify_tempo_workspace": (_Z, [_I, _I, _I]),
+    "grafp_identify_tempo_items_f32": (_I, [_P, _L, _P, _I, _P, _L, _P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I,
+                                            _P, _P, _P, _P, _P, _P, _P]),
+    "grafp_identify_tempo_items_workspace": (_Z, [_I, _I]),
     "grafp_identify_half_f32": (_I, [_P, _L, _P, _I, _P, _L, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "grafp_cross_match_half_f32": (_I, [_P, _L, _P, _I, _P, _L, _P, _I, _P, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P,
                                         _P, _P]),

@@ -226,6 +226,41 @@ extern "C" int grafp_identify_tempo_f32(const float *index_rows, int64_t n, cons
                                         out_offset, out_score, out_votes, out_ratio, (hipStream_t)stream);
 }
 
+// identify_tempo with a ratio window per item (identify_tempo_items.hip): the checks shared with grafp_identify_f32 here;
+// the ratio checks, the table's sizes, the 2^32 bound of the alignment key and the two launches there.
+namespace grafp {
+int identify_tempo_items_launch(const float *rows, int64_t n, const int64_t *first, int T, const float *q_rows,
+                                const int64_t *ids, int k, const int64_t *item_row, const int *item_len, int n_items,
+                                int max_len, int top, int min_overlap, const int32_t *ratio_num, int n_ratios,
+                                const int32_t *work, int n_work, const int32_t *item_scan, int max_cnt, void *ws,
+                                int32_t *out_track, int32_t *out_offset, float *out_score, int32_t *out_votes,
+                                int32_t *out_ratio, hipStream_t stream);
+size_t identify_tempo_items_workspace(int n_work, int top);
+}  // namespace grafp
+
+extern "C" size_t grafp_identify_tempo_items_workspace(int n_work, int top) {
+    return grafp::identify_tempo_items_workspace(n_work, top);
+}
+
+extern "C" int grafp_identify_tempo_items_f32(const float *index_rows, int64_t n, const int64_t *track_first_row,
+                                              int n_tracks, const float *q_rows, int64_t n_qrows,
+                                              const int64_t *topk_ids, int k, const int64_t *item_row,
+                                              const int *item_len, int n_items, int max_len, int top, int min_overlap,
+                                              const int32_t *ratio_num, int n_ratios, const int32_t *work, int n_work,
+                                              const int32_t *item_scan, int max_cnt, void *ws, int32_t *out_track,
+                                              int32_t *out_offset, float *out_score, int32_t *out_votes,
+                                              int32_t *out_ratio, grafp_stream_t stream) {
+    GRAFP_REQUIRE(index_rows && track_first_row && q_rows && topk_ids && item_row && item_len && ratio_num &&
+                  out_track && out_offset && out_score && out_votes && out_ratio, "identify_tempo_items: null pointer");
+    const int st = check_identify("identify_tempo_items", n, nullptr, n_tracks, n_qrows, n_items, top,
+                                  (uintptr_t)index_rows | (uintptr_t)q_rows, 0);
+    if (st != GRAFP_OK) return st;
+    return grafp::identify_tempo_items_launch(index_rows, n, track_first_row, n_tracks, q_rows, topk_ids, k, item_row,
+                                              item_len, n_items, max_len, top, min_overlap, ratio_num, n_ratios, work,
+                                              n_work, item_scan, max_cnt, ws, out_track, out_offset, out_score,
+                                              out_votes, out_ratio, (hipStream_t)stream);
+}
+
 // Identification against a library held as IVF-PQ codes (identify_pq.hip): argument checks here, the kernels there.
 namespace grafp {
 int identify_pq_launch(const int32_t *list_id, const unsigned char *codes, int64_t n, const float *centroids, int nlist,

@@ -185,12 +185,15 @@ struct StrideGrid {
 };
 
 // One item by one workgroup of ID_THREADS threads (blockIdx.x = the item); the four outputs are (gridDim.x, top).
+// identify_tempo_items.hip, whose workgroups take (item, ratio) entries from a work table, names the two indices itself:
+// `item` indexes item_row / item_len, `list` is the row of the four (lists, top) outputs that takes the result.
 template <bool kQLds, typename Grid, typename Span>
 __device__ __forceinline__ void identify_item(
     const Grid &grid, const Span &span, int64_t n, const int64_t *__restrict__ first, int T,
     const float *__restrict__ q_rows, const int64_t *__restrict__ ids, int k, const int64_t *__restrict__ item_row,
     const int *__restrict__ item_len, int max_len, int Pmax, int top, int min_overlap, int32_t *__restrict__ out_track,
-    int32_t *__restrict__ out_offset, float *__restrict__ out_score, int32_t *__restrict__ out_votes) {
+    int32_t *__restrict__ out_offset, float *__restrict__ out_score, int32_t *__restrict__ out_votes,
+    const int item = blockIdx.x, const int list = blockIdx.x) {
     extern __shared__ __attribute__((aligned(16))) unsigned char id_smem[];
     __shared__ int s_ncand;
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(id_smem);
@@ -199,7 +202,7 @@ __device__ __forceinline__ void identify_item(
     unsigned short *idx = reinterpret_cast<unsigned short *>(id_smem + (size_t)14 * Pmax);
     float *sq = reinterpret_cast<float *>(id_smem + (size_t)16 * Pmax);
 
-    const int item = blockIdx.x, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     const int64_t r0 = item_row[item];
     int ql = item_len[item] < max_len ? item_len[item] : max_len;
     if (ql < 0) ql = 0;
@@ -312,7 +315,7 @@ __device__ __forceinline__ void identify_item(
     block_sort<ID_THREADS, true>(keys, idx, P, tid);
     if (tid < top) {
         const unsigned long long key = keys[tid];          // top <= 64 <= P
-        const size_t o = (size_t)item * top + tid;
+        const size_t o = (size_t)list * top + tid;
         if (key != SEQ_NONE) {
             const int t = (int)(key & 0xffffffffull);
             const int slot = idx[tid];

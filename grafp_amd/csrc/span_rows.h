@@ -6,7 +6,7 @@
 // score in span_sum's order (seqmatch.h).
 //   RowSpan<kUnroll>      the library's resident (n, 128) f32 rows     identify.hip, selfmatch.hip, crossmatch.hip
 //   StridedRowSpan<kUnroll>   the same rows, the x rows of consecutive pairs x_step float4s apart    identify_thin.hip
-//   TempoRowSpan<kUnroll>     the same rows, gathered along a sloped alignment (its own call, see there)  identify_tempo.hip
+//   TempoRowSpan<kUnroll>     the same rows, gathered along a sloped alignment (its own call, see there)  identify_tempo.hip, identify_tempo_items.hip
 //   StepRowSpan<kUnroll>      the same rows, the library rows of consecutive pairs Q rows apart (its own loop)  identify_stride.hip
 //   PqSpan<kM, kUnroll>   rows decoded from IVF-PQ codes while scored  identify_pq.hip, crossmatch.hip
 //   Bf16RowSpan<kUnroll>  the half form's resident (n, 128) bf16 rows, widened in registers  identify_half.hip, crossmatch_half.hip

@@ -11,7 +11,7 @@
                                        [--min-score S] [--top 8] [--k-probe 20] [--json OUT]
                                        [--tempo X [--tempo-step G]]
   python -m grafp_amd.identify monitor --ckp MODEL.pth LIBDIR FILES... [--chunk-s 1.0] [--window 3 --hop 1] [--top 5]
-                                       [--query-stride Q]
+                                       [--query-stride Q] [--tempo X [--tempo-step G] [--tempo-lock N]]
 
 `build` fingerprints every track of the source (anything DeviceAudioCorpus accepts) into LIBDIR -- with --index ivfpq as
 a compact library of IVF-PQ codes (about 150 bytes per row instead of 772; `query` works on either form, `dedup` needs
@@ -37,7 +37,10 @@ span of each channel ({"channel", "file", "span": ...}).  build --shards N write
 without it); `query`, `match` and `monitor` load a directory that holds shards.json as one (--devices again says where
 the shards go) and answer as the one-card library would; `dedup` across shards is not built.  query --query-stride Q and
 monitor --query-stride Q embed only every Q-th segment of the recordings (1 / Q of the model's work; a flat library that
-keeps every row, no --tempo) and align those (csrc/identify_stride.hip); what is printed keeps its form."""
+keeps every row, no --tempo) and align those (csrc/identify_stride.hip); what is printed keeps its form.  monitor --tempo X
+follows channels that play up to X faster or slower than the catalogue (a flat library that keeps every row, sharded or
+not; every match and timeline span then carries "tempo"); --tempo-lock N searches a channel whose last N windows agreed
+over three ratios instead of the whole grid (csrc/identify_tempo_items.hip) and marks every window "locked" or not."""
 import argparse
 import json
 import sys
@@ -137,6 +140,11 @@ def main(argv=None):
     mo.add_argument("--min-score", type=float, default=None, help="timeline: drop windows whose best match is weaker")
     mo.add_argument("--query-stride", type=int, default=1,
                     help="embed every Q-th segment of a channel only (1 to 32; a flat library that keeps every row)")
+    mo.add_argument("--tempo", type=float, default=None,
+                    help="also follow channels that play up to this much faster or slower, e.g. 0.06 (a flat library)")
+    mo.add_argument("--tempo-step", type=int, default=None, help="spacing of the ratios searched, in 1/256")
+    mo.add_argument("--tempo-lock", type=int, default=0,
+                    help="with --tempo: windows that must agree before a channel is searched over three ratios only")
     mo.add_argument("--force", action="store_true", help="use a library made with another model")
     mo.add_argument("--devices", default=None, help="a sharded library: its shards' devices, comma-separated")
     args = ap.parse_args(argv)
@@ -207,7 +215,8 @@ def main(argv=None):
         waves = lib._load_queries(list(args.files), None)
         chunk = max(1, int(args.chunk_s * lib.settings["fs"]))
         mon = StreamMonitor(lib, len(waves), window_s=args.window, hop_s=args.hop, top=args.top, k_probe=args.k_probe,
-                            max_chunk_s=args.chunk_s, query_stride=args.query_stride)
+                            max_chunk_s=args.chunk_s, query_stride=args.query_stride, tempo=args.tempo,
+                            tempo_step=args.tempo_step, tempo_lock=args.tempo_lock)
 
         def report(per_channel):
             for ch, windows in enumerate(per_channel):

@@ -34,7 +34,9 @@ than the catalogue: the same embed and search, then one ops.identify_tempo launc
 every candidate along the sloped alignment of each speed ratio of tempo_ratios(); timeline() follows such windows along
 their slope.  match(tempo=...) does the same for whole recordings (one ops.cross_match_tempo launch per batch,
 csrc/crossmatch_tempo.hip) and self_matches(tempo=...) for the tracks of the library itself (ops.self_match_tempo,
-csrc/selfmatch_tempo.hip).  A flat library that keeps every row only; speed, not pitch; StreamMonitor knows no tempo.
+csrc/selfmatch_tempo.hip).  A flat library that keeps every row only; speed, not pitch.  StreamMonitor(tempo=...) follows live
+channels the same way and, with tempo_lock, searches a channel whose speed has shown itself over three ratios only
+(ops.identify_tempo_items, csrc/identify_tempo_items.hip: a ratio window per item).
 
 identify(query_stride=Q) and identify_windows(query_stride=Q) are the query side's counterpart of row_stride: only the
 segments 0, Q, 2 Q, ... of a recording are embedded and searched -- the encoder is nearly all of a query's cost -- and
@@ -272,10 +274,13 @@ class LibraryFront:
         """q (n, 128) f32 -> ids (n, min(k_probe, n_rows)) int64, each row's nearest library rows, on the device."""
         raise NotImplementedError
 
-    def _identify_lists(self, q, ids, item_row, item_len, top, min_overlap, max_len, nums=None, q_stride=1):
+    def _identify_lists(self, q, ids, item_row, item_len, top, min_overlap, max_len, nums=None, q_stride=1,
+                        item_ratios=None):
         """The launch of _identify_items -> the op's device tensors (track, offset, score, votes and, with the ratio
         grid nums, ratio), nothing read back.  q_stride: the items' rows are every q_stride-th segment of the
-        recording (min_overlap and max_len then count those rows)."""
+        recording (min_overlap and max_len then count those rows).  item_ratios: None, or with nums the pair of host
+        arrays (lo, cnt) of ops.identify_tempo_items: item i is searched over nums[lo_i : lo_i + cnt_i] only.  (The
+        front passes the keyword only when it is set.)"""
         raise NotImplementedError
 
     def _match_lists(self, qb, src, k_probe, nums, kw):
@@ -431,13 +436,16 @@ class LibraryFront:
         return q, self._search_rows(q, k_probe)
 
     def _identify_items(self, q, ids, item_row, item_len, top, min_overlap, max_len=None, tempo=None, tempo_step=None,
-                        q_stride=1):
+                        q_stride=1, ratio_window=None):
         """One identify launch (the kernel of the library's form) for all items over the rows q and their hits ids ->
         per-item lists of matches.  max_len: an upper bound of the items' lengths (None: the longest).  (StreamMonitor
         calls it with rows it kept from earlier pushes.)  tempo: tempo_ratios' argument; the launch is then
         ops.identify_tempo over the ratio grid of the longest item, and every match names its ratio.  q_stride: the rows
         q are every q_stride-th segment of the recording and the items count those rows; min_overlap stays in dense
-        segments (the op gets max(1, min_overlap // q_stride) pairs) and the offsets in dense segments."""
+        segments (the op gets max(1, min_overlap // q_stride) pairs) and the offsets in dense segments.
+        ratio_window: None, or with tempo a pair of arrays (lo, cnt), one value per item, of indices into the ratio
+        grid derived here: item i is searched over grid[lo_i : lo_i + cnt_i] only (ops.identify_tempo_items; the tempo
+        lock of StreamMonitor, which fixes the grid by giving tempo_step)."""
         n_items = len(item_row)
         longest = int(np.max(item_len, initial=0))
         if n_items == 0 or longest == 0:
@@ -446,8 +454,13 @@ class LibraryFront:
         nums = None if tempo is None else tempo_ratios(tempo, longest, tempo_step)
         if q_stride != 1 and min_overlap is not None:
             min_overlap = max(1, int(min_overlap) // q_stride)
+        kw = {}
+        if ratio_window is not None:
+            if nums is None:
+                raise ValueError("ratio_window needs tempo: it indexes the tempo search's ratio grid")
+            kw["item_ratios"] = (np.asarray(ratio_window[0], np.int64), np.asarray(ratio_window[1], np.int64))
         lists = self._identify_lists(q, ids, np.asarray(item_row, np.int64), np.asarray(item_len, np.int32), top,
-                                     min_overlap, max_len, nums, q_stride)
+                                     min_overlap, max_len, nums, q_stride, **kw)
         tr, off, sc, vo = (t.cpu().numpy() for t in lists[:4])
         ra = lists[4].cpu().numpy() if nums is not None else None
         step, hop, fs = self.step, self.settings["hop_len"], self.settings["fs"]
@@ -495,7 +508,7 @@ class LibraryFront:
         sloped alignment of every ratio; each match then also carries "tempo" (the ratio) and "tempo_num" (ratio *
         256), and offset / offset_s keep their meaning.  Needs a flat library that keeps every row.  Speed only: pitch
         is not searched; match() takes the same tempo for whole recordings and self_matches() for the tracks of the
-        library itself; StreamMonitor, the IVF-PQ and the thinned forms know no tempo.
+        library itself and StreamMonitor for live channels; the IVF-PQ and the thinned forms know no tempo.
         query_stride: Q in [1, 32]; above 1 only the segments 0, Q, 2 Q, ... of every query are embedded and searched
         (1 / Q of the model's work) and one ops.identify_stride launch aligns them (csrc/identify_stride.hip).  The
         matches keep their form and offset / offset_s their meaning; min_overlap stays in dense segments (the kernel
@@ -1086,7 +1099,8 @@ class FingerprintLibrary(LibraryFront):
     def _search_rows(self, q, k_probe):
         return self.index.search(q, min(int(k_probe), self.n_rows))[1]
 
-    def _identify_lists(self, q, ids, item_row, item_len, top, min_overlap, max_len, nums=None, q_stride=1):
+    def _identify_lists(self, q, ids, item_row, item_len, top, min_overlap, max_len, nums=None, q_stride=1,
+                        item_ratios=None):
         """One launch of the op of the library's form.  (ShardedFingerprintLibrary runs and merges one per shard.)"""
         dev = self.device
         tail = (torch.from_numpy(self.first).to(dev), q, ids, torch.from_numpy(item_row).to(dev),
@@ -1094,6 +1108,8 @@ class FingerprintLibrary(LibraryFront):
         kw = dict(top=top, min_overlap=min_overlap, max_len=max_len)
         if q_stride != 1:                                            # (the front refused tempo and the other forms)
             return ops.identify_stride(self.rows(), *tail, q_stride, **kw)
+        if nums is not None and item_ratios is not None:
+            return ops.identify_tempo_items(self.rows(), *tail, nums, *item_ratios, **kw)
         if nums is not None:
             return ops.identify_tempo(self.rows(), *tail, nums, **kw)
         if self.is_half:

@@ -4,7 +4,9 @@ A StreamMonitor listens to `channels` feeds at once (radio stations, venue micro
 each, a window or so behind real time.  Audio arrives through push(): one ragged chunk per channel.  Only the NEW
 samples are turned into log-mel frames and segments -- by the two launches of csrc/stream_frontend.hip, whatever the
 number of channels -- then all new segments go through one model call and one search, and every window that became due
-on any channel through one identify launch.  Nothing a channel already reported is computed again.
+on any channel through one identify launch.  Nothing a channel already reported is computed again.  With tempo= the
+channels may play faster or slower than the catalogue, and with tempo_lock a channel whose speed has shown itself is
+searched over three ratios of the grid only (ops.identify_tempo_items; the rule is stated at StreamMonitor).
 
 The contract: for every channel, after any sequence of pushes and end(), the frames and
 segments produced so far are the first that many of ops.logmel / FingerprintLibrary.segments on the concatenation of
@@ -32,7 +34,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .library import kept_items, n_segments, segment_step, track_table, window_items
+from .library import kept_items, n_segments, segment_step, tempo_ratios, track_table, window_items
 
 
 # ---- readiness rules: pure host functions ------------------------------------------------------------------------------
@@ -248,12 +250,40 @@ class StreamMonitor:
     channel's stream is a multiple of Q.  push() hands only those to the model (1 / Q of its work); push_rows() still
     takes the channel's dense rows and files the kept ones, the others are never read.  The windows are scheduled on
     the dense segment counts as without it, each one's item is library.kept_items of it, and what is reported is
-    identify_windows(query_stride=Q) of the finished stream."""
+    identify_windows(query_stride=Q) of the finished stream.
+
+    tempo, tempo_step (identify()'s arguments; a flat library that keeps every row, query_stride 1): the feeds may play
+    faster or slower than the catalogue.  The ratio grid is fixed here, tempo_nums = tempo_ratios(tempo, per_window,
+    tempo_step), with tempo_step the step actually used, and every window -- the short ones at a stream's end too -- is
+    searched over it: what is reported is identify_windows(tempo=tempo, tempo_step=mon.tempo_step) of the finished
+    stream, each match with its "tempo" and "tempo_num", and timeline() follows the slope.
+
+    tempo_lock = N >= 1 (with tempo): a station's speed is constant for hours, so a channel whose last N windows agreed
+    is searched over three ratios instead of the whole grid.  Per channel, host state: `lock`,
+    None or (track, j) with j an index into tempo_nums, and `run`, the most recent consecutive windows with a match, each
+    as (track, j).  A window of an unlocked channel is searched over the whole grid; one of a channel locked at (t, j)
+    over tempo_nums[max(0, j - 1) : j + 2], and if that finds nothing or another best track than t the channel unlocks,
+    its run is cleared and the SAME window is identified again over the whole grid (that result is reported).  After a
+    window's final result: no match clears run and lock; else its best match (t', j') extends run if run's last element
+    has track t' and an index within 1 of j', otherwise run = [(t', j')]; once len(run) >= N, lock = (t', j') -- a locked
+    channel follows a drift of one grid step per window.  The windows of one channel are identified in order, each under
+    the state its predecessors left: a push in which some channel has d due windows runs d rounds, each one
+    ops.identify_tempo_items launch for that round's windows of all channels (unlocked ones with the whole grid as their
+    window) plus at most one whole-grid launch for the windows that unlocked -- so what is reported depends on the
+    stream, not on how it was cut into pushes.  Every window then also carries "locked": whether its reported result
+    came from the three-ratio search; tempo_stats counts the windows reported from a whole-grid search ("full"), from a
+    three-ratio one ("locked") and those identified twice ("redone", which are among "full").  reset() clears a
+    channel's lock and run."""
 
     def __init__(self, library, channels, window_s=3.0, hop_s=1.0, top=5, k_probe=20, min_overlap=None,
-                 max_chunk_s=1.0, query_stride=1):
+                 max_chunk_s=1.0, query_stride=1, tempo=None, tempo_step=None, tempo_lock=0):
         self.library = library
-        self.query_stride = library._need_stride_form("StreamMonitor", query_stride)
+        library._need_tempo_form("StreamMonitor", tempo)
+        self.query_stride = library._need_stride_form("StreamMonitor", query_stride, tempo)
+        if int(tempo_lock) != tempo_lock or int(tempo_lock) < 0:
+            raise ValueError(f"tempo_lock={tempo_lock} must be a whole number of windows, 0 for no lock")
+        if int(tempo_lock) and tempo is None:
+            raise ValueError(f"tempo_lock={tempo_lock} needs tempo: it locks a channel to a ratio of the tempo search")
         c = library.settings
         _check_settings(c)
         self.channels = int(channels)
@@ -268,6 +298,13 @@ class StreamMonitor:
             raise ValueError(f"a window of {window_s} s is shorter than one segment")
         self.per_kept = -(-self.per_window // self.query_stride)      # the most kept rows a window holds
         library._check_item_len(self.per_kept, self.k_probe)
+        self.tempo, self.tempo_nums, self.tempo_step, self.tempo_lock = tempo, None, None, int(tempo_lock)
+        if tempo is not None:
+            self.tempo_step = max(1, ops.IDENTIFY_TEMPO_DEN // self.per_window) if tempo_step is None else int(tempo_step)
+            self.tempo_nums = tempo_ratios(tempo, self.per_window, self.tempo_step)
+            self.tempo_stats = {"full": 0, "locked": 0, "redone": 0}
+        self._lock = [None] * self.channels       # tempo_lock: (track, index into tempo_nums) or None
+        self._run = [[] for _ in range(self.channels)]
         self.front = StreamFrontEnd(c, self.channels, library.device, max_chunk_s)
         C = self.channels
         self._mode = [None] * C                  # None, "audio" (push) or "rows" (push_rows)
@@ -418,6 +455,7 @@ class StreamMonitor:
         self._mode[ch], self._closed[ch] = None, False
         self._n_rows[ch] = self._samples[ch] = self._n_win[ch] = 0
         self._windows[ch] = []
+        self._lock[ch], self._run[ch] = None, []
         self._stale[ch] = self._first[ch + 1] - self._first[ch]      # (its kept rows go at the next ingest)
         self._row0[ch] = -self._stale[ch]                            # so that the next row kept is row 0
 
@@ -485,14 +523,84 @@ class StreamMonitor:
         due = [(ch, s, int(k) * Q if n else j, n) for (ch, s, j, _), k, n in zip(due, krow, item_len)]
         item_row = np.array([self._first[ch] + k - self._row0[ch] for (ch, _, _, _), k in zip(due, krow)], np.int64)
         item_row[item_len == 0] = 0
-        if lib.n_rows and self._q is not None and item_len.any():
+        locked = None
+        if not (lib.n_rows and self._q is not None and item_len.any()):
+            res = [[] for _ in due]
+            if self.tempo is not None:
+                self.tempo_stats["full"] += len(due)
+            if self.tempo_lock:
+                locked = [False] * len(due)
+                for ch in {d[0] for d in due}:
+                    self._lock[ch], self._run[ch] = None, []
+        elif self.tempo is None:
             res = lib._identify_items(self._q, self._ids, item_row, item_len, self.top, self.min_overlap,
                                       max_len=self.per_kept, q_stride=Q)
+        elif not self.tempo_lock:
+            res = lib._identify_items(self._q, self._ids, item_row, item_len, self.top, self.min_overlap,
+                                      max_len=self.per_kept, tempo=self.tempo, tempo_step=self.tempo_step)
+            self.tempo_stats["full"] += len(due)
         else:
-            res = [[] for _ in due]
+            res, locked = self._identify_locked([d[0] for d in due], item_row, item_len)
         seg_s = lib.segment_s
-        for (ch, s, j, _), m in zip(due, res):
+        for i, ((ch, s, j, _), m) in enumerate(zip(due, res)):
             win = {"start_s": s, "end_s": s + self.window_s, "segment_start_s": j * seg_s, "matches": m, "channel": ch}
+            if locked is not None:
+                win["locked"] = locked[i]
             self._windows[ch].append(win)
             out[ch].append(win)
         return out
+
+    # ---- the tempo lock ----------------------------------------------------------------------------------------------
+    def _identify_locked(self, chans, item_row, item_len):
+        """The due windows (chans[i]: window i's channel; a channel's windows in order) under the lock rule stated at the
+        top of the class -> (per-window matches, per-window whether the reported result came from the locked search).
+        Round r identifies the r-th due window of every channel that has one: one launch with a ratio window per item,
+        then at most one over the whole grid for the windows that unlocked."""
+        G, R, N = self.tempo_nums, len(self.tempo_nums), self.tempo_lock
+        per_channel = {}
+        for i, ch in enumerate(chans):
+            per_channel.setdefault(ch, []).append(i)
+        res, locked = [None] * len(chans), [False] * len(chans)
+
+        def launch(sel, lo, cnt):
+            return self.library._identify_items(self._q, self._ids, item_row[sel], item_len[sel], self.top,
+                                                self.min_overlap, max_len=self.per_kept, tempo=self.tempo,
+                                                tempo_step=self.tempo_step, ratio_window=(lo, cnt))
+        for r in range(max(len(v) for v in per_channel.values())):
+            sel = np.array([v[r] for v in per_channel.values() if len(v) > r], np.int64)
+            lo, cnt = np.zeros(len(sel), np.int64), np.full(len(sel), R, np.int64)
+            for n, i in enumerate(sel):
+                lock = self._lock[chans[i]]
+                if lock is not None:
+                    lo[n] = max(0, lock[1] - 1)
+                    cnt[n] = min(R, lock[1] + 2) - lo[n]
+            redo = []
+            for n, (i, m) in enumerate(zip(sel, launch(sel, lo, cnt))):
+                ch = chans[i]
+                lock = self._lock[ch]
+                if lock is not None and (not m or m[0]["track"] != lock[0]):
+                    self._lock[ch], self._run[ch] = None, []
+                    redo.append(i)
+                else:
+                    res[i], locked[i] = m, lock is not None
+            if redo:
+                redo = np.array(redo, np.int64)
+                for i, m in zip(redo, launch(redo, np.zeros(len(redo), np.int64), np.full(len(redo), R, np.int64))):
+                    res[i] = m
+                self.tempo_stats["redone"] += len(redo)
+            for i in sel:
+                ch, m = chans[i], res[i]
+                self.tempo_stats["locked" if locked[i] else "full"] += 1
+                if not m:
+                    self._lock[ch], self._run[ch] = None, []
+                    continue
+                here = (m[0]["track"], int(np.searchsorted(G, m[0]["tempo_num"])))
+                run = self._run[ch]
+                if run and run[-1][0] == here[0] and abs(run[-1][1] - here[1]) <= 1:
+                    run.append(here)
+                    del run[:-N]
+                else:
+                    run[:] = [here]
+                if len(run) >= N:
+                    self._lock[ch] = here
+        return res, locked

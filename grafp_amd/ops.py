@@ -2151,6 +2151,68 @@ def identify_tempo(index_rows, track_first_row, q_rows, topk_ids, item_row, item
     return outs
 
 
+def tempo_work_table(n_ratios, item_ratio_lo, item_ratio_cnt, name="identify_tempo_items"):
+    """The work table of ops.identify_tempo_items over a grid of n_ratios ratios: item i is searched over the ratios
+    [lo_i, lo_i + cnt_i) -> (table, n_work, max_cnt): table is one int32 host array holding the n_work = sum(cnt)
+    entries (item, ratio index), ordered by item and then by ratio, followed by the exclusive scan of cnt
+    (n_items + 1 values).  Refuses, naming the first such item, a window with cnt < 1, lo < 0 or lo + cnt > n_ratios."""
+    lo = np.asarray(item_ratio_lo, np.int64).reshape(-1)
+    cnt = np.asarray(item_ratio_cnt, np.int64).reshape(-1)
+    if lo.shape != cnt.shape:
+        raise ValueError(f"{name}: {lo.size} item_ratio_lo for {cnt.size} item_ratio_cnt")
+    bad = np.nonzero((cnt < 1) | (lo < 0) | (lo + cnt > int(n_ratios)))[0]
+    if bad.size:
+        i = int(bad[0])
+        raise ValueError(f"{name}: item {i}'s ratio window lo={int(lo[i])} cnt={int(cnt[i])} does not lie inside the "
+                         f"{int(n_ratios)} ratios of the call (1 <= cnt, 0 <= lo, lo + cnt <= {int(n_ratios)})")
+    scan = np.concatenate([[0], np.cumsum(cnt)])
+    n_work = int(scan[-1])
+    item = np.repeat(np.arange(lo.size, dtype=np.int64), cnt)
+    ratio = np.arange(n_work, dtype=np.int64) - scan[item] + lo[item]
+    table = np.concatenate([np.stack([item, ratio], axis=1).reshape(-1), scan]).astype(np.int32)
+    return table, n_work, int(cnt.max(initial=0))
+
+
+def identify_tempo_items(index_rows, track_first_row, q_rows, topk_ids, item_row, item_len, ratio_num, item_ratio_lo,
+                         item_ratio_cnt, top=5, min_overlap=None, max_len=None):
+    """ops.identify_tempo with a ratio window per item (grafp_identify_tempo_items_f32): ratio_num is the call's
+    ascending grid of R <= 64 ratios, and item i is identified over ratio_num[lo_i : lo_i + cnt_i] only, with the host
+    arrays item_ratio_lo, item_ratio_cnt (n_items each; 1 <= cnt, 0 <= lo, lo + cnt <= R; anything else is a ValueError
+    that names the item).  Row i of the five outputs equals, bit for bit, row 0 of ops.identify_tempo called with item i
+    alone and that sub-list of ratios -- the tie rule (the ratio nearer to 1, then the smaller num, then the smaller
+    alignment) applies among the item's own ratios -- and with every cnt = R the outputs are ops.identify_tempo's.
+    One workgroup per item and ratio OF ITS WINDOW (sum(cnt) of them, listed in a small int32 work table that is built
+    here and uploaded), then one per item that merges its lists; no host synchronisation.  Everything else (arguments,
+    outputs, padding, max_len) as for ops.identify_tempo."""
+    name = "identify_tempo_items"
+    n_items, k, top, max_len, min_overlap = _identify_args(name, index_rows.shape[0], track_first_row, q_rows, topk_ids,
+                                                           item_row, item_len, top, min_overlap, max_len)
+    ratios = _tempo_ratio_list(name, ratio_num)
+    if len(np.asarray(item_ratio_cnt).reshape(-1)) != n_items or len(np.asarray(item_ratio_lo).reshape(-1)) != n_items:
+        raise ValueError(f"{name}: item_ratio_lo and item_ratio_cnt must hold one value per item ({n_items})")
+    table, n_work, max_cnt = tempo_work_table(len(ratios), item_ratio_lo, item_ratio_cnt, name)
+    if int(index_rows.shape[0]) + 2 * IDENTIFY_MAX_LEN - 1 >= 1 << 32:
+        raise ValueError(f"{name}: {int(index_rows.shape[0])} rows reach past the 2^32 alignments a key holds")
+    _require_gpu(index_rows, q_rows, topk_ids, item_row, item_len)
+    index_rows, q_rows = _f32c(index_rows), _f32c(q_rows)
+    dev = index_rows.device
+    first, topk_ids, item_row, item_len, outs = _identify_tensors(dev, track_first_row, topk_ids, item_row, item_len,
+                                                                  top, n_outs=5)
+    if n_items == 0:
+        return outs
+    nums = (ctypes.c_int32 * len(ratios))(*ratios)                       # read by the entry before it returns
+    table = torch.from_numpy(table).to(dev)                              # work entries, then the scan
+    work, scan = table[:2 * n_work], table[2 * n_work:]
+    ws = torch.empty(lib.grafp_identify_tempo_items_workspace(n_work, top), dtype=torch.uint8, device=dev)
+    with _timed(name, (n_items, max_len, k, n_work)):
+        check(lib.grafp_identify_tempo_items_f32(_p(index_rows), index_rows.shape[0], _p(first), first.numel() - 1,
+                                                 _p(q_rows), q_rows.shape[0], _p(topk_ids), k, _p(item_row),
+                                                 _p(item_len), n_items, max_len, top, min_overlap,
+                                                 ctypes.cast(nums, ctypes.c_void_p), len(ratios), _p(work), n_work,
+                                                 _p(scan), max_cnt, _p(ws), *(_p(o) for o in outs), _stream()), name)
+    return outs
+
+
 IDENTIFY_PQ_M = (16, 32, 64, 128)                                      # identify_pq.hip's sub-quantiser counts
 
 

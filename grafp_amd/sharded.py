@@ -296,10 +296,12 @@ class ShardedFingerprintLibrary(LibraryFront):
                 outs.append(launch(sh, q.to(sh.device), (ids - int(self.rb[s])).to(sh.device)))
         return self._merge(outs, live, form)
 
-    def _identify_lists(self, q, ids, item_row, item_len, top, min_overlap, max_len, nums=None, q_stride=1):
+    def _identify_lists(self, q, ids, item_row, item_len, top, min_overlap, max_len, nums=None, q_stride=1,
+                        item_ratios=None):
         """FingerprintLibrary._identify_lists on every shard that holds rows."""
+        kw = {} if item_ratios is None else {"item_ratios": item_ratios}
         return self._on_shards(q, ids, lambda sh, q_s, ids_s: sh._identify_lists(
-            q_s, ids_s, item_row, item_len, top, min_overlap, max_len, nums, q_stride), _IDENTIFY_FORM)
+            q_s, ids_s, item_row, item_len, top, min_overlap, max_len, nums, q_stride, **kw), _IDENTIFY_FORM)
 
     def _match_lists(self, qb, src, k_probe, nums, kw):
         """One merged search, then FingerprintLibrary._match_launch on every shard over the same batch of recordings."""

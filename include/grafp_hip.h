@@ -741,6 +741,28 @@ int grafp_identify_tempo_f32(const float *index_rows, int64_t n, const int64_t *
                              grafp_stream_t stream);
 size_t grafp_identify_tempo_workspace(int n_items, int n_ratios, int top);
 
+/* ---- the same with a ratio window per item (grafp_amd/monitor.py's tempo lock; identify_tempo_items.hip) ----------
+ * grafp_identify_tempo_items_f32 -- grafp_identify_tempo_f32 in which item i is identified over the ratios
+ *   ratio_num[lo_i : lo_i + cnt_i] only (1 <= cnt_i, 0 <= lo_i, lo_i + cnt_i <= n_ratios).  Row i of the five outputs
+ *   is, bit for bit, row 0 of grafp_identify_tempo_f32 called with item i alone and that sub-list of ratios, the tie rule
+ *   applied among the item's own ratios; with every cnt_i = n_ratios the outputs are grafp_identify_tempo_f32's.
+ *   The windows travel as a work table: work (DEVICE, 2 * n_work int32, n_work = sum of cnt_i) holds one entry
+ *   (item, ratio index) per item and ratio of its window, ordered by item and then by ratio; item_scan (DEVICE,
+ *   n_items + 1 int32) is the exclusive scan of the cnt_i; max_cnt is the largest cnt_i (it sizes the merge's LDS).
+ *   An entry whose item or ratio index is out of range yields an empty list, an item whose scan or window is out of
+ *   range (a count outside [1, max_cnt]) an empty row: nothing outside the arrays is read.
+ *   ws: grafp_identify_tempo_items_workspace(n_work, top) bytes on the device, 16-byte aligned (16 bytes per table
+ *   entry and rank; 0 for arguments out of range).  Two launches on `stream`, no host synchronisation.
+ *   Limits: those of grafp_identify_tempo_f32; n_items <= n_work <= n_items * max_cnt, 1 <= max_cnt <= n_ratios. */
+int grafp_identify_tempo_items_f32(const float *index_rows, int64_t n, const int64_t *track_first_row, int n_tracks,
+                                   const float *q_rows, int64_t n_qrows, const int64_t *topk_ids, int k,
+                                   const int64_t *item_row, const int *item_len, int n_items, int max_len, int top,
+                                   int min_overlap, const int32_t *ratio_num, int n_ratios, const int32_t *work,
+                                   int n_work, const int32_t *item_scan, int max_cnt, void *ws, int32_t *out_track,
+                                   int32_t *out_offset, float *out_score, int32_t *out_votes, int32_t *out_ratio,
+                                   grafp_stream_t stream);
+size_t grafp_identify_tempo_items_workspace(int n_work, int top);
+
 /* ---- identification against a library held as IVF-PQ codes (grafp_amd/library.py; identify_pq.hip) ---------------
  * grafp_identify_pq_f32 -- grafp_identify_f32 on a library whose rows exist only as codes.  Library row r is
  *   dec[r][j] = centroids[list_id[r]][j] + codebooks[m][codes[r][m]][c], m = j / dsub, c = j % dsub, dsub = 128 / M

@@ -22,6 +22,12 @@ the same with and without a tempo, and at 4 096 items of 94 rows it would take t
   identify_tempo  ops.identify_tempo of all items over the R ratios 256 - 2 * (R // 2) ... in steps of 2 (plus 266 if it
                   is not among them), next to ops.identify of the same items and hits, calls alternating, and the top-1
                   hit rate of both
+With --tempo-items (next to --tempo-ratios' planted items; the ratio counts given are not used) the same items are
+identified over the three ratios num - 4, num, num + 4 in two ways, calls alternating:
+  identify_tempo        ops.identify_tempo with those three ratios
+  identify_tempo_items  ops.identify_tempo_items over the grid num - 12 ... num + 12 in steps of 4 (7 ratios), every item
+                        with the window lo = 2, cnt = 3: the same workgroups' work behind a work table (host time of the
+                        table and its upload included), medians with min and max, and whether the outputs are bit-equal
 With --query-stride Q only every Q-th row of every item is kept (rows 0, Q, 2 Q, ... of its --qlen: ceil(qlen / Q) rows):
   search           ops.FlatL2Index.search of the kept query rows, next to the search of all of them
   identify_stride  ops.identify_stride of the kept items in one launch (top 5), next to ops.identify of the same items
@@ -206,6 +212,34 @@ def _tempo(args, dev, rows, first, per):
     want_t, want_o = torch.from_numpy(t).to(dev), torch.from_numpy(p0).to(dev)
     dense = lambda: ops.identify(rows, first, q, ids, item_row, item_len, top=5, max_len=ql)
     out = {"rows": int(n), "tracks": T, "queries": nq, "qlen": ql, "k": k, "planted_num": num, "by_ratios": []}
+    if args.tempo_items:
+        three, grid = [num - 4, num, num + 4], list(range(num - 12, num + 13, 4))
+        lo, cnt = np.full(nq, 2, np.int64), np.full(nq, 3, np.int64)
+        whole = lambda: ops.identify_tempo(rows, first, q, ids, item_row, item_len, three, top=5, max_len=ql)
+        items = lambda: ops.identify_tempo_items(rows, first, q, ids, item_row, item_len, grid, lo, cnt, top=5,
+                                                 max_len=ql)
+        for _ in range(3):
+            whole(), items()
+        torch.cuda.synchronize()
+        tw, ti = [], []
+        a, b, c = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+        for _ in range(args.reps):                          # alternating, one synchronise per pair
+            a.record()
+            whole()
+            b.record()
+            items()
+            c.record()
+            torch.cuda.synchronize()
+            tw.append(a.elapsed_time(b))
+            ti.append(b.elapsed_time(c))
+        same = all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(whole(), items()))
+        del out["by_ratios"]
+        out.update({"ratios": three, "identify_tempo_ms": round(float(np.median(tw)), 4),
+                    "identify_tempo_ms_min_max": [round(min(tw), 4), round(max(tw), 4)],
+                    "identify_tempo_items_ms": round(float(np.median(ti)), 4),
+                    "identify_tempo_items_ms_min_max": [round(min(ti), 4), round(max(ti), 4)],
+                    "items_over_whole": round(float(np.median(ti) / np.median(tw)), 3), "bit_equal": bool(same)})
+        return out
     for R in args.tempo_ratios:
         nums = sorted(set([256 + 2 * (i - R // 2) for i in range(R)] + ([num] if R > 1 else [])))
         sloped = lambda: ops.identify_tempo(rows, first, q, ids, item_row, item_len, nums, top=5, max_len=ql)
@@ -257,6 +291,8 @@ def main(argv=None):
     ap.add_argument("--query-stride", type=int, default=None, help="flat: keep every Q-th row of each item")
     ap.add_argument("--tempo-ratios", type=lambda v: [int(x) for x in v.split(",")], default=None,
                     help="ratio counts to time ops.identify_tempo at, e.g. 1,15,31")
+    ap.add_argument("--tempo-items", action="store_true",
+                    help="tempo: ops.identify_tempo at 3 ratios against ops.identify_tempo_items with windows of 3")
     ap.add_argument("--tempo-num", type=int, default=266, help="tempo: the ratio the items are planted at (num / 256)")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
@@ -268,7 +304,7 @@ def main(argv=None):
     rows = torch.randn((n, 128), generator=g, device=dev)
     rows /= rows.norm(dim=1, keepdim=True)
     first = torch.arange(T + 1, device=dev, dtype=torch.int64) * per
-    if args.tempo_ratios is not None:
+    if args.tempo_ratios is not None or args.tempo_items:
         print(json.dumps(_tempo(args, dev, rows, first, per)))
         return
     rng = np.random.RandomState(1)

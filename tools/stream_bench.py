@@ -4,13 +4,17 @@ channel's last window_s seconds as a waveform, run FingerprintLibrary.segments o
 identify of every channel's newest window).
 
     python tools/stream_bench.py [--channels 64 512] [--pushes 10] [--warm 4] [--tracks 64] [--track-s 30]
-                                 [--query-stride 1 2 4] [--monitor-only]
+                                 [--query-stride 1 2 4] [--monitor-only] [--tempo X [--tempo-step G] [--tempo-lock N]]
 
 The monitor embeds only the segments that are new (about 10.4 per channel and second at the default settings); the
 per-channel path embeds the 21 segments of the newest window again every second.  One JSON line per channel count, then
 a table.  --query-stride Q ... times the monitor once per stride (StreamMonitor(query_stride=Q)
 embeds every Q-th segment of a channel only; 1 is the baseline of the same run; DESIGN.md section 12.31);
---monitor-only leaves the per-channel path out."""
+--monitor-only leaves the per-channel path out.  --tempo X also times StreamMonitor(tempo=X) and, with --tempo-lock N,
+StreamMonitor(tempo=X, tempo_lock=N); every channel then plays an excerpt of a library track,
+cut at a multiple of the segment hop, instead of noise, so that channels can lock, and each of these runs reports the
+tempo_stats of its timed pushes -- give --warm N + 4 or more for figures "once locked" (three seconds fill the first
+window, N windows engage the lock)."""
 import argparse
 import json
 import os
@@ -55,13 +59,15 @@ def _median(rows, key):
     return statistics.median(r.get(key, 0.0) for r in rows)
 
 
-def bench_monitor(lib, audio, chunk, warm, phases, query_stride=1):
+def bench_monitor(lib, audio, chunk, warm, phases, query_stride=1, tempo=None, tempo_step=None, tempo_lock=0):
     C, total = audio.shape
-    plain, split, launches, windows = [], [], [], 0
+    plain, split, launches, windows, stats = [], [], [], 0, None
     for instrumented in (False, True):
         phases.enabled = instrumented
-        mon = StreamMonitor(lib, C, max_chunk_s=chunk / lib.settings["fs"], query_stride=query_stride)
+        mon = StreamMonitor(lib, C, max_chunk_s=chunk / lib.settings["fs"], query_stride=query_stride, tempo=tempo,
+                            tempo_step=tempo_step, tempo_lock=tempo_lock)
         mon.front.push = phases.wrap("front_end", mon.front.push)
+        before_stats = None
         for s in range(total // chunk):
             chunks = list(audio[:, s * chunk:(s + 1) * chunk])
             before = mon.front.launches
@@ -72,6 +78,7 @@ def bench_monitor(lib, audio, chunk, warm, phases, query_stride=1):
             torch.cuda.synchronize()
             ms = (time.perf_counter() - t0) * 1e3
             if s < warm:
+                before_stats = dict(mon.tempo_stats) if tempo is not None else None
                 continue
             if instrumented:
                 split.append(dict(phases.take(), total=ms))
@@ -79,8 +86,12 @@ def bench_monitor(lib, audio, chunk, warm, phases, query_stride=1):
                 plain.append(ms)
                 launches.append(mon.front.launches - before)
                 windows += sum(len(w) for w in out)
-    res = {"push_ms": statistics.median(plain), "front_end_launches": max(launches),
-           "windows_per_push": windows / len(plain)}
+        if tempo is not None and not instrumented:
+            stats = {k: v - (before_stats or {}).get(k, 0) for k, v in mon.tempo_stats.items()}
+    res = {"push_ms": statistics.median(plain), "push_ms_min_max": [min(plain), max(plain)],
+           "front_end_launches": max(launches), "windows_per_push": windows / len(plain)}
+    if stats is not None:
+        res["tempo_stats"] = stats
     for key in ("front_end", "embed", "search", "identify"):
         res[key + "_ms"] = _median(split, key)
     res["other_ms"] = max(0.0, _median(split, "total") - sum(res[k + "_ms"] for k in ("front_end", "embed", "search",
@@ -133,6 +144,9 @@ def main():
     ap.add_argument("--chunk-s", type=float, default=1.0)
     ap.add_argument("--query-stride", type=int, nargs="+", default=[1], help="strides to time the monitor at")
     ap.add_argument("--monitor-only", action="store_true", help="leave the per-channel path out")
+    ap.add_argument("--tempo", type=float, default=None, help="also time StreamMonitor(tempo=X), e.g. 0.06")
+    ap.add_argument("--tempo-step", type=int, default=None, help="with --tempo: the ratio grid's spacing in 1/256")
+    ap.add_argument("--tempo-lock", type=int, default=0, help="with --tempo: also time StreamMonitor(tempo_lock=N)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     cfg = load_config()
@@ -148,17 +162,29 @@ def main():
     chunk = int(args.chunk_s * cfg["fs"])
     rows = []
     for C in args.channels:
-        audio = 0.1 * torch.randn((C, (args.warm + args.pushes) * chunk), generator=g, device=dev)
+        total = (args.warm + args.pushes) * chunk
+        if args.tempo is None:
+            audio = 0.1 * torch.randn((C, total), generator=g, device=dev)
+        else:                                   # channel c plays track c from a start of its own
+            cut = 3 * lib.step * cfg["hop_len"]
+            if total + 7 * cut > tracks.shape[1]:
+                raise SystemExit(f"--tempo: tracks of {args.track_s} s are too short for {args.warm + args.pushes} pushes")
+            audio = torch.stack([tracks[c % args.tracks, (c % 8) * cut:(c % 8) * cut + total] for c in range(C)])
         runs = [("monitor" if Q == 1 else f"monitor Q={Q}", bench_monitor, {"query_stride": Q})
                 for Q in args.query_stride]
+        if args.tempo is not None:
+            runs.append(("tempo", bench_monitor, {"tempo": args.tempo, "tempo_step": args.tempo_step}))
+            if args.tempo_lock:
+                runs.append((f"tempo lock={args.tempo_lock}", bench_monitor,
+                             {"tempo": args.tempo, "tempo_step": args.tempo_step, "tempo_lock": args.tempo_lock}))
         for path, fn, kw in runs + ([] if args.monitor_only else [("per_channel", bench_per_channel, {})]):
             res = dict(fn(lib, audio, chunk, args.warm, phases, **kw), channels=C, path=path, library_rows=lib.n_rows)
             rows.append(res)
             print(json.dumps(res), flush=True)
-    print(f"{'C':>5} {'path':<12} {'push ms':>9} {'front end':>10} {'embed':>8} {'search':>8} {'identify':>9} {'other':>7} "
+    print(f"{'C':>5} {'path':<14} {'push ms':>9} {'front end':>10} {'embed':>8} {'search':>8} {'identify':>9} {'other':>7} "
           f"{'front-end launches':>19}")
     for r in rows:
-        print(f"{r['channels']:>5} {r['path']:<12} {r['push_ms']:>9.2f} {r['front_end_ms']:>10.2f} {r['embed_ms']:>8.2f} "
+        print(f"{r['channels']:>5} {r['path']:<14} {r['push_ms']:>9.2f} {r['front_end_ms']:>10.2f} {r['embed_ms']:>8.2f} "
               f"{r['search_ms']:>8.2f} {r['identify_ms']:>9.2f} {r['other_ms']:>7.2f} {r['front_end_launches']:>19d}")
 
 
