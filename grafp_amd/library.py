@@ -7,8 +7,9 @@ they start: log-mel and segments on the device, one batched embed, one batched s
 (csrc/identify.hip) for all queries.  Unlike eval.py's row-level rerank (ops.seq_rerank), a candidate never reads
 across a track boundary and the result is the best tracks, not the best rows.
 
-A library has three forms.  The flat form above keeps every row as f32 (plus the index's bf16 copy and norms: 772 bytes
-per row).  The compact form keeps IVF-PQ codes only -- per row M code bytes in row order, the list id, and the
+A library has three forms, each a class of grafp_amd/_forms.py; it holds one form object, which answers whatever
+depends on how the rows are held (the tensors, the index, the files, the ops).  The flat form above keeps every row as
+f32 (plus the index's bf16 copy and norms: 772 bytes per row).  The compact form keeps IVF-PQ codes only -- per row M code bytes in row order, the list id, and the
 grafp_amd.ivfpq.IVFPQIndex over them (the codes again in list order, the ids): 2 M + 20 bytes per row, 148 at M = 64 --
 and identifies with ops.identify_pq (csrc/identify_pq.hip), which scores the decoded rows without ever storing them.
 build(index="ivfpq"), compress() and load() make one; identify, identify_windows, timeline and match work on either
@@ -64,12 +65,9 @@ import numpy as np
 import torch
 
 from . import ops
+from ._forms import FORMAT, FORMAT_COMPACT, FORMAT_HALF, FORMAT_THIN, FORMS, CompactForm, FlatForm, HalfForm
 
 SETTINGS = ("fs", "n_fft", "win_len", "hop_len", "n_mels", "n_frames", "overlap")
-FORMAT = 1                   # the files of a flat library
-FORMAT_COMPACT = 2           # the files of a compact library
-FORMAT_THIN = 3              # the files of a flat library that keeps every row_stride-th row ("row_stride" in library.json)
-FORMAT_HALF = 5              # the files of a half library (bf16 rows as uint16 bit patterns; 4 is refused, as it always was)
 # What the half form costs against the flat form over the f32 rows X it was rounded from.  bf16 keeps 8 significant bits,
 # so round to nearest even moves a component by at most half an ulp, 2^-8 relative; then ||x^ - x|| <= 2^-8 ||x|| and
 # (Cauchy-Schwarz) an inner product <q, x> moves by at most 2^-8 |q| |x|; a span score, a mean of such products, by at most
@@ -682,10 +680,9 @@ class FingerprintLibrary(LibraryFront):
             raise ValueError(f"row_stride={row_stride} not in [1, {ops.IDENTIFY_MAX_STRIDE}]")
         super().__init__(model, settings, precision,
                          torch.device(device) if device is not None else next(model.parameters()).device, row_stride)
-        # the rows: chunks of (rows f32,), or in the compact form of (list_id int32, codes uint8), as they were appended
+        # the rows: chunks of the form's tuple of tensors ((rows,), or (list_id, codes)), as they were appended
         self._chunks, self._held, self._index = [], None, None
-        self._pq, self._encoder = None, None       # compact form: {"centroids", "codebooks", "nprobe"}
-        self._half = False                         # half form: the chunks are (rows bf16,)
+        self._form = FlatForm(self.device, row_stride)               # how they are held (_forms.py): flat, half or compact
         if rows is not None:
             self._append(rows, first, names)
 
@@ -707,32 +704,24 @@ class FingerprintLibrary(LibraryFront):
         it answers every call it supports bit for bit as the flat library over U does.  Works on device="cpu" (files and
         tables only), like from_codes."""
         lib = cls(model, settings, None, None, precision=precision, device=device)
-        lib._half = True
+        lib._form = HalfForm(lib.device)
         lib._append_half(rows_bf16, first, names)
         return lib
 
     def _set_quantiser(self, quantiser, nprobe):
-        cent = torch.as_tensor(quantiser["centroids"]).to(self.device, torch.float32).contiguous()
-        books = torch.as_tensor(quantiser["codebooks"]).to(self.device, torch.float32).contiguous()
-        M = int(books.shape[0]) if books.dim() == 3 else 0
-        if M not in ops.IDENTIFY_PQ_M or cent.dim() != 2 or cent.shape[1] != 128 or cent.shape[0] < 1 or \
-                tuple(books.shape) != (M, 256, 128 // M):
-            raise ValueError(f"a compact library needs centroids (nlist, 128) and codebooks (M, 256, 128 // M) with M "
-                             f"one of {ops.IDENTIFY_PQ_M}, not {tuple(cent.shape)} and {tuple(books.shape)}")
-        self._pq, self._held = {"centroids": cent, "codebooks": books, "nprobe": int(nprobe)}, None
+        self._form, self._held = CompactForm(self.device, quantiser, nprobe), None
 
     @property
     def is_compact(self):
-        return self._pq is not None
+        return self._form.is_compact
 
     @property
     def is_half(self):
-        return self._half
+        return self._form.is_half
 
     def _need_half(self, what):
         if not self.is_half:
-            raise ValueError(f"FingerprintLibrary.{what}: this is no half library (bf16 rows); halve() makes one of a "
-                             "flat library")
+            raise ValueError(f"FingerprintLibrary.{what}: {HalfForm.missing}")
 
     def half_rows(self):
         """The resident (n_rows, 128) bf16 fingerprints of a half library: the tensor its index searches."""
@@ -742,12 +731,11 @@ class FingerprintLibrary(LibraryFront):
     def quantiser(self):
         """{"centroids", "codebooks"} of a compact library (device tensors)."""
         self._need_compact("quantiser()")
-        return {"centroids": self._pq["centroids"], "codebooks": self._pq["codebooks"]}
+        return self._form.quantiser()
 
     def _need_compact(self, what):
         if not self.is_compact:
-            raise ValueError(f"FingerprintLibrary.{what}: this is a flat library (f32 rows); compress() makes a "
-                             "compact one")
+            raise ValueError(f"FingerprintLibrary.{what}: {CompactForm.missing}")
 
     @property
     def nbytes(self):
@@ -755,34 +743,19 @@ class FingerprintLibrary(LibraryFront):
         plus its index, which is made here if the device has one (on a CPU device only the library's own tensors count).
         Flat: 772 bytes per row.  Compact: 2 M + 20 per row, plus the quantiser and the index's two nlist-sized tables.
         Half: 260 bytes per row -- the bf16 rows, which the index shares, and its norms."""
-        held = list(self._stored()) + ([self._pq["centroids"], self._pq["codebooks"]] if self.is_compact else [])
+        held = self._form.held_tensors(self._stored())
         if self.device.type == "cuda" and self.n_rows:
-            index = self.index
-            if self.is_compact:
-                held += index.held_tensors()
-            elif self.is_half:
-                held += list(index._materialise())
-            else:
-                index._materialise()
-                held += [index._db, index._sq, index._bf16]
-        seen = {t.untyped_storage().data_ptr(): t.untyped_storage().nbytes() for t in held if t is not None}
+            held += self.index.held_tensors()
+        seen = {t.untyped_storage().data_ptr(): t.untyped_storage().nbytes() for t in held}
         return int(sum(seen.values()))
 
     def _stored(self):
-        """All rows as one tuple of tensors, (rows,) (f32, or bf16 in the half form) or (list_id, codes): the chunks concatenated on first use and kept
-        as the one chunk; a library without rows gives its form's empty tensors."""
+        """All rows as one tuple of tensors, (rows,) (f32, or bf16 in the half form) or (list_id, codes): the chunks
+        concatenated on first use and kept as the one chunk; a library without rows gives its form's empty tensors."""
         if self._held is None:
             if len(self._chunks) > 1:
                 self._chunks = [tuple(torch.cat(part) for part in zip(*self._chunks))]
-            if self._chunks:
-                self._held = self._chunks[0]
-            elif self.is_compact:
-                M = int(self._pq["codebooks"].shape[0])
-                self._held = (torch.zeros(0, dtype=torch.int32, device=self.device),
-                              torch.zeros((0, M), dtype=torch.uint8, device=self.device))
-            else:
-                self._held = (torch.zeros((0, 128), dtype=torch.bfloat16 if self.is_half else torch.float32,
-                                          device=self.device),)
+            self._held = self._chunks[0] if self._chunks else self._form.empty()
         return self._held
 
     def rows(self):
@@ -801,16 +774,7 @@ class FingerprintLibrary(LibraryFront):
         for a compact library, the ivfpq.IVFPQIndex over codes() (from_codes: nothing is re-encoded, the row-order codes
         are shared), or, for a half library, the ops.HalfL2Index over half_rows() (it shares that tensor)."""
         if self._index is None:
-            if self.is_half:
-                self._index = ops.HalfL2Index(d=128, device=self.device)
-                self._index.add(self.half_rows())
-            elif self.is_compact:
-                from .ivfpq import IVFPQIndex
-                list_id, codes = self.codes()
-                self._index = IVFPQIndex.from_codes(self.quantiser(), list_id, codes, self.device, self._pq["nprobe"])
-            else:
-                self._index = ops.FlatL2Index(d=128, device=self.device)
-                self._index.add(self.rows())
+            self._index = self._form.index(self._stored())
         return self._index
 
     def _store(self, n_new, chunk, first, names):
@@ -827,68 +791,42 @@ class FingerprintLibrary(LibraryFront):
 
     def _append(self, rows, first, names):
         self._need_flat("_append()")
-        rows = torch.as_tensor(rows).to(self.device, torch.float32).reshape(-1, 128)
-        self._store(rows.shape[0], lambda: (rows.contiguous(),), first, names)
+        self._store(*self._form.chunk(rows), first, names)
 
     def _append_half(self, rows_bf16, first, names):
         self._need_half("_append_half()")
-        if isinstance(rows_bf16, np.ndarray) and rows_bf16.dtype == np.uint16:      # bit patterns, as save() writes them
-            rows_bf16 = torch.from_numpy(np.ascontiguousarray(rows_bf16).view(np.int16)).view(torch.bfloat16)
-        rows = torch.as_tensor(rows_bf16)
-        if rows.dtype != torch.bfloat16 or rows.dim() != 2 or rows.shape[1] != 128:
-            raise ValueError(f"the rows of a half library must be (n, 128) torch.bfloat16 (or their uint16 bit patterns "
-                             f"in a numpy array), not {tuple(rows.shape)} {rows.dtype}")
-        self._store(rows.shape[0], lambda: (rows.detach().to(self.device).contiguous(),), first, names)
+        self._store(*self._form.chunk(rows_bf16), first, names)
 
     def _append_codes(self, list_id, codes, first, names):
         self._need_compact("_append_codes()")
-        M, nlist = int(self._pq["codebooks"].shape[0]), int(self._pq["centroids"].shape[0])
-        codes, list_id = torch.as_tensor(codes), torch.as_tensor(list_id).reshape(-1)
-        if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.shape[1] != M:
-            raise ValueError(f"codes must be (n, {M}) uint8, not {tuple(codes.shape)} {codes.dtype}")
-        if list_id.shape[0] != codes.shape[0] or list_id.dtype not in (torch.int32, torch.int64):
-            raise ValueError(f"{list_id.shape[0]} list ids ({list_id.dtype}) for {codes.shape[0]} rows of codes")
-        if list_id.numel() and not 0 <= int(list_id.min()) <= int(list_id.max()) < nlist:
-            raise ValueError(f"a list id lies outside [0, {nlist})")
-        self._store(codes.shape[0], lambda: (list_id.to(self.device, torch.int32).contiguous(),
-                                             codes.to(self.device).contiguous()), first, names)
+        self._store(*self._form.chunk(list_id, codes), first, names)
 
-    def _encode(self, rows):
-        """f32 rows on the device -> (list_id int32, codes uint8) with the library's quantiser (csrc/ivfpq.hip)."""
-        if self._encoder is None:
-            from .ivfpq import IVFPQIndex
-            M = int(self._pq["codebooks"].shape[0])
-            self._encoder = IVFPQIndex.from_codes(self.quantiser(), torch.zeros(0, dtype=torch.int32),
-                                                  torch.zeros((0, M), dtype=torch.uint8), self.device)
-        a, codes = self._encoder.encode(rows)
-        return a.to(torch.int32), codes
-
-    def _fingerprint_codes(self, waves, max_segments, train=None):
-        """Fingerprint and encode one model call after the other; the f32 rows of a call are dropped once encoded.
-        train = (nlist, pq_m, nprobe, train_rows, seed) for a library that has no quantiser yet: the rows of the first
-        calls are held until train_rows of them are there (or the input ends), the quantiser is trained on them, they are
-        encoded, and from then on every call is encoded as it comes -- never more f32 rows alive than train_rows plus one
-        call's (max_segments, rounded up to whole tracks).  -> (list_id, codes, per-track row counts)."""
+    def _fingerprint_codes(self, waves, max_segments, train):
+        """build(index="ivfpq") without a quantiser: fingerprint and encode one model call after the other; the f32 rows
+        of a call are dropped once encoded.  train = (nlist, pq_m, nprobe, train_rows, seed): the rows of the first
+        calls are held until train_rows of them are there (or the input ends), the quantiser is trained on them (the
+        library is compact from then on), they are encoded, and every later call is encoded as it comes -- never more f32
+        rows alive than train_rows plus one call's (max_segments, rounded up to whole tracks).  -> (list_id, codes,
+        per-track row counts)."""
         counts, held, n_held, out = [], [], 0, []
         for rows in self._fingerprint_batches(waves, max_segments, counts):
-            if not self.is_compact:
+            if held is not None:
                 held.append(rows)
                 n_held += rows.shape[0]
                 if n_held < train[3]:
                     continue
-                rows, held = torch.cat(held), []
+                rows, held = torch.cat(held), None
                 self._train_quantiser(rows, *train[:3], rows.shape[0], train[4])
             if rows.shape[0]:
-                out.append(self._encode(rows))
-        if not self.is_compact:                              # the input ended before train_rows rows were there
+                out.append(self._form.encode(rows))
+        if held is not None:                                 # the input ended before train_rows rows were there
             if n_held == 0:
                 raise ValueError("an IVF-PQ library cannot be trained on tracks that give no fingerprint rows")
             rows = torch.cat(held)
             self._train_quantiser(rows, *train[:3], rows.shape[0], train[4])
-            out.append(self._encode(rows))
-        if not out:
-            return self.codes()[0][:0], self.codes()[1][:0], counts
-        return torch.cat([p[0] for p in out]), torch.cat([p[1] for p in out]), counts
+            out.append(self._form.encode(rows))
+        data = tuple(torch.cat(part) for part in zip(*out)) if out else self._form.empty()
+        return (*data, counts)
 
     def _train_quantiser(self, rows, nlist, pq_m, nprobe, train_rows, seed):
         """Both k-means of ivfpq.IVFPQIndex.train on `rows` (at most train_rows of them, a seeded sample in row order)."""
@@ -924,7 +862,7 @@ class FingerprintLibrary(LibraryFront):
                 raise NotImplementedError(f"build(index='half') needs every row of a track: a thinned half library "
                                           f"(row_stride={row_stride}) is not built; use index='flat' with row_stride")
             lib = cls(model, cfg, None, None, precision=precision)
-            lib._half = True
+            lib._form = HalfForm(lib.device)
             return lib.add(tracks, names=names, max_segments=max_segments)
         if index == "ivfpq" and int(row_stride) != 1:
             raise NotImplementedError(f"build(index='ivfpq') needs every row of a track: row_stride={row_stride} codes "
@@ -944,19 +882,11 @@ class FingerprintLibrary(LibraryFront):
         """Append tracks (as for build) to the library; a compact library encodes them with its own quantiser, a
         thinned one keeps every row_stride-th segment of each, a half one rounds each model call's rows to bf16."""
         waves, own = _as_waveforms(tracks)
-        names = names if names is not None else own
-        if self.is_half:
-            counts = []
-            parts = [ops.rows_to_bf16(rows) for rows in self._fingerprint_batches(waves, int(max_segments), counts)
-                     if rows.shape[0]]
-            rows = torch.cat(parts) if parts else self.half_rows()[:0]
-            self._append_half(rows, track_table(counts), names)
-        elif self.is_compact:
-            a, codes, counts = self._fingerprint_codes(waves, int(max_segments))
-            self._append_codes(a, codes, track_table(counts), names)
-        else:
-            rows, counts = self._fingerprint_tracks(waves, int(max_segments))
-            self._append(rows, track_table(counts), names)
+        counts = []
+        parts = [self._form.encode(rows) for rows in self._fingerprint_batches(waves, int(max_segments), counts)
+                 if rows.shape[0]]
+        data = tuple(torch.cat(part) for part in zip(*parts)) if parts else self._form.empty()
+        self._store(*self._form.chunk(*data), track_table(counts), names if names is not None else own)
         return self
 
     def compress(self, nlist=64, pq_m=64, nprobe=20, train_rows=65536, seed=1234, chunk=1 << 16):
@@ -969,7 +899,7 @@ class FingerprintLibrary(LibraryFront):
         out = FingerprintLibrary(self.model, self.settings, None, None, precision=self.precision, device=self.device)
         rows = self.rows()
         out._train_quantiser(rows, nlist, pq_m, nprobe, train_rows, seed)
-        parts = [out._encode(rows[lo:lo + chunk]) for lo in range(0, rows.shape[0], chunk)]
+        parts = [out._form.encode(rows[lo:lo + chunk]) for lo in range(0, rows.shape[0], chunk)]
         out._append_codes(torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]), self.first, self.names)
         return out
 
@@ -1008,27 +938,10 @@ class FingerprintLibrary(LibraryFront):
         "ivfpq", "nlist", "M", "nprobe"}) -- and no library.mm.  A thinned library writes the flat library's four files
         with "format": 3 and "row_stride": D in library.json.  A half library writes library_half.npy ((n, 128) uint16,
         the bf16 bit patterns), library_tracks.npy and library.json ("format": 5) -- and no library.mm."""
-        from .fpdb import _write_memmap
         os.makedirs(out_dir, exist_ok=True)
         meta = {"format": FORMAT, "names": self.names, "settings": self.settings, "precision": self.precision,
                 "model_digest": model_digest(self.model), "n_rows": self.n_rows, "n_tracks": self.n_tracks}
-        if self.is_half:
-            bits = self.half_rows().cpu().contiguous().view(torch.int16).numpy().view(np.uint16)
-            np.save(os.path.join(out_dir, "library_half.npy"), bits.reshape(-1, 128))
-            meta["format"] = FORMAT_HALF
-        elif self.is_compact:
-            list_id, codes = self.codes()
-            cent, books = self._pq["centroids"].cpu().numpy(), self._pq["codebooks"].cpu().numpy()
-            np.save(os.path.join(out_dir, "library_codes.npy"), codes.cpu().numpy())
-            np.save(os.path.join(out_dir, "library_lists.npy"), list_id.cpu().numpy().astype(np.int32))
-            np.savez(os.path.join(out_dir, "library_pq.npz"), centroids=cent, codebooks=books)
-            meta["format"] = FORMAT_COMPACT
-            meta["index"] = {"type": "ivfpq", "nlist": int(cent.shape[0]), "M": int(books.shape[0]),
-                             "nprobe": self._pq["nprobe"]}
-        else:
-            if self._row_stride != 1:
-                meta["format"], meta["row_stride"] = FORMAT_THIN, self._row_stride
-            _write_memmap(os.path.join(out_dir, "library"), self.rows().cpu().numpy().reshape(-1, 128))
+        self._form.save(out_dir, self._stored(), meta)
         np.save(os.path.join(out_dir, "library_tracks.npy"), self.first.astype(np.int64))
         with open(os.path.join(out_dir, "library.json"), "w") as f:
             json.dump(meta, f, indent=1)
@@ -1050,36 +963,16 @@ class FingerprintLibrary(LibraryFront):
             raise ValueError(f"{lib_dir}: the library was fingerprinted with another model (state_dict digest "
                              f"{meta['model_digest'][:12]}...); pass force=True to use it anyway")
         first = np.load(os.path.join(lib_dir, "library_tracks.npy")).astype(np.int64)
-        compact, half = meta["format"] == FORMAT_COMPACT, meta["format"] == FORMAT_HALF
-        if half:
-            bits = np.load(os.path.join(lib_dir, "library_half.npy"))
-            if bits.dtype != np.uint16 or bits.ndim != 2 or bits.shape[1] != 128:
-                raise ValueError(f"{lib_dir}: library_half.npy must be (n, 128) uint16, not {bits.shape} {bits.dtype}")
-            shape = bits.shape
-        elif compact:
-            if meta.get("index", {}).get("type") != "ivfpq":
-                raise ValueError(f"{lib_dir}: a format {FORMAT_COMPACT} library with index {meta.get('index')!r}")
-            codes = np.load(os.path.join(lib_dir, "library_codes.npy"))
-            lists = np.load(os.path.join(lib_dir, "library_lists.npy"))
-            shape = codes.shape
-        else:
-            shape = tuple(int(v) for v in np.load(os.path.join(lib_dir, "library_shape.npy")))
+        shape, finish = FORMS[meta["format"]].read(lib_dir, meta)
         if shape[0] != int(first[-1]):
             raise ValueError(f"{lib_dir}: {shape[0]} rows but the track table covers {int(first[-1])}")
         if device is not None:
             model = model.to(device)
-        if half:
-            return cls.from_half(model, meta["settings"], bits, first, meta["names"], meta["precision"], device)
-        if compact:
-            with np.load(os.path.join(lib_dir, "library_pq.npz")) as pq:
-                quantiser = {"centroids": torch.from_numpy(pq["centroids"]), "codebooks": torch.from_numpy(pq["codebooks"])}
-            return cls.from_codes(model, meta["settings"], quantiser, torch.from_numpy(lists), torch.from_numpy(codes),
-                                  first, meta["names"], meta["precision"], device, meta["index"]["nprobe"])
-        rows = np.fromfile(os.path.join(lib_dir, "library.mm"), dtype=np.float32).reshape(shape) if shape[0] else \
-            np.zeros((0, 128), np.float32)
-        stride = stride if meta["format"] == FORMAT_THIN else 1
-        return cls(model, meta["settings"], torch.from_numpy(rows), first, meta["names"], meta["precision"], device,
-                   row_stride=stride)
+        lib = cls(model, meta["settings"], None, None, precision=meta["precision"], device=device,
+                  row_stride=stride if meta["format"] == FORMAT_THIN else 1)
+        lib._form, data = finish(lib.device, lib.row_stride)
+        lib._store(*lib._form.chunk(*data), first, meta["names"])
+        return lib
 
     @classmethod
     def from_memmap(cls, db_dir, fname, track_rows, model, cfg, names=None, precision="f32"):
@@ -1112,13 +1005,7 @@ class FingerprintLibrary(LibraryFront):
             return ops.identify_tempo_items(self.rows(), *tail, nums, *item_ratios, **kw)
         if nums is not None:
             return ops.identify_tempo(self.rows(), *tail, nums, **kw)
-        if self.is_half:
-            return ops.identify_half(self.half_rows(), *tail, **kw)
-        if self.is_compact:
-            return ops.identify_pq(*self.codes(), self._pq["centroids"], self._pq["codebooks"], *tail, **kw)
-        if self._row_stride != 1:
-            return ops.identify_thin(self.rows(), *tail, self._row_stride, **kw)
-        return ops.identify(self.rows(), *tail, **kw)
+        return self._form.identify(self._stored(), *tail, **kw)
 
     def _match_lists(self, qb, src, k_probe, nums, kw):
         return self._match_launch(qb, src, self._search_rows(qb, k_probe), nums, kw)
@@ -1129,12 +1016,7 @@ class FingerprintLibrary(LibraryFront):
         first_d = torch.from_numpy(self.first).to(self.device)
         if nums is not None:
             return ops.cross_match_tempo(self.rows(), first_d, qb, src, ids, nums, **kw)
-        if self.is_half:
-            return ops.cross_match_half(self.half_rows(), first_d, qb, src, ids, **kw)
-        if self.is_compact:
-            return ops.cross_match_pq(*self.codes(), self._pq["centroids"], self._pq["codebooks"], first_d, qb, src, ids,
-                                      **kw)
-        return ops.cross_match(self.rows(), first_d, qb, src, ids, **kw)
+        return self._form.cross_match(self._stored(), first_d, qb, src, ids, **kw)
 
     # ---- the catalog itself ------------------------------------------------------------------------------------
     def self_matches(self, k_probe=32, min_overlap_s=3.0, min_votes=4, min_score=None, top=8, tracks=None,

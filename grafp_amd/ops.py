@@ -2639,27 +2639,20 @@ def merge_track_lists(track, score, payload, track_base, pad, top=None):
     return out_t[:, :top], out_s[:, :top], out_p[:, :, :top]
 
 
-class FlatL2Index:
-    """Drop-in for the subset of faiss.IndexFlatL2 that eval.py uses: d, ntotal, add(x), search(q, k).
-    The database lives in HBM; `add` also computes the per-row squared norms once."""
+class _ExactL2Index:
+    """What FlatL2Index and HalfL2Index share: the chunks that add() was given, concatenated once at the first use after
+    them, the empty index's answer and the numpy-in / numpy-out handling.  A class states _checked(x) (add's input ->
+    the device tensor it keeps), _derive(db) -> (squared norms, bf16 copy or None) and _search(db, sq, q, k)."""
 
-    def __init__(self, d=128, device=None, id_base=0, prefilter=True):
+    def __init__(self, d, device, id_base):
         if not torch.cuda.is_available():
-            raise RuntimeError("FlatL2Index needs a HIP device: there is no CPU fallback")
-        self.d = d
-        self.prefilter = bool(prefilter)     # bf16 pre-filter scan + exact rescoring (same results, 2-4x faster)
-        self._bf16 = None
+            raise RuntimeError(f"{type(self).__name__} needs a HIP device: there is no CPU fallback")
+        self.d, self.id_base, self.ntotal = d, int(id_base), 0
         self.device = torch.device(device if device is not None else "cuda")
-        self.id_base = int(id_base)
-        self._chunks = []
-        self._db = None
-        self._sq = None
-        self.ntotal = 0
-        self.nprobe = 1            # attribute assigned at eval.py:122; meaningless for exact search
+        self._chunks, self._db, self._sq, self._bf16 = [], None, None, None
 
     def add(self, x):
-        t = torch.as_tensor(np.ascontiguousarray(x) if isinstance(x, np.ndarray) else x)
-        t = t.to(self.device, dtype=torch.float32).reshape(-1, self.d).contiguous()
+        t = self._checked(x)
         self._chunks.append(t)
         self.ntotal += t.shape[0]
         self._db = None
@@ -2668,13 +2661,12 @@ class FlatL2Index:
         if self._db is None:
             self._db = self._chunks[0] if len(self._chunks) == 1 else torch.cat(self._chunks, dim=0)
             self._chunks = [self._db]
-            self._sq = row_sqnorm(self._db)
-            self._bf16 = rows_to_bf16(self._db) if self.prefilter else None
+            self._sq, self._bf16 = self._derive(self._db)
         return self._db, self._sq
 
-    def rows(self):
-        """The resident (ntotal, d) f32 database tensor (what faiss calls reconstruct_n(0, ntotal))."""
-        return self._materialise()[0]
+    def held_tensors(self):
+        """Every device tensor the index holds once it is searchable (its share of FingerprintLibrary.nbytes)."""
+        return [t for t in (*self._materialise(), self._bf16) if t is not None] if self.ntotal else []
 
     def search(self, q, k):
         """numpy in -> numpy out (D float32 (nq,k), I int64 (nq,k)), like faiss; tensors in -> tensors out."""
@@ -2684,43 +2676,52 @@ class FlatL2Index:
             D = torch.full((qt.shape[0], k), float("inf"), device=self.device)
             I = torch.full((qt.shape[0], k), -1, dtype=torch.int64, device=self.device)
         else:
-            db, sq = self._materialise()
-            D, I = search_l2(db, sq, qt.reshape(-1, self.d), k, self.id_base, db_bf16=self._bf16)
+            D, I = self._search(*self._materialise(), qt.reshape(-1, self.d), k)
         return (D.cpu().numpy(), I.cpu().numpy()) if as_numpy else (D, I)
 
 
-class HalfL2Index:
+class FlatL2Index(_ExactL2Index):
+    """Drop-in for the subset of faiss.IndexFlatL2 that eval.py uses: d, ntotal, add(x), search(q, k).
+    The database lives in HBM; `add` also computes the per-row squared norms once."""
+
+    def __init__(self, d=128, device=None, id_base=0, prefilter=True):
+        super().__init__(d, device, id_base)
+        self.prefilter = bool(prefilter)     # bf16 pre-filter scan + exact rescoring (same results, 2-4x faster)
+        self.nprobe = 1            # attribute assigned at eval.py:122; meaningless for exact search
+
+    def _checked(self, x):
+        t = torch.as_tensor(np.ascontiguousarray(x) if isinstance(x, np.ndarray) else x)
+        return t.to(self.device, dtype=torch.float32).reshape(-1, self.d).contiguous()
+
+    def _derive(self, db):
+        return row_sqnorm(db), rows_to_bf16(db) if self.prefilter else None
+
+    def rows(self):
+        """The resident (ntotal, d) f32 database tensor (what faiss calls reconstruct_n(0, ntotal))."""
+        return self._materialise()[0]
+
+    def _search(self, db, sq, q, k):
+        return search_l2(db, sq, q, k, self.id_base, db_bf16=self._bf16)
+
+
+class HalfL2Index(_ExactL2Index):
     """FlatL2Index for a database held as bf16 rows only: d, ntotal, add(rows_bf16), search(q, k); 260 bytes a row with
     the norm, and no rows() in f32.  With U = the rows' f32 values (exact) every search answers bit for bit as a
     FlatL2Index over U does.  The index shares the rows tensor it is given and copies nothing (several add() calls are
     concatenated once, at the first search after them)."""
 
     def __init__(self, d=128, device=None, id_base=0):
-        if not torch.cuda.is_available():
-            raise RuntimeError("HalfL2Index needs a HIP device: there is no CPU fallback")
+        super().__init__(d, device, id_base)
         if d != 128:
             raise ValueError(f"HalfL2Index: d={d} unsupported (fingerprints are 128-d)")
-        self.d = d
-        self.device = torch.device(device if device is not None else "cuda")
-        self.id_base = int(id_base)
-        self._chunks = []
-        self._db = None
-        self._sq = None
-        self.ntotal = 0
 
-    def add(self, rows_bf16):
+    def _checked(self, rows_bf16):
         t = _half_rows("HalfL2Index.add", rows_bf16)
         _require_gpu(t)
-        self._chunks.append(t)
-        self.ntotal += t.shape[0]
-        self._db = None
+        return t
 
-    def _materialise(self):
-        if self._db is None:
-            self._db = self._chunks[0] if len(self._chunks) == 1 else torch.cat(self._chunks, dim=0)
-            self._chunks = [self._db]
-            self._sq = row_sqnorm_half(self._db)
-        return self._db, self._sq
+    def _derive(self, db):
+        return row_sqnorm_half(db), None
 
     def half_rows(self):
         """The resident (ntotal, 128) bf16 database tensor: the one tensor add() was given, when it was one."""
@@ -2729,19 +2730,7 @@ class HalfL2Index:
     @property
     def nbytes(self):
         """Device bytes of the index: 260 a row."""
-        if self.ntotal == 0:
-            return 0
-        db, sq = self._materialise()
-        return db.numel() * db.element_size() + sq.numel() * sq.element_size()
+        return sum(t.numel() * t.element_size() for t in self.held_tensors())
 
-    def search(self, q, k):
-        """numpy in -> numpy out (D float32 (nq,k), I int64 (nq,k)), like faiss; tensors in -> tensors out."""
-        as_numpy = isinstance(q, np.ndarray)
-        qt = torch.as_tensor(np.ascontiguousarray(q) if as_numpy else q).to(self.device, dtype=torch.float32)
-        if self.ntotal == 0:
-            D = torch.full((qt.shape[0], k), float("inf"), device=self.device)
-            I = torch.full((qt.shape[0], k), -1, dtype=torch.int64, device=self.device)
-        else:
-            db, sq = self._materialise()
-            D, I = search_l2_half(db, sq, qt.reshape(-1, self.d), k, self.id_base)
-        return (D.cpu().numpy(), I.cpu().numpy()) if as_numpy else (D, I)
+    def _search(self, db, sq, q, k):
+        return search_l2_half(db, sq, q, k, self.id_base)

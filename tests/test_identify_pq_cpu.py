@@ -199,7 +199,7 @@ def test_compact_library_tables_save_load_and_refusals(tmp_path):
     assert back.is_compact and back.first.tolist() == lib.first.tolist() and back.names == lib.names
     assert all(torch.equal(x, y) for x, y in zip(back.codes(), lib.codes()))
     assert all(torch.equal(back.quantiser()[k], lib.quantiser()[k]) for k in ("centroids", "codebooks"))
-    assert back.settings == lib.settings and back.precision == "f32" and back._pq["nprobe"] == 3
+    assert back.settings == lib.settings and back.precision == "f32" and back._form.nprobe == 3
     other = _tiny_model()
     with torch.no_grad():
         next(other.parameters()).add_(1.0)

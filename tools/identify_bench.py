@@ -132,8 +132,7 @@ def _half(args, dev, rows, first, q, item_row, item_len, true_track, true_off):
     hit = (got[0][:, 0].long() == torch.from_numpy(true_track).to(dev)) & \
           (got[1][:, 0].long() == torch.from_numpy(true_off).to(dev))
     n = int(rows.shape[0])
-    db, sq = flat._materialise()
-    flat_bytes = db.numel() * 4 + sq.numel() * 4 + flat._bf16.numel() * 2
+    flat_bytes = sum(t.numel() * t.element_size() for t in flat.held_tensors())
     return {"index": "half", "rows": n, "tracks": int(first.numel() - 1), "queries": args.queries, "qlen": ql,
             "k": args.k, "search_flat_ms": round(times["search"][0], 3), "search_half_ms": round(times["search"][1], 3),
             "identify_flat_ms": round(times["identify"][0], 3), "identify_half_ms": round(times["identify"][1], 3),
