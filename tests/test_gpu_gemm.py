@@ -1,5 +1,7 @@
 """GPU tests of the hand-written 1x1-convolution GEMM (gemm.hip): product, folded BatchNorm statistics, normalise-on-load
-prologue, grouped form -- against plain torch f32 arithmetic on the same bf16 operands.  `pytest -m gpu`."""
+prologue, grouped form -- against plain torch f32 arithmetic on the same bf16 operands; at the end every form on every
+tile configuration, and every weight-gradient tile, bit for bit against float64 on exact operands (tests/_gemm_ref.py).
+`pytest -m gpu`."""
 import numpy as np
 import pytest
 import torch
@@ -749,3 +751,172 @@ def test_split_bf16_product_of_the_f32_mode(R, K, M):
     assert float((y.double() - ref).abs().max()) <= 3e-5 * scale, float((y.double() - ref).abs().max()) / scale
     assert float((torch.mm(w.to(torch.bfloat16).float(), x.to(torch.bfloat16).float()).double() - ref).abs().max()) > 1e-3 * scale
     assert torch.equal(y, ops.split_gemm_f32(w, x))
+
+
+# ---- every form of gemm_run on every tile configuration, and every weight-gradient tile, BIT FOR BIT ----------------------
+# Operands on the grid of tests/_gemm_ref.py: every partial sum, in any order, is exact in f32, so the accumulator holds the
+# exact value whatever the tile, ring depth, split-K cut or reduction order, and the output is that value rounded once.  The
+# float64 reference rounded the same way must equal the kernel's output on every element (torch.equal, no allowance); outputs
+# are allocated by the ops on the session's NaN-poisoned allocator, so an element nobody wrote fails too.
+import _gemm_ref as gr  # noqa: E402
+
+_EXACT_DEV = {"shape": None, "moved": {}, "refs": {}}
+
+
+def _exact_operands(case):
+    """The operands of a case on the device.  Consecutive cases of a shape share w / x / g (the makers return the same CPU
+    tensor for the same name) and the references made from them; a new shape drops what the last one held."""
+    st = _EXACT_DEV
+    key = (case in gr.WGRAD_CASES, case.shape)
+    if st["shape"] != key:
+        st.update(shape=key, moved={}, refs={})
+    out = {}
+    for k, v in gr.case_operands(case).items():
+        if torch.is_tensor(v):
+            if id(v) not in st["moved"]:
+                st["moved"][id(v)] = (v, v.to(DEV))
+            out[k] = st["moved"][id(v)][1]
+        else:
+            out[k] = (v[0].to(DEV), v[1], v[2])
+    return out
+
+
+def _exact_product(case, o):
+    """The float64 product of a case on the device, rounded as the kernel's output is, made once per (shape, prologue):
+    the plain, statistics, epilogue and concatenated-operand forms share one (W [x1; x2] = W x)."""
+    R, K, groups, M, views = case.shape
+    key = ("pro", case.arg) if case.form in ("pro", "pro_stats") else ("f32", case.arg) if case.form == "f32" else "plain"
+    refs = _EXACT_DEV["refs"]
+    if key not in refs:
+        refs[key] = gr.product(o["w"], o["x"], groups, views, o.get("pro"), None, DEV,
+                               torch.float32 if case.form == "f32" else torch.bfloat16)
+    return refs[key]
+
+
+def _check_exact_partials(y, part, info, shape):
+    """The statistics partials of a STATS launch against float64 on y: the layout walk and the bars of
+    test_gemm_partials_against_float64 (a division is involved: the statistics are not exact on this grid either)."""
+    R, K, groups, M, views = shape
+    Mg, cols, P = M // views, info[2] * info[6], info[3]
+    assert part.shape == (R, views, P, 3) and P == -(-Mg // cols)
+    yv = y.float().double().reshape(R, views, Mg)
+    full = Mg // cols
+    segs = [yv[:, :, :full * cols].reshape(R, views, full, cols)] + ([yv[:, :, full * cols:, None].transpose(2, 3)] if P > full else [])
+    mean = torch.cat([s.mean(dim=3) for s in segs], dim=2)
+    m2 = torch.cat([((s - s.mean(dim=3, keepdim=True)) ** 2).sum(dim=3) for s in segs], dim=2)
+    got = part.double()
+    assert bool((part[..., 0] == 0).all())
+    np.testing.assert_allclose(got[..., 2].cpu().numpy(), mean.cpu().numpy(), rtol=1e-5, atol=1e-5)
+    np.testing.assert_allclose(got[..., 1].cpu().numpy(), m2.cpu().numpy(), rtol=4e-5)
+
+
+def _where_differs(got, want):
+    """For the message of a failed comparison: how many elements differ, in which rows and columns, and the first one."""
+    bad = (got != want) | torch.isnan(got.float())
+    rows, cols = bad.any(dim=1).nonzero().flatten(), bad.any(dim=0).nonzero().flatten()
+    r, c = int(rows[0]), int(bad[int(rows[0])].nonzero()[0])
+    return (f"{int(bad.sum())} of {bad.numel()} differ: rows {int(rows[0])}..{int(rows[-1])} ({rows.numel()}), columns "
+            f"{int(cols[0])}..{int(cols[-1])} ({cols.numel()}); first [{r}, {c}]: got {float(got[r, c])}, want {float(want[r, c])}")
+
+
+def _exact_launch(case, o):
+    """-> (output, statistics partials or None) of the case's entry point."""
+    from grafp_amd import ops
+    R, K, groups, M, views = case.shape
+    if case.form == "f32":
+        return ops.split_gemm_f32(o["w"], o["x"]), None
+    if case.form == "cat":
+        return ops.conv1x1_gemm_cat(o["w"], o["x"][:case.arg], o["x"][case.arg:]), None
+    if case.form == "epi":
+        tab, act, slope = o["epi"]
+        return ops.conv1x1_gemm_affine(o["w"], o["x"], tab, groups, views, act=act, slope=slope), None
+    tab, act, slope = o.get("pro", (None, 0, 0.0))
+    got = ops.conv1x1_gemm(o["w"], o["x"], groups, views, pro_tab=tab, pro_act=act, pro_slope=slope,
+                           stats=case.form in ("stats", "pro_stats"))
+    return got if isinstance(got, tuple) else (got, None)
+
+
+@pytest.mark.parametrize("name", [c.name for c in gr.GEMM_CASES])
+def test_gemm_equals_float64_bit_for_bit_on_exact_operands(name):
+    """One cell of the form x tile matrix (tests/_gemm_ref.py: CASES): the plan rule sends the shape to the expected tile
+    configuration (an XL plan runs the forms the four-wave tile lacks on the L tile), the operands pass check_grid, and
+    the output of two launches equals the float64 reference on every element -- the product rounded once to bf16; with an
+    affine epilogue the rounded product, transformed, rounded once more; for the f32 output the product itself, with
+    ops.split_planes returning the exact hi + lo of both operands.  A statistics form leaves the bits of y alone; its
+    partials are held against float64 on y with the bars of test_gemm_partials_against_float64."""
+    from grafp_amd import ops
+    case = gr.CASE_BY_NAME[name]
+    R, K, groups, M, views = case.shape
+    info = _plan_info(R, 3 * K if case.form == "f32" else K, groups, M, views)
+    assert info[0] == case.plan, (name, info)
+    o = _exact_operands(case)
+    gr.check_grid(case, o)
+    want = _exact_product(case, o)
+    if case.form == "epi":
+        want = gr.affine(want, o["epi"], views)
+    if case.form == "f32":
+        for t in (o["w"], o["x"]):
+            hi, lo = ops.split_planes(t)
+            assert torch.equal(hi.float() + lo.float(), t)
+    first, part1 = _exact_launch(case, o)
+    assert first.dtype == want.dtype and first.shape == want.shape
+    assert torch.equal(first, want), (name, _where_differs(first, want))
+    if part1 is not None:
+        _check_exact_partials(first, part1, info, case.shape)
+    again, part2 = _exact_launch(case, o)
+    assert torch.equal(again, first) and (part1 is None or torch.equal(part1, part2))
+
+
+def test_normalise_on_load_on_the_128_row_tile_refuses_more_than_1024_operand_rows():
+    """The one cell of the matrix that the library refuses by shape (tests/_gemm_ref.py: REFUSED): a prologue table of an
+    N128-planned product with more than 1024 operand rows per group does not fit beside the ring."""
+    from grafp_amd import ops
+    R, K, M = 128, 1056, 131072
+    assert _plan_cfg(R, K, 1, M, 1) == gr.CFG_N128 and K > gr.N128_PRO_MAX_KG
+    w = torch.ones((R, K), dtype=torch.bfloat16, device=DEV)
+    x = torch.ones((K, M), dtype=torch.bfloat16, device=DEV)
+    tab = gr.affine_table("ge:refused.pro", K, 1).to(DEV)
+    with pytest.raises(RuntimeError, match="at most 1024 operand rows"):
+        ops.conv1x1_gemm(w, x, 1, 1, pro_tab=tab, pro_act=ops.ACT_RELU)
+
+
+@pytest.mark.parametrize("name", [c.name for c in gr.WGRAD_CASES])
+def test_wgrad_equals_float64_bit_for_bit_on_exact_operands(name):
+    """The weight gradient on exact operands (f32 output: the float64 product itself): every LDS-DMA tile forced, plain
+    and with the normalise-on-load operand (T128 / S128 on shapes whose views are no whole 128-column chunks run T / S),
+    the register-staged kernel on both tile widths, and the f32 route (split-bf16 planes, through
+    ops.conv1x1_rows(...).backward) with the low plane on either operand.  Two launches, identical bits."""
+    import ctypes
+    from grafp_amd import ops
+    from grafp_amd._lib import lib
+    case = gr.CASE_BY_NAME[name]
+    cout, cin, groups, M, views = case.shape
+    o = _exact_operands(case)
+    gr.check_grid(case, o)
+    info = (ctypes.c_int * 8)()
+    assert lib.grafp_conv1x1_wgrad_plan(cout, cin, groups, M, views, info) == 0
+    if case.entry == "conv1x1_wgrad":
+        # a forced tile is honoured on an LDS-DMA shape only; plan code -1 is the register-staged kernel
+        assert (info[0] == -1) == (case.plan == -1), (name, list(info))
+        if case.plan == -1:
+            assert info[1] == dict(gr.WG_REG_SHAPES)[case.shape]
+        tab, act, slope = o.get("pro", (None, ops.ACT_NONE, 0.0))
+
+        def run():
+            return ops.conv1x1_wgrad(o["g"], o["x"], cout, cin, groups, M, views, tab, act, slope, tile=case.plan)
+    else:
+        assert not ops.switches.wgrad_f32_library
+
+        def run():
+            w = torch.zeros((cout, cin // groups), device=DEV, requires_grad=True)
+            ops.conv1x1_rows(o["x"], w, groups).backward(o["g"])
+            return w.grad
+    refs = _EXACT_DEV["refs"]
+    key = (case.form, case.arg)                 # plain: the tiles of a shape share one reference
+    if key not in refs:
+        refs[key] = gr.wgrad(o["g"], o["x"], groups, views, o.get("pro"), DEV)
+    want = refs[key]
+    first = run()
+    assert first.dtype == torch.float32 and first.shape == want.shape
+    assert torch.equal(first, want), (name, _where_differs(first, want))
+    assert torch.equal(run(), first)
