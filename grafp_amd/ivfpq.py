@@ -23,6 +23,9 @@ import torch
 from ._lib import check, lib
 
 _vp = ctypes.c_void_p
+# the limits of grafp_ivfpq_search_f32 (csrc/ivfpq.hip): its table templates and the (M x 256) f32 table in LDS
+SEARCH_DSUB = (1, 2, 4, 8)
+SEARCH_MAX_LDS = 150 * 1024
 
 
 def _stream():
@@ -40,6 +43,8 @@ def pq_assign(x, G, cent, base=None, base_idx=None, as_codes=False):
     n, D = x.shape
     k = cent.shape[-2]
     out = torch.empty((n, G), dtype=torch.uint8 if as_codes else torch.int32, device=x.device)
+    if n == 0:                                            # (tensors without elements have no address to hand over)
+        return out
     check(lib.grafp_pq_assign_f32(_ptr(x), n, D, G, _ptr(base), _ptr(base_idx), _ptr(cent), k,
                                   None if as_codes else _ptr(out), _ptr(out) if as_codes else None, _stream()),
           "pq_assign")
@@ -93,6 +98,13 @@ class IVFPQIndex:
             raise NotImplementedError("IVFPQIndex: 8-bit codes (the reference's setting)")
         if d % M:
             raise ValueError("IVFPQIndex: d must be a multiple of M")
+        # what grafp_ivfpq_search_f32 serves: refused here, not after training and adding, at the first search
+        if d // M not in SEARCH_DSUB:
+            raise ValueError(f"IVFPQIndex: d / M = {d // M} not in {{1, 2, 4, 8}} (d={d}, M={M}): the sub-space widths "
+                             "the search kernel has")
+        if M * 256 * 4 > SEARCH_MAX_LDS:
+            raise ValueError(f"IVFPQIndex: M = {M} sub-quantisers need {M * 256 * 4} bytes of LDS for the search "
+                             f"kernel's table (at most {SEARCH_MAX_LDS}: M <= {SEARCH_MAX_LDS // 1024})")
         if not torch.cuda.is_available():
             raise RuntimeError("IVFPQIndex needs a HIP device: there is no CPU fallback")
         self.d, self.nlist, self.M, self.dsub = int(d), int(nlist), int(M), d // M
